@@ -12,12 +12,18 @@ Frames are sharded contiguous per rank with no data-path collective; with N>1 th
 per step (inside the timed region).  Scaling is weak: --frames-per-gpu (default 1024) is fixed as N grows; BASELINE
 configs[3] (65536 frames over 8 GPUs) is `--gpus 8 --frames-per-gpu 8192`.
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with `roofline` (dominant kernel, HIP-event timed on the
-stream it runs on) and `cpu_baseline` (the reference's own code from oracle/_ref when present, else the C oracle port).
-The batch is 1024 DISTINCT animation-bank frames (bench_data/frames1024.npz, row (3 + 9 i) mod 2336: SURVEY 8d config 2;
-larger batches repeat them, every rank starts at another offset); after the timed loop EVERY distinct frame of rank 0's
-batch is compared with what the reference itself produced for it (tests/golden/poses1024.htfx, `verified`), so a number
-from a build that computes something else is reported as such.  Tuning switches of the library (HT_DEBUG_SKIP, HT_NO_SIDE, HT_NO_OVERLAP) make the run refuse.
+Prints ONE JSON line on rank 0: `metric`, `value`, `unit`, `higher_is_better`, `dtype` and
+`ms_per_step` (wall time of one timed step).  A plain run does only that: set up, warm up, time --steps steps, print.
+--dump-outputs DIR also writes what the last timed step computed (poses, or the CNN output of the CNN-only workloads) as
+DIR/<name>.npy; inputs and weights are fixed, so two builds can be compared output for output.
+
+--full adds everything else, after the timed steps: `roofline` (dominant kernel, HIP-event timed on the stream it runs on),
+the phase table, the host-I/O and two-batches-in-flight legs, and `cpu_baseline` (the reference's own code from oracle/_ref
+when present, else the C oracle port).  The batch is 1024 DISTINCT animation-bank frames (bench_data/frames1024.npz, row
+(3 + 9 i) mod 2336: SURVEY 8d config 2; larger batches repeat them, every rank starts at another offset); with --full EVERY
+distinct frame of rank 0's batch is compared with what the reference itself produced for it (tests/golden/poses1024.htfx,
+`verified`), so a number from a build that computes something else is reported as such (exit status 3).  Tuning switches of
+the library (HT_DEBUG_SKIP, HT_NO_SIDE, HT_NO_OVERLAP) make the run refuse.
 """
 import argparse
 import glob
@@ -55,7 +61,14 @@ def parse_args(argv=None):
     ap.add_argument("--no-host-io", action="store_true", help="skip the extra leg that times the same steps with pinned host buffers in and out")
     ap.add_argument("--always-take-cnn", action="store_true", help="cnn+solver workload with the application's always_take_cnn switch (synthetic-tracker.cpp:91): every frame accepts the CNN-driven pose; verified against tests/golden/poses1024_takecnn.htfx")
     ap.add_argument("--force-dist", action="store_true", help="initialise RCCL and run the pose gather even with one rank")
-    return ap.parse_args(argv)
+    ap.add_argument("--full", action="store_true", help="everything beyond the headline figure: the check of the timed batch against the reference's results (`verified`), "
+                    "roofline and phase table, the host-I/O and two-batches-in-flight legs, the CPU baseline.  Off: set up, warm up, time --steps steps, print the result line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps write what the last one computed (the arrays its caller receives) as DIR/<name>.npy, float32, "
+                    "at most 64 MB in all (a fixed, seeded sample of rows beyond that); bench_outputs/ in the tree is ignored by git")
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def self_launch(args):
@@ -367,6 +380,24 @@ def _pmc_issue(kernel_prefix, workload, frames_per_gpu):
     return {}
 
 
+DUMP_LIMIT_BYTES = 64 * 10 ** 6      # 64 MB of .npy files in all, their headers included
+
+
+def dump_outputs(d, arrays):
+    """--dump-outputs: every array as d/<name>.npy in float32.  When they would exceed 64 MB together, every array is cut to the same fraction of its
+    rows, drawn from its own length by a fixed seed (so the same rows from run to run, kept in frame order; arrays of different lengths keep different rows)."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float32) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    budget = DUMP_LIMIT_BYTES - 4096 * len(arrays)      # room for the .npy headers (about 128 B each)
+    for name, a in arrays.items():
+        if total > budget:
+            keep = max(1, int(len(a) * budget // total))
+            a = a[np.sort(np.random.default_rng(0x5EED).choice(len(a), keep, replace=False))]
+        np.save(os.path.join(d, name + ".npy"), a)
+
+
 def main():
     args = parse_args()
     bad = [k for k in TUNING_ENV if os.environ.get(k)]
@@ -496,8 +527,9 @@ def main():
     for _ in range(args.warmup):
         step()
     torch.cuda.synchronize()
-    ctx.profile_enable(1)          # HIP events around the dominant kernel only (on its launch stream), inside the timed region
-    ctx.profile_read(reset=True)
+    if args.full:
+        ctx.profile_enable(1)          # HIP events around the dominant kernel only (on its launch stream), inside the timed region
+        ctx.profile_read(reset=True)
     if use_dist:
         dist.barrier()
     torch.cuda.synchronize()
@@ -513,11 +545,21 @@ def main():
         tmax = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         elapsed = float(tmax.item())
-    prof = ctx.profile_read(reset=True)
+    prof = ctx.profile_read(reset=True) if args.full else None
 
-    # ---- the timed steps' own output against the reference's committed results: every distinct frame of rank 0's batch ----
+    # ---- what the last timed step handed its caller, before anything below runs the step again ----
+    if rank == 0 and args.dump_outputs:
+        if cnn_only:
+            outputs = {"cnn_out": d_cnn_out}
+        else:
+            outputs = {"poses": d_poses}
+            if use_dist:
+                outputs["gathered_poses"] = gathered
+        dump_outputs(args.dump_outputs, {k: v.cpu().numpy() for k, v in outputs.items()})
+
+    # ---- --full: the timed steps' own output against the reference's committed results: every distinct frame of rank 0's batch ----
     verify = None
-    if rank == 0 and args.steps > 0:
+    if rank == 0 and args.full:
         if wl == "cnn" and gold is not None:
             got = d_cnn_out[:8].cpu().numpy()
             dc = float(max(np.abs(got[f] - gold["f%d/cnn_output" % f]).max() for f in range(8)))
@@ -541,7 +583,7 @@ def main():
     # ---- the same steps with the HOST in them (SURVEY 8e names host-side staging as a scaling bound; the application hands update() a host image, synthetic-tracker.cpp:215):
     #      depth and cameras start in pinned host memory, the poses end there; the upload of step k + 1 and the download of step k - 1 run on a copy stream beside step k ----
     host_io = None
-    if rank == 0 and wl == "cnn+solver" and args.steps > 0 and not args.no_host_io:
+    if rank == 0 and args.full and wl == "cnn+solver" and not args.no_host_io:
         h_depth = torch.from_numpy(depth.view(np.int16)).pin_memory(); h_cams = torch.from_numpy(cams).pin_memory()
         h_depth2 = [h_depth, torch.from_numpy(depth.view(np.int16).copy()).pin_memory()]      # the zero-copy variant reads the frames where they lie: two pinned buffers, as a capture loop would fill them in turn
         h_poses = [torch.empty((B, ctx.nb, 7), dtype=torch.float32).pin_memory() for _ in range(2)]
@@ -611,7 +653,7 @@ def main():
     #      leave (at 1024 frames every kernel of the step is latency-bound and the dominant ones take whole CUs: DESIGN.md section 15).  What a deployment with a queue of
     #      INDEPENDENT batches gets out of the GPU; never `value`: the headline stays one 1024-frame batch at a time ----
     two = None
-    if rank == 0 and wl == "cnn+solver" and args.steps > 0 and not args.no_two_in_flight and not use_dist:
+    if rank == 0 and args.full and wl == "cnn+solver" and not args.no_two_in_flight and not use_dist:
         ctx2 = native.Context(os.path.join(ROOT, "hand_tracking_samples_amd", "assets", "model_hand17.htfx"), B, device=local)
         ctx2.load_weights(W.make_cnnb(seed, gain))
         ctx2.set_params(microforce=3.0, mainthreadpasses=3, **({"always_take_cnn": 1} if args.always_take_cnn else {}))
@@ -635,70 +677,19 @@ def main():
         ctx2.close()
 
     # phase table from a second, untimed pass with every phase bracketed (this serialises the side streams)
-    ctx.profile_enable(2)
-    nphase = max(2, min(5, args.steps))
-    for _ in range(nphase):
-        step()
-    torch.cuda.synchronize()
-    prof_all = ctx.profile_read(reset=True)
-    ctx.profile_enable(0)
+    prof_all = nphase = None
+    if args.full:
+        ctx.profile_enable(2)
+        nphase = max(2, min(5, args.steps))
+        for _ in range(nphase):
+            step()
+        torch.cuda.synchronize()
+        prof_all = ctx.profile_read(reset=True)
+        ctx.profile_enable(0)
 
     if rank == 0:
         total_frames = B * world * args.steps
         value = total_frames / elapsed
-        flop_cnn = CNN_FLOP["cnn128" if (cnn128 or e2e) else "cnn"]
-        # dominant kernel of the workload by HIP-event time
-        phases = {k: v for k, v in prof.items() if v[1] > 0}
-        if cnn_only:
-            phases = {k: (v[0] * args.steps / nphase, v[1] * args.steps // nphase) for k, v in prof_all.items() if v[1] > 0}
-        all_phases = {k: v for k, v in prof_all.items() if v[1] > 0}
-        dom = max(all_phases, key=lambda k: all_phases[k][0] / nphase) if all_phases else None
-        if dom not in phases:
-            phases[dom] = (all_phases[dom][0] * args.steps / nphase, all_phases[dom][1] * args.steps // nphase)
-        roof = None
-        if dom == "solve":
-            # One k_solve launch per frame.  HBM side: the body state in and out (2 x nb x 52 B) plus the constraint rows it
-            # consumes (64 B each).  VALU side: 20 sweeps x (120 flop per linear row + 60 per angular row).  Row counts per frame from the data.
-            scale = cams[:, 4].astype(np.float32)[:, None]
-            z = depth.reshape(B, -1).astype(np.float32) * scale
-            npts = (((z >= 0.1) & (z < 0.7)).sum(axis=1) + 3) // 4
-            main_rows = float(np.mean(npts + np.where(npts > 400, 5 * ctx.nb, 0))); sim_rows = float(np.mean((npts + 3) // 4))
-            rows_mean = (3 * main_rows + 4 * sim_rows) / 8.0              # 3 main passes, 4 cloud-bearing MultiStepSim steps (+ 1 without cloud rows)
-            joint_rows, ang_rows, contact_rows = 3.0 * ctx.nj, 71.0 * ctx.nj / 16.0, 3 * 5.1      # 71 angular rows, 5.1 contacts per frame (17-bone hand)
-            per_frame = 2 * ctx.nb * 52 + 64.0 * rows_mean
-            flop_frame = 20.0 * ((rows_mean + joint_rows + contact_rows) * 120.0 + ang_rows * 60.0)
-            avg_ms = phases[dom][0] / phases[dom][1]
-            achieved = per_frame * B / (avg_ms * 1e-3) / 1e9
-            valu = flop_frame * B / (avg_ms * 1e-3) / 1e12
-            # HBM bytes per launch from the committed rocprofv3 PMC passes of THIS workload and batch size (profiles/rNN_pmc_hbm_traffic*.json carry
-            # what they were measured on); null when no such measurement exists
-            traffic = _pmc_traffic("k_solve", wl, B)
-            roof = {"kernel": "k_solve", "bound": "latency", "achieved": round(achieved, 3), "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 6),
-                    "hbm_frac": round(achieved / HBM_PEAK_GBS, 6), "valu_achieved_tflops": round(valu, 3), "valu_peak_tflops": FP32_VALU_PEAK_TF, "valu_frac": round(valu / FP32_VALU_PEAK_TF, 6),
-                    "traffic": traffic, "avg_launch_ms": round(avg_ms, 4), "launches": phases[dom][1], "algorithmic_bytes_per_launch": int(per_frame * B), "algorithmic_flop_per_launch": int(flop_frame * B),
-                    "note": "sequential Gauss-Seidel (physics.h:556-562): bound by the dependent-instruction latency of the longest per-body row chain, neither by HBM nor by VALU throughput; both fractions are reported (SURVEY 8d); "
-                            "issue_frac = VALU instructions issued x 4 clocks / the resident waves' clocks (one wave per SIMD at 1024 frames), from the committed counter pass"}
-            roof.update(_pmc_issue("k_solve", wl, B))
-        elif dom == "contacts":
-            # k_contacts reads the poses of the frame's bodies and writes its contacts (48 B each, data dependent, not counted): like the
-            # solve it is a latency-bound kernel (one wave walks the candidate pairs' GJK/EPA iterations), priced against HBM for the record
-            per_frame = ctx.nb * 28 + 4
-            avg_ms = phases[dom][0] / phases[dom][1]
-            achieved = per_frame * B / (avg_ms * 1e-3) / 1e9
-            roof = {"kernel": "k_contacts", "bound": "latency", "achieved": round(achieved, 3), "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 6), "traffic": None,
-                    "avg_launch_ms": round(avg_ms, 4), "launches": phases[dom][1], "algorithmic_bytes_per_launch": int(per_frame * B),
-                    "note": "broad phase + GJK/EPA over %d body pairs per frame: latency/LDS-bound, not a streaming kernel" % (ctx.nb * (ctx.nb - 1) // 2)}
-        elif dom in ("cnn", "cnn128"):
-            avg_ms = phases[dom][0] / phases[dom][1]
-            achieved = flop_cnn * B / (avg_ms * 1e-3) / 1e12
-            roof = {"kernel": "cnn (k_conv12 + k_fc + k_fc144_pk + k_softmax_decode)" if dom == "cnn" else "cnn (k_conv1 + k_conv2 + k_fc + k_fc144_pk + k_softmax_decode)", "bound": "mfma", "achieved": round(achieved, 3), "peak": FP32_MFMA_PEAK_TF, "unit": "TFLOP/s",
-                    "frac": round(achieved / FP32_MFMA_PEAK_TF, 5), "traffic": None, "avg_launch_ms": round(avg_ms, 4), "launches": phases[dom][1], "flop_per_frame": flop_cnn}
-        cnn_roof = None
-        cnn_phase = "cnn128" if "cnn128" in all_phases else "cnn"
-        if cnn_phase in all_phases and dom != cnn_phase:
-            avg_ms = all_phases[cnn_phase][0] / all_phases[cnn_phase][1]
-            ach = CNN_FLOP[cnn_phase] * B / (avg_ms * 1e-3) / 1e12
-            cnn_roof = {"bound": "mfma", "achieved": round(ach, 3), "peak": FP32_MFMA_PEAK_TF, "unit": "TFLOP/s", "frac": round(ach / FP32_MFMA_PEAK_TF, 5), "avg_ms": round(avg_ms, 4)}
         shard_note = ("; layout of BASELINE configs[3] (contiguous shard per GPU, RCCL all-gather of the poses inside the timed step; configs[3] itself = --gpus 8 --frames-per-gpu 8192)"
                       if world > 1 else "")
         workloads = {
@@ -722,31 +713,11 @@ def main():
             "config": {"workload": workloads[wl][1], "frames_per_gpu": B, "global_frames_per_step": B * world,
                        "parallelism": ("frames sharded per GPU, RCCL all-gather of poses" if not cnn_only else "frames sharded per GPU, no exchange") if world > 1 else "single GPU"},
             **({"gather": gather_impl} if gather_impl else {}),
-            "roofline": roof,
-            "phase_ms_per_step": {k: round(v[0] / nphase, 4) for k, v in sorted(all_phases.items())},
-            "phase_note": "from an extra untimed pass with every phase bracketed and the side streams serialised",
         }
         if bad:
             out["tuning_run_not_a_result"] = bad
-        if verify is not None:
-            out["verified"] = verify["verified"]
-            out["verify"] = verify
-        if cnn_roof:
-            out["roofline_cnn"] = cnn_roof
-        if host_io:
-            out["host_io"] = host_io
-        if two:
-            out["two_batches_in_flight"] = two
-        if world == 1 and not args.no_cpu_baseline:
-            if cnn128:
-                out["cpu_baseline"] = cpu_baseline_cnn128(x128, w128)
-            else:
-                out["cpu_baseline"] = (cpu_baseline_e2e128 if e2e else cpu_baseline_config5 if cfg5 else cpu_baseline)(depth, cams, start, seed, gain)
-                if wl == "cnn" and "cnn_only_fps" in out["cpu_baseline"]:
-                    out["cpu_baseline"]["frame_fps_cnn_plus_solver"] = out["cpu_baseline"]["value"]
-                    out["cpu_baseline"]["value"] = out["cpu_baseline"].pop("cnn_only_fps")
-                    out["cpu_baseline"]["sample"] += "; value = CNN::Eval only"
-            out["speedup_vs_cpu_1thread"] = round(value / out["cpu_baseline"]["value"], 1)
+        if args.full:
+            out.update(full_report(args, ctx, wl, B, world, value, prof, prof_all, nphase, cams, depth, start, seed, gain, x128, w128, verify, host_io, two))
         sys.stdout.flush()
         os.write(json_fd, (json.dumps(out) + "\n").encode())
     ctx.close()
@@ -756,6 +727,93 @@ def main():
         sys.stderr.write("bench.py: the timed steps' output does NOT match the reference's committed results: %s\n" % json.dumps(verify))
         sys.exit(3)
 
+
+def full_report(args, ctx, wl, B, world, value, prof, prof_all, nphase, cams, depth, start, seed, gain, x128, w128, verify, host_io, two):
+    """--full: the keys of the result line beyond the headline figure (roofline, phase table, verify, the extra legs, the CPU baseline)"""
+    import numpy as np
+    e2e = wl == "config5-e2e"
+    cfg5 = wl in ("config5", "config5-e2e")
+    cnn_only = wl in ("cnn", "config5-cnn128")
+    cnn128 = wl == "config5-cnn128"
+    flop_cnn = CNN_FLOP["cnn128" if (cnn128 or e2e) else "cnn"]
+    # dominant kernel of the workload by HIP-event time
+    phases = {k: v for k, v in prof.items() if v[1] > 0}
+    if cnn_only:
+        phases = {k: (v[0] * args.steps / nphase, v[1] * args.steps // nphase) for k, v in prof_all.items() if v[1] > 0}
+    all_phases = {k: v for k, v in prof_all.items() if v[1] > 0}
+    dom = max(all_phases, key=lambda k: all_phases[k][0] / nphase) if all_phases else None
+    if dom not in phases:
+        phases[dom] = (all_phases[dom][0] * args.steps / nphase, all_phases[dom][1] * args.steps // nphase)
+    roof = None
+    if dom == "solve":
+        # One k_solve launch per frame (DESIGN.md section 4).  HBM side: the body state in and out (2 x nb x 52 B) plus the constraint rows it
+        # consumes (64 B each).  VALU side (SURVEY 8d): 20 sweeps x (120 flop per linear row + 60 per angular row).  Row counts per frame from the data.
+        scale = cams[:, 4].astype(np.float32)[:, None]
+        z = depth.reshape(B, -1).astype(np.float32) * scale
+        npts = (((z >= 0.1) & (z < 0.7)).sum(axis=1) + 3) // 4
+        main_rows = float(np.mean(npts + np.where(npts > 400, 5 * ctx.nb, 0))); sim_rows = float(np.mean((npts + 3) // 4))
+        rows_mean = (3 * main_rows + 4 * sim_rows) / 8.0              # 3 main passes, 4 cloud-bearing MultiStepSim steps (+ 1 without cloud rows)
+        joint_rows, ang_rows, contact_rows = 3.0 * ctx.nj, 71.0 * ctx.nj / 16.0, 3 * 5.1      # SURVEY section 6: 71 angular rows, 5.1 contacts per frame (17-bone hand)
+        per_frame = 2 * ctx.nb * 52 + 64.0 * rows_mean
+        flop_frame = 20.0 * ((rows_mean + joint_rows + contact_rows) * 120.0 + ang_rows * 60.0)
+        avg_ms = phases[dom][0] / phases[dom][1]
+        achieved = per_frame * B / (avg_ms * 1e-3) / 1e9
+        valu = flop_frame * B / (avg_ms * 1e-3) / 1e12
+        # HBM bytes per launch from the committed rocprofv3 PMC passes of THIS workload and batch size (profiles/rNN_pmc_hbm_traffic*.json carry
+        # what they were measured on); null when no such measurement exists
+        traffic = _pmc_traffic("k_solve", wl, B)
+        roof = {"kernel": "k_solve", "bound": "latency", "achieved": round(achieved, 3), "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 6),
+                "hbm_frac": round(achieved / HBM_PEAK_GBS, 6), "valu_achieved_tflops": round(valu, 3), "valu_peak_tflops": FP32_VALU_PEAK_TF, "valu_frac": round(valu / FP32_VALU_PEAK_TF, 6),
+                "traffic": traffic, "avg_launch_ms": round(avg_ms, 4), "launches": phases[dom][1], "algorithmic_bytes_per_launch": int(per_frame * B), "algorithmic_flop_per_launch": int(flop_frame * B),
+                "note": "sequential Gauss-Seidel (physics.h:556-562): bound by the dependent-instruction latency of the longest per-body row chain, neither by HBM nor by VALU throughput; both fractions are reported (SURVEY 8d); "
+                        "issue_frac = VALU instructions issued x 4 clocks / the resident waves' clocks (one wave per SIMD at 1024 frames), from the committed counter pass"}
+        roof.update(_pmc_issue("k_solve", wl, B))
+    elif dom == "contacts":
+        # k_contacts reads the poses of the frame's bodies and writes its contacts (48 B each, data dependent, not counted): like the
+        # solve it is a latency-bound kernel (one wave walks the candidate pairs' GJK/EPA iterations), priced against HBM for the record
+        per_frame = ctx.nb * 28 + 4
+        avg_ms = phases[dom][0] / phases[dom][1]
+        achieved = per_frame * B / (avg_ms * 1e-3) / 1e9
+        roof = {"kernel": "k_contacts", "bound": "latency", "achieved": round(achieved, 3), "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 6), "traffic": None,
+                "avg_launch_ms": round(avg_ms, 4), "launches": phases[dom][1], "algorithmic_bytes_per_launch": int(per_frame * B),
+                "note": "broad phase + GJK/EPA over %d body pairs per frame: latency/LDS-bound, not a streaming kernel" % (ctx.nb * (ctx.nb - 1) // 2)}
+    elif dom in ("cnn", "cnn128"):
+        avg_ms = phases[dom][0] / phases[dom][1]
+        achieved = flop_cnn * B / (avg_ms * 1e-3) / 1e12
+        roof = {"kernel": "cnn (k_conv12 + k_fc + k_fc144_pk + k_softmax_decode)" if dom == "cnn" else "cnn (k_conv1 + k_conv2 + k_fc + k_fc144_pk + k_softmax_decode)", "bound": "mfma", "achieved": round(achieved, 3), "peak": FP32_MFMA_PEAK_TF, "unit": "TFLOP/s",
+                "frac": round(achieved / FP32_MFMA_PEAK_TF, 5), "traffic": None, "avg_launch_ms": round(avg_ms, 4), "launches": phases[dom][1], "flop_per_frame": flop_cnn}
+    cnn_roof = None
+    cnn_phase = "cnn128" if "cnn128" in all_phases else "cnn"
+    if cnn_phase in all_phases and dom != cnn_phase:
+        avg_ms = all_phases[cnn_phase][0] / all_phases[cnn_phase][1]
+        ach = CNN_FLOP[cnn_phase] * B / (avg_ms * 1e-3) / 1e12
+        cnn_roof = {"bound": "mfma", "achieved": round(ach, 3), "peak": FP32_MFMA_PEAK_TF, "unit": "TFLOP/s", "frac": round(ach / FP32_MFMA_PEAK_TF, 5), "avg_ms": round(avg_ms, 4)}
+    out = {
+        "roofline": roof,
+        "phase_ms_per_step": {k: round(v[0] / nphase, 4) for k, v in sorted(all_phases.items())},
+        "phase_note": "from an extra untimed pass with every phase bracketed and the side streams serialised",
+    }
+    if verify is not None:
+        out["verified"] = verify["verified"]
+        out["verify"] = verify
+    if cnn_roof:
+        out["roofline_cnn"] = cnn_roof
+    if host_io:
+        out["host_io"] = host_io
+    if two:
+        out["two_batches_in_flight"] = two
+    if world == 1 and not args.no_cpu_baseline:
+        if cnn128:
+            out["cpu_baseline"] = cpu_baseline_cnn128(x128, w128)
+        else:
+            out["cpu_baseline"] = (cpu_baseline_e2e128 if e2e else cpu_baseline_config5 if cfg5 else cpu_baseline)(depth, cams, start, seed, gain)
+            if wl == "cnn" and "cnn_only_fps" in out["cpu_baseline"]:
+                out["cpu_baseline"]["frame_fps_cnn_plus_solver"] = out["cpu_baseline"]["value"]
+                out["cpu_baseline"]["value"] = out["cpu_baseline"].pop("cnn_only_fps")
+                out["cpu_baseline"]["sample"] += "; value = CNN::Eval only"
+        # config5-e2e has no port of its own: without the reference harness under oracle/_ref/ there is no baseline to report
+        out["speedup_vs_cpu_1thread"] = round(value / out["cpu_baseline"]["value"], 1) if out["cpu_baseline"] else None
+    return out
 
 if __name__ == "__main__":
     main()

@@ -2,7 +2,7 @@
 # contacts beside the cloud rows as the lane-per-pair kernel, and the cloud rows' blocks per frame.
 export HT_LIB_PATH=$PWD/hand_tracking_samples_amd/libht_tuning.so HT_BENCH_TUNING_RUN=1
 run() {
-  env "$@" python bench.py --steps 10 --warmup 3 --no-cpu-baseline ${FRAMES:+--frames-per-gpu $FRAMES} 2>/dev/null | python -c "
+  env "$@" python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline ${FRAMES:+--frames-per-gpu $FRAMES} 2>/dev/null | python -c "
 import sys,json
 j=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('$*','ms/step',j['ms_per_step'],'verified',j.get('verified'))"
 }

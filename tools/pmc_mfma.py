@@ -15,7 +15,7 @@ with open(sys.argv[1]) as fp:
         acc[name][r["Counter_Name"]] += float(r["Counter_Value"])
         if r["Counter_Name"] == "GRBM_GUI_ACTIVE":
             cnt[name] += 1
-out = {"_note": "rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CU_CYCLES GRBM_GUI_ACTIVE on `bench.py --workload cnn` (B=1024); means per dispatch; "
+out = {"_note": "rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CU_CYCLES GRBM_GUI_ACTIVE on `bench.py --full --workload cnn` (B=1024); means per dispatch; "
                 "mfma_util = MFMA busy cycles / (GRBM_GUI_ACTIVE/8 x 1024 SIMDs)"}
 for k, v in acc.items():
     n = max(1, cnt[k])

@@ -1,4 +1,4 @@
-"""Aggregates rocprofv3 counter passes on `bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-host-io` into per-kernel issue / wait / L2 figures (profiles/rNN_pmc_solve_issue.json).
+"""Aggregates rocprofv3 counter passes on `bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-host-io` into per-kernel issue / wait / L2 figures (profiles/rNN_pmc_solve_issue.json).
 
     python tools/pmc_solve.py <dir with the passes' *_counter_collection.csv and one *_kernel_trace.csv> [kernel name prefixes ...]
 
@@ -29,7 +29,7 @@ for path in glob.glob(os.path.join(d, "**", "*kernel_trace.csv"), recursive=True
         for r in csv.DictReader(fp):
             name = r["Kernel_Name"].split("(")[0].replace("void ", "")
             dur[name][0] += float(r["End_Timestamp"]) - float(r["Start_Timestamp"]); dur[name][1] += 1
-out = {"_note": __doc__.split("\n\n")[2].strip(), "_measured_on": {"workload": "cnn+solver", "frames_per_gpu": int(os.environ.get("FRAMES", "1024")), "command": "rocprofv3 --kernel-trace --pmc <one pass per counter group> -- python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-host-io"}}
+out = {"_note": __doc__.split("\n\n")[2].strip(), "_measured_on": {"workload": "cnn+solver", "frames_per_gpu": int(os.environ.get("FRAMES", "1024")), "command": "rocprofv3 --kernel-trace --pmc <one pass per counter group> -- python3 bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-host-io"}}
 for name in sorted(acc):
     if not any(name.startswith(w) for w in want):
         continue
