@@ -75,6 +75,8 @@ struct ht_ctx
 	float *d_user_lin = nullptr; unsigned short *d_user_pos = nullptr; float *d_user_ang = nullptr; int *d_user_n = nullptr;      // [B][lin_cap][HT_ROW], [B][lin_cap], [B][ang_cap][HT_AROW], [4][B]
 	int user_lin_cap = 0, user_ang_cap = 0;
 	ht_comm_state *comm = nullptr;                               // multi-GPU pose gather (ht_comm_init), null on a single-GPU host
+	void *d_render = nullptr; size_t render_cap = 0;             // ht_render_depth's staging (poses, cameras, frames, body labels), grown to the largest call; in `allocs`
+	std::vector<float4> render_planes; std::vector<float> render_radii;      // the hull planes ht_render_depth last derived its per-body cull radii from, and those radii (2 per body)
 };
 
 struct ht_prof_scope

@@ -20,7 +20,7 @@ SYMBOLS = (
     "ht_create", "ht_destroy", "ht_model_bake", "ht_last_error", "ht_get_params", "ht_set_params", "ht_model_info", "ht_config_read", "ht_scale",
     "ht_cnn_load_weights", "ht_cnn_eval", "ht_cnn_eval_dev", "ht_cnn_load_weights_sized", "ht_cnn_eval_sized", "ht_cnn_eval_sized_dev", "ht_cnn_train", "ht_cnn_get_weights", "ht_expected_cnn", "ht_expected_cnn_full",
     "ht_model_open", "ht_model_close", "ht_model_error", "ht_model_counts", "ht_model_body", "ht_model_body_mesh", "ht_model_body_sdmesh", "ht_model_hitcheck",
-    "ht_tracker_reset", "ht_get_state", "ht_set_state", "ht_get_tracker_flags", "ht_set_tracker_flags", "ht_update_sync", "ht_update_dev", "ht_update_frames_sync", "ht_update_frames_dev", "ht_update_direct_sync", "ht_update_direct_dev", "ht_update_cnn_model_sync", "ht_get_cnn_results", "ht_get_cnn_layers", "ht_frames_overflow", "ht_reserve_points", "ht_point_capacity", "ht_capacity_events", "ht_segment_vr", "ht_segment_vr_dev", "ht_slowfit", "ht_set_points", "ht_fit_rows", "ht_physics_update",
+    "ht_tracker_reset", "ht_get_state", "ht_set_state", "ht_get_tracker_flags", "ht_set_tracker_flags", "ht_update_sync", "ht_update_dev", "ht_update_frames_sync", "ht_update_frames_dev", "ht_update_direct_sync", "ht_update_direct_dev", "ht_update_cnn_model_sync", "ht_get_cnn_results", "ht_get_cnn_layers", "ht_frames_overflow", "ht_reserve_points", "ht_point_capacity", "ht_capacity_events", "ht_segment_vr", "ht_segment_vr_dev", "ht_render_depth", "ht_render_depth_dev", "ht_slowfit", "ht_set_points", "ht_fit_rows", "ht_physics_update",
     "ht_stage_prepare", "ht_stage_decode", "ht_stage_fit_error", "ht_stage_cloud_rows", "ht_stage_contacts", "ht_stage_fit",
     "ht_stage_multistep", "ht_stage_multistep_range", "ht_stage_scratch_unibody", "ht_stage_chamber", "ht_profile_enable", "ht_profile_read", "ht_debug_solve_stats", "ht_debug_contact_stats", "ht_debug_solver_build", "ht_debug_reset_flags", "ht_debug_reset_organisation", "ht_update_passes_sync", "ht_job_start", "ht_job_poll", "ht_job_wait", "ht_job_collect", "ht_debug_contact_kernel", "ht_contact_capacity", "ht_debug_solve_tables", "ht_debug_solve_tables_header",
     "ht_comm_available", "ht_comm_unique_id", "ht_comm_init", "ht_comm_info", "ht_gather_poses_dev", "ht_gather_wait", "ht_gather_wait_host", "ht_comm_destroy",
@@ -109,6 +109,8 @@ def load(build_if_missing=True):
     L.ht_physics_update.argtypes = [vp, C.c_int, C.c_int, fp, C.c_int, ip, fp, C.c_int, ip]
     L.ht_segment_vr.argtypes = [vp, C.POINTER(C.c_uint16), fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, C.POINTER(C.c_uint16), fp]
     L.ht_segment_vr_dev.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, vp, vp, vp]
+    L.ht_render_depth.argtypes = [vp, fp, fp, C.c_int, C.c_int, C.c_float, C.c_int, u16p, C.POINTER(C.c_int8)]
+    L.ht_render_depth_dev.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_float, C.c_int, vp, vp, vp]
     L.ht_profile_read.argtypes = [vp, C.c_int, C.c_int, C.c_char_p, C.c_int, fp, ip, ip]
     L.ht_debug_solve_stats.argtypes = [vp, C.c_int, fp, C.c_int]
     L.ht_debug_solver_build.argtypes = [vp, C.c_int]
@@ -507,6 +509,21 @@ class Context:
         self._chk(self.L.ht_segment_vr(self.h, depth.ctypes.data_as(C.POINTER(C.c_uint16)), _f(cams), w, h, B, int(entry_options), float(wrange[0]), float(wrange[1]), float(diam),
                                        tiles.ctypes.data_as(C.POINTER(C.c_uint16)), _f(co)))
         return tiles, co
+
+    def render_depth(self, poses, cams, w, h, far=4.0, want_body=False):
+        """FakeDepth (synthetic-tracker.cpp:69-76) for a batch: the context's hand at centre-of-mass poses [B,nb,7], cameras [B,12] ->
+        depth u16[B,h,w] (and the hit body int8[B,h,w], -1 = background, with want_body)."""
+        poses = _c(poses, np.float32).reshape(-1, self.nb, POSE); B = poses.shape[0]
+        cams = _c(cams, np.float32).reshape(B, CAM)
+        depth = np.empty((B, int(h), int(w)), np.uint16)
+        body = np.empty((B, int(h), int(w)), np.int8) if want_body else None
+        self._chk(self.L.ht_render_depth(self.h, _f(poses), _f(cams), int(w), int(h), float(far), B, depth.ctypes.data_as(C.POINTER(C.c_uint16)),
+                                         body.ctypes.data_as(C.POINTER(C.c_int8)) if want_body else None))
+        return (depth, body) if want_body else depth
+
+    def render_depth_dev(self, d_poses, d_cams, w, h, far, B, d_depth, d_body=None, stream=None):
+        """ht_render_depth_dev: device pointers (poses [B,nb,7], cams [B,12] -> depth u16[B,h,w], body int8[B,h,w] or None), asynchronous on `stream`."""
+        self._chk(self.L.ht_render_depth_dev(self.h, d_poses, d_cams, int(w), int(h), float(far), int(B), d_depth, d_body, stream))
 
     def scale(self, s):
         """HandTracker::scale (handtrack.h:591): both models of every slot grow by the factor s."""

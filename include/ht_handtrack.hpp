@@ -485,6 +485,23 @@ struct HandTracker                                                              
 		Pose pose; pose.position = { co[5], co[6], co[7] }; pose.orientation = { co[8], co[9], co[10], co[11] };
 		return Image<unsigned short>(DCamera({ 64, 64 }, { co[0], co[1] }, { co[2], co[3] }, co[4], pose), std::move(tile));
 	}
+	// Addition, not a reference name: the application's FakeDepth (synthetic-tracker.cpp:69-76, the software_rasterizer branch of :182) on this tracker's
+	// device, for a batch of hands at centre-of-mass poses (PhysModel::SetPose) seen through `cam` (its pose is not used: the rays start at the origin)
+	std::vector<Image<unsigned short>> render_depth(const std::vector<std::vector<Pose>> &poses, const DCamera &cam, float far = 4.0f) const
+	{
+		const int B = (int)poses.size(), w = cam.dim().x, h = cam.dim().y;
+		std::vector<float> p7; p7.reserve((size_t)B * nb_ * HT_POSE);
+		for (auto &fr : poses) { if ((int)fr.size() != nb_) throw std::runtime_error("render_depth: one pose per body"); const std::vector<float> f = flat(fr); p7.insert(p7.end(), f.begin(), f.end()); }
+		const float c[HT_CAM] = { cam.focal().x, cam.focal().y, cam.principal().x, cam.principal().y, cam.depth_scale, cam.pose.position.x, cam.pose.position.y, cam.pose.position.z,
+		                          cam.pose.orientation.x, cam.pose.orientation.y, cam.pose.orientation.z, cam.pose.orientation.w };
+		std::vector<float> cams; for (int b = 0; b < B; b++) cams.insert(cams.end(), c, c + HT_CAM);
+		std::vector<unsigned short> d((size_t)B * w * h);
+		check(ctx_, ht_render_depth(ctx_, p7.data(), cams.data(), w, h, far, B, d.data(), nullptr));
+		std::vector<Image<unsigned short>> out;
+		for (int b = 0; b < B; b++) out.emplace_back(cam, std::vector<unsigned short>(d.begin() + (size_t)b * w * h, d.begin() + (size_t)(b + 1) * w * h));
+		return out;
+	}
+	Image<unsigned short> render_depth(const std::vector<Pose> &poses, const DCamera &cam, float far = 4.0f) const { return render_depth(std::vector<std::vector<Pose>>{ poses }, cam, far)[0]; }
 private:
 	ht_ctx *ctx_ = nullptr; int nb_ = 0;
 	ht_ctx *job_ = nullptr; bool job_in_flight_ = false; Image<unsigned short> job_image_; std::string model_path_; int device_ = 0;      // the overlapped mode's second context

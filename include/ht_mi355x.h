@@ -249,6 +249,19 @@ int ht_segment_vr(ht_ctx *ctx, const uint16_t *depth, const float *cams, int w, 
 int ht_segment_vr_dev(ht_ctx *ctx, const uint16_t *d_depth, const float *d_cams, int w, int h, int B, int entry_options, float wrange_lo, float wrange_hi, float diam,
                       uint16_t *d_tiles, float *d_cams_out, void *stream);
 
+/* ---- synthetic depth frames (an addition: the reference renders its fake hand on the host) ---------------------------
+ * ht_render_depth     replaces  the software_rasterizer branch of synthetic-tracker.cpp:182, FakeDepth (:69-76), for B frames: pixel (x, y) of
+ *                     frame f is (uint16)(PhysModel::HitCheck({0,0,0}, deprojectz((x, y), far)).impact.z / depth_scale) (physmodel.h:287-294,
+ *                     geometric.h:275-302, misc_image.h:48) with the context's hand model (as ht_create built it and ht_scale left it) at the
+ *                     centre-of-mass poses poses [B][nb][7] (PhysModel::SetPose, :435).  cams [B][12]: focal, principal point and depth_scale are
+ *                     used; the camera's pose is not -- the ray starts at the origin of the poses' frame, as in FakeDepth.  Bit-identical to the
+ *                     host's HitCheck.  depth [B][h][w]; body (optional, [B][h][w]) = ModelHitInfo::rb, -1 for background.  w, h in [1, 4096],
+ *                     far > 0 (the application uses 4); B is not bounded by the context's max_batch (no tracker slot is used; the call stages
+ *                     through device buffers it grows on demand); B = 0 does nothing.  HT_ERR_STATE for a context without a hand model.
+ * ht_render_depth_dev the same on device buffers, asynchronous on `stream`. */
+int ht_render_depth(ht_ctx *ctx, const float *poses, const float *cams, int w, int h, float far, int B, uint16_t *depth, int8_t *body);
+int ht_render_depth_dev(ht_ctx *ctx, const float *d_poses, const float *d_cams, int w, int h, float far, int B, uint16_t *d_depth, int8_t *d_body, void *stream);
+
 /* ---- annotation fit loop ---------------------------------------------------------------------------------------------
  * ht_slowfit          replaces  void HandTracker::slowfit(const std::vector<float3> &points, int hold, const std::vector<Pose> &refpose,
  *                     int steps_ = 6, RigidBody *selectrb = NULL, const float3 &spoint, const float3 &rbpoint, const std::vector<float4> &crays)

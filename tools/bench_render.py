@@ -1,0 +1,172 @@
+"""Device renderer (ht_render_depth_dev, csrc/ht_render.hip): frames/s by size, model and batch, the empty-frame floor, and the closed loop
+render -> ht_update_frames_dev at 1024 frames with a new batch of poses every step.  Writes profiles/r07_render.json (or --out).
+
+    python tools/bench_render.py [--steps 20] [--warmup 3] [--out profiles/r07_render.json] [--quick]
+
+Hands: the bench recording's ground truths (bench_data/frames1024.npz, 17 bones) and the 26-bone start poses of bench_data/frames5_256.npz, seen
+through the application's 320x240 camera (focal 305) or a 128x128 one (focal 163).  Empty frames: the same hands moved 10 m behind the camera."""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+from hand_tracking_samples_amd import build as hb, native, weights as W  # noqa: E402
+
+M17 = os.path.join(ROOT, "hand_tracking_samples_amd", "assets", "model_hand17.htfx")
+M26 = os.path.join(ROOT, "hand_tracking_samples_amd", "assets", "model_hand26.htfx")
+CAMS = {(320, 240): [305, 305, 160, 120], (128, 128): [163, 163, 64, 64]}
+
+
+def cam_of(w, h, B):
+    c = np.zeros((B, 12), np.float32); c[:, :4] = CAMS[(w, h)]; c[:, 4] = 0.001; c[:, 11] = 1
+    return c
+
+
+def time_it(fn, stream, steps, warmup):
+    for _ in range(warmup):
+        fn()
+    stream.synchronize()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record(stream)
+    for _ in range(steps):
+        fn()
+    e1.record(stream)
+    e1.synchronize()
+    return e0.elapsed_time(e1) / steps
+
+
+def slerp(a, b, t):
+    """[..., 4] quaternions, float64"""
+    d = (a * b).sum(-1, keepdims=True)
+    b = np.where(d < 0, -b, b); d = np.abs(d)
+    th = np.arccos(np.clip(d, -1.0, 1.0))
+    sn = np.sin(th)
+    lin = d > 0.9995
+    q = np.where(lin, a + (b - a) * t, (np.sin((1 - t) * th) * a + np.sin(t * th) * b) / np.where(lin, 1.0, sn))
+    return q / np.linalg.norm(q, axis=-1, keepdims=True)
+
+
+def user_pos(poses, com):
+    """RigidBody::PositionUser (physics.h:142): pose * -com, for comparing body poses with the tracker's GetPoseUser output"""
+    x, y, z, w = (poses[..., 3 + i].astype(np.float64) for i in range(4))
+    v = -com[None].astype(np.float64)
+    m = [[w * w + x * x - y * y - z * z, 2 * (x * y - z * w), 2 * (z * x + y * w)], [2 * (x * y + z * w), w * w - x * x + y * y - z * z, 2 * (y * z - x * w)],
+         [2 * (z * x - y * w), 2 * (y * z + x * w), w * w - x * x - y * y + z * z]]
+    return poses[..., :3] + np.stack([m[r][0] * v[..., 0] + m[r][1] * v[..., 1] + m[r][2] * v[..., 2] for r in range(3)], -1)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r07_render.json"))
+    ap.add_argument("--quick", action="store_true", help="one batch size per case (a check that everything runs)")
+    ap.add_argument("--loop-steps", type=int, default=32)
+    a = ap.parse_args()
+    dev = torch.device("cuda:0")
+    torch.cuda.set_device(dev)
+    s = torch.cuda.Stream(device=dev)
+    z = np.load(os.path.join(ROOT, "bench_data", "frames1024.npz"))
+    z5 = np.load(os.path.join(ROOT, "bench_data", "frames5_256.npz"))
+    hands = {17: z["gtpose"], 26: z5["startpose"]}
+    res = {"device": torch.cuda.get_device_name(dev), "steps": a.steps, "warmup": a.warmup, "render": [], "usage": {}}
+    for k, v in hb.resource_usage().items():
+        if "render" in k:
+            res["usage"][k] = {x: v.get(x) for x in ("VGPRs", "SGPRs", "AGPRs", "ScratchSize", "LDS Size", "Occupancy")}
+    batches = (1024,) if a.quick else (1, 64, 1024, 8192)
+    for nb, model in ((17, M17), (26, M26)):
+        ctx = native.Context(model, 1)
+        try:
+            for (w, h) in ((320, 240), (128, 128)):
+                for B in batches:
+                    for empty in (False, True):
+                        p = hands[nb][np.arange(B) % len(hands[nb])].copy()
+                        if empty:
+                            p[:, :, 2] -= 10.0
+                        tp = torch.from_numpy(p).to(dev); tc = torch.from_numpy(cam_of(w, h, B)).to(dev)
+                        td = torch.empty((B, h, w), dtype=torch.int16, device=dev)
+                        ms = time_it(lambda: ctx.render_depth_dev(tp.data_ptr(), tc.data_ptr(), w, h, 4.0, B, td.data_ptr(), None, s.cuda_stream), s, a.steps, a.warmup)
+                        hand_px = float((td.cpu().numpy().view(np.uint16) < 3999).mean())
+                        row = {"bones": nb, "w": w, "h": h, "B": B, "empty": empty, "ms": round(ms, 4), "frames_per_s": round(B / ms * 1e3, 1), "hand_pixel_fraction": round(hand_px, 4)}
+                        print(json.dumps(row), flush=True)
+                        res["render"].append(row)
+                        del tp, tc, td
+        finally:
+            ctx.close()
+    # ---- closed loop at 1024 frames, 320x240: every step renders a new batch of poses (interpolated between consecutive ground truths) and tracks it ----
+    B, w, h, sub = 1024, 320, 240, 4
+    gt = z["gtpose"]
+    seq = []
+    nerr = 8
+    for st in range(a.loop_steps + a.warmup + nerr):
+        k, t = divmod(st, sub); t = t / sub
+        p0 = gt[(np.arange(B) + k) % len(gt)]; p1 = gt[(np.arange(B) + k + 1) % len(gt)]
+        p = np.empty_like(p0)
+        p[:, :, :3] = p0[:, :, :3] * (1 - t) + p1[:, :, :3] * t
+        p[:, :, 3:] = slerp(p0[:, :, 3:].astype(np.float64), p1[:, :, 3:].astype(np.float64), t)
+        seq.append(p.astype(np.float32))
+    ctx = native.Context(M17, B)
+    L = native.load()
+    try:
+        ctx.load_weights(W.make_cnnb())
+        ctx.set_params(microforce=3.0, mainthreadpasses=3)
+        ctx.reserve_points(w * h // 4)
+        com = np.zeros((17, 3), np.float32)
+        import ctypes as C
+        m = C.c_void_p(); assert L.ht_model_open(M17.encode(), 1, C.byref(m)) == 0
+        for b in range(17):
+            c3 = np.zeros(3, np.float32); L.ht_model_body(m, b, None, None, None, c3.ctypes.data_as(C.POINTER(C.c_float)), None); com[b] = c3
+        L.ht_model_close(m)
+        tseq = torch.from_numpy(np.stack(seq)).to(dev)
+        tc = torch.from_numpy(cam_of(w, h, B)).to(dev)
+        ts = torch.from_numpy(z["startpose"]).to(dev)
+        td = torch.empty((B, h, w), dtype=torch.int16, device=dev); out = torch.empty((B, 17, 7), dtype=torch.float32, device=dev)
+        ctx.render_depth_dev(tseq[0].data_ptr(), tc.data_ptr(), w, h, 4.0, B, td.data_ptr(), None, s.cuda_stream)
+        ctx.update_frames_dev(td.data_ptr(), tc.data_ptr(), w, h, 0.17, ts.data_ptr(), B, out.data_ptr(), s.cuda_stream)      # seeds every slot, grows the point arrays
+        s.synchronize()
+        errs = []
+        e = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+        step = {"i": 1}
+
+        def loop_step():
+            i = step["i"]; step["i"] += 1
+            ctx.render_depth_dev(tseq[i].data_ptr(), tc.data_ptr(), w, h, 4.0, B, td.data_ptr(), None, s.cuda_stream)
+            ctx.update_frames_dev(td.data_ptr(), tc.data_ptr(), w, h, 0.17, None, B, out.data_ptr(), s.cuda_stream)
+        for _ in range(a.warmup - 1):
+            loop_step()
+        s.synchronize()
+        e[0].record(s)
+        for _ in range(a.loop_steps):
+            loop_step()
+        e[1].record(s); e[1].synchronize()
+        loop_ms = e[0].elapsed_time(e[1]) / a.loop_steps
+        for _ in range(nerr):      # then the error against the truth after every step (untimed)
+            loop_step()
+            s.synchronize()
+            got = out.cpu().numpy(); want = user_pos(seq[step["i"] - 1], com)
+            errs.append(float(np.linalg.norm(got[:, :, :3] - want, axis=2).mean()))
+        # the two halves apart, same batch: the render alone and the tracker step alone
+        r_ms = time_it(lambda: ctx.render_depth_dev(tseq[-1].data_ptr(), tc.data_ptr(), w, h, 4.0, B, td.data_ptr(), None, s.cuda_stream), s, a.steps, a.warmup)
+        u_ms = time_it(lambda: ctx.update_frames_dev(td.data_ptr(), tc.data_ptr(), w, h, 0.17, None, B, out.data_ptr(), s.cuda_stream), s, max(4, a.steps // 4), 1)
+        got = out.cpu().numpy()
+    finally:
+        ctx.close()
+    res["closed_loop"] = {"B": B, "w": w, "h": h, "steps": a.loop_steps, "substeps_between_truths": sub, "ms_per_step": round(loop_ms, 3), "frames_per_s": round(B / loop_ms * 1e3, 1),
+                          "render_ms": round(r_ms, 3), "update_frames_dev_ms": round(u_ms, 3), "render_over_update": round(r_ms / u_ms, 4),
+                          "tracked_vs_truth_mean_body_position_error_m": [round(x, 5) for x in errs],
+                          "note": "poses interpolated between consecutive frames1024.npz ground truths (positions lerped, quaternions slerped); error = mean over frames and bodies of |GetPoseUser position - truth|"}
+    print(json.dumps(res["closed_loop"]), flush=True)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            json.dump(res, f, indent=1)
+            f.write("\n")
+
+
+if __name__ == "__main__":
+    main()
