@@ -260,13 +260,40 @@ extern "C" int ht_scale(ht_ctx *ctx, float s)
 }
 // CNN::Train (cnn.h:558-580), one SGD step per sample in the order given (train-cnn.cpp:156-162 calls it with alpha = 0.001), on the weights
 // held by the context; ht_cnn_get_weights reads them back in .cnnb order (CNN::saveb cnn.h:591-593).
+// The steps on device pools: step k trains on sample order[k] (order[k] = k without an order); the indices were checked by the caller.  The
+// training arena ends with a sink for the per-step MSE when the caller asks for none.
+static int cnn_train_steps(ht_ctx *ctx, const float *d_x, const float *d_t, const int *order, int n_steps, float alpha, float *d_mse, hipStream_t s)
+{
+	const size_t na = ht_train_act_floats(), ne = ht_train_err_floats(), np = ht_train_part_floats();
+	if (!ctx->d_train) { int r = dev_alloc(ctx, &ctx->d_train, na + ne + np + 16); if (r) return r; }
+	float *sink = ctx->d_train + na + ne + np;
+	for (int k = 0; k < n_steps; k++)
+	{
+		const size_t i = order ? (size_t)order[k] : (size_t)k;
+		ht_launch_train_step(ctx->d_weights, ctx->d_weights + HT_CNNB_COUNT, d_x + i * HT_CNN_IN, d_t + i * HT_CNN_OUT, alpha, ctx->d_train, ctx->d_train + na, ctx->d_train + na + ne, d_mse ? d_mse + k : sink, s);
+	}
+	ht_launch_pack_w4(ctx->cnnw.W4, ctx->d_weights + HT_CNNB_COUNT + 16384, s);      // the forward kernels' copy of the last layer follows the trained weights
+	return HT_OK;
+}
+extern "C" int ht_cnn_train_dev(ht_ctx *ctx, const float *d_inputs, const float *d_targets, int n_pool, const int *order, int n_steps, float alpha, float *d_mse, void *stream)
+{
+	CHECK_READY(ctx);
+	if (!ctx->have_weights) { ctx->err = "CNN weights not loaded (ht_cnn_load_weights)"; return HT_ERR_STATE; }
+	if (!d_inputs || !d_targets || n_pool < 1 || n_steps < 0) { ctx->err = "ht_cnn_train_dev: bad argument"; return HT_ERR_ARG; }
+	if (!order && n_steps > n_pool) { ctx->err = "ht_cnn_train_dev: without an order, n_steps must not exceed n_pool"; return HT_ERR_ARG; }
+	if (order) for (int k = 0; k < n_steps; k++) if (order[k] < 0 || order[k] >= n_pool) { ctx->err = "ht_cnn_train_dev: order[" + std::to_string(k) + "] is outside [0, n_pool)"; return HT_ERR_ARG; }
+	if (n_steps == 0) return HT_OK;
+	hipStream_t s = ht_user_stream(ctx, stream);
+	{ const int r = cnn_train_steps(ctx, d_inputs, d_targets, order, n_steps, alpha, d_mse, s); if (r) return r; }
+	HIPCHK(ctx, hipGetLastError());
+	return HT_OK;
+}
+// the host-array form: an upload, then the same steps on the context's stream
 extern "C" int ht_cnn_train(ht_ctx *ctx, const float *inputs, const float *targets, int n, float alpha, float *mse_out)
 {
 	CHECK_READY(ctx);
 	if (!ctx->have_weights) { ctx->err = "CNN weights not loaded (ht_cnn_load_weights)"; return HT_ERR_STATE; }
 	if (!inputs || !targets || n < 1) return HT_ERR_ARG;
-	const size_t na = ht_train_act_floats(), ne = ht_train_err_floats(), np = ht_train_part_floats();
-	if (!ctx->d_train) { int r = dev_alloc(ctx, &ctx->d_train, na + ne + np); if (r) return r; }
 	float *d_x = nullptr, *d_t = nullptr, *d_mse = nullptr;
 	int rc = HT_OK;
 	if (hipMalloc((void **)&d_x, (size_t)n * HT_CNN_IN * sizeof(float)) != hipSuccess || hipMalloc((void **)&d_t, (size_t)n * HT_CNN_OUT * sizeof(float)) != hipSuccess ||
@@ -274,14 +301,9 @@ extern "C" int ht_cnn_train(ht_ctx *ctx, const float *inputs, const float *targe
 	hipStream_t s = ctx->stream;
 	if (rc == HT_OK && (hipMemcpyAsync(d_x, inputs, (size_t)n * HT_CNN_IN * sizeof(float), hipMemcpyHostToDevice, s) != hipSuccess ||
 	                    hipMemcpyAsync(d_t, targets, (size_t)n * HT_CNN_OUT * sizeof(float), hipMemcpyHostToDevice, s) != hipSuccess)) { ctx->err = "ht_cnn_train: upload failed"; rc = HT_ERR_HIP; }
-	if (rc == HT_OK)
-	{
-		for (int k = 0; k < n; k++)
-			ht_launch_train_step(ctx->d_weights, ctx->d_weights + HT_CNNB_COUNT, d_x + (size_t)k * HT_CNN_IN, d_t + (size_t)k * HT_CNN_OUT, alpha, ctx->d_train, ctx->d_train + na, ctx->d_train + na + ne, d_mse + k, s);
-		ht_launch_pack_w4(ctx->cnnw.W4, ctx->d_weights + HT_CNNB_COUNT + 16384, s);      // the forward kernels' copy of the last layer follows the trained weights
-		if ((mse_out && hipMemcpyAsync(mse_out, d_mse, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, s) != hipSuccess) || hipStreamSynchronize(s) != hipSuccess || hipGetLastError() != hipSuccess)
-		{ ctx->err = "ht_cnn_train: device error"; rc = HT_ERR_HIP; }
-	}
+	if (rc == HT_OK) rc = cnn_train_steps(ctx, d_x, d_t, nullptr, n, alpha, d_mse, s);
+	if (rc == HT_OK && ((mse_out && hipMemcpyAsync(mse_out, d_mse, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, s) != hipSuccess) || hipStreamSynchronize(s) != hipSuccess || hipGetLastError() != hipSuccess))
+	{ ctx->err = "ht_cnn_train: device error"; rc = HT_ERR_HIP; }
 	(void)hipFree(d_x); (void)hipFree(d_t); (void)hipFree(d_mse);
 	return rc;
 }
@@ -291,7 +313,7 @@ extern "C" int ht_cnn_get_weights(ht_ctx *ctx, float *w, size_t n)
 	if (!w) return HT_ERR_ARG;
 	if (!ctx->have_weights) { ctx->err = "no weights to read"; return HT_ERR_STATE; }
 	if (n != HT_CNNB_COUNT) { ctx->err = "weights: expected HT_CNNB_COUNT fp32 values in .cnnb order"; return HT_ERR_ARG; }
-	HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+	HIPCHK(ctx, ht_sync_all(ctx));      // also a ht_cnn_train_dev on a caller's stream
 	HIPCHK(ctx, hipMemcpy(w, ctx->d_weights, n * sizeof(float), hipMemcpyDeviceToHost));
 	return HT_OK;
 }

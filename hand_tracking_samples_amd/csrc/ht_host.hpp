@@ -76,6 +76,7 @@ struct ht_ctx
 	int user_lin_cap = 0, user_ang_cap = 0;
 	ht_comm_state *comm = nullptr;                               // multi-GPU pose gather (ht_comm_init), null on a single-GPU host
 	void *d_render = nullptr; size_t render_cap = 0;             // ht_render_depth's staging (poses, cameras, frames, body labels), grown to the largest call; in `allocs`
+	void *d_labels = nullptr; size_t labels_cap = 0;             // ht_expected_cnn_batch's staging (poses, cameras, labels, image points, key angles), grown to the largest call; in `allocs`
 	std::vector<float4> render_planes; std::vector<float> render_radii;      // the hull planes ht_render_depth last derived its per-body cull radii from, and those radii (2 per body)
 };
 

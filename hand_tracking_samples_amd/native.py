@@ -14,11 +14,13 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 HT_OK = 0
 CNN_IN, CNN_OUT, CNNB_COUNT, POSE, STATE, CAM, ANALYSIS = 4096, 2304, 9458400, 7, 13, 12, 84
 MAXPTS, ROW, CONTACT = 4096, 16, 12      # HT_MAX_POINTS
+LABELS_SEGMENT_FRAME = 1      # HT_LABELS_SEGMENT_FRAME
 
 # every symbol include/ht_mi355x.h declares (checked by tests/test_abi.py)
 SYMBOLS = (
     "ht_create", "ht_destroy", "ht_model_bake", "ht_last_error", "ht_get_params", "ht_set_params", "ht_model_info", "ht_config_read", "ht_scale",
     "ht_cnn_load_weights", "ht_cnn_eval", "ht_cnn_eval_dev", "ht_cnn_load_weights_sized", "ht_cnn_eval_sized", "ht_cnn_eval_sized_dev", "ht_cnn_train", "ht_cnn_get_weights", "ht_expected_cnn", "ht_expected_cnn_full",
+    "ht_expected_cnn_batch", "ht_expected_cnn_dev", "ht_cnn_input_dev", "ht_cnn_train_dev",
     "ht_model_open", "ht_model_close", "ht_model_error", "ht_model_counts", "ht_model_body", "ht_model_body_mesh", "ht_model_body_sdmesh", "ht_model_hitcheck",
     "ht_tracker_reset", "ht_get_state", "ht_set_state", "ht_get_tracker_flags", "ht_set_tracker_flags", "ht_update_sync", "ht_update_dev", "ht_update_frames_sync", "ht_update_frames_dev", "ht_update_direct_sync", "ht_update_direct_dev", "ht_update_cnn_model_sync", "ht_get_cnn_results", "ht_get_cnn_layers", "ht_frames_overflow", "ht_reserve_points", "ht_point_capacity", "ht_capacity_events", "ht_segment_vr", "ht_segment_vr_dev", "ht_render_depth", "ht_render_depth_dev", "ht_slowfit", "ht_set_points", "ht_fit_rows", "ht_physics_update",
     "ht_stage_prepare", "ht_stage_decode", "ht_stage_fit_error", "ht_stage_cloud_rows", "ht_stage_contacts", "ht_stage_fit",
@@ -101,6 +103,10 @@ def load(build_if_missing=True):
     L.ht_cnn_train.argtypes = [vp, fp, fp, C.c_int, C.c_float, fp]
     L.ht_cnn_get_weights.argtypes = [vp, fp, C.c_size_t]
     L.ht_expected_cnn.argtypes = [fp, fp, fp]
+    L.ht_expected_cnn_batch.argtypes = [vp, fp, fp, C.c_int, C.c_int, fp, fp, fp]
+    L.ht_expected_cnn_dev.argtypes = [vp, vp, vp, C.c_int, C.c_int, vp, vp, vp, vp]
+    L.ht_cnn_input_dev.argtypes = [vp, vp, vp, C.c_int, vp, vp]
+    L.ht_cnn_train_dev.argtypes = [vp, vp, vp, C.c_int, ip, C.c_int, C.c_float, vp, vp]
     L.ht_set_points.argtypes = [vp, C.c_int, fp, C.c_int, ip]
     L.ht_slowfit.argtypes = [vp, C.c_int, C.c_int, fp, C.c_int, C.c_int, fp, fp, fp, C.c_int]
     L.ht_get_cnn_layers.argtypes = [vp, C.c_int, C.c_int, fp, fp, fp, fp]
@@ -543,6 +549,33 @@ class Context:
         mse = np.zeros(x.shape[0], np.float32)
         self._chk(self.L.ht_cnn_train(self.h, _f(x), _f(t), x.shape[0], float(alpha), _f(mse)))
         return mse
+
+    def cnn_train_dev(self, d_inputs, d_targets, n_pool, order=None, n_steps=None, alpha=0.001, d_mse=None, stream=None):
+        """ht_cnn_train_dev: CNN::Train on device pools (inputs [n_pool,4096], targets [n_pool,2304]); step k uses sample order[k] (a host array of
+        indices, checked before anything runs), or sample k without an order.  d_mse [n_steps] optional.  Asynchronous on `stream`."""
+        o = None if order is None else np.ascontiguousarray(order, np.int32)
+        n = (len(o) if o is not None else int(n_pool)) if n_steps is None else int(n_steps)
+        if o is not None and len(o) < n:
+            raise ValueError("order holds fewer than n_steps indices")
+        self._chk(self.L.ht_cnn_train_dev(self.h, d_inputs, d_targets, int(n_pool), None if o is None else _i(o), n, float(alpha), d_mse, stream))
+
+    # -- training samples on the device
+    def expected_cnn_batch(self, poses, cams, segment_frame=False):
+        """GatherHandExpectedCNN (handtrack.h:160-173) for a batch on the device: poses [B,nb,7], tile cameras [B,12] -> (expected [B,2304],
+        image_points [B,8,2], vals [B,16]); segment_frame: train-cnn's compress first (HT_LABELS_SEGMENT_FRAME)."""
+        poses = _c(poses, np.float32).reshape(-1, self.nb, POSE); B = poses.shape[0]
+        cams = _c(cams, np.float32).reshape(B, CAM)
+        e = np.empty((B, CNN_OUT), np.float32); ip = np.empty((B, 8, 2), np.float32); v = np.empty((B, 16), np.float32)
+        self._chk(self.L.ht_expected_cnn_batch(self.h, _f(poses), _f(cams), B, LABELS_SEGMENT_FRAME if segment_frame else 0, _f(e), _f(ip), _f(v)))
+        return e, ip, v
+
+    def expected_cnn_dev(self, d_poses, d_cams, B, d_expected, d_image_points=None, d_vals=None, segment_frame=False, stream=None):
+        """ht_expected_cnn_dev: device pointers (poses [B,nb,7], cams [B,12] -> expected [B,2304], image_points [B,8,2] / vals [B,16] or None), asynchronous on `stream`."""
+        self._chk(self.L.ht_expected_cnn_dev(self.h, d_poses, d_cams, int(B), LABELS_SEGMENT_FRAME if segment_frame else 0, d_expected, d_image_points, d_vals, stream))
+
+    def cnn_input_dev(self, d_tiles, d_cams, B, d_cnn_in, stream=None):
+        """ht_cnn_input_dev: the net's input (handtrack.h:700) of B 64x64 tiles u16[B,4096] with cameras [B,12] -> float [B,4096], asynchronous on `stream`."""
+        self._chk(self.L.ht_cnn_input_dev(self.h, d_tiles, d_cams, int(B), d_cnn_in, stream))
 
     def cnn_get_weights(self):
         w = np.empty(9458400, np.float32)

@@ -280,6 +280,12 @@ public:
 		check(ctx_, ht_cnn_train(ctx_, x.data(), expected.data(), 1, alpha, &mse));
 		return mse;
 	}
+	// Addition: Train (cnn.h:558-580) for a pool on the device, d_inputs [n_pool][4096] and d_targets [n_pool][2304]: step k on sample order[k], in turn
+	// (ht_cnn_train_dev; asynchronous on `stream`, the indices checked first).  d_mse [order.size()] (device, optional) takes what each step returns.
+	void Train(const float *d_inputs, const float *d_targets, int n_pool, const std::vector<int> &order, float alpha = 0.01f, float *d_mse = nullptr, void *stream = nullptr)
+	{
+		check(ctx_, ht_cnn_train_dev(ctx_, d_inputs, d_targets, n_pool, order.data(), (int)order.size(), alpha, d_mse, stream));
+	}
 	void saveb(std::ostream &s)                                                              // cnn.h:591
 	{
 		std::vector<float> w(HT_CNNB_COUNT);
@@ -290,6 +296,7 @@ public:
 	void loadb(std::string fname) { std::ifstream is(fname, std::ios_base::binary | std::ios_base::in); if (!is.is_open()) throw std::runtime_error("cannot open " + fname); loadb(is); }   // cnn.h:592
 };
 
+struct ExpectedCNN;
 struct HandTracker                                                                            // include/handtrack.h:513-846
 {
 	// tunables with the reference's names and defaults (handtrack.h:523-547); pushed to the device context before every update
@@ -502,6 +509,10 @@ struct HandTracker                                                              
 		return out;
 	}
 	Image<unsigned short> render_depth(const std::vector<Pose> &poses, const DCamera &cam, float far = 4.0f) const { return render_depth(std::vector<std::vector<Pose>>{ poses }, cam, far)[0]; }
+	// Addition, not a reference name: GatherHandExpectedCNN (handtrack.h:160-173) for a batch of pose sets on this tracker's device, frame b seen by the
+	// heat-map camera hcams[b] (as the single-frame form takes it); segment_frame: train-cnn's compress first (train-cnn.cpp:31-50: the poses in the
+	// camera's frame, the camera at the identity).  The same ExpectedCNN sets as the single-frame form, bit for bit (ht_expected_cnn_batch).
+	std::vector<ExpectedCNN> GatherHandExpectedCNN(const std::vector<std::vector<Pose>> &poses, const std::vector<DCamera> &hcams, bool segment_frame = false) const;
 private:
 	ht_ctx *ctx_ = nullptr; int nb_ = 0;
 	ht_ctx *job_ = nullptr; bool job_in_flight_ = false; Image<unsigned short> job_image_; std::string model_path_; int device_ = 0;      // the overlapped mode's second context
@@ -591,23 +602,66 @@ inline CNN PoseInitializerCNN(std::string filename, int device = 0)
 
 // GatherHandExpectedCNN(pose, hcam) (handtrack.h:160-173): the labels the net is trained to produce for a hand pose seen by the 16x16 heat-map camera
 struct ExpectedCNN { std::vector<float> cnn_expected; std::vector<float2> image_points; std::vector<Image<unsigned char>> hmaps; Image<unsigned char> vmap; std::vector<float> vals; };
+namespace detail
+{
+// the C-ABI takes the 64x64 tile camera and forms camsub(cam, 4) itself; scaling by 4 and back is exact in binary floating point
+inline void tile_cam_of(const DCamera &hcam, float *cam)
+{
+	const float c[HT_CAM] = { hcam.focal().x * 4.0f, hcam.focal().y * 4.0f, hcam.principal().x * 4.0f, hcam.principal().y * 4.0f, hcam.depth_scale,
+	                          hcam.pose.position.x, hcam.pose.position.y, hcam.pose.position.z, hcam.pose.orientation.x, hcam.pose.orientation.y, hcam.pose.orientation.z, hcam.pose.orientation.w };
+	for (int i = 0; i < HT_CAM; i++) cam[i] = c[i];
+}
+inline void flat_poses(const std::vector<Pose> &pose, float *p7)
+{
+	for (size_t b = 0; b < pose.size(); b++) { float *p = &p7[b * HT_POSE]; p[0] = pose[b].position.x; p[1] = pose[b].position.y; p[2] = pose[b].position.z; p[3] = pose[b].orientation.x; p[4] = pose[b].orientation.y; p[5] = pose[b].orientation.z; p[6] = pose[b].orientation.w; }
+}
+inline void fill_expected(ExpectedCNN &e, const float *ip, const DCamera &hcam);
+}
 inline ExpectedCNN GatherHandExpectedCNN(const std::vector<Pose> &pose, const DCamera &hcam)
 {
 	if (pose.size() < 17) throw std::runtime_error("GatherHandExpectedCNN: the landmark table names bones up to 16 (handtrack.h:77-81)");
 	std::vector<float> p7(pose.size() * HT_POSE);
-	for (size_t b = 0; b < pose.size(); b++) { float *p = &p7[b * HT_POSE]; p[0] = pose[b].position.x; p[1] = pose[b].position.y; p[2] = pose[b].position.z; p[3] = pose[b].orientation.x; p[4] = pose[b].orientation.y; p[5] = pose[b].orientation.z; p[6] = pose[b].orientation.w; }
-	// the C-ABI takes the 64x64 tile camera and forms camsub(cam, 4) itself; scaling by 4 and back is exact in binary floating point
-	const float cam[HT_CAM] = { hcam.focal().x * 4.0f, hcam.focal().y * 4.0f, hcam.principal().x * 4.0f, hcam.principal().y * 4.0f, hcam.depth_scale,
-	                            hcam.pose.position.x, hcam.pose.position.y, hcam.pose.position.z, hcam.pose.orientation.x, hcam.pose.orientation.y, hcam.pose.orientation.z, hcam.pose.orientation.w };
+	detail::flat_poses(pose, p7.data());
+	float cam[HT_CAM];
+	detail::tile_cam_of(hcam, cam);
 	ExpectedCNN e; e.cnn_expected.resize(HT_CNN_OUT); e.vals.resize(16);
 	float ip[16];
 	if (ht_expected_cnn_full(p7.data(), cam, e.cnn_expected.data(), ip, e.vals.data()) != HT_OK) throw std::runtime_error("GatherHandExpectedCNN failed");
+	detail::fill_expected(e, ip, hcam);
+	return e;
+}
+// the members of the Set the C-ABI does not return, made from the labels: image points, the eight 16x16 landmark maps and the key-angle map as bytes
+inline void detail::fill_expected(ExpectedCNN &e, const float *ip, const DCamera &hcam)
+{
 	for (int k = 0; k < 8; k++) e.image_points.push_back({ ip[2 * k], ip[2 * k + 1] });
 	auto gray = [](float v) { v *= 255.0f; return (unsigned char)(v < 0.0f ? 0.0f : v > 255.0f ? 255.0f : v + 0.5f); };      // the labels are bytes / 255: this recovers the byte
 	for (int m = 0; m < 8; m++) { Image<unsigned char> h(hcam); for (int i = 0; i < 256; i++) h.raster[i] = gray(e.cnn_expected[(size_t)256 * m + i]); e.hmaps.push_back(h); }
 	e.vmap = Image<unsigned char>(DCamera({ 16, 16 }, { 16.f, 16.f }, { 8.f, 8.f }, hcam.depth_scale));
 	for (int i = 0; i < 256; i++) e.vmap.raster[i] = gray(e.cnn_expected[2048 + i]);
-	return e;
+}
+inline std::vector<ExpectedCNN> HandTracker::GatherHandExpectedCNN(const std::vector<std::vector<Pose>> &poses, const std::vector<DCamera> &hcams, bool segment_frame) const
+{
+	const int B = (int)poses.size();
+	if (hcams.size() != poses.size()) throw std::runtime_error("GatherHandExpectedCNN: one camera per pose set");
+	std::vector<float> p7((size_t)B * nb_ * HT_POSE), cams((size_t)B * HT_CAM), ex((size_t)B * HT_CNN_OUT), ip((size_t)B * 16), vals((size_t)B * 16);
+	for (int b = 0; b < B; b++)
+	{
+		if ((int)poses[b].size() != nb_) throw std::runtime_error("GatherHandExpectedCNN: one pose per body");
+		detail::flat_poses(poses[b], &p7[(size_t)b * nb_ * HT_POSE]);
+		detail::tile_cam_of(hcams[b], &cams[(size_t)b * HT_CAM]);
+	}
+	check(ctx_, ht_expected_cnn_batch(ctx_, p7.data(), cams.data(), B, segment_frame ? HT_LABELS_SEGMENT_FRAME : 0, ex.data(), ip.data(), vals.data()));
+	std::vector<ExpectedCNN> out((size_t)B);
+	for (int b = 0; b < B; b++)
+	{
+		ExpectedCNN &e = out[(size_t)b];
+		e.cnn_expected.assign(ex.begin() + (size_t)b * HT_CNN_OUT, ex.begin() + (size_t)(b + 1) * HT_CNN_OUT);
+		e.vals.assign(vals.begin() + (size_t)b * 16, vals.begin() + (size_t)(b + 1) * 16);
+		DCamera hc = hcams[(size_t)b];
+		if (segment_frame) hc.pose = Pose();      // compress: the maps belong to the camera at the identity
+		detail::fill_expected(e, &ip[(size_t)b * 16], hc);
+	}
+	return out;
 }
 
 // A hand model that is posed, drawn and ray-cast but not tracked (host only): `PhysModel fakehand = LoadHandModel();` (synthetic-tracker.cpp:94)

@@ -47,6 +47,7 @@ extern "C" {
 #define HT_MAX_POINTS 4096   /* stride of the point / cloud-row arrays of the stage calls, and the point capacity a context starts with (ht_reserve_points) */
 #define HT_POINTS_LIMIT 76800 /* 320x240: the largest cloud a frame can carry (every pixel in range, subsample_fraction 1) */
 #define HT_ANALYSIS 84        /* floats per frame, see ht_stage_decode */
+#define HT_LABELS_SEGMENT_FRAME 1 /* ht_expected_cnn_batch / _dev flag: train-cnn's compress (train-cnn.cpp:31-50) first, see there */
 
 typedef struct ht_ctx ht_ctx;
 
@@ -216,6 +217,30 @@ int ht_cnn_train(ht_ctx *ctx, const float *inputs, const float *targets, int n, 
 int ht_cnn_get_weights(ht_ctx *ctx, float *w, size_t n);
 int ht_expected_cnn(const float *pose, const float *cam, float *expected);
 int ht_expected_cnn_full(const float *pose, const float *cam, float *expected, float *image_points /* [8][2], may be NULL */, float *vals /* [16], may be NULL */);
+
+/* ---- training samples and training on the device (an addition: train-cnn.cpp runs its loop on the host) -----------------
+ * ht_expected_cnn_batch  replaces  GatherHandExpectedCNN(pose, camsub(cam, 4)) (handtrack.h:160-173) for B frames, on the device: poses [B][nb][7]
+ *                        (nb = the context's bone count, >= 17: bones 1, 4, 6, 7, 9, 10, 12, 13, 15, 16 are read; HT_ERR_ARG below 17), the TILE cameras
+ *                        cams [B][12] -> expected [B][2304], image_points [B][8][2] and vals [B][16] (both may be NULL).  Bit-identical to
+ *                        ht_expected_cnn_full frame by frame for every pose whose eight landmark projections are finite.  With flags =
+ *                        HT_LABELS_SEGMENT_FRAME the poses are first re-expressed as cam.pose.inverse() * p and the camera's pose taken as the
+ *                        identity (train-cnn.cpp:31-50 `compress`): the tiles and cameras of ht_segment_vr with the raw poses give train-cnn's labels.
+ *                        B is not bounded by max_batch (no tracker slot; the call stages through a device buffer it grows on demand); B = 0 does
+ *                        nothing.  HT_ERR_STATE for a context without a hand model.
+ * ht_expected_cnn_dev    the same on device buffers, asynchronous on `stream`; d_expected must be 16-byte aligned.
+ * ht_cnn_input_dev       replaces  the net's input of a segment, handtrack.h:700 (1 - (d - 0.1) / (drangey - 0.1) clamped to [0, 1], drangey from the
+ *                        context's parameters), for B 64x64 tiles d_tiles [B][4096] with cams [B][12] (depth_scale) -> d_cnn_in [B][4096]; equal to
+ *                        ht_stage_prepare's cnn_in.  B is not bounded by max_batch.  d_tiles and d_cnn_in must be 16-byte aligned (HT_ERR_ARG).
+ * ht_cnn_train_dev       replaces  CNN::Train (cnn.h:558-580) for n_steps samples drawn from device pools d_inputs [n_pool][4096] and d_targets
+ *                        [n_pool][2304]: step k trains on sample order[k] (`order` is a HOST array; every index is checked against [0, n_pool)
+ *                        before anything is launched, HT_ERR_ARG otherwise), or on sample k when order is NULL (n_steps <= n_pool).  d_mse
+ *                        [n_steps] (optional) = the value Train returns for each step.  Asynchronous on `stream`; the weights change in that
+ *                        stream's order, and the caller orders other streams' use of the net after it.  Uses the context's training scratch only.
+ *                        ht_cnn_train is an upload followed by this call. */
+int ht_expected_cnn_batch(ht_ctx *ctx, const float *poses, const float *cams, int B, int flags, float *expected, float *image_points, float *vals);
+int ht_expected_cnn_dev(ht_ctx *ctx, const float *d_poses, const float *d_cams, int B, int flags, float *d_expected, float *d_image_points, float *d_vals, void *stream);
+int ht_cnn_input_dev(ht_ctx *ctx, const uint16_t *d_tiles, const float *d_cams, int B, float *d_cnn_in, void *stream);
+int ht_cnn_train_dev(ht_ctx *ctx, const float *d_inputs, const float *d_targets, int n_pool, const int *order, int n_steps, float alpha, float *d_mse, void *stream);
 
 /* ---- a hand model that is not being tracked (host only, no device needed) ---------------------------------------------------
  * The reference's applications keep a second PhysModel to pose, draw and ray-cast their synthetic input

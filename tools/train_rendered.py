@@ -1,0 +1,186 @@
+"""train-cnn's loop on the device (train-hand-pose-cnn/train-cnn.cpp: render, compress, label, Train), on one stream, from a seed.  Every round:
+
+  1. B poses interpolated between consecutive bench_data/frames1024.npz ground truths (positions lerped, rotations slerped, as tools/bench_render.py);
+  2. ht_render_depth_dev at 320x240 with the application's camera (synthetic-tracker.cpp:98);
+  3. ht_segment_vr_dev(0xF, {0.1, 0.70});
+  4. ht_cnn_input_dev (handtrack.h:700);
+  5. ht_expected_cnn_dev(..., HT_LABELS_SEGMENT_FRAME): train-cnn's compress + GatherHandExpectedCNN;
+  6. ht_cnn_train_dev over a seeded permutation of the round's samples (batch-1 SGD, lr 0.001, CNN::Train).
+
+Held out: the frames tools/train_synthetic.py holds out (every 16th bench frame) and every interpolation that touches one of them.  Reported: the held-out
+MSE of the net on those 64 bench tiles, and on how many of them the unit of work takes the CNN-driven pose (the measure of tests/test_gpu_trained_net.py).
+Rates: closed-loop samples/s against ht_cnn_train_dev steps/s on a resident pool, and the label and tile-input stages timed with device events.
+
+    python tools/train_rendered.py [--rounds 280] [--batch 1024] [--seed N] [--json profiles/r07_labels.json]"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+from hand_tracking_samples_amd import native, weights as W  # noqa: E402
+from bench_render import slerp  # noqa: E402
+
+SEED = 0x5EED0001
+HOLD = 16
+M17 = os.path.join(ROOT, "hand_tracking_samples_amd", "assets", "model_hand17.htfx")
+QVGA_CAM = np.array([305, 305, 160, 120, 0.001, 0, 0, 0, 0, 0, 0, 1], np.float32)
+
+
+def train_pairs(n):
+    """consecutive ground-truth pairs (k, k + 1) that touch no held-out frame"""
+    held = set(range(0, n, HOLD))
+    return np.array([k for k in range(n - 1) if k not in held and k + 1 not in held])
+
+
+def draw(gt, pairs, B, rng):
+    k = pairs[rng.integers(len(pairs), size=B)]
+    t = rng.uniform(0, 1, size=(B, 1, 1))
+    p0, p1 = gt[k], gt[k + 1]
+    p = np.empty_like(p0)
+    p[:, :, :3] = p0[:, :, :3] * (1 - t) + p1[:, :, :3] * t
+    p[:, :, 3:] = slerp(p0[:, :, 3:].astype(np.float64), p1[:, :, 3:].astype(np.float64), t)
+    return p.astype(np.float32)
+
+
+def held_out(ctx, d):
+    """held-out MSE on the 64 bench tiles train_synthetic.py holds out (host labels of their ground truths), and the CNN-driven pose count"""
+    fr = np.arange(0, len(d["gtpose"]), HOLD)
+    depth, cams, start = d["depth"][fr].reshape(len(fr), -1), d["cam"][fr], d["startpose"][fr]
+    x = ctx.stage_prepare(depth, cams)[0]
+    t = np.stack([native.expected_cnn(d["gtpose"][i], d["cam"][i]) for i in fr])
+    y = ctx.cnn_eval(x)
+    ctx.set_params(microforce=3.0, mainthreadpasses=3)
+    ctx.tracker_reset(start)
+    _, acc = ctx.update_cnn_model_sync(depth.reshape(len(fr), 64, 64), cams)
+    return float(((y - t) ** 2).mean()), int(np.asarray(acc).astype(bool).sum())
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--rounds", type=int, default=280)
+    ap.add_argument("--batch", type=int, default=1024)
+    ap.add_argument("--seed", type=int, default=SEED)
+    ap.add_argument("--json", default=None)
+    ap.add_argument("--rate-steps", type=int, default=2048)
+    a = ap.parse_args()
+    dev = torch.device("cuda:0")
+    d = np.load(os.path.join(ROOT, "bench_data", "frames1024.npz"))
+    gt = d["gtpose"]; pairs = train_pairs(len(gt))
+    B = a.batch
+    rng = np.random.default_rng(a.seed)
+    ctx = native.Context(M17, 64)
+    ctx.load_weights(W.make_cnnb(a.seed, 1.0))
+    s = torch.cuda.Stream(device=dev)
+    cams = torch.from_numpy(np.tile(QVGA_CAM, (B, 1))).to(dev)
+    tp = torch.empty((B, 17, 7), device=dev)
+    depth = torch.empty((B, 240, 320), dtype=torch.int16, device=dev)
+    tiles = torch.empty((B, 64, 64), dtype=torch.int16, device=dev); tcams = torch.empty((B, 12), device=dev)
+    x = torch.empty((B, 4096), device=dev); lab = torch.empty((B, 2304), device=dev); mse = torch.empty(B, device=dev)
+    L = ctx.L
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(6)]
+
+    def round_(poses, order, timed=False):
+        with torch.cuda.stream(s):
+            tp.copy_(torch.from_numpy(poses))      # in the stream's order: the previous round may still read the poses
+            if timed: ev[0].record(s)
+            ctx.render_depth_dev(tp.data_ptr(), cams.data_ptr(), 320, 240, 4.0, B, depth.data_ptr(), None, s.cuda_stream)
+            if timed: ev[1].record(s)
+            assert L.ht_segment_vr_dev(ctx.h, depth.data_ptr(), cams.data_ptr(), 320, 240, B, 0xF, 0.1, 0.70, 0.17, tiles.data_ptr(), tcams.data_ptr(), s.cuda_stream) == 0
+            if timed: ev[2].record(s)
+            ctx.cnn_input_dev(tiles.data_ptr(), tcams.data_ptr(), B, x.data_ptr(), s.cuda_stream)
+            if timed: ev[3].record(s)
+            ctx.expected_cnn_dev(tp.data_ptr(), tcams.data_ptr(), B, lab.data_ptr(), segment_frame=True, stream=s.cuda_stream)
+            if timed: ev[4].record(s)
+            ctx.cnn_train_dev(x.data_ptr(), lab.data_ptr(), B, order=order, d_mse=mse.data_ptr(), stream=s.cuda_stream)
+            if timed: ev[5].record(s)
+
+    mse0, acc0 = held_out(ctx, d)
+    print("before: held-out mse %.3e, CNN-driven pose on %d of 64" % (mse0, acc0), flush=True)
+    curve = []
+    t0 = time.perf_counter()
+    stage_ms = np.zeros(5)
+    for r in range(a.rounds):
+        poses = draw(gt, pairs, B, rng)
+        order = rng.permutation(B).astype(np.int32)
+        round_(poses, order, timed=True)
+        s.synchronize()
+        stage_ms += [ev[i].elapsed_time(ev[i + 1]) for i in range(5)]
+        if (r + 1) % 20 == 0 or r + 1 == a.rounds:
+            rec = {"round": r + 1, "samples": (r + 1) * B, "train_mse": float(mse.mean().item())}
+            if (r + 1) % 70 == 0 or r + 1 == a.rounds:
+                rec["held_out_mse"], rec["cnn_pose_frames"] = held_out(ctx, d)
+            curve.append(rec)
+            print(rec, "%.0f s" % (time.perf_counter() - t0), flush=True)
+    seconds = time.perf_counter() - t0
+    stage_ms /= a.rounds
+    # rates: the closed loop (one untimed-stage round per step of the measurement) against bare training steps on a resident pool
+    poses = draw(gt, pairs, B, rng); order = rng.permutation(B).astype(np.int32)
+    round_(poses, order); s.synchronize()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    nloop = 4
+    with torch.cuda.stream(s):
+        e0.record(s)
+    for _ in range(nloop):
+        round_(poses, order)
+    with torch.cuda.stream(s):
+        e1.record(s)
+    s.synchronize()
+    loop_sps = nloop * B / (e0.elapsed_time(e1) / 1e3)
+    nbare = a.rate_steps
+    bare_order = rng.integers(B, size=nbare).astype(np.int32)
+    with torch.cuda.stream(s):
+        e0.record(s)
+        ctx.cnn_train_dev(x.data_ptr(), lab.data_ptr(), B, order=bare_order, stream=s.cuda_stream)
+        e1.record(s)
+    s.synchronize()
+    bare_sps = nbare / (e0.elapsed_time(e1) / 1e3)
+    # the label kernel alone (B = 1024 and 8192, labels + key angles written) and the tile inputs, device events over repeated launches
+    kern = {}
+    for nB in (1024, 8192):
+        reps = 50
+        P = torch.from_numpy(draw(gt, pairs, nB, rng)).to(dev); Cq = torch.from_numpy(np.tile(QVGA_CAM, (nB, 1))).to(dev)
+        E = torch.empty((nB, 2304), device=dev); V = torch.empty((nB, 16), device=dev)
+        with torch.cuda.stream(s):
+            ctx.expected_cnn_dev(P.data_ptr(), Cq.data_ptr(), nB, E.data_ptr(), None, V.data_ptr(), segment_frame=True, stream=s.cuda_stream)
+            e0.record(s)
+            for _ in range(reps):
+                ctx.expected_cnn_dev(P.data_ptr(), Cq.data_ptr(), nB, E.data_ptr(), None, V.data_ptr(), segment_frame=True, stream=s.cuda_stream)
+            e1.record(s)
+        s.synchronize()
+        ms = e0.elapsed_time(e1) / reps
+        stored = nB * (2304 + 16) * 4
+        kern["labels_B%d" % nB] = {"ms": ms, "frames_per_s": nB / (ms / 1e3), "stored_bytes": stored, "store_GBps": stored / (ms / 1e3) / 1e9, "of_hbm_peak_8TBps": stored / (ms / 1e3) / 8e12}
+        del P, Cq, E, V
+    with torch.cuda.stream(s):
+        ctx.cnn_input_dev(tiles.data_ptr(), tcams.data_ptr(), B, x.data_ptr(), s.cuda_stream)
+        e0.record(s)
+        for _ in range(50):
+            ctx.cnn_input_dev(tiles.data_ptr(), tcams.data_ptr(), B, x.data_ptr(), s.cuda_stream)
+        e1.record(s)
+    s.synchronize()
+    ms = e0.elapsed_time(e1) / 50
+    kern["cnn_input_B%d" % B] = {"ms": ms, "bytes_moved": B * 4096 * 6, "GBps": B * 4096 * 6 / (ms / 1e3) / 1e9}
+    mse1, acc1 = curve[-1]["held_out_mse"], curve[-1]["cnn_pose_frames"]
+    ctx.close()
+    out = {"what": "tools/train_rendered.py: train-cnn's loop on the device, one stream: %d rounds of %d rendered 320x240 frames (render, segment, input, segment-frame labels, "
+                   "batch-1 SGD lr 0.001 over a seeded permutation), seed 0x%X" % (a.rounds, B, a.seed),
+           "rounds": a.rounds, "batch": B, "samples": a.rounds * B, "seconds": seconds,
+           "stage_ms_per_round": {"render": stage_ms[0], "segment": stage_ms[1], "cnn_input": stage_ms[2], "labels": stage_ms[3], "train": stage_ms[4]},
+           "kernels": kern, "closed_loop_samples_per_s": loop_sps, "bare_train_steps_per_s": bare_sps, "loop_over_bare": loop_sps / bare_sps,
+           "held_out": {"frames": 64, "mse_before": mse0, "mse_after": mse1, "cnn_pose_frames_before": acc0, "cnn_pose_frames_after": acc1,
+                        "train_synthetic_reference": "50 of 64 after 300 epochs of the 960 fixed tiles"},
+           "curve": curve}
+    print(json.dumps({k: v for k, v in out.items() if k != "curve"}, indent=1))
+    if a.json:
+        json.dump(out, open(a.json, "w"), indent=1)
+
+
+if __name__ == "__main__":
+    main()
