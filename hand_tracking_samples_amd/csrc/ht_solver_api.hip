@@ -200,7 +200,7 @@ static void main_pass(ht_ctx *ctx, int B, hipStream_t s, float *poses_out = null
 	if (!ctx->planes_valid) { ht_prof_scope ps(ctx, "chamber", s, true); ht_launch_chamber_planes(ctx->model, pts, npts, p.min_point_num, p.boundary_planes, ctx->d_chplanes, ctx->d_chon, B, s); }
 	if (par) { if (tables) fork1(ctx, s, 0); else fork(ctx, s); }
 	if (pose_only) solve_prep(ctx, 0, false, false, nullptr, 0, 0.0f, 0, 0, B, ctx->side[1], 1);      // the pose-only tables ahead of the boundary planes on their side stream: both beside the cloud rows
-	if (!tables) { ht_prof_scope ps(ctx, "chamber", s, true); ht_launch_chamber(ctx->model, ctx->d_state[0], pts, npts, p.min_point_num, p.boundary_planes, 10.0f, ctx->d_chamber, ctx->d_nchamber, B, par ? ctx->side[1] : s, ctx->d_chplanes, ctx->d_chon); }
+	if (!tables) { ht_prof_scope ps(ctx, "chamber", s, true); ht_launch_chamber(ctx->model, ctx->d_state[0], ctx->d_chplanes, ctx->d_chon, 10.0f, ctx->d_chamber, ctx->d_nchamber, B, par ? ctx->side[1] : s); }
 	const cloud_records cr = cloud_rec(ctx);
 	{ ht_prof_scope ps(ctx, "cloud_rows", s, true); ht_launch_cloud_rows(ctx->model, ctx->d_state[0], pts, npts, ctx->d_cams, nullptr, 1, 0, 1, p, ctx->d_rows, ctx->d_nrows, B, par ? ctx->side[0] : s, 0.0f, 0.0f, rec_or_rows(ctx, &cr)); }
 	if (tables) { ht_prof_scope ps(ctx, "solve_prep", s, true); solve_prep(ctx, 0, true, true, nullptr, 0, 0.0f, 0, 0, B, par ? ctx->side[0] : s); }
@@ -890,7 +890,8 @@ extern "C" int ht_stage_chamber(ht_ctx *ctx, int which, int B, float *rows, int 
 	hipStream_t s = ctx->stream;
 	const size_t per = (size_t)5 * ctx->model.nb * HT_ROW;
 	HIPCHK(ctx, hipMemsetAsync(ctx->d_chamber, 0, (size_t)B * per * sizeof(float), s));
-	ht_launch_chamber(ctx->model, ctx->d_state[which], ctx->d_pts, ctx->d_npts, ctx->par.min_point_num, ctx->par.boundary_planes, 10.0f, ctx->d_chamber, ctx->d_nchamber, B, s);
+	ht_launch_chamber_planes(ctx->model, ctx->d_pts, ctx->d_npts, ctx->par.min_point_num, ctx->par.boundary_planes, ctx->d_chplanes, ctx->d_chon, B, s);
+	ht_launch_chamber(ctx->model, ctx->d_state[which], ctx->d_chplanes, ctx->d_chon, 10.0f, ctx->d_chamber, ctx->d_nchamber, B, s);
 	HIPCHK(ctx, hipMemcpyAsync(rows, ctx->d_chamber, (size_t)B * per * sizeof(float), hipMemcpyDeviceToHost, s));
 	HIPCHK(ctx, hipMemcpyAsync(nrows, ctx->d_nchamber, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, s));
 	HIPCHK(ctx, hipStreamSynchronize(s));
