@@ -12,12 +12,6 @@
 #include "ht_launch.hpp"
 #include "ht_model_build.hpp"
 
-#define HIPCHK(ctx, call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { (ctx)->err = std::string(#call) + ": " + hipGetErrorString(e_); return HT_ERR_HIP; } } while (0)
-
-#define CHECK_READY(ctx) if (!(ctx)) return HT_ERR_ARG; if (!(ctx)->ready) { (ctx)->err = "context not initialised (ht_create failed)"; return HT_ERR_STATE; } ht_device_guard dev_guard_((ctx)->device)
-#define CHECK_MODEL(ctx) do { if ((ctx)->cnn_only) { (ctx)->err = "this context was created without a hand model (CNN only)"; return HT_ERR_STATE; } } while (0)
-#define CHECK_BATCH(ctx, B) do { if ((B) < 1 || (B) > (ctx)->B) { (ctx)->err = "batch exceeds the capacity given to ht_create"; return HT_ERR_ARG; } } while (0)
-
 // ------------------------------------------------------------------------------------------------- context
 static void default_params(ht_params &p)     // handtrack.h:523-547, physics.h:45-47, physmodel.h:234, handtrack.h:369,450
 {
@@ -27,14 +21,6 @@ static void default_params(ht_params &p)     // handtrack.h:523-547, physics.h:4
 	p.physics_iterations = 16; p.physics_iterations_post = 4; p.physics_use_collision = 1; p.physics_weak_force = 0.4f; p.bone_sum_error_scale = 4.0f; p.unibody_force = 0.1f;
 }
 
-template <class T> static int dev_alloc(ht_ctx *ctx, T **p, size_t n)
-{
-	void *q = nullptr;
-	HIPCHK(ctx, hipMalloc(&q, n * sizeof(T)));
-	ctx->allocs.push_back(q);
-	*p = (T *)q;
-	return HT_OK;
-}
 template <class T> static int dev_upload(ht_ctx *ctx, T **p, const std::vector<T> &h)
 {
 	int r = dev_alloc(ctx, p, h.size() ? h.size() : 1);
@@ -254,9 +240,7 @@ extern "C" int ht_scale(ht_ctx *ctx, float s)
 	HIPCHK(ctx, hipMemcpy(ctx->d_bodyc_rw, ctx->h_bodyc.data(), ctx->h_bodyc.size() * sizeof(float), hipMemcpyHostToDevice));
 	HIPCHK(ctx, hipMemcpy(ctx->d_jointc_rw, ctx->h_jointc.data(), ctx->h_jointc.size() * sizeof(float), hipMemcpyHostToDevice));
 	for (int w = 0; w < 2; w++) ht_launch_scale_state(ctx->d_state[w], nb, ctx->B, s, st);
-	HIPCHK(ctx, hipStreamSynchronize(st));
-	HIPCHK(ctx, hipGetLastError());
-	return HT_OK;
+	return ht_sync_check(ctx, st);
 }
 // CNN::Train (cnn.h:558-580), one SGD step per sample in the order given (train-cnn.cpp:156-162 calls it with alpha = 0.001), on the weights
 // held by the context; ht_cnn_get_weights reads them back in .cnnb order (CNN::saveb cnn.h:591-593).
@@ -413,118 +397,101 @@ extern "C" int ht_model_info(const ht_ctx *ctx, int *nb, int *nj, int *mb) { if 
 
 
 // ------------------------------------------------------------------------------------------------- CNN
-extern "C" int ht_cnn_load_weights(ht_ctx *ctx, const float *w, size_t n)
+// The net comes in two input sizes with the same layer list: 64x64 (conv5 -> 60, pool -> 30 -> 15, conv4 -> 12, pool -> 6, FC 2304 -> 2048 -> 2304, chunked softmax) and
+// 128x128 (BASELINE configs[4] / SURVEY 8d "config 5 (ii)": conv5 -> 124, pool -> 62 -> 31, conv4 -> 28, pool -> 14, FC 12544 -> 2048 -> 2304).  The larger has a second
+// set of weights and activations beside the 64x64 net's, allocated when its weights are first loaded.  One description of either for the loader and the forward pass:
+struct cnn_net { int side; size_t count, fc_in, in_floats; ht_cnn_weights *w; float **d_w; bool *have; float *d_in, *d_act1, *d_act2; const char *prof, *bad_count, *missing; };
+static cnn_net cnn_net_of(ht_ctx *ctx, int side)
 {
-	CHECK_READY(ctx);
-	if (!w || n != HT_CNNB_COUNT) { ctx->err = "weights: expected HT_CNNB_COUNT fp32 values in .cnnb order"; return HT_ERR_ARG; }
-	if (!ctx->d_weights) { int r = dev_alloc(ctx, &ctx->d_weights, (size_t)HT_CNNB_COUNT + 16384 + HT_W4_COUNT); if (r) return r; }
-	HIPCHK(ctx, hipMemcpy(ctx->d_weights, w, n * sizeof(float), hipMemcpyHostToDevice));
+	if (side == 64) return { 64, HT_CNNB_COUNT, 2304, HT_CNN_IN, &ctx->cnnw, &ctx->d_weights, &ctx->have_weights, ctx->d_cnn_in, ctx->d_act1, ctx->d_act2, "cnn",
+	                         "weights: expected HT_CNNB_COUNT fp32 values in .cnnb order", "CNN weights not loaded (ht_cnn_load_weights)" };
+	return { 128, HT_CNNB128_COUNT, 12544, HT_CNN128_IN, &ctx->cnnw128, &ctx->d_weights128, &ctx->have_weights128, ctx->d_in128, ctx->d_act1_128, ctx->d_act2_128, "cnn128",
+	         "weights: expected HT_CNNB128_COUNT fp32 values in .cnnb order", "weights of the 128x128 net not loaded (ht_cnn_load_weights_sized)" };
+}
+static int cnn_load_weights(ht_ctx *ctx, int side, const float *w, size_t n)
+{
+	const cnn_net net = cnn_net_of(ctx, side);
+	if (!w || n != net.count) { ctx->err = net.bad_count; return HT_ERR_ARG; }
+	if (!*net.d_w)
+	{
+		const size_t B = (size_t)ctx->B;
+		int r;
+		if (side == 128 && ((r = dev_alloc(ctx, &ctx->d_in128, B * HT_CNN128_IN)) || (r = dev_alloc(ctx, &ctx->d_act1_128, B * 16 * 31 * 31)) || (r = dev_alloc(ctx, &ctx->d_act2_128, B * 12544)))) return r;
+		if ((r = dev_alloc(ctx, net.d_w, net.count + 16384 + HT_W4_COUNT))) return r;
+	}
+	float *d = *net.d_w;
+	HIPCHK(ctx, hipMemcpy(d, w, n * sizeof(float), hipMemcpyHostToDevice));
 	// conv2 weights repacked to [k][oc], k = (ky*4+kx)*16 + ic  (reference index: kx + 4*(ky + 4*(ic + 16*oc)), cnn.h:45-47)
 	const float *W2 = w + 416;
 	std::vector<float> w2p(16384);
 	for (int oc = 0; oc < 64; oc++) for (int ic = 0; ic < 16; ic++) for (int ky = 0; ky < 4; ky++) for (int kx = 0; kx < 4; kx++)
 		w2p[(size_t)((ky * 4 + kx) * 16 + ic) * 64 + oc] = W2[kx + 4 * (ky + 4 * (ic + 16 * oc))];
-	float *d = ctx->d_weights;
-	HIPCHK(ctx, hipMemcpy(d + HT_CNNB_COUNT, w2p.data(), 16384 * sizeof(float), hipMemcpyHostToDevice));
-	ht_cnn_weights &cw = ctx->cnnw;
-	cw.W1 = d; cw.B1 = d + 400; cw.W2p = d + HT_CNNB_COUNT; cw.B2 = d + 416 + 16384; cw.W3 = d + 416 + 16448; cw.B3 = cw.W3 + (size_t)2304 * 2048; cw.W4 = cw.B3 + 2048; cw.B4 = cw.W4 + (size_t)2048 * 2304;
-	cw.W4p = d + HT_CNNB_COUNT + 16384;
-	ht_launch_pack_w4(cw.W4, d + HT_CNNB_COUNT + 16384, ctx->stream);
+	HIPCHK(ctx, hipMemcpy(d + net.count, w2p.data(), 16384 * sizeof(float), hipMemcpyHostToDevice));
+	ht_cnn_weights &cw = *net.w;
+	cw.W1 = d; cw.B1 = d + 400; cw.W2p = d + net.count; cw.B2 = d + 416 + 16384; cw.W3 = d + 416 + 16448; cw.B3 = cw.W3 + net.fc_in * 2048; cw.W4 = cw.B3 + 2048; cw.B4 = cw.W4 + (size_t)2048 * 2304;
+	cw.W4p = d + net.count + 16384;
+	ht_launch_pack_w4(cw.W4, d + net.count + 16384, ctx->stream);
 	HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-	ctx->have_weights = true;
+	*net.have = true;
 	return HT_OK;
 }
-static int cnn_forward(ht_ctx *ctx, const float *d_in, float *d_out, int B, hipStream_t s)
+extern "C" int ht_cnn_load_weights(ht_ctx *ctx, const float *w, size_t n) { CHECK_READY(ctx); return cnn_load_weights(ctx, 64, w, n); }
+extern "C" int ht_cnn_load_weights_sized(ht_ctx *ctx, int side, const float *w, size_t n)
 {
-	if (!ctx->have_weights) { ctx->err = "CNN weights not loaded (ht_cnn_load_weights)"; return HT_ERR_STATE; }
-	ht_prof_scope p0(ctx, "cnn", s, true);
-	ht_launch_cnn(ctx->cnnw, d_in, ctx->d_act1, ctx->d_act2, ctx->d_act3, ctx->d_logits, B, s);
+	CHECK_READY(ctx);
+	if (side != 64 && side != 128) { ctx->err = "CNN input side must be 64 or 128"; return HT_ERR_ARG; }
+	return cnn_load_weights(ctx, side, w, n);
+}
+static int cnn_forward(ht_ctx *ctx, const cnn_net &net, const float *d_in, float *d_out, int B, hipStream_t s)
+{
+	if (!*net.have) { ctx->err = net.missing; return HT_ERR_STATE; }
+	ht_prof_scope p0(ctx, net.prof, s, true);
+	ht_launch_cnn(*net.w, d_in, net.d_act1, net.d_act2, ctx->d_act3, ctx->d_logits, B, s, net.side);
 	ht_launch_softmax_decode(ctx->d_logits, d_out, nullptr, nullptr, 1, B, s);
 	return HT_OK;
+}
+static int cnn_eval_dev(ht_ctx *ctx, int side, const float *d_in, float *d_out, int B, void *stream)
+{
+	int r = cnn_forward(ctx, cnn_net_of(ctx, side), d_in, d_out, B, ht_user_stream(ctx, stream));
+	if (r) return r;
+	HIPCHK(ctx, hipGetLastError());
+	return HT_OK;
+}
+static int cnn_eval(ht_ctx *ctx, int side, const float *in, float *out, int B)
+{
+	const cnn_net net = cnn_net_of(ctx, side);
+	if (!*net.have) { ctx->err = net.missing; return HT_ERR_STATE; }      // (the larger net's input buffer comes with its weights)
+	HIPCHK(ctx, hipMemcpyAsync(net.d_in, in, (size_t)B * net.in_floats * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+	int r = cnn_forward(ctx, net, net.d_in, ctx->d_cnn_out, B, ctx->stream);
+	if (r) return r;
+	HIPCHK(ctx, hipMemcpyAsync(out, ctx->d_cnn_out, (size_t)B * HT_CNN_OUT * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+	return ht_sync_check(ctx, ctx->stream);
 }
 extern "C" int ht_cnn_eval_dev(ht_ctx *ctx, const float *d_in, float *d_out, int B, void *stream)
 {
 	CHECK_READY(ctx); CHECK_BATCH(ctx, B);
 	if (!d_in || !d_out) return HT_ERR_ARG;
-	int r = cnn_forward(ctx, d_in, d_out, B, ht_user_stream(ctx, stream));
-	if (r) return r;
-	HIPCHK(ctx, hipGetLastError());
-	return HT_OK;
+	return cnn_eval_dev(ctx, 64, d_in, d_out, B, stream);
 }
 extern "C" int ht_cnn_eval(ht_ctx *ctx, const float *in, float *out, int B)
 {
 	CHECK_READY(ctx); CHECK_BATCH(ctx, B);
 	if (!in || !out) return HT_ERR_ARG;
-	HIPCHK(ctx, hipMemcpyAsync(ctx->d_cnn_in, in, (size_t)B * HT_CNN_IN * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
-	int r = cnn_forward(ctx, ctx->d_cnn_in, ctx->d_cnn_out, B, ctx->stream);
-	if (r) return r;
-	HIPCHK(ctx, hipMemcpyAsync(out, ctx->d_cnn_out, (size_t)B * HT_CNN_OUT * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
-	HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-	HIPCHK(ctx, hipGetLastError());
-	return HT_OK;
-}
-
-// The same layer list on a 128x128 input (BASELINE configs[4] / SURVEY 8d "config 5 (ii)"): conv5 -> 124, pool -> 62 -> 31, conv4 -> 28, pool -> 14,
-// FC 12544 -> 2048 -> 2304, chunked softmax.  A second set of weights and activations beside the 64x64 net's, allocated on first use.
-extern "C" int ht_cnn_load_weights_sized(ht_ctx *ctx, int side, const float *w, size_t n)
-{
-	CHECK_READY(ctx);
-	if (side == 64) return ht_cnn_load_weights(ctx, w, n);
-	if (side != 128) { ctx->err = "CNN input side must be 64 or 128"; return HT_ERR_ARG; }
-	if (!w || n != HT_CNNB128_COUNT) { ctx->err = "weights: expected HT_CNNB128_COUNT fp32 values in .cnnb order"; return HT_ERR_ARG; }
-	if (!ctx->d_weights128)
-	{
-		int r;
-		const size_t B = (size_t)ctx->B;
-		if ((r = dev_alloc(ctx, &ctx->d_weights128, (size_t)HT_CNNB128_COUNT + 16384 + HT_W4_COUNT)) || (r = dev_alloc(ctx, &ctx->d_in128, B * HT_CNN128_IN)) ||
-		    (r = dev_alloc(ctx, &ctx->d_act1_128, B * 16 * 31 * 31)) || (r = dev_alloc(ctx, &ctx->d_act2_128, B * 12544))) return r;
-	}
-	float *d = ctx->d_weights128;
-	HIPCHK(ctx, hipMemcpy(d, w, n * sizeof(float), hipMemcpyHostToDevice));
-	const float *W2 = w + 416;
-	std::vector<float> w2p(16384);      // conv2 repacked as for the 64x64 net
-	for (int oc = 0; oc < 64; oc++) for (int ic = 0; ic < 16; ic++) for (int ky = 0; ky < 4; ky++) for (int kx = 0; kx < 4; kx++)
-		w2p[(size_t)((ky * 4 + kx) * 16 + ic) * 64 + oc] = W2[kx + 4 * (ky + 4 * (ic + 16 * oc))];
-	HIPCHK(ctx, hipMemcpy(d + HT_CNNB128_COUNT, w2p.data(), 16384 * sizeof(float), hipMemcpyHostToDevice));
-	ht_cnn_weights &cw = ctx->cnnw128;
-	cw.W1 = d; cw.B1 = d + 400; cw.W2p = d + HT_CNNB128_COUNT; cw.B2 = d + 416 + 16384; cw.W3 = d + 416 + 16448; cw.B3 = cw.W3 + (size_t)12544 * 2048; cw.W4 = cw.B3 + 2048; cw.B4 = cw.W4 + (size_t)2048 * 2304;
-	cw.W4p = d + HT_CNNB128_COUNT + 16384;
-	ht_launch_pack_w4(cw.W4, d + HT_CNNB128_COUNT + 16384, ctx->stream);
-	HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-	ctx->have_weights128 = true;
-	return HT_OK;
-}
-static int cnn128_forward(ht_ctx *ctx, const float *d_in, float *d_out, int B, hipStream_t s)
-{
-	if (!ctx->have_weights128) { ctx->err = "weights of the 128x128 net not loaded (ht_cnn_load_weights_sized)"; return HT_ERR_STATE; }
-	ht_prof_scope p0(ctx, "cnn128", s, true);
-	ht_launch_cnn(ctx->cnnw128, d_in, ctx->d_act1_128, ctx->d_act2_128, ctx->d_act3, ctx->d_logits, B, s, 128);
-	ht_launch_softmax_decode(ctx->d_logits, d_out, nullptr, nullptr, 1, B, s);
-	return HT_OK;
+	return cnn_eval(ctx, 64, in, out, B);
 }
 extern "C" int ht_cnn_eval_sized_dev(ht_ctx *ctx, int side, const float *d_in, float *d_out, int B, void *stream)
 {
 	CHECK_READY(ctx); CHECK_BATCH(ctx, B);
 	if (side == 64) return ht_cnn_eval_dev(ctx, d_in, d_out, B, stream);
 	if (side != 128 || !d_in || !d_out) { ctx->err = "CNN input side must be 64 or 128"; return HT_ERR_ARG; }
-	int r = cnn128_forward(ctx, d_in, d_out, B, ht_user_stream(ctx, stream));
-	if (r) return r;
-	HIPCHK(ctx, hipGetLastError());
-	return HT_OK;
+	return cnn_eval_dev(ctx, 128, d_in, d_out, B, stream);
 }
 extern "C" int ht_cnn_eval_sized(ht_ctx *ctx, int side, const float *in, float *out, int B)
 {
 	CHECK_READY(ctx); CHECK_BATCH(ctx, B);
 	if (side == 64) return ht_cnn_eval(ctx, in, out, B);
 	if (side != 128 || !in || !out) { ctx->err = "CNN input side must be 64 or 128"; return HT_ERR_ARG; }
-	if (!ctx->have_weights128) { ctx->err = "weights of the 128x128 net not loaded (ht_cnn_load_weights_sized)"; return HT_ERR_STATE; }
-	HIPCHK(ctx, hipMemcpyAsync(ctx->d_in128, in, (size_t)B * HT_CNN128_IN * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
-	int r = cnn128_forward(ctx, ctx->d_in128, ctx->d_cnn_out, B, ctx->stream);
-	if (r) return r;
-	HIPCHK(ctx, hipMemcpyAsync(out, ctx->d_cnn_out, (size_t)B * HT_CNN_OUT * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
-	HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-	HIPCHK(ctx, hipGetLastError());
-	return HT_OK;
+	return cnn_eval(ctx, 128, in, out, B);
 }
 
 // ------------------------------------------------------------------------------------------------- stage: prepare / decode
@@ -540,9 +507,7 @@ extern "C" int ht_stage_prepare(ht_ctx *ctx, const uint16_t *depth, const float 
 	if (cnn_in) HIPCHK(ctx, hipMemcpyAsync(cnn_in, ctx->d_cnn_in, (size_t)B * HT_CNN_IN * sizeof(float), hipMemcpyDeviceToHost, s));
 	if (points) HIPCHK(ctx, hipMemcpy2DAsync(points, HT_MAXPTS * sizeof(float4), ctx->d_pts, (size_t)ctx->model.pts_cap * sizeof(float4), HT_MAXPTS * sizeof(float4), B, hipMemcpyDeviceToHost, s));
 	if (npoints) HIPCHK(ctx, hipMemcpyAsync(npoints, ctx->d_npts, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, s));
-	HIPCHK(ctx, hipStreamSynchronize(s));
-	HIPCHK(ctx, hipGetLastError());
-	return HT_OK;
+	return ht_sync_check(ctx, s);
 }
 extern "C" int ht_stage_decode(ht_ctx *ctx, const float *cnn_out, const float *cams, int B, float *analysis)
 {
@@ -553,9 +518,7 @@ extern "C" int ht_stage_decode(ht_ctx *ctx, const float *cnn_out, const float *c
 	HIPCHK(ctx, hipMemcpyAsync(ctx->d_cams, cams, (size_t)B * HT_CAM * sizeof(float), hipMemcpyHostToDevice, s));
 	ht_launch_softmax_decode(nullptr, ctx->d_cnn_out, ctx->d_cams, ctx->d_analysis, 0, B, s);
 	HIPCHK(ctx, hipMemcpyAsync(analysis, ctx->d_analysis, (size_t)B * HT_ANALYSIS * sizeof(float), hipMemcpyDeviceToHost, s));
-	HIPCHK(ctx, hipStreamSynchronize(s));
-	HIPCHK(ctx, hipGetLastError());
-	return HT_OK;
+	return ht_sync_check(ctx, s);
 }
 
 // ------------------------------------------------------------------------------------------------- profiling hooks
@@ -626,7 +589,7 @@ int ht_reserve_points_locked(ht_ctx *ctx, int points)
 	HIPCHK(ctx, ht_sync_all(ctx));
 	const bool had_voxel = ctx->d_ptsv != nullptr;
 	void *old[5] = { ctx->d_pts, ctx->d_rows, ctx->d_scratch, ctx->d_ptsv, ctx->d_rowbody };
-	for (void *o : old) if (o) { for (auto &q : ctx->allocs) if (q == o) { q = ctx->allocs.back(); ctx->allocs.pop_back(); break; } (void)hipFree(o); }
+	for (void *o : old) drop_alloc(ctx, o);
 	ctx->d_pts = nullptr; ctx->d_rows = nullptr; ctx->d_scratch = nullptr; ctx->d_ptsv = nullptr; ctx->d_rowbody = nullptr; ctx->model.pts_cap = 0;
 	int r;
 	if ((r = dev_alloc(ctx, &ctx->d_pts, B * cap))) return r;

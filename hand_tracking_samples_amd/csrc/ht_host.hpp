@@ -41,7 +41,7 @@ struct ht_ctx
 	// device buffers (capacity B frames / tracker slots)
 	float *d_weights = nullptr;
 	uint16_t *d_depth = nullptr;
-	uint16_t *d_seg_tiles = nullptr, *d_frames = nullptr; float *d_frame_cams = nullptr, *d_frame_cams_in = nullptr; int *d_overflow = nullptr; size_t frames_cap = 0;      // full-size frame path (ht_update_frames)
+	uint16_t *d_seg_tiles = nullptr, *d_frames = nullptr; float *d_frame_cams = nullptr, *d_frame_cams_in = nullptr; int *d_overflow = nullptr; size_t frames_cap = 0;      // full-size frame path (ht_update_frames); d_frames holds the largest frame size seen (dev_grow)
 	float *d_cams = nullptr, *d_cnn_in = nullptr, *d_act1 = nullptr, *d_act2 = nullptr, *d_act3 = nullptr, *d_logits = nullptr, *d_cnn_out = nullptr, *d_analysis = nullptr;
 	float4 *d_pts = nullptr; int *d_npts = nullptr;
 	float4 *d_ptsv = nullptr; int *d_nptsv = nullptr;          // the main-thread cloud when subsample_voxel is set (allocated on first use; d_pts stays the CNN job's cloud)
@@ -71,14 +71,50 @@ struct ht_ctx
 	float *d_scratch = nullptr;                                  // solver row records [B][pts_cap + 5*nb + 32][20] (ht_quad.hpp)
 	float *d_poses_out = nullptr, *d_start = nullptr;
 	float *d_stage = nullptr;                                    // staging for host<->device state copies
-	// caller-built constraint rows (ht_fit_rows / ht_physics_update), allocated on first use and grown to the largest call
+	// caller-built constraint rows (ht_fit_rows / ht_physics_update), allocated on first use and grown to the largest call (dev_grow)
 	float *d_user_lin = nullptr; unsigned short *d_user_pos = nullptr; float *d_user_ang = nullptr; int *d_user_n = nullptr;      // [B][lin_cap][HT_ROW], [B][lin_cap], [B][ang_cap][HT_AROW], [4][B]
 	int user_lin_cap = 0, user_ang_cap = 0;
 	ht_comm_state *comm = nullptr;                               // multi-GPU pose gather (ht_comm_init), null on a single-GPU host
-	void *d_render = nullptr; size_t render_cap = 0;             // ht_render_depth's staging (poses, cameras, frames, body labels), grown to the largest call; in `allocs`
-	void *d_labels = nullptr; size_t labels_cap = 0;             // ht_expected_cnn_batch's staging (poses, cameras, labels, image points, key angles), grown to the largest call; in `allocs`
+	char *d_render = nullptr; size_t render_cap = 0;             // ht_render_depth's staging (poses, cameras, frames, body labels), grown to the largest call (dev_grow)
+	char *d_labels = nullptr; size_t labels_cap = 0;             // ht_expected_cnn_batch's staging (poses, cameras, labels, image points, key angles), grown to the largest call (dev_grow)
 	std::vector<float4> render_planes; std::vector<float> render_radii;      // the hull planes ht_render_depth last derived its per-body cull radii from, and those radii (2 per body)
 };
+
+// what every entry point of the C-ABI starts with and wraps its HIP calls in
+#define HIPCHK(ctx, call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { (ctx)->err = std::string(#call) + ": " + hipGetErrorString(e_); return HT_ERR_HIP; } } while (0)
+#define CHECK_READY(ctx) if (!(ctx)) return HT_ERR_ARG; if (!(ctx)->ready) { (ctx)->err = "context not initialised (ht_create failed)"; return HT_ERR_STATE; } ht_device_guard dev_guard_((ctx)->device)
+#define CHECK_MODEL(ctx) do { if ((ctx)->cnn_only) { (ctx)->err = "this context was created without a hand model (CNN only)"; return HT_ERR_STATE; } } while (0)
+#define CHECK_BATCH(ctx, B) do { if ((B) < 1 || (B) > (ctx)->B) { (ctx)->err = "batch exceeds the capacity given to ht_create"; return HT_ERR_ARG; } } while (0)
+
+// Device memory of a context.  dev_alloc: n elements, listed in `allocs` (ht_destroy frees the list).  drop_alloc: frees one of them now.  dev_grow: a buffer that follows
+// the largest call -- the replacement is allocated FIRST (when that fails the context keeps its old, valid buffer and capacity), then the outgrown one is freed (hipFree
+// waits for the device, so nothing can still be reading it); its contents are not carried over.
+template <class T> static inline int dev_alloc(ht_ctx *ctx, T **p, size_t n)
+{
+	void *q = nullptr;
+	HIPCHK(ctx, hipMalloc(&q, n * sizeof(T)));
+	ctx->allocs.push_back(q);
+	*p = (T *)q;
+	return HT_OK;
+}
+static inline void drop_alloc(ht_ctx *ctx, void *o) { if (!o) return; for (auto &q : ctx->allocs) if (q == o) { q = ctx->allocs.back(); ctx->allocs.pop_back(); break; } (void)hipFree(o); }
+template <class T, class C> static inline int dev_grow(ht_ctx *ctx, T **p, C *cap, size_t want, size_t per = 1)
+{
+	if ((size_t)*cap >= want) return HT_OK;
+	T *q = nullptr;
+	const int r = dev_alloc(ctx, &q, want * per);
+	if (r) return r;
+	drop_alloc(ctx, *p);
+	*p = q; *cap = (C)want;
+	return HT_OK;
+}
+// the end of a synchronous entry point: wait for the stream, then report what its launches left behind
+static inline int ht_sync_check(ht_ctx *ctx, hipStream_t s)
+{
+	HIPCHK(ctx, hipStreamSynchronize(s));
+	HIPCHK(ctx, hipGetLastError());
+	return HT_OK;
+}
 
 struct ht_prof_scope
 {

@@ -121,9 +121,6 @@ __global__ __launch_bounds__(LB_THREADS) void k_expected_cnn(const float *__rest
 	}
 }
 
-#define CHECK_READY(ctx) if (!(ctx)) return HT_ERR_ARG; if (!(ctx)->ready) { (ctx)->err = "context not initialised (ht_create failed)"; return HT_ERR_STATE; } ht_device_guard dev_guard_((ctx)->device)
-#define HIPCHK(ctx, call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { (ctx)->err = std::string(#call) + ": " + hipGetErrorString(e_); return HT_ERR_HIP; } } while (0)
-
 static int lb_check_args(ht_ctx *ctx, const void *poses, const void *cams, int B, const void *expected)
 {
 	if (!poses || !cams || !expected || B < 0) { ctx->err = "ht_expected_cnn: bad argument"; return HT_ERR_ARG; }
@@ -157,16 +154,8 @@ extern "C" int ht_expected_cnn_batch(ht_ctx *ctx, const float *poses, const floa
 	auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
 	const size_t o_cams = up(n * nb * HT_POSE * sizeof(float)), o_exp = o_cams + up(n * HT_CAM * sizeof(float)), o_ip = o_exp + up(n * HT_CNN_OUT * sizeof(float));
 	const size_t o_vals = o_ip + up(n * 16 * sizeof(float)), bytes = o_vals + n * 16 * sizeof(float);
-	if (bytes > ctx->labels_cap)
-	{
-		void *nbuf = nullptr;
-		HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-		HIPCHK(ctx, hipMalloc(&nbuf, bytes));      // the replacement first: on failure the context keeps the old buffer
-		for (auto &q : ctx->allocs) if (q == ctx->d_labels) { q = ctx->allocs.back(); ctx->allocs.pop_back(); break; }
-		if (ctx->d_labels) (void)hipFree(ctx->d_labels);
-		ctx->allocs.push_back(nbuf); ctx->d_labels = nbuf; ctx->labels_cap = bytes;
-	}
-	char *base = (char *)ctx->d_labels;
+	{ const int r = dev_grow(ctx, &ctx->d_labels, &ctx->labels_cap, bytes); if (r) return r; }
+	char *base = ctx->d_labels;
 	float *d_poses = (float *)base, *d_cams = (float *)(base + o_cams), *d_exp = (float *)(base + o_exp);
 	float *d_ip = image_points ? (float *)(base + o_ip) : nullptr, *d_vals = vals ? (float *)(base + o_vals) : nullptr;
 	hipStream_t s = ctx->stream;

@@ -215,9 +215,6 @@ static void rt_fill_model(ht_ctx *ctx, rt_model &m)
 	for (int b = 0; b < m.nb; b++) { m.rad[b] = ctx->render_radii[2 * b]; m.hin[b] = ctx->render_radii[2 * b + 1]; }
 }
 
-#define CHECK_READY(ctx) if (!(ctx)) return HT_ERR_ARG; if (!(ctx)->ready) { (ctx)->err = "context not initialised (ht_create failed)"; return HT_ERR_STATE; } ht_device_guard dev_guard_((ctx)->device)
-#define HIPCHK(ctx, call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { (ctx)->err = std::string(#call) + ": " + hipGetErrorString(e_); return HT_ERR_HIP; } } while (0)
-
 static int rt_check_args(ht_ctx *ctx, const void *poses, const void *cams, const void *depth, int w, int h, float far, int B)
 {
 	if (!poses || !cams || !depth || w < 1 || h < 1 || w > 4096 || h > 4096 || !(far > 0.0f) || B < 0) { ctx->err = "ht_render_depth: bad argument"; return HT_ERR_ARG; }
@@ -255,16 +252,8 @@ extern "C" int ht_render_depth(ht_ctx *ctx, const float *poses, const float *cam
 	const size_t nb = (size_t)ctx->model.nb, npx = (size_t)B * w * h;
 	const size_t o_cams = ((size_t)B * nb * HT_POSE * sizeof(float) + 255) & ~(size_t)255, o_depth = (o_cams + (size_t)B * HT_CAM * sizeof(float) + 255) & ~(size_t)255;
 	const size_t o_body = (o_depth + npx * sizeof(uint16_t) + 255) & ~(size_t)255, bytes = o_body + (body ? npx : 0);
-	if (bytes > ctx->render_cap)
-	{
-		void *nbuf = nullptr;
-		HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-		HIPCHK(ctx, hipMalloc(&nbuf, bytes));      // the replacement first: on failure the context keeps the old buffer
-		for (auto &q : ctx->allocs) if (q == ctx->d_render) { q = ctx->allocs.back(); ctx->allocs.pop_back(); break; }
-		if (ctx->d_render) (void)hipFree(ctx->d_render);
-		ctx->allocs.push_back(nbuf); ctx->d_render = nbuf; ctx->render_cap = bytes;
-	}
-	char *base = (char *)ctx->d_render;
+	{ const int r = dev_grow(ctx, &ctx->d_render, &ctx->render_cap, bytes); if (r) return r; }
+	char *base = ctx->d_render;
 	float *d_poses = (float *)base, *d_cams = (float *)(base + o_cams);
 	uint16_t *d_depth = (uint16_t *)(base + o_depth); int8_t *d_body = body ? (int8_t *)(base + o_body) : nullptr;
 	hipStream_t s = ctx->stream;

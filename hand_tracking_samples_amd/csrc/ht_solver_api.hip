@@ -6,10 +6,6 @@
 #include "ht_host.hpp"
 #include "ht_launch.hpp"
 
-#define HIPCHK(ctx, call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { (ctx)->err = std::string(#call) + ": " + hipGetErrorString(e_); return HT_ERR_HIP; } } while (0)
-#define CHECK_READY(ctx) if (!(ctx)) return HT_ERR_ARG; if (!(ctx)->ready) { (ctx)->err = "context not initialised (ht_create failed)"; return HT_ERR_STATE; } ht_device_guard dev_guard_((ctx)->device)
-#define CHECK_MODEL(ctx) do { if ((ctx)->cnn_only) { (ctx)->err = "this context was created without a hand model (CNN only)"; return HT_ERR_STATE; } } while (0)
-#define CHECK_BATCH(ctx, B) do { if ((B) < 1 || (B) > (ctx)->B) { (ctx)->err = "batch exceeds the capacity given to ht_create"; return HT_ERR_ARG; } } while (0)
 #define CHECK_RANGE(ctx, first, n) do { if ((first) < 0 || (n) < 1 || (first) + (n) > (ctx)->B) { (ctx)->err = "slot range exceeds the capacity given to ht_create"; return HT_ERR_ARG; } } while (0)
 
 static int scratch_stride(const ht_ctx *ctx) { return (int)ht_scratch_rows((size_t)ctx->model.pts_cap, (size_t)ctx->model.nb); }
@@ -17,10 +13,8 @@ static int scratch_stride(const ht_ctx *ctx) { return (int)ht_scratch_rows((size
 // ---- building blocks ------------------------------------------------------------------------------------------------
 static int dev_alloc_points(ht_ctx *ctx)      // the second cloud of a context that uses voxel sub-sampling
 {
-	void *a = nullptr, *b = nullptr;
-	HIPCHK(ctx, hipMalloc(&a, (size_t)ctx->B * ctx->model.pts_cap * sizeof(float4))); ctx->allocs.push_back(a); ctx->d_ptsv = (float4 *)a;
-	if (!ctx->d_nptsv) { HIPCHK(ctx, hipMalloc(&b, (size_t)ctx->B * sizeof(int))); ctx->allocs.push_back(b); ctx->d_nptsv = (int *)b; }
-	return HT_OK;
+	const int r = dev_alloc(ctx, &ctx->d_ptsv, (size_t)ctx->B * ctx->model.pts_cap);
+	return r || ctx->d_nptsv ? r : dev_alloc(ctx, &ctx->d_nptsv, (size_t)ctx->B);
 }
 static cloud_records cloud_rec(ht_ctx *ctx) { cloud_records r = { ctx->d_scratch, scratch_stride(ctx), ctx->d_rowbody, ctx->phys.deltaT }; return r; }
 // the exact-order instantiation of the solver (ht_debug_solver_build 5, tests only) takes the cloud rows in the reference's layout (ctx->d_rows) instead of records
@@ -260,12 +254,10 @@ static int run_update_(ht_ctx *ctx, const uint16_t *d_depth, const float *d_cams
 	const float *img_cams = ctx->d_cams;
 	if (fs)
 	{
-		if (!ctx->d_seg_tiles)
+		if (!ctx->d_seg_tiles)      // the three buffers of the full-size path, the one this asks for last
 		{
-			void *a = nullptr, *b = nullptr, *c = nullptr;
-			HIPCHK(ctx, hipMalloc(&a, (size_t)ctx->B * 4096 * sizeof(uint16_t))); ctx->allocs.push_back(a); ctx->d_seg_tiles = (uint16_t *)a;
-			HIPCHK(ctx, hipMalloc(&b, (size_t)ctx->B * HT_CAM * sizeof(float))); ctx->allocs.push_back(b); ctx->d_frame_cams = (float *)b;
-			HIPCHK(ctx, hipMalloc(&c, sizeof(int))); ctx->allocs.push_back(c); ctx->d_overflow = (int *)c;
+			int r;
+			if ((r = dev_alloc(ctx, &ctx->d_frame_cams, (size_t)ctx->B * HT_CAM)) || (r = dev_alloc(ctx, &ctx->d_overflow, 1)) || (r = dev_alloc(ctx, &ctx->d_seg_tiles, (size_t)ctx->B * 4096))) return r;
 		}
 		HIPCHK(ctx, hipMemcpyAsync(ctx->d_frame_cams, d_cams, (size_t)B * HT_CAM * sizeof(float), hipMemcpyDeviceToDevice, s));
 		HIPCHK(ctx, hipMemsetAsync(ctx->d_overflow, 0, sizeof(int), s));
@@ -320,6 +312,8 @@ static int run_update_(ht_ctx *ctx, const uint16_t *d_depth, const float *d_cams
 	float *cnn_out = d_cnn_out ? d_cnn_out : ctx->d_cnn_out;
 	static const bool no_overlap = ht_tuning_env("HT_NO_OVERLAP");      // timing experiments (-DHT_TUNING builds only)
 	const bool overlap = !no_overlap && !ctx->profile_phases && p.steps >= 1 && p.steps_cloudstart >= 1 && !p.angles_only && ctx->solver_build != 5;
+	ht_fit_after dec; memset(&dec, 0, sizeof dec);      // the reset decision that FitError of the carried pose ends with (handtrack.h:706)
+	dec.mode = 1; dec.reset_thr = p.full_reset_on_error; dec.angles_only = p.angles_only; dec.flags = ctx->d_flags; dec.nflags = ctx->d_nflags; dec.list = ctx->d_flist; dec.nlist = ctx->d_nflist; dec.nreset = ctx->d_nreset;
 	if (overlap)
 	{
 		// Nothing on this side branch needs the CNN: the error of the carried pose and the reset decision only read the point cloud and the
@@ -330,8 +324,6 @@ static int run_update_(ht_ctx *ctx, const uint16_t *d_depth, const float *d_cams
 		update_planes(t);
 		contact_orders(ctx, B, t);
 		if (mode == UPD_FULL && !(d_start && !fs)) ht_launch_set_pose(ctx->d_state[1], ctx->d_state[0], nb, B, 2, t);     // othermodel.SetPose(handmodel.GetPose()) handtrack.h:757 (both were just seeded with the same pose otherwise)
-		ht_fit_after dec; memset(&dec, 0, sizeof dec);
-		dec.mode = 1; dec.reset_thr = p.full_reset_on_error; dec.angles_only = p.angles_only; dec.flags = ctx->d_flags; dec.nflags = ctx->d_nflags; dec.list = ctx->d_flist; dec.nlist = ctx->d_nflist; dec.nreset = ctx->d_nreset;
 		ht_launch_fit_error(ctx->model, ctx->d_state[0], ctx->d_pts, ctx->d_npts, d_depth, img_cams, iw, ih, p.bone_sum_error_scale, ctx->d_err_old, B, t, &dec);      // with the reset decision (handtrack.h:706)
 	}
 	if (!overlap) { contact_orders(ctx, B, s); update_planes(s); }
@@ -416,8 +408,6 @@ static int run_update_(ht_ctx *ctx, const uint16_t *d_depth, const float *d_cams
 	else
 	{
 		if (mode == UPD_FULL) ht_launch_set_pose(ctx->d_state[1], ctx->d_state[0], nb, B, 2, s);     // othermodel.SetPose(handmodel.GetPose()) handtrack.h:757
-		ht_fit_after dec; memset(&dec, 0, sizeof dec);
-		dec.mode = 1; dec.reset_thr = p.full_reset_on_error; dec.angles_only = p.angles_only; dec.flags = ctx->d_flags; dec.nflags = ctx->d_nflags; dec.list = ctx->d_flist; dec.nlist = ctx->d_nflist; dec.nreset = ctx->d_nreset;
 		{ ht_prof_scope ps(ctx, "fit_error", s, true); ht_launch_fit_error(ctx->model, ctx->d_state[0], ctx->d_pts, ctx->d_npts, d_depth, img_cams, iw, ih, p.bone_sum_error_scale, ctx->d_err_old, B, s, &dec); }
 		reset_path(ctx, true, p.steps_unibody, B, s, s);
 		multistep(ctx, B, s);
@@ -452,9 +442,7 @@ extern "C" int ht_tracker_reset(ht_ctx *ctx, int first, int n, const float *pose
 	HIPCHK(ctx, hipMemcpyAsync(ctx->d_stage, poses, (size_t)n * nb * HT_POSE * sizeof(float), hipMemcpyHostToDevice, s));
 	for (int w = 0; w < 2; w++) ht_launch_set_pose(ctx->d_state[w] + (size_t)first * nb * HT_STATE_STRIDE, ctx->d_stage, nb, n, 1, s);
 	ht_launch_clear_flags(ctx->d_prev_err + first, ctx->d_initializing + first, n, s);
-	HIPCHK(ctx, hipStreamSynchronize(s));
-	HIPCHK(ctx, hipGetLastError());
-	return HT_OK;
+	return ht_sync_check(ctx, s);
 }
 extern "C" int ht_get_state(ht_ctx *ctx, int which, int first, int n, float *state)
 {
@@ -464,9 +452,7 @@ extern "C" int ht_get_state(ht_ctx *ctx, int which, int first, int n, float *sta
 	const int nb = ctx->model.nb;
 	ht_launch_get_state(ctx->d_state[which] + (size_t)first * nb * HT_STATE_STRIDE, ctx->d_stage, nb, n, s);
 	HIPCHK(ctx, hipMemcpyAsync(state, ctx->d_stage, (size_t)n * nb * HT_STATE * sizeof(float), hipMemcpyDeviceToHost, s));
-	HIPCHK(ctx, hipStreamSynchronize(s));
-	HIPCHK(ctx, hipGetLastError());
-	return HT_OK;
+	return ht_sync_check(ctx, s);
 }
 extern "C" int ht_set_state(ht_ctx *ctx, int which, int first, int n, const float *state)
 {
@@ -476,9 +462,7 @@ extern "C" int ht_set_state(ht_ctx *ctx, int which, int first, int n, const floa
 	const int nb = ctx->model.nb;
 	HIPCHK(ctx, hipMemcpyAsync(ctx->d_stage, state, (size_t)n * nb * HT_STATE * sizeof(float), hipMemcpyHostToDevice, s));
 	ht_launch_set_pose(ctx->d_state[which] + (size_t)first * nb * HT_STATE_STRIDE, ctx->d_stage, nb, n, 3, s);
-	HIPCHK(ctx, hipStreamSynchronize(s));
-	HIPCHK(ctx, hipGetLastError());
-	return HT_OK;
+	return ht_sync_check(ctx, s);
 }
 extern "C" int ht_get_tracker_flags(ht_ctx *ctx, int first, int n, float *prev_frame_error, int *initializing)
 {
@@ -504,21 +488,54 @@ extern "C" int ht_update_dev(ht_ctx *ctx, const uint16_t *d_depth, const float *
 	HIPCHK(ctx, hipGetLastError());
 	return HT_OK;
 }
+// ---- the synchronous update calls: frames up, run_update, results down --------------------------------------------------
+// Upload: a 64x64 tile goes to d_depth / d_cams, a frame of any other size to d_frames (which follows the largest frame size seen) / d_frame_cams_in.
+// *d_in, *d_cin: what run_update takes.  `depth`, `cams`: host memory (ht_job_start: its pinned copy).
+static int stage_frames(ht_ctx *ctx, const uint16_t *depth, const float *cams, int w, int h, int B, hipStream_t s, const uint16_t **d_in, const float **d_cin)
+{
+	uint16_t *dd = ctx->d_depth; float *dc = ctx->d_cams;
+	if (!(w == 64 && h == 64))
+	{
+		int r;
+		if ((r = dev_grow(ctx, &ctx->d_frames, &ctx->frames_cap, (size_t)ctx->B * w * h))) return r;
+		if (!ctx->d_frame_cams_in && (r = dev_alloc(ctx, &ctx->d_frame_cams_in, (size_t)ctx->B * HT_CAM))) return r;
+		dd = ctx->d_frames; dc = ctx->d_frame_cams_in;
+	}
+	HIPCHK(ctx, hipMemcpyAsync(dd, depth, (size_t)B * w * h * sizeof(uint16_t), hipMemcpyHostToDevice, s));
+	HIPCHK(ctx, hipMemcpyAsync(dc, cams, (size_t)B * HT_CAM * sizeof(float), hipMemcpyHostToDevice, s));
+	*d_in = dd; *d_cin = dc;
+	return HT_OK;
+}
+// Download: the results the caller asked for (accepted as 0 / 1), the stream drained.  `frames_entry`: the call ran on full-size frames, whose clouds the point capacity
+// can cut short (d_overflow counts such frames): that is an error, reported under the entry point's name.
+static int finish_sync(ht_ctx *ctx, int B, hipStream_t s, float *poses_out, float *cnn_out, int *accepted_out, const char *frames_entry)
+{
+	if (poses_out) HIPCHK(ctx, hipMemcpyAsync(poses_out, ctx->d_poses_out, (size_t)B * ctx->model.nb * HT_POSE * sizeof(float), hipMemcpyDeviceToHost, s));
+	if (accepted_out) HIPCHK(ctx, hipMemcpyAsync(accepted_out, ctx->d_accepted, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, s));
+	if (cnn_out) HIPCHK(ctx, hipMemcpyAsync(cnn_out, ctx->d_cnn_out, (size_t)B * HT_CNN_OUT * sizeof(float), hipMemcpyDeviceToHost, s));
+	{ const int r = ht_sync_check(ctx, s); if (r) return r; }
+	if (accepted_out) for (int b = 0; b < B; b++) accepted_out[b] = accepted_out[b] != 0;
+	int over = 0;
+	if (frames_entry) HIPCHK(ctx, hipMemcpy(&over, ctx->d_overflow, sizeof(int), hipMemcpyDeviceToHost));
+	if (over) { ctx->err = std::string(frames_entry) + ": " + std::to_string(over) + " frame(s) have more in-range points than the context's point capacity holds; their result is not the reference's"; return HT_ERR_ARG; }
+	return HT_OK;
+}
+// `fs` of 64x64 pixels: the tile path (run_update without a frame_src).  `frames_entry`: finish_sync's, for frames of another size.
+static int update_sync(ht_ctx *ctx, const uint16_t *depth, const float *cams, const frame_src &fs, int mode, int B, float *poses_out, int *accepted_out, float *cnn_out, const char *frames_entry)
+{
+	hipStream_t s = ctx->stream;
+	const bool tile = fs.w == 64 && fs.h == 64;
+	const uint16_t *d_in; const float *d_cin;
+	int r = stage_frames(ctx, depth, cams, fs.w, fs.h, B, s, &d_in, &d_cin);
+	if (!r) r = run_update(ctx, d_in, d_cin, nullptr, B, ctx->d_poses_out, nullptr, s, tile ? nullptr : &fs, mode);
+	return r ? r : finish_sync(ctx, B, s, poses_out, cnn_out, accepted_out, tile ? nullptr : frames_entry);
+}
 extern "C" int ht_update_sync(ht_ctx *ctx, const uint16_t *depth, const float *cams, int B, float *poses_out, float *cnn_out)
 {
 	CHECK_READY(ctx); CHECK_MODEL(ctx); CHECK_BATCH(ctx, B);
 	if (!depth || !cams || !poses_out) return HT_ERR_ARG;
-	hipStream_t s = ctx->stream;
-	const int nb = ctx->model.nb;
-	HIPCHK(ctx, hipMemcpyAsync(ctx->d_depth, depth, (size_t)B * 4096 * sizeof(uint16_t), hipMemcpyHostToDevice, s));
-	HIPCHK(ctx, hipMemcpyAsync(ctx->d_cams, cams, (size_t)B * HT_CAM * sizeof(float), hipMemcpyHostToDevice, s));
-	int r = run_update(ctx, ctx->d_depth, ctx->d_cams, nullptr, B, ctx->d_poses_out, nullptr, s);
-	if (r) return r;
-	HIPCHK(ctx, hipMemcpyAsync(poses_out, ctx->d_poses_out, (size_t)B * nb * HT_POSE * sizeof(float), hipMemcpyDeviceToHost, s));
-	if (cnn_out) HIPCHK(ctx, hipMemcpyAsync(cnn_out, ctx->d_cnn_out, (size_t)B * HT_CNN_OUT * sizeof(float), hipMemcpyDeviceToHost, s));
-	HIPCHK(ctx, hipStreamSynchronize(s));
-	HIPCHK(ctx, hipGetLastError());
-	return HT_OK;
+	const frame_src fs = { 64, 64, 0.0f, 0 };
+	return update_sync(ctx, depth, cams, fs, UPD_FULL, B, poses_out, nullptr, cnn_out, nullptr);
 }
 
 // HandTracker::update on frames of any size up to 320x240 (handtrack.h:693-785): segmentation for the CNN inside, the cloud of the full frame
@@ -592,30 +609,9 @@ extern "C" int ht_update_frames_sync(ht_ctx *ctx, const uint16_t *depth, const f
 {
 	CHECK_READY(ctx); CHECK_MODEL(ctx); CHECK_BATCH(ctx, B);
 	if (!depth || !cams || !poses_out) return HT_ERR_ARG;
-	if (w == 64 && h == 64) return ht_update_sync(ctx, depth, cams, B, poses_out, cnn_out);
 	if (!frames_args_ok(ctx, w, h)) return HT_ERR_ARG;
-	hipStream_t s = ctx->stream;
-	const int nb = ctx->model.nb;
-	const size_t npx = (size_t)w * h;
-	if (ctx->frames_cap < (size_t)B * npx)
-	{
-		void *a = nullptr;
-		HIPCHK(ctx, hipMalloc(&a, (size_t)ctx->B * npx * sizeof(uint16_t))); ctx->allocs.push_back(a); ctx->d_frames = (uint16_t *)a; ctx->frames_cap = (size_t)ctx->B * npx;
-	}
-	if (!ctx->d_frame_cams_in) { void *a = nullptr; HIPCHK(ctx, hipMalloc(&a, (size_t)ctx->B * HT_CAM * sizeof(float))); ctx->allocs.push_back(a); ctx->d_frame_cams_in = (float *)a; }
-	HIPCHK(ctx, hipMemcpyAsync(ctx->d_frames, depth, (size_t)B * npx * sizeof(uint16_t), hipMemcpyHostToDevice, s));
-	HIPCHK(ctx, hipMemcpyAsync(ctx->d_frame_cams_in, cams, (size_t)B * HT_CAM * sizeof(float), hipMemcpyHostToDevice, s));
 	const frame_src fs = { w, h, segment_scale, 0 };
-	int r = run_update(ctx, ctx->d_frames, ctx->d_frame_cams_in, nullptr, B, ctx->d_poses_out, nullptr, s, &fs);
-	if (r) return r;
-	HIPCHK(ctx, hipMemcpyAsync(poses_out, ctx->d_poses_out, (size_t)B * nb * HT_POSE * sizeof(float), hipMemcpyDeviceToHost, s));
-	if (cnn_out) HIPCHK(ctx, hipMemcpyAsync(cnn_out, ctx->d_cnn_out, (size_t)B * HT_CNN_OUT * sizeof(float), hipMemcpyDeviceToHost, s));
-	HIPCHK(ctx, hipStreamSynchronize(s));
-	HIPCHK(ctx, hipGetLastError());
-	int over = 0;
-	HIPCHK(ctx, hipMemcpy(&over, ctx->d_overflow, sizeof(int), hipMemcpyDeviceToHost));
-	if (over) { ctx->err = "ht_update_frames: " + std::to_string(over) + " frame(s) have more in-range points than the context's point capacity holds; their result is not the reference's"; return HT_ERR_ARG; }
-	return HT_OK;
+	return update_sync(ctx, depth, cams, fs, UPD_FULL, B, poses_out, nullptr, cnn_out, "ht_update_frames");
 }
 
 // BASELINE configs[4] end to end (SURVEY 8d "config 5 (i)-(iii)"): HandTracker::update on side x side frames that are their own segment, evaluated by the net of
@@ -638,23 +634,9 @@ extern "C" int ht_update_direct_sync(ht_ctx *ctx, const uint16_t *depth, const f
 {
 	CHECK_READY(ctx); CHECK_MODEL(ctx); CHECK_BATCH(ctx, B);
 	if (!depth || !cams || !poses_out) return HT_ERR_ARG;
-	if (side == 64) return ht_update_sync(ctx, depth, cams, B, poses_out, cnn_out);
-	if (side != 128) { ctx->err = "ht_update_direct: CNN input side must be 64 or 128"; return HT_ERR_ARG; }
-	hipStream_t s = ctx->stream;
-	const int nb = ctx->model.nb;
-	const size_t npx = (size_t)side * side;
-	if (ctx->frames_cap < (size_t)B * npx) { void *a = nullptr; HIPCHK(ctx, hipMalloc(&a, (size_t)ctx->B * npx * sizeof(uint16_t))); ctx->allocs.push_back(a); ctx->d_frames = (uint16_t *)a; ctx->frames_cap = (size_t)ctx->B * npx; }
-	if (!ctx->d_frame_cams_in) { void *a = nullptr; HIPCHK(ctx, hipMalloc(&a, (size_t)ctx->B * HT_CAM * sizeof(float))); ctx->allocs.push_back(a); ctx->d_frame_cams_in = (float *)a; }
-	HIPCHK(ctx, hipMemcpyAsync(ctx->d_frames, depth, (size_t)B * npx * sizeof(uint16_t), hipMemcpyHostToDevice, s));
-	HIPCHK(ctx, hipMemcpyAsync(ctx->d_frame_cams_in, cams, (size_t)B * HT_CAM * sizeof(float), hipMemcpyHostToDevice, s));
+	if (side != 64 && side != 128) { ctx->err = "ht_update_direct: CNN input side must be 64 or 128"; return HT_ERR_ARG; }
 	const frame_src fs = { side, side, 0.0f, side };
-	int r = run_update(ctx, ctx->d_frames, ctx->d_frame_cams_in, nullptr, B, ctx->d_poses_out, nullptr, s, &fs);
-	if (r) return r;
-	HIPCHK(ctx, hipMemcpyAsync(poses_out, ctx->d_poses_out, (size_t)B * nb * HT_POSE * sizeof(float), hipMemcpyDeviceToHost, s));
-	if (cnn_out) HIPCHK(ctx, hipMemcpyAsync(cnn_out, ctx->d_cnn_out, (size_t)B * HT_CNN_OUT * sizeof(float), hipMemcpyDeviceToHost, s));
-	HIPCHK(ctx, hipStreamSynchronize(s));
-	HIPCHK(ctx, hipGetLastError());
-	return HT_OK;
+	return update_sync(ctx, depth, cams, fs, UPD_FULL, B, poses_out, nullptr, cnn_out, nullptr);      // a frame that is its own segment: the point capacity follows its size
 }
 
 // HandTracker::update_cnn_model (handtrack.h:734-741) and kickstart (:743-746) for B trackers, frames of any supported size
@@ -663,37 +645,9 @@ extern "C" int ht_update_cnn_model_sync(ht_ctx *ctx, const uint16_t *depth, cons
 {
 	CHECK_READY(ctx); CHECK_MODEL(ctx); CHECK_BATCH(ctx, B);
 	if (!depth || !cams) return HT_ERR_ARG;
-	const bool tile = (w == 64 && h == 64);
-	if (!tile && !frames_args_ok(ctx, w, h)) return HT_ERR_ARG;
-	hipStream_t s = ctx->stream;
-	const int nb = ctx->model.nb;
-	const size_t npx = (size_t)w * h;
-	const uint16_t *d_in; const float *d_cin;
-	if (tile)
-	{
-		HIPCHK(ctx, hipMemcpyAsync(ctx->d_depth, depth, (size_t)B * npx * sizeof(uint16_t), hipMemcpyHostToDevice, s));
-		HIPCHK(ctx, hipMemcpyAsync(ctx->d_cams, cams, (size_t)B * HT_CAM * sizeof(float), hipMemcpyHostToDevice, s));
-		d_in = ctx->d_depth; d_cin = ctx->d_cams;
-	}
-	else
-	{
-		if (ctx->frames_cap < (size_t)B * npx) { void *a = nullptr; HIPCHK(ctx, hipMalloc(&a, (size_t)ctx->B * npx * sizeof(uint16_t))); ctx->allocs.push_back(a); ctx->d_frames = (uint16_t *)a; ctx->frames_cap = (size_t)ctx->B * npx; }
-		if (!ctx->d_frame_cams_in) { void *a = nullptr; HIPCHK(ctx, hipMalloc(&a, (size_t)ctx->B * HT_CAM * sizeof(float))); ctx->allocs.push_back(a); ctx->d_frame_cams_in = (float *)a; }
-		HIPCHK(ctx, hipMemcpyAsync(ctx->d_frames, depth, (size_t)B * npx * sizeof(uint16_t), hipMemcpyHostToDevice, s));
-		HIPCHK(ctx, hipMemcpyAsync(ctx->d_frame_cams_in, cams, (size_t)B * HT_CAM * sizeof(float), hipMemcpyHostToDevice, s));
-		d_in = ctx->d_frames; d_cin = ctx->d_frame_cams_in;
-	}
+	if (!frames_args_ok(ctx, w, h)) return HT_ERR_ARG;
 	const frame_src fs = { w, h, segment_scale, 0 };
-	int r = run_update(ctx, d_in, d_cin, nullptr, B, ctx->d_poses_out, nullptr, s, tile ? nullptr : &fs, apply_to_handmodel ? UPD_KICKSTART : UPD_CNN_MODEL);
-	if (r) return r;
-	if (poses_out) HIPCHK(ctx, hipMemcpyAsync(poses_out, ctx->d_poses_out, (size_t)B * nb * HT_POSE * sizeof(float), hipMemcpyDeviceToHost, s));
-	if (accepted_out) HIPCHK(ctx, hipMemcpyAsync(accepted_out, ctx->d_accepted, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, s));
-	if (cnn_out) HIPCHK(ctx, hipMemcpyAsync(cnn_out, ctx->d_cnn_out, (size_t)B * HT_CNN_OUT * sizeof(float), hipMemcpyDeviceToHost, s));
-	HIPCHK(ctx, hipStreamSynchronize(s));
-	HIPCHK(ctx, hipGetLastError());
-	if (accepted_out) for (int b = 0; b < B; b++) accepted_out[b] = accepted_out[b] != 0;
-	if (!tile) { int over = 0; HIPCHK(ctx, hipMemcpy(&over, ctx->d_overflow, sizeof(int), hipMemcpyDeviceToHost)); if (over) { ctx->err = "ht_update_cnn_model: frame(s) with more in-range points than the solver's capacity"; return HT_ERR_ARG; } }
-	return HT_OK;
+	return update_sync(ctx, depth, cams, fs, apply_to_handmodel ? UPD_KICKSTART : UPD_CNN_MODEL, B, poses_out, accepted_out, cnn_out, "ht_update_cnn_model");
 }
 // ---- the reference's OVERLAPPED update() (handtrack.h:748-785) on two contexts of one device ----------------------------------------------------------------
 // The reference runs the CNN job (update_cnn_model_threadsafe: net, decode, FitError, reset, MultiStepSim, accept decision) on a background thread and lets the caller go
@@ -718,34 +672,9 @@ extern "C" int ht_update_passes_sync(ht_ctx *ctx, const uint16_t *depth, const f
 {
 	CHECK_READY(ctx); CHECK_MODEL(ctx); CHECK_BATCH(ctx, B);
 	if (!depth || !cams || !poses_out) return HT_ERR_ARG;
-	const bool tile = (w == 64 && h == 64);
-	if (!tile && !frames_args_ok(ctx, w, h)) return HT_ERR_ARG;
-	hipStream_t s = ctx->stream;
-	const int nb = ctx->model.nb;
-	const size_t npx = (size_t)w * h;
-	const uint16_t *d_in; const float *d_cin;
-	if (tile)
-	{
-		HIPCHK(ctx, hipMemcpyAsync(ctx->d_depth, depth, (size_t)B * npx * sizeof(uint16_t), hipMemcpyHostToDevice, s));
-		HIPCHK(ctx, hipMemcpyAsync(ctx->d_cams, cams, (size_t)B * HT_CAM * sizeof(float), hipMemcpyHostToDevice, s));
-		d_in = ctx->d_depth; d_cin = ctx->d_cams;
-	}
-	else
-	{
-		if (ctx->frames_cap < (size_t)B * npx) { void *a = nullptr; HIPCHK(ctx, hipMalloc(&a, (size_t)ctx->B * npx * sizeof(uint16_t))); ctx->allocs.push_back(a); ctx->d_frames = (uint16_t *)a; ctx->frames_cap = (size_t)ctx->B * npx; }
-		if (!ctx->d_frame_cams_in) { void *a = nullptr; HIPCHK(ctx, hipMalloc(&a, (size_t)ctx->B * HT_CAM * sizeof(float))); ctx->allocs.push_back(a); ctx->d_frame_cams_in = (float *)a; }
-		HIPCHK(ctx, hipMemcpyAsync(ctx->d_frames, depth, (size_t)B * npx * sizeof(uint16_t), hipMemcpyHostToDevice, s));
-		HIPCHK(ctx, hipMemcpyAsync(ctx->d_frame_cams_in, cams, (size_t)B * HT_CAM * sizeof(float), hipMemcpyHostToDevice, s));
-		d_in = ctx->d_frames; d_cin = ctx->d_frame_cams_in;
-	}
+	if (!frames_args_ok(ctx, w, h)) return HT_ERR_ARG;
 	const frame_src fs = { w, h, 0.17f, 0 };
-	int r = run_update(ctx, d_in, d_cin, nullptr, B, ctx->d_poses_out, nullptr, s, tile ? nullptr : &fs, UPD_PASSES);
-	if (r) return r;
-	HIPCHK(ctx, hipMemcpyAsync(poses_out, ctx->d_poses_out, (size_t)B * nb * HT_POSE * sizeof(float), hipMemcpyDeviceToHost, s));
-	HIPCHK(ctx, hipStreamSynchronize(s));
-	HIPCHK(ctx, hipGetLastError());
-	if (!tile) { int over = 0; HIPCHK(ctx, hipMemcpy(&over, ctx->d_overflow, sizeof(int), hipMemcpyDeviceToHost)); if (over) { ctx->err = "ht_update_passes: frame(s) with more in-range points than the context's point capacity holds"; return HT_ERR_ARG; } }
-	return HT_OK;
+	return update_sync(ctx, depth, cams, fs, UPD_PASSES, B, poses_out, nullptr, nullptr, "ht_update_passes");
 }
 extern "C" int ht_job_start(ht_ctx *job, ht_ctx *main, const uint16_t *depth, const float *cams, int w, int h, float segment_scale, int B)
 {
@@ -762,20 +691,7 @@ extern "C" int ht_job_start(ht_ctx *job, ht_ctx *main, const uint16_t *depth, co
 	HIPCHK(job, hipStreamSynchronize(main->stream));      // the caller's context is between two of its (synchronous) calls: its handmodel is final
 	memcpy(job->h_job_in, depth, in_bytes); memcpy((char *)job->h_job_in + in_bytes, cams, cam_bytes);      // the caller's image need not outlive this call (the reference moves it into the task)
 	const uint16_t *d_in; const float *d_cin;
-	if (tile)
-	{
-		HIPCHK(job, hipMemcpyAsync(job->d_depth, job->h_job_in, in_bytes, hipMemcpyHostToDevice, s));
-		HIPCHK(job, hipMemcpyAsync(job->d_cams, (char *)job->h_job_in + in_bytes, cam_bytes, hipMemcpyHostToDevice, s));
-		d_in = job->d_depth; d_cin = job->d_cams;
-	}
-	else
-	{
-		if (job->frames_cap < (size_t)B * npx) { void *a = nullptr; HIPCHK(job, hipMalloc(&a, (size_t)job->B * npx * sizeof(uint16_t))); job->allocs.push_back(a); job->d_frames = (uint16_t *)a; job->frames_cap = (size_t)job->B * npx; }
-		if (!job->d_frame_cams_in) { void *a = nullptr; HIPCHK(job, hipMalloc(&a, (size_t)job->B * HT_CAM * sizeof(float))); job->allocs.push_back(a); job->d_frame_cams_in = (float *)a; }
-		HIPCHK(job, hipMemcpyAsync(job->d_frames, job->h_job_in, in_bytes, hipMemcpyHostToDevice, s));
-		HIPCHK(job, hipMemcpyAsync(job->d_frame_cams_in, (char *)job->h_job_in + in_bytes, cam_bytes, hipMemcpyHostToDevice, s));
-		d_in = job->d_frames; d_cin = job->d_frame_cams_in;
-	}
+	{ const int r = stage_frames(job, (const uint16_t *)job->h_job_in, (const float *)((const char *)job->h_job_in + in_bytes), w, h, B, s, &d_in, &d_cin); if (r) return r; }
 	// the job looks at handmodel (FitError of the carried pose, :704) and starts othermodel from its pose (:757); prev_frame_error and initializing as they stand
 	HIPCHK(job, hipMemcpyAsync(job->d_state[0], main->d_state[0], (size_t)B * nb * HT_STATE_STRIDE * sizeof(float), hipMemcpyDeviceToDevice, s));
 	ht_launch_set_pose(job->d_state[1], main->d_state[0], nb, B, 2, s);
@@ -864,9 +780,7 @@ extern "C" int ht_stage_fit_error(ht_ctx *ctx, int which, int B, float *err)
 	hipStream_t s = ctx->stream;
 	ht_launch_fit_error(ctx->model, ctx->d_state[which], ctx->d_pts, ctx->d_npts, ctx->d_depth, ctx->d_cams, 64, 64, ctx->par.bone_sum_error_scale, ctx->d_err_old, B, s);
 	HIPCHK(ctx, hipMemcpyAsync(err, ctx->d_err_old, (size_t)B * sizeof(float), hipMemcpyDeviceToHost, s));
-	HIPCHK(ctx, hipStreamSynchronize(s));
-	HIPCHK(ctx, hipGetLastError());
-	return HT_OK;
+	return ht_sync_check(ctx, s);
 }
 extern "C" int ht_stage_cloud_rows(ht_ctx *ctx, int which, int stride, int use_cam_origin, int B, float *rows, int *nrows)
 {
@@ -877,9 +791,7 @@ extern "C" int ht_stage_cloud_rows(ht_ctx *ctx, int which, int stride, int use_c
 	ht_launch_cloud_rows(ctx->model, ctx->d_state[which], ctx->d_pts, ctx->d_npts, ctx->d_cams, nullptr, stride, use_cam_origin, 0, ctx->par, ctx->d_rows, ctx->d_nrows, B, s);
 	HIPCHK(ctx, hipMemcpy2DAsync(rows, HT_MAXPTS * HT_ROW * sizeof(float), ctx->d_rows, (size_t)ctx->model.pts_cap * HT_ROW * sizeof(float), HT_MAXPTS * HT_ROW * sizeof(float), B, hipMemcpyDeviceToHost, s));
 	HIPCHK(ctx, hipMemcpyAsync(nrows, ctx->d_nrows, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, s));
-	HIPCHK(ctx, hipStreamSynchronize(s));
-	HIPCHK(ctx, hipGetLastError());
-	return HT_OK;
+	return ht_sync_check(ctx, s);
 }
 // cloud_chamber (physmodel.h:486-496) as HandTracker::update calls it (handtrack.h:774-778): rows [B][5*nb][16], nrows [B] (0 where the frame has no more than
 // min_point_num points or boundary_planes is off)
@@ -894,9 +806,7 @@ extern "C" int ht_stage_chamber(ht_ctx *ctx, int which, int B, float *rows, int 
 	ht_launch_chamber(ctx->model, ctx->d_state[which], ctx->d_chplanes, ctx->d_chon, 10.0f, ctx->d_chamber, ctx->d_nchamber, B, s);
 	HIPCHK(ctx, hipMemcpyAsync(rows, ctx->d_chamber, (size_t)B * per * sizeof(float), hipMemcpyDeviceToHost, s));
 	HIPCHK(ctx, hipMemcpyAsync(nrows, ctx->d_nchamber, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, s));
-	HIPCHK(ctx, hipStreamSynchronize(s));
-	HIPCHK(ctx, hipGetLastError());
-	return HT_OK;
+	return ht_sync_check(ctx, s);
 }
 extern "C" int ht_stage_contacts(ht_ctx *ctx, int which, int B, int cap, float *contacts, int *ncontacts)
 {
@@ -907,8 +817,7 @@ extern "C" int ht_stage_contacts(ht_ctx *ctx, int which, int B, int cap, float *
 	std::vector<float> tmp((size_t)B * HT_MAXCONTACT * HT_CONTACT);
 	HIPCHK(ctx, hipMemcpyAsync(tmp.data(), ctx->d_contacts, tmp.size() * sizeof(float), hipMemcpyDeviceToHost, s));
 	HIPCHK(ctx, hipMemcpyAsync(ncontacts, ctx->d_ncontacts, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, s));
-	HIPCHK(ctx, hipStreamSynchronize(s));
-	HIPCHK(ctx, hipGetLastError());
+	{ const int r = ht_sync_check(ctx, s); if (r) return r; }
 	const int ncopy = cap < HT_MAXCONTACT ? cap : HT_MAXCONTACT;
 	for (int b = 0; b < B; b++) memcpy(contacts + (size_t)b * cap * HT_CONTACT, tmp.data() + (size_t)b * HT_MAXCONTACT * HT_CONTACT, (size_t)ncopy * HT_CONTACT * sizeof(float));
 	return HT_OK;
@@ -917,45 +826,26 @@ extern "C" int ht_stage_fit(ht_ctx *ctx, int B)
 {
 	CHECK_READY(ctx); CHECK_MODEL(ctx); CHECK_BATCH(ctx, B);
 	main_pass(ctx, B, ctx->stream);
-	HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-	HIPCHK(ctx, hipGetLastError());
-	return HT_OK;
+	return ht_sync_check(ctx, ctx->stream);
 }
-extern "C" int ht_stage_multistep(ht_ctx *ctx, const float *analysis, int B)
+// The stage calls that start from a decoded CNN output of the caller's: MultiStepSim, its steps [from_step, to_step) alone (handtrack.h:660-688: every step has its own
+// mix of CNN-driven angular rows, landmark rays and cloud rows; teacher-forced single-step tests start a step from a given state), PoseFromScratch + UnibodyFit.
+template <class F> static int stage_on_analysis(ht_ctx *ctx, const float *analysis, int B, F launch)
 {
 	CHECK_READY(ctx); CHECK_MODEL(ctx); CHECK_BATCH(ctx, B);
 	if (!analysis) return HT_ERR_ARG;
 	hipStream_t s = ctx->stream;
 	HIPCHK(ctx, hipMemcpyAsync(ctx->d_analysis, analysis, (size_t)B * HT_ANALYSIS * sizeof(float), hipMemcpyHostToDevice, s));
-	multistep(ctx, B, s);
-	HIPCHK(ctx, hipStreamSynchronize(s));
-	HIPCHK(ctx, hipGetLastError());
-	return HT_OK;
+	launch(s);
+	return ht_sync_check(ctx, s);
 }
-// steps [from_step, to_step) of MultiStepSim alone (handtrack.h:660-688: every step has its own mix of CNN-driven angular rows, landmark rays and cloud rows): teacher-forced
-// single-step tests start a step from a given state
+extern "C" int ht_stage_multistep(ht_ctx *ctx, const float *analysis, int B) { return stage_on_analysis(ctx, analysis, B, [&](hipStream_t s) { multistep(ctx, B, s); }); }
 extern "C" int ht_stage_multistep_range(ht_ctx *ctx, const float *analysis, int B, int from_step, int to_step)
 {
-	CHECK_READY(ctx); CHECK_MODEL(ctx); CHECK_BATCH(ctx, B);
-	if (!analysis || from_step < 0 || to_step < from_step) return HT_ERR_ARG;
-	hipStream_t s = ctx->stream;
-	HIPCHK(ctx, hipMemcpyAsync(ctx->d_analysis, analysis, (size_t)B * HT_ANALYSIS * sizeof(float), hipMemcpyHostToDevice, s));
-	multistep(ctx, B, s, from_step, to_step);
-	HIPCHK(ctx, hipStreamSynchronize(s));
-	HIPCHK(ctx, hipGetLastError());
-	return HT_OK;
+	const bool range_ok = from_step >= 0 && to_step >= from_step;
+	return stage_on_analysis(ctx, range_ok ? analysis : nullptr, B, [&](hipStream_t s) { multistep(ctx, B, s, from_step, to_step); });
 }
-extern "C" int ht_stage_scratch_unibody(ht_ctx *ctx, const float *analysis, int B, int n_unibody)
-{
-	CHECK_READY(ctx); CHECK_MODEL(ctx); CHECK_BATCH(ctx, B);
-	if (!analysis) return HT_ERR_ARG;
-	hipStream_t s = ctx->stream;
-	HIPCHK(ctx, hipMemcpyAsync(ctx->d_analysis, analysis, (size_t)B * HT_ANALYSIS * sizeof(float), hipMemcpyHostToDevice, s));
-	reset_path(ctx, false, n_unibody, B, s, s);
-	HIPCHK(ctx, hipStreamSynchronize(s));
-	HIPCHK(ctx, hipGetLastError());
-	return HT_OK;
-}
+extern "C" int ht_stage_scratch_unibody(ht_ctx *ctx, const float *analysis, int B, int n_unibody) { return stage_on_analysis(ctx, analysis, B, [&](hipStream_t s) { reset_path(ctx, false, n_unibody, B, s, s); }); }
 
 // Timing experiments only (HT_DEBUG_SKIP & 2048): per-frame k_solve statistics accumulated in the last scratch record of each frame:
 // launches, cycles in chains / two-body linear / angular, cycles in all sweeps, steps (linear, angular), longest chain, row counts.
@@ -985,9 +875,8 @@ extern "C" int ht_debug_solver_build(ht_ctx *ctx, int which)
 	if ((which == 5 || which == 8) && !ctx->d_exact_lin)
 	{
 		ht_device_guard dev_guard_(ctx->device);
-		void *a = nullptr, *b = nullptr;
-		HIPCHK(ctx, hipMalloc(&a, (size_t)ctx->B * HT_EX_LIN * HT_ROW * sizeof(float))); ctx->allocs.push_back(a); ctx->d_exact_lin = (float *)a;
-		HIPCHK(ctx, hipMalloc(&b, (size_t)ctx->B * 256 * 8 * sizeof(float))); ctx->allocs.push_back(b); ctx->d_exact_ang = (float *)b;
+		int r;
+		if ((r = dev_alloc(ctx, &ctx->d_exact_ang, (size_t)ctx->B * 256 * 8)) || (r = dev_alloc(ctx, &ctx->d_exact_lin, (size_t)ctx->B * HT_EX_LIN * HT_ROW))) return r;
 	}
 	ctx->solver_build = which;
 	return HT_OK;
@@ -1095,31 +984,13 @@ extern "C" int ht_segment_vr(ht_ctx *ctx, const uint16_t *depth, const float *ca
 // (physics.h:543-587) take rows the CALLER built.  Row layouts are those of the stage calls: a linear row is 16 floats (rb0 rb1 position0[3]
 // position1[3] normal[3] targetdist targetspeednobias forcelimit.x forcelimit.y friction_master), an angular row 8 (rb0 rb1 axis[3] targetspin
 // mintorque maxtorque); a body is its index in PhysModel::rigidbodies, -1 = NULL.
-static void drop_alloc(ht_ctx *ctx, void *o) { if (!o) return; for (auto &q : ctx->allocs) if (q == o) { q = ctx->allocs.back(); ctx->allocs.pop_back(); break; } (void)hipFree(o); }
 static int user_rows_reserve(ht_ctx *ctx, int lin_cap, int ang_cap)
 {
-	// the replacement is allocated FIRST: when an allocation fails the context keeps its old, valid arrays and capacities
-	if (lin_cap > ctx->user_lin_cap)
-	{
-		HIPCHK(ctx, ht_sync_all(ctx));
-		void *a = nullptr, *b = nullptr;
-		HIPCHK(ctx, hipMalloc(&a, (size_t)ctx->B * lin_cap * HT_ROW * sizeof(float)));
-		if (hipMalloc(&b, (size_t)ctx->B * lin_cap * sizeof(unsigned short)) != hipSuccess) { (void)hipFree(a); ctx->err = "caller-built rows: out of device memory"; return HT_ERR_HIP; }
-		drop_alloc(ctx, ctx->d_user_lin); drop_alloc(ctx, ctx->d_user_pos);
-		ctx->allocs.push_back(a); ctx->d_user_lin = (float *)a; ctx->allocs.push_back(b); ctx->d_user_pos = (unsigned short *)b;
-		ctx->user_lin_cap = lin_cap;
-	}
-	if (ang_cap > ctx->user_ang_cap)
-	{
-		HIPCHK(ctx, ht_sync_all(ctx));
-		void *a = nullptr;
-		HIPCHK(ctx, hipMalloc(&a, (size_t)ctx->B * ang_cap * HT_AROW * sizeof(float)));
-		drop_alloc(ctx, ctx->d_user_ang);
-		ctx->allocs.push_back(a); ctx->d_user_ang = (float *)a;
-		ctx->user_ang_cap = ang_cap;
-	}
-	if (!ctx->d_user_n) { void *a = nullptr; HIPCHK(ctx, hipMalloc(&a, (size_t)4 * ctx->B * sizeof(int))); ctx->allocs.push_back(a); ctx->d_user_n = (int *)a; }
-	return HT_OK;
+	const size_t B = (size_t)ctx->B;
+	int r, pos_cap = ctx->user_lin_cap;      // the two arrays of the linear rows share a capacity: it is raised by the second to grow
+	if ((r = dev_grow(ctx, &ctx->d_user_pos, &pos_cap, lin_cap, B)) || (r = dev_grow(ctx, &ctx->d_user_lin, &ctx->user_lin_cap, lin_cap, B * HT_ROW))) return r;
+	if ((r = dev_grow(ctx, &ctx->d_user_ang, &ctx->user_ang_cap, ang_cap, B * HT_AROW))) return r;
+	return ctx->d_user_n ? HT_OK : dev_alloc(ctx, &ctx->d_user_n, 4 * B);
 }
 static int upload_angulars(ht_ctx *ctx, int B, const float *angulars, int acap, const int *nangulars, std::vector<int> &na)
 {
@@ -1189,9 +1060,7 @@ extern "C" int ht_fit_rows(ht_ctx *ctx, int which, int B, const float *points, i
 	a.force_build = ctx->solver_build;
 	ctx->model.pts_bound = 0;
 	ht_launch_solve(ctx->model, ctx->phys, a, B, s);
-	HIPCHK(ctx, hipStreamSynchronize(s));
-	HIPCHK(ctx, hipGetLastError());
-	return HT_OK;
+	return ht_sync_check(ctx, s);
 }
 // void PhysicsUpdate(const std::vector<RigidBody*> &rigidbodies, std::vector<LimitLinear> &Linears, std::vector<LimitAngular> &Angulars, wgeom = {})
 // (physics.h:543-587) on model `which` of slots [0,B): the caller's rows are all there is (plus the collision rows when physics_use_collision is set).
@@ -1271,9 +1140,7 @@ extern "C" int ht_physics_update(ht_ctx *ctx, int which, int B, const float *lin
 	a.force_build = ctx->solver_build;
 	ctx->model.pts_bound = 0;
 	ht_launch_solve(ctx->model, ctx->phys, a, B, s);
-	HIPCHK(ctx, hipStreamSynchronize(s));
-	HIPCHK(ctx, hipGetLastError());
-	return HT_OK;
+	return ht_sync_check(ctx, s);
 }
 
 // ------------------------------------------------------------------------------------------------- slowfit (annotation fit loop)
@@ -1286,9 +1153,8 @@ extern "C" int ht_slowfit(ht_ctx *ctx, int B, int hold, const float *refpose, in
 	hipStream_t s = ctx->stream;
 	if (!ctx->d_sf_ref)
 	{
-		void *p = nullptr, *q = nullptr;
-		HIPCHK(ctx, hipMalloc(&p, (size_t)ctx->B * nb * HT_POSE * sizeof(float))); ctx->allocs.push_back(p); ctx->d_sf_ref = (float *)p;
-		HIPCHK(ctx, hipMalloc(&q, (size_t)ctx->B * 8 * 4 * sizeof(float))); ctx->allocs.push_back(q); ctx->d_sf_crays = (float *)q;
+		int r;
+		if ((r = dev_alloc(ctx, &ctx->d_sf_crays, (size_t)ctx->B * 8 * 4)) || (r = dev_alloc(ctx, &ctx->d_sf_ref, (size_t)ctx->B * nb * HT_POSE))) return r;
 	}
 	const bool rel = hold && refpose;
 	if (rel) HIPCHK(ctx, hipMemcpyAsync(ctx->d_sf_ref, refpose, (size_t)B * nb * HT_POSE * sizeof(float), hipMemcpyHostToDevice, s));
@@ -1318,9 +1184,7 @@ extern "C" int ht_slowfit(ht_ctx *ctx, int B, int hold, const float *refpose, in
 		a.force_build = ctx->solver_build;
 		ht_launch_solve(ctx->model, ctx->phys, a, B, s);
 	}
-	HIPCHK(ctx, hipStreamSynchronize(s));
-	HIPCHK(ctx, hipGetLastError());
-	return HT_OK;
+	return ht_sync_check(ctx, s);
 }
 
 // Caller-supplied point clouds for the stage functions / ht_slowfit (the reference's slowfit takes its points as an argument):

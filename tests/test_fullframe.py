@@ -261,3 +261,100 @@ def test_gpu_overlapped_update_on_a_full_frame_equals_the_synchronous_one(weight
     finally:
         for c in (ref, main, job):
             c.close()
+
+
+def _qvga():
+    G, (_, model, nb) = GOLD["qvga"], CASES["qvga"]
+    nf = len(G["rows"])
+    depth = np.ascontiguousarray(np.stack([G["f%d/depth" % f] for f in range(nf)])); cams = np.stack([G["f%d/cam" % f] for f in range(nf)]).astype(np.float32)
+    return model, nf, depth, cams, np.stack([G["f%d/startpose" % f] for f in range(nf)])
+
+
+def _qvga_crop(depth, cams):
+    """The central 160x120 pixels of the 320x240 frames; the camera keeps its focal length and pose, its principal point (cam[2:4]) moves with the window."""
+    small = np.ascontiguousarray(depth[:, 60:180, 80:240])
+    c = cams.copy(); c[:, 2] -= 80.0; c[:, 3] -= 60.0
+    return small, c
+
+
+def _context(model, nf, weights):
+    from hand_tracking_samples_amd import native
+    ctx = native.Context(model, nf)
+    ctx.load_weights(weights)
+    ctx.set_params(microforce=3.0, mainthreadpasses=3)
+    return ctx
+
+
+@pytest.mark.gpu
+def test_gpu_growing_frame_sizes_on_one_context(weights):
+    """A context that has seen 160x120 frames and then gets 320x240 ones replaces its frame buffer (the outgrown one is freed): the larger call must give,
+    bit for bit, what it gives on a fresh context -- poses, CNN output, tracker flags and both models' states."""
+    model, nf, depth, cams, start = _qvga()
+    assert nf == 2 and depth.shape[1:] == (240, 320)
+    small, small_cams = _qvga_crop(depth, cams)
+
+    def full(ctx):
+        ctx.tracker_reset(start)
+        poses, cnn = ctx.update_frames_sync(depth, cams, 0.17, want_cnn=True)
+        pfe, ini = ctx.tracker_flags(nf)
+        return poses, cnn, pfe, ini, ctx.get_state(0, nf), ctx.get_state(1, nf)
+
+    fresh = _context(model, nf, weights)
+    try:
+        want = full(fresh)
+    finally:
+        fresh.close()
+    ctx = _context(model, nf, weights)
+    try:
+        ctx.tracker_reset(start)
+        ctx.update_frames_sync(small, small_cams, 0.17)      # any depth image is valid input: the call succeeding is all that is asked of it
+        got = full(ctx)
+    finally:
+        ctx.close()
+    for name, g, w in zip(("poses", "cnn_out", "prev_frame_error", "initializing", "handmodel", "othermodel"), got, want):
+        assert np.array_equal(g, w), name
+
+
+@pytest.mark.gpu
+def test_gpu_growing_frame_sizes_update_cnn_model(weights):
+    """The same sequence through ht_update_cnn_model_sync (the CNN job alone): othermodel's poses and the accept decisions equal a fresh context's."""
+    model, nf, depth, cams, start = _qvga()
+    small, small_cams = _qvga_crop(depth, cams)
+    fresh = _context(model, nf, weights)
+    try:
+        fresh.tracker_reset(start)
+        want_poses, want_acc = fresh.update_cnn_model_sync(depth, cams, kickstart=False)
+    finally:
+        fresh.close()
+    ctx = _context(model, nf, weights)
+    try:
+        ctx.tracker_reset(start)
+        ctx.update_cnn_model_sync(small, small_cams, kickstart=False)
+        ctx.tracker_reset(start)
+        poses, acc = ctx.update_cnn_model_sync(depth, cams, kickstart=False)
+    finally:
+        ctx.close()
+    assert np.array_equal(poses, want_poses) and np.array_equal(acc, want_acc)
+    assert set(acc.tolist()) <= {0, 1}
+
+
+@pytest.mark.gpu
+def test_gpu_tile_entry_points_delegate(weights):
+    """On 64x64 tiles ht_update_frames_sync and ht_update_direct_sync(side = 64) are ht_update_sync: identical poses and CNN outputs from the same start state."""
+    g = htfx.load(os.path.join(HERE, "golden", "golden8.htfx"))
+    nf = 4
+    depth = np.stack([g["f%d/depth" % f].reshape(64, 64) for f in range(nf)]); cams = np.stack([g["f%d/cam" % f] for f in range(nf)])
+    start = np.stack([g["f%d/startpose" % f] for f in range(nf)])
+    ctx = _context(ol.MODEL, nf, weights)
+    try:
+        ctx.tracker_reset(start)
+        want, want_cnn = ctx.update_sync(depth, cams, want_cnn=True)
+        ctx.tracker_reset(start)
+        frames, frames_cnn = ctx.update_frames_sync(depth, cams, 0.17, want_cnn=True)
+        ctx.tracker_reset(start)
+        direct, direct_cnn = ctx.update_direct_sync(depth, cams, 64, want_cnn=True)
+    finally:
+        ctx.close()
+    assert np.isfinite(want).all()
+    assert np.array_equal(frames, want) and np.array_equal(direct, want)
+    assert np.array_equal(frames_cnn, want_cnn) and np.array_equal(direct_cnn, want_cnn)
