@@ -106,6 +106,14 @@ static int load_model(ht_ctx *ctx, const char *path)
 		m.ignore[b] = mask;
 	}
 	m.vert_off[nb] = (int)verts.size(); m.plane_off[nb] = (int)planes.size();
+	// the subdivision meshes (GetMeshes(true)), for ht_render_mesh_depth; a baked model from before they were stored has none, and that call then refuses
+	ctx->h_mesh_corners.clear(); ctx->mesh_off.assign((size_t)nb + 1, 0);
+	for (int b = 0; b < nb; b++)
+	{
+		auto it = fx.find("b" + std::to_string(b) + "/sdverts");
+		if (it != fx.end()) { const size_t nt = it->second.dims[0] / 3; ctx->h_mesh_corners.insert(ctx->h_mesh_corners.end(), it->second.f(), it->second.f() + nt * 9); }
+		ctx->mesh_off[(size_t)b + 1] = (int)(ctx->h_mesh_corners.size() / 9);
+	}
 	// HandModelEnhancements' one-time rewrite (handtrack.h:408-416): a model whose bone 2 (the thumb base) ignores fewer than 10 bodies gets that
 	// bone out of every collision pair.  The reference does it on the first call, which precedes every solve with collisions (:684-685, :773-779,
 	// :798), so doing it at load gives the same pairs.  The list length counts duplicates there; a baked file without "ignore_count" falls back
@@ -141,7 +149,8 @@ static int load_model(ht_ctx *ctx, const char *path)
 	if ((r = dev_upload(ctx, &dv, verts)) || (r = dev_upload(ctx, &dp, planes)) || (r = dev_upload(ctx, &dbc, bodyc)) || (r = dev_upload(ctx, &djc, jointc))) return r;
 	m.verts = dv; m.planes = dp; m.bodyc = dbc; m.jointc = djc;
 	ctx->h_verts = verts; ctx->h_planes = planes; ctx->d_verts_rw = dv; ctx->d_planes_rw = dp; ctx->d_bodyc_rw = dbc; ctx->d_jointc_rw = djc;
-	return upload_padded_verts(ctx);
+	{ const int r2 = upload_padded_verts(ctx); if (r2) return r2; }
+	return ht_mesh_upload(ctx);
 }
 
 static void sync_params(ht_ctx *ctx)
@@ -216,6 +225,7 @@ extern "C" int ht_scale(ht_ctx *ctx, float s)
 	const float ss = s * s;
 	for (auto &v : ctx->h_verts) { v.x *= s; v.y *= s; v.z *= s; }      // w keeps the vertex index
 	for (auto &p : ctx->h_planes) p.w *= s;
+	for (auto &v : ctx->h_mesh_corners) v *= s;      // scale(Mesh&) on the sdmeshes (physmodel.h:215-219,308-309)
 	for (int b = 0; b < nb; b++)
 	{
 		float *c = &ctx->h_bodyc[(size_t)b * HT_BC];
@@ -236,6 +246,8 @@ extern "C" int ht_scale(ht_ctx *ctx, float s)
 	HIPCHK(ctx, hipStreamSynchronize(st));
 	HIPCHK(ctx, hipMemcpy(ctx->d_verts_rw, ctx->h_verts.data(), ctx->h_verts.size() * sizeof(float4), hipMemcpyHostToDevice));
 	{ const int r = upload_padded_verts(ctx); if (r) return r; }
+	if (ctx->last_user_stream && ctx->last_user_stream != st) HIPCHK(ctx, hipStreamSynchronize(ctx->last_user_stream));      // a render of the old meshes on the caller's stream
+	{ const int r = ht_mesh_upload(ctx); if (r) return r; }
 	HIPCHK(ctx, hipMemcpy(ctx->d_planes_rw, ctx->h_planes.data(), ctx->h_planes.size() * sizeof(float4), hipMemcpyHostToDevice));
 	HIPCHK(ctx, hipMemcpy(ctx->d_bodyc_rw, ctx->h_bodyc.data(), ctx->h_bodyc.size() * sizeof(float), hipMemcpyHostToDevice));
 	HIPCHK(ctx, hipMemcpy(ctx->d_jointc_rw, ctx->h_jointc.data(), ctx->h_jointc.size() * sizeof(float), hipMemcpyHostToDevice));

@@ -78,6 +78,9 @@ struct ht_ctx
 	char *d_render = nullptr; size_t render_cap = 0;             // ht_render_depth's staging (poses, cameras, frames, body labels), grown to the largest call (dev_grow)
 	char *d_labels = nullptr; size_t labels_cap = 0;             // ht_expected_cnn_batch's staging (poses, cameras, labels, image points, key angles), grown to the largest call (dev_grow)
 	std::vector<float4> render_planes; std::vector<float> render_radii;      // the hull planes ht_render_depth last derived its per-body cull radii from, and those radii (2 per body)
+	// ht_render_mesh_depth: the subdivision meshes' corners [t][9] over all bodies (ht_scale rewrites them), the first triangle of every body, the device rows
+	// [t][4] float4 (corners and PolyPlane, ht_mesh_rows) and the farthest corner of every body's mesh from its centre of mass (ht_mesh_upload makes both)
+	std::vector<float> h_mesh_corners, mesh_rad; std::vector<int> mesh_off; float4 *d_mesh = nullptr;
 };
 
 // what every entry point of the C-ABI starts with and wraps its HIP calls in
@@ -127,6 +130,7 @@ struct ht_prof_scope
 // to a multiple of 8 when a body beyond the 16th rides on its quad (7 per such body at most), and the tail that takes what does not fit k_solve's LDS
 static inline size_t ht_scratch_rows(size_t pts_cap, size_t nb) { return pts_cap + 5 * nb + 32 + 7 * 16 + HT_SCRATCH_TAIL; }
 int ht_alloc_buffers(ht_ctx *ctx);
+int ht_mesh_upload(ht_ctx *ctx);             // rows and radii of the model's current subdivision meshes to the device (ht_render_mesh.hip); the caller has waited for the renders in flight
 int ht_alloc_solve_tables(ht_ctx *ctx);      // d_tables (first use of the solve-tables path)
 int ht_reserve_points_locked(ht_ctx *ctx, int points);      // grows the per-point arrays (ht_api.hip); waits for the context's streams
 // *_dev entry points: a NULL stream means the context's own stream (never the legacy default stream); the choice is remembered so that the

@@ -618,3 +618,23 @@ bool ht_json_top_level(const char *path, std::map<std::string, std::string> &num
 	for (size_t i = 0; i < root.keys.size(); i++) if (root.items[i].kind == jnode::NUM) numbers[root.keys[i]] = root.items[i].text;
 	return true;
 }
+
+// ------------------------------------------------------------------------------------------------- mesh ray-cast rows
+void ht_mesh_rows(const float *corners, size_t ntri, float *rows16)
+{
+	for (size_t k = 0; k < ntri; k++)
+	{
+		const float *p = corners + 9 * k;
+		const v3 v[3] = { V3(p[0], p[1], p[2]), V3(p[3], p[4], p[5]), V3(p[6], p[7], p[8]) };
+		// PolyPlane: the centroid as a running sum of v * (1.0f / n), the normal as the sum of the fan's cross products about it
+		const float inv = 1.0f / (float)3;
+		v3 c = V3(0, 0, 0), n = V3(0, 0, 0);
+		for (int i = 0; i < 3; i++) c = c + v[i] * inv;
+		for (int i = 0; i < 3; i++) n = n + cross(v[i] - c, v[(i + 1) % 3] - c);
+		v4 pl = V4(0, 0, 0, 0);
+		if (!is_zero(n)) { n = normalize(n); pl = V4(n, -dot(c, n)); }
+		float *r = rows16 + 16 * k;
+		for (int i = 0; i < 3; i++) { r[4 * i] = v[i].x; r[4 * i + 1] = v[i].y; r[4 * i + 2] = v[i].z; r[4 * i + 3] = 0.0f; }
+		r[12] = pl.x; r[13] = pl.y; r[14] = pl.z; r[15] = pl.w;
+	}
+}

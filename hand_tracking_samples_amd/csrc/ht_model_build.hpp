@@ -26,3 +26,8 @@ bool ht_build_model(const char *json_path, int flags, fx_map &out, std::string &
 
 // numeric top-level members of a JSON object file, as text
 bool ht_json_top_level(const char *path, std::map<std::string, std::string> &numbers, std::string &err);
+
+// The subdivision surface as the mesh ray cast reads it (ht_model_hitcheck_mesh, ht_render_mesh_depth): per triangle 16 floats,
+// corners p0 p1 p2 (each padded to four floats) and PolyPlane({p0, p1, p2}) (geometric.h:247-260) in float, in that function's operation order.
+// corners: [ntri][3][3] as ht_model_body_sdmesh hands them out.  Both the host model and the context make their rows here, after the same scaling.
+void ht_mesh_rows(const float *corners, size_t ntri, float *rows16);

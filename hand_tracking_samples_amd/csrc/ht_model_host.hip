@@ -17,6 +17,7 @@ struct ht_model
 	std::vector<std::vector<float>> verts, planes;      // per body: [n][3] com-centred vertices, [n][4] local half-space planes
 	std::vector<std::vector<int>> tris;                 // per body: [n][3] hull triangles over verts
 	std::vector<std::vector<float>> sdverts;            // per body: [3 t][3] the subdivision surface's triangles corner by corner, in the bone's rig frame (GetMeshes(true), physmodel.h:258)
+	std::vector<std::vector<float>> sdrows;             // per body: [t][16] corners and PolyPlane of every sdverts triangle (ht_mesh_rows), what the mesh ray cast reads
 	std::vector<float> com, rest;                       // [nb][3], [nb][7]
 	std::string err;
 };
@@ -45,6 +46,8 @@ extern "C" int ht_model_open(const char *path, int hand_tweaks, ht_model **out)
 		m->tris.emplace_back(t->i(), t->i() + (size_t)t->dims[0] * 3);
 		const fx_arr *sv = get(k + "/sdverts");
 		if (sv) m->sdverts.emplace_back(sv->f(), sv->f() + (size_t)sv->dims[0] * 3); else m->sdverts.emplace_back();
+		m->sdrows.emplace_back((m->sdverts.back().size() / 9) * 16);
+		ht_mesh_rows(m->sdverts.back().data(), m->sdverts.back().size() / 9, m->sdrows.back().data());
 		const float *r = bf->f() + 26 * b;      // mass massinv radius radius_inner damping friction gravscale com3 pos_start3 quat_start4 tensorinv9
 		m->com.insert(m->com.end(), r + 7, r + 10);
 		m->rest.insert(m->rest.end(), r + 10, r + 17);
@@ -111,5 +114,82 @@ extern "C" int ht_model_hitcheck(const ht_model *m, const float *poses, const fl
 	if (impact3) { impact3[0] = impact.x; impact3[1] = impact.y; impact3[2] = impact.z; }
 	if (normal3) { normal3[0] = normal.x; normal3[1] = normal.y; normal3[2] = normal.z; }
 	if (body_out) *body_out = who;
+	return HT_OK;
+}
+
+// PhysModel::scale (physmodel.h:196-219,304-319) for what this view holds: hull vertices and plane offsets, the subdivision meshes and the centres of mass times s,
+// the operations ht_scale applies to a context's model, so a scaled host model and a scaled context stay bit-equal.  The mesh planes are made again from the scaled corners.
+extern "C" int ht_model_scale(ht_model *m, float s)
+{
+	if (!m || !(s > 0.0f)) return HT_ERR_ARG;
+	for (int b = 0; b < m->nb; b++)
+	{
+		for (auto &v : m->verts[b]) v *= s;
+		for (size_t k = 3; k < m->planes[b].size(); k += 4) m->planes[b][k] *= s;
+		for (auto &v : m->sdverts[b]) v *= s;
+		ht_mesh_rows(m->sdverts[b].data(), m->sdverts[b].size() / 9, m->sdrows[b].data());
+	}
+	for (auto &v : m->com) v *= s;
+	return HT_OK;
+}
+
+// The ray cast against the subdivision surface GetMeshes(true) hands to a renderer (physmodel.h:295-303): the software statement of the application's default depth
+// source (synthetic-tracker.cpp:164-165), built from PolyHitCheck (geometric.h:263-273) alone.  Every triangle of every body is tested on the whole segment, in the
+// frame of its mesh pose U_b = {pos_b - qrot(q_b, com_b), q_b}; the candidate with the smallest d0 / (d0 - d1) wins, the first in (body, triangle) order on a tie.
+// No culling of any kind: this is the definition ht_render_mesh_depth is held to.
+struct mesh_hit { int body, tri; v3 impact, normal; };
+static mesh_hit mesh_hitcheck(const ht_model *m, const float *poses, v3 v0, v3 v1)
+{
+	mesh_hit h; h.body = -1; h.tri = -1; h.impact = v1; h.normal = V3(0, 0, 0);
+	float best = INFINITY;
+	for (int b = 0; b < m->nb; b++)
+	{
+		const float *p = poses + 7 * b;
+		const v4 q = V4(p[3], p[4], p[5], p[6]);
+		const xf U = XF(V3(p[0], p[1], p[2]) - qrot(q, V3(m->com[3 * b], m->com[3 * b + 1], m->com[3 * b + 2])), q), inv = inverse(U);
+		const v3 a = apply(inv, v0), c = apply(inv, v1);
+		const std::vector<float> &R = m->sdrows[b];
+		for (size_t k = 0; 16 * k < R.size(); k++)
+		{
+			const float *r = &R[16 * k];
+			const v4 P = V4(r[12], r[13], r[14], r[15]);
+			const float d0 = dot_plane(P, a), d1 = dot_plane(P, c);
+			if (!(d0 > 0 && d1 < 0)) continue;
+			const v3 t[3] = { V3(r[0], r[1], r[2]), V3(r[4], r[5], r[6]), V3(r[8], r[9], r[10]) };
+			bool hit = true;
+			for (int i = 0; hit && i < 3; i++) { m3 M; M.x = t[(i + 1) % 3] - a; M.y = t[i] - a; M.z = c - a; hit = determinant(M) >= 0; }
+			if (!hit) continue;
+			const float tt = d0 / (d0 - d1);
+			if (!(tt < best)) continue;
+			best = tt; h.body = b; h.tri = (int)k;
+			h.impact = apply(U, a + ((c - a) * d0) / (d0 - d1));
+			h.normal = qrot(q, xyz(P));
+		}
+	}
+	return h;
+}
+extern "C" int ht_model_hitcheck_mesh(const ht_model *m, const float *poses, const float *v0, const float *v1, float *impact3, float *normal3, int *body, int *tri)
+{
+	if (!m || !poses || !v0 || !v1) return HT_ERR_ARG;
+	const mesh_hit h = mesh_hitcheck(m, poses, V3(v0[0], v0[1], v0[2]), V3(v1[0], v1[1], v1[2]));
+	if (impact3) { impact3[0] = h.impact.x; impact3[1] = h.impact.y; impact3[2] = h.impact.z; }
+	if (normal3) { normal3[0] = h.normal.x; normal3[1] = h.normal.y; normal3[2] = h.normal.z; }
+	if (body) *body = h.body;
+	if (tri) *tri = h.tri;
+	return HT_OK;
+}
+// One frame: pixel (x, y) = (uint16)(impact.z / depth_scale) of the segment from the origin to deprojectz((x + pixel_offset, y + pixel_offset), far) (misc_image.h:48).
+// A plain loop over pixels, bodies and triangles.  cam12: focal, principal point and depth_scale are used, the camera's pose is not.
+extern "C" int ht_model_render_mesh(const ht_model *m, const float *poses, const float *cam12, int w, int h, float far, float pixel_offset, uint16_t *depth, int8_t *body)
+{
+	if (!m || !poses || !cam12 || !depth || w < 1 || h < 1 || w > 4096 || h > 4096 || !(far > 0.0f) || !(pixel_offset >= 0.0f && pixel_offset <= 1.0f)) return HT_ERR_ARG;
+	const float fx = cam12[0], fy = cam12[1], px = cam12[2], py = cam12[3], ds = cam12[4];
+	for (int y = 0; y < h; y++) for (int x = 0; x < w; x++)
+	{
+		const v3 v1 = V3((((float)x + pixel_offset) - px) / fx * far, (((float)y + pixel_offset) - py) / fy * far, far);
+		const mesh_hit hit = mesh_hitcheck(m, poses, V3(0.0f, 0.0f, 0.0f), v1);
+		depth[(size_t)y * w + x] = (unsigned short)(hit.impact.z / ds);
+		if (body) body[(size_t)y * w + x] = (int8_t)hit.body;
+	}
 	return HT_OK;
 }

@@ -21,7 +21,7 @@ SYMBOLS = (
     "ht_create", "ht_destroy", "ht_model_bake", "ht_last_error", "ht_get_params", "ht_set_params", "ht_model_info", "ht_config_read", "ht_scale",
     "ht_cnn_load_weights", "ht_cnn_eval", "ht_cnn_eval_dev", "ht_cnn_load_weights_sized", "ht_cnn_eval_sized", "ht_cnn_eval_sized_dev", "ht_cnn_train", "ht_cnn_get_weights", "ht_expected_cnn", "ht_expected_cnn_full",
     "ht_expected_cnn_batch", "ht_expected_cnn_dev", "ht_cnn_input_dev", "ht_cnn_train_dev",
-    "ht_model_open", "ht_model_close", "ht_model_error", "ht_model_counts", "ht_model_body", "ht_model_body_mesh", "ht_model_body_sdmesh", "ht_model_hitcheck",
+    "ht_model_open", "ht_model_close", "ht_model_error", "ht_model_counts", "ht_model_body", "ht_model_body_mesh", "ht_model_body_sdmesh", "ht_model_hitcheck", "ht_model_hitcheck_mesh", "ht_model_render_mesh", "ht_model_scale", "ht_render_mesh_depth", "ht_render_mesh_depth_dev",
     "ht_tracker_reset", "ht_get_state", "ht_set_state", "ht_get_tracker_flags", "ht_set_tracker_flags", "ht_update_sync", "ht_update_dev", "ht_update_frames_sync", "ht_update_frames_dev", "ht_update_direct_sync", "ht_update_direct_dev", "ht_update_cnn_model_sync", "ht_get_cnn_results", "ht_get_cnn_layers", "ht_frames_overflow", "ht_reserve_points", "ht_point_capacity", "ht_capacity_events", "ht_segment_vr", "ht_segment_vr_dev", "ht_render_depth", "ht_render_depth_dev", "ht_slowfit", "ht_set_points", "ht_fit_rows", "ht_physics_update",
     "ht_stage_prepare", "ht_stage_decode", "ht_stage_fit_error", "ht_stage_cloud_rows", "ht_stage_contacts", "ht_stage_fit",
     "ht_stage_multistep", "ht_stage_multistep_range", "ht_stage_scratch_unibody", "ht_stage_chamber", "ht_profile_enable", "ht_profile_read", "ht_debug_solve_stats", "ht_debug_contact_stats", "ht_debug_solver_build", "ht_debug_reset_flags", "ht_debug_reset_organisation", "ht_update_passes_sync", "ht_job_start", "ht_job_poll", "ht_job_wait", "ht_job_collect", "ht_debug_contact_kernel", "ht_contact_capacity", "ht_debug_solve_tables", "ht_debug_solve_tables_header",
@@ -117,6 +117,11 @@ def load(build_if_missing=True):
     L.ht_segment_vr_dev.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, vp, vp, vp]
     L.ht_render_depth.argtypes = [vp, fp, fp, C.c_int, C.c_int, C.c_float, C.c_int, u16p, C.POINTER(C.c_int8)]
     L.ht_render_depth_dev.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_float, C.c_int, vp, vp, vp]
+    L.ht_render_mesh_depth.argtypes = [vp, fp, fp, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int, u16p, C.POINTER(C.c_int8)]
+    L.ht_render_mesh_depth_dev.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int, vp, vp, vp]
+    L.ht_model_hitcheck_mesh.argtypes = [vp, fp, fp, fp, fp, fp, ip, ip]
+    L.ht_model_render_mesh.argtypes = [vp, fp, fp, C.c_int, C.c_int, C.c_float, C.c_float, u16p, C.POINTER(C.c_int8)]
+    L.ht_model_scale.argtypes = [vp, C.c_float]
     L.ht_profile_read.argtypes = [vp, C.c_int, C.c_int, C.c_char_p, C.c_int, fp, ip, ip]
     L.ht_debug_solve_stats.argtypes = [vp, C.c_int, fp, C.c_int]
     L.ht_debug_solver_build.argtypes = [vp, C.c_int]
@@ -531,6 +536,21 @@ class Context:
         """ht_render_depth_dev: device pointers (poses [B,nb,7], cams [B,12] -> depth u16[B,h,w], body int8[B,h,w] or None), asynchronous on `stream`."""
         self._chk(self.L.ht_render_depth_dev(self.h, d_poses, d_cams, int(w), int(h), float(far), int(B), d_depth, d_body, stream))
 
+    def render_mesh_depth(self, poses, cams, w, h, far=4.0, pixel_offset=0.0, want_body=False):
+        """The hand's subdivision surface (GetMeshes(true)) ray-cast for a batch, bit-identical to HostModel.render_mesh: poses [B,nb,7], cameras [B,12] ->
+        depth u16[B,h,w] (and the hit body int8[B,h,w], -1 = background, with want_body).  pixel_offset 0 / far 4 matches render_depth's frames,
+        0.5 / 0.85 the application's GL frames."""
+        poses = _c(poses, np.float32).reshape(-1, self.nb, POSE); B = poses.shape[0]
+        cams = _c(cams, np.float32).reshape(B, CAM)
+        depth = np.empty((B, int(h), int(w)), np.uint16); body = np.empty((B, int(h), int(w)), np.int8) if want_body else None
+        self._chk(self.L.ht_render_mesh_depth(self.h, _f(poses), _f(cams), int(w), int(h), float(far), float(pixel_offset), B, depth.ctypes.data_as(C.POINTER(C.c_uint16)),
+                                              body.ctypes.data_as(C.POINTER(C.c_int8)) if want_body else None))
+        return (depth, body) if want_body else depth
+
+    def render_mesh_depth_dev(self, d_poses, d_cams, w, h, far, pixel_offset, B, d_depth, d_body=None, stream=None):
+        """ht_render_mesh_depth_dev: device pointers, asynchronous on `stream`."""
+        self._chk(self.L.ht_render_mesh_depth_dev(self.h, d_poses, d_cams, int(w), int(h), float(far), float(pixel_offset), int(B), d_depth, d_body, stream))
+
     def scale(self, s):
         """HandTracker::scale (handtrack.h:591): both models of every slot grow by the factor s."""
         self._chk(self.L.ht_scale(self.h, float(s)))
@@ -604,3 +624,56 @@ def expected_cnn(pose, cam):
     if r != 0:
         raise HTError("ht_expected_cnn failed with status %d" % r)
     return out
+
+
+class HostModel:
+    """A hand model that is not being tracked (ht_model_*, host only): the mesh ray cast's definition and its frames."""
+
+    def __init__(self, path, hand_tweaks=True):
+        self.L = load()
+        self.m = C.c_void_p()
+        r = self.L.ht_model_open(str(path).encode(), 1 if hand_tweaks else 0, C.byref(self.m))
+        if r:
+            self.L.ht_model_error.restype = C.c_char_p
+            msg = self.L.ht_model_error(self.m).decode(); self.close()
+            raise HTError("ht_model_open(%s): %s" % (path, msg))
+        nb, nj = C.c_int(), C.c_int()
+        self.L.ht_model_counts(self.m, C.byref(nb), C.byref(nj))
+        self.nb, self.nj = nb.value, nj.value
+
+    def close(self):
+        if self.m:
+            self.L.ht_model_close(self.m); self.m = C.c_void_p()
+
+    def scale(self, s):
+        if self.L.ht_model_scale(self.m, float(s)):
+            raise HTError("ht_model_scale: bad argument")
+
+    def sdmesh(self, body):
+        """corner positions [3 t, 3] of body's subdivision mesh, in the bone's rig frame"""
+        n = C.c_int()
+        self.L.ht_model_body_sdmesh(self.m, int(body), C.byref(n), None)
+        v = np.empty((n.value, 3), np.float32)
+        self.L.ht_model_body_sdmesh(self.m, int(body), None, _f(v))
+        return v
+
+    def com(self, body):
+        c = np.empty(3, np.float32)
+        self.L.ht_model_body(self.m, int(body), None, None, None, _f(c), None)
+        return c
+
+    def hitcheck_mesh(self, poses, v0, v1):
+        """(impact[3], normal[3], body, triangle) of the segment v0 -> v1 against the subdivision surface at poses [nb,7]"""
+        poses = _c(poses, np.float32); v0 = _c(v0, np.float32); v1 = _c(v1, np.float32)
+        imp = np.empty(3, np.float32); nrm = np.empty(3, np.float32); b, t = C.c_int(), C.c_int()
+        if self.L.ht_model_hitcheck_mesh(self.m, _f(poses), _f(v0), _f(v1), _f(imp), _f(nrm), C.byref(b), C.byref(t)):
+            raise HTError("ht_model_hitcheck_mesh: bad argument")
+        return imp, nrm, b.value, t.value
+
+    def render_mesh(self, poses, cam, w, h, far=4.0, pixel_offset=0.0):
+        """one frame of the definition: (depth u16[h,w], body int8[h,w])"""
+        poses = _c(poses, np.float32); cam = _c(cam, np.float32)
+        depth = np.empty((int(h), int(w)), np.uint16); body = np.empty((int(h), int(w)), np.int8)
+        if self.L.ht_model_render_mesh(self.m, _f(poses), _f(cam), int(w), int(h), float(far), float(pixel_offset), depth.ctypes.data_as(C.POINTER(C.c_uint16)), body.ctypes.data_as(C.POINTER(C.c_int8))):
+            raise HTError("ht_model_render_mesh: bad argument")
+        return depth, body

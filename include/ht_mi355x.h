@@ -261,6 +261,23 @@ int ht_model_body(const ht_model *m, int body, int *nverts, int *ntris, int *npl
 int ht_model_body_mesh(const ht_model *m, int body, float *verts, int *tris);
 int ht_model_body_sdmesh(const ht_model *m, int body, int *nverts, float *verts);      /* PhysModel::sdmeshes (physmodel.h:258): the twice-subdivided control cage flat-shaded, three corner positions per triangle in the bone's rig frame; verts NULL: the count only */
 int ht_model_hitcheck(const ht_model *m, const float *poses, const float *v0, const float *v1, float *impact3, float *normal3, int *body);
+/* The ray cast against the subdivision surface (an addition: the application draws these meshes with OpenGL and reads the depth buffer back,
+ * synthetic-tracker.cpp:164-165; this is the software statement of that source, as FakeDepth is for the hulls).
+ * ht_model_hitcheck_mesh  for bodies at centre-of-mass poses [nb][7]: every triangle of sdmeshes[b] (ht_model_body_sdmesh, stored order) is tested with
+ *                    PolyHitCheck (geometric.h:263-273) on the whole segment v0 -> v1 in the frame of its mesh pose Pose{pos_b - qrot(q_b, com_b), q_b}
+ *                    (GetMeshes, physmodel.h:297-298), with its PolyPlane (geometric.h:247-260) made once per model in float: a candidate iff d0 > 0,
+ *                    d1 < 0 and the three determinants are >= 0.  The candidate with the smallest d0 / (d0 - d1) wins, the first in (body, triangle)
+ *                    order on a tie; impact = U_b * (a + (c - a) * d0 / (d0 - d1)), normal = qrot(q_b, plane.xyz).  Nothing hit: *body = *tri = -1,
+ *                    impact = v1.  The segment is never shortened, so a triangle's candidacy depends on no other triangle.
+ * ht_model_render_mesh    one w x h frame of it: pixel (x, y) = (uint16)(impact.z / depth_scale) for the segment from the origin to
+ *                    deprojectz((x + pixel_offset, y + pixel_offset), far) (misc_image.h:48); a plain loop over pixels, bodies and triangles, the
+ *                    definition ht_render_mesh_depth equals bit for bit.  pixel_offset in [0, 1]: 0 is FakeDepth's convention, 0.5 where OpenGL samples.
+ *                    body (optional) [h][w], -1 = background.  cam12: focal, principal point and depth_scale are used.
+ * ht_model_scale     replaces  PhysModel::scale (physmodel.h:304-319) for this view's geometry (hull vertices, plane offsets, sdmeshes, centres of mass),
+ *                    with ht_scale's operations: a host model and a context scaled alike render the same bits. */
+int ht_model_hitcheck_mesh(const ht_model *m, const float *poses, const float *v0, const float *v1, float *impact3, float *normal3, int *body, int *tri);
+int ht_model_render_mesh(const ht_model *m, const float *poses, const float *cam12, int w, int h, float far, float pixel_offset, uint16_t *depth, int8_t *body);
+int ht_model_scale(ht_model *m, float s);
 
 /* ---- segmentation: the step before the tracker for full-size frames --------------------------------------------------
  * ht_segment_vr       replaces  Image<unsigned short> HandSegmentVR(const Image<unsigned short> &depth, int entry_options = 0xF,
@@ -286,6 +303,15 @@ int ht_segment_vr_dev(ht_ctx *ctx, const uint16_t *d_depth, const float *d_cams,
  * ht_render_depth_dev the same on device buffers, asynchronous on `stream`. */
 int ht_render_depth(ht_ctx *ctx, const float *poses, const float *cams, int w, int h, float far, int B, uint16_t *depth, int8_t *body);
 int ht_render_depth_dev(ht_ctx *ctx, const float *d_poses, const float *d_cams, int w, int h, float far, int B, uint16_t *d_depth, int8_t *d_body, void *stream);
+/* ht_render_mesh_depth     the hand's subdivision surface instead of its hulls (GetMeshes(true), the application's default depth source,
+ *                     synthetic-tracker.cpp:164-165): ht_model_render_mesh for B frames, bit-identical to it, with the context's model as ht_create
+ *                     built it and ht_scale left it.  poses [B][nb][7], cams [B][12], depth [B][h][w], body (optional) [B][h][w] as ht_render_depth;
+ *                     w, h in [1, 4096], far > 0, pixel_offset finite and in [0, 1] (HT_ERR_ARG otherwise).  The application's GL frames are
+ *                     pixel_offset 0.5, far 0.85; frames interchangeable with ht_render_depth's are pixel_offset 0, far 4.  B is not bounded by
+ *                     max_batch; B = 0 does nothing.  HT_ERR_STATE for a context without a hand model, or whose model file holds no meshes.
+ * ht_render_mesh_depth_dev the same on device buffers, asynchronous on `stream`. */
+int ht_render_mesh_depth(ht_ctx *ctx, const float *poses, const float *cams, int w, int h, float far, float pixel_offset, int B, uint16_t *depth, int8_t *body);
+int ht_render_mesh_depth_dev(ht_ctx *ctx, const float *d_poses, const float *d_cams, int w, int h, float far, float pixel_offset, int B, uint16_t *d_depth, int8_t *d_body, void *stream);
 
 /* ---- annotation fit loop ---------------------------------------------------------------------------------------------
  * ht_slowfit          replaces  void HandTracker::slowfit(const std::vector<float3> &points, int hold, const std::vector<Pose> &refpose,

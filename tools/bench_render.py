@@ -60,14 +60,69 @@ def user_pos(poses, com):
     return poses[..., :3] + np.stack([m[r][0] * v[..., 0] + m[r][1] * v[..., 1] + m[r][2] * v[..., 2] for r in range(3)], -1)
 
 
+def main_mesh(a):
+    """--mesh: ht_render_mesh_depth_dev beside ht_render_depth_dev on the same poses in the same run, the no-body-in-view floor, and the same batch's tracking step"""
+    dev = torch.device("cuda:0")
+    torch.cuda.set_device(dev)
+    s = torch.cuda.Stream(device=dev)
+    z = np.load(os.path.join(ROOT, "bench_data", "frames1024.npz"))
+    z5 = np.load(os.path.join(ROOT, "bench_data", "frames5_256.npz"))
+    hands = {17: z["gtpose"], 26: z5["startpose"]}
+    w, h = 320, 240
+    res = {"device": torch.cuda.get_device_name(dev), "steps": a.steps, "warmup": a.warmup, "w": w, "h": h, "render": [], "usage": {}}
+    for k, v in hb.resource_usage().items():
+        if "render" in k:
+            res["usage"][k] = {x: v.get(x) for x in ("VGPRs", "SGPRs", "AGPRs", "ScratchSize", "LDS Size", "Occupancy")}
+    for nb, model in ((17, M17), (26, M26)):
+        ctx = native.Context(model, 1024 if nb == 17 else 1)
+        try:
+            if nb == 17:
+                ctx.load_weights(W.make_cnnb()); ctx.set_params(microforce=3.0, mainthreadpasses=3); ctx.reserve_points(w * h // 4)
+            for B in ((1024,) if a.quick else (1024, 8192)):
+                p = hands[nb][np.arange(B) % len(hands[nb])].copy()
+                away = p.copy(); away[:, :, 2] -= 10.0
+                tp = torch.from_numpy(p).to(dev); ta = torch.from_numpy(away).to(dev); tc = torch.from_numpy(cam_of(w, h, B)).to(dev)
+                td = torch.empty((B, h, w), dtype=torch.int16, device=dev)
+                row = {"bones": nb, "B": B}
+                for name, off, far in (("mesh_off0_far4", 0.0, 4.0), ("mesh_off05_far085", 0.5, 0.85)):
+                    row[name + "_ms"] = round(time_it(lambda: ctx.render_mesh_depth_dev(tp.data_ptr(), tc.data_ptr(), w, h, far, off, B, td.data_ptr(), None, s.cuda_stream), s, a.steps, a.warmup), 4)
+                    row[name + "_hand_pixel_fraction"] = round(float((td[:64].cpu().numpy().view(np.uint16) < int(far * 1000) - 1).mean()), 4)
+                row["mesh_empty_ms"] = round(time_it(lambda: ctx.render_mesh_depth_dev(ta.data_ptr(), tc.data_ptr(), w, h, 4.0, 0.0, B, td.data_ptr(), None, s.cuda_stream), s, a.steps, a.warmup), 4)
+                row["hull_empty_ms"] = round(time_it(lambda: ctx.render_depth_dev(ta.data_ptr(), tc.data_ptr(), w, h, 4.0, B, td.data_ptr(), None, s.cuda_stream), s, a.steps, a.warmup), 4)
+                row["hull_ms"] = round(time_it(lambda: ctx.render_depth_dev(tp.data_ptr(), tc.data_ptr(), w, h, 4.0, B, td.data_ptr(), None, s.cuda_stream), s, a.steps, a.warmup), 4)
+                if nb == 17 and B == 1024:      # the tracking step these frames feed (hull frames, as section 17 measured it)
+                    ts = torch.from_numpy(z["startpose"]).to(dev); out = torch.empty((B, 17, 7), dtype=torch.float32, device=dev)
+                    ctx.update_frames_dev(td.data_ptr(), tc.data_ptr(), w, h, 0.17, ts.data_ptr(), B, out.data_ptr(), s.cuda_stream)
+                    s.synchronize()
+                    row["update_frames_dev_ms"] = round(time_it(lambda: ctx.update_frames_dev(td.data_ptr(), tc.data_ptr(), w, h, 0.17, None, B, out.data_ptr(), s.cuda_stream), s, max(4, a.steps // 4), 1), 3)
+                    row["mesh_over_update"] = round(row["mesh_off0_far4_ms"] / row["update_frames_dev_ms"], 4)
+                row["mesh_over_hull"] = round(row["mesh_off0_far4_ms"] / row["hull_ms"], 3)
+                print(json.dumps(row), flush=True)
+                res["render"].append(row)
+                del tp, ta, tc, td
+        finally:
+            ctx.close()
+    out_path = a.out if a.out != DEFAULT_OUT else os.path.join(ROOT, "profiles", "r08_render_mesh.json")
+    os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
+    with open(out_path, "w") as f:
+        json.dump(res, f, indent=1)
+        f.write("\n")
+
+
+DEFAULT_OUT = os.path.join(ROOT, "profiles", "r07_render.json")
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--mesh", action="store_true", help="measure ht_render_mesh_depth_dev (the subdivision surface) beside the hull renderer and the tracking step")
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r07_render.json"))
+    ap.add_argument("--out", default=DEFAULT_OUT)
     ap.add_argument("--quick", action="store_true", help="one batch size per case (a check that everything runs)")
     ap.add_argument("--loop-steps", type=int, default=32)
     a = ap.parse_args()
+    if a.mesh:
+        return main_mesh(a)
     dev = torch.device("cuda:0")
     torch.cuda.set_device(dev)
     s = torch.cuda.Stream(device=dev)

@@ -69,6 +69,7 @@ def main():
     ap.add_argument("--seed", type=int, default=SEED)
     ap.add_argument("--json", default=None)
     ap.add_argument("--rate-steps", type=int, default=2048)
+    ap.add_argument("--mesh", action="store_true", help="render the training frames from the subdivision surface (ht_render_mesh_depth_dev, pixel offset 0, far 4) instead of the hulls")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     d = np.load(os.path.join(ROOT, "bench_data", "frames1024.npz"))
@@ -90,7 +91,10 @@ def main():
         with torch.cuda.stream(s):
             tp.copy_(torch.from_numpy(poses))      # in the stream's order: the previous round may still read the poses
             if timed: ev[0].record(s)
-            ctx.render_depth_dev(tp.data_ptr(), cams.data_ptr(), 320, 240, 4.0, B, depth.data_ptr(), None, s.cuda_stream)
+            if a.mesh:
+                ctx.render_mesh_depth_dev(tp.data_ptr(), cams.data_ptr(), 320, 240, 4.0, 0.0, B, depth.data_ptr(), None, s.cuda_stream)
+            else:
+                ctx.render_depth_dev(tp.data_ptr(), cams.data_ptr(), 320, 240, 4.0, B, depth.data_ptr(), None, s.cuda_stream)
             if timed: ev[1].record(s)
             assert L.ht_segment_vr_dev(ctx.h, depth.data_ptr(), cams.data_ptr(), 320, 240, B, 0xF, 0.1, 0.70, 0.17, tiles.data_ptr(), tcams.data_ptr(), s.cuda_stream) == 0
             if timed: ev[2].record(s)
