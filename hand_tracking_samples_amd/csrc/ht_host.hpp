@@ -75,7 +75,7 @@ struct ht_ctx
 	float *d_user_lin = nullptr; unsigned short *d_user_pos = nullptr; float *d_user_ang = nullptr; int *d_user_n = nullptr;      // [B][lin_cap][HT_ROW], [B][lin_cap], [B][ang_cap][HT_AROW], [4][B]
 	int user_lin_cap = 0, user_ang_cap = 0;
 	ht_comm_state *comm = nullptr;                               // multi-GPU pose gather (ht_comm_init), null on a single-GPU host
-	char *d_render = nullptr; size_t render_cap = 0;             // ht_render_depth's staging (poses, cameras, frames, body labels), grown to the largest call (dev_grow)
+	char *d_render = nullptr; size_t render_cap = 0;             // both renderers' staging (ht_render_depth, ht_render_mesh_depth: poses, cameras, frames, body labels), grown to the largest call (dev_grow)
 	char *d_labels = nullptr; size_t labels_cap = 0;             // ht_expected_cnn_batch's staging (poses, cameras, labels, image points, key angles), grown to the largest call (dev_grow)
 	std::vector<float4> render_planes; std::vector<float> render_radii;      // the hull planes ht_render_depth last derived its per-body cull radii from, and those radii (2 per body)
 	// ht_render_mesh_depth: the subdivision meshes' corners [t][9] over all bodies (ht_scale rewrites them), the first triangle of every body, the device rows
@@ -116,6 +116,24 @@ static inline int ht_sync_check(ht_ctx *ctx, hipStream_t s)
 {
 	HIPCHK(ctx, hipStreamSynchronize(s));
 	HIPCHK(ctx, hipGetLastError());
+	return HT_OK;
+}
+
+// A synchronous entry point around its _dev form: the segments laid out 256-aligned in a buffer that follows the largest call (dev_grow), the inputs uploaded,
+// call(stream) run on the device pointers, the outputs downloaded, the context's stream waited for.  A segment without a host pointer (an optional output the
+// caller did not ask for) takes no room and keeps a null device pointer.
+struct ht_seg { void *host; size_t bytes; bool out; char *dev; };
+template <class F> static inline int ht_staged_call(ht_ctx *ctx, char **buf, size_t *cap, ht_seg *seg, int n, F call)
+{
+	size_t off[8], end = 0;      // n <= 8
+	for (int i = 0; i < n; i++) { off[i] = (end + 255) & ~(size_t)255; if (seg[i].host) end = off[i] + seg[i].bytes; }
+	{ const int r = dev_grow(ctx, buf, cap, end); if (r) return r; }
+	for (int i = 0; i < n; i++) seg[i].dev = seg[i].host ? *buf + off[i] : nullptr;
+	hipStream_t s = ctx->stream;
+	for (int i = 0; i < n; i++) if (seg[i].host && !seg[i].out) HIPCHK(ctx, hipMemcpyAsync(seg[i].dev, seg[i].host, seg[i].bytes, hipMemcpyHostToDevice, s));
+	{ const int r = call(s); if (r) return r; }
+	for (int i = 0; i < n; i++) if (seg[i].host && seg[i].out) HIPCHK(ctx, hipMemcpyAsync(seg[i].host, seg[i].dev, seg[i].bytes, hipMemcpyDeviceToHost, s));
+	HIPCHK(ctx, hipStreamSynchronize(s));
 	return HT_OK;
 }
 

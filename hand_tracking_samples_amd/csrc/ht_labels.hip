@@ -143,30 +143,18 @@ extern "C" int ht_expected_cnn_dev(ht_ctx *ctx, const float *d_poses, const floa
 	return HT_OK;
 }
 
-// the synchronous variant stages through one device buffer of its own, grown to the largest call (no tracker slot: B is not bounded by max_batch)
+// the synchronous variant stages through one device buffer of its own (ht_staged_call; no tracker slot: B is not bounded by max_batch)
 extern "C" int ht_expected_cnn_batch(ht_ctx *ctx, const float *poses, const float *cams, int B, int flags, float *expected, float *image_points, float *vals)
 {
 	CHECK_READY(ctx);
 	{ const int r = lb_check_args(ctx, poses, cams, B, expected); if (r) return r; }
 	if (flags & ~HT_LABELS_SEGMENT_FRAME) { ctx->err = "ht_expected_cnn: unknown flags"; return HT_ERR_ARG; }
 	if (B == 0) return HT_OK;
-	const size_t nb = (size_t)ctx->model.nb, n = (size_t)B;
-	auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
-	const size_t o_cams = up(n * nb * HT_POSE * sizeof(float)), o_exp = o_cams + up(n * HT_CAM * sizeof(float)), o_ip = o_exp + up(n * HT_CNN_OUT * sizeof(float));
-	const size_t o_vals = o_ip + up(n * 16 * sizeof(float)), bytes = o_vals + n * 16 * sizeof(float);
-	{ const int r = dev_grow(ctx, &ctx->d_labels, &ctx->labels_cap, bytes); if (r) return r; }
-	char *base = ctx->d_labels;
-	float *d_poses = (float *)base, *d_cams = (float *)(base + o_cams), *d_exp = (float *)(base + o_exp);
-	float *d_ip = image_points ? (float *)(base + o_ip) : nullptr, *d_vals = vals ? (float *)(base + o_vals) : nullptr;
-	hipStream_t s = ctx->stream;
-	HIPCHK(ctx, hipMemcpyAsync(d_poses, poses, n * nb * HT_POSE * sizeof(float), hipMemcpyHostToDevice, s));
-	HIPCHK(ctx, hipMemcpyAsync(d_cams, cams, n * HT_CAM * sizeof(float), hipMemcpyHostToDevice, s));
-	{ const int r = ht_expected_cnn_dev(ctx, d_poses, d_cams, B, flags, d_exp, d_ip, d_vals, s); if (r) return r; }
-	HIPCHK(ctx, hipMemcpyAsync(expected, d_exp, n * HT_CNN_OUT * sizeof(float), hipMemcpyDeviceToHost, s));
-	if (image_points) HIPCHK(ctx, hipMemcpyAsync(image_points, d_ip, n * 16 * sizeof(float), hipMemcpyDeviceToHost, s));
-	if (vals) HIPCHK(ctx, hipMemcpyAsync(vals, d_vals, n * 16 * sizeof(float), hipMemcpyDeviceToHost, s));
-	HIPCHK(ctx, hipStreamSynchronize(s));
-	return HT_OK;
+	const size_t n = (size_t)B;
+	ht_seg seg[5] = { { (void *)poses, n * ctx->model.nb * HT_POSE * sizeof(float), false }, { (void *)cams, n * HT_CAM * sizeof(float), false },
+	                  { expected, n * HT_CNN_OUT * sizeof(float), true }, { image_points, n * 16 * sizeof(float), true }, { vals, n * 16 * sizeof(float), true } };
+	return ht_staged_call(ctx, &ctx->d_labels, &ctx->labels_cap, seg, 5, [&](hipStream_t s)
+	                      { return ht_expected_cnn_dev(ctx, (const float *)seg[0].dev, (const float *)seg[1].dev, B, flags, (float *)seg[2].dev, (float *)seg[3].dev, (float *)seg[4].dev, s); });
 }
 
 // cnn_input (handtrack.h:700) of B 64x64 tiles: k_prepare without a point cloud, as the full-frame update path runs it (ht_solver_api.hip)

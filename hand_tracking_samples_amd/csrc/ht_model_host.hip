@@ -96,7 +96,6 @@ extern "C" int ht_model_hitcheck(const ht_model *m, const float *poses, const fl
 		const float *p = poses + 7 * b;
 		const xf pose = XF(V3(p[0], p[1], p[2]), V4(p[3], p[4], p[5], p[6])), inv = inverse(pose);
 		v3 a = apply(inv, v0w), c = apply(inv, impact), n = V3(0, 0, 0);
-		const v3 c_in = c;
 		bool hit = true;
 		const std::vector<float> &pl = m->planes[b];
 		for (size_t k = 0; k + 3 < pl.size(); k += 4)      // ConvexHitCheck geometric.h:275-297
@@ -108,7 +107,6 @@ extern "C" int ht_model_hitcheck(const ht_model *m, const float *poses, const fl
 			const v3 x = a + ((c - a) * d0) / (d0 - d1);
 			if (d0 >= 0) { n = xyz(plane); a = x; } else c = x;
 		}
-		(void)c_in;
 		if (hit) { impact = apply(pose, a); normal = qrot(pose.q, n); who = b; }
 	}
 	if (impact3) { impact3[0] = impact.x; impact3[1] = impact.y; impact3[2] = impact.z; }

@@ -521,16 +521,20 @@ class Context:
                                        tiles.ctypes.data_as(C.POINTER(C.c_uint16)), _f(co)))
         return tiles, co
 
-    def render_depth(self, poses, cams, w, h, far=4.0, want_body=False):
-        """FakeDepth (synthetic-tracker.cpp:69-76) for a batch: the context's hand at centre-of-mass poses [B,nb,7], cameras [B,12] ->
-        depth u16[B,h,w] (and the hit body int8[B,h,w], -1 = background, with want_body)."""
+    def _render(self, entry, poses, cams, w, h, far, extra, want_body):
+        """a renderer's synchronous entry: `extra` are its arguments between far and B"""
         poses = _c(poses, np.float32).reshape(-1, self.nb, POSE); B = poses.shape[0]
         cams = _c(cams, np.float32).reshape(B, CAM)
         depth = np.empty((B, int(h), int(w)), np.uint16)
         body = np.empty((B, int(h), int(w)), np.int8) if want_body else None
-        self._chk(self.L.ht_render_depth(self.h, _f(poses), _f(cams), int(w), int(h), float(far), B, depth.ctypes.data_as(C.POINTER(C.c_uint16)),
-                                         body.ctypes.data_as(C.POINTER(C.c_int8)) if want_body else None))
+        self._chk(entry(self.h, _f(poses), _f(cams), int(w), int(h), float(far), *extra, B, depth.ctypes.data_as(C.POINTER(C.c_uint16)),
+                        body.ctypes.data_as(C.POINTER(C.c_int8)) if want_body else None))
         return (depth, body) if want_body else depth
+
+    def render_depth(self, poses, cams, w, h, far=4.0, want_body=False):
+        """FakeDepth (synthetic-tracker.cpp:69-76) for a batch: the context's hand at centre-of-mass poses [B,nb,7], cameras [B,12] ->
+        depth u16[B,h,w] (and the hit body int8[B,h,w], -1 = background, with want_body)."""
+        return self._render(self.L.ht_render_depth, poses, cams, w, h, far, (), want_body)
 
     def render_depth_dev(self, d_poses, d_cams, w, h, far, B, d_depth, d_body=None, stream=None):
         """ht_render_depth_dev: device pointers (poses [B,nb,7], cams [B,12] -> depth u16[B,h,w], body int8[B,h,w] or None), asynchronous on `stream`."""
@@ -540,12 +544,7 @@ class Context:
         """The hand's subdivision surface (GetMeshes(true)) ray-cast for a batch, bit-identical to HostModel.render_mesh: poses [B,nb,7], cameras [B,12] ->
         depth u16[B,h,w] (and the hit body int8[B,h,w], -1 = background, with want_body).  pixel_offset 0 / far 4 matches render_depth's frames,
         0.5 / 0.85 the application's GL frames."""
-        poses = _c(poses, np.float32).reshape(-1, self.nb, POSE); B = poses.shape[0]
-        cams = _c(cams, np.float32).reshape(B, CAM)
-        depth = np.empty((B, int(h), int(w)), np.uint16); body = np.empty((B, int(h), int(w)), np.int8) if want_body else None
-        self._chk(self.L.ht_render_mesh_depth(self.h, _f(poses), _f(cams), int(w), int(h), float(far), float(pixel_offset), B, depth.ctypes.data_as(C.POINTER(C.c_uint16)),
-                                              body.ctypes.data_as(C.POINTER(C.c_int8)) if want_body else None))
-        return (depth, body) if want_body else depth
+        return self._render(self.L.ht_render_mesh_depth, poses, cams, w, h, far, (float(pixel_offset),), want_body)
 
     def render_mesh_depth_dev(self, d_poses, d_cams, w, h, far, pixel_offset, B, d_depth, d_body=None, stream=None):
         """ht_render_mesh_depth_dev: device pointers, asynchronous on `stream`."""

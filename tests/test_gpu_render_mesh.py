@@ -1,7 +1,7 @@
 """The device mesh renderer (ht_render_mesh_depth, csrc/ht_render_mesh.hip) held bit for bit, depth and body map, to the host's definition
 (ht_model_render_mesh: a plain loop over pixels, bodies and triangles with no culling): small frames that are no multiple of the 16x4 tile with six
 cameras and poses per call (truth, across the border, very close, far, the camera origin inside a body's bound, edge-on), both pixel offsets and far
-points, 17 and 26 bones; two full 320x240 frames; the empty-tile path; after ht_scale; and render -> track on one stream."""
+points, 17 and 26 bones; two full 320x240 frames; the empty-tile path; after ht_scale; the _dev entry on a side stream; and render -> track on one stream."""
 import ctypes as C
 import os
 
@@ -158,6 +158,24 @@ def test_after_scale_device_equals_a_host_model_scaled_alike():
         assert np.array_equal(got, want) and np.array_equal(gbody, wbody)
     finally:
         m.close(); ctx.close()
+
+
+def test_render_mesh_dev_on_a_side_stream_equals_sync(pair):
+    """ht_render_mesh_depth_dev on a non-default stream, into tensors pre-filled with a sentinel: frames and labels equal the synchronous entry's exactly"""
+    nb, ctx, m = pair
+    w, h, off, far = 33, 25, 0.5, 0.85
+    poses = _six(nb, 3); cams = _cams(w, h, 6)
+    want, wbody = ctx.render_mesh_depth(poses, cams, w, h, far, off, want_body=True)
+    dev = torch.device("cuda:0")
+    tp = torch.from_numpy(poses).to(dev); tc = torch.from_numpy(cams).to(dev)
+    td = torch.full((6, h, w), 7, dtype=torch.int16, device=dev); tb = torch.full((6, h, w), 5, dtype=torch.int8, device=dev)
+    s = torch.cuda.Stream(device=dev)
+    s.wait_stream(torch.cuda.current_stream(dev))
+    with torch.cuda.stream(s):
+        ctx.render_mesh_depth_dev(tp.data_ptr(), tc.data_ptr(), w, h, far, off, 6, td.data_ptr(), tb.data_ptr(), s.cuda_stream)
+    s.synchronize()
+    assert np.array_equal(td.cpu().numpy().view(np.uint16), want)
+    assert np.array_equal(tb.cpu().numpy(), wbody)
 
 
 def test_render_mesh_then_track_on_one_stream(weights):
