@@ -313,6 +313,18 @@ extern "C" int ht_cnn_get_weights(ht_ctx *ctx, float *w, size_t n)
 	HIPCHK(ctx, hipMemcpy(w, ctx->d_weights, n * sizeof(float), hipMemcpyDeviceToHost));
 	return HT_OK;
 }
+// Test aid: the layer outputs and the errors of the training arena as the latest step left them (layout: ht_launch_train_step, csrc/ht_train.hip)
+extern "C" int ht_debug_train_buffers(ht_ctx *ctx, float *act, size_t n_act, float *err, size_t n_err)
+{
+	CHECK_READY(ctx);
+	if (!act || !err) return HT_ERR_ARG;
+	if (n_act != ht_train_act_floats() || n_err != ht_train_err_floats()) { ctx->err = "ht_debug_train_buffers: expected ht_train_act_floats() / ht_train_err_floats() values (74768 / 64272)"; return HT_ERR_ARG; }
+	if (!ctx->d_train) { ctx->err = "ht_debug_train_buffers: no training step has run"; return HT_ERR_STATE; }
+	HIPCHK(ctx, ht_sync_all(ctx));      // also a ht_cnn_train_dev on a caller's stream
+	HIPCHK(ctx, hipMemcpy(act, ctx->d_train, n_act * sizeof(float), hipMemcpyDeviceToHost));
+	HIPCHK(ctx, hipMemcpy(err, ctx->d_train + n_act, n_err * sizeof(float), hipMemcpyDeviceToHost));
+	return HT_OK;
+}
 // Label synthesis, host only.  GatherHandExpectedCNN (handtrack.h:160-173): 8 landmark heat-maps (ImageFeaturePoints :92-96, RenderHeatMap /
 // NormalizeHeatMap misc_image.h:246-272) and 16 one-dimensional maps of the key angles (HandPoseToKeyAngleSet handtrack.h:132-151,
 // Render1DHeatMaps misc_image.h:281-295), as bytes scaled by 1/255.  atan2 / asin / acos / exp / pow without std:: are the C double functions there.

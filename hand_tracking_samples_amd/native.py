@@ -15,6 +15,9 @@ HT_OK = 0
 CNN_IN, CNN_OUT, CNNB_COUNT, POSE, STATE, CAM, ANALYSIS = 4096, 2304, 9458400, 7, 13, 12, 84
 MAXPTS, ROW, CONTACT = 4096, 16, 12      # HT_MAX_POINTS
 LABELS_SEGMENT_FRAME = 1      # HT_LABELS_SEGMENT_FRAME
+# ht_debug_train_buffers: (name, floats, shape) of the segments of act and err, in order (None: padding)
+TRAIN_ACT = (("a1", 57600, (16, 60, 60)), ("a3", 3600, (16, 15, 15)), ("a5", 9216, (64, 12, 12)), ("a6", 2304, (2304,)), ("a8", 2048, (2048,)))
+TRAIN_ERR = (("e9", 2304, (2304,)), ("e7", 2048, (2048,)), ("e6", 2304, (2304,)), ("part3", 57600, (16, 3600)), ("sqp", 9, (9,)), (None, 7, None))
 
 # every symbol include/ht_mi355x.h declares (checked by tests/test_abi.py)
 SYMBOLS = (
@@ -24,7 +27,7 @@ SYMBOLS = (
     "ht_model_open", "ht_model_close", "ht_model_error", "ht_model_counts", "ht_model_body", "ht_model_body_mesh", "ht_model_body_sdmesh", "ht_model_hitcheck", "ht_model_hitcheck_mesh", "ht_model_render_mesh", "ht_model_scale", "ht_render_mesh_depth", "ht_render_mesh_depth_dev",
     "ht_tracker_reset", "ht_get_state", "ht_set_state", "ht_get_tracker_flags", "ht_set_tracker_flags", "ht_update_sync", "ht_update_dev", "ht_update_frames_sync", "ht_update_frames_dev", "ht_update_direct_sync", "ht_update_direct_dev", "ht_update_cnn_model_sync", "ht_get_cnn_results", "ht_get_cnn_layers", "ht_frames_overflow", "ht_reserve_points", "ht_point_capacity", "ht_capacity_events", "ht_segment_vr", "ht_segment_vr_dev", "ht_render_depth", "ht_render_depth_dev", "ht_slowfit", "ht_set_points", "ht_fit_rows", "ht_physics_update",
     "ht_stage_prepare", "ht_stage_decode", "ht_stage_fit_error", "ht_stage_cloud_rows", "ht_stage_contacts", "ht_stage_fit",
-    "ht_stage_multistep", "ht_stage_multistep_range", "ht_stage_scratch_unibody", "ht_stage_chamber", "ht_profile_enable", "ht_profile_read", "ht_debug_solve_stats", "ht_debug_contact_stats", "ht_debug_solver_build", "ht_debug_reset_flags", "ht_debug_reset_organisation", "ht_update_passes_sync", "ht_job_start", "ht_job_poll", "ht_job_wait", "ht_job_collect", "ht_debug_contact_kernel", "ht_contact_capacity", "ht_debug_solve_tables", "ht_debug_solve_tables_header",
+    "ht_stage_multistep", "ht_stage_multistep_range", "ht_stage_scratch_unibody", "ht_stage_chamber", "ht_profile_enable", "ht_profile_read", "ht_debug_solve_stats", "ht_debug_contact_stats", "ht_debug_solver_build", "ht_debug_reset_flags", "ht_debug_reset_organisation", "ht_update_passes_sync", "ht_job_start", "ht_job_poll", "ht_job_wait", "ht_job_collect", "ht_debug_contact_kernel", "ht_contact_capacity", "ht_debug_solve_tables", "ht_debug_solve_tables_header", "ht_debug_train_buffers",
     "ht_comm_available", "ht_comm_unique_id", "ht_comm_init", "ht_comm_info", "ht_gather_poses_dev", "ht_gather_wait", "ht_gather_wait_host", "ht_comm_destroy",
 )
 
@@ -102,6 +105,7 @@ def load(build_if_missing=True):
     L.ht_scale.argtypes = [vp, C.c_float]
     L.ht_cnn_train.argtypes = [vp, fp, fp, C.c_int, C.c_float, fp]
     L.ht_cnn_get_weights.argtypes = [vp, fp, C.c_size_t]
+    L.ht_debug_train_buffers.argtypes = [vp, fp, C.c_size_t, fp, C.c_size_t]
     L.ht_expected_cnn.argtypes = [fp, fp, fp]
     L.ht_expected_cnn_batch.argtypes = [vp, fp, fp, C.c_int, C.c_int, fp, fp, fp]
     L.ht_expected_cnn_dev.argtypes = [vp, vp, vp, C.c_int, C.c_int, vp, vp, vp, vp]
@@ -600,6 +604,21 @@ class Context:
         w = np.empty(9458400, np.float32)
         self._chk(self.L.ht_cnn_get_weights(self.h, _f(w), w.size))
         return w
+
+    def cnn_train_buffers(self):
+        """ht_debug_train_buffers: what the latest training step left behind, as named views of two arrays: the layer outputs a1 [16,60,60],
+        a3 [16,15,15], a5 [64,12,12], a6 [2304], a8 [2048], the errors e9 [2304], e7 [2048], e6 [2304], conv2's backward as partial sums
+        part3 [16,3600] (one per group of four output channels) and the soft-max blocks' sums of squares sqp [9]."""
+        act = np.empty(sum(n for _, n, _ in TRAIN_ACT), np.float32); err = np.empty(sum(n for _, n, _ in TRAIN_ERR), np.float32)
+        self._chk(self.L.ht_debug_train_buffers(self.h, _f(act), act.size, _f(err), err.size))
+        out = {}
+        for buf, table in ((act, TRAIN_ACT), (err, TRAIN_ERR)):
+            o = 0
+            for name, n, shape in table:
+                if name:
+                    out[name] = buf[o:o + n].reshape(shape)
+                o += n
+        return out
 
 
 def comm_available():

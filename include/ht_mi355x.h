@@ -422,6 +422,15 @@ int ht_debug_contact_kernel(ht_ctx *ctx, int which);
  * 2 = only the pose-only tables (joint groups, angular records, block couplings), on the side stream the cloud rows do not use: also measured slower.
  * Where the tables are made, never what they hold: results are identical bit for bit (tests/test_gpu_solve_tables.py). */
 int ht_debug_solve_tables(ht_ctx *ctx, int mode);
+/* Test aid: the layer outputs and the errors that the latest training step (ht_cnn_train / ht_cnn_train_dev) left in the context's training scratch, read after
+ * every stream of the context has drained.  Indices are CNN::Eval's layers (cnn.h:550-556), errors[i] is the error at the output of layer i (cnn.h:565-572).
+ *   act [74768]: a1 [16][60][60] layer 1 (conv 5x5 + tanh) | a3 [16][15][15] layer 3 (two max-pools) | a5 [64][12][12] layer 5 (conv 4x4 + tanh) |
+ *                a6 [2304] layer 6 (max-pool) | a8 [2048] layer 8 (fully connected + tanh)
+ *   err [64272]: e9 [2304] errors[9] (under the soft-max) | e7 [2048] errors[7] (tanh' folded in) | e6 [2304] errors[6] |
+ *                part3 [16][3600] errors[3] as sixteen partial sums, one per group of four conv2 output channels (their sum is the error) |
+ *                sqp [9] the soft-max blocks' sums of E^2 (their sum / 2304 is the value Train returns), 7 unused
+ * n_act / n_err must be exactly those counts (HT_ERR_ARG); HT_ERR_STATE when the context has not trained yet. */
+int ht_debug_train_buffers(ht_ctx *ctx, float *act, size_t n_act, float *err, size_t n_err);
 int ht_debug_solve_tables_header(ht_ctx *ctx, int B, int *hdr);      /* tuning aid: the 32 header words of every frame's tables as the latest k_solve_prep left them ([B][32]; words 20-27: cycle stamps of a -DHT_TUNING build) */
 
 #ifdef __cplusplus

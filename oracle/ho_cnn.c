@@ -149,7 +149,9 @@ static void full_update(float *W, float *B, int M, int N, const float *X, const 
 }
 static void tanh_back(const float *Y, const float *E, int n, float *D) { for (int i = 0; i < n; i++) D[i] = (1.0f - Y[i] * Y[i]) * E[i]; }
 
-float ho_cnn_train(float *weights, const float *input, const float *target, float alpha)
+/* the same step, keeping what it went through: outs[i] (optional, i in 0..10) takes layer i's output, errs[i] the error at layer i's output
+ * (errs[10] = y - t, errs[0] = what conv1's update uses); outs / errs or any entry may be NULL */
+float ho_cnn_train_layers(float *weights, const float *input, const float *target, float alpha, float *const *outs, float *const *errs)
 {
 	float *W1 = weights, *B1 = W1 + 400, *W2 = B1 + 16, *B2 = W2 + 16384, *W3 = B2 + 64, *B3 = W3 + (size_t)2304 * 2048, *W4 = B3 + 2048, *B4 = W4 + (size_t)2048 * 2304;
 	static const int N[11] = { 57600, 57600, 14400, 3600, 9216, 9216, 2304, 2048, 2048, 2304, 2304 };
@@ -182,9 +184,15 @@ float ho_cnn_train(float *weights, const float *input, const float *target, floa
 	conv_update(out[3], err[4], 15, 15, 16, W2, B2, 4, 4, 64, alpha);
 	full_update(W3, B3, 2304, 2048, out[6], err[7], alpha);
 	full_update(W4, B4, 2048, 2304, out[8], err[9], alpha);
-	for (int i = 0; i < 11; i++) { free(out[i]); free(err[i]); }
+	for (int i = 0; i < 11; i++)
+	{
+		if (outs && outs[i]) memcpy(outs[i], out[i], sizeof(float) * N[i]);
+		if (errs && errs[i]) memcpy(errs[i], err[i], sizeof(float) * N[i]);
+		free(out[i]); free(err[i]);
+	}
 	return mse;
 }
+float ho_cnn_train(float *weights, const float *input, const float *target, float alpha) { return ho_cnn_train_layers(weights, input, target, alpha, NULL, NULL); }
 
 /* ---- labels: GatherHandExpectedCNN handtrack.h:160-173 -------------------------------------------------------------------
  * ImageFeaturePoints :92-96, RenderHeatMap / NormalizeHeatMap misc_image.h:246-272, HandPoseToKeyAngleSet handtrack.h:132-151,

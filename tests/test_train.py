@@ -79,7 +79,19 @@ def test_gpu_training_matches_reference(weights):
     mse = np.concatenate([ctx.cnn_train(xs, ts, 0.001) for _ in range(2)])
     print("mse", mse, "reference", G["mse"])
     assert np.abs(mse - G["mse"]).max() <= 1e-5 * np.abs(G["mse"]).max()
-    check_weights(ctx.cnn_get_weights(), tol=1e-5)
+    got = ctx.cnn_get_weights()
+    check_weights(got, tol=1e-5)
+    # the fixture holds samples of W2, W3 and W4 only: every entry against the oracle's six steps (pinned to the fixture bit for bit above), same tolerance
+    ref = np.array(weights, np.float32, copy=True)
+    for _ in range(2):
+        for f in range(3):
+            ol.lib().ho_cnn_train(ol.fptr(ref), ol.fptr(xs[f]), ol.fptr(np.ascontiguousarray(ts[f])), 0.001)
+    check_weights(ref)
+    names = sorted(OFF, key=OFF.get)
+    for k, end in zip(names, [OFF[n] for n in names[1:]] + [ref.size]):
+        d = float(np.abs(got[OFF[k]:end] - ref[OFF[k]:end]).max())
+        print("%s: %d entries, max |device - oracle| %.3e" % (k, end - OFF[k], d))
+        assert d <= 1e-5 * max(1.0, float(np.abs(ref[OFF[k]:end]).max())), k
     y = ctx.cnn_eval(xs[0:1])[0]      # the inference kernels see the trained weights (conv2 repacked)
     assert np.abs(y - G["eval0_after"]).max() <= 2e-5
     ctx.close()
