@@ -77,6 +77,7 @@ struct ht_ctx
 	ht_comm_state *comm = nullptr;                               // multi-GPU pose gather (ht_comm_init), null on a single-GPU host
 	char *d_render = nullptr; size_t render_cap = 0;             // both renderers' staging (ht_render_depth, ht_render_mesh_depth: poses, cameras, frames, body labels), grown to the largest call (dev_grow)
 	char *d_labels = nullptr; size_t labels_cap = 0;             // ht_expected_cnn_batch's staging (poses, cameras, labels, image points, key angles), grown to the largest call (dev_grow)
+	char *d_segment = nullptr; size_t segment_cap = 0;           // ht_segment_vr's staging (frames, cameras, tiles, segment cameras), grown to the largest call (dev_grow)
 	std::vector<float4> render_planes; std::vector<float> render_radii;      // the hull planes ht_render_depth last derived its per-body cull radii from, and those radii (2 per body)
 	// ht_render_mesh_depth: the subdivision meshes' corners [t][9] over all bodies (ht_scale rewrites them), the first triangle of every body, the device rows
 	// [t][4] float4 (corners and PolyPlane, ht_mesh_rows) and the farthest corner of every body's mesh from its centre of mass (ht_mesh_upload makes both)
@@ -149,7 +150,7 @@ struct ht_prof_scope
 static inline size_t ht_scratch_rows(size_t pts_cap, size_t nb) { return pts_cap + 5 * nb + 32 + 7 * 16 + HT_SCRATCH_TAIL; }
 int ht_alloc_buffers(ht_ctx *ctx);
 int ht_mesh_upload(ht_ctx *ctx);             // rows and radii of the model's current subdivision meshes to the device (ht_render_mesh.hip); the caller has waited for the renders in flight
-int ht_alloc_solve_tables(ht_ctx *ctx);      // d_tables (first use of the solve-tables path)
+int ht_alloc_solve_tables(ht_ctx *ctx);      // d_tables alone, once: ht_debug_solve_tables(ctx, 1 or 2), or HT_TABLES in a tuning build (the boundary planes d_chplanes / d_chon are ht_alloc_buffers')
 int ht_reserve_points_locked(ht_ctx *ctx, int points);      // grows the per-point arrays (ht_api.hip); waits for the context's streams
 // *_dev entry points: a NULL stream means the context's own stream (never the legacy default stream); the choice is remembered so that the
 // host-read helpers (ht_capacity_events, ht_frames_overflow, ht_get_tracker_flags, ...) can wait for work enqueued on a caller's stream

@@ -26,35 +26,48 @@ static void exact_args(ht_ctx *ctx, solve_args &a, bool cloud)
 	a.exact_lin = ctx->d_exact_lin; a.exact_ang = ctx->d_exact_ang;
 	if (exact_solver(ctx) && cloud) { a.rows_cloud = ctx->d_rows; a.cloud_body = nullptr; }
 }
-// Solves of an update that keep a history (the slots of the contact launches: MultiStepSim step st -> st, main pass i -> 8 + i), for batches that take several rounds
+// The entry points that solve rows of the caller's (ht_fit_rows, ht_physics_update, ht_slowfit) refuse that instantiation before they upload or launch anything
+#define REFUSE_EXACT_SOLVER(ctx) do { if (exact_solver(ctx)) { (ctx)->err = "the exact-order instantiation (ht_debug_solver_build 5) serves the update entry points only"; return HT_ERR_STATE; } } while (0)
+// What every solve starts from: model `which` of the frames' slots, their scratch, the net's decoded output, the cameras, the capacity counters, the contact pool (if it takes contacts)
+static solve_args solve_head(ht_ctx *ctx, int which, bool contacts)
+{
+	solve_args a; memset(&a, 0, sizeof a); a.sf_select = -1; a.caps = reinterpret_cast<int *>(ctx->d_epa_ws) + 2;
+	a.contacts = contacts ? ctx->d_contacts : nullptr; a.ncontacts = ctx->d_ncontacts;
+	a.analysis = ctx->d_analysis; a.cams = ctx->d_cams; a.state = ctx->d_state[which]; a.scratch = ctx->d_scratch; a.scratch_stride = scratch_stride(ctx); a.batch = ctx->B;
+	return a;
+}
+// The row mix of a solve besides its contacts: MultiStepSim's step st (handtrack.h:660-688: CNN-driven angular rows, landmark rays, cloud rows, the palm drive) or a
+// main-thread pass (:769-780: the boundary planes' rows and the cloud rows)
+struct step_mix { bool angles, rays, cloud, chamber; float palm_drive; int arm_cone, zero_momenta; };
+static step_mix mix_of_step(const ht_params &p, int st)
+{
+	const bool angles = (st < p.steps_keyangles) || p.angles_only, rays = (st < p.steps_keypoints) && !p.angles_only, cloud = (st >= p.steps_cloudstart) && !p.angles_only;
+	step_mix m = { angles, rays, cloud, false, st < p.steps_palmangle ? 10000.0f : 0.0f, 1, 1 };
+	return m;
+}
+static step_mix mix_of_pass() { step_mix m = { false, false, true, true, 0.0f, 0, 0 }; return m; }
+static int step_slot(int st) { return st < 8 ? st : -1; }      // the launches of an update that keep a history, a contact launch its work and a solve its cost (HT_CONTACT_SLOTS): MultiStepSim step st -> st,
+static int pass_slot(int pass) { return pass >= 0 && pass < 8 ? 8 + pass : -1; }      // main-thread pass i -> 8 + i; -1: none
+// Solves of an update that keep a history, for batches that take several rounds
 // per CU: k_solve notes what every frame took, the next update's launch of the same slot takes the frames longest first (contact_orders ranks them beside the net), so
 // that the launch ends on short frames instead of waiting for a long one that started last.  Results do not depend on the order.
 static bool solve_history_on(const ht_ctx *ctx, int B) { return ctx->d_swork && B > ctx->n_cu * 8 && B + 8 <= ctx->cstride; }
-static void solve_step(ht_ctx *ctx, int which, const float *rows_pre, const int *n_pre, bool cloud, bool contacts, const int *active,
-                       int apply_angles, float drive_force, int ray_rows, int arm_cone, int zero_momenta, int B, hipStream_t s, bool shared_gpu = false, float *poses_out = nullptr, const int *out_npts = nullptr,
-                       int hist_slot = -1, bool tables = false)
+struct solve_opts { const int *active = nullptr; int hist_slot = -1; bool tables = false, shared_gpu = false; float *poses_out = nullptr; const int *out_npts = nullptr; };      // active: only the frames whose flag is set; tables: solve_prep has made them for exactly this solve; poses_out: the solve also writes the user poses
+static void solve_step(ht_ctx *ctx, int which, const step_mix &m, int B, hipStream_t s, const solve_opts &o)
 {
-	solve_args a;
-	memset(&a, 0, sizeof a);
-	a.sf_select = -1;
-	a.caps = reinterpret_cast<int *>(ctx->d_epa_ws) + 2;
-	a.rows_pre = rows_pre; a.n_pre = n_pre; a.pre_stride = 5 * ctx->model.nb;
-	a.cloud_body = cloud ? ctx->d_rowbody : nullptr; a.n_cloud = ctx->d_nrows;      // k_cloud_rows wrote the rows' records into the scratch slots (cloud_rec below)
-	a.contacts = contacts ? ctx->d_contacts : nullptr; a.ncontacts = ctx->d_ncontacts;
-	a.analysis = ctx->d_analysis; a.cams = ctx->d_cams; a.active_flag = active;
-	a.state = ctx->d_state[which]; a.scratch = ctx->d_scratch; a.scratch_stride = scratch_stride(ctx); a.batch = ctx->B;
-	a.apply_angles = apply_angles; a.drive_force = drive_force; a.ray_rows = ray_rows; a.arm_cone = arm_cone; a.zero_momenta = zero_momenta;
+	solve_args a = solve_head(ctx, which, ctx->phys.use_collision != 0);
+	a.rows_pre = m.chamber ? ctx->d_chamber : nullptr; a.n_pre = m.chamber ? ctx->d_nchamber : nullptr; a.pre_stride = 5 * ctx->model.nb;
+	a.cloud_body = m.cloud ? ctx->d_rowbody : nullptr; a.n_cloud = ctx->d_nrows;      // k_cloud_rows wrote the rows' records into the scratch slots (cloud_rec)
+	a.active_flag = o.active; a.apply_angles = m.angles; a.drive_force = m.palm_drive; a.ray_rows = m.rays; a.arm_cone = m.arm_cone; a.zero_momenta = m.zero_momenta;
 	a.steps_keyangles = ctx->par.steps_keyangles; a.min_cray_prob = ctx->par.min_cray_prob;
-	a.dbg = ht_tuning_flags();
-	a.shared_gpu = shared_gpu ? 1 : 0;
-	a.tables = tables ? ctx->d_tables : nullptr;      // solve_prep below has made them for exactly this solve
-	exact_args(ctx, a, cloud);
-	a.out_poses = poses_out; a.out_npts = out_npts; a.out_initializing = ctx->d_initializing; a.out_min_point_num = ctx->par.min_point_num;
-	if (hist_slot >= 0 && hist_slot < HT_CONTACT_SLOTS && !active && !exact_solver(ctx) && solve_history_on(ctx, B) && B == ctx->swork_B)
+	a.dbg = ht_tuning_flags(); a.shared_gpu = o.shared_gpu ? 1 : 0; a.tables = o.tables ? ctx->d_tables : nullptr;
+	exact_args(ctx, a, m.cloud);
+	a.out_poses = o.poses_out; a.out_npts = o.out_npts; a.out_initializing = ctx->d_initializing; a.out_min_point_num = ctx->par.min_point_num;
+	if (o.hist_slot >= 0 && o.hist_slot < HT_CONTACT_SLOTS && !o.active && !exact_solver(ctx) && solve_history_on(ctx, B) && B == ctx->swork_B)
 	{
-		a.cost_out = ctx->d_swork + (size_t)hist_slot * ctx->cstride;
-		ctx->swork_mask |= 1u << hist_slot;
-		if ((ctx->sorder_mask >> hist_slot) & 1u) a.frame_order = ctx->d_sorder + (size_t)hist_slot * ctx->cstride;
+		a.cost_out = ctx->d_swork + (size_t)o.hist_slot * ctx->cstride;
+		ctx->swork_mask |= 1u << o.hist_slot;
+		if ((ctx->sorder_mask >> o.hist_slot) & 1u) a.frame_order = ctx->d_sorder + (size_t)o.hist_slot * ctx->cstride;
 	}
 	ht_launch_solve(ctx->model, ctx->phys, a, B, s);
 }
@@ -69,17 +82,17 @@ static int solve_tables_mode(const ht_ctx *ctx)
 	return (m && ctx->d_tables && !exact_solver(ctx)) ? m : 0;
 }
 static bool solve_tables_on(const ht_ctx *ctx) { return solve_tables_mode(ctx) == 1; }
-static void solve_prep(ht_ctx *ctx, int which, bool cloud, bool chamber, const int *active, int apply_angles, float drive_force, int ray_rows, int arm_cone, int B, hipStream_t s, int parts = 3)
+static void solve_prep(ht_ctx *ctx, int which, const step_mix &m, bool pose_only, const int *active, int B, hipStream_t s)      // pose_only: the tables that follow from the pose alone (mode 2); otherwise every table, the lists of the mix's cloud and boundary-plane rows among them
 {
 	prep_args a;
 	memset(&a, 0, sizeof a);
 	a.state = ctx->d_state[which]; a.analysis = ctx->d_analysis; a.cams = ctx->d_cams; a.active_flag = active;
 	a.scratch = ctx->d_scratch; a.scratch_stride = scratch_stride(ctx); a.batch = ctx->B;
-	a.cloud_body = cloud ? ctx->d_rowbody : nullptr; a.n_cloud = ctx->d_nrows;
-	if (chamber) { a.ch_planes = ctx->d_chplanes; a.ch_on = ctx->d_chon; a.rows_pre = ctx->d_chamber; a.n_pre = ctx->d_nchamber; a.ch_maxforce = 10.0f; }
-	a.apply_angles = apply_angles; a.drive_force = drive_force; a.ray_rows = ray_rows; a.arm_cone = arm_cone;
+	a.cloud_body = m.cloud && !pose_only ? ctx->d_rowbody : nullptr; a.n_cloud = ctx->d_nrows;
+	if (m.chamber && !pose_only) { a.ch_planes = ctx->d_chplanes; a.ch_on = ctx->d_chon; a.rows_pre = ctx->d_chamber; a.n_pre = ctx->d_nchamber; a.ch_maxforce = 10.0f; }
+	a.apply_angles = m.angles; a.drive_force = m.palm_drive; a.ray_rows = m.rays; a.arm_cone = m.arm_cone;
 	a.steps_keyangles = ctx->par.steps_keyangles; a.min_cray_prob = ctx->par.min_cray_prob;
-	a.tables = ctx->d_tables; a.dbg = ht_tuning_flags(); a.parts = parts;
+	a.tables = ctx->d_tables; a.dbg = ht_tuning_flags(); a.parts = pose_only ? 1 : 3;
 	ht_launch_solve_prep(ctx->model, ctx->phys, a, B, s);
 }
 // Fork/join helpers: the row-producing kernels of one fit step only read the pose, so they run side by side on two extra streams
@@ -87,8 +100,6 @@ static void solve_prep(ht_ctx *ctx, int which, bool cloud, bool chamber, const i
 // Tuning builds, HT_MARKS=1: events at named points of an update on whichever stream, printed (ms since the first) after the update -- the concurrent streams as
 // they really ran (a kernel trace serialises them).
 #ifdef HT_TUNING
-#include <vector>
-#include <string>
 static std::vector<std::pair<std::string, hipEvent_t>> g_marks;
 static bool marks_on() { static const bool on = getenv("HT_MARKS") != nullptr; return on; }
 static void mark(const char *name, hipStream_t s) { if (!marks_on()) return; hipEvent_t e; (void)hipEventCreate(&e); (void)hipEventRecord(e, s); g_marks.emplace_back(name, e); }
@@ -114,6 +125,14 @@ static contact_slot contact_history(ht_ctx *ctx, int slot, const int *active, in
 	ctx->cwork_mask |= 1u << slot;
 	if ((ctx->corder_mask >> slot) & 1u) c.order = ctx->d_corder + (size_t)slot * ctx->cstride;
 	return c;
+}
+// The contact kernel on model `which`, with what varies from launch to launch: the frames (`active`: when given, only those whose flag is set -- the reset frames in their
+// few-frames organisation unless many reset), the stream, whether cloud rows run beside it, the history slot
+static void launch_contacts(ht_ctx *ctx, int which, const int *active, int B, hipStream_t s, bool beside_cloud_rows = false, int slot = -1)
+{
+	const contact_slot ch = contact_history(ctx, slot, active, B);
+	ht_launch_contacts(ctx->model, ctx->d_state[which], ctx->phys.driftmax, ctx->phys.jiggle_sin, active, ctx->d_epa_ws, ctx->d_contacts, ctx->d_ncontacts, B, s, beside_cloud_rows, ctx->contact_kernel,
+	                   active && active == ctx->d_flags && !ctx->many_reset, ch.order, ch.work);
 }
 // At the head of an update, on a stream that has nothing to do while the net runs: the assignments of this update's contact launches from the works of the last one
 static void contact_orders(ht_ctx *ctx, int B, hipStream_t t)
@@ -141,41 +160,53 @@ static void contact_orders(ht_ctx *ctx, int B, hipStream_t t)
 static void fork(ht_ctx *ctx, hipStream_t s) { (void)hipEventRecord(ctx->ev_fork, s); for (int i = 0; i < 2; i++) (void)hipStreamWaitEvent(ctx->side[i], ctx->ev_fork, 0); }
 static void fork1(ht_ctx *ctx, hipStream_t s, int i) { (void)hipEventRecord(ctx->ev_fork, s); (void)hipStreamWaitEvent(ctx->side[i], ctx->ev_fork, 0); }
 static void join1(ht_ctx *ctx, hipStream_t s, int i) { (void)hipEventRecord(ctx->ev_join[i], ctx->side[i]); (void)hipStreamWaitEvent(s, ctx->ev_join[i], 0); }
-static void join(ht_ctx *ctx, hipStream_t s, int n) { for (int i = 0; i < n; i++) { (void)hipEventRecord(ctx->ev_join[i], ctx->side[i]); (void)hipStreamWaitEvent(s, ctx->ev_join[i], 0); } }
+static void join(ht_ctx *ctx, hipStream_t s, int n) { for (int i = 0; i < n; i++) join1(ctx, s, i); }
 
+// Which steps of MultiStepSim to run, where and how much of each: multistep(ctx, B, steps_on(stream).steps(0, 1).frames(ctx->d_flags).in_order().rows_only()).
+// Unless told otherwise: every step of every frame, whole, bracketed for the profile, the cloud rows of a step on side stream 0 beside its contacts.
+struct steps_on
+{
+	hipStream_t s; int from = 0, to = 1 << 30; const int *active = nullptr; int side = 0; bool prof = true, shared_gpu = false, rows = true, solve = true;
+	explicit steps_on(hipStream_t stream) : s(stream) {}
+	steps_on &steps(int first, int end = 1 << 30) { from = first; to = end; return *this; }      // [first, end), or from `first` to the last
+	steps_on &frames(const int *flags) { active = flags; return *this; }               // only the frames whose flag is set
+	steps_on &all_frames() { active = nullptr; return *this; }
+	steps_on &rows_beside(int i) { side = i; return *this; }                            // the cloud rows on side stream i, beside the contacts on the steps' stream
+	steps_on &in_order() { side = -1; return *this; }                                   // everything in order on the steps' stream
+	steps_on &unprofiled() { prof = false; return *this; }                              // a concurrent second instance: not bracketed for the profile
+	steps_on &shares_gpu() { shared_gpu = true; return *this; }                         // other kernels run beside the solves (solve_args::shared_gpu)
+	steps_on &rows_only() { solve = false; return *this; }                              // only what precedes the solve (cloud rows, contacts)
+	steps_on &solve_only() { rows = false; return *this; }
+};
 // HandTracker::MultiStepSim on othermodel (handtrack.h:642-690)
-// `active`: when given, only the frames whose flag is set are touched.  `side`: index of the side stream the cloud rows of a step run on beside the
-// contacts (-1: everything in order on s).  `prof`: bracket the solves for the profile (off for a concurrent second instance).
-// `part`: 0 a whole step, 1 only what precedes the solve (cloud rows, contacts), 2 only the solve.
-static void multistep(ht_ctx *ctx, int B, hipStream_t s, int from_step = 0, int to_step = 1 << 30, const int *active = nullptr, bool first_contacts_done = false, int side = 0, bool prof = true, bool shared_gpu = false,
-                      int part = 0)
+static void multistep(ht_ctx *ctx, int B, const steps_on &o)
 {
 	const ht_params &p = ctx->par;
-	for (int st = from_step; st < p.steps && st < to_step; st++)
+	hipStream_t s = o.s; const int *active = o.active; const bool whole = o.rows && o.solve;
+	for (int st = o.from; st < p.steps && st < o.to; st++)
 	{
-		const bool angles = (st < p.steps_keyangles) || p.angles_only;
-		const bool rays = (st < p.steps_keypoints) && !p.angles_only;
-		const bool cloud = (st >= p.steps_cloudstart) && !p.angles_only;
-		const bool coll = ctx->phys.use_collision != 0;
+		const step_mix m = mix_of_step(p, st); const bool coll = ctx->phys.use_collision != 0;
 		static const bool no_side = ht_tuning_env("HT_NO_SIDE");      // timing experiments (-DHT_TUNING builds only)
-		const bool pose_only = solve_tables_mode(ctx) == 2 && side >= 0 && coll && !ctx->profile_phases && !no_side && part == 0 && !active;      // the pose-only tables: on the OTHER side stream, beside the cloud rows
+		const bool pose_only = solve_tables_mode(ctx) == 2 && o.side >= 0 && coll && !ctx->profile_phases && !no_side && whole && !active;      // the pose-only tables: on the OTHER side stream, beside the cloud rows
 		const bool tables = solve_tables_on(ctx) || pose_only;
 		// beside the contact kernel: the step's cloud rows, and (round 6) the solve's tables behind them -- a step without cloud rows forks for the tables alone
-		const bool par = side >= 0 && (cloud || tables) && coll && !ctx->profile_phases && !no_side;
-		if (part != 2)
+		const bool par = o.side >= 0 && (m.cloud || tables) && coll && !ctx->profile_phases && !no_side;
+		if (o.rows)
 		{
-			if (par && pose_only) fork(ctx, s); else if (par) fork1(ctx, s, side);
+			hipStream_t rows_stream = par ? ctx->side[o.side] : s;
+			if (par && pose_only) fork(ctx, s); else if (par) fork1(ctx, s, o.side);
 			const cloud_records cr = cloud_rec(ctx);
-			if (cloud) { ht_prof_scope ps(ctx, prof ? "cloud_rows" : nullptr, s, true); ht_launch_cloud_rows(ctx->model, ctx->d_state[1], ctx->d_pts, ctx->d_npts, ctx->d_cams, active, 4, 1, 2, p, ctx->d_rows, ctx->d_nrows, B, par ? ctx->side[side] : s, 0.0f, 0.0f, rec_or_rows(ctx, &cr)); }
-			if (pose_only) solve_prep(ctx, 1, false, false, active, angles, st < p.steps_palmangle ? 10000.0f : 0.0f, rays, 1, B, ctx->side[1 - side], 1);
-			else if (tables) { ht_prof_scope ps(ctx, prof ? "solve_prep" : nullptr, s, true); solve_prep(ctx, 1, cloud, false, active, angles, st < p.steps_palmangle ? 10000.0f : 0.0f, rays, 1, B, par ? ctx->side[side] : s); }
-			if (coll && !(first_contacts_done && st == from_step)) { ht_prof_scope ps(ctx, prof ? "contacts" : nullptr, s, true); const contact_slot ch = contact_history(ctx, st < 8 ? st : -1, active, B); ht_launch_contacts(ctx->model, ctx->d_state[1], ctx->phys.driftmax, ctx->phys.jiggle_sin, active, ctx->d_epa_ws, ctx->d_contacts, ctx->d_ncontacts, B, s, false, ctx->contact_kernel, active && active == ctx->d_flags && !ctx->many_reset, ch.order, ch.work); }
-			if (par && pose_only) join(ctx, s, 2); else if (par) join1(ctx, s, side);
-			if (part == 0 && !active) mark("  step: rows done", s);
+			if (m.cloud) { ht_prof_scope ps(ctx, o.prof ? "cloud_rows" : nullptr, s, true); ht_launch_cloud_rows(ctx->model, ctx->d_state[1], ctx->d_pts, ctx->d_npts, ctx->d_cams, active, 4, 1, 2, p, ctx->d_rows, ctx->d_nrows, B, rows_stream, 0.0f, 0.0f, rec_or_rows(ctx, &cr)); }
+			if (pose_only) solve_prep(ctx, 1, m, true, active, B, ctx->side[1 - o.side]);
+			else if (tables) { ht_prof_scope ps(ctx, o.prof ? "solve_prep" : nullptr, s, true); solve_prep(ctx, 1, m, false, active, B, rows_stream); }
+			if (coll) { ht_prof_scope ps(ctx, o.prof ? "contacts" : nullptr, s, true); launch_contacts(ctx, 1, active, B, s, false, step_slot(st)); }
+			if (par && pose_only) join(ctx, s, 2); else if (par) join1(ctx, s, o.side);
+			if (whole && !active) mark("  step: rows done", s);
 		}
-		if (part == 1) continue;
-		ht_prof_scope ps(ctx, prof ? "solve" : nullptr, s);
-		solve_step(ctx, 1, nullptr, nullptr, cloud, coll, active, angles, st < p.steps_palmangle ? 10000.0f : 0.0f, rays, 1, 1, B, s, shared_gpu, nullptr, nullptr, st < 8 ? st : -1, tables);
+		if (!o.solve) continue;
+		ht_prof_scope ps(ctx, o.prof ? "solve" : nullptr, s);
+		solve_opts so; so.active = active; so.hist_slot = step_slot(st); so.tables = tables; so.shared_gpu = o.shared_gpu;
+		solve_step(ctx, 1, m, B, s, so);
 	}
 }
 // one main-thread pass of HandTracker::update (handtrack.h:769-780)
@@ -184,35 +215,32 @@ static void main_pass(ht_ctx *ctx, int B, hipStream_t s, float *poses_out = null
 	const ht_params &p = ctx->par;
 	const float4 *pts = p.subsample_voxel ? ctx->d_ptsv : ctx->d_pts;      // handtrack.h:751: the main-thread cloud
 	const int *npts = p.subsample_voxel ? ctx->d_nptsv : ctx->d_npts;
-	const bool coll = ctx->phys.use_collision != 0;
+	const step_mix m = mix_of_pass(); const bool coll = ctx->phys.use_collision != 0;
 	static const bool no_side = ht_tuning_env("HT_NO_SIDE");
 	const bool par = !ctx->profile_phases && !no_side;
 	const bool pose_only = solve_tables_mode(ctx) == 2 && par;
 	const bool tables = solve_tables_on(ctx);
-	// Round 6: the five boundary planes follow from the points alone, so an update makes them once (beside the net: run_update) and every pass only their rows (k_chamber,
+	hipStream_t rows_stream = par ? ctx->side[0] : s, chamber_stream = par ? ctx->side[1] : s;
+	// Round 6: the five boundary planes follow from the points alone, so an update makes them once (beside the net: update_planes) and every pass only their rows (k_chamber,
 	// or k_solve_prep with the solve tables).  A pass outside an update (ht_stage_fit) makes them here.
 	if (!ctx->planes_valid) { ht_prof_scope ps(ctx, "chamber", s, true); ht_launch_chamber_planes(ctx->model, pts, npts, p.min_point_num, p.boundary_planes, ctx->d_chplanes, ctx->d_chon, B, s); }
 	if (par) { if (tables) fork1(ctx, s, 0); else fork(ctx, s); }
-	if (pose_only) solve_prep(ctx, 0, false, false, nullptr, 0, 0.0f, 0, 0, B, ctx->side[1], 1);      // the pose-only tables ahead of the boundary planes on their side stream: both beside the cloud rows
-	if (!tables) { ht_prof_scope ps(ctx, "chamber", s, true); ht_launch_chamber(ctx->model, ctx->d_state[0], ctx->d_chplanes, ctx->d_chon, 10.0f, ctx->d_chamber, ctx->d_nchamber, B, par ? ctx->side[1] : s); }
+	if (pose_only) solve_prep(ctx, 0, m, true, nullptr, B, ctx->side[1]);      // the pose-only tables ahead of the boundary planes on their side stream: both beside the cloud rows
+	if (!tables) { ht_prof_scope ps(ctx, "chamber", s, true); ht_launch_chamber(ctx->model, ctx->d_state[0], ctx->d_chplanes, ctx->d_chon, 10.0f, ctx->d_chamber, ctx->d_nchamber, B, chamber_stream); }
 	const cloud_records cr = cloud_rec(ctx);
-	{ ht_prof_scope ps(ctx, "cloud_rows", s, true); ht_launch_cloud_rows(ctx->model, ctx->d_state[0], pts, npts, ctx->d_cams, nullptr, 1, 0, 1, p, ctx->d_rows, ctx->d_nrows, B, par ? ctx->side[0] : s, 0.0f, 0.0f, rec_or_rows(ctx, &cr)); }
-	if (tables) { ht_prof_scope ps(ctx, "solve_prep", s, true); solve_prep(ctx, 0, true, true, nullptr, 0, 0.0f, 0, 0, B, par ? ctx->side[0] : s); }
-	if (coll) { ht_prof_scope ps(ctx, "contacts", s, true); const contact_slot ch = contact_history(ctx, pass >= 0 && pass < 8 ? 8 + pass : -1, nullptr, B); ht_launch_contacts(ctx->model, ctx->d_state[0], ctx->phys.driftmax, ctx->phys.jiggle_sin, nullptr, ctx->d_epa_ws, ctx->d_contacts, ctx->d_ncontacts, B, s, par, ctx->contact_kernel, 0, ch.order, ch.work); }
+	{ ht_prof_scope ps(ctx, "cloud_rows", s, true); ht_launch_cloud_rows(ctx->model, ctx->d_state[0], pts, npts, ctx->d_cams, nullptr, 1, 0, 1, p, ctx->d_rows, ctx->d_nrows, B, rows_stream, 0.0f, 0.0f, rec_or_rows(ctx, &cr)); }
+	if (tables) { ht_prof_scope ps(ctx, "solve_prep", s, true); solve_prep(ctx, 0, m, false, nullptr, B, rows_stream); }
+	if (coll) { ht_prof_scope ps(ctx, "contacts", s, true); launch_contacts(ctx, 0, nullptr, B, s, par, pass_slot(pass)); }
 	mark("  pass: contacts done", s);
-	if (par) { mark("  pass: cloud rows done", ctx->side[0]); if (!tables) mark("  pass: chamber done", ctx->side[1]); }
-	if (par) join(ctx, s, tables ? 1 : 2);
+	if (par) { mark("  pass: cloud rows done", ctx->side[0]); if (!tables) mark("  pass: chamber done", ctx->side[1]); join(ctx, s, tables ? 1 : 2); }
 	ht_prof_scope ps(ctx, "solve", s);
-	solve_step(ctx, 0, ctx->d_chamber, ctx->d_nchamber, true, coll, nullptr, 0, 0.0f, 0, 0, 0, B, s, false, poses_out, npts, pass >= 0 && pass < 8 ? 8 + pass : -1, tables || pose_only);
+	solve_opts so; so.hist_slot = pass_slot(pass); so.tables = tables || pose_only; so.poses_out = poses_out; so.out_npts = npts;
+	solve_step(ctx, 0, m, B, s, so);
 }
 // Behind the join of the side stream, so nothing of the step waits for it: the running counts of reset frames go to the host (ht_host.hpp: d_nreset).  The
 // update's stream picks the copy up again at its very end (reset_tail_join: long finished by then) -- every stream of an update has to come back to the
 // caller's, or the update could not be captured into a HIP graph.
-static void reset_tail(ht_ctx *ctx)
-{
-	(void)hipMemcpyAsync(const_cast<unsigned *>(ctx->h_nreset), ctx->d_nreset, 2 * sizeof(unsigned), hipMemcpyDeviceToHost, ctx->side[0]);
-	ctx->tail_pending = true;
-}
+static void reset_tail(ht_ctx *ctx) { (void)hipMemcpyAsync(const_cast<unsigned *>(ctx->h_nreset), ctx->d_nreset, 2 * sizeof(unsigned), hipMemcpyDeviceToHost, ctx->side[0]); ctx->tail_pending = true; }
 static void reset_tail_join(ht_ctx *ctx, hipStream_t s) { if (ctx->tail_pending) { join(ctx, s, 1); ctx->tail_pending = false; } }
 static void reset_path(ht_ctx *ctx, bool listed, int n_unibody, int B, hipStream_t s, hipStream_t prof_stream, bool many_frames = false)      // listed: the frames of d_flist; otherwise all
 {
@@ -222,7 +250,7 @@ static void reset_path(ht_ctx *ctx, bool listed, int n_unibody, int B, hipStream
 	                ctx->d_rows, ctx->d_nrows, ctx->d_scratch, scratch_stride(ctx), ctx->B, B, s, many_frames, ctx->n_cu, exact_solver(ctx));
 }
 
-// the whole unit of work on device buffers
+// ---- the whole unit of work on device buffers --------------------------------------------------------------------------
 // `fs` != null: d_depth / d_cams are full-size frames (handtrack.h:693-785 with dim != 64x64).  The tracker segments them for the CNN
 // (handtrack.h:697-698) and from then on ctx->d_cams holds the SEGMENT cameras (CNN decode, landmark rays, PoseFromScratch, UnibodyFit and
 // MultiStepSim take segment.cam.pose); the point cloud and FitError keep the full frame and its camera.
@@ -234,45 +262,29 @@ struct frame_src { int w, h; float segment_scale; int direct; };
 // UPD_KICKSTART = kickstart (:743-746) = the same followed by handmodel.SetPose(pose) where the pose was accepted.
 // UPD_PASSES = only the caller's part of update() (:751-753, 769-785): the cloud of the frame, the main-thread passes on handmodel, the user poses (the overlapped mode, ht_update_passes_sync)
 enum { UPD_FULL = 0, UPD_CNN_MODEL = 1, UPD_KICKSTART = 2, UPD_PASSES = 3 };
-static int run_update_(ht_ctx *ctx, const uint16_t *d_depth, const float *d_cams, const float *d_start, int B, float *d_poses_out, float *d_cnn_out, hipStream_t s, const frame_src *fs, int mode);
-static int run_update(ht_ctx *ctx, const uint16_t *d_depth, const float *d_cams, const float *d_start, int B, float *d_poses_out, float *d_cnn_out, hipStream_t s, const frame_src *fs = nullptr, int mode = UPD_FULL)
+struct update_call { const uint16_t *d_depth; const float *d_cams, *d_start; int B; float *d_poses_out, *d_cnn_out; hipStream_t s; const frame_src *fs; int mode; const float *img_cams; int iw, ih; };      // one update call: what the caller gave, and where FitError finds the image (update_inputs: the full-size frame and its cameras, or the tile)
+static bool main_thread_cloud_voxel(const ht_ctx *ctx, const update_call &u) { return (u.mode == UPD_FULL || u.mode == UPD_PASSES) && ctx->par.subsample_voxel; }
+
+// Input staging: the point capacity this frame size needs, the segment for the net (full-size frames), the net's input, the cloud(s), the launch order by point counts
+static int update_inputs(ht_ctx *ctx, update_call &u)
 {
-	const int r = run_update_(ctx, d_depth, d_cams, d_start, B, d_poses_out, d_cnn_out, s, fs, mode);
-	ctx->model.frame_order = nullptr;      // the launch order of the block-per-frame kernels belongs to the update that made it
-	ctx->planes_valid = false;             // and so do the boundary planes of its cloud
-	return r;
-}
-static int run_update_(ht_ctx *ctx, const uint16_t *d_depth, const float *d_cams, const float *d_start, int B, float *d_poses_out, float *d_cnn_out, hipStream_t s, const frame_src *fs, int mode)
-{
-	if (mode == UPD_PASSES) {}      // no net in the caller's part
-	else if (fs && fs->direct) { if (!ctx->have_weights128) { ctx->err = "weights of the 128x128 net not loaded (ht_cnn_load_weights_sized)"; return HT_ERR_STATE; } }
-	else if (!ctx->have_weights) { ctx->err = "CNN weights not loaded (ht_cnn_load_weights)"; return HT_ERR_STATE; }
 	const ht_params &p = ctx->par;
-	const int nb = ctx->model.nb;
-	const int iw = fs ? fs->w : 64, ih = fs ? fs->h : 64;      // the image FitError looks at
-	{ const int npx = iw * ih, fr = p.subsample_fraction > 0 ? p.subsample_fraction : 1, n = ((mode == UPD_FULL || mode == UPD_PASSES) && p.subsample_voxel) ? npx : (npx + fr - 1) / fr; if (n > ctx->model.pts_cap) { const int r = ht_reserve_points_locked(ctx, n); if (r) return r; } ctx->model.pts_bound = (n + 63) & ~63; }
-	const float *img_cams = ctx->d_cams;
+	const frame_src *fs = u.fs; const uint16_t *d_depth = u.d_depth; const float *d_cams = u.d_cams; const int B = u.B, mode = u.mode; hipStream_t s = u.s;
+	u.iw = fs ? fs->w : 64; u.ih = fs ? fs->h : 64;      // the image FitError looks at
+	{ const int npx = u.iw * u.ih, fr = p.subsample_fraction > 0 ? p.subsample_fraction : 1, n = main_thread_cloud_voxel(ctx, u) ? npx : (npx + fr - 1) / fr; if (n > ctx->model.pts_cap) { const int r = ht_reserve_points_locked(ctx, n); if (r) return r; } ctx->model.pts_bound = (n + 63) & ~63; }
+	u.img_cams = ctx->d_cams;
 	if (fs)
 	{
-		if (!ctx->d_seg_tiles)      // the three buffers of the full-size path, the one this asks for last
-		{
-			int r;
-			if ((r = dev_alloc(ctx, &ctx->d_frame_cams, (size_t)ctx->B * HT_CAM)) || (r = dev_alloc(ctx, &ctx->d_overflow, 1)) || (r = dev_alloc(ctx, &ctx->d_seg_tiles, (size_t)ctx->B * 4096))) return r;
-		}
+		int r;      // the three buffers of the full-size path, the one this asks for last
+		if (!ctx->d_seg_tiles && ((r = dev_alloc(ctx, &ctx->d_frame_cams, (size_t)ctx->B * HT_CAM)) || (r = dev_alloc(ctx, &ctx->d_overflow, 1)) || (r = dev_alloc(ctx, &ctx->d_seg_tiles, (size_t)ctx->B * 4096)))) return r;
 		HIPCHK(ctx, hipMemcpyAsync(ctx->d_frame_cams, d_cams, (size_t)B * HT_CAM * sizeof(float), hipMemcpyDeviceToDevice, s));
 		HIPCHK(ctx, hipMemsetAsync(ctx->d_overflow, 0, sizeof(int), s));
 		if (fs->direct) { if (d_cams != ctx->d_cams) HIPCHK(ctx, hipMemcpyAsync(ctx->d_cams, d_cams, (size_t)B * HT_CAM * sizeof(float), hipMemcpyDeviceToDevice, s)); }      // segment.cam = the frame's camera
 		else if (mode != UPD_PASSES) ht_launch_segment(d_depth, ctx->d_frame_cams, fs->w, fs->h, 0xF, p.drangey, fs->segment_scale, ctx->d_seg_tiles, ctx->d_cams, B, s);
-		img_cams = ctx->d_frame_cams;
+		u.img_cams = ctx->d_frame_cams;
 	}
-	// 64x64 tiles: the camera copy and the re-seeding of the trackers ride on k_prepare (below); full-size frames keep their own small kernels
-	ht_prepare_extra px = { (!fs && d_cams != ctx->d_cams) ? ctx->d_cams : nullptr, ctx->d_state[0], ctx->d_state[1], fs ? nullptr : d_start, ctx->d_prev_err, ctx->d_initializing, nb, ctx->d_nflist };
-	if (d_start && fs)
-	{
-		ht_launch_set_pose(ctx->d_state[0], d_start, nb, B, 1, s);
-		ht_launch_set_pose(ctx->d_state[1], d_start, nb, B, 1, s);
-		ht_launch_clear_flags(ctx->d_prev_err, ctx->d_initializing, B, s);
-	}
+	if (u.d_start && fs)      // full-size frames re-seed the trackers with their own small kernels; for 64x64 tiles that, and the camera copy, ride on k_prepare (below)
+	{ for (int w = 0; w < 2; w++) ht_launch_set_pose(ctx->d_state[w], u.d_start, ctx->model.nb, B, 1, s); ht_launch_clear_flags(ctx->d_prev_err, ctx->d_initializing, B, s); }
 	{
 		ht_prof_scope ps(ctx, "prepare", s, true);
 		if (fs)
@@ -280,157 +292,180 @@ static int run_update_(ht_ctx *ctx, const uint16_t *d_depth, const float *d_cams
 			const ht_prepare_extra pz = { nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, ctx->d_nflist };
 			if (fs->direct) { HIPCHK(ctx, hipMemsetAsync(ctx->d_nflist, 0, sizeof(int), s)); ht_launch_cnn_input(d_depth, ctx->d_cams, fs->w * fs->h, p.drangey, ctx->d_in128, B, s); }
 			else if (mode != UPD_PASSES) ht_launch_prepare(ctx->d_seg_tiles, ctx->d_cams, p.drangey, p.subsample_fraction, ctx->d_cnn_in, nullptr, nullptr, ctx->model.pts_cap, B, s, &pz);      // (the caller's part of the overlapped update has no segment and no net)
-			ht_launch_prepare_frame(d_depth, img_cams, fs->w, fs->h, p.drangey, p.subsample_fraction, ctx->d_pts, ctx->d_npts, ctx->d_overflow, ctx->model.pts_cap, B, s);
+			ht_launch_prepare_frame(d_depth, u.img_cams, fs->w, fs->h, p.drangey, p.subsample_fraction, ctx->d_pts, ctx->d_npts, ctx->d_overflow, ctx->model.pts_cap, B, s);
 		}
-		else ht_launch_prepare(d_depth, d_cams, p.drangey, p.subsample_fraction, ctx->d_cnn_in, ctx->d_pts, ctx->d_npts, ctx->model.pts_cap, B, s, &px);
-		if ((mode == UPD_FULL || mode == UPD_PASSES) && p.subsample_voxel)      // UPD_PASSES: the caller's part of the overlapped update runs its passes on this very cloud (handtrack.h:753)
+		else
+		{
+			const ht_prepare_extra px = { d_cams != ctx->d_cams ? ctx->d_cams : nullptr, ctx->d_state[0], ctx->d_state[1], u.d_start, ctx->d_prev_err, ctx->d_initializing, ctx->model.nb, ctx->d_nflist };
+			ht_launch_prepare(d_depth, d_cams, p.drangey, p.subsample_fraction, ctx->d_cnn_in, ctx->d_pts, ctx->d_npts, ctx->model.pts_cap, B, s, &px);
+		}
+		if (main_thread_cloud_voxel(ctx, u))      // UPD_PASSES: the caller's part of the overlapped update runs its passes on this very cloud (handtrack.h:753)
 		{
 			// the main-thread cloud of handtrack.h:751 with the voxel rule: ALL in-range points (taken once more, into the cloud-row array, which nothing
 			// uses before the first fit step) go through the voxel table; the CNN job keeps the every-n-th cloud above (handtrack.h:703)
 			if (!ctx->d_ptsv) { int r = dev_alloc_points(ctx); if (r) return r; }
 			float4 *all = reinterpret_cast<float4 *>(ctx->d_rows);
-			if (fs) ht_launch_prepare_frame(d_depth, img_cams, fs->w, fs->h, p.drangey, 1, all, ctx->d_nrows, ctx->d_overflow, ctx->model.pts_cap, B, s);
+			if (fs) ht_launch_prepare_frame(d_depth, u.img_cams, fs->w, fs->h, p.drangey, 1, all, ctx->d_nrows, ctx->d_overflow, ctx->model.pts_cap, B, s);
 			else ht_launch_prepare(d_depth, ctx->d_cams, p.drangey, 1, nullptr, all, ctx->d_nrows, ctx->model.pts_cap, B, s);
 			ht_launch_voxel(all, ctx->d_nrows, ctx->model.pts_cap, p.subsample_size, p.subsample_fraction, ctx->d_ptsv, ctx->d_nptsv, B, s);
 		}
 	}
 	// batches of several rounds per CU: the block-per-frame kernels take the frames with the most points first, so that a launch ends on short blocks
 	if (ctx->d_porder && B > ctx->n_cu * 8 && !exact_solver(ctx)) { ht_launch_order_by_points(ctx->d_npts, ctx->d_porder, B, s); ctx->model.frame_order = ctx->d_porder; }
-	auto update_planes = [&](hipStream_t t) {      // the boundary planes of the main-thread cloud (handtrack.h:751, 774-778), once per update
-		if (mode == UPD_CNN_MODEL || mode == UPD_KICKSTART || p.angles_only || p.mainthreadpasses < 1) return;
-		ht_launch_chamber_planes(ctx->model, p.subsample_voxel ? ctx->d_ptsv : ctx->d_pts, p.subsample_voxel ? ctx->d_nptsv : ctx->d_npts, p.min_point_num, p.boundary_planes, ctx->d_chplanes, ctx->d_chon, B, t);
-		ctx->planes_valid = true;
-	};
-	if (mode == UPD_PASSES)
+	return HT_OK;
+}
+static void update_planes(ht_ctx *ctx, const update_call &u, hipStream_t t)      // the boundary planes of the main-thread cloud (handtrack.h:751, 774-778), once per update
+{
+	const ht_params &p = ctx->par;
+	if (u.mode == UPD_CNN_MODEL || u.mode == UPD_KICKSTART || p.angles_only || p.mainthreadpasses < 1) return;
+	ht_launch_chamber_planes(ctx->model, p.subsample_voxel ? ctx->d_ptsv : ctx->d_pts, p.subsample_voxel ? ctx->d_nptsv : ctx->d_npts, p.min_point_num, p.boundary_planes, ctx->d_chplanes, ctx->d_chon, u.B, t); ctx->planes_valid = true;
+}
+static void update_fit_error_old(ht_ctx *ctx, const update_call &u, hipStream_t t)      // FitError of the carried pose (handtrack.h:704) and the reset decision it ends with (:706)
+{
+	const ht_params &p = ctx->par;
+	ht_fit_after dec; memset(&dec, 0, sizeof dec);
+	dec.mode = 1; dec.reset_thr = p.full_reset_on_error; dec.angles_only = p.angles_only; dec.flags = ctx->d_flags; dec.nflags = ctx->d_nflags; dec.list = ctx->d_flist; dec.nlist = ctx->d_nflist; dec.nreset = ctx->d_nreset;
+	ht_launch_fit_error(ctx->model, ctx->d_state[0], ctx->d_pts, ctx->d_npts, u.d_depth, u.img_cams, u.iw, u.ih, p.bone_sum_error_scale, ctx->d_err_old, u.B, t, &dec);
+}
+// The side branch beside the net.  Nothing on it needs the CNN: the error of the carried pose and the reset decision only read the point cloud and the
+// tracker state, so they run beside the CNN.  (The contacts of MultiStepSim's first step do not need it either, but the contact kernel
+// owns whole CUs and the FC layers want one block per CU: beside each other they took 0.78 ms, one after the other 0.46.)
+static void update_beside_net(ht_ctx *ctx, const update_call &u)
+{
+	hipStream_t t = ctx->side[1];
+	fork(ctx, u.s);
+	update_planes(ctx, u, t);
+	contact_orders(ctx, u.B, t);
+	if (u.mode == UPD_FULL && !(u.d_start && !u.fs)) ht_launch_set_pose(ctx->d_state[1], ctx->d_state[0], ctx->model.nb, u.B, 2, t);     // othermodel.SetPose(handmodel.GetPose()) handtrack.h:757 (both were just seeded with the same pose otherwise)
+	update_fit_error_old(ctx, u, t);
+}
+static void update_net(ht_ctx *ctx, const update_call &u, bool overlap)      // the net and its decode.  overlap: the side branch's FitError runs beside the net
+{
+	const frame_src *fs = u.fs; const bool direct = fs && fs->direct; hipStream_t s = u.s;
+	ht_prof_scope ps(ctx, direct ? "cnn128" : "cnn", s, true);
+	if (direct) ht_launch_cnn(ctx->cnnw128, ctx->d_in128, ctx->d_act1_128, ctx->d_act2_128, ctx->d_act3, ctx->d_logits, u.B, s, fs->direct, overlap);
+	else ht_launch_cnn(ctx->cnnw, ctx->d_cnn_in, ctx->d_act1, ctx->d_act2, ctx->d_act3, ctx->d_logits, u.B, s, 64, overlap);
+	ht_launch_softmax_decode(ctx->d_logits, u.d_cnn_out ? u.d_cnn_out : ctx->d_cnn_out, ctx->d_cams, ctx->d_analysis, 1, u.B, s, direct ? fs->direct / 16 : 4);
+}
+// The three organisations of the full-reset frames beside the batch's MultiStepSim (update_resets picks one).
+// The full-reset path touches few frames but is long (3 sequential single-body solves): it runs on a side stream while step 0 of
+// MultiStepSim (which uses no cloud rows) proceeds for all other frames; the reset frames then do their step 0 on their own.
+// (Taking the reset frames through ALL their steps on the side stream was measured: their five few-frame steps are pure latency and end
+// later than the main stream's full-batch steps plus this one extra step, 4.6 against 4.5 ms.)
+static void resets_short(ht_ctx *ctx, int B, hipStream_t s)      // p.steps < 2, or HT_NO_STEP1_LAP
+{
+	reset_path(ctx, true, ctx->par.steps_unibody, B, ctx->side[0], s, ctx->many_reset);
+	multistep(ctx, B, steps_on(s).steps(0, 1).frames(ctx->d_nflags).rows_beside(0).shares_gpu());
+	join(ctx, s, 1); reset_tail(ctx);
+	multistep(ctx, B, steps_on(s).steps(0, 1).frames(ctx->d_flags).rows_beside(0));
+	multistep(ctx, B, steps_on(s).steps(1).all_frames().rows_beside(0));
+}
+static void resets_joined_late(ht_ctx *ctx, int B, hipStream_t s, int join_step)      // experiment (HT_RESET_JOIN): the reset frames take steps [0, join_step) on the side stream
+{
+	reset_path(ctx, true, ctx->par.steps_unibody, B, ctx->side[0], s, ctx->many_reset);
+	multistep(ctx, B, steps_on(ctx->side[0]).steps(0, join_step).frames(ctx->d_flags).in_order().unprofiled().shares_gpu());
+	multistep(ctx, B, steps_on(s).steps(0, join_step).frames(ctx->d_nflags).rows_beside(1).shares_gpu());
+	join(ctx, s, 1); reset_tail(ctx);
+	multistep(ctx, B, steps_on(s).steps(join_step).all_frames().rows_beside(0));
+}
+static void resets_lap(ht_ctx *ctx, int B, hipStream_t s)      // p.steps >= 2
+{
+	// The reset frames' chain -- the reset kernel, then their own first step (eight frames: pure latency) -- is what the batch ends up waiting for, and its
+	// few long blocks must find CUs although the batch's kernels ask for all of them (a cooperative contact block for a whole CU's LDS).  So the chain
+	// stays on THIS stream, where it is dispatched the moment the CNN ends, and the batch's first step goes to the side stream, which only starts
+	// after a cross-queue wait: launched the other way round the reset blocks often found no CU until the batch's contact kernel had finished.
+	// While the reset frames take their first step the batch prepares its second (cloud rows and contacts of the other frames: a frame's rows and
+	// contacts are its own), after the reset frames' contact blocks are in (same reason); the reset frames' rows for step 1 follow their solve on this
+	// stream, beside the batch's.  Then ONE solve for all frames.  (The reset frames any further behind the batch was measured and does not pay:
+	// DESIGN.md section 4.)  What the reset frames' contact blocks wait for (event marks): the batch's first solve -- both contact kernels want more
+	// registers than a SIMD has left beside a solver wave (256 and 410 against 512 - 168), so they start when that solve ends, 0.55 ms after the fork,
+	// however early the reset kernel is through (0.25 ms); making the batch's solve wait for them instead was measured: 5.39 against 5.31 ms.
+	hipStream_t u = ctx->side[0];
+	const int *reset_frames = ctx->d_flags, *batch_frames = ctx->d_nflags;
+	mark("fork", s);
+	reset_path(ctx, true, ctx->par.steps_unibody, B, s, s, ctx->many_reset); mark("reset kernel done", s);
+	multistep(ctx, B, steps_on(u).steps(0, 1).frames(batch_frames).in_order().unprofiled().shares_gpu()); mark("batch step 0 done", u);
+	multistep(ctx, B, steps_on(s).steps(0, 1).frames(reset_frames).in_order().rows_only()); mark("reset frames contacts done", s);
+	(void)hipEventRecord(ctx->ev_lap, s); (void)hipStreamWaitEvent(u, ctx->ev_lap, 0);
+	multistep(ctx, B, steps_on(s).steps(0, 1).frames(reset_frames).in_order().solve_only()); mark("reset frames step 0 done", s);
+	multistep(ctx, B, steps_on(u).steps(1, 2).frames(batch_frames).in_order().unprofiled().rows_only()); mark("batch step 1 rows done", u);      // in order on the side stream: there is time (0.76 against 0.82 ms), and a fork out of a forked stream does not survive a HIP graph capture
+	multistep(ctx, B, steps_on(s).steps(1, 2).frames(reset_frames).rows_beside(1).rows_only()); mark("reset frames step 1 rows done", s);      // the reset frames' rows for step 1, beside the batch's
+	join(ctx, s, 1); reset_tail(ctx);
+	multistep(ctx, B, steps_on(s).steps(1, 2).all_frames().solve_only()); mark("step 1 done", s);
+	multistep(ctx, B, steps_on(s).steps(2).all_frames().rows_beside(0)); mark("MultiStepSim done", s);
+}
+// The overlapped update behind the net: the side branch comes back, then the reset frames and MultiStepSim in one of the organisations above
+static void update_resets(ht_ctx *ctx, const update_call &u)
+{
+	hipStream_t s = u.s; join1(ctx, s, 1);      // the side branch comes back
+	static const int join_step = ht_tuning_int("HT_RESET_JOIN", 0);      // experiment (-DHT_TUNING): the reset frames take steps [0, join_step) on the side stream
+	fork(ctx, s);
+	const unsigned frames = ctx->h_nreset[0], updates = ctx->h_nreset[1];      // few or many reset frames (ht_host.hpp: d_nreset): the average over the updates whose counts have arrived since the last look
+	if (updates != ctx->nreset_seen[1])
 	{
-		const int passes = p.angles_only ? 0 : p.mainthreadpasses;
-		update_planes(s);
-		for (int i = 0; i < passes; i++) main_pass(ctx, B, s, i + 1 == passes ? d_poses_out : nullptr, i);
-		if (passes < 1) ht_launch_output(ctx->model, ctx->d_state[0], p.subsample_voxel ? ctx->d_nptsv : ctx->d_npts, ctx->d_initializing, p.min_point_num, d_poses_out, B, s);
-		return HT_OK;
+		ctx->many_reset = (frames - ctx->nreset_seen[0]) / (updates - ctx->nreset_seen[1]) > (unsigned)ctx->n_cu;
+		ctx->nreset_seen[0] = frames; ctx->nreset_seen[1] = updates;
 	}
-	float *cnn_out = d_cnn_out ? d_cnn_out : ctx->d_cnn_out;
+	static const bool no_lap = ht_tuning_env("HT_NO_STEP1_LAP");      // experiment (-DHT_TUNING)
+	if (join_step > 0) resets_joined_late(ctx, u.B, s, join_step);
+	else if (ctx->par.steps >= 2 && !no_lap) resets_lap(ctx, u.B, s);
+	else resets_short(ctx, u.B, s);
+}
+// FitError of the CNN-driven pose, and on its last thread the accept step (handtrack.h:713-731)
+static void update_accept(ht_ctx *ctx, const update_call &u)
+{
+	const ht_params &p = ctx->par;
+	ht_fit_after acc; memset(&acc, 0, sizeof acc);
+	acc.mode = 2; acc.hand = u.mode == UPD_CNN_MODEL ? nullptr : ctx->d_state[0]; acc.other = ctx->d_state[1]; acc.err_old = ctx->d_err_old; acc.prev_err = ctx->d_prev_err;
+	acc.initializing = ctx->d_initializing; acc.accepted = ctx->d_accepted; acc.nb = ctx->model.nb; acc.min_point_num = p.min_point_num; acc.always_take_cnn = p.always_take_cnn;
+	acc.angles_only = p.angles_only; acc.accum_thr = p.accum_error_threshold; ht_prof_scope ps(ctx, "fit_error", u.s, true);
+	ht_launch_fit_error(ctx->model, ctx->d_state[1], ctx->d_pts, ctx->d_npts, u.d_depth, u.img_cams, u.iw, u.ih, p.bone_sum_error_scale, ctx->d_err_new, u.B, u.s, &acc);
+}
+static void update_passes(ht_ctx *ctx, const update_call &u)      // the main-thread passes on handmodel and the user poses: the last pass's solve writes them, k_output when there is no pass
+{
+	const ht_params &p = ctx->par;
+	const int passes = p.angles_only ? 0 : p.mainthreadpasses;
+	for (int i = 0; i < passes; i++) { main_pass(ctx, u.B, u.s, i + 1 == passes ? u.d_poses_out : nullptr, i); mark("pass done", u.s); }
+	if (passes < 1) ht_launch_output(ctx->model, ctx->d_state[0], p.subsample_voxel ? ctx->d_nptsv : ctx->d_npts, ctx->d_initializing, p.min_point_num, u.d_poses_out, u.B, u.s);
+}
+static int run_update_(ht_ctx *ctx, update_call &u)
+{
+	const ht_params &p = ctx->par; hipStream_t s = u.s;
+	if (u.mode == UPD_PASSES) {}      // no net in the caller's part
+	else if (u.fs && u.fs->direct) { if (!ctx->have_weights128) { ctx->err = "weights of the 128x128 net not loaded (ht_cnn_load_weights_sized)"; return HT_ERR_STATE; } }
+	else if (!ctx->have_weights) { ctx->err = "CNN weights not loaded (ht_cnn_load_weights)"; return HT_ERR_STATE; }
+	{ const int r = update_inputs(ctx, u); if (r) return r; }
+	if (u.mode == UPD_PASSES) { update_planes(ctx, u, s); update_passes(ctx, u); return HT_OK; }
 	static const bool no_overlap = ht_tuning_env("HT_NO_OVERLAP");      // timing experiments (-DHT_TUNING builds only)
 	const bool overlap = !no_overlap && !ctx->profile_phases && p.steps >= 1 && p.steps_cloudstart >= 1 && !p.angles_only && ctx->solver_build != 5;
-	ht_fit_after dec; memset(&dec, 0, sizeof dec);      // the reset decision that FitError of the carried pose ends with (handtrack.h:706)
-	dec.mode = 1; dec.reset_thr = p.full_reset_on_error; dec.angles_only = p.angles_only; dec.flags = ctx->d_flags; dec.nflags = ctx->d_nflags; dec.list = ctx->d_flist; dec.nlist = ctx->d_nflist; dec.nreset = ctx->d_nreset;
-	if (overlap)
+	if (overlap) update_beside_net(ctx, u);
+	else { contact_orders(ctx, u.B, s); update_planes(ctx, u, s); }
+	update_net(ctx, u, overlap);
+	if (overlap) update_resets(ctx, u);
+	else      // the same on one stream, in the reference's order
 	{
-		// Nothing on this side branch needs the CNN: the error of the carried pose and the reset decision only read the point cloud and the
-		// tracker state, so they run beside the CNN.  (The contacts of MultiStepSim's first step do not need it either, but the contact kernel
-		// owns whole CUs and the FC layers want one block per CU: beside each other they took 0.78 ms, one after the other 0.46.)
-		hipStream_t t = ctx->side[1];
-		fork(ctx, s);
-		update_planes(t);
-		contact_orders(ctx, B, t);
-		if (mode == UPD_FULL && !(d_start && !fs)) ht_launch_set_pose(ctx->d_state[1], ctx->d_state[0], nb, B, 2, t);     // othermodel.SetPose(handmodel.GetPose()) handtrack.h:757 (both were just seeded with the same pose otherwise)
-		ht_launch_fit_error(ctx->model, ctx->d_state[0], ctx->d_pts, ctx->d_npts, d_depth, img_cams, iw, ih, p.bone_sum_error_scale, ctx->d_err_old, B, t, &dec);      // with the reset decision (handtrack.h:706)
+		if (u.mode == UPD_FULL) ht_launch_set_pose(ctx->d_state[1], ctx->d_state[0], ctx->model.nb, u.B, 2, s);     // othermodel.SetPose(handmodel.GetPose()) handtrack.h:757
+		{ ht_prof_scope ps(ctx, "fit_error", s, true); update_fit_error_old(ctx, u, s); }
+		reset_path(ctx, true, p.steps_unibody, u.B, s, s);
+		multistep(ctx, u.B, steps_on(s).all_frames().rows_beside(0));
 	}
-	if (!overlap) { contact_orders(ctx, B, s); update_planes(s); }
-	{
-		ht_prof_scope ps(ctx, (fs && fs->direct) ? "cnn128" : "cnn", s, true);
-		if (fs && fs->direct) ht_launch_cnn(ctx->cnnw128, ctx->d_in128, ctx->d_act1_128, ctx->d_act2_128, ctx->d_act3, ctx->d_logits, B, s, fs->direct, overlap);
-		else ht_launch_cnn(ctx->cnnw, ctx->d_cnn_in, ctx->d_act1, ctx->d_act2, ctx->d_act3, ctx->d_logits, B, s, 64, overlap);      // overlap: the side branch's FitError runs beside the net
-		ht_launch_softmax_decode(ctx->d_logits, cnn_out, ctx->d_cams, ctx->d_analysis, 1, B, s, (fs && fs->direct) ? fs->direct / 16 : 4);
-	}
-	if (overlap)
-	{
-		(void)hipEventRecord(ctx->ev_join[1], ctx->side[1]); (void)hipStreamWaitEvent(s, ctx->ev_join[1], 0);
-		// the full-reset path touches few frames but is long (3 sequential single-body solves): it runs on a side stream while step 0 of
-		// MultiStepSim (which uses no cloud rows) proceeds for all other frames; the reset frames then do their step 0 on their own.
-		// (Taking the reset frames through ALL their steps on the side stream was measured: their five few-frame steps are pure latency and end
-		// later than the main stream's full-batch steps plus this one extra step, 4.6 against 4.5 ms.)
-		static const int join_step = ht_tuning_int("HT_RESET_JOIN", 0);      // experiment (-DHT_TUNING): the reset frames take steps [0, join_step) on the side stream
-		fork(ctx, s);
-		{
-			// few or many reset frames (ht_host.hpp: d_nreset): the average over the updates whose counts have arrived since the last look
-			const unsigned frames = ctx->h_nreset[0], updates = ctx->h_nreset[1];
-			if (updates != ctx->nreset_seen[1])
-			{
-				ctx->many_reset = (frames - ctx->nreset_seen[0]) / (updates - ctx->nreset_seen[1]) > (unsigned)ctx->n_cu;
-				ctx->nreset_seen[0] = frames; ctx->nreset_seen[1] = updates;
-			}
-		}
-		static const bool no_lap = ht_tuning_env("HT_NO_STEP1_LAP");      // experiment (-DHT_TUNING)
-		if (join_step > 0)
-		{
-			reset_path(ctx, true, p.steps_unibody, B, ctx->side[0], s, ctx->many_reset);
-			multistep(ctx, B, ctx->side[0], 0, join_step, ctx->d_flags, false, -1, false, true);
-			multistep(ctx, B, s, 0, join_step, ctx->d_nflags, false, 1, true, true);
-			join(ctx, s, 1);
-			reset_tail(ctx);
-			multistep(ctx, B, s, join_step);
-		}
-		else if (p.steps >= 2 && !no_lap)
-		{
-			// The reset frames' chain -- the reset kernel, then their own first step (eight frames: pure latency) -- is what the batch ends up waiting for, and its
-			// few long blocks must find CUs although the batch's kernels ask for all of them (a cooperative contact block for a whole CU's LDS).  So the chain
-			// stays on THIS stream, where it is dispatched the moment the CNN ends, and the batch's first step goes to the side stream, which only starts
-			// after a cross-queue wait: launched the other way round the reset blocks often found no CU until the batch's contact kernel had finished.
-			// While the reset frames take their first step the batch prepares its second (cloud rows and contacts of the other frames: a frame's rows and
-			// contacts are its own), after the reset frames' contact blocks are in (same reason); the reset frames' rows for step 1 follow their solve on this
-			// stream, beside the batch's.  Then ONE solve for all frames.  (The reset frames any further behind the batch was measured and does not pay:
-			// DESIGN.md section 4.)  What the reset frames' contact blocks wait for (event marks): the batch's first solve -- both contact kernels want more
-			// registers than a SIMD has left beside a solver wave (256 and 410 against 512 - 168), so they start when that solve ends, 0.55 ms after the fork,
-			// however early the reset kernel is through (0.25 ms); making the batch's solve wait for them instead was measured: 5.39 against 5.31 ms.
-			hipStream_t u = ctx->side[0];
-			mark("fork", s);
-			reset_path(ctx, true, p.steps_unibody, B, s, s, ctx->many_reset);
-			mark("reset kernel done", s);
-			multistep(ctx, B, u, 0, 1, ctx->d_nflags, false, -1, false, true);
-			mark("batch step 0 done", u);
-			multistep(ctx, B, s, 0, 1, ctx->d_flags, false, -1, true, false, 1);
-			mark("reset frames contacts done", s);
-			(void)hipEventRecord(ctx->ev_lap, s); (void)hipStreamWaitEvent(u, ctx->ev_lap, 0);
-			multistep(ctx, B, s, 0, 1, ctx->d_flags, false, -1, true, false, 2);
-			mark("reset frames step 0 done", s);
-			multistep(ctx, B, u, 1, 2, ctx->d_nflags, false, -1, false, false, 1);      // in order on the side stream: there is time (0.76 against 0.82 ms), and a fork out of a forked stream does not survive a HIP graph capture
-			mark("batch step 1 rows done", u);
-			multistep(ctx, B, s, 1, 2, ctx->d_flags, false, 1, true, false, 1);      // the reset frames' rows for step 1, beside the batch's
-			mark("reset frames step 1 rows done", s);
-			join(ctx, s, 1);
-			reset_tail(ctx);
-			multistep(ctx, B, s, 1, 2, nullptr, false, 0, true, false, 2);
-			mark("step 1 done", s);
-			multistep(ctx, B, s, 2);
-			mark("MultiStepSim done", s);
-		}
-		else
-		{
-			reset_path(ctx, true, p.steps_unibody, B, ctx->side[0], s, ctx->many_reset);
-			multistep(ctx, B, s, 0, 1, ctx->d_nflags, false, 0, true, true);
-			join(ctx, s, 1);
-			reset_tail(ctx);
-			multistep(ctx, B, s, 0, 1, ctx->d_flags);
-			multistep(ctx, B, s, 1);
-		}
-	}
-	else
-	{
-		if (mode == UPD_FULL) ht_launch_set_pose(ctx->d_state[1], ctx->d_state[0], nb, B, 2, s);     // othermodel.SetPose(handmodel.GetPose()) handtrack.h:757
-		{ ht_prof_scope ps(ctx, "fit_error", s, true); ht_launch_fit_error(ctx->model, ctx->d_state[0], ctx->d_pts, ctx->d_npts, d_depth, img_cams, iw, ih, p.bone_sum_error_scale, ctx->d_err_old, B, s, &dec); }
-		reset_path(ctx, true, p.steps_unibody, B, s, s);
-		multistep(ctx, B, s);
-	}
-	{
-		// FitError of the CNN-driven pose, and on its last thread the accept step (handtrack.h:713-731)
-		ht_fit_after acc; memset(&acc, 0, sizeof acc);
-		acc.mode = 2; acc.hand = mode == UPD_CNN_MODEL ? nullptr : ctx->d_state[0]; acc.other = ctx->d_state[1]; acc.err_old = ctx->d_err_old; acc.prev_err = ctx->d_prev_err;
-		acc.initializing = ctx->d_initializing; acc.accepted = ctx->d_accepted; acc.nb = nb; acc.min_point_num = p.min_point_num; acc.always_take_cnn = p.always_take_cnn;
-		acc.angles_only = p.angles_only; acc.accum_thr = p.accum_error_threshold;
-		ht_prof_scope ps(ctx, "fit_error", s, true);
-		ht_launch_fit_error(ctx->model, ctx->d_state[1], ctx->d_pts, ctx->d_npts, d_depth, img_cams, iw, ih, p.bone_sum_error_scale, ctx->d_err_new, B, s, &acc);
-	}
-	if (mode != UPD_FULL) { ht_launch_output(ctx->model, ctx->d_state[1], ctx->d_npts, ctx->d_initializing, p.min_point_num, d_poses_out, B, s, 1); reset_tail_join(ctx, s); return HT_OK; }      // othermodel.GetPose()
-	const int passes = p.angles_only ? 0 : p.mainthreadpasses;
+	update_accept(ctx, u);
+	if (u.mode != UPD_FULL) { ht_launch_output(ctx->model, ctx->d_state[1], ctx->d_npts, ctx->d_initializing, p.min_point_num, u.d_poses_out, u.B, s, 1); reset_tail_join(ctx, s); return HT_OK; }      // othermodel.GetPose()
 	mark("accept done", s);
-	for (int i = 0; i < passes; i++) { main_pass(ctx, B, s, i + 1 == passes ? d_poses_out : nullptr, i); mark("pass done", s); }      // the last pass's solve writes the poses
-	if (passes < 1) ht_launch_output(ctx->model, ctx->d_state[0], p.subsample_voxel ? ctx->d_nptsv : ctx->d_npts, ctx->d_initializing, p.min_point_num, d_poses_out, B, s);
-	reset_tail_join(ctx, s);
-	mark("update done", s);
+	update_passes(ctx, u);
+	reset_tail_join(ctx, s); mark("update done", s);
 	marks_dump();
 	return HT_OK;
 }
+static int run_update(ht_ctx *ctx, const uint16_t *d_depth, const float *d_cams, const float *d_start, int B, float *d_poses_out, float *d_cnn_out, hipStream_t s, const frame_src *fs = nullptr, int mode = UPD_FULL)
+{
+	update_call u = { d_depth, d_cams, d_start, B, d_poses_out, d_cnn_out, s, fs, mode, nullptr, 64, 64 };
+	const int r = run_update_(ctx, u);
+	ctx->model.frame_order = nullptr;      // the launch order of the block-per-frame kernels belongs to the update that made it
+	ctx->planes_valid = false;             // and so do the boundary planes of its cloud
+	return r;
+}
+static int update_dev_end(ht_ctx *ctx, int r) { if (r) return r; HIPCHK(ctx, hipGetLastError()); return HT_OK; }      // what a *_dev update ends with: nothing is waited for, a launch that failed is reported
 
 // ---- public entry points ----------------------------------------------------------------------------------------------
 extern "C" int ht_tracker_reset(ht_ctx *ctx, int first, int n, const float *poses)
@@ -483,10 +518,7 @@ extern "C" int ht_update_dev(ht_ctx *ctx, const uint16_t *d_depth, const float *
 {
 	CHECK_READY(ctx); CHECK_MODEL(ctx); CHECK_BATCH(ctx, B);
 	if (!d_depth || !d_cams || !d_poses_out) return HT_ERR_ARG;
-	int r = run_update(ctx, d_depth, d_cams, d_start_poses, B, d_poses_out, nullptr, ht_user_stream(ctx, stream));
-	if (r) return r;
-	HIPCHK(ctx, hipGetLastError());
-	return HT_OK;
+	return update_dev_end(ctx, run_update(ctx, d_depth, d_cams, d_start_poses, B, d_poses_out, nullptr, ht_user_stream(ctx, stream)));
 }
 // ---- the synchronous update calls: frames up, run_update, results down --------------------------------------------------
 // Upload: a 64x64 tile goes to d_depth / d_cams, a frame of any other size to d_frames (which follows the largest frame size seen) / d_frame_cams_in.
@@ -541,9 +573,8 @@ extern "C" int ht_update_sync(ht_ctx *ctx, const uint16_t *depth, const float *c
 // HandTracker::update on frames of any size up to 320x240 (handtrack.h:693-785): segmentation for the CNN inside, the cloud of the full frame
 static int frames_args_ok(ht_ctx *ctx, int w, int h)
 {
-	if (w == 64 && h == 64) return 1;
-	if (!ht_segment_supported(w, h)) { ctx->err = "ht_update_frames: frame size must be a multiple of 4 and at most 320x240 pixels"; return 0; }
-	return 1;
+	if ((w == 64 && h == 64) || ht_segment_supported(w, h)) return 1;
+	ctx->err = "ht_update_frames: frame size must be a multiple of 4 and at most 320x240 pixels"; return 0;
 }
 extern "C" int ht_update_frames_dev(ht_ctx *ctx, const uint16_t *d_depth, const float *d_cams, int w, int h, float segment_scale, const float *d_start_poses, int B, float *d_poses_out, void *stream)
 {
@@ -552,10 +583,7 @@ extern "C" int ht_update_frames_dev(ht_ctx *ctx, const uint16_t *d_depth, const 
 	if (!frames_args_ok(ctx, w, h)) return HT_ERR_ARG;
 	hipStream_t s = ht_user_stream(ctx, stream);
 	const frame_src fs = { w, h, segment_scale, 0 };
-	int r = run_update(ctx, d_depth, d_cams, d_start_poses, B, d_poses_out, nullptr, s, (w == 64 && h == 64) ? nullptr : &fs);
-	if (r) return r;
-	HIPCHK(ctx, hipGetLastError());
-	return HT_OK;
+	return update_dev_end(ctx, run_update(ctx, d_depth, d_cams, d_start_poses, B, d_poses_out, nullptr, s, (w == 64 && h == 64) ? nullptr : &fs));
 }
 // Capacities of the contact kernel that the reference does not have: expanding-polytope runs cut short (128 iterations, 96 vertices, 192
 // triangles in LDS; hull.h:246 loops without bound), touching samples beyond the 192 of a frame's pool, and solves whose angular rows exceed the 126
@@ -625,10 +653,7 @@ extern "C" int ht_update_direct_dev(ht_ctx *ctx, const uint16_t *d_depth, const 
 	if (((uintptr_t)d_depth & 15) != 0) { ctx->err = "ht_update_direct_dev: d_depth must be 16-byte aligned (the input transform reads eight pixels per 128-bit load)"; return HT_ERR_ARG; }
 	hipStream_t s = ht_user_stream(ctx, stream);
 	const frame_src fs = { side, side, 0.0f, side };
-	int r = run_update(ctx, d_depth, d_cams, d_start_poses, B, d_poses_out, nullptr, s, &fs);
-	if (r) return r;
-	HIPCHK(ctx, hipGetLastError());
-	return HT_OK;
+	return update_dev_end(ctx, run_update(ctx, d_depth, d_cams, d_start_poses, B, d_poses_out, nullptr, s, &fs));
 }
 extern "C" int ht_update_direct_sync(ht_ctx *ctx, const uint16_t *depth, const float *cams, int side, int B, float *poses_out, float *cnn_out)
 {
@@ -813,7 +838,7 @@ extern "C" int ht_stage_contacts(ht_ctx *ctx, int which, int B, int cap, float *
 	CHECK_READY(ctx); CHECK_MODEL(ctx); CHECK_BATCH(ctx, B);
 	if (!contacts || !ncontacts || which < 0 || which > 1 || cap < 1) return HT_ERR_ARG;
 	hipStream_t s = ctx->stream;
-	ht_launch_contacts(ctx->model, ctx->d_state[which], ctx->phys.driftmax, ctx->phys.jiggle_sin, nullptr, ctx->d_epa_ws, ctx->d_contacts, ctx->d_ncontacts, B, s, false, ctx->contact_kernel);
+	launch_contacts(ctx, which, nullptr, B, s);
 	std::vector<float> tmp((size_t)B * HT_MAXCONTACT * HT_CONTACT);
 	HIPCHK(ctx, hipMemcpyAsync(tmp.data(), ctx->d_contacts, tmp.size() * sizeof(float), hipMemcpyDeviceToHost, s));
 	HIPCHK(ctx, hipMemcpyAsync(ncontacts, ctx->d_ncontacts, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, s));
@@ -839,11 +864,11 @@ template <class F> static int stage_on_analysis(ht_ctx *ctx, const float *analys
 	launch(s);
 	return ht_sync_check(ctx, s);
 }
-extern "C" int ht_stage_multistep(ht_ctx *ctx, const float *analysis, int B) { return stage_on_analysis(ctx, analysis, B, [&](hipStream_t s) { multistep(ctx, B, s); }); }
+extern "C" int ht_stage_multistep(ht_ctx *ctx, const float *analysis, int B) { return stage_on_analysis(ctx, analysis, B, [&](hipStream_t s) { multistep(ctx, B, steps_on(s).all_frames()); }); }
 extern "C" int ht_stage_multistep_range(ht_ctx *ctx, const float *analysis, int B, int from_step, int to_step)
 {
 	const bool range_ok = from_step >= 0 && to_step >= from_step;
-	return stage_on_analysis(ctx, range_ok ? analysis : nullptr, B, [&](hipStream_t s) { multistep(ctx, B, s, from_step, to_step); });
+	return stage_on_analysis(ctx, range_ok ? analysis : nullptr, B, [&](hipStream_t s) { multistep(ctx, B, steps_on(s).steps(from_step, to_step).all_frames()); });
 }
 extern "C" int ht_stage_scratch_unibody(ht_ctx *ctx, const float *analysis, int B, int n_unibody) { return stage_on_analysis(ctx, analysis, B, [&](hipStream_t s) { reset_path(ctx, false, n_unibody, B, s, s); }); }
 
@@ -962,21 +987,10 @@ extern "C" int ht_segment_vr(ht_ctx *ctx, const uint16_t *depth, const float *ca
 {
 	CHECK_READY(ctx);
 	if (!depth || !cams || !tiles || !cams_out || B < 1 || w < 1 || h < 1) return HT_ERR_ARG;
-	uint16_t *d_in = nullptr, *d_tiles = nullptr; float *d_cams = nullptr, *d_co = nullptr;
-	const size_t nin = (size_t)B * w * h;
-	int rc = HT_OK;
-	if (hipMalloc((void **)&d_in, nin * sizeof(uint16_t)) != hipSuccess || hipMalloc((void **)&d_tiles, (size_t)B * 4096 * sizeof(uint16_t)) != hipSuccess ||
-	    hipMalloc((void **)&d_cams, (size_t)B * HT_CAM * sizeof(float)) != hipSuccess || hipMalloc((void **)&d_co, (size_t)B * HT_CAM * sizeof(float)) != hipSuccess)
-	{ ctx->err = "ht_segment_vr: out of device memory"; rc = HT_ERR_HIP; }
-	hipStream_t s = ctx->stream;
-	if (rc == HT_OK && (hipMemcpyAsync(d_in, depth, nin * sizeof(uint16_t), hipMemcpyHostToDevice, s) != hipSuccess ||
-	                    hipMemcpyAsync(d_cams, cams, (size_t)B * HT_CAM * sizeof(float), hipMemcpyHostToDevice, s) != hipSuccess)) { ctx->err = "ht_segment_vr: upload failed"; rc = HT_ERR_HIP; }
-	if (rc == HT_OK) rc = ht_segment_vr_dev(ctx, d_in, d_cams, w, h, B, entry_options, wrange_lo, wrange_hi, diam, d_tiles, d_co, s);
-	if (rc == HT_OK && (hipMemcpyAsync(tiles, d_tiles, (size_t)B * 4096 * sizeof(uint16_t), hipMemcpyDeviceToHost, s) != hipSuccess ||
-	                    hipMemcpyAsync(cams_out, d_co, (size_t)B * HT_CAM * sizeof(float), hipMemcpyDeviceToHost, s) != hipSuccess ||
-	                    hipStreamSynchronize(s) != hipSuccess)) { ctx->err = "ht_segment_vr: download failed"; rc = HT_ERR_HIP; }
-	(void)hipFree(d_in); (void)hipFree(d_tiles); (void)hipFree(d_cams); (void)hipFree(d_co);
-	return rc;
+	const size_t n = (size_t)B;      // staged through one device buffer of its own (ht_staged_call; no tracker slot: B is not bounded by max_batch)
+	ht_seg seg[4] = { { (void *)depth, n * w * h * sizeof(uint16_t), false }, { (void *)cams, n * HT_CAM * sizeof(float), false }, { tiles, n * 4096 * sizeof(uint16_t), true }, { cams_out, n * HT_CAM * sizeof(float), true } };
+	return ht_staged_call(ctx, &ctx->d_segment, &ctx->segment_cap, seg, 4, [&](hipStream_t s)
+	                      { return ht_segment_vr_dev(ctx, (const uint16_t *)seg[0].dev, (const float *)seg[1].dev, w, h, B, entry_options, wrange_lo, wrange_hi, diam, (uint16_t *)seg[2].dev, (float *)seg[3].dev, s); });
 }
 
 // ------------------------------------------------------------------------------------------------- caller-built constraint rows
@@ -1005,6 +1019,16 @@ static int upload_angulars(ht_ctx *ctx, int B, const float *angulars, int acap, 
 	HIPCHK(ctx, hipMemcpy(ctx->d_user_n + 3 * (size_t)ctx->B, na.data(), (size_t)B * sizeof(int), hipMemcpyHostToDevice));
 	return HT_OK;
 }
+// the solve of ht_fit_rows / ht_physics_update: the caller's angular rows (upload_angulars) join, then the stream is waited for
+static int solve_caller_rows(ht_ctx *ctx, solve_args &a, const std::vector<int> &na, int B, hipStream_t s)
+{
+	a.ang_user = ctx->d_user_ang; a.n_ang_user = ctx->d_user_n + 3 * (size_t)ctx->B; a.ang_user_stride = ctx->user_ang_cap;
+	{ int mx = 0; for (int v : na) mx = v > mx ? v : mx; a.ang_extra_bound = mx; }
+	a.force_build = ctx->solver_build;
+	ctx->model.pts_bound = 0;
+	ht_launch_solve(ctx->model, ctx->phys, a, B, s);
+	return ht_sync_check(ctx, s);
+}
 // void PhysModel::FitPointCloud(const std::vector<float3> &points, std::vector<LimitLinear> linears, std::vector<LimitAngular> angulars, float microforce)
 // on model `which` of slots [0,B): the caller's linear rows, then CloudConstraints(points) with the +-microforce limits (x physics_weak_force on
 // bodies 0-2), then the joints' nailed rows; the caller's angular rows, then the joints' range rows; PhysicsUpdate with collision; SanityCheck.  As
@@ -1028,6 +1052,7 @@ extern "C" int ht_fit_rows(ht_ctx *ctx, int which, int B, const float *points, i
 			if ((int)r[0] >= 0 || (int)r[1] < 0 || (int)r[1] >= nb || r[15] != 0.0f) { ctx->err = "ht_fit_rows: the caller's linear rows must act on one body from the world (rb0 == NULL, no friction master); use ht_physics_update for general rows"; return HT_ERR_ARG; }
 		}
 	}
+	REFUSE_EXACT_SOLVER(ctx);
 	{ const int r = user_rows_reserve(ctx, lcap > 1 ? lcap : 1, acap > 1 ? acap : 1); if (r) return r; }
 	{ const int r = upload_angulars(ctx, B, angulars, acap, nangulars, na); if (r) return r; }
 	// the points (ht_set_points grows the point capacity when it has to)
@@ -1044,23 +1069,11 @@ extern "C" int ht_fit_rows(ht_ctx *ctx, int which, int B, const float *points, i
 	ht_params par = ctx->par; par.microforce = microforce;
 	const cloud_records cr = cloud_rec(ctx);
 	ht_launch_cloud_rows(ctx->model, ctx->d_state[which], ctx->d_pts, ctx->d_npts, ctx->d_cams, nullptr, 1, 0, 1, par, ctx->d_rows, ctx->d_nrows, B, s, 0.0f, 0.0f, &cr);
-	if (coll) ht_launch_contacts(ctx->model, ctx->d_state[which], ctx->phys.driftmax, ctx->phys.jiggle_sin, nullptr, ctx->d_epa_ws, ctx->d_contacts, ctx->d_ncontacts, B, s, false, ctx->contact_kernel);
-	solve_args a;
-	memset(&a, 0, sizeof a);
-	a.sf_select = -1;
-	a.caps = reinterpret_cast<int *>(ctx->d_epa_ws) + 2;
+	if (coll) launch_contacts(ctx, which, nullptr, B, s);
+	solve_args a = solve_head(ctx, which, coll);
 	a.rows_pre = ctx->d_user_lin; a.n_pre = ctx->d_user_n; a.pre_stride = ctx->user_lin_cap;
 	a.cloud_body = ctx->d_rowbody; a.n_cloud = ctx->d_nrows;
-	a.contacts = coll ? ctx->d_contacts : nullptr; a.ncontacts = ctx->d_ncontacts;
-	a.ang_user = ctx->d_user_ang; a.n_ang_user = ctx->d_user_n + 3 * (size_t)ctx->B; a.ang_user_stride = ctx->user_ang_cap;
-	{ int mx = 0; for (int v : na) mx = v > mx ? v : mx; a.ang_extra_bound = mx; }
-	a.analysis = ctx->d_analysis; a.cams = ctx->d_cams;
-	a.state = ctx->d_state[which]; a.scratch = ctx->d_scratch; a.scratch_stride = scratch_stride(ctx); a.batch = ctx->B;
-	if (exact_solver(ctx)) { ctx->err = "the exact-order instantiation (ht_debug_solver_build 5) serves the update entry points only"; return HT_ERR_STATE; }
-	a.force_build = ctx->solver_build;
-	ctx->model.pts_bound = 0;
-	ht_launch_solve(ctx->model, ctx->phys, a, B, s);
-	return ht_sync_check(ctx, s);
+	return solve_caller_rows(ctx, a, na, B, s);
 }
 // void PhysicsUpdate(const std::vector<RigidBody*> &rigidbodies, std::vector<LimitLinear> &Linears, std::vector<LimitAngular> &Angulars, wgeom = {})
 // (physics.h:543-587) on model `which` of slots [0,B): the caller's rows are all there is (plus the collision rows when physics_use_collision is set).
@@ -1103,6 +1116,7 @@ extern "C" int ht_physics_update(ht_ctx *ctx, int which, int B, const float *lin
 		ngrp[b] = g + 1;
 		if (ngrp[b] > HT_MAXNJ) { ctx->err = "ht_physics_update: more than 32 groups of two-body rows in a frame"; return HT_ERR_ARG; }
 	}
+	REFUSE_EXACT_SOLVER(ctx);
 	if (most_pre > ctx->model.pts_cap) { const int r = ht_reserve_points_locked(ctx, most_pre); if (r) return r; }
 	{ const int r = user_rows_reserve(ctx, lcap > 1 ? lcap : 1, acap > 1 ? acap : 1); if (r) return r; }
 	{ const int r = upload_angulars(ctx, B, angulars, acap, nangulars, na); if (r) return r; }
@@ -1122,25 +1136,13 @@ extern "C" int ht_physics_update(ht_ctx *ctx, int which, int B, const float *lin
 	HIPCHK(ctx, hipMemcpy(ctx->d_user_n + 2 * (size_t)ctx->B, ngrp.data(), (size_t)B * sizeof(int), hipMemcpyHostToDevice));
 	hipStream_t s = ctx->stream;
 	const bool coll = ctx->phys.use_collision != 0;
-	if (coll) ht_launch_contacts(ctx->model, ctx->d_state[which], ctx->phys.driftmax, ctx->phys.jiggle_sin, nullptr, ctx->d_epa_ws, ctx->d_contacts, ctx->d_ncontacts, B, s, false, ctx->contact_kernel);
-	solve_args a;
-	memset(&a, 0, sizeof a);
-	a.sf_select = -1;
-	a.caps = reinterpret_cast<int *>(ctx->d_epa_ws) + 2;
+	if (coll) launch_contacts(ctx, which, nullptr, B, s);
+	solve_args a = solve_head(ctx, which, coll);
 	a.rows_cloud = ctx->d_rows; a.n_cloud = ctx->d_nrows;
-	a.contacts = coll ? ctx->d_contacts : nullptr; a.ncontacts = ctx->d_ncontacts;
-	a.ang_user = ctx->d_user_ang; a.n_ang_user = ctx->d_user_n + 3 * (size_t)ctx->B; a.ang_user_stride = ctx->user_ang_cap;
-	{ int mx = 0; for (int v : na) mx = v > mx ? v : mx; a.ang_extra_bound = mx; }
 	a.lin_tail = ctx->d_user_lin; a.n_lin_tail = ctx->d_user_n + (size_t)ctx->B; a.lin_tail_stride = ctx->user_lin_cap;
 	a.lin_tail_pos = ctx->d_user_pos; a.n_tail_groups = ctx->d_user_n + 2 * (size_t)ctx->B;
 	a.no_model_rows = 1;
-	a.analysis = ctx->d_analysis; a.cams = ctx->d_cams;
-	a.state = ctx->d_state[which]; a.scratch = ctx->d_scratch; a.scratch_stride = scratch_stride(ctx); a.batch = ctx->B;
-	if (exact_solver(ctx)) { ctx->err = "the exact-order instantiation (ht_debug_solver_build 5) serves the update entry points only"; return HT_ERR_STATE; }
-	a.force_build = ctx->solver_build;
-	ctx->model.pts_bound = 0;
-	ht_launch_solve(ctx->model, ctx->phys, a, B, s);
-	return ht_sync_check(ctx, s);
+	return solve_caller_rows(ctx, a, na, B, s);
 }
 
 // ------------------------------------------------------------------------------------------------- slowfit (annotation fit loop)
@@ -1150,6 +1152,7 @@ extern "C" int ht_slowfit(ht_ctx *ctx, int B, int hold, const float *refpose, in
 	CHECK_READY(ctx); CHECK_MODEL(ctx); CHECK_BATCH(ctx, B);
 	const int nb = ctx->model.nb;
 	if (steps < 1 || ncray < 0 || ncray > 8 || select_rb >= nb || (select_rb >= 0 && (!spoint || !rbpoint)) || (ncray > 0 && !crays)) { ctx->err = "ht_slowfit: bad arguments"; return HT_ERR_ARG; }
+	REFUSE_EXACT_SOLVER(ctx);
 	hipStream_t s = ctx->stream;
 	if (!ctx->d_sf_ref)
 	{
@@ -1166,21 +1169,15 @@ extern "C" int ht_slowfit(ht_ctx *ctx, int B, int hold, const float *refpose, in
 		const cloud_records cr = cloud_rec(ctx);
 		if (cloud) ht_launch_cloud_rows(ctx->model, ctx->d_state[0], ctx->d_pts, ctx->d_npts, ctx->d_cams, nullptr, 1, 0, 4, ctx->par, ctx->d_rows, ctx->d_nrows, B, s,
 		                                1.0f * (float)(steps - st) / (float)steps, 0.1f * (float)(st < steps - 2), &cr);
-		if (coll) ht_launch_contacts(ctx->model, ctx->d_state[0], ctx->phys.driftmax, ctx->phys.jiggle_sin, nullptr, ctx->d_epa_ws, ctx->d_contacts, ctx->d_ncontacts, B, s, false, ctx->contact_kernel);
-		solve_args a;
-		memset(&a, 0, sizeof a);
-		a.caps = reinterpret_cast<int *>(ctx->d_epa_ws) + 2;
+		if (coll) launch_contacts(ctx, 0, nullptr, B, s);
+		solve_args a = solve_head(ctx, 0, coll);
 		a.cloud_body = cloud ? ctx->d_rowbody : nullptr; a.n_cloud = ctx->d_nrows;
-		a.contacts = coll ? ctx->d_contacts : nullptr; a.ncontacts = ctx->d_ncontacts;
-		a.analysis = ctx->d_analysis; a.cams = ctx->d_cams;
-		a.state = ctx->d_state[0]; a.scratch = ctx->d_scratch; a.scratch_stride = scratch_stride(ctx); a.batch = ctx->B;
 		a.sf_ncray = st < 5 ? ncray : 0; a.sf_crays = ctx->d_sf_crays; a.sf_select = select_rb;
 		for (int i = 0; i < 3; i++) { a.sf_spoint[i] = spoint ? spoint[i] : 0.0f; a.sf_rbpoint[i] = rbpoint ? rbpoint[i] : 0.0f; }
 		a.ray_rows = (a.sf_ncray > 0 || select_rb >= 0) ? 1 : 0;
 		a.sf_refpose = rel ? ctx->d_sf_ref : nullptr; a.sf_hold = rel ? hold : 0;
 		a.ang_extra_bound = rel ? 3 * ctx->model.nj : 0;      // RelativeAngularConstraints: one row per ranged axis of a joint at most
 		a.steps_keyangles = ctx->par.steps_keyangles; a.min_cray_prob = ctx->par.min_cray_prob;
-		if (exact_solver(ctx)) { ctx->err = "the exact-order instantiation (ht_debug_solver_build 5) serves the update entry points only"; return HT_ERR_STATE; }
 		a.force_build = ctx->solver_build;
 		ht_launch_solve(ctx->model, ctx->phys, a, B, s);
 	}

@@ -54,6 +54,15 @@ def test_refused_calls_leave_the_context_usable():
             ctx.update_direct_dev(d.data_ptr() + 2, dc.data_ptr(), 128, 0, B, out.data_ptr(), 0)  # a device pointer the 128-bit loads cannot take
         with pytest.raises(AttributeError):
             ctx.set_params(no_such_parameter=1)
+        # the exact-order instantiation serves the update entry points only: a solve of caller-built rows is refused BEFORE its first upload -- the context's cloud
+        # (which ht_fit_rows would replace with the caller's points) is the one the update left
+        rows_before, n_before = ctx.stage_cloud_rows(0, 1, 0, B)
+        ctx.debug_solver_build(5)
+        with pytest.raises(native.HTError, match="exact-order instantiation"):
+            ctx.fit_rows(0, [np.full((7, 3), 0.3, np.float32)] * B, [[]] * B, [[]] * B)
+        ctx.debug_solver_build(0)
+        rows_after, n_after = ctx.stage_cloud_rows(0, 1, 0, B)
+        assert n_before.min() > 7 and np.array_equal(n_before, n_after) and all(np.array_equal(rows_before[b, :n_before[b]], rows_after[b, :n_after[b]]) for b in range(B))
         # nothing above touched the trackers: the same update gives the same poses
         again = ctx.update_sync(depth, cams)
         assert np.array_equal(good, again)

@@ -361,3 +361,64 @@ def test_exact_order_solver_follows_a_stream_with_every_knob_moved(weights, name
     resets = np.stack([d[5] for d in dev])
     print("%-55s: %d of %d trackers leave the restatement's stream (first at %s); full resets per update %s" % (name, len(bad), T, bad[:4], resets.sum(axis=1).tolist()))
     assert not bad, bad
+
+
+_FORKED = [
+    ("one step", dict(steps=1, steps_cloudstart=1, steps_keypoints=1, steps_keyangles=1, steps_palmangle=1, full_reset_on_error=0.2)),
+    ("default steps", dict(full_reset_on_error=0.2)),
+]
+
+
+@pytest.mark.parametrize("name,knobs", _FORKED, ids=[v[0].replace(" ", "_") for v in _FORKED])
+def test_exact_order_solver_follows_a_stream_under_the_products_launch_sequence(weights, name, knobs):
+    """The overlapped update organises its full-reset frames in one of two ways beside the batch's MultiStepSim: the lap (steps >= 2: the reset frames' chain on the
+    update's stream, the batch's first step on a side stream, one common solve from step 1 on) and the short form (steps < 2: the reset kernel on the side stream beside
+    the batch's only step, then the reset frames' step).  Build 8 keeps that choreography around the exact-order sweeps, so a three-update stream on 32 trackers must
+    equal the restatement bit for bit after every update in both.  An eager full_reset_on_error makes the stream carry real reset frames: with 0.2 the restatement on
+    its own (its own net) sends 1, 14, 21 of the 32 trackers through the full reset in the three updates with one step, and 1, 14, 20 with the default step counts."""
+    from hand_tracking_samples_amd import native
+    T, K = 32, 3
+    idx = [(32 * np.arange(T) + 5 + k) % N for k in range(K)]
+    depth = FR["depth"].reshape(N, -1); start = FR["startpose"][idx[0]]
+    par = dict(microforce=3.0, mainthreadpasses=3); par.update(knobs)
+    ctx = native.Context(ol.MODEL, T)
+    try:
+        ctx.load_weights(weights)
+        ctx.set_params(**par)
+        ctx.debug_solver_build(8)
+        ctx.tracker_reset(start)
+        dev = []
+        for k in range(K):
+            p, c = ctx.update_sync(depth[idx[k]], FR["cam"][idx[k]], want_cnn=True)
+            dev.append((p, c, ctx.get_state(1, T), ctx.get_state(0, T), np.stack(ctx.tracker_flags(T), 1).astype(np.float32), ctx.debug_reset_flags(T)))
+        assert ctx.capacity_events() == (0, 0, 0)
+    finally:
+        ctx.debug_solver_build(0)
+        ctx.close()
+    resets = np.stack([d[5] for d in dev]).sum(axis=1).tolist()
+    print("%-14s: full resets per update %s of %d" % (name, resets, T))
+    assert any(0 < r < T for r in resets), resets      # the forked sequence ran with reset frames AND batch frames
+    orc = ol.Oracle(weights)
+    for k_, v in par.items():
+        setattr(orc.head.par, k_, v)
+    orc.L.ho_set_round_once(1)
+    bad = []
+    try:
+        for i in range(T):
+            orc.reset(start[i])
+            for k in range(K):
+                f = idx[k][i]
+                cam = ol.camera(FR["cam"][f], 64, 64)
+                orc.L.ho_set_cnn_override(orc.h, ol.fptr(np.ascontiguousarray(dev[k][1][i])))
+                user = np.zeros((orc.nb, 7), np.float32)
+                orc.L.ho_update(orc.h, ol.u16ptr(np.ascontiguousarray(depth[f])), C.byref(cam), ol.fptr(user))
+                same = (np.array_equal(dev[k][0][i], user) and np.array_equal(dev[k][2][i], orc.get_state(1)) and np.array_equal(dev[k][3][i], orc.get_state(0))
+                        and np.array_equal(dev[k][4][i], np.array(orc.flags()[:2], np.float32)))
+                if not same:
+                    bad.append((i, k)); break
+        orc.L.ho_set_cnn_override(orc.h, None)
+    finally:
+        orc.L.ho_set_round_once(0)
+        orc.close()
+    print("%-14s: %d of %d trackers leave the restatement's stream (first at %s)" % (name, len(bad), T, bad[:4]))
+    assert not bad, bad
