@@ -381,21 +381,33 @@ __device__ __forceinline__ void cloud_rows_frame(const ht_model_dev &M, const fl
 		out[3] = make_float4(0.0f, fmin_std(fmin, fmax), fmax_std(fmin, fmax), 0.0f);
 	}
 }
+// (k_chamber's body further down: the plane-row blocks of a main-thread pass's cloud-row launch run it too)
+__device__ __forceinline__ void chamber_frame(const ht_model_dev &M, const float *__restrict__ state, float maxforce, float *__restrict__ rows, int *__restrict__ nch,
+                                              const float *__restrict__ planes_in, const int *__restrict__ on_in, const int b, float *tab, float (*planes)[4], int *voff);
+// A main-thread pass also hands this launch its boundary-plane rows (`pl.rows` set): one more block per frame, at the highest blockIdx.y -- dispatched last, so the
+// plane-row blocks fill the launch's ragged tail instead of competing for CUs as a launch of their own.  Their LDS is taken out of the cloud-row block's.
 __global__ __launch_bounds__(CR_THREADS) void k_cloud_rows(ht_model_dev M, const float *__restrict__ state, const float4 *__restrict__ pts, const int *__restrict__ npts,
                                                            const float *__restrict__ cams, const int *__restrict__ active_flag, int stride, int use_cam_origin, int mode,
                                                            float microforce, float weak_force, float cf_max_point, float cf_max_sum, float unibody_force,
-                                                           float *__restrict__ rows, int *__restrict__ nrows, cloud_records rec, int dbg)
+                                                           float *__restrict__ rows, int *__restrict__ nrows, cloud_records rec, plane_rows pl, int dbg)
 {
 	__shared__ float tab[HT_MAXNB * BT];
 	__shared__ closest_lds L;
 	__shared__ float wq[HT_MAXNB][4], wI[HT_MAXNB][10];      // record mode: the bodies' orientations, world inverse inertia and inverse mass, as k_solve forms them
+	static_assert(sizeof(closest_lds::v) >= 5 * 4 * sizeof(float) && sizeof(closest_lds::mask) >= (HT_MAXNB + 1) * sizeof(int), "the plane-row role runs in a cloud-row block and its LDS");
 	const int b = M.frame_order ? M.frame_order[blockIdx.x] : (int)blockIdx.x, t = threadIdx.x;
+	if (pl.rows && blockIdx.y + 1 == gridDim.y)      // the plane-row role: before anything of the cloud rows' own, which is compiled as without it
+	{
+		chamber_frame(M, state, pl.maxforce, pl.rows, pl.nch, pl.planes, pl.on, b, tab, reinterpret_cast<float (*)[4]>(L.v), reinterpret_cast<int *>(L.mask));
+		return;
+	}
+	const int ny = pl.rows ? (int)gridDim.y - 1 : (int)gridDim.y;
 	const int n = npts[b];
 	const int nsub = (n + stride - 1) / stride;
 	if (active_flag && !active_flag[b]) return;      // a masked launch leaves the other frames' rows and counts alone (another launch may be producing them)
-	if ((int)blockIdx.y * CH >= nsub && blockIdx.y > 0) return;      // gridDim.y blocks share a frame's passes (a row only depends on its own point)
+	if ((int)blockIdx.y * CH >= nsub && blockIdx.y > 0) return;      // ny blocks share a frame's passes (a row only depends on its own point)
 	if (t == 0 && blockIdx.y == 0) nrows[b] = nsub;
-	cloud_rows_frame(M, state, pts, cams, stride, use_cam_origin, mode, microforce, weak_force, cf_max_point, cf_max_sum, unibody_force, rows, nrows, rec, dbg, b, n, blockIdx.y, gridDim.y, tab, L, wq, wI);
+	cloud_rows_frame(M, state, pts, cams, stride, use_cam_origin, mode, microforce, weak_force, cf_max_point, cf_max_sum, unibody_force, rows, nrows, rec, dbg, b, n, blockIdx.y, ny, tab, L, wq, wI);
 }
 
 // ------------------------------------------------------------------------------------------------- k_reset
@@ -807,13 +819,12 @@ __global__ __launch_bounds__(256) void k_fit_error(ht_model_dev M, const float *
 // update (handtrack.h:769-780) share one scan made beside the net (a pass outside an update makes them first: ht_stage_chamber, ht_stage_fit).
 // Four waves per frame share the (plane, body) items: the kernel is the items' memory round trips one after the other, 85 items on one wave were 69 us per launch.
 #define CHB_THREADS 256
-__global__ __launch_bounds__(CHB_THREADS) void k_chamber(ht_model_dev M, const float *__restrict__ state, float maxforce, float *__restrict__ rows, int *__restrict__ nch,
-                                                        const float *__restrict__ planes_in, const int *__restrict__ on_in)
+// One frame's plane rows by one block of CHB_THREADS threads.  tab / planes / voff: the block's LDS (voff: the bodies' vertex ranges, picked per lane below: from LDS, not
+// from the kernel-argument segment).  k_chamber below and the plane-row blocks of a main-thread pass's cloud-row launch (k_cloud_rows) both run this.
+__device__ __forceinline__ void chamber_frame(const ht_model_dev &M, const float *__restrict__ state, float maxforce, float *__restrict__ rows, int *__restrict__ nch,
+                                              const float *__restrict__ planes_in, const int *__restrict__ on_in, const int b, float *tab, float (*planes)[4], int *voff)
 {
-	__shared__ float tab[HT_MAXNB * BT];
-	__shared__ float planes[5][4];
-	__shared__ int voff[HT_MAXNB + 1];      // vertex ranges of the bodies (picked per lane below: from LDS, not from the kernel-argument segment)
-	const int b = blockIdx.x, t = threadIdx.x, lane = t & 63, wave = t >> 6;
+	const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
 	const bool on = on_in[b] != 0;        // handtrack.h:774
 	if (t == 0) nch[b] = on ? 5 * M.nb : 0;
 	if (!on) return;
@@ -873,6 +884,15 @@ __global__ __launch_bounds__(CHB_THREADS) void k_chamber(ht_model_dev M, const f
 		}
 	}
 }
+__global__ __launch_bounds__(CHB_THREADS) void k_chamber(ht_model_dev M, const float *__restrict__ state, float maxforce, float *__restrict__ rows, int *__restrict__ nch,
+                                                        const float *__restrict__ planes_in, const int *__restrict__ on_in)
+{
+	__shared__ float tab[HT_MAXNB * BT];
+	__shared__ float planes[5][4];
+	__shared__ int voff[HT_MAXNB + 1];
+	chamber_frame(M, state, maxforce, rows, nch, planes_in, on_in, blockIdx.x, tab, planes, voff);
+}
+static_assert(CHB_THREADS == CR_THREADS, "the plane-row role of k_cloud_rows runs chamber_frame in a cloud-row block");
 
 // ------------------------------------------------------------------------------------------------- k_chamber_planes
 // The five containing planes alone (physmodel.h:183-193): they follow from the frame's points, not from the pose, so the three main-thread passes of an update
@@ -923,9 +943,10 @@ void ht_launch_chamber_planes(const ht_model_dev &M, const float4 *pts, const in
 // `rec`: instead of the 16-float rows, write each row's solver record into the frames' scratch slots and the rows' bodies into rec->body (k_solve then only
 // lists them per body); null: the reference-layout rows (stage calls, UnibodyFit)
 void ht_launch_cloud_rows(const ht_model_dev &M, const float *state, const float4 *pts, const int *npts, const float *cams, const int *active_flag, int stride, int use_cam_origin, int mode,
-                          const ht_params &par, float *rows, int *nrows, int B, hipStream_t s, float sf_ratio, float sf_wrist, const cloud_records *rec)
+                          const ht_params &par, float *rows, int *nrows, int B, hipStream_t s, float sf_ratio, float sf_wrist, const cloud_records *rec, const plane_rows *planes)
 {
 	const cloud_records none = { nullptr, 0, nullptr, 0.0f };
+	const plane_rows no_planes = { nullptr, nullptr, 0.0f, nullptr, nullptr };
 	// blocks per frame: a frame's passes of CH points are independent, so while the batch leaves CUs idle they are spread over up to `split` blocks
 	// (each pays the prologue -- body table, 25 KB of planes into LDS -- again, which is why a large batch keeps one block per frame)
 	const int pts_max = M.pts_bound > 0 ? M.pts_bound : M.pts_cap, passes = ((pts_max + stride - 1) / stride + CH - 1) / CH;
@@ -935,8 +956,9 @@ void ht_launch_cloud_rows(const ht_model_dev &M, const float *state, const float
 #endif
 	if (split > passes) split = passes;
 	if (split < 1) split = 1;
-	hipLaunchKernelGGL(k_cloud_rows, dim3(B, split), dim3(CR_THREADS), ((size_t)M.plane_off[M.nb] + 16) * sizeof(float4), s, M, state, pts, npts, cams, active_flag, stride, use_cam_origin, mode, par.microforce,
-	                   mode == 4 ? sf_ratio : par.physics_weak_force, mode == 4 ? sf_wrist : par.cloudforce_max_point, par.cloudforce_max_sum, par.unibody_force, rows, nrows, rec ? *rec : none, ht_tuning_flags());
+	// `planes`: the frames' boundary-plane rows (k_chamber's) by one more block per frame, behind the cloud-row blocks in dispatch order
+	hipLaunchKernelGGL(k_cloud_rows, dim3(B, split + (planes ? 1 : 0)), dim3(CR_THREADS), ((size_t)M.plane_off[M.nb] + 16) * sizeof(float4), s, M, state, pts, npts, cams, active_flag, stride, use_cam_origin, mode, par.microforce,
+	                   mode == 4 ? sf_ratio : par.physics_weak_force, mode == 4 ? sf_wrist : par.cloudforce_max_point, par.cloudforce_max_sum, par.unibody_force, rows, nrows, rec ? *rec : none, planes ? *planes : no_planes, ht_tuning_flags());
 }
 // the full-reset branch for the frames list[0 .. *nlist) (all B frames with list == nullptr); many_frames: the caller expects more of them than the device has CUs
 // (the two-blocks-per-CU build)

@@ -53,8 +53,10 @@ void ht_launch_solve_prep(const ht_model_dev &M, const ht_physics_dev &ph, const
 
 // where k_cloud_rows puts the solver's records of its rows (ht_quad.hpp): the frames' scratch slots [B][stride][HT_CREC], the rows' bodies [B][pts_cap], the time step
 struct cloud_records { float *scratch; int stride; unsigned char *body; float dt; };
+// the boundary-plane rows a main-thread pass takes from the same launch (k_chamber's rows by extra blocks of k_cloud_rows): planes / on as ht_launch_chamber_planes left them, rows [B][5 * nb][HT_ROW], nch [B]
+struct plane_rows { const float *planes; const int *on; float maxforce; float *rows; int *nch; };
 void ht_launch_cloud_rows(const ht_model_dev &M, const float *state, const float4 *pts, const int *npts, const float *cams, const int *active_flag, int stride, int use_cam_origin, int mode,
-                          const ht_params &par, float *rows, int *nrows, int B, hipStream_t s, float sf_ratio = 0.0f, float sf_wrist = 0.0f, const cloud_records *rec = nullptr);
+                          const ht_params &par, float *rows, int *nrows, int B, hipStream_t s, float sf_ratio = 0.0f, float sf_wrist = 0.0f, const cloud_records *rec = nullptr, const plane_rows *planes = nullptr);
 // What follows a FitError in HandTracker::update and needs nothing but that frame's error rides on the kernel's last thread instead of a launch of its own:
 // mode 1 = the full-reset decision (handtrack.h:706: flags[b] = angles_only || error > threshold), mode 2 = the accept step (handtrack.h:713-731).
 struct ht_fit_after

@@ -157,10 +157,12 @@ static void contact_orders(ht_ctx *ctx, int B, hipStream_t t)
 	}
 	ctx->swork_mask = 0; ctx->swork_B = B;
 }
-static void fork(ht_ctx *ctx, hipStream_t s) { (void)hipEventRecord(ctx->ev_fork, s); for (int i = 0; i < 2; i++) (void)hipStreamWaitEvent(ctx->side[i], ctx->ev_fork, 0); }
-static void fork1(ht_ctx *ctx, hipStream_t s, int i) { (void)hipEventRecord(ctx->ev_fork, s); (void)hipStreamWaitEvent(ctx->side[i], ctx->ev_fork, 0); }
-static void join1(ht_ctx *ctx, hipStream_t s, int i) { (void)hipEventRecord(ctx->ev_join[i], ctx->side[i]); (void)hipStreamWaitEvent(s, ctx->ev_join[i], 0); }
+// (side_open keeps track of the side streams that are out: an update ends by bringing back whichever still is, join_open)
+static void fork(ht_ctx *ctx, hipStream_t s) { (void)hipEventRecord(ctx->ev_fork, s); for (int i = 0; i < 2; i++) (void)hipStreamWaitEvent(ctx->side[i], ctx->ev_fork, 0); ctx->side_open |= 3u; }
+static void fork1(ht_ctx *ctx, hipStream_t s, int i) { (void)hipEventRecord(ctx->ev_fork, s); (void)hipStreamWaitEvent(ctx->side[i], ctx->ev_fork, 0); ctx->side_open |= 1u << i; }
+static void join1(ht_ctx *ctx, hipStream_t s, int i) { (void)hipEventRecord(ctx->ev_join[i], ctx->side[i]); (void)hipStreamWaitEvent(s, ctx->ev_join[i], 0); ctx->side_open &= ~(1u << i); }
 static void join(ht_ctx *ctx, hipStream_t s, int n) { for (int i = 0; i < n; i++) join1(ctx, s, i); }
+static void join_open(ht_ctx *ctx, hipStream_t s) { for (int i = 0; i < 2; i++) if ((ctx->side_open >> i) & 1u) join1(ctx, s, i); }
 
 // Which steps of MultiStepSim to run, where and how much of each: multistep(ctx, B, steps_on(stream).steps(0, 1).frames(ctx->d_flags).in_order().rows_only()).
 // Unless told otherwise: every step of every frame, whole, bracketed for the profile, the cloud rows of a step on side stream 0 beside its contacts.
@@ -209,7 +211,9 @@ static void multistep(ht_ctx *ctx, int B, const steps_on &o)
 		solve_step(ctx, 1, m, B, s, so);
 	}
 }
-// one main-thread pass of HandTracker::update (handtrack.h:769-780)
+// one main-thread pass of HandTracker::update (handtrack.h:769-780).  Its row producers run beside the contact kernel on ONE side stream: a cross-stream edge costs about
+// 10 us and the solve waited for the later of two joins; inside an update the boundary planes' rows are extra blocks of the cloud-row launch (k_cloud_rows: plane_rows), which
+// fill that launch's tail instead of competing with it for the CUs the contact kernel frees.
 static void main_pass(ht_ctx *ctx, int B, hipStream_t s, float *poses_out = nullptr, int pass = -1)      // poses_out: the update's last pass also writes the user poses
 {
 	const ht_params &p = ctx->par;
@@ -220,19 +224,26 @@ static void main_pass(ht_ctx *ctx, int B, hipStream_t s, float *poses_out = null
 	const bool par = !ctx->profile_phases && !no_side;
 	const bool pose_only = solve_tables_mode(ctx) == 2 && par;
 	const bool tables = solve_tables_on(ctx);
-	hipStream_t rows_stream = par ? ctx->side[0] : s, chamber_stream = par ? ctx->side[1] : s;
+	const bool fused = par && !tables && !pose_only && ctx->planes_valid;      // the plane rows ride in the cloud-row launch; otherwise k_chamber makes them (the serial route of the profile, a pass outside an update)
+	hipStream_t rows_stream = par ? ctx->side[0] : s, chamber_stream = pose_only ? ctx->side[1] : rows_stream;      // side stream 1 is a pass's only with the pose-only tables
 	// Round 6: the five boundary planes follow from the points alone, so an update makes them once (beside the net: update_planes) and every pass only their rows (k_chamber,
 	// or k_solve_prep with the solve tables).  A pass outside an update (ht_stage_fit) makes them here.
 	if (!ctx->planes_valid) { ht_prof_scope ps(ctx, "chamber", s, true); ht_launch_chamber_planes(ctx->model, pts, npts, p.min_point_num, p.boundary_planes, ctx->d_chplanes, ctx->d_chon, B, s); }
-	if (par) { if (tables) fork1(ctx, s, 0); else fork(ctx, s); }
+	if (par) { if (pose_only) fork(ctx, s); else fork1(ctx, s, 0); }
 	if (pose_only) solve_prep(ctx, 0, m, true, nullptr, B, ctx->side[1]);      // the pose-only tables ahead of the boundary planes on their side stream: both beside the cloud rows
-	if (!tables) { ht_prof_scope ps(ctx, "chamber", s, true); ht_launch_chamber(ctx->model, ctx->d_state[0], ctx->d_chplanes, ctx->d_chon, 10.0f, ctx->d_chamber, ctx->d_nchamber, B, chamber_stream); }
+	if (!tables && !fused) { ht_prof_scope ps(ctx, "chamber", s, true); ht_launch_chamber(ctx->model, ctx->d_state[0], ctx->d_chplanes, ctx->d_chon, 10.0f, ctx->d_chamber, ctx->d_nchamber, B, chamber_stream); }
 	const cloud_records cr = cloud_rec(ctx);
-	{ ht_prof_scope ps(ctx, "cloud_rows", s, true); ht_launch_cloud_rows(ctx->model, ctx->d_state[0], pts, npts, ctx->d_cams, nullptr, 1, 0, 1, p, ctx->d_rows, ctx->d_nrows, B, rows_stream, 0.0f, 0.0f, rec_or_rows(ctx, &cr)); }
+	const plane_rows pr = { ctx->d_chplanes, ctx->d_chon, 10.0f, ctx->d_chamber, ctx->d_nchamber };
+	{ ht_prof_scope ps(ctx, "cloud_rows", s, true); ht_launch_cloud_rows(ctx->model, ctx->d_state[0], pts, npts, ctx->d_cams, nullptr, 1, 0, 1, p, ctx->d_rows, ctx->d_nrows, B, rows_stream, 0.0f, 0.0f, rec_or_rows(ctx, &cr), fused ? &pr : nullptr); }
 	if (tables) { ht_prof_scope ps(ctx, "solve_prep", s, true); solve_prep(ctx, 0, m, false, nullptr, B, rows_stream); }
 	if (coll) { ht_prof_scope ps(ctx, "contacts", s, true); launch_contacts(ctx, 0, nullptr, B, s, par, pass_slot(pass)); }
 	mark("  pass: contacts done", s);
-	if (par) { mark("  pass: cloud rows done", ctx->side[0]); if (!tables) mark("  pass: chamber done", ctx->side[1]); join(ctx, s, tables ? 1 : 2); }
+	if (par)
+	{
+		mark(fused ? "  pass: cloud + plane rows done" : "  pass: cloud rows done", ctx->side[0]);
+		if (pose_only) { mark("  pass: chamber done", ctx->side[1]); join(ctx, s, 2); } else join1(ctx, s, 0);
+	}
+	mark("  pass: rows joined", s);
 	ht_prof_scope ps(ctx, "solve", s);
 	solve_opts so; so.hist_slot = pass_slot(pass); so.tables = tables || pose_only; so.poses_out = poses_out; so.out_npts = npts;
 	solve_step(ctx, 0, m, B, s, so);
@@ -450,10 +461,10 @@ static int run_update_(ht_ctx *ctx, update_call &u)
 		multistep(ctx, u.B, steps_on(s).all_frames().rows_beside(0));
 	}
 	update_accept(ctx, u);
-	if (u.mode != UPD_FULL) { ht_launch_output(ctx->model, ctx->d_state[1], ctx->d_npts, ctx->d_initializing, p.min_point_num, u.d_poses_out, u.B, s, 1); reset_tail_join(ctx, s); return HT_OK; }      // othermodel.GetPose()
+	if (u.mode != UPD_FULL) { ht_launch_output(ctx->model, ctx->d_state[1], ctx->d_npts, ctx->d_initializing, p.min_point_num, u.d_poses_out, u.B, s, 1); reset_tail_join(ctx, s); join_open(ctx, s); return HT_OK; }      // othermodel.GetPose()
 	mark("accept done", s);
 	update_passes(ctx, u);
-	reset_tail_join(ctx, s); mark("update done", s);
+	reset_tail_join(ctx, s); join_open(ctx, s); mark("update done", s);
 	marks_dump();
 	return HT_OK;
 }

@@ -1,11 +1,14 @@
-# Prints the kernel timeline of the LAST step of a rocprofv3 --kernel-trace CSV of bench.py (one line per kernel: start us, duration us, gap to the
-# previous kernel's end on ANY queue, queue, name) and a summary of the dependent gaps.   usage: python tools/step_timeline.py trace.csv [kernels_per_step]
+# Prints the kernel timeline of one step of a rocprofv3 --kernel-trace CSV of bench.py (one line per kernel: start us, duration us, gap to the
+# previous kernel's end on ANY queue, queue, name) and a summary of the dependent gaps.   usage: python tools/step_timeline.py trace.csv [step]
+# step: which of the trace's steps, counted from 0 (default: the last complete one).  Under `bench.py --full` the last steps are the phase profile's, which
+# takes every kernel in order on ONE queue (37 kernels, k_chamber among them); the timed steps are the ones after the warm-up, on three queues.
 import csv, sys, collections
 rows = list(csv.DictReader(open(sys.argv[1])))
 ev = sorted(((int(r["Start_Timestamp"]), int(r["End_Timestamp"]), r["Queue_Id"], r["Kernel_Name"].split("(")[0][:44]) for r in rows))
 # a step starts with k_prepare
 starts = [i for i, e in enumerate(ev) if e[3].startswith("k_prepare")]
-a, b = starts[-2], starts[-1]
+k = int(sys.argv[2]) if len(sys.argv) > 2 else len(starts) - 2
+a, b = starts[k], starts[k + 1]
 step = ev[a:b]
 t0 = step[0][0]
 busy_end = t0
