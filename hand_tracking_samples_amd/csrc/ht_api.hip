@@ -303,6 +303,78 @@ extern "C" int ht_cnn_train(ht_ctx *ctx, const float *inputs, const float *targe
 	(void)hipFree(d_x); (void)hipFree(d_t); (void)hipFree(d_mse);
 	return rc;
 }
+// Mini-batch steps (ht_train_batch.hip): w' = w - alpha * sum_b g_b(w).  The arguments are checked completely before the arena grows or anything is launched.
+static int cnn_train_batch_check(ht_ctx *ctx, const char *fn, const void *in, const void *tg, int n_pool, const int *order, int n_steps, int batch)
+{
+	const std::string f(fn);
+	if (!ctx->have_weights) { ctx->err = f + ": the context holds no weights of the 64x64-input net (ht_cnn_load_weights); the 128x128-input net is not trained"; return HT_ERR_ARG; }
+	if (batch < 1 || batch > HT_TRAIN_MAX_BATCH) { ctx->err = f + ": batch must be in [1, HT_TRAIN_MAX_BATCH = " + std::to_string(HT_TRAIN_MAX_BATCH) + "]"; return HT_ERR_ARG; }
+	if (!in || !tg) { ctx->err = f + ": inputs and targets must not be NULL"; return HT_ERR_ARG; }
+	if (n_pool < 1) { ctx->err = f + ": n_pool must be positive"; return HT_ERR_ARG; }
+	if (n_steps < 0) { ctx->err = f + ": n_steps must not be negative"; return HT_ERR_ARG; }
+	if (!order && (long long)n_steps * batch > n_pool) { ctx->err = f + ": without an order, n_steps * batch must not exceed n_pool"; return HT_ERR_ARG; }
+	if (order) for (long long k = 0; k < (long long)n_steps * batch; k++) if (order[k] < 0 || order[k] >= n_pool) { ctx->err = f + ": order[" + std::to_string(k) + "] is outside [0, n_pool)"; return HT_ERR_ARG; }
+	return HT_OK;
+}
+// steps of `batch` samples over n_samples indices (order, or 0, 1, ...): the last step takes what is left; then the packed copy of the last layer, once
+static int cnn_train_batch_steps(ht_ctx *ctx, const float *d_x, const float *d_t, const int *order, int n_samples, int batch, float alpha, float *d_mse, hipStream_t s)
+{
+	const int cap = (batch + 31) & ~31;
+	{ const int r = dev_grow(ctx, &ctx->d_train_batch, &ctx->train_batch_cap, (size_t)cap, ht_train_batch_floats(cap) / (size_t)cap + 1); if (r) return r; }
+	int index[HT_TRAIN_MAX_BATCH];
+	for (int k = 0; k < n_samples; k += batch)
+	{
+		const int n = n_samples - k < batch ? n_samples - k : batch;
+		for (int b = 0; b < n; b++) index[b] = order ? order[k + b] : k + b;
+		ht_launch_train_batch_step(ctx->d_weights, ctx->d_weights + HT_CNNB_COUNT, d_x, d_t, index, n, alpha, ctx->d_train_batch, ctx->train_batch_cap, d_mse ? d_mse + k : nullptr, s);
+		ctx->train_batch_last = n;
+	}
+	ht_launch_pack_w4(ctx->cnnw.W4, ctx->d_weights + HT_CNNB_COUNT + 16384, s);      // the forward kernels' copy of the last layer follows the trained weights
+	return HT_OK;
+}
+extern "C" int ht_cnn_train_batch_dev(ht_ctx *ctx, const float *d_inputs, const float *d_targets, int n_pool, const int *order, int n_steps, int batch, float alpha, float *d_mse, void *stream)
+{
+	CHECK_READY(ctx);
+	{ const int r = cnn_train_batch_check(ctx, "ht_cnn_train_batch_dev", d_inputs, d_targets, n_pool, order, n_steps, batch); if (r) return r; }
+	if (n_steps == 0) return HT_OK;
+	hipStream_t s = ht_user_stream(ctx, stream);
+	{ const int r = cnn_train_batch_steps(ctx, d_inputs, d_targets, order, n_steps * batch, batch, alpha, d_mse, s); if (r) return r; }
+	HIPCHK(ctx, hipGetLastError());
+	return HT_OK;
+}
+// the host-array form: an upload, then the same steps on the context's stream
+extern "C" int ht_cnn_train_batch(ht_ctx *ctx, const float *inputs, const float *targets, int n, int batch, float alpha, float *mse_out)
+{
+	CHECK_READY(ctx);
+	{ const int r = cnn_train_batch_check(ctx, "ht_cnn_train_batch", inputs, targets, n, nullptr, 0, batch); if (r) return r; }
+	float *d_x = nullptr, *d_t = nullptr, *d_mse = nullptr;
+	int rc = HT_OK;
+	if (hipMalloc((void **)&d_x, (size_t)n * HT_CNN_IN * sizeof(float)) != hipSuccess || hipMalloc((void **)&d_t, (size_t)n * HT_CNN_OUT * sizeof(float)) != hipSuccess ||
+	    hipMalloc((void **)&d_mse, (size_t)n * sizeof(float)) != hipSuccess) { ctx->err = "ht_cnn_train_batch: out of device memory"; rc = HT_ERR_HIP; }
+	hipStream_t s = ctx->stream;
+	if (rc == HT_OK && (hipMemcpyAsync(d_x, inputs, (size_t)n * HT_CNN_IN * sizeof(float), hipMemcpyHostToDevice, s) != hipSuccess ||
+	                    hipMemcpyAsync(d_t, targets, (size_t)n * HT_CNN_OUT * sizeof(float), hipMemcpyHostToDevice, s) != hipSuccess)) { ctx->err = "ht_cnn_train_batch: upload failed"; rc = HT_ERR_HIP; }
+	if (rc == HT_OK) rc = cnn_train_batch_steps(ctx, d_x, d_t, nullptr, n, batch, alpha, d_mse, s);
+	if (rc == HT_OK && ((mse_out && hipMemcpyAsync(mse_out, d_mse, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, s) != hipSuccess) || hipStreamSynchronize(s) != hipSuccess || hipGetLastError() != hipSuccess))
+	{ ctx->err = "ht_cnn_train_batch: device error"; rc = HT_ERR_HIP; }
+	(void)hipFree(d_x); (void)hipFree(d_t); (void)hipFree(d_mse);
+	return rc;
+}
+// Test aid: the per-sample tensors of the latest mini-batch step (layout: ht_train_batch_views, csrc/ht_train_batch.hip)
+extern "C" int ht_debug_train_batch_buffers(ht_ctx *ctx, int n, float *a3, float *a6, float *a8, float *e9, float *e7, float *e6, float *e3)
+{
+	CHECK_READY(ctx);
+	float *out[7] = { a3, a6, a8, e9, e7, e6, e3 };
+	static const size_t per[7] = { 3600, 2304, 2048, 2304, 2048, 2304, 3600 };
+	for (int i = 0; i < 7; i++) if (!out[i]) { ctx->err = "ht_debug_train_batch_buffers: NULL output"; return HT_ERR_ARG; }
+	if (!ctx->d_train_batch || ctx->train_batch_last < 1) { ctx->err = "ht_debug_train_batch_buffers: no mini-batch step has run"; return HT_ERR_STATE; }
+	if (n != ctx->train_batch_last) { ctx->err = "ht_debug_train_batch_buffers: n must be the latest step's sample count, " + std::to_string(ctx->train_batch_last); return HT_ERR_ARG; }
+	HIPCHK(ctx, ht_sync_all(ctx));
+	const float *view[7];
+	ht_train_batch_views(ctx->d_train_batch, ctx->train_batch_cap, view);
+	for (int i = 0; i < 7; i++) HIPCHK(ctx, hipMemcpy(out[i], view[i], (size_t)n * per[i] * sizeof(float), hipMemcpyDeviceToHost));
+	return HT_OK;
+}
 extern "C" int ht_cnn_get_weights(ht_ctx *ctx, float *w, size_t n)
 {
 	CHECK_READY(ctx);

@@ -874,3 +874,10 @@ void ht_launch_cnn_input(const uint16_t *depth, const float *cams, int npx, floa
 {
 	hipLaunchKernelGGL(k_cnn_input, dim3((npx / 8 + 255) / 256, B), dim3(256), 0, s, depth, cams, npx, drangey, cnn_in);
 }
+// k_fc on row-major weights for any M (the mini-batch training step, ht_train_batch.hip): C[M][N] = bias + A[M][K] W[K][N] (+ tanh), N a multiple of 64, K of 32
+void ht_launch_fc_rowmajor(const float *A, const float *W, const float *bias, float *C, int M, int N, int K, bool tanh, hipStream_t s)
+{
+	const dim3 g(N / 64, (M + 63) / 64), t(256);
+	if (tanh) hipLaunchKernelGGL((k_fc<true, 2, 2, false>), g, t, 0, s, A, W, bias, C, M, N, K);
+	else hipLaunchKernelGGL((k_fc<false, 2, 2, false>), g, t, 0, s, A, W, bias, C, M, N, K);
+}

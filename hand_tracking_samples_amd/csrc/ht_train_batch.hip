@@ -1,0 +1,384 @@
+// ht_train_batch.hip -- one SGD step of the pose-initialiser CNN on a mini-batch: w' = w - alpha * sum_b g_b(w), every sample's gradient taken at
+// the same weights.  g_b is what CNN::Train (third_party/cnn.h:558-580) subtracts for sample b, divided by alpha; the per-sample
+// arithmetic is that of ht_train.hip, whose kernels and launches stay as they are.
+//
+// With n samples in a step the two fully connected layers are dense products, three per layer, on v_mfma_f32_32x32x2_f32:
+//   forward        Y[b,j] = B[j] + sum_i X[b,i] W[i,j]            k_fc (ht_cnn.hip) on the row-major weights
+//   backward-data  D[b,i] = sum_j E[b,j] W[i,j]  (old weights)     k_tb_fc_back: both operands contiguous along j, (1 - y^2) folded into the store
+//   weight step    W[i,j] -= alpha * sum_b X[b,i] E[b,j]            k_tb_fc_wgrad: the batch is the summed index, the tile is applied in one read-modify-write
+// so a matrix is read twice and rewritten once per step, not per sample.  A step is 13 launches:
+//   sample indices | conv1+tanh+pool+pool | conv2+tanh+pool | FC1 | FC2 | softmax, loss, softmax' | FC2 back | FC2 step | FC1 back | FC1 step |
+//   conv2 back | conv1/conv2 gradient partial sums over groups of four samples | their sum in group order, applied to W1 B1 W2 B2 and the packed W2p
+// The convolutions keep, per pooling window, the pooled value and which entry won (the first maximum, cnn.h:150-160) instead of the unpooled maps:
+// that is all the backward pass reads of them (tanh' = 1 - m^2 at the maximum m, the error goes to that entry alone).
+// Every sum has a fixed order and there are no floating-point atomics: the same call on the same weights gives the same bits.
+#include "ht_device.hpp"
+#include "ht_launch.hpp"
+
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+#define TB_GS 4                                  // samples per partial sum of the convolutions' gradients
+#define TB_MAXG (HT_TRAIN_MAX_BATCH / TB_GS)
+#define TB_PW (16384 + 64 + 16 * 26)             // floats of one partial sum: W2, B2, then 16 x (25 taps of W1 + B1)
+struct tb_index { int v[HT_TRAIN_MAX_BATCH]; };
+
+__device__ __forceinline__ float tb_tanh(float t) { float e = (float)exp((double)(2 * t)); return (e - 1) / (e + 1); }      // TanH::f cnn.h:31
+// first maximum of a 2x2 window in the reference's scan order (x then y, strict >: cnn.h:150-160)
+__device__ __forceinline__ int tb_first_max4(float a, float b, float c, float d, float &m)
+{
+	int k = 0; m = a;
+	if (b > m) { m = b; k = 1; }
+	if (c > m) { m = c; k = 2; }
+	if (d > m) { m = d; k = 3; }
+	return k;
+}
+__device__ __forceinline__ float tb_wave_sum(float v) { for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o); return v; }
+__device__ __forceinline__ float tb_seg16_sum(float v) { for (int o = 8; o >= 1; o >>= 1) v += __shfl_xor(v, o); return v; }
+
+// the step's sample indices, handed over as a kernel argument (no host memory has to outlive the call)
+__global__ __launch_bounds__(256) void k_tb_set_index(tb_index ix, int n, int *__restrict__ idx)
+{
+	if ((int)threadIdx.x < n) idx[threadIdx.x] = ix.v[threadIdx.x];
+}
+// conv1 (5x5, 1 -> 16 channels, 64x64 -> 60x60) + tanh + the two max-pools (-> 15x15), k_t_conv1_tanh_pool per sample (blockIdx.z).  Of the 60x60 map
+// only the pooled value a3 and r1 = the input position (y * 64 + x) of the conv output that won both pools are kept.
+__global__ __launch_bounds__(256) void k_tb_conv1_tanh_pool(const float *__restrict__ pool, const int *__restrict__ idx, const float *__restrict__ W, const float *__restrict__ B, float *__restrict__ a3, int *__restrict__ r1)
+{
+	__shared__ float s_o[4][60];
+	const int py = blockIdx.x, oz = blockIdx.y, b = blockIdx.z, t = threadIdx.x;
+	const float *in = pool + (size_t)idx[b] * HT_CNN_IN;
+	if (t < 240)
+	{
+		const int r = t / 60, x = t % 60, y = 4 * py + r;
+		float acc = B[oz];
+#pragma unroll
+		for (int ky = 0; ky < 5; ky++)
+#pragma unroll
+			for (int kx = 0; kx < 5; kx++) acc += in[(y + ky) * 64 + x + kx] * W[kx + 5 * (ky + 5 * oz)];
+		s_o[r][x] = tb_tanh(acc);
+	}
+	__syncthreads();
+	if (t < 15)
+	{
+		float q[4], m;
+#pragma unroll
+		for (int k = 0; k < 4; k++) { const int r = 2 * (k >> 1), c = 4 * t + 2 * (k & 1); float mk; tb_first_max4(s_o[r][c], s_o[r][c + 1], s_o[r + 1][c], s_o[r + 1][c + 1], mk); q[k] = mk; }
+		const int k2 = tb_first_max4(q[0], q[1], q[2], q[3], m);
+		const int r = 2 * (k2 >> 1), c = 4 * t + 2 * (k2 & 1);
+		const int k1 = tb_first_max4(s_o[r][c], s_o[r][c + 1], s_o[r + 1][c], s_o[r + 1][c + 1], m);
+		const size_t o = (size_t)b * 3600 + oz * 225 + py * 15 + t;
+		a3[o] = m; r1[o] = (4 * py + r + (k1 >> 1)) * 64 + c + (k1 & 1);
+	}
+}
+// conv2 (4x4, 16 -> 64 channels, 15x15 -> 12x12) + tanh + max-pool (-> 6x6), k_t_conv2_tanh_pool per sample (blockIdx.y); a6 = the pooled value,
+// r3 = which of the window's four entries (x fastest) is its first maximum
+__global__ __launch_bounds__(192) void k_tb_conv2_tanh_pool(const float *__restrict__ a3, const float *__restrict__ W, const float *__restrict__ B, float *__restrict__ a6, int *__restrict__ r3)
+{
+	__shared__ float s_in[3600], s_w[256], s_o[144];
+	const int oz = blockIdx.x, b = blockIdx.y, t = threadIdx.x;
+	for (int i = t; i < 3600; i += 192) s_in[i] = a3[(size_t)b * 3600 + i];
+	for (int i = t; i < 256; i += 192) s_w[i] = W[oz * 256 + i];
+	__syncthreads();
+	if (t < 144)
+	{
+		const int x = t % 12, y = t / 12;
+		float acc = B[oz];
+		for (int ky = 0; ky < 4; ky++) for (int kx = 0; kx < 4; kx++)
+#pragma unroll
+			for (int iz = 0; iz < 16; iz++) acc += s_in[iz * 225 + (y + ky) * 15 + x + kx] * s_w[kx + 4 * (ky + 4 * iz)];
+		s_o[t] = tb_tanh(acc);
+	}
+	__syncthreads();
+	if (t < 36)
+	{
+		const float *p = s_o + (2 * (t / 6)) * 12 + 2 * (t % 6);
+		float m;
+		const int k = tb_first_max4(p[0], p[1], p[12], p[13], m);
+		a6[(size_t)b * 2304 + oz * 36 + t] = m; r3[(size_t)b * 2304 + oz * 36 + t] = k;
+	}
+}
+// Output layer of sample b = blockIdx.x from its logits: chunked softmax (cnn.h:497-511), E = y - t, softmax backward (cnn.h:512-526) and the loss
+// sum E^2 / 2304.  Thread t owns element t of each 256-wide chunk and element t of the 256 that form the sixteen 16-wide chunks.
+__global__ __launch_bounds__(256) void k_tb_softmax_loss(const float *__restrict__ logits, const float *__restrict__ targets, const int *__restrict__ idx, float *__restrict__ e9, float *__restrict__ mse)
+{
+	__shared__ float red[2][8][4], rsq[4];
+	const int b = blockIdx.x, t = threadIdx.x, w = t >> 6, lane = t & 63;
+	const float *lg = logits + (size_t)b * HT_CNN_OUT, *tg = targets + (size_t)idx[b] * HT_CNN_OUT;
+	float v[9], cs[9];
+#pragma unroll
+	for (int c = 0; c < 9; c++)
+	{
+		v[c] = (float)exp((double)lg[c * 256 + t]);
+		cs[c] = c < 8 ? tb_wave_sum(v[c]) : tb_seg16_sum(v[c]);
+		if (c < 8 && lane == 0) red[0][c][w] = cs[c];
+	}
+	__syncthreads();
+	float y[9], d[9], cd[9], sq = 0.0f;
+#pragma unroll
+	for (int c = 0; c < 9; c++)
+	{
+		if (c < 8) cs[c] = ((red[0][c][0] + red[0][c][1]) + red[0][c][2]) + red[0][c][3];
+		y[c] = v[c] / cs[c]; d[c] = y[c] - tg[c * 256 + t];
+		cd[c] = c < 8 ? tb_wave_sum(d[c] * y[c]) : tb_seg16_sum(d[c] * y[c]);
+		if (c < 8 && lane == 0) red[1][c][w] = cd[c];
+		sq += d[c] * d[c];
+	}
+	sq = tb_wave_sum(sq);
+	if (lane == 0) rsq[w] = sq;
+	__syncthreads();
+#pragma unroll
+	for (int c = 0; c < 9; c++)
+	{
+		if (c < 8) cd[c] = ((red[1][c][0] + red[1][c][1]) + red[1][c][2]) + red[1][c][3];
+		e9[(size_t)b * HT_CNN_OUT + c * 256 + t] = y[c] * (d[c] - cd[c]);
+	}
+	if (t == 0) mse[b] = (((rsq[0] + rsq[1]) + rsq[2]) + rsq[3]) / (float)HT_CNN_OUT;
+}
+// Backward-data of a fully connected layer for the whole step: D[b,i] = sum_j E[b,j] W[i,j] with W [R][K] row-major (R rows i, K columns j), times
+// (1 - Y[b,i]^2) when FOLD (the tanh under the layer).  Block = 32 rows of W x all samples, 8 waves; wave w sums the columns [w K/8, (w+1) K/8) into
+// NB 32x32 accumulator tiles (sample tile x row tile), so W is read once.  Both operands are contiguous along the summed index: a lane (r = lane & 31,
+// h = lane >> 5) reads the four columns j0 + 8 s + 4 h + c of its row with one 128-bit load and component c feeds matrix instruction c, whose two
+// k-slots are therefore columns (j0 + 8 s + c, j0 + 8 s + 4 + c) for A (= E) and B (= W^T) alike.  The eight waves' tiles are added in wave order through
+// LDS.  C/D map of 32x32: column (here i) = lane & 31, row (here b) = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5).
+template <int NB, bool FOLD> __global__ __launch_bounds__(512) void k_tb_fc_back(const float *__restrict__ E, const float *__restrict__ W, const float *__restrict__ Y, float *__restrict__ D, int n, int R, int K)
+{
+	__shared__ float red[8][1024];
+	const int t = threadIdx.x, w = t >> 6, lane = t & 63, r = lane & 31, h = lane >> 5;
+	const int i0 = blockIdx.x * 32, kc = K / 8, j0 = w * kc + 4 * h;
+	const float *wp = W + (size_t)(i0 + r) * K + j0;
+	const float *ep[NB]; bool on[NB];
+	f32x16 acc[NB];
+#pragma unroll
+	for (int q = 0; q < NB; q++)
+	{
+		on[q] = 32 * q + r < n;
+		ep[q] = E + (size_t)(on[q] ? 32 * q + r : 0) * K + j0;
+#pragma unroll
+		for (int g = 0; g < 16; g++) acc[q][g] = 0.0f;
+	}
+#pragma unroll 2
+	for (int s = 0; s < kc; s += 8)
+	{
+		const float4 wv = *reinterpret_cast<const float4 *>(wp + s);
+#pragma unroll
+		for (int q = 0; q < NB; q++)
+		{
+			float4 ev = *reinterpret_cast<const float4 *>(ep[q] + s);
+			if (!on[q]) ev = make_float4(0, 0, 0, 0);
+			acc[q] = __builtin_amdgcn_mfma_f32_32x32x2f32(ev.x, wv.x, acc[q], 0, 0, 0);
+			acc[q] = __builtin_amdgcn_mfma_f32_32x32x2f32(ev.y, wv.y, acc[q], 0, 0, 0);
+			acc[q] = __builtin_amdgcn_mfma_f32_32x32x2f32(ev.z, wv.z, acc[q], 0, 0, 0);
+			acc[q] = __builtin_amdgcn_mfma_f32_32x32x2f32(ev.w, wv.w, acc[q], 0, 0, 0);
+		}
+	}
+#pragma unroll
+	for (int q = 0; q < NB; q++)
+	{
+		if (q) __syncthreads();
+#pragma unroll
+		for (int g = 0; g < 16; g++) red[w][g * 64 + lane] = acc[q][g];
+		__syncthreads();
+#pragma unroll
+		for (int u = 0; u < 2; u++)
+		{
+			const int e = t + 512 * u, g = e >> 6, ln = e & 63;
+			float v = red[0][e];
+#pragma unroll
+			for (int k = 1; k < 8; k++) v += red[k][e];
+			const int b = 32 * q + (g & 3) + 8 * (g >> 2) + 4 * (ln >> 5);
+			const size_t o = (size_t)b * R + i0 + (ln & 31);
+			if (b < n) { if (FOLD) { const float y = Y[o]; v = (1.0f - y * y) * v; } D[o] = v; }
+		}
+	}
+}
+// Weight gradient and step of a fully connected layer: W[i,j] -= alpha * sum_b X[b,i] E[b,j], W [M][N] row-major.  The summed index is the sample:
+// lanes 0..31 hold sample 2 s, lanes 32..63 sample 2 s + 1 (zero beyond n), as 32 consecutive floats of X (A operand, i) and of E (B operand, j).
+// A wave owns one 32x32 tile of W, read before the products and rewritten once after them; a block is four tiles side by side, 4608 tiles per
+// matrix.  The blocks of the first tile row also step the bias, B[j] -= alpha * sum_b E[b,j], samples ascending.
+__global__ __launch_bounds__(256) void k_tb_fc_wgrad(float *__restrict__ W, float *__restrict__ B, const float *__restrict__ X, const float *__restrict__ E, int n, int M, int N, float alpha)
+{
+	const int w = threadIdx.x >> 6, lane = threadIdx.x & 63, r = lane & 31, h = lane >> 5;
+	const int i0 = blockIdx.y * 32, j0 = blockIdx.x * 128 + 32 * w;
+	float *wp = W + (size_t)(i0 + 4 * h) * N + j0 + r;
+	float wv[16];
+#pragma unroll
+	for (int g = 0; g < 16; g++) wv[g] = wp[(size_t)((g & 3) + 8 * (g >> 2)) * N];
+	f32x16 acc;
+#pragma unroll
+	for (int g = 0; g < 16; g++) acc[g] = 0.0f;
+	const float *xp = X + i0 + r, *ep = E + j0 + r;
+#pragma unroll 4
+	for (int s = 0; s < n; s += 2)
+	{
+		const int b = s + h;
+		const bool on = b < n;
+		float xv = xp[(size_t)(on ? b : 0) * M], ev = ep[(size_t)(on ? b : 0) * N];
+		if (!on) { xv = 0.0f; ev = 0.0f; }
+		acc = __builtin_amdgcn_mfma_f32_32x32x2f32(xv, ev, acc, 0, 0, 0);
+	}
+#pragma unroll
+	for (int g = 0; g < 16; g++) wp[(size_t)((g & 3) + 8 * (g >> 2)) * N] = wv[g] - alpha * acc[g];
+	if (blockIdx.y == 0 && lane < 32)
+	{
+		float sum = 0.0f;
+		for (int b = 0; b < n; b++) sum += ep[(size_t)b * N];
+		B[j0 + r] -= alpha * sum;
+	}
+}
+// LConv::backward of conv2 as a gather (cnn.h:236-250) for input channel iz = blockIdx.x of sample b = blockIdx.y: the 64 error maps are rebuilt in LDS
+// from the pooled error (pool backward to the first maximum, then conv2's tanh'), a thread owns one input position and walks output channel, y, x ascending
+__global__ __launch_bounds__(256) void k_tb_conv2_back(const float *__restrict__ a6, const int *__restrict__ r3, const float *__restrict__ e6, const float *__restrict__ W, float *__restrict__ e3)
+{
+	__shared__ float s_e[64 * 144], s_w[64 * 16];
+	const int iz = blockIdx.x, b = blockIdx.y, t = threadIdx.x;
+	for (int i = t; i < 2304; i += 256)
+	{
+		const int oz = i / 36, p = i % 36, base = oz * 144 + (2 * (p / 6)) * 12 + 2 * (p % 6);
+		const size_t o = (size_t)b * 2304 + i;
+		const float m = a6[o], d = (1.0f - m * m) * e6[o];
+		const int k = r3[o];
+		s_e[base] = k == 0 ? d : 0.0f; s_e[base + 1] = k == 1 ? d : 0.0f; s_e[base + 12] = k == 2 ? d : 0.0f; s_e[base + 13] = k == 3 ? d : 0.0f;
+	}
+	for (int i = t; i < 1024; i += 256) s_w[i] = W[(i & 15) + 16 * (iz + 16 * (i >> 4))];
+	__syncthreads();
+	if (t >= 225) return;
+	const int x = t % 15, y = t / 15;
+	const int oy0 = max(0, y - 3), oy1 = min(11, y), ox0 = max(0, x - 3), ox1 = min(11, x);
+	float acc = 0.0f;
+	for (int oz = 0; oz < 64; oz++) for (int oy = oy0; oy <= oy1; oy++) for (int ox = ox0; ox <= ox1; ox++)
+		acc += s_w[oz * 16 + (x - ox) + 4 * (y - oy)] * s_e[oz * 144 + oy * 12 + ox];
+	e3[(size_t)b * 3600 + iz * 225 + t] = acc;
+}
+// LConv::update (cnn.h:252-279) of both convolutions, summed over the TB_GS samples of group blockIdx.y into pw[group][TB_PW] (times -alpha).  Only one
+// entry per pooling window carries an error, so both sums run over (position, value) lists, as k_t_conv_update's conv1 branch does.
+// blocks 0..15: conv2, output channels 4 x .. 4 x + 3: a thread per tap (iz, ky, kx), 36 windows per channel.
+// blocks 16..31: conv1, output channel x - 16: eight lanes per tap share the 225 windows; tap 25 is the bias.
+__global__ __launch_bounds__(256) void k_tb_conv_grad(const float *__restrict__ pool, const int *__restrict__ idx, const float *__restrict__ a3, const int *__restrict__ r1, const float *__restrict__ a6, const int *__restrict__ r3,
+                                                      const float *__restrict__ e6, const float *__restrict__ e3, int n, float alpha, float *__restrict__ pw)
+{
+	__shared__ float s_x[4096], s_e[256];
+	__shared__ int s_i[256];
+	const int t = threadIdx.x, b0 = blockIdx.y * TB_GS, b1 = min(n, b0 + TB_GS);
+	float *out = pw + (size_t)blockIdx.y * TB_PW;
+	if (blockIdx.x < 16)
+	{
+		const int g = blockIdx.x, kx = t & 3, ky = (t >> 2) & 3, iz = t >> 4;
+		float acc[4] = { 0.0f, 0.0f, 0.0f, 0.0f }, bias = 0.0f;
+		for (int b = b0; b < b1; b++)
+		{
+			__syncthreads();
+			for (int i = t; i < 3600; i += 256) s_x[i] = a3[(size_t)b * 3600 + i];
+			if (t < 144)
+			{
+				const int p = t % 36, k = r3[(size_t)b * 2304 + g * 144 + t];
+				const float m = a6[(size_t)b * 2304 + g * 144 + t];
+				s_i[t] = (2 * (p / 6) + (k >> 1)) * 15 + 2 * (p % 6) + (k & 1);
+				s_e[t] = -alpha * ((1.0f - m * m) * e6[(size_t)b * 2304 + g * 144 + t]);
+			}
+			__syncthreads();
+			const float *xp = s_x + iz * 225 + ky * 15 + kx;
+#pragma unroll
+			for (int oz = 0; oz < 4; oz++)
+#pragma unroll 4
+				for (int p = 0; p < 36; p++) acc[oz] += xp[s_i[oz * 36 + p]] * s_e[oz * 36 + p];
+			if (t < 4) for (int p = 0; p < 36; p++) bias += s_e[t * 36 + p];
+		}
+#pragma unroll
+		for (int oz = 0; oz < 4; oz++) out[(4 * g + oz) * 256 + t] = acc[oz];
+		if (t < 4) out[16384 + 4 * g + t] = bias;
+	}
+	else
+	{
+		const int oz = blockIdx.x - 16, tap = t >> 3, sub = t & 7;      // taps 0..24, tap 25 = bias, 26..31 idle
+		const int off = tap < 25 ? (tap / 5) * 64 + tap % 5 : 0;
+		float acc = 0.0f;
+		for (int b = b0; b < b1; b++)
+		{
+			__syncthreads();
+			const float *x0 = pool + (size_t)idx[b] * HT_CNN_IN;
+			for (int i = t; i < 4096; i += 256) s_x[i] = x0[i];
+			if (t < 225)
+			{
+				const size_t o = (size_t)b * 3600 + oz * 225 + t;
+				const float m = a3[o];
+				s_i[t] = r1[o];
+				s_e[t] = -alpha * ((1.0f - m * m) * e3[o]);
+			}
+			__syncthreads();
+			if (tap < 25) for (int p = sub; p < 225; p += 8) acc += s_x[s_i[p] + off] * s_e[p];
+			else if (tap == 25) for (int p = sub; p < 225; p += 8) acc += s_e[p];
+		}
+		for (int o = 4; o >= 1; o >>= 1) acc += __shfl_xor(acc, o);
+		if (sub == 0 && tap < 26) out[16448 + oz * 26 + tap] = acc;
+	}
+}
+// the groups' partial sums added in group order and applied: W2 (with the MFMA-packed copy W2p[(ky*4+kx)*16 + ic][oc] k_conv2 reads), B2, W1, B1
+__global__ __launch_bounds__(256) void k_tb_conv_apply(const float *__restrict__ pw, int groups, float *__restrict__ W1, float *__restrict__ B1, float *__restrict__ W2, float *__restrict__ B2, float *__restrict__ W2p)
+{
+	const int e = blockIdx.x * 256 + threadIdx.x;
+	if (e >= TB_PW) return;
+	float sum = 0.0f;
+	for (int g = 0; g < groups; g++) sum += pw[(size_t)g * TB_PW + e];
+	if (e < 16384)
+	{
+		const int oz = e >> 8, t = e & 255, kx = t & 3, ky = (t >> 2) & 3, iz = t >> 4;
+		const float w = W2[e] + sum;
+		W2[e] = w; W2p[(size_t)((ky * 4 + kx) * 16 + iz) * 64 + oz] = w;
+	}
+	else if (e < 16448) B2[e - 16384] += sum;
+	else
+	{
+		const int q = e - 16448, oz = q / 26, tap = q % 26;
+		if (tap < 25) W1[oz * 25 + tap] += sum; else B1[oz] += sum;
+	}
+}
+
+// The arena of a step of up to cap samples (cap a multiple of 32): per-sample tensors [cap][...], then the partial sums, the indices and a sink for the losses
+struct tb_arena { float *a3, *a6, *a8, *lg, *e9, *e7, *e6, *e3, *pw, *sink; int *r1, *r3, *idx; };
+static tb_arena tb_layout(float *p, size_t cap)
+{
+	tb_arena A;
+	A.a3 = p; p += cap * 3600; A.r1 = (int *)p; p += cap * 3600; A.a6 = p; p += cap * 2304; A.r3 = (int *)p; p += cap * 2304; A.a8 = p; p += cap * 2048;
+	A.lg = p; p += cap * 2304; A.e9 = p; p += cap * 2304; A.e7 = p; p += cap * 2048; A.e6 = p; p += cap * 2304; A.e3 = p; p += cap * 3600;
+	A.pw = p; p += (size_t)TB_MAXG * TB_PW; A.sink = p; p += HT_TRAIN_MAX_BATCH; A.idx = (int *)p;
+	return A;
+}
+size_t ht_train_batch_floats(int cap) { return (size_t)cap * (3 * 3600 + 5 * 2304 + 2 * 2048) + (size_t)TB_MAXG * TB_PW + 2 * HT_TRAIN_MAX_BATCH; }
+// the per-sample tensors ht_debug_train_batch_buffers returns, in its order: a3 a6 a8 e9 e7 e6 e3
+void ht_train_batch_views(float *arena, int cap, const float *view[7])
+{
+	const tb_arena A = tb_layout(arena, (size_t)cap);
+	view[0] = A.a3; view[1] = A.a6; view[2] = A.a8; view[3] = A.e9; view[4] = A.e7; view[5] = A.e6; view[6] = A.e3;
+}
+template <bool FOLD> static void tb_fc_back(const float *E, const float *W, const float *Y, float *D, int n, int R, int K, hipStream_t s)
+{
+	const dim3 g(R / 32), t(512);
+	if (n <= 32) hipLaunchKernelGGL((k_tb_fc_back<1, FOLD>), g, t, 0, s, E, W, Y, D, n, R, K);
+	else if (n <= 64) hipLaunchKernelGGL((k_tb_fc_back<2, FOLD>), g, t, 0, s, E, W, Y, D, n, R, K);
+	else if (n <= 128) hipLaunchKernelGGL((k_tb_fc_back<4, FOLD>), g, t, 0, s, E, W, Y, D, n, R, K);
+	else hipLaunchKernelGGL((k_tb_fc_back<8, FOLD>), g, t, 0, s, E, W, Y, D, n, R, K);
+}
+// One step on samples index[0..n) of the pools; mse_out[n] or null.  The packed copy of the last layer is NOT refreshed here (once per call: ht_api.hip).
+void ht_launch_train_batch_step(float *w, float *W2p, const float *inputs, const float *targets, const int *index, int n, float alpha, float *arena, int cap, float *mse_out, hipStream_t s)
+{
+	const tb_arena A = tb_layout(arena, (size_t)cap);
+	float *W1 = w, *B1 = W1 + 400, *W2 = B1 + 16, *B2 = W2 + 16384, *W3 = B2 + 64, *B3 = W3 + (size_t)2304 * 2048, *W4 = B3 + 2048, *B4 = W4 + (size_t)2048 * 2304;
+	tb_index ix;
+	for (int b = 0; b < n; b++) ix.v[b] = index[b];
+	for (int b = n; b < HT_TRAIN_MAX_BATCH; b++) ix.v[b] = 0;
+	const int groups = (n + TB_GS - 1) / TB_GS;
+	hipLaunchKernelGGL(k_tb_set_index, dim3(1), dim3(256), 0, s, ix, n, A.idx);
+	// forward
+	hipLaunchKernelGGL(k_tb_conv1_tanh_pool, dim3(15, 16, n), dim3(256), 0, s, inputs, A.idx, W1, B1, A.a3, A.r1);
+	hipLaunchKernelGGL(k_tb_conv2_tanh_pool, dim3(64, n), dim3(192), 0, s, A.a3, W2, B2, A.a6, A.r3);
+	ht_launch_fc_rowmajor(A.a6, W3, B3, A.a8, n, 2048, 2304, true, s);
+	ht_launch_fc_rowmajor(A.a8, W4, B4, A.lg, n, 2304, 2048, false, s);
+	hipLaunchKernelGGL(k_tb_softmax_loss, dim3(n), dim3(256), 0, s, A.lg, targets, A.idx, A.e9, mse_out ? mse_out : A.sink);
+	// backward with the old weights, then each layer's step
+	tb_fc_back<true>(A.e9, W4, A.a8, A.e7, n, 2048, 2304, s);
+	hipLaunchKernelGGL(k_tb_fc_wgrad, dim3(2304 / 128, 2048 / 32), dim3(256), 0, s, W4, B4, A.a8, A.e9, n, 2048, 2304, alpha);
+	tb_fc_back<false>(A.e7, W3, nullptr, A.e6, n, 2304, 2048, s);
+	hipLaunchKernelGGL(k_tb_fc_wgrad, dim3(2048 / 128, 2304 / 32), dim3(256), 0, s, W3, B3, A.a6, A.e7, n, 2304, 2048, alpha);
+	hipLaunchKernelGGL(k_tb_conv2_back, dim3(16, n), dim3(256), 0, s, A.a6, A.r3, A.e6, W2, A.e3);
+	hipLaunchKernelGGL(k_tb_conv_grad, dim3(32, groups), dim3(256), 0, s, inputs, A.idx, A.a3, A.r1, A.a6, A.r3, A.e6, A.e3, n, alpha, A.pw);
+	hipLaunchKernelGGL(k_tb_conv_apply, dim3((TB_PW + 255) / 256), dim3(256), 0, s, A.pw, groups, W1, B1, W2, B2, W2p);
+}

@@ -23,7 +23,7 @@ TRAIN_ERR = (("e9", 2304, (2304,)), ("e7", 2048, (2048,)), ("e6", 2304, (2304,))
 SYMBOLS = (
     "ht_create", "ht_destroy", "ht_model_bake", "ht_last_error", "ht_get_params", "ht_set_params", "ht_model_info", "ht_config_read", "ht_scale",
     "ht_cnn_load_weights", "ht_cnn_eval", "ht_cnn_eval_dev", "ht_cnn_load_weights_sized", "ht_cnn_eval_sized", "ht_cnn_eval_sized_dev", "ht_cnn_train", "ht_cnn_get_weights", "ht_expected_cnn", "ht_expected_cnn_full",
-    "ht_expected_cnn_batch", "ht_expected_cnn_dev", "ht_cnn_input_dev", "ht_cnn_train_dev",
+    "ht_expected_cnn_batch", "ht_expected_cnn_dev", "ht_cnn_input_dev", "ht_cnn_train_dev", "ht_cnn_train_batch_dev", "ht_cnn_train_batch", "ht_debug_train_batch_buffers",
     "ht_model_open", "ht_model_close", "ht_model_error", "ht_model_counts", "ht_model_body", "ht_model_body_mesh", "ht_model_body_sdmesh", "ht_model_hitcheck", "ht_model_hitcheck_mesh", "ht_model_render_mesh", "ht_model_scale", "ht_render_mesh_depth", "ht_render_mesh_depth_dev",
     "ht_tracker_reset", "ht_get_state", "ht_set_state", "ht_get_tracker_flags", "ht_set_tracker_flags", "ht_update_sync", "ht_update_dev", "ht_update_frames_sync", "ht_update_frames_dev", "ht_update_direct_sync", "ht_update_direct_dev", "ht_update_cnn_model_sync", "ht_get_cnn_results", "ht_get_cnn_layers", "ht_frames_overflow", "ht_reserve_points", "ht_point_capacity", "ht_capacity_events", "ht_segment_vr", "ht_segment_vr_dev", "ht_render_depth", "ht_render_depth_dev", "ht_slowfit", "ht_set_points", "ht_fit_rows", "ht_physics_update",
     "ht_stage_prepare", "ht_stage_decode", "ht_stage_fit_error", "ht_stage_cloud_rows", "ht_stage_contacts", "ht_stage_fit",
@@ -111,6 +111,9 @@ def load(build_if_missing=True):
     L.ht_expected_cnn_dev.argtypes = [vp, vp, vp, C.c_int, C.c_int, vp, vp, vp, vp]
     L.ht_cnn_input_dev.argtypes = [vp, vp, vp, C.c_int, vp, vp]
     L.ht_cnn_train_dev.argtypes = [vp, vp, vp, C.c_int, ip, C.c_int, C.c_float, vp, vp]
+    L.ht_cnn_train_batch_dev.argtypes = [vp, vp, vp, C.c_int, ip, C.c_int, C.c_int, C.c_float, vp, vp]
+    L.ht_cnn_train_batch.argtypes = [vp, fp, fp, C.c_int, C.c_int, C.c_float, fp]
+    L.ht_debug_train_batch_buffers.argtypes = [vp, C.c_int] + [fp] * 7
     L.ht_set_points.argtypes = [vp, C.c_int, fp, C.c_int, ip]
     L.ht_slowfit.argtypes = [vp, C.c_int, C.c_int, fp, C.c_int, C.c_int, fp, fp, fp, C.c_int]
     L.ht_get_cnn_layers.argtypes = [vp, C.c_int, C.c_int, fp, fp, fp, fp]
@@ -581,6 +584,33 @@ class Context:
         if o is not None and len(o) < n:
             raise ValueError("order holds fewer than n_steps indices")
         self._chk(self.L.ht_cnn_train_dev(self.h, d_inputs, d_targets, int(n_pool), None if o is None else _i(o), n, float(alpha), d_mse, stream))
+
+    def cnn_train_batch(self, inputs, targets, batch, alpha=0.001):
+        """ht_cnn_train_batch: mini-batch steps w' = w - alpha * SUM_b g_b(w) (a sum, not a mean) over the samples in order, `batch` per step (the
+        remainder forms a last, smaller step); returns the per-sample losses at their step's weights."""
+        x = _c(inputs, np.float32).reshape(-1, CNN_IN); t = _c(targets, np.float32).reshape(-1, CNN_OUT)
+        mse = np.zeros(x.shape[0], np.float32)
+        self._chk(self.L.ht_cnn_train_batch(self.h, _f(x), _f(t), x.shape[0], int(batch), float(alpha), _f(mse)))
+        return mse
+
+    def cnn_train_batch_dev(self, d_inputs, d_targets, n_pool, batch, order=None, n_steps=None, alpha=0.001, d_mse=None, stream=None):
+        """ht_cnn_train_batch_dev: mini-batch steps on device pools; step k trains on samples order[k*batch:(k+1)*batch] (a host array, checked before
+        anything runs), or k*batch + b without an order.  d_mse [n_steps*batch] optional.  Asynchronous on `stream`."""
+        o = None if order is None else np.ascontiguousarray(order, np.int32).reshape(-1)
+        batch = int(batch)
+        n = ((len(o) if o is not None else int(n_pool)) // max(batch, 1)) if n_steps is None else int(n_steps)
+        if o is not None and len(o) < n * batch:
+            raise ValueError("order holds fewer than n_steps * batch indices")
+        self._chk(self.L.ht_cnn_train_batch_dev(self.h, d_inputs, d_targets, int(n_pool), None if o is None else _i(o), n, batch, float(alpha), d_mse, stream))
+
+    def cnn_train_batch_buffers(self, n):
+        """ht_debug_train_batch_buffers: the per-sample tensors of the latest mini-batch step (n = its sample count): a3 [n,16,15,15], a6 [n,2304],
+        a8 [n,2048], e9 [n,2304], e7 [n,2048], e6 [n,2304], e3 [n,16,15,15] (conv2's backward, summed over its groups)."""
+        n = int(n)
+        shapes = (("a3", (n, 16, 15, 15)), ("a6", (n, 2304)), ("a8", (n, 2048)), ("e9", (n, 2304)), ("e7", (n, 2048)), ("e6", (n, 2304)), ("e3", (n, 16, 15, 15)))
+        out = {k: np.empty(sh, np.float32) for k, sh in shapes}
+        self._chk(self.L.ht_debug_train_batch_buffers(self.h, n, *[_f(out[k]) for k, _ in shapes]))
+        return out
 
     # -- training samples on the device
     def expected_cnn_batch(self, poses, cams, segment_frame=False):

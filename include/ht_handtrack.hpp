@@ -286,6 +286,14 @@ public:
 	{
 		check(ctx_, ht_cnn_train_dev(ctx_, d_inputs, d_targets, n_pool, order.data(), (int)order.size(), alpha, d_mse, stream));
 	}
+	// Addition: mini-batch steps on the same pools (ht_cnn_train_batch_dev): step k trains on samples order[k*batch .. (k+1)*batch), all at the step's
+	// starting weights, w' = w - alpha * SUM_b g_b(w) -- a sum, not a mean (pass alpha / batch for the mean).  order.size() must be a multiple of batch.
+	// d_mse [order.size()] (device, optional) takes every sample's loss.
+	void TrainBatch(const float *d_inputs, const float *d_targets, int n_pool, const std::vector<int> &order, int batch, float alpha = 0.01f, float *d_mse = nullptr, void *stream = nullptr)
+	{
+		if (batch < 1 || order.size() % (size_t)batch) throw std::runtime_error("CNN::TrainBatch expects a positive batch that divides order.size()");
+		check(ctx_, ht_cnn_train_batch_dev(ctx_, d_inputs, d_targets, n_pool, order.data(), (int)(order.size() / (size_t)batch), batch, alpha, d_mse, stream));
+	}
 	void saveb(std::ostream &s)                                                              // cnn.h:591
 	{
 		std::vector<float> w(HT_CNNB_COUNT);

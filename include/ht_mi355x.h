@@ -242,6 +242,27 @@ int ht_expected_cnn_dev(ht_ctx *ctx, const float *d_poses, const float *d_cams, 
 int ht_cnn_input_dev(ht_ctx *ctx, const uint16_t *d_tiles, const float *d_cams, int B, float *d_cnn_in, void *stream);
 int ht_cnn_train_dev(ht_ctx *ctx, const float *d_inputs, const float *d_targets, int n_pool, const int *order, int n_steps, float alpha, float *d_mse, void *stream);
 
+/* ---- mini-batch training (an addition: the reference trains one sample at a time) --------------------------------------------
+ * One step on samples s_0..s_{batch-1} from weights w is  w' = w - alpha * SUM_b g_b(w),  g_b(w) = what CNN::Train(x_b, t_b, alpha) (cnn.h:558-580)
+ * subtracts from every weight, divided by alpha, ALL taken at the same w.  It is a SUM, not a mean: alpha keeps the reference's per-sample meaning, and a
+ * caller who wants the mean gradient passes alpha / batch.  batch = 1 is CNN::Train (to rounding: another summation order than ht_cnn_train).  A sample
+ * that appears twice in a step counts twice.  Every reduction has a fixed order: the same call on the same weights gives the same bits.
+ * ht_cnn_train_batch_dev   n_steps steps on device pools d_inputs [n_pool][4096], d_targets [n_pool][2304]: step k trains on samples
+ *                          order[k*batch .. (k+1)*batch) (`order` is a HOST array of n_steps*batch indices, all checked against [0, n_pool) before
+ *                          anything is launched), or on samples k*batch + b when order is NULL (n_steps*batch <= n_pool).  d_mse [n_steps*batch]
+ *                          (optional) = the value Train returns for each sample at its step's weights, sum E^2 / 2304.  1 <= batch <=
+ *                          HT_TRAIN_MAX_BATCH, any value.  Asynchronous on `stream` under ht_cnn_train_dev's rules: the weights change in stream
+ *                          order, the call ends with the refresh of the inference kernels' packed copies, ht_cnn_get_weights waits for it.  A
+ *                          refused call (HT_ERR_ARG, the message names the argument; also without weights of the 64x64-input net, the only one trained) leaves the context as it was.
+ * ht_cnn_train_batch       the same on host arrays inputs [n][4096], targets [n][2304], mse_out [n] (optional): an upload, then steps of `batch`
+ *                          samples in order; when n is no multiple of batch the remainder forms a last, smaller step.
+ * ht_debug_train_batch_buffers  test aid: the latest step's per-sample tensors, n = that step's sample count (HT_ERR_ARG otherwise): a3 [n][3600],
+ *                          a6 [n][2304], a8 [n][2048], e9 [n][2304], e7 [n][2048], e6 [n][2304], e3 [n][3600] (conv2's backward, summed over its groups). */
+#define HT_TRAIN_MAX_BATCH 256
+int ht_cnn_train_batch_dev(ht_ctx *ctx, const float *d_inputs, const float *d_targets, int n_pool, const int *order, int n_steps, int batch, float alpha, float *d_mse, void *stream);
+int ht_cnn_train_batch(ht_ctx *ctx, const float *inputs, const float *targets, int n, int batch, float alpha, float *mse_out);
+int ht_debug_train_batch_buffers(ht_ctx *ctx, int n, float *a3, float *a6, float *a8, float *e9, float *e7, float *e6, float *e3);
+
 /* ---- a hand model that is not being tracked (host only, no device needed) ---------------------------------------------------
  * The reference's applications keep a second PhysModel to pose, draw and ray-cast their synthetic input
  * (`PhysModel fakehand = LoadHandModel();` synthetic-tracker.cpp:94, FakeDepth :69-76).

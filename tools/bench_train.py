@@ -1,17 +1,73 @@
-"""Time the device training step (ht_cnn_train) on seeded inputs: ms per SGD step and the implied weight traffic."""
-import sys, time, os
+"""Time the device training step on seeded inputs.
+
+bench_train.py [n]                         ht_cnn_train: ms per SGD step and the implied weight traffic (as before)
+bench_train.py --batch N [N ...] [--out F] samples/s of the mini-batch step (ht_cnn_train_batch_dev) per batch size on a pool resident on the device,
+                                           timed with device events after a warm-up, at least 20 steps per size, beside the batch-1 path
+                                           (ht_cnn_train_dev, one sample a step) in the same run; --out writes the figures as JSON."""
+import argparse, json, sys, time, os
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from hand_tracking_samples_amd import native, weights
 
-n = int(sys.argv[1]) if len(sys.argv) > 1 else 256
+ap = argparse.ArgumentParser()
+ap.add_argument("n", nargs="?", type=int, default=256)
+ap.add_argument("--batch", nargs="+", type=int, default=None)
+ap.add_argument("--steps", type=int, default=40, help="timed steps per batch size (at least 20)")
+ap.add_argument("--out", default=None)
+args = ap.parse_args()
+n = args.n
+if args.batch is not None:
+    import torch      # before the library opens the device
 ctx = native.Context(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden", "model_hand17.htfx"), 1)
-ctx.load_weights(weights.make_cnnb())
+W0 = weights.make_cnnb()
+ctx.load_weights(W0)
 rng = np.random.default_rng(3)
-xs = rng.random((n, 4096), dtype=np.float32)
-ts = np.zeros((n, 2304), np.float32)
+if args.batch is None:
+    xs = rng.random((n, 4096), dtype=np.float32)
+    ts = np.zeros((n, 2304), np.float32)
+    for m in range(24):
+        ts[np.arange(n), (256 * m if m < 8 else 2048 + 16 * (m - 8)) + rng.integers(0, 16, n)] = 1.0
+    ctx.cnn_train(xs[:8], ts[:8], 0.001)
+    t0 = time.perf_counter(); mse = ctx.cnn_train(xs, ts, 0.001); dt = time.perf_counter() - t0
+    print("steps %d  %.3f ms/step  %.1f GB/s weight traffic (75.7 MB/step)  mse first %.5f last %.5f" % (n, dt / n * 1e3, 75.7e-3 / (dt / n), mse[0], mse[-1]))
+    sys.exit(0)
+
+steps = max(20, args.steps)
+pool = max(1024, max(args.batch))
+xs = rng.random((pool, 4096), dtype=np.float32)
+ts = np.zeros((pool, 2304), np.float32)
 for m in range(24):
-    ts[np.arange(n), (256 * m if m < 8 else 2048 + 16 * (m - 8)) + rng.integers(0, 16, n)] = 1.0
-ctx.cnn_train(xs[:8], ts[:8], 0.001)
-t0 = time.perf_counter(); mse = ctx.cnn_train(xs, ts, 0.001); dt = time.perf_counter() - t0
-print("steps %d  %.3f ms/step  %.1f GB/s weight traffic (75.7 MB/step)  mse first %.5f last %.5f" % (n, dt / n * 1e3, 75.7e-3 / (dt / n), mse[0], mse[-1]))
+    ts[np.arange(pool), (256 * m if m < 8 else 2048 + 16 * (m - 8)) + rng.integers(0, 16, pool)] = 1.0
+dev = torch.device("cuda:0")
+tx = torch.from_numpy(xs).to(dev); tt = torch.from_numpy(ts).to(dev)
+stream = torch.cuda.Stream(device=dev)
+
+
+def timed(call, reps=3):
+    """the best of `reps` timings of call() between two device events on the tool's stream, each from the seeded weights, after one warm-up"""
+    best = None
+    for r in range(reps + 1):
+        ctx.load_weights(W0)
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(stream); call(); e1.record(stream); e1.synchronize()
+        if r:
+            best = e0.elapsed_time(e1) if best is None else min(best, e0.elapsed_time(e1))
+    return best
+
+
+out = {"steps": steps, "pool": pool, "batch": {}}
+n1 = max(256, steps)
+order1 = rng.integers(0, pool, n1).astype(np.int32)
+ms = timed(lambda: ctx.cnn_train_dev(tx.data_ptr(), tt.data_ptr(), pool, order=order1, alpha=0.001, stream=stream.cuda_stream))
+base = n1 / ms * 1e3
+out["batch1_path"] = {"samples": n1, "ms_per_step": ms / n1, "samples_per_s": base}
+print("batch-1 path (ht_cnn_train_dev)  %d steps  %.4f ms/step  %.0f samples/s" % (n1, ms / n1, base))
+for b in args.batch:
+    order = rng.integers(0, pool, steps * b).astype(np.int32)
+    ms = timed(lambda: ctx.cnn_train_batch_dev(tx.data_ptr(), tt.data_ptr(), pool, b, order=order, alpha=0.001 / b, stream=stream.cuda_stream))
+    rate = steps * b / ms * 1e3
+    out["batch"][str(b)] = {"steps": steps, "ms_per_step": ms / steps, "samples_per_s": rate, "ratio_to_batch1_path": rate / base}
+    print("batch %-4d %d steps  %.4f ms/step  %.0f samples/s  %.2f x the batch-1 path" % (b, steps, ms / steps, rate, rate / base))
+if args.out:
+    with open(args.out, "w") as f:
+        json.dump(out, f, indent=1)

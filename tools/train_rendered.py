@@ -5,13 +5,14 @@
   3. ht_segment_vr_dev(0xF, {0.1, 0.70});
   4. ht_cnn_input_dev (handtrack.h:700);
   5. ht_expected_cnn_dev(..., HT_LABELS_SEGMENT_FRAME): train-cnn's compress + GatherHandExpectedCNN;
-  6. ht_cnn_train_dev over a seeded permutation of the round's samples (batch-1 SGD, lr 0.001, CNN::Train).
+  6. ht_cnn_train_dev over a seeded permutation of the round's samples (batch-1 SGD, lr 0.001, CNN::Train); with --minibatch N the permutation is cut
+     into steps of N samples for ht_cnn_train_batch_dev (w' = w - lr * SUM_b g_b(w): a sum, so --lr keeps its per-sample meaning).
 
 Held out: the frames tools/train_synthetic.py holds out (every 16th bench frame) and every interpolation that touches one of them.  Reported: the held-out
 MSE of the net on those 64 bench tiles, and on how many of them the unit of work takes the CNN-driven pose (the measure of tests/test_gpu_trained_net.py).
 Rates: closed-loop samples/s against ht_cnn_train_dev steps/s on a resident pool, and the label and tile-input stages timed with device events.
 
-    python tools/train_rendered.py [--rounds 280] [--batch 1024] [--seed N] [--json profiles/r07_labels.json]"""
+    python tools/train_rendered.py [--rounds 280] [--batch 1024] [--minibatch 1] [--lr 0.001] [--seed N] [--json profiles/r07_labels.json]"""
 import argparse
 import json
 import os
@@ -67,10 +68,14 @@ def main():
     ap.add_argument("--rounds", type=int, default=280)
     ap.add_argument("--batch", type=int, default=1024)
     ap.add_argument("--seed", type=int, default=SEED)
+    ap.add_argument("--minibatch", type=int, default=1, help="samples per SGD step: 1 = ht_cnn_train_dev (CNN::Train sample by sample), N > 1 = ht_cnn_train_batch_dev on steps of N of the round's permutation")
+    ap.add_argument("--lr", type=float, default=0.001, help="alpha of every step; a mini-batch step subtracts lr times the SUM of its samples' gradients")
     ap.add_argument("--json", default=None)
     ap.add_argument("--rate-steps", type=int, default=2048)
     ap.add_argument("--mesh", action="store_true", help="render the training frames from the subdivision surface (ht_render_mesh_depth_dev, pixel offset 0, far 4) instead of the hulls")
     a = ap.parse_args()
+    if a.minibatch < 1 or a.batch % a.minibatch:
+        ap.error("--minibatch must divide --batch")
     dev = torch.device("cuda:0")
     d = np.load(os.path.join(ROOT, "bench_data", "frames1024.npz"))
     gt = d["gtpose"]; pairs = train_pairs(len(gt))
@@ -85,6 +90,12 @@ def main():
     tiles = torch.empty((B, 64, 64), dtype=torch.int16, device=dev); tcams = torch.empty((B, 12), device=dev)
     x = torch.empty((B, 4096), device=dev); lab = torch.empty((B, 2304), device=dev); mse = torch.empty(B, device=dev)
     L = ctx.L
+
+    def train(order, d_mse=None):
+        if a.minibatch == 1:
+            ctx.cnn_train_dev(x.data_ptr(), lab.data_ptr(), B, order=order, alpha=a.lr, d_mse=d_mse, stream=s.cuda_stream)
+        else:
+            ctx.cnn_train_batch_dev(x.data_ptr(), lab.data_ptr(), B, a.minibatch, order=order, alpha=a.lr, d_mse=d_mse, stream=s.cuda_stream)
     ev = [torch.cuda.Event(enable_timing=True) for _ in range(6)]
 
     def round_(poses, order, timed=False):
@@ -102,7 +113,7 @@ def main():
             if timed: ev[3].record(s)
             ctx.expected_cnn_dev(tp.data_ptr(), tcams.data_ptr(), B, lab.data_ptr(), segment_frame=True, stream=s.cuda_stream)
             if timed: ev[4].record(s)
-            ctx.cnn_train_dev(x.data_ptr(), lab.data_ptr(), B, order=order, d_mse=mse.data_ptr(), stream=s.cuda_stream)
+            train(order, mse.data_ptr())
             if timed: ev[5].record(s)
 
     mse0, acc0 = held_out(ctx, d)
@@ -137,11 +148,11 @@ def main():
         e1.record(s)
     s.synchronize()
     loop_sps = nloop * B / (e0.elapsed_time(e1) / 1e3)
-    nbare = a.rate_steps
+    nbare = a.rate_steps // a.minibatch * a.minibatch
     bare_order = rng.integers(B, size=nbare).astype(np.int32)
     with torch.cuda.stream(s):
         e0.record(s)
-        ctx.cnn_train_dev(x.data_ptr(), lab.data_ptr(), B, order=bare_order, stream=s.cuda_stream)
+        train(bare_order)
         e1.record(s)
     s.synchronize()
     bare_sps = nbare / (e0.elapsed_time(e1) / 1e3)
@@ -174,10 +185,10 @@ def main():
     mse1, acc1 = curve[-1]["held_out_mse"], curve[-1]["cnn_pose_frames"]
     ctx.close()
     out = {"what": "tools/train_rendered.py: train-cnn's loop on the device, one stream: %d rounds of %d rendered 320x240 frames (render, segment, input, segment-frame labels, "
-                   "batch-1 SGD lr 0.001 over a seeded permutation), seed 0x%X" % (a.rounds, B, a.seed),
-           "rounds": a.rounds, "batch": B, "samples": a.rounds * B, "seconds": seconds,
+                   "SGD in steps of %d lr %g over a seeded permutation), seed 0x%X" % (a.rounds, B, a.minibatch, a.lr, a.seed),
+           "rounds": a.rounds, "batch": B, "minibatch": a.minibatch, "lr": a.lr, "samples": a.rounds * B, "seconds": seconds,
            "stage_ms_per_round": {"render": stage_ms[0], "segment": stage_ms[1], "cnn_input": stage_ms[2], "labels": stage_ms[3], "train": stage_ms[4]},
-           "kernels": kern, "closed_loop_samples_per_s": loop_sps, "bare_train_steps_per_s": bare_sps, "loop_over_bare": loop_sps / bare_sps,
+           "kernels": kern, "closed_loop_samples_per_s": loop_sps, "bare_train_steps_per_s": bare_sps,      # samples/s of the training call alone on the resident pool "loop_over_bare": loop_sps / bare_sps,
            "held_out": {"frames": 64, "mse_before": mse0, "mse_after": mse1, "cnn_pose_frames_before": acc0, "cnn_pose_frames_after": acc1,
                         "train_synthetic_reference": "50 of 64 after 300 epochs of the 960 fixed tiles"},
            "curve": curve}
