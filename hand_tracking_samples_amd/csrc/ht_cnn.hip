@@ -853,6 +853,8 @@ void ht_launch_cnn(const ht_cnn_weights &w, const float *cnn_in, float *act1, fl
 		// (conv2 82 us instead of 52); once they took 0.09 it reached into k_fc, whose one block per CU, all in step, lost 70 us to it (161 instead of 92).  Measured on one
 		// device, same build, three runs each (ms per 1024-frame step, tuning build): two launches, FitError beside 5.694; two launches, FC layers waiting for it 5.713; one
 		// launch, waiting 5.707; one launch, beside 5.737.  So an update keeps the two launches and a stand-alone evaluation takes the one: same results bit for bit.
+		// That holds only while FitError is the first kernel behind the fork on its stream (ht_solver_api.hip: update_beside_net).  With the launch tables and the boundary planes
+		// ahead of it (rounds 5 to 10) it started 0.2 ms late and ran under k_fc144_pk, 196 us long (profiles/r09_step_timeline.txt); they have a side stream of their own now.
 		static const bool conv_split = ht_tuning_env("HT_CONV_SPLIT"), conv_fused = ht_tuning_env("HT_CONV_FUSED");      // measurement (-DHT_TUNING): force either arrangement
 		if ((beside_other_work && !conv_fused) || conv_split)
 		{

@@ -1240,23 +1240,28 @@ int ht_contacts_frames_per_block(const ht_model_dev &M, int B)
 // rest, sorted by their candidate pairs, are dealt back and forth over the remaining blocks: fewer blocks pay a polytope phase at all.  epb: all of a block's frames
 // when the batch takes several rounds per CU (the sum of the blocks' times counts, and the long blocks start first), fewer when every block has a CU of its own (the
 // slowest block is the launch's time, and a block of four such frames would be it).
-// work = candidates + 2 x patches | polytope runs << 16 (k_contacts_coop); order[slot * blocks + block] = frame, B = no frame.  One block per launch slot of an
-// update and segment of 4096 frames (work / order: [slots][stride]); ranks by counting, the keys in LDS.  Runs beside the CNN at the head of an update: off every critical path.
-#define CO_ORDER_SEG 4096      // frames a block of k_contact_order ranks (by counting: quadratic); a larger batch is dealt segment by segment, each over its own blocks
-__global__ __launch_bounds__(1024) void k_contact_order(const int *__restrict__ work, int *__restrict__ order, int Ball, int nfr, int stride, unsigned slots, int epb)
+// work = candidates + 2 x patches | polytope runs << 16 (k_contacts_coop); order[slot * blocks + block] = frame, B = no frame.  Ranks by counting, the keys in LDS
+// (work / order: [slots][stride]).  Grid (launch slot of an update, segment of 4096 frames, part): every block stages its segment's keys and counts the frames with
+// runs itself, then ranks CO_ORDER_PART of the segment's frames, a frame per thread, and writes their places -- and "no frame" to the places of its share that stay
+// empty, which follow from the counts alone (the test ahead of the ranking loop), so every place of the table has exactly one writer per launch and no block clears what another fills.
+// Runs beside the CNN at the head of an update, ahead of the batch's first contact launch, which is the first to read a table.
+#define CO_ORDER_SEG 4096      // frames a segment of k_contact_order holds (ranks by counting: quadratic); a larger batch is dealt segment by segment, each over its own blocks
+#define CO_ORDER_PART 256      // frames a block of it ranks = its threads
+__global__ __launch_bounds__(CO_ORDER_PART) void k_contact_order(const int *__restrict__ work, int *__restrict__ order, int Ball, int nfr, int stride, unsigned slots, int epb)
 {
 	extern __shared__ int ko_w[];
 	__shared__ int ko_ne;
 	if (!((slots >> blockIdx.x) & 1u)) return;
-	const int seg = (CO_ORDER_SEG / nfr) * nfr, f0 = blockIdx.y * seg, B = Ball - f0 < seg ? Ball - f0 : seg;      // this block's frames: [f0, f0 + B)
+	const int seg = (CO_ORDER_SEG / nfr) * nfr, f0 = blockIdx.y * seg, B = Ball - f0 < seg ? Ball - f0 : seg;      // this segment's frames: [f0, f0 + B)
 	const int blocks_all = (Ball + nfr - 1) / nfr, b0 = f0 / nfr;
+	const int blocks = (B + nfr - 1) / nfr, B4 = (B + 3) & ~3, places = blocks * nfr;
+	if ((int)blockIdx.z * CO_ORDER_PART >= places) return;      // a short last segment: the grid's parts follow the longest
 	const int *w = work + (size_t)blockIdx.x * stride + f0;
 	int *o = order + (size_t)blockIdx.x * stride;
-	const int blocks = (B + nfr - 1) / nfr, B4 = (B + 3) & ~3;
 	if (threadIdx.x == 0) ko_ne = 0;
 	__syncthreads();
 	int mine = 0;
-	for (int i = threadIdx.x; i < B4; i += 1024)
+	for (int i = threadIdx.x; i < B4; i += CO_ORDER_PART)
 	{
 		const int v = i < B ? w[i] : -1;
 		const int runs = v < 0 ? 0 : (v >> 16), pairs = v < 0 ? 0 : (v & 0xffff);
@@ -1264,7 +1269,6 @@ __global__ __launch_bounds__(1024) void k_contact_order(const int *__restrict__ 
 		mine += runs > 0 ? 1 : 0;
 	}
 	if (mine) atomicAdd(&ko_ne, mine);
-	for (int i = threadIdx.x; i < blocks * nfr; i += 1024) o[(i / blocks) * blocks_all + b0 + i % blocks] = Ball;
 	__syncthreads();
 	const int ne = ko_ne, ng = B - ne;                      // frames with polytope runs (the first ne places of the sorted order) and without
 	if (epb > nfr) epb = nfr;
@@ -1272,27 +1276,35 @@ __global__ __launch_bounds__(1024) void k_contact_order(const int *__restrict__ 
 	const int neb = (ne + epb - 1) / epb, ngb = blocks - neb;      // blocks that get frames with polytope runs, epb each, and the others
 	const int nfree = neb * nfr - ne;                       // places left in the first kind: the LIGHTEST frames without runs fill them
 	const int nheavy = ng - nfree > 0 ? ng - nfree : 0;     // frames without runs that go to the second kind
-	for (int i = threadIdx.x; i < B; i += 1024)
+	const int i = blockIdx.z * CO_ORDER_PART + threadIdx.x;
+	// the places of this block's share no frame comes to: place (round, col) of the segment's grid is place r = round * nb_ + (col with the snake undone) of its kind,
+	// and the kinds fill their first ne + (ng - nheavy) and nheavy places
+	if (i < places)
 	{
-		const int wi = ko_w[i];
-		int rank = 0;
-		for (int j = 0; j < B4; j += 4)
-		{
-			const int4 k = *reinterpret_cast<const int4 *>(ko_w + j);
-			rank += ((k.x > wi || (k.x == wi && j < i)) ? 1 : 0) + ((k.y > wi || (k.y == wi && j + 1 < i)) ? 1 : 0) + ((k.z > wi || (k.z == wi && j + 2 < i)) ? 1 : 0) + ((k.w > wi || (k.w == wi && j + 3 < i)) ? 1 : 0);
-		}
-		int nb_, base, r;
-		if (rank < ne) { nb_ = neb; base = 0; r = rank; }                                        // place r of the first kind's grid (neb wide, round by round)
-		else if (rank - ne < nheavy) { nb_ = ngb; base = neb; r = rank - ne; }                   // place r of the second kind's grid
-		else { nb_ = neb; base = 0; r = ne + (rank - ne - nheavy); }                             // the lightest: the places the first kind has left
-		const int round = r / nb_, pos = r - round * nb_;
-		o[round * blocks_all + b0 + base + ((round & 1) ? nb_ - 1 - pos : pos)] = f0 + i;
+		const int round = i / blocks, col = i - round * blocks;
+		const bool first = col < neb;
+		const int nb_ = first ? neb : ngb, p = first ? col : col - neb, count = first ? ne + (ng - nheavy) : nheavy;
+		if (round * nb_ + ((round & 1) ? nb_ - 1 - p : p) >= count) o[round * blocks_all + b0 + col] = Ball;
 	}
+	if (i >= B) return;
+	const int wi = ko_w[i];
+	int rank = 0;
+	for (int j = 0; j < B4; j += 4)
+	{
+		const int4 k = *reinterpret_cast<const int4 *>(ko_w + j);
+		rank += ((k.x > wi || (k.x == wi && j < i)) ? 1 : 0) + ((k.y > wi || (k.y == wi && j + 1 < i)) ? 1 : 0) + ((k.z > wi || (k.z == wi && j + 2 < i)) ? 1 : 0) + ((k.w > wi || (k.w == wi && j + 3 < i)) ? 1 : 0);
+	}
+	int nb_, base, r;
+	if (rank < ne) { nb_ = neb; base = 0; r = rank; }                                        // place r of the first kind's grid (neb wide, round by round)
+	else if (rank - ne < nheavy) { nb_ = ngb; base = neb; r = rank - ne; }                   // place r of the second kind's grid
+	else { nb_ = neb; base = 0; r = ne + (rank - ne - nheavy); }                             // the lightest: the places the first kind has left
+	const int round = r / nb_, pos = r - round * nb_;
+	o[round * blocks_all + b0 + base + ((round & 1) ? nb_ - 1 - pos : pos)] = f0 + i;
 }
 void ht_launch_contact_order(const int *work, int *order, int B, int nfr, int stride, unsigned slots, int nslots, int epb, hipStream_t s)
 {
-	const int seg = (CO_ORDER_SEG / nfr) * nfr, nseg = (B + seg - 1) / seg;
-	hipLaunchKernelGGL(k_contact_order, dim3(nslots, nseg), dim3(1024), (size_t)(((B < seg ? B : seg) + 3) & ~3) * sizeof(int), s, work, order, B, nfr, stride, slots, epb);
+	const int seg = (CO_ORDER_SEG / nfr) * nfr, nseg = (B + seg - 1) / seg, first = B < seg ? B : seg, places = (first + nfr - 1) / nfr * nfr;
+	hipLaunchKernelGGL(k_contact_order, dim3(nslots, nseg, (places + CO_ORDER_PART - 1) / CO_ORDER_PART), dim3(CO_ORDER_PART), (size_t)((first + 3) & ~3) * sizeof(int), s, work, order, B, nfr, stride, slots, epb);
 }
 void ht_launch_contacts(const ht_model_dev &M, const float *state, float driftmax, float jiggle_sin, const int *active_flag, void *epa_ws, float *contacts, int *ncontacts, int B, hipStream_t s, bool beside_cloud_rows, int force_kernel, int few_frames,
                         const int *order, int *work_out)

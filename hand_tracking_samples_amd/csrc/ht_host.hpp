@@ -65,6 +65,7 @@ struct ht_ctx
 	int solve_tables = 0;                                       // 1 (ht_debug_solve_tables; tools/exp_tables.sh): k_solve_prep makes every solve's tables beside the contact kernel.  Measured slower in round 6 (profiles/r06_notes.md section 1): off
 	int *d_accepted = nullptr;
 	float *d_contacts = nullptr; int *d_ncontacts = nullptr;    // [B][HT_MAXCONTACT][HT_CONTACT]
+	bool tables_out = false;        // this update's launch tables (d_corder, d_sorder) are still being made on side stream 0: until that stream is joined only launches ON it may read them (ht_solver_api.hip: update_beside_net)
 	int *d_cwork = nullptr, *d_corder = nullptr;                  // [HT_CONTACT_SLOTS][cstride]: what every frame cost in every contact launch of the latest update; the assignment of frames to blocks made from it for the current one (ht_gjk.hip: k_contact_order)
 	int *d_porder = nullptr;      // [B]: the frames by their point counts (ht_model_dev::frame_order inside an update of a batch of several rounds per CU)
 	int *d_swork = nullptr, *d_sorder = nullptr; unsigned swork_mask = 0, sorder_mask = 0; int swork_B = 0;      // the same for the solves of a batch that takes several rounds per CU: what every frame's solve took, the launch order (longest first)

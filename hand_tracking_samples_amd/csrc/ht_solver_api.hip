@@ -53,6 +53,13 @@ static int pass_slot(int pass) { return pass >= 0 && pass < 8 ? 8 + pass : -1; }
 // that the launch ends on short frames instead of waiting for a long one that started last.  Results do not depend on the order.
 static bool solve_history_on(const ht_ctx *ctx, int B) { return ctx->d_swork && B > ctx->n_cu * 8 && B + 8 <= ctx->cstride; }
 struct solve_opts { const int *active = nullptr; int hist_slot = -1; bool tables = false, shared_gpu = false; float *poses_out = nullptr; const int *out_npts = nullptr; };      // active: only the frames whose flag is set; tables: solve_prep has made them for exactly this solve; poses_out: the solve also writes the user poses
+// Tuning builds: a launch that takes a launch table while the tables are still being made on side stream 0 must be on that stream (update_resets)
+static void table_read_on(const ht_ctx *ctx, hipStream_t s)
+{
+#ifdef HT_TUNING
+	if (ctx->tables_out && s != ctx->side[0]) { fprintf(stderr, "a launch table read on a stream that has not joined side stream 0\n"); abort(); }
+#endif
+}
 static void solve_step(ht_ctx *ctx, int which, const step_mix &m, int B, hipStream_t s, const solve_opts &o)
 {
 	solve_args a = solve_head(ctx, which, ctx->phys.use_collision != 0);
@@ -63,12 +70,14 @@ static void solve_step(ht_ctx *ctx, int which, const step_mix &m, int B, hipStre
 	a.dbg = ht_tuning_flags(); a.shared_gpu = o.shared_gpu ? 1 : 0; a.tables = o.tables ? ctx->d_tables : nullptr;
 	exact_args(ctx, a, m.cloud);
 	a.out_poses = o.poses_out; a.out_npts = o.out_npts; a.out_initializing = ctx->d_initializing; a.out_min_point_num = ctx->par.min_point_num;
+	// (a solve on some of the frames -- o.active -- keeps no cost history and takes no order table: update_resets relies on it, as on contact_history's rule for the reset frames)
 	if (o.hist_slot >= 0 && o.hist_slot < HT_CONTACT_SLOTS && !o.active && !exact_solver(ctx) && solve_history_on(ctx, B) && B == ctx->swork_B)
 	{
 		a.cost_out = ctx->d_swork + (size_t)o.hist_slot * ctx->cstride;
 		ctx->swork_mask |= 1u << o.hist_slot;
 		if ((ctx->sorder_mask >> o.hist_slot) & 1u) a.frame_order = ctx->d_sorder + (size_t)o.hist_slot * ctx->cstride;
 	}
+	if (a.frame_order) table_read_on(ctx, s);
 	ht_launch_solve(ctx->model, ctx->phys, a, B, s);
 }
 // Round 6: the tables of a solve (ht_solve_shared.hpp) are made by k_solve_prep on whichever stream runs the solve's row producers, behind the cloud rows (it lists them per
@@ -116,6 +125,7 @@ static inline void mark(const char *, hipStream_t) {}
 static inline void marks_dump() {}
 #endif
 // Contact launches of an update that keep a work history (ht_launch.hpp: HT_CONTACT_SLOTS).  slot < 0 or a launch on the reset frames alone: no history, the fixed assignment.
+// (update_resets relies on the second: under resets_lap the tables are still being made on side stream 0 while this stream launches the reset frames' contacts.)
 struct contact_slot { const int *order; int *work; };
 static contact_slot contact_history(ht_ctx *ctx, int slot, const int *active, int B)
 {
@@ -131,6 +141,7 @@ static contact_slot contact_history(ht_ctx *ctx, int slot, const int *active, in
 static void launch_contacts(ht_ctx *ctx, int which, const int *active, int B, hipStream_t s, bool beside_cloud_rows = false, int slot = -1)
 {
 	const contact_slot ch = contact_history(ctx, slot, active, B);
+	if (ch.order) table_read_on(ctx, s);
 	ht_launch_contacts(ctx->model, ctx->d_state[which], ctx->phys.driftmax, ctx->phys.jiggle_sin, active, ctx->d_epa_ws, ctx->d_contacts, ctx->d_ncontacts, B, s, beside_cloud_rows, ctx->contact_kernel,
 	                   active && active == ctx->d_flags && !ctx->many_reset, ch.order, ch.work);
 }
@@ -160,7 +171,7 @@ static void contact_orders(ht_ctx *ctx, int B, hipStream_t t)
 // (side_open keeps track of the side streams that are out: an update ends by bringing back whichever still is, join_open)
 static void fork(ht_ctx *ctx, hipStream_t s) { (void)hipEventRecord(ctx->ev_fork, s); for (int i = 0; i < 2; i++) (void)hipStreamWaitEvent(ctx->side[i], ctx->ev_fork, 0); ctx->side_open |= 3u; }
 static void fork1(ht_ctx *ctx, hipStream_t s, int i) { (void)hipEventRecord(ctx->ev_fork, s); (void)hipStreamWaitEvent(ctx->side[i], ctx->ev_fork, 0); ctx->side_open |= 1u << i; }
-static void join1(ht_ctx *ctx, hipStream_t s, int i) { (void)hipEventRecord(ctx->ev_join[i], ctx->side[i]); (void)hipStreamWaitEvent(s, ctx->ev_join[i], 0); ctx->side_open &= ~(1u << i); }
+static void join1(ht_ctx *ctx, hipStream_t s, int i) { (void)hipEventRecord(ctx->ev_join[i], ctx->side[i]); (void)hipStreamWaitEvent(s, ctx->ev_join[i], 0); ctx->side_open &= ~(1u << i); if (i == 0) ctx->tables_out = false; }
 static void join(ht_ctx *ctx, hipStream_t s, int n) { for (int i = 0; i < n; i++) join1(ctx, s, i); }
 static void join_open(ht_ctx *ctx, hipStream_t s) { for (int i = 0; i < 2; i++) if ((ctx->side_open >> i) & 1u) join1(ctx, s, i); }
 
@@ -338,17 +349,24 @@ static void update_fit_error_old(ht_ctx *ctx, const update_call &u, hipStream_t 
 	dec.mode = 1; dec.reset_thr = p.full_reset_on_error; dec.angles_only = p.angles_only; dec.flags = ctx->d_flags; dec.nflags = ctx->d_nflags; dec.list = ctx->d_flist; dec.nlist = ctx->d_nflist; dec.nreset = ctx->d_nreset;
 	ht_launch_fit_error(ctx->model, ctx->d_state[0], ctx->d_pts, ctx->d_npts, u.d_depth, u.img_cams, u.iw, u.ih, p.bone_sum_error_scale, ctx->d_err_old, u.B, t, &dec);
 }
-// The side branch beside the net.  Nothing on it needs the CNN: the error of the carried pose and the reset decision only read the point cloud and the
-// tracker state, so they run beside the CNN.  (The contacts of MultiStepSim's first step do not need it either, but the contact kernel
+// The side branches beside the net, in dependency order.  Nothing on them needs the CNN.  What the update's stream waits for behind the net is the reset decision alone,
+// so the carried pose's FitError (with the set_pose it reads behind) has side stream 1 to itself from the fork on and runs under the convolutions (ht_cnn.hip: ht_launch_cnn).
+// The launch tables and the boundary planes have later consumers -- the batch's first contact launch and first solve, the first main pass -- and go to side stream 0, which
+// has nothing else to do beside the net: ahead of FitError on its stream (rounds 5 to 10) they made it start 0.2 ms late, and the reset kernel waited for it 0.1 ms behind the net.
+// Measured (profiles/r11_update_head.md): the reset kernel starts 46 us earlier in a 1024-frame step, 4.459 -> 4.412 and 4.474 -> 4.434 ms per step in two sessions, 19.54 -> 19.15 ms
+// at 8192 frames.  Everything on side stream 1 with FitError first and one join was measured beside it: the same at 1024 frames (4.848 against 4.849 ms, tuning build), 0.05 ms slower at 8192.
+// update_resets says when stream 0 comes back.  (The contacts of MultiStepSim's first step do not need the net either, but the contact kernel
 // owns whole CUs and the FC layers want one block per CU: beside each other they took 0.78 ms, one after the other 0.46.)
 static void update_beside_net(ht_ctx *ctx, const update_call &u)
 {
-	hipStream_t t = ctx->side[1];
+	hipStream_t fit = ctx->side[1], rest = ctx->side[0];
+	mark("update start", u.s);
 	fork(ctx, u.s);
-	update_planes(ctx, u, t);
-	contact_orders(ctx, u.B, t);
-	if (u.mode == UPD_FULL && !(u.d_start && !u.fs)) ht_launch_set_pose(ctx->d_state[1], ctx->d_state[0], ctx->model.nb, u.B, 2, t);     // othermodel.SetPose(handmodel.GetPose()) handtrack.h:757 (both were just seeded with the same pose otherwise)
-	update_fit_error_old(ctx, u, t);
+	if (u.mode == UPD_FULL && !(u.d_start && !u.fs)) ht_launch_set_pose(ctx->d_state[1], ctx->d_state[0], ctx->model.nb, u.B, 2, fit);     // othermodel.SetPose(handmodel.GetPose()) handtrack.h:757 (both were just seeded with the same pose otherwise)
+	update_fit_error_old(ctx, u, fit); mark("carried FitError done", fit);
+	contact_orders(ctx, u.B, rest); mark("orders done", rest);
+	update_planes(ctx, u, rest); mark("planes done", rest);
+	ctx->tables_out = true;      // until side stream 0 is joined (join1)
 }
 static void update_net(ht_ctx *ctx, const update_call &u, bool overlap)      // the net and its decode.  overlap: the side branch's FitError runs beside the net
 {
@@ -401,15 +419,22 @@ static void resets_lap(ht_ctx *ctx, int B, hipStream_t s)      // p.steps >= 2
 	multistep(ctx, B, steps_on(s).steps(0, 1).frames(reset_frames).in_order().solve_only()); mark("reset frames step 0 done", s);
 	multistep(ctx, B, steps_on(u).steps(1, 2).frames(batch_frames).in_order().unprofiled().rows_only()); mark("batch step 1 rows done", u);      // in order on the side stream: there is time (0.76 against 0.82 ms), and a fork out of a forked stream does not survive a HIP graph capture
 	multistep(ctx, B, steps_on(s).steps(1, 2).frames(reset_frames).rows_beside(1).rows_only()); mark("reset frames step 1 rows done", s);      // the reset frames' rows for step 1, beside the batch's
-	join(ctx, s, 1); reset_tail(ctx);
+	join(ctx, s, 1); mark("side branch back", s); reset_tail(ctx);      // the batch's steps so far, and ahead of them the tables and the planes of the update's head
 	multistep(ctx, B, steps_on(s).steps(1, 2).all_frames().solve_only()); mark("step 1 done", s);
 	multistep(ctx, B, steps_on(s).steps(2).all_frames().rows_beside(0)); mark("MultiStepSim done", s);
 }
 // The overlapped update behind the net: the side branch comes back, then the reset frames and MultiStepSim in one of the organisations above
 static void update_resets(ht_ctx *ctx, const update_call &u)
 {
-	hipStream_t s = u.s; join1(ctx, s, 1);      // the side branch comes back
+	hipStream_t s = u.s; mark("net done", s);
 	static const int join_step = ht_tuning_int("HT_RESET_JOIN", 0);      // experiment (-DHT_TUNING): the reset frames take steps [0, join_step) on the side stream
+	static const bool no_lap = ht_tuning_env("HT_NO_STEP1_LAP");      // experiment (-DHT_TUNING)
+	const bool lap = join_step <= 0 && ctx->par.steps >= 2 && !no_lap;
+	join1(ctx, s, 1);      // the reset decision comes back
+	// The tables and the planes (side stream 0).  resets_lap runs the batch's first step in order on that very stream, behind them, and this stream launches nothing that
+	// reads a table or the planes before it takes that stream back; the other organisations launch the batch's first contacts here, so the stream comes back first.
+	if (!lap) join1(ctx, s, 0);
+	mark(lap ? "reset decision back" : "side branch back", s);      // under resets_lap side stream 0 is still out
 	fork(ctx, s);
 	const unsigned frames = ctx->h_nreset[0], updates = ctx->h_nreset[1];      // few or many reset frames (ht_host.hpp: d_nreset): the average over the updates whose counts have arrived since the last look
 	if (updates != ctx->nreset_seen[1])
@@ -417,9 +442,8 @@ static void update_resets(ht_ctx *ctx, const update_call &u)
 		ctx->many_reset = (frames - ctx->nreset_seen[0]) / (updates - ctx->nreset_seen[1]) > (unsigned)ctx->n_cu;
 		ctx->nreset_seen[0] = frames; ctx->nreset_seen[1] = updates;
 	}
-	static const bool no_lap = ht_tuning_env("HT_NO_STEP1_LAP");      // experiment (-DHT_TUNING)
 	if (join_step > 0) resets_joined_late(ctx, u.B, s, join_step);
-	else if (ctx->par.steps >= 2 && !no_lap) resets_lap(ctx, u.B, s);
+	else if (lap) resets_lap(ctx, u.B, s);
 	else resets_short(ctx, u.B, s);
 }
 // FitError of the CNN-driven pose, and on its last thread the accept step (handtrack.h:713-731)
@@ -940,6 +964,37 @@ extern "C" int ht_debug_contact_kernel(ht_ctx *ctx, int which)
 	if (!ctx || which < 0 || which > 2) return HT_ERR_ARG;
 	ctx->contact_kernel = which;
 	return HT_OK;
+}
+// Tests only: the launch tables of one slot from a work array the caller gives.  The product's launchers on the context's stream, over buffers of the call's own
+// (stride as the context lays its histories out: B + 8), preset to -1 so that a place no block wrote shows.
+//   ht_debug_contact_order: order_out[ceil(B / nfr) * nfr] = k_contact_order's table (order_out[round * blocks + block] = frame, B = no frame); 1 <= nfr <= 8, epb >= 1
+//   ht_debug_rank_desc:     order_out[B] = k_rank_desc's
+template <class F> static int debug_order_table(ht_ctx *ctx, const int *work, int B, int n_out, int *order_out, F launch)      // launch(work, order, stride, stream)
+{
+	const int stride = B + 8;
+	int *d = nullptr;
+	HIPCHK(ctx, hipMalloc(&d, (size_t)2 * stride * sizeof(int)));
+	hipStream_t s = ctx->stream;
+	hipError_t e = hipMemcpyAsync(d, work, (size_t)B * sizeof(int), hipMemcpyHostToDevice, s);
+	if (e == hipSuccess) e = hipMemsetAsync(d + stride, 0xff, (size_t)stride * sizeof(int), s);
+	if (e == hipSuccess) { launch(d, d + stride, stride, s); e = hipGetLastError(); }
+	if (e == hipSuccess) e = hipMemcpyAsync(order_out, d + stride, (size_t)n_out * sizeof(int), hipMemcpyDeviceToHost, s);
+	if (e == hipSuccess) e = hipStreamSynchronize(s); else (void)hipStreamSynchronize(s);
+	(void)hipFree(d);
+	HIPCHK(ctx, e);
+	return HT_OK;
+}
+extern "C" int ht_debug_contact_order(ht_ctx *ctx, const int *work, int B, int nfr, int epb, int *order_out)
+{
+	CHECK_READY(ctx);
+	if (!work || !order_out || B < 1 || nfr < 1 || nfr > 8 || epb < 1) return HT_ERR_ARG;
+	return debug_order_table(ctx, work, B, (B + nfr - 1) / nfr * nfr, order_out, [&](const int *w, int *o, int stride, hipStream_t s) { ht_launch_contact_order(w, o, B, nfr, stride, 1u, 1, epb, s); });
+}
+extern "C" int ht_debug_rank_desc(ht_ctx *ctx, const int *work, int B, int *order_out)
+{
+	CHECK_READY(ctx);
+	if (!work || !order_out || B < 1) return HT_ERR_ARG;
+	return debug_order_table(ctx, work, B, B, order_out, [&](const int *w, int *o, int stride, hipStream_t s) { ht_launch_rank_desc(w, o, B, stride, 1u, 1, s); });
 }
 extern "C" int ht_debug_solve_tables(ht_ctx *ctx, int on)
 {

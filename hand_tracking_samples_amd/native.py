@@ -27,7 +27,7 @@ SYMBOLS = (
     "ht_model_open", "ht_model_close", "ht_model_error", "ht_model_counts", "ht_model_body", "ht_model_body_mesh", "ht_model_body_sdmesh", "ht_model_hitcheck", "ht_model_hitcheck_mesh", "ht_model_render_mesh", "ht_model_scale", "ht_render_mesh_depth", "ht_render_mesh_depth_dev",
     "ht_tracker_reset", "ht_get_state", "ht_set_state", "ht_get_tracker_flags", "ht_set_tracker_flags", "ht_update_sync", "ht_update_dev", "ht_update_frames_sync", "ht_update_frames_dev", "ht_update_direct_sync", "ht_update_direct_dev", "ht_update_cnn_model_sync", "ht_get_cnn_results", "ht_get_cnn_layers", "ht_frames_overflow", "ht_reserve_points", "ht_point_capacity", "ht_capacity_events", "ht_segment_vr", "ht_segment_vr_dev", "ht_render_depth", "ht_render_depth_dev", "ht_slowfit", "ht_set_points", "ht_fit_rows", "ht_physics_update",
     "ht_stage_prepare", "ht_stage_decode", "ht_stage_fit_error", "ht_stage_cloud_rows", "ht_stage_contacts", "ht_stage_fit",
-    "ht_stage_multistep", "ht_stage_multistep_range", "ht_stage_scratch_unibody", "ht_stage_chamber", "ht_profile_enable", "ht_profile_read", "ht_debug_solve_stats", "ht_debug_contact_stats", "ht_debug_solver_build", "ht_debug_reset_flags", "ht_debug_reset_organisation", "ht_update_passes_sync", "ht_job_start", "ht_job_poll", "ht_job_wait", "ht_job_collect", "ht_debug_contact_kernel", "ht_contact_capacity", "ht_debug_solve_tables", "ht_debug_solve_tables_header", "ht_debug_train_buffers",
+    "ht_stage_multistep", "ht_stage_multistep_range", "ht_stage_scratch_unibody", "ht_stage_chamber", "ht_profile_enable", "ht_profile_read", "ht_debug_solve_stats", "ht_debug_contact_stats", "ht_debug_solver_build", "ht_debug_reset_flags", "ht_debug_reset_organisation", "ht_update_passes_sync", "ht_job_start", "ht_job_poll", "ht_job_wait", "ht_job_collect", "ht_debug_contact_kernel", "ht_debug_contact_order", "ht_debug_rank_desc", "ht_contact_capacity", "ht_debug_solve_tables", "ht_debug_solve_tables_header", "ht_debug_train_buffers",
     "ht_comm_available", "ht_comm_unique_id", "ht_comm_init", "ht_comm_info", "ht_gather_poses_dev", "ht_gather_wait", "ht_gather_wait_host", "ht_comm_destroy",
 )
 
@@ -135,6 +135,8 @@ def load(build_if_missing=True):
     L.ht_debug_reset_organisation.argtypes = [vp, ip]
     L.ht_debug_reset_flags.argtypes = [vp, ip, C.c_int]
     L.ht_debug_contact_kernel.argtypes = [vp, C.c_int]
+    L.ht_debug_contact_order.argtypes = [vp, ip, C.c_int, C.c_int, C.c_int, ip]
+    L.ht_debug_rank_desc.argtypes = [vp, ip, C.c_int, ip]
     L.ht_debug_solve_tables.argtypes = [vp, C.c_int]
     L.ht_contact_capacity.argtypes = [vp, ip, ip, ip, ip]
     L.ht_debug_solve_tables_header.argtypes = [vp, C.c_int, ip]
@@ -496,6 +498,20 @@ class Context:
     def debug_contact_kernel(self, which):
         """Test aid: pin the contact kernel's organisation (0 auto, 1 cooperative, 2 lane-per-pair).  Same contacts either way."""
         self._chk(self.L.ht_debug_contact_kernel(self.h, int(which)))
+
+    def debug_contact_order(self, work, nfr, epb):
+        """Test aid: k_contact_order's table for one launch slot from the per-frame costs `work` (candidates + 2 x patches | polytope runs << 16): [nfr, ceil(B / nfr)],
+        table[round, block] = frame, B = no frame; -1 where the launch wrote nothing."""
+        work = _c(work, np.int32); B = len(work); blocks = (B + nfr - 1) // nfr
+        out = np.empty(blocks * nfr, np.int32)
+        self._chk(self.L.ht_debug_contact_order(self.h, _i(work), B, int(nfr), int(epb), _i(out)))
+        return out.reshape(nfr, blocks)
+
+    def debug_rank_desc(self, work):
+        """Test aid: k_rank_desc's table for one launch slot: the frames of every 4096-frame segment by `work`, largest first, ties by index; -1 where the launch wrote nothing."""
+        work = _c(work, np.int32); out = np.empty(len(work), np.int32)
+        self._chk(self.L.ht_debug_rank_desc(self.h, _i(work), len(work), _i(out)))
+        return out
 
     def contact_capacity(self):
         """(samples_bound, patches_bound, pool, patch_slots): the most touching samples / five-sample patches a frame of this model can produce, and what the contact kernel holds"""

@@ -438,6 +438,12 @@ int ht_debug_reset_organisation(ht_ctx *ctx, int *many);
 /* Test aid: pins the organisation of the contact kernel (0 = chosen per launch: the cooperative kernel whenever the model fits its LDS; 1 cooperative,
  * 2 one lane group per body pair).  Same contacts in the same order either way. */
 int ht_debug_contact_kernel(ht_ctx *ctx, int which);
+/* Test aid: the launch tables an update makes at its head from the previous update's per-frame costs, here from a cost array the caller gives (one launch slot, host memory):
+ * ht_debug_contact_order: the assignment of frames to the cooperative contact kernel's blocks of nfr frames (1-8; epb: frames with polytope runs per block);
+ *   order_out[ceil(B / nfr) * nfr], order_out[round * blocks + block] = frame, B = no frame.  work[i] = candidate pairs + 2 x patches | polytope runs << 16.
+ * ht_debug_rank_desc: order_out[B] = the frames of every 4096-frame segment by work, largest first, ties by index. */
+int ht_debug_contact_order(ht_ctx *ctx, const int *work, int B, int nfr, int epb, int *order_out);
+int ht_debug_rank_desc(ht_ctx *ctx, const int *work, int B, int *order_out);
 /* Test / measurement aid: 0 (default) = every solve makes its tables (joint groups, angular records, block couplings, chain lists) in k_solve's own one-wave prologue;
  * 1 = k_solve_prep makes them on a side stream beside the contact kernel (csrc/ht_prep.hip; round 6's experiment: k_solve 8 % shorter, the step longer -- profiles/r06_notes.md);
  * 2 = only the pose-only tables (joint groups, angular records, block couplings), on the side stream the cloud rows do not use: also measured slower.

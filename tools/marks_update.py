@@ -1,4 +1,5 @@
-"""Event marks of one update on the tuning build (HT_MARKS=1): where the concurrent streams really are, in ms since the fork."""
+"""Event marks of one update on the tuning build (HT_MARKS=1): where the concurrent streams really are, in ms since the update's start.
+The head: "update start", "carried FitError done" / "orders done" / "planes done" on the side streams, "net done" and "reset decision back" on the update's stream; "side branch back" where side stream 0 is joined."""
 import os, sys
 import numpy as np
 import torch
