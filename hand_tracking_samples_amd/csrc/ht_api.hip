@@ -742,7 +742,9 @@ int ht_alloc_buffers(ht_ctx *ctx)
 	A(d_chamber, B * 5 * nb * HT_ROW); A(d_nchamber, B); A(d_accepted, B); A(d_chplanes, B * 20); A(d_chon, B);
 	if (ht_tuning_int("HT_TABLES", 0) > 0) { if ((r = ht_alloc_solve_tables(ctx))) return r; }      // measurement builds (tools/exp_tables.sh); otherwise on ht_debug_solve_tables(ctx, 1)
 	A(d_contacts, B * HT_MAXCONTACT * HT_CONTACT); A(d_ncontacts, B); A(d_epa_ws, ht_contacts_workspace_bytes((int)B)); HIPCHK(ctx, hipMemset(ctx->d_epa_ws, 0, ht_contacts_workspace_bytes((int)B)));
-	ctx->cstride = (int)B + 8; A(d_cwork, (size_t)HT_CONTACT_SLOTS * ctx->cstride); A(d_corder, (size_t)HT_CONTACT_SLOTS * ctx->cstride); A(d_porder, B); A(d_swork, (size_t)HT_CONTACT_SLOTS * ctx->cstride); A(d_sorder, (size_t)HT_CONTACT_SLOTS * ctx->cstride);
+	if ((r = ht_history_alloc(ctx, ctx->contact_hist))) return r;
+	A(d_porder, B);
+	if ((r = ht_history_alloc(ctx, ctx->solve_hist))) return r;
 	if ((r = ht_reserve_points_locked(ctx, HT_MAXPTS))) return r;
 	A(d_poses_out, B * nb * HT_POSE); A(d_start, B * nb * HT_POSE);
 	A(d_stage, B * nb * HT_STATE_STRIDE);
@@ -754,7 +756,5 @@ int ht_alloc_buffers(ht_ctx *ctx)
 	HIPCHK(ctx, hipMemset(ctx->d_npts, 0, B * sizeof(int)));
 	HIPCHK(ctx, hipMemset(ctx->d_nrows, 0, B * sizeof(int)));
 	HIPCHK(ctx, hipMemset(ctx->d_ncontacts, 0, B * sizeof(int)));
-	HIPCHK(ctx, hipMemset(ctx->d_cwork, 0, (size_t)HT_CONTACT_SLOTS * ctx->cstride * sizeof(int)));      // the work histories: a slot a launch has not written yet ranks equal keys, not garbage
-	HIPCHK(ctx, hipMemset(ctx->d_swork, 0, (size_t)HT_CONTACT_SLOTS * ctx->cstride * sizeof(int)));
 	return HT_OK;
 }

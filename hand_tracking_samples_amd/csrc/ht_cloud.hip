@@ -12,7 +12,6 @@
 // physmodel.h:153 is a per-lane predicate.  Body poses are expanded once per block into an LDS table (lane b <-> body b).
 // All arithmetic keeps the reference's evaluation order (-ffp-contract=off), so rows are bit-identical to the CPU path.
 #include <limits.h>
-#include <mutex>
 #include "ht_device.hpp"
 #include "ht_launch.hpp"
 #include <string.h>
@@ -238,8 +237,7 @@ __device__ __forceinline__ void closest_chunk(const ht_model_dev &M, const float
 }
 
 // ------------------------------------------------------------------------------------------------- k_cloud_rows
-// mode 0: forcelimit (-1,1) (CloudConstraints as is)     1: FitPointCloud scaling (physmodel.h:347)
-//      2: MultiStepSim scaling (handtrack.h:656,681)     3: UnibodyFit scaling (handtrack.h:461)     4: slowfit scaling (handtrack.h:815-816)
+// mode: how the rows' force limits scale (ht_launch.hpp: ht_cloud_mode)
 // One block per frame, CH points per pass: closest feature as above, then ConvexHitCheck (geometric.h:275-297) of the chosen body, one lane per
 // point with the body's faces read per lane from the LDS copy (the clipping of a segment is sequential in the faces; points are independent).
 #define CR_THREADS 256
@@ -359,10 +357,10 @@ __device__ __forceinline__ void cloud_rows_frame(const ht_model_dev &M, const fl
 		else { position1 = tab_to_local(tr, v - xyz(p) * dot_plane(p, v)); normal = xyz(p); }
 		const float targetdist = dot(tab_to_world(tr, position1) - v, normal);                  // ConstrainAlongDirection physics.h:328-331
 		float fmin = -1.0f, fmax = 1.0f;
-		if (mode == 1) { float k = (rb == 0 || rb == 1 || rb == 2) ? weak_force : 1.0f; fmin = -1.0f * k * microforce; fmax = 1.0f * k * microforce; }
-		else if (mode == 2) { float cloudforce = fmin_std(cf_max_point, cf_max_sum / (float)n); float k = (rb == 0) ? 0.1f : 1.0f; fmin = -cloudforce * k; fmax = cloudforce * k; }
-		else if (mode == 3) { fmin = -1.0f * unibody_force; fmax = 1.0f * unibody_force; }
-		else if (mode == 4) { const float k = (microforce * weak_force) * ((rb == 0) ? cf_max_point : 1.0f); fmin = -1.0f * k; fmax = 1.0f * k; }      // slowfit handtrack.h:815-816: weak_force = step ratio, cf_max_point = wrist factor
+		if (mode == CLOUD_FIT) { float k = (rb == 0 || rb == 1 || rb == 2) ? weak_force : 1.0f; fmin = -1.0f * k * microforce; fmax = 1.0f * k * microforce; }
+		else if (mode == CLOUD_MULTISTEP) { float cloudforce = fmin_std(cf_max_point, cf_max_sum / (float)n); float k = (rb == 0) ? 0.1f : 1.0f; fmin = -cloudforce * k; fmax = cloudforce * k; }
+		else if (mode == CLOUD_UNIBODY) { fmin = -1.0f * unibody_force; fmax = 1.0f * unibody_force; }
+		else if (mode == CLOUD_SLOWFIT) { const float k = (microforce * weak_force) * ((rb == 0) ? cf_max_point : 1.0f); fmin = -1.0f * k; fmax = 1.0f * k; }      // slowfit handtrack.h:815-816: weak_force = step ratio, cf_max_point = wrist factor
 		if (rec.scratch)      // the solver's record of this row (ht_quad.hpp), at the point's index of the frame's scratch slot, and the row's body beside it
 		{
 			const v4 q = V4(wq[rb][0], wq[rb][1], wq[rb][2], wq[rb][3]);
@@ -552,7 +550,7 @@ template <bool EXACT> __device__ __forceinline__ void reset_frame(const ht_model
 	for (int it = 0; it < n_unibody; it++)
 	{
 		// ---- the cloud rows of every 4th point from the camera's origin, UnibodyFit's force limits (handtrack.h:457-461)
-		cloud_rows_frame(M, state, pts, cams, 4, 1, 3, 0.0f, 0.0f, 0.0f, 0.0f, unibody_force, rows, nrows, none, dbg, b, n, 0, 1, tab, L, nullptr, nullptr);
+		cloud_rows_frame(M, state, pts, cams, 4, 1, CLOUD_UNIBODY, 0.0f, 0.0f, 0.0f, 0.0f, unibody_force, rows, nrows, none, dbg, b, n, 0, 1, tab, L, nullptr, nullptr);
 		__syncthreads();
 		// ---- UnibodyFit's solve: all rows act on one proxy body, so the Gauss-Seidel chain is sequential: a wave takes it sixteen rows at a time (ht_quad.hpp: the rows' velocity
 		//      terms side by side, the impulses resolved in row order through pre-computed couplings); a cloud too large for that, one quad row by row
@@ -942,14 +940,14 @@ void ht_launch_chamber_planes(const ht_model_dev &M, const float4 *pts, const in
 // ------------------------------------------------------------------------------------------------- launchers
 // `rec`: instead of the 16-float rows, write each row's solver record into the frames' scratch slots and the rows' bodies into rec->body (k_solve then only
 // lists them per body); null: the reference-layout rows (stage calls, UnibodyFit)
-void ht_launch_cloud_rows(const ht_model_dev &M, const float *state, const float4 *pts, const int *npts, const float *cams, const int *active_flag, int stride, int use_cam_origin, int mode,
-                          const ht_params &par, float *rows, int *nrows, int B, hipStream_t s, float sf_ratio, float sf_wrist, const cloud_records *rec, const plane_rows *planes)
+void ht_launch_cloud_rows(const ht_model_dev &M, const float *state, const float4 *pts, const int *npts, const float *cams, const int *active_flag, const cloud_take &take, const cloud_limits &lim,
+                          float *rows, int *nrows, int B, hipStream_t s, const cloud_records *rec, const plane_rows *planes)
 {
 	const cloud_records none = { nullptr, 0, nullptr, 0.0f };
 	const plane_rows no_planes = { nullptr, nullptr, 0.0f, nullptr, nullptr };
 	// blocks per frame: a frame's passes of CH points are independent, so while the batch leaves CUs idle they are spread over up to `split` blocks
 	// (each pays the prologue -- body table, 25 KB of planes into LDS -- again, which is why a large batch keeps one block per frame)
-	const int pts_max = M.pts_bound > 0 ? M.pts_bound : M.pts_cap, passes = ((pts_max + stride - 1) / stride + CH - 1) / CH;
+	const int pts_max = M.pts_bound > 0 ? M.pts_bound : M.pts_cap, passes = ((pts_max + take.stride - 1) / take.stride + CH - 1) / CH;
 	int split = B <= 2048 ? 2 : 1;
 #ifdef HT_TUNING
 	if (const char *e = getenv("HT_CLOUD_SPLIT")) split = atoi(e);
@@ -957,8 +955,8 @@ void ht_launch_cloud_rows(const ht_model_dev &M, const float *state, const float
 	if (split > passes) split = passes;
 	if (split < 1) split = 1;
 	// `planes`: the frames' boundary-plane rows (k_chamber's) by one more block per frame, behind the cloud-row blocks in dispatch order
-	hipLaunchKernelGGL(k_cloud_rows, dim3(B, split + (planes ? 1 : 0)), dim3(CR_THREADS), ((size_t)M.plane_off[M.nb] + 16) * sizeof(float4), s, M, state, pts, npts, cams, active_flag, stride, use_cam_origin, mode, par.microforce,
-	                   mode == 4 ? sf_ratio : par.physics_weak_force, mode == 4 ? sf_wrist : par.cloudforce_max_point, par.cloudforce_max_sum, par.unibody_force, rows, nrows, rec ? *rec : none, planes ? *planes : no_planes, ht_tuning_flags());
+	hipLaunchKernelGGL(k_cloud_rows, dim3(B, split + (planes ? 1 : 0)), dim3(CR_THREADS), ((size_t)M.plane_off[M.nb] + 16) * sizeof(float4), s, M, state, pts, npts, cams, active_flag, take.stride, take.cam_origin, take.mode,
+	                   lim.microforce, lim.weak_force, lim.cf_max_point, lim.cf_max_sum, lim.unibody_force, rows, nrows, rec ? *rec : none, planes ? *planes : no_planes, ht_tuning_flags());
 }
 // the full-reset branch for the frames list[0 .. *nlist) (all B frames with list == nullptr); many_frames: the caller expects more of them than the device has CUs
 // (the two-blocks-per-CU build)
@@ -968,18 +966,7 @@ void ht_launch_reset(const ht_model_dev &M, const ht_physics_dev &ph, float *sta
 	const size_t cloud = (((size_t)M.plane_off[M.nb] + 16 + 3) & ~(size_t)3) * sizeof(float4) + ((sizeof(closest_lds) + 15) & ~(size_t)15) + HT_MAXNB * BT * sizeof(float);
 	const size_t solve = (size_t)(UB_LDS_ROWS + QUAD_CHAIN_SLACK) * (CREC * sizeof(float) + sizeof(float) + sizeof(unsigned short));
 	const size_t dyn = cloud > solve ? cloud : solve;
-	static size_t attr_set[64];               // per device: the attribute belongs to the device's copy of the code object
-	static std::mutex attr_lock;              // contexts of several host threads may launch at the same time: the limit is raised before anybody launches with it
-	int dev = 0; (void)hipGetDevice(&dev); dev &= 63;
-	std::unique_lock<std::mutex> lk(attr_lock);
-	if (attr_set[dev] < dyn)
-	{
-		(void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_reset<1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn);
-		(void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_reset<2>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn);
-		(void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_reset<2, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn);
-		attr_set[dev] = dyn;
-	}
-	lk.unlock();
+	static ht_lds_limit limit; limit.raise(dyn, k_reset<1>, k_reset<2>, k_reset<2, true>);
 	const bool two = !list || many_frames;
 	const int grid = B < (two ? 2 : 1) * n_cu ? B : (two ? 2 : 1) * n_cu;
 	if (exact)      // tests only (ht_debug_solver_build 5)

@@ -11,6 +11,7 @@
 #include <stdint.h>
 #include "../../include/ht_mi355x.h"
 #include <stdlib.h>
+#include <mutex>
 #include "ht_math.hpp"
 
 // Every extern "C" entry point that touches the device makes its context's GPU current for the duration of the call and restores the caller's
@@ -59,6 +60,22 @@ static inline bool ht_tuning_env(const char *name)
 	(void)name; return false;
 #endif
 }
+
+// The dynamic-LDS limit of a family of kernels (every instantiation a launcher may pick), raised on the current device when a launch asks for more than the device's copy of
+// the code object has been given so far.  One per launcher, static: contexts of several host threads (one per GPU) launch at the same time, and the limit is up before anybody
+// launches with it.  A device beyond the table's 64 gets the attribute set at every launch.
+struct ht_lds_limit
+{
+	std::mutex lock; size_t have[64] = {};
+	template <class... K> void raise(size_t bytes, K... kernels)
+	{
+		int dev = -1; (void)hipGetDevice(&dev); const bool listed = dev >= 0 && dev < 64;
+		std::lock_guard<std::mutex> lk(lock);
+		if (listed && have[dev] >= bytes) return;
+		for (const void *k : { reinterpret_cast<const void *>(kernels)... }) (void)hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+		if (listed) have[dev] = bytes;
+	}
+};
 
 #define HT_MAXPTS 4096          // default point capacity of a context (ht_model_dev::pts_cap): every point of a 64x64 tile, every 4th of a 128x128 frame; a context grows
                                 // it when a call brings larger frames (ht_reserve_points)

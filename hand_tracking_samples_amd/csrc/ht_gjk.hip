@@ -30,9 +30,9 @@
 // A second exact shortcut: dot(w,v)/|v| is a lower bound of the distance between the shapes and the separation the reference
 // finally reports is never below it, so once the bound exceeds the contact cut-off the pair cannot produce a contact.
 #include <stdlib.h>
-#include <mutex>
 #include "ht_device.hpp"
 #include "ht_launch.hpp"
+#include "ht_rank.hpp"
 
 extern __shared__ __attribute__((aligned(16))) float4 g_sm[];      // [0, nvert): collision vertices of all bodies; then per-wave areas
 
@@ -1223,15 +1223,29 @@ __global__ __launch_bounds__(64 * CO_NW) void k_contacts_coop(ht_model_dev M, co
 
 size_t ht_contacts_workspace_bytes(int B) { (void)B; return 16; }      // the polytope mesh lives in LDS; the workspace holds the capacity counters (polytope runs cut short, contacts dropped, k_solve's angular overflow)
 
-// frames per block of the cooperative kernel for a batch of B frames (as many as the LDS holds beside the padded vertex copy, the scan list and the waves' polytope areas:
-// 4 for the 17-bone hand); 0 = the model does not fit it
-int ht_contacts_frames_per_block(const ht_model_dev &M, int B)
+// The LDS plan of the cooperative kernel (ht_launch.hpp: coop_plan): beside the padded vertex copy, the scan list and the waves' polytope areas a block takes as many frames as
+// 160 KB hold, CO_MAXF at most (4 for the 17-bone hand) -- or, few_frames: a masked launch that only a handful of frames take (the reset frames' own first step), a frame per
+// block with all waves on it, while the batch is small enough that its empty blocks, each of which still asks for a whole CU's LDS, cost less than that gains (1024 frames:
+// four rounds of them)
+coop_plan ht_contacts_coop_plan(const ht_model_dev &M, int B, bool few_frames)
 {
 	const size_t fixed = (size_t)M.cvert_off[M.nb] * sizeof(float4) + sizeof(co_block) + (size_t)CO_OWN * 64 * 2 * (sizeof(co_req) + sizeof(int)) + CO_EPAQ * sizeof(co_job) + CO_NW * gjk_wave_stride();
-	if (fixed + sizeof(co_frame) > 160 * 1024) return 0;
-	int nfr = CO_MAXF;
-	while (nfr > 1 && fixed + nfr * sizeof(co_frame) > 160 * 1024) nfr--;
-	return B < nfr ? B : nfr;
+	coop_plan p = { 0, 0, few_frames && B <= 2048 };
+	if (fixed + sizeof(co_frame) > 160 * 1024) return p;
+	p.nfr = p.few ? 1 : CO_MAXF;
+	while (p.nfr > 1 && fixed + p.nfr * sizeof(co_frame) > 160 * 1024) p.nfr--;
+	if (B < p.nfr) p.nfr = B; p.lds = fixed + p.nfr * sizeof(co_frame);
+	return p;
+}
+// Which organisation: the cooperative kernel (a CU per block: 156 KB of LDS, 242 VGPRs) whenever a frame of the model fits its LDS beside the padded vertex
+// copy.  Whole steps on one device, cooperative against lane-per-pair: 1536 frames 7.57 against 7.64 ms, 2048 frames 8.46 / 8.56, 4096 frames 14.74 / 14.96,
+// 8192 frames 27.00 / 27.57 (tools/exp_coop_max.sh; until the polytope and the frame-to-block assignment were reworked in round 3 the lane-per-pair kernel won
+// above ~1100 frames because its smaller blocks run beside the cloud-row kernel).  force_kernel (ht_debug_contact_kernel): 1 cooperative, 2 lane-per-pair.
+bool ht_contacts_coop(const ht_model_dev &M, int B, int force_kernel, bool beside_cloud_rows)
+{
+	static const int coop_max = ht_tuning_int("HT_CONTACTS_COOP_MAX", 1 << 30), main_lanes = ht_tuning_int("HT_CONTACTS_MAIN_LANES", 0);      // read once, when the first launch gets here (C++11 statics: thread-safe)
+	const bool fits = ht_contacts_coop_plan(M, B).nfr > 0;
+	return force_kernel == 1 ? fits : (force_kernel != 2 && fits && B <= coop_max && !(beside_cloud_rows && main_lanes));
 }
 // The frames of a launch dealt to the blocks by what they took in the same launch of the PREVIOUS update (poses move little between updates).  A block's time is its
 // scan rounds (latency: about the same for one frame's runs as for four frames') plus, when any of its frames has a run whose simplex encloses the origin, its polytope
@@ -1241,33 +1255,30 @@ int ht_contacts_frames_per_block(const ht_model_dev &M, int B)
 // when the batch takes several rounds per CU (the sum of the blocks' times counts, and the long blocks start first), fewer when every block has a CU of its own (the
 // slowest block is the launch's time, and a block of four such frames would be it).
 // work = candidates + 2 x patches | polytope runs << 16 (k_contacts_coop); order[slot * blocks + block] = frame, B = no frame.  Ranks by counting, the keys in LDS
-// (work / order: [slots][stride]).  Grid (launch slot of an update, segment of 4096 frames, part): every block stages its segment's keys and counts the frames with
+// (work / order: [slots][stride]).  Grid (launch slot of an update, segment of HT_RANK_SEG frames, part): every block stages its segment's keys and counts the frames with
 // runs itself, then ranks CO_ORDER_PART of the segment's frames, a frame per thread, and writes their places -- and "no frame" to the places of its share that stay
 // empty, which follow from the counts alone (the test ahead of the ranking loop), so every place of the table has exactly one writer per launch and no block clears what another fills.
 // Runs beside the CNN at the head of an update, ahead of the batch's first contact launch, which is the first to read a table.
-#define CO_ORDER_SEG 4096      // frames a segment of k_contact_order holds (ranks by counting: quadratic); a larger batch is dealt segment by segment, each over its own blocks
 #define CO_ORDER_PART 256      // frames a block of it ranks = its threads
 __global__ __launch_bounds__(CO_ORDER_PART) void k_contact_order(const int *__restrict__ work, int *__restrict__ order, int Ball, int nfr, int stride, unsigned slots, int epb)
 {
 	extern __shared__ int ko_w[];
 	__shared__ int ko_ne;
 	if (!((slots >> blockIdx.x) & 1u)) return;
-	const int seg = (CO_ORDER_SEG / nfr) * nfr, f0 = blockIdx.y * seg, B = Ball - f0 < seg ? Ball - f0 : seg;      // this segment's frames: [f0, f0 + B)
+	const int seg = (HT_RANK_SEG / nfr) * nfr, f0 = blockIdx.y * seg, B = Ball - f0 < seg ? Ball - f0 : seg;      // this segment's frames: [f0, f0 + B)
 	const int blocks_all = (Ball + nfr - 1) / nfr, b0 = f0 / nfr;
-	const int blocks = (B + nfr - 1) / nfr, B4 = (B + 3) & ~3, places = blocks * nfr;
+	const int blocks = (B + nfr - 1) / nfr, places = blocks * nfr;
 	if ((int)blockIdx.z * CO_ORDER_PART >= places) return;      // a short last segment: the grid's parts follow the longest
-	const int *w = work + (size_t)blockIdx.x * stride + f0;
 	int *o = order + (size_t)blockIdx.x * stride;
 	if (threadIdx.x == 0) ko_ne = 0;
 	__syncthreads();
 	int mine = 0;
-	for (int i = threadIdx.x; i < B4; i += CO_ORDER_PART)
+	rank_stage(ko_w, work + (size_t)blockIdx.x * stride + f0, B, CO_ORDER_PART, [&](int v)      // the key: polytope runs (1023 at most) above the candidate pairs
 	{
-		const int v = i < B ? w[i] : -1;
 		const int runs = v < 0 ? 0 : (v >> 16), pairs = v < 0 ? 0 : (v & 0xffff);
-		ko_w[i] = v < 0 ? -1 : ((runs > 1023 ? 1023 : runs) << 20) | pairs;
 		mine += runs > 0 ? 1 : 0;
-	}
+		return v < 0 ? -1 : ((runs > 1023 ? 1023 : runs) << 20) | pairs;
+	});
 	if (mine) atomicAdd(&ko_ne, mine);
 	__syncthreads();
 	const int ne = ko_ne, ng = B - ne;                      // frames with polytope runs (the first ne places of the sorted order) and without
@@ -1287,13 +1298,7 @@ __global__ __launch_bounds__(CO_ORDER_PART) void k_contact_order(const int *__re
 		if (round * nb_ + ((round & 1) ? nb_ - 1 - p : p) >= count) o[round * blocks_all + b0 + col] = Ball;
 	}
 	if (i >= B) return;
-	const int wi = ko_w[i];
-	int rank = 0;
-	for (int j = 0; j < B4; j += 4)
-	{
-		const int4 k = *reinterpret_cast<const int4 *>(ko_w + j);
-		rank += ((k.x > wi || (k.x == wi && j < i)) ? 1 : 0) + ((k.y > wi || (k.y == wi && j + 1 < i)) ? 1 : 0) + ((k.z > wi || (k.z == wi && j + 2 < i)) ? 1 : 0) + ((k.w > wi || (k.w == wi && j + 3 < i)) ? 1 : 0);
-	}
+	const int rank = rank_desc(RANK_KEYS4(ko_w), ko_w[i], i, B);
 	int nb_, base, r;
 	if (rank < ne) { nb_ = neb; base = 0; r = rank; }                                        // place r of the first kind's grid (neb wide, round by round)
 	else if (rank - ne < nheavy) { nb_ = ngb; base = neb; r = rank - ne; }                   // place r of the second kind's grid
@@ -1303,7 +1308,7 @@ __global__ __launch_bounds__(CO_ORDER_PART) void k_contact_order(const int *__re
 }
 void ht_launch_contact_order(const int *work, int *order, int B, int nfr, int stride, unsigned slots, int nslots, int epb, hipStream_t s)
 {
-	const int seg = (CO_ORDER_SEG / nfr) * nfr, nseg = (B + seg - 1) / seg, first = B < seg ? B : seg, places = (first + nfr - 1) / nfr * nfr;
+	const int seg = (HT_RANK_SEG / nfr) * nfr, nseg = (B + seg - 1) / seg, first = B < seg ? B : seg, places = (first + nfr - 1) / nfr * nfr;
 	hipLaunchKernelGGL(k_contact_order, dim3(nslots, nseg, (places + CO_ORDER_PART - 1) / CO_ORDER_PART), dim3(CO_ORDER_PART), (size_t)((first + 3) & ~3) * sizeof(int), s, work, order, B, nfr, stride, slots, epb);
 }
 void ht_launch_contacts(const ht_model_dev &M, const float *state, float driftmax, float jiggle_sin, const int *active_flag, void *epa_ws, float *contacts, int *ncontacts, int B, hipStream_t s, bool beside_cloud_rows, int force_kernel, int few_frames,
@@ -1311,43 +1316,12 @@ void ht_launch_contacts(const ht_model_dev &M, const float *state, float driftma
 {
 	int *caps = reinterpret_cast<int *>(epa_ws);
 	const int dbg = ht_tuning_flags();
-	static bool attr_set[64];                 // per device: the attribute belongs to the device's copy of the code object
-	static std::mutex attr_lock;              // contexts of several host threads (one per GPU) may launch at the same time
-	int dev = 0; (void)hipGetDevice(&dev); dev &= 63;
-	std::unique_lock<std::mutex> lk(attr_lock);
-	if (!attr_set[dev])
+	static ht_lds_limit limit; limit.raise(160 * 1024, k_contacts<1>, k_contacts<2>, k_contacts_coop);
+	if (ht_contacts_coop(M, B, force_kernel, beside_cloud_rows))
 	{
-		(void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_contacts<1>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-		(void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_contacts<2>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-		(void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_contacts_coop), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-		attr_set[dev] = true;
-	}
-	lk.unlock();
-	// Which organisation: the cooperative kernel (a CU per block: 156 KB of LDS, 242 VGPRs) whenever a frame of the model fits its LDS beside the padded vertex
-	// copy.  Whole steps on one device, cooperative against lane-per-pair: 1536 frames 7.57 against 7.64 ms, 2048 frames 8.46 / 8.56, 4096 frames 14.74 / 14.96,
-	// 8192 frames 27.00 / 27.57 (tools/exp_coop_max.sh; until the polytope and the frame-to-block assignment were reworked in round 3 the lane-per-pair kernel won
-	// above ~1100 frames because its smaller blocks run beside the cloud-row kernel).  force_kernel (ht_debug_contact_kernel): 1 cooperative, 2 lane-per-pair.
-	static const int coop_max = [] {      // read once, when the first launch gets here (a C++11 static: thread-safe)
-#ifdef HT_TUNING
-		if (const char *e = getenv("HT_CONTACTS_COOP_MAX")) return atoi(e);
-#endif
-		return 1 << 30;
-	}();
-	static const int main_lanes = ht_tuning_int("HT_CONTACTS_MAIN_LANES", 0);
-	const size_t coop_fixed = (size_t)M.cvert_off[M.nb] * sizeof(float4) + sizeof(co_block) + (size_t)CO_OWN * 64 * 2 * (sizeof(co_req) + sizeof(int)) + CO_EPAQ * sizeof(co_job) + CO_NW * gjk_wave_stride();
-	const bool coop_fits = coop_fixed + sizeof(co_frame) <= 160 * 1024;
-	if (force_kernel == 1 ? coop_fits : (force_kernel != 2 && coop_fits && B <= coop_max && !(beside_cloud_rows && main_lanes)))
-	{
-		// as many frames per block as the LDS holds beside the padded vertex copy, the scan list and the waves' polytope areas (4 for the 17-bone hand)
-		const int nvp = M.cvert_off[M.nb];
-		const size_t fixed = (size_t)nvp * sizeof(float4) + sizeof(co_block) + (size_t)CO_OWN * 64 * 2 * (sizeof(co_req) + sizeof(int)) + CO_EPAQ * sizeof(co_job) + CO_NW * gjk_wave_stride();
-		// few_frames: a masked launch that only a handful of frames take (the reset frames' own first step): a block per frame, all waves on it -- while the
-		// batch is small enough that its empty blocks, each of which still asks for a whole CU's LDS, cost less than that gains (1024 frames: four rounds of them)
-		int nfr = few_frames && B <= 2048 ? 1 : CO_MAXF;
-		while (nfr > 1 && fixed + nfr * sizeof(co_frame) > 160 * 1024) nfr--;
-		if (B < nfr) nfr = B;
-		const size_t smem = fixed + nfr * sizeof(co_frame);
-		hipLaunchKernelGGL(k_contacts_coop, dim3((B + nfr - 1) / nfr), dim3(64 * CO_NW), smem, s, M, state, driftmax, jiggle_sin, active_flag, contacts, ncontacts, B, nfr, nvp, dbg, caps, nfr == ht_contacts_frames_per_block(M, B) ? order : nullptr, work_out);
+		const coop_plan p = ht_contacts_coop_plan(M, B, few_frames != 0);
+		hipLaunchKernelGGL(k_contacts_coop, dim3((B + p.nfr - 1) / p.nfr), dim3(64 * CO_NW), p.lds, s, M, state, driftmax, jiggle_sin, active_flag, contacts, ncontacts, B, p.nfr, M.cvert_off[M.nb], dbg, caps,
+		                   p.few ? nullptr : order, work_out);      // the tables deal the frames over the blocks of the whole-batch form
 		return;
 	}
 	const int wpf = M.nb * (M.nb - 1) / 2 > 200 ? 2 : 1;

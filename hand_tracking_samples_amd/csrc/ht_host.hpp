@@ -4,9 +4,34 @@
 #include <string>
 #include <vector>
 #include "ht_device.hpp"
+#include "ht_launch.hpp"
 
 struct ht_comm_state;      // RCCL communicator + communication stream (ht_comm.hip)
 struct ht_prof_entry { std::vector<hipEvent_t> ev; size_t used; float total_ms; int launches; };
+
+// A work history: what every frame took in each launch slot (HT_CONTACT_SLOTS) of the latest update, and the launch tables the current update made from it at its head.
+// Both [HT_CONTACT_SLOTS][stride].  Contact launches keep one (work: k_contacts_coop, tables: k_contact_order) and the solves of a batch of several rounds per CU another
+// (k_solve's cost, k_rank_desc); which launches take part is their users' rule (ht_solver_api.hip: launch_contacts, solve_step).
+struct ht_history
+{
+	int *work = nullptr, *order = nullptr; int stride = 0, B = 0; unsigned written = 0, published = 0;      // the slots whose work the latest update wrote, for B frames; the slots whose table the current update may use
+	struct rows { int *work; const int *order; };
+	static int stride_for(int B) { return B + 8; }
+	// The head of an update of B_ frames.  `on`: this update's launches take tables; rank(slots) then makes them, when the latest update wrote any for the same B_
+	template <class F> void begin(int B_, bool on, F rank)
+	{
+		published = 0;
+		if (on && work && stride_for(B_) <= stride && B == B_ && written) { rank(written); published = written; }
+		written = 0; B = B_;
+	}
+	// A launch of B_ frames in `slot`: where it leaves its work, and its table if the head of the update published one.  Neither for a slot out of range or another B_
+	rows take(int slot, int B_)
+	{
+		if (slot < 0 || slot >= HT_CONTACT_SLOTS || !work || B_ != B) return rows{ nullptr, nullptr };
+		written |= 1u << slot;
+		return rows{ work + (size_t)slot * stride, (published >> slot) & 1u ? order + (size_t)slot * stride : nullptr };
+	}
+};
 
 struct ht_ctx
 {
@@ -65,11 +90,9 @@ struct ht_ctx
 	int solve_tables = 0;                                       // 1 (ht_debug_solve_tables; tools/exp_tables.sh): k_solve_prep makes every solve's tables beside the contact kernel.  Measured slower in round 6 (profiles/r06_notes.md section 1): off
 	int *d_accepted = nullptr;
 	float *d_contacts = nullptr; int *d_ncontacts = nullptr;    // [B][HT_MAXCONTACT][HT_CONTACT]
-	bool tables_out = false;        // this update's launch tables (d_corder, d_sorder) are still being made on side stream 0: until that stream is joined only launches ON it may read them (ht_solver_api.hip: update_beside_net)
-	int *d_cwork = nullptr, *d_corder = nullptr;                  // [HT_CONTACT_SLOTS][cstride]: what every frame cost in every contact launch of the latest update; the assignment of frames to blocks made from it for the current one (ht_gjk.hip: k_contact_order)
+	bool tables_out = false;        // this update's launch tables (contact_hist.order, solve_hist.order) are still being made on side stream 0: until that stream is joined only launches ON it may read them (ht_solver_api.hip: update_beside_net)
+	ht_history contact_hist, solve_hist;
 	int *d_porder = nullptr;      // [B]: the frames by their point counts (ht_model_dev::frame_order inside an update of a batch of several rounds per CU)
-	int *d_swork = nullptr, *d_sorder = nullptr; unsigned swork_mask = 0, sorder_mask = 0; int swork_B = 0;      // the same for the solves of a batch that takes several rounds per CU: what every frame's solve took, the launch order (longest first)
-	int cstride = 0, cwork_B = 0; unsigned cwork_mask = 0, corder_mask = 0;      // slots whose work the latest update wrote (for cwork_B frames) / whose order the current update may use
 	unsigned char *d_epa_ws = nullptr;                           // expanding-polytope workspace, one per (frame, wave)
 	float *d_scratch = nullptr;                                  // solver row records [B][pts_cap + 5*nb + 32][20] (ht_quad.hpp)
 	float *d_poses_out = nullptr, *d_start = nullptr;
@@ -113,6 +136,14 @@ template <class T, class C> static inline int dev_grow(ht_ctx *ctx, T **p, C *ca
 	if (r) return r;
 	drop_alloc(ctx, *p);
 	*p = q; *cap = (C)want;
+	return HT_OK;
+}
+static inline int ht_history_alloc(ht_ctx *ctx, ht_history &h)      // for the context's capacity; the works zeroed: a slot no launch has written yet ranks equal keys, not garbage
+{
+	h.stride = ht_history::stride_for(ctx->B);
+	const size_t n = (size_t)HT_CONTACT_SLOTS * h.stride;
+	if (int r = dev_alloc(ctx, &h.work, n)) return r; else if ((r = dev_alloc(ctx, &h.order, n))) return r;
+	HIPCHK(ctx, hipMemset(h.work, 0, n * sizeof(int)));
 	return HT_OK;
 }
 // the end of a synchronous entry point: wait for the stream, then report what its launches left behind

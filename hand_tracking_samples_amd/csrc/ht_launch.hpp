@@ -55,8 +55,21 @@ void ht_launch_solve_prep(const ht_model_dev &M, const ht_physics_dev &ph, const
 struct cloud_records { float *scratch; int stride; unsigned char *body; float dt; };
 // the boundary-plane rows a main-thread pass takes from the same launch (k_chamber's rows by extra blocks of k_cloud_rows): planes / on as ht_launch_chamber_planes left them, rows [B][5 * nb][HT_ROW], nch [B]
 struct plane_rows { const float *planes; const int *on; float maxforce; float *rows; int *nch; };
-void ht_launch_cloud_rows(const ht_model_dev &M, const float *state, const float4 *pts, const int *npts, const float *cams, const int *active_flag, int stride, int use_cam_origin, int mode,
-                          const ht_params &par, float *rows, int *nrows, int B, hipStream_t s, float sf_ratio = 0.0f, float sf_wrist = 0.0f, const cloud_records *rec = nullptr, const plane_rows *planes = nullptr);
+// Which points of a frame's cloud k_cloud_rows takes (every stride-th), where their rays start (cam_origin: the camera's position; 0: the origin) and how the rows' force limits scale
+//   CLOUD_UNIT: forcelimit (-1, 1), CloudConstraints as is     CLOUD_FIT: FitPointCloud (physmodel.h:347)     CLOUD_MULTISTEP: MultiStepSim (handtrack.h:656, 681)
+//   CLOUD_UNIBODY: UnibodyFit (handtrack.h:461)                 CLOUD_SLOWFIT: slowfit (handtrack.h:815-816)
+enum ht_cloud_mode { CLOUD_UNIT = 0, CLOUD_FIT = 1, CLOUD_MULTISTEP = 2, CLOUD_UNIBODY = 3, CLOUD_SLOWFIT = 4 };
+struct cloud_take { int stride, cam_origin, mode; };
+// The kernel's five force-limit parameters.  ht_cloud_limits: from the tracker's parameters -- except that slowfit's scaling has no use for weak_force / cf_max_point and
+// sends its step ratio and wrist factor in their places
+struct cloud_limits { float microforce, weak_force, cf_max_point, cf_max_sum, unibody_force; };
+static inline cloud_limits ht_cloud_limits(const ht_params &par, int mode, float sf_ratio = 0.0f, float sf_wrist = 0.0f)
+{
+	const bool sf = mode == CLOUD_SLOWFIT;
+	return cloud_limits{ par.microforce, sf ? sf_ratio : par.physics_weak_force, sf ? sf_wrist : par.cloudforce_max_point, par.cloudforce_max_sum, par.unibody_force };
+}
+void ht_launch_cloud_rows(const ht_model_dev &M, const float *state, const float4 *pts, const int *npts, const float *cams, const int *active_flag, const cloud_take &take, const cloud_limits &lim,
+                          float *rows, int *nrows, int B, hipStream_t s, const cloud_records *rec = nullptr, const plane_rows *planes = nullptr);
 // What follows a FitError in HandTracker::update and needs nothing but that frame's error rides on the kernel's last thread instead of a launch of its own:
 // mode 1 = the full-reset decision (handtrack.h:706: flags[b] = angles_only || error > threshold), mode 2 = the accept step (handtrack.h:713-731).
 struct ht_fit_after
@@ -68,12 +81,16 @@ struct ht_fit_after
 void ht_launch_fit_error(const ht_model_dev &M, const float *state, const float4 *pts, const int *npts, const uint16_t *depth, const float *cams, int w, int h, float scale, float *err, int B, hipStream_t s, const ht_fit_after *after = nullptr);
 void ht_launch_chamber_planes(const ht_model_dev &M, const float4 *pts, const int *npts, int min_point_num, int enabled, float *planes, int *on, int B, hipStream_t s);      // the five containing planes [B][5][4], on [B] = the frame has them: once per update
 void ht_launch_chamber(const ht_model_dev &M, const float *state, const float *planes, const int *planes_on, float maxforce, float *rows, int *nch, int B, hipStream_t s);      // their rows, pass by pass, from planes / planes_on of ht_launch_chamber_planes (k_solve_prep makes them itself with the solve tables)
+// The cooperative contact kernel for a model and a batch: frames a block takes (0: a frame of the model does not fit the kernel), the dynamic LDS that needs, and whether that
+// is the few-frames form (a frame per block) a launch on a handful of frames may ask for.  ht_contacts_coop: whether a launch takes that kernel or the lane-per-pair one
+struct coop_plan { int nfr; size_t lds; bool few; };
+coop_plan ht_contacts_coop_plan(const ht_model_dev &M, int B, bool few_frames = false);
+bool ht_contacts_coop(const ht_model_dev &M, int B, int force_kernel, bool beside_cloud_rows);
 void ht_launch_contacts(const ht_model_dev &M, const float *state, float driftmax, float jiggle_sin, const int *active_flag, void *epa_ws, float *contacts, int *ncontacts, int B, hipStream_t s, bool beside_cloud_rows = false, int force_kernel = 0, int few_frames = 0,
-                        const int *order = nullptr, int *work_out = nullptr);      // order / work_out (cooperative kernel only, both may be null): the frame of every (slot, block) as k_contact_order dealt them; where every live frame leaves what it cost
-int ht_contacts_frames_per_block(const ht_model_dev &M, int B);
+                        const int *order = nullptr, int *work_out = nullptr);      // order / work_out (cooperative kernel only, both may be null): the frame of every (slot, block) as k_contact_order dealt them for the plan's whole-batch form; where every live frame leaves what it cost
 #define HT_CONTACT_SLOTS 16      // unmasked contact launches of an update that keep a work history: MultiStepSim step st -> slot st (< 8), main-thread pass i -> slot 8 + i
 void ht_launch_order_by_points(const int *npts, int *order, int B, hipStream_t s);      // order = the frames by their point counts, most first (ht_model_dev::frame_order)
-void ht_launch_rank_desc(const int *work, int *order, int B, int stride, unsigned slots, int nslots, hipStream_t s);      // order[slot][.] = the frames of every 4096-frame segment by work[slot][.], largest first
+void ht_launch_rank_desc(const int *work, int *order, int B, int stride, unsigned slots, int nslots, hipStream_t s);      // order[slot][.] = the frames of every segment (ht_rank.hpp: HT_RANK_SEG) by work[slot][.], largest first
 void ht_launch_contact_order(const int *work, int *order, int B, int nfr, int stride, unsigned slots, int nslots, int epb, hipStream_t s);
 size_t ht_contacts_workspace_bytes(int B);
 void ht_launch_solve(const ht_model_dev &M, const ht_physics_dev &ph, const solve_args &a, int B, hipStream_t s);

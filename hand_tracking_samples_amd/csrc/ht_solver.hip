@@ -30,6 +30,7 @@
 // row instead of ~80 and the dependent chain through the momenta is 8-11 operations.  Same rows, same order, same clamps as the reference;
 // another association order of the floating-point operations: see ht_quad.hpp and DESIGN.md (Numerics) for the measured effect.
 #include "ht_solve_shared.hpp"
+#include "ht_rank.hpp"
 
 template <int NGRP_, int NSUM_, int NANG_, int NIDX_, int AS_ = 2, int NCG_ = 0> struct lds_t
 {
@@ -1531,36 +1532,26 @@ __global__ __launch_bounds__(64, 2) void k_solve(ht_model_dev M, ht_physics_dev 
 	if (a.cost_out && lane == 0) a.cost_out[b] = (int)((clock64() - t_cost) >> 4);      // what the frame took: the next update's launch order (ht_launch_rank_desc)
 }
 
-// order[slot][f0 + r] = the frame of segment [f0, f0 + 4096) with the r-th largest work[slot][.] (ties by index): ranks by counting, the works in LDS.  Grid (slot whose
+// order[slot][f0 + r] = the frame of segment [f0, f0 + HT_RANK_SEG) with the r-th largest work[slot][.] (ties by index): ranks by counting, the works in LDS.  Grid (slot whose
 // bit is set in `slots`, segment, part): every block stages the whole segment's works (16 KB at most, from the L2 after the first block) and ranks RANK_PART of its
 // frames, a frame per thread, so the quadratic count spreads over the chip instead of one CU; a place has one writer, whichever block it sits in.
 // For launches whose blocks outnumber the resident ones several times: taken in this order the launch ends on short frames.
 #define RANK_PART 256      // frames a block of k_rank_desc ranks = its threads
 __global__ __launch_bounds__(RANK_PART) void k_rank_desc(const int *__restrict__ work, int *__restrict__ order, int Ball, int stride, unsigned slots)
 {
-	__shared__ int rk_w[4096];
+	__shared__ int rk_w[HT_RANK_SEG];
 	if (!((slots >> blockIdx.x) & 1u)) return;
-	const int f0 = blockIdx.y * 4096, B = Ball - f0 < 4096 ? Ball - f0 : 4096, B4 = (B + 3) & ~3;
+	const int f0 = blockIdx.y * HT_RANK_SEG, B = Ball - f0 < HT_RANK_SEG ? Ball - f0 : HT_RANK_SEG;
 	if ((int)blockIdx.z * RANK_PART >= B) return;      // a short last segment: the grid's parts follow the longest
-	const int *w = work + (size_t)blockIdx.x * stride + f0;
-	int *o = order + (size_t)blockIdx.x * stride + f0;
-	for (int i = threadIdx.x; i < B4; i += RANK_PART) rk_w[i] = i < B ? w[i] : -1;
+	rank_stage(rk_w, work + (size_t)blockIdx.x * stride + f0, B, RANK_PART, [](int v) { return v; });
 	__syncthreads();
 	const int i = blockIdx.z * RANK_PART + threadIdx.x;
-	if (i >= B) return;
-	const int wi = rk_w[i];
-	int rank = 0;
-	for (int j = 0; j < B4; j += 4)
-	{
-		const int4 k = *reinterpret_cast<const int4 *>(rk_w + j);
-		rank += ((k.x > wi || (k.x == wi && j < i)) ? 1 : 0) + ((k.y > wi || (k.y == wi && j + 1 < i)) ? 1 : 0) + ((k.z > wi || (k.z == wi && j + 2 < i)) ? 1 : 0) + ((k.w > wi || (k.w == wi && j + 3 < i)) ? 1 : 0);
-	}
-	o[rank] = f0 + i;
+	if (i < B) order[(size_t)blockIdx.x * stride + f0 + rank_desc(RANK_KEYS4(rk_w), rk_w[i], i, B)] = f0 + i;
 }
 void ht_launch_rank_desc(const int *work, int *order, int B, int stride, unsigned slots, int nslots, hipStream_t s)
 {
-	const int seg = B < 4096 ? B : 4096;
-	hipLaunchKernelGGL(k_rank_desc, dim3(nslots, (B + 4095) / 4096, (seg + RANK_PART - 1) / RANK_PART), dim3(RANK_PART), 0, s, work, order, B, stride, slots);
+	const int seg = B < HT_RANK_SEG ? B : HT_RANK_SEG;
+	hipLaunchKernelGGL(k_rank_desc, dim3(nslots, (B + HT_RANK_SEG - 1) / HT_RANK_SEG, (seg + RANK_PART - 1) / RANK_PART), dim3(RANK_PART), 0, s, work, order, B, stride, slots);
 }
 
 #define SOLVE_ONLY_NCG 1440      // floats of single-body-row couplings the build for 1024 frames keeps in LDS: what is left of a quarter of a CU's 160 KB (144 blocks of four rows)

@@ -16,6 +16,8 @@ static int dev_alloc_points(ht_ctx *ctx)      // the second cloud of a context t
 	const int r = dev_alloc(ctx, &ctx->d_ptsv, (size_t)ctx->B * ctx->model.pts_cap);
 	return r || ctx->d_nptsv ? r : dev_alloc(ctx, &ctx->d_nptsv, (size_t)ctx->B);
 }
+static const cloud_take step_take = { /* stride */ 4, /* cam_origin */ 1, CLOUD_MULTISTEP };      // MultiStepSim: every 4th point, rays from the camera (handtrack.h:656, 681)
+static cloud_take fit_take(int mode) { const cloud_take t = { /* stride */ 1, /* cam_origin */ 0, mode }; return t; }      // FitPointCloud's callers: every point, rays from the origin
 static cloud_records cloud_rec(ht_ctx *ctx) { cloud_records r = { ctx->d_scratch, scratch_stride(ctx), ctx->d_rowbody, ctx->phys.deltaT }; return r; }
 // the exact-order instantiation of the solver (ht_debug_solver_build 5, tests only) takes the cloud rows in the reference's layout (ctx->d_rows) instead of records
 static bool exact_solver(const ht_ctx *ctx) { return ctx->solver_build == 5 || ctx->solver_build == 8; }      // 8: the same sweeps with the product's forked launch sequence (5 takes the kernels in order on one stream)
@@ -48,10 +50,10 @@ static step_mix mix_of_step(const ht_params &p, int st)
 static step_mix mix_of_pass() { step_mix m = { false, false, true, true, 0.0f, 0, 0 }; return m; }
 static int step_slot(int st) { return st < 8 ? st : -1; }      // the launches of an update that keep a history, a contact launch its work and a solve its cost (HT_CONTACT_SLOTS): MultiStepSim step st -> st,
 static int pass_slot(int pass) { return pass >= 0 && pass < 8 ? 8 + pass : -1; }      // main-thread pass i -> 8 + i; -1: none
-// Solves of an update that keep a history, for batches that take several rounds
-// per CU: k_solve notes what every frame took, the next update's launch of the same slot takes the frames longest first (contact_orders ranks them beside the net), so
-// that the launch ends on short frames instead of waiting for a long one that started last.  Results do not depend on the order.
-static bool solve_history_on(const ht_ctx *ctx, int B) { return ctx->d_swork && B > ctx->n_cu * 8 && B + 8 <= ctx->cstride; }
+// Batches that take several rounds per CU launch their block-per-frame kernels longest frame first, so that a launch ends on short frames instead of waiting for a long one
+// that started last (results do not depend on the order): the cloud-row and FitError kernels by the frames' point counts (update_inputs), the solves by what every frame took
+// in the same launch of the previous update (solve_hist: k_solve notes it, update_orders ranks it beside the net).
+static bool several_rounds(const ht_ctx *ctx, int B) { return B > ctx->n_cu * 8; }
 struct solve_opts { const int *active = nullptr; int hist_slot = -1; bool tables = false, shared_gpu = false; float *poses_out = nullptr; const int *out_npts = nullptr; };      // active: only the frames whose flag is set; tables: solve_prep has made them for exactly this solve; poses_out: the solve also writes the user poses
 // Tuning builds: a launch that takes a launch table while the tables are still being made on side stream 0 must be on that stream (update_resets)
 static void table_read_on(const ht_ctx *ctx, hipStream_t s)
@@ -70,13 +72,8 @@ static void solve_step(ht_ctx *ctx, int which, const step_mix &m, int B, hipStre
 	a.dbg = ht_tuning_flags(); a.shared_gpu = o.shared_gpu ? 1 : 0; a.tables = o.tables ? ctx->d_tables : nullptr;
 	exact_args(ctx, a, m.cloud);
 	a.out_poses = o.poses_out; a.out_npts = o.out_npts; a.out_initializing = ctx->d_initializing; a.out_min_point_num = ctx->par.min_point_num;
-	// (a solve on some of the frames -- o.active -- keeps no cost history and takes no order table: update_resets relies on it, as on contact_history's rule for the reset frames)
-	if (o.hist_slot >= 0 && o.hist_slot < HT_CONTACT_SLOTS && !o.active && !exact_solver(ctx) && solve_history_on(ctx, B) && B == ctx->swork_B)
-	{
-		a.cost_out = ctx->d_swork + (size_t)o.hist_slot * ctx->cstride;
-		ctx->swork_mask |= 1u << o.hist_slot;
-		if ((ctx->sorder_mask >> o.hist_slot) & 1u) a.frame_order = ctx->d_sorder + (size_t)o.hist_slot * ctx->cstride;
-	}
+	// (a solve on some of the frames -- o.active -- keeps no cost history and takes no order table: update_resets relies on it, as on launch_contacts' rule for the reset frames)
+	if (!o.active && !exact_solver(ctx) && several_rounds(ctx, B)) { const ht_history::rows h = ctx->solve_hist.take(o.hist_slot, B); a.cost_out = h.work; a.frame_order = h.order; }
 	if (a.frame_order) table_read_on(ctx, s);
 	ht_launch_solve(ctx->model, ctx->phys, a, B, s);
 }
@@ -124,49 +121,29 @@ static void marks_dump()
 static inline void mark(const char *, hipStream_t) {}
 static inline void marks_dump() {}
 #endif
-// Contact launches of an update that keep a work history (ht_launch.hpp: HT_CONTACT_SLOTS).  slot < 0 or a launch on the reset frames alone: no history, the fixed assignment.
-// (update_resets relies on the second: under resets_lap the tables are still being made on side stream 0 while this stream launches the reset frames' contacts.)
-struct contact_slot { const int *order; int *work; };
-static contact_slot contact_history(ht_ctx *ctx, int slot, const int *active, int B)
-{
-	contact_slot c = { nullptr, nullptr };
-	if (slot < 0 || slot >= HT_CONTACT_SLOTS || !ctx->d_cwork || active == ctx->d_flags || B != ctx->cwork_B) return c;
-	c.work = ctx->d_cwork + (size_t)slot * ctx->cstride;
-	ctx->cwork_mask |= 1u << slot;
-	if ((ctx->corder_mask >> slot) & 1u) c.order = ctx->d_corder + (size_t)slot * ctx->cstride;
-	return c;
-}
 // The contact kernel on model `which`, with what varies from launch to launch: the frames (`active`: when given, only those whose flag is set -- the reset frames in their
-// few-frames organisation unless many reset), the stream, whether cloud rows run beside it, the history slot
+// few-frames organisation unless many reset), the stream, whether cloud rows run beside it, the history slot (ht_launch.hpp: HT_CONTACT_SLOTS).  A launch on the reset frames
+// alone keeps no history and takes the fixed assignment (update_resets relies on it: under resets_lap the tables are still being made on side stream 0 while this stream
+// launches the reset frames' contacts).
 static void launch_contacts(ht_ctx *ctx, int which, const int *active, int B, hipStream_t s, bool beside_cloud_rows = false, int slot = -1)
 {
-	const contact_slot ch = contact_history(ctx, slot, active, B);
-	if (ch.order) table_read_on(ctx, s);
+	const bool reset_frames = active && active == ctx->d_flags;
+	const ht_history::rows h = ctx->contact_hist.take(reset_frames ? -1 : slot, B);
+	if (h.order) table_read_on(ctx, s);
 	ht_launch_contacts(ctx->model, ctx->d_state[which], ctx->phys.driftmax, ctx->phys.jiggle_sin, active, ctx->d_epa_ws, ctx->d_contacts, ctx->d_ncontacts, B, s, beside_cloud_rows, ctx->contact_kernel,
-	                   active && active == ctx->d_flags && !ctx->many_reset, ch.order, ch.work);
+	                   reset_frames && !ctx->many_reset, h.order, h.work);
 }
-// At the head of an update, on a stream that has nothing to do while the net runs: the assignments of this update's contact launches from the works of the last one
-static void contact_orders(ht_ctx *ctx, int B, hipStream_t t)
+// At the head of an update, on a stream that has nothing to do while the net runs: this update's launch tables from the works of the last one
+static void update_orders(ht_ctx *ctx, int B, hipStream_t t)
 {
-	const int nfr = ht_contacts_frames_per_block(ctx->model, B);
-	ctx->corder_mask = 0;
-	if (ctx->d_cwork && ctx->cwork_B == B && ctx->cwork_mask && nfr > 1 && B + 8 <= ctx->cstride && ctx->contact_kernel != 2)
-	{
-		// frames with polytope runs per block: every block a CU of its own (the slowest block is the launch's time) -> one; several rounds per CU (the sum counts) -> all.
-		// tools/exp_contact_epb.sh at 1024 frames, 1 / 2 / 3 / 4 per block: slowest block 329 / 339 / 355 / 369 k cycles, mean frame 2.13 / 2.11 / 2.05 / 2.01 M cycles per step
-		static const int epb_env = ht_tuning_int("HT_CONTACT_EPB", 0);      // -DHT_TUNING builds: pins it
-		const int blocks = (B + nfr - 1) / nfr;
-		ht_launch_contact_order(ctx->d_cwork, ctx->d_corder, B, nfr, ctx->cstride, ctx->cwork_mask, HT_CONTACT_SLOTS, epb_env > 0 ? epb_env : blocks > ctx->n_cu ? nfr : 1, t);
-		ctx->corder_mask = ctx->cwork_mask;
-	}
-	ctx->cwork_mask = 0; ctx->cwork_B = B;
-	ctx->sorder_mask = 0;
-	if (solve_history_on(ctx, B) && ctx->swork_B == B && ctx->swork_mask)
-	{
-		ht_launch_rank_desc(ctx->d_swork, ctx->d_sorder, B, ctx->cstride, ctx->swork_mask, HT_CONTACT_SLOTS, t);
-		ctx->sorder_mask = ctx->swork_mask;
-	}
-	ctx->swork_mask = 0; ctx->swork_B = B;
+	const coop_plan plan = ht_contacts_coop_plan(ctx->model, B);      // the tables deal the frames over the blocks of the cooperative kernel's whole-batch form
+	// frames with polytope runs per block: every block a CU of its own (the slowest block is the launch's time) -> one; several rounds per CU (the sum counts) -> all.
+	// tools/exp_contact_epb.sh at 1024 frames, 1 / 2 / 3 / 4 per block: slowest block 329 / 339 / 355 / 369 k cycles, mean frame 2.13 / 2.11 / 2.05 / 2.01 M cycles per step
+	static const int epb_env = ht_tuning_int("HT_CONTACT_EPB", 0);      // -DHT_TUNING builds: pins it
+	const int blocks = plan.nfr > 0 ? (B + plan.nfr - 1) / plan.nfr : 0, epb = epb_env > 0 ? epb_env : blocks > ctx->n_cu ? plan.nfr : 1;
+	ht_history &c = ctx->contact_hist, &v = ctx->solve_hist;
+	c.begin(B, plan.nfr > 1 && ht_contacts_coop(ctx->model, B, ctx->contact_kernel, false), [&](unsigned slots) { ht_launch_contact_order(c.work, c.order, B, plan.nfr, c.stride, slots, HT_CONTACT_SLOTS, epb, t); });
+	v.begin(B, several_rounds(ctx, B), [&](unsigned slots) { ht_launch_rank_desc(v.work, v.order, B, v.stride, slots, HT_CONTACT_SLOTS, t); });
 }
 // (side_open keeps track of the side streams that are out: an update ends by bringing back whichever still is, join_open)
 static void fork(ht_ctx *ctx, hipStream_t s) { (void)hipEventRecord(ctx->ev_fork, s); for (int i = 0; i < 2; i++) (void)hipStreamWaitEvent(ctx->side[i], ctx->ev_fork, 0); ctx->side_open |= 3u; }
@@ -209,7 +186,7 @@ static void multistep(ht_ctx *ctx, int B, const steps_on &o)
 			hipStream_t rows_stream = par ? ctx->side[o.side] : s;
 			if (par && pose_only) fork(ctx, s); else if (par) fork1(ctx, s, o.side);
 			const cloud_records cr = cloud_rec(ctx);
-			if (m.cloud) { ht_prof_scope ps(ctx, o.prof ? "cloud_rows" : nullptr, s, true); ht_launch_cloud_rows(ctx->model, ctx->d_state[1], ctx->d_pts, ctx->d_npts, ctx->d_cams, active, 4, 1, 2, p, ctx->d_rows, ctx->d_nrows, B, rows_stream, 0.0f, 0.0f, rec_or_rows(ctx, &cr)); }
+			if (m.cloud) { ht_prof_scope ps(ctx, o.prof ? "cloud_rows" : nullptr, s, true); ht_launch_cloud_rows(ctx->model, ctx->d_state[1], ctx->d_pts, ctx->d_npts, ctx->d_cams, active, step_take, ht_cloud_limits(p, CLOUD_MULTISTEP), ctx->d_rows, ctx->d_nrows, B, rows_stream, rec_or_rows(ctx, &cr)); }
 			if (pose_only) solve_prep(ctx, 1, m, true, active, B, ctx->side[1 - o.side]);
 			else if (tables) { ht_prof_scope ps(ctx, o.prof ? "solve_prep" : nullptr, s, true); solve_prep(ctx, 1, m, false, active, B, rows_stream); }
 			if (coll) { ht_prof_scope ps(ctx, o.prof ? "contacts" : nullptr, s, true); launch_contacts(ctx, 1, active, B, s, false, step_slot(st)); }
@@ -245,7 +222,7 @@ static void main_pass(ht_ctx *ctx, int B, hipStream_t s, float *poses_out = null
 	if (!tables && !fused) { ht_prof_scope ps(ctx, "chamber", s, true); ht_launch_chamber(ctx->model, ctx->d_state[0], ctx->d_chplanes, ctx->d_chon, 10.0f, ctx->d_chamber, ctx->d_nchamber, B, chamber_stream); }
 	const cloud_records cr = cloud_rec(ctx);
 	const plane_rows pr = { ctx->d_chplanes, ctx->d_chon, 10.0f, ctx->d_chamber, ctx->d_nchamber };
-	{ ht_prof_scope ps(ctx, "cloud_rows", s, true); ht_launch_cloud_rows(ctx->model, ctx->d_state[0], pts, npts, ctx->d_cams, nullptr, 1, 0, 1, p, ctx->d_rows, ctx->d_nrows, B, rows_stream, 0.0f, 0.0f, rec_or_rows(ctx, &cr), fused ? &pr : nullptr); }
+	{ ht_prof_scope ps(ctx, "cloud_rows", s, true); ht_launch_cloud_rows(ctx->model, ctx->d_state[0], pts, npts, ctx->d_cams, nullptr, fit_take(CLOUD_FIT), ht_cloud_limits(p, CLOUD_FIT), ctx->d_rows, ctx->d_nrows, B, rows_stream, rec_or_rows(ctx, &cr), fused ? &pr : nullptr); }
 	if (tables) { ht_prof_scope ps(ctx, "solve_prep", s, true); solve_prep(ctx, 0, m, false, nullptr, B, rows_stream); }
 	if (coll) { ht_prof_scope ps(ctx, "contacts", s, true); launch_contacts(ctx, 0, nullptr, B, s, par, pass_slot(pass)); }
 	mark("  pass: contacts done", s);
@@ -333,7 +310,7 @@ static int update_inputs(ht_ctx *ctx, update_call &u)
 		}
 	}
 	// batches of several rounds per CU: the block-per-frame kernels take the frames with the most points first, so that a launch ends on short blocks
-	if (ctx->d_porder && B > ctx->n_cu * 8 && !exact_solver(ctx)) { ht_launch_order_by_points(ctx->d_npts, ctx->d_porder, B, s); ctx->model.frame_order = ctx->d_porder; }
+	if (ctx->d_porder && several_rounds(ctx, B) && !exact_solver(ctx)) { ht_launch_order_by_points(ctx->d_npts, ctx->d_porder, B, s); ctx->model.frame_order = ctx->d_porder; }
 	return HT_OK;
 }
 static void update_planes(ht_ctx *ctx, const update_call &u, hipStream_t t)      // the boundary planes of the main-thread cloud (handtrack.h:751, 774-778), once per update
@@ -364,7 +341,7 @@ static void update_beside_net(ht_ctx *ctx, const update_call &u)
 	fork(ctx, u.s);
 	if (u.mode == UPD_FULL && !(u.d_start && !u.fs)) ht_launch_set_pose(ctx->d_state[1], ctx->d_state[0], ctx->model.nb, u.B, 2, fit);     // othermodel.SetPose(handmodel.GetPose()) handtrack.h:757 (both were just seeded with the same pose otherwise)
 	update_fit_error_old(ctx, u, fit); mark("carried FitError done", fit);
-	contact_orders(ctx, u.B, rest); mark("orders done", rest);
+	update_orders(ctx, u.B, rest); mark("orders done", rest);
 	update_planes(ctx, u, rest); mark("planes done", rest);
 	ctx->tables_out = true;      // until side stream 0 is joined (join1)
 }
@@ -474,7 +451,7 @@ static int run_update_(ht_ctx *ctx, update_call &u)
 	static const bool no_overlap = ht_tuning_env("HT_NO_OVERLAP");      // timing experiments (-DHT_TUNING builds only)
 	const bool overlap = !no_overlap && !ctx->profile_phases && p.steps >= 1 && p.steps_cloudstart >= 1 && !p.angles_only && ctx->solver_build != 5;
 	if (overlap) update_beside_net(ctx, u);
-	else { contact_orders(ctx, u.B, s); update_planes(ctx, u, s); }
+	else { update_orders(ctx, u.B, s); update_planes(ctx, u, s); }
 	update_net(ctx, u, overlap);
 	if (overlap) update_resets(ctx, u);
 	else      // the same on one stream, in the reference's order
@@ -496,8 +473,8 @@ static int run_update(ht_ctx *ctx, const uint16_t *d_depth, const float *d_cams,
 {
 	update_call u = { d_depth, d_cams, d_start, B, d_poses_out, d_cnn_out, s, fs, mode, nullptr, 64, 64 };
 	const int r = run_update_(ctx, u);
-	ctx->model.frame_order = nullptr;      // the launch order of the block-per-frame kernels belongs to the update that made it
-	ctx->planes_valid = false;             // and so do the boundary planes of its cloud
+	ctx->model.frame_order = nullptr; ctx->model.pts_bound = 0;      // the per-call hints of update_inputs (launch order of the block-per-frame kernels, largest cloud) belong to the update that set them
+	ctx->planes_valid = false;                                       // and so do the boundary planes of its cloud
 	return r;
 }
 static int update_dev_end(ht_ctx *ctx, int r) { if (r) return r; HIPCHK(ctx, hipGetLastError()); return HT_OK; }      // what a *_dev update ends with: nothing is waited for, a launch that failed is reported
@@ -848,7 +825,8 @@ extern "C" int ht_stage_cloud_rows(ht_ctx *ctx, int which, int stride, int use_c
 	if (!rows || !nrows || which < 0 || which > 1 || stride < 1) return HT_ERR_ARG;
 	hipStream_t s = ctx->stream;
 	HIPCHK(ctx, hipMemsetAsync(ctx->d_rows, 0, (size_t)B * ctx->model.pts_cap * HT_ROW * sizeof(float), s));
-	ht_launch_cloud_rows(ctx->model, ctx->d_state[which], ctx->d_pts, ctx->d_npts, ctx->d_cams, nullptr, stride, use_cam_origin, 0, ctx->par, ctx->d_rows, ctx->d_nrows, B, s);
+	const cloud_take take = { stride, use_cam_origin, CLOUD_UNIT };
+	ht_launch_cloud_rows(ctx->model, ctx->d_state[which], ctx->d_pts, ctx->d_npts, ctx->d_cams, nullptr, take, ht_cloud_limits(ctx->par, CLOUD_UNIT), ctx->d_rows, ctx->d_nrows, B, s);
 	HIPCHK(ctx, hipMemcpy2DAsync(rows, HT_MAXPTS * HT_ROW * sizeof(float), ctx->d_rows, (size_t)ctx->model.pts_cap * HT_ROW * sizeof(float), HT_MAXPTS * HT_ROW * sizeof(float), B, hipMemcpyDeviceToHost, s));
 	HIPCHK(ctx, hipMemcpyAsync(nrows, ctx->d_nrows, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, s));
 	return ht_sync_check(ctx, s);
@@ -971,7 +949,7 @@ extern "C" int ht_debug_contact_kernel(ht_ctx *ctx, int which)
 //   ht_debug_rank_desc:     order_out[B] = k_rank_desc's
 template <class F> static int debug_order_table(ht_ctx *ctx, const int *work, int B, int n_out, int *order_out, F launch)      // launch(work, order, stride, stream)
 {
-	const int stride = B + 8;
+	const int stride = ht_history::stride_for(B);
 	int *d = nullptr;
 	HIPCHK(ctx, hipMalloc(&d, (size_t)2 * stride * sizeof(int)));
 	hipStream_t s = ctx->stream;
@@ -1132,9 +1110,9 @@ extern "C" int ht_fit_rows(ht_ctx *ctx, int which, int B, const float *points, i
 	HIPCHK(ctx, hipMemcpy(ctx->d_user_n, nl.data(), (size_t)B * sizeof(int), hipMemcpyHostToDevice));
 	hipStream_t s = ctx->stream;
 	const bool coll = ctx->phys.use_collision != 0;
-	ht_params par = ctx->par; par.microforce = microforce;
+	cloud_limits lim = ht_cloud_limits(ctx->par, CLOUD_FIT); lim.microforce = microforce;
 	const cloud_records cr = cloud_rec(ctx);
-	ht_launch_cloud_rows(ctx->model, ctx->d_state[which], ctx->d_pts, ctx->d_npts, ctx->d_cams, nullptr, 1, 0, 1, par, ctx->d_rows, ctx->d_nrows, B, s, 0.0f, 0.0f, &cr);
+	ht_launch_cloud_rows(ctx->model, ctx->d_state[which], ctx->d_pts, ctx->d_npts, ctx->d_cams, nullptr, fit_take(CLOUD_FIT), lim, ctx->d_rows, ctx->d_nrows, B, s, &cr);
 	if (coll) launch_contacts(ctx, which, nullptr, B, s);
 	solve_args a = solve_head(ctx, which, coll);
 	a.rows_pre = ctx->d_user_lin; a.n_pre = ctx->d_user_n; a.pre_stride = ctx->user_lin_cap;
@@ -1233,8 +1211,8 @@ extern "C" int ht_slowfit(ht_ctx *ctx, int B, int hold, const float *refpose, in
 	{
 		const bool cloud = st < steps - 1;
 		const cloud_records cr = cloud_rec(ctx);
-		if (cloud) ht_launch_cloud_rows(ctx->model, ctx->d_state[0], ctx->d_pts, ctx->d_npts, ctx->d_cams, nullptr, 1, 0, 4, ctx->par, ctx->d_rows, ctx->d_nrows, B, s,
-		                                1.0f * (float)(steps - st) / (float)steps, 0.1f * (float)(st < steps - 2), &cr);
+		const cloud_limits lim = ht_cloud_limits(ctx->par, CLOUD_SLOWFIT, 1.0f * (float)(steps - st) / (float)steps, 0.1f * (float)(st < steps - 2));
+		if (cloud) ht_launch_cloud_rows(ctx->model, ctx->d_state[0], ctx->d_pts, ctx->d_npts, ctx->d_cams, nullptr, fit_take(CLOUD_SLOWFIT), lim, ctx->d_rows, ctx->d_nrows, B, s, &cr);
 		if (coll) launch_contacts(ctx, 0, nullptr, B, s);
 		solve_args a = solve_head(ctx, 0, coll);
 		a.cloud_body = cloud ? ctx->d_rowbody : nullptr; a.n_cloud = ctx->d_nrows;
