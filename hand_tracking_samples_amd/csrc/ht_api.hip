@@ -11,6 +11,7 @@
 #include "ht_host.hpp"
 #include "ht_launch.hpp"
 #include "ht_model_build.hpp"
+#include "ht_train_shared.hpp"      // the .cnnb layout and the packed conv2 index
 
 // ------------------------------------------------------------------------------------------------- context
 static void default_params(ht_params &p)     // handtrack.h:523-547, physics.h:45-47, physmodel.h:234, handtrack.h:369,450
@@ -254,59 +255,14 @@ extern "C" int ht_scale(ht_ctx *ctx, float s)
 	for (int w = 0; w < 2; w++) ht_launch_scale_state(ctx->d_state[w], nb, ctx->B, s, st);
 	return ht_sync_check(ctx, st);
 }
-// CNN::Train (cnn.h:558-580), one SGD step per sample in the order given (train-cnn.cpp:156-162 calls it with alpha = 0.001), on the weights
-// held by the context; ht_cnn_get_weights reads them back in .cnnb order (CNN::saveb cnn.h:591-593).
-// The steps on device pools: step k trains on sample order[k] (order[k] = k without an order); the indices were checked by the caller.  The
-// training arena ends with a sink for the per-step MSE when the caller asks for none.
-static int cnn_train_steps(ht_ctx *ctx, const float *d_x, const float *d_t, const int *order, int n_steps, float alpha, float *d_mse, hipStream_t s)
-{
-	const size_t na = ht_train_act_floats(), ne = ht_train_err_floats(), np = ht_train_part_floats();
-	if (!ctx->d_train) { int r = dev_alloc(ctx, &ctx->d_train, na + ne + np + 16); if (r) return r; }
-	float *sink = ctx->d_train + na + ne + np;
-	for (int k = 0; k < n_steps; k++)
-	{
-		const size_t i = order ? (size_t)order[k] : (size_t)k;
-		ht_launch_train_step(ctx->d_weights, ctx->d_weights + HT_CNNB_COUNT, d_x + i * HT_CNN_IN, d_t + i * HT_CNN_OUT, alpha, ctx->d_train, ctx->d_train + na, ctx->d_train + na + ne, d_mse ? d_mse + k : sink, s);
-	}
-	ht_launch_pack_w4(ctx->cnnw.W4, ctx->d_weights + HT_CNNB_COUNT + 16384, s);      // the forward kernels' copy of the last layer follows the trained weights
-	return HT_OK;
-}
-extern "C" int ht_cnn_train_dev(ht_ctx *ctx, const float *d_inputs, const float *d_targets, int n_pool, const int *order, int n_steps, float alpha, float *d_mse, void *stream)
-{
-	CHECK_READY(ctx);
-	if (!ctx->have_weights) { ctx->err = "CNN weights not loaded (ht_cnn_load_weights)"; return HT_ERR_STATE; }
-	if (!d_inputs || !d_targets || n_pool < 1 || n_steps < 0) { ctx->err = "ht_cnn_train_dev: bad argument"; return HT_ERR_ARG; }
-	if (!order && n_steps > n_pool) { ctx->err = "ht_cnn_train_dev: without an order, n_steps must not exceed n_pool"; return HT_ERR_ARG; }
-	if (order) for (int k = 0; k < n_steps; k++) if (order[k] < 0 || order[k] >= n_pool) { ctx->err = "ht_cnn_train_dev: order[" + std::to_string(k) + "] is outside [0, n_pool)"; return HT_ERR_ARG; }
-	if (n_steps == 0) return HT_OK;
-	hipStream_t s = ht_user_stream(ctx, stream);
-	{ const int r = cnn_train_steps(ctx, d_inputs, d_targets, order, n_steps, alpha, d_mse, s); if (r) return r; }
-	HIPCHK(ctx, hipGetLastError());
-	return HT_OK;
-}
-// the host-array form: an upload, then the same steps on the context's stream
-extern "C" int ht_cnn_train(ht_ctx *ctx, const float *inputs, const float *targets, int n, float alpha, float *mse_out)
-{
-	CHECK_READY(ctx);
-	if (!ctx->have_weights) { ctx->err = "CNN weights not loaded (ht_cnn_load_weights)"; return HT_ERR_STATE; }
-	if (!inputs || !targets || n < 1) return HT_ERR_ARG;
-	float *d_x = nullptr, *d_t = nullptr, *d_mse = nullptr;
-	int rc = HT_OK;
-	if (hipMalloc((void **)&d_x, (size_t)n * HT_CNN_IN * sizeof(float)) != hipSuccess || hipMalloc((void **)&d_t, (size_t)n * HT_CNN_OUT * sizeof(float)) != hipSuccess ||
-	    hipMalloc((void **)&d_mse, (size_t)n * sizeof(float)) != hipSuccess) { ctx->err = "ht_cnn_train: out of device memory"; rc = HT_ERR_HIP; }
-	hipStream_t s = ctx->stream;
-	if (rc == HT_OK && (hipMemcpyAsync(d_x, inputs, (size_t)n * HT_CNN_IN * sizeof(float), hipMemcpyHostToDevice, s) != hipSuccess ||
-	                    hipMemcpyAsync(d_t, targets, (size_t)n * HT_CNN_OUT * sizeof(float), hipMemcpyHostToDevice, s) != hipSuccess)) { ctx->err = "ht_cnn_train: upload failed"; rc = HT_ERR_HIP; }
-	if (rc == HT_OK) rc = cnn_train_steps(ctx, d_x, d_t, nullptr, n, alpha, d_mse, s);
-	if (rc == HT_OK && ((mse_out && hipMemcpyAsync(mse_out, d_mse, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, s) != hipSuccess) || hipStreamSynchronize(s) != hipSuccess || hipGetLastError() != hipSuccess))
-	{ ctx->err = "ht_cnn_train: device error"; rc = HT_ERR_HIP; }
-	(void)hipFree(d_x); (void)hipFree(d_t); (void)hipFree(d_mse);
-	return rc;
-}
-// Mini-batch steps (ht_train_batch.hip): w' = w - alpha * sum_b g_b(w).  The arguments are checked completely before the arena grows or anything is launched.
-static int cnn_train_batch_check(ht_ctx *ctx, const char *fn, const void *in, const void *tg, int n_pool, const int *order, int n_steps, int batch)
+// Training on the weights held by the context; ht_cnn_get_weights reads them back in .cnnb order (CNN::saveb cnn.h:591-593).  Two step implementations, chosen by
+// the entry point: CNN::Train (cnn.h:558-580), one SGD step per sample in the order given (train-cnn.cpp:156-162 calls it with alpha = 0.001; ht_train.hip), and
+// mini-batch steps w' = w - alpha * sum_b g_b(w) (ht_train_batch.hip).  `batched` says which; the per-sample forms are checked as steps of batch = 1.
+// The arguments are checked completely before an arena or the staging buffer grows or anything is launched.
+static int cnn_train_check(ht_ctx *ctx, const char *fn, bool batched, const void *in, const void *tg, int n_pool, const int *order, int n_steps, int batch)
 {
 	const std::string f(fn);
+	if (!ctx->have_weights && !batched) { ctx->err = "CNN weights not loaded (ht_cnn_load_weights)"; return HT_ERR_STATE; }
 	if (!ctx->have_weights) { ctx->err = f + ": the context holds no weights of the 64x64-input net (ht_cnn_load_weights); the 128x128-input net is not trained"; return HT_ERR_ARG; }
 	if (batch < 1 || batch > HT_TRAIN_MAX_BATCH) { ctx->err = f + ": batch must be in [1, HT_TRAIN_MAX_BATCH = " + std::to_string(HT_TRAIN_MAX_BATCH) + "]"; return HT_ERR_ARG; }
 	if (!in || !tg) { ctx->err = f + ": inputs and targets must not be NULL"; return HT_ERR_ARG; }
@@ -316,49 +272,74 @@ static int cnn_train_batch_check(ht_ctx *ctx, const char *fn, const void *in, co
 	if (order) for (long long k = 0; k < (long long)n_steps * batch; k++) if (order[k] < 0 || order[k] >= n_pool) { ctx->err = f + ": order[" + std::to_string(k) + "] is outside [0, n_pool)"; return HT_ERR_ARG; }
 	return HT_OK;
 }
-// steps of `batch` samples over n_samples indices (order, or 0, 1, ...): the last step takes what is left; then the packed copy of the last layer, once
-static int cnn_train_batch_steps(ht_ctx *ctx, const float *d_x, const float *d_t, const int *order, int n_samples, int batch, float alpha, float *d_mse, hipStream_t s)
+// The steps on device pools over n_samples indices (order, or 0, 1, ...), checked by the caller.  Per sample: step k trains on index k; the training arena ends with
+// a sink for the per-step MSE when the caller asks for none.  Batched: steps of `batch` indices, the last step takes what is left.  Then, once, the forward
+// kernels' packed copy of the last layer follows the trained weights.
+static int cnn_train_steps(ht_ctx *ctx, bool batched, const float *d_x, const float *d_t, const int *order, int n_samples, int batch, float alpha, float *d_mse, hipStream_t s)
 {
-	const int cap = (batch + 31) & ~31;
-	{ const int r = dev_grow(ctx, &ctx->d_train_batch, &ctx->train_batch_cap, (size_t)cap, ht_train_batch_floats(cap) / (size_t)cap + 1); if (r) return r; }
-	int index[HT_TRAIN_MAX_BATCH];
-	for (int k = 0; k < n_samples; k += batch)
+	float *w = ctx->d_weights, *W2p = ctx->d_weights + HT_CNNB_COUNT;
+	if (!batched)
 	{
-		const int n = n_samples - k < batch ? n_samples - k : batch;
-		for (int b = 0; b < n; b++) index[b] = order ? order[k + b] : k + b;
-		ht_launch_train_batch_step(ctx->d_weights, ctx->d_weights + HT_CNNB_COUNT, d_x, d_t, index, n, alpha, ctx->d_train_batch, ctx->train_batch_cap, d_mse ? d_mse + k : nullptr, s);
-		ctx->train_batch_last = n;
+		const size_t na = ht_train_act_floats(), ne = ht_train_err_floats(), np = ht_train_part_floats();
+		if (!ctx->d_train) { int r = dev_alloc(ctx, &ctx->d_train, na + ne + np + 16); if (r) return r; }
+		float *sink = ctx->d_train + na + ne + np;
+		for (int k = 0; k < n_samples; k++)
+		{
+			const size_t i = order ? (size_t)order[k] : (size_t)k;
+			ht_launch_train_step(w, W2p, d_x + i * HT_CNN_IN, d_t + i * HT_CNN_OUT, alpha, ctx->d_train, ctx->d_train + na, ctx->d_train + na + ne, d_mse ? d_mse + k : sink, s);
+		}
 	}
-	ht_launch_pack_w4(ctx->cnnw.W4, ctx->d_weights + HT_CNNB_COUNT + 16384, s);      // the forward kernels' copy of the last layer follows the trained weights
+	else
+	{
+		const int cap = (batch + 31) & ~31;
+		{ const int r = dev_grow(ctx, &ctx->d_train_batch, &ctx->train_batch_cap, (size_t)cap, ht_train_batch_floats(cap) / (size_t)cap + 1); if (r) return r; }
+		int index[HT_TRAIN_MAX_BATCH];
+		for (int k = 0; k < n_samples; k += batch)
+		{
+			const int n = n_samples - k < batch ? n_samples - k : batch;
+			for (int b = 0; b < n; b++) index[b] = order ? order[k + b] : k + b;
+			ht_launch_train_batch_step(w, W2p, d_x, d_t, index, n, alpha, ctx->d_train_batch, ctx->train_batch_cap, d_mse ? d_mse + k : nullptr, s);
+			ctx->train_batch_last = n;
+		}
+	}
+	ht_launch_pack_w4(ctx->cnnw.W4, W2p + 16384, s);
+	HIPCHK(ctx, hipGetLastError());
 	return HT_OK;
+}
+// the device-pool forms: asynchronous on the caller's stream
+static int cnn_train_dev(ht_ctx *ctx, const char *fn, bool batched, const float *d_inputs, const float *d_targets, int n_pool, const int *order, int n_steps, int batch, float alpha, float *d_mse, void *stream)
+{
+	{ const int r = cnn_train_check(ctx, fn, batched, d_inputs, d_targets, n_pool, order, n_steps, batch); if (r) return r; }
+	if (n_steps == 0) return HT_OK;
+	return cnn_train_steps(ctx, batched, d_inputs, d_targets, order, n_steps * batch, batch, alpha, d_mse, ht_user_stream(ctx, stream));
+}
+// the host-array forms: the n samples staged through the context's buffer (ht_staged_call), then the same steps in order on the context's stream
+static int cnn_train_host(ht_ctx *ctx, const char *fn, bool batched, const float *inputs, const float *targets, int n, int batch, float alpha, float *mse_out)
+{
+	{ const int r = cnn_train_check(ctx, fn, batched, inputs, targets, n, nullptr, 0, batch); if (r) return r; }
+	ht_seg seg[3] = { { (void *)inputs, (size_t)n * HT_CNN_IN * sizeof(float), false }, { (void *)targets, (size_t)n * HT_CNN_OUT * sizeof(float), false }, { mse_out, (size_t)n * sizeof(float), true } };
+	return ht_staged_call(ctx, &ctx->d_train_io, &ctx->train_io_cap, seg, 3, [&](hipStream_t s)
+	                      { return cnn_train_steps(ctx, batched, (const float *)seg[0].dev, (const float *)seg[1].dev, nullptr, n, batch, alpha, (float *)seg[2].dev, s); });
+}
+extern "C" int ht_cnn_train_dev(ht_ctx *ctx, const float *d_inputs, const float *d_targets, int n_pool, const int *order, int n_steps, float alpha, float *d_mse, void *stream)
+{
+	CHECK_READY(ctx);
+	return cnn_train_dev(ctx, "ht_cnn_train_dev", false, d_inputs, d_targets, n_pool, order, n_steps, 1, alpha, d_mse, stream);
+}
+extern "C" int ht_cnn_train(ht_ctx *ctx, const float *inputs, const float *targets, int n, float alpha, float *mse_out)
+{
+	CHECK_READY(ctx);
+	return cnn_train_host(ctx, "ht_cnn_train", false, inputs, targets, n, 1, alpha, mse_out);
 }
 extern "C" int ht_cnn_train_batch_dev(ht_ctx *ctx, const float *d_inputs, const float *d_targets, int n_pool, const int *order, int n_steps, int batch, float alpha, float *d_mse, void *stream)
 {
 	CHECK_READY(ctx);
-	{ const int r = cnn_train_batch_check(ctx, "ht_cnn_train_batch_dev", d_inputs, d_targets, n_pool, order, n_steps, batch); if (r) return r; }
-	if (n_steps == 0) return HT_OK;
-	hipStream_t s = ht_user_stream(ctx, stream);
-	{ const int r = cnn_train_batch_steps(ctx, d_inputs, d_targets, order, n_steps * batch, batch, alpha, d_mse, s); if (r) return r; }
-	HIPCHK(ctx, hipGetLastError());
-	return HT_OK;
+	return cnn_train_dev(ctx, "ht_cnn_train_batch_dev", true, d_inputs, d_targets, n_pool, order, n_steps, batch, alpha, d_mse, stream);
 }
-// the host-array form: an upload, then the same steps on the context's stream
 extern "C" int ht_cnn_train_batch(ht_ctx *ctx, const float *inputs, const float *targets, int n, int batch, float alpha, float *mse_out)
 {
 	CHECK_READY(ctx);
-	{ const int r = cnn_train_batch_check(ctx, "ht_cnn_train_batch", inputs, targets, n, nullptr, 0, batch); if (r) return r; }
-	float *d_x = nullptr, *d_t = nullptr, *d_mse = nullptr;
-	int rc = HT_OK;
-	if (hipMalloc((void **)&d_x, (size_t)n * HT_CNN_IN * sizeof(float)) != hipSuccess || hipMalloc((void **)&d_t, (size_t)n * HT_CNN_OUT * sizeof(float)) != hipSuccess ||
-	    hipMalloc((void **)&d_mse, (size_t)n * sizeof(float)) != hipSuccess) { ctx->err = "ht_cnn_train_batch: out of device memory"; rc = HT_ERR_HIP; }
-	hipStream_t s = ctx->stream;
-	if (rc == HT_OK && (hipMemcpyAsync(d_x, inputs, (size_t)n * HT_CNN_IN * sizeof(float), hipMemcpyHostToDevice, s) != hipSuccess ||
-	                    hipMemcpyAsync(d_t, targets, (size_t)n * HT_CNN_OUT * sizeof(float), hipMemcpyHostToDevice, s) != hipSuccess)) { ctx->err = "ht_cnn_train_batch: upload failed"; rc = HT_ERR_HIP; }
-	if (rc == HT_OK) rc = cnn_train_batch_steps(ctx, d_x, d_t, nullptr, n, batch, alpha, d_mse, s);
-	if (rc == HT_OK && ((mse_out && hipMemcpyAsync(mse_out, d_mse, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, s) != hipSuccess) || hipStreamSynchronize(s) != hipSuccess || hipGetLastError() != hipSuccess))
-	{ ctx->err = "ht_cnn_train_batch: device error"; rc = HT_ERR_HIP; }
-	(void)hipFree(d_x); (void)hipFree(d_t); (void)hipFree(d_mse);
-	return rc;
+	return cnn_train_host(ctx, "ht_cnn_train_batch", true, inputs, targets, n, batch, alpha, mse_out);
 }
 // Test aid: the per-sample tensors of the latest mini-batch step (layout: ht_train_batch_views, csrc/ht_train_batch.hip)
 extern "C" int ht_debug_train_batch_buffers(ht_ctx *ctx, int n, float *a3, float *a6, float *a8, float *e9, float *e7, float *e6, float *e3)
@@ -517,14 +498,15 @@ static int cnn_load_weights(ht_ctx *ctx, int side, const float *w, size_t n)
 	}
 	float *d = *net.d_w;
 	HIPCHK(ctx, hipMemcpy(d, w, n * sizeof(float), hipMemcpyHostToDevice));
-	// conv2 weights repacked to [k][oc], k = (ky*4+kx)*16 + ic  (reference index: kx + 4*(ky + 4*(ic + 16*oc)), cnn.h:45-47)
-	const float *W2 = w + 416;
+	// conv2 weights repacked for the matrix kernel (cnn_w2p_index)
+	const float *W2 = cnnb_layout_of(w, net.fc_in).W2;
 	std::vector<float> w2p(16384);
 	for (int oc = 0; oc < 64; oc++) for (int ic = 0; ic < 16; ic++) for (int ky = 0; ky < 4; ky++) for (int kx = 0; kx < 4; kx++)
-		w2p[(size_t)((ky * 4 + kx) * 16 + ic) * 64 + oc] = W2[kx + 4 * (ky + 4 * (ic + 16 * oc))];
+		w2p[cnn_w2p_index(oc, ic, ky, kx)] = W2[kx + 4 * (ky + 4 * (ic + 16 * oc))];
 	HIPCHK(ctx, hipMemcpy(d + net.count, w2p.data(), 16384 * sizeof(float), hipMemcpyHostToDevice));
 	ht_cnn_weights &cw = *net.w;
-	cw.W1 = d; cw.B1 = d + 400; cw.W2p = d + net.count; cw.B2 = d + 416 + 16384; cw.W3 = d + 416 + 16448; cw.B3 = cw.W3 + net.fc_in * 2048; cw.W4 = cw.B3 + 2048; cw.B4 = cw.W4 + (size_t)2048 * 2304;
+	const cnnb_layout<float> L = cnnb_layout_of(d, net.fc_in);
+	cw.W1 = L.W1; cw.B1 = L.B1; cw.W2p = d + net.count; cw.B2 = L.B2; cw.W3 = L.W3; cw.B3 = L.B3; cw.W4 = L.W4; cw.B4 = L.B4;
 	cw.W4p = d + net.count + 16384;
 	ht_launch_pack_w4(cw.W4, d + net.count + 16384, ctx->stream);
 	HIPCHK(ctx, hipStreamSynchronize(ctx->stream));

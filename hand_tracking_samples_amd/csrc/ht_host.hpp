@@ -59,6 +59,7 @@ struct ht_ctx
 	std::vector<float4> h_verts, h_planes;                        // host copies of the model geometry (ht_scale rewrites them)
 	float *d_train_batch = nullptr; int train_batch_cap = 0, train_batch_last = 0;      // mini-batch training arena (ht_train_batch.hip) for train_batch_cap samples, grown to the largest batch seen (dev_grow); samples of the latest step
 	float *d_train = nullptr;                                    // training arena: layer outputs, errors, split-K partial sums (allocated on first use)
+	char *d_train_io = nullptr; size_t train_io_cap = 0;         // ht_cnn_train's and ht_cnn_train_batch's staging (inputs, targets, per-sample MSE), grown to the largest call (dev_grow)
 	float *d_sf_ref = nullptr, *d_sf_crays = nullptr;             // slowfit inputs [B][nb][7], [B][8][4] (allocated on first use)
 	float4 *d_cverts_rw = nullptr;                                // padded copy of the collision vertices (ht_model_dev::cverts)
 	float4 *d_verts_rw = nullptr, *d_planes_rw = nullptr; float *d_bodyc_rw = nullptr, *d_jointc_rw = nullptr;

@@ -17,24 +17,12 @@
 // Sums are reduced in parallel (fixed order, deterministic), so results agree with the reference to float rounding, not bit for bit.
 #include "ht_device.hpp"
 #include "ht_launch.hpp"
+#include "ht_train_shared.hpp"
 
-__device__ __forceinline__ float t_tanh(float t) { float e = (float)exp((double)(2 * t)); return (e - 1) / (e + 1); }      // TanH::f cnn.h:31
-
-// first maximum of a 2x2 window in the reference's scan order (x then y, strict >: cnn.h:150-160)
-__device__ __forceinline__ int first_max4(float a, float b, float c, float d, float &m)
-{
-	int k = 0; m = a;
-	if (b > m) { m = b; k = 1; }
-	if (c > m) { m = c; k = 2; }
-	if (d > m) { m = d; k = 3; }
-	return k;
-}
 __device__ __forceinline__ float max4(float a, float b, float c, float d) { return fmax_std(fmax_std(fmax_std(a, b), c), d); }
-__device__ __forceinline__ float wave_sum(float v) { for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o); return v; }
-__device__ __forceinline__ float seg16_sum(float v) { for (int o = 8; o >= 1; o >>= 1) v += __shfl_xor(v, o); return v; }
 
-// conv1 (5x5, 1 -> 16 channels, 64x64 -> 60x60) + tanh + the two max-pools (-> 30x30 -> 15x15).  Block (py, oz): four output rows of one
-// channel, one thread per output, taps in the reference's order (cnn.h:226-228); the first 15 threads then pool the 4x60 strip.
+// conv1 + tanh (t_conv1_out) + the two max-pools (-> 30x30 -> 15x15).  Block (py, oz): four output rows of one channel, one thread per output;
+// the first 15 threads then pool the 4x60 strip.
 __global__ __launch_bounds__(256) void k_t_conv1_tanh_pool(const float *__restrict__ in, const float *__restrict__ W, const float *__restrict__ B, float *__restrict__ a1, float *__restrict__ a3)
 {
 	__shared__ float s_o[4][60];
@@ -42,12 +30,7 @@ __global__ __launch_bounds__(256) void k_t_conv1_tanh_pool(const float *__restri
 	if (t < 240)
 	{
 		const int r = t / 60, x = t % 60, y = 4 * py + r;
-		float acc = B[oz];
-#pragma unroll
-		for (int ky = 0; ky < 5; ky++)
-#pragma unroll
-			for (int kx = 0; kx < 5; kx++) acc += in[(y + ky) * 64 + x + kx] * W[kx + 5 * (ky + 5 * oz)];
-		const float o = t_tanh(acc);
+		const float o = t_conv1_out(in, W, B, oz, y, x);
 		a1[oz * 3600 + y * 60 + x] = o; s_o[r][x] = o;
 	}
 	__syncthreads();
@@ -59,24 +42,13 @@ __global__ __launch_bounds__(256) void k_t_conv1_tanh_pool(const float *__restri
 		a3[oz * 225 + py * 15 + t] = max4(q[0], q[1], q[2], q[3]);
 	}
 }
-// conv2 (4x4, 16 -> 64 channels, 15x15 -> 12x12) + tanh + max-pool (-> 6x6): one block per output channel, input and taps in LDS
+// conv2 + tanh (t_conv2_out) + max-pool (-> 6x6): one block per output channel
 __global__ __launch_bounds__(192) void k_t_conv2_tanh_pool(const float *__restrict__ a3, const float *__restrict__ W, const float *__restrict__ B, float *__restrict__ a5, float *__restrict__ a6)
 {
 	__shared__ float s_in[3600], s_w[256], s_o[144];
 	const int oz = blockIdx.x, t = threadIdx.x;
-	for (int i = t; i < 3600; i += 192) s_in[i] = a3[i];
-	for (int i = t; i < 256; i += 192) s_w[i] = W[oz * 256 + i];
-	__syncthreads();
-	if (t < 144)
-	{
-		const int x = t % 12, y = t / 12;
-		float acc = B[oz];
-		for (int ky = 0; ky < 4; ky++) for (int kx = 0; kx < 4; kx++)
-#pragma unroll
-			for (int iz = 0; iz < 16; iz++) acc += s_in[iz * 225 + (y + ky) * 15 + x + kx] * s_w[kx + 4 * (ky + 4 * iz)];
-		const float o = t_tanh(acc);
-		a5[oz * 144 + t] = o; s_o[t] = o;
-	}
+	const float o = t_conv2_out(a3, W, B, oz, s_in, s_w, s_o);
+	if (t < 144) a5[oz * 144 + t] = o;
 	__syncthreads();
 	if (t < 36) { const float *p = s_o + (2 * (t / 6)) * 12 + 2 * (t % 6); a6[oz * 36 + t] = max4(p[0], p[1], p[12], p[13]); }
 }
@@ -171,19 +143,17 @@ template <bool OUTPUT> __global__ __launch_bounds__(256) void k_t_fc_back_update
 	acc = wave_sum(acc);
 	if (lane == 0) D[i] = OUTPUT ? (1.0f - xi * xi) * acc : acc;
 }
-// third max-pool backward + conv2's tanh backward for pooled element p of channel oz: the first maximum of the 2x2 window takes the
-// error (cnn.h:150-164); writes the window's four entries of the channel's 12x12 error map, times scale
+// third max-pool backward + conv2's tanh backward for pooled element p of channel oz: the first maximum of the 2x2 window, found in a5, takes
+// the error times scale (t_window_scatter)
 __device__ __forceinline__ void pool3_back_tanh(const float *__restrict__ a5, const float *__restrict__ e6, int oz, int p, float scale, float *__restrict__ e4c)
 {
-	const int base = (2 * (p / 6)) * 12 + 2 * (p % 6);
-	const float *a = a5 + oz * 144 + base;
+	const float *a = a5 + oz * 144 + (2 * (p / 6)) * 12 + 2 * (p % 6);
 	float m;
 	const int k = first_max4(a[0], a[1], a[12], a[13], m);
-	const float d = scale * ((1.0f - m * m) * e6[oz * 36 + p]);
-	e4c[base] = k == 0 ? d : 0.0f; e4c[base + 1] = k == 1 ? d : 0.0f; e4c[base + 12] = k == 2 ? d : 0.0f; e4c[base + 13] = k == 3 ? d : 0.0f;
+	t_window_scatter(e4c, p, k, scale * ((1.0f - m * m) * e6[oz * 36 + p]));
 }
-// LConv::backward of conv2 as a gather (cnn.h:236-250).  Block (iz, g): input channel iz, output channels [4g, 4g+4), whose error maps
-// are rebuilt in LDS from the pooled error; a thread owns one input position and walks output channel, output y, output x ascending.
+// LConv::backward of conv2 (t_conv2_back_gather).  Block (iz, g): input channel iz, output channels [4g, 4g+4), whose error maps
+// are rebuilt in LDS from the pooled error; a thread owns one input position.
 #define T_CB_GROUPS 16
 __global__ __launch_bounds__(256) void k_t_conv2_back(const float *__restrict__ a5, const float *__restrict__ e6, const float *__restrict__ W, float *__restrict__ part3)
 {
@@ -193,18 +163,13 @@ __global__ __launch_bounds__(256) void k_t_conv2_back(const float *__restrict__ 
 	if (t < 64) { const int oz = t >> 4, k = t & 15; s_w[t] = W[k + 16 * (iz + 16 * (4 * g + oz))]; }
 	__syncthreads();
 	if (t >= 225) return;
-	const int x = t % 15, y = t / 15;
-	const int oy0 = max(0, y - 3), oy1 = min(11, y), ox0 = max(0, x - 3), ox1 = min(11, x);
-	float acc = 0.0f;
-	for (int oz = 0; oz < 4; oz++) for (int oy = oy0; oy <= oy1; oy++) for (int ox = ox0; ox <= ox1; ox++)
-		acc += s_w[oz * 16 + (x - ox) + 4 * (y - oy)] * s_e[oz * 144 + oy * 12 + ox];
-	part3[g * 3600 + iz * 225 + t] = acc;
+	part3[g * 3600 + iz * 225 + t] = t_conv2_back_gather<4>(s_w, s_e, t % 15, t / 15);
 }
 // LConv::update (cnn.h:252-279) of both convolutions in one launch.
 // blocks 0..63: conv2, output channel = block, a thread per tap walks the 144 output positions in the reference's order, then the
-//               MFMA-packed copy W2p[(ky*4+kx)*16 + ic][oc] k_conv2 reads is refreshed;
-// blocks 64..79: conv1, output channel = block - 64.  The two max-pools pass conv1's error to one position per 4x4 window only, so the
-//               block first finds those 225 (position, value after tanh') pairs, then eight lanes per tap share them.
+//               MFMA-packed copy (cnn_w2p_index) k_conv2 reads is refreshed;
+// blocks 64..79: conv1, output channel = block - 64: the block first finds the 225 (position, value after tanh') pairs that carry conv1's
+//               error, then eight lanes per tap share them (t_conv1_grad_add).
 __global__ __launch_bounds__(256) void k_t_conv_update(const float *__restrict__ x0, const float *__restrict__ a1, const float *__restrict__ a3, const float *__restrict__ a5, const float *__restrict__ e6, const float *__restrict__ part3,
                                                        float *__restrict__ W1, float *__restrict__ B1, float *__restrict__ W2, float *__restrict__ B2, float *__restrict__ W2p, float alpha)
 {
@@ -224,7 +189,7 @@ __global__ __launch_bounds__(256) void k_t_conv_update(const float *__restrict__
 #pragma unroll
 			for (int x = 0; x < 12; x++) w += xp[y * 15 + x] * s_e[y * 12 + x];
 		W2[oz * 256 + t] = w;
-		W2p[(size_t)((ky * 4 + kx) * 16 + iz) * 64 + oz] = w;
+		W2p[cnn_w2p_index(oz, iz, ky, kx)] = w;
 		if (t == 0) { float bb = B2[oz]; for (int p = 0; p < 144; p++) bb += s_e[p]; B2[oz] = bb; }
 	}
 	else
@@ -248,12 +213,8 @@ __global__ __launch_bounds__(256) void k_t_conv_update(const float *__restrict__
 			s_e[t] = -alpha * ((1.0f - m * m) * e3);
 		}
 		__syncthreads();
-		const int tap = t >> 3, sub = t & 7;      // taps 0..24, tap 25 = bias, 26..31 idle
-		const int off = tap < 25 ? (tap / 5) * 64 + tap % 5 : 0;
-		float acc = 0.0f;
-		if (tap < 25) for (int p = sub; p < 225; p += 8) acc += s_x[s_i[p] + off] * s_e[p];
-		else if (tap == 25) for (int p = sub; p < 225; p += 8) acc += s_e[p];
-		for (int o = 4; o >= 1; o >>= 1) acc += __shfl_xor(acc, o);
+		const int tap = t >> 3, sub = t & 7;
+		const float acc = seg8_sum(t_conv1_grad_add(0.0f, s_x, s_i, s_e, tap, sub));
 		if (sub == 0 && tap < 25) W1[oz * 25 + tap] += acc;
 		if (sub == 0 && tap == 25) B1[oz] += acc;
 	}
@@ -265,18 +226,18 @@ void ht_launch_train_step(float *w, float *W2p, const float *x, const float *tar
 	float *a1 = act, *a3 = a1 + 57600, *a5 = a3 + 3600, *a6 = a5 + 9216, *a8 = a6 + 2304;
 	float *e9 = err, *e7 = e9 + 2304, *e6 = e7 + 2048, *part3 = e6 + 2304, *sqp = part3 + T_CB_GROUPS * 3600;
 	float *part1 = part, *part2 = part + (size_t)T_KSPLIT * 2048;
-	float *W1 = w, *B1 = W1 + 400, *W2 = B1 + 16, *B2 = W2 + 16384, *W3 = B2 + 64, *B3 = W3 + (size_t)2304 * 2048, *W4 = B3 + 2048, *B4 = W4 + (size_t)2048 * 2304;
+	const cnnb_layout<float> L = cnnb_layout_of(w);
 	// forward
-	hipLaunchKernelGGL(k_t_conv1_tanh_pool, dim3(15, 16), dim3(256), 0, s, x, W1, B1, a1, a3);
-	hipLaunchKernelGGL(k_t_conv2_tanh_pool, dim3(64), dim3(192), 0, s, a3, W2, B2, a5, a6);
-	hipLaunchKernelGGL(k_t_fc_partial<false>, dim3(2048 / 256, T_KSPLIT), dim3(256), 0, s, a6, nullptr, nullptr, nullptr, W3, part1, 2304, 2048);
-	hipLaunchKernelGGL(k_t_fc_partial<true>, dim3(2304 / 256, T_KSPLIT), dim3(256), 0, s, nullptr, part1, B3, a8, W4, part2, 2048, 2304);
-	hipLaunchKernelGGL(k_t_softmax_loss, dim3(9), dim3(256), 0, s, part2, B4, target, e9, sqp);
+	hipLaunchKernelGGL(k_t_conv1_tanh_pool, dim3(15, 16), dim3(256), 0, s, x, L.W1, L.B1, a1, a3);
+	hipLaunchKernelGGL(k_t_conv2_tanh_pool, dim3(64), dim3(192), 0, s, a3, L.W2, L.B2, a5, a6);
+	hipLaunchKernelGGL(k_t_fc_partial<false>, dim3(2048 / 256, T_KSPLIT), dim3(256), 0, s, a6, nullptr, nullptr, nullptr, L.W3, part1, 2304, 2048);
+	hipLaunchKernelGGL(k_t_fc_partial<true>, dim3(2304 / 256, T_KSPLIT), dim3(256), 0, s, nullptr, part1, L.B3, a8, L.W4, part2, 2048, 2304);
+	hipLaunchKernelGGL(k_t_softmax_loss, dim3(9), dim3(256), 0, s, part2, L.B4, target, e9, sqp);
 	// backward with the old weights, each layer's update in the same pass
-	hipLaunchKernelGGL(k_t_fc_back_update<true>, dim3(2048 / 4), dim3(256), 0, s, W4, B4, a8, e9, e7, 2048, 2304, alpha, sqp, mse_out);
-	hipLaunchKernelGGL(k_t_fc_back_update<false>, dim3(2304 / 4), dim3(256), 0, s, W3, B3, a6, e7, e6, 2304, 2048, alpha, nullptr, nullptr);
-	hipLaunchKernelGGL(k_t_conv2_back, dim3(16, T_CB_GROUPS), dim3(256), 0, s, a5, e6, W2, part3);
-	hipLaunchKernelGGL(k_t_conv_update, dim3(80), dim3(256), 0, s, x, a1, a3, a5, e6, part3, W1, B1, W2, B2, W2p, alpha);
+	hipLaunchKernelGGL(k_t_fc_back_update<true>, dim3(2048 / 4), dim3(256), 0, s, L.W4, L.B4, a8, e9, e7, 2048, 2304, alpha, sqp, mse_out);
+	hipLaunchKernelGGL(k_t_fc_back_update<false>, dim3(2304 / 4), dim3(256), 0, s, L.W3, L.B3, a6, e7, e6, 2304, 2048, alpha, nullptr, nullptr);
+	hipLaunchKernelGGL(k_t_conv2_back, dim3(16, T_CB_GROUPS), dim3(256), 0, s, a5, e6, L.W2, part3);
+	hipLaunchKernelGGL(k_t_conv_update, dim3(80), dim3(256), 0, s, x, a1, a3, a5, e6, part3, L.W1, L.B1, L.W2, L.B2, W2p, alpha);
 }
 size_t ht_train_act_floats() { return 57600 + 3600 + 9216 + 2304 + 2048; }
 size_t ht_train_err_floats() { return 2304 + 2048 + 2304 + T_CB_GROUPS * 3600 + 16; }

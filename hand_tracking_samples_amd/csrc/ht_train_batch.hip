@@ -1,6 +1,6 @@
 // ht_train_batch.hip -- one SGD step of the pose-initialiser CNN on a mini-batch: w' = w - alpha * sum_b g_b(w), every sample's gradient taken at
 // the same weights.  g_b is what CNN::Train (third_party/cnn.h:558-580) subtracts for sample b, divided by alpha; the per-sample
-// arithmetic is that of ht_train.hip, whose kernels and launches stay as they are.
+// arithmetic is that of ht_train.hip: what the two steps compute alike is written once, in ht_train_shared.hpp.
 //
 // With n samples in a step the two fully connected layers are dense products, three per layer, on v_mfma_f32_32x32x2_f32:
 //   forward        Y[b,j] = B[j] + sum_i X[b,i] W[i,j]            k_fc (ht_cnn.hip) on the row-major weights
@@ -14,6 +14,7 @@
 // Every sum has a fixed order and there are no floating-point atomics: the same call on the same weights gives the same bits.
 #include "ht_device.hpp"
 #include "ht_launch.hpp"
+#include "ht_train_shared.hpp"
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 #define TB_GS 4                                  // samples per partial sum of the convolutions' gradients
@@ -21,25 +22,12 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 #define TB_PW (16384 + 64 + 16 * 26)             // floats of one partial sum: W2, B2, then 16 x (25 taps of W1 + B1)
 struct tb_index { int v[HT_TRAIN_MAX_BATCH]; };
 
-__device__ __forceinline__ float tb_tanh(float t) { float e = (float)exp((double)(2 * t)); return (e - 1) / (e + 1); }      // TanH::f cnn.h:31
-// first maximum of a 2x2 window in the reference's scan order (x then y, strict >: cnn.h:150-160)
-__device__ __forceinline__ int tb_first_max4(float a, float b, float c, float d, float &m)
-{
-	int k = 0; m = a;
-	if (b > m) { m = b; k = 1; }
-	if (c > m) { m = c; k = 2; }
-	if (d > m) { m = d; k = 3; }
-	return k;
-}
-__device__ __forceinline__ float tb_wave_sum(float v) { for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o); return v; }
-__device__ __forceinline__ float tb_seg16_sum(float v) { for (int o = 8; o >= 1; o >>= 1) v += __shfl_xor(v, o); return v; }
-
 // the step's sample indices, handed over as a kernel argument (no host memory has to outlive the call)
 __global__ __launch_bounds__(256) void k_tb_set_index(tb_index ix, int n, int *__restrict__ idx)
 {
 	if ((int)threadIdx.x < n) idx[threadIdx.x] = ix.v[threadIdx.x];
 }
-// conv1 (5x5, 1 -> 16 channels, 64x64 -> 60x60) + tanh + the two max-pools (-> 15x15), k_t_conv1_tanh_pool per sample (blockIdx.z).  Of the 60x60 map
+// conv1 + tanh (t_conv1_out) + the two max-pools (-> 15x15), k_t_conv1_tanh_pool per sample (blockIdx.z).  Of the 60x60 map
 // only the pooled value a3 and r1 = the input position (y * 64 + x) of the conv output that won both pools are kept.
 __global__ __launch_bounds__(256) void k_tb_conv1_tanh_pool(const float *__restrict__ pool, const int *__restrict__ idx, const float *__restrict__ W, const float *__restrict__ B, float *__restrict__ a3, int *__restrict__ r1)
 {
@@ -49,50 +37,34 @@ __global__ __launch_bounds__(256) void k_tb_conv1_tanh_pool(const float *__restr
 	if (t < 240)
 	{
 		const int r = t / 60, x = t % 60, y = 4 * py + r;
-		float acc = B[oz];
-#pragma unroll
-		for (int ky = 0; ky < 5; ky++)
-#pragma unroll
-			for (int kx = 0; kx < 5; kx++) acc += in[(y + ky) * 64 + x + kx] * W[kx + 5 * (ky + 5 * oz)];
-		s_o[r][x] = tb_tanh(acc);
+		s_o[r][x] = t_conv1_out(in, W, B, oz, y, x);
 	}
 	__syncthreads();
 	if (t < 15)
 	{
 		float q[4], m;
 #pragma unroll
-		for (int k = 0; k < 4; k++) { const int r = 2 * (k >> 1), c = 4 * t + 2 * (k & 1); float mk; tb_first_max4(s_o[r][c], s_o[r][c + 1], s_o[r + 1][c], s_o[r + 1][c + 1], mk); q[k] = mk; }
-		const int k2 = tb_first_max4(q[0], q[1], q[2], q[3], m);
+		for (int k = 0; k < 4; k++) { const int r = 2 * (k >> 1), c = 4 * t + 2 * (k & 1); float mk; first_max4(s_o[r][c], s_o[r][c + 1], s_o[r + 1][c], s_o[r + 1][c + 1], mk); q[k] = mk; }
+		const int k2 = first_max4(q[0], q[1], q[2], q[3], m);
 		const int r = 2 * (k2 >> 1), c = 4 * t + 2 * (k2 & 1);
-		const int k1 = tb_first_max4(s_o[r][c], s_o[r][c + 1], s_o[r + 1][c], s_o[r + 1][c + 1], m);
+		const int k1 = first_max4(s_o[r][c], s_o[r][c + 1], s_o[r + 1][c], s_o[r + 1][c + 1], m);
 		const size_t o = (size_t)b * 3600 + oz * 225 + py * 15 + t;
 		a3[o] = m; r1[o] = (4 * py + r + (k1 >> 1)) * 64 + c + (k1 & 1);
 	}
 }
-// conv2 (4x4, 16 -> 64 channels, 15x15 -> 12x12) + tanh + max-pool (-> 6x6), k_t_conv2_tanh_pool per sample (blockIdx.y); a6 = the pooled value,
+// conv2 + tanh (t_conv2_out) + max-pool (-> 6x6), k_t_conv2_tanh_pool per sample (blockIdx.y); a6 = the pooled value,
 // r3 = which of the window's four entries (x fastest) is its first maximum
 __global__ __launch_bounds__(192) void k_tb_conv2_tanh_pool(const float *__restrict__ a3, const float *__restrict__ W, const float *__restrict__ B, float *__restrict__ a6, int *__restrict__ r3)
 {
 	__shared__ float s_in[3600], s_w[256], s_o[144];
 	const int oz = blockIdx.x, b = blockIdx.y, t = threadIdx.x;
-	for (int i = t; i < 3600; i += 192) s_in[i] = a3[(size_t)b * 3600 + i];
-	for (int i = t; i < 256; i += 192) s_w[i] = W[oz * 256 + i];
-	__syncthreads();
-	if (t < 144)
-	{
-		const int x = t % 12, y = t / 12;
-		float acc = B[oz];
-		for (int ky = 0; ky < 4; ky++) for (int kx = 0; kx < 4; kx++)
-#pragma unroll
-			for (int iz = 0; iz < 16; iz++) acc += s_in[iz * 225 + (y + ky) * 15 + x + kx] * s_w[kx + 4 * (ky + 4 * iz)];
-		s_o[t] = tb_tanh(acc);
-	}
+	t_conv2_out(a3 + (size_t)b * 3600, W, B, oz, s_in, s_w, s_o);
 	__syncthreads();
 	if (t < 36)
 	{
 		const float *p = s_o + (2 * (t / 6)) * 12 + 2 * (t % 6);
 		float m;
-		const int k = tb_first_max4(p[0], p[1], p[12], p[13], m);
+		const int k = first_max4(p[0], p[1], p[12], p[13], m);
 		a6[(size_t)b * 2304 + oz * 36 + t] = m; r3[(size_t)b * 2304 + oz * 36 + t] = k;
 	}
 }
@@ -108,7 +80,7 @@ __global__ __launch_bounds__(256) void k_tb_softmax_loss(const float *__restrict
 	for (int c = 0; c < 9; c++)
 	{
 		v[c] = (float)exp((double)lg[c * 256 + t]);
-		cs[c] = c < 8 ? tb_wave_sum(v[c]) : tb_seg16_sum(v[c]);
+		cs[c] = c < 8 ? wave_sum(v[c]) : seg16_sum(v[c]);
 		if (c < 8 && lane == 0) red[0][c][w] = cs[c];
 	}
 	__syncthreads();
@@ -118,11 +90,11 @@ __global__ __launch_bounds__(256) void k_tb_softmax_loss(const float *__restrict
 	{
 		if (c < 8) cs[c] = ((red[0][c][0] + red[0][c][1]) + red[0][c][2]) + red[0][c][3];
 		y[c] = v[c] / cs[c]; d[c] = y[c] - tg[c * 256 + t];
-		cd[c] = c < 8 ? tb_wave_sum(d[c] * y[c]) : tb_seg16_sum(d[c] * y[c]);
+		cd[c] = c < 8 ? wave_sum(d[c] * y[c]) : seg16_sum(d[c] * y[c]);
 		if (c < 8 && lane == 0) red[1][c][w] = cd[c];
 		sq += d[c] * d[c];
 	}
-	sq = tb_wave_sum(sq);
+	sq = wave_sum(sq);
 	if (lane == 0) rsq[w] = sq;
 	__syncthreads();
 #pragma unroll
@@ -224,34 +196,27 @@ __global__ __launch_bounds__(256) void k_tb_fc_wgrad(float *__restrict__ W, floa
 		B[j0 + r] -= alpha * sum;
 	}
 }
-// LConv::backward of conv2 as a gather (cnn.h:236-250) for input channel iz = blockIdx.x of sample b = blockIdx.y: the 64 error maps are rebuilt in LDS
-// from the pooled error (pool backward to the first maximum, then conv2's tanh'), a thread owns one input position and walks output channel, y, x ascending
+// LConv::backward of conv2 (t_conv2_back_gather) for input channel iz = blockIdx.x of sample b = blockIdx.y: the 64 error maps are rebuilt in LDS
+// from the pooled error (conv2's tanh' at the kept maximum, then t_window_scatter to the kept entry), a thread owns one input position
 __global__ __launch_bounds__(256) void k_tb_conv2_back(const float *__restrict__ a6, const int *__restrict__ r3, const float *__restrict__ e6, const float *__restrict__ W, float *__restrict__ e3)
 {
 	__shared__ float s_e[64 * 144], s_w[64 * 16];
 	const int iz = blockIdx.x, b = blockIdx.y, t = threadIdx.x;
 	for (int i = t; i < 2304; i += 256)
 	{
-		const int oz = i / 36, p = i % 36, base = oz * 144 + (2 * (p / 6)) * 12 + 2 * (p % 6);
 		const size_t o = (size_t)b * 2304 + i;
-		const float m = a6[o], d = (1.0f - m * m) * e6[o];
-		const int k = r3[o];
-		s_e[base] = k == 0 ? d : 0.0f; s_e[base + 1] = k == 1 ? d : 0.0f; s_e[base + 12] = k == 2 ? d : 0.0f; s_e[base + 13] = k == 3 ? d : 0.0f;
+		const float m = a6[o];
+		t_window_scatter(s_e + (i / 36) * 144, i % 36, r3[o], (1.0f - m * m) * e6[o]);
 	}
 	for (int i = t; i < 1024; i += 256) s_w[i] = W[(i & 15) + 16 * (iz + 16 * (i >> 4))];
 	__syncthreads();
 	if (t >= 225) return;
-	const int x = t % 15, y = t / 15;
-	const int oy0 = max(0, y - 3), oy1 = min(11, y), ox0 = max(0, x - 3), ox1 = min(11, x);
-	float acc = 0.0f;
-	for (int oz = 0; oz < 64; oz++) for (int oy = oy0; oy <= oy1; oy++) for (int ox = ox0; ox <= ox1; ox++)
-		acc += s_w[oz * 16 + (x - ox) + 4 * (y - oy)] * s_e[oz * 144 + oy * 12 + ox];
-	e3[(size_t)b * 3600 + iz * 225 + t] = acc;
+	e3[(size_t)b * 3600 + iz * 225 + t] = t_conv2_back_gather<64>(s_w, s_e, t % 15, t / 15);
 }
 // LConv::update (cnn.h:252-279) of both convolutions, summed over the TB_GS samples of group blockIdx.y into pw[group][TB_PW] (times -alpha).  Only one
 // entry per pooling window carries an error, so both sums run over (position, value) lists, as k_t_conv_update's conv1 branch does.
 // blocks 0..15: conv2, output channels 4 x .. 4 x + 3: a thread per tap (iz, ky, kx), 36 windows per channel.
-// blocks 16..31: conv1, output channel x - 16: eight lanes per tap share the 225 windows; tap 25 is the bias.
+// blocks 16..31: conv1, output channel x - 16: t_conv1_grad_add per sample, the eight lanes of a tap added once after the group's samples.
 __global__ __launch_bounds__(256) void k_tb_conv_grad(const float *__restrict__ pool, const int *__restrict__ idx, const float *__restrict__ a3, const int *__restrict__ r1, const float *__restrict__ a6, const int *__restrict__ r3,
                                                       const float *__restrict__ e6, const float *__restrict__ e3, int n, float alpha, float *__restrict__ pw)
 {
@@ -288,8 +253,7 @@ __global__ __launch_bounds__(256) void k_tb_conv_grad(const float *__restrict__ 
 	}
 	else
 	{
-		const int oz = blockIdx.x - 16, tap = t >> 3, sub = t & 7;      // taps 0..24, tap 25 = bias, 26..31 idle
-		const int off = tap < 25 ? (tap / 5) * 64 + tap % 5 : 0;
+		const int oz = blockIdx.x - 16, tap = t >> 3, sub = t & 7;
 		float acc = 0.0f;
 		for (int b = b0; b < b1; b++)
 		{
@@ -304,14 +268,13 @@ __global__ __launch_bounds__(256) void k_tb_conv_grad(const float *__restrict__ 
 				s_e[t] = -alpha * ((1.0f - m * m) * e3[o]);
 			}
 			__syncthreads();
-			if (tap < 25) for (int p = sub; p < 225; p += 8) acc += s_x[s_i[p] + off] * s_e[p];
-			else if (tap == 25) for (int p = sub; p < 225; p += 8) acc += s_e[p];
+			acc = t_conv1_grad_add(acc, s_x, s_i, s_e, tap, sub);
 		}
-		for (int o = 4; o >= 1; o >>= 1) acc += __shfl_xor(acc, o);
+		acc = seg8_sum(acc);
 		if (sub == 0 && tap < 26) out[16448 + oz * 26 + tap] = acc;
 	}
 }
-// the groups' partial sums added in group order and applied: W2 (with the MFMA-packed copy W2p[(ky*4+kx)*16 + ic][oc] k_conv2 reads), B2, W1, B1
+// the groups' partial sums added in group order and applied: W2 (with the MFMA-packed copy k_conv2 reads, cnn_w2p_index), B2, W1, B1
 __global__ __launch_bounds__(256) void k_tb_conv_apply(const float *__restrict__ pw, int groups, float *__restrict__ W1, float *__restrict__ B1, float *__restrict__ W2, float *__restrict__ B2, float *__restrict__ W2p)
 {
 	const int e = blockIdx.x * 256 + threadIdx.x;
@@ -322,7 +285,7 @@ __global__ __launch_bounds__(256) void k_tb_conv_apply(const float *__restrict__
 	{
 		const int oz = e >> 8, t = e & 255, kx = t & 3, ky = (t >> 2) & 3, iz = t >> 4;
 		const float w = W2[e] + sum;
-		W2[e] = w; W2p[(size_t)((ky * 4 + kx) * 16 + iz) * 64 + oz] = w;
+		W2[e] = w; W2p[cnn_w2p_index(oz, iz, ky, kx)] = w;
 	}
 	else if (e < 16448) B2[e - 16384] += sum;
 	else
@@ -361,24 +324,24 @@ template <bool FOLD> static void tb_fc_back(const float *E, const float *W, cons
 void ht_launch_train_batch_step(float *w, float *W2p, const float *inputs, const float *targets, const int *index, int n, float alpha, float *arena, int cap, float *mse_out, hipStream_t s)
 {
 	const tb_arena A = tb_layout(arena, (size_t)cap);
-	float *W1 = w, *B1 = W1 + 400, *W2 = B1 + 16, *B2 = W2 + 16384, *W3 = B2 + 64, *B3 = W3 + (size_t)2304 * 2048, *W4 = B3 + 2048, *B4 = W4 + (size_t)2048 * 2304;
+	const cnnb_layout<float> L = cnnb_layout_of(w);
 	tb_index ix;
 	for (int b = 0; b < n; b++) ix.v[b] = index[b];
 	for (int b = n; b < HT_TRAIN_MAX_BATCH; b++) ix.v[b] = 0;
 	const int groups = (n + TB_GS - 1) / TB_GS;
 	hipLaunchKernelGGL(k_tb_set_index, dim3(1), dim3(256), 0, s, ix, n, A.idx);
 	// forward
-	hipLaunchKernelGGL(k_tb_conv1_tanh_pool, dim3(15, 16, n), dim3(256), 0, s, inputs, A.idx, W1, B1, A.a3, A.r1);
-	hipLaunchKernelGGL(k_tb_conv2_tanh_pool, dim3(64, n), dim3(192), 0, s, A.a3, W2, B2, A.a6, A.r3);
-	ht_launch_fc_rowmajor(A.a6, W3, B3, A.a8, n, 2048, 2304, true, s);
-	ht_launch_fc_rowmajor(A.a8, W4, B4, A.lg, n, 2304, 2048, false, s);
+	hipLaunchKernelGGL(k_tb_conv1_tanh_pool, dim3(15, 16, n), dim3(256), 0, s, inputs, A.idx, L.W1, L.B1, A.a3, A.r1);
+	hipLaunchKernelGGL(k_tb_conv2_tanh_pool, dim3(64, n), dim3(192), 0, s, A.a3, L.W2, L.B2, A.a6, A.r3);
+	ht_launch_fc_rowmajor(A.a6, L.W3, L.B3, A.a8, n, 2048, 2304, true, s);
+	ht_launch_fc_rowmajor(A.a8, L.W4, L.B4, A.lg, n, 2304, 2048, false, s);
 	hipLaunchKernelGGL(k_tb_softmax_loss, dim3(n), dim3(256), 0, s, A.lg, targets, A.idx, A.e9, mse_out ? mse_out : A.sink);
 	// backward with the old weights, then each layer's step
-	tb_fc_back<true>(A.e9, W4, A.a8, A.e7, n, 2048, 2304, s);
-	hipLaunchKernelGGL(k_tb_fc_wgrad, dim3(2304 / 128, 2048 / 32), dim3(256), 0, s, W4, B4, A.a8, A.e9, n, 2048, 2304, alpha);
-	tb_fc_back<false>(A.e7, W3, nullptr, A.e6, n, 2304, 2048, s);
-	hipLaunchKernelGGL(k_tb_fc_wgrad, dim3(2048 / 128, 2304 / 32), dim3(256), 0, s, W3, B3, A.a6, A.e7, n, 2304, 2048, alpha);
-	hipLaunchKernelGGL(k_tb_conv2_back, dim3(16, n), dim3(256), 0, s, A.a6, A.r3, A.e6, W2, A.e3);
+	tb_fc_back<true>(A.e9, L.W4, A.a8, A.e7, n, 2048, 2304, s);
+	hipLaunchKernelGGL(k_tb_fc_wgrad, dim3(2304 / 128, 2048 / 32), dim3(256), 0, s, L.W4, L.B4, A.a8, A.e9, n, 2048, 2304, alpha);
+	tb_fc_back<false>(A.e7, L.W3, nullptr, A.e6, n, 2304, 2048, s);
+	hipLaunchKernelGGL(k_tb_fc_wgrad, dim3(2048 / 128, 2304 / 32), dim3(256), 0, s, L.W3, L.B3, A.a6, A.e7, n, 2304, 2048, alpha);
+	hipLaunchKernelGGL(k_tb_conv2_back, dim3(16, n), dim3(256), 0, s, A.a6, A.r3, A.e6, L.W2, A.e3);
 	hipLaunchKernelGGL(k_tb_conv_grad, dim3(32, groups), dim3(256), 0, s, inputs, A.idx, A.a3, A.r1, A.a6, A.r3, A.e6, A.e3, n, alpha, A.pw);
-	hipLaunchKernelGGL(k_tb_conv_apply, dim3((TB_PW + 255) / 256), dim3(256), 0, s, A.pw, groups, W1, B1, W2, B2, W2p);
+	hipLaunchKernelGGL(k_tb_conv_apply, dim3((TB_PW + 255) / 256), dim3(256), 0, s, A.pw, groups, L.W1, L.B1, L.W2, L.B2, W2p);
 }

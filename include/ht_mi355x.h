@@ -210,6 +210,8 @@ int ht_contact_capacity(ht_ctx *ctx, int *samples_bound, int *patches_bound, int
  * ht_cnn_train        replaces  float CNN::Train(const std::vector<float> &x, const std::vector<float> &t, float alpha) (cnn.h:558-580) called for
  *                     n samples in sequence (batch-1 SGD as train-cnn.cpp:156-162 does with alpha = 0.001): inputs [n][4096], targets
  *                     [n][2304], mse_out [n] (optional) = the value Train returns for each sample.  The context's weights are updated in place.
+ *                     The arrays are staged through a device buffer of the context that follows the largest call of ht_cnn_train / ht_cnn_train_batch and
+ *                     is kept until ht_destroy: n * 6401 floats.
  * ht_cnn_get_weights  replaces  CNN::saveb (cnn.h:591-593): the weights in .cnnb order.
  * ht_expected_cnn     replaces  GatherHandExpectedCNN(pose, hcam).cnn_expected (handtrack.h:160-173), host only: pose [17][7] and the TILE
  *                     camera [12] (the heat-map camera camsub(cam, 4) is formed inside) -> expected [2304]. */
@@ -256,6 +258,7 @@ int ht_cnn_train_dev(ht_ctx *ctx, const float *d_inputs, const float *d_targets,
  *                          refused call (HT_ERR_ARG, the message names the argument; also without weights of the 64x64-input net, the only one trained) leaves the context as it was.
  * ht_cnn_train_batch       the same on host arrays inputs [n][4096], targets [n][2304], mse_out [n] (optional): an upload, then steps of `batch`
  *                          samples in order; when n is no multiple of batch the remainder forms a last, smaller step.
+ *                          Staged through the same buffer as ht_cnn_train (n * 6401 floats, kept by the context until ht_destroy).
  * ht_debug_train_batch_buffers  test aid: the latest step's per-sample tensors, n = that step's sample count (HT_ERR_ARG otherwise): a3 [n][3600],
  *                          a6 [n][2304], a8 [n][2048], e9 [n][2304], e7 [n][2048], e6 [n][2304], e3 [n][3600] (conv2's backward, summed over its groups). */
 #define HT_TRAIN_MAX_BATCH 256

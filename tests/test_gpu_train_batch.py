@@ -85,7 +85,8 @@ def test_every_weight_and_every_sample_tensor_matches_float64(name, runs, refs):
 
 
 def test_a_batch_of_one_is_cnn_train(runs, refs, weights):
-    """two implementations of one function: ht_cnn_train_batch with batch = 1 against ht_cnn_train on the same sample, under the same rule"""
+    """two implementations of one function: ht_cnn_train_batch with batch = 1 against ht_cnn_train on the same sample, under the same rule;
+    the pooled outputs of both convolutions, which the two steps compute with shared code, bit for bit"""
     from hand_tracking_samples_amd import native
     x, t = tb.pool_arrays("S1", weights)
     ctx = native.Context(ol.MODEL, 1)
@@ -93,6 +94,7 @@ def test_a_batch_of_one_is_cnn_train(runs, refs, weights):
         ctx.load_weights(tb.start_weights("seed", weights))
         mse = ctx.cnn_train(x, t, tb.BATCHES["S1"]["alpha"])
         w1 = ctx.cnn_get_weights()
+        buf1 = ctx.cnn_train_buffers()
     finally:
         ctx.close()
     step = refs["S1"][0]
@@ -106,6 +108,9 @@ def test_a_batch_of_one_is_cnn_train(runs, refs, weights):
     d, b = abs(float(mse[0]) - float(runs["S1"]["mse"][0])), step["samples"][0]["bound"]["mse"]
     print("  loss %.3e %.3e" % (d, b))
     assert not bad and d <= b, (bad, d, b)
+    # both convolutions forward are one piece of code for the two steps (csrc/ht_train_shared.hpp): the same bits from the same weights
+    for T in ("a3", "a6"):
+        assert np.array_equal(buf1[T].reshape(-1), runs["S1"]["buf"][T][0].reshape(-1)), T
 
 
 def test_the_same_call_gives_the_same_bits(runs, weights):
