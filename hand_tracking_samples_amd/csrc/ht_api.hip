@@ -257,13 +257,18 @@ extern "C" int ht_scale(ht_ctx *ctx, float s)
 }
 // Training on the weights held by the context; ht_cnn_get_weights reads them back in .cnnb order (CNN::saveb cnn.h:591-593).  Two step implementations, chosen by
 // the entry point: CNN::Train (cnn.h:558-580), one SGD step per sample in the order given (train-cnn.cpp:156-162 calls it with alpha = 0.001; ht_train.hip), and
-// mini-batch steps w' = w - alpha * sum_b g_b(w) (ht_train_batch.hip).  `batched` says which; the per-sample forms are checked as steps of batch = 1.
+// mini-batch steps w' = w - alpha * sum_b g_b(w) (ht_train_batch.hip).  `batched` says which; the per-sample forms are checked as steps of batch = 1.  The mini-batch
+// step trains either net (side = 64 or 128, the *_sized entry points), the per-sample step the 64x64-input net only.
 // The arguments are checked completely before an arena or the staging buffer grows or anything is launched.
-static int cnn_train_check(ht_ctx *ctx, const char *fn, bool batched, const void *in, const void *tg, int n_pool, const int *order, int n_steps, int batch)
+static int cnn_train_check(ht_ctx *ctx, const char *fn, bool batched, int side, const void *in, const void *tg, int n_pool, const int *order, int n_steps, int batch)
 {
 	const std::string f(fn);
-	if (!ctx->have_weights && !batched) { ctx->err = "CNN weights not loaded (ht_cnn_load_weights)"; return HT_ERR_STATE; }
-	if (!ctx->have_weights) { ctx->err = f + ": the context holds no weights of the 64x64-input net (ht_cnn_load_weights); the 128x128-input net is not trained"; return HT_ERR_ARG; }
+	if (side == 128) { if (!ctx->have_weights128) { ctx->err = f + ": the context holds no weights of the 128x128-input net (ht_cnn_load_weights_sized)"; return HT_ERR_ARG; } }
+	else
+	{
+		if (!ctx->have_weights && !batched) { ctx->err = "CNN weights not loaded (ht_cnn_load_weights)"; return HT_ERR_STATE; }
+		if (!ctx->have_weights) { ctx->err = f + ": the context holds no weights of the 64x64-input net (ht_cnn_load_weights); the 128x128-input net is trained by ht_cnn_train_batch_sized"; return HT_ERR_ARG; }
+	}
 	if (batch < 1 || batch > HT_TRAIN_MAX_BATCH) { ctx->err = f + ": batch must be in [1, HT_TRAIN_MAX_BATCH = " + std::to_string(HT_TRAIN_MAX_BATCH) + "]"; return HT_ERR_ARG; }
 	if (!in || !tg) { ctx->err = f + ": inputs and targets must not be NULL"; return HT_ERR_ARG; }
 	if (n_pool < 1) { ctx->err = f + ": n_pool must be positive"; return HT_ERR_ARG; }
@@ -272,12 +277,20 @@ static int cnn_train_check(ht_ctx *ctx, const char *fn, bool batched, const void
 	if (order) for (long long k = 0; k < (long long)n_steps * batch; k++) if (order[k] < 0 || order[k] >= n_pool) { ctx->err = f + ": order[" + std::to_string(k) + "] is outside [0, n_pool)"; return HT_ERR_ARG; }
 	return HT_OK;
 }
+// the mini-batch arena of either net: the buffer, its capacity in samples and the latest step's sample count
+struct cnn_train_arena { float **buf; int *cap, *last; };
+static cnn_train_arena cnn_train_arena_of(ht_ctx *ctx, int side)
+{
+	if (side == 128) return { &ctx->d_train_batch128, &ctx->train_batch_cap128, &ctx->train_batch_last128 };
+	return { &ctx->d_train_batch, &ctx->train_batch_cap, &ctx->train_batch_last };
+}
 // The steps on device pools over n_samples indices (order, or 0, 1, ...), checked by the caller.  Per sample: step k trains on index k; the training arena ends with
 // a sink for the per-step MSE when the caller asks for none.  Batched: steps of `batch` indices, the last step takes what is left.  Then, once, the forward
-// kernels' packed copy of the last layer follows the trained weights.
-static int cnn_train_steps(ht_ctx *ctx, bool batched, const float *d_x, const float *d_t, const int *order, int n_samples, int batch, float alpha, float *d_mse, hipStream_t s)
+// kernels' packed copy of the trained net's last layer follows the trained weights.
+static int cnn_train_steps(ht_ctx *ctx, bool batched, int side, const float *d_x, const float *d_t, const int *order, int n_samples, int batch, float alpha, float *d_mse, hipStream_t s)
 {
-	float *w = ctx->d_weights, *W2p = ctx->d_weights + HT_CNNB_COUNT;
+	const ht_cnn_weights &cw = side == 128 ? ctx->cnnw128 : ctx->cnnw;
+	float *w = side == 128 ? ctx->d_weights128 : ctx->d_weights, *W2p = w + (side == 128 ? HT_CNNB128_COUNT : HT_CNNB_COUNT);
 	if (!batched)
 	{
 		const size_t na = ht_train_act_floats(), ne = ht_train_err_floats(), np = ht_train_part_floats();
@@ -292,79 +305,116 @@ static int cnn_train_steps(ht_ctx *ctx, bool batched, const float *d_x, const fl
 	else
 	{
 		const int cap = (batch + 31) & ~31;
-		{ const int r = dev_grow(ctx, &ctx->d_train_batch, &ctx->train_batch_cap, (size_t)cap, ht_train_batch_floats(cap) / (size_t)cap + 1); if (r) return r; }
+		const cnn_train_arena ar = cnn_train_arena_of(ctx, side);
+		{ const int r = dev_grow(ctx, ar.buf, ar.cap, (size_t)cap, ht_train_batch_floats(cap, side) / (size_t)cap + 1); if (r) return r; }
 		int index[HT_TRAIN_MAX_BATCH];
 		for (int k = 0; k < n_samples; k += batch)
 		{
 			const int n = n_samples - k < batch ? n_samples - k : batch;
 			for (int b = 0; b < n; b++) index[b] = order ? order[k + b] : k + b;
-			ht_launch_train_batch_step(w, W2p, d_x, d_t, index, n, alpha, ctx->d_train_batch, ctx->train_batch_cap, d_mse ? d_mse + k : nullptr, s);
-			ctx->train_batch_last = n;
+			ht_launch_train_batch_step(w, W2p, d_x, d_t, index, n, alpha, *ar.buf, *ar.cap, d_mse ? d_mse + k : nullptr, s, side);
+			*ar.last = n;
 		}
 	}
-	ht_launch_pack_w4(ctx->cnnw.W4, W2p + 16384, s);
+	ht_launch_pack_w4(cw.W4, W2p + 16384, s);
 	HIPCHK(ctx, hipGetLastError());
 	return HT_OK;
 }
 // the device-pool forms: asynchronous on the caller's stream
-static int cnn_train_dev(ht_ctx *ctx, const char *fn, bool batched, const float *d_inputs, const float *d_targets, int n_pool, const int *order, int n_steps, int batch, float alpha, float *d_mse, void *stream)
+static int cnn_train_dev(ht_ctx *ctx, const char *fn, bool batched, int side, const float *d_inputs, const float *d_targets, int n_pool, const int *order, int n_steps, int batch, float alpha, float *d_mse, void *stream)
 {
-	{ const int r = cnn_train_check(ctx, fn, batched, d_inputs, d_targets, n_pool, order, n_steps, batch); if (r) return r; }
+	{ const int r = cnn_train_check(ctx, fn, batched, side, d_inputs, d_targets, n_pool, order, n_steps, batch); if (r) return r; }
 	if (n_steps == 0) return HT_OK;
-	return cnn_train_steps(ctx, batched, d_inputs, d_targets, order, n_steps * batch, batch, alpha, d_mse, ht_user_stream(ctx, stream));
+	return cnn_train_steps(ctx, batched, side, d_inputs, d_targets, order, n_steps * batch, batch, alpha, d_mse, ht_user_stream(ctx, stream));
 }
 // the host-array forms: the n samples staged through the context's buffer (ht_staged_call), then the same steps in order on the context's stream
-static int cnn_train_host(ht_ctx *ctx, const char *fn, bool batched, const float *inputs, const float *targets, int n, int batch, float alpha, float *mse_out)
+static int cnn_train_host(ht_ctx *ctx, const char *fn, bool batched, int side, const float *inputs, const float *targets, int n, int batch, float alpha, float *mse_out)
 {
-	{ const int r = cnn_train_check(ctx, fn, batched, inputs, targets, n, nullptr, 0, batch); if (r) return r; }
-	ht_seg seg[3] = { { (void *)inputs, (size_t)n * HT_CNN_IN * sizeof(float), false }, { (void *)targets, (size_t)n * HT_CNN_OUT * sizeof(float), false }, { mse_out, (size_t)n * sizeof(float), true } };
+	{ const int r = cnn_train_check(ctx, fn, batched, side, inputs, targets, n, nullptr, 0, batch); if (r) return r; }
+	ht_seg seg[3] = { { (void *)inputs, (size_t)n * side * side * sizeof(float), false }, { (void *)targets, (size_t)n * HT_CNN_OUT * sizeof(float), false }, { mse_out, (size_t)n * sizeof(float), true } };
 	return ht_staged_call(ctx, &ctx->d_train_io, &ctx->train_io_cap, seg, 3, [&](hipStream_t s)
-	                      { return cnn_train_steps(ctx, batched, (const float *)seg[0].dev, (const float *)seg[1].dev, nullptr, n, batch, alpha, (float *)seg[2].dev, s); });
+	                      { return cnn_train_steps(ctx, batched, side, (const float *)seg[0].dev, (const float *)seg[1].dev, nullptr, n, batch, alpha, (float *)seg[2].dev, s); });
 }
 extern "C" int ht_cnn_train_dev(ht_ctx *ctx, const float *d_inputs, const float *d_targets, int n_pool, const int *order, int n_steps, float alpha, float *d_mse, void *stream)
 {
 	CHECK_READY(ctx);
-	return cnn_train_dev(ctx, "ht_cnn_train_dev", false, d_inputs, d_targets, n_pool, order, n_steps, 1, alpha, d_mse, stream);
+	return cnn_train_dev(ctx, "ht_cnn_train_dev", false, 64, d_inputs, d_targets, n_pool, order, n_steps, 1, alpha, d_mse, stream);
 }
 extern "C" int ht_cnn_train(ht_ctx *ctx, const float *inputs, const float *targets, int n, float alpha, float *mse_out)
 {
 	CHECK_READY(ctx);
-	return cnn_train_host(ctx, "ht_cnn_train", false, inputs, targets, n, 1, alpha, mse_out);
+	return cnn_train_host(ctx, "ht_cnn_train", false, 64, inputs, targets, n, 1, alpha, mse_out);
 }
 extern "C" int ht_cnn_train_batch_dev(ht_ctx *ctx, const float *d_inputs, const float *d_targets, int n_pool, const int *order, int n_steps, int batch, float alpha, float *d_mse, void *stream)
 {
 	CHECK_READY(ctx);
-	return cnn_train_dev(ctx, "ht_cnn_train_batch_dev", true, d_inputs, d_targets, n_pool, order, n_steps, batch, alpha, d_mse, stream);
+	return cnn_train_dev(ctx, "ht_cnn_train_batch_dev", true, 64, d_inputs, d_targets, n_pool, order, n_steps, batch, alpha, d_mse, stream);
 }
 extern "C" int ht_cnn_train_batch(ht_ctx *ctx, const float *inputs, const float *targets, int n, int batch, float alpha, float *mse_out)
 {
 	CHECK_READY(ctx);
-	return cnn_train_host(ctx, "ht_cnn_train_batch", true, inputs, targets, n, batch, alpha, mse_out);
+	return cnn_train_host(ctx, "ht_cnn_train_batch", true, 64, inputs, targets, n, batch, alpha, mse_out);
 }
-// Test aid: the per-sample tensors of the latest mini-batch step (layout: ht_train_batch_views, csrc/ht_train_batch.hip)
-extern "C" int ht_debug_train_batch_buffers(ht_ctx *ctx, int n, float *a3, float *a6, float *a8, float *e9, float *e7, float *e6, float *e3)
+// Test aid: the per-sample tensors of the latest mini-batch step of a net (layout: ht_train_batch_views, csrc/ht_train_batch.hip)
+static int cnn_train_batch_buffers(ht_ctx *ctx, const char *fn, int side, int n, float *const out[7])
 {
-	CHECK_READY(ctx);
-	float *out[7] = { a3, a6, a8, e9, e7, e6, e3 };
-	static const size_t per[7] = { 3600, 2304, 2048, 2304, 2048, 2304, 3600 };
-	for (int i = 0; i < 7; i++) if (!out[i]) { ctx->err = "ht_debug_train_batch_buffers: NULL output"; return HT_ERR_ARG; }
-	if (!ctx->d_train_batch || ctx->train_batch_last < 1) { ctx->err = "ht_debug_train_batch_buffers: no mini-batch step has run"; return HT_ERR_STATE; }
-	if (n != ctx->train_batch_last) { ctx->err = "ht_debug_train_batch_buffers: n must be the latest step's sample count, " + std::to_string(ctx->train_batch_last); return HT_ERR_ARG; }
+	const std::string f(fn);
+	const cnn_train_arena ar = cnn_train_arena_of(ctx, side);
+	for (int i = 0; i < 7; i++) if (!out[i]) { ctx->err = f + ": NULL output"; return HT_ERR_ARG; }
+	if (!*ar.buf || *ar.last < 1) { ctx->err = f + ": no mini-batch step has run"; return HT_ERR_STATE; }
+	if (n != *ar.last) { ctx->err = f + ": n must be the latest step's sample count, " + std::to_string(*ar.last); return HT_ERR_ARG; }
 	HIPCHK(ctx, ht_sync_all(ctx));
-	const float *view[7];
-	ht_train_batch_views(ctx->d_train_batch, ctx->train_batch_cap, view);
+	const float *view[7]; size_t per[7];
+	ht_train_batch_views(*ar.buf, *ar.cap, view, per, side);
 	for (int i = 0; i < 7; i++) HIPCHK(ctx, hipMemcpy(out[i], view[i], (size_t)n * per[i] * sizeof(float), hipMemcpyDeviceToHost));
 	return HT_OK;
 }
-extern "C" int ht_cnn_get_weights(ht_ctx *ctx, float *w, size_t n)
+extern "C" int ht_debug_train_batch_buffers(ht_ctx *ctx, int n, float *a3, float *a6, float *a8, float *e9, float *e7, float *e6, float *e3)
 {
 	CHECK_READY(ctx);
+	float *const out[7] = { a3, a6, a8, e9, e7, e6, e3 };
+	return cnn_train_batch_buffers(ctx, "ht_debug_train_batch_buffers", 64, n, out);
+}
+static int cnn_get_weights(ht_ctx *ctx, int side, float *w, size_t n)
+{
 	if (!w) return HT_ERR_ARG;
-	if (!ctx->have_weights) { ctx->err = "no weights to read"; return HT_ERR_STATE; }
-	if (n != HT_CNNB_COUNT) { ctx->err = "weights: expected HT_CNNB_COUNT fp32 values in .cnnb order"; return HT_ERR_ARG; }
+	if (!(side == 128 ? ctx->have_weights128 : ctx->have_weights)) { ctx->err = "no weights to read"; return HT_ERR_STATE; }
+	if (n != (side == 128 ? (size_t)HT_CNNB128_COUNT : (size_t)HT_CNNB_COUNT)) { ctx->err = side == 128 ? "weights: expected HT_CNNB128_COUNT fp32 values in .cnnb order" : "weights: expected HT_CNNB_COUNT fp32 values in .cnnb order"; return HT_ERR_ARG; }
 	HIPCHK(ctx, ht_sync_all(ctx));      // also a ht_cnn_train_dev on a caller's stream
-	HIPCHK(ctx, hipMemcpy(w, ctx->d_weights, n * sizeof(float), hipMemcpyDeviceToHost));
+	HIPCHK(ctx, hipMemcpy(w, side == 128 ? ctx->d_weights128 : ctx->d_weights, n * sizeof(float), hipMemcpyDeviceToHost));
 	return HT_OK;
+}
+extern "C" int ht_cnn_get_weights(ht_ctx *ctx, float *w, size_t n) { CHECK_READY(ctx); return cnn_get_weights(ctx, 64, w, n); }
+// The sized forms: side = 64 is the entry point above, side = 128 the same path on the larger net's weights, pools of [..][16384] inputs and an arena of its own
+#define CHECK_SIDE(ctx, side) do { if ((side) != 128) { (ctx)->err = "CNN input side must be 64 or 128"; return HT_ERR_ARG; } } while (0)
+extern "C" int ht_cnn_train_batch_sized_dev(ht_ctx *ctx, int side, const float *d_inputs, const float *d_targets, int n_pool, const int *order, int n_steps, int batch, float alpha, float *d_mse, void *stream)
+{
+	CHECK_READY(ctx);
+	if (side == 64) return ht_cnn_train_batch_dev(ctx, d_inputs, d_targets, n_pool, order, n_steps, batch, alpha, d_mse, stream);
+	CHECK_SIDE(ctx, side);
+	return cnn_train_dev(ctx, "ht_cnn_train_batch_sized_dev", true, 128, d_inputs, d_targets, n_pool, order, n_steps, batch, alpha, d_mse, stream);
+}
+extern "C" int ht_cnn_train_batch_sized(ht_ctx *ctx, int side, const float *inputs, const float *targets, int n, int batch, float alpha, float *mse_out)
+{
+	CHECK_READY(ctx);
+	if (side == 64) return ht_cnn_train_batch(ctx, inputs, targets, n, batch, alpha, mse_out);
+	CHECK_SIDE(ctx, side);
+	return cnn_train_host(ctx, "ht_cnn_train_batch_sized", true, 128, inputs, targets, n, batch, alpha, mse_out);
+}
+extern "C" int ht_debug_train_batch_buffers_sized(ht_ctx *ctx, int side, int n, float *a3, float *a6, float *a8, float *e9, float *e7, float *e6, float *e3)
+{
+	CHECK_READY(ctx);
+	if (side == 64) return ht_debug_train_batch_buffers(ctx, n, a3, a6, a8, e9, e7, e6, e3);
+	CHECK_SIDE(ctx, side);
+	float *const out[7] = { a3, a6, a8, e9, e7, e6, e3 };
+	return cnn_train_batch_buffers(ctx, "ht_debug_train_batch_buffers_sized", 128, n, out);
+}
+extern "C" int ht_cnn_get_weights_sized(ht_ctx *ctx, int side, float *w, size_t n)
+{
+	CHECK_READY(ctx);
+	if (side == 64) return ht_cnn_get_weights(ctx, w, n);
+	CHECK_SIDE(ctx, side);
+	return cnn_get_weights(ctx, 128, w, n);
 }
 // Test aid: the layer outputs and the errors of the training arena as the latest step left them (layout: ht_launch_train_step, csrc/ht_train.hip)
 extern "C" int ht_debug_train_buffers(ht_ctx *ctx, float *act, size_t n_act, float *err, size_t n_err)

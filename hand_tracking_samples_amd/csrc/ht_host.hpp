@@ -57,6 +57,7 @@ struct ht_ctx
 	float *d_weights128 = nullptr, *d_in128 = nullptr, *d_act1_128 = nullptr, *d_act2_128 = nullptr;
 	std::vector<float> h_bodyc, h_jointc;
 	std::vector<float4> h_verts, h_planes;                        // host copies of the model geometry (ht_scale rewrites them)
+	float *d_train_batch128 = nullptr; int train_batch_cap128 = 0, train_batch_last128 = 0;      // the same for the 128x128-input net (ht_cnn_train_batch_sized*), not allocated before its first step
 	float *d_train_batch = nullptr; int train_batch_cap = 0, train_batch_last = 0;      // mini-batch training arena (ht_train_batch.hip) for train_batch_cap samples, grown to the largest batch seen (dev_grow); samples of the latest step
 	float *d_train = nullptr;                                    // training arena: layer outputs, errors, split-K partial sums (allocated on first use)
 	char *d_train_io = nullptr; size_t train_io_cap = 0;         // ht_cnn_train's and ht_cnn_train_batch's staging (inputs, targets, per-sample MSE), grown to the largest call (dev_grow)

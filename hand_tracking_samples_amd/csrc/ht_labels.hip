@@ -27,7 +27,7 @@
 __device__ __forceinline__ long long lb_trunc(float f) { return (f >= -2147483648.0f && f < 2147483648.0f) ? (long long)(int)f : (long long)INT_MIN; }
 __device__ __forceinline__ unsigned char lb_gray(float x) { float v = x * 255.0f; v = fmin_std(fmax_std(v, 0.0f), 255.0f); return (unsigned char)v; }      // gray_of
 
-__global__ __launch_bounds__(LB_THREADS) void k_expected_cnn(const float *__restrict__ poses, const float *__restrict__ cams, int nb, int B, int segment_frame,
+__global__ __launch_bounds__(LB_THREADS) void k_expected_cnn(const float *__restrict__ poses, const float *__restrict__ cams, int nb, int B, int segment_frame, float sub,
                                                              float *__restrict__ expected, float *__restrict__ image_points, float *__restrict__ vals_out)
 {
 	__shared__ __attribute__((aligned(16))) unsigned char img[LB_FRAMES][HT_CNN_OUT];
@@ -58,7 +58,7 @@ __global__ __launch_bounds__(LB_THREADS) void k_expected_cnn(const float *__rest
 		const int k = lane;
 		const int b = k == 0 || k == 1 || k == 2 ? 1 : 3 * k - 5;      // fbone = { 1, 1, 1, 4, 7, 10, 13, 16 }
 		const v3 off = V3(k == 1 ? -0.03f : k == 2 ? 0.03f : 0.0f, 0.0f, k == 1 || k == 2 ? -0.03f : 0.0f);
-		const float fx = cam[0] / 4.0f, fy = cam[1] / 4.0f, px = cam[2] / 4.0f, py = cam[3] / 4.0f;      // hcam = camsub(cam, 4)
+		const float fx = cam[0] / sub, fy = cam[1] / sub, px = cam[2] / sub, py = cam[3] / sub;      // hcam = camsub(cam, sub): 4 of a 64x64 tile, 8 of a 128x128 one (HT_LABELS_SIDE128)
 		const v3 v = apply(ci, apply(P(b), off));
 		const float ux = v.x / v.z * fx + px, uy = v.y / v.z * fy + py;
 		if (image_points) { image_points[(size_t)f * 16 + 2 * k] = ux; image_points[(size_t)f * 16 + 2 * k + 1] = uy; }
@@ -133,12 +133,12 @@ extern "C" int ht_expected_cnn_dev(ht_ctx *ctx, const float *d_poses, const floa
 {
 	CHECK_READY(ctx);
 	{ const int r = lb_check_args(ctx, d_poses, d_cams, B, d_expected); if (r) return r; }
-	if (flags & ~HT_LABELS_SEGMENT_FRAME) { ctx->err = "ht_expected_cnn: unknown flags"; return HT_ERR_ARG; }
+	if (flags & ~(HT_LABELS_SEGMENT_FRAME | HT_LABELS_SIDE128)) { ctx->err = "ht_expected_cnn: unknown flags"; return HT_ERR_ARG; }
 	if (((uintptr_t)d_expected & 15) != 0) { ctx->err = "ht_expected_cnn_dev: d_expected must be 16-byte aligned (the labels are written as float4 rows)"; return HT_ERR_ARG; }
 	if (B == 0) return HT_OK;
 	hipStream_t s = ht_user_stream(ctx, stream);
 	const int blocks = (int)(((long long)B + LB_FRAMES - 1) / LB_FRAMES);
-	hipLaunchKernelGGL(k_expected_cnn, dim3(blocks), dim3(LB_THREADS), 0, s, d_poses, d_cams, ctx->model.nb, B, (flags & HT_LABELS_SEGMENT_FRAME) ? 1 : 0, d_expected, d_image_points, d_vals);
+	hipLaunchKernelGGL(k_expected_cnn, dim3(blocks), dim3(LB_THREADS), 0, s, d_poses, d_cams, ctx->model.nb, B, (flags & HT_LABELS_SEGMENT_FRAME) ? 1 : 0, (flags & HT_LABELS_SIDE128) ? 8.0f : 4.0f, d_expected, d_image_points, d_vals);
 	HIPCHK(ctx, hipGetLastError());
 	return HT_OK;
 }
@@ -148,7 +148,7 @@ extern "C" int ht_expected_cnn_batch(ht_ctx *ctx, const float *poses, const floa
 {
 	CHECK_READY(ctx);
 	{ const int r = lb_check_args(ctx, poses, cams, B, expected); if (r) return r; }
-	if (flags & ~HT_LABELS_SEGMENT_FRAME) { ctx->err = "ht_expected_cnn: unknown flags"; return HT_ERR_ARG; }
+	if (flags & ~(HT_LABELS_SEGMENT_FRAME | HT_LABELS_SIDE128)) { ctx->err = "ht_expected_cnn: unknown flags"; return HT_ERR_ARG; }
 	if (B == 0) return HT_OK;
 	const size_t n = (size_t)B;
 	ht_seg seg[5] = { { (void *)poses, n * ctx->model.nb * HT_POSE * sizeof(float), false }, { (void *)cams, n * HT_CAM * sizeof(float), false },
@@ -167,6 +167,21 @@ extern "C" int ht_cnn_input_dev(ht_ctx *ctx, const uint16_t *d_tiles, const floa
 	hipStream_t s = ht_user_stream(ctx, stream);
 	const ht_prepare_extra pz = { nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr };
 	ht_launch_prepare(d_tiles, d_cams, ctx->par.drangey, ctx->par.subsample_fraction, d_cnn_in, nullptr, nullptr, 0, B, s, &pz);
+	HIPCHK(ctx, hipGetLastError());
+	return HT_OK;
+}
+// the same for side x side tiles; side = 128: the whole-frame transform that ht_update_direct_* feeds the 128x128-input net with (k_cnn_input)
+extern "C" int ht_cnn_input_sized_dev(ht_ctx *ctx, int side, const uint16_t *d_tiles, const float *d_cams, int B, float *d_cnn_in, void *stream)
+{
+	CHECK_READY(ctx);
+	if (side == 64) return ht_cnn_input_dev(ctx, d_tiles, d_cams, B, d_cnn_in, stream);
+	if (side != 128) { ctx->err = "CNN input side must be 64 or 128"; return HT_ERR_ARG; }
+	if (!d_tiles || !d_cams || !d_cnn_in || B < 0) { ctx->err = "ht_cnn_input_sized_dev: bad argument"; return HT_ERR_ARG; }
+	if (((uintptr_t)d_tiles & 15) != 0 || ((uintptr_t)d_cnn_in & 15) != 0) { ctx->err = "ht_cnn_input_sized_dev: d_tiles and d_cnn_in must be 16-byte aligned (the input transform reads eight pixels per 128-bit load and writes float4)"; return HT_ERR_ARG; }
+	if (B == 0) return HT_OK;
+	hipStream_t s = ht_user_stream(ctx, stream);
+	for (int b0 = 0; b0 < B; b0 += 32768)      // (a launch takes one tile per block row, at most 65535)
+		ht_launch_cnn_input(d_tiles + (size_t)b0 * HT_CNN128_IN, d_cams + (size_t)b0 * HT_CAM, HT_CNN128_IN, ctx->par.drangey, d_cnn_in + (size_t)b0 * HT_CNN128_IN, B - b0 < 32768 ? B - b0 : 32768, s);
 	HIPCHK(ctx, hipGetLastError());
 	return HT_OK;
 }

@@ -27,20 +27,21 @@ __global__ __launch_bounds__(256) void k_tb_set_index(tb_index ix, int n, int *_
 {
 	if ((int)threadIdx.x < n) idx[threadIdx.x] = ix.v[threadIdx.x];
 }
-// conv1 + tanh (t_conv1_out) + the two max-pools (-> 15x15), k_t_conv1_tanh_pool per sample (blockIdx.z).  Of the 60x60 map
-// only the pooled value a3 and r1 = the input position (y * 64 + x) of the conv output that won both pools are kept.
-__global__ __launch_bounds__(256) void k_tb_conv1_tanh_pool(const float *__restrict__ pool, const int *__restrict__ idx, const float *__restrict__ W, const float *__restrict__ B, float *__restrict__ a3, int *__restrict__ r1)
+// conv1 + tanh (t_conv1_out) + the two max-pools (-> P2 x P2), k_t_conv1_tanh_pool per sample (blockIdx.z) for the net of input side S (cnn_dims).  Of the
+// C1 x C1 map only the pooled value a3 and r1 = the input position (y * S + x) of the conv output that won both pools are kept.
+template <int S> __global__ __launch_bounds__(256) void k_tb_conv1_tanh_pool(const float *__restrict__ pool, const int *__restrict__ idx, const float *__restrict__ W, const float *__restrict__ B, float *__restrict__ a3, int *__restrict__ r1)
 {
-	__shared__ float s_o[4][60];
+	typedef cnn_dims<S> D;
+	__shared__ float s_o[4][D::C1];
 	const int py = blockIdx.x, oz = blockIdx.y, b = blockIdx.z, t = threadIdx.x;
-	const float *in = pool + (size_t)idx[b] * HT_CNN_IN;
-	if (t < 240)
+	const float *in = pool + (size_t)idx[b] * (S * S);
+	for (int e = t; e < 4 * D::C1; e += 256)
 	{
-		const int r = t / 60, x = t % 60, y = 4 * py + r;
-		s_o[r][x] = t_conv1_out(in, W, B, oz, y, x);
+		const int r = e / D::C1, x = e % D::C1, y = 4 * py + r;
+		s_o[r][x] = t_conv1_out<S>(in, W, B, oz, y, x);
 	}
 	__syncthreads();
-	if (t < 15)
+	if (t < D::P2)
 	{
 		float q[4], m;
 #pragma unroll
@@ -48,24 +49,25 @@ __global__ __launch_bounds__(256) void k_tb_conv1_tanh_pool(const float *__restr
 		const int k2 = first_max4(q[0], q[1], q[2], q[3], m);
 		const int r = 2 * (k2 >> 1), c = 4 * t + 2 * (k2 & 1);
 		const int k1 = first_max4(s_o[r][c], s_o[r][c + 1], s_o[r + 1][c], s_o[r + 1][c + 1], m);
-		const size_t o = (size_t)b * 3600 + oz * 225 + py * 15 + t;
-		a3[o] = m; r1[o] = (4 * py + r + (k1 >> 1)) * 64 + c + (k1 & 1);
+		const size_t o = (size_t)b * D::A3 + oz * D::NP2 + py * D::P2 + t;
+		a3[o] = m; r1[o] = (4 * py + r + (k1 >> 1)) * S + c + (k1 & 1);
 	}
 }
-// conv2 + tanh (t_conv2_out) + max-pool (-> 6x6), k_t_conv2_tanh_pool per sample (blockIdx.y); a6 = the pooled value,
-// r3 = which of the window's four entries (x fastest) is its first maximum
-__global__ __launch_bounds__(192) void k_tb_conv2_tanh_pool(const float *__restrict__ a3, const float *__restrict__ W, const float *__restrict__ B, float *__restrict__ a6, int *__restrict__ r3)
+// conv2 + tanh (t_conv2_out) + max-pool (-> P3 x P3), k_t_conv2_tanh_pool per sample (blockIdx.y) by NT threads; a6 = the pooled value,
+// r3 = which of the window's four entries (x fastest) is its first maximum.  The whole a3 of the sample is staged (14 KB; 61.5 KB at S = 128)
+template <int S, int NT> __global__ __launch_bounds__(NT) void k_tb_conv2_tanh_pool(const float *__restrict__ a3, const float *__restrict__ W, const float *__restrict__ B, float *__restrict__ a6, int *__restrict__ r3)
 {
-	__shared__ float s_in[3600], s_w[256], s_o[144];
+	typedef cnn_dims<S> D;
+	__shared__ float s_in[D::A3], s_w[256], s_o[D::NC2];
 	const int oz = blockIdx.x, b = blockIdx.y, t = threadIdx.x;
-	t_conv2_out(a3 + (size_t)b * 3600, W, B, oz, s_in, s_w, s_o);
+	t_conv2_out<D::P2, NT>(a3 + (size_t)b * D::A3, W, B, oz, s_in, s_w, s_o);
 	__syncthreads();
-	if (t < 36)
+	for (int e = t; e < D::NP3; e += NT)
 	{
-		const float *p = s_o + (2 * (t / 6)) * 12 + 2 * (t % 6);
+		const float *p = s_o + (2 * (e / D::P3)) * D::C2 + 2 * (e % D::P3);
 		float m;
-		const int k = first_max4(p[0], p[1], p[12], p[13], m);
-		a6[(size_t)b * 2304 + oz * 36 + t] = m; r3[(size_t)b * 2304 + oz * 36 + t] = k;
+		const int k = first_max4(p[0], p[1], p[D::C2], p[D::C2 + 1], m);
+		a6[(size_t)b * D::A6 + oz * D::NP3 + e] = m; r3[(size_t)b * D::A6 + oz * D::NP3 + e] = k;
 	}
 }
 // Output layer of sample b = blockIdx.x from its logits: chunked softmax (cnn.h:497-511), E = y - t, softmax backward (cnn.h:512-526) and the loss
@@ -164,7 +166,7 @@ template <int NB, bool FOLD> __global__ __launch_bounds__(512) void k_tb_fc_back
 }
 // Weight gradient and step of a fully connected layer: W[i,j] -= alpha * sum_b X[b,i] E[b,j], W [M][N] row-major.  The summed index is the sample:
 // lanes 0..31 hold sample 2 s, lanes 32..63 sample 2 s + 1 (zero beyond n), as 32 consecutive floats of X (A operand, i) and of E (B operand, j).
-// A wave owns one 32x32 tile of W, read before the products and rewritten once after them; a block is four tiles side by side, 4608 tiles per
+// A wave owns one 32x32 tile of W, read before the products and rewritten once after them; a block is four tiles side by side, M N / 1024 tiles per
 // matrix.  The blocks of the first tile row also step the bias, B[j] -= alpha * sum_b E[b,j], samples ascending.
 __global__ __launch_bounds__(256) void k_tb_fc_wgrad(float *__restrict__ W, float *__restrict__ B, const float *__restrict__ X, const float *__restrict__ E, int n, int M, int N, float alpha)
 {
@@ -196,32 +198,48 @@ __global__ __launch_bounds__(256) void k_tb_fc_wgrad(float *__restrict__ W, floa
 		B[j0 + r] -= alpha * sum;
 	}
 }
-// LConv::backward of conv2 (t_conv2_back_gather) for input channel iz = blockIdx.x of sample b = blockIdx.y: the 64 error maps are rebuilt in LDS
-// from the pooled error (conv2's tanh' at the kept maximum, then t_window_scatter to the kept entry), a thread owns one input position
-__global__ __launch_bounds__(256) void k_tb_conv2_back(const float *__restrict__ a6, const int *__restrict__ r3, const float *__restrict__ e6, const float *__restrict__ W, float *__restrict__ e3)
+// LConv::backward of conv2 (t_conv2_back_gather) for the IZB input channels from IZB blockIdx.x of sample b = blockIdx.y, input rows [BH z, BH z + BH) (z = blockIdx.z):
+// the rows of the 64 error maps that those positions read are rebuilt in LDS from the pooled error (conv2's tanh' at the kept maximum, then t_window_scatter to the
+// kept entry), whole pooling windows: WR window rows from row pr0.  A thread owns an input position of one channel at a time.  S = 64: one channel and one band, the
+// whole maps (36 KB); S = 128: bands of BH = 4 rows, eight map rows each (56 KB of the 196 KB that the whole maps would take), shared by IZB = 4 input channels, so
+// that a sample's bands are rebuilt 32 times, not 128.
+template <int S, int BH, int NT, int IZB> __global__ __launch_bounds__(NT) void k_tb_conv2_back(const float *__restrict__ a6, const int *__restrict__ r3, const float *__restrict__ e6, const float *__restrict__ W, float *__restrict__ e3)
 {
-	__shared__ float s_e[64 * 144], s_w[64 * 16];
-	const int iz = blockIdx.x, b = blockIdx.y, t = threadIdx.x;
-	for (int i = t; i < 2304; i += 256)
+	typedef cnn_dims<S> D;
+	static_assert(BH >= D::P2 || BH % 2 == 0, "a band starts on an even input row");
+	static_assert(16 % IZB == 0, "the input channels are dealt out evenly");
+	constexpr int WR = BH >= D::P2 ? D::P3 : (BH + 4) / 2, ROWS = 2 * WR;
+	__shared__ float s_e[64 * ROWS * D::C2], s_w[IZB * 64 * 16];
+	const int iz0 = blockIdx.x * IZB, b = blockIdx.y, y0 = blockIdx.z * BH, t = threadIdx.x;
+	const int pr0 = max(0, y0 - 3) / 2;
+	for (int i = t; i < 64 * WR * D::P3; i += NT)
 	{
-		const size_t o = (size_t)b * 2304 + i;
+		const int oz = i / (WR * D::P3), p = i % (WR * D::P3), py = pr0 + p / D::P3;
+		if (py >= D::P3) continue;
+		const size_t o = (size_t)b * D::A6 + oz * D::NP3 + py * D::P3 + p % D::P3;
 		const float m = a6[o];
-		t_window_scatter(s_e + (i / 36) * 144, i % 36, r3[o], (1.0f - m * m) * e6[o]);
+		t_window_scatter<D::C2>(s_e + oz * (ROWS * D::C2), p, r3[o], (1.0f - m * m) * e6[o]);
 	}
-	for (int i = t; i < 1024; i += 256) s_w[i] = W[(i & 15) + 16 * (iz + 16 * (i >> 4))];
+	for (int i = t; i < IZB * 1024; i += NT) { const int j = i & 1023; s_w[i] = W[(j & 15) + 16 * (iz0 + (i >> 10) + 16 * (j >> 4))]; }
 	__syncthreads();
-	if (t >= 225) return;
-	e3[(size_t)b * 3600 + iz * 225 + t] = t_conv2_back_gather<64>(s_w, s_e, t % 15, t / 15);
+	for (int e = t; e < IZB * BH * D::P2; e += NT)
+	{
+		const int q = e / (BH * D::P2), r = e % (BH * D::P2), x = r % D::P2, y = y0 + r / D::P2;
+		if (y < D::P2) e3[(size_t)b * D::A3 + (iz0 + q) * D::NP2 + y * D::P2 + x] = t_conv2_back_gather<64, D::C2, ROWS>(s_w + q * 1024, s_e, x, y, 2 * pr0);
+	}
 }
 // LConv::update (cnn.h:252-279) of both convolutions, summed over the TB_GS samples of group blockIdx.y into pw[group][TB_PW] (times -alpha).  Only one
 // entry per pooling window carries an error, so both sums run over (position, value) lists, as k_t_conv_update's conv1 branch does.
-// blocks 0..15: conv2, output channels 4 x .. 4 x + 3: a thread per tap (iz, ky, kx), 36 windows per channel.
-// blocks 16..31: conv1, output channel x - 16: t_conv1_grad_add per sample, the eight lanes of a tap added once after the group's samples.
-__global__ __launch_bounds__(256) void k_tb_conv_grad(const float *__restrict__ pool, const int *__restrict__ idx, const float *__restrict__ a3, const int *__restrict__ r1, const float *__restrict__ a6, const int *__restrict__ r3,
-                                                      const float *__restrict__ e6, const float *__restrict__ e3, int n, float alpha, float *__restrict__ pw)
+// blocks 0..15: conv2, output channels 4 x .. 4 x + 3: a thread per tap (iz, ky, kx), NP3 windows per channel (36; 196 at S = 128) over the staged a3.
+// blocks 16..31: conv1, output channel x - 16: t_conv1_grad_add per sample over the staged input, the eight lanes of a tap added once after the group's samples.
+template <int S> __global__ __launch_bounds__(256) void k_tb_conv_grad(const float *__restrict__ pool, const int *__restrict__ idx, const float *__restrict__ a3, const int *__restrict__ r1, const float *__restrict__ a6, const int *__restrict__ r3,
+                                                                       const float *__restrict__ e6, const float *__restrict__ e3, int n, float alpha, float *__restrict__ pw)
 {
-	__shared__ float s_x[4096], s_e[256];
-	__shared__ int s_i[256];
+	typedef cnn_dims<S> D;
+	constexpr int NL = ((4 * D::NP3 > D::NP2 ? 4 * D::NP3 : D::NP2) + 255) & ~255;      // the longer list: 4 channels' windows of conv2, a channel's of conv1
+	__shared__ float s_x[S * S], s_e[NL];
+	__shared__ int s_i[NL];
+	static_assert(D::A3 <= S * S, "a3 is staged where the input is");
 	const int t = threadIdx.x, b0 = blockIdx.y * TB_GS, b1 = min(n, b0 + TB_GS);
 	float *out = pw + (size_t)blockIdx.y * TB_PW;
 	if (blockIdx.x < 16)
@@ -231,21 +249,22 @@ __global__ __launch_bounds__(256) void k_tb_conv_grad(const float *__restrict__ 
 		for (int b = b0; b < b1; b++)
 		{
 			__syncthreads();
-			for (int i = t; i < 3600; i += 256) s_x[i] = a3[(size_t)b * 3600 + i];
-			if (t < 144)
+			for (int i = t; i < D::A3; i += 256) s_x[i] = a3[(size_t)b * D::A3 + i];
+			for (int e = t; e < 4 * D::NP3; e += 256)
 			{
-				const int p = t % 36, k = r3[(size_t)b * 2304 + g * 144 + t];
-				const float m = a6[(size_t)b * 2304 + g * 144 + t];
-				s_i[t] = (2 * (p / 6) + (k >> 1)) * 15 + 2 * (p % 6) + (k & 1);
-				s_e[t] = -alpha * ((1.0f - m * m) * e6[(size_t)b * 2304 + g * 144 + t]);
+				const size_t o = (size_t)b * D::A6 + g * (4 * D::NP3) + e;
+				const int p = e % D::NP3, k = r3[o];
+				const float m = a6[o];
+				s_i[e] = (2 * (p / D::P3) + (k >> 1)) * D::P2 + 2 * (p % D::P3) + (k & 1);
+				s_e[e] = -alpha * ((1.0f - m * m) * e6[o]);
 			}
 			__syncthreads();
-			const float *xp = s_x + iz * 225 + ky * 15 + kx;
+			const float *xp = s_x + iz * D::NP2 + ky * D::P2 + kx;
 #pragma unroll
 			for (int oz = 0; oz < 4; oz++)
 #pragma unroll 4
-				for (int p = 0; p < 36; p++) acc[oz] += xp[s_i[oz * 36 + p]] * s_e[oz * 36 + p];
-			if (t < 4) for (int p = 0; p < 36; p++) bias += s_e[t * 36 + p];
+				for (int p = 0; p < D::NP3; p++) acc[oz] += xp[s_i[oz * D::NP3 + p]] * s_e[oz * D::NP3 + p];
+			if (t < 4) for (int p = 0; p < D::NP3; p++) bias += s_e[t * D::NP3 + p];
 		}
 #pragma unroll
 		for (int oz = 0; oz < 4; oz++) out[(4 * g + oz) * 256 + t] = acc[oz];
@@ -258,17 +277,17 @@ __global__ __launch_bounds__(256) void k_tb_conv_grad(const float *__restrict__ 
 		for (int b = b0; b < b1; b++)
 		{
 			__syncthreads();
-			const float *x0 = pool + (size_t)idx[b] * HT_CNN_IN;
-			for (int i = t; i < 4096; i += 256) s_x[i] = x0[i];
-			if (t < 225)
+			const float *x0 = pool + (size_t)idx[b] * (S * S);
+			for (int i = t; i < S * S; i += 256) s_x[i] = x0[i];
+			for (int e = t; e < D::NP2; e += 256)
 			{
-				const size_t o = (size_t)b * 3600 + oz * 225 + t;
+				const size_t o = (size_t)b * D::A3 + oz * D::NP2 + e;
 				const float m = a3[o];
-				s_i[t] = r1[o];
-				s_e[t] = -alpha * ((1.0f - m * m) * e3[o]);
+				s_i[e] = r1[o];
+				s_e[e] = -alpha * ((1.0f - m * m) * e3[o]);
 			}
 			__syncthreads();
-			acc = t_conv1_grad_add(acc, s_x, s_i, s_e, tap, sub);
+			acc = t_conv1_grad_add<S, D::NP2>(acc, s_x, s_i, s_e, tap, sub);
 		}
 		acc = seg8_sum(acc);
 		if (sub == 0 && tap < 26) out[16448 + oz * 26 + tap] = acc;
@@ -295,22 +314,27 @@ __global__ __launch_bounds__(256) void k_tb_conv_apply(const float *__restrict__
 	}
 }
 
-// The arena of a step of up to cap samples (cap a multiple of 32): per-sample tensors [cap][...], then the partial sums, the indices and a sink for the losses
+// The arena of a step of up to cap samples (cap a multiple of 32) of the net of input side `side`: per-sample tensors [cap][...], then the partial sums, the
+// indices and a sink for the losses
 struct tb_arena { float *a3, *a6, *a8, *lg, *e9, *e7, *e6, *e3, *pw, *sink; int *r1, *r3, *idx; };
-static tb_arena tb_layout(float *p, size_t cap)
+static size_t tb_a3(int side) { return side == 128 ? cnn_dims<128>::A3 : cnn_dims<64>::A3; }
+static size_t tb_a6(int side) { return side == 128 ? cnn_dims<128>::A6 : cnn_dims<64>::A6; }
+static tb_arena tb_layout(float *p, size_t cap, int side)
 {
+	const size_t n3 = tb_a3(side), n6 = tb_a6(side);
 	tb_arena A;
-	A.a3 = p; p += cap * 3600; A.r1 = (int *)p; p += cap * 3600; A.a6 = p; p += cap * 2304; A.r3 = (int *)p; p += cap * 2304; A.a8 = p; p += cap * 2048;
-	A.lg = p; p += cap * 2304; A.e9 = p; p += cap * 2304; A.e7 = p; p += cap * 2048; A.e6 = p; p += cap * 2304; A.e3 = p; p += cap * 3600;
+	A.a3 = p; p += cap * n3; A.r1 = (int *)p; p += cap * n3; A.a6 = p; p += cap * n6; A.r3 = (int *)p; p += cap * n6; A.a8 = p; p += cap * 2048;
+	A.lg = p; p += cap * 2304; A.e9 = p; p += cap * 2304; A.e7 = p; p += cap * 2048; A.e6 = p; p += cap * n6; A.e3 = p; p += cap * n3;
 	A.pw = p; p += (size_t)TB_MAXG * TB_PW; A.sink = p; p += HT_TRAIN_MAX_BATCH; A.idx = (int *)p;
 	return A;
 }
-size_t ht_train_batch_floats(int cap) { return (size_t)cap * (3 * 3600 + 5 * 2304 + 2 * 2048) + (size_t)TB_MAXG * TB_PW + 2 * HT_TRAIN_MAX_BATCH; }
-// the per-sample tensors ht_debug_train_batch_buffers returns, in its order: a3 a6 a8 e9 e7 e6 e3
-void ht_train_batch_views(float *arena, int cap, const float *view[7])
+size_t ht_train_batch_floats(int cap, int side) { return (size_t)cap * (3 * tb_a3(side) + 3 * tb_a6(side) + 2 * 2304 + 2 * 2048) + (size_t)TB_MAXG * TB_PW + 2 * HT_TRAIN_MAX_BATCH; }
+// the per-sample tensors ht_debug_train_batch_buffers returns, in its order: a3 a6 a8 e9 e7 e6 e3, and the floats of each per sample
+void ht_train_batch_views(float *arena, int cap, const float *view[7], size_t per[7], int side)
 {
-	const tb_arena A = tb_layout(arena, (size_t)cap);
+	const tb_arena A = tb_layout(arena, (size_t)cap, side);
 	view[0] = A.a3; view[1] = A.a6; view[2] = A.a8; view[3] = A.e9; view[4] = A.e7; view[5] = A.e6; view[6] = A.e3;
+	per[0] = tb_a3(side); per[1] = tb_a6(side); per[2] = 2048; per[3] = 2304; per[4] = 2048; per[5] = tb_a6(side); per[6] = tb_a3(side);
 }
 template <bool FOLD> static void tb_fc_back(const float *E, const float *W, const float *Y, float *D, int n, int R, int K, hipStream_t s)
 {
@@ -320,28 +344,36 @@ template <bool FOLD> static void tb_fc_back(const float *E, const float *W, cons
 	else if (n <= 128) hipLaunchKernelGGL((k_tb_fc_back<4, FOLD>), g, t, 0, s, E, W, Y, D, n, R, K);
 	else hipLaunchKernelGGL((k_tb_fc_back<8, FOLD>), g, t, 0, s, E, W, Y, D, n, R, K);
 }
-// One step on samples index[0..n) of the pools; mse_out[n] or null.  The packed copy of the last layer is NOT refreshed here (once per call: ht_api.hip).
-void ht_launch_train_batch_step(float *w, float *W2p, const float *inputs, const float *targets, const int *index, int n, float alpha, float *arena, int cap, float *mse_out, hipStream_t s)
+// One step of the net of input side S on samples index[0..n) of the pools; C2T = threads of a conv2 block, BH / BT / IZB = band height, threads and input channels per block of conv2's backward
+template <int S, int C2T, int BH, int BT, int IZB> static void tb_step(float *w, float *W2p, const float *inputs, const float *targets, const int *index, int n, float alpha, float *arena, int cap, float *mse_out, hipStream_t s)
 {
-	const tb_arena A = tb_layout(arena, (size_t)cap);
-	const cnnb_layout<float> L = cnnb_layout_of(w);
+	typedef cnn_dims<S> D;
+	const tb_arena A = tb_layout(arena, (size_t)cap, S);
+	const cnnb_layout<float> L = cnnb_layout_of(w, (size_t)D::A6);
 	tb_index ix;
 	for (int b = 0; b < n; b++) ix.v[b] = index[b];
 	for (int b = n; b < HT_TRAIN_MAX_BATCH; b++) ix.v[b] = 0;
 	const int groups = (n + TB_GS - 1) / TB_GS;
 	hipLaunchKernelGGL(k_tb_set_index, dim3(1), dim3(256), 0, s, ix, n, A.idx);
 	// forward
-	hipLaunchKernelGGL(k_tb_conv1_tanh_pool, dim3(15, 16, n), dim3(256), 0, s, inputs, A.idx, L.W1, L.B1, A.a3, A.r1);
-	hipLaunchKernelGGL(k_tb_conv2_tanh_pool, dim3(64, n), dim3(192), 0, s, A.a3, L.W2, L.B2, A.a6, A.r3);
-	ht_launch_fc_rowmajor(A.a6, L.W3, L.B3, A.a8, n, 2048, 2304, true, s);
+	hipLaunchKernelGGL(k_tb_conv1_tanh_pool<S>, dim3(D::P2, 16, n), dim3(256), 0, s, inputs, A.idx, L.W1, L.B1, A.a3, A.r1);
+	hipLaunchKernelGGL((k_tb_conv2_tanh_pool<S, C2T>), dim3(64, n), dim3(C2T), 0, s, A.a3, L.W2, L.B2, A.a6, A.r3);
+	ht_launch_fc_rowmajor(A.a6, L.W3, L.B3, A.a8, n, 2048, D::A6, true, s);
 	ht_launch_fc_rowmajor(A.a8, L.W4, L.B4, A.lg, n, 2304, 2048, false, s);
 	hipLaunchKernelGGL(k_tb_softmax_loss, dim3(n), dim3(256), 0, s, A.lg, targets, A.idx, A.e9, mse_out ? mse_out : A.sink);
 	// backward with the old weights, then each layer's step
 	tb_fc_back<true>(A.e9, L.W4, A.a8, A.e7, n, 2048, 2304, s);
 	hipLaunchKernelGGL(k_tb_fc_wgrad, dim3(2304 / 128, 2048 / 32), dim3(256), 0, s, L.W4, L.B4, A.a8, A.e9, n, 2048, 2304, alpha);
-	tb_fc_back<false>(A.e7, L.W3, nullptr, A.e6, n, 2304, 2048, s);
-	hipLaunchKernelGGL(k_tb_fc_wgrad, dim3(2048 / 128, 2304 / 32), dim3(256), 0, s, L.W3, L.B3, A.a6, A.e7, n, 2304, 2048, alpha);
-	hipLaunchKernelGGL(k_tb_conv2_back, dim3(16, n), dim3(256), 0, s, A.a6, A.r3, A.e6, L.W2, A.e3);
-	hipLaunchKernelGGL(k_tb_conv_grad, dim3(32, groups), dim3(256), 0, s, inputs, A.idx, A.a3, A.r1, A.a6, A.r3, A.e6, A.e3, n, alpha, A.pw);
+	tb_fc_back<false>(A.e7, L.W3, nullptr, A.e6, n, D::A6, 2048, s);
+	hipLaunchKernelGGL(k_tb_fc_wgrad, dim3(2048 / 128, D::A6 / 32), dim3(256), 0, s, L.W3, L.B3, A.a6, A.e7, n, D::A6, 2048, alpha);
+	hipLaunchKernelGGL((k_tb_conv2_back<S, BH, BT, IZB>), dim3(16 / IZB, n, (D::P2 + BH - 1) / BH), dim3(BT), 0, s, A.a6, A.r3, A.e6, L.W2, A.e3);
+	hipLaunchKernelGGL(k_tb_conv_grad<S>, dim3(32, groups), dim3(256), 0, s, inputs, A.idx, A.a3, A.r1, A.a6, A.r3, A.e6, A.e3, n, alpha, A.pw);
 	hipLaunchKernelGGL(k_tb_conv_apply, dim3((TB_PW + 255) / 256), dim3(256), 0, s, A.pw, groups, L.W1, L.B1, L.W2, L.B2, W2p);
+}
+// One step on samples index[0..n) of the pools ([..][side side] inputs); mse_out[n] or null.  The packed copy of the last layer is NOT refreshed here (once per
+// call: ht_api.hip).  side = 64 or 128, checked by the caller.
+void ht_launch_train_batch_step(float *w, float *W2p, const float *inputs, const float *targets, const int *index, int n, float alpha, float *arena, int cap, float *mse_out, hipStream_t s, int side)
+{
+	if (side == 128) tb_step<128, 256, 4, 256, 4>(w, W2p, inputs, targets, index, n, alpha, arena, cap, mse_out, s);
+	else tb_step<64, 192, 15, 256, 1>(w, W2p, inputs, targets, index, n, alpha, arena, cap, mse_out, s);
 }

@@ -15,6 +15,8 @@ HT_OK = 0
 CNN_IN, CNN_OUT, CNNB_COUNT, POSE, STATE, CAM, ANALYSIS = 4096, 2304, 9458400, 7, 13, 12, 84
 MAXPTS, ROW, CONTACT = 4096, 16, 12      # HT_MAX_POINTS
 LABELS_SEGMENT_FRAME = 1      # HT_LABELS_SEGMENT_FRAME
+LABELS_SIDE128 = 2            # HT_LABELS_SIDE128
+CNN128_IN, CNNB128_COUNT = 16384, 30429920
 # ht_debug_train_buffers: (name, floats, shape) of the segments of act and err, in order (None: padding)
 TRAIN_ACT = (("a1", 57600, (16, 60, 60)), ("a3", 3600, (16, 15, 15)), ("a5", 9216, (64, 12, 12)), ("a6", 2304, (2304,)), ("a8", 2048, (2048,)))
 TRAIN_ERR = (("e9", 2304, (2304,)), ("e7", 2048, (2048,)), ("e6", 2304, (2304,)), ("part3", 57600, (16, 3600)), ("sqp", 9, (9,)), (None, 7, None))
@@ -24,6 +26,7 @@ SYMBOLS = (
     "ht_create", "ht_destroy", "ht_model_bake", "ht_last_error", "ht_get_params", "ht_set_params", "ht_model_info", "ht_config_read", "ht_scale",
     "ht_cnn_load_weights", "ht_cnn_eval", "ht_cnn_eval_dev", "ht_cnn_load_weights_sized", "ht_cnn_eval_sized", "ht_cnn_eval_sized_dev", "ht_cnn_train", "ht_cnn_get_weights", "ht_expected_cnn", "ht_expected_cnn_full",
     "ht_expected_cnn_batch", "ht_expected_cnn_dev", "ht_cnn_input_dev", "ht_cnn_train_dev", "ht_cnn_train_batch_dev", "ht_cnn_train_batch", "ht_debug_train_batch_buffers",
+    "ht_cnn_train_batch_sized_dev", "ht_cnn_train_batch_sized", "ht_cnn_get_weights_sized", "ht_debug_train_batch_buffers_sized", "ht_cnn_input_sized_dev",
     "ht_model_open", "ht_model_close", "ht_model_error", "ht_model_counts", "ht_model_body", "ht_model_body_mesh", "ht_model_body_sdmesh", "ht_model_hitcheck", "ht_model_hitcheck_mesh", "ht_model_render_mesh", "ht_model_scale", "ht_render_mesh_depth", "ht_render_mesh_depth_dev",
     "ht_tracker_reset", "ht_get_state", "ht_set_state", "ht_get_tracker_flags", "ht_set_tracker_flags", "ht_update_sync", "ht_update_dev", "ht_update_frames_sync", "ht_update_frames_dev", "ht_update_direct_sync", "ht_update_direct_dev", "ht_update_cnn_model_sync", "ht_get_cnn_results", "ht_get_cnn_layers", "ht_frames_overflow", "ht_reserve_points", "ht_point_capacity", "ht_capacity_events", "ht_segment_vr", "ht_segment_vr_dev", "ht_render_depth", "ht_render_depth_dev", "ht_slowfit", "ht_set_points", "ht_fit_rows", "ht_physics_update",
     "ht_stage_prepare", "ht_stage_decode", "ht_stage_fit_error", "ht_stage_cloud_rows", "ht_stage_contacts", "ht_stage_fit",
@@ -114,6 +117,11 @@ def load(build_if_missing=True):
     L.ht_cnn_train_batch_dev.argtypes = [vp, vp, vp, C.c_int, ip, C.c_int, C.c_int, C.c_float, vp, vp]
     L.ht_cnn_train_batch.argtypes = [vp, fp, fp, C.c_int, C.c_int, C.c_float, fp]
     L.ht_debug_train_batch_buffers.argtypes = [vp, C.c_int] + [fp] * 7
+    L.ht_cnn_train_batch_sized_dev.argtypes = [vp, C.c_int, vp, vp, C.c_int, ip, C.c_int, C.c_int, C.c_float, vp, vp]
+    L.ht_cnn_train_batch_sized.argtypes = [vp, C.c_int, fp, fp, C.c_int, C.c_int, C.c_float, fp]
+    L.ht_cnn_get_weights_sized.argtypes = [vp, C.c_int, fp, C.c_size_t]
+    L.ht_debug_train_batch_buffers_sized.argtypes = [vp, C.c_int, C.c_int] + [fp] * 7
+    L.ht_cnn_input_sized_dev.argtypes = [vp, C.c_int, vp, vp, C.c_int, vp, vp]
     L.ht_set_points.argtypes = [vp, C.c_int, fp, C.c_int, ip]
     L.ht_slowfit.argtypes = [vp, C.c_int, C.c_int, fp, C.c_int, C.c_int, fp, fp, fp, C.c_int]
     L.ht_get_cnn_layers.argtypes = [vp, C.c_int, C.c_int, fp, fp, fp, fp]
@@ -601,54 +609,92 @@ class Context:
             raise ValueError("order holds fewer than n_steps indices")
         self._chk(self.L.ht_cnn_train_dev(self.h, d_inputs, d_targets, int(n_pool), None if o is None else _i(o), n, float(alpha), d_mse, stream))
 
-    def cnn_train_batch(self, inputs, targets, batch, alpha=0.001):
-        """ht_cnn_train_batch: mini-batch steps w' = w - alpha * SUM_b g_b(w) (a sum, not a mean) over the samples in order, `batch` per step (the
-        remainder forms a last, smaller step); returns the per-sample losses at their step's weights."""
-        x = _c(inputs, np.float32).reshape(-1, CNN_IN); t = _c(targets, np.float32).reshape(-1, CNN_OUT)
+    @staticmethod
+    def _side(side):
+        side = int(side)
+        if side not in (64, 128):
+            raise ValueError("CNN input side must be 64 or 128")
+        return side
+
+    def cnn_train_batch(self, inputs, targets, batch, alpha=0.001, side=64):
+        """ht_cnn_train_batch / _sized: mini-batch steps w' = w - alpha * SUM_b g_b(w) (a sum, not a mean) over the samples in order, `batch` per step (the
+        remainder forms a last, smaller step); returns the per-sample losses at their step's weights.  side = 128 trains the 128x128-input net
+        (inputs [n,16384])."""
+        side = self._side(side)
+        x = _c(inputs, np.float32).reshape(-1, side * side); t = _c(targets, np.float32).reshape(-1, CNN_OUT)
         mse = np.zeros(x.shape[0], np.float32)
-        self._chk(self.L.ht_cnn_train_batch(self.h, _f(x), _f(t), x.shape[0], int(batch), float(alpha), _f(mse)))
+        if side == 64:
+            self._chk(self.L.ht_cnn_train_batch(self.h, _f(x), _f(t), x.shape[0], int(batch), float(alpha), _f(mse)))
+        else:
+            self._chk(self.L.ht_cnn_train_batch_sized(self.h, side, _f(x), _f(t), x.shape[0], int(batch), float(alpha), _f(mse)))
         return mse
 
-    def cnn_train_batch_dev(self, d_inputs, d_targets, n_pool, batch, order=None, n_steps=None, alpha=0.001, d_mse=None, stream=None):
-        """ht_cnn_train_batch_dev: mini-batch steps on device pools; step k trains on samples order[k*batch:(k+1)*batch] (a host array, checked before
-        anything runs), or k*batch + b without an order.  d_mse [n_steps*batch] optional.  Asynchronous on `stream`."""
+    def cnn_train_batch_dev(self, d_inputs, d_targets, n_pool, batch, order=None, n_steps=None, alpha=0.001, d_mse=None, stream=None, side=64):
+        """ht_cnn_train_batch_dev / _sized_dev: mini-batch steps on device pools (inputs [n_pool, side*side]); step k trains on samples
+        order[k*batch:(k+1)*batch] (a host array, checked before anything runs), or k*batch + b without an order.  d_mse [n_steps*batch] optional.
+        Asynchronous on `stream`."""
+        side = self._side(side)
         o = None if order is None else np.ascontiguousarray(order, np.int32).reshape(-1)
         batch = int(batch)
         n = ((len(o) if o is not None else int(n_pool)) // max(batch, 1)) if n_steps is None else int(n_steps)
         if o is not None and len(o) < n * batch:
             raise ValueError("order holds fewer than n_steps * batch indices")
-        self._chk(self.L.ht_cnn_train_batch_dev(self.h, d_inputs, d_targets, int(n_pool), None if o is None else _i(o), n, batch, float(alpha), d_mse, stream))
+        if side == 64:
+            self._chk(self.L.ht_cnn_train_batch_dev(self.h, d_inputs, d_targets, int(n_pool), None if o is None else _i(o), n, batch, float(alpha), d_mse, stream))
+        else:
+            self._chk(self.L.ht_cnn_train_batch_sized_dev(self.h, side, d_inputs, d_targets, int(n_pool), None if o is None else _i(o), n, batch, float(alpha), d_mse, stream))
 
-    def cnn_train_batch_buffers(self, n):
-        """ht_debug_train_batch_buffers: the per-sample tensors of the latest mini-batch step (n = its sample count): a3 [n,16,15,15], a6 [n,2304],
-        a8 [n,2048], e9 [n,2304], e7 [n,2048], e6 [n,2304], e3 [n,16,15,15] (conv2's backward, summed over its groups)."""
-        n = int(n)
-        shapes = (("a3", (n, 16, 15, 15)), ("a6", (n, 2304)), ("a8", (n, 2048)), ("e9", (n, 2304)), ("e7", (n, 2048)), ("e6", (n, 2304)), ("e3", (n, 16, 15, 15)))
+    def cnn_train_batch_buffers(self, n, side=64):
+        """ht_debug_train_batch_buffers / _sized: the per-sample tensors of the latest mini-batch step of that net (n = its sample count): a3 [n,16,15,15],
+        a6 [n,2304], a8 [n,2048], e9 [n,2304], e7 [n,2048], e6 [n,2304], e3 [n,16,15,15] (conv2's backward, summed over its groups); at side 128
+        a3 / e3 [n,16,31,31] and a6 / e6 [n,12544]."""
+        n = int(n); side = self._side(side)
+        p2, n6 = (15, 2304) if side == 64 else (31, 12544)
+        shapes = (("a3", (n, 16, p2, p2)), ("a6", (n, n6)), ("a8", (n, 2048)), ("e9", (n, 2304)), ("e7", (n, 2048)), ("e6", (n, n6)), ("e3", (n, 16, p2, p2)))
         out = {k: np.empty(sh, np.float32) for k, sh in shapes}
-        self._chk(self.L.ht_debug_train_batch_buffers(self.h, n, *[_f(out[k]) for k, _ in shapes]))
+        if side == 64:
+            self._chk(self.L.ht_debug_train_batch_buffers(self.h, n, *[_f(out[k]) for k, _ in shapes]))
+        else:
+            self._chk(self.L.ht_debug_train_batch_buffers_sized(self.h, side, n, *[_f(out[k]) for k, _ in shapes]))
         return out
 
     # -- training samples on the device
-    def expected_cnn_batch(self, poses, cams, segment_frame=False):
+    def expected_cnn_batch(self, poses, cams, segment_frame=False, side=64):
         """GatherHandExpectedCNN (handtrack.h:160-173) for a batch on the device: poses [B,nb,7], tile cameras [B,12] -> (expected [B,2304],
-        image_points [B,8,2], vals [B,16]); segment_frame: train-cnn's compress first (HT_LABELS_SEGMENT_FRAME)."""
+        image_points [B,8,2], vals [B,16]); segment_frame: train-cnn's compress first (HT_LABELS_SEGMENT_FRAME); side = 128: the cameras are those of
+        128x128 tiles (HT_LABELS_SIDE128)."""
         poses = _c(poses, np.float32).reshape(-1, self.nb, POSE); B = poses.shape[0]
         cams = _c(cams, np.float32).reshape(B, CAM)
         e = np.empty((B, CNN_OUT), np.float32); ip = np.empty((B, 8, 2), np.float32); v = np.empty((B, 16), np.float32)
-        self._chk(self.L.ht_expected_cnn_batch(self.h, _f(poses), _f(cams), B, LABELS_SEGMENT_FRAME if segment_frame else 0, _f(e), _f(ip), _f(v)))
+        flags = self._label_flags(segment_frame, side)
+        self._chk(self.L.ht_expected_cnn_batch(self.h, _f(poses), _f(cams), B, flags, _f(e), _f(ip), _f(v)))
         return e, ip, v
 
-    def expected_cnn_dev(self, d_poses, d_cams, B, d_expected, d_image_points=None, d_vals=None, segment_frame=False, stream=None):
+    def _label_flags(self, segment_frame, side):
+        return (LABELS_SEGMENT_FRAME if segment_frame else 0) | (LABELS_SIDE128 if self._side(side) == 128 else 0)
+
+    def expected_cnn_dev(self, d_poses, d_cams, B, d_expected, d_image_points=None, d_vals=None, segment_frame=False, stream=None, side=64):
         """ht_expected_cnn_dev: device pointers (poses [B,nb,7], cams [B,12] -> expected [B,2304], image_points [B,8,2] / vals [B,16] or None), asynchronous on `stream`."""
-        self._chk(self.L.ht_expected_cnn_dev(self.h, d_poses, d_cams, int(B), LABELS_SEGMENT_FRAME if segment_frame else 0, d_expected, d_image_points, d_vals, stream))
+        flags = self._label_flags(segment_frame, side)
+        self._chk(self.L.ht_expected_cnn_dev(self.h, d_poses, d_cams, int(B), flags, d_expected, d_image_points, d_vals, stream))
 
-    def cnn_input_dev(self, d_tiles, d_cams, B, d_cnn_in, stream=None):
-        """ht_cnn_input_dev: the net's input (handtrack.h:700) of B 64x64 tiles u16[B,4096] with cameras [B,12] -> float [B,4096], asynchronous on `stream`."""
-        self._chk(self.L.ht_cnn_input_dev(self.h, d_tiles, d_cams, int(B), d_cnn_in, stream))
+    def cnn_input_dev(self, d_tiles, d_cams, B, d_cnn_in, stream=None, side=64):
+        """ht_cnn_input_dev / _sized_dev: the net's input (handtrack.h:700) of B side x side tiles u16[B,side*side] with cameras [B,12] -> float
+        [B,side*side], asynchronous on `stream`."""
+        side = self._side(side)
+        if side == 64:
+            self._chk(self.L.ht_cnn_input_dev(self.h, d_tiles, d_cams, int(B), d_cnn_in, stream))
+        else:
+            self._chk(self.L.ht_cnn_input_sized_dev(self.h, side, d_tiles, d_cams, int(B), d_cnn_in, stream))
 
-    def cnn_get_weights(self):
-        w = np.empty(9458400, np.float32)
-        self._chk(self.L.ht_cnn_get_weights(self.h, _f(w), w.size))
+    def cnn_get_weights(self, side=64):
+        """ht_cnn_get_weights / _sized: the weights of either net in .cnnb order (CNN::saveb)."""
+        side = self._side(side)
+        w = np.empty(CNNB_COUNT if side == 64 else CNNB128_COUNT, np.float32)
+        if side == 64:
+            self._chk(self.L.ht_cnn_get_weights(self.h, _f(w), w.size))
+        else:
+            self._chk(self.L.ht_cnn_get_weights_sized(self.h, side, _f(w), w.size))
         return w
 
     def cnn_train_buffers(self):

@@ -48,6 +48,7 @@ extern "C" {
 #define HT_POINTS_LIMIT 76800 /* 320x240: the largest cloud a frame can carry (every pixel in range, subsample_fraction 1) */
 #define HT_ANALYSIS 84        /* floats per frame, see ht_stage_decode */
 #define HT_LABELS_SEGMENT_FRAME 1 /* ht_expected_cnn_batch / _dev flag: train-cnn's compress (train-cnn.cpp:31-50) first, see there */
+#define HT_LABELS_SIDE128 2       /* ht_expected_cnn_batch / _dev flag: labels of a 128x128 tile, the heat-map camera camsub(cam, 8), see there */
 
 typedef struct ht_ctx ht_ctx;
 
@@ -255,7 +256,7 @@ int ht_cnn_train_dev(ht_ctx *ctx, const float *d_inputs, const float *d_targets,
  *                          (optional) = the value Train returns for each sample at its step's weights, sum E^2 / 2304.  1 <= batch <=
  *                          HT_TRAIN_MAX_BATCH, any value.  Asynchronous on `stream` under ht_cnn_train_dev's rules: the weights change in stream
  *                          order, the call ends with the refresh of the inference kernels' packed copies, ht_cnn_get_weights waits for it.  A
- *                          refused call (HT_ERR_ARG, the message names the argument; also without weights of the 64x64-input net, the only one trained) leaves the context as it was.
+ *                          refused call (HT_ERR_ARG, the message names the argument; also without weights of the 64x64-input net: the larger one is trained by the sized forms below) leaves the context as it was.
  * ht_cnn_train_batch       the same on host arrays inputs [n][4096], targets [n][2304], mse_out [n] (optional): an upload, then steps of `batch`
  *                          samples in order; when n is no multiple of batch the remainder forms a last, smaller step.
  *                          Staged through the same buffer as ht_cnn_train (n * 6401 floats, kept by the context until ht_destroy).
@@ -265,6 +266,29 @@ int ht_cnn_train_dev(ht_ctx *ctx, const float *d_inputs, const float *d_targets,
 int ht_cnn_train_batch_dev(ht_ctx *ctx, const float *d_inputs, const float *d_targets, int n_pool, const int *order, int n_steps, int batch, float alpha, float *d_mse, void *stream);
 int ht_cnn_train_batch(ht_ctx *ctx, const float *inputs, const float *targets, int n, int batch, float alpha, float *mse_out);
 int ht_debug_train_batch_buffers(ht_ctx *ctx, int n, float *a3, float *a6, float *a8, float *e9, float *e7, float *e6, float *e3);
+
+/* ---- mini-batch training of either net ---------------------------------------------------------------------------------------------
+ * The calls above with the net's input side: side = 64 IS the call above (same launches, same bits), side = 128 trains the 128x128-input net of
+ * ht_cnn_load_weights_sized under the same contract word for word (w' = w - alpha * SUM_b g_b(w), the same checks before anything is launched or
+ * grown, the same order rules, fixed summation orders, no floating-point atomics); any other side is HT_ERR_ARG.  Only the mini-batch step trains the
+ * larger net: ht_cnn_train / ht_cnn_train_dev and the C++ CNN class stay 64-only, and a batch of one through the sized call is CNN::Train to rounding.
+ * The two nets of a context are independent: training one leaves the other's weights and outputs as they were.
+ * ht_cnn_train_batch_sized_dev  side 128: pools d_inputs [n_pool][16384], d_targets [n_pool][2304]; HT_ERR_ARG if the context holds no weights of that
+ *                          net.  Ends with the refresh of that net's packed copies.  Its arena (about 370 KB a sample) is allocated by the first such call.
+ * ht_cnn_train_batch_sized  the host-array form, staged through the same buffer as ht_cnn_train: n * (side*side + 2305) floats at the largest call.
+ * ht_cnn_get_weights_sized  CNN::saveb for either net: n = HT_CNNB_COUNT or HT_CNNB128_COUNT; waits for training on a caller's stream.
+ * ht_debug_train_batch_buffers_sized  side 128: a3 / e3 [n][15376], a6 / e6 [n][12544], a8 / e7 [n][2048], e9 [n][2304]; n = the latest step's sample
+ *                          count of that net.
+ * ht_cnn_input_sized_dev   handtrack.h:700 for B side x side tiles d_tiles [B][side*side] -> d_cnn_in [B][side*side]; side 128 is what ht_update_direct_*
+ *                          feeds the net with.  The alignment rule of ht_cnn_input_dev.
+ * HT_LABELS_SIDE128        flag of ht_expected_cnn_batch / _dev (may be combined with HT_LABELS_SEGMENT_FRAME): the heat-map camera is camsub(cam, 8), so
+ *                          that a 128x128 tile gives 16x16 maps again.  Bit-identical to the call without it on a camera whose focal lengths and
+ *                          principal point are halved. */
+int ht_cnn_train_batch_sized_dev(ht_ctx *ctx, int side, const float *d_inputs, const float *d_targets, int n_pool, const int *order, int n_steps, int batch, float alpha, float *d_mse, void *stream);
+int ht_cnn_train_batch_sized(ht_ctx *ctx, int side, const float *inputs, const float *targets, int n, int batch, float alpha, float *mse_out);
+int ht_cnn_get_weights_sized(ht_ctx *ctx, int side, float *w, size_t n);
+int ht_debug_train_batch_buffers_sized(ht_ctx *ctx, int side, int n, float *a3, float *a6, float *a8, float *e9, float *e7, float *e6, float *e3);
+int ht_cnn_input_sized_dev(ht_ctx *ctx, int side, const uint16_t *d_tiles, const float *d_cams, int B, float *d_cnn_in, void *stream);
 
 /* ---- a hand model that is not being tracked (host only, no device needed) ---------------------------------------------------
  * The reference's applications keep a second PhysModel to pose, draw and ray-cast their synthetic input

@@ -3,7 +3,9 @@
 bench_train.py [n]                         ht_cnn_train: ms per SGD step and the implied weight traffic (as before)
 bench_train.py --batch N [N ...] [--out F] samples/s of the mini-batch step (ht_cnn_train_batch_dev) per batch size on a pool resident on the device,
                                            timed with device events after a warm-up, at least 20 steps per size, beside the batch-1 path
-                                           (ht_cnn_train_dev, one sample a step) in the same run; --out writes the figures as JSON."""
+                                           (ht_cnn_train_dev, one sample a step) in the same run; --out writes the figures as JSON.
+bench_train.py --side 128 --batch N [...]  the same sizes for the 128x128-input net as well (ht_cnn_train_batch_sized_dev on a pool of 16384-float inputs), after the
+                                           64x64-input path of the same run, with the ratio of the two steps per size (no stage's work grows by more than 5.44 x); profiles/r14_train128.json is its --out."""
 import argparse, json, sys, time, os
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -13,8 +15,11 @@ ap = argparse.ArgumentParser()
 ap.add_argument("n", nargs="?", type=int, default=256)
 ap.add_argument("--batch", nargs="+", type=int, default=None)
 ap.add_argument("--steps", type=int, default=40, help="timed steps per batch size (at least 20)")
+ap.add_argument("--side", type=int, default=64, choices=(64, 128), help="128: time the 128x128-input net's step too, beside the 64x64-input one")
 ap.add_argument("--out", default=None)
 args = ap.parse_args()
+if args.side == 128 and args.batch is None:
+    ap.error("--side 128 times the mini-batch step: give --batch N [N ...]")
 n = args.n
 if args.batch is not None:
     import torch      # before the library opens the device
@@ -43,11 +48,11 @@ tx = torch.from_numpy(xs).to(dev); tt = torch.from_numpy(ts).to(dev)
 stream = torch.cuda.Stream(device=dev)
 
 
-def timed(call, reps=3):
+def timed(call, reps=3, reload=lambda: ctx.load_weights(W0)):
     """the best of `reps` timings of call() between two device events on the tool's stream, each from the seeded weights, after one warm-up"""
     best = None
     for r in range(reps + 1):
-        ctx.load_weights(W0)
+        reload()
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record(stream); call(); e1.record(stream); e1.synchronize()
         if r:
@@ -68,6 +73,17 @@ for b in args.batch:
     rate = steps * b / ms * 1e3
     out["batch"][str(b)] = {"steps": steps, "ms_per_step": ms / steps, "samples_per_s": rate, "ratio_to_batch1_path": rate / base}
     print("batch %-4d %d steps  %.4f ms/step  %.0f samples/s  %.2f x the batch-1 path" % (b, steps, ms / steps, rate, rate / base))
+if args.side == 128:
+    W128 = weights.make_cnnb128()
+    tx128 = torch.from_numpy(rng.random((pool, 16384), dtype=np.float32)).to(dev)
+    out["side128"] = {"pool": pool, "batch": {}}
+    for b in args.batch:
+        order = rng.integers(0, pool, steps * b).astype(np.int32)
+        ms = timed(lambda: ctx.cnn_train_batch_dev(tx128.data_ptr(), tt.data_ptr(), pool, b, order=order, alpha=0.001 / b, stream=stream.cuda_stream, side=128), reload=lambda: ctx.load_weights128(W128))
+        rate = steps * b / ms * 1e3
+        small = out["batch"][str(b)]["ms_per_step"]
+        out["side128"]["batch"][str(b)] = {"steps": steps, "ms_per_step": ms / steps, "samples_per_s": rate, "step_over_side64_step": ms / steps / small}
+        print("side 128 batch %-4d %d steps  %.4f ms/step  %.0f samples/s  %.2f x the 64x64-input net's step (work grows by at most 5.44 x)" % (b, steps, ms / steps, rate, ms / steps / small))
 if args.out:
     with open(args.out, "w") as f:
         json.dump(out, f, indent=1)

@@ -12,7 +12,12 @@ Held out: the frames tools/train_synthetic.py holds out (every 16th bench frame)
 MSE of the net on those 64 bench tiles, and on how many of them the unit of work takes the CNN-driven pose (the measure of tests/test_gpu_trained_net.py).
 Rates: closed-loop samples/s against ht_cnn_train_dev steps/s on a resident pool, and the label and tile-input stages timed with device events.
 
-    python tools/train_rendered.py [--rounds 280] [--batch 1024] [--minibatch 1] [--lr 0.001] [--seed N] [--json profiles/r07_labels.json]"""
+    python tools/train_rendered.py [--rounds 280] [--batch 1024] [--minibatch 1] [--lr 0.001] [--seed N] [--json profiles/r07_labels.json]
+
+--side 128 trains the 128x128-input net instead (BASELINE configs[4]): the 26-bone hand rendered straight at 128x128 by the camera of that configuration's frames (focal 163,
+principal 64, depth scale 0.001, identity pose), no segmentation step; poses interpolated between consecutive start poses of bench_data/frames5_256.npz, every 16th held out;
+inputs from ht_cnn_input_sized_dev, labels with HT_LABELS_SIDE128, steps of --minibatch samples through ht_cnn_train_batch_sized_dev.  Reported: the held-out MSE (the
+16 held-out poses, rendered the same way) before and after, and the closed-loop samples/s against the training call alone."""
 import argparse
 import json
 import os
@@ -31,6 +36,8 @@ from bench_render import slerp  # noqa: E402
 SEED = 0x5EED0001
 HOLD = 16
 M17 = os.path.join(ROOT, "hand_tracking_samples_amd", "assets", "model_hand17.htfx")
+M26 = os.path.join(ROOT, "hand_tracking_samples_amd", "assets", "model_hand26.htfx")
+CAM128 = np.array([163, 163, 64, 64, 0.001, 0, 0, 0, 0, 0, 0, 1], np.float32)
 QVGA_CAM = np.array([305, 305, 160, 120, 0.001, 0, 0, 0, 0, 0, 0, 1], np.float32)
 
 
@@ -63,8 +70,99 @@ def held_out(ctx, d):
     return float(((y - t) ** 2).mean()), int(np.asarray(acc).astype(bool).sum())
 
 
+def main128(a):
+    """the loop for the 128x128-input net: render at 128x128, tile inputs, labels at camsub(cam, 8), mini-batch steps"""
+    dev = torch.device("cuda:0")
+    d = np.load(os.path.join(ROOT, "bench_data", "frames5_256.npz"))
+    gt = d["startpose"].astype(np.float32); pairs = train_pairs(len(gt)); nb = gt.shape[1]
+    B = a.batch
+    rng = np.random.default_rng(a.seed)
+    ctx = native.Context(M26, 64)
+    ctx.load_weights128(W.make_cnnb128(a.seed, 1.0))
+    s = torch.cuda.Stream(device=dev)
+    cams = torch.from_numpy(np.tile(CAM128, (B, 1))).to(dev)
+    tp = torch.empty((B, nb, 7), device=dev)
+    depth = torch.empty((B, 128, 128), dtype=torch.int16, device=dev)
+    x = torch.empty((B, 16384), device=dev); lab = torch.empty((B, 2304), device=dev); mse = torch.empty(B, device=dev)
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(5)]
+
+    def train(order, d_mse=None):
+        ctx.cnn_train_batch_dev(x.data_ptr(), lab.data_ptr(), B, a.minibatch, order=order, alpha=a.lr, d_mse=d_mse, stream=s.cuda_stream, side=128)
+
+    def round_(poses, order, timed=False):
+        with torch.cuda.stream(s):
+            tp.copy_(torch.from_numpy(poses))
+            if timed: ev[0].record(s)
+            ctx.render_depth_dev(tp.data_ptr(), cams.data_ptr(), 128, 128, 4.0, B, depth.data_ptr(), None, s.cuda_stream)
+            if timed: ev[1].record(s)
+            ctx.cnn_input_dev(depth.data_ptr(), cams.data_ptr(), B, x.data_ptr(), s.cuda_stream, side=128)
+            if timed: ev[2].record(s)
+            ctx.expected_cnn_dev(tp.data_ptr(), cams.data_ptr(), B, lab.data_ptr(), stream=s.cuda_stream, side=128)
+            if timed: ev[3].record(s)
+            train(order, mse.data_ptr())
+            if timed: ev[4].record(s)
+
+    # held out: every 16th start pose, rendered by the same camera (host forms), labels from the host's GatherHandExpectedCNN on the halved camera
+    fr = np.arange(0, len(gt), HOLD)
+    hd = ctx.render_depth(gt[fr], np.tile(CAM128, (len(fr), 1)), 128, 128, 4.0)
+    hd = (hd[0] if isinstance(hd, tuple) else hd).reshape(len(fr), -1)
+    hx = np.clip(1.0 - (hd.astype(np.float32) * np.float32(CAM128[4]) - np.float32(0.1)) / (np.float32(ctx.params.drangey) - np.float32(0.1)), 0.0, 1.0).astype(np.float32)
+    half = CAM128.copy(); half[:4] *= 0.5
+    ht = np.stack([native.expected_cnn(gt[i], half) for i in fr])
+
+    def held_out():
+        return float(((ctx.cnn128_eval(hx) - ht) ** 2).mean())
+
+    mse0 = held_out()
+    print("before: held-out mse %.3e on %d rendered poses" % (mse0, len(fr)), flush=True)
+    curve = []
+    stage_ms = np.zeros(4)
+    t0 = time.perf_counter()
+    for r in range(a.rounds):
+        poses = draw(gt, pairs, B, rng); order = rng.permutation(B).astype(np.int32)
+        round_(poses, order, timed=True)
+        s.synchronize()
+        stage_ms += [ev[i].elapsed_time(ev[i + 1]) for i in range(4)]
+        if (r + 1) % 10 == 0 or r + 1 == a.rounds:
+            rec = {"round": r + 1, "samples": (r + 1) * B, "train_mse": float(mse.mean().item()), "held_out_mse": held_out()}
+            curve.append(rec)
+            print(rec, "%.0f s" % (time.perf_counter() - t0), flush=True)
+    seconds = time.perf_counter() - t0
+    stage_ms /= a.rounds
+    poses = draw(gt, pairs, B, rng); order = rng.permutation(B).astype(np.int32)
+    round_(poses, order); s.synchronize()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    nloop = 4
+    with torch.cuda.stream(s):
+        e0.record(s)
+    for _ in range(nloop):
+        round_(poses, order)
+    with torch.cuda.stream(s):
+        e1.record(s)
+    s.synchronize()
+    loop_sps = nloop * B / (e0.elapsed_time(e1) / 1e3)
+    with torch.cuda.stream(s):
+        e0.record(s)
+        train(order)
+        e1.record(s)
+    s.synchronize()
+    bare_sps = B / (e0.elapsed_time(e1) / 1e3)
+    mse1 = held_out()
+    ctx.close()
+    out = {"what": "tools/train_rendered.py --side 128: %d rounds of %d frames of the 26-bone hand rendered at 128x128 (render, input, HT_LABELS_SIDE128 labels, steps of %d lr %g over a "
+                   "seeded permutation), seed 0x%X" % (a.rounds, B, a.minibatch, a.lr, a.seed),
+           "side": 128, "rounds": a.rounds, "batch": B, "minibatch": a.minibatch, "lr": a.lr, "samples": a.rounds * B, "seconds": seconds,
+           "stage_ms_per_round": {"render": stage_ms[0], "cnn_input": stage_ms[1], "labels": stage_ms[2], "train": stage_ms[3]},
+           "closed_loop_samples_per_s": loop_sps, "bare_train_samples_per_s": bare_sps,
+           "held_out": {"frames": int(len(fr)), "mse_before": mse0, "mse_after": mse1}, "curve": curve}
+    print(json.dumps({k: v for k, v in out.items() if k != "curve"}, indent=1))
+    if a.json:
+        json.dump(out, open(a.json, "w"), indent=1)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--side", type=int, default=64, choices=(64, 128), help="128: train the 128x128-input net on frames rendered at 128x128 (see the module's text)")
     ap.add_argument("--rounds", type=int, default=280)
     ap.add_argument("--batch", type=int, default=1024)
     ap.add_argument("--seed", type=int, default=SEED)
@@ -76,6 +174,8 @@ def main():
     a = ap.parse_args()
     if a.minibatch < 1 or a.batch % a.minibatch:
         ap.error("--minibatch must divide --batch")
+    if a.side == 128:
+        return main128(a)
     dev = torch.device("cuda:0")
     d = np.load(os.path.join(ROOT, "bench_data", "frames1024.npz"))
     gt = d["gtpose"]; pairs = train_pairs(len(gt))
