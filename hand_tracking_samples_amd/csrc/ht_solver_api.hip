@@ -793,12 +793,12 @@ extern "C" int ht_get_cnn_results(ht_ctx *ctx, int first, int n, float *cnn_inpu
 // The CNN's intermediate layers of the latest evaluation (ht_cnn_eval, an update call) of slots [first, first + n), for per-layer parity tests:
 // act1 [n][3600] = layer 3 of the reference's list (conv 5x5, tanh, two 2x2 max-pools: 16 x 15 x 15), act2 [n][2304] = layer 6 (conv 4x4, tanh, pool: 64 x 6 x 6),
 // act3 [n][2048] = layer 8 (first fully connected layer + tanh), logits [n][2304] = layer 9 (second fully connected layer, before the chunked soft-max).
-extern "C" int ht_get_cnn_layers(ht_ctx *ctx, int first, int n, float *act1, float *act2, float *act3, float *logits)
+// (d_a1 / d_a2: the convolution layers' buffers of the net asked for, n1 / n2 floats a frame; act3 and the logits are the one pair both nets write)
+static int get_cnn_layers(ht_ctx *ctx, const float *d_a1, size_t n1, const float *d_a2, size_t n2, int first, int n, float *act1, float *act2, float *act3, float *logits)
 {
-	CHECK_READY(ctx); CHECK_RANGE(ctx, first, n);
 	HIPCHK(ctx, ht_sync_all(ctx));
-	if (act1) HIPCHK(ctx, hipMemcpy(act1, ctx->d_act1 + (size_t)first * 3600, (size_t)n * 3600 * sizeof(float), hipMemcpyDeviceToHost));
-	if (act2) HIPCHK(ctx, hipMemcpy(act2, ctx->d_act2 + (size_t)first * 2304, (size_t)n * 2304 * sizeof(float), hipMemcpyDeviceToHost));
+	if (act1) HIPCHK(ctx, hipMemcpy(act1, d_a1 + (size_t)first * n1, (size_t)n * n1 * sizeof(float), hipMemcpyDeviceToHost));
+	if (act2) HIPCHK(ctx, hipMemcpy(act2, d_a2 + (size_t)first * n2, (size_t)n * n2 * sizeof(float), hipMemcpyDeviceToHost));
 	if (act3)      // the device holds the layer in the column order the last layer's kernel reads (k_fc<PACK16>): position (c & ~15) | (c & 3) << 2 | (c >> 2) & 3 holds column c
 	{
 		std::vector<float> packed((size_t)n * 2048);
@@ -807,6 +807,22 @@ extern "C" int ht_get_cnn_layers(ht_ctx *ctx, int first, int n, float *act1, flo
 	}
 	if (logits) HIPCHK(ctx, hipMemcpy(logits, ctx->d_logits + (size_t)first * HT_CNN_OUT, (size_t)n * HT_CNN_OUT * sizeof(float), hipMemcpyDeviceToHost));
 	return HT_OK;
+}
+extern "C" int ht_get_cnn_layers(ht_ctx *ctx, int first, int n, float *act1, float *act2, float *act3, float *logits)
+{
+	CHECK_READY(ctx); CHECK_RANGE(ctx, first, n);
+	return get_cnn_layers(ctx, ctx->d_act1, 3600, ctx->d_act2, 2304, first, n, act1, act2, act3, logits);
+}
+// The same of the net with a side x side input: 64 is the call above; 128 reads the larger net's own convolution buffers (act1 [n][16 * 31 * 31], act2 [n][12544]), which
+// exist once its weights are loaded.
+extern "C" int ht_get_cnn_layers_sized(ht_ctx *ctx, int side, int first, int n, float *act1, float *act2, float *act3, float *logits)
+{
+	CHECK_READY(ctx);
+	if (side == 64) return ht_get_cnn_layers(ctx, first, n, act1, act2, act3, logits);
+	if (side != 128) { ctx->err = "CNN input side must be 64 or 128"; return HT_ERR_ARG; }
+	CHECK_RANGE(ctx, first, n);
+	if (!ctx->have_weights128) { ctx->err = "weights of the 128x128 net not loaded (ht_cnn_load_weights_sized)"; return HT_ERR_STATE; }
+	return get_cnn_layers(ctx, ctx->d_act1_128, 16 * 31 * 31, ctx->d_act2_128, 12544, first, n, act1, act2, act3, logits);
 }
 
 // ---- stage entry points (operate on the buffers ht_stage_prepare filled and on the tracker state of slots [0,B)) -------------

@@ -28,7 +28,7 @@ SYMBOLS = (
     "ht_expected_cnn_batch", "ht_expected_cnn_dev", "ht_cnn_input_dev", "ht_cnn_train_dev", "ht_cnn_train_batch_dev", "ht_cnn_train_batch", "ht_debug_train_batch_buffers",
     "ht_cnn_train_batch_sized_dev", "ht_cnn_train_batch_sized", "ht_cnn_get_weights_sized", "ht_debug_train_batch_buffers_sized", "ht_cnn_input_sized_dev",
     "ht_model_open", "ht_model_close", "ht_model_error", "ht_model_counts", "ht_model_body", "ht_model_body_mesh", "ht_model_body_sdmesh", "ht_model_hitcheck", "ht_model_hitcheck_mesh", "ht_model_render_mesh", "ht_model_scale", "ht_render_mesh_depth", "ht_render_mesh_depth_dev",
-    "ht_tracker_reset", "ht_get_state", "ht_set_state", "ht_get_tracker_flags", "ht_set_tracker_flags", "ht_update_sync", "ht_update_dev", "ht_update_frames_sync", "ht_update_frames_dev", "ht_update_direct_sync", "ht_update_direct_dev", "ht_update_cnn_model_sync", "ht_get_cnn_results", "ht_get_cnn_layers", "ht_frames_overflow", "ht_reserve_points", "ht_point_capacity", "ht_capacity_events", "ht_segment_vr", "ht_segment_vr_dev", "ht_render_depth", "ht_render_depth_dev", "ht_slowfit", "ht_set_points", "ht_fit_rows", "ht_physics_update",
+    "ht_tracker_reset", "ht_get_state", "ht_set_state", "ht_get_tracker_flags", "ht_set_tracker_flags", "ht_update_sync", "ht_update_dev", "ht_update_frames_sync", "ht_update_frames_dev", "ht_update_direct_sync", "ht_update_direct_dev", "ht_update_cnn_model_sync", "ht_get_cnn_results", "ht_get_cnn_layers", "ht_get_cnn_layers_sized", "ht_frames_overflow", "ht_reserve_points", "ht_point_capacity", "ht_capacity_events", "ht_segment_vr", "ht_segment_vr_dev", "ht_render_depth", "ht_render_depth_dev", "ht_slowfit", "ht_set_points", "ht_fit_rows", "ht_physics_update",
     "ht_stage_prepare", "ht_stage_decode", "ht_stage_fit_error", "ht_stage_cloud_rows", "ht_stage_contacts", "ht_stage_fit",
     "ht_stage_multistep", "ht_stage_multistep_range", "ht_stage_scratch_unibody", "ht_stage_chamber", "ht_profile_enable", "ht_profile_read", "ht_debug_solve_stats", "ht_debug_contact_stats", "ht_debug_solver_build", "ht_debug_reset_flags", "ht_debug_reset_organisation", "ht_update_passes_sync", "ht_job_start", "ht_job_poll", "ht_job_wait", "ht_job_collect", "ht_debug_contact_kernel", "ht_debug_contact_order", "ht_debug_rank_desc", "ht_contact_capacity", "ht_debug_solve_tables", "ht_debug_solve_tables_header", "ht_debug_train_buffers",
     "ht_comm_available", "ht_comm_unique_id", "ht_comm_init", "ht_comm_info", "ht_gather_poses_dev", "ht_gather_wait", "ht_gather_wait_host", "ht_comm_destroy",
@@ -125,6 +125,7 @@ def load(build_if_missing=True):
     L.ht_set_points.argtypes = [vp, C.c_int, fp, C.c_int, ip]
     L.ht_slowfit.argtypes = [vp, C.c_int, C.c_int, fp, C.c_int, C.c_int, fp, fp, fp, C.c_int]
     L.ht_get_cnn_layers.argtypes = [vp, C.c_int, C.c_int, fp, fp, fp, fp]
+    L.ht_get_cnn_layers_sized.argtypes = [vp, C.c_int, C.c_int, C.c_int, fp, fp, fp, fp]
     L.ht_stage_chamber.argtypes = [vp, C.c_int, C.c_int, fp, ip]
     L.ht_fit_rows.argtypes = [vp, C.c_int, C.c_int, fp, C.c_int, ip, fp, C.c_int, ip, fp, C.c_int, ip, C.c_float]
     L.ht_physics_update.argtypes = [vp, C.c_int, C.c_int, fp, C.c_int, ip, fp, C.c_int, ip]
@@ -343,10 +344,16 @@ class Context:
         self._chk(self.L.ht_capacity_events(self.h, C.byref(a), C.byref(b), C.byref(c)))
         return a.value, b.value, c.value
 
-    def cnn_layers(self, n, first=0):
-        """(act1 [n,3600], act2 [n,2304], act3 [n,2048], logits [n,2304]) of the latest CNN evaluation (ht_get_cnn_layers)."""
-        a1 = np.zeros((n, 3600), np.float32); a2 = np.zeros((n, 2304), np.float32); a3 = np.zeros((n, 2048), np.float32); lg = np.zeros((n, 2304), np.float32)
-        self._chk(self.L.ht_get_cnn_layers(self.h, int(first), int(n), _f(a1), _f(a2), _f(a3), _f(lg)))
+    def cnn_layers(self, n, first=0, side=64):
+        """(act1 [n,3600], act2 [n,2304], act3 [n,2048], logits [n,2304]) of the latest CNN evaluation (ht_get_cnn_layers); side = 128: the 128x128-input net's
+        act1 [n,15376] and act2 [n,12544] (ht_get_cnn_layers_sized; act3 and logits belong to whichever net ran last)."""
+        side = int(side)
+        n1, n2 = (3600, 2304) if side == 64 else (16 * 31 * 31, 12544)      # any other side: the library refuses it
+        a1 = np.zeros((n, n1), np.float32); a2 = np.zeros((n, n2), np.float32); a3 = np.zeros((n, 2048), np.float32); lg = np.zeros((n, 2304), np.float32)
+        if side == 64:
+            self._chk(self.L.ht_get_cnn_layers(self.h, int(first), int(n), _f(a1), _f(a2), _f(a3), _f(lg)))
+        else:
+            self._chk(self.L.ht_get_cnn_layers_sized(self.h, side, int(first), int(n), _f(a1), _f(a2), _f(a3), _f(lg)))
         return a1, a2, a3, lg
 
     def stage_chamber(self, which, B):

@@ -196,6 +196,10 @@ int ht_job_collect(ht_ctx *job, ht_ctx *main, int B, int *accepted_out);
  *                     handtrack.h:108-111), act2 [n][2304] after conv 4x4 + tanh + pool (layer 6), act3 [n][2048] after the first fully connected layer + tanh
  *                     (layer 8), logits [n][2304] after the second one (layer 9, before the chunked soft-max).  Any pointer may be NULL. */
 int ht_get_cnn_layers(ht_ctx *ctx, int first, int n, float *act1, float *act2, float *act3, float *logits);
+/* ht_get_cnn_layers_sized   the same of the net with a side x side input, side = 64 (ht_get_cnn_layers itself) or 128 (ht_cnn_eval_sized, ht_update_direct_*):
+ *                     act1 [n][16 * 31 * 31], act2 [n][12544], act3 [n][2048], logits [n][2304].  act3 and logits are the one pair both nets write: they hold whichever
+ *                     net was evaluated last.  Any other side, or side 128 before ht_cnn_load_weights_sized(128), is refused with a message; the context stays usable. */
+int ht_get_cnn_layers_sized(ht_ctx *ctx, int side, int first, int n, float *act1, float *act2, float *act3, float *logits);
 /* ht_capacity_events  how often, since ht_create, a kernel hit a capacity the reference does not have: expanding-polytope runs cut short (gjk.h:417 /
  *                     hull.h:233-310 loop without bound; here at most 128 iterations, 96 vertices, 192 triangles); touching samples beyond the 192 the contact
  *                     kernel's per-frame pool holds, or beyond 40 five-sample patches (physics.h:451-462 keeps them all; every sample the pool holds IS kept and

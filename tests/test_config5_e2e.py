@@ -102,7 +102,7 @@ def test_gpu_config5_end_to_end_on_the_256_bench_frames(weights128):
         ctx.load_weights128(weights128)
         ctx.set_params(microforce=3.0, mainthreadpasses=3)
         ctx.tracker_reset(FR256["startpose"])
-        poses, _ = ctx.update_direct_sync(FR256["depth"], FR256["cam"], 128, want_cnn=True)
+        poses, cnn = ctx.update_direct_sync(FR256["depth"], FR256["cam"], 128, want_cnn=True)
         other = ctx.get_state(1, n)[:, :, :7]
         ref = G256["all/uw_pose_user"]
         dp = np.abs(poses[:, :, :3] - ref[:, :, :3]).max(axis=(1, 2)); dq = np.abs(poses[:, :, 3:] - ref[:, :, 3:]).max(axis=(1, 2))
@@ -126,6 +126,14 @@ def test_gpu_config5_end_to_end_on_the_256_bench_frames(weights128):
             assert ok, key
         assert np.median(do) <= FULL_POS_TOL
         assert ctx.capacity_events() == (0, 0, 0)
+        # the heat-maps of this call: 256 frames are the one batch on real frames that takes k_fc's FULL instantiation at K = 12544 (B % 128 == 0).  The 64 frames this set
+        # shares with the 64-frame one, evaluated by the net alone at B = 64 (the tiled instantiation with its row tests), give the same bits
+        sub = np.arange(len(FR["depth"])) * 4
+        assert np.array_equal(FR["depth"], FR256["depth"][sub])
+        x = np.zeros((len(sub), 128 * 128), np.float32)
+        for k, i in enumerate(sub):
+            ol.lib().ho_cnn_input(ol.u16ptr(np.ascontiguousarray(FR256["depth"][i].reshape(-1))), 128 * 128, float(FR256["cam"][i][4]), 0.1, 0.7, ol.fptr(x[k]))
+        assert np.isfinite(cnn).all() and np.array_equal(cnn[sub], ctx.cnn128_eval(x))
     finally:
         ctx.close()
 

@@ -1,6 +1,7 @@
 """tests/train_ref.py's float64 training step with the net's dimensions as parameters (side 64 or 128, .cnnb order, cnnb_count(side)), a float32 mode of
 the same step, and the mini-batch composition of tests/train_batch_ref.py on them.  A helper, not a test; it needs no GPU and no compiled oracle.
 
+forward(w, X, side, mode) is the forward pass alone (the inference tests' reference: tests/test_cnn_forward_ref.py, tests/test_gpu_cnn_forward.py); step() calls it.
 step(w, X, T, alpha, side, mode) steps every row of X [n, side*side] / T [n, 2304] at the same weights w:
     mode "f64"   train_ref.train_step's arithmetic (the same tap loops, the same products), float64, the n samples side by side
     mode "f32"   float32 throughout, every sum accumulated in third_party/cnn.h's order as oracle/ho_cnn.c restates it: one multiply and one add per term
@@ -113,32 +114,51 @@ def _seqsum(a, axis=-1):
     return np.take(np.cumsum(a, axis=axis, dtype=a.dtype), -1, axis=axis)
 
 
-def step(w, X, T, alpha, side, mode="f64", want_delta=True):
+def forward(w, X, side, mode="f64", mut=None):
+    """the forward pass of every row of X [n, side*side] at the weights w: the layers a3 [n,16,p2,p2], a6 [n,fc], a8 [n,2048], logits, y [n,2304] (and what the
+    backward pass needs of it: a1, a5 and the pooling choices k1 k2 k3).  step() calls it, so the inference tests and the training tests share one text.
+    `mut` (float64 mode only; tests/test_cnn_forward_ref.py) makes one mistake of a banded or tiled kernel, on whole rows since a single pixel can lose its pooling window:
+        conv1_row (ch, r)              conv1's output row r of channel ch misses its ky = 0 taps
+        pool_row (ch, r, r_from)       row r of a3's channel ch is taken from row r_from
+        conv2_row (oz, r, iz, ky, kx)  conv2's output row r of channel oz misses one tap
+        fc1_slab k0 / fc2_block k0     the product misses the 32 / 16 rows of its weights from k0 on
+        act3_swap c                    columns c and c + 1 of a8 change places on their way into the last layer
+        softmax_sum (c, c_from)        soft-max chunk c is divided by chunk c_from's sum"""
     D = dims(side)
-    S, c1, p2, c2, p3, fc = side, D["c1"], D["p2"], D["c2"], D["p3"], D["fc"]
+    S, c1, c2, fc = side, D["c1"], D["c2"], D["fc"]
     f32 = mode == "f32"
+    mut = mut or {}
+    assert not (f32 and mut)
     dt = np.float32 if f32 else np.float64
     w = np.asarray(w, dt)
     P = split(w, side)
-    X = np.asarray(X, dt).reshape(-1, S, S); T = np.asarray(T, dt).reshape(-1, 2304)
+    X = np.asarray(X, dt).reshape(-1, S, S)
     n = X.shape[0]
-    alpha = dt(np.float32(alpha))
-    one = dt(1)
     W1, W2, W3, W4 = P["W1"], P["W2"], P["W3"], P["W4"]
     tanh = _tanh32 if f32 else np.tanh
-    # forward (ho_cnn_eval_sized): taps ky, kx (then the input channel), every position of a map at once
+    # ho_cnn_eval_sized: taps ky, kx (then the input channel), every position of a map at once
     z = np.broadcast_to(P["B1"][None, :, None, None], (n, 16, c1, c1)).copy()
     for ky in range(5):
         for kx in range(5):
             z += X[:, None, ky:ky + c1, kx:kx + c1] * W1[None, :, ky, kx, None, None]
+    if "conv1_row" in mut:
+        ch, r = mut["conv1_row"]
+        for kx in range(5):
+            z[:, ch, r] -= X[:, r, kx:kx + c1] * W1[ch, 0, kx]
     a1 = tanh(z)
     a2, k1 = _pool(a1)
     a3, k2 = _pool(a2)
+    if "pool_row" in mut:
+        ch, r, r_from = mut["pool_row"]
+        a3[:, ch, r] = a3[:, ch, r_from]
     z = np.broadcast_to(P["B2"][None, :, None, None], (n, 64, c2, c2)).copy()
     for ky in range(4):
         for kx in range(4):
             for iz in range(16):
                 z += a3[:, None, iz, ky:ky + c2, kx:kx + c2] * W2[None, :, iz, ky, kx, None, None]
+    if "conv2_row" in mut:
+        oz, r, iz, ky, kx = mut["conv2_row"]
+        z[:, oz, r] -= a3[:, iz, r + ky, kx:kx + c2] * W2[oz, iz, ky, kx]
     a5 = tanh(z)
     a6m, k3 = _pool(a5)
     a6 = a6m.reshape(n, fc)
@@ -152,11 +172,40 @@ def step(w, X, T, alpha, side, mode="f64", want_delta=True):
             logits += a8[:, i, None] * W4[i][None]
         y = _exp32(logits)
     else:
-        a8 = np.tanh(P["B3"] + a6 @ W3)
-        logits = P["B4"] + a8 @ W4
+        xs = a6
+        if "fc1_slab" in mut:
+            xs = a6.copy(); xs[:, mut["fc1_slab"]:mut["fc1_slab"] + 32] = 0.0
+        a8 = np.tanh(P["B3"] + xs @ W3)
+        xs = a8
+        if "fc2_block" in mut:
+            xs = a8.copy(); xs[:, mut["fc2_block"]:mut["fc2_block"] + 16] = 0.0
+        if "act3_swap" in mut:
+            c = mut["act3_swap"]
+            xs = a8.copy(); xs[:, [c, c + 1]] = xs[:, [c + 1, c]]
+        logits = P["B4"] + xs @ W4
         y = np.exp(logits)
-    for b, m in CHUNKS:
-        y[:, b:b + m] /= (_seqsum(y[:, b:b + m]) if f32 else y[:, b:b + m].sum(-1))[:, None]
+    sums = [(_seqsum(y[:, b:b + m]) if f32 else y[:, b:b + m].sum(-1)) for b, m in CHUNKS]
+    if "softmax_sum" in mut:
+        sums[mut["softmax_sum"][0]] = sums[mut["softmax_sum"][1]]
+    for (b, m), sm in zip(CHUNKS, sums):
+        y[:, b:b + m] /= sm[:, None]
+    return dict(a3=a3, a6=a6, a8=a8, logits=logits, y=y, a1=a1, a5=a5, k1=k1, k2=k2, k3=k3)
+
+
+def step(w, X, T, alpha, side, mode="f64", want_delta=True):
+    D = dims(side)
+    S, c1, p2, c2, p3, fc = side, D["c1"], D["p2"], D["c2"], D["p3"], D["fc"]
+    f32 = mode == "f32"
+    dt = np.float32 if f32 else np.float64
+    w = np.asarray(w, dt)
+    P = split(w, side)
+    X = np.asarray(X, dt).reshape(-1, S, S); T = np.asarray(T, dt).reshape(-1, 2304)
+    n = X.shape[0]
+    alpha = dt(np.float32(alpha))
+    one = dt(1)
+    W1, W2, W3, W4 = P["W1"], P["W2"], P["W3"], P["W4"]
+    F = forward(w, X, side, mode)
+    a1, a3, a5, a6, a8, logits, y, k1, k2, k3 = (F[k] for k in ("a1", "a3", "a5", "a6", "a8", "logits", "y", "k1", "k2", "k3"))
     # errors (ho_cnn_train)
     e10 = y - T
     sq = e10 * e10
@@ -290,9 +339,7 @@ def _frames():
         fp = C.POINTER(C.c_float)
         out = {}
         for f in FRAMES:
-            d = z["depth"][f].reshape(-1).astype(np.float32) * np.float32(z["cam"][f][4])      # ho_cnn_input, handtrack.h:700
-            v = np.float32(1) - (d - np.float32(0.1)) / (np.float32(0.7) - np.float32(0.1))
-            x = np.minimum(np.maximum(v, np.float32(0)), np.float32(1)).astype(np.float32)
+            x = _tile_input(z["depth"][f], z["cam"][f][4])
             cam = np.array(z["cam"][f], np.float32); cam[:4] *= np.float32(0.5)      # camsub(cam, 8) = camsub of the halved camera by 4
             pose = np.ascontiguousarray(z["startpose"][f], np.float32)
             t = np.zeros(2304, np.float32)
@@ -310,6 +357,77 @@ def sample(name):
         return np.full(16384, 0.0 if name == "z0" else 1.0, np.float32), _frames()["f33" if name == "z0" else "f60"][1]
     rng = np.random.default_rng(100 + int(name[1:]))
     return rng.random(16384).astype(np.float32), rng.random(2304).astype(np.float32)
+
+
+# ---- the inference nets' cases (tests/test_cnn_forward_ref.py, tests/test_gpu_cnn_forward.py) ---------------------------------------------
+FWD_TENSORS = ("a3", "a6", "a8", "logits", "y")
+FWD_SEED = ("f0", "f9", "z0", "z1", "x0", "x1")      # on the seeded weights
+FWD_SAT = ("x0", "x1")                               # on the weights scaled as batch Td (side 128) / case d (side 64) scales them: "Td:x0", "Td:x1"
+FWD_CASES = FWD_SEED + tuple("Td:" + s for s in FWD_SAT)
+
+
+def _tile_input(depth, dscale):
+    """ho_cnn_input, handtrack.h:700, float32 operation for operation"""
+    d = np.asarray(depth).reshape(-1).astype(np.float32) * np.float32(dscale)
+    v = np.float32(1) - (d - np.float32(0.1)) / (np.float32(0.7) - np.float32(0.1))
+    return np.minimum(np.maximum(v, np.float32(0)), np.float32(1)).astype(np.float32)
+
+
+def forward_input(name, side):
+    """the input [side*side] float32 of a sample: sample(name)[0] at side 128; at side 64 "f<k>" is tile k of tests/golden/frames256.npz, the others the same
+    constructions on 4096 values.  No labels, so no library is needed."""
+    n = side * side
+    if name[0] == "f":
+        z = np.load(os.path.join(HERE, "golden", "frames5_64.npz" if side == 128 else "frames256.npz"))
+        k = int(name[1:])
+        return _tile_input(z["depth"][k], z["cam"][k][4])
+    if name in ("z0", "z1"):
+        return np.full(n, 0.0 if name == "z0" else 1.0, np.float32)
+    return np.random.default_rng(100 + int(name[1:])).random(n).astype(np.float32)
+
+
+def forward_weights(key, w, side):
+    """"seed": w itself; "sat": start_weights("sat") at side 128, train_ref's case d (W1 and W2 times SAT_SCALE) at side 64"""
+    if key == "seed":
+        return np.array(w, np.float32, copy=True)
+    if side == 128:
+        return start_weights("sat", w)
+    import train_ref
+    off, _, _ = layout(64)
+    w = np.array(w, np.float32, copy=True)
+    w[off["W1"]:off["B1"]] *= np.float32(train_ref.SAT_SCALE); w[off["W2"]:off["B2"]] *= np.float32(train_ref.SAT_SCALE)
+    return w
+
+
+def forward_bounds(f64, f32):
+    """per tensor the rule's bound of every row: 4 d32 + 4 * 2^-24 max|T_64|, and d32"""
+    out = {}
+    for T in FWD_TENSORS:
+        a, b = np.asarray(f64[T], np.float64).reshape(len(f64[T]), -1), np.asarray(f32[T], np.float64).reshape(len(f64[T]), -1)
+        d32 = np.abs(a - b).max(1)
+        out[T] = (4.0 * d32 + 4.0 * 2.0 ** -24 * np.abs(a).max(1), d32)
+    return out
+
+
+def forward_references(side, w):
+    """the eight cases of a side at the seeded weights w of that side: names, X [8, side*side], which weights a case runs on, and per case (row) the float64 forward, the
+    float32 forward in the reference's order and the rule's bound per tensor.  Computed once per side and not to be modified."""
+    key = ("fwd", side)
+    if key not in _cache:
+        X = np.stack([forward_input(s.split(":")[-1], side) for s in FWD_CASES])
+        wkey = ["sat" if s.startswith("Td:") else "seed" for s in FWD_CASES]
+        f64 = {T: [None] * len(FWD_CASES) for T in FWD_TENSORS}; f32 = {T: [None] * len(FWD_CASES) for T in FWD_TENSORS}
+        for k in ("seed", "sat"):
+            rows = [i for i, q in enumerate(wkey) if q == k]
+            wk = forward_weights(k, w, side)
+            a, b = forward(np.float64(wk), X[rows], side, "f64"), forward(wk, X[rows], side, "f32")
+            for T in FWD_TENSORS:
+                for j, i in enumerate(rows):
+                    f64[T][i] = np.asarray(a[T][j]).reshape(-1); f32[T][i] = np.asarray(b[T][j]).reshape(-1)
+        f64 = {T: np.stack(v) for T, v in f64.items()}; f32 = {T: np.stack(v) for T, v in f32.items()}
+        bd = forward_bounds(f64, f32)
+        _cache[key] = dict(names=FWD_CASES, X=X, wkey=wkey, f64=f64, f32=f32, bound={T: bd[T][0] for T in FWD_TENSORS}, d32={T: bd[T][1] for T in FWD_TENSORS})
+    return _cache[key]
 
 
 def start_weights(key, w128):
