@@ -16,6 +16,7 @@ CNN_IN, CNN_OUT, CNNB_COUNT, POSE, STATE, CAM, ANALYSIS = 4096, 2304, 9458400, 7
 MAXPTS, ROW, CONTACT = 4096, 16, 12      # HT_MAX_POINTS
 LABELS_SEGMENT_FRAME = 1      # HT_LABELS_SEGMENT_FRAME
 LABELS_SIDE128 = 2            # HT_LABELS_SIDE128
+SENSOR_IVY, SENSOR_DS4 = 0, 1 # HT_SENSOR_IVY, HT_SENSOR_DS4
 CNN128_IN, CNNB128_COUNT = 16384, 30429920
 # ht_debug_train_buffers: (name, floats, shape) of the segments of act and err, in order (None: padding)
 TRAIN_ACT = (("a1", 57600, (16, 60, 60)), ("a3", 3600, (16, 15, 15)), ("a5", 9216, (64, 12, 12)), ("a6", 2304, (2304,)), ("a8", 2048, (2048,)))
@@ -31,6 +32,7 @@ SYMBOLS = (
     "ht_tracker_reset", "ht_get_state", "ht_set_state", "ht_get_tracker_flags", "ht_set_tracker_flags", "ht_update_sync", "ht_update_dev", "ht_update_frames_sync", "ht_update_frames_dev", "ht_update_direct_sync", "ht_update_direct_dev", "ht_update_cnn_model_sync", "ht_get_cnn_results", "ht_get_cnn_layers", "ht_get_cnn_layers_sized", "ht_frames_overflow", "ht_reserve_points", "ht_point_capacity", "ht_capacity_events", "ht_segment_vr", "ht_segment_vr_dev", "ht_render_depth", "ht_render_depth_dev", "ht_slowfit", "ht_set_points", "ht_fit_rows", "ht_physics_update",
     "ht_stage_prepare", "ht_stage_decode", "ht_stage_fit_error", "ht_stage_cloud_rows", "ht_stage_contacts", "ht_stage_fit",
     "ht_stage_multistep", "ht_stage_multistep_range", "ht_stage_scratch_unibody", "ht_stage_chamber", "ht_profile_enable", "ht_profile_read", "ht_debug_solve_stats", "ht_debug_contact_stats", "ht_debug_solver_build", "ht_debug_reset_flags", "ht_debug_reset_organisation", "ht_update_passes_sync", "ht_job_start", "ht_job_poll", "ht_job_wait", "ht_job_collect", "ht_debug_contact_kernel", "ht_debug_contact_order", "ht_debug_rank_desc", "ht_contact_capacity", "ht_debug_solve_tables", "ht_debug_solve_tables_header", "ht_debug_train_buffers",
+    "ht_sensor_out_dims", "ht_sensor_filter", "ht_sensor_filter_dev", "ht_sensor_background", "ht_sensor_background_dev",
     "ht_comm_available", "ht_comm_unique_id", "ht_comm_init", "ht_comm_info", "ht_gather_poses_dev", "ht_gather_wait", "ht_gather_wait_host", "ht_comm_destroy",
 )
 
@@ -133,6 +135,11 @@ def load(build_if_missing=True):
     L.ht_segment_vr_dev.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, vp, vp, vp]
     L.ht_render_depth.argtypes = [vp, fp, fp, C.c_int, C.c_int, C.c_float, C.c_int, u16p, C.POINTER(C.c_int8)]
     L.ht_render_depth_dev.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_float, C.c_int, vp, vp, vp]
+    L.ht_sensor_out_dims.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, ip, ip]
+    L.ht_sensor_filter.argtypes = [vp, C.c_int, u16p, C.POINTER(C.c_uint8), fp, C.c_int, C.c_int, C.c_int, C.c_int, u16p, u16p, fp]
+    L.ht_sensor_filter_dev.argtypes = [vp, C.c_int, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp]
+    L.ht_sensor_background.argtypes = [vp, u16p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, u16p]
+    L.ht_sensor_background_dev.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]
     L.ht_render_mesh_depth.argtypes = [vp, fp, fp, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int, u16p, C.POINTER(C.c_int8)]
     L.ht_render_mesh_depth_dev.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int, vp, vp, vp]
     L.ht_model_hitcheck_mesh.argtypes = [vp, fp, fp, fp, fp, fp, ip, ip]
@@ -588,6 +595,45 @@ class Context:
         """ht_render_mesh_depth_dev: device pointers, asynchronous on `stream`."""
         self._chk(self.L.ht_render_mesh_depth_dev(self.h, d_poses, d_cams, int(w), int(h), float(far), float(pixel_offset), int(B), d_depth, d_body, stream))
 
+    def sensor_filter(self, kind, depth, cams, ir=None, background=None, max_width=320):
+        """RSCam::FilterIvy / FilterDS4 (dcam.h:174-226) for a batch of raw frames: depth u16[B,h,w], cams [B,12], ir u8[B,h,w] (DS4), background u16[B,h,w]
+        (DS4, optional) -> (depth u16[B,h_out,w_out], cams [B,12])."""
+        depth = _c(depth, np.uint16); B, h, w = depth.shape
+        cams = _c(cams, np.float32).reshape(B, CAM)
+        ir = None if ir is None else _c(ir, np.uint8); background = None if background is None else _c(background, np.uint16)
+        for a in (ir, background):
+            if a is not None and a.shape != depth.shape:
+                raise ValueError("ir and background have the frames' shape")
+        try:
+            wo, ho = sensor_out_dims(kind, w, h, max_width)
+        except ValueError:
+            wo, ho = w, h      # the call below refuses it, with the library's message
+        out = np.empty((B, ho, wo), np.uint16); co = np.empty((B, CAM), np.float32)
+        u8p, u16p = C.POINTER(C.c_uint8), C.POINTER(C.c_uint16)
+        self._chk(self.L.ht_sensor_filter(self.h, int(kind), depth.ctypes.data_as(u16p), None if ir is None else ir.ctypes.data_as(u8p), _f(cams), w, h, B, int(max_width),
+                                          None if background is None else background.ctypes.data_as(u16p), out.ctypes.data_as(u16p), _f(co)))
+        return out, co
+
+    def sensor_filter_dev(self, kind, d_depth, d_ir, d_cams, w, h, B, max_width, d_background, d_depth_out, d_cams_out, stream=None):
+        """ht_sensor_filter_dev: device pointers (d_ir / d_background may be None), asynchronous on `stream`."""
+        self._chk(self.L.ht_sensor_filter_dev(self.h, int(kind), d_depth, d_ir, d_cams, int(w), int(h), int(B), int(max_width), d_background, d_depth_out, d_cams_out, stream))
+
+    def sensor_background(self, depth, background=None, fudge=3):
+        """RSCam::addbackground (dcam.h:157-162) for a batch: depth u16[B,h,w] folded into the model background u16[B,h,w] (None: a model that starts at 4096);
+        returns the new model."""
+        depth = _c(depth, np.uint16); B, h, w = depth.shape
+        init = background is None
+        bg = np.empty(depth.shape, np.uint16) if init else np.array(background, dtype=np.uint16, order="C")
+        if bg.shape != depth.shape:
+            raise ValueError("the background model has the frames' shape")
+        u16p = C.POINTER(C.c_uint16)
+        self._chk(self.L.ht_sensor_background(self.h, depth.ctypes.data_as(u16p), w, h, B, int(fudge), int(init), bg.ctypes.data_as(u16p)))
+        return bg
+
+    def sensor_background_dev(self, d_depth, w, h, B, fudge, init, d_background, stream=None):
+        """ht_sensor_background_dev: device pointers, asynchronous on `stream`."""
+        self._chk(self.L.ht_sensor_background_dev(self.h, d_depth, int(w), int(h), int(B), int(fudge), int(bool(init)), d_background, stream))
+
     def scale(self, s):
         """HandTracker::scale (handtrack.h:591): both models of every slot grow by the factor s."""
         self._chk(self.L.ht_scale(self.h, float(s)))
@@ -718,6 +764,14 @@ class Context:
                     out[name] = buf[o:o + n].reshape(shape)
                 o += n
         return out
+
+
+def sensor_out_dims(kind, w, h, max_width=320):
+    """ht_sensor_out_dims: (w_out, h_out) of a filtered frame; ValueError for what the filters refuse on sizes alone.  No context, no device."""
+    wo, ho = C.c_int(0), C.c_int(0)
+    if load().ht_sensor_out_dims(int(kind), int(w), int(h), int(max_width), C.byref(wo), C.byref(ho)) != HT_OK:
+        raise ValueError("ht_sensor_out_dims refuses kind %d, %dx%d, max_width %d" % (kind, w, h, max_width))
+    return wo.value, ho.value
 
 
 def comm_available():

@@ -595,6 +595,40 @@ inline Image<unsigned short> HandSegmentVR(const Image<unsigned short> &depth, i
 	return HandTracker::segment_on(detail::live_ctx(), depth, entry_options, wrange, diam);
 }
 
+// RSCam's depth filters (include/dcam.h:144-244): what dcam.GetDepth() does to the sensor's frame before htk.update() sees it, on the device of the first live
+// HandTracker.  No librealsense and no device handle: the caller hands over the raw frame (and, for an R200, the IR image of the same size) it got from its camera.
+//     auto dimage = cam.FilterIvy(raw);  auto pose = htk.update(std::move(dimage));      // replaces htk.update(dcam.GetDepth()), realtime-tracker.cpp:56
+struct RSCam
+{
+	int image_width_max_allowed = 320;                                                         // dcam.h:153
+	std::vector<uint16_t> background;                                                          // dcam.h:156: empty until addbackground is called
+	void addbackground(const Image<unsigned short> &dp, unsigned short fudge = 3)              // dcam.h:157-162
+	{
+		const bool init = background.size() != dp.raster.size();
+		if (init) background.resize(dp.raster.size());
+		detail_check(ht_sensor_background(ctx(), dp.raster.data(), dp.dim().x, dp.dim().y, 1, fudge, init ? 1 : 0, background.data()));
+	}
+	Image<unsigned short> FilterDS4(const Image<unsigned short> &dp, const Image<unsigned char> &ir) { return filter(HT_SENSOR_DS4, dp, ir.raster.data(), ir.raster.size()); }      // dcam.h:174-208
+	Image<unsigned short> FilterIvy(const Image<unsigned short> &dp) { return filter(HT_SENSOR_IVY, dp, nullptr, 0); }                                                             // dcam.h:209-226
+private:
+	static ht_ctx *ctx() { if (!detail::live_ctx()) throw std::runtime_error("RSCam: construct a HandTracker first (the filters run on its device)"); return detail::live_ctx(); }
+	static void detail_check(int rc) { check(detail::live_ctx(), rc); }
+	Image<unsigned short> filter(int kind, const Image<unsigned short> &dp, const unsigned char *ir, size_t nir)
+	{
+		const int w = dp.dim().x, h = dp.dim().y;
+		int wo = 0, ho = 0;
+		if (dp.raster.size() != (size_t)w * h || (kind == HT_SENSOR_DS4 && nir != dp.raster.size()) || ht_sensor_out_dims(kind, w, h, image_width_max_allowed, &wo, &ho) != HT_OK)
+			throw std::runtime_error("RSCam: a frame of this size cannot be filtered");
+		float cam[HT_CAM] = { dp.cam.focal().x, dp.cam.focal().y, dp.cam.principal().x, dp.cam.principal().y, dp.cam.depth_scale, dp.cam.pose.position.x, dp.cam.pose.position.y, dp.cam.pose.position.z,
+		                      dp.cam.pose.orientation.x, dp.cam.pose.orientation.y, dp.cam.pose.orientation.z, dp.cam.pose.orientation.w }, co[HT_CAM];
+		Image<unsigned short> out(DCamera({ wo, ho }, { 0, 0 }, { 0, 0 }, dp.cam.depth_scale, dp.cam.pose));
+		const bool bg = kind == HT_SENSOR_DS4 && background.size() == dp.raster.size();      // dcam.h:201
+		detail_check(ht_sensor_filter(ctx(), kind, dp.raster.data(), ir, cam, w, h, 1, image_width_max_allowed, bg ? background.data() : nullptr, out.raster.data(), co));
+		out.cam.focal() = { co[0], co[1] }; out.cam.principal() = { co[2], co[3] };
+		return out;
+	}
+};
+
 // CNN PoseInitializerCNN(std::string filename) (handtrack.h:103-130): the pose net as an object of its own (own CNN-only device context); like the
 // reference, a missing weight file is not an error here -- Eval then fails loudly instead of running on random weights.
 inline CNN PoseInitializerCNN(std::string filename, int device = 0)
@@ -730,5 +764,5 @@ inline PhysModel LoadHandModel(const char *jsonfile = "../assets/model_hand.json
 using ht_mi355x::float2; using ht_mi355x::float3; using ht_mi355x::float4; using ht_mi355x::int2; using ht_mi355x::int3;
 using ht_mi355x::Pose; using ht_mi355x::DCamera; using ht_mi355x::Image; using ht_mi355x::Mesh; using ht_mi355x::CNN; using ht_mi355x::HandTracker; using ht_mi355x::PhysModel;
 using ht_mi355x::RigidBody; using ht_mi355x::LimitLinear; using ht_mi355x::LimitAngular; using ht_mi355x::PhysicsUpdate; using ht_mi355x::Addresses;
-using ht_mi355x::HandSegmentVR; using ht_mi355x::PointCloud; using ht_mi355x::camsub; using ht_mi355x::GatherHandExpectedCNN; using ht_mi355x::PoseInitializerCNN; using ht_mi355x::LoadHandModel;
+using ht_mi355x::HandSegmentVR; using ht_mi355x::RSCam; using ht_mi355x::PointCloud; using ht_mi355x::camsub; using ht_mi355x::GatherHandExpectedCNN; using ht_mi355x::PoseInitializerCNN; using ht_mi355x::LoadHandModel;
 #endif

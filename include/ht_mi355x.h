@@ -365,6 +365,41 @@ int ht_render_depth_dev(ht_ctx *ctx, const float *d_poses, const float *d_cams, 
 int ht_render_mesh_depth(ht_ctx *ctx, const float *poses, const float *cams, int w, int h, float far, float pixel_offset, int B, uint16_t *depth, int8_t *body);
 int ht_render_mesh_depth_dev(ht_ctx *ctx, const float *d_poses, const float *d_cams, int w, int h, float far, float pixel_offset, int B, uint16_t *d_depth, int8_t *d_body, void *stream);
 
+/* ---- camera front end: the depth filters of RSCam::GetDepth (include/dcam.h:238-244) for raw sensor frames ------------------------------
+ * Every real-time program of the reference feeds the tracker htk.update(dcam.GetDepth()); GetDepth filters the sensor's frame first.  All arithmetic is
+ * integer, the constants are dcam.h's own (it assumes millimetre counts, dcam.h:180).
+ * ht_sensor_out_dims    the size a filtered frame has: k = the number of halvings until w >> k <= max_width (dcam.h:205-206, 212-213), *w_out = w >> k,
+ *                       *h_out = h >> k.  No context.  HT_ERR_ARG for what the filter refuses on sizes alone (below).
+ * ht_sensor_filter      kind HT_SENSOR_IVY replaces  Image<unsigned short> RSCam::FilterIvy(unsigned short *dp) (dcam.h:209-226), SR300 / F200: output pixel
+ *                       (x, y) = input pixel (x << k, y << k) (DownSampleFst k times, misc_image.h:81-94,136), the camera is cam / 2 k times (focal and
+ *                       principal halved, depth_scale and pose kept, misc_image.h:62), then every output pixel equal to 0 becomes
+ *                       (unsigned short)(4.0f / depth_scale), formed as the x86 build forms it: the float quotient, a truncating conversion to int32, its
+ *                       low 16 bits.
+ *                       kind HT_SENSOR_DS4 replaces  Image<unsigned short> RSCam::FilterDS4(unsigned short *dp) (dcam.h:174-208), R200: (1) d < 30 || ir < 8
+ *                       -> 4096; (2) pixels i = 0 .. w*h-1 in raster order, skipping x < 2, x >= w-2, y < 2, y >= h-2: with has(s) = |p[i+s] - p[i]| < 10 ||
+ *                       |p[i-s] - p[i]| < 10 in int, p[i] = 4096 AT ONCE unless has(1), has(w), has(2) and has(2w) all hold -- so p[i-1], p[i-2], p[i-w],
+ *                       p[i-2w] are read as already rewritten; (3) with a background model, p[i] > background[i] -> 4096.  Bit-identical to that
+ *                       sequential loop (csrc/ht_sensor.hip has the decomposition).
+ *                       depth [B][h*w], ir [B][h*w] (DS4: required; Ivy: ignored), cams [B][12], background [B][h*w] (DS4 only, caller-owned, may be NULL)
+ *                       -> depth_out [B][h_out*w_out], cams_out [B][12]: an ordinary input of ht_update_frames_* and ht_segment_vr*, which keep their own
+ *                       checks.  B is not bounded by max_batch (no tracker slot; the host form stages through a device buffer it grows on demand); B = 0
+ *                       does nothing.  HT_ERR_ARG, checked before anything is launched or grown: a NULL required buffer; w or h < 1 or > 4096;
+ *                       max_width < 1; Ivy with w or h not divisible by 2^k (the reference reads past the image there); DS4 with w > max_width (the
+ *                       reference indexes the full-size frame with an IR image it has already halved, dcam.h:170-171,184; R200 streams 320x240); a
+ *                       background with Ivy (its path has none); depth_out overlapping depth.
+ * ht_sensor_filter_dev  the same on device buffers, asynchronous on `stream`.
+ * ht_sensor_background  replaces  void RSCam::addbackground(const unsigned short *dp, unsigned short fudge = 3) (dcam.h:157-162) for B frames:
+ *                       background[i] = min(background[i], (unsigned short)(dp[i] - fudge)), the subtraction in int, the cast wrapping; init != 0 treats
+ *                       the old model as 4096 everywhere (what the first call's resize gives, dcam.h:159).  depth, background [B][h*w].
+ * ht_sensor_background_dev  the same on device buffers, asynchronous on `stream`. */
+#define HT_SENSOR_IVY 0
+#define HT_SENSOR_DS4 1
+int ht_sensor_out_dims(int kind, int w, int h, int max_width, int *w_out, int *h_out);
+int ht_sensor_filter(ht_ctx *ctx, int kind, const uint16_t *depth, const uint8_t *ir, const float *cams, int w, int h, int B, int max_width, const uint16_t *background, uint16_t *depth_out, float *cams_out);
+int ht_sensor_filter_dev(ht_ctx *ctx, int kind, const uint16_t *d_depth, const uint8_t *d_ir, const float *d_cams, int w, int h, int B, int max_width, const uint16_t *d_background, uint16_t *d_depth_out, float *d_cams_out, void *stream);
+int ht_sensor_background(ht_ctx *ctx, const uint16_t *depth, int w, int h, int B, int fudge, int init, uint16_t *background);
+int ht_sensor_background_dev(ht_ctx *ctx, const uint16_t *d_depth, int w, int h, int B, int fudge, int init, uint16_t *d_background, void *stream);
+
 /* ---- annotation fit loop ---------------------------------------------------------------------------------------------
  * ht_slowfit          replaces  void HandTracker::slowfit(const std::vector<float3> &points, int hold, const std::vector<Pose> &refpose,
  *                     int steps_ = 6, RigidBody *selectrb = NULL, const float3 &spoint, const float3 &rbpoint, const std::vector<float4> &crays)
