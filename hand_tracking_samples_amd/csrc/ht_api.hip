@@ -11,7 +11,7 @@
 #include "ht_host.hpp"
 #include "ht_launch.hpp"
 #include "ht_model_build.hpp"
-#include "ht_train_shared.hpp"      // the .cnnb layout and the packed conv2 index
+#include "ht_train_shared.hpp"      // the packed conv2 index
 
 // ------------------------------------------------------------------------------------------------- context
 static void default_params(ht_params &p)     // handtrack.h:523-547, physics.h:45-47, physmodel.h:234, handtrack.h:369,450
@@ -258,17 +258,14 @@ extern "C" int ht_scale(ht_ctx *ctx, float s)
 // Training on the weights held by the context; ht_cnn_get_weights reads them back in .cnnb order (CNN::saveb cnn.h:591-593).  Two step implementations, chosen by
 // the entry point: CNN::Train (cnn.h:558-580), one SGD step per sample in the order given (train-cnn.cpp:156-162 calls it with alpha = 0.001; ht_train.hip), and
 // mini-batch steps w' = w - alpha * sum_b g_b(w) (ht_train_batch.hip).  `batched` says which; the per-sample forms are checked as steps of batch = 1.  The mini-batch
-// step trains either net (side = 64 or 128, the *_sized entry points), the per-sample step the 64x64-input net only.
-// The arguments are checked completely before an arena or the staging buffer grows or anything is launched.
-static int cnn_train_check(ht_ctx *ctx, const char *fn, bool batched, int side, const void *in, const void *tg, int n_pool, const int *order, int n_steps, int batch)
+// step trains either net (the *_sized entry points: ht_net_of), the per-sample step the 64x64-input net only.  Every implementation below takes the net and refuses
+// a null one (ht_net_of has said why).  The arguments are checked completely before an arena or the staging buffer grows or anything is launched.
+static int cnn_train_check(ht_ctx *ctx, const char *fn, bool batched, const ht_net *net, const void *in, const void *tg, int n_pool, const int *order, int n_steps, int batch)
 {
 	const std::string f(fn);
-	if (side == 128) { if (!ctx->have_weights128) { ctx->err = f + ": the context holds no weights of the 128x128-input net (ht_cnn_load_weights_sized)"; return HT_ERR_ARG; } }
-	else
-	{
-		if (!ctx->have_weights && !batched) { ctx->err = "CNN weights not loaded (ht_cnn_load_weights)"; return HT_ERR_STATE; }
-		if (!ctx->have_weights) { ctx->err = f + ": the context holds no weights of the 64x64-input net (ht_cnn_load_weights); the 128x128-input net is trained by ht_cnn_train_batch_sized"; return HT_ERR_ARG; }
-	}
+	if (!net) return HT_ERR_ARG;
+	if (!net->have && !batched) { ctx->err = net->missing; return HT_ERR_STATE; }
+	if (!net->have) { ctx->err = f + net->train_missing; return HT_ERR_ARG; }
 	if (batch < 1 || batch > HT_TRAIN_MAX_BATCH) { ctx->err = f + ": batch must be in [1, HT_TRAIN_MAX_BATCH = " + std::to_string(HT_TRAIN_MAX_BATCH) + "]"; return HT_ERR_ARG; }
 	if (!in || !tg) { ctx->err = f + ": inputs and targets must not be NULL"; return HT_ERR_ARG; }
 	if (n_pool < 1) { ctx->err = f + ": n_pool must be positive"; return HT_ERR_ARG; }
@@ -277,20 +274,12 @@ static int cnn_train_check(ht_ctx *ctx, const char *fn, bool batched, int side, 
 	if (order) for (long long k = 0; k < (long long)n_steps * batch; k++) if (order[k] < 0 || order[k] >= n_pool) { ctx->err = f + ": order[" + std::to_string(k) + "] is outside [0, n_pool)"; return HT_ERR_ARG; }
 	return HT_OK;
 }
-// the mini-batch arena of either net: the buffer, its capacity in samples and the latest step's sample count
-struct cnn_train_arena { float **buf; int *cap, *last; };
-static cnn_train_arena cnn_train_arena_of(ht_ctx *ctx, int side)
-{
-	if (side == 128) return { &ctx->d_train_batch128, &ctx->train_batch_cap128, &ctx->train_batch_last128 };
-	return { &ctx->d_train_batch, &ctx->train_batch_cap, &ctx->train_batch_last };
-}
 // The steps on device pools over n_samples indices (order, or 0, 1, ...), checked by the caller.  Per sample: step k trains on index k; the training arena ends with
 // a sink for the per-step MSE when the caller asks for none.  Batched: steps of `batch` indices, the last step takes what is left.  Then, once, the forward
 // kernels' packed copy of the trained net's last layer follows the trained weights.
-static int cnn_train_steps(ht_ctx *ctx, bool batched, int side, const float *d_x, const float *d_t, const int *order, int n_samples, int batch, float alpha, float *d_mse, hipStream_t s)
+static int cnn_train_steps(ht_ctx *ctx, bool batched, ht_net &net, const float *d_x, const float *d_t, const int *order, int n_samples, int batch, float alpha, float *d_mse, hipStream_t s)
 {
-	const ht_cnn_weights &cw = side == 128 ? ctx->cnnw128 : ctx->cnnw;
-	float *w = side == 128 ? ctx->d_weights128 : ctx->d_weights, *W2p = w + (side == 128 ? HT_CNNB128_COUNT : HT_CNNB_COUNT);
+	float *w = net.d_weights, *W2p = w + net.dims.count;
 	if (!batched)
 	{
 		const size_t na = ht_train_act_floats(), ne = ht_train_err_floats(), np = ht_train_part_floats();
@@ -299,123 +288,112 @@ static int cnn_train_steps(ht_ctx *ctx, bool batched, int side, const float *d_x
 		for (int k = 0; k < n_samples; k++)
 		{
 			const size_t i = order ? (size_t)order[k] : (size_t)k;
-			ht_launch_train_step(w, W2p, d_x + i * HT_CNN_IN, d_t + i * HT_CNN_OUT, alpha, ctx->d_train, ctx->d_train + na, ctx->d_train + na + ne, d_mse ? d_mse + k : sink, s);
+			ht_launch_train_step(w, W2p, d_x + i * net.dims.in, d_t + i * HT_CNN_OUT, alpha, ctx->d_train, ctx->d_train + na, ctx->d_train + na + ne, d_mse ? d_mse + k : sink, s);
 		}
 	}
 	else
 	{
 		const int cap = (batch + 31) & ~31;
-		const cnn_train_arena ar = cnn_train_arena_of(ctx, side);
-		{ const int r = dev_grow(ctx, ar.buf, ar.cap, (size_t)cap, ht_train_batch_floats(cap, side) / (size_t)cap + 1); if (r) return r; }
+		{ const int r = dev_grow(ctx, &net.train.buf, &net.train.cap, (size_t)cap, ht_train_batch_floats(cap, net.dims) / (size_t)cap + 1); if (r) return r; }
 		int index[HT_TRAIN_MAX_BATCH];
 		for (int k = 0; k < n_samples; k += batch)
 		{
 			const int n = n_samples - k < batch ? n_samples - k : batch;
 			for (int b = 0; b < n; b++) index[b] = order ? order[k + b] : k + b;
-			ht_launch_train_batch_step(w, W2p, d_x, d_t, index, n, alpha, *ar.buf, *ar.cap, d_mse ? d_mse + k : nullptr, s, side);
-			*ar.last = n;
+			ht_launch_train_batch_step(w, W2p, d_x, d_t, index, n, alpha, net.train.buf, net.train.cap, d_mse ? d_mse + k : nullptr, s, net.dims);
+			net.train.last = n;
 		}
 	}
-	ht_launch_pack_w4(cw.W4, W2p + 16384, s);
+	ht_launch_pack_w4(net.w.W4, W2p + 16384, s);
 	HIPCHK(ctx, hipGetLastError());
 	return HT_OK;
 }
 // the device-pool forms: asynchronous on the caller's stream
-static int cnn_train_dev(ht_ctx *ctx, const char *fn, bool batched, int side, const float *d_inputs, const float *d_targets, int n_pool, const int *order, int n_steps, int batch, float alpha, float *d_mse, void *stream)
+static int cnn_train_dev(ht_ctx *ctx, const char *fn, bool batched, ht_net *net, const float *d_inputs, const float *d_targets, int n_pool, const int *order, int n_steps, int batch, float alpha, float *d_mse, void *stream)
 {
-	{ const int r = cnn_train_check(ctx, fn, batched, side, d_inputs, d_targets, n_pool, order, n_steps, batch); if (r) return r; }
+	{ const int r = cnn_train_check(ctx, fn, batched, net, d_inputs, d_targets, n_pool, order, n_steps, batch); if (r) return r; }
 	if (n_steps == 0) return HT_OK;
-	return cnn_train_steps(ctx, batched, side, d_inputs, d_targets, order, n_steps * batch, batch, alpha, d_mse, ht_user_stream(ctx, stream));
+	return cnn_train_steps(ctx, batched, *net, d_inputs, d_targets, order, n_steps * batch, batch, alpha, d_mse, ht_user_stream(ctx, stream));
 }
 // the host-array forms: the n samples staged through the context's buffer (ht_staged_call), then the same steps in order on the context's stream
-static int cnn_train_host(ht_ctx *ctx, const char *fn, bool batched, int side, const float *inputs, const float *targets, int n, int batch, float alpha, float *mse_out)
+static int cnn_train_host(ht_ctx *ctx, const char *fn, bool batched, ht_net *net, const float *inputs, const float *targets, int n, int batch, float alpha, float *mse_out)
 {
-	{ const int r = cnn_train_check(ctx, fn, batched, side, inputs, targets, n, nullptr, 0, batch); if (r) return r; }
-	ht_seg seg[3] = { { (void *)inputs, (size_t)n * side * side * sizeof(float), false }, { (void *)targets, (size_t)n * HT_CNN_OUT * sizeof(float), false }, { mse_out, (size_t)n * sizeof(float), true } };
+	{ const int r = cnn_train_check(ctx, fn, batched, net, inputs, targets, n, nullptr, 0, batch); if (r) return r; }
+	ht_seg seg[3] = { { (void *)inputs, (size_t)n * net->dims.in * sizeof(float), false }, { (void *)targets, (size_t)n * HT_CNN_OUT * sizeof(float), false }, { mse_out, (size_t)n * sizeof(float), true } };
 	return ht_staged_call(ctx, &ctx->d_train_io, &ctx->train_io_cap, seg, 3, [&](hipStream_t s)
-	                      { return cnn_train_steps(ctx, batched, side, (const float *)seg[0].dev, (const float *)seg[1].dev, nullptr, n, batch, alpha, (float *)seg[2].dev, s); });
+	                      { return cnn_train_steps(ctx, batched, *net, (const float *)seg[0].dev, (const float *)seg[1].dev, nullptr, n, batch, alpha, (float *)seg[2].dev, s); });
 }
+// Test aid: the per-sample tensors of the latest mini-batch step of a net (layout: ht_train_batch_views, csrc/ht_train_batch.hip)
+static int cnn_train_batch_buffers(ht_ctx *ctx, const char *fn, ht_net *net, int n, float *a3, float *a6, float *a8, float *e9, float *e7, float *e6, float *e3)
+{
+	const std::string f(fn);
+	float *const out[7] = { a3, a6, a8, e9, e7, e6, e3 };
+	if (!net) return HT_ERR_ARG;
+	for (int i = 0; i < 7; i++) if (!out[i]) { ctx->err = f + ": NULL output"; return HT_ERR_ARG; }
+	if (!net->train.buf || net->train.last < 1) { ctx->err = f + ": no mini-batch step has run"; return HT_ERR_STATE; }
+	if (n != net->train.last) { ctx->err = f + ": n must be the latest step's sample count, " + std::to_string(net->train.last); return HT_ERR_ARG; }
+	HIPCHK(ctx, ht_sync_all(ctx));
+	const float *view[7]; size_t per[7];
+	ht_train_batch_views(net->train.buf, net->train.cap, view, per, net->dims);
+	for (int i = 0; i < 7; i++) HIPCHK(ctx, hipMemcpy(out[i], view[i], (size_t)n * per[i] * sizeof(float), hipMemcpyDeviceToHost));
+	return HT_OK;
+}
+static int cnn_get_weights(ht_ctx *ctx, const ht_net *net, float *w, size_t n)
+{
+	if (!net || !w) return HT_ERR_ARG;
+	if (!net->have) { ctx->err = "no weights to read"; return HT_ERR_STATE; }
+	if (n != net->dims.count) { ctx->err = net->bad_count; return HT_ERR_ARG; }
+	HIPCHK(ctx, ht_sync_all(ctx));      // also a ht_cnn_train_dev on a caller's stream
+	HIPCHK(ctx, hipMemcpy(w, net->d_weights, n * sizeof(float), hipMemcpyDeviceToHost));
+	return HT_OK;
+}
+// The exports.  The unsized forms are the 64x64-input net's; a sized form takes the net of its side (side = 128: the larger net's weights, pools of [..][16384] inputs
+// and an arena of its own) and at side 64 is the unsized form, whose name its messages then carry (ht_form_name).
 extern "C" int ht_cnn_train_dev(ht_ctx *ctx, const float *d_inputs, const float *d_targets, int n_pool, const int *order, int n_steps, float alpha, float *d_mse, void *stream)
 {
 	CHECK_READY(ctx);
-	return cnn_train_dev(ctx, "ht_cnn_train_dev", false, 64, d_inputs, d_targets, n_pool, order, n_steps, 1, alpha, d_mse, stream);
+	return cnn_train_dev(ctx, "ht_cnn_train_dev", false, ht_net_of(ctx, 64), d_inputs, d_targets, n_pool, order, n_steps, 1, alpha, d_mse, stream);
 }
 extern "C" int ht_cnn_train(ht_ctx *ctx, const float *inputs, const float *targets, int n, float alpha, float *mse_out)
 {
 	CHECK_READY(ctx);
-	return cnn_train_host(ctx, "ht_cnn_train", false, 64, inputs, targets, n, 1, alpha, mse_out);
+	return cnn_train_host(ctx, "ht_cnn_train", false, ht_net_of(ctx, 64), inputs, targets, n, 1, alpha, mse_out);
 }
 extern "C" int ht_cnn_train_batch_dev(ht_ctx *ctx, const float *d_inputs, const float *d_targets, int n_pool, const int *order, int n_steps, int batch, float alpha, float *d_mse, void *stream)
 {
 	CHECK_READY(ctx);
-	return cnn_train_dev(ctx, "ht_cnn_train_batch_dev", true, 64, d_inputs, d_targets, n_pool, order, n_steps, batch, alpha, d_mse, stream);
+	return cnn_train_dev(ctx, "ht_cnn_train_batch_dev", true, ht_net_of(ctx, 64), d_inputs, d_targets, n_pool, order, n_steps, batch, alpha, d_mse, stream);
 }
 extern "C" int ht_cnn_train_batch(ht_ctx *ctx, const float *inputs, const float *targets, int n, int batch, float alpha, float *mse_out)
 {
 	CHECK_READY(ctx);
-	return cnn_train_host(ctx, "ht_cnn_train_batch", true, 64, inputs, targets, n, batch, alpha, mse_out);
-}
-// Test aid: the per-sample tensors of the latest mini-batch step of a net (layout: ht_train_batch_views, csrc/ht_train_batch.hip)
-static int cnn_train_batch_buffers(ht_ctx *ctx, const char *fn, int side, int n, float *const out[7])
-{
-	const std::string f(fn);
-	const cnn_train_arena ar = cnn_train_arena_of(ctx, side);
-	for (int i = 0; i < 7; i++) if (!out[i]) { ctx->err = f + ": NULL output"; return HT_ERR_ARG; }
-	if (!*ar.buf || *ar.last < 1) { ctx->err = f + ": no mini-batch step has run"; return HT_ERR_STATE; }
-	if (n != *ar.last) { ctx->err = f + ": n must be the latest step's sample count, " + std::to_string(*ar.last); return HT_ERR_ARG; }
-	HIPCHK(ctx, ht_sync_all(ctx));
-	const float *view[7]; size_t per[7];
-	ht_train_batch_views(*ar.buf, *ar.cap, view, per, side);
-	for (int i = 0; i < 7; i++) HIPCHK(ctx, hipMemcpy(out[i], view[i], (size_t)n * per[i] * sizeof(float), hipMemcpyDeviceToHost));
-	return HT_OK;
+	return cnn_train_host(ctx, "ht_cnn_train_batch", true, ht_net_of(ctx, 64), inputs, targets, n, batch, alpha, mse_out);
 }
 extern "C" int ht_debug_train_batch_buffers(ht_ctx *ctx, int n, float *a3, float *a6, float *a8, float *e9, float *e7, float *e6, float *e3)
 {
 	CHECK_READY(ctx);
-	float *const out[7] = { a3, a6, a8, e9, e7, e6, e3 };
-	return cnn_train_batch_buffers(ctx, "ht_debug_train_batch_buffers", 64, n, out);
+	return cnn_train_batch_buffers(ctx, "ht_debug_train_batch_buffers", ht_net_of(ctx, 64), n, a3, a6, a8, e9, e7, e6, e3);
 }
-static int cnn_get_weights(ht_ctx *ctx, int side, float *w, size_t n)
-{
-	if (!w) return HT_ERR_ARG;
-	if (!(side == 128 ? ctx->have_weights128 : ctx->have_weights)) { ctx->err = "no weights to read"; return HT_ERR_STATE; }
-	if (n != (side == 128 ? (size_t)HT_CNNB128_COUNT : (size_t)HT_CNNB_COUNT)) { ctx->err = side == 128 ? "weights: expected HT_CNNB128_COUNT fp32 values in .cnnb order" : "weights: expected HT_CNNB_COUNT fp32 values in .cnnb order"; return HT_ERR_ARG; }
-	HIPCHK(ctx, ht_sync_all(ctx));      // also a ht_cnn_train_dev on a caller's stream
-	HIPCHK(ctx, hipMemcpy(w, side == 128 ? ctx->d_weights128 : ctx->d_weights, n * sizeof(float), hipMemcpyDeviceToHost));
-	return HT_OK;
-}
-extern "C" int ht_cnn_get_weights(ht_ctx *ctx, float *w, size_t n) { CHECK_READY(ctx); return cnn_get_weights(ctx, 64, w, n); }
-// The sized forms: side = 64 is the entry point above, side = 128 the same path on the larger net's weights, pools of [..][16384] inputs and an arena of its own
-#define CHECK_SIDE(ctx, side) do { if ((side) != 128) { (ctx)->err = "CNN input side must be 64 or 128"; return HT_ERR_ARG; } } while (0)
+extern "C" int ht_cnn_get_weights(ht_ctx *ctx, float *w, size_t n) { CHECK_READY(ctx); return cnn_get_weights(ctx, ht_net_of(ctx, 64), w, n); }
 extern "C" int ht_cnn_train_batch_sized_dev(ht_ctx *ctx, int side, const float *d_inputs, const float *d_targets, int n_pool, const int *order, int n_steps, int batch, float alpha, float *d_mse, void *stream)
 {
 	CHECK_READY(ctx);
-	if (side == 64) return ht_cnn_train_batch_dev(ctx, d_inputs, d_targets, n_pool, order, n_steps, batch, alpha, d_mse, stream);
-	CHECK_SIDE(ctx, side);
-	return cnn_train_dev(ctx, "ht_cnn_train_batch_sized_dev", true, 128, d_inputs, d_targets, n_pool, order, n_steps, batch, alpha, d_mse, stream);
+	ht_net *net = ht_net_of(ctx, side);
+	return cnn_train_dev(ctx, ht_form_name(ctx, net, "ht_cnn_train_batch_dev", "ht_cnn_train_batch_sized_dev"), true, net, d_inputs, d_targets, n_pool, order, n_steps, batch, alpha, d_mse, stream);
 }
 extern "C" int ht_cnn_train_batch_sized(ht_ctx *ctx, int side, const float *inputs, const float *targets, int n, int batch, float alpha, float *mse_out)
 {
 	CHECK_READY(ctx);
-	if (side == 64) return ht_cnn_train_batch(ctx, inputs, targets, n, batch, alpha, mse_out);
-	CHECK_SIDE(ctx, side);
-	return cnn_train_host(ctx, "ht_cnn_train_batch_sized", true, 128, inputs, targets, n, batch, alpha, mse_out);
+	ht_net *net = ht_net_of(ctx, side);
+	return cnn_train_host(ctx, ht_form_name(ctx, net, "ht_cnn_train_batch", "ht_cnn_train_batch_sized"), true, net, inputs, targets, n, batch, alpha, mse_out);
 }
 extern "C" int ht_debug_train_batch_buffers_sized(ht_ctx *ctx, int side, int n, float *a3, float *a6, float *a8, float *e9, float *e7, float *e6, float *e3)
 {
 	CHECK_READY(ctx);
-	if (side == 64) return ht_debug_train_batch_buffers(ctx, n, a3, a6, a8, e9, e7, e6, e3);
-	CHECK_SIDE(ctx, side);
-	float *const out[7] = { a3, a6, a8, e9, e7, e6, e3 };
-	return cnn_train_batch_buffers(ctx, "ht_debug_train_batch_buffers_sized", 128, n, out);
+	ht_net *net = ht_net_of(ctx, side);
+	return cnn_train_batch_buffers(ctx, ht_form_name(ctx, net, "ht_debug_train_batch_buffers", "ht_debug_train_batch_buffers_sized"), net, n, a3, a6, a8, e9, e7, e6, e3);
 }
-extern "C" int ht_cnn_get_weights_sized(ht_ctx *ctx, int side, float *w, size_t n)
-{
-	CHECK_READY(ctx);
-	if (side == 64) return ht_cnn_get_weights(ctx, w, n);
-	CHECK_SIDE(ctx, side);
-	return cnn_get_weights(ctx, 128, w, n);
-}
+extern "C" int ht_cnn_get_weights_sized(ht_ctx *ctx, int side, float *w, size_t n) { CHECK_READY(ctx); return cnn_get_weights(ctx, ht_net_of(ctx, side), w, n); }
 // Test aid: the layer outputs and the errors of the training arena as the latest step left them (layout: ht_launch_train_step, csrc/ht_train.hip)
 extern "C" int ht_debug_train_buffers(ht_ctx *ctx, float *act, size_t n_act, float *err, size_t n_err)
 {
@@ -525,114 +503,87 @@ extern "C" int ht_model_info(const ht_ctx *ctx, int *nb, int *nj, int *mb) { if 
 
 // ------------------------------------------------------------------------------------------------- CNN
 // The net comes in two input sizes with the same layer list: 64x64 (conv5 -> 60, pool -> 30 -> 15, conv4 -> 12, pool -> 6, FC 2304 -> 2048 -> 2304, chunked softmax) and
-// 128x128 (BASELINE configs[4] / SURVEY 8d "config 5 (ii)": conv5 -> 124, pool -> 62 -> 31, conv4 -> 28, pool -> 14, FC 12544 -> 2048 -> 2304).  The larger has a second
-// set of weights and activations beside the 64x64 net's, allocated when its weights are first loaded.  One description of either for the loader and the forward pass:
-struct cnn_net { int side; size_t count, fc_in, in_floats; ht_cnn_weights *w; float **d_w; bool *have; float *d_in, *d_act1, *d_act2; const char *prof, *bad_count, *missing; };
-static cnn_net cnn_net_of(ht_ctx *ctx, int side)
+// 128x128 (BASELINE configs[4] / SURVEY 8d "config 5 (ii)": conv5 -> 124, pool -> 62 -> 31, conv4 -> 28, pool -> 14, FC 12544 -> 2048 -> 2304).  Each is one ht_net of the
+// context (ht_host.hpp); the loader and the forward pass take the net and refuse a null one (ht_net_of has said why).
+static int net_alloc_frames(ht_ctx *ctx, ht_net &net)      // the net's input and convolution buffers, for the context's capacity
 {
-	if (side == 64) return { 64, HT_CNNB_COUNT, 2304, HT_CNN_IN, &ctx->cnnw, &ctx->d_weights, &ctx->have_weights, ctx->d_cnn_in, ctx->d_act1, ctx->d_act2, "cnn",
-	                         "weights: expected HT_CNNB_COUNT fp32 values in .cnnb order", "CNN weights not loaded (ht_cnn_load_weights)" };
-	return { 128, HT_CNNB128_COUNT, 12544, HT_CNN128_IN, &ctx->cnnw128, &ctx->d_weights128, &ctx->have_weights128, ctx->d_in128, ctx->d_act1_128, ctx->d_act2_128, "cnn128",
-	         "weights: expected HT_CNNB128_COUNT fp32 values in .cnnb order", "weights of the 128x128 net not loaded (ht_cnn_load_weights_sized)" };
+	const size_t B = (size_t)ctx->B;
+	int r;
+	if ((r = dev_alloc(ctx, &net.d_in, B * net.dims.in)) || (r = dev_alloc(ctx, &net.d_act1, B * net.dims.act1)) || (r = dev_alloc(ctx, &net.d_act2, B * net.dims.act2))) return r;
+	return HT_OK;
 }
-static int cnn_load_weights(ht_ctx *ctx, int side, const float *w, size_t n)
+static int cnn_load_weights(ht_ctx *ctx, ht_net *net, const float *w, size_t n)
 {
-	const cnn_net net = cnn_net_of(ctx, side);
-	if (!w || n != net.count) { ctx->err = net.bad_count; return HT_ERR_ARG; }
-	if (!*net.d_w)
+	if (!net) return HT_ERR_ARG;
+	if (!w || n != net->dims.count) { ctx->err = net->bad_count; return HT_ERR_ARG; }
+	const size_t count = net->dims.count;
+	if (!net->d_weights)
 	{
-		const size_t B = (size_t)ctx->B;
 		int r;
-		if (side == 128 && ((r = dev_alloc(ctx, &ctx->d_in128, B * HT_CNN128_IN)) || (r = dev_alloc(ctx, &ctx->d_act1_128, B * 16 * 31 * 31)) || (r = dev_alloc(ctx, &ctx->d_act2_128, B * 12544)))) return r;
-		if ((r = dev_alloc(ctx, net.d_w, net.count + 16384 + HT_W4_COUNT))) return r;
+		if (!net->d_in && (r = net_alloc_frames(ctx, *net))) return r;      // (the larger net's: the 64x64-input net's came with the context)
+		if ((r = dev_alloc(ctx, &net->d_weights, count + 16384 + HT_W4_COUNT))) return r;
 	}
-	float *d = *net.d_w;
+	float *d = net->d_weights;
 	HIPCHK(ctx, hipMemcpy(d, w, n * sizeof(float), hipMemcpyHostToDevice));
 	// conv2 weights repacked for the matrix kernel (cnn_w2p_index)
-	const float *W2 = cnnb_layout_of(w, net.fc_in).W2;
+	const float *W2 = cnnb_layout_of(w, net->dims.act2).W2;
 	std::vector<float> w2p(16384);
 	for (int oc = 0; oc < 64; oc++) for (int ic = 0; ic < 16; ic++) for (int ky = 0; ky < 4; ky++) for (int kx = 0; kx < 4; kx++)
 		w2p[cnn_w2p_index(oc, ic, ky, kx)] = W2[kx + 4 * (ky + 4 * (ic + 16 * oc))];
-	HIPCHK(ctx, hipMemcpy(d + net.count, w2p.data(), 16384 * sizeof(float), hipMemcpyHostToDevice));
-	ht_cnn_weights &cw = *net.w;
-	const cnnb_layout<float> L = cnnb_layout_of(d, net.fc_in);
-	cw.W1 = L.W1; cw.B1 = L.B1; cw.W2p = d + net.count; cw.B2 = L.B2; cw.W3 = L.W3; cw.B3 = L.B3; cw.W4 = L.W4; cw.B4 = L.B4;
-	cw.W4p = d + net.count + 16384;
-	ht_launch_pack_w4(cw.W4, d + net.count + 16384, ctx->stream);
+	HIPCHK(ctx, hipMemcpy(d + count, w2p.data(), 16384 * sizeof(float), hipMemcpyHostToDevice));
+	ht_cnn_weights &cw = net->w;
+	const cnnb_layout<float> L = cnnb_layout_of(d, net->dims.act2);
+	cw.W1 = L.W1; cw.B1 = L.B1; cw.W2p = d + count; cw.B2 = L.B2; cw.W3 = L.W3; cw.B3 = L.B3; cw.W4 = L.W4; cw.B4 = L.B4;
+	cw.W4p = d + count + 16384;
+	ht_launch_pack_w4(cw.W4, d + count + 16384, ctx->stream);
 	HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-	*net.have = true;
+	net->have = true;
 	return HT_OK;
 }
-extern "C" int ht_cnn_load_weights(ht_ctx *ctx, const float *w, size_t n) { CHECK_READY(ctx); return cnn_load_weights(ctx, 64, w, n); }
-extern "C" int ht_cnn_load_weights_sized(ht_ctx *ctx, int side, const float *w, size_t n)
+static int cnn_forward(ht_ctx *ctx, const ht_net &net, const float *d_in, float *d_out, int B, hipStream_t s)
 {
-	CHECK_READY(ctx);
-	if (side != 64 && side != 128) { ctx->err = "CNN input side must be 64 or 128"; return HT_ERR_ARG; }
-	return cnn_load_weights(ctx, side, w, n);
-}
-static int cnn_forward(ht_ctx *ctx, const cnn_net &net, const float *d_in, float *d_out, int B, hipStream_t s)
-{
-	if (!*net.have) { ctx->err = net.missing; return HT_ERR_STATE; }
+	if (!net.have) { ctx->err = net.missing; return HT_ERR_STATE; }      // (the larger net's buffers come with its weights)
 	ht_prof_scope p0(ctx, net.prof, s, true);
-	ht_launch_cnn(*net.w, d_in, net.d_act1, net.d_act2, ctx->d_act3, ctx->d_logits, B, s, net.side);
+	ht_launch_cnn(net, d_in, ctx->d_act3, ctx->d_logits, B, s);
 	ht_launch_softmax_decode(ctx->d_logits, d_out, nullptr, nullptr, 1, B, s);
 	return HT_OK;
 }
-static int cnn_eval_dev(ht_ctx *ctx, int side, const float *d_in, float *d_out, int B, void *stream)
+static int cnn_eval_dev(ht_ctx *ctx, const ht_net *net, const float *d_in, float *d_out, int B, void *stream)
 {
-	int r = cnn_forward(ctx, cnn_net_of(ctx, side), d_in, d_out, B, ht_user_stream(ctx, stream));
+	if (!net || !d_in || !d_out) return HT_ERR_ARG;
+	int r = cnn_forward(ctx, *net, d_in, d_out, B, ht_user_stream(ctx, stream));
 	if (r) return r;
 	HIPCHK(ctx, hipGetLastError());
 	return HT_OK;
 }
-static int cnn_eval(ht_ctx *ctx, int side, const float *in, float *out, int B)
+static int cnn_eval(ht_ctx *ctx, const ht_net *net, const float *in, float *out, int B)
 {
-	const cnn_net net = cnn_net_of(ctx, side);
-	if (!*net.have) { ctx->err = net.missing; return HT_ERR_STATE; }      // (the larger net's input buffer comes with its weights)
-	HIPCHK(ctx, hipMemcpyAsync(net.d_in, in, (size_t)B * net.in_floats * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
-	int r = cnn_forward(ctx, net, net.d_in, ctx->d_cnn_out, B, ctx->stream);
+	if (!net || !in || !out) return HT_ERR_ARG;
+	if (!net->have) { ctx->err = net->missing; return HT_ERR_STATE; }
+	HIPCHK(ctx, hipMemcpyAsync(net->d_in, in, (size_t)B * net->dims.in * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+	int r = cnn_forward(ctx, *net, net->d_in, ctx->d_cnn_out, B, ctx->stream);
 	if (r) return r;
 	HIPCHK(ctx, hipMemcpyAsync(out, ctx->d_cnn_out, (size_t)B * HT_CNN_OUT * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
 	return ht_sync_check(ctx, ctx->stream);
 }
-extern "C" int ht_cnn_eval_dev(ht_ctx *ctx, const float *d_in, float *d_out, int B, void *stream)
-{
-	CHECK_READY(ctx); CHECK_BATCH(ctx, B);
-	if (!d_in || !d_out) return HT_ERR_ARG;
-	return cnn_eval_dev(ctx, 64, d_in, d_out, B, stream);
-}
-extern "C" int ht_cnn_eval(ht_ctx *ctx, const float *in, float *out, int B)
-{
-	CHECK_READY(ctx); CHECK_BATCH(ctx, B);
-	if (!in || !out) return HT_ERR_ARG;
-	return cnn_eval(ctx, 64, in, out, B);
-}
-extern "C" int ht_cnn_eval_sized_dev(ht_ctx *ctx, int side, const float *d_in, float *d_out, int B, void *stream)
-{
-	CHECK_READY(ctx); CHECK_BATCH(ctx, B);
-	if (side == 64) return ht_cnn_eval_dev(ctx, d_in, d_out, B, stream);
-	if (side != 128 || !d_in || !d_out) { ctx->err = "CNN input side must be 64 or 128"; return HT_ERR_ARG; }
-	return cnn_eval_dev(ctx, 128, d_in, d_out, B, stream);
-}
-extern "C" int ht_cnn_eval_sized(ht_ctx *ctx, int side, const float *in, float *out, int B)
-{
-	CHECK_READY(ctx); CHECK_BATCH(ctx, B);
-	if (side == 64) return ht_cnn_eval(ctx, in, out, B);
-	if (side != 128 || !in || !out) { ctx->err = "CNN input side must be 64 or 128"; return HT_ERR_ARG; }
-	return cnn_eval(ctx, 128, in, out, B);
-}
+extern "C" int ht_cnn_load_weights(ht_ctx *ctx, const float *w, size_t n) { CHECK_READY(ctx); return cnn_load_weights(ctx, ht_net_of(ctx, 64), w, n); }
+extern "C" int ht_cnn_load_weights_sized(ht_ctx *ctx, int side, const float *w, size_t n) { CHECK_READY(ctx); return cnn_load_weights(ctx, ht_net_of(ctx, side), w, n); }
+extern "C" int ht_cnn_eval_dev(ht_ctx *ctx, const float *d_in, float *d_out, int B, void *stream) { CHECK_READY(ctx); CHECK_BATCH(ctx, B); return cnn_eval_dev(ctx, ht_net_of(ctx, 64), d_in, d_out, B, stream); }
+extern "C" int ht_cnn_eval(ht_ctx *ctx, const float *in, float *out, int B) { CHECK_READY(ctx); CHECK_BATCH(ctx, B); return cnn_eval(ctx, ht_net_of(ctx, 64), in, out, B); }
+extern "C" int ht_cnn_eval_sized_dev(ht_ctx *ctx, int side, const float *d_in, float *d_out, int B, void *stream) { CHECK_READY(ctx); CHECK_BATCH(ctx, B); return cnn_eval_dev(ctx, ht_net_of(ctx, side), d_in, d_out, B, stream); }
+extern "C" int ht_cnn_eval_sized(ht_ctx *ctx, int side, const float *in, float *out, int B) { CHECK_READY(ctx); CHECK_BATCH(ctx, B); return cnn_eval(ctx, ht_net_of(ctx, side), in, out, B); }
 
 // ------------------------------------------------------------------------------------------------- stage: prepare / decode
 extern "C" int ht_stage_prepare(ht_ctx *ctx, const uint16_t *depth, const float *cams, int B, float *cnn_in, float *points, int *npoints)
 {
 	CHECK_READY(ctx); CHECK_MODEL(ctx); CHECK_BATCH(ctx, B);
 	if (!depth || !cams) return HT_ERR_ARG;
-	hipStream_t s = ctx->stream;
+	hipStream_t s = ctx->stream; const ht_net &tile = *ht_net_of(ctx, 64);
 	HIPCHK(ctx, hipMemcpyAsync(ctx->d_depth, depth, (size_t)B * 4096 * sizeof(uint16_t), hipMemcpyHostToDevice, s));
 	HIPCHK(ctx, hipMemcpyAsync(ctx->d_cams, cams, (size_t)B * HT_CAM * sizeof(float), hipMemcpyHostToDevice, s));
-	ht_launch_prepare(ctx->d_depth, ctx->d_cams, ctx->par.drangey, ctx->par.subsample_fraction, ctx->d_cnn_in, ctx->d_pts, ctx->d_npts, ctx->model.pts_cap, B, s);
+	ht_launch_prepare(ctx->d_depth, ctx->d_cams, ctx->par.drangey, ctx->par.subsample_fraction, tile.d_in, ctx->d_pts, ctx->d_npts, ctx->model.pts_cap, B, s);
 	ctx->model.pts_bound = 0;      // stage calls: no assumption about the cloud size
-	if (cnn_in) HIPCHK(ctx, hipMemcpyAsync(cnn_in, ctx->d_cnn_in, (size_t)B * HT_CNN_IN * sizeof(float), hipMemcpyDeviceToHost, s));
+	if (cnn_in) HIPCHK(ctx, hipMemcpyAsync(cnn_in, tile.d_in, (size_t)B * tile.dims.in * sizeof(float), hipMemcpyDeviceToHost, s));
 	if (points) HIPCHK(ctx, hipMemcpy2DAsync(points, HT_MAXPTS * sizeof(float4), ctx->d_pts, (size_t)ctx->model.pts_cap * sizeof(float4), HT_MAXPTS * sizeof(float4), B, hipMemcpyDeviceToHost, s));
 	if (npoints) HIPCHK(ctx, hipMemcpyAsync(npoints, ctx->d_npts, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, s));
 	return ht_sync_check(ctx, s);
@@ -755,7 +706,9 @@ int ht_alloc_buffers(ht_ctx *ctx)
 	const size_t B = (size_t)ctx->B, nb = (size_t)ctx->model.nb;
 	int r;
 #define A(ptr, n) if ((r = dev_alloc(ctx, &ctx->ptr, (n)))) return r
-	A(d_depth, B * 4096); A(d_cams, B * HT_CAM); A(d_cnn_in, B * HT_CNN_IN); A(d_act1, B * 3600); A(d_act2, B * 2304); A(d_act3, B * 2048);
+	A(d_depth, B * 4096); A(d_cams, B * HT_CAM);
+	if ((r = net_alloc_frames(ctx, *ht_net_of(ctx, 64)))) return r;      // the larger net's come with its first weights (cnn_load_weights)
+	A(d_act3, B * 2048);
 	A(d_logits, B * HT_CNN_OUT); A(d_cnn_out, B * HT_CNN_OUT); A(d_analysis, B * HT_ANALYSIS);
 	if (ctx->cnn_only) return HT_OK;
 	A(d_npts, B);

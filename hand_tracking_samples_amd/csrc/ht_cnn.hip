@@ -832,19 +832,19 @@ void ht_launch_prepare_frame(const uint16_t *depth, const float *cams, int w, in
 {
 	hipLaunchKernelGGL(k_prepare_frame, dim3(B), dim3(256), 0, s, depth, cams, w, h, drangey, fraction, pts, npts, overflow, cap);
 }
-// side = 64: PoseInitializerCNN's topology (handtrack.h:108-118); side = 128: the same layers on a 128x128 input (act1 [B][16*31*31], act2 [B][12544])
-void ht_launch_cnn(const ht_cnn_weights &w, const float *cnn_in, float *act1, float *act2, float *act3, float *logits, int B, hipStream_t s, int side, bool beside_other_work)
+// side = 64: PoseInitializerCNN's topology (handtrack.h:108-118); side = 128: the same layers on a 128x128 input.  Every size comes from the net's dims; the nets differ
+// in the convolution kernels' template arguments, and in the choice between two arrangements of them, which exists at side 64 only.
+void ht_launch_cnn(const ht_net &net, const float *cnn_in, float *act3, float *logits, int B, hipStream_t s, bool beside_other_work)
 {
+	const ht_cnn_weights &w = net.w; float *act1 = net.d_act1, *act2 = net.d_act2;
 	const dim3 g1(2048 / 64, (B + 127) / 128), t1(512);
 #ifdef HT_TUNING
 	{ static int done = 0; if (!done) { const int f = ht_tuning_flags(); (void)hipMemcpyToSymbol(HIP_SYMBOL(ht_fc_dbg), &f, sizeof(int)); done = 1; } }
 #endif
-	if (side == 128)
+	if (net.dims.side == 128)
 	{
 		hipLaunchKernelGGL((k_conv1<128, 31, 8>), dim3(B, 4), dim3(256), 0, s, cnn_in, w.W1, w.B1, act1);
 		hipLaunchKernelGGL((k_conv2<31, 28, 4>), dim3(B, 7), dim3(256), 0, s, act1, w.W2p, w.B2, act2);
-		if (B % 128 == 0) hipLaunchKernelGGL((k_fc<true, 2, 4, true, true>), g1, t1, 0, s, act2, w.W3, w.B3, act3, B, 2048, 12544);
-		else hipLaunchKernelGGL((k_fc<true, 2, 4, false, true>), g1, t1, 0, s, act2, w.W3, w.B3, act3, B, 2048, 12544);
 	}
 	else
 	{
@@ -862,9 +862,9 @@ void ht_launch_cnn(const ht_cnn_weights &w, const float *cnn_in, float *act1, fl
 			hipLaunchKernelGGL((k_conv2<15, 12, 12>), dim3(B, 1), dim3(256), 0, s, act1, w.W2p, w.B2, act2);
 		}
 		else hipLaunchKernelGGL(k_conv12, dim3(B), dim3(256), 0, s, cnn_in, w.W1, w.B1, w.W2p, w.B2, act1, act2);
-		if (B % 128 == 0) hipLaunchKernelGGL((k_fc<true, 2, 4, true, true>), g1, t1, 0, s, act2, w.W3, w.B3, act3, B, 2048, 2304);
-		else hipLaunchKernelGGL((k_fc<true, 2, 4, false, true>), g1, t1, 0, s, act2, w.W3, w.B3, act3, B, 2048, 2304);
 	}
+	if (B % 128 == 0) hipLaunchKernelGGL((k_fc<true, 2, 4, true, true>), g1, t1, 0, s, act2, w.W3, w.B3, act3, B, 2048, (int)net.dims.act2);
+	else hipLaunchKernelGGL((k_fc<true, 2, 4, false, true>), g1, t1, 0, s, act2, w.W3, w.B3, act3, B, 2048, (int)net.dims.act2);
 	// the last layer: act3 comes from k_fc in the packed column order and meets the packed copy of W4 (k_fc144_pk)
 	hipLaunchKernelGGL(k_fc144_pk, dim3(2304 / F2_BN, (B + F2_BM - 1) / F2_BM), dim3(768), 0, s, act3, w.W4p, w.B4, logits, B, 2304, 2048);
 }

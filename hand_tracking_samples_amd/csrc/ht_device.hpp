@@ -3,9 +3,9 @@
 // HBM layout (per context, capacity = max_batch tracker slots; everything resident for the life of the context):
 //   constants  : model (vertices, planes, per-body and per-joint constants), CNN weights (37.8 MB in .cnnb order + conv2 repacked k-major + the last layer repacked for k_fc144_pk, 18.9 MB)
 //   per slot   : handmodel / othermodel state [nb][16] floats (pos3 quat4 linmom3 angmom3 pad3), prev_frame_error, initializing
-//   per frame  : depth u16[4096] (only for host-buffer calls), cam[12], cnn_in[4096], act1[3600], act2[2304], act3[2048],
-//                logits/cnn_out[2304], analysis[84], points float4[HT_MAXPTS] + count, cloud rows [HT_MAXPTS][16], chamber rows [5*nb][16],
-//                contacts, solver scratch (pre-computed row stream)
+//   per frame  : depth u16[4096] (only for host-buffer calls), cam[12], per net (ht_net: the 64x64-input net's with the context, the 128x128-input net's with its
+//                first weights) in[side side], act1[16 P2 P2], act2[64 P3 P3] (cnn_dims), for both nets act3[2048], logits/cnn_out[2304], analysis[84],
+//                points float4[HT_MAXPTS] + count, cloud rows [HT_MAXPTS][16], chamber rows [5*nb][16], contacts, solver scratch (pre-computed row stream)
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -158,6 +158,40 @@ struct ht_physics_dev      // physics.h:34-47 after handtrack.h:837-838
 
 struct ht_cnn_weights { const float *W1, *B1, *W2p, *B2, *W3, *B3, *W4, *B4, *W4p; };      // W2p, W4p: copies of the conv2 / last-layer weights in the order the matrix kernels read them (ht_cnn.hip)
 #define HT_W4_COUNT ((size_t)2048 * 2304)
+// The layer dimensions of either net from its input side S (64: 60 -> 15, 12 -> 6, FC 2304; 128: 124 -> 31, 28 -> 14, FC 12544): C1 = conv1's output side,
+// P2 = after the two pools, C2 = conv2's output side, P3 = after the third pool; A3 / A6 = floats of a sample's a3 [16][P2][P2] / a6 [64][P3][P3]
+template <int S> struct cnn_dims
+{
+	static constexpr int SIDE = S, C1 = S - 4, P2 = C1 / 4, NP2 = P2 * P2, A3 = 16 * NP2, C2 = P2 - 3, NC2 = C2 * C2, P3 = C2 / 2, NP3 = P3 * P3, A6 = 64 * NP3;
+};
+// The .cnnb order of the weights (CNN::saveb cnn.h:591-593) from the base pointer; fc_in = inputs of the first fully connected layer (a sample's a6)
+template <class T> struct cnnb_layout { T *W1, *B1, *W2, *B2, *W3, *B3, *W4, *B4; };
+template <class T> static inline cnnb_layout<T> cnnb_layout_of(T *w, size_t fc_in = cnn_dims<64>::A6)
+{
+	cnnb_layout<T> L;
+	L.W1 = w; L.B1 = L.W1 + 400; L.W2 = L.B1 + 16; L.B2 = L.W2 + 16384; L.W3 = L.B2 + 64; L.B3 = L.W3 + fc_in * 2048; L.W4 = L.B3 + 2048; L.B4 = L.W4 + (size_t)2048 * 2304;
+	return L;
+}
+// The same at run time, for the host layer: floats a frame of the net's input, of its two convolution buffers (act2 is the first FC layer's fc_in) and the .cnnb
+// value count; sub: the heat-map camera is camsub(cam, sub)
+struct ht_net_dims { int side; size_t in, act1, act2, count; int sub; };
+template <int S> constexpr ht_net_dims ht_net_dims_of()
+{
+	return { S, (size_t)S * S, (size_t)cnn_dims<S>::A3, (size_t)cnn_dims<S>::A6, 400 + 16 + 16384 + 64 + (size_t)cnn_dims<S>::A6 * 2048 + 2048 + (size_t)2048 * 2304 + 2304, S / 16 };
+}
+static_assert(ht_net_dims_of<64>().in == HT_CNN_IN && ht_net_dims_of<64>().count == HT_CNNB_COUNT, "public header and cnn_dims disagree on the 64x64-input net");
+static_assert(ht_net_dims_of<128>().in == HT_CNN128_IN && ht_net_dims_of<128>().count == HT_CNNB128_COUNT, "public header and cnn_dims disagree on the 128x128-input net");
+// One pose net of a context (ht_ctx::net, ht_net_of): its weights on the device (.cnnb order, then W2p, then W4p) and the views the kernels take, its input and
+// convolution buffers [max_batch][dims.in / act1 / act2], the arena of its mini-batch training step (ht_train_batch.hip) for `cap` samples, grown to the largest batch
+// seen (dev_grow), with the latest step's sample count, its label in the profile and the texts of its refusals: no weights (forward pass; training, behind the
+// entry point's name), a wrong value count.
+struct ht_net
+{
+	ht_net_dims dims; const char *prof, *missing, *train_missing, *bad_count;
+	bool have = false; float *d_weights = nullptr; ht_cnn_weights w = {};
+	float *d_in = nullptr, *d_act1 = nullptr, *d_act2 = nullptr;
+	struct { float *buf = nullptr; int cap = 0, last = 0; } train;
+};
 void ht_launch_pack_w4(const float *W4, float *W4p, hipStream_t s);      // refreshes the packed copy (after a weight upload, after a training step)
 
 // ---- kernel launchers (defined in the .hip files) ----
@@ -167,6 +201,6 @@ struct ht_prepare_extra { float *cams_out; float *state0, *state1; const float *
 void ht_launch_prepare(const uint16_t *depth, const float *cams, float drangey, int fraction, float *cnn_in, float4 *pts, int *npts, int cap, int B, hipStream_t s, const ht_prepare_extra *extra = nullptr);
 void ht_launch_voxel(const float4 *all, const int *nall, int cap, float size, int min_count, float4 *out, int *nout, int B, hipStream_t s);
 void ht_launch_prepare_frame(const uint16_t *depth, const float *cams, int w, int h, float drangey, int fraction, float4 *pts, int *npts, int *overflow, int cap, int B, hipStream_t s);
-void ht_launch_cnn(const ht_cnn_weights &w, const float *cnn_in, float *act1, float *act2, float *act3, float *logits, int B, hipStream_t s, int side = 64, bool beside_other_work = false);      // beside_other_work: another stream's kernel runs beside the net (an update's side branch): picks the launch arrangement, not the results
+void ht_launch_cnn(const ht_net &net, const float *cnn_in, float *act3, float *logits, int B, hipStream_t s, bool beside_other_work = false);      // the net's act1 / act2 on the way; beside_other_work: another stream's kernel runs beside the net (an update's side branch): picks the launch arrangement, not the results
 void ht_launch_softmax_decode(const float *logits, float *cnn_out, const float *cams, float *analysis, int softmax, int B, hipStream_t s, int sub = 4);      // sub: the heat-map camera is camsub(cam, sub)
 void ht_launch_cnn_input(const uint16_t *depth, const float *cams, int npx, float drangey, float *cnn_in, int B, hipStream_t s);

@@ -35,7 +35,7 @@ struct ht_history
 
 struct ht_ctx
 {
-	bool ready = false, have_weights = false, profile = false;
+	bool ready = false, profile = false;
 	bool cnn_only = false;          // created without a hand model: only the CNN entry points work
 	bool profile_phases = false;     // also time the minor phases (serialises the side streams; used for the phase table, not for the timed region)
 	int B = 0, device = 0;
@@ -52,14 +52,16 @@ struct ht_ctx
 	ht_params par;
 	ht_physics_dev phys;
 	ht_model_dev model;
-	ht_cnn_weights cnnw;
-	ht_cnn_weights cnnw128; bool have_weights128 = false;         // the 128x128-input variant of the net (BASELINE configs[4]); buffers allocated on first use
-	float *d_weights128 = nullptr, *d_in128 = nullptr, *d_act1_128 = nullptr, *d_act2_128 = nullptr;
+	// The two pose nets (ht_net_of): the reference's, on 64x64 tiles, whose input and convolution buffers come with the context (ht_alloc_buffers), and the same layers on
+	// a larger input (BASELINE configs[4]), whose buffers come with its first weights (ht_cnn_load_weights_sized).  Either net's mini-batch arena comes with its first step.
+	ht_net net[2] = { { ht_net_dims_of<64>(), "cnn", "CNN weights not loaded (ht_cnn_load_weights)",
+	                    ": the context holds no weights of the 64x64-input net (ht_cnn_load_weights); the 128x128-input net is trained by ht_cnn_train_batch_sized",
+	                    "weights: expected HT_CNNB_COUNT fp32 values in .cnnb order" },
+	                  { ht_net_dims_of<128>(), "cnn128", "weights of the 128x128 net not loaded (ht_cnn_load_weights_sized)",
+	                    ": the context holds no weights of the 128x128-input net (ht_cnn_load_weights_sized)", "weights: expected HT_CNNB128_COUNT fp32 values in .cnnb order" } };
 	std::vector<float> h_bodyc, h_jointc;
 	std::vector<float4> h_verts, h_planes;                        // host copies of the model geometry (ht_scale rewrites them)
-	float *d_train_batch128 = nullptr; int train_batch_cap128 = 0, train_batch_last128 = 0;      // the same for the 128x128-input net (ht_cnn_train_batch_sized*), not allocated before its first step
-	float *d_train_batch = nullptr; int train_batch_cap = 0, train_batch_last = 0;      // mini-batch training arena (ht_train_batch.hip) for train_batch_cap samples, grown to the largest batch seen (dev_grow); samples of the latest step
-	float *d_train = nullptr;                                    // training arena: layer outputs, errors, split-K partial sums (allocated on first use)
+	float *d_train = nullptr;                                    // the per-sample step's training arena (the 64x64-input net only): layer outputs, errors, split-K partial sums (allocated on first use)
 	char *d_train_io = nullptr; size_t train_io_cap = 0;         // ht_cnn_train's and ht_cnn_train_batch's staging (inputs, targets, per-sample MSE), grown to the largest call (dev_grow)
 	float *d_sf_ref = nullptr, *d_sf_crays = nullptr;             // slowfit inputs [B][nb][7], [B][8][4] (allocated on first use)
 	float4 *d_cverts_rw = nullptr;                                // padded copy of the collision vertices (ht_model_dev::cverts)
@@ -68,10 +70,10 @@ struct ht_ctx
 	std::map<std::string, ht_prof_entry> prof;
 
 	// device buffers (capacity B frames / tracker slots)
-	float *d_weights = nullptr;
 	uint16_t *d_depth = nullptr;
 	uint16_t *d_seg_tiles = nullptr, *d_frames = nullptr; float *d_frame_cams = nullptr, *d_frame_cams_in = nullptr; int *d_overflow = nullptr; size_t frames_cap = 0;      // full-size frame path (ht_update_frames); d_frames holds the largest frame size seen (dev_grow)
-	float *d_cams = nullptr, *d_cnn_in = nullptr, *d_act1 = nullptr, *d_act2 = nullptr, *d_act3 = nullptr, *d_logits = nullptr, *d_cnn_out = nullptr, *d_analysis = nullptr;
+	float *d_cams = nullptr, *d_analysis = nullptr;
+	float *d_act3 = nullptr, *d_logits = nullptr, *d_cnn_out = nullptr;      // shared by both nets: the latest evaluation's first FC layer, logits and output, whichever net ran
 	float4 *d_pts = nullptr; int *d_npts = nullptr;
 	float4 *d_ptsv = nullptr; int *d_nptsv = nullptr;          // the main-thread cloud when subsample_voxel is set (allocated on first use; d_pts stays the CNN job's cloud)
 	float *d_state[2] = { nullptr, nullptr };      // [B][nb][HT_STATE_STRIDE]: 0 handmodel, 1 othermodel
@@ -113,6 +115,15 @@ struct ht_ctx
 	std::vector<float> h_mesh_corners, mesh_rad; std::vector<int> mesh_off; float4 *d_mesh = nullptr;
 };
 
+// The net of a side x side input; any other side is refused here, and only here
+static inline ht_net *ht_net_of(ht_ctx *ctx, int side)
+{
+	for (ht_net &n : ctx->net) if (n.dims.side == side) return &n;
+	ctx->err = "CNN input side must be 64 or 128";
+	return nullptr;
+}
+// the entry point's name in the messages of a *_sized call: at side 64 it is the unsized call and says so
+static inline const char *ht_form_name(const ht_ctx *ctx, const ht_net *net, const char *unsized, const char *sized) { return net == &ctx->net[0] ? unsized : sized; }
 // what every entry point of the C-ABI starts with and wraps its HIP calls in
 #define HIPCHK(ctx, call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { (ctx)->err = std::string(#call) + ": " + hipGetErrorString(e_); return HT_ERR_HIP; } } while (0)
 #define CHECK_READY(ctx) if (!(ctx)) return HT_ERR_ARG; if (!(ctx)->ready) { (ctx)->err = "context not initialised (ht_create failed)"; return HT_ERR_STATE; } ht_device_guard dev_guard_((ctx)->device)

@@ -138,7 +138,7 @@ extern "C" int ht_expected_cnn_dev(ht_ctx *ctx, const float *d_poses, const floa
 	if (B == 0) return HT_OK;
 	hipStream_t s = ht_user_stream(ctx, stream);
 	const int blocks = (int)(((long long)B + LB_FRAMES - 1) / LB_FRAMES);
-	hipLaunchKernelGGL(k_expected_cnn, dim3(blocks), dim3(LB_THREADS), 0, s, d_poses, d_cams, ctx->model.nb, B, (flags & HT_LABELS_SEGMENT_FRAME) ? 1 : 0, (flags & HT_LABELS_SIDE128) ? 8.0f : 4.0f, d_expected, d_image_points, d_vals);
+	hipLaunchKernelGGL(k_expected_cnn, dim3(blocks), dim3(LB_THREADS), 0, s, d_poses, d_cams, ctx->model.nb, B, (flags & HT_LABELS_SEGMENT_FRAME) ? 1 : 0, (float)ht_net_of(ctx, (flags & HT_LABELS_SIDE128) ? 128 : 64)->dims.sub, d_expected, d_image_points, d_vals);
 	HIPCHK(ctx, hipGetLastError());
 	return HT_OK;
 }
@@ -157,31 +157,35 @@ extern "C" int ht_expected_cnn_batch(ht_ctx *ctx, const float *poses, const floa
 	                      { return ht_expected_cnn_dev(ctx, (const float *)seg[0].dev, (const float *)seg[1].dev, B, flags, (float *)seg[2].dev, (float *)seg[3].dev, (float *)seg[4].dev, s); });
 }
 
-// cnn_input (handtrack.h:700) of B 64x64 tiles: k_prepare without a point cloud, as the full-frame update path runs it (ht_solver_api.hip)
-extern "C" int ht_cnn_input_dev(ht_ctx *ctx, const uint16_t *d_tiles, const float *d_cams, int B, float *d_cnn_in, void *stream)
+// cnn_input (handtrack.h:700) of B tiles of a net's input size.  A 64x64 tile: k_prepare without a point cloud, as the full-frame update path runs it
+// (ht_solver_api.hip); a larger one: the whole-frame transform that ht_update_direct_* feeds the 128x128-input net with (k_cnn_input)
+static int cnn_input_dev(ht_ctx *ctx, const char *fn, const ht_net *net, const uint16_t *d_tiles, const float *d_cams, int B, float *d_cnn_in, void *stream)
 {
-	CHECK_READY(ctx);
-	if (!d_tiles || !d_cams || !d_cnn_in || B < 0) { ctx->err = "ht_cnn_input_dev: bad argument"; return HT_ERR_ARG; }
-	if (((uintptr_t)d_tiles & 15) != 0 || ((uintptr_t)d_cnn_in & 15) != 0) { ctx->err = "ht_cnn_input_dev: d_tiles and d_cnn_in must be 16-byte aligned (the input transform reads eight pixels per 128-bit load and writes float4)"; return HT_ERR_ARG; }
+	const std::string f(fn);
+	if (!net) return HT_ERR_ARG;
+	if (!d_tiles || !d_cams || !d_cnn_in || B < 0) { ctx->err = f + ": bad argument"; return HT_ERR_ARG; }
+	if (((uintptr_t)d_tiles & 15) != 0 || ((uintptr_t)d_cnn_in & 15) != 0) { ctx->err = f + ": d_tiles and d_cnn_in must be 16-byte aligned (the input transform reads eight pixels per 128-bit load and writes float4)"; return HT_ERR_ARG; }
 	if (B == 0) return HT_OK;
 	hipStream_t s = ht_user_stream(ctx, stream);
-	const ht_prepare_extra pz = { nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr };
-	ht_launch_prepare(d_tiles, d_cams, ctx->par.drangey, ctx->par.subsample_fraction, d_cnn_in, nullptr, nullptr, 0, B, s, &pz);
+	const size_t npx = net->dims.in;
+	if (net->dims.side == 64)
+	{
+		const ht_prepare_extra pz = { nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr };
+		ht_launch_prepare(d_tiles, d_cams, ctx->par.drangey, ctx->par.subsample_fraction, d_cnn_in, nullptr, nullptr, 0, B, s, &pz);
+	}
+	else for (int b0 = 0; b0 < B; b0 += 32768)      // (a launch takes one tile per block row, at most 65535)
+		ht_launch_cnn_input(d_tiles + (size_t)b0 * npx, d_cams + (size_t)b0 * HT_CAM, (int)npx, ctx->par.drangey, d_cnn_in + (size_t)b0 * npx, B - b0 < 32768 ? B - b0 : 32768, s);
 	HIPCHK(ctx, hipGetLastError());
 	return HT_OK;
 }
-// the same for side x side tiles; side = 128: the whole-frame transform that ht_update_direct_* feeds the 128x128-input net with (k_cnn_input)
+extern "C" int ht_cnn_input_dev(ht_ctx *ctx, const uint16_t *d_tiles, const float *d_cams, int B, float *d_cnn_in, void *stream)
+{
+	CHECK_READY(ctx);
+	return cnn_input_dev(ctx, "ht_cnn_input_dev", ht_net_of(ctx, 64), d_tiles, d_cams, B, d_cnn_in, stream);
+}
 extern "C" int ht_cnn_input_sized_dev(ht_ctx *ctx, int side, const uint16_t *d_tiles, const float *d_cams, int B, float *d_cnn_in, void *stream)
 {
 	CHECK_READY(ctx);
-	if (side == 64) return ht_cnn_input_dev(ctx, d_tiles, d_cams, B, d_cnn_in, stream);
-	if (side != 128) { ctx->err = "CNN input side must be 64 or 128"; return HT_ERR_ARG; }
-	if (!d_tiles || !d_cams || !d_cnn_in || B < 0) { ctx->err = "ht_cnn_input_sized_dev: bad argument"; return HT_ERR_ARG; }
-	if (((uintptr_t)d_tiles & 15) != 0 || ((uintptr_t)d_cnn_in & 15) != 0) { ctx->err = "ht_cnn_input_sized_dev: d_tiles and d_cnn_in must be 16-byte aligned (the input transform reads eight pixels per 128-bit load and writes float4)"; return HT_ERR_ARG; }
-	if (B == 0) return HT_OK;
-	hipStream_t s = ht_user_stream(ctx, stream);
-	for (int b0 = 0; b0 < B; b0 += 32768)      // (a launch takes one tile per block row, at most 65535)
-		ht_launch_cnn_input(d_tiles + (size_t)b0 * HT_CNN128_IN, d_cams + (size_t)b0 * HT_CAM, HT_CNN128_IN, ctx->par.drangey, d_cnn_in + (size_t)b0 * HT_CNN128_IN, B - b0 < 32768 ? B - b0 : 32768, s);
-	HIPCHK(ctx, hipGetLastError());
-	return HT_OK;
+	const ht_net *net = ht_net_of(ctx, side);
+	return cnn_input_dev(ctx, ht_form_name(ctx, net, "ht_cnn_input_dev", "ht_cnn_input_sized_dev"), net, d_tiles, d_cams, B, d_cnn_in, stream);
 }

@@ -112,6 +112,6 @@ size_t ht_train_err_floats();
 size_t ht_train_part_floats();
 void ht_launch_fc_rowmajor(const float *A, const float *W, const float *bias, float *C, int M, int N, int K, bool tanh, hipStream_t s);      // ht_cnn.hip
 // ht_train_batch.hip
-void ht_launch_train_batch_step(float *w, float *W2p, const float *inputs, const float *targets, const int *index, int n, float alpha, float *arena, int cap, float *mse_out, hipStream_t s, int side);
-size_t ht_train_batch_floats(int cap, int side);
-void ht_train_batch_views(float *arena, int cap, const float *view[7], size_t per[7], int side);
+void ht_launch_train_batch_step(float *w, float *W2p, const float *inputs, const float *targets, const int *index, int n, float alpha, float *arena, int cap, float *mse_out, hipStream_t s, const ht_net_dims &d);
+size_t ht_train_batch_floats(int cap, const ht_net_dims &d);
+void ht_train_batch_views(float *arena, int cap, const float *view[7], size_t per[7], const ht_net_dims &d);

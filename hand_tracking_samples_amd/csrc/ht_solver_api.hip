@@ -261,7 +261,7 @@ struct frame_src { int w, h; float segment_scale; int direct; };
 // UPD_KICKSTART = kickstart (:743-746) = the same followed by handmodel.SetPose(pose) where the pose was accepted.
 // UPD_PASSES = only the caller's part of update() (:751-753, 769-785): the cloud of the frame, the main-thread passes on handmodel, the user poses (the overlapped mode, ht_update_passes_sync)
 enum { UPD_FULL = 0, UPD_CNN_MODEL = 1, UPD_KICKSTART = 2, UPD_PASSES = 3 };
-struct update_call { const uint16_t *d_depth; const float *d_cams, *d_start; int B; float *d_poses_out, *d_cnn_out; hipStream_t s; const frame_src *fs; int mode; const float *img_cams; int iw, ih; };      // one update call: what the caller gave, and where FitError finds the image (update_inputs: the full-size frame and its cameras, or the tile)
+struct update_call { const uint16_t *d_depth; const float *d_cams, *d_start; int B; float *d_poses_out, *d_cnn_out; hipStream_t s; const frame_src *fs; int mode; const float *img_cams; int iw, ih; const ht_net *net; };      // one update call: what the caller gave, where FitError finds the image (update_inputs: the full-size frame and its cameras, or the tile), and the net that looks at it (run_update_)
 static bool main_thread_cloud_voxel(const ht_ctx *ctx, const update_call &u) { return (u.mode == UPD_FULL || u.mode == UPD_PASSES) && ctx->par.subsample_voxel; }
 
 // Input staging: the point capacity this frame size needs, the segment for the net (full-size frames), the net's input, the cloud(s), the launch order by point counts
@@ -289,14 +289,14 @@ static int update_inputs(ht_ctx *ctx, update_call &u)
 		if (fs)
 		{
 			const ht_prepare_extra pz = { nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, ctx->d_nflist };
-			if (fs->direct) { HIPCHK(ctx, hipMemsetAsync(ctx->d_nflist, 0, sizeof(int), s)); ht_launch_cnn_input(d_depth, ctx->d_cams, fs->w * fs->h, p.drangey, ctx->d_in128, B, s); }
-			else if (mode != UPD_PASSES) ht_launch_prepare(ctx->d_seg_tiles, ctx->d_cams, p.drangey, p.subsample_fraction, ctx->d_cnn_in, nullptr, nullptr, ctx->model.pts_cap, B, s, &pz);      // (the caller's part of the overlapped update has no segment and no net)
+			if (fs->direct) { HIPCHK(ctx, hipMemsetAsync(ctx->d_nflist, 0, sizeof(int), s)); ht_launch_cnn_input(d_depth, ctx->d_cams, fs->w * fs->h, p.drangey, u.net->d_in, B, s); }
+			else if (mode != UPD_PASSES) ht_launch_prepare(ctx->d_seg_tiles, ctx->d_cams, p.drangey, p.subsample_fraction, u.net->d_in, nullptr, nullptr, ctx->model.pts_cap, B, s, &pz);      // (the caller's part of the overlapped update has no segment and no net)
 			ht_launch_prepare_frame(d_depth, u.img_cams, fs->w, fs->h, p.drangey, p.subsample_fraction, ctx->d_pts, ctx->d_npts, ctx->d_overflow, ctx->model.pts_cap, B, s);
 		}
 		else
 		{
 			const ht_prepare_extra px = { d_cams != ctx->d_cams ? ctx->d_cams : nullptr, ctx->d_state[0], ctx->d_state[1], u.d_start, ctx->d_prev_err, ctx->d_initializing, ctx->model.nb, ctx->d_nflist };
-			ht_launch_prepare(d_depth, d_cams, p.drangey, p.subsample_fraction, ctx->d_cnn_in, ctx->d_pts, ctx->d_npts, ctx->model.pts_cap, B, s, &px);
+			ht_launch_prepare(d_depth, d_cams, p.drangey, p.subsample_fraction, u.net->d_in, ctx->d_pts, ctx->d_npts, ctx->model.pts_cap, B, s, &px);
 		}
 		if (main_thread_cloud_voxel(ctx, u))      // UPD_PASSES: the caller's part of the overlapped update runs its passes on this very cloud (handtrack.h:753)
 		{
@@ -347,11 +347,10 @@ static void update_beside_net(ht_ctx *ctx, const update_call &u)
 }
 static void update_net(ht_ctx *ctx, const update_call &u, bool overlap)      // the net and its decode.  overlap: the side branch's FitError runs beside the net
 {
-	const frame_src *fs = u.fs; const bool direct = fs && fs->direct; hipStream_t s = u.s;
-	ht_prof_scope ps(ctx, direct ? "cnn128" : "cnn", s, true);
-	if (direct) ht_launch_cnn(ctx->cnnw128, ctx->d_in128, ctx->d_act1_128, ctx->d_act2_128, ctx->d_act3, ctx->d_logits, u.B, s, fs->direct, overlap);
-	else ht_launch_cnn(ctx->cnnw, ctx->d_cnn_in, ctx->d_act1, ctx->d_act2, ctx->d_act3, ctx->d_logits, u.B, s, 64, overlap);
-	ht_launch_softmax_decode(ctx->d_logits, u.d_cnn_out ? u.d_cnn_out : ctx->d_cnn_out, ctx->d_cams, ctx->d_analysis, 1, u.B, s, direct ? fs->direct / 16 : 4);
+	const ht_net &net = *u.net; hipStream_t s = u.s;
+	ht_prof_scope ps(ctx, net.prof, s, true);
+	ht_launch_cnn(net, net.d_in, ctx->d_act3, ctx->d_logits, u.B, s, overlap);
+	ht_launch_softmax_decode(ctx->d_logits, u.d_cnn_out ? u.d_cnn_out : ctx->d_cnn_out, ctx->d_cams, ctx->d_analysis, 1, u.B, s, net.dims.sub);
 }
 // The three organisations of the full-reset frames beside the batch's MultiStepSim (update_resets picks one).
 // The full-reset path touches few frames but is long (3 sequential single-body solves): it runs on a side stream while step 0 of
@@ -443,9 +442,8 @@ static void update_passes(ht_ctx *ctx, const update_call &u)      // the main-th
 static int run_update_(ht_ctx *ctx, update_call &u)
 {
 	const ht_params &p = ctx->par; hipStream_t s = u.s;
-	if (u.mode == UPD_PASSES) {}      // no net in the caller's part
-	else if (u.fs && u.fs->direct) { if (!ctx->have_weights128) { ctx->err = "weights of the 128x128 net not loaded (ht_cnn_load_weights_sized)"; return HT_ERR_STATE; } }
-	else if (!ctx->have_weights) { ctx->err = "CNN weights not loaded (ht_cnn_load_weights)"; return HT_ERR_STATE; }
+	u.net = ht_net_of(ctx, u.fs && u.fs->direct ? u.fs->direct : 64);      // a frame that is its own segment goes to the net of its size, everything else to the tiles' (the entry points have checked the side)
+	if (u.mode != UPD_PASSES && !u.net->have) { ctx->err = u.net->missing; return HT_ERR_STATE; }      // (no net in the caller's part of the overlapped update)
 	{ const int r = update_inputs(ctx, u); if (r) return r; }
 	if (u.mode == UPD_PASSES) { update_planes(ctx, u, s); update_passes(ctx, u); return HT_OK; }
 	static const bool no_overlap = ht_tuning_env("HT_NO_OVERLAP");      // timing experiments (-DHT_TUNING builds only)
@@ -471,7 +469,7 @@ static int run_update_(ht_ctx *ctx, update_call &u)
 }
 static int run_update(ht_ctx *ctx, const uint16_t *d_depth, const float *d_cams, const float *d_start, int B, float *d_poses_out, float *d_cnn_out, hipStream_t s, const frame_src *fs = nullptr, int mode = UPD_FULL)
 {
-	update_call u = { d_depth, d_cams, d_start, B, d_poses_out, d_cnn_out, s, fs, mode, nullptr, 64, 64 };
+	update_call u = { d_depth, d_cams, d_start, B, d_poses_out, d_cnn_out, s, fs, mode, nullptr, 64, 64, nullptr };
 	const int r = run_update_(ctx, u);
 	ctx->model.frame_order = nullptr; ctx->model.pts_bound = 0;      // the per-call hints of update_inputs (launch order of the block-per-frame kernels, largest cloud) belong to the update that set them
 	ctx->planes_valid = false;                                       // and so do the boundary planes of its cloud
@@ -660,8 +658,8 @@ extern "C" int ht_update_direct_dev(ht_ctx *ctx, const uint16_t *d_depth, const 
 {
 	CHECK_READY(ctx); CHECK_MODEL(ctx); CHECK_BATCH(ctx, B);
 	if (!d_depth || !d_cams || !d_poses_out) return HT_ERR_ARG;
+	if (!ht_net_of(ctx, side)) { ctx->err = "ht_update_direct: " + ctx->err; return HT_ERR_ARG; }
 	if (side == 64) return ht_update_dev(ctx, d_depth, d_cams, d_start_poses, B, d_poses_out, stream);
-	if (side != 128) { ctx->err = "ht_update_direct: CNN input side must be 64 or 128"; return HT_ERR_ARG; }
 	if (((uintptr_t)d_depth & 15) != 0) { ctx->err = "ht_update_direct_dev: d_depth must be 16-byte aligned (the input transform reads eight pixels per 128-bit load)"; return HT_ERR_ARG; }
 	hipStream_t s = ht_user_stream(ctx, stream);
 	const frame_src fs = { side, side, 0.0f, side };
@@ -671,7 +669,7 @@ extern "C" int ht_update_direct_sync(ht_ctx *ctx, const uint16_t *depth, const f
 {
 	CHECK_READY(ctx); CHECK_MODEL(ctx); CHECK_BATCH(ctx, B);
 	if (!depth || !cams || !poses_out) return HT_ERR_ARG;
-	if (side != 64 && side != 128) { ctx->err = "ht_update_direct: CNN input side must be 64 or 128"; return HT_ERR_ARG; }
+	if (!ht_net_of(ctx, side)) { ctx->err = "ht_update_direct: " + ctx->err; return HT_ERR_ARG; }
 	const frame_src fs = { side, side, 0.0f, side };
 	return update_sync(ctx, depth, cams, fs, UPD_FULL, B, poses_out, nullptr, cnn_out, nullptr);      // a frame that is its own segment: the point capacity follows its size
 }
@@ -784,7 +782,8 @@ extern "C" int ht_get_cnn_results(ht_ctx *ctx, int first, int n, float *cnn_inpu
 {
 	CHECK_READY(ctx); CHECK_MODEL(ctx); CHECK_RANGE(ctx, first, n);
 	HIPCHK(ctx, ht_sync_all(ctx));
-	if (cnn_input) HIPCHK(ctx, hipMemcpy(cnn_input, ctx->d_cnn_in + (size_t)first * HT_CNN_IN, (size_t)n * HT_CNN_IN * sizeof(float), hipMemcpyDeviceToHost));
+	const ht_net &tile = *ht_net_of(ctx, 64);
+	if (cnn_input) HIPCHK(ctx, hipMemcpy(cnn_input, tile.d_in + (size_t)first * tile.dims.in, (size_t)n * tile.dims.in * sizeof(float), hipMemcpyDeviceToHost));
 	if (cnn_output) HIPCHK(ctx, hipMemcpy(cnn_output, ctx->d_cnn_out + (size_t)first * HT_CNN_OUT, (size_t)n * HT_CNN_OUT * sizeof(float), hipMemcpyDeviceToHost));
 	if (analysis) HIPCHK(ctx, hipMemcpy(analysis, ctx->d_analysis + (size_t)first * HT_ANALYSIS, (size_t)n * HT_ANALYSIS * sizeof(float), hipMemcpyDeviceToHost));
 	return HT_OK;
@@ -793,12 +792,17 @@ extern "C" int ht_get_cnn_results(ht_ctx *ctx, int first, int n, float *cnn_inpu
 // The CNN's intermediate layers of the latest evaluation (ht_cnn_eval, an update call) of slots [first, first + n), for per-layer parity tests:
 // act1 [n][3600] = layer 3 of the reference's list (conv 5x5, tanh, two 2x2 max-pools: 16 x 15 x 15), act2 [n][2304] = layer 6 (conv 4x4, tanh, pool: 64 x 6 x 6),
 // act3 [n][2048] = layer 8 (first fully connected layer + tanh), logits [n][2304] = layer 9 (second fully connected layer, before the chunked soft-max).
-// (d_a1 / d_a2: the convolution layers' buffers of the net asked for, n1 / n2 floats a frame; act3 and the logits are the one pair both nets write)
-static int get_cnn_layers(ht_ctx *ctx, const float *d_a1, size_t n1, const float *d_a2, size_t n2, int first, int n, float *act1, float *act2, float *act3, float *logits)
+// The net's own convolution buffers (act1 [n][dims.act1], act2 [n][dims.act2]) exist once it has any: the 64x64-input net's from the start, the larger net's with its
+// weights; act3 and the logits are the one pair both nets write.
+static int get_cnn_layers(ht_ctx *ctx, const ht_net *net, int first, int n, float *act1, float *act2, float *act3, float *logits)
 {
+	if (!net) return HT_ERR_ARG;
+	CHECK_RANGE(ctx, first, n);
+	if (!net->d_act1) { ctx->err = net->missing; return HT_ERR_STATE; }
+	const size_t n1 = net->dims.act1, n2 = net->dims.act2;
 	HIPCHK(ctx, ht_sync_all(ctx));
-	if (act1) HIPCHK(ctx, hipMemcpy(act1, d_a1 + (size_t)first * n1, (size_t)n * n1 * sizeof(float), hipMemcpyDeviceToHost));
-	if (act2) HIPCHK(ctx, hipMemcpy(act2, d_a2 + (size_t)first * n2, (size_t)n * n2 * sizeof(float), hipMemcpyDeviceToHost));
+	if (act1) HIPCHK(ctx, hipMemcpy(act1, net->d_act1 + (size_t)first * n1, (size_t)n * n1 * sizeof(float), hipMemcpyDeviceToHost));
+	if (act2) HIPCHK(ctx, hipMemcpy(act2, net->d_act2 + (size_t)first * n2, (size_t)n * n2 * sizeof(float), hipMemcpyDeviceToHost));
 	if (act3)      // the device holds the layer in the column order the last layer's kernel reads (k_fc<PACK16>): position (c & ~15) | (c & 3) << 2 | (c >> 2) & 3 holds column c
 	{
 		std::vector<float> packed((size_t)n * 2048);
@@ -808,22 +812,9 @@ static int get_cnn_layers(ht_ctx *ctx, const float *d_a1, size_t n1, const float
 	if (logits) HIPCHK(ctx, hipMemcpy(logits, ctx->d_logits + (size_t)first * HT_CNN_OUT, (size_t)n * HT_CNN_OUT * sizeof(float), hipMemcpyDeviceToHost));
 	return HT_OK;
 }
-extern "C" int ht_get_cnn_layers(ht_ctx *ctx, int first, int n, float *act1, float *act2, float *act3, float *logits)
-{
-	CHECK_READY(ctx); CHECK_RANGE(ctx, first, n);
-	return get_cnn_layers(ctx, ctx->d_act1, 3600, ctx->d_act2, 2304, first, n, act1, act2, act3, logits);
-}
-// The same of the net with a side x side input: 64 is the call above; 128 reads the larger net's own convolution buffers (act1 [n][16 * 31 * 31], act2 [n][12544]), which
-// exist once its weights are loaded.
-extern "C" int ht_get_cnn_layers_sized(ht_ctx *ctx, int side, int first, int n, float *act1, float *act2, float *act3, float *logits)
-{
-	CHECK_READY(ctx);
-	if (side == 64) return ht_get_cnn_layers(ctx, first, n, act1, act2, act3, logits);
-	if (side != 128) { ctx->err = "CNN input side must be 64 or 128"; return HT_ERR_ARG; }
-	CHECK_RANGE(ctx, first, n);
-	if (!ctx->have_weights128) { ctx->err = "weights of the 128x128 net not loaded (ht_cnn_load_weights_sized)"; return HT_ERR_STATE; }
-	return get_cnn_layers(ctx, ctx->d_act1_128, 16 * 31 * 31, ctx->d_act2_128, 12544, first, n, act1, act2, act3, logits);
-}
+extern "C" int ht_get_cnn_layers(ht_ctx *ctx, int first, int n, float *act1, float *act2, float *act3, float *logits) { CHECK_READY(ctx); return get_cnn_layers(ctx, ht_net_of(ctx, 64), first, n, act1, act2, act3, logits); }
+// the same of the net with a side x side input
+extern "C" int ht_get_cnn_layers_sized(ht_ctx *ctx, int side, int first, int n, float *act1, float *act2, float *act3, float *logits) { CHECK_READY(ctx); return get_cnn_layers(ctx, ht_net_of(ctx, side), first, n, act1, act2, act3, logits); }
 
 // ---- stage entry points (operate on the buffers ht_stage_prepare filled and on the tracker state of slots [0,B)) -------------
 extern "C" int ht_stage_fit_error(ht_ctx *ctx, int which, int B, float *err)

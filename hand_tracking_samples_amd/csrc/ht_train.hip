@@ -223,8 +223,8 @@ __global__ __launch_bounds__(256) void k_t_conv_update(const float *__restrict__
 // act: layer outputs kept for the backward pass; err: errors and conv2-backward partial sums; part: FC1's and FC2's partial sums
 void ht_launch_train_step(float *w, float *W2p, const float *x, const float *target, float alpha, float *act, float *err, float *part, float *mse_out, hipStream_t s)
 {
-	float *a1 = act, *a3 = a1 + 57600, *a5 = a3 + 3600, *a6 = a5 + 9216, *a8 = a6 + 2304;
-	float *e9 = err, *e7 = e9 + 2304, *e6 = e7 + 2048, *part3 = e6 + 2304, *sqp = part3 + T_CB_GROUPS * 3600;
+	float *a1 = act, *a3 = a1 + 57600, *a5 = a3 + cnn_dims<64>::A3, *a6 = a5 + 9216, *a8 = a6 + 2304;
+	float *e9 = err, *e7 = e9 + 2304, *e6 = e7 + 2048, *part3 = e6 + 2304, *sqp = part3 + T_CB_GROUPS * cnn_dims<64>::A3;
 	float *part1 = part, *part2 = part + (size_t)T_KSPLIT * 2048;
 	const cnnb_layout<float> L = cnnb_layout_of(w);
 	// forward
@@ -239,6 +239,6 @@ void ht_launch_train_step(float *w, float *W2p, const float *x, const float *tar
 	hipLaunchKernelGGL(k_t_conv2_back, dim3(16, T_CB_GROUPS), dim3(256), 0, s, a5, e6, L.W2, part3);
 	hipLaunchKernelGGL(k_t_conv_update, dim3(80), dim3(256), 0, s, x, a1, a3, a5, e6, part3, L.W1, L.B1, L.W2, L.B2, W2p, alpha);
 }
-size_t ht_train_act_floats() { return 57600 + 3600 + 9216 + 2304 + 2048; }
-size_t ht_train_err_floats() { return 2304 + 2048 + 2304 + T_CB_GROUPS * 3600 + 16; }
+size_t ht_train_act_floats() { return 57600 + cnn_dims<64>::A3 + 9216 + 2304 + 2048; }
+size_t ht_train_err_floats() { return 2304 + 2048 + 2304 + T_CB_GROUPS * cnn_dims<64>::A3 + 16; }
 size_t ht_train_part_floats() { return (size_t)T_KSPLIT * (2048 + 2304); }

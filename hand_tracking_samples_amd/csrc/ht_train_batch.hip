@@ -314,27 +314,25 @@ __global__ __launch_bounds__(256) void k_tb_conv_apply(const float *__restrict__
 	}
 }
 
-// The arena of a step of up to cap samples (cap a multiple of 32) of the net of input side `side`: per-sample tensors [cap][...], then the partial sums, the
+// The arena of a step of up to cap samples (cap a multiple of 32) of the net of dimensions d: per-sample tensors [cap][...], then the partial sums, the
 // indices and a sink for the losses
 struct tb_arena { float *a3, *a6, *a8, *lg, *e9, *e7, *e6, *e3, *pw, *sink; int *r1, *r3, *idx; };
-static size_t tb_a3(int side) { return side == 128 ? cnn_dims<128>::A3 : cnn_dims<64>::A3; }
-static size_t tb_a6(int side) { return side == 128 ? cnn_dims<128>::A6 : cnn_dims<64>::A6; }
-static tb_arena tb_layout(float *p, size_t cap, int side)
+static tb_arena tb_layout(float *p, size_t cap, const ht_net_dims &d)
 {
-	const size_t n3 = tb_a3(side), n6 = tb_a6(side);
+	const size_t n3 = d.act1, n6 = d.act2;
 	tb_arena A;
 	A.a3 = p; p += cap * n3; A.r1 = (int *)p; p += cap * n3; A.a6 = p; p += cap * n6; A.r3 = (int *)p; p += cap * n6; A.a8 = p; p += cap * 2048;
 	A.lg = p; p += cap * 2304; A.e9 = p; p += cap * 2304; A.e7 = p; p += cap * 2048; A.e6 = p; p += cap * n6; A.e3 = p; p += cap * n3;
 	A.pw = p; p += (size_t)TB_MAXG * TB_PW; A.sink = p; p += HT_TRAIN_MAX_BATCH; A.idx = (int *)p;
 	return A;
 }
-size_t ht_train_batch_floats(int cap, int side) { return (size_t)cap * (3 * tb_a3(side) + 3 * tb_a6(side) + 2 * 2304 + 2 * 2048) + (size_t)TB_MAXG * TB_PW + 2 * HT_TRAIN_MAX_BATCH; }
+size_t ht_train_batch_floats(int cap, const ht_net_dims &d) { return (size_t)cap * (3 * d.act1 + 3 * d.act2 + 2 * 2304 + 2 * 2048) + (size_t)TB_MAXG * TB_PW + 2 * HT_TRAIN_MAX_BATCH; }
 // the per-sample tensors ht_debug_train_batch_buffers returns, in its order: a3 a6 a8 e9 e7 e6 e3, and the floats of each per sample
-void ht_train_batch_views(float *arena, int cap, const float *view[7], size_t per[7], int side)
+void ht_train_batch_views(float *arena, int cap, const float *view[7], size_t per[7], const ht_net_dims &d)
 {
-	const tb_arena A = tb_layout(arena, (size_t)cap, side);
+	const tb_arena A = tb_layout(arena, (size_t)cap, d);
 	view[0] = A.a3; view[1] = A.a6; view[2] = A.a8; view[3] = A.e9; view[4] = A.e7; view[5] = A.e6; view[6] = A.e3;
-	per[0] = tb_a3(side); per[1] = tb_a6(side); per[2] = 2048; per[3] = 2304; per[4] = 2048; per[5] = tb_a6(side); per[6] = tb_a3(side);
+	per[0] = d.act1; per[1] = d.act2; per[2] = 2048; per[3] = 2304; per[4] = 2048; per[5] = d.act2; per[6] = d.act1;
 }
 template <bool FOLD> static void tb_fc_back(const float *E, const float *W, const float *Y, float *D, int n, int R, int K, hipStream_t s)
 {
@@ -348,7 +346,7 @@ template <bool FOLD> static void tb_fc_back(const float *E, const float *W, cons
 template <int S, int C2T, int BH, int BT, int IZB> static void tb_step(float *w, float *W2p, const float *inputs, const float *targets, const int *index, int n, float alpha, float *arena, int cap, float *mse_out, hipStream_t s)
 {
 	typedef cnn_dims<S> D;
-	const tb_arena A = tb_layout(arena, (size_t)cap, S);
+	const tb_arena A = tb_layout(arena, (size_t)cap, ht_net_dims_of<S>());
 	const cnnb_layout<float> L = cnnb_layout_of(w, (size_t)D::A6);
 	tb_index ix;
 	for (int b = 0; b < n; b++) ix.v[b] = index[b];
@@ -371,9 +369,9 @@ template <int S, int C2T, int BH, int BT, int IZB> static void tb_step(float *w,
 	hipLaunchKernelGGL(k_tb_conv_apply, dim3((TB_PW + 255) / 256), dim3(256), 0, s, A.pw, groups, L.W1, L.B1, L.W2, L.B2, W2p);
 }
 // One step on samples index[0..n) of the pools ([..][side side] inputs); mse_out[n] or null.  The packed copy of the last layer is NOT refreshed here (once per
-// call: ht_api.hip).  side = 64 or 128, checked by the caller.
-void ht_launch_train_batch_step(float *w, float *W2p, const float *inputs, const float *targets, const int *index, int n, float alpha, float *arena, int cap, float *mse_out, hipStream_t s, int side)
+// call: ht_api.hip).  d: the dimensions of one of the context's nets (ht_net_of).
+void ht_launch_train_batch_step(float *w, float *W2p, const float *inputs, const float *targets, const int *index, int n, float alpha, float *arena, int cap, float *mse_out, hipStream_t s, const ht_net_dims &d)
 {
-	if (side == 128) tb_step<128, 256, 4, 256, 4>(w, W2p, inputs, targets, index, n, alpha, arena, cap, mse_out, s);
+	if (d.side == 128) tb_step<128, 256, 4, 256, 4>(w, W2p, inputs, targets, index, n, alpha, arena, cap, mse_out, s);
 	else tb_step<64, 192, 15, 256, 1>(w, W2p, inputs, targets, index, n, alpha, arena, cap, mse_out, s);
 }

@@ -1,21 +1,12 @@
 // ht_train_shared.hpp -- what the per-sample training step (ht_train.hip) and the mini-batch step (ht_train_batch.hip) compute alike: the two
 // convolutions forward, the pool / tanh backward into an error map, conv2's backward gather and conv1's gradient over the compact list, each
-// written once, with the net's dimensions as template parameters (cnn_dims: the 64x64-input net by default, the 128x128-input one for the sized
-// mini-batch step), so that a correction reaches every step.  Every function is the floating-point operations of the kernels it came from, in their
-// order (the build has no contraction and no fast math, so that fixes the bits).  Also the .cnnb layout and the index of the packed conv2 copy,
-// which the weight loader (ht_api.hip) reads too.
+// written once, with the net's dimensions as template parameters (cnn_dims, ht_device.hpp: the 64x64-input net by default, the 128x128-input one for the
+// sized mini-batch step), so that a correction reaches every step.  Every function is the floating-point operations of the kernels it came from, in their
+// order (the build has no contraction and no fast math, so that fixes the bits).  Also the index of the packed conv2 copy, which the weight loader
+// (ht_api.hip) reads too.
 #pragma once
 #include "ht_device.hpp"
 
-// The .cnnb order of the weights (CNN::saveb cnn.h:591-593) from the base pointer; fc_in = inputs of the first fully connected layer (2304 of the
-// 64x64-input net, 12544 of the 128x128 one)
-template <class T> struct cnnb_layout { T *W1, *B1, *W2, *B2, *W3, *B3, *W4, *B4; };
-template <class T> static inline cnnb_layout<T> cnnb_layout_of(T *w, size_t fc_in = 2304)
-{
-	cnnb_layout<T> L;
-	L.W1 = w; L.B1 = L.W1 + 400; L.W2 = L.B1 + 16; L.B2 = L.W2 + 16384; L.W3 = L.B2 + 64; L.B3 = L.W3 + fc_in * 2048; L.W4 = L.B3 + 2048; L.B4 = L.W4 + (size_t)2048 * 2304;
-	return L;
-}
 // conv2 weight (oc, ic, ky, kx) in the MFMA-packed copy W2p[k][oc], k = (ky*4+kx)*16 + ic, that k_conv2 reads (reference index: kx + 4*(ky + 4*(ic + 16*oc)), cnn.h:45-47)
 __host__ __device__ static inline size_t cnn_w2p_index(int oc, int ic, int ky, int kx) { return (size_t)((ky * 4 + kx) * 16 + ic) * 64 + oc; }
 
@@ -32,13 +23,6 @@ __device__ __forceinline__ int first_max4(float a, float b, float c, float d, fl
 __device__ __forceinline__ float wave_sum(float v) { for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o); return v; }
 __device__ __forceinline__ float seg16_sum(float v) { for (int o = 8; o >= 1; o >>= 1) v += __shfl_xor(v, o); return v; }
 __device__ __forceinline__ float seg8_sum(float v) { for (int o = 4; o >= 1; o >>= 1) v += __shfl_xor(v, o); return v; }
-
-// The layer dimensions of either net from its input side S (64: 60 -> 15, 12 -> 6, FC 2304; 128: 124 -> 31, 28 -> 14, FC 12544): C1 = conv1's output side,
-// P2 = after the two pools, C2 = conv2's output side, P3 = after the third pool; A3 / A6 = floats of a sample's a3 [16][P2][P2] / a6 [64][P3][P3]
-template <int S> struct cnn_dims
-{
-	static constexpr int SIDE = S, C1 = S - 4, P2 = C1 / 4, NP2 = P2 * P2, A3 = 16 * NP2, C2 = P2 - 3, NC2 = C2 * C2, P3 = C2 / 2, NP3 = P3 * P3, A6 = 64 * NP3;
-};
 
 // conv1 (5x5, 1 -> 16 channels, S x S -> (S-4) x (S-4)) + tanh: output (oz, y, x) of one S x S input, taps in the reference's order (cnn.h:226-228)
 template <int S = 64> __device__ __forceinline__ float t_conv1_out(const float *in, const float *W, const float *B, int oz, int y, int x)

@@ -241,32 +241,30 @@ class Context:
         self._chk(self.L.ht_set_params(self.h, C.byref(p)))
 
     # -- CNN
-    def load_weights(self, w):
-        w = _c(w, np.float32)
-        self._chk(self.L.ht_cnn_load_weights(self.h, _f(w), w.size))
+    def load_weights(self, w, side=64):
+        """The weights of the net of a side x side input (64: the reference's; 128: BASELINE configs[4]) in .cnnb order."""
+        w = _c(w, np.float32); side = self._side(side)
+        self._chk(self.L.ht_cnn_load_weights(self.h, _f(w), w.size) if side == 64 else self.L.ht_cnn_load_weights_sized(self.h, side, _f(w), w.size))
 
-    def cnn_eval(self, x):
-        x = _c(x, np.float32).reshape(-1, CNN_IN)
+    def cnn_eval(self, x, side=64):
+        side = self._side(side)
+        x = _c(x, np.float32).reshape(-1, side * side)
         out = np.empty((x.shape[0], CNN_OUT), np.float32)
-        self._chk(self.L.ht_cnn_eval(self.h, _f(x), _f(out), x.shape[0]))
+        self._chk(self.L.ht_cnn_eval(self.h, _f(x), _f(out), x.shape[0]) if side == 64 else self.L.ht_cnn_eval_sized(self.h, side, _f(x), _f(out), x.shape[0]))
         return out
 
-    def cnn_eval_dev(self, d_in, d_out, B, stream):
-        self._chk(self.L.ht_cnn_eval_dev(self.h, d_in, d_out, B, stream))
+    def cnn_eval_dev(self, d_in, d_out, B, stream, side=64):
+        side = self._side(side)
+        self._chk(self.L.ht_cnn_eval_dev(self.h, d_in, d_out, B, stream) if side == 64 else self.L.ht_cnn_eval_sized_dev(self.h, side, d_in, d_out, B, stream))
 
-    # -- the same layers on a 128x128 input (BASELINE configs[4])
     def load_weights128(self, w):
-        w = _c(w, np.float32)
-        self._chk(self.L.ht_cnn_load_weights_sized(self.h, 128, _f(w), w.size))
+        self.load_weights(w, side=128)
 
     def cnn128_eval(self, x):
-        x = _c(x, np.float32).reshape(-1, 128 * 128)
-        out = np.empty((x.shape[0], CNN_OUT), np.float32)
-        self._chk(self.L.ht_cnn_eval_sized(self.h, 128, _f(x), _f(out), x.shape[0]))
-        return out
+        return self.cnn_eval(x, side=128)
 
     def cnn128_eval_dev(self, d_in, d_out, B, stream):
-        self._chk(self.L.ht_cnn_eval_sized_dev(self.h, 128, d_in, d_out, B, stream))
+        self.cnn_eval_dev(d_in, d_out, B, stream, side=128)
 
     # -- tracker
     def tracker_reset(self, poses, first=0):
