@@ -71,7 +71,7 @@ struct ht_ctx
 
 	// device buffers (capacity B frames / tracker slots)
 	uint16_t *d_depth = nullptr;
-	uint16_t *d_seg_tiles = nullptr, *d_frames = nullptr; float *d_frame_cams = nullptr, *d_frame_cams_in = nullptr; int *d_overflow = nullptr; size_t frames_cap = 0;      // full-size frame path (ht_update_frames); d_frames holds the largest frame size seen (dev_grow)
+	uint16_t *d_seg_tiles = nullptr, *d_frames = nullptr; float *d_frame_cams = nullptr, *d_frame_cams_in = nullptr; int *d_overflow = nullptr; size_t frames_cap = 0, seg_tiles_cap = 0;      // full-size frame path (ht_update_frames); d_frames holds the largest frame size seen, d_seg_tiles the largest tile side (dev_grow)
 	float *d_cams = nullptr, *d_analysis = nullptr;
 	float *d_act3 = nullptr, *d_logits = nullptr, *d_cnn_out = nullptr;      // shared by both nets: the latest evaluation's first FC layer, logits and output, whichever net ran
 	float4 *d_pts = nullptr; int *d_npts = nullptr;

@@ -102,8 +102,9 @@ void ht_launch_reset(const ht_model_dev &M, const ht_physics_dev &ph, float *sta
                      int n_unibody, const ht_params &par, float *rows, int *nrows, float *scratch, int scratch_stride, int batch, int B, hipStream_t s, bool many_frames, int n_cu, bool exact = false);
 void ht_launch_output(const ht_model_dev &M, const float *hand, const int *npts, int *initializing, int min_point_num, float *poses, int n, hipStream_t s, int raw = 0);
 // ht_segment.hip
-bool ht_segment_supported(int w, int h);
-void ht_launch_segment(const uint16_t *depth, const float *cams, int w, int h, int entry_options, float wrange_hi, float diam, uint16_t *tiles, float *cams_out, int B, hipStream_t s);
+bool ht_segment_supported(int w, int h);                             // frames of the unsized entry points: at most 320x240
+bool ht_segment_supported_sized(int w, int h, int side);             // frames and tile sides of the sized ones: at most 640x480, side 64 or 128
+void ht_launch_segment(const uint16_t *depth, const float *cams, int w, int h, int entry_options, float wrange_hi, float diam, uint16_t *tiles, float *cams_out, int B, hipStream_t s, int side = 64);
 void ht_launch_scale_state(float *state, int nb, int n, float s, hipStream_t st);      // ht_track.hip
 // ht_train.hip
 void ht_launch_train_step(float *w, float *W2p, const float *x, const float *target, float alpha, float *act, float *err, float *part, float *mse_out, hipStream_t s);

@@ -1,4 +1,4 @@
-// ht_segment.hip -- the step before the tracker for full-size depth frames: hand segmentation to a 64x64 tile.
+// ht_segment.hip -- the step before the tracker for full-size depth frames: hand segmentation to a tile of the net's input side, 64x64 or 128x128.
 //
 // Reference computations:
 //   HandSegmentVR                 include/handtrack.h:280-344
@@ -6,13 +6,18 @@
 //   Threshold, DistanceTransform  include/misc_image.h:179-195
 //   SampleD                       include/misc_image.h:154-162
 //
-// One 256-thread block per frame; the quarter-size image (80x60 for a 320x240 frame) and its distance transform stay in LDS.
+// One 256-thread block per frame; the quarter-size image (80x60 for a 320x240 frame, 160x120 for 640x480), its distance transform and the compacted list
+// stay in dynamic LDS: 5 bytes per quarter pixel, 24000 bytes up to 320x240 (several blocks per CU), sized from the frame beyond that, 96000 bytes at 640x480
+// (one block per CU).
+// The tile side S (template parameter) enters in dstcam = ({S,S}, avgdepth*S/diam, {S/2,S/2}) and the S x S loop of SampleD alone (handtrack.h:338-342);
+// S is a power of two, so the side-128 camera is the side-64 camera with focal doubled and principal (64,64), bit for bit.
 //   1. 4x4 min pooling straight from the frame (two 2x2 min poolings compose exactly), threshold.
 //   2. The reference's two raster passes of the Manhattan distance transform are min-plus recurrences over integers; each is
 //      evaluated exactly as a row scan followed by a column scan (one thread per row / column).
 //   3. Entry point and extreme point are "first maximum" searches in a fixed order: parallel arg-max on (value, order index).
-//   4. The weighted centroid sums are float accumulations in raster order, so they stay sequential: the selected pixels are
-//      compacted in raster order first, then four lanes each accumulate one of the four sums over that list.
+//   4. The weighted centroid sums are float accumulations in raster order, so the additions stay sequential: the selected pixels are
+//      compacted in raster order first, the block forms their weights and products 256 at a time, and four lanes each add one of the
+//      four products of every entry in list order.
 //   5. Rotated resampling (SampleD), 16 output pixels per thread.
 // atan2 at handtrack.h:326 is the unqualified C function, i.e. evaluated in double; sin/cos of the half angle are formed in double and
 // rounded once (the reference calls sinf/cosf; the two agree except in rare half-ulp cases).
@@ -20,7 +25,8 @@
 #include "ht_launch.hpp"
 
 #define SEG_THREADS 256
-#define SEG_MAXSMALL 4800      // quarter-size pixels held in LDS (320x240 input)
+#define SEG_MAXSMALL 4800      // quarter-size pixels of the unsized entry points (320x240 input): 24 KB of LDS
+#define SEG_MAXSMALL_SIZED 19200      // ... of the sized ones (640x480 input): 96 KB, indices still fit 16 bits
 
 __device__ __forceinline__ v3 seg_deproject(float fx, float fy, float px, float py, float x, float y, float d)      // DCamera::deprojectz, misc_image.h:48
 {
@@ -60,12 +66,17 @@ __device__ int seg_block_argmax_f(float val, int ord, float *redf, int *redi)
 	return bo;
 }
 
-__global__ __launch_bounds__(SEG_THREADS) void k_segment(const uint16_t *__restrict__ depth, const float *__restrict__ cams, int w, int h, int entry_options, float wrange_hi, float diam,
+// The dynamic LDS of a block: small u16[nsp], sel u16[nsp], then the distance transform u8[nsp], whose region the products of the centroid sums take over once the
+// compaction is through (SEG_THREADS float4).  nsp = the frame's quarter-size pixels rounded to 8 (every array 16-byte aligned), or CAP for the instantiation of the
+// frames the unsized entry points take: its offsets are compile-time constants and its footprint the 24000 bytes the static arrays had.
+static __host__ __device__ __forceinline__ int seg_lds_pixels(int ns) { return (ns + 7) & ~7; }
+static __host__ __device__ __forceinline__ size_t seg_lds_bytes(int nsp) { return (size_t)4 * nsp + (nsp > SEG_THREADS * 16 ? nsp : SEG_THREADS * 16); }
+template <int S, int CAP> __global__ __launch_bounds__(SEG_THREADS) void k_segment(const uint16_t *__restrict__ depth, const float *__restrict__ cams, int w, int h, int entry_options, float wrange_hi, float diam,
                                                          uint16_t *__restrict__ tiles, float *__restrict__ cams_out)
 {
-	__shared__ uint16_t small[SEG_MAXSMALL];
-	__shared__ unsigned char dt[SEG_MAXSMALL];
-	__shared__ uint16_t sel[SEG_MAXSMALL];
+	static_assert(S == 64 || S == 128, "tile side");
+	static_assert(CAP % 8 == 0 && (CAP == 0 || CAP >= SEG_THREADS * 16), "a fixed capacity holds the products too");
+	extern __shared__ __align__(16) unsigned char seg_lds[];     // seg_lds_bytes(nsp), from ht_launch_segment
 	__shared__ int red[2 * SEG_THREADS / 64]; __shared__ float redf[SEG_THREADS / 64];
 	__shared__ int wavecnt[SEG_THREADS / 64 + 1];
 	__shared__ float sums[4];
@@ -74,7 +85,9 @@ __global__ __launch_bounds__(SEG_THREADS) void k_segment(const uint16_t *__restr
 	const uint16_t *src = depth + (size_t)b * w * h;
 	const float *cam = cams + (size_t)b * HT_CAM;
 	const float fx = cam[0], fy = cam[1], px = cam[2], py = cam[3], depth_scale = cam[4];
-	const int sw = (w / 2) / 2, sh = (h / 2) / 2, ns = sw * sh;
+	const int sw = (w / 2) / 2, sh = (h / 2) / 2, ns = sw * sh, nsp = CAP ? CAP : seg_lds_pixels(ns);
+	uint16_t *small = reinterpret_cast<uint16_t *>(seg_lds), *sel = small + nsp;
+	unsigned char *dt = reinterpret_cast<unsigned char *>(sel + nsp);
 	const unsigned short wy = (unsigned short)(wrange_hi / depth_scale);      // ushort2(wrange / depth_scale).y, handtrack.h:287
 	// ---- 1. 4x4 min pooling + threshold ----
 	for (int i = t; i < ns; i += SEG_THREADS)
@@ -141,19 +154,33 @@ __global__ __launch_bounds__(SEG_THREADS) void k_segment(const uint16_t *__restr
 		__syncthreads();
 	}
 	const int count = total;
-	// the four sums of handtrack.h:303-311, each in raster order: lane c of wave 0 accumulates sum c
-	if (t < 4)
+	// the four sums of handtrack.h:303-311, each in raster order.  The weight (two integer divisions, a square root) and the four products of a pixel do not depend on
+	// the sums: the block forms them for SEG_THREADS list entries at a time, in parallel and rounded exactly as the one-lane loop rounded them (no contraction), into `prod`
+	// -- the distance transform's LDS, which nothing reads after the compaction -- and lane c of wave 0 then adds the c-th product of every entry in list order.  What stays
+	// sequential is one float addition per entry.
 	{
+		float4 *prod = reinterpret_cast<float4 *>(dt);      // [SEG_THREADS]: (1, x, y, depth) * weight (ht_launch_segment sizes the region for it)
 		float acc = 0.0f;
-		for (int k = 0; k < count; k++)
+		for (int base = 0; base < count; base += SEG_THREADS)
 		{
-			const int i = sel[k], x = i % sw, y = i / sw;
-			const float dx = (float)(x - ex), dy = (float)(y - ey);
-			const float wgt = sqrtf(dx * dx + dy * dy) + 0.00001f;
-			const float f = t == 0 ? 1.0f : t == 1 ? (float)x : t == 2 ? (float)y : (float)small[i];
-			acc += f * wgt;
+			const int k = base + t;
+			if (k < count)
+			{
+				const int i = sel[k], x = i % sw, y = i / sw;
+				const float dx = (float)(x - ex), dy = (float)(y - ey);
+				const float wgt = sqrtf(dx * dx + dy * dy) + 0.00001f;
+				prod[t] = make_float4(wgt, (float)x * wgt, (float)y * wgt, (float)small[i] * wgt);      // 1.0f * wgt == wgt
+			}
+			__syncthreads();
+			if (t < 4)
+			{
+				const float *p = reinterpret_cast<const float *>(prod) + t;
+				const int n = min(SEG_THREADS, count - base);
+				for (int j = 0; j < n; j++) acc += p[4 * j];
+			}
+			__syncthreads();
 		}
-		sums[t] = acc;
+		if (t < 4) sums[t] = acc;
 	}
 	__syncthreads();
 	float wtotal = sums[0], comx = sums[1], comy = sums[2], avgdepth = sums[3];
@@ -189,31 +216,46 @@ __global__ __launch_bounds__(SEG_THREADS) void k_segment(const uint16_t *__restr
 			const float shift = exrad - diam / 2.0f / avgdepth * sfx;
 			comx += nx * shift; comy += ny * shift;
 		}
-		const float dfocal = avgdepth * 64.0f / diam;
+		const float dfocal = avgdepth * (float)S / diam;
 		const v4 dq = qmul(quat_from_to(seg_deproject(sfx, sfy, spx, spy, spx, spy, 1.0f), seg_deproject(sfx, sfy, spx, spy, comx, comy, 1.0f)), quat_axis_angle(V3(0, 0, 1), angle));
 		fin[0] = dq.x; fin[1] = dq.y; fin[2] = dq.z; fin[3] = dq.w; fin[4] = dfocal;
 		float *co = cams_out + (size_t)b * HT_CAM;
-		co[0] = dfocal; co[1] = dfocal; co[2] = 32.0f; co[3] = 32.0f; co[4] = depth_scale; co[5] = 0; co[6] = 0; co[7] = 0; co[8] = dq.x; co[9] = dq.y; co[10] = dq.z; co[11] = dq.w;
+		co[0] = dfocal; co[1] = dfocal; co[2] = (float)(S / 2); co[3] = (float)(S / 2); co[4] = depth_scale; co[5] = 0; co[6] = 0; co[7] = 0; co[8] = dq.x; co[9] = dq.y; co[10] = dq.z; co[11] = dq.w;
 	}
 	__syncthreads();
 	// ---- 5. SampleD with a 4 m background ----
 	const v4 dq = V4(fin[0], fin[1], fin[2], fin[3]); const float dfocal = fin[4];
 	const unsigned short background = (unsigned short)(4.0f / depth_scale);
-	const v3 ppdir = V3(0, 0, 0) + qrot(dq, seg_deproject(dfocal, dfocal, 32.0f, 32.0f, 32.0f, 32.0f, 1.0f));
-	for (int i = t; i < 4096; i += SEG_THREADS)
+	const float pp = (float)(S / 2);
+	const v3 ppdir = V3(0, 0, 0) + qrot(dq, seg_deproject(dfocal, dfocal, pp, pp, pp, pp, 1.0f));
+	for (int i = t; i < S * S; i += SEG_THREADS)
 	{
-		const int x = i & 63, y = i >> 6;
-		const v3 dir = V3(0, 0, 0) + qrot(dq, seg_deproject(dfocal, dfocal, 32.0f, 32.0f, (float)x, (float)y, 1.0f));
+		const int x = i & (S - 1), y = i >> (S == 128 ? 7 : 6);
+		const v3 dir = V3(0, 0, 0) + qrot(dq, seg_deproject(dfocal, dfocal, pp, pp, (float)x, (float)y, 1.0f));
 		const float u = dir.x / dir.z * fx + px, v = dir.y / dir.z * fy + py;
 		const int sx = (int)u, sy = (int)v;
 		unsigned short o = background;
 		if (sx >= 0 && sx <= w - 1 && sy >= 0 && sy <= h - 1) o = (unsigned short)dot(ppdir, seg_deproject(fx, fy, px, py, (float)sx, (float)sy, (float)src[(size_t)sy * w + sx]));
-		tiles[(size_t)b * 4096 + i] = o;
+		tiles[(size_t)b * (S * S) + i] = o;
 	}
 }
 
-bool ht_segment_supported(int w, int h) { return w >= 8 && h >= 8 && (w % 4) == 0 && (h % 4) == 0 && (w / 4) * (h / 4) <= SEG_MAXSMALL; }
-void ht_launch_segment(const uint16_t *depth, const float *cams, int w, int h, int entry_options, float wrange_hi, float diam, uint16_t *tiles, float *cams_out, int B, hipStream_t s)
+static bool seg_shape_ok(int w, int h, int maxsmall) { return w >= 8 && h >= 8 && (w % 4) == 0 && (h % 4) == 0 && (long long)(w / 4) * (h / 4) <= maxsmall; }
+bool ht_segment_supported(int w, int h) { return seg_shape_ok(w, h, SEG_MAXSMALL); }      // the unsized entry points' rule
+bool ht_segment_supported_sized(int w, int h, int side) { return (side == 64 || side == 128) && seg_shape_ok(w, h, SEG_MAXSMALL_SIZED); }      // ht_segment_vr_supported
+// side: 64 or 128 (the callers have checked it, and the frame size against the entry point's rule)
+void ht_launch_segment(const uint16_t *depth, const float *cams, int w, int h, int entry_options, float wrange_hi, float diam, uint16_t *tiles, float *cams_out, int B, hipStream_t s, int side)
 {
-	hipLaunchKernelGGL(k_segment, dim3(B), dim3(SEG_THREADS), 0, s, depth, cams, w, h, entry_options, wrange_hi, diam, tiles, cams_out);
+	const int ns = (w / 4) * (h / 4);
+	if (ns <= SEG_MAXSMALL)      // up to 320x240: the fixed layout, 24000 bytes, several blocks per CU
+	{
+		const size_t dyn = seg_lds_bytes(SEG_MAXSMALL);
+		if (side == 128) hipLaunchKernelGGL((k_segment<128, SEG_MAXSMALL>), dim3(B), dim3(SEG_THREADS), dyn, s, depth, cams, w, h, entry_options, wrange_hi, diam, tiles, cams_out);
+		else hipLaunchKernelGGL((k_segment<64, SEG_MAXSMALL>), dim3(B), dim3(SEG_THREADS), dyn, s, depth, cams, w, h, entry_options, wrange_hi, diam, tiles, cams_out);
+		return;
+	}
+	const size_t dyn = seg_lds_bytes(seg_lds_pixels(ns));      // 96000 bytes at 640x480: beyond a launch's default limit, one block per CU
+	static ht_lds_limit limit; limit.raise(seg_lds_bytes(SEG_MAXSMALL_SIZED), k_segment<64, 0>, k_segment<128, 0>);
+	if (side == 128) hipLaunchKernelGGL((k_segment<128, 0>), dim3(B), dim3(SEG_THREADS), dyn, s, depth, cams, w, h, entry_options, wrange_hi, diam, tiles, cams_out);
+	else hipLaunchKernelGGL((k_segment<64, 0>), dim3(B), dim3(SEG_THREADS), dyn, s, depth, cams, w, h, entry_options, wrange_hi, diam, tiles, cams_out);
 }

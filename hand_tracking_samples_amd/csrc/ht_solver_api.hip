@@ -255,7 +255,9 @@ static void reset_path(ht_ctx *ctx, bool listed, int n_unibody, int B, hipStream
 // MultiStepSim take segment.cam.pose); the point cloud and FitError keep the full frame and its camera.
 // `direct` != 0: the frame (direct x direct pixels) is its own segment and feeds the net of that input size -- what HandSegmentVR returns for a frame of the net's
 // size (handtrack.h:283-284), the stages of :693-729 called directly (BASELINE configs[4] end to end, SURVEY 8d config 5 i-iii); heat-map camera camsub(cam, direct / 16).
-struct frame_src { int w, h; float segment_scale; int direct; };
+// `side`: the tile side the segment is cut at, that of the net that looks at it (64: the reference's; 128: the sized calls, ht_update_frames_sized_*): the segment camera
+// of side 128 is that of side 64 with focal doubled and principal (64,64), its heat-map camera camsub(cam, 8) is camsub(cam64, 4), and the pose is the same pose.
+struct frame_src { int w, h; float segment_scale; int direct; int side = 64; };
 // `mode`: UPD_FULL = HandTracker::update (handtrack.h:748-785); UPD_CNN_MODEL = update_cnn_model alone (:734-741): othermodel is NOT re-seeded from
 // handmodel, no main-thread passes, no "initializing = 50" rule, the result is othermodel.GetPose() plus the accept decision, handmodel untouched;
 // UPD_KICKSTART = kickstart (:743-746) = the same followed by handmodel.SetPose(pose) where the pose was accepted.
@@ -274,12 +276,13 @@ static int update_inputs(ht_ctx *ctx, update_call &u)
 	u.img_cams = ctx->d_cams;
 	if (fs)
 	{
-		int r;      // the three buffers of the full-size path, the one this asks for last
-		if (!ctx->d_seg_tiles && ((r = dev_alloc(ctx, &ctx->d_frame_cams, (size_t)ctx->B * HT_CAM)) || (r = dev_alloc(ctx, &ctx->d_overflow, 1)) || (r = dev_alloc(ctx, &ctx->d_seg_tiles, (size_t)ctx->B * 4096)))) return r;
+		int r;      // the three buffers of the full-size path: the two of fixed size by the one this asks for last, the tiles following the largest side seen
+		if (!ctx->d_overflow && ((r = dev_alloc(ctx, &ctx->d_frame_cams, (size_t)ctx->B * HT_CAM)) || (r = dev_alloc(ctx, &ctx->d_overflow, 1)))) return r;
+		if ((r = dev_grow(ctx, &ctx->d_seg_tiles, &ctx->seg_tiles_cap, (size_t)ctx->B * fs->side * fs->side))) return r;
 		HIPCHK(ctx, hipMemcpyAsync(ctx->d_frame_cams, d_cams, (size_t)B * HT_CAM * sizeof(float), hipMemcpyDeviceToDevice, s));
 		HIPCHK(ctx, hipMemsetAsync(ctx->d_overflow, 0, sizeof(int), s));
 		if (fs->direct) { if (d_cams != ctx->d_cams) HIPCHK(ctx, hipMemcpyAsync(ctx->d_cams, d_cams, (size_t)B * HT_CAM * sizeof(float), hipMemcpyDeviceToDevice, s)); }      // segment.cam = the frame's camera
-		else if (mode != UPD_PASSES) ht_launch_segment(d_depth, ctx->d_frame_cams, fs->w, fs->h, 0xF, p.drangey, fs->segment_scale, ctx->d_seg_tiles, ctx->d_cams, B, s);
+		else if (mode != UPD_PASSES) ht_launch_segment(d_depth, ctx->d_frame_cams, fs->w, fs->h, 0xF, p.drangey, fs->segment_scale, ctx->d_seg_tiles, ctx->d_cams, B, s, fs->side);
 		u.img_cams = ctx->d_frame_cams;
 	}
 	if (u.d_start && fs)      // full-size frames re-seed the trackers with their own small kernels; for 64x64 tiles that, and the camera copy, ride on k_prepare (below)
@@ -290,6 +293,7 @@ static int update_inputs(ht_ctx *ctx, update_call &u)
 		{
 			const ht_prepare_extra pz = { nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, ctx->d_nflist };
 			if (fs->direct) { HIPCHK(ctx, hipMemsetAsync(ctx->d_nflist, 0, sizeof(int), s)); ht_launch_cnn_input(d_depth, ctx->d_cams, fs->w * fs->h, p.drangey, u.net->d_in, B, s); }
+			else if (mode != UPD_PASSES && fs->side != 64) { HIPCHK(ctx, hipMemsetAsync(ctx->d_nflist, 0, sizeof(int), s)); ht_launch_cnn_input(ctx->d_seg_tiles, ctx->d_cams, fs->side * fs->side, p.drangey, u.net->d_in, B, s); }      // the larger tile goes the direct path's way (handtrack.h:700)
 			else if (mode != UPD_PASSES) ht_launch_prepare(ctx->d_seg_tiles, ctx->d_cams, p.drangey, p.subsample_fraction, u.net->d_in, nullptr, nullptr, ctx->model.pts_cap, B, s, &pz);      // (the caller's part of the overlapped update has no segment and no net)
 			ht_launch_prepare_frame(d_depth, u.img_cams, fs->w, fs->h, p.drangey, p.subsample_fraction, ctx->d_pts, ctx->d_npts, ctx->d_overflow, ctx->model.pts_cap, B, s);
 		}
@@ -442,7 +446,7 @@ static void update_passes(ht_ctx *ctx, const update_call &u)      // the main-th
 static int run_update_(ht_ctx *ctx, update_call &u)
 {
 	const ht_params &p = ctx->par; hipStream_t s = u.s;
-	u.net = ht_net_of(ctx, u.fs && u.fs->direct ? u.fs->direct : 64);      // a frame that is its own segment goes to the net of its size, everything else to the tiles' (the entry points have checked the side)
+	u.net = ht_net_of(ctx, u.fs ? (u.fs->direct ? u.fs->direct : u.fs->side) : 64);      // a frame that is its own segment goes to the net of its size, a segmented one to the net of its tile side, tiles to theirs (the entry points have checked the side)
 	if (u.mode != UPD_PASSES && !u.net->have) { ctx->err = u.net->missing; return HT_ERR_STATE; }      // (no net in the caller's part of the overlapped update)
 	{ const int r = update_inputs(ctx, u); if (r) return r; }
 	if (u.mode == UPD_PASSES) { update_planes(ctx, u, s); update_passes(ctx, u); return HT_OK; }
@@ -566,7 +570,7 @@ static int finish_sync(ht_ctx *ctx, int B, hipStream_t s, float *poses_out, floa
 static int update_sync(ht_ctx *ctx, const uint16_t *depth, const float *cams, const frame_src &fs, int mode, int B, float *poses_out, int *accepted_out, float *cnn_out, const char *frames_entry)
 {
 	hipStream_t s = ctx->stream;
-	const bool tile = fs.w == 64 && fs.h == 64;
+	const bool tile = fs.w == 64 && fs.h == 64 && fs.side == 64;      // (a 64x64 frame is segmented like any other when the tile side is 128)
 	const uint16_t *d_in; const float *d_cin;
 	int r = stage_frames(ctx, depth, cams, fs.w, fs.h, B, s, &d_in, &d_cin);
 	if (!r) r = run_update(ctx, d_in, d_cin, nullptr, B, ctx->d_poses_out, nullptr, s, tile ? nullptr : &fs, mode);
@@ -650,6 +654,40 @@ extern "C" int ht_update_frames_sync(ht_ctx *ctx, const uint16_t *depth, const f
 	if (!frames_args_ok(ctx, w, h)) return HT_ERR_ARG;
 	const frame_src fs = { w, h, segment_scale, 0 };
 	return update_sync(ctx, depth, cams, fs, UPD_FULL, B, poses_out, nullptr, cnn_out, "ht_update_frames");
+}
+
+// HandTracker::update (handtrack.h:693-785) as ht_update_frames_* states it, on frames up to 640x480 and for either net: HandSegmentVR (:280-344) cuts the segment at
+// `side` (dstcam :338-340 is the only place the side enters), the net is the one of that input size, the decode camera camsub(segment.cam, side / 16) (:218-241).
+// Everything behind the net takes the segment's pose, which does not depend on the side.  Checked completely before anything is uploaded, grown or launched.
+static int frames_sized_args_ok(ht_ctx *ctx, int side, int w, int h)
+{
+	const ht_net *net = ht_net_of(ctx, side);
+	if (!net) { ctx->err = "ht_update_frames_sized: " + ctx->err; return HT_ERR_ARG; }
+	if (!(w == side && h == side) && !ht_segment_supported_sized(w, h, side)) { ctx->err = "ht_update_frames_sized: frame size must be a multiple of 4, at least 8x8 and at most 640x480 pixels (19200 quarter-size pixels)"; return HT_ERR_ARG; }
+	if (!net->have) { ctx->err = net->missing; return HT_ERR_STATE; }
+	const ht_params &p = ctx->par;      // the cloud a frame can carry, as update_inputs counts it
+	const long long npx = (long long)w * h, fr = p.subsample_fraction > 0 ? p.subsample_fraction : 1, n = p.subsample_voxel ? npx : (npx + fr - 1) / fr;
+	if (n > HT_POINTS_LIMIT) { ctx->err = "ht_update_frames_sized: these frames can carry " + std::to_string(n) + " points each, the per-point arrays hold at most 76800 (ht_reserve_points): raise subsample_fraction, and leave the voxel rule off"; return HT_ERR_ARG; }
+	return HT_OK;
+}
+extern "C" int ht_update_frames_sized_dev(ht_ctx *ctx, int side, const uint16_t *d_depth, const float *d_cams, int w, int h, float segment_scale, const float *d_start_poses, int B, float *d_poses_out, void *stream)
+{
+	CHECK_READY(ctx); CHECK_MODEL(ctx); CHECK_BATCH(ctx, B);
+	if (!d_depth || !d_cams || !d_poses_out) return HT_ERR_ARG;
+	{ const int r = frames_sized_args_ok(ctx, side, w, h); if (r) return r; }
+	if (w == side && h == side) return ht_update_direct_dev(ctx, d_depth, d_cams, side, d_start_poses, B, d_poses_out, stream);      // handtrack.h:283-284: the frame is its own segment (with that call's alignment rule)
+	hipStream_t s = ht_user_stream(ctx, stream);
+	const frame_src fs = { w, h, segment_scale, 0, side };      // (the input transform of the larger tile reads the context's own tile buffer: no alignment rule for d_depth)
+	return update_dev_end(ctx, run_update(ctx, d_depth, d_cams, d_start_poses, B, d_poses_out, nullptr, s, &fs));
+}
+extern "C" int ht_update_frames_sized_sync(ht_ctx *ctx, int side, const uint16_t *depth, const float *cams, int w, int h, float segment_scale, int B, float *poses_out, float *cnn_out)
+{
+	CHECK_READY(ctx); CHECK_MODEL(ctx); CHECK_BATCH(ctx, B);
+	if (!depth || !cams || !poses_out) return HT_ERR_ARG;
+	{ const int r = frames_sized_args_ok(ctx, side, w, h); if (r) return r; }
+	if (w == side && h == side) return ht_update_direct_sync(ctx, depth, cams, side, B, poses_out, cnn_out);
+	const frame_src fs = { w, h, segment_scale, 0, side };
+	return update_sync(ctx, depth, cams, fs, UPD_FULL, B, poses_out, nullptr, cnn_out, "ht_update_frames_sized");
 }
 
 // BASELINE configs[4] end to end (SURVEY 8d "config 5 (i)-(iii)"): HandTracker::update on side x side frames that are their own segment, evaluated by the net of
@@ -1015,33 +1053,64 @@ extern "C" int ht_debug_contact_stats(ht_ctx *ctx, int B, float *out, int reset)
 }
 
 // ------------------------------------------------------------------------------------------------- segmentation (before the tracker)
+// One implementation for both forms: `sized` = the *_sized entry points (either tile side, frames up to 640x480), otherwise the unsized ones with their own limit and message.
+static int segment_dev(ht_ctx *ctx, bool sized, int side, const uint16_t *d_depth, const float *d_cams, int w, int h, int B, int entry_options, float wrange_hi, float diam,
+                       uint16_t *d_tiles, float *d_cams_out, void *stream)
+{
+	if (!d_depth || !d_cams || !d_tiles || !d_cams_out || B < 1) return HT_ERR_ARG;
+	if (side != 64 && side != 128) { ctx->err = "ht_segment_vr_sized: the tile side must be 64 or 128"; return HT_ERR_ARG; }
+	hipStream_t s = ht_user_stream(ctx, stream);
+	if (w == side && h == side)      // handtrack.h:283-284: a frame of the net's own size is returned as it is
+	{
+		HIPCHK(ctx, hipMemcpyAsync(d_tiles, d_depth, (size_t)B * side * side * sizeof(uint16_t), hipMemcpyDeviceToDevice, s));
+		HIPCHK(ctx, hipMemcpyAsync(d_cams_out, d_cams, (size_t)B * HT_CAM * sizeof(float), hipMemcpyDeviceToDevice, s));
+		return HT_OK;
+	}
+	if (!sized && !ht_segment_supported(w, h)) { ctx->err = "ht_segment_vr: frame size must be a multiple of 4 and at most 320x240 pixels"; return HT_ERR_ARG; }
+	if (sized && !ht_segment_supported_sized(w, h, side)) { ctx->err = "ht_segment_vr_sized: frame size must be a multiple of 4, at least 8x8 and at most 640x480 pixels (19200 quarter-size pixels)"; return HT_ERR_ARG; }
+	ht_launch_segment(d_depth, d_cams, w, h, entry_options, wrange_hi, diam, d_tiles, d_cams_out, B, s, side);
+	HIPCHK(ctx, hipGetLastError());
+	return HT_OK;
+}
+static int segment_host(ht_ctx *ctx, bool sized, int side, const uint16_t *depth, const float *cams, int w, int h, int B, int entry_options, float wrange_hi, float diam, uint16_t *tiles, float *cams_out)
+{
+	if (!depth || !cams || !tiles || !cams_out || B < 1 || w < 1 || h < 1) return HT_ERR_ARG;
+	if (sized && !(w == side && h == side) && !ht_segment_supported_sized(w, h, side)) return segment_dev(ctx, true, side, depth, cams, w, h, B, entry_options, wrange_hi, diam, tiles, cams_out, nullptr);      // refused before the staging buffer grows
+	const size_t n = (size_t)B;      // staged through one device buffer of its own (ht_staged_call; no tracker slot: B is not bounded by max_batch)
+	ht_seg seg[4] = { { (void *)depth, n * w * h * sizeof(uint16_t), false }, { (void *)cams, n * HT_CAM * sizeof(float), false }, { tiles, n * side * side * sizeof(uint16_t), true }, { cams_out, n * HT_CAM * sizeof(float), true } };
+	return ht_staged_call(ctx, &ctx->d_segment, &ctx->segment_cap, seg, 4, [&](hipStream_t s)
+	                      { return segment_dev(ctx, sized, side, (const uint16_t *)seg[0].dev, (const float *)seg[1].dev, w, h, B, entry_options, wrange_hi, diam, (uint16_t *)seg[2].dev, (float *)seg[3].dev, s); });
+}
 extern "C" int ht_segment_vr_dev(ht_ctx *ctx, const uint16_t *d_depth, const float *d_cams, int w, int h, int B, int entry_options, float wrange_lo, float wrange_hi, float diam,
                                  uint16_t *d_tiles, float *d_cams_out, void *stream)
 {
 	CHECK_READY(ctx);
 	(void)wrange_lo;      // the reference's lower bound is commented out (handtrack.h:288)
-	if (!d_depth || !d_cams || !d_tiles || !d_cams_out || B < 1) return HT_ERR_ARG;
-	hipStream_t s = ht_user_stream(ctx, stream);
-	if (w == 64 && h == 64)      // handtrack.h:283-284: a 64x64 frame is returned as it is
-	{
-		HIPCHK(ctx, hipMemcpyAsync(d_tiles, d_depth, (size_t)B * 4096 * sizeof(uint16_t), hipMemcpyDeviceToDevice, s));
-		HIPCHK(ctx, hipMemcpyAsync(d_cams_out, d_cams, (size_t)B * HT_CAM * sizeof(float), hipMemcpyDeviceToDevice, s));
-		return HT_OK;
-	}
-	if (!ht_segment_supported(w, h)) { ctx->err = "ht_segment_vr: frame size must be a multiple of 4 and at most 320x240 pixels"; return HT_ERR_ARG; }
-	ht_launch_segment(d_depth, d_cams, w, h, entry_options, wrange_hi, diam, d_tiles, d_cams_out, B, s);
-	HIPCHK(ctx, hipGetLastError());
-	return HT_OK;
+	return segment_dev(ctx, false, 64, d_depth, d_cams, w, h, B, entry_options, wrange_hi, diam, d_tiles, d_cams_out, stream);
 }
 extern "C" int ht_segment_vr(ht_ctx *ctx, const uint16_t *depth, const float *cams, int w, int h, int B, int entry_options, float wrange_lo, float wrange_hi, float diam,
                              uint16_t *tiles, float *cams_out)
 {
 	CHECK_READY(ctx);
-	if (!depth || !cams || !tiles || !cams_out || B < 1 || w < 1 || h < 1) return HT_ERR_ARG;
-	const size_t n = (size_t)B;      // staged through one device buffer of its own (ht_staged_call; no tracker slot: B is not bounded by max_batch)
-	ht_seg seg[4] = { { (void *)depth, n * w * h * sizeof(uint16_t), false }, { (void *)cams, n * HT_CAM * sizeof(float), false }, { tiles, n * 4096 * sizeof(uint16_t), true }, { cams_out, n * HT_CAM * sizeof(float), true } };
-	return ht_staged_call(ctx, &ctx->d_segment, &ctx->segment_cap, seg, 4, [&](hipStream_t s)
-	                      { return ht_segment_vr_dev(ctx, (const uint16_t *)seg[0].dev, (const float *)seg[1].dev, w, h, B, entry_options, wrange_lo, wrange_hi, diam, (uint16_t *)seg[2].dev, (float *)seg[3].dev, s); });
+	(void)wrange_lo;
+	return segment_host(ctx, false, 64, depth, cams, w, h, B, entry_options, wrange_hi, diam, tiles, cams_out);
+}
+// HandSegmentVR (handtrack.h:280-344) with the tile side of dstcam (:338-340) a parameter, on frames up to 640x480: the one place the size rule lives
+extern "C" int ht_segment_vr_supported(int w, int h, int side) { return ht_segment_supported_sized(w, h, side) || ((side == 64 || side == 128) && w == side && h == side) ? HT_OK : HT_ERR_ARG; }
+extern "C" int ht_segment_vr_sized_dev(ht_ctx *ctx, int side, const uint16_t *d_depth, const float *d_cams, int w, int h, int B, int entry_options, float wrange_lo, float wrange_hi, float diam,
+                                       uint16_t *d_tiles, float *d_cams_out, void *stream)
+{
+	CHECK_READY(ctx);
+	(void)wrange_lo;
+	return segment_dev(ctx, true, side, d_depth, d_cams, w, h, B, entry_options, wrange_hi, diam, d_tiles, d_cams_out, stream);
+}
+extern "C" int ht_segment_vr_sized(ht_ctx *ctx, int side, const uint16_t *depth, const float *cams, int w, int h, int B, int entry_options, float wrange_lo, float wrange_hi, float diam,
+                                   uint16_t *tiles, float *cams_out)
+{
+	CHECK_READY(ctx);
+	(void)wrange_lo;
+	if (side != 64 && side != 128) { ctx->err = "ht_segment_vr_sized: the tile side must be 64 or 128"; return HT_ERR_ARG; }
+	return segment_host(ctx, true, side, depth, cams, w, h, B, entry_options, wrange_hi, diam, tiles, cams_out);
 }
 
 // ------------------------------------------------------------------------------------------------- caller-built constraint rows

@@ -29,7 +29,7 @@ SYMBOLS = (
     "ht_expected_cnn_batch", "ht_expected_cnn_dev", "ht_cnn_input_dev", "ht_cnn_train_dev", "ht_cnn_train_batch_dev", "ht_cnn_train_batch", "ht_debug_train_batch_buffers",
     "ht_cnn_train_batch_sized_dev", "ht_cnn_train_batch_sized", "ht_cnn_get_weights_sized", "ht_debug_train_batch_buffers_sized", "ht_cnn_input_sized_dev",
     "ht_model_open", "ht_model_close", "ht_model_error", "ht_model_counts", "ht_model_body", "ht_model_body_mesh", "ht_model_body_sdmesh", "ht_model_hitcheck", "ht_model_hitcheck_mesh", "ht_model_render_mesh", "ht_model_scale", "ht_render_mesh_depth", "ht_render_mesh_depth_dev",
-    "ht_tracker_reset", "ht_get_state", "ht_set_state", "ht_get_tracker_flags", "ht_set_tracker_flags", "ht_update_sync", "ht_update_dev", "ht_update_frames_sync", "ht_update_frames_dev", "ht_update_direct_sync", "ht_update_direct_dev", "ht_update_cnn_model_sync", "ht_get_cnn_results", "ht_get_cnn_layers", "ht_get_cnn_layers_sized", "ht_frames_overflow", "ht_reserve_points", "ht_point_capacity", "ht_capacity_events", "ht_segment_vr", "ht_segment_vr_dev", "ht_render_depth", "ht_render_depth_dev", "ht_slowfit", "ht_set_points", "ht_fit_rows", "ht_physics_update",
+    "ht_tracker_reset", "ht_get_state", "ht_set_state", "ht_get_tracker_flags", "ht_set_tracker_flags", "ht_update_sync", "ht_update_dev", "ht_update_frames_sync", "ht_update_frames_dev", "ht_update_direct_sync", "ht_update_direct_dev", "ht_update_cnn_model_sync", "ht_get_cnn_results", "ht_get_cnn_layers", "ht_get_cnn_layers_sized", "ht_frames_overflow", "ht_reserve_points", "ht_point_capacity", "ht_capacity_events", "ht_segment_vr", "ht_segment_vr_dev", "ht_segment_vr_supported", "ht_segment_vr_sized", "ht_segment_vr_sized_dev", "ht_update_frames_sized_sync", "ht_update_frames_sized_dev", "ht_render_depth", "ht_render_depth_dev", "ht_slowfit", "ht_set_points", "ht_fit_rows", "ht_physics_update",
     "ht_stage_prepare", "ht_stage_decode", "ht_stage_fit_error", "ht_stage_cloud_rows", "ht_stage_contacts", "ht_stage_fit",
     "ht_stage_multistep", "ht_stage_multistep_range", "ht_stage_scratch_unibody", "ht_stage_chamber", "ht_profile_enable", "ht_profile_read", "ht_debug_solve_stats", "ht_debug_contact_stats", "ht_debug_solver_build", "ht_debug_reset_flags", "ht_debug_reset_organisation", "ht_update_passes_sync", "ht_job_start", "ht_job_poll", "ht_job_wait", "ht_job_collect", "ht_debug_contact_kernel", "ht_debug_contact_order", "ht_debug_rank_desc", "ht_contact_capacity", "ht_debug_solve_tables", "ht_debug_solve_tables_header", "ht_debug_train_buffers",
     "ht_sensor_out_dims", "ht_sensor_filter", "ht_sensor_filter_dev", "ht_sensor_background", "ht_sensor_background_dev",
@@ -56,6 +56,11 @@ _lib = None
 
 def lib_path():
     return _build.LIB
+
+
+def segment_vr_supported(w, h, side):
+    """Whether the sized segmentation and update calls take w x h frames at tile side `side` (ht_segment_vr_supported; no context, no GPU)."""
+    return load().ht_segment_vr_supported(int(w), int(h), int(side)) == 0
 
 
 def load(build_if_missing=True):
@@ -133,7 +138,12 @@ def load(build_if_missing=True):
     L.ht_physics_update.argtypes = [vp, C.c_int, C.c_int, fp, C.c_int, ip, fp, C.c_int, ip]
     L.ht_segment_vr.argtypes = [vp, C.POINTER(C.c_uint16), fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, C.POINTER(C.c_uint16), fp]
     L.ht_segment_vr_dev.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, vp, vp, vp]
-    L.ht_render_depth.argtypes = [vp, fp, fp, C.c_int, C.c_int, C.c_float, C.c_int, u16p, C.POINTER(C.c_int8)]
+    L.ht_segment_vr_supported.argtypes = [C.c_int, C.c_int, C.c_int]
+    L.ht_segment_vr_sized.argtypes = [vp, C.c_int] + L.ht_segment_vr.argtypes[1:]
+    L.ht_segment_vr_sized_dev.argtypes = [vp, C.c_int] + L.ht_segment_vr_dev.argtypes[1:]
+    L.ht_update_frames_sized_sync.argtypes = [vp, C.c_int] + L.ht_update_frames_sync.argtypes[1:]
+    L.ht_update_frames_sized_dev.argtypes = [vp, C.c_int] + L.ht_update_frames_dev.argtypes[1:]
+    L.ht_render_depth.argtypes =[vp, fp, fp, C.c_int, C.c_int, C.c_float, C.c_int, u16p, C.POINTER(C.c_int8)]
     L.ht_render_depth_dev.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_float, C.c_int, vp, vp, vp]
     L.ht_sensor_out_dims.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, ip, ip]
     L.ht_sensor_filter.argtypes = [vp, C.c_int, u16p, C.POINTER(C.c_uint8), fp, C.c_int, C.c_int, C.c_int, C.c_int, u16p, u16p, fp]
@@ -312,6 +322,18 @@ class Context:
 
     def update_frames_dev(self, d_depth, d_cams, w, h, segment_scale, d_start, B, d_poses_out, stream):
         self._chk(self.L.ht_update_frames_dev(self.h, d_depth, d_cams, int(w), int(h), float(segment_scale), d_start, B, d_poses_out, stream))
+
+    def update_frames_sized_sync(self, depth, cams, side=128, segment_scale=0.17, want_cnn=False):
+        """HandTracker::update on frames up to 640x480 with the segment cut at `side` for the net of that input size (ht_update_frames_sized_sync): depth u16[B,h,w], cams [B,12]."""
+        depth = _c(depth, np.uint16); B, h, w = depth.shape
+        cams = _c(cams, np.float32).reshape(B, CAM)
+        poses = np.empty((B, self.nb, POSE), np.float32)
+        cnn = np.empty((B, CNN_OUT), np.float32) if want_cnn else None
+        self._chk(self.L.ht_update_frames_sized_sync(self.h, int(side), depth.ctypes.data_as(C.POINTER(C.c_uint16)), _f(cams), w, h, float(segment_scale), B, _f(poses), _f(cnn) if want_cnn else None))
+        return (poses, cnn) if want_cnn else poses
+
+    def update_frames_sized_dev(self, side, d_depth, d_cams, w, h, segment_scale, d_start, B, d_poses_out, stream):
+        self._chk(self.L.ht_update_frames_sized_dev(self.h, int(side), d_depth, d_cams, int(w), int(h), float(segment_scale), d_start, B, d_poses_out, stream))
 
     def update_direct_sync(self, depth, cams, side=128, want_cnn=False):
         """BASELINE configs[4] end to end: depth u16[B,side,side] frames that are their own segment, the net of that input size (ht_update_direct_sync)."""
@@ -563,6 +585,20 @@ class Context:
         self._chk(self.L.ht_segment_vr(self.h, depth.ctypes.data_as(C.POINTER(C.c_uint16)), _f(cams), w, h, B, int(entry_options), float(wrange[0]), float(wrange[1]), float(diam),
                                        tiles.ctypes.data_as(C.POINTER(C.c_uint16)), _f(co)))
         return tiles, co
+
+    def segment_vr_sized(self, depth, cams, side=128, entry_options=0xF, wrange=(0.1, 0.65), diam=0.17):
+        """HandSegmentVR with the tile side a parameter, frames up to 640x480 (ht_segment_vr_sized): depth u16[B,h,w], cams [B,12] -> (tiles u16[B,side,side], cams [B,12])."""
+        depth = _c(depth, np.uint16); B, h, w = depth.shape
+        cams = _c(cams, np.float32).reshape(B, CAM)
+        if side not in (64, 128):      # the output cannot be shaped for any other side: the library's own refusal, with nothing to write into
+            self._chk(self.L.ht_segment_vr_sized(self.h, int(side), depth.ctypes.data_as(C.POINTER(C.c_uint16)), _f(cams), w, h, B, int(entry_options), float(wrange[0]), float(wrange[1]), float(diam), None, None))
+        tiles = np.empty((B, side, side), np.uint16); co = np.empty((B, CAM), np.float32)
+        self._chk(self.L.ht_segment_vr_sized(self.h, int(side), depth.ctypes.data_as(C.POINTER(C.c_uint16)), _f(cams), w, h, B, int(entry_options), float(wrange[0]), float(wrange[1]), float(diam),
+                                             tiles.ctypes.data_as(C.POINTER(C.c_uint16)), _f(co)))
+        return tiles, co
+
+    def segment_vr_sized_dev(self, side, d_depth, d_cams, w, h, B, d_tiles, d_cams_out, stream=None, entry_options=0xF, wrange=(0.1, 0.65), diam=0.17):
+        self._chk(self.L.ht_segment_vr_sized_dev(self.h, int(side), d_depth, d_cams, int(w), int(h), int(B), int(entry_options), float(wrange[0]), float(wrange[1]), float(diam), d_tiles, d_cams_out, stream))
 
     def _render(self, entry, poses, cams, w, h, far, extra, want_body):
         """a renderer's synchronous entry: `extra` are its arguments between far and B"""

@@ -163,6 +163,15 @@ int ht_update_frames_dev(ht_ctx *ctx, const uint16_t *d_depth, const float *d_ca
  */
 int ht_update_direct_sync(ht_ctx *ctx, const uint16_t *depth, const float *cams, int side, int B, float *poses_out, float *cnn_out);
 int ht_update_direct_dev(ht_ctx *ctx, const uint16_t *d_depth, const float *d_cams, int side, const float *d_start_poses, int B, float *d_poses_out, void *stream);
+/* ht_update_frames_sized_*  HandTracker::update (handtrack.h:693-785) as ht_update_frames_* states it, for either net and frames up to 640x480
+ *                     (ht_segment_vr_supported): HandSegmentVR (:697-698, :280-344) cuts the segment at `side` (ht_segment_vr_sized), the net is the one of
+ *                     that input size, and the heat maps are decoded with camsub(segment.cam, side / 16) (:218-241).  The point cloud and FitError stay on the
+ *                     full frame (:703-704, :751); PoseFromScratch, UnibodyFit and MultiStepSim take segment.cam.pose (:708-713), which does not depend on the
+ *                     side.  side 64 on a frame ht_update_frames_* takes is that call; a side x side frame is ht_update_direct_* (with its alignment rule).
+ *                     HT_ERR_STATE without the weights of that net.  HT_ERR_ARG, before anything is uploaded or launched, for a call whose frames can
+ *                     carry more than HT_POINTS_LIMIT points (w*h / subsample_fraction, or w*h with the voxel rule: 640x480 needs subsample_fraction >= 4). */
+int ht_update_frames_sized_sync(ht_ctx *ctx, int side, const uint16_t *depth, const float *cams, int w, int h, float segment_scale, int B, float *poses_out, float *cnn_out);
+int ht_update_frames_sized_dev(ht_ctx *ctx, int side, const uint16_t *d_depth, const float *d_cams, int w, int h, float segment_scale, const float *d_start_poses, int B, float *d_poses_out, void *stream);
 int ht_frames_overflow(ht_ctx *ctx, int *frames_over);
 int ht_reserve_points(ht_ctx *ctx, int points);
 int ht_point_capacity(ht_ctx *ctx, int *points);
@@ -342,6 +351,20 @@ int ht_segment_vr(ht_ctx *ctx, const uint16_t *depth, const float *cams, int w, 
                   uint16_t *tiles, float *cams_out);
 int ht_segment_vr_dev(ht_ctx *ctx, const uint16_t *d_depth, const float *d_cams, int w, int h, int B, int entry_options, float wrange_lo, float wrange_hi, float diam,
                       uint16_t *d_tiles, float *d_cams_out, void *stream);
+/* ht_segment_vr_supported  the size rule of the sized calls, in one place and without a context: HT_OK for side 64 or 128 and a frame with w, h >= 8, both
+ *                     multiples of 4, and (w/4)*(h/4) <= 19200 (640x480, the SR300's native frame, or any other shape with that many quarter-size
+ *                     pixels: the two DownSampleMin of handtrack.h:285-286 stay in on-chip memory), or a side x side frame; HT_ERR_ARG otherwise.
+ * ht_segment_vr_sized      HandSegmentVR (handtrack.h:280-344) with the side of its 64x64 tile a parameter: dstcam (:338-340) becomes
+ *                     ({side,side}, avgdepth*side/diam, {side/2,side/2}) and SampleD (:342, misc_image.h:154-162) runs over side x side pixels; nothing else
+ *                     of the function sees the side.  tiles [B][side*side]; the segment camera of side 128 is that of side 64 with focal doubled and
+ *                     principal (64,64), bit for bit.  A side x side frame is passed through (:283-284 for the net's own size).  Needs no weights.
+ *                     side 64 runs the very kernel of ht_segment_vr and returns its bits.  HT_ERR_ARG for what ht_segment_vr_supported refuses.
+ * ht_segment_vr_sized_dev  the same on device buffers, asynchronous on `stream`. */
+int ht_segment_vr_supported(int w, int h, int side);
+int ht_segment_vr_sized(ht_ctx *ctx, int side, const uint16_t *depth, const float *cams, int w, int h, int B, int entry_options, float wrange_lo, float wrange_hi, float diam,
+                        uint16_t *tiles, float *cams_out);
+int ht_segment_vr_sized_dev(ht_ctx *ctx, int side, const uint16_t *d_depth, const float *d_cams, int w, int h, int B, int entry_options, float wrange_lo, float wrange_hi, float diam,
+                            uint16_t *d_tiles, float *d_cams_out, void *stream);
 
 /* ---- synthetic depth frames (an addition: the reference renders its fake hand on the host) ---------------------------
  * ht_render_depth     replaces  the software_rasterizer branch of synthetic-tracker.cpp:182, FakeDepth (:69-76), for B frames: pixel (x, y) of
@@ -382,7 +405,7 @@ int ht_render_mesh_depth_dev(ht_ctx *ctx, const float *d_poses, const float *d_c
  *                       sequential loop (csrc/ht_sensor.hip has the decomposition).
  *                       depth [B][h*w], ir [B][h*w] (DS4: required; Ivy: ignored), cams [B][12], background [B][h*w] (DS4 only, caller-owned, may be NULL)
  *                       -> depth_out [B][h_out*w_out], cams_out [B][12]: an ordinary input of ht_update_frames_* and ht_segment_vr*, which keep their own
- *                       checks.  B is not bounded by max_batch (no tracker slot; the host form stages through a device buffer it grows on demand); B = 0
+ *                       checks (a 640x480 frame: the *_sized forms).  B is not bounded by max_batch (no tracker slot; the host form stages through a device buffer it grows on demand); B = 0
  *                       does nothing.  HT_ERR_ARG, checked before anything is launched or grown: a NULL required buffer; w or h < 1 or > 4096;
  *                       max_width < 1; Ivy with w or h not divisible by 2^k (the reference reads past the image there); DS4 with w > max_width (the
  *                       reference indexes the full-size frame with an IR image it has already halved, dcam.h:170-171,184; R200 streams 320x240); a

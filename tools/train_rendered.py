@@ -17,7 +17,11 @@ Rates: closed-loop samples/s against ht_cnn_train_dev steps/s on a resident pool
 --side 128 trains the 128x128-input net instead (BASELINE configs[4]): the 26-bone hand rendered straight at 128x128 by the camera of that configuration's frames (focal 163,
 principal 64, depth scale 0.001, identity pose), no segmentation step; poses interpolated between consecutive start poses of bench_data/frames5_256.npz, every 16th held out;
 inputs from ht_cnn_input_sized_dev, labels with HT_LABELS_SIDE128, steps of --minibatch samples through ht_cnn_train_batch_sized_dev.  Reported: the held-out MSE (the
-16 held-out poses, rendered the same way) before and after, and the closed-loop samples/s against the training call alone."""
+16 held-out poses, rendered the same way) before and after, and the closed-loop samples/s against the training call alone.
+
+--side 128 --frame 640x480 trains that net on what a segmenter hands it: the 17-bone hand of bench_data/frames1024.npz rendered at 640x480 by the SR300's camera (focal 610,
+principal (320, 240)), ht_segment_vr_sized_dev(128, 0xF, {0.1, 0.70}), ht_cnn_input_sized_dev, labels with HT_LABELS_SEGMENT_FRAME | HT_LABELS_SIDE128,
+ht_cnn_train_batch_sized_dev.  Held out: every 16th ground truth, rendered and segmented the same way."""
 import argparse
 import json
 import os
@@ -38,6 +42,7 @@ HOLD = 16
 M17 = os.path.join(ROOT, "hand_tracking_samples_amd", "assets", "model_hand17.htfx")
 M26 = os.path.join(ROOT, "hand_tracking_samples_amd", "assets", "model_hand26.htfx")
 CAM128 = np.array([163, 163, 64, 64, 0.001, 0, 0, 0, 0, 0, 0, 1], np.float32)
+VGA_CAM = np.array([610, 610, 320, 240, 0.001, 0, 0, 0, 0, 0, 0, 1], np.float32)
 QVGA_CAM = np.array([305, 305, 160, 120, 0.001, 0, 0, 0, 0, 0, 0, 1], np.float32)
 
 
@@ -73,18 +78,25 @@ def held_out(ctx, d):
 def main128(a):
     """the loop for the 128x128-input net: render at 128x128, tile inputs, labels at camsub(cam, 8), mini-batch steps"""
     dev = torch.device("cuda:0")
-    d = np.load(os.path.join(ROOT, "bench_data", "frames5_256.npz"))
-    gt = d["startpose"].astype(np.float32); pairs = train_pairs(len(gt)); nb = gt.shape[1]
+    seg = a.frame is not None      # full-size frames, segmented to the 128x128 tile
+    fw, fh = a.frame if seg else (128, 128)
+    d = np.load(os.path.join(ROOT, "bench_data", "frames1024.npz" if seg else "frames5_256.npz"))
+    gt = d["gtpose" if seg else "startpose"].astype(np.float32); pairs = train_pairs(len(gt)); nb = gt.shape[1]
+    fcam = VGA_CAM.copy() if seg else CAM128
+    if seg:
+        fcam[:4] *= fw / 640.0
     B = a.batch
     rng = np.random.default_rng(a.seed)
-    ctx = native.Context(M26, 64)
+    ctx = native.Context(M17 if seg else M26, 64)
     ctx.load_weights128(W.make_cnnb128(a.seed, 1.0))
     s = torch.cuda.Stream(device=dev)
-    cams = torch.from_numpy(np.tile(CAM128, (B, 1))).to(dev)
+    cams = torch.from_numpy(np.tile(fcam, (B, 1))).to(dev)
     tp = torch.empty((B, nb, 7), device=dev)
-    depth = torch.empty((B, 128, 128), dtype=torch.int16, device=dev)
+    depth = torch.empty((B, fh, fw), dtype=torch.int16, device=dev)
+    tiles = torch.empty((B, 128, 128), dtype=torch.int16, device=dev) if seg else depth
+    tcams = torch.empty((B, 12), device=dev) if seg else cams
     x = torch.empty((B, 16384), device=dev); lab = torch.empty((B, 2304), device=dev); mse = torch.empty(B, device=dev)
-    ev = [torch.cuda.Event(enable_timing=True) for _ in range(5)]
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(6)]
 
     def train(order, d_mse=None):
         ctx.cnn_train_batch_dev(x.data_ptr(), lab.data_ptr(), B, a.minibatch, order=order, alpha=a.lr, d_mse=d_mse, stream=s.cuda_stream, side=128)
@@ -93,22 +105,30 @@ def main128(a):
         with torch.cuda.stream(s):
             tp.copy_(torch.from_numpy(poses))
             if timed: ev[0].record(s)
-            ctx.render_depth_dev(tp.data_ptr(), cams.data_ptr(), 128, 128, 4.0, B, depth.data_ptr(), None, s.cuda_stream)
+            ctx.render_depth_dev(tp.data_ptr(), cams.data_ptr(), fw, fh, 4.0, B, depth.data_ptr(), None, s.cuda_stream)
             if timed: ev[1].record(s)
-            ctx.cnn_input_dev(depth.data_ptr(), cams.data_ptr(), B, x.data_ptr(), s.cuda_stream, side=128)
+            if seg:
+                ctx.segment_vr_sized_dev(128, depth.data_ptr(), cams.data_ptr(), fw, fh, B, tiles.data_ptr(), tcams.data_ptr(), s.cuda_stream, 0xF, (0.1, 0.70), 0.17)
             if timed: ev[2].record(s)
-            ctx.expected_cnn_dev(tp.data_ptr(), cams.data_ptr(), B, lab.data_ptr(), stream=s.cuda_stream, side=128)
+            ctx.cnn_input_dev(tiles.data_ptr(), tcams.data_ptr(), B, x.data_ptr(), s.cuda_stream, side=128)
             if timed: ev[3].record(s)
-            train(order, mse.data_ptr())
+            ctx.expected_cnn_dev(tp.data_ptr(), tcams.data_ptr(), B, lab.data_ptr(), segment_frame=seg, stream=s.cuda_stream, side=128)
             if timed: ev[4].record(s)
+            train(order, mse.data_ptr())
+            if timed: ev[5].record(s)
 
     # held out: every 16th start pose, rendered by the same camera (host forms), labels from the host's GatherHandExpectedCNN on the halved camera
     fr = np.arange(0, len(gt), HOLD)
-    hd = ctx.render_depth(gt[fr], np.tile(CAM128, (len(fr), 1)), 128, 128, 4.0)
-    hd = (hd[0] if isinstance(hd, tuple) else hd).reshape(len(fr), -1)
-    hx = np.clip(1.0 - (hd.astype(np.float32) * np.float32(CAM128[4]) - np.float32(0.1)) / (np.float32(ctx.params.drangey) - np.float32(0.1)), 0.0, 1.0).astype(np.float32)
-    half = CAM128.copy(); half[:4] *= 0.5
-    ht = np.stack([native.expected_cnn(gt[i], half) for i in fr])
+    hd = ctx.render_depth(gt[fr], np.tile(fcam, (len(fr), 1)), fw, fh, 4.0)
+    hd = hd[0] if isinstance(hd, tuple) else hd
+    if seg:      # the held-out frames go the same way: the device's segment and its camera, the labels of train-cnn's compress in that camera
+        hd, hcams = ctx.segment_vr_sized(hd.reshape(len(fr), fh, fw), np.tile(fcam, (len(fr), 1)), 128, 0xF, (0.1, 0.70), 0.17)
+        ht = ctx.expected_cnn_batch(gt[fr], hcams, segment_frame=True, side=128)[0]
+    else:
+        half = CAM128.copy(); half[:4] *= 0.5
+        ht = np.stack([native.expected_cnn(gt[i], half) for i in fr])
+    hd = hd.reshape(len(fr), -1)
+    hx = np.clip(1.0 - (hd.astype(np.float32) * np.float32(fcam[4]) - np.float32(0.1)) / (np.float32(ctx.params.drangey) - np.float32(0.1)), 0.0, 1.0).astype(np.float32)
 
     def held_out():
         return float(((ctx.cnn128_eval(hx) - ht) ** 2).mean())
@@ -116,13 +136,13 @@ def main128(a):
     mse0 = held_out()
     print("before: held-out mse %.3e on %d rendered poses" % (mse0, len(fr)), flush=True)
     curve = []
-    stage_ms = np.zeros(4)
+    stage_ms = np.zeros(5)
     t0 = time.perf_counter()
     for r in range(a.rounds):
         poses = draw(gt, pairs, B, rng); order = rng.permutation(B).astype(np.int32)
         round_(poses, order, timed=True)
         s.synchronize()
-        stage_ms += [ev[i].elapsed_time(ev[i + 1]) for i in range(4)]
+        stage_ms += [ev[i].elapsed_time(ev[i + 1]) for i in range(5)]
         if (r + 1) % 10 == 0 or r + 1 == a.rounds:
             rec = {"round": r + 1, "samples": (r + 1) * B, "train_mse": float(mse.mean().item()), "held_out_mse": held_out()}
             curve.append(rec)
@@ -149,10 +169,12 @@ def main128(a):
     bare_sps = B / (e0.elapsed_time(e1) / 1e3)
     mse1 = held_out()
     ctx.close()
-    out = {"what": "tools/train_rendered.py --side 128: %d rounds of %d frames of the 26-bone hand rendered at 128x128 (render, input, HT_LABELS_SIDE128 labels, steps of %d lr %g over a "
-                   "seeded permutation), seed 0x%X" % (a.rounds, B, a.minibatch, a.lr, a.seed),
+    what = "the 17-bone hand rendered at %dx%d (render, ht_segment_vr_sized_dev(128), input, HT_LABELS_SEGMENT_FRAME | HT_LABELS_SIDE128 labels" % (fw, fh) if seg else \
+        "the 26-bone hand rendered at 128x128 (render, input, HT_LABELS_SIDE128 labels"
+    out = {"what": "tools/train_rendered.py --side 128%s: %d rounds of %d frames of %s, steps of %d lr %g over a "
+                   "seeded permutation), seed 0x%X" % (" --frame %dx%d" % (fw, fh) if seg else "", a.rounds, B, what, a.minibatch, a.lr, a.seed),
            "side": 128, "rounds": a.rounds, "batch": B, "minibatch": a.minibatch, "lr": a.lr, "samples": a.rounds * B, "seconds": seconds,
-           "stage_ms_per_round": {"render": stage_ms[0], "cnn_input": stage_ms[1], "labels": stage_ms[2], "train": stage_ms[3]},
+           "stage_ms_per_round": {"render": stage_ms[0], "segment": stage_ms[1], "cnn_input": stage_ms[2], "labels": stage_ms[3], "train": stage_ms[4]},
            "closed_loop_samples_per_s": loop_sps, "bare_train_samples_per_s": bare_sps,
            "held_out": {"frames": int(len(fr)), "mse_before": mse0, "mse_after": mse1}, "curve": curve}
     print(json.dumps({k: v for k, v in out.items() if k != "curve"}, indent=1))
@@ -170,10 +192,13 @@ def main():
     ap.add_argument("--lr", type=float, default=0.001, help="alpha of every step; a mini-batch step subtracts lr times the SUM of its samples' gradients")
     ap.add_argument("--json", default=None)
     ap.add_argument("--rate-steps", type=int, default=2048)
+    ap.add_argument("--frame", default=None, type=lambda v: tuple(int(x) for x in v.lower().split("x")), help="with --side 128: render full-size frames of this size (640x480) and segment them to the 128x128 tile")
     ap.add_argument("--mesh", action="store_true", help="render the training frames from the subdivision surface (ht_render_mesh_depth_dev, pixel offset 0, far 4) instead of the hulls")
     a = ap.parse_args()
     if a.minibatch < 1 or a.batch % a.minibatch:
         ap.error("--minibatch must divide --batch")
+    if a.frame is not None and (a.side != 128 or len(a.frame) != 2 or not native.segment_vr_supported(a.frame[0], a.frame[1], 128)):
+        ap.error("--frame needs --side 128 and a size ht_segment_vr_supported takes")
     if a.side == 128:
         return main128(a)
     dev = torch.device("cuda:0")
