@@ -151,6 +151,11 @@ static int load_model(ht_ctx *ctx, const char *path)
 	m.verts = dv; m.planes = dp; m.bodyc = dbc; m.jointc = djc;
 	ctx->h_verts = verts; ctx->h_planes = planes; ctx->d_verts_rw = dv; ctx->d_planes_rw = dp; ctx->d_bodyc_rw = dbc; ctx->d_jointc_rw = djc;
 	{ const int r2 = upload_padded_verts(ctx); if (r2) return r2; }
+	{   // the limits of the joint coordinates, with the host's sinf, once (ht_joints.hip)
+		std::vector<float> jl((size_t)nj * HT_JL, 0.0f);
+		ht_joint_limits(jointc.data(), nj, jl.data());
+		const int r2 = dev_upload(ctx, &ctx->d_jointl, jl); if (r2) return r2;
+	}
 	return ht_mesh_upload(ctx);
 }
 

@@ -124,6 +124,12 @@ static_assert(HT_MAXPTS == HT_MAX_POINTS, "public header and kernels disagree on
 #define HT_JC_RMIN 8
 #define HT_JC_RMAX 11
 #define HT_JC_FRAME 14
+// per-joint limits of the joint coordinates (ht_joints.hip: ht_joint_limits), 8 floats each: lo[3] hi[3] swapped unbounded-axes-as-bits
+#define HT_JL 8
+#define HT_JL_LO 0
+#define HT_JL_HI 3
+#define HT_JL_SWAPPED 6
+#define HT_JL_UNBOUNDED 7
 
 struct ht_model_dev
 {

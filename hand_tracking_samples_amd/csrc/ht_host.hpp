@@ -113,6 +113,8 @@ struct ht_ctx
 	// ht_render_mesh_depth: the subdivision meshes' corners [t][9] over all bodies (ht_scale rewrites them), the first triangle of every body, the device rows
 	// [t][4] float4 (corners and PolyPlane, ht_mesh_rows) and the farthest corner of every body's mesh from its centre of mass (ht_mesh_upload makes both)
 	std::vector<float> h_mesh_corners, mesh_rad; std::vector<int> mesh_off; float4 *d_mesh = nullptr;
+	float *d_jointl = nullptr;                                   // [nj][HT_JL] the limits of the joint coordinates, made once at model load beside jointc (ht_joint_limits; ht_scale leaves them)
+	char *d_joints = nullptr; size_t joints_cap = 0;             // ht_joint_coords', ht_joint_pose's and ht_sample_poses' staging (poses, roots, coordinates, gaps), grown to the largest call (dev_grow)
 };
 
 // The net of a side x side input; any other side is refused here, and only here

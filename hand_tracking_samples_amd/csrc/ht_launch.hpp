@@ -116,3 +116,9 @@ void ht_launch_fc_rowmajor(const float *A, const float *W, const float *bias, fl
 void ht_launch_train_batch_step(float *w, float *W2p, const float *inputs, const float *targets, const int *index, int n, float alpha, float *arena, int cap, float *mse_out, hipStream_t s, const ht_net_dims &d);
 size_t ht_train_batch_floats(int cap, const ht_net_dims &d);
 void ht_train_batch_views(float *arena, int cap, const float *view[7], size_t per[7], const ht_net_dims &d);
+// ht_joints.hip (host only): the limits table [nj][HT_JL] of a joint table [nj][HT_JC], its public form (lo / hi [nj][3], an unbounded axis as -inf / +inf; swapped [nj];
+// any may be null), and whether a top-down walk in model order places every body
+void ht_joint_limits(const float *jointc, int nj, float *table);
+void ht_joint_limits_public(const float *table, int nj, float *lo, float *hi, int *swapped);
+bool ht_joints_ordered(const float *jointc, int nb, int nj);
+bool ht_joints_hand_layout(const float *jointc, int nb, int nj);

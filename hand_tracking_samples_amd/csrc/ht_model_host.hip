@@ -10,6 +10,7 @@
 #include <vector>
 #include "ht_device.hpp"
 #include "ht_model_build.hpp"
+#include "ht_launch.hpp"
 
 struct ht_model
 {
@@ -19,6 +20,7 @@ struct ht_model
 	std::vector<std::vector<float>> sdverts;            // per body: [3 t][3] the subdivision surface's triangles corner by corner, in the bone's rig frame (GetMeshes(true), physmodel.h:258)
 	std::vector<std::vector<float>> sdrows;             // per body: [t][16] corners and PolyPlane of every sdverts triangle (ht_mesh_rows), what the mesh ray cast reads
 	std::vector<float> com, rest;                       // [nb][3], [nb][7]
+	std::vector<float> jointc;                          // [nj][HT_JC] the joint table as a context keeps it
 	std::string err;
 };
 
@@ -52,6 +54,25 @@ extern "C" int ht_model_open(const char *path, int hand_tweaks, ht_model **out)
 		m->com.insert(m->com.end(), r + 7, r + 10);
 		m->rest.insert(m->rest.end(), r + 10, r + 17);
 	}
+	const fx_arr *ji = get("joint_i"), *jf = get("joint_f");
+	if (m->nj > 0 && (!ji || !jf)) { m->err = "model joint arrays missing"; return HT_ERR_IO; }
+	m->jointc.assign((size_t)m->nj * HT_JC, 0.0f);
+	for (int j = 0; j < m->nj; j++)
+	{
+		float *c = &m->jointc[(size_t)j * HT_JC]; const float *r = jf->f() + 16 * j;      // p0 p1 rangemin rangemax jointframe
+		c[HT_JC_RB0] = (float)ji->i()[2 * j]; c[HT_JC_RB1] = (float)ji->i()[2 * j + 1];
+		for (int i = 0; i < 3; i++) { c[HT_JC_P0 + i] = r[i]; c[HT_JC_P1 + i] = r[3 + i]; c[HT_JC_RMIN + i] = r[6 + i]; c[HT_JC_RMAX + i] = r[9 + i]; }
+		for (int i = 0; i < 4; i++) c[HT_JC_FRAME + i] = r[12 + i];
+	}
+	return HT_OK;
+}
+// the limits of the joint coordinates c = (s.x, s.y, t.z) (ConstrainAngularRangeW physics.h:351-393), as a context computes them at model load
+extern "C" int ht_model_joint_limits(const ht_model *m, float *lo, float *hi, int *swapped)
+{
+	if (!m || m->jointc.size() != (size_t)m->nj * HT_JC) return HT_ERR_ARG;
+	std::vector<float> jl((size_t)m->nj * HT_JL, 0.0f);
+	ht_joint_limits(m->jointc.data(), m->nj, jl.data());
+	ht_joint_limits_public(jl.data(), m->nj, lo, hi, swapped);
 	return HT_OK;
 }
 extern "C" int ht_model_close(ht_model *m) { if (!m) return HT_ERR_ARG; delete m; return HT_OK; }

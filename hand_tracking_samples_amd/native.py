@@ -17,6 +17,8 @@ MAXPTS, ROW, CONTACT = 4096, 16, 12      # HT_MAX_POINTS
 LABELS_SEGMENT_FRAME = 1      # HT_LABELS_SEGMENT_FRAME
 LABELS_SIDE128 = 2            # HT_LABELS_SIDE128
 SENSOR_IVY, SENSOR_DS4 = 0, 1 # HT_SENSOR_IVY, HT_SENSOR_DS4
+JOINTS_COM_POSES = 1          # HT_JOINTS_COM_POSES
+SAMPLE_ENHANCED = 2           # HT_SAMPLE_ENHANCED
 CNN128_IN, CNNB128_COUNT = 16384, 30429920
 # ht_debug_train_buffers: (name, floats, shape) of the segments of act and err, in order (None: padding)
 TRAIN_ACT = (("a1", 57600, (16, 60, 60)), ("a3", 3600, (16, 15, 15)), ("a5", 9216, (64, 12, 12)), ("a6", 2304, (2304,)), ("a8", 2048, (2048,)))
@@ -33,6 +35,7 @@ SYMBOLS = (
     "ht_stage_prepare", "ht_stage_decode", "ht_stage_fit_error", "ht_stage_cloud_rows", "ht_stage_contacts", "ht_stage_fit",
     "ht_stage_multistep", "ht_stage_multistep_range", "ht_stage_scratch_unibody", "ht_stage_chamber", "ht_profile_enable", "ht_profile_read", "ht_debug_solve_stats", "ht_debug_contact_stats", "ht_debug_solver_build", "ht_debug_reset_flags", "ht_debug_reset_organisation", "ht_update_passes_sync", "ht_job_start", "ht_job_poll", "ht_job_wait", "ht_job_collect", "ht_debug_contact_kernel", "ht_debug_contact_order", "ht_debug_rank_desc", "ht_contact_capacity", "ht_debug_solve_tables", "ht_debug_solve_tables_header", "ht_debug_train_buffers",
     "ht_sensor_out_dims", "ht_sensor_filter", "ht_sensor_filter_dev", "ht_sensor_background", "ht_sensor_background_dev",
+    "ht_model_joint_limits", "ht_joint_coords", "ht_joint_coords_dev", "ht_joint_pose", "ht_joint_pose_dev", "ht_sample_poses", "ht_sample_poses_dev",
     "ht_comm_available", "ht_comm_unique_id", "ht_comm_init", "ht_comm_info", "ht_gather_poses_dev", "ht_gather_wait", "ht_gather_wait_host", "ht_comm_destroy",
 )
 
@@ -175,6 +178,13 @@ def load(build_if_missing=True):
     L.ht_comm_available.argtypes = []
     L.ht_comm_destroy.argtypes = [vp]
     L.ht_debug_contact_stats.argtypes = [vp, C.c_int, fp, C.c_int]
+    L.ht_model_joint_limits.argtypes = [vp, fp, fp, ip]
+    L.ht_joint_coords.argtypes = [vp, fp, C.c_int, C.c_int, fp, fp]
+    L.ht_joint_coords_dev.argtypes = [vp, vp, C.c_int, C.c_int, vp, vp, vp]
+    L.ht_joint_pose.argtypes = [vp, fp, fp, C.c_int, C.c_int, fp]
+    L.ht_joint_pose_dev.argtypes = [vp, vp, vp, C.c_int, C.c_int, vp, vp]
+    L.ht_sample_poses.argtypes = [vp, fp, C.c_int, C.c_uint64, C.c_uint64, C.c_float, C.c_int, fp, fp]
+    L.ht_sample_poses_dev.argtypes = [vp, vp, C.c_int, C.c_uint64, C.c_uint64, C.c_float, C.c_int, vp, vp, vp]
     for name in SYMBOLS:
         if name not in ("ht_last_error", "ht_model_error"):
             getattr(L, name).restype = C.c_int
@@ -629,6 +639,40 @@ class Context:
         """ht_render_mesh_depth_dev: device pointers, asynchronous on `stream`."""
         self._chk(self.L.ht_render_mesh_depth_dev(self.h, d_poses, d_cams, int(w), int(h), float(far), float(pixel_offset), int(B), d_depth, d_body, stream))
 
+    # -- joint coordinates (ht_mi355x.h "joint coordinates"): c = (s.x, s.y, t.z) per joint; com_poses: centre-of-mass poses instead of user poses
+    def joint_coords(self, poses, com_poses=False, want_gaps=False):
+        """poses [B,nb,7] -> coords [B,nj,3] (and the joints' anchor gaps [B,nj] with want_gaps)."""
+        poses = _c(poses, np.float32).reshape(-1, self.nb, POSE); B = poses.shape[0]
+        coords = np.empty((B, self.nj, 3), np.float32); gaps = np.empty((B, self.nj), np.float32) if want_gaps else None
+        self._chk(self.L.ht_joint_coords(self.h, _f(poses), B, JOINTS_COM_POSES if com_poses else 0, _f(coords), _f(gaps) if want_gaps else None))
+        return (coords, gaps) if want_gaps else coords
+
+    def joint_coords_dev(self, d_poses, B, d_coords, d_gaps=None, com_poses=False, stream=None):
+        self._chk(self.L.ht_joint_coords_dev(self.h, d_poses, int(B), JOINTS_COM_POSES if com_poses else 0, d_coords, d_gaps, stream))
+
+    def joint_pose(self, roots, coords, com_poses=False):
+        """Forward kinematics: body 0's poses [B,7] and coords [B,nj,3] -> poses [B,nb,7].  Coordinates outside a unit quaternion's are refused."""
+        roots = _c(roots, np.float32).reshape(-1, POSE); B = roots.shape[0]
+        coords = _c(coords, np.float32).reshape(B, self.nj, 3)
+        poses = np.empty((B, self.nb, POSE), np.float32)
+        self._chk(self.L.ht_joint_pose(self.h, _f(roots), _f(coords), B, JOINTS_COM_POSES if com_poses else 0, _f(poses)))
+        return poses
+
+    def joint_pose_dev(self, d_roots, d_coords, B, d_poses, com_poses=False, stream=None):
+        """ht_joint_pose_dev: device pointers, asynchronous on `stream`; out-of-range coordinates are clamped, not refused."""
+        self._chk(self.L.ht_joint_pose_dev(self.h, d_roots, d_coords, int(B), JOINTS_COM_POSES if com_poses else 0, d_poses, stream))
+
+    def sample_poses(self, roots, seed, first_index=0, spread=1.0, com_poses=False, want_coords=False, enhanced=False):
+        """B poses inside the joint limits, sample i drawn from (seed, first_index + i): roots [B,7] -> poses [B,nb,7] (and coords [B,nj,3]);
+        enhanced: HandModelEnhancements' couplings (fingertip joints follow their knuckles, no abduction on a clenched finger)."""
+        roots = _c(roots, np.float32).reshape(-1, POSE); B = roots.shape[0]
+        poses = np.empty((B, self.nb, POSE), np.float32); coords = np.empty((B, self.nj, 3), np.float32) if want_coords else None
+        self._chk(self.L.ht_sample_poses(self.h, _f(roots), B, int(seed), int(first_index), float(spread), (JOINTS_COM_POSES if com_poses else 0) | (SAMPLE_ENHANCED if enhanced else 0), _f(poses), _f(coords) if want_coords else None))
+        return (poses, coords) if want_coords else poses
+
+    def sample_poses_dev(self, d_roots, B, seed, first_index, spread, d_poses, d_coords=None, com_poses=False, enhanced=False, stream=None):
+        self._chk(self.L.ht_sample_poses_dev(self.h, d_roots, int(B), int(seed), int(first_index), float(spread), (JOINTS_COM_POSES if com_poses else 0) | (SAMPLE_ENHANCED if enhanced else 0), d_poses, d_coords, stream))
+
     def sensor_filter(self, kind, depth, cams, ir=None, background=None, max_width=320):
         """RSCam::FilterIvy / FilterDS4 (dcam.h:174-226) for a batch of raw frames: depth u16[B,h,w], cams [B,12], ir u8[B,h,w] (DS4), background u16[B,h,w]
         (DS4, optional) -> (depth u16[B,h_out,w_out], cams [B,12])."""
@@ -831,6 +875,20 @@ def expected_cnn(pose, cam):
     return out
 
 
+def joint_degrees(coords):
+    """Joint coordinates as angles in the reference's degrees: 2 asin(c) 180 / 3.14 (its 3.14; a host-side convenience)."""
+    return 2.0 * np.arcsin(np.clip(np.asarray(coords, np.float64), -1.0, 1.0)) * 180.0 / 3.14
+
+
+def model_joint_limits(path, hand_tweaks=True):
+    """(lo [nj,3], hi [nj,3], swapped bool[nj]) of a model file's joint coordinates (ht_model_joint_limits; host only, no GPU)."""
+    m = HostModel(path, hand_tweaks)
+    try:
+        return m.joint_limits()
+    finally:
+        m.close()
+
+
 class HostModel:
     """A hand model that is not being tracked (ht_model_*, host only): the mesh ray cast's definition and its frames."""
 
@@ -853,6 +911,12 @@ class HostModel:
     def scale(self, s):
         if self.L.ht_model_scale(self.m, float(s)):
             raise HTError("ht_model_scale: bad argument")
+
+    def joint_limits(self):
+        lo = np.empty((self.nj, 3), np.float32); hi = np.empty((self.nj, 3), np.float32); sw = np.zeros(self.nj, np.int32)
+        if self.L.ht_model_joint_limits(self.m, _f(lo), _f(hi), _i(sw)):
+            raise HTError("ht_model_joint_limits: bad argument")
+        return lo, hi, sw.astype(bool)
 
     def sdmesh(self, body):
         """corner positions [3 t, 3] of body's subdivision mesh, in the bone's rig frame"""

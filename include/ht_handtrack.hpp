@@ -18,6 +18,7 @@
 // Errors are reported the way the reference's apps expect them: by throwing std::runtime_error (synthetic-tracker.cpp:255-264).
 #pragma once
 #include <cfloat>
+#include <cmath>
 #include <cstdint>
 #include <fstream>
 #include <memory>
@@ -351,7 +352,42 @@ struct HandTracker                                                              
 			check(ctx_, ht_fit_rows(ctx_, which_, 1, n ? &points[0].x : nullptr, n, &n, l.data(), nl, &nl, a.data(), na, &na, microforce));
 		}
 		void FitPointCloud(const std::vector<float3> &points, float microforce) { FitPointCloud(points, {}, {}, microforce); }      // round-1 shorthand
+		// Additions (the reference's PhysModel has no such members; its solver computes these on every pass and keeps them, physics.h:351-393): the model in its
+		// joints' own coordinates c = (s.x, s.y, t.z) per joint (ht_joint_coords), the same as angles in the reference's degrees (2 asin(c) 180 / 3.14), how far every
+		// joint's two anchors are apart (what FixPositions closes, physmodel.h:404-408), and the way back (ht_joint_pose: FixOrientations / FixPositions top down
+		// from body 0, which stays where it is; momenta untouched).  SetJointCoords(GetJointCoords()) closes the joints and keeps the orientations.
+		std::vector<float3> GetJointCoords() const { std::vector<float3> c; joints(&c, nullptr); return c; }
+		std::vector<float> GetJointGaps() const { std::vector<float> g; joints(nullptr, &g); return g; }
+		std::vector<float3> JointAngles() const
+		{
+			std::vector<float3> c = GetJointCoords();
+			for (auto &a : c) a = { 2.0f * std::asin(a.x) * 180.0f / 3.14f, 2.0f * std::asin(a.y) * 180.0f / 3.14f, 2.0f * std::asin(a.z) * 180.0f / 3.14f };
+			return c;
+		}
+		TrackedModel &SetJointCoords(const std::vector<float3> &coords)
+		{
+			int nj = 0; ht_model_info(ctx_, nullptr, &nj, nullptr);
+			if ((int)coords.size() != nj) throw std::runtime_error("SetJointCoords expects one coordinate triple per joint");
+			const std::vector<Pose> now = read(false);
+			const float root[7] = { now[0].position.x, now[0].position.y, now[0].position.z, now[0].orientation.x, now[0].orientation.y, now[0].orientation.z, now[0].orientation.w };
+			std::vector<float> p((size_t)nb_ * HT_POSE);
+			check(ctx_, ht_joint_pose(ctx_, root, nj ? &coords[0].x : root, 1, HT_JOINTS_COM_POSES, p.data()));
+			std::vector<Pose> poses(nb_);
+			for (int b = 0; b < nb_; b++) { const float *s = &p[(size_t)b * HT_POSE]; poses[b].position = { s[0], s[1], s[2] }; poses[b].orientation = { s[3], s[4], s[5], s[6] }; }
+			poses[0] = now[0];      // to the bit (the walk takes the root through the rig frame and back)
+			return SetPose(poses);
+		}
 	private:
+		void joints(std::vector<float3> *c, std::vector<float> *g) const
+		{
+			int nj = 0; ht_model_info(ctx_, nullptr, &nj, nullptr);
+			const std::vector<Pose> now = read(false);
+			std::vector<float> p; for (auto &q : now) { const float r[7] = { q.position.x, q.position.y, q.position.z, q.orientation.x, q.orientation.y, q.orientation.z, q.orientation.w }; p.insert(p.end(), r, r + 7); }
+			std::vector<float3> cc((size_t)nj); std::vector<float> gg((size_t)nj);
+			if (nj) check(ctx_, ht_joint_coords(ctx_, p.data(), 1, HT_JOINTS_COM_POSES, &cc[0].x, gg.data()));
+			if (c) *c = cc;
+			if (g) *g = gg;
+		}
 		friend struct HandTracker;
 		ht_ctx *ctx_ = nullptr; int which_ = 0, nb_ = 0; std::vector<float3> com_; std::vector<Mesh> meshes_, sdmeshes_;
 		std::vector<Pose> read(bool user) const

@@ -388,6 +388,50 @@ int ht_render_depth_dev(ht_ctx *ctx, const float *d_poses, const float *d_cams, 
 int ht_render_mesh_depth(ht_ctx *ctx, const float *poses, const float *cams, int w, int h, float far, float pixel_offset, int B, uint16_t *depth, int8_t *body);
 int ht_render_mesh_depth_dev(ht_ctx *ctx, const float *d_poses, const float *d_cams, int w, int h, float far, float pixel_offset, int B, uint16_t *d_depth, int8_t *d_body, void *stream);
 
+/* ---- joint coordinates (an addition: the reference decomposes every joint on every solver pass and never hands the result out) ----
+ * Joint j of the model (parent body rbi0 at orientation q0, child rbi1 at q1, jointframe F, anchors p0 / p1) has the coordinates c = (s.x, s.y, t.z) of
+ * ConstrainAngularRangeW (third_party/physics.h:351-393): Jb = q0 F, Jf = q1, both times cb = normalize(0,-1,0,1) for a "swapped" joint (:358-362: rangemin.x ==
+ * rangemax.x == 0 and rangemin.z < rangemax.z; its limits become (min.z, min.y, 0), (max.z, max.y, 0)); r = conj(Jb) Jf, s = quat_from_to((0,0,1), qzdir(r))
+ * (geometric.h:319-328), t = conj(s) r.  No sign is canonicalised: t.z follows the sign of the stored quaternions, as in the reference.  An angle in the
+ * reference's degrees is 2 asin(c) 180 / 3.14.  All arrays are fp32; poses [B][nb][7] are position + quaternion xyzw per body, user poses (GetPoseUser
+ * physmodel.h:434, what the update calls return) unless flags has HT_JOINTS_COM_POSES: then centre-of-mass poses (GetPose, what ht_render_depth takes), on
+ * input and on output, the root included.  B is not bounded by max_batch; B = 0 does nothing; every check runs before anything grows or launches;
+ * HT_ERR_STATE for a context without a hand model.
+ * ht_model_joint_limits  host only, no context: the values of c that satisfy the reference's rows (:367-391), lo / hi [nj][3], swapped [nj] (any may be NULL).
+ *                     With jmin = deg * 3.14f / 180.0f: x locked at sinf(jmin.x / 2), or in [sinf(jmin.x / 2), sinf(jmax.x / 2)], or, for a range of
+ *                     360 * 3.14 / 180 or more (no rows), -inf .. +inf; y locked at jmin.y IN RADIANS (:378), or ranged by sines; z locked at 0 whatever
+ *                     jmin.z is (:386), or ranged by sines.  A context computes the same table once at model load; ht_scale leaves it alone.
+ * ht_joint_coords     poses [B][nb][7] -> coords [B][nj][3] and (optional) gaps [B][nj] = |PoseUser(rbi0) p0 - PoseUser(rbi1) p1|, the distance
+ *                     GetLinearConstraints / FixPositions close (physmodel.h:328-334, 404-408): a per-joint tracking-quality figure.
+ * ht_joint_pose       forward kinematics, FixOrientations / FixPositions top down (physmodel.h:357-408): roots [B][7] (body 0's pose) and coords [B][nj][3] ->
+ *                     poses [B][nb][7].  Joints in model order: s = (cx, cy, 0, sqrt(max(0, 1 - cx cx - cy cy))), t = (0, 0, cz, sqrt(max(0, 1 - cz cz))),
+ *                     q1 = normalize(q0 F [cb] s t [conj(cb)]), PositionUser1 = PoseUser0 p0 - q1 p1.  HT_ERR_STATE for a model whose joints are not in
+ *                     top-down order from body 0 (both shipped models are).  The host form refuses non-finite coordinates, |c| > 1 and
+ *                     cx cx + cy cy > 1 (HT_ERR_ARG); the device form cannot look and clamps them through the two max(0, .) above.
+ *                     ht_joint_coords of the result gives coords back; the other way round the orientations come back where the twist quaternion of
+ *                     the read-out has t.w >= 0 (a twist within 180 degrees between quaternions stored on the same side): with no sign canonicalised,
+ *                     t.z alone does not tell t from its mirror image.
+ * ht_sample_poses     B poses inside the model's joint limits: sample i, joint j, axis a takes u in [0, 1) from a counter-based hash of (seed, first_index + i,
+ *                     j, a) (24 bits, exact in fp32; independent of B and of the launch), c = (lo + hi) / 2 + (u - 0.5) (hi - lo) spread, a locked axis its
+ *                     lock value, an unbounded one +-sinf(90 deg / 2); then ht_joint_pose's walk in the same kernel.  Uniform in the coordinate, not the
+ *                     angle.  spread in [0, 1] (HT_ERR_ARG otherwise).  coords [B][nj][3] is optional.  The poses respect every joint limit; they are not
+ *                     checked for contact between fingers (run solver passes on them for that).
+ *                     flags & HT_SAMPLE_ENHANCED applies HandModelEnhancements' couplings (handtrack.h:417-420, 434-440) as the tracker sees them, for hand
+ *                     layouts (at least 17 bodies, fingers as chains of bones 5..16 on bone 1; HT_ERR_ARG otherwise): the x of each fingertip joint
+ *                     (6, 9, 12, 15) is locked at sin of half of acos(clamp(dot(qzdir(q[b-2]), qzdir(q[b-1])), 0, 1)) * 180 / 3.14159f / 2 degrees taken
+ *                     back to radians with 3.14f (both literals are the reference's), and a knuckle (joint 4, 7, 10, 13) whose finger is not "up" on the
+ *                     built pose (dot(qydir(q[1]), qydir(q[bone])) > cos(40 * 3.14 / 180) fails) has its y set to 0 and is rebuilt once.
+ * The *_dev forms take device buffers and are asynchronous on `stream`. */
+#define HT_JOINTS_COM_POSES 1
+#define HT_SAMPLE_ENHANCED 2
+int ht_model_joint_limits(const ht_model *m, float *lo, float *hi, int *swapped);
+int ht_joint_coords(ht_ctx *ctx, const float *poses, int B, int flags, float *coords, float *gaps);
+int ht_joint_coords_dev(ht_ctx *ctx, const float *d_poses, int B, int flags, float *d_coords, float *d_gaps, void *stream);
+int ht_joint_pose(ht_ctx *ctx, const float *roots, const float *coords, int B, int flags, float *poses);
+int ht_joint_pose_dev(ht_ctx *ctx, const float *d_roots, const float *d_coords, int B, int flags, float *d_poses, void *stream);
+int ht_sample_poses(ht_ctx *ctx, const float *roots, int B, uint64_t seed, uint64_t first_index, float spread, int flags, float *poses, float *coords);
+int ht_sample_poses_dev(ht_ctx *ctx, const float *d_roots, int B, uint64_t seed, uint64_t first_index, float spread, int flags, float *d_poses, float *d_coords, void *stream);
+
 /* ---- camera front end: the depth filters of RSCam::GetDepth (include/dcam.h:238-244) for raw sensor frames ------------------------------
  * Every real-time program of the reference feeds the tracker htk.update(dcam.GetDepth()); GetDepth filters the sensor's frame first.  All arithmetic is
  * integer, the constants are dcam.h's own (it assumes millimetre counts, dcam.h:180).

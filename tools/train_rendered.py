@@ -21,7 +21,10 @@ inputs from ht_cnn_input_sized_dev, labels with HT_LABELS_SIDE128, steps of --mi
 
 --side 128 --frame 640x480 trains that net on what a segmenter hands it: the 17-bone hand of bench_data/frames1024.npz rendered at 640x480 by the SR300's camera (focal 610,
 principal (320, 240)), ht_segment_vr_sized_dev(128, 0xF, {0.1, 0.70}), ht_cnn_input_sized_dev, labels with HT_LABELS_SEGMENT_FRAME | HT_LABELS_SIDE128,
-ht_cnn_train_batch_sized_dev.  Held out: every 16th ground truth, rendered and segmented the same way."""
+ht_cnn_train_batch_sized_dev.  Held out: every 16th ground truth, rendered and segmented the same way.
+
+--sampled (64x64 net) replaces step 1: only the wrist pose of each interpolated ground truth is uploaded (B x 7 floats) and ht_sample_poses_dev(HT_SAMPLE_ENHANCED, --spread)
+draws the hand on the device inside the model's joint limits, sample i of round r from (--seed, r * B + i).  Off by default: the other modes compute what they did."""
 import argparse
 import json
 import os
@@ -194,7 +197,12 @@ def main():
     ap.add_argument("--rate-steps", type=int, default=2048)
     ap.add_argument("--frame", default=None, type=lambda v: tuple(int(x) for x in v.lower().split("x")), help="with --side 128: render full-size frames of this size (640x480) and segment them to the 128x128 tile")
     ap.add_argument("--mesh", action="store_true", help="render the training frames from the subdivision surface (ht_render_mesh_depth_dev, pixel offset 0, far 4) instead of the hulls")
+    ap.add_argument("--sampled", action="store_true", help="draw the hands with ht_sample_poses_dev (HT_SAMPLE_ENHANCED, seed --seed) inside the model's joint limits; only the wrists come from the "
+                                                            "interpolated ground truths.  64x64 net only")
+    ap.add_argument("--spread", type=float, default=0.98, help="with --sampled: the share of every joint range the sampler uses")
     a = ap.parse_args()
+    if a.sampled and a.side != 64:
+        ap.error("--sampled trains the 64x64-input net")
     if a.minibatch < 1 or a.batch % a.minibatch:
         ap.error("--minibatch must divide --batch")
     if a.frame is not None and (a.side != 128 or len(a.frame) != 2 or not native.segment_vr_supported(a.frame[0], a.frame[1], 128)):
@@ -223,9 +231,17 @@ def main():
             ctx.cnn_train_batch_dev(x.data_ptr(), lab.data_ptr(), B, a.minibatch, order=order, alpha=a.lr, d_mse=d_mse, stream=s.cuda_stream)
     ev = [torch.cuda.Event(enable_timing=True) for _ in range(6)]
 
+    nsampled = [0]      # samples drawn so far: the next round's first_index
+    troots = torch.empty((B, 7), device=dev)
+
     def round_(poses, order, timed=False):
         with torch.cuda.stream(s):
-            tp.copy_(torch.from_numpy(poses))      # in the stream's order: the previous round may still read the poses
+            if a.sampled:      # `poses` gives the wrists only; the hands are drawn on the device, inside the model's joint limits
+                troots.copy_(torch.from_numpy(np.ascontiguousarray(poses[:, 0])))
+                ctx.sample_poses_dev(troots.data_ptr(), B, a.seed, nsampled[0], a.spread, tp.data_ptr(), None, com_poses=True, enhanced=True, stream=s.cuda_stream)
+                nsampled[0] += B
+            else:
+                tp.copy_(torch.from_numpy(poses))      # in the stream's order: the previous round may still read the poses
             if timed: ev[0].record(s)
             if a.mesh:
                 ctx.render_mesh_depth_dev(tp.data_ptr(), cams.data_ptr(), 320, 240, 4.0, 0.0, B, depth.data_ptr(), None, s.cuda_stream)
@@ -309,8 +325,10 @@ def main():
     kern["cnn_input_B%d" % B] = {"ms": ms, "bytes_moved": B * 4096 * 6, "GBps": B * 4096 * 6 / (ms / 1e3) / 1e9}
     mse1, acc1 = curve[-1]["held_out_mse"], curve[-1]["cnn_pose_frames"]
     ctx.close()
-    out = {"what": "tools/train_rendered.py: train-cnn's loop on the device, one stream: %d rounds of %d rendered 320x240 frames (render, segment, input, segment-frame labels, "
-                   "SGD in steps of %d lr %g over a seeded permutation), seed 0x%X" % (a.rounds, B, a.minibatch, a.lr, a.seed),
+    out = {"what": "tools/train_rendered.py%s: train-cnn's loop on the device, one stream: %d rounds of %d rendered 320x240 frames (%srender, segment, input, segment-frame labels, "
+                   "SGD in steps of %d lr %g over a seeded permutation), seed 0x%X" % (" --sampled" if a.sampled else "", a.rounds, B,
+                                                                                        "ht_sample_poses_dev HT_SAMPLE_ENHANCED spread %g at the interpolated wrists, " % a.spread if a.sampled else "", a.minibatch, a.lr, a.seed),
+           "pose_source": "sampled" if a.sampled else "interpolated",
            "rounds": a.rounds, "batch": B, "minibatch": a.minibatch, "lr": a.lr, "samples": a.rounds * B, "seconds": seconds,
            "stage_ms_per_round": {"render": stage_ms[0], "segment": stage_ms[1], "cnn_input": stage_ms[2], "labels": stage_ms[3], "train": stage_ms[4]},
            "kernels": kern, "closed_loop_samples_per_s": loop_sps, "bare_train_steps_per_s": bare_sps,      # samples/s of the training call alone on the resident pool "loop_over_bare": loop_sps / bare_sps,
