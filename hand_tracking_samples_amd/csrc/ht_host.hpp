@@ -115,6 +115,10 @@ struct ht_ctx
 	std::vector<float> h_mesh_corners, mesh_rad; std::vector<int> mesh_off; float4 *d_mesh = nullptr;
 	float *d_jointl = nullptr;                                   // [nj][HT_JL] the limits of the joint coordinates, made once at model load beside jointc (ht_joint_limits; ht_scale leaves them)
 	char *d_joints = nullptr; size_t joints_cap = 0;             // ht_joint_coords', ht_joint_pose's and ht_sample_poses' staging (poses, roots, coordinates, gaps), grown to the largest call (dev_grow)
+	char *d_mirror = nullptr; size_t mirror_cap = 0;             // the host forms of ht_mirror_frames / _cams / _poses: their staging (input, flags, output), grown to the largest call (dev_grow)
+	// ht_update_hands_*: the mirrored inputs an update of flagged frames runs on, [B][hands_px] pixels, [B][12], [B][nb][7], and the flags of the host form [B]; nothing until the
+	// first flagged call or ht_reserve_hands, then grown to the largest frame (hands_reserve, ht_solver_api.hip: one synchronising re-allocation, never smaller)
+	uint16_t *d_hands_frames = nullptr; size_t hands_px = 0; float *d_hands_cams = nullptr, *d_hands_start = nullptr; unsigned char *d_hands_flags = nullptr;
 };
 
 // The net of a side x side input; any other side is refused here, and only here

@@ -21,6 +21,7 @@ struct ht_model
 	std::vector<std::vector<float>> sdrows;             // per body: [t][16] corners and PolyPlane of every sdverts triangle (ht_mesh_rows), what the mesh ray cast reads
 	std::vector<float> com, rest;                       // [nb][3], [nb][7]
 	std::vector<float> jointc;                          // [nj][HT_JC] the joint table as a context keeps it
+	bool mirrored = false;                              // ht_model_mirror was applied an odd number of times (ht_model_scale makes the mesh rows from the unmirrored corners)
 	std::string err;
 };
 
@@ -138,9 +139,11 @@ extern "C" int ht_model_hitcheck(const ht_model *m, const float *poses, const fl
 
 // PhysModel::scale (physmodel.h:196-219,304-319) for what this view holds: hull vertices and plane offsets, the subdivision meshes and the centres of mass times s,
 // the operations ht_scale applies to a context's model, so a scaled host model and a scaled context stay bit-equal.  The mesh planes are made again from the scaled corners.
+static void model_mirror_arrays(ht_model *m);
 extern "C" int ht_model_scale(ht_model *m, float s)
 {
 	if (!m || !(s > 0.0f)) return HT_ERR_ARG;
+	if (m->mirrored) { model_mirror_arrays(m); const int r = ht_model_scale(m, s); model_mirror_arrays(m); return r; }      // PolyPlane's sums depend on the corner order: scaled as the right hand, so that scale and mirror commute to the bit
 	for (int b = 0; b < m->nb; b++)
 	{
 		for (auto &v : m->verts[b]) v *= s;
@@ -149,6 +152,47 @@ extern "C" int ht_model_scale(ht_model *m, float s)
 		ht_mesh_rows(m->sdverts[b].data(), m->sdverts[b].size() / 9, m->sdrows[b].data());
 	}
 	for (auto &v : m->com) v *= s;
+	return HT_OK;
+}
+
+// The left hand of this model: the mirror x -> -x of what is drawn and ray-cast, by sign flips and swaps of the stored arrays alone -- nothing is
+// computed again, so twice is the identity byte for byte.  Vertices, corners and centres of mass: x negated.  Planes (hull planes, the meshes' PolyPlanes): x of the
+// normal negated, the offset kept.  Rest poses: (-px,py,pz, qx,-qy,-qz,qw).  Triangles keep their first corner and swap the other two, which keeps them facing outwards.
+// The joint table is left alone: the joint coordinates of a left hand are those of its mirror image.
+static inline void flip_sign(float &v) { unsigned u; memcpy(&u, &v, 4); u ^= 0x80000000u; memcpy(&v, &u, 4); }
+static void model_mirror_arrays(ht_model *m)
+{
+	for (int b = 0; b < m->nb; b++)
+	{
+		for (size_t k = 0; k < m->verts[b].size(); k += 3) flip_sign(m->verts[b][k]);
+		for (size_t k = 0; k < m->planes[b].size(); k += 4) flip_sign(m->planes[b][k]);
+		for (size_t k = 0; k + 2 < m->tris[b].size(); k += 3) std::swap(m->tris[b][k + 1], m->tris[b][k + 2]);
+		std::vector<float> &sv = m->sdverts[b], &sr = m->sdrows[b];
+		for (size_t t = 0; t < sv.size() / 9; t++)
+		{
+			float *c = &sv[9 * t], *r = &sr[16 * t];
+			for (int i = 0; i < 3; i++) { std::swap(c[3 + i], c[6 + i]); std::swap(r[4 + i], r[8 + i]); }
+			for (int i = 0; i < 3; i++) { flip_sign(c[3 * i]); flip_sign(r[4 * i]); }
+			flip_sign(r[12]);
+		}
+		flip_sign(m->com[3 * b]);
+		float *p = &m->rest[7 * b];
+		flip_sign(p[0]); flip_sign(p[4]); flip_sign(p[5]);
+	}
+	m->mirrored = !m->mirrored;
+}
+// the stored planes of a body: its hull's [nplanes][4] and the PolyPlane [t][4] of every triangle of its subdivision mesh (what the two ray casts read); either may be null
+extern "C" int ht_model_body_planes(const ht_model *m, int body, float *hull_planes, float *mesh_planes)
+{
+	if (!m || body < 0 || body >= m->nb) return HT_ERR_ARG;
+	if (hull_planes) memcpy(hull_planes, m->planes[body].data(), m->planes[body].size() * sizeof(float));
+	if (mesh_planes) for (size_t t = 0; t < m->sdrows[body].size() / 16; t++) memcpy(mesh_planes + 4 * t, &m->sdrows[body][16 * t + 12], 4 * sizeof(float));
+	return HT_OK;
+}
+extern "C" int ht_model_mirror(ht_model *m)
+{
+	if (!m) return HT_ERR_ARG;
+	model_mirror_arrays(m);
 	return HT_OK;
 }
 

@@ -712,6 +712,70 @@ extern "C" int ht_update_direct_sync(ht_ctx *ctx, const uint16_t *depth, const f
 	return update_sync(ctx, depth, cams, fs, UPD_FULL, B, poses_out, nullptr, cnn_out, nullptr);      // a frame that is its own segment: the point capacity follows its size
 }
 
+// ---- left hands (an addition) -------------------------------------------------------------------------------------------------------------
+// A left-hand update is the existing update on the mirror image: frames, cameras and start poses of the flagged frames mirrored into a staging of the context
+// (ht_mirror.hip), ht_update_frames_sized_dev on that staging, the poses that come out mirrored in place.  The slots' state stays the right hand's.  Without
+// flags the call IS ht_update_frames_sized_*, on the caller's own pointers.
+// The staging: max_batch frames of `px` pixels, cameras and start poses, and the host form's flags.  Never smaller; growing is one synchronising re-allocation, the
+// replacement made first (dev_grow), so a failure leaves what was there.
+static int hands_reserve(ht_ctx *ctx, size_t px)
+{
+	int r;
+	if (!ctx->d_hands_cams && ((r = dev_alloc(ctx, &ctx->d_hands_start, (size_t)ctx->B * ctx->model.nb * HT_POSE)) || (r = dev_alloc(ctx, &ctx->d_hands_flags, (size_t)ctx->B)) ||
+	                           (r = dev_alloc(ctx, &ctx->d_hands_cams, (size_t)ctx->B * HT_CAM)))) return r;
+	if (px <= ctx->hands_px) return HT_OK;
+	HIPCHK(ctx, ht_sync_all(ctx));
+	return dev_grow(ctx, &ctx->d_hands_frames, &ctx->hands_px, px, (size_t)ctx->B);
+}
+extern "C" int ht_reserve_hands(ht_ctx *ctx, int w, int h)
+{
+	CHECK_READY(ctx); CHECK_MODEL(ctx);
+	if (w < 1 || h < 1 || (long long)w * h > 640LL * 480) { ctx->err = "ht_reserve_hands: a frame of 1 to 640x480 pixels"; return HT_ERR_ARG; }
+	return hands_reserve(ctx, (size_t)w * h);
+}
+extern "C" int ht_hands_capacity(ht_ctx *ctx, size_t *frame_pixels)
+{
+	CHECK_READY(ctx);
+	if (!frame_pixels) return HT_ERR_ARG;
+	*frame_pixels = ctx->hands_px;
+	return HT_OK;
+}
+// the flagged call, checked: mirror in, update, mirror out, all enqueued on s
+static int hands_enqueue(ht_ctx *ctx, int side, const uint16_t *d_depth, const float *d_cams, int w, int h, float segment_scale, const unsigned char *d_hands, const float *d_start, int B, float *d_poses_out, hipStream_t s)
+{
+	{ const int r = hands_reserve(ctx, (size_t)w * h); if (r) return r; }
+	const int nb = ctx->model.nb;
+	{ ht_prof_scope ps(ctx, "k_mirror_frames", s); ht_launch_mirror_frames(d_depth, w, h, B, d_hands, ctx->d_hands_frames, s); }
+	{ ht_prof_scope ps(ctx, "k_mirror_cams", s); ht_launch_mirror_cams(d_cams, w, B, d_hands, ctx->d_hands_cams, s); }
+	if (d_start) { ht_prof_scope ps(ctx, "k_mirror_poses", s); ht_launch_mirror_poses(d_start, nb, B, d_hands, ctx->d_hands_start, s); }
+	{ const int r = ht_update_frames_sized_dev(ctx, side, ctx->d_hands_frames, ctx->d_hands_cams, w, h, segment_scale, d_start ? ctx->d_hands_start : nullptr, B, d_poses_out, s); if (r) return r; }
+	{ ht_prof_scope ps(ctx, "k_mirror_poses", s); ht_launch_mirror_poses(d_poses_out, nb, B, d_hands, d_poses_out, s); }
+	return HT_OK;
+}
+extern "C" int ht_update_hands_dev(ht_ctx *ctx, int side, const uint16_t *d_depth, const float *d_cams, int w, int h, float segment_scale, const unsigned char *d_hands, const float *d_start_poses, int B, float *d_poses_out, void *stream)
+{
+	if (!d_hands) return ht_update_frames_sized_dev(ctx, side, d_depth, d_cams, w, h, segment_scale, d_start_poses, B, d_poses_out, stream);
+	CHECK_READY(ctx); CHECK_MODEL(ctx); CHECK_BATCH(ctx, B);
+	if (!d_depth || !d_cams || !d_poses_out) return HT_ERR_ARG;
+	{ const int r = frames_sized_args_ok(ctx, side, w, h); if (r) return r; }
+	return update_dev_end(ctx, hands_enqueue(ctx, side, d_depth, d_cams, w, h, segment_scale, d_hands, d_start_poses, B, d_poses_out, ht_user_stream(ctx, stream)));
+}
+extern "C" int ht_update_hands_sync(ht_ctx *ctx, int side, const uint16_t *depth, const float *cams, int w, int h, float segment_scale, const unsigned char *hands, int B, float *poses_out, float *cnn_out)
+{
+	if (!hands) return ht_update_frames_sized_sync(ctx, side, depth, cams, w, h, segment_scale, B, poses_out, cnn_out);
+	CHECK_READY(ctx); CHECK_MODEL(ctx); CHECK_BATCH(ctx, B);
+	if (!depth || !cams || !poses_out) return HT_ERR_ARG;
+	{ const int r = frames_sized_args_ok(ctx, side, w, h); if (r) return r; }
+	hipStream_t s = ctx->stream;
+	const uint16_t *d_in; const float *d_cin;
+	int r = hands_reserve(ctx, (size_t)w * h);      // (first: it may wait for the stream, and the uploads below are already on it)
+	if (!r) r = stage_frames(ctx, depth, cams, w, h, B, s, &d_in, &d_cin);
+	if (r) return r;
+	HIPCHK(ctx, hipMemcpyAsync(ctx->d_hands_flags, hands, (size_t)B, hipMemcpyHostToDevice, s));
+	if ((r = hands_enqueue(ctx, side, d_in, d_cin, w, h, segment_scale, ctx->d_hands_flags, nullptr, B, ctx->d_poses_out, s))) return r;
+	return finish_sync(ctx, B, s, poses_out, cnn_out, nullptr, (w == side && h == side) ? nullptr : "ht_update_hands");
+}
+
 // HandTracker::update_cnn_model (handtrack.h:734-741) and kickstart (:743-746) for B trackers, frames of any supported size
 extern "C" int ht_update_cnn_model_sync(ht_ctx *ctx, const uint16_t *depth, const float *cams, int w, int h, float segment_scale, int B, int apply_to_handmodel,
                                         float *poses_out, int *accepted_out, float *cnn_out)

@@ -36,6 +36,8 @@ SYMBOLS = (
     "ht_stage_multistep", "ht_stage_multistep_range", "ht_stage_scratch_unibody", "ht_stage_chamber", "ht_profile_enable", "ht_profile_read", "ht_debug_solve_stats", "ht_debug_contact_stats", "ht_debug_solver_build", "ht_debug_reset_flags", "ht_debug_reset_organisation", "ht_update_passes_sync", "ht_job_start", "ht_job_poll", "ht_job_wait", "ht_job_collect", "ht_debug_contact_kernel", "ht_debug_contact_order", "ht_debug_rank_desc", "ht_contact_capacity", "ht_debug_solve_tables", "ht_debug_solve_tables_header", "ht_debug_train_buffers",
     "ht_sensor_out_dims", "ht_sensor_filter", "ht_sensor_filter_dev", "ht_sensor_background", "ht_sensor_background_dev",
     "ht_model_joint_limits", "ht_joint_coords", "ht_joint_coords_dev", "ht_joint_pose", "ht_joint_pose_dev", "ht_sample_poses", "ht_sample_poses_dev",
+    "ht_mirror_frames", "ht_mirror_frames_dev", "ht_mirror_cams", "ht_mirror_cams_dev", "ht_mirror_poses", "ht_mirror_poses_dev", "ht_update_hands_sync", "ht_update_hands_dev", "ht_reserve_hands", "ht_hands_capacity",
+    "ht_model_mirror", "ht_model_body_planes",
     "ht_comm_available", "ht_comm_unique_id", "ht_comm_init", "ht_comm_info", "ht_gather_poses_dev", "ht_gather_wait", "ht_gather_wait_host", "ht_comm_destroy",
 )
 
@@ -185,6 +187,19 @@ def load(build_if_missing=True):
     L.ht_joint_pose_dev.argtypes = [vp, vp, vp, C.c_int, C.c_int, vp, vp]
     L.ht_sample_poses.argtypes = [vp, fp, C.c_int, C.c_uint64, C.c_uint64, C.c_float, C.c_int, fp, fp]
     L.ht_sample_poses_dev.argtypes = [vp, vp, C.c_int, C.c_uint64, C.c_uint64, C.c_float, C.c_int, vp, vp, vp]
+    u8p = C.POINTER(C.c_uint8)
+    L.ht_mirror_frames.argtypes = [vp, u16p, C.c_int, C.c_int, C.c_int, u8p, u16p]
+    L.ht_mirror_frames_dev.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp]
+    L.ht_mirror_cams.argtypes = [vp, fp, C.c_int, C.c_int, u8p, fp]
+    L.ht_mirror_cams_dev.argtypes = [vp, vp, C.c_int, C.c_int, vp, vp, vp]
+    L.ht_mirror_poses.argtypes = [vp, fp, C.c_int, C.c_int, u8p, fp]
+    L.ht_mirror_poses_dev.argtypes = [vp, vp, C.c_int, C.c_int, vp, vp, vp]
+    L.ht_update_hands_sync.argtypes = [vp, C.c_int, u16p, fp, C.c_int, C.c_int, C.c_float, u8p, C.c_int, fp, fp]
+    L.ht_update_hands_dev.argtypes = [vp, C.c_int, vp, vp, C.c_int, C.c_int, C.c_float, vp, vp, C.c_int, vp, vp]
+    L.ht_reserve_hands.argtypes = [vp, C.c_int, C.c_int]
+    L.ht_hands_capacity.argtypes = [vp, C.POINTER(C.c_size_t)]
+    L.ht_model_mirror.argtypes = [vp]
+    L.ht_model_body_planes.argtypes = [vp, C.c_int, fp, fp]
     for name in SYMBOLS:
         if name not in ("ht_last_error", "ht_model_error"):
             getattr(L, name).restype = C.c_int
@@ -344,6 +359,72 @@ class Context:
 
     def update_frames_sized_dev(self, side, d_depth, d_cams, w, h, segment_scale, d_start, B, d_poses_out, stream):
         self._chk(self.L.ht_update_frames_sized_dev(self.h, int(side), d_depth, d_cams, int(w), int(h), float(segment_scale), d_start, B, d_poses_out, stream))
+
+    # ---- left hands (include/ht_mi355x.h "left hands"): hands uint8[B], nonzero = left
+    @staticmethod
+    def _hands(hands, B):
+        if hands is None:
+            return None, None
+        hands = np.ascontiguousarray(hands, np.uint8).reshape(-1)
+        if hands.shape[0] != B:
+            raise HTError("hands: one flag per frame")
+        return hands, hands.ctypes.data_as(C.POINTER(C.c_uint8))
+
+    def mirror_frames(self, depth, hands=None):
+        """depth u16[B,h,w] -> the frames flipped left to right where hands is set (None: everywhere), copied elsewhere (ht_mirror_frames)."""
+        depth = _c(depth, np.uint16); B, h, w = depth.shape
+        hands, hp = self._hands(hands, B)
+        out = np.empty_like(depth)
+        u16 = C.POINTER(C.c_uint16)
+        self._chk(self.L.ht_mirror_frames(self.h, depth.ctypes.data_as(u16), w, h, B, hp, out.ctypes.data_as(u16)))
+        return out
+
+    def mirror_frames_dev(self, d_depth, w, h, B, d_hands, d_depth_out, stream=None):
+        self._chk(self.L.ht_mirror_frames_dev(self.h, d_depth, int(w), int(h), int(B), d_hands, d_depth_out, stream))
+
+    def mirror_cams(self, cams, w, hands=None):
+        """cams [B,12] of frames w pixels wide -> the mirrored cameras (cx' = (w-1) - cx, the pose mirrored) where hands is set (ht_mirror_cams)."""
+        cams = _c(cams, np.float32); B = cams.shape[0]
+        hands, hp = self._hands(hands, B)
+        out = np.empty_like(cams)
+        self._chk(self.L.ht_mirror_cams(self.h, _f(cams), int(w), B, hp, _f(out)))
+        return out
+
+    def mirror_cams_dev(self, d_cams, w, B, d_hands, d_cams_out, stream=None):
+        self._chk(self.L.ht_mirror_cams_dev(self.h, d_cams, int(w), int(B), d_hands, d_cams_out, stream))
+
+    def mirror_poses(self, poses, hands=None):
+        """poses [B,n,7] (or [B,7]) -> (-px,py,pz, qx,-qy,-qz,qw) where hands is set (ht_mirror_poses)."""
+        poses = _c(poses, np.float32); B = poses.shape[0]; per = int(np.prod(poses.shape[1:-1])) if poses.ndim > 2 else 1
+        hands, hp = self._hands(hands, B)
+        out = np.empty_like(poses)
+        self._chk(self.L.ht_mirror_poses(self.h, _f(poses), per, B, hp, _f(out)))
+        return out
+
+    def mirror_poses_dev(self, d_poses, per_frame, B, d_hands, d_poses_out, stream=None):
+        self._chk(self.L.ht_mirror_poses_dev(self.h, d_poses, int(per_frame), int(B), d_hands, d_poses_out, stream))
+
+    def update_hands_sync(self, depth, cams, hands, side=64, segment_scale=0.17, want_cnn=False):
+        """ht_update_frames_sized_sync with a handedness flag per frame (ht_update_hands_sync): the poses of flagged frames are a left hand's; cnn_out stays canonical."""
+        depth = _c(depth, np.uint16); cams = _c(cams, np.float32)
+        B, h, w = depth.shape
+        hands, hp = self._hands(hands, B)
+        poses = np.empty((B, self.nb, POSE), np.float32)
+        cnn = np.empty((B, CNN_OUT), np.float32) if want_cnn else None
+        self._chk(self.L.ht_update_hands_sync(self.h, int(side), depth.ctypes.data_as(C.POINTER(C.c_uint16)), _f(cams), w, h, float(segment_scale), hp, B, _f(poses), _f(cnn) if want_cnn else None))
+        return (poses, cnn) if want_cnn else poses
+
+    def update_hands_dev(self, side, d_depth, d_cams, w, h, segment_scale, d_hands, d_start, B, d_poses_out, stream=None):
+        self._chk(self.L.ht_update_hands_dev(self.h, int(side), d_depth, d_cams, int(w), int(h), float(segment_scale), d_hands, d_start, int(B), d_poses_out, stream))
+
+    def reserve_hands(self, w, h):
+        self._chk(self.L.ht_reserve_hands(self.h, int(w), int(h)))
+
+    def hands_capacity(self):
+        """pixels per frame the left-hand staging holds (0: not allocated)"""
+        n = C.c_size_t()
+        self._chk(self.L.ht_hands_capacity(self.h, C.byref(n)))
+        return n.value
 
     def update_direct_sync(self, depth, cams, side=128, want_cnn=False):
         """BASELINE configs[4] end to end: depth u16[B,side,side] frames that are their own segment, the net of that input size (ht_update_direct_sync)."""
@@ -912,6 +993,37 @@ class HostModel:
         if self.L.ht_model_scale(self.m, float(s)):
             raise HTError("ht_model_scale: bad argument")
 
+    def mirror(self):
+        """the left hand of this model, in place (ht_model_mirror): sign flips of the stored arrays, twice is the identity"""
+        if self.L.ht_model_mirror(self.m):
+            raise HTError("ht_model_mirror: bad argument")
+
+    def body(self, body):
+        """(verts [n,3], tris int32[t,3], planes [p,4], com [3], rest pose [7]) of a body's hull"""
+        nv, nt, npl = C.c_int(), C.c_int(), C.c_int()
+        com = np.empty(3, np.float32); rest = np.empty(7, np.float32)
+        self.L.ht_model_body(self.m, int(body), C.byref(nv), C.byref(nt), C.byref(npl), _f(com), _f(rest))
+        v = np.empty((nv.value, 3), np.float32); t = np.empty((nt.value, 3), np.int32); p = np.empty((npl.value, 4), np.float32)
+        self.L.ht_model_body_mesh(self.m, int(body), _f(v), _i(t))
+        self.L.ht_model_body_planes(self.m, int(body), _f(p), None)
+        return v, t, p, com, rest
+
+    def sdmesh_planes(self, body):
+        """the PolyPlane [t,4] of every triangle of body's subdivision mesh, as the mesh ray cast reads it"""
+        n = C.c_int()
+        self.L.ht_model_body_sdmesh(self.m, int(body), C.byref(n), None)
+        p = np.empty((n.value // 3, 4), np.float32)
+        self.L.ht_model_body_planes(self.m, int(body), None, _f(p))
+        return p
+
+    def hitcheck(self, poses, v0, v1):
+        """(impact[3], normal[3], body) of the segment v0 -> v1 against the hulls at centre-of-mass poses [nb,7] (ht_model_hitcheck)"""
+        poses = _c(poses, np.float32); v0 = _c(v0, np.float32); v1 = _c(v1, np.float32)
+        imp = np.empty(3, np.float32); nrm = np.empty(3, np.float32); b = C.c_int()
+        if self.L.ht_model_hitcheck(self.m, _f(poses), _f(v0), _f(v1), _f(imp), _f(nrm), C.byref(b)):
+            raise HTError("ht_model_hitcheck: bad argument")
+        return imp, nrm, b.value
+
     def joint_limits(self):
         lo = np.empty((self.nj, 3), np.float32); hi = np.empty((self.nj, 3), np.float32); sw = np.zeros(self.nj, np.int32)
         if self.L.ht_model_joint_limits(self.m, _f(lo), _f(hi), _i(sw)):
@@ -946,3 +1058,6 @@ class HostModel:
         if self.L.ht_model_render_mesh(self.m, _f(poses), _f(cam), int(w), int(h), float(far), float(pixel_offset), depth.ctypes.data_as(C.POINTER(C.c_uint16)), body.ctypes.data_as(C.POINTER(C.c_int8))):
             raise HTError("ht_model_render_mesh: bad argument")
         return depth, body
+
+
+Model = HostModel      # the name the C ABI uses (ht_model): Model.mirror() is ht_model_mirror

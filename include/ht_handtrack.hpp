@@ -125,6 +125,9 @@ inline DCamera camsub(const DCamera &c, int s)                                  
 {
 	return DCamera({ c.dim().x / s, c.dim().y / s }, { c.focal().x / (float)s, c.focal().y / (float)s }, { c.principal().x / (float)s, c.principal().y / (float)s }, c.depth_scale, c.pose);
 }
+// Addition (left hands, include/ht_mi355x.h "left hands"): a pose under the mirror x -> -x, (px,py,pz, qx,qy,qz,qw) -> (-px,py,pz, qx,-qy,-qz,qw)
+inline Pose mirrored(const Pose &p) { Pose q = p; q.position.x = -p.position.x; q.orientation.y = -p.orientation.y; q.orientation.z = -p.orientation.z; return q; }
+inline std::vector<Pose> mirrored(std::vector<Pose> v) { for (auto &p : v) p = mirrored(p); return v; }
 struct Mesh { std::vector<float3> verts; std::vector<int3> tris; Pose pose; float4 hack{ 1, 1, 1, 1 }; std::string material; };      // mesh.h (what GetMeshes hands to a renderer)
 namespace detail
 {
@@ -138,6 +141,17 @@ inline Mesh subdivision_mesh(const ht_model *m, int body)
 	ht_model_body_sdmesh(m, body, nullptr, v.data());
 	for (int i = 0; i < nv; i++) mesh.verts.push_back({ v[3 * i], v[3 * i + 1], v[3 * i + 2] });
 	for (int i = 0; i + 2 < nv; i += 3) mesh.tris.push_back({ i, i + 1, i + 2 });
+	return mesh;
+}
+// PhysModel::meshes[body]: the collision hull in the centre-of-mass frame (ht_model_body_mesh)
+inline Mesh hull_mesh(const ht_model *m, int body)
+{
+	Mesh mesh; int nv = 0, nt = 0;
+	ht_model_body(m, body, &nv, &nt, nullptr, nullptr, nullptr);
+	std::vector<float> v((size_t)nv * 3); std::vector<int> t((size_t)nt * 3);
+	ht_model_body_mesh(m, body, v.data(), t.data());
+	for (int i = 0; i < nv; i++) mesh.verts.push_back({ v[3 * i], v[3 * i + 1], v[3 * i + 2] });
+	for (int i = 0; i < nt; i++) mesh.tris.push_back({ t[3 * i], t[3 * i + 1], t[3 * i + 2] });
 	return mesh;
 }
 }
@@ -321,12 +335,21 @@ struct HandTracker                                                              
 	// on a second device context beside the caller's passes and is collected by a later call, when it is through (the 1 ms wait_for = one poll); the caller's latency is
 	// the passes alone.  overlapped_wait = true (tests) waits for the job before the passes: the same sequence of operations as the synchronous call.
 	bool overlapped_update = false, overlapped_wait = false;
+	// Addition (the reference tracks right hands only; its README lists left / right as open work): the hand in front of the camera is a LEFT hand.  update,
+	// update_cnn_model, kickstart and SetPose, and handmodel / othermodel's GetPose, GetPoseUser, SetPose and GetMeshes then speak the left hand's space.  Inside, the
+	// tracker stays a right hand's on the mirror image (include/ht_mi355x.h "left hands"): cnn_input, cnn_output, the heat maps and cnn_output_analysis stay CANONICAL,
+	// they show the mirrored frame the net saw.  Set it before the first frame; changing it on a running tracker wants a new SetPose.
+	bool left_hand = false;
 	// PhysModel facade of the two tracked models (handtrack.h:517-518): the members the applications use on them (physmodel.h:295-303,345,433-435)
 	struct TrackedModel
 	{
-		std::vector<Pose> GetPose() const { return read(false); }                                                    // body poses (centre-of-mass frames)
-		std::vector<Pose> GetPoseUser() const { return read(true); }                                                 // rig space: RigidBody::PositionUser physics.h:142
-		TrackedModel &SetPose(const std::vector<Pose> &poses)                                                        // poses only, momenta untouched (physmodel.h:435)
+		// (Addition: with HandTracker::left_hand set, GetPose, GetPoseUser, SetPose and GetMeshes speak the left hand's space -- the mirror image of the slot's canonical
+		// state, which stays a right hand's; the joint coordinates are those of the mirror image, the same numbers for both hands.)
+		std::vector<Pose> GetPose() const { return left() ? mirrored(read(false)) : read(false); }                   // body poses (centre-of-mass frames)
+		std::vector<Pose> GetPoseUser() const { return left() ? mirrored(read(true)) : read(true); }                 // rig space: RigidBody::PositionUser physics.h:142
+		TrackedModel &SetPose(const std::vector<Pose> &poses) { return left() ? set(mirrored(poses)) : set(poses); } // poses only, momenta untouched (physmodel.h:435)
+	private:
+		TrackedModel &set(const std::vector<Pose> &poses)
 		{
 			std::vector<float> st((size_t)nb_ * HT_STATE);
 			check(ctx_, ht_get_state(ctx_, which_, 0, 1, st.data()));
@@ -334,13 +357,15 @@ struct HandTracker                                                              
 			check(ctx_, ht_set_state(ctx_, which_, 0, 1, st.data()));
 			return *this;
 		}
+	public:
 		// physmodel.h:295-303: the subdivision meshes live in rig space (pose = PositionUser, orientation), the hull meshes in the centre-of-mass frames
 		std::vector<Mesh> &GetMeshes(int show_subdiv = 0)
 		{
 			const std::vector<Pose> p = GetPose(), u = GetPoseUser();
-			for (size_t b = 0; b < sdmeshes_.size() && b < u.size(); b++) sdmeshes_[b].pose = u[b];
-			for (size_t b = 0; b < meshes_.size() && b < p.size(); b++) meshes_[b].pose = p[b];
-			return show_subdiv ? sdmeshes_ : meshes_;
+			std::vector<Mesh> &sd = left() ? sdmeshes_left_ : sdmeshes_, &hull = left() ? meshes_left_ : meshes_;      // (addition: a left hand draws the mirrored meshes, ht_model_mirror)
+			for (size_t b = 0; b < sd.size() && b < u.size(); b++) sd[b].pose = u[b];
+			for (size_t b = 0; b < hull.size() && b < p.size(); b++) hull[b].pose = p[b];
+			return show_subdiv ? sd : hull;
 		}
 		// void FitPointCloud(const std::vector<float3> &points, std::vector<LimitLinear> linears = {}, std::vector<LimitAngular> angulars = {}, float microforce = 1.0f)
 		// (physmodel.h:345-356): one fit step of this model against a point cloud under the caller's rows, the cloud rows, the joint rows and the collision rows
@@ -375,7 +400,7 @@ struct HandTracker                                                              
 			std::vector<Pose> poses(nb_);
 			for (int b = 0; b < nb_; b++) { const float *s = &p[(size_t)b * HT_POSE]; poses[b].position = { s[0], s[1], s[2] }; poses[b].orientation = { s[3], s[4], s[5], s[6] }; }
 			poses[0] = now[0];      // to the bit (the walk takes the root through the rig frame and back)
-			return SetPose(poses);
+			return set(poses);
 		}
 	private:
 		void joints(std::vector<float3> *c, std::vector<float> *g) const
@@ -390,6 +415,8 @@ struct HandTracker                                                              
 		}
 		friend struct HandTracker;
 		ht_ctx *ctx_ = nullptr; int which_ = 0, nb_ = 0; std::vector<float3> com_; std::vector<Mesh> meshes_, sdmeshes_;
+		const bool *left_ = nullptr; std::vector<Mesh> meshes_left_, sdmeshes_left_;      // (addition) HandTracker::left_hand, and the meshes of the mirrored model
+		bool left() const { return left_ && *left_; }
 		std::vector<Pose> read(bool user) const
 		{
 			std::vector<float> st((size_t)nb_ * HT_STATE);
@@ -426,16 +453,15 @@ struct HandTracker                                                              
 			if (ht_model_open(model_path.c_str(), 1, &m) == HT_OK)
 				for (int b = 0; b < nb_; b++)
 				{
-					int nv = 0, nt = 0; float com[3] = { 0, 0, 0 };
-					ht_model_body(m, b, &nv, &nt, nullptr, com, nullptr);
-					Mesh mesh; std::vector<float> v((size_t)nv * 3); std::vector<int> t((size_t)nt * 3);
-					ht_model_body_mesh(m, b, v.data(), t.data());
-					for (int i = 0; i < nv; i++) mesh.verts.push_back({ v[3 * i], v[3 * i + 1], v[3 * i + 2] });
-					for (int i = 0; i < nt; i++) mesh.tris.push_back({ t[3 * i], t[3 * i + 1], t[3 * i + 2] });
-					handmodel.com_.push_back({ com[0], com[1], com[2] }); handmodel.meshes_.push_back(mesh); handmodel.sdmeshes_.push_back(detail::subdivision_mesh(m, b));
+					float com[3] = { 0, 0, 0 };
+					ht_model_body(m, b, nullptr, nullptr, nullptr, com, nullptr);
+					handmodel.com_.push_back({ com[0], com[1], com[2] }); handmodel.meshes_.push_back(detail::hull_mesh(m, b)); handmodel.sdmeshes_.push_back(detail::subdivision_mesh(m, b));
 				}
+			if (m && !handmodel.meshes_.empty() && ht_model_mirror(m) == HT_OK)      // (addition) the left hand's meshes: the same model mirrored
+				for (int b = 0; b < nb_; b++) { handmodel.meshes_left_.push_back(detail::hull_mesh(m, b)); handmodel.sdmeshes_left_.push_back(detail::subdivision_mesh(m, b)); }
 			if (m) ht_model_close(m);
 			othermodel.com_ = handmodel.com_; othermodel.meshes_ = handmodel.meshes_; othermodel.sdmeshes_ = handmodel.sdmeshes_;
+			othermodel.meshes_left_ = handmodel.meshes_left_; othermodel.sdmeshes_left_ = handmodel.sdmeshes_left_; handmodel.left_ = othermodel.left_ = &left_hand;
 			handmodel.ctx_ = othermodel.ctx_ = ctx_; handmodel.nb_ = othermodel.nb_ = nb_; handmodel.which_ = 0; othermodel.which_ = 1;
 			for (int b = 0; b < nb_; b++) { handmodel.rigidbodies.push_back(RigidBody{ ctx_, 0, b }); othermodel.rigidbodies.push_back(RigidBody{ ctx_, 1, b }); }
 		}
@@ -462,7 +488,7 @@ struct HandTracker                                                              
 		check(ctx_, ht_set_params(ctx_, &p));      // also carries physics_iterations(_post), physics_use_collision, physics_weak_force, bone_sum_error_scale, unibody_force
 		if (pfe != pfe0) check(ctx_, ht_set_tracker_flags(ctx_, 0, 1, &pfe, &ini));
 	}
-	void SetPose(const std::vector<Pose> &pose) { check(ctx_, ht_tracker_reset(ctx_, 0, 1, flat(pose).data())); }          // handmodel/othermodel.SetPose
+	void SetPose(const std::vector<Pose> &pose) { check(ctx_, ht_tracker_reset(ctx_, 0, 1, flat(left_hand ? mirrored(pose) : pose).data())); }          // handmodel/othermodel.SetPose
 
 	std::vector<Pose> update(Image<unsigned short> dimage)                                   // handtrack.h:748
 	{
@@ -472,6 +498,10 @@ struct HandTracker                                                              
 		push_params();
 		const bool full = dimage.dim().x != 64 || dimage.dim().y != 64;
 		std::vector<float> out((size_t)nb_ * HT_POSE);
+		// Addition: a left hand.  The synchronous call hands the frame over with one flag (ht_update_hands_sync mirrors on the device); everything else below -- the
+		// overlapped arrangement, the segment for the visualisation members -- takes the canonical frame, mirrored here with the host calls, and the poses are mirrored after.
+		const Image<unsigned short> given = (left_hand && !overlapped_update) ? dimage : Image<unsigned short>();
+		if (left_hand) dimage = mirror_image(dimage);
 		const DCamera &fc = dimage.cam;
 		const float fcam[HT_CAM] = { fc.focal().x, fc.focal().y, fc.principal().x, fc.principal().y, fc.depth_scale, fc.pose.position.x, fc.pose.position.y, fc.pose.position.z,
 		                             fc.pose.orientation.x, fc.pose.orientation.y, fc.pose.orientation.z, fc.pose.orientation.w };
@@ -495,6 +525,14 @@ struct HandTracker                                                              
 				job_in_flight_ = false;
 			}
 			check(ctx_, ht_update_passes_sync(ctx_, dimage.raster.data(), fcam, dimage.dim().x, dimage.dim().y, 1, out.data()));
+			if (left_hand) check(ctx_, ht_mirror_poses(ctx_, out.data(), nb_, 1, nullptr, out.data()));
+		}
+		else if (left_hand)
+		{
+			const uint8_t left = 1; float gcam[HT_CAM]; cam12(given.cam, gcam);
+			check(ctx_, ht_update_hands_sync(ctx_, 64, given.raster.data(), gcam, given.dim().x, given.dim().y, segment_scale, &left, 1, out.data(), cnn_output.data()));
+			if (full) dimage = segment(dimage, 0xF, { 0.1f, drangey }, segment_scale);
+			fill_visualisation(dimage);      // canonical: the mirrored frame's segment, as the net saw it
 		}
 		else
 		{
@@ -575,6 +613,7 @@ private:
 	std::vector<Pose> cnn_job(Image<unsigned short> dimage, bool apply)
 	{
 		push_params();
+		if (left_hand) dimage = mirror_image(dimage);      // (addition) the job runs on the canonical frame; its pose is mirrored on the way out
 		const DCamera &fc = dimage.cam;
 		const float fcam[HT_CAM] = { fc.focal().x, fc.focal().y, fc.principal().x, fc.principal().y, fc.depth_scale, fc.pose.position.x, fc.pose.position.y, fc.pose.position.z,
 		                             fc.pose.orientation.x, fc.pose.orientation.y, fc.pose.orientation.z, fc.pose.orientation.w };
@@ -584,7 +623,25 @@ private:
 		fill_visualisation(dimage);
 		std::vector<Pose> pose;
 		if (accepted) { pose.resize(nb_); for (int b = 0; b < nb_; b++) { const float *p = &out[(size_t)b * HT_POSE]; pose[b].position = { p[0], p[1], p[2] }; pose[b].orientation = { p[3], p[4], p[5], p[6] }; } }
-		return pose;
+		return left_hand ? mirrored(pose) : pose;
+	}
+	// (addition) the frame and its camera under the mirror, by the host mirror calls (ht_mirror_frames, ht_mirror_cams)
+	static void cam12(const DCamera &c, float *cam)
+	{
+		const float v[HT_CAM] = { c.focal().x, c.focal().y, c.principal().x, c.principal().y, c.depth_scale, c.pose.position.x, c.pose.position.y, c.pose.position.z,
+		                          c.pose.orientation.x, c.pose.orientation.y, c.pose.orientation.z, c.pose.orientation.w };
+		for (int i = 0; i < HT_CAM; i++) cam[i] = v[i];
+	}
+	Image<unsigned short> mirror_image(const Image<unsigned short> &im) const
+	{
+		const int w = im.dim().x, h = im.dim().y;
+		float cam[HT_CAM], co[HT_CAM]; cam12(im.cam, cam);
+		std::vector<unsigned short> flipped(im.raster.size());
+		if (im.raster.size() != (size_t)w * h) throw std::runtime_error("HandTracker: the raster does not match the camera's dimensions");
+		check(ctx_, ht_mirror_frames(ctx_, im.raster.data(), w, h, 1, nullptr, flipped.data()));
+		check(ctx_, ht_mirror_cams(ctx_, cam, w, 1, nullptr, co));
+		Pose pose; pose.position = { co[5], co[6], co[7] }; pose.orientation = { co[8], co[9], co[10], co[11] };
+		return Image<unsigned short>(DCamera({ w, h }, { co[0], co[1] }, { co[2], co[3] }, co[4], pose), std::move(flipped));
 	}
 	// cnn_input and the drawn parts of cnn_output_analysis, filled on the host from what the device returned (handtrack.h:700, 225, 236-238)
 	void fill_visualisation(const Image<unsigned short> &tile)
@@ -762,17 +819,28 @@ public:
 		int nb = 0; ht_model_counts(m, &nb, nullptr);
 		for (int b = 0; b < nb; b++)
 		{
-			int nv = 0, nt = 0; float com[3], rest[7];
-			ht_model_body(m, b, &nv, &nt, nullptr, com, rest);
+			float com[3], rest[7];
+			ht_model_body(m, b, nullptr, nullptr, nullptr, com, rest);
 			Body rb; rb.position = { rest[0], rest[1], rest[2] }; rb.orientation = { rest[3], rest[4], rest[5], rest[6] }; rb.com = { com[0], com[1], com[2] };
 			rigidbodies.push_back(rb);
-			Mesh mesh; std::vector<float> v((size_t)nv * 3); std::vector<int> t((size_t)nt * 3);
-			ht_model_body_mesh(m, b, v.data(), t.data());
-			for (int i = 0; i < nv; i++) mesh.verts.push_back({ v[3 * i], v[3 * i + 1], v[3 * i + 2] });
-			for (int i = 0; i < nt; i++) mesh.tris.push_back({ t[3 * i], t[3 * i + 1], t[3 * i + 2] });
-			meshes.push_back(mesh);
+			meshes.push_back(detail::hull_mesh(m, b));
 			sdmeshes.push_back(detail::subdivision_mesh(m, b));
 		}
+	}
+	// Addition: this model becomes its own mirror image (ht_model_mirror: the left hand of a right-hand model, and back): hulls, subdivision meshes, centres of
+	// mass and what HitCheck reads, and the bodies' current poses with them, so a posed model stays the same hand seen in a mirror.
+	PhysModel &Mirror()
+	{
+		if (ht_model_mirror(m_.get()) != HT_OK) throw std::runtime_error("PhysModel::Mirror failed");
+		for (size_t b = 0; b < rigidbodies.size(); b++)
+		{
+			float com[3] = { 0, 0, 0 };
+			ht_model_body(m_.get(), (int)b, nullptr, nullptr, nullptr, com, nullptr);
+			const Pose p = mirrored(rigidbodies[b].pose());
+			rigidbodies[b].position = p.position; rigidbodies[b].orientation = p.orientation; rigidbodies[b].com = { com[0], com[1], com[2] };
+			meshes[b] = detail::hull_mesh(m_.get(), (int)b); sdmeshes[b] = detail::subdivision_mesh(m_.get(), (int)b);
+		}
+		return *this;
 	}
 	std::vector<Pose> GetPose() const { std::vector<Pose> p; for (auto &rb : rigidbodies) p.push_back(rb.pose()); return p; }                                            // physmodel.h:433
 	std::vector<Pose> GetPoseUser() const { std::vector<Pose> p; for (auto &rb : rigidbodies) { Pose q = rb.pose(); q.position = rb.PositionUser(); p.push_back(q); } return p; }      // :434
@@ -798,7 +866,7 @@ inline PhysModel LoadHandModel(const char *jsonfile = "../assets/model_hand.json
 
 #ifdef HT_MI355X_GLOBAL_NAMES      // the reference's headers declare these names at global scope
 using ht_mi355x::float2; using ht_mi355x::float3; using ht_mi355x::float4; using ht_mi355x::int2; using ht_mi355x::int3;
-using ht_mi355x::Pose; using ht_mi355x::DCamera; using ht_mi355x::Image; using ht_mi355x::Mesh; using ht_mi355x::CNN; using ht_mi355x::HandTracker; using ht_mi355x::PhysModel;
+using ht_mi355x::Pose; using ht_mi355x::mirrored; using ht_mi355x::DCamera; using ht_mi355x::Image; using ht_mi355x::Mesh; using ht_mi355x::CNN; using ht_mi355x::HandTracker; using ht_mi355x::PhysModel;
 using ht_mi355x::RigidBody; using ht_mi355x::LimitLinear; using ht_mi355x::LimitAngular; using ht_mi355x::PhysicsUpdate; using ht_mi355x::Addresses;
 using ht_mi355x::HandSegmentVR; using ht_mi355x::RSCam; using ht_mi355x::PointCloud; using ht_mi355x::camsub; using ht_mi355x::GatherHandExpectedCNN; using ht_mi355x::PoseInitializerCNN; using ht_mi355x::LoadHandModel;
 #endif

@@ -467,6 +467,52 @@ int ht_sensor_filter_dev(ht_ctx *ctx, int kind, const uint16_t *d_depth, const u
 int ht_sensor_background(ht_ctx *ctx, const uint16_t *depth, int w, int h, int B, int fudge, int init, uint16_t *background);
 int ht_sensor_background_dev(ht_ctx *ctx, const uint16_t *d_depth, int w, int h, int B, int fudge, int init, uint16_t *d_background, void *stream);
 
+/* ---- left hands (an addition: the reference's model, nets and segmentation are a right hand's; its README lists left / right as open work) ----------------
+ * A left hand seen by a camera is the mirror image of a right hand seen by the mirrored camera.  The mirror M is x -> -x of the camera's space:
+ *   frame  [h][w] u16:  F'[y][x] = F[y][w-1-x]
+ *   camera [12]:        focal, cy and depth_scale unchanged; cx' = (float)(w-1) - cx, one fp32 subtraction (DCamera::deprojectz's whole-pixel convention,
+ *                       misc_image.h:48, the one PointCloud, FakeDepth and pixel_offset 0 use); the camera's pose mirrored as a pose
+ *   pose   [7]:         (px,py,pz, qx,qy,qz,qw) -> (-px,py,pz, qx,-qy,-qz,qw): the pose of a bone whose geometry is x-negated in its own frame; it holds for
+ *                       centre-of-mass poses and rig-space (user) poses alike.  Sign BITS are flipped: -0.0 and NaNs follow.
+ * A left-hand update mirrors the frame, its camera and (if given) its start poses, runs the existing update on them in the frame's slot, and mirrors the poses
+ * that come out.  The slot's state stays CANONICAL (the right hand's, mirrored space) from update to update: ht_get_state / ht_set_state, ht_tracker_reset,
+ * cnn_out and ht_get_cnn_results, the stage calls and ht_joint_coords all speak the canonical space -- a caller who seeds a left slot mirrors the poses first
+ * (ht_mirror_poses), and the joint coordinates of a left hand are those of its mirror image: the same numbers for both hands.  Changing a slot's flag without
+ * re-seeding it is the caller's error.  Which hand a frame shows is not decided here.
+ * hands [B] (uint8, nonzero = left) is optional everywhere: NULL means every frame for the three mirror calls, and NO frame for ht_update_hands_*.
+ * ht_mirror_frames    depth [B][h][w] -> depth_out [B][h][w]; frames whose flag is 0 are copied.  w, h in [1, 4096].  Not in place: equal or overlapping
+ *                     buffers are HT_ERR_ARG.  The device form moves 16 bytes per thread when w % 8 == 0 and both pointers are 16-byte aligned, 8 or 4
+ *                     bytes for lesser widths and alignments, and single pixels for a buffer aligned to two bytes only (a view one pixel into an allocation).
+ * ht_mirror_cams      cams [B][12] -> cams_out [B][12] for frames w pixels wide; may be in place.
+ * ht_mirror_poses     poses [B][per_frame][7] -> poses_out; per_frame poses per frame (nb for a hand, 1 for single camera poses); may be in place.
+ *                     For all three B is not bounded by max_batch (no tracker slot; the host forms stage through a buffer that follows the largest call);
+ *                     B = 0 does nothing; the *_dev forms take device buffers (hands included) and are asynchronous on `stream`.
+ * ht_update_hands_*   ht_update_frames_sized_* with a handedness flag per frame: shapes, sides, errors and point-capacity rules are exactly that call's,
+ *                     64x64 tiles and side x side frames included (the update runs on the context's own 16-byte aligned staging, so ht_update_direct_dev's
+ *                     alignment rule is met whatever d_depth is).  d_hands is a DEVICE pointer [B].  Without flags (NULL) the call forwards to
+ *                     ht_update_frames_sized_* with the caller's own pointers: no staging, no extra launch, the same bits.  With flags it enqueues the three
+ *                     mirror kernels, the update on the staging, and the pose mirror in place on d_poses_out; it only enqueues, so it can be captured into a
+ *                     HIP graph once its staging exists.  cnn_out stays canonical.
+ * ht_reserve_hands    allocates that staging ahead of time: max_batch frames of w x h pixels (at most 640x480), cameras and start poses.  Nothing is allocated
+ *                     before the first flagged call or this one; it never shrinks; a flagged call that finds it too small grows it with one synchronising
+ *                     re-allocation, as ht_reserve_points does.  1024 frames of 640x480 are 629 MB.  ht_hands_capacity reads the pixels per frame it holds.
+ * ht_model_mirror     host only: mirrors the drawn and ray-cast geometry of an untracked model in place, by sign flips of the stored arrays: x of the hull vertices,
+ *                     the sdmesh corners, the centres of mass and every stored plane (hull planes and the meshes' PolyPlanes) negated, the rest poses mirrored as
+ *                     poses, every triangle (hull and sdmesh) keeping its first corner and swapping the other two.  Applied twice it restores every array byte for
+ *                     byte; it commutes with ht_model_scale; ht_model_joint_limits is unchanged by it. */
+int ht_mirror_frames(ht_ctx *ctx, const uint16_t *depth, int w, int h, int B, const uint8_t *hands, uint16_t *depth_out);
+int ht_mirror_frames_dev(ht_ctx *ctx, const uint16_t *d_depth, int w, int h, int B, const uint8_t *d_hands, uint16_t *d_depth_out, void *stream);
+int ht_mirror_cams(ht_ctx *ctx, const float *cams, int w, int B, const uint8_t *hands, float *cams_out);
+int ht_mirror_cams_dev(ht_ctx *ctx, const float *d_cams, int w, int B, const uint8_t *d_hands, float *d_cams_out, void *stream);
+int ht_mirror_poses(ht_ctx *ctx, const float *poses, int per_frame, int B, const uint8_t *hands, float *poses_out);
+int ht_mirror_poses_dev(ht_ctx *ctx, const float *d_poses, int per_frame, int B, const uint8_t *d_hands, float *d_poses_out, void *stream);
+int ht_update_hands_sync(ht_ctx *ctx, int side, const uint16_t *depth, const float *cams, int w, int h, float segment_scale, const uint8_t *hands, int B, float *poses_out, float *cnn_out);
+int ht_update_hands_dev(ht_ctx *ctx, int side, const uint16_t *d_depth, const float *d_cams, int w, int h, float segment_scale, const uint8_t *d_hands, const float *d_start_poses, int B, float *d_poses_out, void *stream);
+int ht_reserve_hands(ht_ctx *ctx, int w, int h);
+int ht_hands_capacity(ht_ctx *ctx, size_t *frame_pixels);
+int ht_model_mirror(ht_model *m);
+int ht_model_body_planes(const ht_model *m, int body, float *hull_planes, float *mesh_planes);      /* the stored planes ht_model_mirror flips: the hull's [nplanes][4] (ht_model_body), the PolyPlane [t][4] of every sdmesh triangle; either may be NULL */
+
 /* ---- annotation fit loop ---------------------------------------------------------------------------------------------
  * ht_slowfit          replaces  void HandTracker::slowfit(const std::vector<float3> &points, int hold, const std::vector<Pose> &refpose,
  *                     int steps_ = 6, RigidBody *selectrb = NULL, const float3 &spoint, const float3 &rbpoint, const std::vector<float4> &crays)
