@@ -119,6 +119,10 @@ struct ht_ctx
 	// ht_update_hands_*: the mirrored inputs an update of flagged frames runs on, [B][hands_px] pixels, [B][12], [B][nb][7], and the flags of the host form [B]; nothing until the
 	// first flagged call or ht_reserve_hands, then grown to the largest frame (hands_reserve, ht_solver_api.hip: one synchronising re-allocation, never smaller)
 	uint16_t *d_hands_frames = nullptr; size_t hands_px = 0; float *d_hands_cams = nullptr, *d_hands_start = nullptr; unsigned char *d_hands_flags = nullptr;
+	// ht_split_hands (ht_split.hip): the host form's staging, and the label image of a call whose caller wants none (the frames are cut along it), both grown to the largest
+	// call (dev_grow).  ht_update_two_hands_*: its info [B/2][2][8] when the caller wants none, and the flags 0, 1, 0, 1, ... [B] its pose mirrors take (made once)
+	char *d_split = nullptr; size_t split_cap = 0; uint16_t *d_split_labels = nullptr; size_t split_labels_cap = 0;
+	int32_t *d_two_info = nullptr; unsigned char *d_two_flags = nullptr;
 };
 
 // The net of a side x side input; any other side is refused here, and only here

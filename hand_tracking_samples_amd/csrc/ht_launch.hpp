@@ -128,3 +128,11 @@ int ht_mirror_frames_pixels(const void *in, const void *out, int w);
 void ht_launch_mirror_frames(const uint16_t *in, int w, int h, int B, const unsigned char *hands, uint16_t *out, hipStream_t s);
 void ht_launch_mirror_cams(const float *in, int w, int B, const unsigned char *hands, float *out, hipStream_t s);
 void ht_launch_mirror_poses(const float *in, int per_frame, int B, const unsigned char *hands, float *out, hipStream_t s);
+// ht_split.hip: the blobs of frames [B][h][w] (k_split_label: info [B][2][8], eligible components [B] or null, label images [B][h/4][w/4]), one masked frame per hand
+// out [B][2][h][w] cut along those labels (the left one mirrored with HT_SPLIT_MIRROR_LEFT; in and out must not overlap) and the cameras [B][2][12].  ht_split_check: the
+// arguments every entry point refuses (HT_ERR_ARG and ctx->err, named after `fn`)
+struct ht_ctx;
+int ht_split_check(ht_ctx *ctx, const char *fn, int w, int h, int range_lo, int range_hi, int min_pixels, int far, int flags);
+void ht_launch_split_label(const uint16_t *depth, int w, int h, int B, unsigned lo, unsigned hi, unsigned max_step, int min_pixels, int flags, int32_t *info, int32_t *ncomp, uint16_t *labels, hipStream_t s);
+void ht_launch_split_write(const uint16_t *in, const uint16_t *labels, const int32_t *info, int w, int h, int B, unsigned far, int flags, uint16_t *out, hipStream_t s);
+void ht_launch_split_cams(const float *in, int w, int B, int flags, float *out, hipStream_t s);

@@ -20,6 +20,7 @@
 //   k_mirror_poses
 #include <string.h>
 #include "ht_host.hpp"
+#include "ht_mirror.hpp"
 
 #define MR_THREADS 256
 
@@ -65,11 +66,7 @@ __global__ __launch_bounds__(MR_THREADS) void k_mirror_cams(const unsigned *in, 
 	if (i >= n) return;
 	const unsigned f = i / HT_CAM, k = i - f * HT_CAM;
 	unsigned v = in[i];
-	if (mr_left(hands, f))
-	{
-		if (k == 2) v = __float_as_uint(wm1 - __uint_as_float(v));
-		else if (k == 5 || k == 9 || k == 10) v ^= 0x80000000u;
-	}
+	if (mr_left(hands, f)) v = ht_mirror_cam_word(v, k, wm1);
 	out[i] = v;
 }
 // poses [B][per_frame][7]: px, qy, qz change sign

@@ -776,6 +776,73 @@ extern "C" int ht_update_hands_sync(ht_ctx *ctx, int side, const uint16_t *depth
 	return finish_sync(ctx, B, s, poses_out, cnn_out, nullptr, (w == side && h == side) ? nullptr : "ht_update_hands");
 }
 
+// ---- two hands in one frame (an addition) ------------------------------------------------------------------------------------------------
+// B frames become 2B hand frames: the split (ht_split.hip) writes frame i's right hand into slot 2i of the hands staging above and its left hand, mirrored, into slot
+// 2i + 1, with their cameras; ht_update_frames_sized_dev runs on the staging; the odd slots' poses are mirrored back.  Slot state stays canonical.
+struct two_hands_args { uint16_t lo, hi, step, far; int min_pixels, flags; };
+static int two_hands_check(ht_ctx *ctx, int side, int w, int h, const two_hands_args &a, int B)
+{
+	if (B < 1 || 2 * (long long)B > ctx->B) { ctx->err = "ht_update_two_hands: two slots per frame: 2 * B exceeds the capacity given to ht_create"; return HT_ERR_ARG; }
+	{ const int r = frames_sized_args_ok(ctx, side, w, h); if (r) return r; }
+	return ht_split_check(ctx, "ht_update_two_hands", w, h, a.lo, a.hi, a.min_pixels, a.far, a.flags);
+}
+static int two_hands_reserve(ht_ctx *ctx, int w, int h)
+{
+	int r = hands_reserve(ctx, (size_t)w * h);
+	if (r) return r;
+	if (!ctx->d_two_flags)
+	{
+		unsigned char *f = nullptr;
+		if ((r = dev_alloc(ctx, &ctx->d_two_info, (size_t)ctx->B * 8)) || (r = dev_alloc(ctx, &f, (size_t)ctx->B))) return r;
+		std::vector<unsigned char> pat((size_t)ctx->B);
+		for (size_t i = 0; i < pat.size(); i++) pat[i] = (unsigned char)(i & 1);
+		HIPCHK(ctx, hipMemcpy(f, pat.data(), pat.size(), hipMemcpyHostToDevice));
+		ctx->d_two_flags = f;
+	}
+	const size_t cells = (size_t)(ctx->B / 2) * (w / 4) * (h / 4);
+	if (cells > ctx->split_labels_cap) HIPCHK(ctx, ht_sync_all(ctx));
+	return dev_grow(ctx, &ctx->d_split_labels, &ctx->split_labels_cap, cells);
+}
+// checked and reserved: split, update, mirror back, all enqueued on s
+static int two_hands_enqueue(ht_ctx *ctx, int side, const uint16_t *d_depth, const float *d_cams, int w, int h, float segment_scale, const two_hands_args &a, const float *d_start, int B, float *d_poses_out,
+                             int32_t *d_info, hipStream_t s)
+{
+	const int nb = ctx->model.nb, flags = a.flags | HT_SPLIT_MIRROR_LEFT;
+	{ ht_prof_scope ps(ctx, "k_split_label", s); ht_launch_split_label(d_depth, w, h, B, a.lo, a.hi, a.step, a.min_pixels, flags, d_info, nullptr, ctx->d_split_labels, s); }
+	{ ht_prof_scope ps(ctx, "k_split_write", s); ht_launch_split_write(d_depth, ctx->d_split_labels, d_info, w, h, B, a.far, flags, ctx->d_hands_frames, s); }
+	{ ht_prof_scope ps(ctx, "k_split_cams", s); ht_launch_split_cams(d_cams, w, B, flags, ctx->d_hands_cams, s); }
+	if (d_start) { ht_prof_scope ps(ctx, "k_mirror_poses", s); ht_launch_mirror_poses(d_start, nb, 2 * B, ctx->d_two_flags, ctx->d_hands_start, s); }
+	{ const int r = ht_update_frames_sized_dev(ctx, side, ctx->d_hands_frames, ctx->d_hands_cams, w, h, segment_scale, d_start ? ctx->d_hands_start : nullptr, 2 * B, d_poses_out, s); if (r) return r; }
+	{ ht_prof_scope ps(ctx, "k_mirror_poses", s); ht_launch_mirror_poses(d_poses_out, nb, 2 * B, ctx->d_two_flags, d_poses_out, s); }
+	return HT_OK;
+}
+extern "C" int ht_update_two_hands_dev(ht_ctx *ctx, int side, const uint16_t *d_depth, const float *d_cams, int w, int h, float segment_scale, uint16_t range_lo, uint16_t range_hi, uint16_t max_step,
+                                       int min_pixels, uint16_t far, int flags, const float *d_start_poses, int B, float *d_poses_out, int32_t *d_info, void *stream)
+{
+	CHECK_READY(ctx); CHECK_MODEL(ctx);
+	if (!d_depth || !d_cams || !d_poses_out) return HT_ERR_ARG;
+	const two_hands_args a = { range_lo, range_hi, max_step, far, min_pixels, flags };
+	{ const int r = two_hands_check(ctx, side, w, h, a, B); if (r) return r; }
+	{ const int r = two_hands_reserve(ctx, w, h); if (r) return r; }
+	return update_dev_end(ctx, two_hands_enqueue(ctx, side, d_depth, d_cams, w, h, segment_scale, a, d_start_poses, B, d_poses_out, d_info ? d_info : ctx->d_two_info, ht_user_stream(ctx, stream)));
+}
+extern "C" int ht_update_two_hands_sync(ht_ctx *ctx, int side, const uint16_t *depth, const float *cams, int w, int h, float segment_scale, uint16_t range_lo, uint16_t range_hi, uint16_t max_step,
+                                        int min_pixels, uint16_t far, int flags, int B, float *poses_out, int32_t *info, float *cnn_out)
+{
+	CHECK_READY(ctx); CHECK_MODEL(ctx);
+	if (!depth || !cams || !poses_out) return HT_ERR_ARG;
+	const two_hands_args a = { range_lo, range_hi, max_step, far, min_pixels, flags };
+	{ const int r = two_hands_check(ctx, side, w, h, a, B); if (r) return r; }
+	hipStream_t s = ctx->stream;
+	const uint16_t *d_in; const float *d_cin;
+	int r = two_hands_reserve(ctx, w, h);      // (first: it may wait for the stream, and the uploads below are already on it)
+	if (!r) r = stage_frames(ctx, depth, cams, w, h, B, s, &d_in, &d_cin);
+	if (r) return r;
+	if ((r = two_hands_enqueue(ctx, side, d_in, d_cin, w, h, segment_scale, a, nullptr, B, ctx->d_poses_out, ctx->d_two_info, s))) return r;
+	if (info) HIPCHK(ctx, hipMemcpyAsync(info, ctx->d_two_info, (size_t)B * 16 * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+	return finish_sync(ctx, 2 * B, s, poses_out, cnn_out, nullptr, (w == side && h == side) ? nullptr : "ht_update_two_hands");
+}
+
 // HandTracker::update_cnn_model (handtrack.h:734-741) and kickstart (:743-746) for B trackers, frames of any supported size
 extern "C" int ht_update_cnn_model_sync(ht_ctx *ctx, const uint16_t *depth, const float *cams, int w, int h, float segment_scale, int B, int apply_to_handmodel,
                                         float *poses_out, int *accepted_out, float *cnn_out)

@@ -19,6 +19,7 @@ LABELS_SIDE128 = 2            # HT_LABELS_SIDE128
 SENSOR_IVY, SENSOR_DS4 = 0, 1 # HT_SENSOR_IVY, HT_SENSOR_DS4
 JOINTS_COM_POSES = 1          # HT_JOINTS_COM_POSES
 SAMPLE_ENHANCED = 2           # HT_SAMPLE_ENHANCED
+SPLIT_RIGHT_IS_LOW_X, SPLIT_MIRROR_LEFT = 1, 2      # HT_SPLIT_RIGHT_IS_LOW_X, HT_SPLIT_MIRROR_LEFT
 CNN128_IN, CNNB128_COUNT = 16384, 30429920
 # ht_debug_train_buffers: (name, floats, shape) of the segments of act and err, in order (None: padding)
 TRAIN_ACT = (("a1", 57600, (16, 60, 60)), ("a3", 3600, (16, 15, 15)), ("a5", 9216, (64, 12, 12)), ("a6", 2304, (2304,)), ("a8", 2048, (2048,)))
@@ -38,6 +39,7 @@ SYMBOLS = (
     "ht_model_joint_limits", "ht_joint_coords", "ht_joint_coords_dev", "ht_joint_pose", "ht_joint_pose_dev", "ht_sample_poses", "ht_sample_poses_dev",
     "ht_mirror_frames", "ht_mirror_frames_dev", "ht_mirror_cams", "ht_mirror_cams_dev", "ht_mirror_poses", "ht_mirror_poses_dev", "ht_update_hands_sync", "ht_update_hands_dev", "ht_reserve_hands", "ht_hands_capacity",
     "ht_model_mirror", "ht_model_body_planes",
+    "ht_split_hands", "ht_split_hands_dev", "ht_update_two_hands_sync", "ht_update_two_hands_dev",
     "ht_comm_available", "ht_comm_unique_id", "ht_comm_init", "ht_comm_info", "ht_gather_poses_dev", "ht_gather_wait", "ht_gather_wait_host", "ht_comm_destroy",
 )
 
@@ -199,6 +201,11 @@ def load(build_if_missing=True):
     L.ht_reserve_hands.argtypes = [vp, C.c_int, C.c_int]
     L.ht_hands_capacity.argtypes = [vp, C.POINTER(C.c_size_t)]
     L.ht_model_mirror.argtypes = [vp]
+    u16, i32p = C.c_uint16, C.POINTER(C.c_int32)
+    L.ht_split_hands.argtypes = [vp, u16p, fp, C.c_int, C.c_int, C.c_int, u16, u16, u16, C.c_int, u16, C.c_int, u16p, fp, i32p, i32p, u16p]
+    L.ht_split_hands_dev.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, u16, u16, u16, C.c_int, u16, C.c_int, vp, vp, vp, vp, vp, vp]
+    L.ht_update_two_hands_sync.argtypes = [vp, C.c_int, u16p, fp, C.c_int, C.c_int, C.c_float, u16, u16, u16, C.c_int, u16, C.c_int, C.c_int, fp, i32p, fp]
+    L.ht_update_two_hands_dev.argtypes = [vp, C.c_int, vp, vp, C.c_int, C.c_int, C.c_float, u16, u16, u16, C.c_int, u16, C.c_int, vp, C.c_int, vp, vp, vp]
     L.ht_model_body_planes.argtypes = [vp, C.c_int, fp, fp]
     for name in SYMBOLS:
         if name not in ("ht_last_error", "ht_model_error"):
@@ -425,6 +432,42 @@ class Context:
         n = C.c_size_t()
         self._chk(self.L.ht_hands_capacity(self.h, C.byref(n)))
         return n.value
+
+    # ---- two hands in one frame (include/ht_mi355x.h "two hands in one frame")
+    def split_hands(self, depth, range_lo, range_hi, far, cams=None, max_step=65535, min_pixels=1, flags=0, want_labels=False, want_n=True):
+        """depth u16[B,h,w] -> dict(frames u16[B,2,h,w] (0 right, 1 left), info i32[B,2,8], and on request cams [B,2,12], n_components [B], labels u16[B,h/4,w/4]) (ht_split_hands)"""
+        depth = _c(depth, np.uint16)
+        B, h, w = depth.shape
+        u16 = C.POINTER(C.c_uint16); i32 = C.POINTER(C.c_int32)
+        out = dict(frames=np.empty((B, 2, h, w), np.uint16), info=np.empty((B, 2, 8), np.int32))
+        if cams is not None:
+            cams = _c(cams, np.float32); out["cams"] = np.empty((B, 2, CAM), np.float32)
+        if want_n:
+            out["n_components"] = np.empty(B, np.int32)
+        if want_labels:
+            out["labels"] = np.empty((B, h // 4, w // 4), np.uint16)
+        self._chk(self.L.ht_split_hands(self.h, depth.ctypes.data_as(u16), None if cams is None else _f(cams), w, h, B, int(range_lo), int(range_hi), int(max_step), int(min_pixels), int(far), int(flags),
+                                        out["frames"].ctypes.data_as(u16), None if cams is None else _f(out["cams"]), out["info"].ctypes.data_as(i32),
+                                        out["n_components"].ctypes.data_as(i32) if want_n else None, out["labels"].ctypes.data_as(u16) if want_labels else None))
+        return out
+
+    def split_hands_dev(self, d_depth, d_cams, w, h, B, range_lo, range_hi, max_step, min_pixels, far, flags, d_depth_out, d_cams_out, d_info, d_n_components=None, d_labels=None, stream=None):
+        self._chk(self.L.ht_split_hands_dev(self.h, d_depth, d_cams, int(w), int(h), int(B), int(range_lo), int(range_hi), int(max_step), int(min_pixels), int(far), int(flags), d_depth_out, d_cams_out,
+                                            d_info, d_n_components, d_labels, stream))
+
+    def update_two_hands_sync(self, depth, cams, range_lo, range_hi, far, side=64, segment_scale=0.17, max_step=65535, min_pixels=1, flags=0, want_cnn=False):
+        """B frames of two hands each in slots 2i (right) and 2i+1 (left): poses [B,2,nb,7] in the camera's space, info i32[B,2,8], and cnn_out [2B,2304] (canonical) on request"""
+        depth = _c(depth, np.uint16); cams = _c(cams, np.float32)
+        B, h, w = depth.shape
+        poses = np.empty((B, 2, self.nb, POSE), np.float32); info = np.empty((B, 2, 8), np.int32)
+        cnn = np.empty((2 * B, CNN_OUT), np.float32) if want_cnn else None
+        self._chk(self.L.ht_update_two_hands_sync(self.h, int(side), depth.ctypes.data_as(C.POINTER(C.c_uint16)), _f(cams), w, h, float(segment_scale), int(range_lo), int(range_hi), int(max_step),
+                                                  int(min_pixels), int(far), int(flags), B, _f(poses), info.ctypes.data_as(C.POINTER(C.c_int32)), _f(cnn) if want_cnn else None))
+        return (poses, info, cnn) if want_cnn else (poses, info)
+
+    def update_two_hands_dev(self, side, d_depth, d_cams, w, h, segment_scale, range_lo, range_hi, max_step, min_pixels, far, flags, d_start, B, d_poses_out, d_info=None, stream=None):
+        self._chk(self.L.ht_update_two_hands_dev(self.h, int(side), d_depth, d_cams, int(w), int(h), float(segment_scale), int(range_lo), int(range_hi), int(max_step), int(min_pixels), int(far), int(flags),
+                                                 d_start, int(B), d_poses_out, d_info, stream))
 
     def update_direct_sync(self, depth, cams, side=128, want_cnn=False):
         """BASELINE configs[4] end to end: depth u16[B,side,side] frames that are their own segment, the net of that input size (ht_update_direct_sync)."""

@@ -271,6 +271,7 @@ class CNN                                                                       
 	ht_ctx *ctx_ = nullptr;
 	std::shared_ptr<ht_ctx> own_;      // set when the object owns its (CNN-only) context: PoseInitializerCNN
 	friend struct HandTracker;
+	friend struct TwoHandTracker;
 	friend CNN PoseInitializerCNN(std::string, int);
 public:
 	std::vector<float> Eval(const std::vector<float> &x)                                     // cnn.h:550
@@ -687,6 +688,95 @@ inline Image<unsigned short> HandSegmentVR(const Image<unsigned short> &depth, i
 	if (!detail::live_ctx()) throw std::runtime_error("HandSegmentVR: construct a HandTracker first (the segmentation runs on its device)");
 	return HandTracker::segment_on(detail::live_ctx(), depth, entry_options, wrange, diam);
 }
+
+// Additions (two hands in one frame, include/ht_mi355x.h "two hands in one frame"; the reference segments one hand per frame).
+// SplitHands cuts a frame into one masked frame per hand on the device of the first live HandTracker or TwoHandTracker: the blobs of the quarter-size image in
+// [range_lo, range_hi) raw depth units, the two largest, the right hand the one at higher x (lower x with HT_SPLIT_RIGHT_IS_LOW_X).  With HT_SPLIT_MIRROR_LEFT the left
+// frame and its camera come mirrored, ready for a right-hand tracker.  present[k] says whether hand k (0 right, 1 left) was found; info is ht_split_hands' record.
+struct SplitResult { Image<unsigned short> right, left; bool present[2]; int info[2][8]; int n_components; };
+inline SplitResult SplitHandsOn(ht_ctx *ctx, const Image<unsigned short> &depth, unsigned short range_lo, unsigned short range_hi, unsigned short far, unsigned short max_step = 65535, int min_pixels = 1, int flags = 0)
+{
+	const int w = depth.dim().x, h = depth.dim().y;
+	if (depth.raster.size() != (size_t)w * h) throw std::runtime_error("SplitHands: the raster does not match the camera's dimensions");
+	const DCamera &c = depth.cam;
+	const float cam[HT_CAM] = { c.focal().x, c.focal().y, c.principal().x, c.principal().y, c.depth_scale, c.pose.position.x, c.pose.position.y, c.pose.position.z,
+	                            c.pose.orientation.x, c.pose.orientation.y, c.pose.orientation.z, c.pose.orientation.w };
+	std::vector<unsigned short> out((size_t)2 * w * h); float co[2][HT_CAM];
+	SplitResult r;
+	check(ctx, ht_split_hands(ctx, depth.raster.data(), cam, w, h, 1, range_lo, range_hi, max_step, min_pixels, far, flags, out.data(), &co[0][0], &r.info[0][0], &r.n_components, nullptr));
+	Image<unsigned short> *im[2] = { &r.right, &r.left };
+	for (int k = 0; k < 2; k++)
+	{
+		Pose pose; pose.position = { co[k][5], co[k][6], co[k][7] }; pose.orientation = { co[k][8], co[k][9], co[k][10], co[k][11] };
+		*im[k] = Image<unsigned short>(DCamera({ w, h }, { co[k][0], co[k][1] }, { co[k][2], co[k][3] }, co[k][4], pose), std::vector<unsigned short>(out.begin() + (size_t)k * w * h, out.begin() + (size_t)(k + 1) * w * h));
+		r.present[k] = r.info[k][0] > 0;
+	}
+	return r;
+}
+inline SplitResult SplitHands(const Image<unsigned short> &depth, unsigned short range_lo, unsigned short range_hi, unsigned short far, unsigned short max_step = 65535, int min_pixels = 1, int flags = 0)
+{
+	if (!detail::live_ctx()) throw std::runtime_error("SplitHands: construct a HandTracker or a TwoHandTracker first (the split runs on its device)");
+	return SplitHandsOn(detail::live_ctx(), depth, range_lo, range_hi, far, max_step, min_pixels, flags);
+}
+// Both hands of one camera: one context of two tracker slots, slot 0 the right hand, slot 1 the left hand in canonical (mirrored) space.  update() splits the frame on the
+// device, tracks both slots with ht_update_two_hands_sync and returns both hands' rig-space poses (what handmodel.GetPoseUser() is for a HandTracker) in the camera's own
+// space, with the presence flags: the poses of an absent hand mean nothing.  Synchronous only (no overlapped arrangement).  The range is in metres like HandSegmentVR's
+// wrange; everything nearer than wrange.y and not nearer than wrange.x is foreground, and `far` metres is written where a hand's frame is masked.
+struct TwoHandTracker
+{
+	struct Hands { std::vector<Pose> right, left; bool present[2]; int info[2][8]; };
+	float segment_scale = 0.17f; float2 wrange{ 0.1f, 0.65f }; float far = 4.0f; float max_step = 0.0f;      // max_step in metres between neighbouring quarter-size pixels of one blob; 0: no depth test
+	int min_pixels = 16; bool right_is_low_x = false;      // right_is_low_x: a camera facing the user
+	int side = 64; CNN cnn;
+	explicit TwoHandTracker(const std::string &model_path = "../assets/model_hand.json", const std::string &cnnb_path = "../assets/handposedd.cnnb", int device = 0)
+	{
+		const int rc = ht_create(model_path.c_str(), 2, device, &ctx_);
+		if (rc != HT_OK) { std::string msg = ctx_ ? ht_last_error(ctx_) : "ht_create failed"; if (ctx_) ht_destroy(ctx_); ctx_ = nullptr; throw std::runtime_error("TwoHandTracker: " + msg); }
+		cnn.ctx_ = ctx_;
+		if (!detail::live_ctx()) detail::live_ctx() = ctx_;
+		ht_model_info(ctx_, &nb_, nullptr, nullptr);
+		if (!cnnb_path.empty()) { std::ifstream is(cnnb_path, std::ios_base::in | std::ios_base::binary); if (is.is_open()) cnn.loadb(is); }
+	}
+	~TwoHandTracker() { if (detail::live_ctx() == ctx_) detail::live_ctx() = nullptr; if (ctx_) ht_destroy(ctx_); }
+	TwoHandTracker(const TwoHandTracker &) = delete; TwoHandTracker &operator=(const TwoHandTracker &) = delete;
+	ht_ctx *context() const { return ctx_; }
+	// both hands' starting poses in the camera's space (centre-of-mass poses, as HandTracker::SetPose takes them): the left hand's are mirrored into its slot
+	void SetPose(const std::vector<Pose> &right, const std::vector<Pose> &left)
+	{
+		std::vector<float> f = flat(right); const std::vector<float> l = flat(mirrored(left));
+		f.insert(f.end(), l.begin(), l.end());
+		check(ctx_, ht_tracker_reset(ctx_, 0, 2, f.data()));
+	}
+	Hands update(const Image<unsigned short> &dimage)
+	{
+		const DCamera &c = dimage.cam;
+		const int w = dimage.dim().x, h = dimage.dim().y;
+		if (dimage.raster.size() != (size_t)w * h) throw std::runtime_error("TwoHandTracker: the raster does not match the camera's dimensions");
+		const float cam[HT_CAM] = { c.focal().x, c.focal().y, c.principal().x, c.principal().y, c.depth_scale, c.pose.position.x, c.pose.position.y, c.pose.position.z,
+		                            c.pose.orientation.x, c.pose.orientation.y, c.pose.orientation.z, c.pose.orientation.w };
+		const auto units = [&](float metres) { const float u = metres / c.depth_scale; return (unsigned short)(u < 0.0f ? 0.0f : (u > 65535.0f ? 65535.0f : u)); };
+		std::vector<float> out((size_t)2 * nb_ * HT_POSE);
+		Hands r;
+		check(ctx_, ht_update_two_hands_sync(ctx_, side, dimage.raster.data(), cam, w, h, segment_scale, units(wrange.x), units(wrange.y), max_step > 0.0f ? units(max_step) : (unsigned short)65535, min_pixels,
+		                                     units(far), right_is_low_x ? HT_SPLIT_RIGHT_IS_LOW_X : 0, 1, out.data(), &r.info[0][0], nullptr));
+		std::vector<Pose> *hand[2] = { &r.right, &r.left };
+		for (int k = 0; k < 2; k++)
+		{
+			hand[k]->resize(nb_);
+			for (int b = 0; b < nb_; b++) { const float *p = &out[((size_t)k * nb_ + b) * HT_POSE]; (*hand[k])[b].position = { p[0], p[1], p[2] }; (*hand[k])[b].orientation = { p[3], p[4], p[5], p[6] }; }
+			r.present[k] = r.info[k][0] > 0;
+		}
+		return r;
+	}
+private:
+	std::vector<float> flat(const std::vector<Pose> &pose) const
+	{
+		std::vector<float> f((size_t)nb_ * HT_POSE, 0.f);
+		for (int b = 0; b < nb_ && b < (int)pose.size(); b++) { float *p = &f[(size_t)b * HT_POSE]; p[0] = pose[b].position.x; p[1] = pose[b].position.y; p[2] = pose[b].position.z; p[3] = pose[b].orientation.x; p[4] = pose[b].orientation.y; p[5] = pose[b].orientation.z; p[6] = pose[b].orientation.w; }
+		return f;
+	}
+	ht_ctx *ctx_ = nullptr; int nb_ = 0;
+};
 
 // RSCam's depth filters (include/dcam.h:144-244): what dcam.GetDepth() does to the sensor's frame before htk.update() sees it, on the device of the first live
 // HandTracker.  No librealsense and no device handle: the caller hands over the raw frame (and, for an R200, the IR image of the same size) it got from its camera.

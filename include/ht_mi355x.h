@@ -513,6 +513,41 @@ int ht_hands_capacity(ht_ctx *ctx, size_t *frame_pixels);
 int ht_model_mirror(ht_model *m);
 int ht_model_body_planes(const ht_model *m, int body, float *hull_planes, float *mesh_planes);      /* the stored planes ht_model_mirror flips: the hull's [nplanes][4] (ht_model_body), the PolyPlane [t][4] of every sdmesh triangle; either may be NULL */
 
+/* ---- two hands in one frame (an addition: HandSegmentVR, handtrack.h:280-344, treats everything nearer than wrange.y as ONE hand and arm) ----------------------
+ * One front-end step on the device finds the blobs of a frame, takes the two largest, decides from their position which is the right hand and which the left, and
+ * writes one masked frame per hand.  All integers on u16 pixels; W4 = w / 4, H4 = h / 4; sizes as ht_segment_vr_supported: w, h >= 8, multiples of 4, W4 * H4 <= 19200.
+ *   quarter image  Q[Y][X] = the minimum of the 4x4 block of input pixels [4Y..4Y+3][4X..4X+3] (DownSampleMin(DownSampleMin(depth)), handtrack.h:285)
+ *   foreground     range_lo <= Q < range_hi, raw depth units (range_lo = 0: the reference's one-sided threshold, :287)
+ *   connectivity   two 4-neighbours are connected iff both are foreground and |Qa - Qb| <= max_step (65535 switches the depth test off)
+ *   label          of a cell: the smallest raster index Y * W4 + X in its connected component; background cells carry 0xFFFF
+ *   selection      components of count >= min_pixels cells are eligible and n_components counts them; the two with the largest count are taken, ties to the smaller label
+ *   left / right   a is LOWER than b iff sum_x_a * count_b < sum_x_b * count_a (64-bit), a tie to the smaller label.  HT_SPLIT_RIGHT_IS_LOW_X clear (an egocentric
+ *                  camera, HandSegmentVR's): the higher component is the right hand, the lower the left; set (a camera facing the user): the other way round.  A single
+ *                  eligible component is low iff 2 * sum_x < count * (W4 - 1); it becomes the hand the flag puts on that side and the other hand is absent
+ *   frames         depth_out[b][k][y][x] = depth[b][y][x] if label[y/4][x/4] is hand k's, else `far` (e.g. 4 / depth_scale, SampleD's background :343); k = 0 the right
+ *                  hand, k = 1 the left; an absent hand's frame is all far.  With HT_SPLIT_MIRROR_LEFT frame k = 1 is written mirrored, out[1][y][x] = masked[y][w-1-x],
+ *                  and cams_out[b][1] is the mirrored camera ("left hands" above); cams_out[b][0], and [b][1] without the flag, are the frame's camera
+ *   info [B][2][8] int32 per hand: count (0 = absent), label, sum_x, sum_y, min_x, min_y, max_x, max_y in quarter-image cells; an absent hand reads 0, 0xFFFF, 0 ...
+ * ht_split_hands      depth [B][h][w] -> depth_out [B][2][h][w], cams_out [B][2][12], info, n_components [B], labels [B][H4][W4] (uint16).  cams with cams_out (both or
+ *                     neither), n_components and labels are optional (NULL).  B is not bounded by max_batch and the call needs no tracker slot, model or weights; the
+ *                     host form stages through a buffer that follows the largest call; B = 0 does nothing; depth and depth_out must not overlap.  HT_ERR_ARG for a size
+ *                     the rule refuses, range_lo >= range_hi, far < range_hi, min_pixels < 1 and unknown flag bits.  The device form takes device buffers, is
+ *                     asynchronous on `stream`, and moves 16, 8 or 4 bytes per thread as the width and both frame pointers allow, else single pixels; without
+ *                     d_labels it cuts along a label image the context keeps (grown with one synchronising re-allocation to the largest call).
+ * ht_update_two_hands_*  B frames of two hands each, tracked in 2B slots (2 * B <= max_batch): slot 2i frame i's right hand, slot 2i + 1 its left hand in canonical
+ *                     (mirrored) space.  The split writes straight into the left-hands staging (ht_reserve_hands sizes it; a call that finds it too small grows it the
+ *                     same way), right hands unmirrored, left hands mirrored whether or not HT_SPLIT_MIRROR_LEFT is given; ht_update_frames_sized_* runs on those 2B
+ *                     frames with that call's shapes, sides, errors and point-capacity rules; the odd slots' poses are mirrored back.  poses_out [B][2][nb][7] and
+ *                     d_start_poses [B][2][nb][7] are in the camera's own space; cnn_out [2B][HT_CNN_OUT] and the slots' state stay canonical.  An absent hand's slot
+ *                     sees an all-far frame and takes the update's too-few-points path: info [B][2][8] (optional) tells the caller that its pose means nothing.  The
+ *                     device form only enqueues once its staging exists. */
+#define HT_SPLIT_RIGHT_IS_LOW_X 1
+#define HT_SPLIT_MIRROR_LEFT 2
+int ht_split_hands(ht_ctx *ctx, const uint16_t *depth, const float *cams, int w, int h, int B, uint16_t range_lo, uint16_t range_hi, uint16_t max_step, int min_pixels, uint16_t far, int flags, uint16_t *depth_out, float *cams_out, int32_t *info, int32_t *n_components, uint16_t *labels);
+int ht_split_hands_dev(ht_ctx *ctx, const uint16_t *d_depth, const float *d_cams, int w, int h, int B, uint16_t range_lo, uint16_t range_hi, uint16_t max_step, int min_pixels, uint16_t far, int flags, uint16_t *d_depth_out, float *d_cams_out, int32_t *d_info, int32_t *d_n_components, uint16_t *d_labels, void *stream);
+int ht_update_two_hands_sync(ht_ctx *ctx, int side, const uint16_t *depth, const float *cams, int w, int h, float segment_scale, uint16_t range_lo, uint16_t range_hi, uint16_t max_step, int min_pixels, uint16_t far, int flags, int B, float *poses_out, int32_t *info, float *cnn_out);
+int ht_update_two_hands_dev(ht_ctx *ctx, int side, const uint16_t *d_depth, const float *d_cams, int w, int h, float segment_scale, uint16_t range_lo, uint16_t range_hi, uint16_t max_step, int min_pixels, uint16_t far, int flags, const float *d_start_poses, int B, float *d_poses_out, int32_t *d_info, void *stream);
+
 /* ---- annotation fit loop ---------------------------------------------------------------------------------------------
  * ht_slowfit          replaces  void HandTracker::slowfit(const std::vector<float3> &points, int hold, const std::vector<Pose> &refpose,
  *                     int steps_ = 6, RigidBody *selectrb = NULL, const float3 &spoint, const float3 &rbpoint, const std::vector<float4> &crays)
