@@ -248,6 +248,7 @@ extern "C" int ht_scale(ht_ctx *ctx, float s)
 		c[HT_BC_DIAM] = sqrtf(diam2);
 	}
 	for (int j = 0; j < nj; j++) { float *c = &ctx->h_jointc[(size_t)j * HT_JC]; for (int i = 0; i < 3; i++) { c[HT_JC_P0 + i] *= s; c[HT_JC_P1 + i] *= s; } }
+	for (float &o : ctx->kp_feature8) o *= s;      // the built-in keypoint tables follow the model (HT_KP_SKELETON is read off the anchors and centres of mass above)
 	hipStream_t st = ctx->stream;
 	HIPCHK(ctx, hipStreamSynchronize(st));
 	HIPCHK(ctx, hipMemcpy(ctx->d_verts_rw, ctx->h_verts.data(), ctx->h_verts.size() * sizeof(float4), hipMemcpyHostToDevice));

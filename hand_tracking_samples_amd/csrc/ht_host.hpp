@@ -123,6 +123,12 @@ struct ht_ctx
 	// call (dev_grow).  ht_update_two_hands_*: its info [B/2][2][8] when the caller wants none, and the flags 0, 1, 0, 1, ... [B] its pose mirrors take (made once)
 	char *d_split = nullptr; size_t split_cap = 0; uint16_t *d_split_labels = nullptr; size_t split_labels_cap = 0;
 	int32_t *d_two_info = nullptr; unsigned char *d_two_flags = nullptr;
+	// tracking accuracy (ht_quality.hip): the offsets of HT_KP_FEATURE8 [8][3] (handmodelfeaturepoints, handtrack.h:77-81; ht_scale multiplies them as it does the
+	// centres of mass -- HT_KP_SKELETON is read off h_jointc / h_bodyc when asked for); the host forms' staging (dev_grow); ht_pose_depth_residual's render poses
+	// [B][nb][7] and rendered frames [B][h][w], grown to the largest call with one synchronising re-allocation before anything is enqueued (quality_reserve)
+	float kp_feature8[24] = { 0, 0, 0, -0.03f, 0, -0.03f, 0.03f, 0, -0.03f, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0 };
+	char *d_quality = nullptr; size_t quality_cap = 0;
+	float *d_quality_poses = nullptr; size_t quality_poses_cap = 0; uint16_t *d_quality_frames = nullptr; size_t quality_frames_cap = 0;
 };
 
 // The net of a side x side input; any other side is refused here, and only here

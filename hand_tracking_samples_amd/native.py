@@ -20,6 +20,8 @@ SENSOR_IVY, SENSOR_DS4 = 0, 1 # HT_SENSOR_IVY, HT_SENSOR_DS4
 JOINTS_COM_POSES = 1          # HT_JOINTS_COM_POSES
 SAMPLE_ENHANCED = 2           # HT_SAMPLE_ENHANCED
 SPLIT_RIGHT_IS_LOW_X, SPLIT_MIRROR_LEFT = 1, 2      # HT_SPLIT_RIGHT_IS_LOW_X, HT_SPLIT_MIRROR_LEFT
+KP_COM_POSES = 1              # HT_KP_COM_POSES
+KP_FEATURE8, KP_SKELETON, KP_CALLER, KP_MAX, KP_MAX_THR = 0, 1, 2, 64, 32      # HT_KP_FEATURE8, HT_KP_SKELETON, HT_KP_CALLER, HT_KP_MAX, HT_KP_MAX_THR
 CNN128_IN, CNNB128_COUNT = 16384, 30429920
 # ht_debug_train_buffers: (name, floats, shape) of the segments of act and err, in order (None: padding)
 TRAIN_ACT = (("a1", 57600, (16, 60, 60)), ("a3", 3600, (16, 15, 15)), ("a5", 9216, (64, 12, 12)), ("a6", 2304, (2304,)), ("a8", 2048, (2048,)))
@@ -40,6 +42,8 @@ SYMBOLS = (
     "ht_mirror_frames", "ht_mirror_frames_dev", "ht_mirror_cams", "ht_mirror_cams_dev", "ht_mirror_poses", "ht_mirror_poses_dev", "ht_update_hands_sync", "ht_update_hands_dev", "ht_reserve_hands", "ht_hands_capacity",
     "ht_model_mirror", "ht_model_body_planes",
     "ht_split_hands", "ht_split_hands_dev", "ht_update_two_hands_sync", "ht_update_two_hands_dev",
+    "ht_keypoint_table", "ht_keypoints", "ht_keypoints_dev", "ht_keypoint_errors", "ht_keypoint_errors_dev", "ht_depth_compare", "ht_depth_compare_dev",
+    "ht_pose_depth_residual", "ht_pose_depth_residual_dev",
     "ht_comm_available", "ht_comm_unique_id", "ht_comm_init", "ht_comm_info", "ht_gather_poses_dev", "ht_gather_wait", "ht_gather_wait_host", "ht_comm_destroy",
 )
 
@@ -207,6 +211,16 @@ def load(build_if_missing=True):
     L.ht_update_two_hands_sync.argtypes = [vp, C.c_int, u16p, fp, C.c_int, C.c_int, C.c_float, u16, u16, u16, C.c_int, u16, C.c_int, C.c_int, fp, i32p, fp]
     L.ht_update_two_hands_dev.argtypes = [vp, C.c_int, vp, vp, C.c_int, C.c_int, C.c_float, u16, u16, u16, C.c_int, u16, C.c_int, vp, C.c_int, vp, vp, vp]
     L.ht_model_body_planes.argtypes = [vp, C.c_int, fp, fp]
+    dp, i64p, ci, cf = C.POINTER(C.c_double), C.POINTER(C.c_int64), C.c_int, C.c_float
+    L.ht_keypoint_table.argtypes = [vp, ci, ip, ip, fp, ip]
+    L.ht_keypoints.argtypes = [vp, fp, ci, ci, ci, ci, ip, fp, ip, u8p, fp, u16p, ci, ci, cf, cf, fp, fp, fp, u8p]
+    L.ht_keypoints_dev.argtypes = [vp, vp, ci, ci, ci, ci, ip, fp, ip, vp, vp, vp, ci, ci, cf, cf, vp, vp, vp, vp, vp]
+    L.ht_keypoint_errors.argtypes = [vp, fp, fp, ci, ci, fp, ci, fp, fp, dp, i64p, i64p]
+    L.ht_keypoint_errors_dev.argtypes = [vp, vp, vp, ci, ci, fp, ci, vp, vp, vp, vp, vp, vp]
+    L.ht_depth_compare.argtypes = [vp, u16p, u16p, ci, ci, ci, ci, ci, ci, i64p]
+    L.ht_depth_compare_dev.argtypes = [vp, vp, vp, ci, ci, ci, ci, ci, ci, vp, vp]
+    L.ht_pose_depth_residual.argtypes = [vp, fp, fp, u16p, ci, ci, ci, ci, cf, ci, ci, ci, i64p, u16p]
+    L.ht_pose_depth_residual_dev.argtypes = [vp, vp, vp, vp, ci, ci, ci, ci, cf, ci, ci, ci, vp, vp, vp]
     for name in SYMBOLS:
         if name not in ("ht_last_error", "ht_model_error"):
             getattr(L, name).restype = C.c_int
@@ -796,6 +810,113 @@ class Context:
 
     def sample_poses_dev(self, d_roots, B, seed, first_index, spread, d_poses, d_coords=None, com_poses=False, enhanced=False, stream=None):
         self._chk(self.L.ht_sample_poses_dev(self.h, d_roots, int(B), int(seed), int(first_index), float(spread), (JOINTS_COM_POSES if com_poses else 0) | (SAMPLE_ENHANCED if enhanced else 0), d_poses, d_coords, stream))
+
+    # -- tracking accuracy (ht_mi355x.h "tracking accuracy"): keypoints, keypoint errors, depth residuals
+    def keypoint_table(self, which):
+        """A built-in keypoint table (KP_FEATURE8, KP_SKELETON) of the model as ht_scale left it -> (bones i32[K], offsets f32[K,3], rel i32[K])."""
+        K = C.c_int()
+        self._chk(self.L.ht_keypoint_table(self.h, int(which), C.byref(K), None, None, None))
+        bones, off, rel = np.empty(K.value, np.int32), np.empty((K.value, 3), np.float32), np.empty(K.value, np.int32)
+        self._chk(self.L.ht_keypoint_table(self.h, int(which), None, _i(bones), _f(off), _i(rel)))
+        return bones, off, rel
+
+    @staticmethod
+    def _kp_table(table):
+        """table: KP_FEATURE8 / KP_SKELETON, or a caller table (bones [K], offsets [K,3], rel [K]) -> (which, K, keep-alive arrays, the three pointers)"""
+        if isinstance(table, (int, np.integer)):
+            return int(table), 0, (), (None, None, None)
+        bones, off, rel = _c(table[0], np.int32).reshape(-1), _c(table[1], np.float32).reshape(-1, 3), _c(table[2], np.int32).reshape(-1)
+        if not (len(off) == len(bones) == len(rel)):
+            raise ValueError("a keypoint table is (bones [K], offsets [K,3], rel [K])")
+        return KP_CALLER, len(bones), (bones, off, rel), (_i(bones), _f(off), _i(rel))
+
+    def keypoints(self, poses, table=KP_FEATURE8, com_poses=False, hands=None, cams=None, depth=None, near_tol=0.03, far_tol=0.02, want_xyz=True, want_zc=True):
+        """poses [B,nb,7] (user poses; com_poses: centre-of-mass poses) -> dict(xyz f32[B,K,3]; with cams [B,12]: pix f32[B,K,2], zc f32[B,K]; with depth
+        u16[B,h,w] as well: vis u8[B,K], 0 visible, 1 occluded, 2 nothing there, 3 outside the image, 4 behind the camera).  hands u8[B]: left hands."""
+        poses = _c(poses, np.float32).reshape(-1, self.nb, POSE); B = poses.shape[0]
+        which, K, keep, tp = self._kp_table(table)
+        if which != KP_CALLER:
+            Kc = C.c_int(); self._chk(self.L.ht_keypoint_table(self.h, which, C.byref(Kc), None, None, None)); K = Kc.value
+        u8p, u16p = C.POINTER(C.c_uint8), C.POINTER(C.c_uint16)
+        hands = None if hands is None else _c(hands, np.uint8).reshape(B)
+        cams = None if cams is None else _c(cams, np.float32).reshape(B, CAM)
+        h = w = 0
+        if depth is not None:
+            depth = _c(depth, np.uint16); h, w = depth.shape[-2:]; depth = depth.reshape(B, h, w)
+        out = {}
+        if want_xyz:
+            out["xyz"] = np.empty((B, K, 3), np.float32)
+        if cams is not None:
+            out["pix"] = np.empty((B, K, 2), np.float32)
+            if want_zc:
+                out["zc"] = np.empty((B, K), np.float32)
+            if depth is not None:
+                out["vis"] = np.empty((B, K), np.uint8)
+        g = lambda n: _f(out[n]) if n in out else None
+        self._chk(self.L.ht_keypoints(self.h, _f(poses), B, KP_COM_POSES if com_poses else 0, which, K, tp[0], tp[1], tp[2], None if hands is None else hands.ctypes.data_as(u8p),
+                                      None if cams is None else _f(cams), None if depth is None else depth.ctypes.data_as(u16p), int(w), int(h), float(near_tol), float(far_tol),
+                                      g("xyz"), g("pix"), g("zc"), out["vis"].ctypes.data_as(u8p) if "vis" in out else None))
+        return out
+
+    def keypoints_dev(self, d_poses, B, table, d_xyz, d_pix=None, d_zc=None, d_vis=None, com_poses=False, d_hands=None, d_cams=None, d_depth=None, w=0, h=0, near_tol=0.03, far_tol=0.02, stream=None):
+        """ht_keypoints_dev: device pointers (the table stays a host table), asynchronous on `stream`."""
+        which, K, keep, tp = self._kp_table(table)
+        self._chk(self.L.ht_keypoints_dev(self.h, d_poses, int(B), KP_COM_POSES if com_poses else 0, which, K, tp[0], tp[1], tp[2], d_hands, d_cams, d_depth, int(w), int(h), float(near_tol), float(far_tol),
+                                          d_xyz, d_pix, d_zc, d_vis, stream))
+
+    def keypoint_errors(self, a, b, thr=()):
+        """a, b f32[B,K,3] -> dict(dist f32[B,K], frame f32[B,2] (mean, max), sum_kp f64[K], hits_kp i64[T], hits_frame i64[T], and from them mean_kp f64[K],
+        mean f64, pck f64[T] = hits_kp / (B K), success f64[T] = hits_frame / B)."""
+        a = _c(a, np.float32); B, K = a.shape[0], a.shape[1]; a = a.reshape(B, K, 3); b = _c(b, np.float32).reshape(B, K, 3)
+        thr = _c(thr, np.float32).reshape(-1); T = len(thr)
+        dist, frame = np.empty((B, K), np.float32), np.empty((B, 2), np.float32)
+        sum_kp, hk, hf = np.zeros(K, np.float64), np.zeros(T, np.int64), np.zeros(T, np.int64)
+        dp, i64p = C.POINTER(C.c_double), C.POINTER(C.c_int64)
+        self._chk(self.L.ht_keypoint_errors(self.h, _f(a), _f(b), B, K, _f(thr) if T else None, T, _f(dist), _f(frame), sum_kp.ctypes.data_as(dp), hk.ctypes.data_as(i64p) if T else None,
+                                            hf.ctypes.data_as(i64p) if T else None))
+        n = max(B, 1)
+        return dict(dist=dist, frame=frame, sum_kp=sum_kp, hits_kp=hk, hits_frame=hf, mean_kp=sum_kp / n, mean=sum_kp.sum() / (n * K), pck=hk / float(n * K), success=hf / float(n))
+
+    def keypoint_errors_dev(self, d_a, d_b, B, K, thr, d_dist=None, d_frame=None, d_sum_kp=None, d_hits_kp=None, d_hits_frame=None, stream=None):
+        """ht_keypoint_errors_dev: device pointers (thr stays a host array), asynchronous on `stream`."""
+        thr = _c(thr, np.float32).reshape(-1)
+        self._chk(self.L.ht_keypoint_errors_dev(self.h, d_a, d_b, int(B), int(K), _f(thr) if len(thr) else None, len(thr), d_dist, d_frame, d_sum_kp, d_hits_kp, d_hits_frame, stream))
+
+    @staticmethod
+    def depth_figures(info, depth_scale=None):
+        """info i64[B,8] -> dict(info, iou f64[B] (NaN for two empty frames), close f64[B] = n_close / n_both, mean_abs, rms, max_abs in raw units, or in metres with
+        depth_scale (a scalar or [B])) -- host arithmetic on the exact integers."""
+        info = np.asarray(info, np.int64); f = info.astype(np.float64)
+        s = 1.0 if depth_scale is None else np.asarray(depth_scale, np.float64)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return dict(info=info, iou=f[:, 2] / (f[:, 0] + f[:, 1] - f[:, 2]), close=f[:, 3] / f[:, 2], mean_abs=f[:, 4] / f[:, 2] * s, rms=np.sqrt(f[:, 5] / f[:, 2]) * s, max_abs=f[:, 6] * s)
+
+    def depth_compare(self, a, b, lo, hi, tol=0, depth_scale=None):
+        """a, b u16[B,h,w] -> depth_figures of info i64[B,8]: n_a, n_b, n_both, n_close, sum |a-b|, sum (a-b)^2, max |a-b|, 0 over the pixels with lo <= p < hi."""
+        a = _c(a, np.uint16); B, h, w = a.shape; b = _c(b, np.uint16).reshape(B, h, w)
+        info = np.zeros((B, 8), np.int64); u16p = C.POINTER(C.c_uint16)
+        self._chk(self.L.ht_depth_compare(self.h, a.ctypes.data_as(u16p), b.ctypes.data_as(u16p), w, h, B, int(lo), int(hi), int(tol), info.ctypes.data_as(C.POINTER(C.c_int64))))
+        return self.depth_figures(info, depth_scale)
+
+    def depth_compare_dev(self, d_a, d_b, w, h, B, lo, hi, tol, d_info, stream=None):
+        self._chk(self.L.ht_depth_compare_dev(self.h, d_a, d_b, int(w), int(h), int(B), int(lo), int(hi), int(tol), d_info, stream))
+
+    def pose_depth_residual(self, poses, cams, depth, lo, hi, tol=0, far=4.0, com_poses=False, want_rendered=False):
+        """Poses against frames: poses [B,nb,7] rendered as ht_render_depth does in each frame's camera and compared with depth u16[B,h,w] (a = observed, b = rendered)
+        -> depth_figures in metres (and rendered u16[B,h,w] with want_rendered).  Choose hi <= far / depth_scale to keep the rendered background out."""
+        depth = _c(depth, np.uint16); B, h, w = depth.shape
+        poses = _c(poses, np.float32).reshape(B, self.nb, POSE); cams = _c(cams, np.float32).reshape(B, CAM)
+        info = np.zeros((B, 8), np.int64); rendered = np.empty((B, h, w), np.uint16) if want_rendered else None
+        u16p = C.POINTER(C.c_uint16)
+        self._chk(self.L.ht_pose_depth_residual(self.h, _f(poses), _f(cams), depth.ctypes.data_as(u16p), w, h, B, KP_COM_POSES if com_poses else 0, float(far), int(lo), int(hi), int(tol),
+                                                info.ctypes.data_as(C.POINTER(C.c_int64)), rendered.ctypes.data_as(u16p) if want_rendered else None))
+        out = self.depth_figures(info, cams[:, 4])
+        if want_rendered:
+            out["rendered"] = rendered
+        return out
+
+    def pose_depth_residual_dev(self, d_poses, d_cams, d_depth, w, h, B, lo, hi, tol, d_info, d_rendered=None, far=4.0, com_poses=False, stream=None):
+        self._chk(self.L.ht_pose_depth_residual_dev(self.h, d_poses, d_cams, d_depth, int(w), int(h), int(B), KP_COM_POSES if com_poses else 0, float(far), int(lo), int(hi), int(tol), d_info, d_rendered, stream))
 
     def sensor_filter(self, kind, depth, cams, ir=None, background=None, max_width=320):
         """RSCam::FilterIvy / FilterDS4 (dcam.h:174-226) for a batch of raw frames: depth u16[B,h,w], cams [B,12], ir u8[B,h,w] (DS4), background u16[B,h,w]

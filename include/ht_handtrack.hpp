@@ -264,6 +264,47 @@ inline float3 operator*(const Pose &p, const float3 &v) { const float3 r = qrot_
 namespace detail { inline ht_ctx *&live_ctx() { static ht_ctx *c = nullptr; return c; } }      // a context the free functions below can run on
 inline void check(ht_ctx *ctx, int rc) { if (rc != HT_OK) throw std::runtime_error(std::string("ht_mi355x: ") + (ctx ? ht_last_error(ctx) : "no context")); }
 
+// Model points in space and in the image (handtrack.h:76-96).  Additions to the reference's ModelFeaturePoint: `rel` says whose frame the offset is in (1, the default and
+// the reference's only case: the body's centre-of-mass frame, the frame of GetPose; 0: its rig frame, the frame of GetPoseUser), see ht_mi355x.h "tracking accuracy".
+// Skin and ImageFeaturePoints take one pose set as GetPose() returns it and run on the device of the first live HandTracker (ht_keypoints, the host form).
+struct ModelFeaturePoint { int bone; float3 offset; int rel = 1; ModelFeaturePoint(int b = 0, float3 o = { 0, 0, 0 }, int r = 1) : bone(b), offset(o), rel(r) {} };
+static const std::vector<ModelFeaturePoint> handmodelfeaturepoints =                             // handtrack.h:77-81
+{
+	{ 1, { 0, 0.0f, 0.0f } }, { 1, { -0.03f, 0, -0.03f } }, { 1, { 0.03f, 0, -0.03f } },
+	{ 4, { 0, 0, 0 } }, { 7, { 0, 0, 0 } }, { 10, { 0, 0, 0 } }, { 13, { 0, 0, 0 } }, { 16, { 0, 0, 0 } },
+};
+namespace detail
+{
+// ht_keypoints (host form) for one set of centre-of-mass poses and a caller table; cam / depth may be null
+inline void keypoints_on(ht_ctx *ctx, const std::vector<Pose> &pose, const std::vector<ModelFeaturePoint> &pts, bool left, const float *cam, const unsigned short *depth, int w, int h, float near_tol, float far_tol,
+                         std::vector<float3> *xyz, std::vector<float2> *pix, std::vector<unsigned char> *vis)
+{
+	if (!ctx) throw std::runtime_error("Skin / ImageFeaturePoints need a live HandTracker (they run on its device)");
+	const int K = (int)pts.size();
+	std::vector<float> p7; for (auto &q : pose) { const float r[7] = { q.position.x, q.position.y, q.position.z, q.orientation.x, q.orientation.y, q.orientation.z, q.orientation.w }; p7.insert(p7.end(), r, r + 7); }
+	int nb = 0; ht_model_info(ctx, &nb, nullptr, nullptr);
+	if ((int)pose.size() != nb) throw std::runtime_error("Skin: one pose per body of the model");
+	std::vector<int> bones(K), rel(K); std::vector<float> off((size_t)K * 3);
+	for (int k = 0; k < K; k++) { bones[k] = pts[k].bone; rel[k] = pts[k].rel; off[3 * k] = pts[k].offset.x; off[3 * k + 1] = pts[k].offset.y; off[3 * k + 2] = pts[k].offset.z; }
+	if (xyz) xyz->assign(K, float3{ 0, 0, 0 });
+	if (pix) pix->assign(K, float2{ 0, 0 });
+	if (vis) vis->assign(K, 0);
+	const unsigned char hand = left ? 1 : 0;
+	if (K) check(ctx, ht_keypoints(ctx, p7.data(), 1, HT_KP_COM_POSES, HT_KP_CALLER, K, bones.data(), off.data(), rel.data(), &hand, cam, depth, w, h, near_tol, far_tol,
+	                               xyz ? &(*xyz)[0].x : nullptr, pix ? &(*pix)[0].x : nullptr, nullptr, vis ? vis->data() : nullptr));
+}
+}
+inline std::vector<float3> Skin(const std::vector<Pose> &pose, const std::vector<ModelFeaturePoint> &pts)                                                     // handtrack.h:83-84
+{
+	std::vector<float3> x; detail::keypoints_on(detail::live_ctx(), pose, pts, false, nullptr, nullptr, 0, 0, 0.0f, 0.0f, &x, nullptr, nullptr); return x;
+}
+inline std::vector<float2> ImageFeaturePoints(const std::vector<Pose> &pose, const std::vector<ModelFeaturePoint> &modelfeaturepoints, const DCamera &hcam)      // handtrack.h:92-96
+{
+	const float cam[HT_CAM] = { hcam.focal().x, hcam.focal().y, hcam.principal().x, hcam.principal().y, hcam.depth_scale, hcam.pose.position.x, hcam.pose.position.y, hcam.pose.position.z,
+	                            hcam.pose.orientation.x, hcam.pose.orientation.y, hcam.pose.orientation.z, hcam.pose.orientation.w };
+	std::vector<float2> u; detail::keypoints_on(detail::live_ctx(), pose, modelfeaturepoints, false, cam, nullptr, 0, 0, 0.0f, 0.0f, nullptr, &u, nullptr); return u;
+}
+
 class CNN;
 CNN PoseInitializerCNN(std::string filename, int device);
 class CNN                                                                                    // third_party/cnn.h:100-605 (Eval / Train / loadb / saveb)
@@ -382,6 +423,16 @@ struct HandTracker                                                              
 		// joints' own coordinates c = (s.x, s.y, t.z) per joint (ht_joint_coords), the same as angles in the reference's degrees (2 asin(c) 180 / 3.14), how far every
 		// joint's two anchors are apart (what FixPositions closes, physmodel.h:404-408), and the way back (ht_joint_pose: FixOrientations / FixPositions top down
 		// from body 0, which stays where it is; momenta untouched).  SetJointCoords(GetJointCoords()) closes the joints and keeps the orientations.
+		// (Addition) a built-in keypoint table of the model as scale() left it: HT_KP_FEATURE8 (handmodelfeaturepoints) or HT_KP_SKELETON (the wrist, every joint, every fingertip)
+		std::vector<ModelFeaturePoint> GetKeypoints(int which = HT_KP_FEATURE8) const
+		{
+			int K = 0; check(ctx_, ht_keypoint_table(ctx_, which, &K, nullptr, nullptr, nullptr));
+			std::vector<int> bones(K), rel(K); std::vector<float> off((size_t)K * 3);
+			check(ctx_, ht_keypoint_table(ctx_, which, nullptr, bones.data(), off.data(), rel.data()));
+			std::vector<ModelFeaturePoint> t;
+			for (int k = 0; k < K; k++) t.push_back(ModelFeaturePoint(bones[k], float3{ off[3 * k], off[3 * k + 1], off[3 * k + 2] }, rel[k]));
+			return t;
+		}
 		std::vector<float3> GetJointCoords() const { std::vector<float3> c; joints(&c, nullptr); return c; }
 		std::vector<float> GetJointGaps() const { std::vector<float> g; joints(nullptr, &g); return g; }
 		std::vector<float3> JointAngles() const
@@ -592,6 +643,38 @@ struct HandTracker                                                              
 		return out;
 	}
 	Image<unsigned short> render_depth(const std::vector<Pose> &poses, const DCamera &cam, float far = 4.0f) const { return render_depth(std::vector<std::vector<Pose>>{ poses }, cam, far)[0]; }
+	// Additions, not reference names (ht_mi355x.h "tracking accuracy").  keypoints: where the hand of the latest update is in `image` -- the points of a built-in table in
+	// the poses' frame, in pixels of image.cam, and their visibility against the frame (0 visible, 1 occluded, 2 nothing there, 3 outside the image, 4 behind the camera;
+	// the tolerances in metres).  What the reference's overlay computes per point (handtrack.h:632-634).  With left_hand set the points are the left hand's.
+	struct Keypoints { std::vector<float3> xyz; std::vector<float2> pixels; std::vector<unsigned char> visibility; };
+	Keypoints keypoints(const Image<unsigned short> &image, int which = HT_KP_FEATURE8, float near_tol = 0.03f, float far_tol = 0.02f) const
+	{
+		if (image.raster.size() != (size_t)image.dim().x * image.dim().y) throw std::runtime_error("HandTracker: the raster does not match the camera's dimensions");
+		float cam[HT_CAM]; cam12(image.cam, cam);
+		Keypoints k;
+		detail::keypoints_on(ctx_, handmodel.GetPose(), handmodel.GetKeypoints(which), left_hand, cam, image.raster.data(), image.dim().x, image.dim().y, near_tol, far_tol, &k.xyz, &k.pixels, &k.visibility);
+		return k;
+	}
+	// depth_residual: how well the posed model explains `image` -- the hull model of the latest update rendered through image.cam (ht_render_depth) and compared with the
+	// frame over the pixels inside wrange (metres, half open as HandSegmentVR's): pixel counts, silhouette overlap, and the depth residual over the overlap in metres.
+	// A left hand is compared in the mirrored frame, where its slot's state lives.
+	struct DepthResidual { long long n_observed, n_rendered, n_both, n_close; double iou, mean_abs, rms, max_abs; };
+	DepthResidual depth_residual(const Image<unsigned short> &image, float2 wrange = { 0.1f, 0.65f }, float close_tol = 0.01f) const
+	{
+		const Image<unsigned short> im = left_hand ? mirror_image(image) : image;
+		const int w = im.dim().x, h = im.dim().y;
+		if (im.raster.size() != (size_t)w * h) throw std::runtime_error("HandTracker: the raster does not match the camera's dimensions");
+		float cam[HT_CAM]; cam12(im.cam, cam);
+		const float ds = im.cam.depth_scale;
+		const std::vector<float> p7 = flat(handmodel.read(false));
+		long long info[8];
+		check(ctx_, ht_pose_depth_residual(ctx_, p7.data(), cam, im.raster.data(), w, h, 1, HT_KP_COM_POSES, 4.0f, (int)(wrange.x / ds), (int)(wrange.y / ds), (int)(close_tol / ds), (int64_t *)info, nullptr));
+		DepthResidual r = { info[0], info[1], info[2], info[3], 0.0, 0.0, 0.0, (double)info[6] * ds };
+		const long long uni = info[0] + info[1] - info[2];
+		r.iou = uni ? (double)info[2] / (double)uni : 0.0;
+		if (info[2]) { r.mean_abs = (double)info[4] / (double)info[2] * ds; r.rms = std::sqrt((double)info[5] / (double)info[2]) * ds; }
+		return r;
+	}
 	// Addition, not a reference name: GatherHandExpectedCNN (handtrack.h:160-173) for a batch of pose sets on this tracker's device, frame b seen by the
 	// heat-map camera hcams[b] (as the single-frame form takes it); segment_frame: train-cnn's compress first (train-cnn.cpp:31-50: the poses in the
 	// camera's frame, the camera at the identity).  The same ExpectedCNN sets as the single-frame form, bit for bit (ht_expected_cnn_batch).

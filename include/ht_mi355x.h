@@ -548,6 +548,63 @@ int ht_split_hands_dev(ht_ctx *ctx, const uint16_t *d_depth, const float *d_cams
 int ht_update_two_hands_sync(ht_ctx *ctx, int side, const uint16_t *depth, const float *cams, int w, int h, float segment_scale, uint16_t range_lo, uint16_t range_hi, uint16_t max_step, int min_pixels, uint16_t far, int flags, int B, float *poses_out, int32_t *info, float *cnn_out);
 int ht_update_two_hands_dev(ht_ctx *ctx, int side, const uint16_t *d_depth, const float *d_cams, int w, int h, float segment_scale, uint16_t range_lo, uint16_t range_hi, uint16_t max_step, int min_pixels, uint16_t far, int flags, const float *d_start_poses, int B, float *d_poses_out, int32_t *d_info, void *stream);
 
+/* ---- tracking accuracy (an addition: the reference places model points in the image in every application and measures nothing) -----------------------------
+ * Keypoints of a batch of poses in 3-D and in pixels with their visibility against the depth frame, keypoint errors between two pose sets with the literature's
+ * summary figures, the depth residual and silhouette overlap of two sets of frames, and poses against frames in one call.  Everything fp32, one IEEE operation
+ * after another in the written order; a pose is position + quaternion xyzw, a camera the 12 floats of the header (focal xy, principal xy, depth_scale, pose).
+ * For all of them B is not bounded by max_batch, B = 0 does nothing, every check runs before anything grows or launches, and a refused call leaves the context usable.
+ *   keypoint table  K entries (bone, offset[3], rel): rel = 0, the offset is in the body's user frame (GetPoseUser); rel = 1, in its centre-of-mass frame (GetPose).
+ *                   HT_KP_FEATURE8: handmodelfeaturepoints (handtrack.h:77-81) verbatim, rel = 1, hand layouts only (HT_SAMPLE_ENHANCED's rule; HT_ERR_ARG otherwise).
+ *                   HT_KP_SKELETON, all rel = 0: body 0's user origin; then per joint in model order its child-side anchor (rbi1, p1); then per leaf body (a body
+ *                   that is no joint's rbi0) in body order (b, com[b]): 1 + 16 + 5 = 22 entries for the stock hand.  ht_scale rescales both with the model.
+ *                   HT_KP_CALLER: the caller's bones / offsets [K][3] / rel (HOST arrays in both forms), 1 <= K <= HT_KP_MAX, bones in [0, nb), finite offsets.
+ *   position        o' = o when rel matches the poses' convention; user poses (the default, what the update calls return) and rel = 1: o' = o + com[bone];
+ *                   HT_KP_COM_POSES and rel = 0: o' = o - com[bone]; then, for a frame flagged in hands [B] (uint8, optional: a left hand in real space as
+ *                   ht_update_hands_* returns it), the sign bit of o'.x is flipped.  X = pos + qrot(q, o'): Skin (handtrack.h:82-84).  xyz [B][K][3], the poses' frame.
+ *   pixels          v = qrot(conj(qc), X - pc) with the camera's pose (pc, qc); u = v.x / v.z * fx + cx, likewise y: projectz(cam.pose.inverse() * X),
+ *                   ImageFeaturePoints (handtrack.h:92-96; the overlay :632-634, dataexporter.cpp:82,105, annotation-fixer.cpp:315-317).  pix [B][K][2], zc [B][K] = v.z.
+ *   visibility      vis [B][K] uint8 against depth [B][h][w]: ix = floorf(u + 0.5f), iy likewise (deprojectz's whole-pixel convention, misc_image.h:48); tested in
+ *                   this order: 4 if !(v.z > 0); 3 if !(u + 0.5f >= 0 && u + 0.5f < w) or the same fails for y (in float, so non-finite values land here);
+ *                   with d = (float)depth[iy][ix] * depth_scale: 1 (occluded) if d < v.z - near_tol; 2 (nothing there) if d > v.z + far_tol; 0 (visible) otherwise.
+ *                   Keypoints lie inside their bones: near_tol must cover a bone's half thickness.
+ * ht_keypoint_table   a built-in table of the context's model as ht_scale left it: *K, bones [K], offsets [K][3], rel [K]; any output may be NULL.
+ * ht_keypoints        poses [B][nb][7] -> xyz, pix, zc, vis, each optional (NULL).  which: HT_KP_FEATURE8, HT_KP_SKELETON or HT_KP_CALLER (K, bones, offsets, rel are
+ *                     read only then).  flags: HT_KP_COM_POSES.  pix and zc need cams [B][12]; vis needs cams and depth, w, h in [1, 4096] and finite tolerances >= 0
+ *                     in metres (HT_ERR_ARG otherwise).  HT_ERR_STATE for a context without a hand model.
+ * ht_keypoint_errors  a, b [B][K][3] -> dist [B][K] = sqrtf(dx dx + dy dy + dz dz) summed left to right; frame [B][2] = the fp32 sum over k ascending divided by
+ *                     (float)K, and the maximum over k (a NaN distance makes both NaN); over the batch sum_kp [K] (double: every distance widened, then added, in
+ *                     any order), hits_kp [T] (int64: pairs with dist <= thr[t]) and hits_frame [T] (int64: frames whose maximum is <= thr[t], the "fraction of
+ *                     frames with the worst joint under e" curve).  NaN hits nothing.  1 <= K <= HT_KP_MAX, 0 <= T <= HT_KP_MAX_THR, thr [T] a HOST array in both
+ *                     forms; every output is optional.  Needs no model: works on a CNN-only context.
+ * ht_depth_compare    a, b [B][h][w] u16 -> info [B][8] int64; a pixel is foreground iff lo <= p < hi in raw units (ht_split_hands' half-open rule; 0 <= lo < hi <= 65536):
+ *                     n_a, n_b, n_both, n_close (in both, |a - b| <= tol), sum |a - b| over both, sum (a - b)^2 over both, max |a - b| over both (0 if none), 0.
+ *                     Exact integers.  w, h in [1, 4096], tol in [0, 65535].  IoU = n_both / (n_a + n_b - n_both); residuals in metres are host arithmetic with
+ *                     depth_scale.  The device form loads 16, 8 or 4 bytes per thread as the width and both pointers allow (ht_mirror_frames' rule), else single
+ *                     pixels.  Needs no model.
+ * ht_pose_depth_residual  poses against frames: each pose is brought to what ht_render_depth takes -- without HT_KP_COM_POSES pos += qrot(q, com[b]) (the inverse of
+ *                     PositionUser, physics.h:142); then, unless the frame's camera pose is bit for bit (0,0,0, 0,0,0,1), pos' = qrot(conj(qc), pos - pc) and
+ *                     q' = qmul(conj(qc), q) -- ht_render_depth renders them at `far` into a buffer of the context (grown to the largest call by one synchronising
+ *                     re-allocation before anything is enqueued), and ht_depth_compare runs with a = depth (observed) and b = rendered.  rendered [B][h][w] is
+ *                     an optional output.  Choose hi <= far / depth_scale to keep the rendered background out (not checked: depth_scale is per frame).
+ *                     HT_ERR_STATE for a context without a hand model.  No left-hand form (mirror first), no mesh-renderer form (ht_render_mesh_depth, then
+ *                     ht_depth_compare).
+ * The host forms refuse output buffers that overlap an input (HT_ERR_ARG); the *_dev forms take device buffers (hands included) and are asynchronous on `stream`. */
+#define HT_KP_COM_POSES 1
+#define HT_KP_FEATURE8 0
+#define HT_KP_SKELETON 1
+#define HT_KP_CALLER 2
+#define HT_KP_MAX 64
+#define HT_KP_MAX_THR 32
+int ht_keypoint_table(ht_ctx *ctx, int which, int *K, int *bones, float *offsets, int *rel);
+int ht_keypoints(ht_ctx *ctx, const float *poses, int B, int flags, int which, int K, const int *bones, const float *offsets, const int *rel, const uint8_t *hands, const float *cams, const uint16_t *depth, int w, int h, float near_tol, float far_tol, float *xyz, float *pix, float *zc, uint8_t *vis);
+int ht_keypoints_dev(ht_ctx *ctx, const float *d_poses, int B, int flags, int which, int K, const int *bones, const float *offsets, const int *rel, const uint8_t *d_hands, const float *d_cams, const uint16_t *d_depth, int w, int h, float near_tol, float far_tol, float *d_xyz, float *d_pix, float *d_zc, uint8_t *d_vis, void *stream);
+int ht_keypoint_errors(ht_ctx *ctx, const float *a, const float *b, int B, int K, const float *thr, int T, float *dist, float *frame, double *sum_kp, int64_t *hits_kp, int64_t *hits_frame);
+int ht_keypoint_errors_dev(ht_ctx *ctx, const float *d_a, const float *d_b, int B, int K, const float *thr, int T, float *d_dist, float *d_frame, double *d_sum_kp, int64_t *d_hits_kp, int64_t *d_hits_frame, void *stream);
+int ht_depth_compare(ht_ctx *ctx, const uint16_t *a, const uint16_t *b, int w, int h, int B, int lo, int hi, int tol, int64_t *info);
+int ht_depth_compare_dev(ht_ctx *ctx, const uint16_t *d_a, const uint16_t *d_b, int w, int h, int B, int lo, int hi, int tol, int64_t *d_info, void *stream);
+int ht_pose_depth_residual(ht_ctx *ctx, const float *poses, const float *cams, const uint16_t *depth, int w, int h, int B, int flags, float far, int lo, int hi, int tol, int64_t *info, uint16_t *rendered);
+int ht_pose_depth_residual_dev(ht_ctx *ctx, const float *d_poses, const float *d_cams, const uint16_t *d_depth, int w, int h, int B, int flags, float far, int lo, int hi, int tol, int64_t *d_info, uint16_t *d_rendered, void *stream);
+
 /* ---- annotation fit loop ---------------------------------------------------------------------------------------------
  * ht_slowfit          replaces  void HandTracker::slowfit(const std::vector<float3> &points, int hold, const std::vector<Pose> &refpose,
  *                     int steps_ = 6, RigidBody *selectrb = NULL, const float3 &spoint, const float3 &rbpoint, const std::vector<float4> &crays)
