@@ -108,7 +108,7 @@ struct ht_ctx
 	char *d_render = nullptr; size_t render_cap = 0;             // both renderers' staging (ht_render_depth, ht_render_mesh_depth: poses, cameras, frames, body labels), grown to the largest call (dev_grow)
 	char *d_labels = nullptr; size_t labels_cap = 0;             // ht_expected_cnn_batch's staging (poses, cameras, labels, image points, key angles), grown to the largest call (dev_grow)
 	char *d_segment = nullptr; size_t segment_cap = 0;           // ht_segment_vr's staging (frames, cameras, tiles, segment cameras), grown to the largest call (dev_grow)
-	char *d_sensor = nullptr; size_t sensor_cap = 0;             // ht_sensor_filter's and ht_sensor_background's staging (frames, IR, cameras, background model, filtered frames), grown to the largest call (dev_grow)
+	char *d_sensor = nullptr; size_t sensor_cap = 0;             // ht_sensor_filter's, ht_sensor_background's and ht_sensor_simulate's staging (frames, IR, cameras, background model, output frames), grown to the largest call (dev_grow)
 	std::vector<float4> render_planes; std::vector<float> render_radii;     // the hull planes ht_render_depth last derived its per-body cull radii from, and those radii (2 per body)
 	// ht_render_mesh_depth: the subdivision meshes' corners [t][9] over all bodies (ht_scale rewrites them), the first triangle of every body, the device rows
 	// [t][4] float4 (corners and PolyPlane, ht_mesh_rows) and the farthest corner of every body's mesh from its centre of mass (ht_mesh_upload makes both)

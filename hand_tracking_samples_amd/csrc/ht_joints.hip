@@ -22,6 +22,7 @@
 #include <string.h>
 #include <math.h>
 #include "ht_host.hpp"
+#include "ht_mix.hpp"
 
 #define JT_THREADS 64
 #define JC_THREADS 256
@@ -88,15 +89,10 @@ __global__ __launch_bounds__(JC_THREADS) void k_joint_coords(const ht_model_dev 
 	}
 }
 
-// ---- the sampler's uniform numbers: a counter-based hash of (seed, sample, joint, axis), the top 24 bits of the second mix -------------------------------
-HT_HD unsigned long long jt_mix(unsigned long long x)
-{
-	x ^= x >> 30; x *= 0xBF58476D1CE4E5B9ull; x ^= x >> 27; x *= 0x94D049BB133111EBull; x ^= x >> 31;
-	return x;
-}
+// ---- the sampler's uniform numbers: a counter-based hash of (seed, sample, joint, axis), the top 24 bits of the second mix (ht_mix.hpp) -------------------------------
 HT_HD float jt_uniform(unsigned long long seed, unsigned long long sample, int joint, int axis)
 {
-	const unsigned long long h = jt_mix(jt_mix(seed ^ (sample * 0x9E3779B97F4A7C15ull)) ^ ((unsigned long long)(joint * 3 + axis + 1) * 0xD6E8FEB86659FD93ull));
+	const unsigned long long h = ht_mix64(ht_mix64(seed ^ (sample * 0x9E3779B97F4A7C15ull)) ^ ((unsigned long long)(joint * 3 + axis + 1) * 0xD6E8FEB86659FD93ull));
 	return (float)(unsigned)(h >> 40) * 5.9604644775390625e-8f;      // exact: 24 bits times 2^-24
 }
 

@@ -20,9 +20,13 @@
 //             pixels is the sequential composition, the carry across lanes is the scan, and no carry crosses a wave.  LDS: a rolling window of five rows of
 //             u16 (rows y-2 .. y+2) and one row of transition bytes, 11 bytes per pixel of width (3.5 KB at 320).
 // Pass 1, pass 3 (the background model), the halving and FilterIvy are pointwise.
+//
+// ht_sensor_simulate, the way back -- rendered frames made raw -- is an addition with no reference code; it has the second half of this file.
 #include <limits.h>
+#include <string.h>
 #include "ht_device.hpp"
 #include "ht_host.hpp"
+#include "ht_mix.hpp"
 
 #define SN_DARK 4096            // what a dropped pixel becomes (dcam.h:186,196,203), and what the background model starts at (:159)
 #define SN_THREADS 256          // the pointwise kernels
@@ -259,4 +263,233 @@ extern "C" int ht_sensor_background(ht_ctx *ctx, const uint16_t *depth, int w, i
 		                      if (!init) HIPCHK(ctx, hipMemcpyAsync(seg[1].dev, background, bytes, hipMemcpyHostToDevice, s));
 		                      return ht_sensor_background_dev(ctx, (const uint16_t *)seg[0].dev, w, h, B, fudge, init, (uint16_t *)seg[1].dev, s);
 	                      });
+}
+
+// ---- ht_sensor_simulate: raw camera frames from rendered depth (an addition; the definition is include/ht_mi355x.h's) -------------------------
+// A 3x3 stencil over u16 frames plus one 64-bit mix per pixel (two with an IR image).
+//   mapping   one thread makes N consecutive pixels of a row: it loads its own N pixels of rows y-1, y, y+1 as one vector each (global_load_dwordx4 at N = 8)
+//             and the single pixels left and right of them, six u16 loads.  Lane i reads base + 16 i of three rows, whole contiguous lines; rows y-1 and y+1 are
+//             the rows the threads of the neighbouring rows load as their own, so every line comes from memory once and from the cache twice more.  No LDS: a
+//             tile with its halo would carry the same lines through one more copy, and the stage's time is its arithmetic, not its loads.
+//             N follows what the width and the pointers allow, by ht_mirror_frames' rule: 8 pixels (16 bytes) for w % 8 == 0 and 16-byte aligned frames (the IR
+//             image, whose store is N bytes, 8-byte aligned), 4, 2, and a pixel per thread for an odd width or buffers aligned to their element only.
+//   frames    thread r of blockIdx.x owns vector r of every frame blockIdx.y, blockIdx.y + gridDim.y, ...: its place in the frame is worked out once.  The frame's
+//             key is wave-uniform (scalar unit); the pixel's mix is the only 64-bit multiply chain in the lane.
+//   noise set by value in the kernel's arguments (80 bytes, scalar registers).
+
+#define SS_THREADS 256
+template <int N> struct alignas(2 * N) ss_px { uint16_t v[N]; };
+template <int N> struct alignas(N) ss_ir { uint8_t v[N]; };
+
+HT_HD bool ss_fg(int q, int far_count) { return (unsigned)(q - 1) < (unsigned)(far_count - 1); }      // q != 0 && q < far_count; -1 (outside the image) is not
+HT_HD int ss_abs(int a) { return a < 0 ? -a : a; }
+HT_HD int ss_noise(const ht_sensor_noise &nz, int d, int g)
+{
+	const int s = nz.sigma0_256 + (int)(((unsigned long long)(unsigned)nz.sigma2 * ((unsigned)d * (unsigned)d)) >> 20);      // d <= 65535, sigma2 <= 4096: the shift leaves at most 2^24
+	const int n = s * g + 4736;                    // |s * g| < 2^31 - 4736 for every set the call accepts
+	int q = n / 9472; if (n - q * 9472 < 0) q--;      // floor
+	const int r = d + q;
+	return r < 1 ? 1 : r > 65535 ? 65535 : r;
+}
+// p and its 8 neighbours in raster order (-1: outside the image) -> the output depth and, with want_ir, the IR value
+HT_HD void ss_pixel(const ht_sensor_noise &nz, int kind, unsigned long long key, unsigned i, bool want_ir, int p, const int (&nb)[8], uint16_t &dout, uint8_t &iout)
+{
+	const bool fg = ss_fg(p, nz.far_count), wall = kind == HT_SENSOR_DS4 && nz.wall_count > 0;
+	unsigned long long H = 0;
+	if (fg || wall || want_ir) H = ht_mix64(key ^ ((unsigned long long)(i + 1u) * 0xD6E8FEB86659FD93ull));
+	const int g = (int)((H >> 40) & 63u) + (int)((H >> 46) & 63u) + (int)((H >> 52) & 63u) + (int)(H >> 58) - 126;
+	int d1 = 0;
+	if (fg)
+	{
+		int best = -1, far = 0;
+#pragma unroll
+		for (int k = 0; k < 8; k++)
+		{
+			const int q = nb[k];
+			const int v = ss_fg(q, nz.far_count) ? q : nz.fly_bg_count, diff = ss_abs(v - p);
+			if (q >= 0 && diff > best) { best = diff; far = v; }      // the first of the largest
+		}
+		const int ua = (int)(H & 0xFFFFu), t = (int)((H >> 16) & 0xFFu), ub = (int)((H >> 24) & 0xFFFFu);
+		bool drop = ub >= 65536 - nz.p_hole;
+		int base = p;
+		if (best > nz.edge_step)
+		{
+			if (ua < nz.p_edge_drop) drop = true;
+			else if (ua < nz.p_edge_drop + nz.p_edge_fly) base = p + (((far - p) * t) >> 8);
+		}
+		else
+		{
+			const int gx = ss_fg(nb[3], nz.far_count) && ss_fg(nb[4], nz.far_count) ? ss_abs(nb[4] - nb[3]) : 0;
+			const int gy = ss_fg(nb[1], nz.far_count) && ss_fg(nb[6], nz.far_count) ? ss_abs(nb[6] - nb[1]) : 0;
+			if ((gx > gy ? gx : gy) > nz.slope_step && ub < nz.p_slope_drop) drop = true;
+		}
+		if (!drop) d1 = ss_noise(nz, base, g);
+	}
+	else if (wall) d1 = ss_noise(nz, nz.wall_count, g);
+	if (kind == HT_SENSOR_DS4 && nz.disparity_k > 0 && d1 != 0)
+	{
+		const unsigned K2 = 2u * (unsigned)nz.disparity_k, disp = (K2 + (unsigned)d1) / (2u * (unsigned)d1);      // K <= 2^30: 2K + d1 < 2^32
+		if (disp == 0) d1 = 0;
+		else { const unsigned back = (K2 + disp) / (2u * disp); d1 = (int)(back < 65535u ? back : 65535u); }
+	}
+	dout = (uint16_t)d1;
+	if (want_ir)
+	{
+		const unsigned long long H2 = ht_mix64(H ^ 0xA0761D6478BD642Full);
+		if (d1 != 0)
+		{
+			const unsigned dd = (unsigned)d1 * (unsigned)d1;
+			const int gi = (int)((H2 >> 8) & 63u) + (int)((H2 >> 14) & 63u) - 63;
+			const long long v = (long long)nz.ir_floor + (long long)((unsigned)nz.ir_gain / ((dd >> 8) + 1u)) + (long long)((gi * nz.ir_noise) >> 6);
+			iout = (uint8_t)(v < 8 ? 8 : v > 255 ? 255 : v);
+		}
+		else iout = (uint8_t)(H2 & 7u);
+	}
+}
+
+// vector (x0 .. x0 + N - 1, y) of frame f; host and device, so that a CPU build can walk the same code
+template <int N> HT_HD void ss_vector(const uint16_t *__restrict__ in, uint16_t *__restrict__ out, uint8_t *__restrict__ ir, int kind, int w, int h, int y, int x0, unsigned f, const ht_sensor_noise &nz)
+{
+	const bool lf = x0 > 0, rt = x0 + N < w, have[3] = { y > 0, true, y + 1 < h };
+	const size_t frame_px = (size_t)w * h, o = (size_t)y * w + x0;
+	const bool want_ir = ir != nullptr;
+	const unsigned long long key = ht_mix64(nz.seed ^ ((nz.first_index + f) * 0x9E3779B97F4A7C15ull));
+	const uint16_t *F = in + (size_t)f * frame_px + o;
+	int a[3][N + 2];
+#pragma unroll
+	for (int j = 0; j < 3; j++)
+	{
+		if (have[j])
+		{
+			const uint16_t *row = F + (ptrdiff_t)(j - 1) * w;      // inside the frame: have[j]
+			const ss_px<N> v = *(const ss_px<N> *)row;
+#pragma unroll
+			for (int k = 0; k < N; k++) a[j][k + 1] = v.v[k];
+			a[j][0] = lf ? (int)row[-1] : -1;
+			a[j][N + 1] = rt ? (int)row[N] : -1;
+		}
+		else
+		{
+#pragma unroll
+			for (int k = 0; k < N + 2; k++) a[j][k] = -1;
+		}
+	}
+	ss_px<N> po; ss_ir<N> io;
+#pragma unroll
+	for (int k = 0; k < N; k++)
+	{
+		const int nb[8] = { a[0][k], a[0][k + 1], a[0][k + 2], a[1][k], a[1][k + 2], a[2][k], a[2][k + 1], a[2][k + 2] };
+		io.v[k] = 0;
+		ss_pixel(nz, kind, key, (unsigned)o + (unsigned)k, want_ir, a[1][k + 1], nb, po.v[k], io.v[k]);
+	}
+	*(ss_px<N> *)(out + (size_t)f * frame_px + o) = po;
+	if (want_ir) *(ss_ir<N> *)(ir + (size_t)f * frame_px + o) = io;
+}
+template <int N> __global__ __launch_bounds__(SS_THREADS) void k_sensor_simulate(const uint16_t *__restrict__ in, uint16_t *__restrict__ out, uint8_t *__restrict__ ir, int kind, int w, int h,
+                                                                                 unsigned per_row, unsigned per_frame, unsigned B, const ht_sensor_noise nz)
+{
+	const unsigned r = blockIdx.x * SS_THREADS + threadIdx.x;
+	if (r >= per_frame) return;
+	const int y = (int)(r / per_row), x0 = (int)(r - (unsigned)y * per_row) * N;
+	for (unsigned f = blockIdx.y; f < B; f += gridDim.y) ss_vector<N>(in, out, ir, kind, w, h, y, x0, f, nz);
+}
+
+// x86's truncating float -> int conversion, then the low 16 bits (sn_fill above, on the host)
+static int ss_trunc16(float q)
+{
+	const int v = (q >= -2147483648.0f && q < 2147483648.0f) ? (int)q : INT_MIN;
+	return (int)((unsigned)v & 0xFFFFu);
+}
+extern "C" int ht_sensor_noise_default(int kind, float depth_scale, float far, ht_sensor_noise *out)
+{
+	if (!out || (kind != HT_SENSOR_IVY && kind != HT_SENSOR_DS4) || !(depth_scale > 0.0f) || !(far > 0.0f)) return HT_ERR_ARG;
+	const int far_count = ss_trunc16(far / depth_scale);
+	if (far_count == 0) return HT_ERR_ARG;
+	const bool ds4 = kind == HT_SENSOR_DS4;
+	const double c = 1.0 / (double)depth_scale;      // counts per metre
+	auto rnd = [](double v, double hi) { return (int)(v < 0.0 ? 0.0 : v > hi ? hi : v + 0.5); };
+	ht_sensor_noise n;
+	memset(&n, 0, sizeof n);
+	n.far_count = far_count;
+	n.sigma0_256 = rnd(256.0 * (ds4 ? 0.0002 : 0.0005) * c, 65536.0);
+	n.sigma2 = rnd(268435456.0 * (ds4 ? 0.004 : 0.002) / c, 4096.0);
+	n.edge_step = rnd(0.020 * c, 65535.0); n.slope_step = rnd(0.015 * c, 65535.0);
+	n.p_edge_drop = rnd(65536.0 * (ds4 ? 0.25 : 0.35), 65536.0); n.p_edge_fly = rnd(65536.0 * (ds4 ? 0.35 : 0.25), 65536.0);
+	n.p_slope_drop = 32768; n.p_hole = rnd(65536.0 * (ds4 ? 0.01 : 0.002), 65536.0);
+	n.fly_bg_count = far_count < 65535 ? far_count : 65535;
+	n.disparity_k = ds4 ? rnd(305.0 * 0.070 * 32.0 * c, 1073741824.0) : 0;
+	n.wall_count = 0;
+	n.ir_floor = 16; n.ir_gain = rnd(c * c / 8.0, 2147483647.0); n.ir_noise = 8;
+	*out = n;
+	return HT_OK;
+}
+
+static int ss_pixels_per_thread(const void *in, const void *out, const void *ir, int w)
+{
+	const uintptr_t a = (uintptr_t)in | (uintptr_t)out, i = (uintptr_t)ir;
+	if (w % 8 == 0 && (a & 15) == 0 && (i & 7) == 0) return 8;
+	if (w % 4 == 0 && (a & 7) == 0 && (i & 3) == 0) return 4;
+	if (w % 2 == 0 && (a & 3) == 0 && (i & 1) == 0) return 2;
+	return 1;
+}
+template <int N> static void ss_launch(int kind, const uint16_t *in, int w, int h, int B, const ht_sensor_noise &nz, uint16_t *out, uint8_t *ir, hipStream_t s)
+{
+	const unsigned per_row = (unsigned)w / N, per_frame = per_row * (unsigned)h;
+	const unsigned gx = (per_frame + SS_THREADS - 1) / SS_THREADS;
+	unsigned gy = (2048 + gx - 1) / gx;      // about eight blocks a CU; a thread then walks the frames blockIdx.y, blockIdx.y + gridDim.y, ...
+	if (gy > (unsigned)B) gy = (unsigned)B;
+	if (gy > 65535u) gy = 65535u;
+	hipLaunchKernelGGL(k_sensor_simulate<N>, dim3(gx, gy), dim3(SS_THREADS), 0, s, in, out, ir, kind, w, h, per_row, per_frame, (unsigned)B, nz);
+}
+
+// every check both forms share, made before anything is launched or grown
+static int ss_check(ht_ctx *ctx, int kind, const void *depth, int w, int h, int B, const ht_sensor_noise *nz, const void *depth_out, const void *ir_out)
+{
+	const char *bad = nullptr;
+	auto in = [](int v, long long hi) { return v >= 0 && (long long)v <= hi; };
+	if (kind != HT_SENSOR_IVY && kind != HT_SENSOR_DS4) bad = "kind";
+	else if (w < 1 || h < 1 || w > 4096 || h > 4096) bad = "w and h between 1 and 4096";
+	else if (B < 0) bad = "B";
+	else if (!depth || !depth_out || !nz) bad = "a NULL buffer";
+	else if (kind == HT_SENSOR_DS4 && !ir_out) bad = "DS4 needs ir_out";
+	else if (nz->far_count < 1 || nz->far_count > 65536) bad = "far_count between 1 and 65536";
+	else if (!in(nz->p_edge_drop, 65536) || !in(nz->p_edge_fly, 65536) || !in(nz->p_slope_drop, 65536) || !in(nz->p_hole, 65536) || nz->p_edge_drop + nz->p_edge_fly > 65536)
+		bad = "a probability outside [0, 65536], or p_edge_drop + p_edge_fly above it";
+	else if (!in(nz->sigma0_256, 65536) || !in(nz->sigma2, 4096) || !in(nz->edge_step, 65535) || !in(nz->slope_step, 65535) || !in(nz->fly_bg_count, 65535) || !in(nz->wall_count, 65535) ||
+	         !in(nz->disparity_k, 1 << 30) || !in(nz->ir_floor, 65536) || nz->ir_gain < 0 || !in(nz->ir_noise, 65536))
+		bad = "a noise figure outside its range";
+	else if (sn_overlap(depth, (size_t)B * w * h * sizeof(uint16_t), depth_out, (size_t)B * w * h * sizeof(uint16_t))) bad = "depth_out overlaps depth";
+	if (bad) { ctx->err = std::string("ht_sensor_simulate: bad argument (") + bad + ")"; return HT_ERR_ARG; }
+	return HT_OK;
+}
+
+extern "C" int ht_sensor_simulate_dev(ht_ctx *ctx, int kind, const uint16_t *d_depth, int w, int h, int B, const ht_sensor_noise *noise, uint16_t *d_depth_out, uint8_t *d_ir_out, void *stream)
+{
+	CHECK_READY(ctx);
+	{ const int r = ss_check(ctx, kind, d_depth, w, h, B, noise, d_depth_out, d_ir_out); if (r) return r; }
+	if (B == 0) return HT_OK;
+	hipStream_t s = ht_user_stream(ctx, stream);
+	{
+		ht_prof_scope ps(ctx, "k_sensor_simulate", s);
+		switch (ss_pixels_per_thread(d_depth, d_depth_out, d_ir_out, w))
+		{
+		case 8: ss_launch<8>(kind, d_depth, w, h, B, *noise, d_depth_out, d_ir_out, s); break;
+		case 4: ss_launch<4>(kind, d_depth, w, h, B, *noise, d_depth_out, d_ir_out, s); break;
+		case 2: ss_launch<2>(kind, d_depth, w, h, B, *noise, d_depth_out, d_ir_out, s); break;
+		default: ss_launch<1>(kind, d_depth, w, h, B, *noise, d_depth_out, d_ir_out, s); break;
+		}
+	}
+	HIPCHK(ctx, hipGetLastError());
+	return HT_OK;
+}
+
+extern "C" int ht_sensor_simulate(ht_ctx *ctx, int kind, const uint16_t *depth, int w, int h, int B, const ht_sensor_noise *noise, uint16_t *depth_out, uint8_t *ir_out)
+{
+	CHECK_READY(ctx);
+	{ const int r = ss_check(ctx, kind, depth, w, h, B, noise, depth_out, ir_out); if (r) return r; }
+	if (B == 0) return HT_OK;
+	const size_t npx = (size_t)B * w * h;
+	ht_seg seg[3] = { { (void *)depth, npx * sizeof(uint16_t), false }, { depth_out, npx * sizeof(uint16_t), true }, { ir_out, npx, true } };
+	return ht_staged_call(ctx, &ctx->d_sensor, &ctx->sensor_cap, seg, 3, [&](hipStream_t s)
+	                      { return ht_sensor_simulate_dev(ctx, kind, (const uint16_t *)seg[0].dev, w, h, B, noise, (uint16_t *)seg[1].dev, (uint8_t *)seg[2].dev, s); });
 }

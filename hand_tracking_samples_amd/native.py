@@ -38,6 +38,7 @@ SYMBOLS = (
     "ht_stage_prepare", "ht_stage_decode", "ht_stage_fit_error", "ht_stage_cloud_rows", "ht_stage_contacts", "ht_stage_fit",
     "ht_stage_multistep", "ht_stage_multistep_range", "ht_stage_scratch_unibody", "ht_stage_chamber", "ht_profile_enable", "ht_profile_read", "ht_debug_solve_stats", "ht_debug_contact_stats", "ht_debug_solver_build", "ht_debug_reset_flags", "ht_debug_reset_organisation", "ht_update_passes_sync", "ht_job_start", "ht_job_poll", "ht_job_wait", "ht_job_collect", "ht_debug_contact_kernel", "ht_debug_contact_order", "ht_debug_rank_desc", "ht_contact_capacity", "ht_debug_solve_tables", "ht_debug_solve_tables_header", "ht_debug_train_buffers",
     "ht_sensor_out_dims", "ht_sensor_filter", "ht_sensor_filter_dev", "ht_sensor_background", "ht_sensor_background_dev",
+    "ht_sensor_noise_default", "ht_sensor_simulate", "ht_sensor_simulate_dev",
     "ht_model_joint_limits", "ht_joint_coords", "ht_joint_coords_dev", "ht_joint_pose", "ht_joint_pose_dev", "ht_sample_poses", "ht_sample_poses_dev",
     "ht_mirror_frames", "ht_mirror_frames_dev", "ht_mirror_cams", "ht_mirror_cams_dev", "ht_mirror_poses", "ht_mirror_poses_dev", "ht_update_hands_sync", "ht_update_hands_dev", "ht_reserve_hands", "ht_hands_capacity",
     "ht_model_mirror", "ht_model_body_planes",
@@ -56,6 +57,22 @@ class Params(C.Structure):
                 ("physics_iterations", C.c_int), ("physics_iterations_post", C.c_int), ("physics_use_collision", C.c_int),
                 ("physics_weak_force", C.c_float), ("bone_sum_error_scale", C.c_float), ("unibody_force", C.c_float),
                 ("subsample_voxel", C.c_int), ("subsample_size", C.c_float)]
+
+
+class SensorNoise(C.Structure):
+    """ht_sensor_noise (include/ht_mi355x.h): the noise set of ht_sensor_simulate, field for field."""
+    _fields_ = [("seed", C.c_uint64), ("first_index", C.c_uint64), ("far_count", C.c_int), ("sigma0_256", C.c_int), ("sigma2", C.c_int), ("edge_step", C.c_int), ("slope_step", C.c_int),
+                ("p_edge_drop", C.c_int), ("p_edge_fly", C.c_int), ("p_slope_drop", C.c_int), ("p_hole", C.c_int), ("fly_bg_count", C.c_int), ("disparity_k", C.c_int), ("wall_count", C.c_int),
+                ("ir_floor", C.c_int), ("ir_gain", C.c_int), ("ir_noise", C.c_int)]
+
+    def but(self, **kw):
+        """a copy with some fields changed"""
+        n = SensorNoise.from_buffer_copy(self)
+        for k, v in kw.items():
+            if k not in dict(self._fields_):
+                raise TypeError("ht_sensor_noise has no field %r" % k)
+            setattr(n, k, int(v))
+        return n
 
 
 class HTError(RuntimeError):
@@ -161,6 +178,9 @@ def load(build_if_missing=True):
     L.ht_sensor_filter_dev.argtypes = [vp, C.c_int, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp]
     L.ht_sensor_background.argtypes = [vp, u16p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, u16p]
     L.ht_sensor_background_dev.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]
+    L.ht_sensor_noise_default.argtypes = [C.c_int, C.c_float, C.c_float, C.POINTER(SensorNoise)]
+    L.ht_sensor_simulate.argtypes = [vp, C.c_int, u16p, C.c_int, C.c_int, C.c_int, C.POINTER(SensorNoise), u16p, C.POINTER(C.c_uint8)]
+    L.ht_sensor_simulate_dev.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.POINTER(SensorNoise), vp, vp, vp]
     L.ht_render_mesh_depth.argtypes = [vp, fp, fp, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int, u16p, C.POINTER(C.c_int8)]
     L.ht_render_mesh_depth_dev.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int, vp, vp, vp]
     L.ht_model_hitcheck_mesh.argtypes = [vp, fp, fp, fp, fp, fp, ip, ip]
@@ -957,6 +977,21 @@ class Context:
         """ht_sensor_background_dev: device pointers, asynchronous on `stream`."""
         self._chk(self.L.ht_sensor_background_dev(self.h, d_depth, int(w), int(h), int(B), int(fudge), int(bool(init)), d_background, stream))
 
+    def sensor_simulate(self, kind, depth, noise, want_ir=None):
+        """ht_sensor_simulate: clean rendered frames u16[B,h,w] -> raw frames of camera `kind` under the noise set `noise` (SensorNoise; sensor_noise_default);
+        frame f is stream noise.first_index + f.  Returns (depth u16[B,h,w], ir u8[B,h,w] or None); want_ir defaults to what the kind needs (DS4)."""
+        depth = _c(depth, np.uint16); B, h, w = depth.shape
+        if want_ir is None:
+            want_ir = int(kind) == SENSOR_DS4
+        out = np.empty((B, h, w), np.uint16); ir = np.empty((B, h, w), np.uint8) if want_ir else None
+        u8p, u16p = C.POINTER(C.c_uint8), C.POINTER(C.c_uint16)
+        self._chk(self.L.ht_sensor_simulate(self.h, int(kind), depth.ctypes.data_as(u16p), w, h, B, C.byref(noise), out.ctypes.data_as(u16p), ir.ctypes.data_as(u8p) if want_ir else None))
+        return out, ir
+
+    def sensor_simulate_dev(self, kind, d_depth, w, h, B, noise, d_depth_out, d_ir_out=None, stream=None):
+        """ht_sensor_simulate_dev: device pointers (d_ir_out may be None for Ivy), asynchronous on `stream`; `noise` is read now and travels by value."""
+        self._chk(self.L.ht_sensor_simulate_dev(self.h, int(kind), d_depth, int(w), int(h), int(B), C.byref(noise), d_depth_out, d_ir_out, stream))
+
     def scale(self, s):
         """HandTracker::scale (handtrack.h:591): both models of every slot grow by the factor s."""
         self._chk(self.L.ht_scale(self.h, float(s)))
@@ -1087,6 +1122,15 @@ class Context:
                     out[name] = buf[o:o + n].reshape(shape)
                 o += n
         return out
+
+
+def sensor_noise_default(kind, depth_scale=0.001, far=4.0, **kw):
+    """ht_sensor_noise_default: a plausible SensorNoise for camera `kind` (figures reasoned from data sheets, never measured against a camera), with the fields
+    in kw changed.  ValueError for what the library refuses.  No context, no device."""
+    n = SensorNoise()
+    if load().ht_sensor_noise_default(int(kind), float(depth_scale), float(far), C.byref(n)) != HT_OK:
+        raise ValueError("ht_sensor_noise_default refuses kind %d, depth_scale %g, far %g" % (kind, depth_scale, far))
+    return n.but(**kw) if kw else n
 
 
 def sensor_out_dims(kind, w, h, max_width=320):

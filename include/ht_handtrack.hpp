@@ -861,12 +861,35 @@ private:
 	ht_ctx *ctx_ = nullptr; int nb_ = 0;
 };
 
+// The noise set of ht_sensor_simulate (ht_mi355x.h) as a value: SensorNoise(HT_SENSOR_DS4, cam.depth_scale) holds ht_sensor_noise_default's figures -- reasoned
+// from data sheets, never measured against a camera -- and every field can be changed afterwards (n.seed = ..., n.p_hole = 0).
+struct SensorNoise : ht_sensor_noise
+{
+	SensorNoise() : ht_sensor_noise() { far_count = 3999; fly_bg_count = 3999; edge_step = 20; slope_step = 15; ir_floor = 16; }      // everything off, millimetre counts, 4 m
+	SensorNoise(int kind, float depth_scale = 0.001f, float far = 4.0f)
+	{
+		if (ht_sensor_noise_default(kind, depth_scale, far, this) != HT_OK) throw std::runtime_error("SensorNoise: kind, depth_scale or far refused (ht_sensor_noise_default)");
+	}
+};
+
 // RSCam's depth filters (include/dcam.h:144-244): what dcam.GetDepth() does to the sensor's frame before htk.update() sees it, on the device of the first live
 // HandTracker.  No librealsense and no device handle: the caller hands over the raw frame (and, for an R200, the IR image of the same size) it got from its camera.
 //     auto dimage = cam.FilterIvy(raw);  auto pose = htk.update(std::move(dimage));      // replaces htk.update(dcam.GetDepth()), realtime-tracker.cpp:56
 struct RSCam
 {
 	int image_width_max_allowed = 320;                                                         // dcam.h:153
+	Image<unsigned char> cache_ir;                                                             // dcam.h:163: the IR image that goes with the latest depth frame; SimulateDS4 writes it
+	// Raw frames from rendered ones (ht_sensor_simulate; an addition): what a camera of either kind would have handed over instead of the clean frame `image`.
+	// One frame is one stream: the frame is stream noise.first_index.  SimulateDS4 also gives the IR image (in *ir if asked for, and in cache_ir), so that
+	//     auto raw = cam.SimulateDS4(rendered, noise);  auto dimage = cam.FilterDS4(raw, cam.cache_ir);
+	Image<unsigned short> SimulateIvy(const Image<unsigned short> &image, const SensorNoise &noise) { return simulate(HT_SENSOR_IVY, image, noise, nullptr); }
+	Image<unsigned short> SimulateDS4(const Image<unsigned short> &image, const SensorNoise &noise, Image<unsigned char> *ir = nullptr)
+	{
+		cache_ir = Image<unsigned char>(image.cam);
+		Image<unsigned short> out = simulate(HT_SENSOR_DS4, image, noise, cache_ir.raster.data());
+		if (ir) *ir = cache_ir;
+		return out;
+	}
 	std::vector<uint16_t> background;                                                          // dcam.h:156: empty until addbackground is called
 	void addbackground(const Image<unsigned short> &dp, unsigned short fudge = 3)              // dcam.h:157-162
 	{
@@ -879,6 +902,14 @@ struct RSCam
 private:
 	static ht_ctx *ctx() { if (!detail::live_ctx()) throw std::runtime_error("RSCam: construct a HandTracker first (the filters run on its device)"); return detail::live_ctx(); }
 	static void detail_check(int rc) { check(detail::live_ctx(), rc); }
+	Image<unsigned short> simulate(int kind, const Image<unsigned short> &image, const SensorNoise &noise, unsigned char *ir)
+	{
+		const int w = image.dim().x, h = image.dim().y;
+		if (w < 1 || h < 1 || image.raster.size() != (size_t)w * h) throw std::runtime_error("RSCam: a frame of this size cannot be simulated");
+		Image<unsigned short> out(image.cam);
+		detail_check(ht_sensor_simulate(ctx(), kind, image.raster.data(), w, h, 1, &noise, out.raster.data(), ir));
+		return out;
+	}
 	Image<unsigned short> filter(int kind, const Image<unsigned short> &dp, const unsigned char *ir, size_t nir)
 	{
 		const int w = dp.dim().x, h = dp.dim().y;

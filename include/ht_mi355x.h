@@ -467,6 +467,76 @@ int ht_sensor_filter_dev(ht_ctx *ctx, int kind, const uint16_t *d_depth, const u
 int ht_sensor_background(ht_ctx *ctx, const uint16_t *depth, int w, int h, int B, int fudge, int init, uint16_t *background);
 int ht_sensor_background_dev(ht_ctx *ctx, const uint16_t *d_depth, int w, int h, int B, int fudge, int init, uint16_t *d_background, void *stream);
 
+/* ---- raw camera frames from rendered depth (an addition: the reference has no sensor model) --------------------------------------------
+ * ht_render_depth and ht_render_mesh_depth give perfect frames.  ht_sensor_simulate turns them into what a camera of either kind would hand to the filters
+ * above: axial noise that grows with depth, silhouettes that fray (drop-outs and flying pixels), drop-outs at grazing angles, random holes, the R200's
+ * disparity quantisation and an IR image -- the input ht_sensor_filter was written for.  Frames keep their size and their camera.  Reproducible from a seed.
+ * All arithmetic is integer; an intermediate is int64 wherever a product can exceed 31 bits; `//` is floor division; `>>` is arithmetic on signed values.
+ *
+ * Random bits.  mix is the 64-bit mixing function of ht_sample_poses (csrc/ht_mix.hpp).  Frame f of a call is stream first_index + f (mod 2^64):
+ *     key = mix(seed ^ ((first_index + f) * 0x9E3779B97F4A7C15))                    per frame
+ *     H   = mix(key ^ ((i + 1) * 0xD6E8FEB86659FD93)),  i = y*w + x                 per pixel: one mix
+ *     H2  = mix(H ^ 0xA0761D6478BD642F)                                             per pixel, only with an IR image
+ *   fields of H:  ua = bits 0-15, t = bits 16-23, ub = bits 24-39, g = the sum of the four 6-bit fields at bits 40, 46, 52 and 58, minus 126 (mean 0, sd 36.95)
+ *   fields of H2: dark = bits 0-2, gi = the sum of the two 6-bit fields at bits 8 and 14, minus 63
+ *   A frame's output depends on (seed, first_index + f) and the frame alone, never on B, on the frame's position in the call or on the launch.
+ * Axial noise.  s(d) = sigma0_256 + ((int64)sigma2 * d * d >> 20) is the sd in 1/256 count at depth d, and
+ *     noise(d) = clamp(d + (s(d) * g + 4736) // 9472, 1, 65535)                     9472 = 256 * 37; the sd of the sum is sqrt((s/256)^2 * 1365/1369 + 1/12) counts
+ * A count c is foreground iff c != 0 && c < far_count.  A foreground pixel p at (x, y), in this order:
+ *   1  its neighbours are the 8-neighbours that lie in the image, in raster order (x-1,y-1) (x,y-1) (x+1,y-1) (x-1,y) (x+1,y) (x-1,y+1) (x,y+1) (x+1,y+1);
+ *      v(q) = q if q is foreground, else fly_bg_count; diff(q) = |v(q) - p|
+ *   2  it is an edge pixel iff some diff(q) > edge_step; its far neighbour is the first neighbour in that order with the largest diff
+ *   3  edge pixel, ua < p_edge_drop: dropped
+ *   4  edge pixel, otherwise ua < p_edge_drop + p_edge_fly: a flying pixel, base = p + ((v(far) - p) * t >> 8), between p and v(far)
+ *   5  any other pixel: base = p
+ *   6  not an edge pixel: gx = |p[x+1] - p[x-1]| if both are in the image and foreground, else 0; gy likewise along y; max(gx, gy) > slope_step and
+ *      ub < p_slope_drop: dropped
+ *   7  every foreground pixel with ub >= 65536 - p_hole: dropped
+ *   8  d1 = noise(base)
+ *   9  DS4 with disparity_k = K > 0: disp = (2K + d1) // (2 d1); disp == 0: dropped; otherwise d1 = min(65535, (2K + disp) // (2 disp))
+ *   10 the output is d1; a dropped pixel is 0
+ * A background pixel: Ivy 0 (the sensor's "no data", which FilterIvy turns into the far count); DS4 with wall_count > 0: noise(wall_count) through step 9;
+ *   DS4 otherwise 0.  Background pixels never become flying pixels: the silhouette frays inwards only, the hand never grows.
+ * IR (ir_out given).  A pixel whose output depth d is nonzero: min(255, max(8, ir_floor + ir_gain // ((d * d >> 8) + 1) + (gi * ir_noise >> 6))); a pixel whose
+ *   output is 0: dark, in [0, 8) -- what FilterDS4's `ir < 8` rule looks for.
+ *
+ * ht_sensor_noise_default  fills *out for `kind` from the camera's depth_scale (metres per count) and far (metres).  Host only, no context.  far_count is formed as
+ *                       FilterIvy forms its constant, (unsigned short)(far / depth_scale) the x86 way: 3999 at 0.001 and 4.  NOBODY HAS MEASURED THESE FIGURES AGAINST A
+ *                       CAMERA: there is no camera and no recording in this project.  They are defaults for experiments, reasoned from data sheets, not a
+ *                       calibrated model (c = 1 / depth_scale counts per metre):
+ *                         axial sd a + b z^2 metres: sigma0_256 = 256 a c, sigma2 = 2^28 b / c.  Ivy (SR300, coded light) a = 0.5 mm, b = 2 mm/m^2: 1 mm at half a
+ *                           metre, 2.5 mm at one.  DS4 (R200, stereo) a = 0.2 mm, b = 4 mm/m^2: the stereo error z^2 * 0.08 px / (305 px * 70 mm) = 3.7 mm/m^2 at
+ *                           the 320x240 stream's focal length, the R200's 70 mm baseline and a twelfth of a pixel of matching error
+ *                         disparity_k (DS4) = 305 px * 0.070 m * 32 * c: the R200 reports disparity in steps of 1/32 pixel, disp = K / d
+ *                         edge_step 20 mm, slope_step 15 mm over two pixels (a surface turned about 75 degrees away at half a metre), fly_bg_count = far_count
+ *                         p_edge_drop / p_edge_fly 0.35 / 0.25 (Ivy: coded light loses the pattern at an edge) and 0.25 / 0.35 (DS4: block matching blends
+ *                           the two sides), p_slope_drop 0.5, p_hole 0.002 (Ivy) and 0.01 (DS4), wall_count 0
+ *                         ir_floor 16, ir_gain so that a surface at half a metre reads 128 above it (ir_gain = c^2 / 8) and falls with 1 / z^2, ir_noise 8 (sd 3.3 grey levels)
+ *                       HT_ERR_ARG: out NULL, a kind that is neither, depth_scale or far not positive (NaN included), a far_count that comes out 0.
+ * ht_sensor_simulate    depth [B][h*w] -> depth_out [B][h*w], ir_out [B][h*w] (optional for Ivy, required for DS4).  *noise is read on the host at call time.  B is
+ *                       not bounded by max_batch (no tracker slot; the host form stages through a device buffer it grows on demand); B = 0 does nothing.
+ *                       HT_ERR_ARG, checked before anything is launched or grown: a NULL required buffer; a kind that is neither; w or h < 1 or > 4096; B < 0;
+ *                       far_count outside [1, 65536]; a probability outside [0, 65536] or p_edge_drop + p_edge_fly > 65536; depth_out overlapping depth; and, so
+ *                       that no intermediate leaves the width the definition gives it (s(d) * g stays inside 31 bits, 2K + d1 inside 32): sigma0_256, ir_floor or
+ *                       ir_noise outside [0, 65536], sigma2 outside [0, 4096], edge_step, slope_step, fly_bg_count or wall_count outside [0, 65535],
+ *                       disparity_k outside [0, 2^30], ir_gain < 0.
+ * ht_sensor_simulate_dev  the same on device buffers, asynchronous on `stream`: it only enqueues.  The noise set travels by value in the kernel's arguments. */
+typedef struct ht_sensor_noise
+{
+	uint64_t seed, first_index;        /* frame f of a call is stream first_index + f */
+	int far_count;                     /* an input count of 0 or >= far_count is background */
+	int sigma0_256, sigma2;            /* axial sd in 1/256 count at depth d: sigma0_256 + ((int64)sigma2 * d * d >> 20) */
+	int edge_step, slope_step;         /* counts */
+	int p_edge_drop, p_edge_fly, p_slope_drop, p_hole;      /* probabilities in 1/65536 */
+	int fly_bg_count;                  /* the depth a background neighbour stands for when an edge is judged and a flying pixel is mixed */
+	int disparity_k;                   /* DS4 only; 0 = no disparity quantisation */
+	int wall_count;                    /* DS4 only; the depth of the background, 0 = none */
+	int ir_floor, ir_gain, ir_noise;   /* the IR image */
+} ht_sensor_noise;
+int ht_sensor_noise_default(int kind, float depth_scale, float far, ht_sensor_noise *out);
+int ht_sensor_simulate(ht_ctx *ctx, int kind, const uint16_t *depth, int w, int h, int B, const ht_sensor_noise *noise, uint16_t *depth_out, uint8_t *ir_out);
+int ht_sensor_simulate_dev(ht_ctx *ctx, int kind, const uint16_t *d_depth, int w, int h, int B, const ht_sensor_noise *noise, uint16_t *d_depth_out, uint8_t *d_ir_out, void *stream);
+
 /* ---- left hands (an addition: the reference's model, nets and segmentation are a right hand's; its README lists left / right as open work) ----------------
  * A left hand seen by a camera is the mirror image of a right hand seen by the mirrored camera.  The mirror M is x -> -x of the camera's space:
  *   frame  [h][w] u16:  F'[y][x] = F[y][w-1-x]

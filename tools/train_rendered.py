@@ -24,7 +24,14 @@ principal (320, 240)), ht_segment_vr_sized_dev(128, 0xF, {0.1, 0.70}), ht_cnn_in
 ht_cnn_train_batch_sized_dev.  Held out: every 16th ground truth, rendered and segmented the same way.
 
 --sampled (64x64 net) replaces step 1: only the wrist pose of each interpolated ground truth is uploaded (B x 7 floats) and ht_sample_poses_dev(HT_SAMPLE_ENHANCED, --spread)
-draws the hand on the device inside the model's joint limits, sample i of round r from (--seed, r * B + i).  Off by default: the other modes compute what they did."""
+draws the hand on the device inside the model's joint limits, sample i of round r from (--seed, r * B + i).  Off by default: the other modes compute what they did.
+
+--sensor-noise {ivy,ds4} (64x64 net; off by default, and then nothing below runs) puts the camera between the renderer and the segmenter: every rendered 320x240 frame is made
+raw by ht_sensor_simulate_dev under ht_sensor_noise_default's figures (frame f of round r is stream r * B + f of --seed) and filtered by ht_sensor_filter_dev before step 3.  The
+tool then trains TWO nets from the same weights on the same poses and permutations for the same number of frames -- one on clean frames (the same filter call, no simulation; a
+uniformly bright IR image for ds4), one on simulated frames -- and reports each net's held-out MSE on simulated and on clean renderings of the held-out ground truths (every 16th,
+rendered, filtered and segmented the same way; the simulated ones from streams 2^48 onwards).  The noise figures were never measured against a camera: recorded figures, no bar.
+--json writes profiles/r22_sensor_train.json."""
 import argparse
 import json
 import os
@@ -185,6 +192,79 @@ def main128(a):
         json.dump(out, open(a.json, "w"), indent=1)
 
 
+def main_sensor(a):
+    """--sensor-noise: the 64x64 net trained on clean and on simulated frames, both judged on held-out simulated and clean frames"""
+    dev = torch.device("cuda:0")
+    kind = native.SENSOR_IVY if a.sensor_noise == "ivy" else native.SENSOR_DS4
+    noise = native.sensor_noise_default(kind, float(QVGA_CAM[4]), 4.0, seed=a.seed)
+    d = np.load(os.path.join(ROOT, "bench_data", "frames1024.npz"))
+    gt = d["gtpose"].astype(np.float32); pairs = train_pairs(len(gt))
+    B = a.batch
+    fr = np.arange(0, len(gt), HOLD)
+    results, held = {}, None
+    for trained_on in ("clean", "simulated"):
+        rng = np.random.default_rng(a.seed)
+        ctx = native.Context(M17, 64)
+        ctx.load_weights(W.make_cnnb(a.seed, 1.0))
+        if held is None:      # the held-out inputs and labels, once: (x, labels) per kind of frame
+            hcams = np.tile(QVGA_CAM, (len(fr), 1))
+            clean = ctx.render_depth(gt[fr], hcams, 320, 240)
+            raw, ir = ctx.sensor_simulate(kind, clean, noise.but(first_index=1 << 48), want_ir=True)
+            held = {}
+            for name, frames, irs in (("clean", clean, np.full(clean.shape, 120, np.uint8)), ("simulated", raw, ir)):
+                filtered, fc = ctx.sensor_filter(kind, frames, hcams, ir=irs if kind == native.SENSOR_DS4 else None, max_width=320)
+                tiles, tc = ctx.segment_vr(filtered, fc, 0xF, (0.1, 0.70), 0.17)
+                held[name] = (ctx.stage_prepare(tiles.reshape(len(fr), -1), tc)[0], ctx.expected_cnn_batch(gt[fr], tc, segment_frame=True)[0])
+        s = torch.cuda.Stream(device=dev)
+        cams = torch.from_numpy(np.tile(QVGA_CAM, (B, 1))).to(dev); fcams = torch.empty((B, 12), device=dev); tcams = torch.empty((B, 12), device=dev)
+        tp = torch.empty((B, 17, 7), device=dev)
+        depth = torch.empty((B, 240, 320), dtype=torch.int16, device=dev); raw_d = torch.empty_like(depth); filtered_d = torch.empty_like(depth)
+        ir_d = torch.full((B, 240, 320), 120, dtype=torch.uint8, device=dev)
+        tiles = torch.empty((B, 64, 64), dtype=torch.int16, device=dev)
+        x = torch.empty((B, 4096), device=dev); lab = torch.empty((B, 2304), device=dev); mse = torch.empty(B, device=dev)
+        d_ir = ir_d.data_ptr() if kind == native.SENSOR_DS4 else None
+
+        def score():
+            return {name: float(((ctx.cnn_eval(hx) - ht) ** 2).mean()) for name, (hx, ht) in held.items()}
+        before = score()
+        print("%s frames: held-out mse before %s" % (trained_on, before), flush=True)
+        curve = []
+        t0 = time.perf_counter()
+        for r in range(a.rounds):
+            poses = draw(gt, pairs, B, rng); order = rng.permutation(B).astype(np.int32)
+            with torch.cuda.stream(s):
+                tp.copy_(torch.from_numpy(poses))
+                ctx.render_depth_dev(tp.data_ptr(), cams.data_ptr(), 320, 240, 4.0, B, depth.data_ptr(), None, s.cuda_stream)
+                src = depth
+                if trained_on == "simulated":
+                    ctx.sensor_simulate_dev(kind, depth.data_ptr(), 320, 240, B, noise.but(first_index=r * B), raw_d.data_ptr(), d_ir, s.cuda_stream)
+                    src = raw_d
+                ctx.sensor_filter_dev(kind, src.data_ptr(), d_ir, cams.data_ptr(), 320, 240, B, 320, None, filtered_d.data_ptr(), fcams.data_ptr(), s.cuda_stream)
+                assert ctx.L.ht_segment_vr_dev(ctx.h, filtered_d.data_ptr(), fcams.data_ptr(), 320, 240, B, 0xF, 0.1, 0.70, 0.17, tiles.data_ptr(), tcams.data_ptr(), s.cuda_stream) == 0
+                ctx.cnn_input_dev(tiles.data_ptr(), tcams.data_ptr(), B, x.data_ptr(), s.cuda_stream)
+                ctx.expected_cnn_dev(tp.data_ptr(), tcams.data_ptr(), B, lab.data_ptr(), segment_frame=True, stream=s.cuda_stream)
+                if a.minibatch == 1:
+                    ctx.cnn_train_dev(x.data_ptr(), lab.data_ptr(), B, order=order, alpha=a.lr, d_mse=mse.data_ptr(), stream=s.cuda_stream)
+                else:
+                    ctx.cnn_train_batch_dev(x.data_ptr(), lab.data_ptr(), B, a.minibatch, order=order, alpha=a.lr, d_mse=mse.data_ptr(), stream=s.cuda_stream)
+            s.synchronize()
+            if (r + 1) % 10 == 0 or r + 1 == a.rounds:
+                rec = {"round": r + 1, "samples": (r + 1) * B, "train_mse": float(mse.mean().item()), "held_out_mse": score()}
+                curve.append(rec)
+                print(trained_on, rec, "%.0f s" % (time.perf_counter() - t0), flush=True)
+        results[trained_on] = {"held_out_mse_before": before, "held_out_mse_after": curve[-1]["held_out_mse"], "seconds": time.perf_counter() - t0, "curve": curve}
+        ctx.close()
+    out = {"what": "tools/train_rendered.py --sensor-noise %s: two nets from the same seeded weights, %d rounds of %d rendered 320x240 frames each (render, [ht_sensor_simulate_dev,] "
+                   "ht_sensor_filter_dev, segment, input, segment-frame labels, SGD in steps of %d lr %g over a seeded permutation), seed 0x%X; held-out MSE on %d held-out ground "
+                   "truths rendered clean and simulated" % (a.sensor_noise, a.rounds, B, a.minibatch, a.lr, a.seed, len(fr)),
+           "note": "noise figures: ht_sensor_noise_default, reasoned from data sheets, never measured against a camera; recorded figures, no bar",
+           "kind": a.sensor_noise, "noise": {k: getattr(noise, k) for k, _ in noise._fields_}, "rounds": a.rounds, "batch": B, "minibatch": a.minibatch, "lr": a.lr, "samples": a.rounds * B,
+           "trained_on": results}
+    print(json.dumps({"trained_on": {k: {"held_out_mse_before": v["held_out_mse_before"], "held_out_mse_after": v["held_out_mse_after"]} for k, v in results.items()}}, indent=1))
+    if a.json:
+        json.dump(out, open(a.json, "w"), indent=1)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--side", type=int, default=64, choices=(64, 128), help="128: train the 128x128-input net on frames rendered at 128x128 (see the module's text)")
@@ -200,7 +280,11 @@ def main():
     ap.add_argument("--sampled", action="store_true", help="draw the hands with ht_sample_poses_dev (HT_SAMPLE_ENHANCED, seed --seed) inside the model's joint limits; only the wrists come from the "
                                                             "interpolated ground truths.  64x64 net only")
     ap.add_argument("--spread", type=float, default=0.98, help="with --sampled: the share of every joint range the sampler uses")
+    ap.add_argument("--sensor-noise", default=None, choices=("ivy", "ds4"), help="64x64 net: train one net on clean and one on simulated raw frames of this camera (ht_sensor_simulate_dev, "
+                                                                                 "ht_sensor_filter_dev) and report both on held-out simulated frames (see the module's text).  Off by default")
     a = ap.parse_args()
+    if a.sensor_noise and (a.side != 64 or a.sampled or a.mesh):
+        ap.error("--sensor-noise trains the 64x64-input net on hull renderings of the interpolated poses")
     if a.sampled and a.side != 64:
         ap.error("--sampled trains the 64x64-input net")
     if a.minibatch < 1 or a.batch % a.minibatch:
@@ -209,6 +293,8 @@ def main():
         ap.error("--frame needs --side 128 and a size ht_segment_vr_supported takes")
     if a.side == 128:
         return main128(a)
+    if a.sensor_noise:
+        return main_sensor(a)
     dev = torch.device("cuda:0")
     d = np.load(os.path.join(ROOT, "bench_data", "frames1024.npz"))
     gt = d["gtpose"]; pairs = train_pairs(len(gt))
