@@ -4,6 +4,8 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
+#include <limits.h>
+#include <cmath>
 #include <string>
 #include <vector>
 #include <map>
@@ -400,6 +402,238 @@ extern "C" int ht_debug_train_batch_buffers_sized(ht_ctx *ctx, int side, int n, 
 	return cnn_train_batch_buffers(ctx, ht_form_name(ctx, net, "ht_debug_train_batch_buffers", "ht_debug_train_batch_buffers_sized"), net, n, a3, a6, a8, e9, e7, e6, e3);
 }
 extern "C" int ht_cnn_get_weights_sized(ht_ctx *ctx, int side, float *w, size_t n) { CHECK_READY(ctx); return cnn_get_weights(ctx, ht_net_of(ctx, side), w, n); }
+
+// ---- the gradient as a buffer, and the optimiser steps over it (ht_optim.hip) ----
+// G = (accumulate ? G : 0) + SUM_b g_b(w) of the samples index[0..n) (null: 0, 1, ...) of the pools; the arguments have been checked (cnn_grad_check).  G comes with the
+// first call, the arena grows as it does for a step.
+static int cnn_grad_check(ht_ctx *ctx, const char *fn, const ht_net *net, const void *in, const void *tg, int n_pool, const int *order, int calls, int batch, int accumulate)
+{
+	{ const int r = cnn_train_check(ctx, fn, true, net, in, tg, n_pool, order, calls, batch); if (r) return r; }
+	if (accumulate && !net->opt.G) { ctx->err = std::string(fn) + ": accumulate needs a gradient buffer, which the first call without it makes"; return HT_ERR_STATE; }
+	return HT_OK;
+}
+static int cnn_grad_launch(ht_ctx *ctx, ht_net &net, const float *d_x, const float *d_t, const int *order, int n, int accumulate, float *d_mse, hipStream_t s)
+{
+	if (!net.opt.G) { const int r = dev_alloc(ctx, &net.opt.G, net.dims.count); if (r) return r; }
+	const int cap = (n + 31) & ~31;
+	{ const int r = dev_grow(ctx, &net.train.buf, &net.train.cap, (size_t)cap, ht_train_batch_floats(cap, net.dims) / (size_t)cap + 1); if (r) return r; }
+	int index[HT_TRAIN_MAX_BATCH];
+	for (int b = 0; b < n; b++) index[b] = order ? order[b] : b;
+	ht_launch_train_batch_grad(net.d_weights, net.opt.G, accumulate ? 1 : 0, d_x, d_t, index, n, net.train.buf, net.train.cap, d_mse, s, net.dims);
+	net.train.last = n;
+	HIPCHK(ctx, hipGetLastError());
+	return HT_OK;
+}
+extern "C" int ht_cnn_grad_batch_sized_dev(ht_ctx *ctx, int side, const float *d_inputs, const float *d_targets, int n_pool, const int *order, int batch, int accumulate, float *d_mse, void *stream)
+{
+	CHECK_READY(ctx);
+	ht_net *net = ht_net_of(ctx, side);
+	{ const int r = cnn_grad_check(ctx, "ht_cnn_grad_batch_sized_dev", net, d_inputs, d_targets, n_pool, order, 1, batch, accumulate); if (r) return r; }
+	return cnn_grad_launch(ctx, *net, d_inputs, d_targets, order, batch, accumulate, d_mse, ht_user_stream(ctx, stream));
+}
+extern "C" int ht_cnn_grad_batch_sized(ht_ctx *ctx, int side, const float *inputs, const float *targets, int n, int accumulate, float *mse_out)
+{
+	CHECK_READY(ctx);
+	ht_net *net = ht_net_of(ctx, side);
+	{ const int r = cnn_grad_check(ctx, "ht_cnn_grad_batch_sized", net, inputs, targets, n, nullptr, 1, n, accumulate); if (r) return r; }
+	ht_seg seg[3] = { { (void *)inputs, (size_t)n * net->dims.in * sizeof(float), false }, { (void *)targets, (size_t)n * HT_CNN_OUT * sizeof(float), false }, { mse_out, (size_t)n * sizeof(float), true } };
+	return ht_staged_call(ctx, &ctx->d_train_io, &ctx->train_io_cap, seg, 3, [&](hipStream_t s)
+	                      { return cnn_grad_launch(ctx, *net, (const float *)seg[0].dev, (const float *)seg[1].dev, nullptr, n, accumulate, (float *)seg[2].dev, s); });
+}
+// a float array of the net's size on the device (G, m or v), host <-> device: the length every such call checks, and the upload
+static int opt_array_check(ht_ctx *ctx, const char *fn, const ht_net *net, size_t n)
+{
+	if (!net) return HT_ERR_ARG;
+	if (n != net->dims.count) { ctx->err = std::string(fn) + ": n must be the net's value count (HT_CNNB_COUNT / HT_CNNB128_COUNT)"; return HT_ERR_ARG; }
+	return HT_OK;
+}
+static int opt_array_set(ht_ctx *ctx, const ht_net &net, float **d, const float *host)      // allocates on first need; host null: zeros
+{
+	float *fresh = nullptr;
+	if (!*d) { const int r = dev_alloc(ctx, &fresh, net.dims.count); if (r) return r; }
+	float *p = *d ? *d : fresh;
+	const hipError_t e = host ? hipMemcpy(p, host, net.dims.count * sizeof(float), hipMemcpyHostToDevice) : hipMemset(p, 0, net.dims.count * sizeof(float));
+	if (e != hipSuccess) { if (fresh) drop_alloc(ctx, fresh); ctx->err = std::string("optimiser state upload: ") + hipGetErrorString(e); return HT_ERR_HIP; }
+	*d = p;
+	return HT_OK;
+}
+extern "C" int ht_cnn_grad_get_sized(ht_ctx *ctx, int side, float *g, size_t n)
+{
+	CHECK_READY(ctx);
+	ht_net *net = ht_net_of(ctx, side);
+	if (!net || !g) return HT_ERR_ARG;
+	{ const int r = opt_array_check(ctx, "ht_cnn_grad_get_sized", net, n); if (r) return r; }
+	if (!net->opt.G) { ctx->err = "ht_cnn_grad_get_sized: no gradient buffer yet (ht_cnn_grad_batch_sized, ht_cnn_grad_set_sized)"; return HT_ERR_STATE; }
+	HIPCHK(ctx, ht_sync_all(ctx));
+	HIPCHK(ctx, hipMemcpy(g, net->opt.G, n * sizeof(float), hipMemcpyDeviceToHost));
+	return HT_OK;
+}
+extern "C" int ht_cnn_grad_set_sized(ht_ctx *ctx, int side, const float *g, size_t n)
+{
+	CHECK_READY(ctx);
+	ht_net *net = ht_net_of(ctx, side);
+	if (!net || !g) return HT_ERR_ARG;
+	{ const int r = opt_array_check(ctx, "ht_cnn_grad_set_sized", net, n); if (r) return r; }
+	HIPCHK(ctx, ht_sync_all(ctx));
+	return opt_array_set(ctx, *net, &net->opt.G, g);
+}
+extern "C" int ht_cnn_grad_ptr_sized(ht_ctx *ctx, int side, float **d_g, size_t *n)
+{
+	CHECK_READY(ctx);
+	ht_net *net = ht_net_of(ctx, side);
+	if (!net || !d_g) return HT_ERR_ARG;
+	if (!net->opt.G) { ctx->err = "ht_cnn_grad_ptr_sized: no gradient buffer yet (ht_cnn_grad_batch_sized, ht_cnn_grad_set_sized)"; return HT_ERR_STATE; }
+	*d_g = net->opt.G;
+	if (n) *n = net->dims.count;
+	return HT_OK;
+}
+extern "C" int ht_opt_default(int kind, ht_opt *o)
+{
+	if (!o || kind < HT_OPT_SGD || kind > HT_OPT_ADAM) return HT_ERR_ARG;
+	o->kind = kind; o->lr = 0.001f; o->momentum = 0.9f; o->beta1 = 0.9f; o->beta2 = 0.999f; o->eps = 1e-8f; o->weight_decay = 0.0f; o->decoupled_decay = 0;
+	o->grad_scale = 1.0f; o->clip_norm = 0.0f;
+	return HT_OK;
+}
+// every field of an ht_opt, before anything is allocated or launched; the message names the field
+static int opt_check(ht_ctx *ctx, const char *fn, const ht_opt *o)
+{
+	const char *bad = nullptr;
+	auto unit = [](float x) { return x >= 0.0f && x < 1.0f; };      // false for NaN
+	if (!o) bad = "the options must not be NULL";
+	else if (o->kind < HT_OPT_SGD || o->kind > HT_OPT_ADAM) bad = "kind must be HT_OPT_SGD, _MOMENTUM, _NESTEROV or _ADAM";
+	else if (!(std::isfinite(o->lr) && o->lr >= 0.0f)) bad = "lr must be finite and not negative";
+	else if (!unit(o->momentum)) bad = "momentum must be in [0, 1)";
+	else if (!unit(o->beta1)) bad = "beta1 must be in [0, 1)";
+	else if (!unit(o->beta2)) bad = "beta2 must be in [0, 1)";
+	else if (!std::isfinite(o->eps) || (o->kind == HT_OPT_ADAM && !(o->eps > 0.0f))) bad = "eps must be finite, and positive for HT_OPT_ADAM";
+	else if (!std::isfinite(o->weight_decay)) bad = "weight_decay must be finite";
+	else if (o->decoupled_decay != 0 && o->decoupled_decay != 1) bad = "decoupled_decay must be 0 or 1";
+	else if (o->decoupled_decay && o->kind != HT_OPT_ADAM) bad = "decoupled_decay is HT_OPT_ADAM's; the other kinds take weight_decay coupled";
+	else if (!std::isfinite(o->grad_scale)) bad = "grad_scale must be finite";
+	else if (!(std::isfinite(o->clip_norm) && o->clip_norm >= 0.0f)) bad = "clip_norm must be finite and not negative (0 = off)";
+	if (bad) { ctx->err = std::string(fn) + ": " + bad; return HT_ERR_ARG; }
+	return HT_OK;
+}
+static int opt_net_check(ht_ctx *ctx, const char *fn, const ht_net *net)
+{
+	if (!net) return HT_ERR_ARG;
+	if (!net->have) { ctx->err = std::string(fn) + net->train_missing; return HT_ERR_ARG; }
+	return HT_OK;
+}
+// One step of the optimiser o (checked: opt_check) over all weights of the net from its G: the norm and the factor when clipping, the step, the packed copies
+static int cnn_opt_launch(ht_ctx *ctx, ht_net &net, const ht_opt &o, hipStream_t s)
+{
+	const size_t n = net.dims.count;
+	if (o.kind != HT_OPT_SGD && !net.opt.m) { const int r = opt_array_set(ctx, net, &net.opt.m, nullptr); if (r) return r; }
+	if (o.kind == HT_OPT_ADAM && !net.opt.v) { const int r = opt_array_set(ctx, net, &net.opt.v, nullptr); if (r) return r; }
+	if (!net.opt.stat) { const int r = dev_alloc(ctx, &net.opt.stat, ht_opt_stat_doubles()); if (r) return r; }
+	ht_opt_args a = {};
+	a.lr = o.lr; a.momentum = o.momentum; a.beta1 = o.beta1; a.beta2 = o.beta2; a.eps = o.eps; a.wd = o.weight_decay; a.gs = o.grad_scale;
+	a.omb1 = 1.0f - o.beta1; a.omb2 = 1.0f - o.beta2; a.bc1 = a.bc2 = 1.0f;
+	a.coupled = !o.decoupled_decay && o.weight_decay != 0.0f; a.decoupled = o.decoupled_decay != 0;
+	if (o.kind == HT_OPT_ADAM)
+	{
+		const int t = ++net.opt.t;
+		a.bc1 = (float)(1.0 - pow((double)o.beta1, (double)t)); a.bc2 = (float)(1.0 - pow((double)o.beta2, (double)t));
+	}
+	{
+		const cnnb_layout<float> L = cnnb_layout_of(net.d_weights, net.dims.act2);
+		float *const at[8] = { L.W1, L.B1, L.W2, L.B2, L.W3, L.B3, L.W4, L.B4 };
+		for (int k = 0; k < 8; k++) a.r[k] = (unsigned)(at[k] - net.d_weights);
+	}
+	const bool clip = o.clip_norm > 0.0f;
+	if (clip) ht_launch_opt_norm(net.opt.G, n, o.grad_scale, o.clip_norm, net.opt.stat, s);
+	ht_launch_opt_step(o.kind, net.d_weights, net.opt.G, net.opt.m, net.opt.v, n, clip ? reinterpret_cast<const float *>(net.opt.stat + 1) : nullptr, a, s);
+	ht_launch_opt_pack_w2(cnnb_layout_of(net.d_weights, net.dims.act2).W2, net.d_weights + n, s);
+	ht_launch_pack_w4(net.w.W4, net.d_weights + n + 16384, s);
+	net.opt.clipped = clip; net.opt.steps++;
+	HIPCHK(ctx, hipGetLastError());
+	return HT_OK;
+}
+extern "C" int ht_cnn_opt_step_sized_dev(ht_ctx *ctx, int side, const ht_opt *o, void *stream)
+{
+	CHECK_READY(ctx);
+	ht_net *net = ht_net_of(ctx, side);
+	{ int r = opt_net_check(ctx, "ht_cnn_opt_step_sized_dev", net); if (r || (r = opt_check(ctx, "ht_cnn_opt_step_sized_dev", o))) return r; }
+	if (!net->opt.G) { ctx->err = "ht_cnn_opt_step_sized_dev: no gradient buffer yet (ht_cnn_grad_batch_sized, ht_cnn_grad_set_sized)"; return HT_ERR_STATE; }
+	return cnn_opt_launch(ctx, *net, *o, ht_user_stream(ctx, stream));
+}
+extern "C" int ht_cnn_opt_reset_sized(ht_ctx *ctx, int side)
+{
+	CHECK_READY(ctx);
+	ht_net *net = ht_net_of(ctx, side);
+	if (!net) return HT_ERR_ARG;
+	HIPCHK(ctx, ht_sync_all(ctx));
+	if (net->opt.m) HIPCHK(ctx, hipMemset(net->opt.m, 0, net->dims.count * sizeof(float)));
+	if (net->opt.v) HIPCHK(ctx, hipMemset(net->opt.v, 0, net->dims.count * sizeof(float)));
+	net->opt.t = 0;
+	return HT_OK;
+}
+extern "C" int ht_cnn_opt_state_get_sized(ht_ctx *ctx, int side, float *m, float *v, size_t n, int *t)
+{
+	CHECK_READY(ctx);
+	ht_net *net = ht_net_of(ctx, side);
+	if (!net) return HT_ERR_ARG;
+	if (m || v) { const int r = opt_array_check(ctx, "ht_cnn_opt_state_get_sized", net, n); if (r) return r; }
+	HIPCHK(ctx, ht_sync_all(ctx));
+	float *const host[2] = { m, v }, *const dev[2] = { net->opt.m, net->opt.v };
+	for (int k = 0; k < 2; k++)      // a moment no step has needed yet is all zeros
+		if (host[k]) { if (dev[k]) HIPCHK(ctx, hipMemcpy(host[k], dev[k], n * sizeof(float), hipMemcpyDeviceToHost)); else memset(host[k], 0, n * sizeof(float)); }
+	if (t) *t = net->opt.t;
+	return HT_OK;
+}
+extern "C" int ht_cnn_opt_state_set_sized(ht_ctx *ctx, int side, const float *m, const float *v, size_t n, int t)
+{
+	CHECK_READY(ctx);
+	ht_net *net = ht_net_of(ctx, side);
+	if (!net) return HT_ERR_ARG;
+	if (m || v) { const int r = opt_array_check(ctx, "ht_cnn_opt_state_set_sized", net, n); if (r) return r; }
+	if (t < 0) { ctx->err = "ht_cnn_opt_state_set_sized: t must not be negative"; return HT_ERR_ARG; }
+	HIPCHK(ctx, ht_sync_all(ctx));
+	if (m) { const int r = opt_array_set(ctx, *net, &net->opt.m, m); if (r) return r; }
+	if (v) { const int r = opt_array_set(ctx, *net, &net->opt.v, v); if (r) return r; }
+	net->opt.t = t;
+	return HT_OK;
+}
+extern "C" int ht_cnn_opt_last_sized(ht_ctx *ctx, int side, double *grad_norm, float *clip_factor)
+{
+	CHECK_READY(ctx);
+	ht_net *net = ht_net_of(ctx, side);
+	if (!net) return HT_ERR_ARG;
+	if (!net->opt.steps) { ctx->err = "ht_cnn_opt_last_sized: no optimiser step has run on this net"; return HT_ERR_STATE; }
+	HIPCHK(ctx, ht_sync_all(ctx));
+	double st[2] = { -1.0, 0.0 }; float c = 1.0f;      // a step that did not clip formed no norm: -1 and 1.0f
+	if (net->opt.clipped) { HIPCHK(ctx, hipMemcpy(st, net->opt.stat, sizeof st, hipMemcpyDeviceToHost)); memcpy(&c, &st[1], sizeof c); }
+	if (grad_norm) *grad_norm = st[0];
+	if (clip_factor) *clip_factor = c;
+	return HT_OK;
+}
+// n_steps optimiser steps, each after accum gradient calls of `batch` samples (the first with accumulate = 0): the calls above in that order, nothing else
+extern "C" int ht_cnn_train_opt_sized_dev(ht_ctx *ctx, int side, const float *d_inputs, const float *d_targets, int n_pool, const int *order, int n_steps, int batch, int accum, const ht_opt *o, float *d_mse, void *stream)
+{
+	CHECK_READY(ctx);
+	const char *fn = "ht_cnn_train_opt_sized_dev";
+	ht_net *net = ht_net_of(ctx, side);
+	if (!net) return HT_ERR_ARG;
+	if (accum < 1) { ctx->err = std::string(fn) + ": accum must be at least 1"; return HT_ERR_ARG; }
+	if (n_steps < 0 || (long long)n_steps * accum > INT_MAX / HT_TRAIN_MAX_BATCH) { ctx->err = std::string(fn) + ": n_steps must not be negative, n_steps * accum * batch must fit an int"; return HT_ERR_ARG; }
+	{ int r = cnn_grad_check(ctx, fn, net, d_inputs, d_targets, n_pool, order, n_steps * accum, batch, 0); if (r || (r = opt_check(ctx, fn, o))) return r; }
+	hipStream_t s = ht_user_stream(ctx, stream);
+	size_t k = 0;
+	for (int i = 0; i < n_steps; i++)
+	{
+		for (int j = 0; j < accum; j++, k += (size_t)batch)
+		{
+			int index[HT_TRAIN_MAX_BATCH];
+			for (int b = 0; b < batch; b++) index[b] = order ? order[k + b] : (int)k + b;
+			const int r = cnn_grad_launch(ctx, *net, d_inputs, d_targets, index, batch, j > 0, d_mse ? d_mse + k : nullptr, s);
+			if (r) return r;
+		}
+		const int r = cnn_opt_launch(ctx, *net, *o, s);
+		if (r) return r;
+	}
+	return HT_OK;
+}
 // Test aid: the layer outputs and the errors of the training arena as the latest step left them (layout: ht_launch_train_step, csrc/ht_train.hip)
 extern "C" int ht_debug_train_buffers(ht_ctx *ctx, float *act, size_t n_act, float *err, size_t n_err)
 {

@@ -197,6 +197,9 @@ struct ht_net
 	bool have = false; float *d_weights = nullptr; ht_cnn_weights w = {};
 	float *d_in = nullptr, *d_act1 = nullptr, *d_act2 = nullptr;
 	struct { float *buf = nullptr; int cap = 0, last = 0; } train;
+	// the gradient buffer G [dims.count] of ht_cnn_grad_batch_* (with its first call, or ht_cnn_grad_set_sized), the optimiser's moments m and v (on first need of
+	// the kind that keeps them), the count t of Adam steps, the norm, clip factor and partial sums of the latest step (ht_opt_stat_doubles) and whether that step clipped
+	struct { float *G = nullptr, *m = nullptr, *v = nullptr; double *stat = nullptr; int t = 0, steps = 0; bool clipped = false; } opt;
 };
 void ht_launch_pack_w4(const float *W4, float *W4p, hipStream_t s);      // refreshes the packed copy (after a weight upload, after a training step)
 

@@ -116,6 +116,16 @@ void ht_launch_fc_rowmajor(const float *A, const float *W, const float *bias, fl
 void ht_launch_train_batch_step(float *w, float *W2p, const float *inputs, const float *targets, const int *index, int n, float alpha, float *arena, int cap, float *mse_out, hipStream_t s, const ht_net_dims &d);
 size_t ht_train_batch_floats(int cap, const ht_net_dims &d);
 void ht_train_batch_views(float *arena, int cap, const float *view[7], size_t per[7], const ht_net_dims &d);
+// the same launches up to the weight steps, which become G = (accumulate ? G : 0) + sum_b g_b(w) over G [d.count] in .cnnb order; the weights are read only
+void ht_launch_train_batch_grad(const float *w, float *G, int accumulate, const float *inputs, const float *targets, const int *index, int n, float *arena, int cap, float *mse_out, hipStream_t s, const ht_net_dims &d);
+// ht_optim.hip: the gradient's own kernels, the global norm with the clip factor, the optimiser step (its arithmetic: the head of that file) and conv2's packed copy
+struct ht_opt_args { float lr, momentum, beta1, beta2, omb1, omb2, bc1, bc2, eps, wd, gs; int coupled, decoupled; unsigned r[8]; };
+void ht_launch_opt_fc_wgrad(float *G, float *GB, const float *X, const float *E, int n, int M, int N, int accumulate, hipStream_t s);
+void ht_launch_opt_conv_reduce(const float *pw, int groups, int stride, float *G1, float *GB1, float *G2, float *GB2, int accumulate, hipStream_t s);
+size_t ht_opt_stat_doubles();
+void ht_launch_opt_norm(const float *G, size_t n, float gs, float clip_norm, double *stat, hipStream_t s);
+void ht_launch_opt_step(int kind, float *W, const float *G, float *M, float *V, size_t n, const float *clip, const ht_opt_args &a, hipStream_t s);
+void ht_launch_opt_pack_w2(const float *W2, float *W2p, hipStream_t s);
 // ht_joints.hip (host only): the limits table [nj][HT_JL] of a joint table [nj][HT_JC], its public form (lo / hi [nj][3], an unbounded axis as -inf / +inf; swapped [nj];
 // any may be null), and whether a top-down walk in model order places every body
 void ht_joint_limits(const float *jointc, int nj, float *table);

@@ -343,11 +343,14 @@ template <bool FOLD> static void tb_fc_back(const float *E, const float *W, cons
 	else hipLaunchKernelGGL((k_tb_fc_back<8, FOLD>), g, t, 0, s, E, W, Y, D, n, R, K);
 }
 // One step of the net of input side S on samples index[0..n) of the pools; C2T = threads of a conv2 block, BH / BT / IZB = band height, threads and input channels per block of conv2's backward
-template <int S, int C2T, int BH, int BT, int IZB> static void tb_step(float *w, float *W2p, const float *inputs, const float *targets, const int *index, int n, float alpha, float *arena, int cap, float *mse_out, hipStream_t s)
+// G: null for the step; else the weights are left alone and the three weight launches write G = (accumulate ? G : 0) + sum_b g_b(w) in .cnnb order instead (ht_optim.hip;
+// k_tb_conv_grad at alpha = -1 forms the plain sums, -(-1) * x being x).  Everything before them is the same launch either way.
+template <int S, int C2T, int BH, int BT, int IZB> static void tb_step(float *w, float *W2p, const float *inputs, const float *targets, const int *index, int n, float alpha, float *arena, int cap, float *mse_out, hipStream_t s,
+                                                                       float *G = nullptr, int accumulate = 0)
 {
 	typedef cnn_dims<S> D;
 	const tb_arena A = tb_layout(arena, (size_t)cap, ht_net_dims_of<S>());
-	const cnnb_layout<float> L = cnnb_layout_of(w, (size_t)D::A6);
+	const cnnb_layout<float> L = cnnb_layout_of(w, (size_t)D::A6), LG = G ? cnnb_layout_of(G, (size_t)D::A6) : cnnb_layout<float>{};
 	tb_index ix;
 	for (int b = 0; b < n; b++) ix.v[b] = index[b];
 	for (int b = n; b < HT_TRAIN_MAX_BATCH; b++) ix.v[b] = 0;
@@ -361,12 +364,15 @@ template <int S, int C2T, int BH, int BT, int IZB> static void tb_step(float *w,
 	hipLaunchKernelGGL(k_tb_softmax_loss, dim3(n), dim3(256), 0, s, A.lg, targets, A.idx, A.e9, mse_out ? mse_out : A.sink);
 	// backward with the old weights, then each layer's step
 	tb_fc_back<true>(A.e9, L.W4, A.a8, A.e7, n, 2048, 2304, s);
-	hipLaunchKernelGGL(k_tb_fc_wgrad, dim3(2304 / 128, 2048 / 32), dim3(256), 0, s, L.W4, L.B4, A.a8, A.e9, n, 2048, 2304, alpha);
+	if (G) ht_launch_opt_fc_wgrad(LG.W4, LG.B4, A.a8, A.e9, n, 2048, 2304, accumulate, s);
+	else hipLaunchKernelGGL(k_tb_fc_wgrad, dim3(2304 / 128, 2048 / 32), dim3(256), 0, s, L.W4, L.B4, A.a8, A.e9, n, 2048, 2304, alpha);
 	tb_fc_back<false>(A.e7, L.W3, nullptr, A.e6, n, D::A6, 2048, s);
-	hipLaunchKernelGGL(k_tb_fc_wgrad, dim3(2048 / 128, D::A6 / 32), dim3(256), 0, s, L.W3, L.B3, A.a6, A.e7, n, D::A6, 2048, alpha);
+	if (G) ht_launch_opt_fc_wgrad(LG.W3, LG.B3, A.a6, A.e7, n, D::A6, 2048, accumulate, s);
+	else hipLaunchKernelGGL(k_tb_fc_wgrad, dim3(2048 / 128, D::A6 / 32), dim3(256), 0, s, L.W3, L.B3, A.a6, A.e7, n, D::A6, 2048, alpha);
 	hipLaunchKernelGGL((k_tb_conv2_back<S, BH, BT, IZB>), dim3(16 / IZB, n, (D::P2 + BH - 1) / BH), dim3(BT), 0, s, A.a6, A.r3, A.e6, L.W2, A.e3);
-	hipLaunchKernelGGL(k_tb_conv_grad<S>, dim3(32, groups), dim3(256), 0, s, inputs, A.idx, A.a3, A.r1, A.a6, A.r3, A.e6, A.e3, n, alpha, A.pw);
-	hipLaunchKernelGGL(k_tb_conv_apply, dim3((TB_PW + 255) / 256), dim3(256), 0, s, A.pw, groups, L.W1, L.B1, L.W2, L.B2, W2p);
+	hipLaunchKernelGGL(k_tb_conv_grad<S>, dim3(32, groups), dim3(256), 0, s, inputs, A.idx, A.a3, A.r1, A.a6, A.r3, A.e6, A.e3, n, G ? -1.0f : alpha, A.pw);
+	if (G) ht_launch_opt_conv_reduce(A.pw, groups, TB_PW, LG.W1, LG.B1, LG.W2, LG.B2, accumulate, s);
+	else hipLaunchKernelGGL(k_tb_conv_apply, dim3((TB_PW + 255) / 256), dim3(256), 0, s, A.pw, groups, L.W1, L.B1, L.W2, L.B2, W2p);
 }
 // One step on samples index[0..n) of the pools ([..][side side] inputs); mse_out[n] or null.  The packed copy of the last layer is NOT refreshed here (once per
 // call: ht_api.hip).  d: the dimensions of one of the context's nets (ht_net_of).
@@ -374,4 +380,11 @@ void ht_launch_train_batch_step(float *w, float *W2p, const float *inputs, const
 {
 	if (d.side == 128) tb_step<128, 256, 4, 256, 4>(w, W2p, inputs, targets, index, n, alpha, arena, cap, mse_out, s);
 	else tb_step<64, 192, 15, 256, 1>(w, W2p, inputs, targets, index, n, alpha, arena, cap, mse_out, s);
+}
+// The gradient of the same samples at the weights w, which are only read: G [d.count] in .cnnb order = (accumulate ? G : 0) + sum_b g_b(w)
+void ht_launch_train_batch_grad(const float *w, float *G, int accumulate, const float *inputs, const float *targets, const int *index, int n, float *arena, int cap, float *mse_out, hipStream_t s, const ht_net_dims &d)
+{
+	float *wr = const_cast<float *>(w);      // tb_step with a G writes neither the weights nor W2p
+	if (d.side == 128) tb_step<128, 256, 4, 256, 4>(wr, nullptr, inputs, targets, index, n, 0.0f, arena, cap, mse_out, s, G, accumulate);
+	else tb_step<64, 192, 15, 256, 1>(wr, nullptr, inputs, targets, index, n, 0.0f, arena, cap, mse_out, s, G, accumulate);
 }

@@ -33,6 +33,8 @@ SYMBOLS = (
     "ht_cnn_load_weights", "ht_cnn_eval", "ht_cnn_eval_dev", "ht_cnn_load_weights_sized", "ht_cnn_eval_sized", "ht_cnn_eval_sized_dev", "ht_cnn_train", "ht_cnn_get_weights", "ht_expected_cnn", "ht_expected_cnn_full",
     "ht_expected_cnn_batch", "ht_expected_cnn_dev", "ht_cnn_input_dev", "ht_cnn_train_dev", "ht_cnn_train_batch_dev", "ht_cnn_train_batch", "ht_debug_train_batch_buffers",
     "ht_cnn_train_batch_sized_dev", "ht_cnn_train_batch_sized", "ht_cnn_get_weights_sized", "ht_debug_train_batch_buffers_sized", "ht_cnn_input_sized_dev",
+    "ht_cnn_grad_batch_sized_dev", "ht_cnn_grad_batch_sized", "ht_cnn_grad_get_sized", "ht_cnn_grad_set_sized", "ht_cnn_grad_ptr_sized", "ht_opt_default", "ht_cnn_opt_step_sized_dev",
+    "ht_cnn_opt_reset_sized", "ht_cnn_opt_state_get_sized", "ht_cnn_opt_state_set_sized", "ht_cnn_opt_last_sized", "ht_cnn_train_opt_sized_dev",
     "ht_model_open", "ht_model_close", "ht_model_error", "ht_model_counts", "ht_model_body", "ht_model_body_mesh", "ht_model_body_sdmesh", "ht_model_hitcheck", "ht_model_hitcheck_mesh", "ht_model_render_mesh", "ht_model_scale", "ht_render_mesh_depth", "ht_render_mesh_depth_dev",
     "ht_tracker_reset", "ht_get_state", "ht_set_state", "ht_get_tracker_flags", "ht_set_tracker_flags", "ht_update_sync", "ht_update_dev", "ht_update_frames_sync", "ht_update_frames_dev", "ht_update_direct_sync", "ht_update_direct_dev", "ht_update_cnn_model_sync", "ht_get_cnn_results", "ht_get_cnn_layers", "ht_get_cnn_layers_sized", "ht_frames_overflow", "ht_reserve_points", "ht_point_capacity", "ht_capacity_events", "ht_segment_vr", "ht_segment_vr_dev", "ht_segment_vr_supported", "ht_segment_vr_sized", "ht_segment_vr_sized_dev", "ht_update_frames_sized_sync", "ht_update_frames_sized_dev", "ht_render_depth", "ht_render_depth_dev", "ht_slowfit", "ht_set_points", "ht_fit_rows", "ht_physics_update",
     "ht_stage_prepare", "ht_stage_decode", "ht_stage_fit_error", "ht_stage_cloud_rows", "ht_stage_contacts", "ht_stage_fit",
@@ -72,6 +74,33 @@ class SensorNoise(C.Structure):
             if k not in dict(self._fields_):
                 raise TypeError("ht_sensor_noise has no field %r" % k)
             setattr(n, k, int(v))
+        return n
+
+
+OPT_SGD, OPT_MOMENTUM, OPT_NESTEROV, OPT_ADAM = 0, 1, 2, 3      # HT_OPT_*
+OPT_KINDS = {"sgd": OPT_SGD, "momentum": OPT_MOMENTUM, "nesterov": OPT_NESTEROV, "adam": OPT_ADAM}
+
+
+class Opt(C.Structure):
+    """ht_opt (include/ht_mi355x.h): the optimiser ht_cnn_opt_step_sized_dev applies, field for field.  Opt.default(kind) is ht_opt_default."""
+    _fields_ = [("kind", C.c_int), ("lr", C.c_float), ("momentum", C.c_float), ("beta1", C.c_float), ("beta2", C.c_float), ("eps", C.c_float), ("weight_decay", C.c_float),
+                ("decoupled_decay", C.c_int), ("grad_scale", C.c_float), ("clip_norm", C.c_float)]
+
+    @classmethod
+    def default(cls, kind, **kw):
+        """ht_opt_default for a kind (a number or "sgd" / "momentum" / "nesterov" / "adam"), then the fields given"""
+        o = cls()
+        if load().ht_opt_default(OPT_KINDS.get(kind, -1) if isinstance(kind, str) else int(kind), C.byref(o)) != 0:
+            raise ValueError("unknown optimiser kind %r" % (kind,))
+        return o.but(**kw)
+
+    def but(self, **kw):
+        """a copy with some fields changed"""
+        n = Opt.from_buffer_copy(self)
+        for k, v in kw.items():
+            if k not in dict(self._fields_):
+                raise TypeError("ht_opt has no field %r" % k)
+            setattr(n, k, v)
         return n
 
 
@@ -156,6 +185,18 @@ def load(build_if_missing=True):
     L.ht_cnn_train_batch_sized.argtypes = [vp, C.c_int, fp, fp, C.c_int, C.c_int, C.c_float, fp]
     L.ht_cnn_get_weights_sized.argtypes = [vp, C.c_int, fp, C.c_size_t]
     L.ht_debug_train_batch_buffers_sized.argtypes = [vp, C.c_int, C.c_int] + [fp] * 7
+    L.ht_cnn_grad_batch_sized_dev.argtypes = [vp, C.c_int, vp, vp, C.c_int, ip, C.c_int, C.c_int, vp, vp]
+    L.ht_cnn_grad_batch_sized.argtypes = [vp, C.c_int, fp, fp, C.c_int, C.c_int, fp]
+    L.ht_cnn_grad_get_sized.argtypes = [vp, C.c_int, fp, C.c_size_t]
+    L.ht_cnn_grad_set_sized.argtypes = [vp, C.c_int, fp, C.c_size_t]
+    L.ht_cnn_grad_ptr_sized.argtypes = [vp, C.c_int, C.POINTER(vp), C.POINTER(C.c_size_t)]
+    L.ht_opt_default.argtypes = [C.c_int, C.POINTER(Opt)]
+    L.ht_cnn_opt_step_sized_dev.argtypes = [vp, C.c_int, C.POINTER(Opt), vp]
+    L.ht_cnn_opt_reset_sized.argtypes = [vp, C.c_int]
+    L.ht_cnn_opt_state_get_sized.argtypes = [vp, C.c_int, fp, fp, C.c_size_t, ip]
+    L.ht_cnn_opt_state_set_sized.argtypes = [vp, C.c_int, fp, fp, C.c_size_t, C.c_int]
+    L.ht_cnn_opt_last_sized.argtypes = [vp, C.c_int, C.POINTER(C.c_double), fp]
+    L.ht_cnn_train_opt_sized_dev.argtypes = [vp, C.c_int, vp, vp, C.c_int, ip, C.c_int, C.c_int, C.c_int, C.POINTER(Opt), vp, vp]
     L.ht_cnn_input_sized_dev.argtypes = [vp, C.c_int, vp, vp, C.c_int, vp, vp]
     L.ht_set_points.argtypes = [vp, C.c_int, fp, C.c_int, ip]
     L.ht_slowfit.argtypes = [vp, C.c_int, C.c_int, fp, C.c_int, C.c_int, fp, fp, fp, C.c_int]
@@ -1068,6 +1109,86 @@ class Context:
         else:
             self._chk(self.L.ht_debug_train_batch_buffers_sized(self.h, side, n, *[_f(out[k]) for k, _ in shapes]))
         return out
+
+    # -- the gradient as a buffer and the optimiser steps over it (ht_cnn_grad_* / ht_cnn_opt_*, csrc/ht_optim.hip)
+    def _count(self, side):
+        return CNNB_COUNT if self._side(side) == 64 else CNNB128_COUNT
+
+    def cnn_grad_batch(self, inputs, targets, accumulate=False, side=64):
+        """ht_cnn_grad_batch_sized: G = (accumulate ? G : 0) + SUM_b g_b(w) over the samples (at most 256), the weights untouched; returns their losses."""
+        side = self._side(side)
+        x = _c(inputs, np.float32).reshape(-1, side * side); t = _c(targets, np.float32).reshape(-1, CNN_OUT)
+        mse = np.zeros(x.shape[0], np.float32)
+        self._chk(self.L.ht_cnn_grad_batch_sized(self.h, side, _f(x), _f(t), x.shape[0], int(bool(accumulate)), _f(mse)))
+        return mse
+
+    def cnn_grad_batch_dev(self, d_inputs, d_targets, n_pool, batch, order=None, accumulate=False, d_mse=None, stream=None, side=64):
+        """ht_cnn_grad_batch_sized_dev: the same on device pools, samples order[0:batch] (a host array) or 0..batch-1; asynchronous on `stream`."""
+        side = self._side(side)
+        o = None if order is None else np.ascontiguousarray(order, np.int32).reshape(-1)
+        if o is not None and len(o) < int(batch):
+            raise ValueError("order holds fewer than batch indices")
+        self._chk(self.L.ht_cnn_grad_batch_sized_dev(self.h, side, d_inputs, d_targets, int(n_pool), None if o is None else _i(o), int(batch), int(bool(accumulate)), d_mse, stream))
+
+    def cnn_grad_get(self, side=64):
+        """ht_cnn_grad_get_sized: G in .cnnb order"""
+        g = np.empty(self._count(side), np.float32)
+        self._chk(self.L.ht_cnn_grad_get_sized(self.h, int(side), _f(g), g.size))
+        return g
+
+    def cnn_grad_set(self, g, side=64):
+        """ht_cnn_grad_set_sized"""
+        g = _c(g, np.float32).reshape(-1)
+        side = self._side(side)
+        self._chk(self.L.ht_cnn_grad_set_sized(self.h, side, _f(g), g.size))
+
+    def cnn_grad_ptr(self, side=64):
+        """ht_cnn_grad_ptr_sized: (device address of G, its length)"""
+        p = C.c_void_p(); n = C.c_size_t()
+        side = self._side(side)
+        self._chk(self.L.ht_cnn_grad_ptr_sized(self.h, side, C.byref(p), C.byref(n)))
+        return p.value, n.value
+
+    def cnn_opt_step(self, opt, stream=None, side=64):
+        """ht_cnn_opt_step_sized_dev: one step of the optimiser `opt` (an Opt) over all weights of the net from its G; asynchronous on `stream`."""
+        side = self._side(side)
+        self._chk(self.L.ht_cnn_opt_step_sized_dev(self.h, side, C.byref(opt), stream))
+
+    def cnn_opt_reset(self, side=64):
+        """ht_cnn_opt_reset_sized: m = v = 0, t = 0"""
+        side = self._side(side)
+        self._chk(self.L.ht_cnn_opt_reset_sized(self.h, side))
+
+    def cnn_opt_state(self, side=64):
+        """ht_cnn_opt_state_get_sized: (m, v, t); a moment no step has needed yet is zeros"""
+        n = self._count(side)
+        m = np.empty(n, np.float32); v = np.empty(n, np.float32); t = C.c_int()
+        self._chk(self.L.ht_cnn_opt_state_get_sized(self.h, int(side), _f(m), _f(v), n, C.byref(t)))
+        return m, v, t.value
+
+    def cnn_opt_set_state(self, m=None, v=None, t=0, side=64):
+        """ht_cnn_opt_state_set_sized: m and / or v (None: left as it is) and t"""
+        side = self._side(side)
+        m = None if m is None else _c(m, np.float32).reshape(-1); v = None if v is None else _c(v, np.float32).reshape(-1)
+        self._chk(self.L.ht_cnn_opt_state_set_sized(self.h, side, None if m is None else _f(m), None if v is None else _f(v), self._count(side), int(t)))
+
+    def cnn_opt_last(self, side=64):
+        """ht_cnn_opt_last_sized: (gradient norm, clip factor) of the latest step; (-1, 1) when it did not clip"""
+        nrm = C.c_double(); c = C.c_float()
+        side = self._side(side)
+        self._chk(self.L.ht_cnn_opt_last_sized(self.h, side, C.byref(nrm), C.byref(c)))
+        return nrm.value, np.float32(c.value)
+
+    def cnn_train_opt_dev(self, d_inputs, d_targets, n_pool, batch, opt, accum=1, order=None, n_steps=None, d_mse=None, stream=None, side=64):
+        """ht_cnn_train_opt_sized_dev: n_steps optimiser steps, each after `accum` gradient calls of `batch` samples; order holds n_steps * accum * batch
+        indices (a host array, checked before anything runs).  Exactly that sequence of cnn_grad_batch_dev and cnn_opt_step calls."""
+        side = self._side(side)
+        o = None if order is None else np.ascontiguousarray(order, np.int32).reshape(-1)
+        batch = int(batch); accum = int(accum); per = max(batch, 1) * max(accum, 1)
+        n = ((len(o) if o is not None else int(n_pool)) // per) if n_steps is None else int(n_steps)
+        if o is not None and len(o) < n * per:
+            raise ValueError("order holds fewer than n_steps * accum * batch indices")
+        self._chk(self.L.ht_cnn_train_opt_sized_dev(self.h, side, d_inputs, d_targets, int(n_pool), None if o is None else _i(o), n, batch, accum, C.byref(opt), d_mse, stream))
 
     # -- training samples on the device
     def expected_cnn_batch(self, poses, cams, segment_frame=False, side=64):

@@ -305,6 +305,12 @@ inline std::vector<float2> ImageFeaturePoints(const std::vector<Pose> &pose, con
 	std::vector<float2> u; detail::keypoints_on(detail::live_ctx(), pose, modelfeaturepoints, false, cam, nullptr, 0, 0, 0.0f, 0.0f, nullptr, &u, nullptr); return u;
 }
 
+// Addition: the optimiser CNN::Step and CNN::TrainOpt apply: an ht_opt with ht_opt_default's values for its kind (HT_OPT_SGD, _MOMENTUM, _NESTEROV, _ADAM); set the fields on .opt
+struct Optimizer
+{
+	ht_opt opt;
+	explicit Optimizer(int kind = HT_OPT_SGD) { if (ht_opt_default(kind, &opt) != HT_OK) throw std::runtime_error("Optimizer: unknown kind"); }
+};
 class CNN;
 CNN PoseInitializerCNN(std::string filename, int device);
 class CNN                                                                                    // third_party/cnn.h:100-605 (Eval / Train / loadb / saveb)
@@ -350,6 +356,24 @@ public:
 	{
 		if (batch < 1 || order.size() % (size_t)batch) throw std::runtime_error("CNN::TrainBatch expects a positive batch that divides order.size()");
 		check(ctx_, ht_cnn_train_batch_dev(ctx_, d_inputs, d_targets, n_pool, order.data(), (int)(order.size() / (size_t)batch), batch, alpha, d_mse, stream));
+	}
+	// Addition: the mini-batch gradient as a buffer and optimiser steps over it (ht_cnn_grad_batch_sized, ht_cnn_opt_step_sized_dev, ht_cnn_train_opt_sized_dev at
+	// side 64; their contract is in ht_mi355x.h).  GradBatch: G = (accumulate ? G : 0) + SUM_b g_b(w) over up to HT_TRAIN_MAX_BATCH host samples x [n][4096],
+	// expected [n][2304], the weights untouched; returns the samples' losses.  Step: one step of the optimiser over all weights from G.  TrainOpt: on device pools,
+	// order.size() / (accum * batch) steps, each after `accum` gradient calls of `batch` samples -- exactly that sequence of the two calls.
+	std::vector<float> GradBatch(const std::vector<float> &x, const std::vector<float> &expected, bool accumulate = false)
+	{
+		const size_t n = x.size() / HT_CNN_IN;
+		if (!n || x.size() != n * HT_CNN_IN || expected.size() != n * HT_CNN_OUT) throw std::runtime_error("CNN::GradBatch expects n x 64*64 inputs and n x 2304 labels");
+		std::vector<float> mse(n);
+		check(ctx_, ht_cnn_grad_batch_sized(ctx_, 64, x.data(), expected.data(), (int)n, accumulate ? 1 : 0, mse.data()));
+		return mse;
+	}
+	void Step(const Optimizer &o, void *stream = nullptr) { check(ctx_, ht_cnn_opt_step_sized_dev(ctx_, 64, &o.opt, stream)); }
+	void TrainOpt(const float *d_inputs, const float *d_targets, int n_pool, const std::vector<int> &order, int batch, int accum, const Optimizer &o, float *d_mse = nullptr, void *stream = nullptr)
+	{
+		if (batch < 1 || accum < 1 || order.size() % ((size_t)batch * (size_t)accum)) throw std::runtime_error("CNN::TrainOpt expects positive batch and accum whose product divides order.size()");
+		check(ctx_, ht_cnn_train_opt_sized_dev(ctx_, 64, d_inputs, d_targets, n_pool, order.data(), (int)(order.size() / ((size_t)batch * (size_t)accum)), batch, accum, &o.opt, d_mse, stream));
 	}
 	void saveb(std::ostream &s)                                                              // cnn.h:591
 	{

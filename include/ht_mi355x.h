@@ -303,6 +303,71 @@ int ht_cnn_get_weights_sized(ht_ctx *ctx, int side, float *w, size_t n);
 int ht_debug_train_batch_buffers_sized(ht_ctx *ctx, int side, int n, float *a3, float *a6, float *a8, float *e9, float *e7, float *e6, float *e3);
 int ht_cnn_input_sized_dev(ht_ctx *ctx, int side, const uint16_t *d_tiles, const float *d_cams, int B, float *d_cnn_in, void *stream);
 
+/* ---- the mini-batch gradient as a buffer, and optimiser steps over it (csrc/ht_optim.hip) --------------------------
+ * The calls above fuse w' = w - alpha * SUM_b g_b(w) into the kernels that form the sums.  These write the sums out and step from them, for either net
+ * (side 64 or 128, anything else HT_ERR_ARG), so that a caller can accumulate over more than HT_TRAIN_MAX_BATCH samples, clip, reduce G over ranks, or
+ * step with momentum or Adam.  The calls above, their launches and their bits are unchanged.
+ * ht_cnn_grad_batch_sized_dev  G = (accumulate ? G : 0) + SUM_b g_b(w) over samples order[0..batch) of the pools (order NULL: samples 0..batch-1), g_b as above.
+ *                          The weights are NOT touched.  G holds one float per weight in .cnnb order (the order CNN::saveb writes the weights in), one buffer per
+ *                          net, owned by the context and allocated by the first call.  1 <= batch <= HT_TRAIN_MAX_BATCH; the checks of
+ *                          ht_cnn_train_batch_sized_dev run before anything grows or launches.  d_mse [batch] optional.  Fixed summation orders, no
+ *                          floating-point atomics; accumulate != 0 adds the fresh sums to G with one float addition per element.  HT_ERR_STATE for
+ *                          accumulate before a buffer exists.  Asynchronous on `stream`.  The forward pass, the soft-max and the backward-data launches are
+ *                          those of ht_cnn_train_batch_sized_dev, so ht_debug_train_batch_buffers_sized reads this call's per-sample tensors too.
+ * ht_cnn_grad_batch_sized  the same on host arrays inputs [n][side*side], targets [n][2304], mse_out [n] (optional), n <= HT_TRAIN_MAX_BATCH, one gradient call.
+ * ht_cnn_grad_get_sized / _set_sized  G to / from a host array, n = HT_CNNB_COUNT or HT_CNNB128_COUNT (HT_ERR_ARG otherwise); both wait for the work in flight.
+ *                          set allocates the buffer if there is none; get without one is HT_ERR_STATE.
+ * ht_cnn_grad_ptr_sized    the device buffer itself and its length, for a caller's own reduction (in stream order with the calls around it); HT_ERR_STATE
+ *                          before a buffer exists.
+ *
+ * ht_opt / ht_opt_default  the optimiser a step applies.  ht_opt_default (host only) fills kind, lr 0.001, momentum 0.9, beta1 0.9, beta2 0.999, eps 1e-8,
+ *                          weight_decay 0, decoupled_decay 0, grad_scale 1, clip_norm 0 (= off); HT_ERR_ARG for an unknown kind or a NULL o.
+ * ht_cnn_opt_step_sized_dev  one step over all weights of the net from its G.  fp32, one IEEE operation per written operation, in this order (gs = grad_scale,
+ *                          c = the clip factor):
+ *                              g = (G[i] * gs) * c
+ *                            Decay applies to W1 W2 W3 W4 only, never to B1..B4.
+ *                            Coupled decay (decoupled_decay = 0, weight_decay != 0), on the W ranges:   g = g + weight_decay * w
+ *                            SGD        w' = w - lr * g
+ *                            MOMENTUM   m' = momentum * m + g,   w' = w - lr * m'
+ *                            NESTEROV   the same m',             w' = w - lr * (g + momentum * m')
+ *                            ADAM       t' = t + 1
+ *                                       m' = beta1 * m + omb1 * g
+ *                                       v' = beta2 * v + (omb2 * g) * g
+ *                                       u = (m' / bc1) / (sqrtf(v' / bc2) + eps)
+ *                                       with decoupled_decay, on the W ranges:   u = u + weight_decay * w
+ *                                       w' = w - lr * u
+ *                                       omb1 = 1.0f - beta1, omb2 = 1.0f - beta2 in float; bc1 = (float)(1.0 - pow((double)beta1, t')), likewise bc2.
+ *                            Clip       norm = sqrt(SUM_i ((double)G[i] * (double)gs)^2), float64, in a fixed order;
+ *                                       c = norm > clip_norm ? (float)((double)clip_norm / norm) : 1.0f.  clip_norm = 0: c = 1.0f, no norm is formed.
+ *                          m and v start as zeros and are allocated on first need of a kind that keeps them; t counts the net's Adam steps (the other kinds
+ *                          leave it).  Changing kind between steps is allowed and uses whatever state is there.  The step ends with the refresh of the
+ *                          inference kernels' packed copies, so ht_cnn_get_weights_sized and ht_cnn_eval_* see the stepped weights.  Asynchronous on `stream`
+ *                          (the factor reaches the step on the device).  o is checked completely before anything launches: kind; every field finite;
+ *                          lr >= 0; momentum, beta1, beta2 in [0, 1); eps > 0 for Adam; clip_norm >= 0; decoupled_decay 0 or 1, and 1 only with Adam.  A
+ *                          violation is HT_ERR_ARG with the field's name in ht_last_error and leaves the context as it was.  HT_ERR_STATE without a gradient buffer.
+ * ht_cnn_opt_reset_sized   m = v = 0, t = 0.
+ * ht_cnn_opt_state_get_sized / _set_sized  m, v [n] and t to / from the host; any of m, v, t (get) or m, v (set) may be NULL; n as for G.  A moment that no
+ *                          step has needed yet reads as zeros; set allocates what it is given.  t >= 0.
+ * ht_cnn_opt_last_sized    the latest step's norm and clip factor; waits for it.  A step that did not clip formed no norm: -1 and 1.0f.  HT_ERR_STATE before a step.
+ * ht_cnn_train_opt_sized_dev  n_steps optimiser steps, each preceded by accum >= 1 gradient calls of `batch` samples, the first with accumulate = 0.  order holds
+ *                          n_steps * accum * batch indices, all checked before anything is launched (NULL: samples 0, 1, ...; that many must exist).
+ *                          d_mse [n_steps * accum * batch] optional.  It is exactly that sequence of ht_cnn_grad_batch_sized_dev and
+ *                          ht_cnn_opt_step_sized_dev calls: the same launches, the same bits. */
+enum { HT_OPT_SGD = 0, HT_OPT_MOMENTUM = 1, HT_OPT_NESTEROV = 2, HT_OPT_ADAM = 3 };
+typedef struct ht_opt { int kind; float lr, momentum, beta1, beta2, eps, weight_decay; int decoupled_decay; float grad_scale; float clip_norm; } ht_opt;
+int ht_cnn_grad_batch_sized_dev(ht_ctx *ctx, int side, const float *d_inputs, const float *d_targets, int n_pool, const int *order, int batch, int accumulate, float *d_mse, void *stream);
+int ht_cnn_grad_batch_sized(ht_ctx *ctx, int side, const float *inputs, const float *targets, int n, int accumulate, float *mse_out);
+int ht_cnn_grad_get_sized(ht_ctx *ctx, int side, float *g, size_t n);
+int ht_cnn_grad_set_sized(ht_ctx *ctx, int side, const float *g, size_t n);
+int ht_cnn_grad_ptr_sized(ht_ctx *ctx, int side, float **d_g, size_t *n);
+int ht_opt_default(int kind, ht_opt *o);
+int ht_cnn_opt_step_sized_dev(ht_ctx *ctx, int side, const ht_opt *o, void *stream);
+int ht_cnn_opt_reset_sized(ht_ctx *ctx, int side);
+int ht_cnn_opt_state_get_sized(ht_ctx *ctx, int side, float *m, float *v, size_t n, int *t);
+int ht_cnn_opt_state_set_sized(ht_ctx *ctx, int side, const float *m, const float *v, size_t n, int t);
+int ht_cnn_opt_last_sized(ht_ctx *ctx, int side, double *grad_norm, float *clip_factor);
+int ht_cnn_train_opt_sized_dev(ht_ctx *ctx, int side, const float *d_inputs, const float *d_targets, int n_pool, const int *order, int n_steps, int batch, int accum, const ht_opt *o, float *d_mse, void *stream);
+
 /* ---- a hand model that is not being tracked (host only, no device needed) ---------------------------------------------------
  * The reference's applications keep a second PhysModel to pose, draw and ray-cast their synthetic input
  * (`PhysModel fakehand = LoadHandModel();` synthetic-tracker.cpp:94, FakeDepth :69-76).

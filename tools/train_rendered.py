@@ -6,7 +6,9 @@
   4. ht_cnn_input_dev (handtrack.h:700);
   5. ht_expected_cnn_dev(..., HT_LABELS_SEGMENT_FRAME): train-cnn's compress + GatherHandExpectedCNN;
   6. ht_cnn_train_dev over a seeded permutation of the round's samples (batch-1 SGD, lr 0.001, CNN::Train); with --minibatch N the permutation is cut
-     into steps of N samples for ht_cnn_train_batch_dev (w' = w - lr * SUM_b g_b(w): a sum, so --lr keeps its per-sample meaning).
+     into steps of N samples for ht_cnn_train_batch_dev (w' = w - lr * SUM_b g_b(w): a sum, so --lr keeps its per-sample meaning).  --optimizer / --weight-decay /
+     --clip-norm / --accum (with --minibatch > 1) step through ht_cnn_train_opt_sized_dev instead: sgd at grad_scale 1 (the same --lr), momentum / nesterov / adam on the
+     mean gradient (grad_scale = 1 / (minibatch * accum)); the defaults are the fused step, unchanged.
 
 Held out: the frames tools/train_synthetic.py holds out (every 16th bench frame) and every interpolation that touches one of them.  Reported: the held-out
 MSE of the net on those 64 bench tiles, and on how many of them the unit of work takes the CNN-driven pose (the measure of tests/test_gpu_trained_net.py).
@@ -109,7 +111,10 @@ def main128(a):
     ev = [torch.cuda.Event(enable_timing=True) for _ in range(6)]
 
     def train(order, d_mse=None):
-        ctx.cnn_train_batch_dev(x.data_ptr(), lab.data_ptr(), B, a.minibatch, order=order, alpha=a.lr, d_mse=d_mse, stream=s.cuda_stream, side=128)
+        if a.opt is not None:
+            ctx.cnn_train_opt_dev(x.data_ptr(), lab.data_ptr(), B, a.minibatch, a.opt, accum=a.accum, order=order, d_mse=d_mse, stream=s.cuda_stream, side=128)
+        else:
+            ctx.cnn_train_batch_dev(x.data_ptr(), lab.data_ptr(), B, a.minibatch, order=order, alpha=a.lr, d_mse=d_mse, stream=s.cuda_stream, side=128)
 
     def round_(poses, order, timed=False):
         with torch.cuda.stream(s):
@@ -183,7 +188,7 @@ def main128(a):
         "the 26-bone hand rendered at 128x128 (render, input, HT_LABELS_SIDE128 labels"
     out = {"what": "tools/train_rendered.py --side 128%s: %d rounds of %d frames of %s, steps of %d lr %g over a "
                    "seeded permutation), seed 0x%X" % (" --frame %dx%d" % (fw, fh) if seg else "", a.rounds, B, what, a.minibatch, a.lr, a.seed),
-           "side": 128, "rounds": a.rounds, "batch": B, "minibatch": a.minibatch, "lr": a.lr, "samples": a.rounds * B, "seconds": seconds,
+           "side": 128, "rounds": a.rounds, "batch": B, "minibatch": a.minibatch, "lr": a.lr, "optimizer": None if a.opt is None else {k: getattr(a.opt, k) for k, _ in a.opt._fields_}, "accum": a.accum, "samples": a.rounds * B, "seconds": seconds,
            "stage_ms_per_round": {"render": stage_ms[0], "segment": stage_ms[1], "cnn_input": stage_ms[2], "labels": stage_ms[3], "train": stage_ms[4]},
            "closed_loop_samples_per_s": loop_sps, "bare_train_samples_per_s": bare_sps,
            "held_out": {"frames": int(len(fr)), "mse_before": mse0, "mse_after": mse1}, "curve": curve}
@@ -258,7 +263,7 @@ def main_sensor(a):
                    "ht_sensor_filter_dev, segment, input, segment-frame labels, SGD in steps of %d lr %g over a seeded permutation), seed 0x%X; held-out MSE on %d held-out ground "
                    "truths rendered clean and simulated" % (a.sensor_noise, a.rounds, B, a.minibatch, a.lr, a.seed, len(fr)),
            "note": "noise figures: ht_sensor_noise_default, reasoned from data sheets, never measured against a camera; recorded figures, no bar",
-           "kind": a.sensor_noise, "noise": {k: getattr(noise, k) for k, _ in noise._fields_}, "rounds": a.rounds, "batch": B, "minibatch": a.minibatch, "lr": a.lr, "samples": a.rounds * B,
+           "kind": a.sensor_noise, "noise": {k: getattr(noise, k) for k, _ in noise._fields_}, "rounds": a.rounds, "batch": B, "minibatch": a.minibatch, "lr": a.lr, "optimizer": None if a.opt is None else {k: getattr(a.opt, k) for k, _ in a.opt._fields_}, "accum": a.accum, "samples": a.rounds * B,
            "trained_on": results}
     print(json.dumps({"trained_on": {k: {"held_out_mse_before": v["held_out_mse_before"], "held_out_mse_after": v["held_out_mse_after"]} for k, v in results.items()}}, indent=1))
     if a.json:
@@ -273,6 +278,12 @@ def main():
     ap.add_argument("--seed", type=int, default=SEED)
     ap.add_argument("--minibatch", type=int, default=1, help="samples per SGD step: 1 = ht_cnn_train_dev (CNN::Train sample by sample), N > 1 = ht_cnn_train_batch_dev on steps of N of the round's permutation")
     ap.add_argument("--lr", type=float, default=0.001, help="alpha of every step; a mini-batch step subtracts lr times the SUM of its samples' gradients")
+    ap.add_argument("--optimizer", default="sgd", choices=("sgd", "momentum", "nesterov", "adam"), help="with --minibatch > 1: the optimiser of every step (ht_cnn_train_opt_sized_dev).  sgd without "
+                    "--weight-decay, --clip-norm or --accum is the fused step above, unchanged.  sgd keeps --lr's per-sample meaning (grad_scale 1); the other kinds step on the MEAN "
+                    "gradient, grad_scale = 1 / (minibatch * accum), with ht_opt_default's momentum and betas")
+    ap.add_argument("--weight-decay", type=float, default=0.0, help="coupled weight decay on W1..W4 (decoupled for adam)")
+    ap.add_argument("--clip-norm", type=float, default=0.0, help="clip the scaled gradient to this global norm (0 = off)")
+    ap.add_argument("--accum", type=int, default=1, help="gradient calls of --minibatch samples per optimiser step")
     ap.add_argument("--json", default=None)
     ap.add_argument("--rate-steps", type=int, default=2048)
     ap.add_argument("--frame", default=None, type=lambda v: tuple(int(x) for x in v.lower().split("x")), help="with --side 128: render full-size frames of this size (640x480) and segment them to the 128x128 tile")
@@ -289,6 +300,12 @@ def main():
         ap.error("--sampled trains the 64x64-input net")
     if a.minibatch < 1 or a.batch % a.minibatch:
         ap.error("--minibatch must divide --batch")
+    a.opt = None      # the optimiser of the steps, or None for the fused SGD step
+    if a.optimizer != "sgd" or a.weight_decay or a.clip_norm or a.accum != 1:
+        if a.minibatch < 2 or a.accum < 1 or a.batch % (a.minibatch * a.accum) or a.sensor_noise:
+            ap.error("--optimizer, --weight-decay, --clip-norm and --accum need --minibatch > 1 with minibatch * accum dividing --batch, and no --sensor-noise")
+        a.opt = native.Opt.default(a.optimizer, lr=a.lr, weight_decay=a.weight_decay, clip_norm=a.clip_norm, decoupled_decay=int(a.optimizer == "adam"),
+                                   grad_scale=1.0 if a.optimizer == "sgd" else 1.0 / (a.minibatch * a.accum))
     if a.frame is not None and (a.side != 128 or len(a.frame) != 2 or not native.segment_vr_supported(a.frame[0], a.frame[1], 128)):
         ap.error("--frame needs --side 128 and a size ht_segment_vr_supported takes")
     if a.side == 128:
@@ -311,7 +328,9 @@ def main():
     L = ctx.L
 
     def train(order, d_mse=None):
-        if a.minibatch == 1:
+        if a.opt is not None:
+            ctx.cnn_train_opt_dev(x.data_ptr(), lab.data_ptr(), B, a.minibatch, a.opt, accum=a.accum, order=order, d_mse=d_mse, stream=s.cuda_stream)
+        elif a.minibatch == 1:
             ctx.cnn_train_dev(x.data_ptr(), lab.data_ptr(), B, order=order, alpha=a.lr, d_mse=d_mse, stream=s.cuda_stream)
         else:
             ctx.cnn_train_batch_dev(x.data_ptr(), lab.data_ptr(), B, a.minibatch, order=order, alpha=a.lr, d_mse=d_mse, stream=s.cuda_stream)
@@ -415,7 +434,7 @@ def main():
                    "SGD in steps of %d lr %g over a seeded permutation), seed 0x%X" % (" --sampled" if a.sampled else "", a.rounds, B,
                                                                                         "ht_sample_poses_dev HT_SAMPLE_ENHANCED spread %g at the interpolated wrists, " % a.spread if a.sampled else "", a.minibatch, a.lr, a.seed),
            "pose_source": "sampled" if a.sampled else "interpolated",
-           "rounds": a.rounds, "batch": B, "minibatch": a.minibatch, "lr": a.lr, "samples": a.rounds * B, "seconds": seconds,
+           "rounds": a.rounds, "batch": B, "minibatch": a.minibatch, "lr": a.lr, "optimizer": None if a.opt is None else {k: getattr(a.opt, k) for k, _ in a.opt._fields_}, "accum": a.accum, "samples": a.rounds * B, "seconds": seconds,
            "stage_ms_per_round": {"render": stage_ms[0], "segment": stage_ms[1], "cnn_input": stage_ms[2], "labels": stage_ms[3], "train": stage_ms[4]},
            "kernels": kern, "closed_loop_samples_per_s": loop_sps, "bare_train_steps_per_s": bare_sps,      # samples/s of the training call alone on the resident pool "loop_over_bare": loop_sps / bare_sps,
            "held_out": {"frames": 64, "mse_before": mse0, "mse_after": mse1, "cnn_pose_frames_before": acc0, "cnn_pose_frames_after": acc1,
