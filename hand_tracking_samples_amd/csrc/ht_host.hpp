@@ -123,6 +123,9 @@ struct ht_ctx
 	// call (dev_grow).  ht_update_two_hands_*: its info [B/2][2][8] when the caller wants none, and the flags 0, 1, 0, 1, ... [B] its pose mirrors take (made once)
 	char *d_split = nullptr; size_t split_cap = 0; uint16_t *d_split_labels = nullptr; size_t split_labels_cap = 0;
 	int32_t *d_two_info = nullptr; unsigned char *d_two_flags = nullptr;
+	// the model split (ht_split_model.hip): the blob split's component counts of a MERGED call whose caller wants none (ht_update_two_hands_model_*: and behind them, from
+	// max_batch / 2, the frames' sources), grown to the largest call (dev_grow)
+	int32_t *d_model_ncomp = nullptr; size_t model_ncomp_cap = 0;
 	// tracking accuracy (ht_quality.hip): the offsets of HT_KP_FEATURE8 [8][3] (handmodelfeaturepoints, handtrack.h:77-81; ht_scale multiplies them as it does the
 	// centres of mass -- HT_KP_SKELETON is read off h_jointc / h_bodyc when asked for); the host forms' staging (dev_grow); ht_pose_depth_residual's render poses
 	// [B][nb][7] and rendered frames [B][h][w], grown to the largest call with one synchronising re-allocation before anything is enqueued (quality_reserve)
@@ -190,7 +193,7 @@ static inline int ht_sync_check(ht_ctx *ctx, hipStream_t s)
 struct ht_seg { void *host; size_t bytes; bool out; char *dev; };
 template <class F> static inline int ht_staged_call(ht_ctx *ctx, char **buf, size_t *cap, ht_seg *seg, int n, F call)
 {
-	size_t off[8], end = 0;      // n <= 8
+	size_t off[12], end = 0;      // n <= 12
 	for (int i = 0; i < n; i++) { off[i] = (end + 255) & ~(size_t)255; if (seg[i].host) end = off[i] + seg[i].bytes; }
 	{ const int r = dev_grow(ctx, buf, cap, end); if (r) return r; }
 	for (int i = 0; i < n; i++) seg[i].dev = seg[i].host ? *buf + off[i] : nullptr;

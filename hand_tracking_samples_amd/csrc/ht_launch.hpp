@@ -146,3 +146,9 @@ int ht_split_check(ht_ctx *ctx, const char *fn, int w, int h, int range_lo, int 
 void ht_launch_split_label(const uint16_t *depth, int w, int h, int B, unsigned lo, unsigned hi, unsigned max_step, int min_pixels, int flags, int32_t *info, int32_t *ncomp, uint16_t *labels, hipStream_t s);
 void ht_launch_split_write(const uint16_t *in, const uint16_t *labels, const int32_t *info, int w, int h, int B, unsigned far, int flags, uint16_t *out, hipStream_t s);
 void ht_launch_split_cams(const float *in, int w, int B, int flags, float *out, hipStream_t s);
+// ht_split_model.hip: the cells of frames go to the nearer of two tracked models (k_split_model; in MERGED mode behind k_split_label, whose counts go to ncomp, never null
+// then): info, labels [B][h/4][w/4] (never null), and optionally source [B] and dist [B][h/4][w/4][2].  Hand k of frame f's prior is at poses + ((2 f + k) nb + b) pose_stride
+// floats; left_canonical: the left prior is in canonical space already.  ht_split_model_check: what every model entry point refuses on top of ht_split_check
+int ht_split_model_check(ht_ctx *ctx, const char *fn, float max_dist, int mode, int flags);
+void ht_launch_split_model(ht_ctx *ctx, const uint16_t *depth, const float *cams, const float *poses, int pose_stride, int left_canonical, int w, int h, int B, unsigned lo, unsigned hi, unsigned max_step,
+                           int min_pixels, float max_dist, int mode, int flags, int32_t *info, int32_t *ncomp, int32_t *source, float *dist, uint16_t *labels, hipStream_t s);

@@ -779,14 +779,17 @@ extern "C" int ht_update_hands_sync(ht_ctx *ctx, int side, const uint16_t *depth
 // ---- two hands in one frame (an addition) ------------------------------------------------------------------------------------------------
 // B frames become 2B hand frames: the split (ht_split.hip) writes frame i's right hand into slot 2i of the hands staging above and its left hand, mirrored, into slot
 // 2i + 1, with their cameras; ht_update_frames_sized_dev runs on the staging; the odd slots' poses are mirrored back.  Slot state stays canonical.
-struct two_hands_args { uint16_t lo, hi, step, far; int min_pixels, flags; };
+// model_mode: -1 the blob split; HT_SPLIT_MODEL_ALWAYS / _MERGED: the cells go to the nearer tracked model (ht_split_model.hip), priors the start poses
+// where given, else the slots' own hand-model state (the left one canonical already)
+struct two_hands_args { uint16_t lo, hi, step, far; int min_pixels, flags; float max_dist; int model_mode; };
 static int two_hands_check(ht_ctx *ctx, int side, int w, int h, const two_hands_args &a, int B)
 {
 	if (B < 1 || 2 * (long long)B > ctx->B) { ctx->err = "ht_update_two_hands: two slots per frame: 2 * B exceeds the capacity given to ht_create"; return HT_ERR_ARG; }
 	{ const int r = frames_sized_args_ok(ctx, side, w, h); if (r) return r; }
+	if (a.model_mode >= 0) { const int r = ht_split_model_check(ctx, "ht_update_two_hands_model", a.max_dist, a.model_mode, a.flags); if (r) return r; }
 	return ht_split_check(ctx, "ht_update_two_hands", w, h, a.lo, a.hi, a.min_pixels, a.far, a.flags);
 }
-static int two_hands_reserve(ht_ctx *ctx, int w, int h)
+static int two_hands_reserve(ht_ctx *ctx, int w, int h, bool model)
 {
 	int r = hands_reserve(ctx, (size_t)w * h);
 	if (r) return r;
@@ -799,16 +802,23 @@ static int two_hands_reserve(ht_ctx *ctx, int w, int h)
 		HIPCHK(ctx, hipMemcpy(f, pat.data(), pat.size(), hipMemcpyHostToDevice));
 		ctx->d_two_flags = f;
 	}
+	if (model && (size_t)ctx->B > ctx->model_ncomp_cap)      // the blob split's counts [B / 2] and, behind them, the frames' sources [B / 2]
+	{
+		HIPCHK(ctx, ht_sync_all(ctx));
+		if ((r = dev_grow(ctx, &ctx->d_model_ncomp, &ctx->model_ncomp_cap, (size_t)ctx->B))) return r;
+	}
 	const size_t cells = (size_t)(ctx->B / 2) * (w / 4) * (h / 4);
 	if (cells > ctx->split_labels_cap) HIPCHK(ctx, ht_sync_all(ctx));
 	return dev_grow(ctx, &ctx->d_split_labels, &ctx->split_labels_cap, cells);
 }
 // checked and reserved: split, update, mirror back, all enqueued on s
 static int two_hands_enqueue(ht_ctx *ctx, int side, const uint16_t *d_depth, const float *d_cams, int w, int h, float segment_scale, const two_hands_args &a, const float *d_start, int B, float *d_poses_out,
-                             int32_t *d_info, hipStream_t s)
+                             int32_t *d_info, int32_t *d_source, hipStream_t s)
 {
 	const int nb = ctx->model.nb, flags = a.flags | HT_SPLIT_MIRROR_LEFT;
-	{ ht_prof_scope ps(ctx, "k_split_label", s); ht_launch_split_label(d_depth, w, h, B, a.lo, a.hi, a.step, a.min_pixels, flags, d_info, nullptr, ctx->d_split_labels, s); }
+	if (a.model_mode < 0) { ht_prof_scope ps(ctx, "k_split_label", s); ht_launch_split_label(d_depth, w, h, B, a.lo, a.hi, a.step, a.min_pixels, flags, d_info, nullptr, ctx->d_split_labels, s); }
+	else ht_launch_split_model(ctx, d_depth, d_cams, d_start ? d_start : ctx->d_state[0], d_start ? HT_POSE : HT_STATE_STRIDE, d_start ? 0 : 1, w, h, B, a.lo, a.hi, a.step, a.min_pixels, a.max_dist, a.model_mode, flags,
+	                           d_info, ctx->d_model_ncomp, d_source, nullptr, ctx->d_split_labels, s);
 	{ ht_prof_scope ps(ctx, "k_split_write", s); ht_launch_split_write(d_depth, ctx->d_split_labels, d_info, w, h, B, a.far, flags, ctx->d_hands_frames, s); }
 	{ ht_prof_scope ps(ctx, "k_split_cams", s); ht_launch_split_cams(d_cams, w, B, flags, ctx->d_hands_cams, s); }
 	if (d_start) { ht_prof_scope ps(ctx, "k_mirror_poses", s); ht_launch_mirror_poses(d_start, nb, 2 * B, ctx->d_two_flags, ctx->d_hands_start, s); }
@@ -816,31 +826,56 @@ static int two_hands_enqueue(ht_ctx *ctx, int side, const uint16_t *d_depth, con
 	{ ht_prof_scope ps(ctx, "k_mirror_poses", s); ht_launch_mirror_poses(d_poses_out, nb, 2 * B, ctx->d_two_flags, d_poses_out, s); }
 	return HT_OK;
 }
-extern "C" int ht_update_two_hands_dev(ht_ctx *ctx, int side, const uint16_t *d_depth, const float *d_cams, int w, int h, float segment_scale, uint16_t range_lo, uint16_t range_hi, uint16_t max_step,
-                                       int min_pixels, uint16_t far, int flags, const float *d_start_poses, int B, float *d_poses_out, int32_t *d_info, void *stream)
+static int two_hands_dev(ht_ctx *ctx, int side, const uint16_t *d_depth, const float *d_cams, int w, int h, float segment_scale, const two_hands_args &a, const float *d_start_poses, int B, float *d_poses_out,
+                         int32_t *d_info, int32_t *d_source, void *stream)
 {
 	CHECK_READY(ctx); CHECK_MODEL(ctx);
 	if (!d_depth || !d_cams || !d_poses_out) return HT_ERR_ARG;
-	const two_hands_args a = { range_lo, range_hi, max_step, far, min_pixels, flags };
 	{ const int r = two_hands_check(ctx, side, w, h, a, B); if (r) return r; }
-	{ const int r = two_hands_reserve(ctx, w, h); if (r) return r; }
-	return update_dev_end(ctx, two_hands_enqueue(ctx, side, d_depth, d_cams, w, h, segment_scale, a, d_start_poses, B, d_poses_out, d_info ? d_info : ctx->d_two_info, ht_user_stream(ctx, stream)));
+	{ const int r = two_hands_reserve(ctx, w, h, a.model_mode >= 0); if (r) return r; }
+	return update_dev_end(ctx, two_hands_enqueue(ctx, side, d_depth, d_cams, w, h, segment_scale, a, d_start_poses, B, d_poses_out, d_info ? d_info : ctx->d_two_info, d_source, ht_user_stream(ctx, stream)));
+}
+static int two_hands_sync(ht_ctx *ctx, int side, const uint16_t *depth, const float *cams, int w, int h, float segment_scale, const two_hands_args &a, int B, float *poses_out, int32_t *info, int32_t *source, float *cnn_out)
+{
+	CHECK_READY(ctx); CHECK_MODEL(ctx);
+	if (!depth || !cams || !poses_out) return HT_ERR_ARG;
+	{ const int r = two_hands_check(ctx, side, w, h, a, B); if (r) return r; }
+	hipStream_t s = ctx->stream;
+	const uint16_t *d_in; const float *d_cin;
+	int r = two_hands_reserve(ctx, w, h, a.model_mode >= 0);      // (first: it may wait for the stream, and the uploads below are already on it)
+	if (!r) r = stage_frames(ctx, depth, cams, w, h, B, s, &d_in, &d_cin);
+	if (r) return r;
+	int32_t *d_source = a.model_mode >= 0 ? ctx->d_model_ncomp + ctx->B / 2 : nullptr;
+	if ((r = two_hands_enqueue(ctx, side, d_in, d_cin, w, h, segment_scale, a, nullptr, B, ctx->d_poses_out, ctx->d_two_info, d_source, s))) return r;
+	if (info) HIPCHK(ctx, hipMemcpyAsync(info, ctx->d_two_info, (size_t)B * 16 * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+	if (source && d_source) HIPCHK(ctx, hipMemcpyAsync(source, d_source, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+	return finish_sync(ctx, 2 * B, s, poses_out, cnn_out, nullptr, (w == side && h == side) ? nullptr : "ht_update_two_hands");
+}
+extern "C" int ht_update_two_hands_dev(ht_ctx *ctx, int side, const uint16_t *d_depth, const float *d_cams, int w, int h, float segment_scale, uint16_t range_lo, uint16_t range_hi, uint16_t max_step,
+                                       int min_pixels, uint16_t far, int flags, const float *d_start_poses, int B, float *d_poses_out, int32_t *d_info, void *stream)
+{
+	const two_hands_args a = { range_lo, range_hi, max_step, far, min_pixels, flags, 0.0f, -1 };
+	return two_hands_dev(ctx, side, d_depth, d_cams, w, h, segment_scale, a, d_start_poses, B, d_poses_out, d_info, nullptr, stream);
 }
 extern "C" int ht_update_two_hands_sync(ht_ctx *ctx, int side, const uint16_t *depth, const float *cams, int w, int h, float segment_scale, uint16_t range_lo, uint16_t range_hi, uint16_t max_step,
                                         int min_pixels, uint16_t far, int flags, int B, float *poses_out, int32_t *info, float *cnn_out)
 {
-	CHECK_READY(ctx); CHECK_MODEL(ctx);
-	if (!depth || !cams || !poses_out) return HT_ERR_ARG;
-	const two_hands_args a = { range_lo, range_hi, max_step, far, min_pixels, flags };
-	{ const int r = two_hands_check(ctx, side, w, h, a, B); if (r) return r; }
-	hipStream_t s = ctx->stream;
-	const uint16_t *d_in; const float *d_cin;
-	int r = two_hands_reserve(ctx, w, h);      // (first: it may wait for the stream, and the uploads below are already on it)
-	if (!r) r = stage_frames(ctx, depth, cams, w, h, B, s, &d_in, &d_cin);
-	if (r) return r;
-	if ((r = two_hands_enqueue(ctx, side, d_in, d_cin, w, h, segment_scale, a, nullptr, B, ctx->d_poses_out, ctx->d_two_info, s))) return r;
-	if (info) HIPCHK(ctx, hipMemcpyAsync(info, ctx->d_two_info, (size_t)B * 16 * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-	return finish_sync(ctx, 2 * B, s, poses_out, cnn_out, nullptr, (w == side && h == side) ? nullptr : "ht_update_two_hands");
+	const two_hands_args a = { range_lo, range_hi, max_step, far, min_pixels, flags, 0.0f, -1 };
+	return two_hands_sync(ctx, side, depth, cams, w, h, segment_scale, a, B, poses_out, info, nullptr, cnn_out);
+}
+// The same calls with the model split in front.  mode below 0 would name the blob split: refused with every other unknown mode.  HT_SPLIT_USER_POSES
+// is the split calls' alone: d_start_poses also seed the slots, as centre-of-mass poses
+extern "C" int ht_update_two_hands_model_dev(ht_ctx *ctx, int side, const uint16_t *d_depth, const float *d_cams, int w, int h, float segment_scale, uint16_t range_lo, uint16_t range_hi, uint16_t max_step,
+                                             int min_pixels, uint16_t far, float max_dist, int mode, int flags, const float *d_start_poses, int B, float *d_poses_out, int32_t *d_info, int32_t *d_source, void *stream)
+{
+	const two_hands_args a = { range_lo, range_hi, max_step, far, min_pixels, flags, max_dist, mode < 0 ? 0x7fffffff : mode };
+	return two_hands_dev(ctx, side, d_depth, d_cams, w, h, segment_scale, a, d_start_poses, B, d_poses_out, d_info, d_source, stream);
+}
+extern "C" int ht_update_two_hands_model_sync(ht_ctx *ctx, int side, const uint16_t *depth, const float *cams, int w, int h, float segment_scale, uint16_t range_lo, uint16_t range_hi, uint16_t max_step,
+                                              int min_pixels, uint16_t far, float max_dist, int mode, int flags, int B, float *poses_out, int32_t *info, int32_t *source, float *cnn_out)
+{
+	const two_hands_args a = { range_lo, range_hi, max_step, far, min_pixels, flags, max_dist, mode < 0 ? 0x7fffffff : mode };
+	return two_hands_sync(ctx, side, depth, cams, w, h, segment_scale, a, B, poses_out, info, source, cnn_out);
 }
 
 // HandTracker::update_cnn_model (handtrack.h:734-741) and kickstart (:743-746) for B trackers, frames of any supported size

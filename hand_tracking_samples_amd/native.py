@@ -20,6 +20,7 @@ SENSOR_IVY, SENSOR_DS4 = 0, 1 # HT_SENSOR_IVY, HT_SENSOR_DS4
 JOINTS_COM_POSES = 1          # HT_JOINTS_COM_POSES
 SAMPLE_ENHANCED = 2           # HT_SAMPLE_ENHANCED
 SPLIT_RIGHT_IS_LOW_X, SPLIT_MIRROR_LEFT = 1, 2      # HT_SPLIT_RIGHT_IS_LOW_X, HT_SPLIT_MIRROR_LEFT
+SPLIT_MODEL_ALWAYS, SPLIT_MODEL_MERGED, SPLIT_USER_POSES = 0, 1, 4      # HT_SPLIT_MODEL_ALWAYS, HT_SPLIT_MODEL_MERGED, HT_SPLIT_USER_POSES
 KP_COM_POSES = 1              # HT_KP_COM_POSES
 KP_FEATURE8, KP_SKELETON, KP_CALLER, KP_MAX, KP_MAX_THR = 0, 1, 2, 64, 32      # HT_KP_FEATURE8, HT_KP_SKELETON, HT_KP_CALLER, HT_KP_MAX, HT_KP_MAX_THR
 CNN128_IN, CNNB128_COUNT = 16384, 30429920
@@ -45,6 +46,7 @@ SYMBOLS = (
     "ht_mirror_frames", "ht_mirror_frames_dev", "ht_mirror_cams", "ht_mirror_cams_dev", "ht_mirror_poses", "ht_mirror_poses_dev", "ht_update_hands_sync", "ht_update_hands_dev", "ht_reserve_hands", "ht_hands_capacity",
     "ht_model_mirror", "ht_model_body_planes",
     "ht_split_hands", "ht_split_hands_dev", "ht_update_two_hands_sync", "ht_update_two_hands_dev",
+    "ht_split_hands_model", "ht_split_hands_model_dev", "ht_update_two_hands_model_sync", "ht_update_two_hands_model_dev",
     "ht_keypoint_table", "ht_keypoints", "ht_keypoints_dev", "ht_keypoint_errors", "ht_keypoint_errors_dev", "ht_depth_compare", "ht_depth_compare_dev",
     "ht_pose_depth_residual", "ht_pose_depth_residual_dev",
     "ht_comm_available", "ht_comm_unique_id", "ht_comm_init", "ht_comm_info", "ht_gather_poses_dev", "ht_gather_wait", "ht_gather_wait_host", "ht_comm_destroy",
@@ -271,6 +273,10 @@ def load(build_if_missing=True):
     L.ht_split_hands_dev.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, u16, u16, u16, C.c_int, u16, C.c_int, vp, vp, vp, vp, vp, vp]
     L.ht_update_two_hands_sync.argtypes = [vp, C.c_int, u16p, fp, C.c_int, C.c_int, C.c_float, u16, u16, u16, C.c_int, u16, C.c_int, C.c_int, fp, i32p, fp]
     L.ht_update_two_hands_dev.argtypes = [vp, C.c_int, vp, vp, C.c_int, C.c_int, C.c_float, u16, u16, u16, C.c_int, u16, C.c_int, vp, C.c_int, vp, vp, vp]
+    L.ht_split_hands_model.argtypes = [vp, u16p, fp, fp, C.c_int, C.c_int, C.c_int, u16, u16, u16, C.c_int, u16, C.c_float, C.c_int, C.c_int, u16p, fp, i32p, i32p, i32p, fp, u16p]
+    L.ht_split_hands_model_dev.argtypes = [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, u16, u16, u16, C.c_int, u16, C.c_float, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.ht_update_two_hands_model_sync.argtypes = [vp, C.c_int, u16p, fp, C.c_int, C.c_int, C.c_float, u16, u16, u16, C.c_int, u16, C.c_float, C.c_int, C.c_int, C.c_int, fp, i32p, i32p, fp]
+    L.ht_update_two_hands_model_dev.argtypes = [vp, C.c_int, vp, vp, C.c_int, C.c_int, C.c_float, u16, u16, u16, C.c_int, u16, C.c_float, C.c_int, C.c_int, vp, C.c_int, vp, vp, vp, vp]
     L.ht_model_body_planes.argtypes = [vp, C.c_int, fp, fp]
     dp, i64p, ci, cf = C.POINTER(C.c_double), C.POINTER(C.c_int64), C.c_int, C.c_float
     L.ht_keypoint_table.argtypes = [vp, ci, ip, ip, fp, ip]
@@ -543,6 +549,54 @@ class Context:
     def update_two_hands_dev(self, side, d_depth, d_cams, w, h, segment_scale, range_lo, range_hi, max_step, min_pixels, far, flags, d_start, B, d_poses_out, d_info=None, stream=None):
         self._chk(self.L.ht_update_two_hands_dev(self.h, int(side), d_depth, d_cams, int(w), int(h), float(segment_scale), int(range_lo), int(range_hi), int(max_step), int(min_pixels), int(far), int(flags),
                                                  d_start, int(B), d_poses_out, d_info, stream))
+
+    # ---- two hands that touch or cross (include/ht_mi355x.h "two hands that touch or cross")
+    def split_hands_model(self, depth, cams, poses, range_lo, range_hi, far, max_dist=float("inf"), mode=SPLIT_MODEL_ALWAYS, max_step=65535, min_pixels=1, flags=0, want_cams=True, want_n=True, want_source=True,
+                          want_dist=False, want_labels=False):
+        """depth u16[B,h,w], cams [B,12], poses [B,2,nb,7] (0 right, 1 left, real space) -> dict(frames u16[B,2,h,w], info i32[B,2,8], and on request cams [B,2,12], n_components [B],
+        source i32[B], dist f32[B,h/4,w/4,2], labels u16[B,h/4,w/4]) (ht_split_hands_model)"""
+        depth = _c(depth, np.uint16); cams = _c(cams, np.float32); poses = _c(poses, np.float32)
+        B, h, w = depth.shape
+        assert cams.size == B * CAM and (self.nb == 0 or poses.size == B * 2 * self.nb * POSE)
+        u16 = C.POINTER(C.c_uint16); i32 = C.POINTER(C.c_int32)
+        out = dict(frames=np.empty((B, 2, h, w), np.uint16), info=np.empty((B, 2, 8), np.int32))
+        if want_cams:
+            out["cams"] = np.empty((B, 2, CAM), np.float32)
+        if want_n:
+            out["n_components"] = np.empty(B, np.int32)
+        if want_source:
+            out["source"] = np.empty(B, np.int32)
+        if want_dist:
+            out["dist"] = np.empty((B, h // 4, w // 4, 2), np.float32)
+        if want_labels:
+            out["labels"] = np.empty((B, h // 4, w // 4), np.uint16)
+        self._chk(self.L.ht_split_hands_model(self.h, depth.ctypes.data_as(u16), _f(cams), _f(poses), w, h, B, int(range_lo), int(range_hi), int(max_step), int(min_pixels), int(far), float(max_dist), int(mode),
+                                              int(flags), out["frames"].ctypes.data_as(u16), _f(out["cams"]) if want_cams else None, out["info"].ctypes.data_as(i32),
+                                              out["n_components"].ctypes.data_as(i32) if want_n else None, out["source"].ctypes.data_as(i32) if want_source else None,
+                                              _f(out["dist"]) if want_dist else None, out["labels"].ctypes.data_as(u16) if want_labels else None))
+        return out
+
+    def split_hands_model_dev(self, d_depth, d_cams, d_poses, w, h, B, range_lo, range_hi, max_step, min_pixels, far, max_dist, mode, flags, d_depth_out, d_cams_out, d_info, d_n_components=None, d_source=None,
+                              d_dist=None, d_labels=None, stream=None):
+        self._chk(self.L.ht_split_hands_model_dev(self.h, d_depth, d_cams, d_poses, int(w), int(h), int(B), int(range_lo), int(range_hi), int(max_step), int(min_pixels), int(far), float(max_dist), int(mode), int(flags),
+                                                  d_depth_out, d_cams_out, d_info, d_n_components, d_source, d_dist, d_labels, stream))
+
+    def update_two_hands_model(self, depth, cams, range_lo, range_hi, far, max_dist=float("inf"), mode=SPLIT_MODEL_MERGED, side=64, segment_scale=0.17, max_step=65535, min_pixels=1, flags=0, want_cnn=False):
+        """update_two_hands_sync with the model split in front, priors the slots' carried state: poses [B,2,nb,7], info i32[B,2,8], source i32[B], and cnn_out [2B,2304] on request
+        (ht_update_two_hands_model_sync)"""
+        depth = _c(depth, np.uint16); cams = _c(cams, np.float32)
+        B, h, w = depth.shape
+        poses = np.empty((B, 2, self.nb, POSE), np.float32); info = np.empty((B, 2, 8), np.int32); source = np.empty(B, np.int32)
+        cnn = np.empty((2 * B, CNN_OUT), np.float32) if want_cnn else None
+        i32 = C.POINTER(C.c_int32)
+        self._chk(self.L.ht_update_two_hands_model_sync(self.h, int(side), depth.ctypes.data_as(C.POINTER(C.c_uint16)), _f(cams), w, h, float(segment_scale), int(range_lo), int(range_hi), int(max_step),
+                                                        int(min_pixels), int(far), float(max_dist), int(mode), int(flags), B, _f(poses), info.ctypes.data_as(i32), source.ctypes.data_as(i32),
+                                                        _f(cnn) if want_cnn else None))
+        return (poses, info, source, cnn) if want_cnn else (poses, info, source)
+
+    def update_two_hands_model_dev(self, side, d_depth, d_cams, w, h, segment_scale, range_lo, range_hi, max_step, min_pixels, far, max_dist, mode, flags, d_start, B, d_poses_out, d_info=None, d_source=None, stream=None):
+        self._chk(self.L.ht_update_two_hands_model_dev(self.h, int(side), d_depth, d_cams, int(w), int(h), float(segment_scale), int(range_lo), int(range_hi), int(max_step), int(min_pixels), int(far),
+                                                       float(max_dist), int(mode), int(flags), d_start, int(B), d_poses_out, d_info, d_source, stream))
 
     def update_direct_sync(self, depth, cams, side=128, want_cnn=False):
         """BASELINE configs[4] end to end: depth u16[B,side,side] frames that are their own segment, the net of that input size (ht_update_direct_sync)."""

@@ -21,6 +21,7 @@
 #include <cmath>
 #include <cstdint>
 #include <fstream>
+#include <limits>
 #include <memory>
 #include <stdexcept>
 #include <string>
@@ -825,13 +826,57 @@ inline SplitResult SplitHands(const Image<unsigned short> &depth, unsigned short
 	if (!detail::live_ctx()) throw std::runtime_error("SplitHands: construct a HandTracker or a TwoHandTracker first (the split runs on its device)");
 	return SplitHandsOn(detail::live_ctx(), depth, range_lo, range_hi, far, max_step, min_pixels, flags);
 }
+// SplitHandsByModel (include/ht_mi355x.h "two hands that touch or cross"): the same cut by the tracked models and not by blobs -- every foreground cell goes to the hand
+// whose bodies, at the given centre-of-mass poses in the camera's own space (HT_SPLIT_USER_POSES: rig-space poses, what update() returns), are nearer by the tracker's
+// closest().  `left` is the left hand's own (unmirrored) pose.  mode HT_SPLIT_MODEL_ALWAYS or HT_SPLIT_MODEL_MERGED (only where the blobs have merged and both hands come
+// out present); max_dist in metres drops cells far from both hands.  source: 1 the models decided, 0 the blob split's result stands.
+struct SplitModelResult : SplitResult { int source; };
+inline SplitModelResult SplitHandsByModelOn(ht_ctx *ctx, const Image<unsigned short> &depth, const std::vector<Pose> &right, const std::vector<Pose> &left, unsigned short range_lo, unsigned short range_hi,
+                                            unsigned short far, float max_dist = std::numeric_limits<float>::infinity(), int mode = HT_SPLIT_MODEL_ALWAYS, unsigned short max_step = 65535, int min_pixels = 1, int flags = 0)
+{
+	const int w = depth.dim().x, h = depth.dim().y;
+	if (depth.raster.size() != (size_t)w * h) throw std::runtime_error("SplitHandsByModel: the raster does not match the camera's dimensions");
+	int nb = 0; ht_model_info(ctx, &nb, nullptr, nullptr);
+	if ((int)right.size() != nb || (int)left.size() != nb) throw std::runtime_error("SplitHandsByModel: one pose per body of the tracker's model for either hand");
+	const DCamera &c = depth.cam;
+	const float cam[HT_CAM] = { c.focal().x, c.focal().y, c.principal().x, c.principal().y, c.depth_scale, c.pose.position.x, c.pose.position.y, c.pose.position.z,
+	                            c.pose.orientation.x, c.pose.orientation.y, c.pose.orientation.z, c.pose.orientation.w };
+	std::vector<float> poses((size_t)2 * nb * HT_POSE);
+	for (int k = 0; k < 2; k++) for (int b = 0; b < nb; b++)
+	{
+		const Pose &q = (k ? left : right)[b]; float *p = &poses[((size_t)k * nb + b) * HT_POSE];
+		p[0] = q.position.x; p[1] = q.position.y; p[2] = q.position.z; p[3] = q.orientation.x; p[4] = q.orientation.y; p[5] = q.orientation.z; p[6] = q.orientation.w;
+	}
+	std::vector<unsigned short> out((size_t)2 * w * h); float co[2][HT_CAM];
+	SplitModelResult r;
+	check(ctx, ht_split_hands_model(ctx, depth.raster.data(), cam, poses.data(), w, h, 1, range_lo, range_hi, max_step, min_pixels, far, max_dist, mode, flags, out.data(), &co[0][0], &r.info[0][0], &r.n_components,
+	                                &r.source, nullptr, nullptr));
+	Image<unsigned short> *im[2] = { &r.right, &r.left };
+	for (int k = 0; k < 2; k++)
+	{
+		Pose pose; pose.position = { co[k][5], co[k][6], co[k][7] }; pose.orientation = { co[k][8], co[k][9], co[k][10], co[k][11] };
+		*im[k] = Image<unsigned short>(DCamera({ w, h }, { co[k][0], co[k][1] }, { co[k][2], co[k][3] }, co[k][4], pose), std::vector<unsigned short>(out.begin() + (size_t)k * w * h, out.begin() + (size_t)(k + 1) * w * h));
+		r.present[k] = r.info[k][0] > 0;
+	}
+	return r;
+}
+inline SplitModelResult SplitHandsByModel(const Image<unsigned short> &depth, const std::vector<Pose> &right, const std::vector<Pose> &left, unsigned short range_lo, unsigned short range_hi, unsigned short far,
+                                          float max_dist = std::numeric_limits<float>::infinity(), int mode = HT_SPLIT_MODEL_ALWAYS, unsigned short max_step = 65535, int min_pixels = 1, int flags = 0)
+{
+	if (!detail::live_ctx()) throw std::runtime_error("SplitHandsByModel: construct a HandTracker or a TwoHandTracker first (the split runs on its device and its model)");
+	return SplitHandsByModelOn(detail::live_ctx(), depth, right, left, range_lo, range_hi, far, max_dist, mode, max_step, min_pixels, flags);
+}
 // Both hands of one camera: one context of two tracker slots, slot 0 the right hand, slot 1 the left hand in canonical (mirrored) space.  update() splits the frame on the
 // device, tracks both slots with ht_update_two_hands_sync and returns both hands' rig-space poses (what handmodel.GetPoseUser() is for a HandTracker) in the camera's own
 // space, with the presence flags: the poses of an absent hand mean nothing.  Synchronous only (no overlapped arrangement).  The range is in metres like HandSegmentVR's
 // wrange; everything nearer than wrange.y and not nearer than wrange.x is foreground, and `far` metres is written where a hand's frame is masked.
 struct TwoHandTracker
 {
-	struct Hands { std::vector<Pose> right, left; bool present[2]; int info[2][8]; };
+	struct Hands { std::vector<Pose> right, left; bool present[2]; int info[2][8]; int source; };      // source: 1 the tracked models split the frame, 0 the blobs
+	// how update() splits the frame: by blobs (the default; hands that touch are one blob and one of them is lost), by the slots' tracked models where the blobs have
+	// merged, or always by the models; max_dist (metres): with the models, cells farther than this from both hands are dropped (a forearm, a torso in range)
+	enum split_mode_t { Blobs, ModelWhenMerged, ModelAlways };
+	split_mode_t split_mode = Blobs; float max_dist = std::numeric_limits<float>::infinity();
 	float segment_scale = 0.17f; float2 wrange{ 0.1f, 0.65f }; float far = 4.0f; float max_step = 0.0f;      // max_step in metres between neighbouring quarter-size pixels of one blob; 0: no depth test
 	int min_pixels = 16; bool right_is_low_x = false;      // right_is_low_x: a camera facing the user
 	int side = 64; CNN cnn;
@@ -864,8 +909,15 @@ struct TwoHandTracker
 		const auto units = [&](float metres) { const float u = metres / c.depth_scale; return (unsigned short)(u < 0.0f ? 0.0f : (u > 65535.0f ? 65535.0f : u)); };
 		std::vector<float> out((size_t)2 * nb_ * HT_POSE);
 		Hands r;
-		check(ctx_, ht_update_two_hands_sync(ctx_, side, dimage.raster.data(), cam, w, h, segment_scale, units(wrange.x), units(wrange.y), max_step > 0.0f ? units(max_step) : (unsigned short)65535, min_pixels,
-		                                     units(far), right_is_low_x ? HT_SPLIT_RIGHT_IS_LOW_X : 0, 1, out.data(), &r.info[0][0], nullptr));
+		const unsigned short step = max_step > 0.0f ? units(max_step) : (unsigned short)65535;
+		r.source = 0;
+		if (split_mode == Blobs)
+			check(ctx_, ht_update_two_hands_sync(ctx_, side, dimage.raster.data(), cam, w, h, segment_scale, units(wrange.x), units(wrange.y), step, min_pixels, units(far), right_is_low_x ? HT_SPLIT_RIGHT_IS_LOW_X : 0, 1,
+			                                     out.data(), &r.info[0][0], nullptr));
+		else      // (the position rule names no hand in ModelAlways: right_is_low_x bears on the blob split of ModelWhenMerged only)
+			check(ctx_, ht_update_two_hands_model_sync(ctx_, side, dimage.raster.data(), cam, w, h, segment_scale, units(wrange.x), units(wrange.y), step, min_pixels, units(far), max_dist,
+			                                           split_mode == ModelAlways ? HT_SPLIT_MODEL_ALWAYS : HT_SPLIT_MODEL_MERGED, split_mode == ModelWhenMerged && right_is_low_x ? HT_SPLIT_RIGHT_IS_LOW_X : 0, 1,
+			                                           out.data(), &r.info[0][0], &r.source, nullptr));
 		std::vector<Pose> *hand[2] = { &r.right, &r.left };
 		for (int k = 0; k < 2; k++)
 		{

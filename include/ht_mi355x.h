@@ -683,6 +683,43 @@ int ht_split_hands_dev(ht_ctx *ctx, const uint16_t *d_depth, const float *d_cams
 int ht_update_two_hands_sync(ht_ctx *ctx, int side, const uint16_t *depth, const float *cams, int w, int h, float segment_scale, uint16_t range_lo, uint16_t range_hi, uint16_t max_step, int min_pixels, uint16_t far, int flags, int B, float *poses_out, int32_t *info, float *cnn_out);
 int ht_update_two_hands_dev(ht_ctx *ctx, int side, const uint16_t *d_depth, const float *d_cams, int w, int h, float segment_scale, uint16_t range_lo, uint16_t range_hi, uint16_t max_step, int min_pixels, uint16_t far, int flags, const float *d_start_poses, int B, float *d_poses_out, int32_t *d_info, void *stream);
 
+/* ---- two hands that touch or cross (an addition: the blob split above gives ONE blob for hands that touch, and names hands by their place in the image) ---------
+ * Each foreground cell of the quarter image goes to the hand whose tracked model is nearer, by the tracker's own closest() (physmodel.h:137-162, the signed distance
+ * FitError and the cloud rows use).  Labels, info and frames have the blob split's shape, so the frame writer, the cameras and the update behind them are the calls above.
+ * The context needs a hand model (HT_ERR_STATE otherwise).  Sizes as ht_split_hands.
+ *   cell depth     Q[Y][X] as above; (x*, y*) the first pixel of the 4x4 block, in raster order, that attains it; foreground range_lo <= Q < range_hi
+ *   cell point     v = deprojectz((x*, y*), (float)Q * depth_scale) with cams[f]'s focal, principal point and depth_scale in the expression order of misc_image.h:48;
+ *                  the camera's pose is not used: poses are in the camera's own space, as ht_update_two_hands_*'s poses_out and d_start_poses and as ht_render_depth
+ *   priors         poses [B][2][nb][7]: index 0 the right hand, 1 the left hand in real (unmirrored) space; centre-of-mass poses (ht_tracker_reset's, ht_render_depth's).
+ *                  The left prior is first mirrored into canonical space ("left hands" above: sign bits, exact).  With HT_SPLIT_USER_POSES every pose is a user pose
+ *                  (an update's poses_out) and pos += qrot(q, com[b]) is applied after that mirror, in the space the model's com[b] belongs to
+ *   distances      d_R = dot(plane, (v, 1)) with plane = closest(bodies at the right prior, v); d_L the same with the bodies at the canonical left prior and the
+ *                  point (-v.x, v.y, v.z).  fp32, one IEEE operation after another in the reference's order
+ *   assignment     a foreground cell gets label 0 (right) iff d_R <= d_L, otherwise 1; if (d_L < d_R ? d_L : d_R) > max_dist it is background.  max_dist in metres;
+ *                  +inf or FLT_MAX switch the test off; NaN or negative: HT_ERR_ARG.  Background cells carry 0xFFFF
+ *   info [B][2][8] as above over the cells of each label, label = 0 or 1; a hand of count < min_pixels is absent (0, 0xFFFF, 0, ...) and the frame writer matches none
+ *                  of its cells
+ *   modes          HT_SPLIT_MODEL_ALWAYS: every frame as above; no blob labelling runs, max_step is not used, HT_SPLIT_RIGHT_IS_LOW_X is refused; n_components is the
+ *                  number of present hands.  HT_SPLIT_MODEL_MERGED: the blob split runs first, unchanged; a frame takes the model assignment iff the blob split found
+ *                  n_components < 2 AND the model assignment leaves both hands present; otherwise the blob split's labels and info stand, byte for byte.
+ *                  n_components is the blob split's
+ *   source [B]     int32, optional: 0 the frame's result is the blob split's, 1 the model's
+ *   dist           [B][H4][W4][2] fp32, optional: d_R, d_L of every foreground cell (also of one that max_dist dropped), +inf for the others; in MERGED mode +inf
+ *                  throughout a frame whose blob split found two components (nothing was evaluated)
+ * ht_split_hands_model      depth, cams, poses -> depth_out [B][2][h][w], cams_out [B][2][12], info, n_components, source, dist, labels.  cams is required; cams_out,
+ *                  n_components, source, dist and labels are optional (NULL).  B is not bounded by max_batch; the host form stages through the buffer that follows
+ *                  the largest call; B = 0 does nothing; every check runs before anything grows or launches and a refused call leaves the context usable.
+ * ht_update_two_hands_model_*  ht_update_two_hands_* with this split in front: the same staging, 2 * B <= max_batch rule and errors.  The priors are the poses the
+ *                  update starts from: d_start_poses where given, else slot 2i's and 2i + 1's carried hand-model state (the left one is canonical already and is not
+ *                  mirrored: the same bits).  HT_SPLIT_USER_POSES is refused here (d_start_poses also seed the slots, as centre-of-mass poses). */
+#define HT_SPLIT_MODEL_ALWAYS 0
+#define HT_SPLIT_MODEL_MERGED 1
+#define HT_SPLIT_USER_POSES   4   /* accepted by the new calls only */
+int ht_split_hands_model(ht_ctx *ctx, const uint16_t *depth, const float *cams, const float *poses, int w, int h, int B, uint16_t range_lo, uint16_t range_hi, uint16_t max_step, int min_pixels, uint16_t far, float max_dist, int mode, int flags, uint16_t *depth_out, float *cams_out, int32_t *info, int32_t *n_components, int32_t *source, float *dist, uint16_t *labels);
+int ht_split_hands_model_dev(ht_ctx *ctx, const uint16_t *d_depth, const float *d_cams, const float *d_poses, int w, int h, int B, uint16_t range_lo, uint16_t range_hi, uint16_t max_step, int min_pixels, uint16_t far, float max_dist, int mode, int flags, uint16_t *d_depth_out, float *d_cams_out, int32_t *d_info, int32_t *d_n_components, int32_t *d_source, float *d_dist, uint16_t *d_labels, void *stream);
+int ht_update_two_hands_model_sync(ht_ctx *ctx, int side, const uint16_t *depth, const float *cams, int w, int h, float segment_scale, uint16_t range_lo, uint16_t range_hi, uint16_t max_step, int min_pixels, uint16_t far, float max_dist, int mode, int flags, int B, float *poses_out, int32_t *info, int32_t *source, float *cnn_out);
+int ht_update_two_hands_model_dev(ht_ctx *ctx, int side, const uint16_t *d_depth, const float *d_cams, int w, int h, float segment_scale, uint16_t range_lo, uint16_t range_hi, uint16_t max_step, int min_pixels, uint16_t far, float max_dist, int mode, int flags, const float *d_start_poses, int B, float *d_poses_out, int32_t *d_info, int32_t *d_source, void *stream);
+
 /* ---- tracking accuracy (an addition: the reference places model points in the image in every application and measures nothing) -----------------------------
  * Keypoints of a batch of poses in 3-D and in pixels with their visibility against the depth frame, keypoint errors between two pose sets with the literature's
  * summary figures, the depth residual and silhouette overlap of two sets of frames, and poses against frames in one call.  Everything fp32, one IEEE operation

@@ -10,6 +10,15 @@ with the series' spread (max - min), the compared calls' series taking turns (th
  (d) --parent-lib PATH (a library built from the parent commit: HT_LIB_PATH=PATH python -m hand_tracking_samples_amd.build in a checkout of it):
      ht_update_frames_sized_dev, no two-hand call made, against the parent's, alternating.  Bar: the same poses, the difference inside twice the parent's spread.
 
+--model measures the model split in place of (a)-(d) and writes profiles/r24_split_model.json (or --out): the hands 0.05 m either side of the axis, where
+they touch and the blob split sees one component.
+ (e) k_split_model (HT_SPLIT_MODEL_ALWAYS: every frame evaluated) at 320x240 and 640x480 beside k_split_label on the same frames, with the foreground cells per frame
+     and the closest() evaluations per second that follow.  No bar.
+ (f) ht_update_two_hands_model_dev in both modes on 512 touching scenes beside ht_update_two_hands_dev on the same frames, interleaved: the difference is the feature's
+     cost, stated as a share of the update.  No bar.
+ (g) with --parent-lib: ht_update_two_hands_dev and ht_update_frames_sized_dev on a context no model-split call was made on against the parent commit's library,
+     alternating.  Bar: the same poses, the difference inside twice the parent's spread.
+
 Exits 1 when a bar is missed.  Writes profiles/r20_split.json (or --out).  Scenes: two of the bench hands rendered on the device, one of them mirrored, 0.09 m either
 side of the optical axis."""
 import argparse
@@ -50,6 +59,141 @@ def kernel_series(ctx, fn, stream, names, steps, warmup):
     return {k: prof[k][0] / prof[k][1] for k in names}
 
 
+def parent_two_hands(path, weights):
+    """ht_update_two_hands_dev and ht_update_frames_sized_dev of the library at `path` on a context of its own (plain ctypes, as bench_mirror.parent_update)"""
+    L = C.CDLL(path)
+    vp = C.c_void_p; u16 = C.c_uint16
+    L.ht_create.argtypes = [C.c_char_p, C.c_int, C.c_int, C.POINTER(vp)]; L.ht_destroy.argtypes = [vp]
+    L.ht_cnn_load_weights.argtypes = [vp, C.POINTER(C.c_float), C.c_size_t]; L.ht_get_params.argtypes = [vp, C.POINTER(native.Params)]; L.ht_set_params.argtypes = [vp, C.POINTER(native.Params)]
+    L.ht_update_frames_sized_dev.argtypes = [vp, C.c_int, vp, vp, C.c_int, C.c_int, C.c_float, vp, C.c_int, vp, vp]
+    L.ht_update_two_hands_dev.argtypes = [vp, C.c_int, vp, vp, C.c_int, C.c_int, C.c_float, u16, u16, u16, C.c_int, u16, C.c_int, vp, C.c_int, vp, vp, vp]
+    h = vp()
+    if L.ht_create(os.fsencode(BM.M17), B, 0, C.byref(h)) != 0 or L.ht_cnn_load_weights(h, weights.ctypes.data_as(C.POINTER(C.c_float)), weights.size) != 0:
+        raise RuntimeError("cannot set up a context of " + path)
+    p = native.Params(); L.ht_get_params(h, C.byref(p)); p.microforce = 3.0; p.mainthreadpasses = 3; L.ht_set_params(h, C.byref(p))
+
+    def two(d_depth, d_cams, w, hgt, d_start, n, d_out, d_info, stream):
+        if L.ht_update_two_hands_dev(h, 64, d_depth, d_cams, w, hgt, 0.17, LO, HI, 65535, MINPX, FAR, 0, d_start, n, d_out, d_info, stream) != 0:
+            raise RuntimeError("ht_update_two_hands_dev failed for " + path)
+
+    def frames(d_depth, d_cams, w, hgt, d_start, d_out, stream):
+        if L.ht_update_frames_sized_dev(h, 64, d_depth, d_cams, w, hgt, 0.17, d_start, B, d_out, stream) != 0:
+            raise RuntimeError("ht_update_frames_sized_dev failed for " + path)
+    return two, frames, (lambda: L.ht_destroy(h))
+
+
+def model_rows(a):
+    """(e), (f), (g) of the module's text"""
+    z = np.load(os.path.join(ROOT, "bench_data", "frames1024.npz"))
+    dev = torch.device("cuda:0")
+    s = torch.cuda.Stream(device=dev)
+    st = s.cuda_stream
+    inf = float("inf")
+    ctx = native.Context(BM.M17, B)
+    res = {"device": torch.cuda.get_device_name(0), "frames": B, "steps": a.steps, "update_steps": a.update_steps, "rounds": a.rounds, "lateral_offset_m": 0.05,
+           "resources": {k: {q: v[q] for q in ("VGPRs", "ScratchSize", "LDS Size", "Occupancy") if q in v} for k, v in hb.resource_usage().items() if "k_split" in k}}
+    ok = True
+    try:
+        ctx.set_params(microforce=3.0, mainthreadpasses=3)
+        cam = {(640, 480): np.zeros((B, 12), np.float32)}
+        cam[(640, 480)][:, :5] = [610, 610, 320, 240, 0.001]; cam[(640, 480)][:, 11] = 1
+        cam[(320, 240)] = cam[(640, 480)].copy(); cam[(320, 240)][:, :4] /= 2
+        gt = z["gtpose"].astype(np.float32)
+        right = gt.copy(); right[..., 0] += 0.05
+        lcanon = np.roll(gt, 341, axis=0).copy(); lcanon[..., 0] += 0.05      # the left hands in canonical space; their frames are rendered through the mirrored camera and flipped
+        left = mirror_poses(lcanon)
+        frames = {}
+        for wh in cam:
+            mcam = cam[wh].copy(); mcam[:, 2] = np.float32(wh[0] - 1) - mcam[:, 2]
+            frames[wh] = np.minimum(ctx.render_depth(right, cam[wh], wh[0], wh[1]).reshape(B, wh[1], wh[0]), ctx.render_depth(lcanon, mcam, wh[0], wh[1]).reshape(B, wh[1], wh[0])[:, :, ::-1])
+        priors = np.ascontiguousarray(np.stack([right, left], axis=1).astype(np.float32))      # [B][2][nb][7], the camera's space
+        with torch.cuda.stream(s):
+            td = {wh: torch.from_numpy(np.ascontiguousarray(frames[wh]).view(np.int16)).to(dev) for wh in cam}
+            tc = {wh: torch.from_numpy(cam[wh]).to(dev) for wh in cam}
+            to = {wh: torch.empty((B, 2) + td[wh].shape[1:], dtype=torch.int16, device=dev) for wh in cam}
+            tp = torch.from_numpy(priors).to(dev)
+            tco = torch.empty((B, 2, 12), dtype=torch.float32, device=dev); info = torch.empty((B, 2, 8), dtype=torch.int32, device=dev); ncomp = torch.empty(B, dtype=torch.int32, device=dev)
+            src = torch.empty(B, dtype=torch.int32, device=dev)
+        s.synchronize()
+        ctx.profile_enable(1)
+        res["split_model"] = []
+        for wh in ((320, 240), (640, 480)):
+            blob = lambda wh=wh: ctx.split_hands_dev(td[wh].data_ptr(), tc[wh].data_ptr(), wh[0], wh[1], B, LO, HI, 65535, MINPX, FAR, native.SPLIT_MIRROR_LEFT, to[wh].data_ptr(), tco.data_ptr(), info.data_ptr(),
+                                                     ncomp.data_ptr(), None, st)
+            model = lambda wh=wh: ctx.split_hands_model_dev(td[wh].data_ptr(), tc[wh].data_ptr(), tp.data_ptr(), wh[0], wh[1], B, LO, HI, 65535, 1, FAR, inf, native.SPLIT_MODEL_ALWAYS, native.SPLIT_MIRROR_LEFT,
+                                                            to[wh].data_ptr(), tco.data_ptr(), info.data_ptr(), None, src.data_ptr(), None, None, st)
+            blob(); s.synchronize()
+            merged = int((ncomp < 2).sum().item())
+            model(); s.synchronize()
+            cells = float(info[:, :, 0].sum().item()) / B      # min_pixels 1, no max_dist: every foreground cell is counted for one hand
+            km, kl = [], []
+            for _ in range(a.rounds):
+                km.append(kernel_series(ctx, model, s, ("k_split_model",), a.steps, a.warmup)["k_split_model"])
+                kl.append(kernel_series(ctx, blob, s, ("k_split_label",), a.steps, a.warmup)["k_split_label"])
+            km, kl = BM.stat(km), BM.stat(kl)
+            row = {"frame": "%dx%d" % wh, "frames_whose_blobs_merged": merged, "foreground_cells_per_frame": round(cells, 1), "k_split_model": km, "k_split_label": kl, "model_over_label": round(km["ms"] / kl["ms"], 4),
+                   "closest_evaluations_per_s": round(2 * cells * B / (km["ms"] * 1e-3), 0)}
+            res["split_model"].append(row); print(json.dumps(row), flush=True)
+        ctx.profile_enable(0)
+        # (f) the model update beside the blob update on the same touching scenes
+        w64 = W.make_cnnb()
+        ctx.load_weights(w64)
+        wh = (320, 240); S = B // 2
+        with torch.cuda.stream(s):
+            out = torch.empty((B, 17, 7), dtype=torch.float32, device=dev); out2 = torch.empty_like(out)
+        s.synchronize()
+        ctx.reserve_hands(*wh)
+        two = lambda: ctx.update_two_hands_dev(64, td[wh].data_ptr(), tc[wh].data_ptr(), wh[0], wh[1], 0.17, LO, HI, 65535, MINPX, FAR, 0, tp.data_ptr(), S, out.data_ptr(), info.data_ptr(), st)
+        mod = lambda mode: (lambda: ctx.update_two_hands_model_dev(64, td[wh].data_ptr(), tc[wh].data_ptr(), wh[0], wh[1], 0.17, LO, HI, 65535, MINPX, FAR, inf, mode, 0, tp.data_ptr(), S, out2.data_ptr(), info.data_ptr(),
+                                                                   src.data_ptr(), st))
+        fns = {"ht_update_two_hands_dev": two, "model, merged": mod(native.SPLIT_MODEL_MERGED), "model, always": mod(native.SPLIT_MODEL_ALWAYS)}
+        present = {}
+        for k, fn in fns.items():
+            fn(); s.synchronize()
+            present[k] = int((info[:S, :, 0] > 0).all(dim=1).sum().item())
+        ms = {k: BM.stat(v) for k, v in BM.interleaved(fns, s, a.update_steps, 1, a.rounds).items()}
+        base = ms["ht_update_two_hands_dev"]["ms"]
+        row = {"scenes": S, "frame": "320x240, side 64, re-seeded every call", "scenes_with_both_hands_present": present, "ms": ms,
+               "cost_ms": {k: round(ms[k]["ms"] - base, 5) for k in ms if k != "ht_update_two_hands_dev"}, "cost_share_of_the_update": {k: round((ms[k]["ms"] - base) / base, 5) for k in ms if k != "ht_update_two_hands_dev"},
+               "frames_overflow": ctx.frames_overflow()}
+        res["update_two_hands_model"] = row; print(json.dumps(row), flush=True)
+        # (g) the existing calls against the parent commit's library
+        if a.parent_lib:
+            ctx2 = native.Context(BM.M17, B)      # a context no model-split call was made on
+            try:
+                ctx2.set_params(microforce=3.0, mainthreadpasses=3); ctx2.load_weights(w64)
+                ptwo, pframes, pclose = parent_two_hands(os.path.abspath(a.parent_lib), w64)
+                with torch.cuda.stream(s):
+                    ts1 = torch.from_numpy(z["startpose"].astype(np.float32)).to(dev); info2 = torch.empty_like(info)
+                s.synchronize()
+                res["existing_calls_against_parent"] = []
+                pairs = {"ht_update_two_hands_dev, 512 scenes of 320x240, side 64":
+                         (lambda: ctx2.update_two_hands_dev(64, td[wh].data_ptr(), tc[wh].data_ptr(), wh[0], wh[1], 0.17, LO, HI, 65535, MINPX, FAR, 0, tp.data_ptr(), S, out.data_ptr(), info.data_ptr(), st),
+                          lambda: ptwo(td[wh].data_ptr(), tc[wh].data_ptr(), wh[0], wh[1], tp.data_ptr(), S, out2.data_ptr(), info2.data_ptr(), st)),
+                         "ht_update_frames_sized_dev, 1024 frames of 320x240, side 64":
+                         (lambda: ctx2.update_frames_sized_dev(64, td[wh].data_ptr(), tc[wh].data_ptr(), wh[0], wh[1], 0.17, ts1.data_ptr(), B, out.data_ptr(), st),
+                          lambda: pframes(td[wh].data_ptr(), tc[wh].data_ptr(), wh[0], wh[1], ts1.data_ptr(), out2.data_ptr(), st))}
+                for name, (this, parent) in pairs.items():
+                    fns = {"this library": this, "parent library": parent}
+                    for fn in fns.values():
+                        fn()
+                    s.synchronize()
+                    same = bool(torch.equal(out, out2))
+                    ms = BM.interleaved(fns, s, a.update_steps, 1, a.rounds)
+                    n, p = BM.stat(ms["this library"]), BM.stat(ms["parent library"])
+                    row = {"call": name, "this": n, "parent": p, "difference_ms": round(n["ms"] - p["ms"], 5), "same_poses": same, "within_bar": bool(abs(n["ms"] - p["ms"]) <= 2 * p["spread_ms"]) and same}
+                    ok = ok and row["within_bar"]
+                    res["existing_calls_against_parent"].append(row); print(json.dumps(row), flush=True)
+                pclose()
+            finally:
+                ctx2.close()
+        else:
+            res["existing_calls_against_parent"] = "not measured (no --parent-lib)"
+    finally:
+        ctx.close()
+    return res, ok
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=30)
@@ -57,8 +201,18 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--parent-lib", default=None)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r20_split.json"))
+    ap.add_argument("--model", action="store_true", help="the model split's rows (e)-(g) in place of (a)-(d)")
+    ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    if a.model:
+        res, ok = model_rows(a)
+        a.out = a.out or os.path.join(ROOT, "profiles", "r24_split_model.json")
+        os.makedirs(os.path.dirname(a.out), exist_ok=True)
+        with open(a.out, "w") as f:
+            json.dump(res, f, indent=1)
+        print(json.dumps({"out": a.out, "within_bars": ok}))
+        sys.exit(0 if ok else 1)
+    a.out = a.out or os.path.join(ROOT, "profiles", "r20_split.json")
     z = np.load(os.path.join(ROOT, "bench_data", "frames1024.npz"))
     dev = torch.device("cuda:0")
     s = torch.cuda.Stream(device=dev)
