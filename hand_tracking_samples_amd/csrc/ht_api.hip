@@ -328,7 +328,7 @@ static int cnn_train_host(ht_ctx *ctx, const char *fn, bool batched, ht_net *net
 {
 	{ const int r = cnn_train_check(ctx, fn, batched, net, inputs, targets, n, nullptr, 0, batch); if (r) return r; }
 	ht_seg seg[3] = { { (void *)inputs, (size_t)n * net->dims.in * sizeof(float), false }, { (void *)targets, (size_t)n * HT_CNN_OUT * sizeof(float), false }, { mse_out, (size_t)n * sizeof(float), true } };
-	return ht_staged_call(ctx, &ctx->d_train_io, &ctx->train_io_cap, seg, 3, [&](hipStream_t s)
+	return ht_staged_call(ctx, seg, 3, [&](hipStream_t s)
 	                      { return cnn_train_steps(ctx, batched, *net, (const float *)seg[0].dev, (const float *)seg[1].dev, nullptr, n, batch, alpha, (float *)seg[2].dev, s); });
 }
 // Test aid: the per-sample tensors of the latest mini-batch step of a net (layout: ht_train_batch_views, csrc/ht_train_batch.hip)
@@ -437,7 +437,7 @@ extern "C" int ht_cnn_grad_batch_sized(ht_ctx *ctx, int side, const float *input
 	ht_net *net = ht_net_of(ctx, side);
 	{ const int r = cnn_grad_check(ctx, "ht_cnn_grad_batch_sized", net, inputs, targets, n, nullptr, 1, n, accumulate); if (r) return r; }
 	ht_seg seg[3] = { { (void *)inputs, (size_t)n * net->dims.in * sizeof(float), false }, { (void *)targets, (size_t)n * HT_CNN_OUT * sizeof(float), false }, { mse_out, (size_t)n * sizeof(float), true } };
-	return ht_staged_call(ctx, &ctx->d_train_io, &ctx->train_io_cap, seg, 3, [&](hipStream_t s)
+	return ht_staged_call(ctx, seg, 3, [&](hipStream_t s)
 	                      { return cnn_grad_launch(ctx, *net, (const float *)seg[0].dev, (const float *)seg[1].dev, nullptr, n, accumulate, (float *)seg[2].dev, s); });
 }
 // a float array of the net's size on the device (G, m or v), host <-> device: the length every such call checks, and the upload

@@ -62,7 +62,7 @@ struct ht_ctx
 	std::vector<float> h_bodyc, h_jointc;
 	std::vector<float4> h_verts, h_planes;                        // host copies of the model geometry (ht_scale rewrites them)
 	float *d_train = nullptr;                                    // the per-sample step's training arena (the 64x64-input net only): layer outputs, errors, split-K partial sums (allocated on first use)
-	char *d_train_io = nullptr; size_t train_io_cap = 0;         // ht_cnn_train's and ht_cnn_train_batch's staging (inputs, targets, per-sample MSE), grown to the largest call (dev_grow)
+	char *d_io = nullptr; size_t io_cap = 0;                     // the staging of every synchronous host form (ht_staged_call: inputs up, outputs down), grown to the largest call (dev_grow)
 	float *d_sf_ref = nullptr, *d_sf_crays = nullptr;             // slowfit inputs [B][nb][7], [B][8][4] (allocated on first use)
 	float4 *d_cverts_rw = nullptr;                                // padded copy of the collision vertices (ht_model_dev::cverts)
 	float4 *d_verts_rw = nullptr, *d_planes_rw = nullptr; float *d_bodyc_rw = nullptr, *d_jointc_rw = nullptr;
@@ -105,32 +105,25 @@ struct ht_ctx
 	float *d_user_lin = nullptr; unsigned short *d_user_pos = nullptr; float *d_user_ang = nullptr; int *d_user_n = nullptr;      // [B][lin_cap][HT_ROW], [B][lin_cap], [B][ang_cap][HT_AROW], [4][B]
 	int user_lin_cap = 0, user_ang_cap = 0;
 	ht_comm_state *comm = nullptr;                               // multi-GPU pose gather (ht_comm_init), null on a single-GPU host
-	char *d_render = nullptr; size_t render_cap = 0;             // both renderers' staging (ht_render_depth, ht_render_mesh_depth: poses, cameras, frames, body labels), grown to the largest call (dev_grow)
-	char *d_labels = nullptr; size_t labels_cap = 0;             // ht_expected_cnn_batch's staging (poses, cameras, labels, image points, key angles), grown to the largest call (dev_grow)
-	char *d_segment = nullptr; size_t segment_cap = 0;           // ht_segment_vr's staging (frames, cameras, tiles, segment cameras), grown to the largest call (dev_grow)
-	char *d_sensor = nullptr; size_t sensor_cap = 0;             // ht_sensor_filter's, ht_sensor_background's and ht_sensor_simulate's staging (frames, IR, cameras, background model, output frames), grown to the largest call (dev_grow)
 	std::vector<float4> render_planes; std::vector<float> render_radii;     // the hull planes ht_render_depth last derived its per-body cull radii from, and those radii (2 per body)
 	// ht_render_mesh_depth: the subdivision meshes' corners [t][9] over all bodies (ht_scale rewrites them), the first triangle of every body, the device rows
 	// [t][4] float4 (corners and PolyPlane, ht_mesh_rows) and the farthest corner of every body's mesh from its centre of mass (ht_mesh_upload makes both)
 	std::vector<float> h_mesh_corners, mesh_rad; std::vector<int> mesh_off; float4 *d_mesh = nullptr;
 	float *d_jointl = nullptr;                                   // [nj][HT_JL] the limits of the joint coordinates, made once at model load beside jointc (ht_joint_limits; ht_scale leaves them)
-	char *d_joints = nullptr; size_t joints_cap = 0;             // ht_joint_coords', ht_joint_pose's and ht_sample_poses' staging (poses, roots, coordinates, gaps), grown to the largest call (dev_grow)
-	char *d_mirror = nullptr; size_t mirror_cap = 0;             // the host forms of ht_mirror_frames / _cams / _poses: their staging (input, flags, output), grown to the largest call (dev_grow)
 	// ht_update_hands_*: the mirrored inputs an update of flagged frames runs on, [B][hands_px] pixels, [B][12], [B][nb][7], and the flags of the host form [B]; nothing until the
 	// first flagged call or ht_reserve_hands, then grown to the largest frame (hands_reserve, ht_solver_api.hip: one synchronising re-allocation, never smaller)
 	uint16_t *d_hands_frames = nullptr; size_t hands_px = 0; float *d_hands_cams = nullptr, *d_hands_start = nullptr; unsigned char *d_hands_flags = nullptr;
-	// ht_split_hands (ht_split.hip): the host form's staging, and the label image of a call whose caller wants none (the frames are cut along it), both grown to the largest
-	// call (dev_grow).  ht_update_two_hands_*: its info [B/2][2][8] when the caller wants none, and the flags 0, 1, 0, 1, ... [B] its pose mirrors take (made once)
-	char *d_split = nullptr; size_t split_cap = 0; uint16_t *d_split_labels = nullptr; size_t split_labels_cap = 0;
+	// ht_split_hands (ht_split.hip): the label image of a call whose caller wants none (the frames are cut along it), grown to the largest call (dev_grow).
+	// ht_update_two_hands_*: its info [B/2][2][8] when the caller wants none, and the flags 0, 1, 0, 1, ... [B] its pose mirrors take (made once)
+	uint16_t *d_split_labels = nullptr; size_t split_labels_cap = 0;
 	int32_t *d_two_info = nullptr; unsigned char *d_two_flags = nullptr;
 	// the model split (ht_split_model.hip): the blob split's component counts of a MERGED call whose caller wants none (ht_update_two_hands_model_*: and behind them, from
 	// max_batch / 2, the frames' sources), grown to the largest call (dev_grow)
 	int32_t *d_model_ncomp = nullptr; size_t model_ncomp_cap = 0;
 	// tracking accuracy (ht_quality.hip): the offsets of HT_KP_FEATURE8 [8][3] (handmodelfeaturepoints, handtrack.h:77-81; ht_scale multiplies them as it does the
-	// centres of mass -- HT_KP_SKELETON is read off h_jointc / h_bodyc when asked for); the host forms' staging (dev_grow); ht_pose_depth_residual's render poses
+	// centres of mass -- HT_KP_SKELETON is read off h_jointc / h_bodyc when asked for); ht_pose_depth_residual's render poses
 	// [B][nb][7] and rendered frames [B][h][w], grown to the largest call with one synchronising re-allocation before anything is enqueued (quality_reserve)
 	float kp_feature8[24] = { 0, 0, 0, -0.03f, 0, -0.03f, 0.03f, 0, -0.03f, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0 };
-	char *d_quality = nullptr; size_t quality_cap = 0;
 	float *d_quality_poses = nullptr; size_t quality_poses_cap = 0; uint16_t *d_quality_frames = nullptr; size_t quality_frames_cap = 0;
 };
 
@@ -148,6 +141,9 @@ static inline const char *ht_form_name(const ht_ctx *ctx, const ht_net *net, con
 #define CHECK_READY(ctx) if (!(ctx)) return HT_ERR_ARG; if (!(ctx)->ready) { (ctx)->err = "context not initialised (ht_create failed)"; return HT_ERR_STATE; } ht_device_guard dev_guard_((ctx)->device)
 #define CHECK_MODEL(ctx) do { if ((ctx)->cnn_only) { (ctx)->err = "this context was created without a hand model (CNN only)"; return HT_ERR_STATE; } } while (0)
 #define CHECK_BATCH(ctx, B) do { if ((B) < 1 || (B) > (ctx)->B) { (ctx)->err = "batch exceeds the capacity given to ht_create"; return HT_ERR_ARG; } } while (0)
+// argument checks the entry points share (each composes its own message): whether two byte ranges overlap (a null or empty one overlaps nothing), and a frame's size
+static inline bool ht_ranges_overlap(const void *a, size_t na, const void *b, size_t nb) { return a && b && na && nb && (uintptr_t)a < (uintptr_t)b + nb && (uintptr_t)b < (uintptr_t)a + na; }
+static inline bool ht_frame_dims_ok(int w, int h) { return w >= 1 && h >= 1 && w <= 4096 && h <= 4096; }
 
 // Device memory of a context.  dev_alloc: n elements, listed in `allocs` (ht_destroy frees the list).  drop_alloc: frees one of them now.  dev_grow: a buffer that follows
 // the largest call -- the replacement is allocated FIRST (when that fails the context keeps its old, valid buffer and capacity), then the outgrown one is freed (hipFree
@@ -187,16 +183,18 @@ static inline int ht_sync_check(ht_ctx *ctx, hipStream_t s)
 	return HT_OK;
 }
 
-// A synchronous entry point around its _dev form: the segments laid out 256-aligned in a buffer that follows the largest call (dev_grow), the inputs uploaded,
+// A synchronous entry point around its _dev form: the segments laid out 256-aligned in ctx->d_io, which follows the largest call (dev_grow), the inputs uploaded,
 // call(stream) run on the device pointers, the outputs downloaded, the context's stream waited for.  A segment without a host pointer (an optional output the
 // caller did not ask for) takes no room and keeps a null device pointer.
+// Every host form shares the one buffer.  That is sound because a staged call is synchronous on ctx->stream (nothing reads d_io once it has returned, and hipFree
+// of an outgrown buffer waits for the device), and because no `call` body enters another host form: each runs its own _dev form or enqueue function, which stage nothing.
 struct ht_seg { void *host; size_t bytes; bool out; char *dev; };
-template <class F> static inline int ht_staged_call(ht_ctx *ctx, char **buf, size_t *cap, ht_seg *seg, int n, F call)
+template <class F> static inline int ht_staged_call(ht_ctx *ctx, ht_seg *seg, int n, F call)
 {
 	size_t off[12], end = 0;      // n <= 12
 	for (int i = 0; i < n; i++) { off[i] = (end + 255) & ~(size_t)255; if (seg[i].host) end = off[i] + seg[i].bytes; }
-	{ const int r = dev_grow(ctx, buf, cap, end); if (r) return r; }
-	for (int i = 0; i < n; i++) seg[i].dev = seg[i].host ? *buf + off[i] : nullptr;
+	{ const int r = dev_grow(ctx, &ctx->d_io, &ctx->io_cap, end); if (r) return r; }
+	for (int i = 0; i < n; i++) seg[i].dev = seg[i].host ? ctx->d_io + off[i] : nullptr;
 	hipStream_t s = ctx->stream;
 	for (int i = 0; i < n; i++) if (seg[i].host && !seg[i].out) HIPCHK(ctx, hipMemcpyAsync(seg[i].dev, seg[i].host, seg[i].bytes, hipMemcpyHostToDevice, s));
 	{ const int r = call(s); if (r) return r; }
@@ -217,7 +215,7 @@ struct ht_prof_scope
 static inline size_t ht_scratch_rows(size_t pts_cap, size_t nb) { return pts_cap + 5 * nb + 32 + 7 * 16 + HT_SCRATCH_TAIL; }
 int ht_alloc_buffers(ht_ctx *ctx);
 int ht_mesh_upload(ht_ctx *ctx);             // rows and radii of the model's current subdivision meshes to the device (ht_render_mesh.hip); the caller has waited for the renders in flight
-int ht_alloc_solve_tables(ht_ctx *ctx);      // d_tables alone, once: ht_debug_solve_tables(ctx, 1 or 2), or HT_TABLES in a tuning build (the boundary planes d_chplanes / d_chon are ht_alloc_buffers')
+int ht_alloc_solve_tables(ht_ctx *ctx);      // d_tables and nothing else, once (d_chplanes / d_chon come with ht_alloc_buffers): from ht_debug_solve_tables(ctx, 1 or 2), and from ht_alloc_buffers under HT_TABLES in a tuning build
 int ht_reserve_points_locked(ht_ctx *ctx, int points);      // grows the per-point arrays (ht_api.hip); waits for the context's streams
 // *_dev entry points: a NULL stream means the context's own stream (never the legacy default stream); the choice is remembered so that the
 // host-read helpers (ht_capacity_events, ht_frames_overflow, ht_get_tracker_flags, ...) can wait for work enqueued on a caller's stream

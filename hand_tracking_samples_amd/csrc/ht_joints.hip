@@ -39,8 +39,6 @@ __device__ __forceinline__ jt_tables jt_load_tables(float *lds, const ht_model_d
 	jt_tables t; t.jc = a; t.jl = b; t.com = c;
 	return t;
 }
-__device__ __forceinline__ v3 P3(const float *p) { return V3(p[0], p[1], p[2]); }
-__device__ __forceinline__ v4 P4(const float *p) { return V4(p[0], p[1], p[2], p[3]); }
 __device__ __forceinline__ v4 jt_cb() { return normalize(V4(0, -1, 0, 1)); }
 
 // c = (s.x, s.y, t.z) of a joint, physics.h:358-365
@@ -78,14 +76,14 @@ __global__ __launch_bounds__(JC_THREADS) void k_joint_coords(const ht_model_dev 
 	const float *jc = T.jc + j * HT_JC;
 	const int rb0 = (int)jc[HT_JC_RB0], rb1 = (int)jc[HT_JC_RB1];
 	const float *a = poses + ((size_t)f * nb + rb0) * HT_POSE, *b = poses + ((size_t)f * nb + rb1) * HT_POSE;
-	const v4 q0 = P4(a + 3), q1 = P4(b + 3);
-	const v3 c = jt_coords(q0, q1, P4(jc + HT_JC_FRAME), T.jl[j * HT_JL + HT_JL_SWAPPED] != 0.0f);
+	const v4 q0 = load4(a + 3), q1 = load4(b + 3);
+	const v3 c = jt_coords(q0, q1, load4(jc + HT_JC_FRAME), T.jl[j * HT_JL + HT_JL_SWAPPED] != 0.0f);
 	coords[idx * 3] = c.x; coords[idx * 3 + 1] = c.y; coords[idx * 3 + 2] = c.z;
 	if (gaps)
 	{
-		v3 u0 = P3(a), u1 = P3(b);
-		if (com_poses) { u0 = u0 + qrot(q0, -P3(T.com + rb0 * 3)); u1 = u1 + qrot(q1, -P3(T.com + rb1 * 3)); }      // PositionUser physics.h:142
-		gaps[idx] = length((u0 + qrot(q0, P3(jc + HT_JC_P0))) - (u1 + qrot(q1, P3(jc + HT_JC_P1))));
+		v3 u0 = load3(a), u1 = load3(b);
+		if (com_poses) { u0 = u0 + qrot(q0, -load3(T.com + rb0 * 3)); u1 = u1 + qrot(q1, -load3(T.com + rb1 * 3)); }      // PositionUser physics.h:142
+		gaps[idx] = length((u0 + qrot(q0, load3(jc + HT_JC_P0))) - (u1 + qrot(q1, load3(jc + HT_JC_P1))));
 	}
 }
 
@@ -116,8 +114,8 @@ template <bool SAMPLE> __device__ __forceinline__ void jt_walk(const ht_model_de
 		float *my = ptab + tid * pstride, *myc = ctab + tid * cstride;
 		{
 			const float *r = roots + (size_t)f * HT_POSE;
-			v3 p = P3(r); const v4 q = P4(r + 3);
-			if (com_poses) p = p + qrot(q, -P3(T.com));
+			v3 p = load3(r); const v4 q = load4(r + 3);
+			if (com_poses) p = p + qrot(q, -load3(T.com));
 			my[0] = p.x; my[1] = p.y; my[2] = p.z; my[3] = q.x; my[4] = q.y; my[5] = q.z; my[6] = q.w;
 		}
 		for (int j = 0; j < nj; j++)
@@ -125,8 +123,8 @@ template <bool SAMPLE> __device__ __forceinline__ void jt_walk(const ht_model_de
 			const float *jc = T.jc + j * HT_JC, *l = T.jl + j * HT_JL;
 			const int rb0 = (int)jc[HT_JC_RB0], rb1 = (int)jc[HT_JC_RB1];
 			const float *par = my + rb0 * HT_POSE;
-			const v3 p0 = P3(par); const v4 q0 = P4(par + 3);
-			const v4 F = P4(jc + HT_JC_FRAME); const bool swapped = l[HT_JL_SWAPPED] != 0.0f;
+			const v3 p0 = load3(par); const v4 q0 = load4(par + 3);
+			const v4 F = load4(jc + HT_JC_FRAME); const bool swapped = l[HT_JL_SWAPPED] != 0.0f;
 			v3 c;
 			if (SAMPLE)
 			{
@@ -143,21 +141,21 @@ template <bool SAMPLE> __device__ __forceinline__ void jt_walk(const ht_model_de
 				// (bones b - 2 and b - 1, both placed); the literals 3.14159f and 3.14f are the reference's
 				if (sm.enhanced && j >= 6 && j <= 15 && j % 3 == 0)
 				{
-					const float cs = clamp_std(dot(qzdir(P4(my + (j - 1) * HT_POSE + 3)), qzdir(P4(my + j * HT_POSE + 3))), 0.0f, 1.0f);
+					const float cs = clamp_std(dot(qzdir(load4(my + (j - 1) * HT_POSE + 3)), qzdir(load4(my + j * HT_POSE + 3))), 0.0f, 1.0f);
 					const float deg = (float)(acos((double)cs) * (double)180.0f / (double)3.14159f / (double)2.0f);
 					c.x = sin_f(((deg * 3.14f) / 180.0f) / 2.0f);
 				}
 			}
-			else c = P3(myc + j * 3);
+			else c = load3(myc + j * 3);
 			v4 q1 = jt_child(q0, F, swapped, c);
 			// :434-440: a knuckle (joint 4, 7, 10, 13 of bone 5, 8, 11, 14 on the palm) abducts only while its finger is up; otherwise y is locked at 0: one rebuild
-			if (SAMPLE && sm.enhanced && (j == 4 || j == 7 || j == 10 || j == 13) && !((double)dot(qydir(P4(my + HT_POSE + 3)), qydir(q1)) > sm.cos40))
+			if (SAMPLE && sm.enhanced && (j == 4 || j == 7 || j == 10 || j == 13) && !((double)dot(qydir(load4(my + HT_POSE + 3)), qydir(q1)) > sm.cos40))
 			{
 				c.y = 0.0f;
 				q1 = jt_child(q0, F, swapped, c);
 			}
 			if (SAMPLE) { myc[j * 3] = c.x; myc[j * 3 + 1] = c.y; myc[j * 3 + 2] = c.z; }
-			const v3 p1 = (p0 + qrot(q0, P3(jc + HT_JC_P0))) - qrot(q1, P3(jc + HT_JC_P1));
+			const v3 p1 = (p0 + qrot(q0, load3(jc + HT_JC_P0))) - qrot(q1, load3(jc + HT_JC_P1));
 			float *ch = my + rb1 * HT_POSE;
 			ch[0] = p1.x; ch[1] = p1.y; ch[2] = p1.z; ch[3] = q1.x; ch[4] = q1.y; ch[5] = q1.z; ch[6] = q1.w;
 		}
@@ -165,7 +163,7 @@ template <bool SAMPLE> __device__ __forceinline__ void jt_walk(const ht_model_de
 			for (int b = 0; b < nb; b++)
 			{
 				float *e = my + b * HT_POSE;
-				const v3 p = P3(e) + qrot(P4(e + 3), P3(T.com + b * 3));
+				const v3 p = load3(e) + qrot(load4(e + 3), load3(T.com + b * 3));
 				e[0] = p.x; e[1] = p.y; e[2] = p.z;
 			}
 	}
@@ -296,7 +294,7 @@ extern "C" int ht_joint_coords(ht_ctx *ctx, const float *poses, int B, int flags
 	if (B == 0 || ctx->model.nj == 0) return HT_OK;
 	const size_t n = (size_t)B, nb = ctx->model.nb, nj = ctx->model.nj;
 	ht_seg seg[3] = { { (void *)poses, n * nb * HT_POSE * sizeof(float), false }, { coords, n * nj * 3 * sizeof(float), true }, { gaps, n * nj * sizeof(float), true } };
-	return ht_staged_call(ctx, &ctx->d_joints, &ctx->joints_cap, seg, 3, [&](hipStream_t s)
+	return ht_staged_call(ctx, seg, 3, [&](hipStream_t s)
 	                      { return ht_joint_coords_dev(ctx, (const float *)seg[0].dev, B, flags, (float *)seg[1].dev, (float *)seg[2].dev, s); });
 }
 
@@ -330,7 +328,7 @@ extern "C" int ht_joint_pose(ht_ctx *ctx, const float *roots, const float *coord
 		}
 	}
 	ht_seg seg[3] = { { (void *)roots, n * HT_POSE * sizeof(float), false }, { (void *)coords, n * nj * 3 * sizeof(float), false }, { poses, n * nb * HT_POSE * sizeof(float), true } };
-	return ht_staged_call(ctx, &ctx->d_joints, &ctx->joints_cap, seg, 3, [&](hipStream_t s)
+	return ht_staged_call(ctx, seg, 3, [&](hipStream_t s)
 	                      { return ht_joint_pose_dev(ctx, (const float *)seg[0].dev, (const float *)seg[1].dev, B, flags, (float *)seg[2].dev, s); });
 }
 
@@ -365,6 +363,6 @@ extern "C" int ht_sample_poses(ht_ctx *ctx, const float *roots, int B, uint64_t 
 	if (B == 0) return HT_OK;
 	const size_t n = (size_t)B, nb = ctx->model.nb, nj = ctx->model.nj;
 	ht_seg seg[3] = { { (void *)roots, n * HT_POSE * sizeof(float), false }, { poses, n * nb * HT_POSE * sizeof(float), true }, { coords, n * nj * 3 * sizeof(float), true } };
-	return ht_staged_call(ctx, &ctx->d_joints, &ctx->joints_cap, seg, 3, [&](hipStream_t s)
+	return ht_staged_call(ctx, seg, 3, [&](hipStream_t s)
 	                      { return ht_sample_poses_dev(ctx, (const float *)seg[0].dev, B, seed, first_index, spread, flags, (float *)seg[1].dev, (float *)seg[2].dev, s); });
 }

@@ -143,7 +143,7 @@ extern "C" int ht_expected_cnn_dev(ht_ctx *ctx, const float *d_poses, const floa
 	return HT_OK;
 }
 
-// the synchronous variant stages through one device buffer of its own (ht_staged_call; no tracker slot: B is not bounded by max_batch)
+// the synchronous variant stages through the context's buffer (ht_staged_call; no tracker slot: B is not bounded by max_batch)
 extern "C" int ht_expected_cnn_batch(ht_ctx *ctx, const float *poses, const float *cams, int B, int flags, float *expected, float *image_points, float *vals)
 {
 	CHECK_READY(ctx);
@@ -153,7 +153,7 @@ extern "C" int ht_expected_cnn_batch(ht_ctx *ctx, const float *poses, const floa
 	const size_t n = (size_t)B;
 	ht_seg seg[5] = { { (void *)poses, n * ctx->model.nb * HT_POSE * sizeof(float), false }, { (void *)cams, n * HT_CAM * sizeof(float), false },
 	                  { expected, n * HT_CNN_OUT * sizeof(float), true }, { image_points, n * 16 * sizeof(float), true }, { vals, n * 16 * sizeof(float), true } };
-	return ht_staged_call(ctx, &ctx->d_labels, &ctx->labels_cap, seg, 5, [&](hipStream_t s)
+	return ht_staged_call(ctx, seg, 5, [&](hipStream_t s)
 	                      { return ht_expected_cnn_dev(ctx, (const float *)seg[0].dev, (const float *)seg[1].dev, B, flags, (float *)seg[2].dev, (float *)seg[3].dev, (float *)seg[4].dev, s); });
 }
 

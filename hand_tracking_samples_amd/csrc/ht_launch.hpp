@@ -133,8 +133,7 @@ void ht_joint_limits_public(const float *table, int nj, float *lo, float *hi, in
 bool ht_joints_ordered(const float *jointc, int nb, int nj);
 bool ht_joints_hand_layout(const float *jointc, int nb, int nj);
 // ht_mirror.hip: the mirror x -> -x of frames [B][h][w], cameras [B][12] and poses [B][per_frame][7] where hands[b] != 0 (hands null: everywhere), a copy elsewhere.
-// Frames must not overlap; cameras and poses may be in place.  ht_mirror_frames_pixels: the pixels per load the frame kernel takes for these sizes and pointers (8, 4, 2 or 1)
-int ht_mirror_frames_pixels(const void *in, const void *out, int w);
+// Frames must not overlap; cameras and poses may be in place.
 void ht_launch_mirror_frames(const uint16_t *in, int w, int h, int B, const unsigned char *hands, uint16_t *out, hipStream_t s);
 void ht_launch_mirror_cams(const float *in, int w, int B, const unsigned char *hands, float *out, hipStream_t s);
 void ht_launch_mirror_poses(const float *in, int per_frame, int B, const unsigned char *hands, float *out, hipStream_t s);

@@ -23,6 +23,8 @@ HT_HD v3 V3(float x, float y, float z) { v3 r; r.x = x; r.y = y; r.z = z; return
 HT_HD v4 V4(float x, float y, float z, float w) { v4 r; r.x = x; r.y = y; r.z = z; r.w = w; return r; }
 HT_HD v4 V4(v3 v, float w) { return V4(v.x, v.y, v.z, w); }
 HT_HD v3 xyz(v4 v) { return V3(v.x, v.y, v.z); }
+HT_HD v3 load3(const float *p) { return V3(p[0], p[1], p[2]); }      // three / four consecutive floats (a position, a quaternion xyzw)
+HT_HD v4 load4(const float *p) { return V4(p[0], p[1], p[2], p[3]); }
 
 // std::min / std::max as the reference spells them (argument order matters for NaN)
 HT_HD float fmax_std(float a, float b) { return (a < b) ? b : a; }

@@ -13,18 +13,18 @@
 //                    order, each rotated by 16 bits), one store of the same width at the mirrored place of the same row.  Lane i reads base + 16 i and writes
 //                    rowend - 16 i: both sides of a wave's access are whole contiguous lines, no LDS.  Thread r of blockIdx.x owns vector r of every frame
 //                    blockIdx.y, blockIdx.y + gridDim.y, ...: its row position is worked out once.  The width follows what the call's sizes and pointers allow
-//                    (ht_mirror_frames_pixels): 16 bytes for w % 8 == 0 and 16-byte aligned buffers, 8 for w % 4 == 0 and 8-byte alignment (rows are 8-byte
+//                    (ht_frame_vec_pixels, ht_frame_vec.hpp): 16 bytes for w % 8 == 0 and 16-byte aligned buffers, 8 for w % 4 == 0 and 8-byte alignment (rows are 8-byte
 //                    multiples wherever the update takes a frame), 4, and a pixel-per-thread form (k_mirror_frames<0>) for a buffer aligned to two bytes only
 //                    or an odd width.  No path assumes more alignment than was checked.
 //   k_mirror_cams /  one thread per float, in place or not (every element is read and written by the same thread).
 //   k_mirror_poses
 #include <string.h>
 #include "ht_host.hpp"
+#include "ht_frame_vec.hpp"
 #include "ht_mirror.hpp"
 
 #define MR_THREADS 256
 
-template <int N> struct alignas(4 * N) mr_words { unsigned v[N]; };
 __device__ __forceinline__ bool mr_left(const unsigned char *hands, unsigned f) { return !hands || hands[f] != 0; }
 
 template <int N> __global__ __launch_bounds__(MR_THREADS) void k_mirror_frames(const uint16_t *__restrict__ in, uint16_t *__restrict__ out, unsigned per_row, unsigned per_frame, unsigned B,
@@ -33,15 +33,16 @@ template <int N> __global__ __launch_bounds__(MR_THREADS) void k_mirror_frames(c
 	const unsigned r = blockIdx.x * MR_THREADS + threadIdx.x;
 	if (r >= per_frame) return;
 	const unsigned xv = r % per_row, rm = r - xv + (per_row - 1u - xv);      // the same row, counted from its other end
-	const mr_words<N> *src = (const mr_words<N> *)in; mr_words<N> *dst = (mr_words<N> *)out;
+	const ht_dwords<N> *src = (const ht_dwords<N> *)in; ht_dwords<N> *dst = (ht_dwords<N> *)out;
 	for (unsigned f = blockIdx.y; f < B; f += gridDim.y)
 	{
 		const bool left = mr_left(hands, f);
 		const size_t base = (size_t)f * per_frame;
-		const mr_words<N> a = src[base + r];
-		mr_words<N> o;
+		const ht_dwords<N> a = src[base + r];
+		ht_dwords<N> m, o;
+		ht_reverse(a, m);
 #pragma unroll
-		for (int i = 0; i < N; i++) { const unsigned d = a.v[N - 1 - i]; o.v[i] = left ? (d >> 16) | (d << 16) : a.v[i]; }
+		for (int i = 0; i < N; i++) o.v[i] = left ? m.v[i] : a.v[i];
 		dst[base + (left ? rm : r)] = o;
 	}
 }
@@ -81,32 +82,13 @@ __global__ __launch_bounds__(MR_THREADS) void k_mirror_poses(const unsigned *in,
 }
 
 // ---- launch layer ----------------------------------------------------------------------------------------------------------------------------------------------
-int ht_mirror_frames_pixels(const void *in, const void *out, int w)
-{
-	const uintptr_t a = (uintptr_t)in | (uintptr_t)out;
-	if (w % 8 == 0 && (a & 15) == 0) return 8;
-	if (w % 4 == 0 && (a & 7) == 0) return 4;
-	if (w % 2 == 0 && (a & 3) == 0) return 2;
-	return 1;
-}
-template <int N> static void mirror_frames_launch(const uint16_t *in, int w, int h, int B, const unsigned char *hands, uint16_t *out, hipStream_t s)
-{
-	const unsigned px = N ? 2 * N : 1, per_row = (unsigned)w / px, per_frame = per_row * (unsigned)h;
-	const unsigned gx = (per_frame + MR_THREADS - 1) / MR_THREADS;
-	unsigned gy = (2048 + gx - 1) / gx;      // about eight blocks a CU; a thread then walks the frames blockIdx.y, blockIdx.y + gridDim.y, ...
-	if (gy > (unsigned)B) gy = (unsigned)B;
-	if (gy > 65535u) gy = 65535u;
-	hipLaunchKernelGGL(k_mirror_frames<N>, dim3(gx, gy), dim3(MR_THREADS), 0, s, in, out, per_row, per_frame, (unsigned)B, hands);
-}
 void ht_launch_mirror_frames(const uint16_t *in, int w, int h, int B, const unsigned char *hands, uint16_t *out, hipStream_t s)
 {
-	switch (ht_mirror_frames_pixels(in, out, w))
+	ht_frame_vec_dispatch(ht_frame_vec_pixels((uintptr_t)in | (uintptr_t)out, w), [&](auto px)
 	{
-	case 8: mirror_frames_launch<4>(in, w, h, B, hands, out, s); break;
-	case 4: mirror_frames_launch<2>(in, w, h, B, hands, out, s); break;
-	case 2: mirror_frames_launch<1>(in, w, h, B, hands, out, s); break;
-	default: mirror_frames_launch<0>(in, w, h, B, hands, out, s); break;
-	}
+		const ht_frame_grid g(w, h, B, px, MR_THREADS);
+		hipLaunchKernelGGL(k_mirror_frames<px / 2>, g.grid, dim3(MR_THREADS), 0, s, in, out, g.per_row, g.per_frame, (unsigned)B, hands);
+	});
 }
 void ht_launch_mirror_cams(const float *in, int w, int B, const unsigned char *hands, float *out, hipStream_t s)
 {
@@ -121,14 +103,12 @@ void ht_launch_mirror_poses(const float *in, int per_frame, int B, const unsigne
 
 // ---- C ABI -----------------------------------------------------------------------------------------------------------------------------------------------------
 // Every check runs before anything grows or launches.  B is not bounded by max_batch: no tracker slot is used.
-#define MR_MAX_DIM 4096
 static int mr_check_frames(ht_ctx *ctx, const void *in, const void *out, int w, int h, int B)
 {
 	if (!in || !out || B < 0) { ctx->err = "ht_mirror_frames: bad argument"; return HT_ERR_ARG; }
-	if (w < 1 || h < 1 || w > MR_MAX_DIM || h > MR_MAX_DIM) { ctx->err = "ht_mirror_frames: w and h between 1 and 4096"; return HT_ERR_ARG; }
+	if (!ht_frame_dims_ok(w, h)) { ctx->err = "ht_mirror_frames: w and h between 1 and 4096"; return HT_ERR_ARG; }
 	const size_t bytes = (size_t)B * w * h * sizeof(uint16_t);
-	const uintptr_t a = (uintptr_t)in, b = (uintptr_t)out;
-	if (a < b + bytes && b < a + bytes) { ctx->err = "ht_mirror_frames: the frames are not mirrored in place: depth and depth_out must not overlap"; return HT_ERR_ARG; }
+	if (ht_ranges_overlap(in, bytes, out, bytes)) { ctx->err = "ht_mirror_frames: the frames are not mirrored in place: depth and depth_out must not overlap"; return HT_ERR_ARG; }
 	return HT_OK;
 }
 static int mr_check_floats(ht_ctx *ctx, const char *fn, const void *in, const void *out, long long B, long long per)
@@ -151,7 +131,7 @@ extern "C" int ht_mirror_cams_dev(ht_ctx *ctx, const float *d_cams, int w, int B
 {
 	CHECK_READY(ctx);
 	{ const int r = mr_check_floats(ctx, "ht_mirror_cams", d_cams, d_cams_out, B, HT_CAM); if (r) return r; }
-	if (w < 1 || w > MR_MAX_DIM) { ctx->err = "ht_mirror_cams: w between 1 and 4096"; return HT_ERR_ARG; }
+	if (!ht_frame_dims_ok(w, 1)) { ctx->err = "ht_mirror_cams: w between 1 and 4096"; return HT_ERR_ARG; }
 	if (B == 0) return HT_OK;
 	hipStream_t s = ht_user_stream(ctx, stream);
 	{ ht_prof_scope ps(ctx, "k_mirror_cams", s); ht_launch_mirror_cams(d_cams, w, B, d_hands, d_cams_out, s); }
@@ -177,18 +157,18 @@ extern "C" int ht_mirror_frames(ht_ctx *ctx, const uint16_t *depth, int w, int h
 	if (B == 0) return HT_OK;
 	const size_t bytes = (size_t)B * w * h * sizeof(uint16_t);
 	ht_seg seg[3] = { { (void *)depth, bytes, false }, { (void *)hands, (size_t)B, false }, { depth_out, bytes, true } };
-	return ht_staged_call(ctx, &ctx->d_mirror, &ctx->mirror_cap, seg, 3, [&](hipStream_t s)
+	return ht_staged_call(ctx, seg, 3, [&](hipStream_t s)
 	                      { return ht_mirror_frames_dev(ctx, (const uint16_t *)seg[0].dev, w, h, B, (const unsigned char *)seg[1].dev, (uint16_t *)seg[2].dev, s); });
 }
 extern "C" int ht_mirror_cams(ht_ctx *ctx, const float *cams, int w, int B, const unsigned char *hands, float *cams_out)
 {
 	CHECK_READY(ctx);
 	{ const int r = mr_check_floats(ctx, "ht_mirror_cams", cams, cams_out, B, HT_CAM); if (r) return r; }
-	if (w < 1 || w > MR_MAX_DIM) { ctx->err = "ht_mirror_cams: w between 1 and 4096"; return HT_ERR_ARG; }
+	if (!ht_frame_dims_ok(w, 1)) { ctx->err = "ht_mirror_cams: w between 1 and 4096"; return HT_ERR_ARG; }
 	if (B == 0) return HT_OK;
 	const size_t bytes = (size_t)B * HT_CAM * sizeof(float);
 	ht_seg seg[3] = { { (void *)cams, bytes, false }, { (void *)hands, (size_t)B, false }, { cams_out, bytes, true } };
-	return ht_staged_call(ctx, &ctx->d_mirror, &ctx->mirror_cap, seg, 3, [&](hipStream_t s)
+	return ht_staged_call(ctx, seg, 3, [&](hipStream_t s)
 	                      { return ht_mirror_cams_dev(ctx, (const float *)seg[0].dev, w, B, (const unsigned char *)seg[1].dev, (float *)seg[2].dev, s); });
 }
 extern "C" int ht_mirror_poses(ht_ctx *ctx, const float *poses, int per_frame, int B, const unsigned char *hands, float *poses_out)
@@ -198,6 +178,6 @@ extern "C" int ht_mirror_poses(ht_ctx *ctx, const float *poses, int per_frame, i
 	if (B == 0) return HT_OK;
 	const size_t bytes = (size_t)B * per_frame * HT_POSE * sizeof(float);
 	ht_seg seg[3] = { { (void *)poses, bytes, false }, { (void *)hands, (size_t)B, false }, { poses_out, bytes, true } };
-	return ht_staged_call(ctx, &ctx->d_mirror, &ctx->mirror_cap, seg, 3, [&](hipStream_t s)
+	return ht_staged_call(ctx, seg, 3, [&](hipStream_t s)
 	                      { return ht_mirror_poses_dev(ctx, (const float *)seg[0].dev, per_frame, B, (const unsigned char *)seg[1].dev, (float *)seg[2].dev, s); });
 }

@@ -17,23 +17,20 @@
 //   k_kp_errors         one block per 256 frames, one thread per frame walks the keypoints in order (the ordered fp32 mean).  Per keypoint a wave adds its lanes'
 //                       distances in double (__shfl) and counts the hits per threshold (__ballot); each wave leaves its partials in its own LDS row, the block adds
 //                       the rows in a fixed order and issues one atomicAdd per quantity into the summary, which the call zeroes first (hipMemsetAsync).
-//   k_depth_compare<N>  grid (chunks of a frame, frames).  One thread takes N dwords = 2N pixels of both inputs per load (16 / 8 / 4 bytes by ht_mirror_frames_pixels'
-//                       rule on the width and both pointers; <0>: single pixels), about four loads of each input per thread.  Counters in registers (32-bit counts, 64-bit
+//   k_depth_compare<N>  grid (chunks of a frame, frames).  One thread takes N dwords = 2N pixels of both inputs per load (16 / 8 / 4 bytes by the one width rule, ht_frame_vec_pixels,
+//                       on the width and both pointers; <0>: single pixels), about four loads of each input per thread.  Counters in registers (32-bit counts, 64-bit
 //                       sums), wave reduction by __shfl_xor, the four waves through LDS, then one 64-bit atomicAdd / atomicMax per quantity per block into info
 //                       (zeroed first).  Integers: exact and order-free.
 //   k_pose_to_render    one thread per (frame, body): user pose -> centre-of-mass pose -> the camera's frame (skipped for a camera whose pose is the identity bit for bit).
 #include <string.h>
 #include <math.h>
 #include "ht_host.hpp"
+#include "ht_frame_vec.hpp"
 
 #define QL_THREADS 256
-#define QL_MAX_DIM 4096
 
 struct ql_table { int K; unsigned char bone[HT_KP_MAX], rel[HT_KP_MAX]; float off[HT_KP_MAX * 3]; };
 struct ql_thr { int T; float v[HT_KP_MAX_THR]; };
-
-__device__ __forceinline__ v3 ql3(const float *p) { return V3(p[0], p[1], p[2]); }
-__device__ __forceinline__ v4 ql4(const float *p) { return V4(p[0], p[1], p[2], p[3]); }
 
 // ---- keypoints ---------------------------------------------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(QL_THREADS) void k_keypoints(const ht_model_dev M, const ql_table T, const float *__restrict__ poses, long long n, int com_poses, const unsigned char *__restrict__ hands,
@@ -46,8 +43,8 @@ __global__ __launch_bounds__(QL_THREADS) void k_keypoints(const ht_model_dev M, 
 	for (int i = threadIdx.x; i < K; i += QL_THREADS)
 	{
 		const int b = T.bone[i];
-		const v3 com = ql3(M.bodyc + b * HT_BC + HT_BC_COM);
-		v3 o = ql3(T.off + 3 * i);
+		const v3 com = load3(M.bodyc + b * HT_BC + HT_BC_COM);
+		v3 o = load3(T.off + 3 * i);
 		if (T.rel[i] && !com_poses) o = o + com; else if (!T.rel[i] && com_poses) o = o - com;
 		s_off[3 * i] = o.x; s_off[3 * i + 1] = o.y; s_off[3 * i + 2] = o.z; s_bone[i] = b;
 	}
@@ -55,14 +52,14 @@ __global__ __launch_bounds__(QL_THREADS) void k_keypoints(const ht_model_dev M, 
 	const long long idx = (long long)blockIdx.x * QL_THREADS + threadIdx.x;
 	if (idx >= n) return;
 	const long long f = idx / K; const int k = (int)(idx - f * K);
-	v3 o = ql3(s_off + 3 * k);
+	v3 o = load3(s_off + 3 * k);
 	if (hands && hands[f]) o.x = __uint_as_float(__float_as_uint(o.x) ^ 0x80000000u);
 	const float *p = poses + ((size_t)f * nb + s_bone[k]) * HT_POSE;
-	const v3 X = ql3(p) + qrot(ql4(p + 3), o);
+	const v3 X = load3(p) + qrot(load4(p + 3), o);
 	if (xyz) { xyz[idx * 3] = X.x; xyz[idx * 3 + 1] = X.y; xyz[idx * 3 + 2] = X.z; }
 	if (!cams) return;
 	const float *cam = cams + (size_t)f * HT_CAM;
-	const v3 v = qrot(qconj(ql4(cam + 8)), X - ql3(cam + 5));
+	const v3 v = qrot(qconj(load4(cam + 8)), X - load3(cam + 5));
 	const float u0 = v.x / v.z * cam[0] + cam[2], u1 = v.y / v.z * cam[1] + cam[3];
 	if (pix) { pix[idx * 2] = u0; pix[idx * 2 + 1] = u1; }
 	if (zc) zc[idx] = v.z;
@@ -129,7 +126,6 @@ __global__ __launch_bounds__(QL_THREADS) void k_kp_errors(const float *__restric
 }
 
 // ---- depth comparison --------------------------------------------------------------------------------------------------------------------------------------------
-template <int N> struct alignas(4 * N) ql_words { unsigned v[N]; };
 struct ql_acc { unsigned na, nb, both, close, mx; unsigned long long sabs, ssq; };
 __device__ __forceinline__ void ql_pixel(ql_acc &c, unsigned pa, unsigned pb, unsigned lo, unsigned hi, unsigned tol)
 {
@@ -169,11 +165,11 @@ template <int N> __global__ __launch_bounds__(QL_THREADS) void k_depth_compare(c
                                                                                unsigned long long *__restrict__ info)
 {
 	const size_t base = (size_t)blockIdx.y * per_frame;
-	const ql_words<N> *A = (const ql_words<N> *)a + base, *Bv = (const ql_words<N> *)b + base;
+	const ht_dwords<N> *A = (const ht_dwords<N> *)a + base, *Bv = (const ht_dwords<N> *)b + base;
 	ql_acc c = { 0u, 0u, 0u, 0u, 0u, 0ull, 0ull };
 	for (unsigned r = blockIdx.x * QL_THREADS + threadIdx.x; r < per_frame; r += gridDim.x * QL_THREADS)
 	{
-		const ql_words<N> x = A[r], y = Bv[r];
+		const ht_dwords<N> x = A[r], y = Bv[r];
 #pragma unroll
 		for (int i = 0; i < N; i++) { ql_pixel(c, x.v[i] & 0xFFFFu, y.v[i] & 0xFFFFu, lo, hi, tol); ql_pixel(c, x.v[i] >> 16, y.v[i] >> 16, lo, hi, tol); }
 	}
@@ -195,14 +191,14 @@ __global__ __launch_bounds__(QL_THREADS) void k_pose_to_render(const ht_model_de
 	if (idx >= n) return;
 	const long long f = idx / M.nb; const int b = (int)(idx - f * M.nb);
 	const float *p = poses + idx * HT_POSE, *cam = cams + f * HT_CAM;
-	v3 pos = ql3(p); v4 q = ql4(p + 3);
-	if (!com_poses) pos = pos + qrot(q, ql3(M.bodyc + b * HT_BC + HT_BC_COM));
+	v3 pos = load3(p); v4 q = load4(p + 3);
+	if (!com_poses) pos = pos + qrot(q, load3(M.bodyc + b * HT_BC + HT_BC_COM));
 	const unsigned *cw = (const unsigned *)cam + 5;
 	const bool ident = (cw[0] | cw[1] | cw[2] | cw[3] | cw[4] | cw[5]) == 0u && cw[6] == 0x3F800000u;
 	if (!ident)
 	{
-		const v4 qi = qconj(ql4(cam + 8));
-		pos = qrot(qi, pos - ql3(cam + 5));
+		const v4 qi = qconj(load4(cam + 8));
+		pos = qrot(qi, pos - load3(cam + 5));
 		q = qmul(qi, q);
 	}
 	float *o = out + idx * HT_POSE;
@@ -258,15 +254,14 @@ static int ql_table_of(ht_ctx *ctx, const char *fn, int which, int K, const int 
 	}
 	return HT_OK;
 }
-static bool ql_overlap(const void *a, size_t na, const void *b, size_t nb) { return a && b && na && nb && (uintptr_t)a < (uintptr_t)b + nb && (uintptr_t)b < (uintptr_t)a + na; }
 struct ql_buf { const void *p; size_t bytes; };
 // whether any of the outputs overlaps an input or another output (the host forms can see that)
 static bool ql_any_overlap(const ql_buf *in, int nin, const ql_buf *out, int nout)
 {
 	for (int o = 0; o < nout; o++)
 	{
-		for (int i = 0; i < nin; i++) if (ql_overlap(in[i].p, in[i].bytes, out[o].p, out[o].bytes)) return true;
-		for (int i = o + 1; i < nout; i++) if (ql_overlap(out[i].p, out[i].bytes, out[o].p, out[o].bytes)) return true;
+		for (int i = 0; i < nin; i++) if (ht_ranges_overlap(in[i].p, in[i].bytes, out[o].p, out[o].bytes)) return true;
+		for (int i = o + 1; i < nout; i++) if (ht_ranges_overlap(out[i].p, out[i].bytes, out[o].p, out[o].bytes)) return true;
 	}
 	return false;
 }
@@ -299,7 +294,7 @@ static int kp_check(ht_ctx *ctx, const void *poses, int B, int flags, int which,
 	if (vis)
 	{
 		if (!depth) { ctx->err = "ht_keypoints: vis needs depth"; return HT_ERR_ARG; }
-		if (w < 1 || h < 1 || w > QL_MAX_DIM || h > QL_MAX_DIM) { ctx->err = "ht_keypoints: w and h between 1 and 4096"; return HT_ERR_ARG; }
+		if (!ht_frame_dims_ok(w, h)) { ctx->err = "ht_keypoints: w and h between 1 and 4096"; return HT_ERR_ARG; }
 		if (!(isfinite(near_tol) && isfinite(far_tol) && near_tol >= 0.0f && far_tol >= 0.0f)) { ctx->err = "ht_keypoints: near_tol and far_tol must be finite and not negative"; return HT_ERR_ARG; }
 	}
 	return HT_OK;
@@ -338,7 +333,7 @@ extern "C" int ht_keypoints(ht_ctx *ctx, const float *poses, int B, int flags, i
 	if (B == 0) return HT_OK;
 	ht_seg seg[8] = { { (void *)in[0].p, in[0].bytes, false }, { (void *)hands, n, false }, { (void *)cams, in[2].bytes, false }, { (void *)(vis ? depth : nullptr), in[3].bytes, false },
 	                  { xyz, out[0].bytes, true }, { pix, out[1].bytes, true }, { zc, out[2].bytes, true }, { vis, out[3].bytes, true } };
-	return ht_staged_call(ctx, &ctx->d_quality, &ctx->quality_cap, seg, 8, [&](hipStream_t s)
+	return ht_staged_call(ctx, seg, 8, [&](hipStream_t s)
 	                      {
 		                      kp_launch(ctx, t, (const float *)seg[0].dev, B, flags, (const uint8_t *)seg[1].dev, (const float *)seg[2].dev, (const uint16_t *)seg[3].dev, w, h, near_tol, far_tol,
 		                                (float *)seg[4].dev, (float *)seg[5].dev, (float *)seg[6].dev, (uint8_t *)seg[7].dev, s);
@@ -390,7 +385,7 @@ extern "C" int ht_keypoint_errors(ht_ctx *ctx, const float *a, const float *b, i
 	if (B == 0) return HT_OK;
 	ht_seg seg[7] = { { (void *)a, in[0].bytes, false }, { (void *)b, in[1].bytes, false }, { dist, out[0].bytes, true }, { frame, out[1].bytes, true }, { sum_kp, out[2].bytes, true },
 	                  { T ? hits_kp : nullptr, out[3].bytes, true }, { T ? hits_frame : nullptr, out[4].bytes, true } };
-	return ht_staged_call(ctx, &ctx->d_quality, &ctx->quality_cap, seg, 7, [&](hipStream_t s)
+	return ht_staged_call(ctx, seg, 7, [&](hipStream_t s)
 	                      { return ke_enqueue(ctx, (const float *)seg[0].dev, (const float *)seg[1].dev, B, K, th, (float *)seg[2].dev, (float *)seg[3].dev, (double *)seg[4].dev, (int64_t *)seg[5].dev, (int64_t *)seg[6].dev, s); });
 }
 
@@ -398,33 +393,27 @@ static int dc_check(ht_ctx *ctx, const char *fn, const void *a, const void *b, c
 {
 	const std::string f(fn);
 	if (!a || !b || !info || B < 0) { ctx->err = f + ": bad argument"; return HT_ERR_ARG; }
-	if (w < 1 || h < 1 || w > QL_MAX_DIM || h > QL_MAX_DIM) { ctx->err = f + ": w and h between 1 and 4096"; return HT_ERR_ARG; }
+	if (!ht_frame_dims_ok(w, h)) { ctx->err = f + ": w and h between 1 and 4096"; return HT_ERR_ARG; }
 	if (lo < 0 || hi > 65536 || lo >= hi) { ctx->err = f + ": the foreground range is 0 <= lo < hi <= 65536"; return HT_ERR_ARG; }
 	if (tol < 0 || tol > 65535) { ctx->err = f + ": tol between 0 and 65535"; return HT_ERR_ARG; }
 	return HT_OK;
-}
-template <int N> static void dc_launch(const uint16_t *a, const uint16_t *b, int w, int h, int B, unsigned lo, unsigned hi, unsigned tol, int64_t *info, hipStream_t s)
-{
-	const unsigned px = N ? 2 * N : 1, per_frame = ((unsigned)w / px) * (unsigned)h;
-	const unsigned gx = (per_frame + 4 * QL_THREADS - 1) / (4 * QL_THREADS);      // about four loads of each input per thread
-	for (int f0 = 0; f0 < B; f0 += 65535)      // blockIdx.y is the frame
-	{
-		const unsigned nf = (unsigned)(B - f0 < 65535 ? B - f0 : 65535);
-		const size_t off = (size_t)f0 * w * h;
-		hipLaunchKernelGGL(k_depth_compare<N>, dim3(gx, nf), dim3(QL_THREADS), 0, s, a + off, b + off, per_frame, lo, hi, tol, (unsigned long long *)info + (size_t)f0 * 8);
-	}
 }
 static int dc_enqueue(ht_ctx *ctx, const uint16_t *d_a, const uint16_t *d_b, int w, int h, int B, int lo, int hi, int tol, int64_t *d_info, hipStream_t s)
 {
 	HIPCHK(ctx, hipMemsetAsync(d_info, 0, (size_t)B * 8 * sizeof(int64_t), s));
 	ht_prof_scope ps(ctx, "k_depth_compare", s);
-	switch (ht_mirror_frames_pixels(d_a, d_b, w))      // the same rule as the mirror kernel's, on both inputs: frame f starts f * w * h pixels in
+	ht_frame_vec_dispatch(ht_frame_vec_pixels((uintptr_t)d_a | (uintptr_t)d_b, w), [&](auto px)      // both inputs are loaded
 	{
-	case 8: dc_launch<4>(d_a, d_b, w, h, B, lo, hi, tol, d_info, s); break;
-	case 4: dc_launch<2>(d_a, d_b, w, h, B, lo, hi, tol, d_info, s); break;
-	case 2: dc_launch<1>(d_a, d_b, w, h, B, lo, hi, tol, d_info, s); break;
-	default: dc_launch<0>(d_a, d_b, w, h, B, lo, hi, tol, d_info, s); break;
-	}
+		const unsigned per_frame = ((unsigned)w / px) * (unsigned)h;
+		const unsigned gx = (per_frame + 4 * QL_THREADS - 1) / (4 * QL_THREADS);      // about four loads of each input per thread
+		for (int f0 = 0; f0 < B; f0 += 65535)      // blockIdx.y is the frame
+		{
+			const unsigned nf = (unsigned)(B - f0 < 65535 ? B - f0 : 65535);
+			const size_t off = (size_t)f0 * w * h;
+			hipLaunchKernelGGL(k_depth_compare<px / 2>, dim3(gx, nf), dim3(QL_THREADS), 0, s, d_a + off, d_b + off, per_frame, (unsigned)lo, (unsigned)hi, (unsigned)tol,
+			                   (unsigned long long *)d_info + (size_t)f0 * 8);
+		}
+	});
 	HIPCHK(ctx, hipGetLastError());
 	return HT_OK;
 }
@@ -440,10 +429,10 @@ extern "C" int ht_depth_compare(ht_ctx *ctx, const uint16_t *a, const uint16_t *
 	CHECK_READY(ctx);
 	{ const int r = dc_check(ctx, "ht_depth_compare", a, b, info, w, h, B, lo, hi, tol); if (r) return r; }
 	const size_t bytes = (size_t)B * w * h * sizeof(uint16_t), ib = (size_t)B * 8 * sizeof(int64_t);
-	if (ql_overlap(a, bytes, info, ib) || ql_overlap(b, bytes, info, ib)) { ctx->err = "ht_depth_compare: info overlaps a frame"; return HT_ERR_ARG; }
+	if (ht_ranges_overlap(a, bytes, info, ib) || ht_ranges_overlap(b, bytes, info, ib)) { ctx->err = "ht_depth_compare: info overlaps a frame"; return HT_ERR_ARG; }
 	if (B == 0) return HT_OK;
 	ht_seg seg[3] = { { (void *)a, bytes, false }, { (void *)b, bytes, false }, { info, ib, true } };
-	return ht_staged_call(ctx, &ctx->d_quality, &ctx->quality_cap, seg, 3, [&](hipStream_t s)
+	return ht_staged_call(ctx, seg, 3, [&](hipStream_t s)
 	                      { return dc_enqueue(ctx, (const uint16_t *)seg[0].dev, (const uint16_t *)seg[1].dev, w, h, B, lo, hi, tol, (int64_t *)seg[2].dev, s); });
 }
 
@@ -497,6 +486,6 @@ extern "C" int ht_pose_depth_residual(ht_ctx *ctx, const float *poses, const flo
 	if (B == 0) return HT_OK;
 	{ const int r = quality_reserve(ctx, n * ctx->model.nb * HT_POSE, rendered ? 0 : n * w * h); if (r) return r; }
 	ht_seg seg[5] = { { (void *)poses, in[0].bytes, false }, { (void *)cams, in[1].bytes, false }, { (void *)depth, bytes, false }, { info, out[0].bytes, true }, { rendered, bytes, true } };
-	return ht_staged_call(ctx, &ctx->d_quality, &ctx->quality_cap, seg, 5, [&](hipStream_t s)
+	return ht_staged_call(ctx, seg, 5, [&](hipStream_t s)
 	                      { return pr_enqueue(ctx, (const float *)seg[0].dev, (const float *)seg[1].dev, (const uint16_t *)seg[2].dev, w, h, B, flags, far, lo, hi, tol, (int64_t *)seg[3].dev, (uint16_t *)seg[4].dev, s); });
 }

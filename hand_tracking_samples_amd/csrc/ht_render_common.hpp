@@ -105,17 +105,17 @@ template <class F> static inline void rc_launch_frames(int w, int h, int B, F la
 // the checks both entries of a renderer share; off_ok: the mesh renderer's pixel offset lies in [0, 1]
 static inline int rc_check_args(ht_ctx *ctx, const char *name, const void *poses, const void *cams, const void *depth, int w, int h, float far, int B, bool off_ok = true)
 {
-	if (!poses || !cams || !depth || w < 1 || h < 1 || w > 4096 || h > 4096 || !(far > 0.0f) || !off_ok || B < 0) { ctx->err = std::string(name) + ": bad argument"; return HT_ERR_ARG; }
+	if (!poses || !cams || !depth || !ht_frame_dims_ok(w, h) || !(far > 0.0f) || !off_ok || B < 0) { ctx->err = std::string(name) + ": bad argument"; return HT_ERR_ARG; }
 	CHECK_MODEL(ctx);
 	return HT_OK;
 }
 
-// A renderer's synchronous entry: poses, cameras, frames and labels staged through ctx->d_render, which both renderers share (each call is synchronous on
-// the context's stream; the renderers use no tracker slot, so B is not bounded by max_batch).  dev(d_poses, d_cams, d_depth, d_body, stream) is its _dev entry.
+// A renderer's synchronous entry: poses, cameras, frames and labels staged through the context's buffer (ht_staged_call; the renderers use no tracker slot, so B
+// is not bounded by max_batch).  dev(d_poses, d_cams, d_depth, d_body, stream) is its _dev entry.
 template <class F> static inline int rc_render_sync(ht_ctx *ctx, const float *poses, const float *cams, int w, int h, int B, uint16_t *depth, int8_t *body, F dev)
 {
 	const size_t nb = (size_t)ctx->model.nb, npx = (size_t)B * w * h;
 	ht_seg seg[4] = { { (void *)poses, (size_t)B * nb * HT_POSE * sizeof(float), false }, { (void *)cams, (size_t)B * HT_CAM * sizeof(float), false },
 	                  { depth, npx * sizeof(uint16_t), true }, { body, npx, true } };
-	return ht_staged_call(ctx, &ctx->d_render, &ctx->render_cap, seg, 4, [&](hipStream_t s) { return dev((const float *)seg[0].dev, (const float *)seg[1].dev, (uint16_t *)seg[2].dev, (int8_t *)seg[3].dev, s); });
+	return ht_staged_call(ctx, seg, 4, [&](hipStream_t s) { return dev((const float *)seg[0].dev, (const float *)seg[1].dev, (uint16_t *)seg[2].dev, (int8_t *)seg[3].dev, s); });
 }

@@ -26,6 +26,7 @@
 #include <string.h>
 #include "ht_device.hpp"
 #include "ht_host.hpp"
+#include "ht_frame_vec.hpp"
 #include "ht_mix.hpp"
 
 #define SN_DARK 4096            // what a dropped pixel becomes (dcam.h:186,196,203), and what the background model starts at (:159)
@@ -156,7 +157,7 @@ __global__ __launch_bounds__(64) void k_sensor_ds4(const uint16_t *__restrict__ 
 // k halvings until w >> k <= max_width, and every refusal that needs no context
 static int sn_dims(int kind, int w, int h, int max_width, int *k_out, int *w_out, int *h_out)
 {
-	if ((kind != HT_SENSOR_IVY && kind != HT_SENSOR_DS4) || w < 1 || h < 1 || w > 4096 || h > 4096 || max_width < 1) return HT_ERR_ARG;
+	if ((kind != HT_SENSOR_IVY && kind != HT_SENSOR_DS4) || !ht_frame_dims_ok(w, h) || max_width < 1) return HT_ERR_ARG;
 	int k = 0;
 	while ((w >> k) > max_width) k++;
 	if (kind == HT_SENSOR_DS4 && k > 0) return HT_ERR_ARG;      // the reference indexes the full-size frame with an IR image it has already halved (dcam.h:170-171,184)
@@ -172,11 +173,6 @@ extern "C" int ht_sensor_out_dims(int kind, int w, int h, int max_width, int *w_
 	return sn_dims(kind, w, h, max_width, nullptr, w_out, h_out);
 }
 
-static inline bool sn_overlap(const void *a, size_t na, const void *b, size_t nb)
-{
-	const uintptr_t p = (uintptr_t)a, q = (uintptr_t)b;
-	return p < q + nb && q < p + na;
-}
 // the checks both forms of the filter share, all made before anything is launched or grown
 static int sn_check_filter(ht_ctx *ctx, int kind, const void *depth, const void *ir, const void *cams, int w, int h, int B, int max_width, const void *background,
                            const void *depth_out, const void *cams_out, int *k, int *wo, int *ho)
@@ -187,7 +183,7 @@ static int sn_check_filter(ht_ctx *ctx, int kind, const void *depth, const void 
 	else if (!depth || !cams || !depth_out || !cams_out) bad = "a NULL buffer";
 	else if (kind == HT_SENSOR_DS4 && !ir) bad = "DS4 needs the IR image";
 	else if (kind == HT_SENSOR_IVY && background) bad = "FilterIvy has no background model";
-	else if (sn_overlap(depth, (size_t)B * w * h * sizeof(uint16_t), depth_out, (size_t)B * *wo * *ho * sizeof(uint16_t))) bad = "depth_out aliases depth";
+	else if (ht_ranges_overlap(depth, (size_t)B * w * h * sizeof(uint16_t), depth_out, (size_t)B * *wo * *ho * sizeof(uint16_t))) bad = "depth_out aliases depth";
 	if (bad) { ctx->err = std::string("ht_sensor_filter: bad argument (") + bad + ")"; return HT_ERR_ARG; }
 	return HT_OK;
 }
@@ -226,17 +222,17 @@ extern "C" int ht_sensor_filter(ht_ctx *ctx, int kind, const uint16_t *depth, co
 	int k, wo, ho;
 	{ const int r = sn_check_filter(ctx, kind, depth, ir, cams, w, h, B, max_width, background, depth_out, cams_out, &k, &wo, &ho); if (r) return r; }
 	if (B == 0) return HT_OK;
-	const size_t n = (size_t)B, npx = n * w * h;      // staged through one device buffer of its own (no tracker slot: B is not bounded by max_batch)
+	const size_t n = (size_t)B, npx = n * w * h;      // staged through the context's buffer (no tracker slot: B is not bounded by max_batch)
 	ht_seg seg[6] = { { (void *)depth, npx * sizeof(uint16_t), false }, { kind == HT_SENSOR_DS4 ? (void *)ir : nullptr, npx, false }, { (void *)cams, n * HT_CAM * sizeof(float), false },
 	                  { (void *)background, npx * sizeof(uint16_t), false }, { depth_out, n * wo * ho * sizeof(uint16_t), true }, { cams_out, n * HT_CAM * sizeof(float), true } };
-	return ht_staged_call(ctx, &ctx->d_sensor, &ctx->sensor_cap, seg, 6, [&](hipStream_t s)
+	return ht_staged_call(ctx, seg, 6, [&](hipStream_t s)
 	                      { return ht_sensor_filter_dev(ctx, kind, (const uint16_t *)seg[0].dev, (const uint8_t *)seg[1].dev, (const float *)seg[2].dev, w, h, B, max_width,
 	                                                    (const uint16_t *)seg[3].dev, (uint16_t *)seg[4].dev, (float *)seg[5].dev, s); });
 }
 
 static int sn_check_background(ht_ctx *ctx, const void *depth, int w, int h, int B, const void *background)
 {
-	if (!depth || !background || w < 1 || h < 1 || w > 4096 || h > 4096 || B < 0 || sn_overlap(depth, (size_t)B * w * h * sizeof(uint16_t), background, (size_t)B * w * h * sizeof(uint16_t)))
+	if (!depth || !background || !ht_frame_dims_ok(w, h) || B < 0 || ht_ranges_overlap(depth, (size_t)B * w * h * sizeof(uint16_t), background, (size_t)B * w * h * sizeof(uint16_t)))
 	{ ctx->err = "ht_sensor_background: bad argument"; return HT_ERR_ARG; }
 	return HT_OK;
 }
@@ -258,7 +254,7 @@ extern "C" int ht_sensor_background(ht_ctx *ctx, const uint16_t *depth, int w, i
 	if (B == 0) return HT_OK;
 	const size_t bytes = (size_t)B * w * h * sizeof(uint16_t);
 	ht_seg seg[2] = { { (void *)depth, bytes, false }, { background, bytes, true } };      // the model goes both ways: up here unless it starts afresh, down with the outputs
-	return ht_staged_call(ctx, &ctx->d_sensor, &ctx->sensor_cap, seg, 2, [&](hipStream_t s)
+	return ht_staged_call(ctx, seg, 2, [&](hipStream_t s)
 	                      {
 		                      if (!init) HIPCHK(ctx, hipMemcpyAsync(seg[1].dev, background, bytes, hipMemcpyHostToDevice, s));
 		                      return ht_sensor_background_dev(ctx, (const uint16_t *)seg[0].dev, w, h, B, fudge, init, (uint16_t *)seg[1].dev, s);
@@ -271,14 +267,13 @@ extern "C" int ht_sensor_background(ht_ctx *ctx, const uint16_t *depth, int w, i
 //             and the single pixels left and right of them, six u16 loads.  Lane i reads base + 16 i of three rows, whole contiguous lines; rows y-1 and y+1 are
 //             the rows the threads of the neighbouring rows load as their own, so every line comes from memory once and from the cache twice more.  No LDS: a
 //             tile with its halo would carry the same lines through one more copy, and the stage's time is its arithmetic, not its loads.
-//             N follows what the width and the pointers allow, by ht_mirror_frames' rule: 8 pixels (16 bytes) for w % 8 == 0 and 16-byte aligned frames (the IR
+//             N follows what the width and the pointers allow, by the one width rule (ht_frame_vec_pixels): 8 pixels (16 bytes) for w % 8 == 0 and 16-byte aligned frames (the IR
 //             image, whose store is N bytes, 8-byte aligned), 4, 2, and a pixel per thread for an odd width or buffers aligned to their element only.
 //   frames    thread r of blockIdx.x owns vector r of every frame blockIdx.y, blockIdx.y + gridDim.y, ...: its place in the frame is worked out once.  The frame's
 //             key is wave-uniform (scalar unit); the pixel's mix is the only 64-bit multiply chain in the lane.
 //   noise set by value in the kernel's arguments (80 bytes, scalar registers).
 
 #define SS_THREADS 256
-template <int N> struct alignas(2 * N) ss_px { uint16_t v[N]; };
 template <int N> struct alignas(N) ss_ir { uint8_t v[N]; };
 
 HT_HD bool ss_fg(int q, int far_count) { return (unsigned)(q - 1) < (unsigned)(far_count - 1); }      // q != 0 && q < far_count; -1 (outside the image) is not
@@ -362,7 +357,7 @@ template <int N> HT_HD void ss_vector(const uint16_t *__restrict__ in, uint16_t 
 		if (have[j])
 		{
 			const uint16_t *row = F + (ptrdiff_t)(j - 1) * w;      // inside the frame: have[j]
-			const ss_px<N> v = *(const ss_px<N> *)row;
+			const ht_pixels<N> v = *(const ht_pixels<N> *)row;
 #pragma unroll
 			for (int k = 0; k < N; k++) a[j][k + 1] = v.v[k];
 			a[j][0] = lf ? (int)row[-1] : -1;
@@ -374,7 +369,7 @@ template <int N> HT_HD void ss_vector(const uint16_t *__restrict__ in, uint16_t 
 			for (int k = 0; k < N + 2; k++) a[j][k] = -1;
 		}
 	}
-	ss_px<N> po; ss_ir<N> io;
+	ht_pixels<N> po; ss_ir<N> io;
 #pragma unroll
 	for (int k = 0; k < N; k++)
 	{
@@ -382,7 +377,7 @@ template <int N> HT_HD void ss_vector(const uint16_t *__restrict__ in, uint16_t 
 		io.v[k] = 0;
 		ss_pixel(nz, kind, key, (unsigned)o + (unsigned)k, want_ir, a[1][k + 1], nb, po.v[k], io.v[k]);
 	}
-	*(ss_px<N> *)(out + (size_t)f * frame_px + o) = po;
+	*(ht_pixels<N> *)(out + (size_t)f * frame_px + o) = po;
 	if (want_ir) *(ss_ir<N> *)(ir + (size_t)f * frame_px + o) = io;
 }
 template <int N> __global__ __launch_bounds__(SS_THREADS) void k_sensor_simulate(const uint16_t *__restrict__ in, uint16_t *__restrict__ out, uint8_t *__restrict__ ir, int kind, int w, int h,
@@ -424,31 +419,13 @@ extern "C" int ht_sensor_noise_default(int kind, float depth_scale, float far, h
 	return HT_OK;
 }
 
-static int ss_pixels_per_thread(const void *in, const void *out, const void *ir, int w)
-{
-	const uintptr_t a = (uintptr_t)in | (uintptr_t)out, i = (uintptr_t)ir;
-	if (w % 8 == 0 && (a & 15) == 0 && (i & 7) == 0) return 8;
-	if (w % 4 == 0 && (a & 7) == 0 && (i & 3) == 0) return 4;
-	if (w % 2 == 0 && (a & 3) == 0 && (i & 1) == 0) return 2;
-	return 1;
-}
-template <int N> static void ss_launch(int kind, const uint16_t *in, int w, int h, int B, const ht_sensor_noise &nz, uint16_t *out, uint8_t *ir, hipStream_t s)
-{
-	const unsigned per_row = (unsigned)w / N, per_frame = per_row * (unsigned)h;
-	const unsigned gx = (per_frame + SS_THREADS - 1) / SS_THREADS;
-	unsigned gy = (2048 + gx - 1) / gx;      // about eight blocks a CU; a thread then walks the frames blockIdx.y, blockIdx.y + gridDim.y, ...
-	if (gy > (unsigned)B) gy = (unsigned)B;
-	if (gy > 65535u) gy = 65535u;
-	hipLaunchKernelGGL(k_sensor_simulate<N>, dim3(gx, gy), dim3(SS_THREADS), 0, s, in, out, ir, kind, w, h, per_row, per_frame, (unsigned)B, nz);
-}
-
 // every check both forms share, made before anything is launched or grown
 static int ss_check(ht_ctx *ctx, int kind, const void *depth, int w, int h, int B, const ht_sensor_noise *nz, const void *depth_out, const void *ir_out)
 {
 	const char *bad = nullptr;
 	auto in = [](int v, long long hi) { return v >= 0 && (long long)v <= hi; };
 	if (kind != HT_SENSOR_IVY && kind != HT_SENSOR_DS4) bad = "kind";
-	else if (w < 1 || h < 1 || w > 4096 || h > 4096) bad = "w and h between 1 and 4096";
+	else if (!ht_frame_dims_ok(w, h)) bad = "w and h between 1 and 4096";
 	else if (B < 0) bad = "B";
 	else if (!depth || !depth_out || !nz) bad = "a NULL buffer";
 	else if (kind == HT_SENSOR_DS4 && !ir_out) bad = "DS4 needs ir_out";
@@ -458,7 +435,7 @@ static int ss_check(ht_ctx *ctx, int kind, const void *depth, int w, int h, int 
 	else if (!in(nz->sigma0_256, 65536) || !in(nz->sigma2, 4096) || !in(nz->edge_step, 65535) || !in(nz->slope_step, 65535) || !in(nz->fly_bg_count, 65535) || !in(nz->wall_count, 65535) ||
 	         !in(nz->disparity_k, 1 << 30) || !in(nz->ir_floor, 65536) || nz->ir_gain < 0 || !in(nz->ir_noise, 65536))
 		bad = "a noise figure outside its range";
-	else if (sn_overlap(depth, (size_t)B * w * h * sizeof(uint16_t), depth_out, (size_t)B * w * h * sizeof(uint16_t))) bad = "depth_out overlaps depth";
+	else if (ht_ranges_overlap(depth, (size_t)B * w * h * sizeof(uint16_t), depth_out, (size_t)B * w * h * sizeof(uint16_t))) bad = "depth_out overlaps depth";
 	if (bad) { ctx->err = std::string("ht_sensor_simulate: bad argument (") + bad + ")"; return HT_ERR_ARG; }
 	return HT_OK;
 }
@@ -471,13 +448,12 @@ extern "C" int ht_sensor_simulate_dev(ht_ctx *ctx, int kind, const uint16_t *d_d
 	hipStream_t s = ht_user_stream(ctx, stream);
 	{
 		ht_prof_scope ps(ctx, "k_sensor_simulate", s);
-		switch (ss_pixels_per_thread(d_depth, d_depth_out, d_ir_out, w))
+		// the IR image's store is N bytes: its address counts doubled
+		ht_frame_vec_dispatch(ht_frame_vec_pixels((uintptr_t)d_depth | (uintptr_t)d_depth_out | ((uintptr_t)d_ir_out << 1), w), [&](auto px)
 		{
-		case 8: ss_launch<8>(kind, d_depth, w, h, B, *noise, d_depth_out, d_ir_out, s); break;
-		case 4: ss_launch<4>(kind, d_depth, w, h, B, *noise, d_depth_out, d_ir_out, s); break;
-		case 2: ss_launch<2>(kind, d_depth, w, h, B, *noise, d_depth_out, d_ir_out, s); break;
-		default: ss_launch<1>(kind, d_depth, w, h, B, *noise, d_depth_out, d_ir_out, s); break;
-		}
+			const ht_frame_grid g(w, h, B, px, SS_THREADS);
+			hipLaunchKernelGGL(k_sensor_simulate<px>, g.grid, dim3(SS_THREADS), 0, s, d_depth, d_depth_out, d_ir_out, kind, w, h, g.per_row, g.per_frame, (unsigned)B, *noise);
+		});
 	}
 	HIPCHK(ctx, hipGetLastError());
 	return HT_OK;
@@ -490,6 +466,6 @@ extern "C" int ht_sensor_simulate(ht_ctx *ctx, int kind, const uint16_t *depth, 
 	if (B == 0) return HT_OK;
 	const size_t npx = (size_t)B * w * h;
 	ht_seg seg[3] = { { (void *)depth, npx * sizeof(uint16_t), false }, { depth_out, npx * sizeof(uint16_t), true }, { ir_out, npx, true } };
-	return ht_staged_call(ctx, &ctx->d_sensor, &ctx->sensor_cap, seg, 3, [&](hipStream_t s)
+	return ht_staged_call(ctx, seg, 3, [&](hipStream_t s)
 	                      { return ht_sensor_simulate_dev(ctx, kind, (const uint16_t *)seg[0].dev, w, h, B, noise, (uint16_t *)seg[1].dev, (uint8_t *)seg[2].dev, s); });
 }

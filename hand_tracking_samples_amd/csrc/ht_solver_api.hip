@@ -1242,9 +1242,9 @@ static int segment_host(ht_ctx *ctx, bool sized, int side, const uint16_t *depth
 {
 	if (!depth || !cams || !tiles || !cams_out || B < 1 || w < 1 || h < 1) return HT_ERR_ARG;
 	if (sized && !(w == side && h == side) && !ht_segment_supported_sized(w, h, side)) return segment_dev(ctx, true, side, depth, cams, w, h, B, entry_options, wrange_hi, diam, tiles, cams_out, nullptr);      // refused before the staging buffer grows
-	const size_t n = (size_t)B;      // staged through one device buffer of its own (ht_staged_call; no tracker slot: B is not bounded by max_batch)
+	const size_t n = (size_t)B;      // staged through the context's buffer (ht_staged_call; no tracker slot: B is not bounded by max_batch)
 	ht_seg seg[4] = { { (void *)depth, n * w * h * sizeof(uint16_t), false }, { (void *)cams, n * HT_CAM * sizeof(float), false }, { tiles, n * side * side * sizeof(uint16_t), true }, { cams_out, n * HT_CAM * sizeof(float), true } };
-	return ht_staged_call(ctx, &ctx->d_segment, &ctx->segment_cap, seg, 4, [&](hipStream_t s)
+	return ht_staged_call(ctx, seg, 4, [&](hipStream_t s)
 	                      { return segment_dev(ctx, sized, side, (const uint16_t *)seg[0].dev, (const float *)seg[1].dev, w, h, B, entry_options, wrange_hi, diam, (uint16_t *)seg[2].dev, (float *)seg[3].dev, s); });
 }
 extern "C" int ht_segment_vr_dev(ht_ctx *ctx, const uint16_t *d_depth, const float *d_cams, int w, int h, int B, int entry_options, float wrange_lo, float wrange_hi, float diam,

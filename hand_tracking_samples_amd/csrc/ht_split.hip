@@ -31,6 +31,7 @@
 //   k_split_cams    [B][12] -> [B][2][12]: the frame's camera, and for k = 1 its mirror image (ht_mirror_cam_word, ht_mirror.hpp).
 #include <string.h>
 #include "ht_host.hpp"
+#include "ht_frame_vec.hpp"
 #include "ht_mirror.hpp"
 
 #define SP_THREADS 1024
@@ -253,7 +254,6 @@ __global__ __launch_bounds__(SP_THREADS) void k_split_label(const uint16_t *__re
 }
 
 // ---- frames --------------------------------------------------------------------------------------------------------------------------------------------------------
-template <int N> struct alignas(4 * N) sp_words { unsigned v[N]; };
 __device__ __forceinline__ unsigned sp_hand_label(const int32_t *info, unsigned f, unsigned k) { return info[(size_t)f * 16 + k * 8] ? (unsigned)info[(size_t)f * 16 + k * 8 + 1] : 0x10000u; }
 
 // in [B][h][w], labels [B][H4][W4], info [B][2][8] -> out [B][2][h][w].  per_row vectors a row (w % (2N) == 0), W4 cells a row
@@ -264,23 +264,17 @@ template <int N> __global__ __launch_bounds__(SP_WTHREADS) void k_split_write(co
 	if (r >= per_frame) return;
 	const unsigned y = r / per_row, xv = r - y * per_row, rm = r - xv + (per_row - 1u - xv);
 	const unsigned cell = (y >> 2) * W4 + ((xv * 2u * N) >> 2);
-	const sp_words<N> *src = (const sp_words<N> *)in; sp_words<N> *dst = (sp_words<N> *)out;
+	const ht_dwords<N> *src = (const ht_dwords<N> *)in; ht_dwords<N> *dst = (ht_dwords<N> *)out;
 	for (unsigned f = blockIdx.y; f < B; f += gridDim.y)
 	{
 		const unsigned right = sp_hand_label(info, f, 0), left = sp_hand_label(info, f, 1);
 		const unsigned l0 = labels[(size_t)f * cells + cell], l1 = N == 4 ? (unsigned)labels[(size_t)f * cells + cell + 1] : l0;      // 8 pixels: two cells
-		const sp_words<N> a = src[(size_t)f * per_frame + r];
-		sp_words<N> o, m;
+		const ht_dwords<N> a = src[(size_t)f * per_frame + r];
+		ht_dwords<N> o, m;
 #pragma unroll
 		for (int i = 0; i < N; i++) { const unsigned l = i >= 2 ? l1 : l0; o.v[i] = l == right ? a.v[i] : far2; m.v[i] = l == left ? a.v[i] : far2; }
 		dst[(size_t)(2u * f) * per_frame + r] = o;
-		if (mirror)
-		{
-			sp_words<N> x;
-#pragma unroll
-			for (int i = 0; i < N; i++) { const unsigned d = m.v[N - 1 - i]; x.v[i] = (d >> 16) | (d << 16); }
-			dst[(size_t)(2u * f + 1u) * per_frame + rm] = x;
-		}
+		if (mirror) { ht_dwords<N> x; ht_reverse(m, x); dst[(size_t)(2u * f + 1u) * per_frame + rm] = x; }
 		else dst[(size_t)(2u * f + 1u) * per_frame + r] = m;
 	}
 }
@@ -317,26 +311,15 @@ void ht_launch_split_label(const uint16_t *depth, int w, int h, int B, unsigned 
 	const int wide = ((uintptr_t)depth & 7) == 0;      // (w % 4 == 0: every 4-pixel group of an 8-byte aligned buffer is 8-byte aligned)
 	hipLaunchKernelGGL(k_split_label, dim3(B), dim3(SP_THREADS), 0, s, depth, w, h, lo, hi, max_step, min_pixels, (flags & HT_SPLIT_RIGHT_IS_LOW_X) ? 1 : 0, wide, info, ncomp, labels);
 }
-template <int N> static void split_write_launch(const uint16_t *in, const uint16_t *labels, const int32_t *info, int w, int h, int B, unsigned far, int mirror, uint16_t *out, hipStream_t s)
-{
-	const unsigned px = N ? 2 * N : 1, per_row = (unsigned)w / px, per_frame = per_row * (unsigned)h;
-	const unsigned gx = (per_frame + SP_WTHREADS - 1) / SP_WTHREADS;
-	unsigned gy = (2048 + gx - 1) / gx;      // as k_mirror_frames: about eight blocks a CU, a thread walks the frames blockIdx.y, blockIdx.y + gridDim.y, ...
-	if (gy > (unsigned)B) gy = (unsigned)B;
-	if (gy > 65535u) gy = 65535u;
-	hipLaunchKernelGGL(k_split_write<N>, dim3(gx, gy), dim3(SP_WTHREADS), 0, s, in, labels, info, out, per_row, per_frame, (unsigned)w / 4u, ((unsigned)w / 4u) * ((unsigned)h / 4u), (unsigned)B,
-	                   far | (far << 16), mirror);
-}
 void ht_launch_split_write(const uint16_t *in, const uint16_t *labels, const int32_t *info, int w, int h, int B, unsigned far, int flags, uint16_t *out, hipStream_t s)
 {
 	const int mirror = (flags & HT_SPLIT_MIRROR_LEFT) ? 1 : 0;
-	switch (ht_mirror_frames_pixels(in, out, w))      // the same rule as the mirror kernel's: a hand's frame starts a multiple of w * h pixels into `out`
+	ht_frame_vec_dispatch(ht_frame_vec_pixels((uintptr_t)in | (uintptr_t)out, w), [&](auto px)      // a hand's frame starts a multiple of w * h pixels into `out`
 	{
-	case 8: split_write_launch<4>(in, labels, info, w, h, B, far, mirror, out, s); break;
-	case 4: split_write_launch<2>(in, labels, info, w, h, B, far, mirror, out, s); break;
-	case 2: split_write_launch<1>(in, labels, info, w, h, B, far, mirror, out, s); break;
-	default: split_write_launch<0>(in, labels, info, w, h, B, far, mirror, out, s); break;
-	}
+		const ht_frame_grid g(w, h, B, px, SP_WTHREADS);
+		hipLaunchKernelGGL(k_split_write<px / 2>, g.grid, dim3(SP_WTHREADS), 0, s, in, labels, info, out, g.per_row, g.per_frame, (unsigned)w / 4u, ((unsigned)w / 4u) * ((unsigned)h / 4u), (unsigned)B,
+		                   far | (far << 16), mirror);
+	});
 }
 void ht_launch_split_cams(const float *in, int w, int B, int flags, float *out, hipStream_t s)
 {
@@ -362,30 +345,29 @@ static int split_check_call(ht_ctx *ctx, const void *in, const void *out, const 
 	if ((cams_out != nullptr) != (cams != nullptr)) { ctx->err = "ht_split_hands: cams and cams_out are given together or not at all"; return HT_ERR_ARG; }
 	{ const int r = ht_split_check(ctx, "ht_split_hands", w, h, range_lo, range_hi, min_pixels, far, flags); if (r) return r; }
 	const size_t bytes = (size_t)B * w * h * sizeof(uint16_t);
-	const uintptr_t a = (uintptr_t)in, b = (uintptr_t)out;
-	if (a < b + 2 * bytes && b < a + bytes) { ctx->err = "ht_split_hands: depth and depth_out must not overlap"; return HT_ERR_ARG; }
+	if (ht_ranges_overlap(in, bytes, out, 2 * bytes)) { ctx->err = "ht_split_hands: depth and depth_out must not overlap"; return HT_ERR_ARG; }
 	return HT_OK;
 }
 extern "C" int ht_split_hands_dev(ht_ctx *ctx, const uint16_t *d_depth, const float *d_cams, int w, int h, int B, uint16_t range_lo, uint16_t range_hi, uint16_t max_step, int min_pixels, uint16_t far, int flags,
-                                  uint16_t *d_depth_out, float *d_cams_out, int32_t *d_info, int32_t *d_n_components, uint16_t *d_labels, void *stream)
+                                  uint16_t *d_depth_out, float *d_cams_out, int32_t *d_info, int32_t *d_n_components, uint16_t *d_label_img, void *stream)
 {
 	CHECK_READY(ctx);
 	{ const int r = split_check_call(ctx, d_depth, d_depth_out, d_info, w, h, B, range_lo, range_hi, min_pixels, far, flags, d_cams, d_cams_out); if (r) return r; }
 	if (B == 0) return HT_OK;
-	if (!d_labels)      // the frames are cut along the label image: the context keeps one when the caller wants none
+	if (!d_label_img)      // the frames are cut along the label image: the context keeps one when the caller wants none
 	{
 		const int r = dev_grow(ctx, &ctx->d_split_labels, &ctx->split_labels_cap, (size_t)B * (w / 4) * (h / 4));
 		if (r) return r;
-		d_labels = ctx->d_split_labels;
+		d_label_img = ctx->d_split_labels;
 	}
 	hipStream_t s = ht_user_stream(ctx, stream);
-	{ ht_prof_scope ps(ctx, "k_split_label", s); ht_launch_split_label(d_depth, w, h, B, range_lo, range_hi, max_step, min_pixels, flags, d_info, d_n_components, d_labels, s); }
-	{ ht_prof_scope ps(ctx, "k_split_write", s); ht_launch_split_write(d_depth, d_labels, d_info, w, h, B, far, flags, d_depth_out, s); }
+	{ ht_prof_scope ps(ctx, "k_split_label", s); ht_launch_split_label(d_depth, w, h, B, range_lo, range_hi, max_step, min_pixels, flags, d_info, d_n_components, d_label_img, s); }
+	{ ht_prof_scope ps(ctx, "k_split_write", s); ht_launch_split_write(d_depth, d_label_img, d_info, w, h, B, far, flags, d_depth_out, s); }
 	if (d_cams) { ht_prof_scope ps(ctx, "k_split_cams", s); ht_launch_split_cams(d_cams, w, B, flags, d_cams_out, s); }
 	HIPCHK(ctx, hipGetLastError());
 	return HT_OK;
 }
-// The host form: inputs and outputs through a staging of the context (ht_staged_call), the same kernels.  Its segments are 256-byte aligned: the widest path the width allows.
+// The host form: inputs and outputs through the context's staging (ht_staged_call), the same kernels.  Its segments are 256-byte aligned: the widest path the width allows.
 extern "C" int ht_split_hands(ht_ctx *ctx, const uint16_t *depth, const float *cams, int w, int h, int B, uint16_t range_lo, uint16_t range_hi, uint16_t max_step, int min_pixels, uint16_t far, int flags,
                               uint16_t *depth_out, float *cams_out, int32_t *info, int32_t *n_components, uint16_t *labels)
 {
@@ -395,7 +377,7 @@ extern "C" int ht_split_hands(ht_ctx *ctx, const uint16_t *depth, const float *c
 	const size_t bytes = (size_t)B * w * h * sizeof(uint16_t), cb = (size_t)B * HT_CAM * sizeof(float);
 	ht_seg seg[7] = { { (void *)depth, bytes, false }, { (void *)cams, cb, false }, { depth_out, 2 * bytes, true }, { cams_out, 2 * cb, true }, { info, (size_t)B * 16 * sizeof(int32_t), true },
 	                  { n_components, (size_t)B * sizeof(int32_t), true }, { labels, (size_t)B * (w / 4) * (h / 4) * sizeof(uint16_t), true } };
-	return ht_staged_call(ctx, &ctx->d_split, &ctx->split_cap, seg, 7, [&](hipStream_t s)
+	return ht_staged_call(ctx, seg, 7, [&](hipStream_t s)
 	                      { return ht_split_hands_dev(ctx, (const uint16_t *)seg[0].dev, (const float *)seg[1].dev, w, h, B, range_lo, range_hi, max_step, min_pixels, far, flags, (uint16_t *)seg[2].dev,
 	                                                  (float *)seg[3].dev, (int32_t *)seg[4].dev, (int32_t *)seg[5].dev, (uint16_t *)seg[6].dev, s); });
 }

@@ -243,29 +243,28 @@ static int split_model_check_call(ht_ctx *ctx, const void *in, const void *cams,
 	if (!in || !cams || !poses || !out || !info || B < 0 || (B > 0x7fffffff / 24)) { ctx->err = "ht_split_hands_model: bad argument (depth, cams, poses, depth_out and info are required)"; return HT_ERR_ARG; }
 	{ const int r = ht_split_check(ctx, "ht_split_hands_model", w, h, range_lo, range_hi, min_pixels, far, flags & SM_SPLIT_FLAGS); if (r) return r; }
 	const size_t bytes = (size_t)B * w * h * sizeof(uint16_t);
-	const uintptr_t a = (uintptr_t)in, b = (uintptr_t)out;
-	if (a < b + 2 * bytes && b < a + bytes) { ctx->err = "ht_split_hands_model: depth and depth_out must not overlap"; return HT_ERR_ARG; }
+	if (ht_ranges_overlap(in, bytes, out, 2 * bytes)) { ctx->err = "ht_split_hands_model: depth and depth_out must not overlap"; return HT_ERR_ARG; }
 	return HT_OK;
 }
 extern "C" int ht_split_hands_model_dev(ht_ctx *ctx, const uint16_t *d_depth, const float *d_cams, const float *d_poses, int w, int h, int B, uint16_t range_lo, uint16_t range_hi, uint16_t max_step, int min_pixels,
                                         uint16_t far, float max_dist, int mode, int flags, uint16_t *d_depth_out, float *d_cams_out, int32_t *d_info, int32_t *d_n_components, int32_t *d_source, float *d_dist,
-                                        uint16_t *d_labels, void *stream)
+                                        uint16_t *d_label_img, void *stream)
 {
 	CHECK_READY(ctx);
 	{ const int r = split_model_check_call(ctx, d_depth, d_cams, d_poses, d_depth_out, d_info, w, h, B, range_lo, range_hi, min_pixels, far, max_dist, mode, flags); if (r) return r; }
 	if (B == 0) return HT_OK;
 	const bool need_ncomp = mode == HT_SPLIT_MODEL_MERGED && !d_n_components;
-	{ const int r = split_model_reserve(ctx, w, h, B, !d_labels, need_ncomp); if (r) return r; }
-	if (!d_labels) d_labels = ctx->d_split_labels;
+	{ const int r = split_model_reserve(ctx, w, h, B, !d_label_img, need_ncomp); if (r) return r; }
+	if (!d_label_img) d_label_img = ctx->d_split_labels;
 	hipStream_t s = ht_user_stream(ctx, stream);
 	ht_launch_split_model(ctx, d_depth, d_cams, d_poses, HT_POSE, 0, w, h, B, range_lo, range_hi, max_step, min_pixels, max_dist, mode, flags, d_info, need_ncomp ? ctx->d_model_ncomp : d_n_components, d_source, d_dist,
-	                      d_labels, s);
-	{ ht_prof_scope ps(ctx, "k_split_write", s); ht_launch_split_write(d_depth, d_labels, d_info, w, h, B, far, flags & SM_SPLIT_FLAGS, d_depth_out, s); }
+	                      d_label_img, s);
+	{ ht_prof_scope ps(ctx, "k_split_write", s); ht_launch_split_write(d_depth, d_label_img, d_info, w, h, B, far, flags & SM_SPLIT_FLAGS, d_depth_out, s); }
 	if (d_cams_out) { ht_prof_scope ps(ctx, "k_split_cams", s); ht_launch_split_cams(d_cams, w, B, flags & SM_SPLIT_FLAGS, d_cams_out, s); }
 	HIPCHK(ctx, hipGetLastError());
 	return HT_OK;
 }
-// The host form: inputs and outputs through the split's staging of the context (ht_staged_call), the same kernels
+// The host form: inputs and outputs through the context's staging (ht_staged_call), the same kernels
 extern "C" int ht_split_hands_model(ht_ctx *ctx, const uint16_t *depth, const float *cams, const float *poses, int w, int h, int B, uint16_t range_lo, uint16_t range_hi, uint16_t max_step, int min_pixels, uint16_t far,
                                     float max_dist, int mode, int flags, uint16_t *depth_out, float *cams_out, int32_t *info, int32_t *n_components, int32_t *source, float *dist, uint16_t *labels)
 {
@@ -276,7 +275,7 @@ extern "C" int ht_split_hands_model(ht_ctx *ctx, const uint16_t *depth, const fl
 	ht_seg seg[10] = { { (void *)depth, bytes, false }, { (void *)cams, cb, false }, { (void *)poses, (size_t)B * 2 * ctx->model.nb * HT_POSE * sizeof(float), false }, { depth_out, 2 * bytes, true },
 	                   { cams_out, 2 * cb, true }, { info, (size_t)B * 16 * sizeof(int32_t), true }, { n_components, (size_t)B * sizeof(int32_t), true }, { source, (size_t)B * sizeof(int32_t), true },
 	                   { dist, cells * 2 * sizeof(float), true }, { labels, cells * sizeof(uint16_t), true } };
-	return ht_staged_call(ctx, &ctx->d_split, &ctx->split_cap, seg, 10, [&](hipStream_t s)
+	return ht_staged_call(ctx, seg, 10, [&](hipStream_t s)
 	                      { return ht_split_hands_model_dev(ctx, (const uint16_t *)seg[0].dev, (const float *)seg[1].dev, (const float *)seg[2].dev, w, h, B, range_lo, range_hi, max_step, min_pixels, far, max_dist, mode,
 	                                                        flags, (uint16_t *)seg[3].dev, (float *)seg[4].dev, (int32_t *)seg[5].dev, (int32_t *)seg[6].dev, (int32_t *)seg[7].dev, (float *)seg[8].dev,
 	                                                        (uint16_t *)seg[9].dev, s); });

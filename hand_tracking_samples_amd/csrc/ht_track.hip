@@ -6,8 +6,6 @@
 #include "ht_launch.hpp"
 #include "ht_quad.hpp"
 
-__device__ __forceinline__ v3 G3(const float *p) { return V3(p[0], p[1], p[2]); }
-__device__ __forceinline__ v4 G4(const float *p) { return V4(p[0], p[1], p[2], p[3]); }
 __device__ __forceinline__ m3 GM(const float *p) { m3 m; m.x = V3(p[0], p[1], p[2]); m.y = V3(p[3], p[4], p[5]); m.z = V3(p[6], p[7], p[8]); return m; }
 
 // ---- state plumbing ---------------------------------------------------------------------------------------------
@@ -49,7 +47,7 @@ __global__ void k_output(ht_model_dev M, const float *__restrict__ hand, const i
 	const int b = i / M.nb, rb = i % M.nb;
 	const float *s = hand + (size_t)i * HT_STATE_STRIDE;
 	if (raw) { for (int k = 0; k < 7; k++) poses[(size_t)i * HT_POSE + k] = s[k]; return; }
-	v3 pu = apply(XF(G3(s), G4(s + 3)), -G3(M.bodyc + rb * HT_BC + HT_BC_COM));
+	v3 pu = apply(XF(load3(s), load4(s + 3)), -load3(M.bodyc + rb * HT_BC + HT_BC_COM));
 	float *o = poses + (size_t)i * HT_POSE;
 	o[0] = pu.x; o[1] = pu.y; o[2] = pu.z; o[3] = s[3]; o[4] = s[4]; o[5] = s[5]; o[6] = s[6];
 	if (rb == 0 && npts[b] < min_point_num) initializing[b] = 50;

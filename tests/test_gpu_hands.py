@@ -50,10 +50,10 @@ def _host(t, like):
 
 # ---- the mirror kernels ---------------------------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("B", [1, 3, 70])
-@pytest.mark.parametrize("w,h", [(4, 4), (8, 4), (12, 8), (64, 64), (68, 12), (320, 240)])
+@pytest.mark.parametrize("w,h", [(1, 1), (7, 5), (4, 4), (8, 4), (12, 8), (64, 64), (68, 12), (320, 240)])
 def test_mirror_frames_equal_the_reference_bytes(ctx, w, h, B):
     """Every path of the frame kernel: 16 bytes a thread for (8,4) (64,64) (320,240), 8 for (4,4) (12,8) (68,12), 4 for an output two pixels into its allocation, and
-    single pixels for views one pixel into an allocation, on input, on output and on both."""
+    single pixels for views one pixel into an allocation, on input, on output and on both -- and for the odd widths (7,5) (1,1), whatever the alignment."""
     rng = np.random.default_rng(w * 1000 + h * 10 + B)
     depth = rng.integers(0, 65536, (B, h, w)).astype(np.uint16)
     n = depth.size

@@ -3,7 +3,7 @@ bit: every size at which the kernel takes another path, both kinds, with and wit
 (the counts are asserted, so an all-background input cannot pass); views that reach each narrower load width, guard bytes, host against device form, second calls,
 stream independence, the ends of the probability range, refusals, and rendered hands made raw, filtered and tracked on one stream.
 
-The width a call takes follows ht_mirror_frames' rule: 8 pixels a thread (16 bytes) for w % 8 == 0 and 16-byte aligned frames with an 8-byte aligned IR image, then 4, 2
+The width a call takes follows the one width rule (ht_frame_vec_pixels, csrc/ht_frame_vec.hpp): 8 pixels a thread (16 bytes) for w % 8 == 0 and 16-byte aligned frames with an 8-byte aligned IR image, then 4, 2
 and 1.  Of the sizes below 40x12, 320x240 and 640x480 take 16 bytes; 36x20 and 76x20 (divisible by 4, not by 8) take 8; 17x9, 3x3 and 1x1 single pixels; 4x4 eight bytes."""
 import ctypes as C
 import os
