@@ -141,6 +141,10 @@ static inline const char *ht_form_name(const ht_ctx *ctx, const ht_net *net, con
 #define CHECK_READY(ctx) if (!(ctx)) return HT_ERR_ARG; if (!(ctx)->ready) { (ctx)->err = "context not initialised (ht_create failed)"; return HT_ERR_STATE; } ht_device_guard dev_guard_((ctx)->device)
 #define CHECK_MODEL(ctx) do { if ((ctx)->cnn_only) { (ctx)->err = "this context was created without a hand model (CNN only)"; return HT_ERR_STATE; } } while (0)
 #define CHECK_BATCH(ctx, B) do { if ((B) < 1 || (B) > (ctx)->B) { (ctx)->err = "batch exceeds the capacity given to ht_create"; return HT_ERR_ARG; } } while (0)
+// the exact-order instantiation of the solver (ht_debug_solver_build 5, tests only) takes the cloud rows in the reference's layout (ctx->d_rows) instead of records
+static inline bool exact_solver(const ht_ctx *ctx) { return ctx->solver_build == 5 || ctx->solver_build == 8; }      // 8: the same sweeps with the product's forked launch sequence (5 takes the kernels in order on one stream)
+// The entry points that solve rows of the caller's (ht_fit_rows, ht_physics_update, ht_slowfit, ht_fit_keypoints) refuse that instantiation before they upload or launch anything
+#define REFUSE_EXACT_SOLVER(ctx) do { if (exact_solver(ctx)) { (ctx)->err = "the exact-order instantiation (ht_debug_solver_build 5) serves the update entry points only"; return HT_ERR_STATE; } } while (0)
 // argument checks the entry points share (each composes its own message): whether two byte ranges overlap (a null or empty one overlaps nothing), and a frame's size
 static inline bool ht_ranges_overlap(const void *a, size_t na, const void *b, size_t nb) { return a && b && na && nb && (uintptr_t)a < (uintptr_t)b + nb && (uintptr_t)b < (uintptr_t)a + na; }
 static inline bool ht_frame_dims_ok(int w, int h) { return w >= 1 && h >= 1 && w <= 4096 && h <= 4096; }
@@ -202,6 +206,17 @@ template <class F> static inline int ht_staged_call(ht_ctx *ctx, ht_seg *seg, in
 	HIPCHK(ctx, hipStreamSynchronize(s));
 	return HT_OK;
 }
+
+// Keypoint tables (ht_quality.hip; shared with ht_kpfit.hip): the table a call names, checked -- a built-in one of the context's model as ht_scale left it, or the
+// caller's -- as the kernels take it by value, and whether any output of a host form overlaps an input or another output
+struct ql_table { int K; unsigned char bone[HT_KP_MAX], rel[HT_KP_MAX]; float off[HT_KP_MAX * 3]; };
+struct ql_buf { const void *p; size_t bytes; };
+int ql_table_of(ht_ctx *ctx, const char *fn, int which, int K, const int *bones, const float *offsets, const int *rel, ql_table &t);
+bool ql_any_overlap(const ql_buf *in, int nin, const ql_buf *out, int nout);
+// Caller-built rows (ht_solver_api.hip; shared with ht_kpfit.hip): the context's row buffers for lin_cap linear and ang_cap angular rows a frame, and one
+// PhysModel::FitPointCloud step on model `which` of slots [0,B) with the linear rows and counts that d_user_lin / d_user_n hold, enqueued on s and not waited for
+int ht_user_rows_reserve(ht_ctx *ctx, int lin_cap, int ang_cap);
+void ht_fit_rows_enqueue(ht_ctx *ctx, int which, int B, float microforce, int ang_bound, int zero_momenta, hipStream_t s);
 
 struct ht_prof_scope
 {

@@ -29,7 +29,6 @@
 
 #define QL_THREADS 256
 
-struct ql_table { int K; unsigned char bone[HT_KP_MAX], rel[HT_KP_MAX]; float off[HT_KP_MAX * 3]; };
 struct ql_thr { int T; float v[HT_KP_MAX_THR]; };
 
 // ---- keypoints ---------------------------------------------------------------------------------------------------------------------------------------------------
@@ -206,8 +205,8 @@ __global__ __launch_bounds__(QL_THREADS) void k_pose_to_render(const ht_model_de
 }
 
 // ---- host: the tables --------------------------------------------------------------------------------------------------------------------------------------------
-// The table a call names, checked: a built-in one of the context's model as ht_scale left it, or the caller's
-static int ql_table_of(ht_ctx *ctx, const char *fn, int which, int K, const int *bones, const float *offsets, const int *rel, ql_table &t)
+// The table a call names, checked: a built-in one of the context's model as ht_scale left it, or the caller's (ht_host.hpp: ht_kpfit.hip takes it too)
+int ql_table_of(ht_ctx *ctx, const char *fn, int which, int K, const int *bones, const float *offsets, const int *rel, ql_table &t)
 {
 	const std::string f(fn);
 	const int nb = ctx->model.nb, nj = ctx->model.nj;
@@ -254,9 +253,8 @@ static int ql_table_of(ht_ctx *ctx, const char *fn, int which, int K, const int 
 	}
 	return HT_OK;
 }
-struct ql_buf { const void *p; size_t bytes; };
 // whether any of the outputs overlaps an input or another output (the host forms can see that)
-static bool ql_any_overlap(const ql_buf *in, int nin, const ql_buf *out, int nout)
+bool ql_any_overlap(const ql_buf *in, int nin, const ql_buf *out, int nout)
 {
 	for (int o = 0; o < nout; o++)
 	{

@@ -19,8 +19,6 @@ static int dev_alloc_points(ht_ctx *ctx)      // the second cloud of a context t
 static const cloud_take step_take = { /* stride */ 4, /* cam_origin */ 1, CLOUD_MULTISTEP };      // MultiStepSim: every 4th point, rays from the camera (handtrack.h:656, 681)
 static cloud_take fit_take(int mode) { const cloud_take t = { /* stride */ 1, /* cam_origin */ 0, mode }; return t; }      // FitPointCloud's callers: every point, rays from the origin
 static cloud_records cloud_rec(ht_ctx *ctx) { cloud_records r = { ctx->d_scratch, scratch_stride(ctx), ctx->d_rowbody, ctx->phys.deltaT }; return r; }
-// the exact-order instantiation of the solver (ht_debug_solver_build 5, tests only) takes the cloud rows in the reference's layout (ctx->d_rows) instead of records
-static bool exact_solver(const ht_ctx *ctx) { return ctx->solver_build == 5 || ctx->solver_build == 8; }      // 8: the same sweeps with the product's forked launch sequence (5 takes the kernels in order on one stream)
 static const cloud_records *rec_or_rows(const ht_ctx *ctx, const cloud_records *cr) { return exact_solver(ctx) ? nullptr : cr; }
 static void exact_args(ht_ctx *ctx, solve_args &a, bool cloud)
 {
@@ -28,8 +26,6 @@ static void exact_args(ht_ctx *ctx, solve_args &a, bool cloud)
 	a.exact_lin = ctx->d_exact_lin; a.exact_ang = ctx->d_exact_ang;
 	if (exact_solver(ctx) && cloud) { a.rows_cloud = ctx->d_rows; a.cloud_body = nullptr; }
 }
-// The entry points that solve rows of the caller's (ht_fit_rows, ht_physics_update, ht_slowfit) refuse that instantiation before they upload or launch anything
-#define REFUSE_EXACT_SOLVER(ctx) do { if (exact_solver(ctx)) { (ctx)->err = "the exact-order instantiation (ht_debug_solver_build 5) serves the update entry points only"; return HT_ERR_STATE; } } while (0)
 // What every solve starts from: model `which` of the frames' slots, their scratch, the net's decoded output, the cameras, the capacity counters, the contact pool (if it takes contacts)
 static solve_args solve_head(ht_ctx *ctx, int which, bool contacts)
 {
@@ -1284,7 +1280,7 @@ extern "C" int ht_segment_vr_sized(ht_ctx *ctx, int side, const uint16_t *depth,
 // (physics.h:543-587) take rows the CALLER built.  Row layouts are those of the stage calls: a linear row is 16 floats (rb0 rb1 position0[3]
 // position1[3] normal[3] targetdist targetspeednobias forcelimit.x forcelimit.y friction_master), an angular row 8 (rb0 rb1 axis[3] targetspin
 // mintorque maxtorque); a body is its index in PhysModel::rigidbodies, -1 = NULL.
-static int user_rows_reserve(ht_ctx *ctx, int lin_cap, int ang_cap)
+int ht_user_rows_reserve(ht_ctx *ctx, int lin_cap, int ang_cap)
 {
 	const size_t B = (size_t)ctx->B;
 	int r, pos_cap = ctx->user_lin_cap;      // the two arrays of the linear rows share a capacity: it is raised by the second to grow
@@ -1305,15 +1301,37 @@ static int upload_angulars(ht_ctx *ctx, int B, const float *angulars, int acap, 
 	HIPCHK(ctx, hipMemcpy(ctx->d_user_n + 3 * (size_t)ctx->B, na.data(), (size_t)B * sizeof(int), hipMemcpyHostToDevice));
 	return HT_OK;
 }
-// the solve of ht_fit_rows / ht_physics_update: the caller's angular rows (upload_angulars) join, then the stream is waited for
-static int solve_caller_rows(ht_ctx *ctx, solve_args &a, const std::vector<int> &na, int B, hipStream_t s)
+// the solve of ht_fit_rows / ht_physics_update / ht_fit_keypoints: the caller's angular rows (upload_angulars; ang_bound: the largest count of a frame) join
+static void enqueue_caller_rows(ht_ctx *ctx, solve_args &a, int ang_bound, int B, hipStream_t s)
 {
 	a.ang_user = ctx->d_user_ang; a.n_ang_user = ctx->d_user_n + 3 * (size_t)ctx->B; a.ang_user_stride = ctx->user_ang_cap;
-	{ int mx = 0; for (int v : na) mx = v > mx ? v : mx; a.ang_extra_bound = mx; }
+	a.ang_extra_bound = ang_bound;
 	a.force_build = ctx->solver_build;
 	ctx->model.pts_bound = 0;
 	ht_launch_solve(ctx->model, ctx->phys, a, B, s);
+}
+// ... then the stream is waited for
+static int solve_caller_rows(ht_ctx *ctx, solve_args &a, const std::vector<int> &na, int B, hipStream_t s)
+{
+	int mx = 0; for (int v : na) mx = v > mx ? v : mx;
+	enqueue_caller_rows(ctx, a, mx, B, s);
 	return ht_sync_check(ctx, s);
+}
+// One FitPointCloud step on what the context's buffers hold (ht_fit_rows' launch sequence; ht_fit_keypoints runs it once per step with rows its kernel wrote): the cloud
+// rows of the prepared points, the contacts if physics_use_collision, and k_solve with the caller's linear rows (d_user_lin / d_user_n) ahead of them.  k_solve brings the
+// joint ranges up to date itself.  Enqueued on s, not waited for
+void ht_fit_rows_enqueue(ht_ctx *ctx, int which, int B, float microforce, int ang_bound, int zero_momenta, hipStream_t s)
+{
+	const bool coll = ctx->phys.use_collision != 0;
+	cloud_limits lim = ht_cloud_limits(ctx->par, CLOUD_FIT); lim.microforce = microforce;
+	const cloud_records cr = cloud_rec(ctx);
+	ht_launch_cloud_rows(ctx->model, ctx->d_state[which], ctx->d_pts, ctx->d_npts, ctx->d_cams, nullptr, fit_take(CLOUD_FIT), lim, ctx->d_rows, ctx->d_nrows, B, s, &cr);
+	if (coll) launch_contacts(ctx, which, nullptr, B, s);
+	solve_args a = solve_head(ctx, which, coll);
+	a.rows_pre = ctx->d_user_lin; a.n_pre = ctx->d_user_n; a.pre_stride = ctx->user_lin_cap;
+	a.cloud_body = ctx->d_rowbody; a.n_cloud = ctx->d_nrows;
+	a.zero_momenta = zero_momenta;
+	enqueue_caller_rows(ctx, a, ang_bound, B, s);
 }
 // void PhysModel::FitPointCloud(const std::vector<float3> &points, std::vector<LimitLinear> linears, std::vector<LimitAngular> angulars, float microforce)
 // on model `which` of slots [0,B): the caller's linear rows, then CloudConstraints(points) with the +-microforce limits (x physics_weak_force on
@@ -1339,7 +1357,7 @@ extern "C" int ht_fit_rows(ht_ctx *ctx, int which, int B, const float *points, i
 		}
 	}
 	REFUSE_EXACT_SOLVER(ctx);
-	{ const int r = user_rows_reserve(ctx, lcap > 1 ? lcap : 1, acap > 1 ? acap : 1); if (r) return r; }
+	{ const int r = ht_user_rows_reserve(ctx, lcap > 1 ? lcap : 1, acap > 1 ? acap : 1); if (r) return r; }
 	{ const int r = upload_angulars(ctx, B, angulars, acap, nangulars, na); if (r) return r; }
 	// the points (ht_set_points grows the point capacity when it has to)
 	{
@@ -1350,16 +1368,9 @@ extern "C" int ht_fit_rows(ht_ctx *ctx, int which, int B, const float *points, i
 	}
 	if (lcap > 0 && linears) HIPCHK(ctx, hipMemcpy2D(ctx->d_user_lin, (size_t)ctx->user_lin_cap * HT_ROW * sizeof(float), linears, (size_t)lcap * HT_ROW * sizeof(float), (size_t)lcap * HT_ROW * sizeof(float), B, hipMemcpyHostToDevice));
 	HIPCHK(ctx, hipMemcpy(ctx->d_user_n, nl.data(), (size_t)B * sizeof(int), hipMemcpyHostToDevice));
-	hipStream_t s = ctx->stream;
-	const bool coll = ctx->phys.use_collision != 0;
-	cloud_limits lim = ht_cloud_limits(ctx->par, CLOUD_FIT); lim.microforce = microforce;
-	const cloud_records cr = cloud_rec(ctx);
-	ht_launch_cloud_rows(ctx->model, ctx->d_state[which], ctx->d_pts, ctx->d_npts, ctx->d_cams, nullptr, fit_take(CLOUD_FIT), lim, ctx->d_rows, ctx->d_nrows, B, s, &cr);
-	if (coll) launch_contacts(ctx, which, nullptr, B, s);
-	solve_args a = solve_head(ctx, which, coll);
-	a.rows_pre = ctx->d_user_lin; a.n_pre = ctx->d_user_n; a.pre_stride = ctx->user_lin_cap;
-	a.cloud_body = ctx->d_rowbody; a.n_cloud = ctx->d_nrows;
-	return solve_caller_rows(ctx, a, na, B, s);
+	int most_ang = 0; for (int v : na) most_ang = v > most_ang ? v : most_ang;
+	ht_fit_rows_enqueue(ctx, which, B, microforce, most_ang, 0, ctx->stream);
+	return ht_sync_check(ctx, ctx->stream);
 }
 // void PhysicsUpdate(const std::vector<RigidBody*> &rigidbodies, std::vector<LimitLinear> &Linears, std::vector<LimitAngular> &Angulars, wgeom = {})
 // (physics.h:543-587) on model `which` of slots [0,B): the caller's rows are all there is (plus the collision rows when physics_use_collision is set).
@@ -1404,7 +1415,7 @@ extern "C" int ht_physics_update(ht_ctx *ctx, int which, int B, const float *lin
 	}
 	REFUSE_EXACT_SOLVER(ctx);
 	if (most_pre > ctx->model.pts_cap) { const int r = ht_reserve_points_locked(ctx, most_pre); if (r) return r; }
-	{ const int r = user_rows_reserve(ctx, lcap > 1 ? lcap : 1, acap > 1 ? acap : 1); if (r) return r; }
+	{ const int r = ht_user_rows_reserve(ctx, lcap > 1 ? lcap : 1, acap > 1 ? acap : 1); if (r) return r; }
 	{ const int r = upload_angulars(ctx, B, angulars, acap, nangulars, na); if (r) return r; }
 	const size_t pc = (size_t)ctx->model.pts_cap;
 	for (int b = 0; b < B; b++)

@@ -23,6 +23,7 @@ SPLIT_RIGHT_IS_LOW_X, SPLIT_MIRROR_LEFT = 1, 2      # HT_SPLIT_RIGHT_IS_LOW_X, H
 SPLIT_MODEL_ALWAYS, SPLIT_MODEL_MERGED, SPLIT_USER_POSES = 0, 1, 4      # HT_SPLIT_MODEL_ALWAYS, HT_SPLIT_MODEL_MERGED, HT_SPLIT_USER_POSES
 KP_COM_POSES = 1              # HT_KP_COM_POSES
 KP_FEATURE8, KP_SKELETON, KP_CALLER, KP_MAX, KP_MAX_THR = 0, 1, 2, 64, 32      # HT_KP_FEATURE8, HT_KP_SKELETON, HT_KP_CALLER, HT_KP_MAX, HT_KP_MAX_THR
+KPFIT_KEEP_MOMENTA = 1        # HT_KPFIT_KEEP_MOMENTA
 CNN128_IN, CNNB128_COUNT = 16384, 30429920
 # ht_debug_train_buffers: (name, floats, shape) of the segments of act and err, in order (None: padding)
 TRAIN_ACT = (("a1", 57600, (16, 60, 60)), ("a3", 3600, (16, 15, 15)), ("a5", 9216, (64, 12, 12)), ("a6", 2304, (2304,)), ("a8", 2048, (2048,)))
@@ -49,6 +50,7 @@ SYMBOLS = (
     "ht_split_hands_model", "ht_split_hands_model_dev", "ht_update_two_hands_model_sync", "ht_update_two_hands_model_dev",
     "ht_keypoint_table", "ht_keypoints", "ht_keypoints_dev", "ht_keypoint_errors", "ht_keypoint_errors_dev", "ht_depth_compare", "ht_depth_compare_dev",
     "ht_pose_depth_residual", "ht_pose_depth_residual_dev",
+    "ht_kpfit_default", "ht_fit_keypoints", "ht_fit_keypoints_dev",
     "ht_comm_available", "ht_comm_unique_id", "ht_comm_init", "ht_comm_info", "ht_gather_poses_dev", "ht_gather_wait", "ht_gather_wait_host", "ht_comm_destroy",
 )
 
@@ -104,6 +106,11 @@ class Opt(C.Structure):
                 raise TypeError("ht_opt has no field %r" % k)
             setattr(n, k, v)
         return n
+
+
+class KpFit(C.Structure):
+    """ht_kpfit: the options of ht_fit_keypoints (kpfit_default() fills in slowfit's figures)"""
+    _fields_ = [("steps", C.c_int), ("max_force", C.c_float), ("ray_radius", C.c_float), ("ray_force", C.c_float), ("flags", C.c_int)]
 
 
 class HTError(RuntimeError):
@@ -282,6 +289,9 @@ def load(build_if_missing=True):
     L.ht_keypoint_table.argtypes = [vp, ci, ip, ip, fp, ip]
     L.ht_keypoints.argtypes = [vp, fp, ci, ci, ci, ci, ip, fp, ip, u8p, fp, u16p, ci, ci, cf, cf, fp, fp, fp, u8p]
     L.ht_keypoints_dev.argtypes = [vp, vp, ci, ci, ci, ci, ip, fp, ip, vp, vp, vp, ci, ci, cf, cf, vp, vp, vp, vp, vp]
+    L.ht_kpfit_default.argtypes = [C.POINTER(KpFit)]
+    L.ht_fit_keypoints.argtypes = [vp, ci, ci, ci, ci, ip, fp, ip, ip, fp, fp, fp, fp, C.POINTER(KpFit), fp, fp]
+    L.ht_fit_keypoints_dev.argtypes = [vp, ci, ci, ci, ci, ip, fp, ip, ip, vp, vp, vp, vp, C.POINTER(KpFit), vp, vp, vp]
     L.ht_keypoint_errors.argtypes = [vp, fp, fp, ci, ci, fp, ci, fp, fp, dp, i64p, i64p]
     L.ht_keypoint_errors_dev.argtypes = [vp, vp, vp, ci, ci, fp, ci, vp, vp, vp, vp, vp, vp]
     L.ht_depth_compare.argtypes = [vp, u16p, u16p, ci, ci, ci, ci, ci, ci, i64p]
@@ -979,6 +989,39 @@ class Context:
         self._chk(self.L.ht_keypoints_dev(self.h, d_poses, int(B), KP_COM_POSES if com_poses else 0, which, K, tp[0], tp[1], tp[2], d_hands, d_cams, d_depth, int(w), int(h), float(near_tol), float(far_tol),
                                           d_xyz, d_pix, d_zc, d_vis, stream))
 
+    # -- keypoint fit (ht_mi355x.h "keypoint fit"): from keypoint targets to a pose
+    def _kp_count(self, which, K):
+        if which != KP_CALLER:
+            Kc = C.c_int(); self._chk(self.L.ht_keypoint_table(self.h, which, C.byref(Kc), None, None, None)); K = Kc.value
+        return K
+
+    def fit_keypoints(self, B, table=KP_SKELETON, xyz=None, pix=None, cams=None, weights=None, kind=None, options=None, which_model=0, want_poses=True, want_resid=True):
+        """Fits model which_model of slots [0,B) from its current state to the targets: xyz f32[B,K,3] for the keypoints of kind 0, pix f32[B,K,2] in cams f32[B,12]
+        for those of kind 1 (kind i32[K], None: all 0), weights f32[B,K] in [0,1] (0 or a NaN target: not annotated).  options: a KpFit (None: kpfit_default()).
+        -> dict(poses f32[B,nb,7] user poses, resid f32[B,2,K] before and after; -1: absent)."""
+        which, K, keep, tp = self._kp_table(table)
+        K = self._kp_count(which, K); B = int(B)
+        a = lambda x, tail: None if x is None else _c(x, np.float32).reshape((B, K) + tail)
+        xyz, pix, weights = a(xyz, (3,)), a(pix, (2,)), a(weights, ())
+        cams = None if cams is None else _c(cams, np.float32).reshape(B, CAM)
+        kind = None if kind is None else _c(kind, np.int32).reshape(K)
+        out = {}
+        if want_poses:
+            out["poses"] = np.empty((B, self.nb, POSE), np.float32)
+        if want_resid:
+            out["resid"] = np.empty((B, 2, K), np.float32)
+        g = lambda x: None if x is None else _f(x)
+        self._chk(self.L.ht_fit_keypoints(self.h, int(which_model), B, which, K if which == KP_CALLER else 0, tp[0], tp[1], tp[2], None if kind is None else _i(kind), g(xyz), g(pix), g(weights), g(cams),
+                                          None if options is None else C.byref(options), g(out.get("poses")), g(out.get("resid"))))
+        return out
+
+    def fit_keypoints_dev(self, B, table, d_xyz=None, d_pix=None, d_cams=None, d_weights=None, kind=None, options=None, which_model=0, d_poses=None, d_resid=None, stream=None):
+        """ht_fit_keypoints_dev: device pointers (the table and kind stay host arrays), only enqueued on `stream`."""
+        which, K, keep, tp = self._kp_table(table)
+        kind = None if kind is None else _c(kind, np.int32).reshape(-1)
+        self._chk(self.L.ht_fit_keypoints_dev(self.h, int(which_model), int(B), which, K, tp[0], tp[1], tp[2], None if kind is None else _i(kind), d_xyz, d_pix, d_weights, d_cams,
+                                              None if options is None else C.byref(options), d_poses, d_resid, stream))
+
     def keypoint_errors(self, a, b, thr=()):
         """a, b f32[B,K,3] -> dict(dist f32[B,K], frame f32[B,2] (mean, max), sum_kp f64[K], hits_kp i64[T], hits_frame i64[T], and from them mean_kp f64[K],
         mean f64, pck f64[T] = hits_kp / (B K), success f64[T] = hits_frame / B)."""
@@ -1297,6 +1340,20 @@ class Context:
                     out[name] = buf[o:o + n].reshape(shape)
                 o += n
         return out
+
+
+def kpfit_default(**kw):
+    """ht_kpfit_default's options (6 steps, FLT_MAX, radius 0.01, ray force 100000, no flags) with the given fields replaced; keep_momenta=True sets the flag."""
+    o = KpFit()
+    if load().ht_kpfit_default(C.byref(o)) != HT_OK:
+        raise HTError("ht_kpfit_default failed")
+    if kw.pop("keep_momenta", False):
+        o.flags |= KPFIT_KEEP_MOMENTA
+    for k, v in kw.items():
+        if not hasattr(o, k):
+            raise AttributeError(k)
+        setattr(o, k, v)
+    return o
 
 
 def sensor_noise_default(kind, depth_scale=0.001, far=4.0, **kw):

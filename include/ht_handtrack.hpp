@@ -700,6 +700,37 @@ struct HandTracker                                                              
 		if (info[2]) { r.mean_abs = (double)info[4] / (double)info[2] * ds; r.rms = std::sqrt((double)info[5] / (double)info[2]) * ds; }
 		return r;
 	}
+	// Addition, not a reference name (ht_mi355x.h "keypoint fit"): handmodel goes from its current pose to keypoint targets -- 3-D points (kind 0, three nailed rows a
+	// keypoint, physics.h:342-346) and pixels of targets.cam (kind 1, a dead-zone pair on each axis across the pixel's ray, physics.h:332-340) -- in options.steps solver
+	// steps that stay on the device.  table: handmodel.GetKeypoints(...) or the caller's own points; targets.kind empty: all points; targets.weights empty: all 1; a weight
+	// of 0 or a NaN target: not annotated.  Returns the user poses as update() does and every keypoint's residual before and after (-1: absent).  With left_hand set the
+	// point targets and the poses are the left hand's (mirrored on the way in and out); pixel targets of a left hand are refused: mirror the frame first.
+	struct KeypointFit : ht_kpfit { KeypointFit() { ht_kpfit_default(this); } };      // steps 6, max_force FLT_MAX, ray_radius 0.01, ray_force 100000, flags 0 (HT_KPFIT_KEEP_MOMENTA)
+	struct KeypointTargets { std::vector<float3> xyz; std::vector<float2> pixels; std::vector<int> kind; std::vector<float> weights; DCamera cam; };
+	struct KeypointFitResult { std::vector<Pose> pose; std::vector<float> before, after; };
+	KeypointFitResult fit_keypoints(const std::vector<ModelFeaturePoint> &table, const KeypointTargets &targets, const KeypointFit &options = KeypointFit())
+	{
+		const int K = (int)table.size();
+		std::vector<int> bones(K), rel(K); std::vector<float> off((size_t)K * 3);
+		for (int k = 0; k < K; k++) { bones[k] = table[k].bone; rel[k] = table[k].rel; off[3 * k] = table[k].offset.x; off[3 * k + 1] = table[k].offset.y; off[3 * k + 2] = table[k].offset.z; }
+		bool rays = false; for (int k : targets.kind) rays = rays || k != 0;
+		if ((!targets.kind.empty() && (int)targets.kind.size() != K) || (!targets.weights.empty() && (int)targets.weights.size() != K) || (!targets.xyz.empty() && (int)targets.xyz.size() != K) ||
+		    (!targets.pixels.empty() && (int)targets.pixels.size() != K))
+			throw std::runtime_error("fit_keypoints: one target, kind and weight per table entry");
+		if (rays && left_hand) throw std::runtime_error("fit_keypoints: pixel targets of a left hand: mirror the frame and its pixels first");
+		std::vector<float3> xyz = targets.xyz;
+		if (left_hand) for (auto &p : xyz) p.x = -p.x;
+		float cam[HT_CAM]; cam12(targets.cam, cam);
+		std::vector<float> poses((size_t)nb_ * HT_POSE), resid((size_t)2 * (K > 0 ? K : 1));
+		check(ctx_, ht_fit_keypoints(ctx_, 0, 1, HT_KP_CALLER, K, bones.data(), off.data(), rel.data(), targets.kind.empty() ? nullptr : targets.kind.data(), xyz.empty() ? nullptr : &xyz[0].x,
+		                             targets.pixels.empty() ? nullptr : &targets.pixels[0].x, targets.weights.empty() ? nullptr : targets.weights.data(), rays ? cam : nullptr, &options, poses.data(), resid.data()));
+		KeypointFitResult r;
+		r.pose.resize(nb_);
+		for (int b = 0; b < nb_; b++) { const float *p = &poses[(size_t)b * HT_POSE]; r.pose[b].position = { p[0], p[1], p[2] }; r.pose[b].orientation = { p[3], p[4], p[5], p[6] }; }
+		if (left_hand) r.pose = mirrored(r.pose);
+		r.before.assign(resid.begin(), resid.begin() + K); r.after.assign(resid.begin() + K, resid.begin() + 2 * K);
+		return r;
+	}
 	// Addition, not a reference name: GatherHandExpectedCNN (handtrack.h:160-173) for a batch of pose sets on this tracker's device, frame b seen by the
 	// heat-map camera hcams[b] (as the single-frame form takes it); segment_frame: train-cnn's compress first (train-cnn.cpp:31-50: the poses in the
 	// camera's frame, the camera at the identity).  The same ExpectedCNN sets as the single-frame form, bit for bit (ht_expected_cnn_batch).

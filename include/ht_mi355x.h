@@ -777,6 +777,39 @@ int ht_depth_compare_dev(ht_ctx *ctx, const uint16_t *d_a, const uint16_t *d_b, 
 int ht_pose_depth_residual(ht_ctx *ctx, const float *poses, const float *cams, const uint16_t *depth, int w, int h, int B, int flags, float far, int lo, int hi, int tol, int64_t *info, uint16_t *rendered);
 int ht_pose_depth_residual_dev(ht_ctx *ctx, const float *d_poses, const float *d_cams, const uint16_t *d_depth, int w, int h, int B, int flags, float far, int lo, int hi, int tol, int64_t *d_info, uint16_t *d_rendered, void *stream);
 
+/* ---- keypoint fit (an addition: the reference nails one dragged bone and pulls its own eight landmarks onto rays, one frame at a time) -----------------------
+ * From keypoint targets to a pose: the inverse of ht_keypoints.  The slots' current state of model which_model (0 handmodel, 1 othermodel) is the start pose; every
+ * step writes the targets' constraint rows from that state on the device and solves them with ht_fit_rows' own launch sequence without points (the joint ranges
+ * brought up to date, contacts if physics_use_collision, the rows ahead of the joints' rows); nothing is copied or waited for between the steps.
+ *   table      which / K / bones / offsets / rel exactly as ht_keypoints takes them (HT_KP_FEATURE8, HT_KP_SKELETON, HT_KP_CALLER; HOST arrays in both forms).
+ *   position   the states are centre-of-mass poses: rel = 1, o' = o; rel = 0, o' = o - com[bone]; X = pos + qrot(q, o').
+ *   kind [K]   HOST array in both forms, NULL = all 0.  0: a point target t = xyz[b][k], three rows as ConstrainPositionNailed writes them (physics.h:342-346): rb0 = -1,
+ *              rb1 = bone, position0 = t, position1 = o', normals (1,0,0), (0,1,0), (0,0,1), targetdist = (X - t) by component, forcelimit (-f, f).
+ *              1: a pixel target (u, v) = pix[b][k] in the frame's camera (pc, qc) = cams[b]: r = normalize(qrot(qc, ((u - cx) / fx, (v - cy) / fy, 1))) (deprojectz,
+ *              misc_image.h:48), q = quat_from_to((0,0,1), r); for the axes a = qxdir(q), then qydir(q): d = dot(X - pc, a) and the dead-zone pair of
+ *              ConstrainAlongDirectionDeadzone (physics.h:337-338): targetdist d + ray_radius with forcelimit (0, fr), then d - ray_radius with (-fr, 0); position0 = pc,
+ *              the camera's position (handtrack.h:672), so a camera away from the origin is served.  Four rows.
+ *   presence   a keypoint is present iff its weight > 0 (weights [B][K] optional, NULL = 1) and every target component it reads is finite: NaN is "not annotated".
+ *              Absent keypoints write no rows; the others keep the table's order.  f = max_force * weight, fr = ray_force * weight.
+ *   resid      [B][2][K], optional: at the start pose and after the last step; sqrtf(dx dx + dy dy + dz dz) of X - t for a point, the distance to the ray
+ *              sqrtf(d d + d' d') of the two axes' d for a pixel, -1 for an absent keypoint.
+ *   poses      [B][nb][7], optional: the user poses (GetPoseUser) after the last step, as the update calls return them.
+ *   options    steps in [1, 64]; max_force > 0 (INFINITY is taken as FLT_MAX); ray_radius >= 0; ray_force > 0.  HT_KPFIT_KEEP_MOMENTA: the momenta are never touched
+ *              (slowfit's behaviour); otherwise they are zeroed on entry and after every step (MultiStepSim's, handtrack.h:686-687).  NULL = ht_kpfit_default's:
+ *              6 steps, FLT_MAX, 0.01, 100000, no flags (slowfit's figures).
+ * xyz [B][K][3] is read (and required) only if kind 0 occurs, pix [B][K][2] and cams [B][12] only if kind 1 does.  Refused before anything grows or runs (HT_ERR_ARG /
+ * HT_ERR_STATE): a context without a hand model, the exact-order solver build, B outside [1, max_batch], a bad table or kind, a table of more than 5 * nb + 128 rows
+ * (3 a point, 4 a pixel), a missing array, bad options; the host form also refuses a weight outside [0, 1] and an output that overlaps an input.  A refused call leaves
+ * the context usable and the states unchanged.  The _dev form takes device arrays, grows the context's row buffer before its first launch and only enqueues on
+ * `stream`; the host form stages through the context's buffer and returns when the work is done.  Slots >= B are not touched.  Like ht_fit_rows, the call leaves
+ * the slots' prepared points empty (follow with ht_update_passes_sync or ht_stage_prepare for a depth cloud).  There is no left-hand form: mirror the targets
+ * (x -> -x) and bring the poses back with ht_mirror_poses. */
+#define HT_KPFIT_KEEP_MOMENTA 1
+typedef struct { int steps; float max_force, ray_radius, ray_force; int flags; } ht_kpfit;
+int ht_kpfit_default(ht_kpfit *o);
+int ht_fit_keypoints(ht_ctx *ctx, int which_model, int B, int which, int K, const int *bones, const float *offsets, const int *rel, const int *kind, const float *xyz, const float *pix, const float *weights, const float *cams, const ht_kpfit *o, float *poses, float *resid);
+int ht_fit_keypoints_dev(ht_ctx *ctx, int which_model, int B, int which, int K, const int *bones, const float *offsets, const int *rel, const int *kind, const float *d_xyz, const float *d_pix, const float *d_weights, const float *d_cams, const ht_kpfit *o, float *d_poses, float *d_resid, void *stream);
+
 /* ---- annotation fit loop ---------------------------------------------------------------------------------------------
  * ht_slowfit          replaces  void HandTracker::slowfit(const std::vector<float3> &points, int hold, const std::vector<Pose> &refpose,
  *                     int steps_ = 6, RigidBody *selectrb = NULL, const float3 &spoint, const float3 &rbpoint, const std::vector<float4> &crays)
