@@ -1311,6 +1311,8 @@ void ht_launch_contact_order(const int *work, int *order, int B, int nfr, int st
 	const int seg = (HT_RANK_SEG / nfr) * nfr, nseg = (B + seg - 1) / seg, first = B < seg ? B : seg, places = (first + nfr - 1) / nfr * nfr;
 	hipLaunchKernelGGL(k_contact_order, dim3(nslots, nseg, (places + CO_ORDER_PART - 1) / CO_ORDER_PART), dim3(CO_ORDER_PART), (size_t)((first + 3) & ~3) * sizeof(int), s, work, order, B, nfr, stride, slots, epb);
 }
+// Waves per frame of the lane-per-pair kernel: two for a model of more than 200 body pairs (the comment at GJK_MAXWPF)
+int ht_contacts_lane_waves(const ht_model_dev &M) { return M.nb * (M.nb - 1) / 2 > 200 ? 2 : 1; }
 void ht_launch_contacts(const ht_model_dev &M, const float *state, float driftmax, float jiggle_sin, const int *active_flag, void *epa_ws, float *contacts, int *ncontacts, int B, hipStream_t s, bool beside_cloud_rows, int force_kernel, int few_frames,
                         const int *order, int *work_out)
 {
@@ -1324,7 +1326,7 @@ void ht_launch_contacts(const ht_model_dev &M, const float *state, float driftma
 		                   p.few ? nullptr : order, work_out);      // the tables deal the frames over the blocks of the whole-batch form
 		return;
 	}
-	const int wpf = M.nb * (M.nb - 1) / 2 > 200 ? 2 : 1;
+	const int wpf = ht_contacts_lane_waves(M);
 	const size_t smem = (size_t)M.vert_off[M.nb] * sizeof(float4) + GJK_FRAMES * gjk_frame_stride() + GJK_FRAMES * wpf * gjk_wave_stride();
 	const dim3 grid((B + GJK_FRAMES - 1) / GJK_FRAMES);
 	if (wpf == 2) hipLaunchKernelGGL(k_contacts<2>, grid, dim3(64 * GJK_FRAMES * 2), smem, s, M, state, driftmax, jiggle_sin, active_flag, contacts, ncontacts, B, dbg, caps);

@@ -86,6 +86,7 @@ void ht_launch_chamber(const ht_model_dev &M, const float *state, const float *p
 struct coop_plan { int nfr; size_t lds; bool few; };
 coop_plan ht_contacts_coop_plan(const ht_model_dev &M, int B, bool few_frames = false);
 bool ht_contacts_coop(const ht_model_dev &M, int B, int force_kernel, bool beside_cloud_rows);
+int ht_contacts_lane_waves(const ht_model_dev &M);      // waves per frame of the lane-per-pair kernel (k_contacts<1> / k_contacts<2>)
 void ht_launch_contacts(const ht_model_dev &M, const float *state, float driftmax, float jiggle_sin, const int *active_flag, void *epa_ws, float *contacts, int *ncontacts, int B, hipStream_t s, bool beside_cloud_rows = false, int force_kernel = 0, int few_frames = 0,
                         const int *order = nullptr, int *work_out = nullptr);      // order / work_out (cooperative kernel only, both may be null): the frame of every (slot, block) as k_contact_order dealt them for the plan's whole-batch form; where every live frame leaves what it cost
 #define HT_CONTACT_SLOTS 16      // unmasked contact launches of an update that keep a work history: MultiStepSim step st -> slot st (< 8), main-thread pass i -> slot 8 + i

@@ -1150,6 +1150,16 @@ extern "C" int ht_debug_contact_kernel(ht_ctx *ctx, int which)
 	ctx->contact_kernel = which;
 	return HT_OK;
 }
+// Tests only: which kernel a contact launch on B frames takes under the current pin, from the launcher's own functions: the cooperative kernel's frames per block
+// (0 = not taken, e.g. because a frame of the model does not fit its LDS) and the lane-per-pair kernel's waves per frame (0 = not taken; 2 = k_contacts<2>).
+extern "C" int ht_debug_contact_plan(ht_ctx *ctx, int B, int *coop_frames, int *lane_waves)
+{
+	CHECK_READY(ctx); CHECK_MODEL(ctx); CHECK_BATCH(ctx, B);
+	const bool coop = ht_contacts_coop(ctx->model, B, ctx->contact_kernel, false);
+	if (coop_frames) *coop_frames = coop ? ht_contacts_coop_plan(ctx->model, B).nfr : 0;
+	if (lane_waves) *lane_waves = coop ? 0 : ht_contacts_lane_waves(ctx->model);
+	return HT_OK;
+}
 // Tests only: the launch tables of one slot from a work array the caller gives.  The product's launchers on the context's stream, over buffers of the call's own
 // (stride as the context lays its histories out: B + 8), preset to -1 so that a place no block wrote shows.
 //   ht_debug_contact_order: order_out[ceil(B / nfr) * nfr] = k_contact_order's table (order_out[round * blocks + block] = frame, B = no frame); 1 <= nfr <= 8, epb >= 1

@@ -39,7 +39,7 @@ SYMBOLS = (
     "ht_cnn_opt_reset_sized", "ht_cnn_opt_state_get_sized", "ht_cnn_opt_state_set_sized", "ht_cnn_opt_last_sized", "ht_cnn_train_opt_sized_dev",
     "ht_model_open", "ht_model_close", "ht_model_error", "ht_model_counts", "ht_model_body", "ht_model_body_mesh", "ht_model_body_sdmesh", "ht_model_hitcheck", "ht_model_hitcheck_mesh", "ht_model_render_mesh", "ht_model_scale", "ht_render_mesh_depth", "ht_render_mesh_depth_dev",
     "ht_tracker_reset", "ht_get_state", "ht_set_state", "ht_get_tracker_flags", "ht_set_tracker_flags", "ht_update_sync", "ht_update_dev", "ht_update_frames_sync", "ht_update_frames_dev", "ht_update_direct_sync", "ht_update_direct_dev", "ht_update_cnn_model_sync", "ht_get_cnn_results", "ht_get_cnn_layers", "ht_get_cnn_layers_sized", "ht_frames_overflow", "ht_reserve_points", "ht_point_capacity", "ht_capacity_events", "ht_segment_vr", "ht_segment_vr_dev", "ht_segment_vr_supported", "ht_segment_vr_sized", "ht_segment_vr_sized_dev", "ht_update_frames_sized_sync", "ht_update_frames_sized_dev", "ht_render_depth", "ht_render_depth_dev", "ht_slowfit", "ht_set_points", "ht_fit_rows", "ht_physics_update",
-    "ht_stage_prepare", "ht_stage_decode", "ht_stage_fit_error", "ht_stage_cloud_rows", "ht_stage_contacts", "ht_stage_fit",
+    "ht_stage_prepare", "ht_stage_decode", "ht_stage_fit_error", "ht_stage_cloud_rows", "ht_stage_contacts", "ht_stage_fit", "ht_debug_contact_plan",
     "ht_stage_multistep", "ht_stage_multistep_range", "ht_stage_scratch_unibody", "ht_stage_chamber", "ht_profile_enable", "ht_profile_read", "ht_debug_solve_stats", "ht_debug_contact_stats", "ht_debug_solver_build", "ht_debug_reset_flags", "ht_debug_reset_organisation", "ht_update_passes_sync", "ht_job_start", "ht_job_poll", "ht_job_wait", "ht_job_collect", "ht_debug_contact_kernel", "ht_debug_contact_order", "ht_debug_rank_desc", "ht_contact_capacity", "ht_debug_solve_tables", "ht_debug_solve_tables_header", "ht_debug_train_buffers",
     "ht_sensor_out_dims", "ht_sensor_filter", "ht_sensor_filter_dev", "ht_sensor_background", "ht_sensor_background_dev",
     "ht_sensor_noise_default", "ht_sensor_simulate", "ht_sensor_simulate_dev",
@@ -242,6 +242,7 @@ def load(build_if_missing=True):
     L.ht_debug_reset_organisation.argtypes = [vp, ip]
     L.ht_debug_reset_flags.argtypes = [vp, ip, C.c_int]
     L.ht_debug_contact_kernel.argtypes = [vp, C.c_int]
+    L.ht_debug_contact_plan.argtypes = [vp, C.c_int, ip, ip]
     L.ht_debug_contact_order.argtypes = [vp, ip, C.c_int, C.c_int, C.c_int, ip]
     L.ht_debug_rank_desc.argtypes = [vp, ip, C.c_int, ip]
     L.ht_debug_solve_tables.argtypes = [vp, C.c_int]
@@ -813,6 +814,13 @@ class Context:
     def debug_contact_kernel(self, which):
         """Test aid: pin the contact kernel's organisation (0 auto, 1 cooperative, 2 lane-per-pair).  Same contacts either way."""
         self._chk(self.L.ht_debug_contact_kernel(self.h, int(which)))
+
+    def debug_contact_plan(self, B):
+        """Test aid: (frames per block of the cooperative kernel, waves per frame of the lane-per-pair kernel) of a contact launch on B frames under the current pin; the
+        kernel that does not run has 0."""
+        a, b = C.c_int(0), C.c_int(0)
+        self._chk(self.L.ht_debug_contact_plan(self.h, int(B), C.byref(a), C.byref(b)))
+        return a.value, b.value
 
     def debug_contact_order(self, work, nfr, epb):
         """Test aid: k_contact_order's table for one launch slot from the per-frame costs `work` (candidates + 2 x patches | polytope runs << 16): [nfr, ceil(B / nfr)],

@@ -914,6 +914,10 @@ int ht_debug_reset_organisation(ht_ctx *ctx, int *many);
 /* Test aid: pins the organisation of the contact kernel (0 = chosen per launch: the cooperative kernel whenever the model fits its LDS; 1 cooperative,
  * 2 one lane group per body pair).  Same contacts in the same order either way. */
 int ht_debug_contact_kernel(ht_ctx *ctx, int which);
+/* Test aid: the kernel a contact launch on B frames takes under that pin: *coop_frames = frames per block of the cooperative kernel (0: the lane-group kernel runs, also
+ * under pin 1 when a frame of the model does not fit the cooperative kernel's LDS), *lane_waves = waves per frame of the lane-group kernel (0: the cooperative kernel
+ * runs; 2 for models of more than 200 body pairs). */
+int ht_debug_contact_plan(ht_ctx *ctx, int B, int *coop_frames, int *lane_waves);
 /* Test aid: the launch tables an update makes at its head from the previous update's per-frame costs, here from a cost array the caller gives (one launch slot, host memory):
  * ht_debug_contact_order: the assignment of frames to the cooperative contact kernel's blocks of nfr frames (1-8; epb: frames with polytope runs per block);
  *   order_out[ceil(B / nfr) * nfr], order_out[round * blocks + block] = frame, B = no frame.  work[i] = candidate pairs + 2 x patches | polytope runs << 16.

@@ -193,6 +193,17 @@ static int above(const f3 *verts, const int t[3], f3 p, float epsilon)   /* hull
 	f3 n = tri_normal(verts[t[0]], verts[t[1]], verts[t[2]]);
 	return dot3(n, sub3(p, verts[t[0]])) > epsilon;
 }
+/* counters around expanding_polytope (tests: which polytope sizes a scene set reaches); results are unchanged */
+static int epa_runs, epa_max_verts, epa_max_tris, epa_max_iterations, epa_peak_tris;
+void ho_epa_stats(int *runs, int *max_verts, int *max_tris, int *max_iterations, int reset)
+{
+	if (runs) *runs = epa_runs;
+	if (max_verts) *max_verts = epa_max_verts;
+	if (max_tris) *max_tris = epa_max_tris;
+	if (max_iterations) *max_iterations = epa_max_iterations;
+	if (reset) epa_runs = epa_max_verts = epa_max_tris = epa_max_iterations = epa_peak_tris = 0;
+}
+int ho_epa_peak_tris(void) { return epa_peak_tris; }
 static f4 expanding_polytope(const f3 start[4], const support_t *A, const support_t *B)   /* hull.h:233-310 */
 {
 	f4 plane = F4(0, 0, 0, -FLT_MAX);
@@ -204,9 +215,12 @@ static f4 expanding_polytope(const f3 start[4], const support_t *A, const suppor
 	f3 center = div3(add3(add3(add3(verts[0], verts[1]), verts[2]), verts[3]), 4.0f);
 	if (dot3(cross3(sub3(verts[2], verts[0]), sub3(verts[1], verts[0])), sub3(verts[3], verts[0])) > 0.0f) { f3 tmp = verts[2]; verts[2] = verts[3]; verts[3] = tmp; }
 	tv_push(&tv, 2, 3, 1, 0, 2, 3, 1); tv_push(&tv, 3, 2, 0, 1, 3, 2, 0); tv_push(&tv, 0, 1, 3, 2, 0, 1, 3); tv_push(&tv, 1, 0, 2, 3, 1, 0, 2);
+	epa_runs++;
 	for (int guard = 0; guard < 256; guard++)
 	{
 		f4 face = F4(0, 0, 0, -FLT_MAX);
+		if (guard + 1 > epa_max_iterations) epa_max_iterations = guard + 1;
+		if (tv.n > epa_max_tris) epa_max_tris = tv.n;
 		for (int i = 0; i < tv.n; i++)
 		{
 			tri_t *t = &tv.t[i];
@@ -244,6 +258,8 @@ static f4 expanding_polytope(const f3 start[4], const support_t *A, const suppor
 				j = tv.n;
 			}
 		}
+		if (nv > epa_max_verts) epa_max_verts = nv;
+		if (tv.n > epa_peak_tris) epa_peak_tris = tv.n;
 		j = tv.n;
 		while (j--)
 		{

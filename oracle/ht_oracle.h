@@ -137,6 +137,10 @@ void ho_unibody_fit(ho_tracker *t, ho_model *m, const f3 *pts, int n, f3 camera_
 typedef struct ho_gjk_contact { f3 normal, p0w, p1w, impact; float separation, dist; int type; } ho_gjk_contact;
 ho_gjk_contact ho_separated_bodies(const ho_body *a, const ho_body *b);
 int ho_contact_patch_bodies(const ho_body *a, const ho_body *b, float max_separation, ho_gjk_contact *out5);
+/* counters around the expanding polytope since the last reset: runs, most vertices, most triangles at a face search (the live mesh), most face searches of one run;
+ * ho_epa_peak_tris: most triangles held at once, the extruded ones not yet removed included.  Results are unchanged. */
+void ho_epa_stats(int *runs, int *max_verts, int *max_tris, int *max_iterations, int reset);
+int ho_epa_peak_tris(void);
 
 /* ---- the unit of work: update_cnn_model + mainthreadpasses passes (handtrack.h:693-785, synchronous) ---- */
 int ho_update_cnn_model(ho_tracker *t, const uint16_t *depth, const ho_camera *cam, float *pose_out7);   /* returns number of poses (0 or nb) */

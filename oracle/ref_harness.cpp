@@ -37,6 +37,10 @@
 //   e2e128 <frames128.htfx> <idx,comma> <seed> <fc2gain> <out.htfx>   BASELINE configs[4] end to end (SURVEY 8d config 5 i-iii): that net, its decode with
 //                                                  camsub(cam, 8) and the tracker's stages called directly on the 128x128 frame, no segmentation
 //   bench128 <frames128.htfx> <seed> <fc2gain> <reps> [maxframes]    reference CPU time of that unit of work
+//   contacts <hand|model.json> <scale> <scenes.htfx> <out.htfx>   the narrow phase on generated scenes (tests/contact_scenes.py): every row of "pairs" [n,16] through
+//                                                  Separated and ContactPatch as S13 of `golden` does, plus the contact count of FindShapeShapeContacts with every other
+//                                                  body parked; every state of "poses" [m,nb,7] through FindShapeShapeContacts as S7 does.  "clear_ignore" [k,2]: pairs
+//                                                  taken off the model's ignore lists first.  A scene on which the reference throws is flagged, not fatal.
 //
 #include "/root/reference/include/handtrack.h"
 #include "/root/reference/include/dataset.h"
@@ -1270,6 +1274,75 @@ static int mode_dataset_header(const char *jsonfn, const char *posefn, int npose
 	return 0;
 }
 
+// The reference's answers to generated contact scenes (tests/contact_scenes.py, tests/golden/make_contact_fuzz.py)
+static int mode_contacts(const char *model, double sc, const char *infn, const char *outfn)
+{
+	HandTracker htk;      // sets the physics globals (handtrack.h:837-838); its hand model is the "hand" of the first argument
+	std::unique_ptr<PhysModel> own;
+	if (std::string(model) != "hand") own.reset(new PhysModel(model));
+	if (sc != 1.0) { if (own) own->scale((float)sc); else htk.scale((float)sc); }
+	PhysModel &m = own ? *own : htk.handmodel;
+	const int nb = (int)m.rigidbodies.size();
+	std::vector<float> pairs, poses; std::vector<int> clear; uint32_t npair = 0, npose = 0;
+	for (auto &a : htfx_read(infn))
+	{
+		if (a.name == "pairs") { npair = a.dims[0]; pairs.assign((const float *)a.data.data(), (const float *)a.data.data() + a.data.size() / 4); }
+		if (a.name == "poses") { npose = a.dims[0]; if ((int)a.dims[1] != nb) { fprintf(stderr, "poses are for %d bodies, the model has %d\n", (int)a.dims[1], nb); return 2; } poses.assign((const float *)a.data.data(), (const float *)a.data.data() + a.data.size() / 4); }
+		if (a.name == "clear_ignore") clear.assign((const int *)a.data.data(), (const int *)a.data.data() + a.data.size() / 4);
+	}
+	for (size_t k = 0; k + 1 < clear.size(); k += 2)
+	{
+		RigidBody *x = &m.rigidbodies[clear[k]], *y = &m.rigidbodies[clear[k + 1]];
+		x->ignore.erase(std::remove(x->ignore.begin(), x->ignore.end(), y), x->ignore.end());
+		y->ignore.erase(std::remove(y->ignore.begin(), y->ignore.end(), x), y->ignore.end());
+	}
+	auto put_contacts = [&](std::vector<float> &v, const std::vector<PhysContact> &C)
+	{
+		for (auto &c : C)
+		{
+			v.push_back((float)rbidx(m, c.rb0)); v.push_back((float)rbidx(m, c.rb1));
+			for (int i = 0; i < 3; i++) v.push_back(c.normal[i]); for (int i = 0; i < 3; i++) v.push_back(c.p0w[i]); for (int i = 0; i < 3; i++) v.push_back(c.p1w[i]);
+			v.push_back(c.separation);
+		}
+	};
+	std::vector<float> pout((size_t)npair * 46, 0.0f); std::vector<int> pn(npair, 0), pfail(npair, 0);
+	for (uint32_t k = 0; k < npair; k++)
+	{
+		const float *c = &pairs[(size_t)k * 16];
+		const int a = (int)c[0], b = (int)c[1];
+		for (int i = 0; i < nb; i++) { m.rigidbodies[i].position = float3(10.0f * (1 + i), 0, 0); m.rigidbodies[i].orientation = float4(0, 0, 0, 1); }
+		auto &A = m.rigidbodies[a]; auto &B = m.rigidbodies[b];
+		A.position = float3(c[2], c[3], c[4]); A.orientation = float4(c[5], c[6], c[7], c[8]); B.position = float3(c[9], c[10], c[11]); B.orientation = float4(c[12], c[13], c[14], c[15]);
+		try
+		{
+			float *o = &pout[(size_t)k * 46];
+			auto h = Separated(SupportFunc(&A, A.shapes[0]), SupportFunc(&B, B.shapes[0]), 1);
+			for (int i = 0; i < 3; i++) { o[i] = h.normal[i]; o[3 + i] = h.p0w[i]; o[6 + i] = h.p1w[i]; } o[9] = h.separation;
+			auto patch = ContactPatch(SupportFunc(&A, A.shapes[0]), SupportFunc(&B, B.shapes[0]), physics_driftmax);
+			o[10] = (float)patch.count;
+			for (int q = 0; q < patch.count && q < 5; q++) { for (int i = 0; i < 3; i++) { o[11 + 7 * q + i] = patch[q].p0w[i]; o[14 + 7 * q + i] = patch[q].p1w[i]; } o[17 + 7 * q] = patch[q].separation; }
+			std::vector<PhysContact> C; FindShapeShapeContacts(C, Addresses(m.rigidbodies));
+			pn[k] = (int)C.size();
+		}
+		catch (...) { pfail[k] = 1; for (int i = 0; i < 46; i++) pout[(size_t)k * 46 + i] = 0; pn[k] = 0; }
+	}
+	std::vector<float> sout; std::vector<int> sn(npose, 0), sfail(npose, 0);
+	for (uint32_t k = 0; k < npose; k++)
+	{
+		const float *p = &poses[(size_t)k * nb * 7];
+		for (int i = 0; i < nb; i++) { m.rigidbodies[i].position = float3(p[7 * i], p[7 * i + 1], p[7 * i + 2]); m.rigidbodies[i].orientation = float4(p[7 * i + 3], p[7 * i + 4], p[7 * i + 5], p[7 * i + 6]); }
+		try { std::vector<PhysContact> C; FindShapeShapeContacts(C, Addresses(m.rigidbodies)); sn[k] = (int)C.size(); put_contacts(sout, C); }
+		catch (...) { sfail[k] = 1; }
+	}
+	Out o; if (htfx_open(&o.w, outfn)) return 2;
+	if (npair) { o.f32("pair_out", pout, { npair, 46 }); o.i32("pair_scene_n", pn); o.i32("pair_failed", pfail); }
+	if (npose) { o.i32("scene_n", sn); o.i32("scene_failed", sfail); if (sout.empty()) sout.assign(12, 0.0f); o.f32("scene_contacts", sout, { (uint32_t)(sout.size() / 12), 12 }); }
+	htfx_close(&o.w);
+	int bad = 0; for (int f : pfail) bad += f; for (int f : sfail) bad += f;
+	printf("contacts: %d pair scenes, %d whole scenes, %d the reference threw on -> %s\n", (int)npair, (int)npose, bad, outfn);
+	return 0;
+}
+
 int main(int argc, char **argv) try
 {
 	if (argc < 2) { fprintf(stderr, "usage: see header of ref_harness.cpp\n"); return 1; }
@@ -1301,6 +1374,7 @@ int main(int argc, char **argv) try
 	if (mode == "poses" && a.size() == 5 && a[4] == "takecnn") return mode_poses(a[0].c_str(), strtoull(a[1].c_str(), 0, 0), atof(a[2].c_str()), a[3].c_str(), 1);
 	if (mode == "viz" && a.size() == 3) return mode_viz(a[0].c_str(), atoi(a[1].c_str()), a[2].c_str());
 	if (mode == "posesfull" && a.size() == 4) return mode_posesfull(a[0].c_str(), strtoull(a[1].c_str(), 0, 0), atof(a[2].c_str()), a[3].c_str());
+	if (mode == "contacts" && a.size() == 4) return mode_contacts(a[0].c_str(), atof(a[1].c_str()), a[2].c_str(), a[3].c_str());
 	if (mode == "bench" && a.size() >= 4) return mode_bench(a[0].c_str(), strtoull(a[1].c_str(), 0, 0), atof(a[2].c_str()), atoi(a[3].c_str()), a.size() > 4 ? atoi(a[4].c_str()) : 0);
 	fprintf(stderr, "bad arguments\n");
 	return 1;

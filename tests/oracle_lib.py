@@ -123,6 +123,9 @@ def lib():
         L.ho_model_ptr.argtypes = [C.c_void_p, C.c_int]; L.ho_model_ptr.restype = C.c_void_p
         L.ho_contact_patch_bodies.argtypes = [C.c_void_p, C.c_void_p, C.c_float, C.POINTER(GjkContact)]; L.ho_contact_patch_bodies.restype = C.c_int
         L.ho_separated_bodies.argtypes = [C.c_void_p, C.c_void_p]; L.ho_separated_bodies.restype = GjkContact
+        ip = C.POINTER(C.c_int)
+        L.ho_epa_stats.argtypes = [ip, ip, ip, ip, C.c_int]; L.ho_epa_stats.restype = None
+        L.ho_epa_peak_tris.argtypes = []; L.ho_epa_peak_tris.restype = C.c_int
         L.ho_body_ptr.argtypes = [C.c_void_p, C.c_int]; L.ho_body_ptr.restype = C.c_void_p
         L.ho_scale.argtypes = [C.c_void_p, C.c_float]
         L.ho_cnn_train.argtypes = [fp, fp, fp, C.c_float]; L.ho_cnn_train.restype = C.c_float
@@ -215,6 +218,14 @@ class Oracle:
 
     def reset(self, pose7):
         self.L.ho_reset_tracker(self.h, fptr(np.ascontiguousarray(pose7, dtype=np.float32)))
+
+
+def epa_stats(reset=False):
+    """(runs, max_verts, max_tris, max_iterations, peak_tris) of the restatement's expanding polytope since the last reset (ho_epa_stats)"""
+    v = [C.c_int(0) for _ in range(4)]
+    peak = lib().ho_epa_peak_tris()
+    lib().ho_epa_stats(*[C.byref(x) for x in v], 1 if reset else 0)
+    return tuple(x.value for x in v) + (peak,)
 
 
 def segment_vr(depth, cam12, entry_options=0xF, wrange=(0.1, 0.65), diam=0.17):
