@@ -246,52 +246,58 @@ static void reset_path(ht_ctx *ctx, bool listed, int n_unibody, int B, hipStream
 }
 
 // ---- the whole unit of work on device buffers --------------------------------------------------------------------------
-// `fs` != null: d_depth / d_cams are full-size frames (handtrack.h:693-785 with dim != 64x64).  The tracker segments them for the CNN
-// (handtrack.h:697-698) and from then on ctx->d_cams holds the SEGMENT cameras (CNN decode, landmark rays, PoseFromScratch, UnibodyFit and
-// MultiStepSim take segment.cam.pose); the point cloud and FitError keep the full frame and its camera.
-// `direct` != 0: the frame (direct x direct pixels) is its own segment and feeds the net of that input size -- what HandSegmentVR returns for a frame of the net's
-// size (handtrack.h:283-284), the stages of :693-729 called directly (BASELINE configs[4] end to end, SURVEY 8d config 5 i-iii); heat-map camera camsub(cam, direct / 16).
-// `side`: the tile side the segment is cut at, that of the net that looks at it (64: the reference's; 128: the sized calls, ht_update_frames_sized_*): the segment camera
-// of side 128 is that of side 64 with focal doubled and principal (64,64), its heat-map camera camsub(cam, 8) is camsub(cam64, 4), and the pose is the same pose.
-struct frame_src { int w, h; float segment_scale; int direct; int side = 64; };
+// What an update call's d_depth / d_cams hold, by name (resolve_frames, below, makes it from an entry point's arguments and is the only place that compares sizes):
+//   FRAME_TILE         the reference's 64x64 tile for the 64x64 net; the camera copy and the re-seeding from start poses ride on k_prepare
+//   FRAME_OWN_SEGMENT  a side x side frame that is its own segment and feeds the net of that input size -- what HandSegmentVR returns for a frame of the net's size
+//                      (handtrack.h:283-284), the stages of :693-729 called directly (BASELINE configs[4] end to end, SURVEY 8d config 5 i-iii); heat-map camera
+//                      camsub(cam, side / 16).  Arises for side 128 only (at side 64 it is the tile)
+//   FRAME_SEGMENTED    a full-size frame (handtrack.h:693-785 with dim != 64x64): the tracker segments it for the CNN (:697-698) at `side`, the tile side of the net that
+//                      looks at it (64: the reference's; 128: the sized calls -- the segment camera of side 128 is that of side 64 with focal doubled and principal
+//                      (64,64), its heat-map camera camsub(cam, 8) is camsub(cam64, 4), and the pose is the same pose).  From then on ctx->d_cams holds the SEGMENT
+//                      cameras (CNN decode, landmark rays, PoseFromScratch, UnibodyFit and MultiStepSim take segment.cam.pose); the point cloud and FitError keep the
+//                      full frame and its camera, whose cloud the point capacity can cut short (d_overflow counts such frames; the host forms report them)
+// w x h: the image FitError looks at (a tile's 64 x 64).  `side`: the input side of the net (ht_net_of).  `px64`: the frame has a tile's pixels whatever its kind (a 64x64
+// frame at side 128 is segmented like any other): the host forms upload such frames to d_depth / d_cams (stage_frames).
+enum frame_kind { FRAME_TILE, FRAME_OWN_SEGMENT, FRAME_SEGMENTED };
+struct frame_src { frame_kind kind; int w, h, side; float segment_scale; bool px64; };
 // `mode`: UPD_FULL = HandTracker::update (handtrack.h:748-785); UPD_CNN_MODEL = update_cnn_model alone (:734-741): othermodel is NOT re-seeded from
 // handmodel, no main-thread passes, no "initializing = 50" rule, the result is othermodel.GetPose() plus the accept decision, handmodel untouched;
 // UPD_KICKSTART = kickstart (:743-746) = the same followed by handmodel.SetPose(pose) where the pose was accepted.
 // UPD_PASSES = only the caller's part of update() (:751-753, 769-785): the cloud of the frame, the main-thread passes on handmodel, the user poses (the overlapped mode, ht_update_passes_sync)
 enum { UPD_FULL = 0, UPD_CNN_MODEL = 1, UPD_KICKSTART = 2, UPD_PASSES = 3 };
-struct update_call { const uint16_t *d_depth; const float *d_cams, *d_start; int B; float *d_poses_out, *d_cnn_out; hipStream_t s; const frame_src *fs; int mode; const float *img_cams; int iw, ih; const ht_net *net; };      // one update call: what the caller gave, where FitError finds the image (update_inputs: the full-size frame and its cameras, or the tile), and the net that looks at it (run_update_)
+struct update_call { const uint16_t *d_depth; const float *d_cams, *d_start; int B; float *d_poses_out, *d_cnn_out; hipStream_t s; frame_src fs; int mode; const float *img_cams; const ht_net *net; };      // one update call: what the caller gave, where FitError finds the image (update_inputs: the full-size frame and its cameras, or the tile), and the net that looks at it (run_update_)
 static bool main_thread_cloud_voxel(const ht_ctx *ctx, const update_call &u) { return (u.mode == UPD_FULL || u.mode == UPD_PASSES) && ctx->par.subsample_voxel; }
 
 // Input staging: the point capacity this frame size needs, the segment for the net (full-size frames), the net's input, the cloud(s), the launch order by point counts
 static int update_inputs(ht_ctx *ctx, update_call &u)
 {
 	const ht_params &p = ctx->par;
-	const frame_src *fs = u.fs; const uint16_t *d_depth = u.d_depth; const float *d_cams = u.d_cams; const int B = u.B, mode = u.mode; hipStream_t s = u.s;
-	u.iw = fs ? fs->w : 64; u.ih = fs ? fs->h : 64;      // the image FitError looks at
-	{ const int npx = u.iw * u.ih, fr = p.subsample_fraction > 0 ? p.subsample_fraction : 1, n = main_thread_cloud_voxel(ctx, u) ? npx : (npx + fr - 1) / fr; if (n > ctx->model.pts_cap) { const int r = ht_reserve_points_locked(ctx, n); if (r) return r; } ctx->model.pts_bound = (n + 63) & ~63; }
+	const frame_src &fs = u.fs; const uint16_t *d_depth = u.d_depth; const float *d_cams = u.d_cams; const int B = u.B, mode = u.mode; hipStream_t s = u.s;
+	const bool tile = fs.kind == FRAME_TILE, own = fs.kind == FRAME_OWN_SEGMENT, segment = fs.kind == FRAME_SEGMENTED && mode != UPD_PASSES;      // (the caller's part of the overlapped update has no segment and no net)
+	{ const int npx = fs.w * fs.h, fr = p.subsample_fraction > 0 ? p.subsample_fraction : 1, n = main_thread_cloud_voxel(ctx, u) ? npx : (npx + fr - 1) / fr; if (n > ctx->model.pts_cap) { const int r = ht_reserve_points_locked(ctx, n); if (r) return r; } ctx->model.pts_bound = (n + 63) & ~63; }
 	u.img_cams = ctx->d_cams;
-	if (fs)
+	if (!tile)
 	{
 		int r;      // the three buffers of the full-size path: the two of fixed size by the one this asks for last, the tiles following the largest side seen
 		if (!ctx->d_overflow && ((r = dev_alloc(ctx, &ctx->d_frame_cams, (size_t)ctx->B * HT_CAM)) || (r = dev_alloc(ctx, &ctx->d_overflow, 1)))) return r;
-		if ((r = dev_grow(ctx, &ctx->d_seg_tiles, &ctx->seg_tiles_cap, (size_t)ctx->B * fs->side * fs->side))) return r;
+		if ((r = dev_grow(ctx, &ctx->d_seg_tiles, &ctx->seg_tiles_cap, (size_t)ctx->B * (own ? 64 * 64 : fs.side * fs.side)))) return r;      // (a frame that is its own segment cuts no tile: the buffer comes with the first frame call, at the reference's side)
 		HIPCHK(ctx, hipMemcpyAsync(ctx->d_frame_cams, d_cams, (size_t)B * HT_CAM * sizeof(float), hipMemcpyDeviceToDevice, s));
 		HIPCHK(ctx, hipMemsetAsync(ctx->d_overflow, 0, sizeof(int), s));
-		if (fs->direct) { if (d_cams != ctx->d_cams) HIPCHK(ctx, hipMemcpyAsync(ctx->d_cams, d_cams, (size_t)B * HT_CAM * sizeof(float), hipMemcpyDeviceToDevice, s)); }      // segment.cam = the frame's camera
-		else if (mode != UPD_PASSES) ht_launch_segment(d_depth, ctx->d_frame_cams, fs->w, fs->h, 0xF, p.drangey, fs->segment_scale, ctx->d_seg_tiles, ctx->d_cams, B, s, fs->side);
+		if (own) { if (d_cams != ctx->d_cams) HIPCHK(ctx, hipMemcpyAsync(ctx->d_cams, d_cams, (size_t)B * HT_CAM * sizeof(float), hipMemcpyDeviceToDevice, s)); }      // segment.cam = the frame's camera
+		else if (segment) ht_launch_segment(d_depth, ctx->d_frame_cams, fs.w, fs.h, 0xF, p.drangey, fs.segment_scale, ctx->d_seg_tiles, ctx->d_cams, B, s, fs.side);
 		u.img_cams = ctx->d_frame_cams;
 	}
-	if (u.d_start && fs)      // full-size frames re-seed the trackers with their own small kernels; for 64x64 tiles that, and the camera copy, ride on k_prepare (below)
+	if (u.d_start && !tile)      // full-size frames re-seed the trackers with their own small kernels; for 64x64 tiles that, and the camera copy, ride on k_prepare (below)
 	{ for (int w = 0; w < 2; w++) ht_launch_set_pose(ctx->d_state[w], u.d_start, ctx->model.nb, B, 1, s); ht_launch_clear_flags(ctx->d_prev_err, ctx->d_initializing, B, s); }
 	{
 		ht_prof_scope ps(ctx, "prepare", s, true);
-		if (fs)
+		if (!tile)
 		{
 			const ht_prepare_extra pz = { nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, ctx->d_nflist };
-			if (fs->direct) { HIPCHK(ctx, hipMemsetAsync(ctx->d_nflist, 0, sizeof(int), s)); ht_launch_cnn_input(d_depth, ctx->d_cams, fs->w * fs->h, p.drangey, u.net->d_in, B, s); }
-			else if (mode != UPD_PASSES && fs->side != 64) { HIPCHK(ctx, hipMemsetAsync(ctx->d_nflist, 0, sizeof(int), s)); ht_launch_cnn_input(ctx->d_seg_tiles, ctx->d_cams, fs->side * fs->side, p.drangey, u.net->d_in, B, s); }      // the larger tile goes the direct path's way (handtrack.h:700)
-			else if (mode != UPD_PASSES) ht_launch_prepare(ctx->d_seg_tiles, ctx->d_cams, p.drangey, p.subsample_fraction, u.net->d_in, nullptr, nullptr, ctx->model.pts_cap, B, s, &pz);      // (the caller's part of the overlapped update has no segment and no net)
-			ht_launch_prepare_frame(d_depth, u.img_cams, fs->w, fs->h, p.drangey, p.subsample_fraction, ctx->d_pts, ctx->d_npts, ctx->d_overflow, ctx->model.pts_cap, B, s);
+			const bool by_prepare = u.net->dims.in == HT_CNN_IN;      // k_prepare makes the input of the net that looks at the reference's tile; a larger net takes its own from the input transform, off the frame itself or off the segment's tile (handtrack.h:700)
+			if (own || (segment && !by_prepare)) { HIPCHK(ctx, hipMemsetAsync(ctx->d_nflist, 0, sizeof(int), s)); ht_launch_cnn_input(own ? d_depth : ctx->d_seg_tiles, ctx->d_cams, fs.side * fs.side, p.drangey, u.net->d_in, B, s); }
+			else if (segment) ht_launch_prepare(ctx->d_seg_tiles, ctx->d_cams, p.drangey, p.subsample_fraction, u.net->d_in, nullptr, nullptr, ctx->model.pts_cap, B, s, &pz);
+			ht_launch_prepare_frame(d_depth, u.img_cams, fs.w, fs.h, p.drangey, p.subsample_fraction, ctx->d_pts, ctx->d_npts, ctx->d_overflow, ctx->model.pts_cap, B, s);
 		}
 		else
 		{
@@ -304,7 +310,7 @@ static int update_inputs(ht_ctx *ctx, update_call &u)
 			// uses before the first fit step) go through the voxel table; the CNN job keeps the every-n-th cloud above (handtrack.h:703)
 			if (!ctx->d_ptsv) { int r = dev_alloc_points(ctx); if (r) return r; }
 			float4 *all = reinterpret_cast<float4 *>(ctx->d_rows);
-			if (fs) ht_launch_prepare_frame(d_depth, u.img_cams, fs->w, fs->h, p.drangey, 1, all, ctx->d_nrows, ctx->d_overflow, ctx->model.pts_cap, B, s);
+			if (!tile) ht_launch_prepare_frame(d_depth, u.img_cams, fs.w, fs.h, p.drangey, 1, all, ctx->d_nrows, ctx->d_overflow, ctx->model.pts_cap, B, s);
 			else ht_launch_prepare(d_depth, ctx->d_cams, p.drangey, 1, nullptr, all, ctx->d_nrows, ctx->model.pts_cap, B, s);
 			ht_launch_voxel(all, ctx->d_nrows, ctx->model.pts_cap, p.subsample_size, p.subsample_fraction, ctx->d_ptsv, ctx->d_nptsv, B, s);
 		}
@@ -324,7 +330,7 @@ static void update_fit_error_old(ht_ctx *ctx, const update_call &u, hipStream_t 
 	const ht_params &p = ctx->par;
 	ht_fit_after dec; memset(&dec, 0, sizeof dec);
 	dec.mode = 1; dec.reset_thr = p.full_reset_on_error; dec.angles_only = p.angles_only; dec.flags = ctx->d_flags; dec.nflags = ctx->d_nflags; dec.list = ctx->d_flist; dec.nlist = ctx->d_nflist; dec.nreset = ctx->d_nreset;
-	ht_launch_fit_error(ctx->model, ctx->d_state[0], ctx->d_pts, ctx->d_npts, u.d_depth, u.img_cams, u.iw, u.ih, p.bone_sum_error_scale, ctx->d_err_old, u.B, t, &dec);
+	ht_launch_fit_error(ctx->model, ctx->d_state[0], ctx->d_pts, ctx->d_npts, u.d_depth, u.img_cams, u.fs.w, u.fs.h, p.bone_sum_error_scale, ctx->d_err_old, u.B, t, &dec);
 }
 // The side branches beside the net, in dependency order.  Nothing on them needs the CNN.  What the update's stream waits for behind the net is the reset decision alone,
 // so the carried pose's FitError (with the set_pose it reads behind) has side stream 1 to itself from the fork on and runs under the convolutions (ht_cnn.hip: ht_launch_cnn).
@@ -339,7 +345,7 @@ static void update_beside_net(ht_ctx *ctx, const update_call &u)
 	hipStream_t fit = ctx->side[1], rest = ctx->side[0];
 	mark("update start", u.s);
 	fork(ctx, u.s);
-	if (u.mode == UPD_FULL && !(u.d_start && !u.fs)) ht_launch_set_pose(ctx->d_state[1], ctx->d_state[0], ctx->model.nb, u.B, 2, fit);     // othermodel.SetPose(handmodel.GetPose()) handtrack.h:757 (both were just seeded with the same pose otherwise)
+	if (u.mode == UPD_FULL && !(u.d_start && u.fs.kind == FRAME_TILE)) ht_launch_set_pose(ctx->d_state[1], ctx->d_state[0], ctx->model.nb, u.B, 2, fit);     // othermodel.SetPose(handmodel.GetPose()) handtrack.h:757 (both were just seeded with the same pose otherwise)
 	update_fit_error_old(ctx, u, fit); mark("carried FitError done", fit);
 	update_orders(ctx, u.B, rest); mark("orders done", rest);
 	update_planes(ctx, u, rest); mark("planes done", rest);
@@ -430,7 +436,7 @@ static void update_accept(ht_ctx *ctx, const update_call &u)
 	acc.mode = 2; acc.hand = u.mode == UPD_CNN_MODEL ? nullptr : ctx->d_state[0]; acc.other = ctx->d_state[1]; acc.err_old = ctx->d_err_old; acc.prev_err = ctx->d_prev_err;
 	acc.initializing = ctx->d_initializing; acc.accepted = ctx->d_accepted; acc.nb = ctx->model.nb; acc.min_point_num = p.min_point_num; acc.always_take_cnn = p.always_take_cnn;
 	acc.angles_only = p.angles_only; acc.accum_thr = p.accum_error_threshold; ht_prof_scope ps(ctx, "fit_error", u.s, true);
-	ht_launch_fit_error(ctx->model, ctx->d_state[1], ctx->d_pts, ctx->d_npts, u.d_depth, u.img_cams, u.iw, u.ih, p.bone_sum_error_scale, ctx->d_err_new, u.B, u.s, &acc);
+	ht_launch_fit_error(ctx->model, ctx->d_state[1], ctx->d_pts, ctx->d_npts, u.d_depth, u.img_cams, u.fs.w, u.fs.h, p.bone_sum_error_scale, ctx->d_err_new, u.B, u.s, &acc);
 }
 static void update_passes(ht_ctx *ctx, const update_call &u)      // the main-thread passes on handmodel and the user poses: the last pass's solve writes them, k_output when there is no pass
 {
@@ -442,7 +448,7 @@ static void update_passes(ht_ctx *ctx, const update_call &u)      // the main-th
 static int run_update_(ht_ctx *ctx, update_call &u)
 {
 	const ht_params &p = ctx->par; hipStream_t s = u.s;
-	u.net = ht_net_of(ctx, u.fs ? (u.fs->direct ? u.fs->direct : u.fs->side) : 64);      // a frame that is its own segment goes to the net of its size, a segmented one to the net of its tile side, tiles to theirs (the entry points have checked the side)
+	u.net = ht_net_of(ctx, u.fs.side);      // (resolve_frames has checked the side)
 	if (u.mode != UPD_PASSES && !u.net->have) { ctx->err = u.net->missing; return HT_ERR_STATE; }      // (no net in the caller's part of the overlapped update)
 	{ const int r = update_inputs(ctx, u); if (r) return r; }
 	if (u.mode == UPD_PASSES) { update_planes(ctx, u, s); update_passes(ctx, u); return HT_OK; }
@@ -467,9 +473,9 @@ static int run_update_(ht_ctx *ctx, update_call &u)
 	marks_dump();
 	return HT_OK;
 }
-static int run_update(ht_ctx *ctx, const uint16_t *d_depth, const float *d_cams, const float *d_start, int B, float *d_poses_out, float *d_cnn_out, hipStream_t s, const frame_src *fs = nullptr, int mode = UPD_FULL)
+static int run_update(ht_ctx *ctx, const uint16_t *d_depth, const float *d_cams, const float *d_start, int B, float *d_poses_out, float *d_cnn_out, hipStream_t s, const frame_src &fs, int mode = UPD_FULL)
 {
-	update_call u = { d_depth, d_cams, d_start, B, d_poses_out, d_cnn_out, s, fs, mode, nullptr, 64, 64, nullptr };
+	update_call u = { d_depth, d_cams, d_start, B, d_poses_out, d_cnn_out, s, fs, mode, nullptr, nullptr };
 	const int r = run_update_(ctx, u);
 	ctx->model.frame_order = nullptr; ctx->model.pts_bound = 0;      // the per-call hints of update_inputs (launch order of the block-per-frame kernels, largest cloud) belong to the update that set them
 	ctx->planes_valid = false;                                       // and so do the boundary planes of its cloud
@@ -524,77 +530,6 @@ extern "C" int ht_set_tracker_flags(ht_ctx *ctx, int first, int n, const float *
 	if (initializing) HIPCHK(ctx, hipMemcpy(ctx->d_initializing + first, initializing, (size_t)n * sizeof(int), hipMemcpyHostToDevice));
 	return HT_OK;
 }
-extern "C" int ht_update_dev(ht_ctx *ctx, const uint16_t *d_depth, const float *d_cams, const float *d_start_poses, int B, float *d_poses_out, void *stream)
-{
-	CHECK_READY(ctx); CHECK_MODEL(ctx); CHECK_BATCH(ctx, B);
-	if (!d_depth || !d_cams || !d_poses_out) return HT_ERR_ARG;
-	return update_dev_end(ctx, run_update(ctx, d_depth, d_cams, d_start_poses, B, d_poses_out, nullptr, ht_user_stream(ctx, stream)));
-}
-// ---- the synchronous update calls: frames up, run_update, results down --------------------------------------------------
-// Upload: a 64x64 tile goes to d_depth / d_cams, a frame of any other size to d_frames (which follows the largest frame size seen) / d_frame_cams_in.
-// *d_in, *d_cin: what run_update takes.  `depth`, `cams`: host memory (ht_job_start: its pinned copy).
-static int stage_frames(ht_ctx *ctx, const uint16_t *depth, const float *cams, int w, int h, int B, hipStream_t s, const uint16_t **d_in, const float **d_cin)
-{
-	uint16_t *dd = ctx->d_depth; float *dc = ctx->d_cams;
-	if (!(w == 64 && h == 64))
-	{
-		int r;
-		if ((r = dev_grow(ctx, &ctx->d_frames, &ctx->frames_cap, (size_t)ctx->B * w * h))) return r;
-		if (!ctx->d_frame_cams_in && (r = dev_alloc(ctx, &ctx->d_frame_cams_in, (size_t)ctx->B * HT_CAM))) return r;
-		dd = ctx->d_frames; dc = ctx->d_frame_cams_in;
-	}
-	HIPCHK(ctx, hipMemcpyAsync(dd, depth, (size_t)B * w * h * sizeof(uint16_t), hipMemcpyHostToDevice, s));
-	HIPCHK(ctx, hipMemcpyAsync(dc, cams, (size_t)B * HT_CAM * sizeof(float), hipMemcpyHostToDevice, s));
-	*d_in = dd; *d_cin = dc;
-	return HT_OK;
-}
-// Download: the results the caller asked for (accepted as 0 / 1), the stream drained.  `frames_entry`: the call ran on full-size frames, whose clouds the point capacity
-// can cut short (d_overflow counts such frames): that is an error, reported under the entry point's name.
-static int finish_sync(ht_ctx *ctx, int B, hipStream_t s, float *poses_out, float *cnn_out, int *accepted_out, const char *frames_entry)
-{
-	if (poses_out) HIPCHK(ctx, hipMemcpyAsync(poses_out, ctx->d_poses_out, (size_t)B * ctx->model.nb * HT_POSE * sizeof(float), hipMemcpyDeviceToHost, s));
-	if (accepted_out) HIPCHK(ctx, hipMemcpyAsync(accepted_out, ctx->d_accepted, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, s));
-	if (cnn_out) HIPCHK(ctx, hipMemcpyAsync(cnn_out, ctx->d_cnn_out, (size_t)B * HT_CNN_OUT * sizeof(float), hipMemcpyDeviceToHost, s));
-	{ const int r = ht_sync_check(ctx, s); if (r) return r; }
-	if (accepted_out) for (int b = 0; b < B; b++) accepted_out[b] = accepted_out[b] != 0;
-	int over = 0;
-	if (frames_entry) HIPCHK(ctx, hipMemcpy(&over, ctx->d_overflow, sizeof(int), hipMemcpyDeviceToHost));
-	if (over) { ctx->err = std::string(frames_entry) + ": " + std::to_string(over) + " frame(s) have more in-range points than the context's point capacity holds; their result is not the reference's"; return HT_ERR_ARG; }
-	return HT_OK;
-}
-// `fs` of 64x64 pixels: the tile path (run_update without a frame_src).  `frames_entry`: finish_sync's, for frames of another size.
-static int update_sync(ht_ctx *ctx, const uint16_t *depth, const float *cams, const frame_src &fs, int mode, int B, float *poses_out, int *accepted_out, float *cnn_out, const char *frames_entry)
-{
-	hipStream_t s = ctx->stream;
-	const bool tile = fs.w == 64 && fs.h == 64 && fs.side == 64;      // (a 64x64 frame is segmented like any other when the tile side is 128)
-	const uint16_t *d_in; const float *d_cin;
-	int r = stage_frames(ctx, depth, cams, fs.w, fs.h, B, s, &d_in, &d_cin);
-	if (!r) r = run_update(ctx, d_in, d_cin, nullptr, B, ctx->d_poses_out, nullptr, s, tile ? nullptr : &fs, mode);
-	return r ? r : finish_sync(ctx, B, s, poses_out, cnn_out, accepted_out, tile ? nullptr : frames_entry);
-}
-extern "C" int ht_update_sync(ht_ctx *ctx, const uint16_t *depth, const float *cams, int B, float *poses_out, float *cnn_out)
-{
-	CHECK_READY(ctx); CHECK_MODEL(ctx); CHECK_BATCH(ctx, B);
-	if (!depth || !cams || !poses_out) return HT_ERR_ARG;
-	const frame_src fs = { 64, 64, 0.0f, 0 };
-	return update_sync(ctx, depth, cams, fs, UPD_FULL, B, poses_out, nullptr, cnn_out, nullptr);
-}
-
-// HandTracker::update on frames of any size up to 320x240 (handtrack.h:693-785): segmentation for the CNN inside, the cloud of the full frame
-static int frames_args_ok(ht_ctx *ctx, int w, int h)
-{
-	if ((w == 64 && h == 64) || ht_segment_supported(w, h)) return 1;
-	ctx->err = "ht_update_frames: frame size must be a multiple of 4 and at most 320x240 pixels"; return 0;
-}
-extern "C" int ht_update_frames_dev(ht_ctx *ctx, const uint16_t *d_depth, const float *d_cams, int w, int h, float segment_scale, const float *d_start_poses, int B, float *d_poses_out, void *stream)
-{
-	CHECK_READY(ctx); CHECK_MODEL(ctx); CHECK_BATCH(ctx, B);
-	if (!d_depth || !d_cams || !d_poses_out) return HT_ERR_ARG;
-	if (!frames_args_ok(ctx, w, h)) return HT_ERR_ARG;
-	hipStream_t s = ht_user_stream(ctx, stream);
-	const frame_src fs = { w, h, segment_scale, 0 };
-	return update_dev_end(ctx, run_update(ctx, d_depth, d_cams, d_start_poses, B, d_poses_out, nullptr, s, (w == 64 && h == 64) ? nullptr : &fs));
-}
 // Capacities of the contact kernel that the reference does not have: expanding-polytope runs cut short (128 iterations, 96 vertices, 192
 // triangles in LDS; hull.h:246 loops without bound), touching samples beyond the 192 of a frame's pool, and solves whose angular rows exceed the 126
 // the solver keeps (a model with many ranged joints).  Counted since ht_create; 0 on every
@@ -643,75 +578,70 @@ extern "C" int ht_frames_overflow(ht_ctx *ctx, int *frames_over)
 	if (ctx->d_overflow) HIPCHK(ctx, hipMemcpy(frames_over, ctx->d_overflow, sizeof(int), hipMemcpyDeviceToHost));
 	return HT_OK;
 }
-extern "C" int ht_update_frames_sync(ht_ctx *ctx, const uint16_t *depth, const float *cams, int w, int h, float segment_scale, int B, float *poses_out, float *cnn_out)
+// ---- the update entry points: one frame source, one request ------------------------------------------------------------------------------------------------------
+// The rules of the three families of entry points, stated once.  resolve_frames makes an entry's (family, side, w, h, segment_scale) into a frame_src and makes every
+// argument check of the family, in this order; it is the only place that compares w, h and side with each other or with 64.
+//   FRAMES_PLAIN   ht_update_*, ht_update_frames_*, ht_update_cnn_model_sync, ht_update_passes_sync, ht_job_start: HandTracker::update on frames of any size up to 320x240
+//                  (handtrack.h:693-785) for the reference's net.  64x64 is the tile; anything else must pass ht_segment_supported and is segmented at 64.  No point limit.
+//   FRAMES_SIZED   ht_update_frames_sized_*, ht_update_hands_*, ht_update_two_hands*: the same on frames up to 640x480 and for either net: HandSegmentVR (:280-344) cuts the
+//                  segment at `side` (dstcam :338-340 is the only place the side enters), the net is the one of that input size, the decode camera camsub(segment.cam,
+//                  side / 16) (:218-241); everything behind the net takes the segment's pose, which does not depend on the side.  The net of `side` must exist; the size
+//                  must be side x side or pass ht_segment_supported_sized; the net's weights must be there; the cloud a frame can carry, as update_inputs counts it, must
+//                  fit HT_POINTS_LIMIT.  side x side is the frame that is its own segment (:283-284; at side 64: the tile); a 64x64 frame at side 128 is segmented.
+//   FRAMES_DIRECT  ht_update_direct_*: side x side frames that are their own segment (BASELINE configs[4] end to end, SURVEY 8d "config 5 (i)-(iii)"), no HandSegmentVR.
+//                  Only the side is checked (missing weights are run_update_'s to report, behind the alignment rule of update_check).
+enum frame_family { FRAMES_PLAIN, FRAMES_SIZED, FRAMES_DIRECT };
+static int resolve_frames(ht_ctx *ctx, frame_family family, int side, int w, int h, float segment_scale, frame_src &fs)
 {
-	CHECK_READY(ctx); CHECK_MODEL(ctx); CHECK_BATCH(ctx, B);
-	if (!depth || !cams || !poses_out) return HT_ERR_ARG;
-	if (!frames_args_ok(ctx, w, h)) return HT_ERR_ARG;
-	const frame_src fs = { w, h, segment_scale, 0 };
-	return update_sync(ctx, depth, cams, fs, UPD_FULL, B, poses_out, nullptr, cnn_out, "ht_update_frames");
-}
-
-// HandTracker::update (handtrack.h:693-785) as ht_update_frames_* states it, on frames up to 640x480 and for either net: HandSegmentVR (:280-344) cuts the segment at
-// `side` (dstcam :338-340 is the only place the side enters), the net is the one of that input size, the decode camera camsub(segment.cam, side / 16) (:218-241).
-// Everything behind the net takes the segment's pose, which does not depend on the side.  Checked completely before anything is uploaded, grown or launched.
-static int frames_sized_args_ok(ht_ctx *ctx, int side, int w, int h)
-{
+	const frame_src tile = { FRAME_TILE, 64, 64, 64, 0.0f, true };
+	const bool px64 = w == 64 && h == 64;
+	if (family == FRAMES_PLAIN)
+	{
+		if (!px64 && !ht_segment_supported(w, h)) { ctx->err = "ht_update_frames: frame size must be a multiple of 4 and at most 320x240 pixels"; return HT_ERR_ARG; }
+		fs = px64 ? tile : frame_src{ FRAME_SEGMENTED, w, h, 64, segment_scale, false };
+		return HT_OK;
+	}
 	const ht_net *net = ht_net_of(ctx, side);
-	if (!net) { ctx->err = "ht_update_frames_sized: " + ctx->err; return HT_ERR_ARG; }
-	if (!(w == side && h == side) && !ht_segment_supported_sized(w, h, side)) { ctx->err = "ht_update_frames_sized: frame size must be a multiple of 4, at least 8x8 and at most 640x480 pixels (19200 quarter-size pixels)"; return HT_ERR_ARG; }
-	if (!net->have) { ctx->err = net->missing; return HT_ERR_STATE; }
-	const ht_params &p = ctx->par;      // the cloud a frame can carry, as update_inputs counts it
-	const long long npx = (long long)w * h, fr = p.subsample_fraction > 0 ? p.subsample_fraction : 1, n = p.subsample_voxel ? npx : (npx + fr - 1) / fr;
-	if (n > HT_POINTS_LIMIT) { ctx->err = "ht_update_frames_sized: these frames can carry " + std::to_string(n) + " points each, the per-point arrays hold at most 76800 (ht_reserve_points): raise subsample_fraction, and leave the voxel rule off"; return HT_ERR_ARG; }
+	if (!net) { ctx->err = (family == FRAMES_DIRECT ? "ht_update_direct: " : "ht_update_frames_sized: ") + ctx->err; return HT_ERR_ARG; }
+	const bool own = family == FRAMES_DIRECT || (w == side && h == side);
+	if (family == FRAMES_SIZED)
+	{
+		if (!own && !ht_segment_supported_sized(w, h, side)) { ctx->err = "ht_update_frames_sized: frame size must be a multiple of 4, at least 8x8 and at most 640x480 pixels (19200 quarter-size pixels)"; return HT_ERR_ARG; }
+		if (!net->have) { ctx->err = net->missing; return HT_ERR_STATE; }
+		const ht_params &p = ctx->par;
+		const long long npx = (long long)w * h, fr = p.subsample_fraction > 0 ? p.subsample_fraction : 1, n = p.subsample_voxel ? npx : (npx + fr - 1) / fr;
+		if (n > HT_POINTS_LIMIT) { ctx->err = "ht_update_frames_sized: these frames can carry " + std::to_string(n) + " points each, the per-point arrays hold at most 76800 (ht_reserve_points): raise subsample_fraction, and leave the voxel rule off"; return HT_ERR_ARG; }
+	}
+	if (!own) fs = frame_src{ FRAME_SEGMENTED, w, h, side, segment_scale, px64 };
+	else fs = side == 64 ? tile : frame_src{ FRAME_OWN_SEGMENT, side, side, side, 0.0f, false };
 	return HT_OK;
 }
-extern "C" int ht_update_frames_sized_dev(ht_ctx *ctx, int side, const uint16_t *d_depth, const float *d_cams, int w, int h, float segment_scale, const float *d_start_poses, int B, float *d_poses_out, void *stream)
+
+// ---- host forms: frames up ---------------------------------------------------------------------------------------------------------------------------
+// Upload: a frame of a tile's pixels goes to d_depth / d_cams, a frame of any other size to d_frames (which follows the largest frame size seen) / d_frame_cams_in.
+// *d_in, *d_cin: what run_update takes.  `depth`, `cams`: host memory (ht_job_start: its pinned copy).
+static int stage_frames(ht_ctx *ctx, const uint16_t *depth, const float *cams, const frame_src &fs, int B, hipStream_t s, const uint16_t **d_in, const float **d_cin)
 {
-	CHECK_READY(ctx); CHECK_MODEL(ctx); CHECK_BATCH(ctx, B);
-	if (!d_depth || !d_cams || !d_poses_out) return HT_ERR_ARG;
-	{ const int r = frames_sized_args_ok(ctx, side, w, h); if (r) return r; }
-	if (w == side && h == side) return ht_update_direct_dev(ctx, d_depth, d_cams, side, d_start_poses, B, d_poses_out, stream);      // handtrack.h:283-284: the frame is its own segment (with that call's alignment rule)
-	hipStream_t s = ht_user_stream(ctx, stream);
-	const frame_src fs = { w, h, segment_scale, 0, side };      // (the input transform of the larger tile reads the context's own tile buffer: no alignment rule for d_depth)
-	return update_dev_end(ctx, run_update(ctx, d_depth, d_cams, d_start_poses, B, d_poses_out, nullptr, s, &fs));
-}
-extern "C" int ht_update_frames_sized_sync(ht_ctx *ctx, int side, const uint16_t *depth, const float *cams, int w, int h, float segment_scale, int B, float *poses_out, float *cnn_out)
-{
-	CHECK_READY(ctx); CHECK_MODEL(ctx); CHECK_BATCH(ctx, B);
-	if (!depth || !cams || !poses_out) return HT_ERR_ARG;
-	{ const int r = frames_sized_args_ok(ctx, side, w, h); if (r) return r; }
-	if (w == side && h == side) return ht_update_direct_sync(ctx, depth, cams, side, B, poses_out, cnn_out);
-	const frame_src fs = { w, h, segment_scale, 0, side };
-	return update_sync(ctx, depth, cams, fs, UPD_FULL, B, poses_out, nullptr, cnn_out, "ht_update_frames_sized");
+	uint16_t *dd = ctx->d_depth; float *dc = ctx->d_cams;
+	const size_t npx = (size_t)fs.w * fs.h;
+	if (!fs.px64)
+	{
+		int r;
+		if ((r = dev_grow(ctx, &ctx->d_frames, &ctx->frames_cap, (size_t)ctx->B * npx))) return r;
+		if (!ctx->d_frame_cams_in && (r = dev_alloc(ctx, &ctx->d_frame_cams_in, (size_t)ctx->B * HT_CAM))) return r;
+		dd = ctx->d_frames; dc = ctx->d_frame_cams_in;
+	}
+	HIPCHK(ctx, hipMemcpyAsync(dd, depth, (size_t)B * npx * sizeof(uint16_t), hipMemcpyHostToDevice, s));
+	HIPCHK(ctx, hipMemcpyAsync(dc, cams, (size_t)B * HT_CAM * sizeof(float), hipMemcpyHostToDevice, s));
+	*d_in = dd; *d_cin = dc;
+	return HT_OK;
 }
 
-// BASELINE configs[4] end to end (SURVEY 8d "config 5 (i)-(iii)"): HandTracker::update on side x side frames that are their own segment, evaluated by the net of
-// that input size (ht_cnn_load_weights_sized) -- no HandSegmentVR, heat-map camera camsub(cam, side / 16), everything else as handtrack.h:693-785
-extern "C" int ht_update_direct_dev(ht_ctx *ctx, const uint16_t *d_depth, const float *d_cams, int side, const float *d_start_poses, int B, float *d_poses_out, void *stream)
-{
-	CHECK_READY(ctx); CHECK_MODEL(ctx); CHECK_BATCH(ctx, B);
-	if (!d_depth || !d_cams || !d_poses_out) return HT_ERR_ARG;
-	if (!ht_net_of(ctx, side)) { ctx->err = "ht_update_direct: " + ctx->err; return HT_ERR_ARG; }
-	if (side == 64) return ht_update_dev(ctx, d_depth, d_cams, d_start_poses, B, d_poses_out, stream);
-	if (((uintptr_t)d_depth & 15) != 0) { ctx->err = "ht_update_direct_dev: d_depth must be 16-byte aligned (the input transform reads eight pixels per 128-bit load)"; return HT_ERR_ARG; }
-	hipStream_t s = ht_user_stream(ctx, stream);
-	const frame_src fs = { side, side, 0.0f, side };
-	return update_dev_end(ctx, run_update(ctx, d_depth, d_cams, d_start_poses, B, d_poses_out, nullptr, s, &fs));
-}
-extern "C" int ht_update_direct_sync(ht_ctx *ctx, const uint16_t *depth, const float *cams, int side, int B, float *poses_out, float *cnn_out)
-{
-	CHECK_READY(ctx); CHECK_MODEL(ctx); CHECK_BATCH(ctx, B);
-	if (!depth || !cams || !poses_out) return HT_ERR_ARG;
-	if (!ht_net_of(ctx, side)) { ctx->err = "ht_update_direct: " + ctx->err; return HT_ERR_ARG; }
-	const frame_src fs = { side, side, 0.0f, side };
-	return update_sync(ctx, depth, cams, fs, UPD_FULL, B, poses_out, nullptr, cnn_out, nullptr);      // a frame that is its own segment: the point capacity follows its size
-}
-
-// ---- left hands (an addition) -------------------------------------------------------------------------------------------------------------
+// ---- the staging of the left-hand and two-hand calls (additions; DESIGN sections 26, 27, 31) ---------------------------------------------------------------------------
 // A left-hand update is the existing update on the mirror image: frames, cameras and start poses of the flagged frames mirrored into a staging of the context
-// (ht_mirror.hip), ht_update_frames_sized_dev on that staging, the poses that come out mirrored in place.  The slots' state stays the right hand's.  Without
-// flags the call IS ht_update_frames_sized_*, on the caller's own pointers.
+// (ht_mirror.hip), the update on that staging, the poses that come out mirrored in place.  The slots' state stays the right hand's.
+// Two hands in one frame: B frames become 2B hand frames: the split (ht_split.hip) writes frame i's right hand into slot 2i of the same staging and its left hand,
+// mirrored, into slot 2i + 1, with their cameras; the update runs on the staging; the odd slots' poses are mirrored back.  Slot state stays canonical.
 // The staging: max_batch frames of `px` pixels, cameras and start poses, and the host form's flags.  Never smaller; growing is one synchronising re-allocation, the
 // replacement made first (dev_grow), so a failure leaves what was there.
 static int hands_reserve(ht_ctx *ctx, size_t px)
@@ -736,55 +666,9 @@ extern "C" int ht_hands_capacity(ht_ctx *ctx, size_t *frame_pixels)
 	*frame_pixels = ctx->hands_px;
 	return HT_OK;
 }
-// the flagged call, checked: mirror in, update, mirror out, all enqueued on s
-static int hands_enqueue(ht_ctx *ctx, int side, const uint16_t *d_depth, const float *d_cams, int w, int h, float segment_scale, const unsigned char *d_hands, const float *d_start, int B, float *d_poses_out, hipStream_t s)
-{
-	{ const int r = hands_reserve(ctx, (size_t)w * h); if (r) return r; }
-	const int nb = ctx->model.nb;
-	{ ht_prof_scope ps(ctx, "k_mirror_frames", s); ht_launch_mirror_frames(d_depth, w, h, B, d_hands, ctx->d_hands_frames, s); }
-	{ ht_prof_scope ps(ctx, "k_mirror_cams", s); ht_launch_mirror_cams(d_cams, w, B, d_hands, ctx->d_hands_cams, s); }
-	if (d_start) { ht_prof_scope ps(ctx, "k_mirror_poses", s); ht_launch_mirror_poses(d_start, nb, B, d_hands, ctx->d_hands_start, s); }
-	{ const int r = ht_update_frames_sized_dev(ctx, side, ctx->d_hands_frames, ctx->d_hands_cams, w, h, segment_scale, d_start ? ctx->d_hands_start : nullptr, B, d_poses_out, s); if (r) return r; }
-	{ ht_prof_scope ps(ctx, "k_mirror_poses", s); ht_launch_mirror_poses(d_poses_out, nb, B, d_hands, d_poses_out, s); }
-	return HT_OK;
-}
-extern "C" int ht_update_hands_dev(ht_ctx *ctx, int side, const uint16_t *d_depth, const float *d_cams, int w, int h, float segment_scale, const unsigned char *d_hands, const float *d_start_poses, int B, float *d_poses_out, void *stream)
-{
-	if (!d_hands) return ht_update_frames_sized_dev(ctx, side, d_depth, d_cams, w, h, segment_scale, d_start_poses, B, d_poses_out, stream);
-	CHECK_READY(ctx); CHECK_MODEL(ctx); CHECK_BATCH(ctx, B);
-	if (!d_depth || !d_cams || !d_poses_out) return HT_ERR_ARG;
-	{ const int r = frames_sized_args_ok(ctx, side, w, h); if (r) return r; }
-	return update_dev_end(ctx, hands_enqueue(ctx, side, d_depth, d_cams, w, h, segment_scale, d_hands, d_start_poses, B, d_poses_out, ht_user_stream(ctx, stream)));
-}
-extern "C" int ht_update_hands_sync(ht_ctx *ctx, int side, const uint16_t *depth, const float *cams, int w, int h, float segment_scale, const unsigned char *hands, int B, float *poses_out, float *cnn_out)
-{
-	if (!hands) return ht_update_frames_sized_sync(ctx, side, depth, cams, w, h, segment_scale, B, poses_out, cnn_out);
-	CHECK_READY(ctx); CHECK_MODEL(ctx); CHECK_BATCH(ctx, B);
-	if (!depth || !cams || !poses_out) return HT_ERR_ARG;
-	{ const int r = frames_sized_args_ok(ctx, side, w, h); if (r) return r; }
-	hipStream_t s = ctx->stream;
-	const uint16_t *d_in; const float *d_cin;
-	int r = hands_reserve(ctx, (size_t)w * h);      // (first: it may wait for the stream, and the uploads below are already on it)
-	if (!r) r = stage_frames(ctx, depth, cams, w, h, B, s, &d_in, &d_cin);
-	if (r) return r;
-	HIPCHK(ctx, hipMemcpyAsync(ctx->d_hands_flags, hands, (size_t)B, hipMemcpyHostToDevice, s));
-	if ((r = hands_enqueue(ctx, side, d_in, d_cin, w, h, segment_scale, ctx->d_hands_flags, nullptr, B, ctx->d_poses_out, s))) return r;
-	return finish_sync(ctx, B, s, poses_out, cnn_out, nullptr, (w == side && h == side) ? nullptr : "ht_update_hands");
-}
-
-// ---- two hands in one frame (an addition) ------------------------------------------------------------------------------------------------
-// B frames become 2B hand frames: the split (ht_split.hip) writes frame i's right hand into slot 2i of the hands staging above and its left hand, mirrored, into slot
-// 2i + 1, with their cameras; ht_update_frames_sized_dev runs on the staging; the odd slots' poses are mirrored back.  Slot state stays canonical.
 // model_mode: -1 the blob split; HT_SPLIT_MODEL_ALWAYS / _MERGED: the cells go to the nearer tracked model (ht_split_model.hip), priors the start poses
 // where given, else the slots' own hand-model state (the left one canonical already)
 struct two_hands_args { uint16_t lo, hi, step, far; int min_pixels, flags; float max_dist; int model_mode; };
-static int two_hands_check(ht_ctx *ctx, int side, int w, int h, const two_hands_args &a, int B)
-{
-	if (B < 1 || 2 * (long long)B > ctx->B) { ctx->err = "ht_update_two_hands: two slots per frame: 2 * B exceeds the capacity given to ht_create"; return HT_ERR_ARG; }
-	{ const int r = frames_sized_args_ok(ctx, side, w, h); if (r) return r; }
-	if (a.model_mode >= 0) { const int r = ht_split_model_check(ctx, "ht_update_two_hands_model", a.max_dist, a.model_mode, a.flags); if (r) return r; }
-	return ht_split_check(ctx, "ht_update_two_hands", w, h, a.lo, a.hi, a.min_pixels, a.far, a.flags);
-}
 static int two_hands_reserve(ht_ctx *ctx, int w, int h, bool model)
 {
 	int r = hands_reserve(ctx, (size_t)w * h);
@@ -807,57 +691,176 @@ static int two_hands_reserve(ht_ctx *ctx, int w, int h, bool model)
 	if (cells > ctx->split_labels_cap) HIPCHK(ctx, ht_sync_all(ctx));
 	return dev_grow(ctx, &ctx->d_split_labels, &ctx->split_labels_cap, cells);
 }
-// checked and reserved: split, update, mirror back, all enqueued on s
-static int two_hands_enqueue(ht_ctx *ctx, int side, const uint16_t *d_depth, const float *d_cams, int w, int h, float segment_scale, const two_hands_args &a, const float *d_start, int B, float *d_poses_out,
-                             int32_t *d_info, int32_t *d_source, hipStream_t s)
+
+// ---- one request -----------------------------------------------------------------------------------------------------------------------------------------------------
+// Any update call: `entry` names it in the overflow report; (family, side, w, h, segment_scale) are the caller's, `fs` what update_check resolved them into; B frames in
+// B slots, or with `two` in 2B; `hands`: a handedness flag per frame (null: none, nothing is staged); depth / cams / start / poses / info / source are host pointers in
+// the host form's record and device pointers in the one update_enqueue takes.
+struct update_req
 {
-	const int nb = ctx->model.nb, flags = a.flags | HT_SPLIT_MIRROR_LEFT;
-	if (a.model_mode < 0) { ht_prof_scope ps(ctx, "k_split_label", s); ht_launch_split_label(d_depth, w, h, B, a.lo, a.hi, a.step, a.min_pixels, flags, d_info, nullptr, ctx->d_split_labels, s); }
-	else ht_launch_split_model(ctx, d_depth, d_cams, d_start ? d_start : ctx->d_state[0], d_start ? HT_POSE : HT_STATE_STRIDE, d_start ? 0 : 1, w, h, B, a.lo, a.hi, a.step, a.min_pixels, a.max_dist, a.model_mode, flags,
-	                           d_info, ctx->d_model_ncomp, d_source, nullptr, ctx->d_split_labels, s);
-	{ ht_prof_scope ps(ctx, "k_split_write", s); ht_launch_split_write(d_depth, ctx->d_split_labels, d_info, w, h, B, a.far, flags, ctx->d_hands_frames, s); }
-	{ ht_prof_scope ps(ctx, "k_split_cams", s); ht_launch_split_cams(d_cams, w, B, flags, ctx->d_hands_cams, s); }
-	if (d_start) { ht_prof_scope ps(ctx, "k_mirror_poses", s); ht_launch_mirror_poses(d_start, nb, 2 * B, ctx->d_two_flags, ctx->d_hands_start, s); }
-	{ const int r = ht_update_frames_sized_dev(ctx, side, ctx->d_hands_frames, ctx->d_hands_cams, w, h, segment_scale, d_start ? ctx->d_hands_start : nullptr, 2 * B, d_poses_out, s); if (r) return r; }
-	{ ht_prof_scope ps(ctx, "k_mirror_poses", s); ht_launch_mirror_poses(d_poses_out, nb, 2 * B, ctx->d_two_flags, d_poses_out, s); }
+	const char *entry; frame_family family; int side, w, h; float segment_scale; int mode, B; const uint16_t *depth; const float *cams; float *poses;      // what every entry gives, in this order
+	const float *start; float *cnn; int *accepted; bool poses_optional; const unsigned char *hands; const two_hands_args *two; int32_t *info, *source;      // null / false unless the entry sets them
+	frame_src fs;
+	int slots() const { return two ? 2 * B : B; }
+	bool staged() const { return hands || two; }
+};
+// Everything a call can be refused for, in the order the faults are reported; complete before anything is uploaded, grown or launched.  (The context itself: CHECK_READY,
+// in update_dev / update_host, whose device guard has to outlive the call.)  dev: depth is the caller's device pointer.
+static int update_check(ht_ctx *ctx, update_req &q, bool dev)
+{
+	CHECK_MODEL(ctx);
+	const int B = q.B;      // (CHECK_BATCH's parameter is also the name of the context's capacity)
+	if (!q.two) CHECK_BATCH(ctx, B);
+	if (!q.depth || !q.cams || (!q.poses && !q.poses_optional)) return HT_ERR_ARG;
+	if (q.two && (q.B < 1 || 2 * (long long)q.B > ctx->B)) { ctx->err = "ht_update_two_hands: two slots per frame: 2 * B exceeds the capacity given to ht_create"; return HT_ERR_ARG; }
+	{ const int r = resolve_frames(ctx, q.family, q.side, q.w, q.h, q.segment_scale, q.fs); if (r) return r; }
+	if (q.two)
+	{
+		const two_hands_args &a = *q.two;
+		if (a.model_mode >= 0) { const int r = ht_split_model_check(ctx, "ht_update_two_hands_model", a.max_dist, a.model_mode, a.flags); if (r) return r; }
+		const int r = ht_split_check(ctx, "ht_update_two_hands", q.w, q.h, a.lo, a.hi, a.min_pixels, a.far, a.flags); if (r) return r;
+	}
+	// the input transform of the larger net reads eight pixels per load off the frame that is its own segment: the caller's, unless the call stages (the context's staging is aligned)
+	if (dev && q.fs.kind == FRAME_OWN_SEGMENT && !q.staged() && ((uintptr_t)q.depth & 15) != 0) { ctx->err = "ht_update_direct_dev: d_depth must be 16-byte aligned (the input transform reads eight pixels per 128-bit load)"; return HT_ERR_ARG; }
 	return HT_OK;
 }
-static int two_hands_dev(ht_ctx *ctx, int side, const uint16_t *d_depth, const float *d_cams, int w, int h, float segment_scale, const two_hands_args &a, const float *d_start_poses, int B, float *d_poses_out,
-                         int32_t *d_info, int32_t *d_source, void *stream)
+static int update_reserve(ht_ctx *ctx, const update_req &q)      // the staging of a flagged or split call; may wait for the context's streams when it grows
 {
-	CHECK_READY(ctx); CHECK_MODEL(ctx);
-	if (!d_depth || !d_cams || !d_poses_out) return HT_ERR_ARG;
-	{ const int r = two_hands_check(ctx, side, w, h, a, B); if (r) return r; }
-	{ const int r = two_hands_reserve(ctx, w, h, a.model_mode >= 0); if (r) return r; }
-	return update_dev_end(ctx, two_hands_enqueue(ctx, side, d_depth, d_cams, w, h, segment_scale, a, d_start_poses, B, d_poses_out, d_info ? d_info : ctx->d_two_info, d_source, ht_user_stream(ctx, stream)));
+	if (!q.staged()) return HT_OK;
+	return q.two ? two_hands_reserve(ctx, q.w, q.h, q.two->model_mode >= 0) : hands_reserve(ctx, (size_t)q.w * q.h);
 }
-static int two_hands_sync(ht_ctx *ctx, int side, const uint16_t *depth, const float *cams, int w, int h, float segment_scale, const two_hands_args &a, int B, float *poses_out, int32_t *info, int32_t *source, float *cnn_out)
+// A checked request on device pointers, all enqueued on s: mirror in or split where the call stages, the update, the poses of left hands mirrored back in place
+static int update_enqueue(ht_ctx *ctx, const update_req &q, hipStream_t s)
 {
-	CHECK_READY(ctx); CHECK_MODEL(ctx);
-	if (!depth || !cams || !poses_out) return HT_ERR_ARG;
-	{ const int r = two_hands_check(ctx, side, w, h, a, B); if (r) return r; }
+	{ const int r = update_reserve(ctx, q); if (r) return r; }      // (nothing left to do behind the host form, which reserves before it uploads)
+	const int nb = ctx->model.nb, n = q.slots();
+	const uint16_t *d_depth = q.depth; const float *d_cams = q.cams, *d_start = q.start;
+	const unsigned char *left = q.two ? ctx->d_two_flags : q.hands;      // the slots whose poses are a left hand's
+	if (q.two)
+	{
+		const two_hands_args &a = *q.two; const int flags = a.flags | HT_SPLIT_MIRROR_LEFT; int32_t *d_info = q.info ? q.info : ctx->d_two_info;
+		if (a.model_mode < 0) { ht_prof_scope ps(ctx, "k_split_label", s); ht_launch_split_label(d_depth, q.w, q.h, q.B, a.lo, a.hi, a.step, a.min_pixels, flags, d_info, nullptr, ctx->d_split_labels, s); }
+		else ht_launch_split_model(ctx, d_depth, d_cams, d_start ? d_start : ctx->d_state[0], d_start ? HT_POSE : HT_STATE_STRIDE, d_start ? 0 : 1, q.w, q.h, q.B, a.lo, a.hi, a.step, a.min_pixels, a.max_dist, a.model_mode, flags,
+		                           d_info, ctx->d_model_ncomp, q.source, nullptr, ctx->d_split_labels, s);
+		{ ht_prof_scope ps(ctx, "k_split_write", s); ht_launch_split_write(d_depth, ctx->d_split_labels, d_info, q.w, q.h, q.B, a.far, flags, ctx->d_hands_frames, s); }
+		{ ht_prof_scope ps(ctx, "k_split_cams", s); ht_launch_split_cams(d_cams, q.w, q.B, flags, ctx->d_hands_cams, s); }
+	}
+	else if (q.hands)
+	{
+		{ ht_prof_scope ps(ctx, "k_mirror_frames", s); ht_launch_mirror_frames(d_depth, q.w, q.h, q.B, left, ctx->d_hands_frames, s); }
+		{ ht_prof_scope ps(ctx, "k_mirror_cams", s); ht_launch_mirror_cams(d_cams, q.w, q.B, left, ctx->d_hands_cams, s); }
+	}
+	if (q.staged())
+	{
+		if (d_start) { ht_prof_scope ps(ctx, "k_mirror_poses", s); ht_launch_mirror_poses(d_start, nb, n, left, ctx->d_hands_start, s); d_start = ctx->d_hands_start; }
+		d_depth = ctx->d_hands_frames; d_cams = ctx->d_hands_cams;
+	}
+	{ const int r = run_update(ctx, d_depth, d_cams, d_start, n, q.poses, nullptr, s, q.fs, q.mode); if (r) return r; }
+	if (q.staged()) { ht_prof_scope ps(ctx, "k_mirror_poses", s); ht_launch_mirror_poses(q.poses, nb, n, left, q.poses, s); }
+	return HT_OK;
+}
+// The device form of every entry: nothing is waited for, a launch that failed is reported (update_dev_end)
+static int update_dev(ht_ctx *ctx, update_req &q, void *stream)
+{
+	CHECK_READY(ctx);
+	{ const int r = update_check(ctx, q, true); if (r) return r; }
+	return update_dev_end(ctx, update_enqueue(ctx, q, ht_user_stream(ctx, stream)));
+}
+// The host form: the staging reserved first (it may wait for the stream, and the uploads below are already on it), frames and flags up, the request on the context's
+// own buffers, the split's records and the results the caller asked for down (accepted as 0 / 1), the stream drained.  Segmented frames whose clouds the point capacity
+// cut short (d_overflow counts them) are an error, reported under the entry point's name.
+static int update_host(ht_ctx *ctx, update_req &q)
+{
+	CHECK_READY(ctx);
+	{ const int r = update_check(ctx, q, false); if (r) return r; }
 	hipStream_t s = ctx->stream;
-	const uint16_t *d_in; const float *d_cin;
-	int r = two_hands_reserve(ctx, w, h, a.model_mode >= 0);      // (first: it may wait for the stream, and the uploads below are already on it)
-	if (!r) r = stage_frames(ctx, depth, cams, w, h, B, s, &d_in, &d_cin);
+	update_req d = q;
+	int r = update_reserve(ctx, q);
+	if (!r) r = stage_frames(ctx, q.depth, q.cams, q.fs, q.B, s, &d.depth, &d.cams);
 	if (r) return r;
-	int32_t *d_source = a.model_mode >= 0 ? ctx->d_model_ncomp + ctx->B / 2 : nullptr;
-	if ((r = two_hands_enqueue(ctx, side, d_in, d_cin, w, h, segment_scale, a, nullptr, B, ctx->d_poses_out, ctx->d_two_info, d_source, s))) return r;
-	if (info) HIPCHK(ctx, hipMemcpyAsync(info, ctx->d_two_info, (size_t)B * 16 * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-	if (source && d_source) HIPCHK(ctx, hipMemcpyAsync(source, d_source, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-	return finish_sync(ctx, 2 * B, s, poses_out, cnn_out, nullptr, (w == side && h == side) ? nullptr : "ht_update_two_hands");
+	d.start = nullptr; d.poses = ctx->d_poses_out;
+	if (q.hands) { HIPCHK(ctx, hipMemcpyAsync(ctx->d_hands_flags, q.hands, (size_t)q.B, hipMemcpyHostToDevice, s)); d.hands = ctx->d_hands_flags; }
+	if (q.two) { d.info = ctx->d_two_info; d.source = q.two->model_mode >= 0 ? ctx->d_model_ncomp + ctx->B / 2 : nullptr; }
+	if ((r = update_enqueue(ctx, d, s))) return r;
+	if (q.two && q.info) HIPCHK(ctx, hipMemcpyAsync(q.info, d.info, (size_t)q.B * 16 * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+	if (q.two && q.source && d.source) HIPCHK(ctx, hipMemcpyAsync(q.source, d.source, (size_t)q.B * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+	const int n = q.slots();
+	if (q.poses) HIPCHK(ctx, hipMemcpyAsync(q.poses, ctx->d_poses_out, (size_t)n * ctx->model.nb * HT_POSE * sizeof(float), hipMemcpyDeviceToHost, s));
+	if (q.accepted) HIPCHK(ctx, hipMemcpyAsync(q.accepted, ctx->d_accepted, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, s));
+	if (q.cnn) HIPCHK(ctx, hipMemcpyAsync(q.cnn, ctx->d_cnn_out, (size_t)n * HT_CNN_OUT * sizeof(float), hipMemcpyDeviceToHost, s));
+	if ((r = ht_sync_check(ctx, s))) return r;
+	if (q.accepted) for (int b = 0; b < n; b++) q.accepted[b] = q.accepted[b] != 0;
+	int over = 0;
+	if (q.fs.kind == FRAME_SEGMENTED) HIPCHK(ctx, hipMemcpy(&over, ctx->d_overflow, sizeof(int), hipMemcpyDeviceToHost));
+	if (over) { ctx->err = std::string(q.entry) + ": " + std::to_string(over) + " frame(s) have more in-range points than the context's point capacity holds; their result is not the reference's"; return HT_ERR_ARG; }
+	return HT_OK;
+}
+
+// ---- the entries: fill the record, hand it to the device or the host form ----------------------------------------------------------------------------------------------
+extern "C" int ht_update_dev(ht_ctx *ctx, const uint16_t *d_depth, const float *d_cams, const float *d_start_poses, int B, float *d_poses_out, void *stream)
+{
+	update_req q = { "ht_update", FRAMES_PLAIN, 64, 64, 64, 0.0f, UPD_FULL, B, d_depth, d_cams, d_poses_out }; q.start = d_start_poses;
+	return update_dev(ctx, q, stream);
+}
+extern "C" int ht_update_sync(ht_ctx *ctx, const uint16_t *depth, const float *cams, int B, float *poses_out, float *cnn_out)
+{
+	update_req q = { "ht_update", FRAMES_PLAIN, 64, 64, 64, 0.0f, UPD_FULL, B, depth, cams, poses_out }; q.cnn = cnn_out;
+	return update_host(ctx, q);
+}
+extern "C" int ht_update_frames_dev(ht_ctx *ctx, const uint16_t *d_depth, const float *d_cams, int w, int h, float segment_scale, const float *d_start_poses, int B, float *d_poses_out, void *stream)
+{
+	update_req q = { "ht_update_frames", FRAMES_PLAIN, 64, w, h, segment_scale, UPD_FULL, B, d_depth, d_cams, d_poses_out }; q.start = d_start_poses;
+	return update_dev(ctx, q, stream);
+}
+extern "C" int ht_update_frames_sync(ht_ctx *ctx, const uint16_t *depth, const float *cams, int w, int h, float segment_scale, int B, float *poses_out, float *cnn_out)
+{
+	update_req q = { "ht_update_frames", FRAMES_PLAIN, 64, w, h, segment_scale, UPD_FULL, B, depth, cams, poses_out }; q.cnn = cnn_out;
+	return update_host(ctx, q);
+}
+extern "C" int ht_update_frames_sized_dev(ht_ctx *ctx, int side, const uint16_t *d_depth, const float *d_cams, int w, int h, float segment_scale, const float *d_start_poses, int B, float *d_poses_out, void *stream)
+{
+	update_req q = { "ht_update_frames_sized", FRAMES_SIZED, side, w, h, segment_scale, UPD_FULL, B, d_depth, d_cams, d_poses_out }; q.start = d_start_poses;
+	return update_dev(ctx, q, stream);
+}
+extern "C" int ht_update_frames_sized_sync(ht_ctx *ctx, int side, const uint16_t *depth, const float *cams, int w, int h, float segment_scale, int B, float *poses_out, float *cnn_out)
+{
+	update_req q = { "ht_update_frames_sized", FRAMES_SIZED, side, w, h, segment_scale, UPD_FULL, B, depth, cams, poses_out }; q.cnn = cnn_out;
+	return update_host(ctx, q);
+}
+extern "C" int ht_update_direct_dev(ht_ctx *ctx, const uint16_t *d_depth, const float *d_cams, int side, const float *d_start_poses, int B, float *d_poses_out, void *stream)
+{
+	update_req q = { "ht_update_direct", FRAMES_DIRECT, side, side, side, 0.0f, UPD_FULL, B, d_depth, d_cams, d_poses_out }; q.start = d_start_poses;
+	return update_dev(ctx, q, stream);
+}
+extern "C" int ht_update_direct_sync(ht_ctx *ctx, const uint16_t *depth, const float *cams, int side, int B, float *poses_out, float *cnn_out)
+{
+	update_req q = { "ht_update_direct", FRAMES_DIRECT, side, side, side, 0.0f, UPD_FULL, B, depth, cams, poses_out }; q.cnn = cnn_out;
+	return update_host(ctx, q);
+}
+// Without flags the call IS ht_update_frames_sized_*, on the caller's own pointers: no mirror launch, no staging, that call's name and alignment rule
+extern "C" int ht_update_hands_dev(ht_ctx *ctx, int side, const uint16_t *d_depth, const float *d_cams, int w, int h, float segment_scale, const unsigned char *d_hands, const float *d_start_poses, int B, float *d_poses_out, void *stream)
+{
+	update_req q = { d_hands ? "ht_update_hands" : "ht_update_frames_sized", FRAMES_SIZED, side, w, h, segment_scale, UPD_FULL, B, d_depth, d_cams, d_poses_out }; q.start = d_start_poses; q.hands = d_hands;
+	return update_dev(ctx, q, stream);
+}
+extern "C" int ht_update_hands_sync(ht_ctx *ctx, int side, const uint16_t *depth, const float *cams, int w, int h, float segment_scale, const unsigned char *hands, int B, float *poses_out, float *cnn_out)
+{
+	update_req q = { hands ? "ht_update_hands" : "ht_update_frames_sized", FRAMES_SIZED, side, w, h, segment_scale, UPD_FULL, B, depth, cams, poses_out }; q.cnn = cnn_out; q.hands = hands;
+	return update_host(ctx, q);
 }
 extern "C" int ht_update_two_hands_dev(ht_ctx *ctx, int side, const uint16_t *d_depth, const float *d_cams, int w, int h, float segment_scale, uint16_t range_lo, uint16_t range_hi, uint16_t max_step,
                                        int min_pixels, uint16_t far, int flags, const float *d_start_poses, int B, float *d_poses_out, int32_t *d_info, void *stream)
 {
 	const two_hands_args a = { range_lo, range_hi, max_step, far, min_pixels, flags, 0.0f, -1 };
-	return two_hands_dev(ctx, side, d_depth, d_cams, w, h, segment_scale, a, d_start_poses, B, d_poses_out, d_info, nullptr, stream);
+	update_req q = { "ht_update_two_hands", FRAMES_SIZED, side, w, h, segment_scale, UPD_FULL, B, d_depth, d_cams, d_poses_out }; q.start = d_start_poses; q.two = &a; q.info = d_info;
+	return update_dev(ctx, q, stream);
 }
 extern "C" int ht_update_two_hands_sync(ht_ctx *ctx, int side, const uint16_t *depth, const float *cams, int w, int h, float segment_scale, uint16_t range_lo, uint16_t range_hi, uint16_t max_step,
                                         int min_pixels, uint16_t far, int flags, int B, float *poses_out, int32_t *info, float *cnn_out)
 {
 	const two_hands_args a = { range_lo, range_hi, max_step, far, min_pixels, flags, 0.0f, -1 };
-	return two_hands_sync(ctx, side, depth, cams, w, h, segment_scale, a, B, poses_out, info, nullptr, cnn_out);
+	update_req q = { "ht_update_two_hands", FRAMES_SIZED, side, w, h, segment_scale, UPD_FULL, B, depth, cams, poses_out }; q.cnn = cnn_out; q.two = &a; q.info = info;
+	return update_host(ctx, q);
 }
 // The same calls with the model split in front.  mode below 0 would name the blob split: refused with every other unknown mode.  HT_SPLIT_USER_POSES
 // is the split calls' alone: d_start_poses also seed the slots, as centre-of-mass poses
@@ -865,24 +868,23 @@ extern "C" int ht_update_two_hands_model_dev(ht_ctx *ctx, int side, const uint16
                                              int min_pixels, uint16_t far, float max_dist, int mode, int flags, const float *d_start_poses, int B, float *d_poses_out, int32_t *d_info, int32_t *d_source, void *stream)
 {
 	const two_hands_args a = { range_lo, range_hi, max_step, far, min_pixels, flags, max_dist, mode < 0 ? 0x7fffffff : mode };
-	return two_hands_dev(ctx, side, d_depth, d_cams, w, h, segment_scale, a, d_start_poses, B, d_poses_out, d_info, d_source, stream);
+	update_req q = { "ht_update_two_hands", FRAMES_SIZED, side, w, h, segment_scale, UPD_FULL, B, d_depth, d_cams, d_poses_out }; q.start = d_start_poses; q.two = &a; q.info = d_info; q.source = d_source;
+	return update_dev(ctx, q, stream);
 }
 extern "C" int ht_update_two_hands_model_sync(ht_ctx *ctx, int side, const uint16_t *depth, const float *cams, int w, int h, float segment_scale, uint16_t range_lo, uint16_t range_hi, uint16_t max_step,
                                               int min_pixels, uint16_t far, float max_dist, int mode, int flags, int B, float *poses_out, int32_t *info, int32_t *source, float *cnn_out)
 {
 	const two_hands_args a = { range_lo, range_hi, max_step, far, min_pixels, flags, max_dist, mode < 0 ? 0x7fffffff : mode };
-	return two_hands_sync(ctx, side, depth, cams, w, h, segment_scale, a, B, poses_out, info, source, cnn_out);
+	update_req q = { "ht_update_two_hands", FRAMES_SIZED, side, w, h, segment_scale, UPD_FULL, B, depth, cams, poses_out }; q.cnn = cnn_out; q.two = &a; q.info = info; q.source = source;
+	return update_host(ctx, q);
 }
-
-// HandTracker::update_cnn_model (handtrack.h:734-741) and kickstart (:743-746) for B trackers, frames of any supported size
+// HandTracker::update_cnn_model (handtrack.h:734-741) and kickstart (:743-746) for B trackers; every output is optional
 extern "C" int ht_update_cnn_model_sync(ht_ctx *ctx, const uint16_t *depth, const float *cams, int w, int h, float segment_scale, int B, int apply_to_handmodel,
                                         float *poses_out, int *accepted_out, float *cnn_out)
 {
-	CHECK_READY(ctx); CHECK_MODEL(ctx); CHECK_BATCH(ctx, B);
-	if (!depth || !cams) return HT_ERR_ARG;
-	if (!frames_args_ok(ctx, w, h)) return HT_ERR_ARG;
-	const frame_src fs = { w, h, segment_scale, 0 };
-	return update_sync(ctx, depth, cams, fs, apply_to_handmodel ? UPD_KICKSTART : UPD_CNN_MODEL, B, poses_out, accepted_out, cnn_out, "ht_update_cnn_model");
+	update_req q = { "ht_update_cnn_model", FRAMES_PLAIN, 64, w, h, segment_scale, apply_to_handmodel ? UPD_KICKSTART : UPD_CNN_MODEL, B, depth, cams, poses_out };
+	q.cnn = cnn_out; q.accepted = accepted_out; q.poses_optional = true;
+	return update_host(ctx, q);
 }
 // ---- the reference's OVERLAPPED update() (handtrack.h:748-785) on two contexts of one device ----------------------------------------------------------------
 // The reference runs the CNN job (update_cnn_model_threadsafe: net, decode, FitError, reset, MultiStepSim, accept decision) on a background thread and lets the caller go
@@ -905,19 +907,16 @@ __global__ void k_job_collect(float *__restrict__ hand, const float *__restrict_
 }
 extern "C" int ht_update_passes_sync(ht_ctx *ctx, const uint16_t *depth, const float *cams, int w, int h, int B, float *poses_out)
 {
-	CHECK_READY(ctx); CHECK_MODEL(ctx); CHECK_BATCH(ctx, B);
-	if (!depth || !cams || !poses_out) return HT_ERR_ARG;
-	if (!frames_args_ok(ctx, w, h)) return HT_ERR_ARG;
-	const frame_src fs = { w, h, 0.17f, 0 };
-	return update_sync(ctx, depth, cams, fs, UPD_PASSES, B, poses_out, nullptr, nullptr, "ht_update_passes");
+	update_req q = { "ht_update_passes", FRAMES_PLAIN, 64, w, h, 0.17f, UPD_PASSES, B, depth, cams, poses_out };
+	return update_host(ctx, q);
 }
 extern "C" int ht_job_start(ht_ctx *job, ht_ctx *main, const uint16_t *depth, const float *cams, int w, int h, float segment_scale, int B)
 {
 	CHECK_READY(job); CHECK_MODEL(job); CHECK_BATCH(job, B);
 	if (!main || !depth || !cams || main == job || main->device != job->device || main->model.nb != job->model.nb || B > main->B) { job->err = "ht_job_start: the two contexts must be different ones of one device with the same model"; return HT_ERR_ARG; }
 	if (job->job_pending) { job->err = "ht_job_start: a job is in flight on this context (ht_job_collect takes it over)"; return HT_ERR_STATE; }
-	const bool tile = (w == 64 && h == 64);
-	if (!tile && !frames_args_ok(job, w, h)) return HT_ERR_ARG;
+	frame_src fs;
+	{ const int r = resolve_frames(job, FRAMES_PLAIN, 64, w, h, segment_scale, fs); if (r) return r; }
 	hipStream_t s = job->stream;
 	const int nb = job->model.nb;
 	const size_t npx = (size_t)w * h, in_bytes = (size_t)B * npx * sizeof(uint16_t), cam_bytes = (size_t)B * HT_CAM * sizeof(float);
@@ -926,7 +925,7 @@ extern "C" int ht_job_start(ht_ctx *job, ht_ctx *main, const uint16_t *depth, co
 	HIPCHK(job, hipStreamSynchronize(main->stream));      // the caller's context is between two of its (synchronous) calls: its handmodel is final
 	memcpy(job->h_job_in, depth, in_bytes); memcpy((char *)job->h_job_in + in_bytes, cams, cam_bytes);      // the caller's image need not outlive this call (the reference moves it into the task)
 	const uint16_t *d_in; const float *d_cin;
-	{ const int r = stage_frames(job, (const uint16_t *)job->h_job_in, (const float *)((const char *)job->h_job_in + in_bytes), w, h, B, s, &d_in, &d_cin); if (r) return r; }
+	{ const int r = stage_frames(job, (const uint16_t *)job->h_job_in, (const float *)((const char *)job->h_job_in + in_bytes), fs, B, s, &d_in, &d_cin); if (r) return r; }
 	// the job looks at handmodel (FitError of the carried pose, :704) and starts othermodel from its pose (:757); prev_frame_error and initializing as they stand
 	HIPCHK(job, hipMemcpyAsync(job->d_state[0], main->d_state[0], (size_t)B * nb * HT_STATE_STRIDE * sizeof(float), hipMemcpyDeviceToDevice, s));
 	ht_launch_set_pose(job->d_state[1], main->d_state[0], nb, B, 2, s);
@@ -937,8 +936,7 @@ extern "C" int ht_job_start(ht_ctx *job, ht_ctx *main, const uint16_t *depth, co
 	if (!job->ev_seed) HIPCHK(job, hipEventCreateWithFlags(&job->ev_seed, hipEventDisableTiming));
 	HIPCHK(job, hipEventRecord(job->ev_seed, s));
 	HIPCHK(job, hipStreamWaitEvent(main->stream, job->ev_seed, 0));
-	const frame_src fs = { w, h, segment_scale, 0 };
-	int r = run_update(job, d_in, d_cin, nullptr, B, job->d_poses_out, nullptr, s, tile ? nullptr : &fs, UPD_CNN_MODEL);
+	int r = run_update(job, d_in, d_cin, nullptr, B, job->d_poses_out, nullptr, s, fs, UPD_CNN_MODEL);
 	if (r) { (void)hipStreamSynchronize(s); return r; }      // the queued uploads read h_job_in: nothing may be in flight when the caller frees or reuses it
 	HIPCHK(job, hipEventRecord(job->ev_job, s));
 	job->job_pending = true;

@@ -423,13 +423,24 @@ class Context:
         e = _c(prev_frame_error, np.float32); i = _c(initializing, np.int32)
         self._chk(self.L.ht_set_tracker_flags(self.h, first, e.size, _f(e), _i(i)))
 
+    def _update_io(self, depth, cams, want_cnn, pixels=None, per_frame=1, cam_rows=0):
+        """What every update_*_sync starts with -> (B, h, w, depth pointer, cams pointer, poses, cnn, poses pointer, cnn pointer or None): depth as contiguous uint16
+        [B,h,w] (pixels: flattened frames [B,pixels]; h and w are None then), cams as float32 (cam_rows: 0 one row per frame, -1 any number of rows, None taken as they
+        come), fresh poses [B,nb,7] (per_frame 2: [B,2,nb,7]) and, on request, cnn_out of per_frame * B rows.  The pointers keep their arrays alive."""
+        depth = _c(depth, np.uint16)
+        if pixels is not None:
+            depth = depth.reshape(-1, pixels)
+        B, h, w = depth.shape if pixels is None else (depth.shape[0], None, None)
+        cams = _c(cams, np.float32)
+        if cam_rows is not None:
+            cams = cams.reshape(cam_rows or B, CAM)
+        poses = np.empty((B, self.nb, POSE) if per_frame == 1 else (B, per_frame, self.nb, POSE), np.float32)
+        cnn = np.empty((per_frame * B, CNN_OUT), np.float32) if want_cnn else None
+        return B, h, w, depth.ctypes.data_as(C.POINTER(C.c_uint16)), _f(cams), poses, cnn, _f(poses), _f(cnn) if want_cnn else None
+
     def update_sync(self, depth, cams, want_cnn=False):
-        depth = _c(depth, np.uint16).reshape(-1, 4096)
-        cams = _c(cams, np.float32).reshape(-1, CAM)
-        B = depth.shape[0]
-        poses = np.empty((B, self.nb, POSE), np.float32)
-        cnn = np.empty((B, CNN_OUT), np.float32) if want_cnn else None
-        self._chk(self.L.ht_update_sync(self.h, depth.ctypes.data_as(C.POINTER(C.c_uint16)), _f(cams), B, _f(poses), _f(cnn) if want_cnn else None))
+        B, _, _, dp, cp, poses, cnn, pp, np_ = self._update_io(depth, cams, want_cnn, pixels=4096, cam_rows=-1)
+        self._chk(self.L.ht_update_sync(self.h, dp, cp, B, pp, np_))
         return (poses, cnn) if want_cnn else poses
 
     def update_dev(self, d_depth, d_cams, d_start, B, d_poses_out, stream):
@@ -437,11 +448,8 @@ class Context:
 
     def update_frames_sync(self, depth, cams, segment_scale=0.17, want_cnn=False):
         """HandTracker::update on frames of any size (handtrack.h:693-785): depth u16[B,h,w], cams [B,12] = the frames' cameras."""
-        depth = _c(depth, np.uint16); B, h, w = depth.shape
-        cams = _c(cams, np.float32).reshape(B, CAM)
-        poses = np.empty((B, self.nb, POSE), np.float32)
-        cnn = np.empty((B, CNN_OUT), np.float32) if want_cnn else None
-        self._chk(self.L.ht_update_frames_sync(self.h, depth.ctypes.data_as(C.POINTER(C.c_uint16)), _f(cams), w, h, float(segment_scale), B, _f(poses), _f(cnn) if want_cnn else None))
+        B, h, w, dp, cp, poses, cnn, pp, np_ = self._update_io(depth, cams, want_cnn)
+        self._chk(self.L.ht_update_frames_sync(self.h, dp, cp, w, h, float(segment_scale), B, pp, np_))
         return (poses, cnn) if want_cnn else poses
 
     def update_frames_dev(self, d_depth, d_cams, w, h, segment_scale, d_start, B, d_poses_out, stream):
@@ -449,11 +457,8 @@ class Context:
 
     def update_frames_sized_sync(self, depth, cams, side=128, segment_scale=0.17, want_cnn=False):
         """HandTracker::update on frames up to 640x480 with the segment cut at `side` for the net of that input size (ht_update_frames_sized_sync): depth u16[B,h,w], cams [B,12]."""
-        depth = _c(depth, np.uint16); B, h, w = depth.shape
-        cams = _c(cams, np.float32).reshape(B, CAM)
-        poses = np.empty((B, self.nb, POSE), np.float32)
-        cnn = np.empty((B, CNN_OUT), np.float32) if want_cnn else None
-        self._chk(self.L.ht_update_frames_sized_sync(self.h, int(side), depth.ctypes.data_as(C.POINTER(C.c_uint16)), _f(cams), w, h, float(segment_scale), B, _f(poses), _f(cnn) if want_cnn else None))
+        B, h, w, dp, cp, poses, cnn, pp, np_ = self._update_io(depth, cams, want_cnn)
+        self._chk(self.L.ht_update_frames_sized_sync(self.h, int(side), dp, cp, w, h, float(segment_scale), B, pp, np_))
         return (poses, cnn) if want_cnn else poses
 
     def update_frames_sized_dev(self, side, d_depth, d_cams, w, h, segment_scale, d_start, B, d_poses_out, stream):
@@ -505,12 +510,9 @@ class Context:
 
     def update_hands_sync(self, depth, cams, hands, side=64, segment_scale=0.17, want_cnn=False):
         """ht_update_frames_sized_sync with a handedness flag per frame (ht_update_hands_sync): the poses of flagged frames are a left hand's; cnn_out stays canonical."""
-        depth = _c(depth, np.uint16); cams = _c(cams, np.float32)
-        B, h, w = depth.shape
+        B, h, w, dp, cp, poses, cnn, pp, np_ = self._update_io(depth, cams, want_cnn, cam_rows=None)
         hands, hp = self._hands(hands, B)
-        poses = np.empty((B, self.nb, POSE), np.float32)
-        cnn = np.empty((B, CNN_OUT), np.float32) if want_cnn else None
-        self._chk(self.L.ht_update_hands_sync(self.h, int(side), depth.ctypes.data_as(C.POINTER(C.c_uint16)), _f(cams), w, h, float(segment_scale), hp, B, _f(poses), _f(cnn) if want_cnn else None))
+        self._chk(self.L.ht_update_hands_sync(self.h, int(side), dp, cp, w, h, float(segment_scale), hp, B, pp, np_))
         return (poses, cnn) if want_cnn else poses
 
     def update_hands_dev(self, side, d_depth, d_cams, w, h, segment_scale, d_hands, d_start, B, d_poses_out, stream=None):
@@ -549,12 +551,10 @@ class Context:
 
     def update_two_hands_sync(self, depth, cams, range_lo, range_hi, far, side=64, segment_scale=0.17, max_step=65535, min_pixels=1, flags=0, want_cnn=False):
         """B frames of two hands each in slots 2i (right) and 2i+1 (left): poses [B,2,nb,7] in the camera's space, info i32[B,2,8], and cnn_out [2B,2304] (canonical) on request"""
-        depth = _c(depth, np.uint16); cams = _c(cams, np.float32)
-        B, h, w = depth.shape
-        poses = np.empty((B, 2, self.nb, POSE), np.float32); info = np.empty((B, 2, 8), np.int32)
-        cnn = np.empty((2 * B, CNN_OUT), np.float32) if want_cnn else None
-        self._chk(self.L.ht_update_two_hands_sync(self.h, int(side), depth.ctypes.data_as(C.POINTER(C.c_uint16)), _f(cams), w, h, float(segment_scale), int(range_lo), int(range_hi), int(max_step),
-                                                  int(min_pixels), int(far), int(flags), B, _f(poses), info.ctypes.data_as(C.POINTER(C.c_int32)), _f(cnn) if want_cnn else None))
+        B, h, w, dp, cp, poses, cnn, pp, np_ = self._update_io(depth, cams, want_cnn, per_frame=2, cam_rows=None)
+        info = np.empty((B, 2, 8), np.int32)
+        self._chk(self.L.ht_update_two_hands_sync(self.h, int(side), dp, cp, w, h, float(segment_scale), int(range_lo), int(range_hi), int(max_step),
+                                                  int(min_pixels), int(far), int(flags), B, pp, info.ctypes.data_as(C.POINTER(C.c_int32)), np_))
         return (poses, info, cnn) if want_cnn else (poses, info)
 
     def update_two_hands_dev(self, side, d_depth, d_cams, w, h, segment_scale, range_lo, range_hi, max_step, min_pixels, far, flags, d_start, B, d_poses_out, d_info=None, stream=None):
@@ -595,14 +595,11 @@ class Context:
     def update_two_hands_model(self, depth, cams, range_lo, range_hi, far, max_dist=float("inf"), mode=SPLIT_MODEL_MERGED, side=64, segment_scale=0.17, max_step=65535, min_pixels=1, flags=0, want_cnn=False):
         """update_two_hands_sync with the model split in front, priors the slots' carried state: poses [B,2,nb,7], info i32[B,2,8], source i32[B], and cnn_out [2B,2304] on request
         (ht_update_two_hands_model_sync)"""
-        depth = _c(depth, np.uint16); cams = _c(cams, np.float32)
-        B, h, w = depth.shape
-        poses = np.empty((B, 2, self.nb, POSE), np.float32); info = np.empty((B, 2, 8), np.int32); source = np.empty(B, np.int32)
-        cnn = np.empty((2 * B, CNN_OUT), np.float32) if want_cnn else None
+        B, h, w, dp, cp, poses, cnn, pp, np_ = self._update_io(depth, cams, want_cnn, per_frame=2, cam_rows=None)
+        info = np.empty((B, 2, 8), np.int32); source = np.empty(B, np.int32)
         i32 = C.POINTER(C.c_int32)
-        self._chk(self.L.ht_update_two_hands_model_sync(self.h, int(side), depth.ctypes.data_as(C.POINTER(C.c_uint16)), _f(cams), w, h, float(segment_scale), int(range_lo), int(range_hi), int(max_step),
-                                                        int(min_pixels), int(far), float(max_dist), int(mode), int(flags), B, _f(poses), info.ctypes.data_as(i32), source.ctypes.data_as(i32),
-                                                        _f(cnn) if want_cnn else None))
+        self._chk(self.L.ht_update_two_hands_model_sync(self.h, int(side), dp, cp, w, h, float(segment_scale), int(range_lo), int(range_hi), int(max_step),
+                                                        int(min_pixels), int(far), float(max_dist), int(mode), int(flags), B, pp, info.ctypes.data_as(i32), source.ctypes.data_as(i32), np_))
         return (poses, info, source, cnn) if want_cnn else (poses, info, source)
 
     def update_two_hands_model_dev(self, side, d_depth, d_cams, w, h, segment_scale, range_lo, range_hi, max_step, min_pixels, far, max_dist, mode, flags, d_start, B, d_poses_out, d_info=None, d_source=None, stream=None):
@@ -611,12 +608,8 @@ class Context:
 
     def update_direct_sync(self, depth, cams, side=128, want_cnn=False):
         """BASELINE configs[4] end to end: depth u16[B,side,side] frames that are their own segment, the net of that input size (ht_update_direct_sync)."""
-        depth = _c(depth, np.uint16).reshape(-1, side * side)
-        B = depth.shape[0]
-        cams = _c(cams, np.float32).reshape(B, CAM)
-        poses = np.empty((B, self.nb, POSE), np.float32)
-        cnn = np.empty((B, CNN_OUT), np.float32) if want_cnn else None
-        self._chk(self.L.ht_update_direct_sync(self.h, depth.ctypes.data_as(C.POINTER(C.c_uint16)), _f(cams), int(side), B, _f(poses), _f(cnn) if want_cnn else None))
+        B, _, _, dp, cp, poses, cnn, pp, np_ = self._update_io(depth, cams, want_cnn, pixels=side * side)
+        self._chk(self.L.ht_update_direct_sync(self.h, dp, cp, int(side), B, pp, np_))
         return (poses, cnn) if want_cnn else (poses, None)
 
     def update_direct_dev(self, d_depth, d_cams, side, d_start, B, d_poses_out, stream):
@@ -627,10 +620,9 @@ class Context:
         depth = _c(depth, np.uint16)
         if depth.ndim == 2:
             depth = depth.reshape(-1, 64, 64)
-        B, h, w = depth.shape
-        cams = _c(cams, np.float32).reshape(B, CAM)
-        poses = np.empty((B, self.nb, POSE), np.float32); acc = np.empty(B, np.int32)
-        self._chk(self.L.ht_update_cnn_model_sync(self.h, depth.ctypes.data_as(C.POINTER(C.c_uint16)), _f(cams), w, h, float(segment_scale), B, int(bool(kickstart)), _f(poses), _i(acc), None))
+        B, h, w, dp, cp, poses, _, pp, _ = self._update_io(depth, cams, False)
+        acc = np.empty(B, np.int32)
+        self._chk(self.L.ht_update_cnn_model_sync(self.h, dp, cp, w, h, float(segment_scale), B, int(bool(kickstart)), pp, _i(acc), None))
         return poses, acc
 
     def cnn_results(self, n, first=0):
