@@ -11,6 +11,7 @@
 #include "ht_device.hpp"
 #include "ht_model_build.hpp"
 #include "ht_launch.hpp"
+#include "ht_raster.hpp"
 
 struct ht_model
 {
@@ -253,6 +254,46 @@ extern "C" int ht_model_render_mesh(const ht_model *m, const float *poses, const
 		const mesh_hit hit = mesh_hitcheck(m, poses, V3(0.0f, 0.0f, 0.0f), v1);
 		depth[(size_t)y * w + x] = (unsigned short)(hit.impact.z / ds);
 		if (body) body[(size_t)y * w + x] = (int8_t)hit.body;
+	}
+	return HT_OK;
+}
+
+// The forward z-buffer rasteriser of the same meshes (the definition is in include/ht_mi355x.h and, per triangle and pixel, in ht_raster.hpp):
+// a plain loop over bodies, triangles and the pixels of each triangle's own rectangle.  The smallest count wins a pixel, the first in (body, triangle) order on equal
+// counts.  This is the definition ht_raster_mesh_depth is held to.
+extern "C" int ht_model_raster_mesh(const ht_model *m, const float *poses, const float *cam12, int w, int h, float far, float pixel_offset, uint16_t *depth, int8_t *body)
+{
+	if (!m || !poses || !cam12 || !depth || w < 1 || h < 1 || w > 4096 || h > 4096 || !(far > 0.0f) || !(pixel_offset >= 0.0f && pixel_offset <= 1.0f)) return HT_ERR_ARG;
+	const float fx = cam12[0], fy = cam12[1], px = cam12[2], py = cam12[3], ds = cam12[4];
+	std::vector<int> best((size_t)w * h, 65536), who((size_t)w * h, -1);
+	for (int b = 0; b < m->nb; b++)
+	{
+		const float *p = poses + 7 * b;
+		const m3 R = qmat(V4(p[3], p[4], p[5], p[6]));
+		const v3 up = V3(p[0], p[1], p[2]) - mul(R, V3(m->com[3 * b], m->com[3 * b + 1], m->com[3 * b + 2]));
+		const std::vector<float> &C = m->sdverts[b];
+		for (size_t k = 0; 9 * k < C.size(); k++)
+		{
+			const float *c = &C[9 * k];
+			rz_tri T;
+			if (!rz_setup(R, up, V3(c[0], c[1], c[2]), V3(c[3], c[4], c[5]), V3(c[6], c[7], c[8]), fx, fy, px, py, pixel_offset, T)) continue;
+			int x0, x1, y0, y1;
+			rz_rect(T, x0, x1, y0, y1);
+			x0 = x0 < 0 ? 0 : x0; y0 = y0 < 0 ? 0 : y0; x1 = x1 > w - 1 ? w - 1 : x1; y1 = y1 > h - 1 ? h - 1 : y1;
+			for (int y = y0; y <= y1; y++) for (int x = x0; x <= x1; x++)
+			{
+				if (!rz_inside(T, x, y)) continue;
+				const int n = rz_count(T, rz_ray(x, pixel_offset, px, fx), rz_ray(y, pixel_offset, py, fy), far, ds);
+				const size_t o = (size_t)y * w + x;
+				if (n >= 0 && n < best[o]) { best[o] = n; who[o] = b; }
+			}
+		}
+	}
+	const unsigned short bg = (unsigned short)(far / ds);
+	for (size_t o = 0; o < best.size(); o++)
+	{
+		depth[o] = who[o] >= 0 ? (unsigned short)best[o] : bg;
+		if (body) body[o] = (int8_t)who[o];
 	}
 	return HT_OK;
 }

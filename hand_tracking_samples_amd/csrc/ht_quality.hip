@@ -443,17 +443,22 @@ static int quality_reserve(ht_ctx *ctx, size_t pose_floats, size_t frame_px)
 	{ const int r = dev_grow(ctx, &ctx->d_quality_poses, &ctx->quality_poses_cap, pose_floats); if (r) return r; }
 	return dev_grow(ctx, &ctx->d_quality_frames, &ctx->quality_frames_cap, frame_px);
 }
-static int pr_check(ht_ctx *ctx, const void *poses, const void *cams, const void *depth, const void *info, int w, int h, int B, int flags, float far, int lo, int hi, int tol)
+// The two composites differ in their renderer alone: the hulls (ht_pose_depth_residual) or the rasterised meshes at pixel offset 0 (ht_pose_mesh_residual)
+static const char *pr_name(bool mesh) { return mesh ? "ht_pose_mesh_residual" : "ht_pose_depth_residual"; }
+static int pr_check(ht_ctx *ctx, bool mesh, const void *poses, const void *cams, const void *depth, const void *info, int w, int h, int B, int flags, float far, int lo, int hi, int tol)
 {
+	const std::string fn = pr_name(mesh);
 	CHECK_MODEL(ctx);
-	if (!poses || !cams) { ctx->err = "ht_pose_depth_residual: bad argument"; return HT_ERR_ARG; }
-	if (flags & ~HT_KP_COM_POSES) { ctx->err = "ht_pose_depth_residual: unknown flags"; return HT_ERR_ARG; }
-	if (!(far > 0.0f) || !isfinite(far)) { ctx->err = "ht_pose_depth_residual: far must be positive and finite"; return HT_ERR_ARG; }
-	if ((long long)B * ctx->model.nb > 0x7fffffffLL / HT_POSE) { ctx->err = "ht_pose_depth_residual: more than 2^31 pose floats in one call"; return HT_ERR_ARG; }
-	return dc_check(ctx, "ht_pose_depth_residual", depth, depth, info, w, h, B, lo, hi, tol);
+	if (!poses || !cams) { ctx->err = fn + ": bad argument"; return HT_ERR_ARG; }
+	if (flags & ~HT_KP_COM_POSES) { ctx->err = fn + ": unknown flags"; return HT_ERR_ARG; }
+	if (!(far > 0.0f) || !isfinite(far)) { ctx->err = fn + ": far must be positive and finite"; return HT_ERR_ARG; }
+	if ((long long)B * ctx->model.nb > 0x7fffffffLL / HT_POSE) { ctx->err = fn + ": more than 2^31 pose floats in one call"; return HT_ERR_ARG; }
+	{ const int r = dc_check(ctx, pr_name(mesh), depth, depth, info, w, h, B, lo, hi, tol); if (r) return r; }
+	if (mesh && !ctx->d_mesh) { ctx->err = "the model file holds no subdivision meshes (bake it again)"; return HT_ERR_STATE; }
+	return HT_OK;
 }
-static int pr_enqueue(ht_ctx *ctx, const float *d_poses, const float *d_cams, const uint16_t *d_depth, int w, int h, int B, int flags, float far, int lo, int hi, int tol, int64_t *d_info, uint16_t *d_rendered,
-                      hipStream_t s)
+static int pr_enqueue(ht_ctx *ctx, bool mesh, const float *d_poses, const float *d_cams, const uint16_t *d_depth, int w, int h, int B, int flags, float far, int lo, int hi, int tol, int64_t *d_info,
+                      uint16_t *d_rendered, hipStream_t s)
 {
 	const long long n = (long long)B * ctx->model.nb;
 	uint16_t *frames = d_rendered ? d_rendered : ctx->d_quality_frames;
@@ -461,29 +466,42 @@ static int pr_enqueue(ht_ctx *ctx, const float *d_poses, const float *d_cams, co
 		ht_prof_scope ps(ctx, "k_pose_to_render", s);
 		hipLaunchKernelGGL(k_pose_to_render, dim3((unsigned)((n + QL_THREADS - 1) / QL_THREADS)), dim3(QL_THREADS), 0, s, ctx->model, d_poses, d_cams, n, (flags & HT_KP_COM_POSES) ? 1 : 0, ctx->d_quality_poses);
 	}
-	{ const int r = ht_render_depth_dev(ctx, ctx->d_quality_poses, d_cams, w, h, far, B, frames, nullptr, s); if (r) return r; }
+	{
+		const int r = mesh ? ht_raster_mesh_depth_dev(ctx, ctx->d_quality_poses, d_cams, w, h, far, 0.0f, B, frames, nullptr, s) : ht_render_depth_dev(ctx, ctx->d_quality_poses, d_cams, w, h, far, B, frames, nullptr, s);
+		if (r) return r;
+	}
 	return dc_enqueue(ctx, d_depth, frames, w, h, B, lo, hi, tol, d_info, s);
 }
-extern "C" int ht_pose_depth_residual_dev(ht_ctx *ctx, const float *d_poses, const float *d_cams, const uint16_t *d_depth, int w, int h, int B, int flags, float far, int lo, int hi, int tol, int64_t *d_info,
-                                          uint16_t *d_rendered, void *stream)
+static int pr_dev(ht_ctx *ctx, bool mesh, const float *d_poses, const float *d_cams, const uint16_t *d_depth, int w, int h, int B, int flags, float far, int lo, int hi, int tol, int64_t *d_info,
+                  uint16_t *d_rendered, void *stream)
 {
 	CHECK_READY(ctx);
-	{ const int r = pr_check(ctx, d_poses, d_cams, d_depth, d_info, w, h, B, flags, far, lo, hi, tol); if (r) return r; }
+	{ const int r = pr_check(ctx, mesh, d_poses, d_cams, d_depth, d_info, w, h, B, flags, far, lo, hi, tol); if (r) return r; }
 	if (B == 0) return HT_OK;
 	{ const int r = quality_reserve(ctx, (size_t)B * ctx->model.nb * HT_POSE, d_rendered ? 0 : (size_t)B * w * h); if (r) return r; }
-	return pr_enqueue(ctx, d_poses, d_cams, d_depth, w, h, B, flags, far, lo, hi, tol, d_info, d_rendered, ht_user_stream(ctx, stream));
+	return pr_enqueue(ctx, mesh, d_poses, d_cams, d_depth, w, h, B, flags, far, lo, hi, tol, d_info, d_rendered, ht_user_stream(ctx, stream));
 }
-extern "C" int ht_pose_depth_residual(ht_ctx *ctx, const float *poses, const float *cams, const uint16_t *depth, int w, int h, int B, int flags, float far, int lo, int hi, int tol, int64_t *info, uint16_t *rendered)
+static int pr_host(ht_ctx *ctx, bool mesh, const float *poses, const float *cams, const uint16_t *depth, int w, int h, int B, int flags, float far, int lo, int hi, int tol, int64_t *info, uint16_t *rendered)
 {
 	CHECK_READY(ctx);
-	{ const int r = pr_check(ctx, poses, cams, depth, info, w, h, B, flags, far, lo, hi, tol); if (r) return r; }
+	{ const int r = pr_check(ctx, mesh, poses, cams, depth, info, w, h, B, flags, far, lo, hi, tol); if (r) return r; }
 	const size_t n = (size_t)B, bytes = n * w * h * sizeof(uint16_t);
 	const ql_buf in[3] = { { poses, n * ctx->model.nb * HT_POSE * sizeof(float) }, { cams, n * HT_CAM * sizeof(float) }, { depth, bytes } };
 	const ql_buf out[2] = { { info, n * 8 * sizeof(int64_t) }, { rendered, bytes } };
-	if (ql_any_overlap(in, 3, out, 2)) { ctx->err = "ht_pose_depth_residual: an output overlaps an input or another output"; return HT_ERR_ARG; }
+	if (ql_any_overlap(in, 3, out, 2)) { ctx->err = std::string(pr_name(mesh)) + ": an output overlaps an input or another output"; return HT_ERR_ARG; }
 	if (B == 0) return HT_OK;
 	{ const int r = quality_reserve(ctx, n * ctx->model.nb * HT_POSE, rendered ? 0 : n * w * h); if (r) return r; }
 	ht_seg seg[5] = { { (void *)poses, in[0].bytes, false }, { (void *)cams, in[1].bytes, false }, { (void *)depth, bytes, false }, { info, out[0].bytes, true }, { rendered, bytes, true } };
 	return ht_staged_call(ctx, seg, 5, [&](hipStream_t s)
-	                      { return pr_enqueue(ctx, (const float *)seg[0].dev, (const float *)seg[1].dev, (const uint16_t *)seg[2].dev, w, h, B, flags, far, lo, hi, tol, (int64_t *)seg[3].dev, (uint16_t *)seg[4].dev, s); });
+	                      { return pr_enqueue(ctx, mesh, (const float *)seg[0].dev, (const float *)seg[1].dev, (const uint16_t *)seg[2].dev, w, h, B, flags, far, lo, hi, tol, (int64_t *)seg[3].dev, (uint16_t *)seg[4].dev, s); });
 }
+extern "C" int ht_pose_depth_residual_dev(ht_ctx *ctx, const float *d_poses, const float *d_cams, const uint16_t *d_depth, int w, int h, int B, int flags, float far, int lo, int hi, int tol, int64_t *d_info,
+                                          uint16_t *d_rendered, void *stream)
+{ return pr_dev(ctx, false, d_poses, d_cams, d_depth, w, h, B, flags, far, lo, hi, tol, d_info, d_rendered, stream); }
+extern "C" int ht_pose_depth_residual(ht_ctx *ctx, const float *poses, const float *cams, const uint16_t *depth, int w, int h, int B, int flags, float far, int lo, int hi, int tol, int64_t *info, uint16_t *rendered)
+{ return pr_host(ctx, false, poses, cams, depth, w, h, B, flags, far, lo, hi, tol, info, rendered); }
+extern "C" int ht_pose_mesh_residual_dev(ht_ctx *ctx, const float *d_poses, const float *d_cams, const uint16_t *d_depth, int w, int h, int B, int flags, float far, int lo, int hi, int tol, int64_t *d_info,
+                                         uint16_t *d_rendered, void *stream)
+{ return pr_dev(ctx, true, d_poses, d_cams, d_depth, w, h, B, flags, far, lo, hi, tol, d_info, d_rendered, stream); }
+extern "C" int ht_pose_mesh_residual(ht_ctx *ctx, const float *poses, const float *cams, const uint16_t *depth, int w, int h, int B, int flags, float far, int lo, int hi, int tol, int64_t *info, uint16_t *rendered)
+{ return pr_host(ctx, true, poses, cams, depth, w, h, B, flags, far, lo, hi, tol, info, rendered); }

@@ -38,6 +38,7 @@ SYMBOLS = (
     "ht_cnn_grad_batch_sized_dev", "ht_cnn_grad_batch_sized", "ht_cnn_grad_get_sized", "ht_cnn_grad_set_sized", "ht_cnn_grad_ptr_sized", "ht_opt_default", "ht_cnn_opt_step_sized_dev",
     "ht_cnn_opt_reset_sized", "ht_cnn_opt_state_get_sized", "ht_cnn_opt_state_set_sized", "ht_cnn_opt_last_sized", "ht_cnn_train_opt_sized_dev",
     "ht_model_open", "ht_model_close", "ht_model_error", "ht_model_counts", "ht_model_body", "ht_model_body_mesh", "ht_model_body_sdmesh", "ht_model_hitcheck", "ht_model_hitcheck_mesh", "ht_model_render_mesh", "ht_model_scale", "ht_render_mesh_depth", "ht_render_mesh_depth_dev",
+    "ht_model_raster_mesh", "ht_raster_mesh_depth", "ht_raster_mesh_depth_dev",
     "ht_tracker_reset", "ht_get_state", "ht_set_state", "ht_get_tracker_flags", "ht_set_tracker_flags", "ht_update_sync", "ht_update_dev", "ht_update_frames_sync", "ht_update_frames_dev", "ht_update_direct_sync", "ht_update_direct_dev", "ht_update_cnn_model_sync", "ht_get_cnn_results", "ht_get_cnn_layers", "ht_get_cnn_layers_sized", "ht_frames_overflow", "ht_reserve_points", "ht_point_capacity", "ht_capacity_events", "ht_segment_vr", "ht_segment_vr_dev", "ht_segment_vr_supported", "ht_segment_vr_sized", "ht_segment_vr_sized_dev", "ht_update_frames_sized_sync", "ht_update_frames_sized_dev", "ht_render_depth", "ht_render_depth_dev", "ht_slowfit", "ht_set_points", "ht_fit_rows", "ht_physics_update",
     "ht_stage_prepare", "ht_stage_decode", "ht_stage_fit_error", "ht_stage_cloud_rows", "ht_stage_contacts", "ht_stage_fit", "ht_debug_contact_plan",
     "ht_stage_multistep", "ht_stage_multistep_range", "ht_stage_scratch_unibody", "ht_stage_chamber", "ht_profile_enable", "ht_profile_read", "ht_debug_solve_stats", "ht_debug_contact_stats", "ht_debug_solver_build", "ht_debug_reset_flags", "ht_debug_reset_organisation", "ht_update_passes_sync", "ht_job_start", "ht_job_poll", "ht_job_wait", "ht_job_collect", "ht_debug_contact_kernel", "ht_debug_contact_order", "ht_debug_rank_desc", "ht_contact_capacity", "ht_debug_solve_tables", "ht_debug_solve_tables_header", "ht_debug_train_buffers",
@@ -49,7 +50,7 @@ SYMBOLS = (
     "ht_split_hands", "ht_split_hands_dev", "ht_update_two_hands_sync", "ht_update_two_hands_dev",
     "ht_split_hands_model", "ht_split_hands_model_dev", "ht_update_two_hands_model_sync", "ht_update_two_hands_model_dev",
     "ht_keypoint_table", "ht_keypoints", "ht_keypoints_dev", "ht_keypoint_errors", "ht_keypoint_errors_dev", "ht_depth_compare", "ht_depth_compare_dev",
-    "ht_pose_depth_residual", "ht_pose_depth_residual_dev",
+    "ht_pose_depth_residual", "ht_pose_depth_residual_dev", "ht_pose_mesh_residual", "ht_pose_mesh_residual_dev",
     "ht_kpfit_default", "ht_fit_keypoints", "ht_fit_keypoints_dev",
     "ht_comm_available", "ht_comm_unique_id", "ht_comm_init", "ht_comm_info", "ht_gather_poses_dev", "ht_gather_wait", "ht_gather_wait_host", "ht_comm_destroy",
 )
@@ -235,6 +236,9 @@ def load(build_if_missing=True):
     L.ht_render_mesh_depth_dev.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int, vp, vp, vp]
     L.ht_model_hitcheck_mesh.argtypes = [vp, fp, fp, fp, fp, fp, ip, ip]
     L.ht_model_render_mesh.argtypes = [vp, fp, fp, C.c_int, C.c_int, C.c_float, C.c_float, u16p, C.POINTER(C.c_int8)]
+    L.ht_raster_mesh_depth.argtypes = L.ht_render_mesh_depth.argtypes
+    L.ht_raster_mesh_depth_dev.argtypes = L.ht_render_mesh_depth_dev.argtypes
+    L.ht_model_raster_mesh.argtypes = L.ht_model_render_mesh.argtypes
     L.ht_model_scale.argtypes = [vp, C.c_float]
     L.ht_profile_read.argtypes = [vp, C.c_int, C.c_int, C.c_char_p, C.c_int, fp, ip, ip]
     L.ht_debug_solve_stats.argtypes = [vp, C.c_int, fp, C.c_int]
@@ -299,6 +303,8 @@ def load(build_if_missing=True):
     L.ht_depth_compare_dev.argtypes = [vp, vp, vp, ci, ci, ci, ci, ci, ci, vp, vp]
     L.ht_pose_depth_residual.argtypes = [vp, fp, fp, u16p, ci, ci, ci, ci, cf, ci, ci, ci, i64p, u16p]
     L.ht_pose_depth_residual_dev.argtypes = [vp, vp, vp, vp, ci, ci, ci, ci, cf, ci, ci, ci, vp, vp, vp]
+    L.ht_pose_mesh_residual.argtypes = L.ht_pose_depth_residual.argtypes
+    L.ht_pose_mesh_residual_dev.argtypes = L.ht_pose_depth_residual_dev.argtypes
     for name in SYMBOLS:
         if name not in ("ht_last_error", "ht_model_error"):
             getattr(L, name).restype = C.c_int
@@ -902,6 +908,15 @@ class Context:
         """ht_render_mesh_depth_dev: device pointers, asynchronous on `stream`."""
         self._chk(self.L.ht_render_mesh_depth_dev(self.h, d_poses, d_cams, int(w), int(h), float(far), float(pixel_offset), int(B), d_depth, d_body, stream))
 
+    def raster_mesh_depth(self, poses, cams, w, h, far=4.0, pixel_offset=0.0, want_body=False):
+        """The same surface through the z-buffer rasteriser (ht_raster_mesh_depth), bit-identical to HostModel.raster_mesh: shapes and conventions as
+        render_mesh_depth.  Its definition is its own (ht_mi355x.h), within one count of the ray cast where both pick the same triangle."""
+        return self._render(self.L.ht_raster_mesh_depth, poses, cams, w, h, far, (float(pixel_offset),), want_body)
+
+    def raster_mesh_depth_dev(self, d_poses, d_cams, w, h, far, pixel_offset, B, d_depth, d_body=None, stream=None):
+        """ht_raster_mesh_depth_dev: device pointers, asynchronous on `stream`."""
+        self._chk(self.L.ht_raster_mesh_depth_dev(self.h, d_poses, d_cams, int(w), int(h), float(far), float(pixel_offset), int(B), d_depth, d_body, stream))
+
     # -- joint coordinates (ht_mi355x.h "joint coordinates"): c = (s.x, s.y, t.z) per joint; com_poses: centre-of-mass poses instead of user poses
     def joint_coords(self, poses, com_poses=False, want_gaps=False):
         """poses [B,nb,7] -> coords [B,nj,3] (and the joints' anchor gaps [B,nj] with want_gaps)."""
@@ -1062,12 +1077,22 @@ class Context:
     def pose_depth_residual(self, poses, cams, depth, lo, hi, tol=0, far=4.0, com_poses=False, want_rendered=False):
         """Poses against frames: poses [B,nb,7] rendered as ht_render_depth does in each frame's camera and compared with depth u16[B,h,w] (a = observed, b = rendered)
         -> depth_figures in metres (and rendered u16[B,h,w] with want_rendered).  Choose hi <= far / depth_scale to keep the rendered background out."""
+        return self._pose_residual(self.L.ht_pose_depth_residual, poses, cams, depth, lo, hi, tol, far, com_poses, want_rendered)
+
+    def pose_mesh_residual(self, poses, cams, depth, lo, hi, tol=0, far=4.0, com_poses=False, want_rendered=False):
+        """pose_depth_residual against the hand's subdivision surface: the renderer is raster_mesh_depth at pixel offset 0 (ht_pose_mesh_residual)."""
+        return self._pose_residual(self.L.ht_pose_mesh_residual, poses, cams, depth, lo, hi, tol, far, com_poses, want_rendered)
+
+    def pose_mesh_residual_dev(self, d_poses, d_cams, d_depth, w, h, B, lo, hi, tol, d_info, d_rendered=None, far=4.0, com_poses=False, stream=None):
+        self._chk(self.L.ht_pose_mesh_residual_dev(self.h, d_poses, d_cams, d_depth, int(w), int(h), int(B), KP_COM_POSES if com_poses else 0, float(far), int(lo), int(hi), int(tol), d_info, d_rendered, stream))
+
+    def _pose_residual(self, entry, poses, cams, depth, lo, hi, tol, far, com_poses, want_rendered):
         depth = _c(depth, np.uint16); B, h, w = depth.shape
         poses = _c(poses, np.float32).reshape(B, self.nb, POSE); cams = _c(cams, np.float32).reshape(B, CAM)
         info = np.zeros((B, 8), np.int64); rendered = np.empty((B, h, w), np.uint16) if want_rendered else None
         u16p = C.POINTER(C.c_uint16)
-        self._chk(self.L.ht_pose_depth_residual(self.h, _f(poses), _f(cams), depth.ctypes.data_as(u16p), w, h, B, KP_COM_POSES if com_poses else 0, float(far), int(lo), int(hi), int(tol),
-                                                info.ctypes.data_as(C.POINTER(C.c_int64)), rendered.ctypes.data_as(u16p) if want_rendered else None))
+        self._chk(entry(self.h, _f(poses), _f(cams), depth.ctypes.data_as(u16p), w, h, B, KP_COM_POSES if com_poses else 0, float(far), int(lo), int(hi), int(tol),
+                        info.ctypes.data_as(C.POINTER(C.c_int64)), rendered.ctypes.data_as(u16p) if want_rendered else None))
         out = self.depth_figures(info, cams[:, 4])
         if want_rendered:
             out["rendered"] = rendered
@@ -1497,6 +1522,14 @@ class HostModel:
         depth = np.empty((int(h), int(w)), np.uint16); body = np.empty((int(h), int(w)), np.int8)
         if self.L.ht_model_render_mesh(self.m, _f(poses), _f(cam), int(w), int(h), float(far), float(pixel_offset), depth.ctypes.data_as(C.POINTER(C.c_uint16)), body.ctypes.data_as(C.POINTER(C.c_int8))):
             raise HTError("ht_model_render_mesh: bad argument")
+        return depth, body
+
+    def raster_mesh(self, poses, cam, w, h, far=4.0, pixel_offset=0.0):
+        """one frame of the rasteriser's definition (ht_model_raster_mesh): (depth u16[h,w], body int8[h,w])"""
+        poses = _c(poses, np.float32); cam = _c(cam, np.float32)
+        depth = np.empty((int(h), int(w)), np.uint16); body = np.empty((int(h), int(w)), np.int8)
+        if self.L.ht_model_raster_mesh(self.m, _f(poses), _f(cam), int(w), int(h), float(far), float(pixel_offset), depth.ctypes.data_as(C.POINTER(C.c_uint16)), body.ctypes.data_as(C.POINTER(C.c_int8))):
+            raise HTError("ht_model_raster_mesh: bad argument")
         return depth, body
 
 

@@ -668,6 +668,25 @@ struct HandTracker                                                              
 		return out;
 	}
 	Image<unsigned short> render_depth(const std::vector<Pose> &poses, const DCamera &cam, float far = 4.0f) const { return render_depth(std::vector<std::vector<Pose>>{ poses }, cam, far)[0]; }
+	// Addition, not a reference name: the hand's subdivision surface (GetMeshes(true), what the application draws with OpenGL, synthetic-tracker.cpp:164-182) through the
+	// device's z-buffer rasteriser (ht_raster_mesh_depth), shaped like render_depth.  pixel_offset 0 / far 4 gives frames interchangeable with render_depth's, 0.5 / 0.85
+	// the application's GL convention
+	std::vector<Image<unsigned short>> render_mesh_raster(const std::vector<std::vector<Pose>> &poses, const DCamera &cam, float far = 4.0f, float pixel_offset = 0.0f) const
+	{
+		const int B = (int)poses.size(), w = cam.dim().x, h = cam.dim().y;
+		std::vector<float> p7; p7.reserve((size_t)B * nb_ * HT_POSE);
+		for (auto &fr : poses) { if ((int)fr.size() != nb_) throw std::runtime_error("render_mesh_raster: one pose per body"); const std::vector<float> f = flat(fr); p7.insert(p7.end(), f.begin(), f.end()); }
+		const float c[HT_CAM] = { cam.focal().x, cam.focal().y, cam.principal().x, cam.principal().y, cam.depth_scale, cam.pose.position.x, cam.pose.position.y, cam.pose.position.z,
+		                          cam.pose.orientation.x, cam.pose.orientation.y, cam.pose.orientation.z, cam.pose.orientation.w };
+		std::vector<float> cams; for (int b = 0; b < B; b++) cams.insert(cams.end(), c, c + HT_CAM);
+		std::vector<unsigned short> d((size_t)B * w * h);
+		check(ctx_, ht_raster_mesh_depth(ctx_, p7.data(), cams.data(), w, h, far, pixel_offset, B, d.data(), nullptr));
+		std::vector<Image<unsigned short>> out;
+		for (int b = 0; b < B; b++) out.emplace_back(cam, std::vector<unsigned short>(d.begin() + (size_t)b * w * h, d.begin() + (size_t)(b + 1) * w * h));
+		return out;
+	}
+	Image<unsigned short> render_mesh_raster(const std::vector<Pose> &poses, const DCamera &cam, float far = 4.0f, float pixel_offset = 0.0f) const
+	{ return render_mesh_raster(std::vector<std::vector<Pose>>{ poses }, cam, far, pixel_offset)[0]; }
 	// Additions, not reference names (ht_mi355x.h "tracking accuracy").  keypoints: where the hand of the latest update is in `image` -- the points of a built-in table in
 	// the poses' frame, in pixels of image.cam, and their visibility against the frame (0 visible, 1 occluded, 2 nothing there, 3 outside the image, 4 behind the camera;
 	// the tolerances in metres).  What the reference's overlay computes per point (handtrack.h:632-634).  With left_hand set the points are the left hand's.

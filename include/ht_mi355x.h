@@ -404,6 +404,24 @@ int ht_model_hitcheck(const ht_model *m, const float *poses, const float *v0, co
 int ht_model_hitcheck_mesh(const ht_model *m, const float *poses, const float *v0, const float *v1, float *impact3, float *normal3, int *body, int *tri);
 int ht_model_render_mesh(const ht_model *m, const float *poses, const float *cam12, int w, int h, float far, float pixel_offset, uint16_t *depth, int8_t *body);
 int ht_model_scale(ht_model *m, float s);
+/* The same meshes through a forward z-buffer rasteriser (an addition; what the application's GL path does, synthetic-tracker.cpp:164-182, stated in software with a
+ * definition of its own, not the ray cast's: work grows with triangles plus covered pixels, not with pixels times triangles).
+ * ht_model_raster_mesh    one w x h frame.  For body b at centre-of-mass pose (pos, q), R = qmat(q), up = pos - R com_b, every triangle (v0, v1, v2) of sdmeshes[b] in
+ *                    stored order, all in float with one rounding per operation:
+ *                      corners   w_i = up + R v_i; the triangle is dropped if any w_i.z < HT_RASTER_NEAR or any coordinate is not finite
+ *                      screen    sx_i = (fx (w_i.x / w_i.z) + px) - pixel_offset, sy_i likewise, so pixel (x, y)'s sample is the integer point (x, y); dropped if any
+ *                                |sx_i| or |sy_i| >= 2^20 or is not finite; X_i = rint(256 sx_i), Y_i = rint(256 sy_i), round-half-even, as integers
+ *                      facing    A2 = (X1-X0)(Y2-Y0) - (X2-X0)(Y1-Y0) in exact integers; kept iff A2 < 0 (with y downwards the side PolyHitCheck's d0 > 0 keeps)
+ *                      coverage  pixel (x, y) is inside iff (X_j-X_i)(256y-Y_i) - (Y_j-Y_i)(256x-X_i) <= 0 for the edges i -> j = 0->1, 1->2, 2->0, in exact integers:
+ *                                edges are inclusive on both sides, shared corners are bit-equal in sdmeshes, so a closed body has no cracks
+ *                      depth     N = cross(w1-w0, w2-w0), k = dot(N, w0); rx = ((x + pixel_offset) - px) / fx, ry likewise; den = (N.x rx + N.y ry) + N.z,
+ *                                z = k / den, c = z / depth_scale; a candidate iff c is finite, HT_RASTER_NEAR <= z < far and 0 <= c < 65536; its count is (uint16)c
+ *                      winner    the smallest count, the first in (body, triangle) order on equal counts; body = that body.  No candidate: (uint16)(far /
+ *                                depth_scale) and body -1, as in the ray cast, so frames of pixel_offset 0 and far 4 are interchangeable with ht_render_depth's.
+ *                    No perspective clipping: a triangle that crosses the near distance is dropped.  Arguments as ht_model_render_mesh.  Against the ray cast evaluated
+ *                    in double, on the same pixels: counts differ by at most 1 where both pick the same triangle (DESIGN section 35 has the measured shares). */
+#define HT_RASTER_NEAR 0.01f   /* metres */
+int ht_model_raster_mesh(const ht_model *m, const float *poses, const float *cam12, int w, int h, float far, float pixel_offset, uint16_t *depth, int8_t *body);
 
 /* ---- segmentation: the step before the tracker for full-size frames --------------------------------------------------
  * ht_segment_vr       replaces  Image<unsigned short> HandSegmentVR(const Image<unsigned short> &depth, int entry_options = 0xF,
@@ -452,6 +470,13 @@ int ht_render_depth_dev(ht_ctx *ctx, const float *d_poses, const float *d_cams, 
  * ht_render_mesh_depth_dev the same on device buffers, asynchronous on `stream`. */
 int ht_render_mesh_depth(ht_ctx *ctx, const float *poses, const float *cams, int w, int h, float far, float pixel_offset, int B, uint16_t *depth, int8_t *body);
 int ht_render_mesh_depth_dev(ht_ctx *ctx, const float *d_poses, const float *d_cams, int w, int h, float far, float pixel_offset, int B, uint16_t *d_depth, int8_t *d_body, void *stream);
+/* ht_raster_mesh_depth     the same meshes rasterised: ht_model_raster_mesh (above, where the definition is) for B frames, bit-identical to it for depth and body,
+ *                     with the context's model as ht_create built it and ht_scale left it.  Shapes, argument rules and return codes are ht_render_mesh_depth's;
+ *                     also HT_ERR_STATE for a model of 65535 or more mesh triangles (the z-buffer keeps a 16-bit triangle index; the stock hands have 6016 and
+ *                     8896).  Deterministic: the z-buffer is filled with atomic minima of (count, triangle), so the order of arrival does not matter.
+ * ht_raster_mesh_depth_dev the same on device buffers, asynchronous on `stream`. */
+int ht_raster_mesh_depth(ht_ctx *ctx, const float *poses, const float *cams, int w, int h, float far, float pixel_offset, int B, uint16_t *depth, int8_t *body);
+int ht_raster_mesh_depth_dev(ht_ctx *ctx, const float *d_poses, const float *d_cams, int w, int h, float far, float pixel_offset, int B, uint16_t *d_depth, int8_t *d_body, void *stream);
 
 /* ---- joint coordinates (an addition: the reference decomposes every joint on every solver pass and never hands the result out) ----
  * Joint j of the model (parent body rbi0 at orientation q0, child rbi1 at q1, jointframe F, anchors p0 / p1) has the coordinates c = (s.x, s.y, t.z) of
@@ -758,8 +783,9 @@ int ht_update_two_hands_model_dev(ht_ctx *ctx, int side, const uint16_t *d_depth
  *                     q' = qmul(conj(qc), q) -- ht_render_depth renders them at `far` into a buffer of the context (grown to the largest call by one synchronising
  *                     re-allocation before anything is enqueued), and ht_depth_compare runs with a = depth (observed) and b = rendered.  rendered [B][h][w] is
  *                     an optional output.  Choose hi <= far / depth_scale to keep the rendered background out (not checked: depth_scale is per frame).
- *                     HT_ERR_STATE for a context without a hand model.  No left-hand form (mirror first), no mesh-renderer form (ht_render_mesh_depth, then
- *                     ht_depth_compare).
+ *                     HT_ERR_STATE for a context without a hand model.  No left-hand form (mirror first).
+ * ht_pose_mesh_residual   the same against the hand's subdivision surface: arguments, pose preparation and comparison are ht_pose_depth_residual's, the renderer is
+ *                     ht_raster_mesh_depth at pixel offset 0.  Also HT_ERR_STATE where that call gives it (a model file without meshes).
  * The host forms refuse output buffers that overlap an input (HT_ERR_ARG); the *_dev forms take device buffers (hands included) and are asynchronous on `stream`. */
 #define HT_KP_COM_POSES 1
 #define HT_KP_FEATURE8 0
@@ -776,6 +802,8 @@ int ht_depth_compare(ht_ctx *ctx, const uint16_t *a, const uint16_t *b, int w, i
 int ht_depth_compare_dev(ht_ctx *ctx, const uint16_t *d_a, const uint16_t *d_b, int w, int h, int B, int lo, int hi, int tol, int64_t *d_info, void *stream);
 int ht_pose_depth_residual(ht_ctx *ctx, const float *poses, const float *cams, const uint16_t *depth, int w, int h, int B, int flags, float far, int lo, int hi, int tol, int64_t *info, uint16_t *rendered);
 int ht_pose_depth_residual_dev(ht_ctx *ctx, const float *d_poses, const float *d_cams, const uint16_t *d_depth, int w, int h, int B, int flags, float far, int lo, int hi, int tol, int64_t *d_info, uint16_t *d_rendered, void *stream);
+int ht_pose_mesh_residual(ht_ctx *ctx, const float *poses, const float *cams, const uint16_t *depth, int w, int h, int B, int flags, float far, int lo, int hi, int tol, int64_t *info, uint16_t *rendered);
+int ht_pose_mesh_residual_dev(ht_ctx *ctx, const float *d_poses, const float *d_cams, const uint16_t *d_depth, int w, int h, int B, int flags, float far, int lo, int hi, int tol, int64_t *d_info, uint16_t *d_rendered, void *stream);
 
 /* ---- keypoint fit (an addition: the reference nails one dragged bone and pulls its own eight landmarks onto rays, one frame at a time) -----------------------
  * From keypoint targets to a pose: the inverse of ht_keypoints.  The slots' current state of model which_model (0 handmodel, 1 othermodel) is the start pose; every

@@ -2,6 +2,8 @@
 render -> ht_update_frames_dev at 1024 frames with a new batch of poses every step.  Writes profiles/r07_render.json (or --out).
 
     python tools/bench_render.py [--steps 20] [--warmup 3] [--out profiles/r07_render.json] [--quick]
+    python tools/bench_render.py --mesh      the mesh ray cast beside the hulls (profiles/r08_render_mesh.json)
+    python tools/bench_render.py --raster    the mesh rasteriser beside the ray cast, the hulls and the tracking step (profiles/r26_raster_mesh.json)
 
 Hands: the bench recording's ground truths (bench_data/frames1024.npz, 17 bones) and the 26-bone start poses of bench_data/frames5_256.npz, seen
 through the application's 320x240 camera (focal 305) or a 128x128 one (focal 163).  Empty frames: the same hands moved 10 m behind the camera."""
@@ -19,7 +21,7 @@ from hand_tracking_samples_amd import build as hb, native, weights as W  # noqa:
 
 M17 = os.path.join(ROOT, "hand_tracking_samples_amd", "assets", "model_hand17.htfx")
 M26 = os.path.join(ROOT, "hand_tracking_samples_amd", "assets", "model_hand26.htfx")
-CAMS = {(320, 240): [305, 305, 160, 120], (128, 128): [163, 163, 64, 64]}
+CAMS = {(320, 240): [305, 305, 160, 120], (128, 128): [163, 163, 64, 64], (640, 480): [610, 610, 320, 240]}
 
 
 def cam_of(w, h, B):
@@ -109,12 +111,68 @@ def main_mesh(a):
         f.write("\n")
 
 
+def main_raster(a):
+    """--raster: ht_raster_mesh_depth_dev beside ht_render_mesh_depth_dev and ht_render_depth_dev on the same poses in the same run, the none-in-view floor of each,
+    and the same batch's tracking step (17 bones, 1024 frames of 320x240)"""
+    dev = torch.device("cuda:0")
+    torch.cuda.set_device(dev)
+    s = torch.cuda.Stream(device=dev)
+    z = np.load(os.path.join(ROOT, "bench_data", "frames1024.npz"))
+    z5 = np.load(os.path.join(ROOT, "bench_data", "frames5_256.npz"))
+    hands = {17: z["gtpose"], 26: z5["startpose"]}
+    res = {"device": torch.cuda.get_device_name(dev), "steps": a.steps, "warmup": a.warmup, "render": [], "usage": {}}
+    for k, v in hb.resource_usage().items():
+        if "render" in k or "raster" in k:
+            res["usage"][k] = {x: v.get(x) for x in ("VGPRs", "SGPRs", "AGPRs", "ScratchSize", "LDS Size", "Occupancy")}
+    cases = ((320, 240, 1024),) if a.quick else ((320, 240, 1024), (320, 240, 8192), (640, 480, 1024))
+    few = max(3, a.steps // 4)      # the ray cast and the tracking step take tens of milliseconds a call
+    for nb, model in ((17, M17), (26, M26)):
+        ctx = native.Context(model, 1024 if nb == 17 else 1)
+        try:
+            if nb == 17:
+                ctx.load_weights(W.make_cnnb()); ctx.set_params(microforce=3.0, mainthreadpasses=3); ctx.reserve_points(320 * 240 // 4)
+            for w, h, B in cases:
+                p = hands[nb][np.arange(B) % len(hands[nb])].copy()
+                away = p.copy(); away[:, :, 2] -= 10.0
+                tp = torch.from_numpy(p).to(dev); ta = torch.from_numpy(away).to(dev); tc = torch.from_numpy(cam_of(w, h, B)).to(dev)
+                td = torch.empty((B, h, w), dtype=torch.int16, device=dev)
+                row = {"bones": nb, "w": w, "h": h, "B": B}
+                for name, off, far in (("raster_off0_far4", 0.0, 4.0), ("raster_off05_far085", 0.5, 0.85)):
+                    row[name + "_ms"] = round(time_it(lambda: ctx.raster_mesh_depth_dev(tp.data_ptr(), tc.data_ptr(), w, h, far, off, B, td.data_ptr(), None, s.cuda_stream), s, a.steps, a.warmup), 4)
+                    row[name + "_hand_pixel_fraction"] = round(float((td[:64].cpu().numpy().view(np.uint16) < int(far * 1000) - 1).mean()), 4)
+                row["raster_frames_per_s"] = round(B / row["raster_off0_far4_ms"] * 1e3, 1)
+                row["raster_empty_ms"] = round(time_it(lambda: ctx.raster_mesh_depth_dev(ta.data_ptr(), tc.data_ptr(), w, h, 4.0, 0.0, B, td.data_ptr(), None, s.cuda_stream), s, a.steps, a.warmup), 4)
+                row["mesh_ms"] = round(time_it(lambda: ctx.render_mesh_depth_dev(tp.data_ptr(), tc.data_ptr(), w, h, 4.0, 0.0, B, td.data_ptr(), None, s.cuda_stream), s, few, 1), 4)
+                row["mesh_empty_ms"] = round(time_it(lambda: ctx.render_mesh_depth_dev(ta.data_ptr(), tc.data_ptr(), w, h, 4.0, 0.0, B, td.data_ptr(), None, s.cuda_stream), s, few, 1), 4)
+                row["hull_empty_ms"] = round(time_it(lambda: ctx.render_depth_dev(ta.data_ptr(), tc.data_ptr(), w, h, 4.0, B, td.data_ptr(), None, s.cuda_stream), s, a.steps, a.warmup), 4)
+                row["hull_ms"] = round(time_it(lambda: ctx.render_depth_dev(tp.data_ptr(), tc.data_ptr(), w, h, 4.0, B, td.data_ptr(), None, s.cuda_stream), s, a.steps, a.warmup), 4)
+                if nb == 17 and B == 1024 and (w, h) == (320, 240):      # the tracking step these frames feed (hull frames, as section 17 measured it)
+                    ts = torch.from_numpy(z["startpose"]).to(dev); out = torch.empty((B, 17, 7), dtype=torch.float32, device=dev)
+                    ctx.update_frames_dev(td.data_ptr(), tc.data_ptr(), w, h, 0.17, ts.data_ptr(), B, out.data_ptr(), s.cuda_stream)
+                    s.synchronize()
+                    row["update_frames_dev_ms"] = round(time_it(lambda: ctx.update_frames_dev(td.data_ptr(), tc.data_ptr(), w, h, 0.17, None, B, out.data_ptr(), s.cuda_stream), s, few, 1), 3)
+                    row["raster_over_update"] = round(row["raster_off0_far4_ms"] / row["update_frames_dev_ms"], 4)
+                row["raster_over_mesh"] = round(row["raster_off0_far4_ms"] / row["mesh_ms"], 4)
+                row["raster_over_hull"] = round(row["raster_off0_far4_ms"] / row["hull_ms"], 3)
+                print(json.dumps(row), flush=True)
+                res["render"].append(row)
+                del tp, ta, tc, td
+        finally:
+            ctx.close()
+    out_path = a.out if a.out != DEFAULT_OUT else os.path.join(ROOT, "profiles", "r26_raster_mesh.json")
+    os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
+    with open(out_path, "w") as f:
+        json.dump(res, f, indent=1)
+        f.write("\n")
+
+
 DEFAULT_OUT = os.path.join(ROOT, "profiles", "r07_render.json")
 
 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--mesh", action="store_true", help="measure ht_render_mesh_depth_dev (the subdivision surface) beside the hull renderer and the tracking step")
+    ap.add_argument("--raster", action="store_true", help="measure ht_raster_mesh_depth_dev (the z-buffer rasteriser) beside the mesh ray cast, the hull renderer and the tracking step")
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--out", default=DEFAULT_OUT)
@@ -123,6 +181,8 @@ def main():
     a = ap.parse_args()
     if a.mesh:
         return main_mesh(a)
+    if a.raster:
+        return main_raster(a)
     dev = torch.device("cuda:0")
     torch.cuda.set_device(dev)
     s = torch.cuda.Stream(device=dev)

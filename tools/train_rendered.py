@@ -288,13 +288,20 @@ def main():
     ap.add_argument("--rate-steps", type=int, default=2048)
     ap.add_argument("--frame", default=None, type=lambda v: tuple(int(x) for x in v.lower().split("x")), help="with --side 128: render full-size frames of this size (640x480) and segment them to the 128x128 tile")
     ap.add_argument("--mesh", action="store_true", help="render the training frames from the subdivision surface (ht_render_mesh_depth_dev, pixel offset 0, far 4) instead of the hulls")
+    ap.add_argument("--mesh-raster", action="store_true", help="render the training frames from the subdivision surface with the z-buffer rasteriser (ht_raster_mesh_depth_dev, pixel offset 0, far 4); "
+                                                                "the JSON then also holds the closed loop's samples/s with the mesh ray cast and with the hulls, measured in the same run")
     ap.add_argument("--sampled", action="store_true", help="draw the hands with ht_sample_poses_dev (HT_SAMPLE_ENHANCED, seed --seed) inside the model's joint limits; only the wrists come from the "
                                                             "interpolated ground truths.  64x64 net only")
     ap.add_argument("--spread", type=float, default=0.98, help="with --sampled: the share of every joint range the sampler uses")
     ap.add_argument("--sensor-noise", default=None, choices=("ivy", "ds4"), help="64x64 net: train one net on clean and one on simulated raw frames of this camera (ht_sensor_simulate_dev, "
                                                                                  "ht_sensor_filter_dev) and report both on held-out simulated frames (see the module's text).  Off by default")
     a = ap.parse_args()
-    if a.sensor_noise and (a.side != 64 or a.sampled or a.mesh):
+    if a.mesh and a.mesh_raster:
+        ap.error("--mesh and --mesh-raster name two renderers of the same surface: choose one")
+    if a.mesh_raster and a.side != 64:
+        ap.error("--mesh-raster trains the 64x64-input net")
+    a.renderer = "raster" if a.mesh_raster else "mesh" if a.mesh else "hull"
+    if a.sensor_noise and (a.side != 64 or a.sampled or a.mesh or a.mesh_raster):
         ap.error("--sensor-noise trains the 64x64-input net on hull renderings of the interpolated poses")
     if a.sampled and a.side != 64:
         ap.error("--sampled trains the 64x64-input net")
@@ -339,7 +346,7 @@ def main():
     nsampled = [0]      # samples drawn so far: the next round's first_index
     troots = torch.empty((B, 7), device=dev)
 
-    def round_(poses, order, timed=False):
+    def round_(poses, order, timed=False, renderer=a.renderer):
         with torch.cuda.stream(s):
             if a.sampled:      # `poses` gives the wrists only; the hands are drawn on the device, inside the model's joint limits
                 troots.copy_(torch.from_numpy(np.ascontiguousarray(poses[:, 0])))
@@ -348,7 +355,9 @@ def main():
             else:
                 tp.copy_(torch.from_numpy(poses))      # in the stream's order: the previous round may still read the poses
             if timed: ev[0].record(s)
-            if a.mesh:
+            if renderer == "raster":
+                ctx.raster_mesh_depth_dev(tp.data_ptr(), cams.data_ptr(), 320, 240, 4.0, 0.0, B, depth.data_ptr(), None, s.cuda_stream)
+            elif renderer == "mesh":
                 ctx.render_mesh_depth_dev(tp.data_ptr(), cams.data_ptr(), 320, 240, 4.0, 0.0, B, depth.data_ptr(), None, s.cuda_stream)
             else:
                 ctx.render_depth_dev(tp.data_ptr(), cams.data_ptr(), 320, 240, 4.0, B, depth.data_ptr(), None, s.cuda_stream)
@@ -386,15 +395,19 @@ def main():
     round_(poses, order); s.synchronize()
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     nloop = 4
-    with torch.cuda.stream(s):
-        e0.record(s)
-    for _ in range(nloop):
-        round_(poses, order)
-    with torch.cuda.stream(s):
-        e1.record(s)
-    s.synchronize()
-    loop_sps = nloop * B / (e0.elapsed_time(e1) / 1e3)
-    nbare = a.rate_steps // a.minibatch * a.minibatch
+    by_renderer = {}
+    for renderer in ((a.renderer, "mesh", "hull") if a.mesh_raster else (a.renderer,)):      # --mesh-raster: the same loop on the other two renderers' frames, in the same run
+        round_(poses, order, renderer=renderer); s.synchronize()
+        with torch.cuda.stream(s):
+            e0.record(s)
+        for _ in range(nloop):
+            round_(poses, order, renderer=renderer)
+        with torch.cuda.stream(s):
+            e1.record(s)
+        s.synchronize()
+        by_renderer[renderer] = nloop * B / (e0.elapsed_time(e1) / 1e3)
+    loop_sps = by_renderer[a.renderer]
+    nbare =a.rate_steps // a.minibatch * a.minibatch
     bare_order = rng.integers(B, size=nbare).astype(np.int32)
     with torch.cuda.stream(s):
         e0.record(s)
@@ -436,7 +449,7 @@ def main():
            "pose_source": "sampled" if a.sampled else "interpolated",
            "rounds": a.rounds, "batch": B, "minibatch": a.minibatch, "lr": a.lr, "optimizer": None if a.opt is None else {k: getattr(a.opt, k) for k, _ in a.opt._fields_}, "accum": a.accum, "samples": a.rounds * B, "seconds": seconds,
            "stage_ms_per_round": {"render": stage_ms[0], "segment": stage_ms[1], "cnn_input": stage_ms[2], "labels": stage_ms[3], "train": stage_ms[4]},
-           "kernels": kern, "closed_loop_samples_per_s": loop_sps, "bare_train_steps_per_s": bare_sps,      # samples/s of the training call alone on the resident pool "loop_over_bare": loop_sps / bare_sps,
+           "kernels": kern, "renderer": a.renderer, "closed_loop_samples_per_s": loop_sps, "closed_loop_samples_per_s_by_renderer": by_renderer, "bare_train_steps_per_s": bare_sps,      # samples/s of the training call alone on the resident pool "loop_over_bare": loop_sps / bare_sps,
            "held_out": {"frames": 64, "mse_before": mse0, "mse_after": mse1, "cnn_pose_frames_before": acc0, "cnn_pose_frames_after": acc1,
                         "train_synthetic_reference": "50 of 64 after 300 epochs of the 960 fixed tiles"},
            "curve": curve}
