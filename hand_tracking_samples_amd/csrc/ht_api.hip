@@ -24,17 +24,9 @@ static void default_params(ht_params &p)     // handtrack.h:523-547, physics.h:4
 	p.physics_iterations = 16; p.physics_iterations_post = 4; p.physics_use_collision = 1; p.physics_weak_force = 0.4f; p.bone_sum_error_scale = 4.0f; p.unibody_force = 0.1f;
 }
 
-template <class T> static int dev_upload(ht_ctx *ctx, T **p, const std::vector<T> &h)
-{
-	int r = dev_alloc(ctx, p, h.size() ? h.size() : 1);
-	if (r) return r;
-	if (h.size()) HIPCHK(ctx, hipMemcpy(*p, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice));
-	return HT_OK;
-}
-
 // The contact kernel's image of the collision vertices: every body padded to whole rows of 16 with copies of its vertex 0 (index 0), built from
-// the host copy (again after ht_scale).
-static int upload_padded_verts(ht_ctx *ctx)
+// the model's vertices as the device takes them (again after ht_scale).
+static int upload_padded_verts(ht_ctx *ctx, const std::vector<float4> &verts)
 {
 	ht_model_dev &m = ctx->model;
 	std::vector<float4> pv;
@@ -42,7 +34,7 @@ static int upload_padded_verts(ht_ctx *ctx)
 	{
 		m.cvert_off[b] = (int)pv.size();
 		const int n = m.vert_off[b + 1] - m.vert_off[b], np = (n + 15) & ~15;
-		for (int k = 0; k < np; k++) { const int src = k < n ? k : 0; float4 q = ctx->h_verts[(size_t)m.vert_off[b] + src]; memcpy(&q.w, &src, 4); pv.push_back(q); }
+		for (int k = 0; k < np; k++) { const int src = k < n ? k : 0; float4 q = verts[(size_t)m.vert_off[b] + src]; memcpy(&q.w, &src, 4); pv.push_back(q); }
 	}
 	m.cvert_off[m.nb] = (int)pv.size();
 	if (!ctx->d_cverts_rw) { int r = dev_alloc(ctx, &ctx->d_cverts_rw, pv.size() ? pv.size() : 1); if (r) return r; }
@@ -50,28 +42,52 @@ static int upload_padded_verts(ht_ctx *ctx)
 	m.cverts = ctx->d_cverts_rw;
 	return HT_OK;
 }
+// a model array on the device: allocated by the first call (load_model), written again by the later ones (ht_scale; the sizes do not change)
+template <class T> static int dev_put(ht_ctx *ctx, T **p, const T *h, size_t n)
+{
+	if (!*p) { const int r = dev_alloc(ctx, p, n ? n : 1); if (r) return r; }
+	if (n) HIPCHK(ctx, hipMemcpy(*p, h, n * sizeof(T), hipMemcpyHostToDevice));
+	return HT_OK;
+}
+// The record laid out for the device, at load and again after ht_scale: vertices as float4 with the index within the body in w (bit pattern, used by the support
+// scans), the padded collision vertices, the mesh rows and radii, planes, body and joint tables.  It waits for the context's stream first and, before the mesh rows
+// go, for a render of the old meshes on the caller's stream.
+static int model_to_device(ht_ctx *ctx)
+{
+	const ht_model_rec &rec = ctx->rec;
+	ht_model_dev &m = ctx->model;
+	std::vector<float4> verts(rec.verts.size() / 3);
+	for (int b = 0; b < m.nb; b++) for (int i = m.vert_off[b], k = 0; i < m.vert_off[b + 1]; i++, k++)
+	{ verts[i] = make_float4(rec.verts[3 * (size_t)i], rec.verts[3 * (size_t)i + 1], rec.verts[3 * (size_t)i + 2], 0.0f); memcpy(&verts[i].w, &k, 4); }
+	int r;
+	HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+	if ((r = dev_put(ctx, &ctx->d_verts_rw, verts.data(), verts.size())) || (r = upload_padded_verts(ctx, verts))) return r;
+	if (ctx->last_user_stream && ctx->last_user_stream != ctx->stream) HIPCHK(ctx, hipStreamSynchronize(ctx->last_user_stream));
+	if ((r = ht_mesh_upload(ctx))) return r;
+	if ((r = dev_put(ctx, &ctx->d_planes_rw, (const float4 *)rec.planes.data(), rec.planes.size() / 4)) || (r = dev_put(ctx, &ctx->d_bodyc_rw, rec.bodyc.data(), rec.bodyc.size())) ||
+	    (r = dev_put(ctx, &ctx->d_jointc_rw, rec.jointc.data(), rec.jointc.size()))) return r;
+	m.verts = ctx->d_verts_rw; m.planes = ctx->d_planes_rw; m.bodyc = ctx->d_bodyc_rw; m.jointc = ctx->d_jointc_rw;
+	return HT_OK;
+}
 
 static int load_model(ht_ctx *ctx, const char *path)
 {
-	// `path` is either the reference's model JSON (built here, a33) or a model baked earlier with ht_model_bake
-	fx_map fx;
-	char magic[8] = { 0 };
-	{ FILE *fp = fopen(path, "rb"); if (!fp) { ctx->err = std::string("cannot open model ") + path; return HT_ERR_IO; } size_t n = fread(magic, 1, 8, fp); (void)n; fclose(fp); }
-	if (!memcmp(magic, "HTFX0001", 8)) { if (!fx_load(path, fx)) { ctx->err = std::string("cannot read baked model ") + path; return HT_ERR_IO; } }
-	else if (!ht_build_model(path, HT_BUILD_HAND_TWEAKS, fx, ctx->err)) return HT_ERR_IO;
-	auto need = [&](const char *n) -> const fx_arr * { auto it = fx.find(n); if (it == fx.end()) { ctx->err = std::string("model entry missing: ") + n; return nullptr; } return &it->second; };
-	const fx_arr *a;
-	if (!(a = need("nb"))) return HT_ERR_IO; int nb = a->i()[0];
-	if (!(a = need("nj"))) return HT_ERR_IO; int nj = a->i()[0];
+	ht_model_rec &rec = ctx->rec;
+	if (!ht_model_read(path, HT_BUILD_HAND_TWEAKS, rec, ctx->err)) return HT_ERR_IO;
+	auto lacks = [&](const char *n) { if (!rec.lacks(n)) return false; ctx->err = std::string("model entry missing: ") + n; return true; };
+	if (lacks("nb") || lacks("nj")) return HT_ERR_IO;
+	const int nb = rec.nb, nj = rec.nj;
 	// body slot HT_MAXNB-1 is the solver's idle body; 26 joints: the most whose angular rows a solve can always keep (13 CNN-driven + 6 range rows + slowfit's 3 relative
 	// rows per joint = 247 of 252: csrc/ht_solver.hip), so that no model this accepts can run into that capacity
 	if (nb < 1 || nb >= HT_MAXNB || nj > 26) { ctx->err = "model too large (at most 31 bodies and 26 joints)"; return HT_ERR_IO; }
+	// a context needs the physics constants, collision lists and unibody proxy and can do without the hull triangles; of several absent entries the last one is named
+	bool absent = false;
+	for (const char *n : { "body_f", "body_collide", "ignore", "joint_i", "joint_f", "physics", "unibody/verts", "unibody/f" }) absent = lacks(n) || absent;
+	for (const std::string &n : rec.missing) if (!absent && (n.size() < 5 || n.compare(n.size() - 5, 5, "/tris"))) absent = lacks(n.c_str());
+	if (absent) return HT_ERR_IO;
 	ht_model_dev &m = ctx->model;
-	memset(&m, 0, sizeof m);
-	m.nb = nb; m.nj = nj;
-	const fx_arr *bf = need("body_f"), *bc = need("body_collide"), *ig = need("ignore"), *ji = need("joint_i"), *jf = need("joint_f"), *ph = need("physics"), *ubv = need("unibody/verts"), *ubf = need("unibody/f");
-	if (!bf || !bc || !ig || !ji || !jf || !ph || !ubv || !ubf) return HT_ERR_IO;
-	const float *P = ph->f();
+	memset(&m, 0, sizeof m); m.nb = nb; m.nj = nj;
+	const float *P = rec.physics.data();
 	ht_physics_dev &phys = ctx->phys;
 	phys.deltaT = P[0]; phys.restitution = P[1]; phys.gravity_len = sqrtf((P[2] * P[2] + P[3] * P[3]) + P[4] * P[4]); phys.coloumb = P[5]; phys.biasfactorjoint = P[6]; phys.biasfactorpositive = P[7];
 	phys.falltime_to_ballistic = P[9]; phys.driftmax = P[10];
@@ -79,86 +95,41 @@ static int load_model(ht_ctx *ctx, const char *path)
 	phys.cos40 = (float)phys.cos40d;
 	phys.jiggle_sin = sinf(3.14f / 180.0f * (4.0f) / 2.0f);    // gjk.h:626-628
 	const float physics_damping = P[11];
-	std::vector<float4> verts, planes; std::vector<float> bodyc((size_t)nb * HT_BC, 0.0f), jointc((size_t)nj * HT_JC, 0.0f);
-	ctx->h_bodyc.clear();
 	for (int b = 0; b < nb; b++)
 	{
-		char nm[64];
-		snprintf(nm, sizeof nm, "b%d/verts", b); const fx_arr *v = need(nm); if (!v) return HT_ERR_IO;
-		snprintf(nm, sizeof nm, "b%d/planes", b); const fx_arr *pl = need(nm); if (!pl) return HT_ERR_IO;
-		m.vert_off[b] = (int)verts.size(); m.plane_off[b] = (int)planes.size();
-		float diam2 = 0.0f;
-		for (uint32_t i = 0; i < v->dims[0]; i++) { float4 q = make_float4(v->f()[3 * i], v->f()[3 * i + 1], v->f()[3 * i + 2], 0.0f); memcpy(&q.w, &i, 4); verts.push_back(q); }      // w = index within the body (bit pattern), used by the support scans
-		for (uint32_t i = 0; i < v->dims[0]; i++) for (uint32_t j = i + 1; j < v->dims[0]; j++)
-		{
-			float dx = v->f()[3 * i] - v->f()[3 * j], dy = v->f()[3 * i + 1] - v->f()[3 * j + 1], dz = v->f()[3 * i + 2] - v->f()[3 * j + 2];
-			float d2 = dx * dx + dy * dy + dz * dz; if (d2 > diam2) diam2 = d2;
-		}
-		for (uint32_t i = 0; i < pl->dims[0]; i++) planes.push_back(make_float4(pl->f()[4 * i], pl->f()[4 * i + 1], pl->f()[4 * i + 2], pl->f()[4 * i + 3]));
-		const float *r = bf->f() + 26 * b;     // mass massinv radius radius_inner damping friction gravscale com3 pos_start3 quat_start4 tensorinv9
-		float *c = &bodyc[(size_t)b * HT_BC];
-		c[HT_BC_MASS] = r[0]; c[HT_BC_MASSINV] = r[1]; c[HT_BC_RADIUS] = r[2]; c[HT_BC_RINNER] = r[3];
-		c[HT_BC_DAMPLEFT] = powf((1.0f - (r[4] < physics_damping ? physics_damping : r[4])), phys.deltaT);      // physics.h:506
-		c[HT_BC_FRICTION] = r[5]; c[HT_BC_DIAM] = sqrtf(diam2);
-		for (int i = 0; i < 3; i++) c[HT_BC_COM + i] = r[7 + i];
-		for (int i = 0; i < 3; i++) c[HT_BC_POS0 + i] = r[10 + i];
-		for (int i = 0; i < 4; i++) c[HT_BC_Q0 + i] = r[13 + i];
-		for (int i = 0; i < 9; i++) c[HT_BC_TINV + i] = r[17 + i];
-		m.collide[b] = bc->i()[b];
-		unsigned mask = 0; for (int j = 0; j < nb; j++) if (ig->i()[b * nb + j]) mask |= 1u << j;
+		m.vert_off[b] = rec.vert_off[b]; m.plane_off[b] = rec.plane_off[b];
+		rec.bodyc[(size_t)b * HT_BC + HT_BC_DAMPLEFT] = powf((1.0f - (rec.damping[b] < physics_damping ? physics_damping : rec.damping[b])), phys.deltaT);      // physics.h:506
+		m.collide[b] = rec.collide[b];
+		unsigned mask = 0; for (int j = 0; j < nb; j++) if (rec.ignore[b * nb + j]) mask |= 1u << j;
 		m.ignore[b] = mask;
 	}
-	m.vert_off[nb] = (int)verts.size(); m.plane_off[nb] = (int)planes.size();
-	// the subdivision meshes (GetMeshes(true)), for ht_render_mesh_depth; a baked model from before they were stored has none, and that call then refuses
-	ctx->h_mesh_corners.clear(); ctx->mesh_off.assign((size_t)nb + 1, 0);
-	for (int b = 0; b < nb; b++)
-	{
-		auto it = fx.find("b" + std::to_string(b) + "/sdverts");
-		if (it != fx.end()) { const size_t nt = it->second.dims[0] / 3; ctx->h_mesh_corners.insert(ctx->h_mesh_corners.end(), it->second.f(), it->second.f() + nt * 9); }
-		ctx->mesh_off[(size_t)b + 1] = (int)(ctx->h_mesh_corners.size() / 9);
-	}
+	m.vert_off[nb] = rec.vert_off[nb]; m.plane_off[nb] = rec.plane_off[nb];
 	// HandModelEnhancements' one-time rewrite (handtrack.h:408-416): a model whose bone 2 (the thumb base) ignores fewer than 10 bodies gets that
 	// bone out of every collision pair.  The reference does it on the first call, which precedes every solve with collisions (:684-685, :773-779,
 	// :798), so doing it at load gives the same pairs.  The list length counts duplicates there; a baked file without "ignore_count" falls back
 	// to the number of distinct bodies.
 	if (nb > 2)
 	{
-		auto itc = fx.find("ignore_count");
 		int n2 = 0;
-		if (itc != fx.end()) n2 = itc->second.i()[2]; else for (int j = 0; j < nb; j++) n2 += (m.ignore[2] >> j) & 1u;
+		if (!rec.ignore_count.empty()) n2 = rec.ignore_count[2]; else for (int j = 0; j < nb; j++) n2 += (m.ignore[2] >> j) & 1u;
 		if (n2 < 10)
 		{
 			m.ignore[2] = 0;
 			for (int j = 0; j < nb; j++) if (j != 2) { m.ignore[2] |= 1u << j; m.ignore[j] |= 1u << 2; }
 		}
 	}
-	for (int j = 0; j < nj; j++)
-	{
-		float *c = &jointc[(size_t)j * HT_JC]; const float *r = jf->f() + 16 * j;
-		c[HT_JC_RB0] = (float)ji->i()[2 * j]; c[HT_JC_RB1] = (float)ji->i()[2 * j + 1];
-		for (int i = 0; i < 3; i++) { c[HT_JC_P0 + i] = r[i]; c[HT_JC_P1 + i] = r[3 + i]; c[HT_JC_RMIN + i] = r[6 + i]; c[HT_JC_RMAX + i] = r[9 + i]; }
-		for (int i = 0; i < 4; i++) c[HT_JC_FRAME + i] = r[12 + i];
-	}
 	{   // unibody cube: f = mass massinv radius damping friction gravscale com3 tensorinv9
-		const float *u = ubf->f();
+		const float *u = rec.ub_f.data();
 		m.ub_massinv = u[1];
 		m.ub_dampleft = powf((1.0f - (u[3] < physics_damping ? physics_damping : u[3])), phys.deltaT);
 		for (int i = 0; i < 3; i++) m.ub_com[i] = u[6 + i];
 		for (int i = 0; i < 9; i++) m.ub_tinv[i] = u[9 + i];
 	}
-	ctx->h_bodyc = bodyc; ctx->h_jointc = jointc;
-	float4 *dv, *dp; float *dbc, *djc;
-	int r;
-	if ((r = dev_upload(ctx, &dv, verts)) || (r = dev_upload(ctx, &dp, planes)) || (r = dev_upload(ctx, &dbc, bodyc)) || (r = dev_upload(ctx, &djc, jointc))) return r;
-	m.verts = dv; m.planes = dp; m.bodyc = dbc; m.jointc = djc;
-	ctx->h_verts = verts; ctx->h_planes = planes; ctx->d_verts_rw = dv; ctx->d_planes_rw = dp; ctx->d_bodyc_rw = dbc; ctx->d_jointc_rw = djc;
-	{ const int r2 = upload_padded_verts(ctx); if (r2) return r2; }
-	{   // the limits of the joint coordinates, with the host's sinf, once (ht_joints.hip)
-		std::vector<float> jl((size_t)nj * HT_JL, 0.0f);
-		ht_joint_limits(jointc.data(), nj, jl.data());
-		const int r2 = dev_upload(ctx, &ctx->d_jointl, jl); if (r2) return r2;
-	}
-	return ht_mesh_upload(ctx);
+	{ const int r = model_to_device(ctx); if (r) return r; }
+	// the limits of the joint coordinates, with the host's sinf, once (ht_joints.hip)
+	std::vector<float> jl((size_t)nj * HT_JL, 0.0f);
+	ht_joint_limits(rec.jointc.data(), nj, jl.data());
+	return dev_put(ctx, &ctx->d_jointl, jl.data(), jl.size());
 }
 
 static void sync_params(ht_ctx *ctx)
@@ -229,39 +200,11 @@ extern "C" int ht_config_read(const char *jsonfile, ht_params *p, float *segment
 extern "C" int ht_scale(ht_ctx *ctx, float s)
 {
 	CHECK_READY(ctx); CHECK_MODEL(ctx);
-	const int nb = ctx->model.nb, nj = ctx->model.nj;
-	const float ss = s * s;
-	for (auto &v : ctx->h_verts) { v.x *= s; v.y *= s; v.z *= s; }      // w keeps the vertex index
-	for (auto &p : ctx->h_planes) p.w *= s;
-	for (auto &v : ctx->h_mesh_corners) v *= s;      // scale(Mesh&) on the sdmeshes (physmodel.h:215-219,308-309)
-	for (int b = 0; b < nb; b++)
-	{
-		float *c = &ctx->h_bodyc[(size_t)b * HT_BC];
-		for (int i = 0; i < 3; i++) c[HT_BC_COM + i] *= s;
-		c[HT_BC_RADIUS] *= s; c[HT_BC_RINNER] *= s;
-		for (int i = 0; i < 9; i++) c[HT_BC_TINV + i] /= ss;
-		float diam2 = 0.0f;      // vertex diameter (used by the exact contact-patch shortcut) of the scaled shape
-		const int v0 = ctx->model.vert_off[b], v1 = ctx->model.vert_off[b + 1];
-		for (int i = v0; i < v1; i++) for (int j = i + 1; j < v1; j++)
-		{
-			const float dx = ctx->h_verts[i].x - ctx->h_verts[j].x, dy = ctx->h_verts[i].y - ctx->h_verts[j].y, dz = ctx->h_verts[i].z - ctx->h_verts[j].z;
-			const float d2 = dx * dx + dy * dy + dz * dz; if (d2 > diam2) diam2 = d2;
-		}
-		c[HT_BC_DIAM] = sqrtf(diam2);
-	}
-	for (int j = 0; j < nj; j++) { float *c = &ctx->h_jointc[(size_t)j * HT_JC]; for (int i = 0; i < 3; i++) { c[HT_JC_P0 + i] *= s; c[HT_JC_P1 + i] *= s; } }
-	for (float &o : ctx->kp_feature8) o *= s;      // the built-in keypoint tables follow the model (HT_KP_SKELETON is read off the anchors and centres of mass above)
-	hipStream_t st = ctx->stream;
-	HIPCHK(ctx, hipStreamSynchronize(st));
-	HIPCHK(ctx, hipMemcpy(ctx->d_verts_rw, ctx->h_verts.data(), ctx->h_verts.size() * sizeof(float4), hipMemcpyHostToDevice));
-	{ const int r = upload_padded_verts(ctx); if (r) return r; }
-	if (ctx->last_user_stream && ctx->last_user_stream != st) HIPCHK(ctx, hipStreamSynchronize(ctx->last_user_stream));      // a render of the old meshes on the caller's stream
-	{ const int r = ht_mesh_upload(ctx); if (r) return r; }
-	HIPCHK(ctx, hipMemcpy(ctx->d_planes_rw, ctx->h_planes.data(), ctx->h_planes.size() * sizeof(float4), hipMemcpyHostToDevice));
-	HIPCHK(ctx, hipMemcpy(ctx->d_bodyc_rw, ctx->h_bodyc.data(), ctx->h_bodyc.size() * sizeof(float), hipMemcpyHostToDevice));
-	HIPCHK(ctx, hipMemcpy(ctx->d_jointc_rw, ctx->h_jointc.data(), ctx->h_jointc.size() * sizeof(float), hipMemcpyHostToDevice));
-	for (int w = 0; w < 2; w++) ht_launch_scale_state(ctx->d_state[w], nb, ctx->B, s, st);
-	return ht_sync_check(ctx, st);
+	ht_model_rec_scale(ctx->rec, s);
+	for (float &o : ctx->kp_feature8) o *= s;      // the built-in keypoint tables follow the model (HT_KP_SKELETON is read off the record's anchors and centres of mass)
+	{ const int r = model_to_device(ctx); if (r) return r; }
+	for (int w = 0; w < 2; w++) ht_launch_scale_state(ctx->d_state[w], ctx->model.nb, ctx->B, s, ctx->stream);
+	return ht_sync_check(ctx, ctx->stream);
 }
 // Training on the weights held by the context; ht_cnn_get_weights reads them back in .cnnb order (CNN::saveb cnn.h:591-593).  Two step implementations, chosen by
 // the entry point: CNN::Train (cnn.h:558-580), one SGD step per sample in the order given (train-cnn.cpp:156-162 calls it with alpha = 0.001; ht_train.hip), and

@@ -5,6 +5,7 @@
 #include <vector>
 #include "ht_device.hpp"
 #include "ht_launch.hpp"
+#include "ht_model_build.hpp"
 
 struct ht_comm_state;      // RCCL communicator + communication stream (ht_comm.hip)
 struct ht_prof_entry { std::vector<hipEvent_t> ev; size_t used; float total_ms; int launches; };
@@ -59,8 +60,8 @@ struct ht_ctx
 	                    "weights: expected HT_CNNB_COUNT fp32 values in .cnnb order" },
 	                  { ht_net_dims_of<128>(), "cnn128", "weights of the 128x128 net not loaded (ht_cnn_load_weights_sized)",
 	                    ": the context holds no weights of the 128x128-input net (ht_cnn_load_weights_sized)", "weights: expected HT_CNNB128_COUNT fp32 values in .cnnb order" } };
-	std::vector<float> h_bodyc, h_jointc;
-	std::vector<float4> h_verts, h_planes;                        // host copies of the model geometry (ht_scale rewrites them)
+	ht_model_rec rec;                                             // the model on the host, the one copy (ht_model_build.hpp): load_model reads it, ht_scale scales it, both lay it out for the device
+	std::vector<float> &h_bodyc = rec.bodyc, &h_jointc = rec.jointc;      // its body and joint tables under the names their readers know
 	float *d_train = nullptr;                                    // the per-sample step's training arena (the 64x64-input net only): layer outputs, errors, split-K partial sums (allocated on first use)
 	char *d_io = nullptr; size_t io_cap = 0;                     // the staging of every synchronous host form (ht_staged_call: inputs up, outputs down), grown to the largest call (dev_grow)
 	float *d_sf_ref = nullptr, *d_sf_crays = nullptr;             // slowfit inputs [B][nb][7], [B][8][4] (allocated on first use)
@@ -105,10 +106,10 @@ struct ht_ctx
 	float *d_user_lin = nullptr; unsigned short *d_user_pos = nullptr; float *d_user_ang = nullptr; int *d_user_n = nullptr;      // [B][lin_cap][HT_ROW], [B][lin_cap], [B][ang_cap][HT_AROW], [4][B]
 	int user_lin_cap = 0, user_ang_cap = 0;
 	ht_comm_state *comm = nullptr;                               // multi-GPU pose gather (ht_comm_init), null on a single-GPU host
-	std::vector<float4> render_planes; std::vector<float> render_radii;     // the hull planes ht_render_depth last derived its per-body cull radii from, and those radii (2 per body)
-	// ht_render_mesh_depth: the subdivision meshes' corners [t][9] over all bodies (ht_scale rewrites them), the first triangle of every body, the device rows
-	// [t][4] float4 (corners and PolyPlane, ht_mesh_rows) and the farthest corner of every body's mesh from its centre of mass (ht_mesh_upload makes both)
-	std::vector<float> h_mesh_corners, mesh_rad; std::vector<int> mesh_off; float4 *d_mesh = nullptr;
+	std::vector<float> render_radii; unsigned render_gen = 0;     // ht_render_depth's per-body cull radii (2 per body) and the record's generation (rec.gen) they were derived at
+	// ht_render_mesh_depth: the record's mesh rows on the device, [t][4] float4 (corners and PolyPlane), and the farthest corner of every body's mesh from its centre of
+	// mass (ht_mesh_upload makes both)
+	std::vector<float> mesh_rad; float4 *d_mesh = nullptr;
 	float *d_jointl = nullptr;                                   // [nj][HT_JL] the limits of the joint coordinates, made once at model load beside jointc (ht_joint_limits; ht_scale leaves them)
 	// ht_update_hands_*: the mirrored inputs an update of flagged frames runs on, [B][hands_px] pixels, [B][12], [B][nb][7], and the flags of the host form [B]; nothing until the
 	// first flagged call or ht_reserve_hands, then grown to the largest frame (hands_reserve, ht_solver_api.hip: one synchronising re-allocation, never smaller)
@@ -230,6 +231,12 @@ struct ht_prof_scope
 static inline size_t ht_scratch_rows(size_t pts_cap, size_t nb) { return pts_cap + 5 * nb + 32 + 7 * 16 + HT_SCRATCH_TAIL; }
 int ht_alloc_buffers(ht_ctx *ctx);
 int ht_mesh_upload(ht_ctx *ctx);             // rows and radii of the model's current subdivision meshes to the device (ht_render_mesh.hip); the caller has waited for the renders in flight
+// What the mesh renderers' kernel arguments take from the record: the bodies' centres of mass [nb][3] and first mesh triangles [nb + 1] (com, tri_off of rm_model / rz_model)
+static inline void ht_mesh_args(const ht_ctx *ctx, float *com, int *tri_off)
+{
+	for (int b = 0; b <= ctx->model.nb; b++) tri_off[b] = ctx->rec.mesh_off[b];
+	for (int b = 0; b < ctx->model.nb; b++) for (int i = 0; i < 3; i++) com[3 * b + i] = ctx->rec.bodyc[(size_t)b * HT_BC + HT_BC_COM + i];
+}
 int ht_alloc_solve_tables(ht_ctx *ctx);      // d_tables and nothing else, once (d_chplanes / d_chon come with ht_alloc_buffers): from ht_debug_solve_tables(ctx, 1 or 2), and from ht_alloc_buffers under HT_TABLES in a tuning build
 int ht_reserve_points_locked(ht_ctx *ctx, int points);      // grows the per-point arrays (ht_api.hip); waits for the context's streams
 // *_dev entry points: a NULL stream means the context's own stream (never the legacy default stream); the choice is remembered so that the

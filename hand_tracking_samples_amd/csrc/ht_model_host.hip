@@ -13,97 +13,154 @@
 #include "ht_launch.hpp"
 #include "ht_raster.hpp"
 
+// ------------------------------------------------------------------------------------------------- the record (ht_model_build.hpp)
+static float body_diam(const ht_model_rec &rec, int b)      // HT_BC_DIAM: the largest distance between two of body b's vertices (the exact contact-patch shortcut uses it)
+{
+	float diam2 = 0.0f;
+	for (int i = rec.vert_off[b]; i < rec.vert_off[b + 1]; i++) for (int j = i + 1; j < rec.vert_off[b + 1]; j++)
+	{
+		const float *p = &rec.verts[3 * (size_t)i], *q = &rec.verts[3 * (size_t)j], dx = p[0] - q[0], dy = p[1] - q[1], dz = p[2] - q[2];
+		const float d2 = dx * dx + dy * dy + dz * dz; if (d2 > diam2) diam2 = d2;
+	}
+	return sqrtf(diam2);
+}
+bool ht_model_read(const char *path, int flags, ht_model_rec &rec, std::string &err)
+{
+	// `path` is either the reference's model JSON (built here, a33) or a model baked earlier with ht_model_bake
+	fx_map fx;
+	char magic[8] = { 0 };
+	{ FILE *fp = fopen(path, "rb"); if (!fp) { err = std::string("cannot open model ") + path; return false; } size_t n = fread(magic, 1, 8, fp); (void)n; fclose(fp); }
+	if (!memcmp(magic, "HTFX0001", 8)) { if (!fx_load(path, fx)) { err = std::string("cannot read baked model ") + path; return false; } }
+	else if (!ht_build_model(path, flags, fx, err)) return false;
+	rec = ht_model_rec();
+	auto get = [&](const std::string &n) -> const fx_arr * { auto it = fx.find(n); if (it == fx.end()) { rec.missing.push_back(n); return nullptr; } return &it->second; };
+	auto floats = [&](const fx_arr *a) { return a ? std::vector<float>(a->f(), a->f() + a->data.size() / 4) : std::vector<float>(); };
+	auto ints = [&](const fx_arr *a) { return a ? std::vector<int>(a->i(), a->i() + a->data.size() / 4) : std::vector<int>(); };
+	const fx_arr *nb = get("nb"), *nj = get("nj");
+	if (!nb || !nj) return true;
+	rec.nb = nb->i()[0]; rec.nj = nj->i()[0];
+	const fx_arr *bf = get("body_f");
+	rec.collide = ints(get("body_collide")); rec.ignore = ints(get("ignore"));
+	const fx_arr *ji = get("joint_i"), *jf = get("joint_f");
+	rec.physics = floats(get("physics")); rec.ub_verts = floats(get("unibody/verts")); rec.ub_f = floats(get("unibody/f"));
+	{ auto it = fx.find("ignore_count"); if (it != fx.end()) rec.ignore_count = ints(&it->second); }
+	for (int b = 0; bf && b < rec.nb; b++)
+	{
+		const std::string k = "b" + std::to_string(b);
+		const fx_arr *v = get(k + "/verts"), *p = get(k + "/planes"), *t = get(k + "/tris");
+		if (!v || !p) break;
+		rec.verts.insert(rec.verts.end(), v->f(), v->f() + (size_t)v->dims[0] * 3);
+		rec.planes.insert(rec.planes.end(), p->f(), p->f() + (size_t)p->dims[0] * 4);
+		if (t) rec.tris.insert(rec.tris.end(), t->i(), t->i() + (size_t)t->dims[0] * 3);
+		// the subdivision meshes (GetMeshes(true)); a baked model from before they were stored has none, and the mesh renderers then refuse
+		auto sv = fx.find(k + "/sdverts");
+		if (sv != fx.end()) rec.corners.insert(rec.corners.end(), sv->second.f(), sv->second.f() + (size_t)(sv->second.dims[0] / 3) * 9);
+		rec.vert_off.push_back((int)(rec.verts.size() / 3)); rec.plane_off.push_back((int)(rec.planes.size() / 4));
+		rec.tri_off.push_back((int)(rec.tris.size() / 3)); rec.mesh_off.push_back((int)(rec.corners.size() / 9));
+		const float *r = bf->f() + 26 * b;     // mass massinv radius radius_inner damping friction gravscale com3 pos_start3 quat_start4 tensorinv9
+		rec.bodyc.resize((size_t)(b + 1) * HT_BC, 0.0f); rec.damping.push_back(r[4]);
+		float *c = &rec.bodyc[(size_t)b * HT_BC];
+		c[HT_BC_MASS] = r[0]; c[HT_BC_MASSINV] = r[1]; c[HT_BC_RADIUS] = r[2]; c[HT_BC_RINNER] = r[3]; c[HT_BC_FRICTION] = r[5]; c[HT_BC_DIAM] = body_diam(rec, b);
+		for (int i = 0; i < 3; i++) { c[HT_BC_COM + i] = r[7 + i]; c[HT_BC_POS0 + i] = r[10 + i]; }
+		for (int i = 0; i < 4; i++) c[HT_BC_Q0 + i] = r[13 + i];
+		for (int i = 0; i < 9; i++) c[HT_BC_TINV + i] = r[17 + i];
+	}
+	rec.rows.resize(rec.corners.size() / 9 * 16); ht_mesh_rows(rec.corners.data(), rec.corners.size() / 9, rec.rows.data());
+	if (ji && jf && rec.nj > 0) rec.jointc.assign((size_t)rec.nj * HT_JC, 0.0f);
+	for (size_t j = 0; j < rec.jointc.size() / HT_JC; j++)
+	{
+		float *c = &rec.jointc[j * HT_JC]; const float *r = jf->f() + 16 * j;      // p0 p1 rangemin rangemax jointframe
+		c[HT_JC_RB0] = (float)ji->i()[2 * j]; c[HT_JC_RB1] = (float)ji->i()[2 * j + 1];
+		for (int i = 0; i < 3; i++) { c[HT_JC_P0 + i] = r[i]; c[HT_JC_P1 + i] = r[3 + i]; c[HT_JC_RMIN + i] = r[6 + i]; c[HT_JC_RMAX + i] = r[9 + i]; }
+		for (int i = 0; i < 4; i++) c[HT_JC_FRAME + i] = r[12 + i];
+	}
+	return true;
+}
+void ht_model_rec_scale(ht_model_rec &rec, float s)
+{
+	const float ss = s * s;
+	for (float &v : rec.verts) v *= s;
+	for (size_t k = 3; k < rec.planes.size(); k += 4) rec.planes[k] *= s;
+	for (float &v : rec.corners) v *= s;      // scale(Mesh&) on the sdmeshes (physmodel.h:215-219,308-309)
+	for (size_t b = 0; b < rec.bodyc.size() / HT_BC; b++)
+	{
+		float *c = &rec.bodyc[b * HT_BC];
+		for (int i = 0; i < 3; i++) c[HT_BC_COM + i] *= s;
+		c[HT_BC_RADIUS] *= s; c[HT_BC_RINNER] *= s;
+		for (int i = 0; i < 9; i++) c[HT_BC_TINV + i] /= ss;
+		c[HT_BC_DIAM] = body_diam(rec, (int)b);
+	}
+	for (size_t j = 0; j < rec.jointc.size() / HT_JC; j++) { float *c = &rec.jointc[j * HT_JC]; for (int i = 0; i < 3; i++) { c[HT_JC_P0 + i] *= s; c[HT_JC_P1 + i] *= s; } }
+	ht_mesh_rows(rec.corners.data(), rec.corners.size() / 9, rec.rows.data());      // PolyPlane of the scaled corners
+	rec.gen++;
+}
+
+// ------------------------------------------------------------------------------------------------- the host view
 struct ht_model
 {
-	int nb = 0, nj = 0;
-	std::vector<std::vector<float>> verts, planes;      // per body: [n][3] com-centred vertices, [n][4] local half-space planes
-	std::vector<std::vector<int>> tris;                 // per body: [n][3] hull triangles over verts
-	std::vector<std::vector<float>> sdverts;            // per body: [3 t][3] the subdivision surface's triangles corner by corner, in the bone's rig frame (GetMeshes(true), physmodel.h:258)
-	std::vector<std::vector<float>> sdrows;             // per body: [t][16] corners and PolyPlane of every sdverts triangle (ht_mesh_rows), what the mesh ray cast reads
-	std::vector<float> com, rest;                       // [nb][3], [nb][7]
-	std::vector<float> jointc;                          // [nj][HT_JC] the joint table as a context keeps it
-	bool mirrored = false;                              // ht_model_mirror was applied an odd number of times (ht_model_scale makes the mesh rows from the unmirrored corners)
+	ht_model_rec rec;
+	bool mirrored = false;      // ht_model_mirror was applied an odd number of times (ht_model_scale makes the mesh rows from the unmirrored corners)
 	std::string err;
+	int bodies() const { return (int)rec.vert_off.size() - 1; }      // the bodies held: nb of a model that opened
+	bool has(int body) const { return body >= 0 && body < bodies(); }
+	const float *com(int b) const { return &rec.bodyc[(size_t)b * HT_BC + HT_BC_COM]; }
 };
 
 extern "C" int ht_model_open(const char *path, int hand_tweaks, ht_model **out)
 {
 	if (!path || !out) return HT_ERR_ARG;
-	ht_model *m = new ht_model();
-	*out = m;
-	fx_map fx;
-	char magic[8] = { 0 };
-	{ FILE *fp = fopen(path, "rb"); if (!fp) { m->err = std::string("cannot open model ") + path; return HT_ERR_IO; } size_t n = fread(magic, 1, 8, fp); (void)n; fclose(fp); }
-	if (!memcmp(magic, "HTFX0001", 8)) { if (!fx_load(path, fx)) { m->err = std::string("cannot read baked model ") + path; return HT_ERR_IO; } }
-	else if (!ht_build_model(path, hand_tweaks ? HT_BUILD_HAND_TWEAKS : 0, fx, m->err)) return HT_ERR_IO;
-	auto get = [&](const std::string &n) -> const fx_arr * { auto it = fx.find(n); return it == fx.end() ? nullptr : &it->second; };
-	const fx_arr *nb = get("nb"), *nj = get("nj"), *bf = get("body_f");
-	if (!nb || !nj || !bf) { m->err = "model entries missing"; return HT_ERR_IO; }
-	m->nb = nb->i()[0]; m->nj = nj->i()[0];
-	for (int b = 0; b < m->nb; b++)
-	{
-		const std::string k = "b" + std::to_string(b);
-		const fx_arr *v = get(k + "/verts"), *p = get(k + "/planes"), *t = get(k + "/tris");
-		if (!v || !p || !t) { m->err = "model body arrays missing"; return HT_ERR_IO; }
-		m->verts.emplace_back(v->f(), v->f() + (size_t)v->dims[0] * 3);
-		m->planes.emplace_back(p->f(), p->f() + (size_t)p->dims[0] * 4);
-		m->tris.emplace_back(t->i(), t->i() + (size_t)t->dims[0] * 3);
-		const fx_arr *sv = get(k + "/sdverts");
-		if (sv) m->sdverts.emplace_back(sv->f(), sv->f() + (size_t)sv->dims[0] * 3); else m->sdverts.emplace_back();
-		m->sdrows.emplace_back((m->sdverts.back().size() / 9) * 16);
-		ht_mesh_rows(m->sdverts.back().data(), m->sdverts.back().size() / 9, m->sdrows.back().data());
-		const float *r = bf->f() + 26 * b;      // mass massinv radius radius_inner damping friction gravscale com3 pos_start3 quat_start4 tensorinv9
-		m->com.insert(m->com.end(), r + 7, r + 10);
-		m->rest.insert(m->rest.end(), r + 10, r + 17);
-	}
-	const fx_arr *ji = get("joint_i"), *jf = get("joint_f");
-	if (m->nj > 0 && (!ji || !jf)) { m->err = "model joint arrays missing"; return HT_ERR_IO; }
-	m->jointc.assign((size_t)m->nj * HT_JC, 0.0f);
-	for (int j = 0; j < m->nj; j++)
-	{
-		float *c = &m->jointc[(size_t)j * HT_JC]; const float *r = jf->f() + 16 * j;      // p0 p1 rangemin rangemax jointframe
-		c[HT_JC_RB0] = (float)ji->i()[2 * j]; c[HT_JC_RB1] = (float)ji->i()[2 * j + 1];
-		for (int i = 0; i < 3; i++) { c[HT_JC_P0 + i] = r[i]; c[HT_JC_P1 + i] = r[3 + i]; c[HT_JC_RMIN + i] = r[6 + i]; c[HT_JC_RMAX + i] = r[9 + i]; }
-		for (int i = 0; i < 4; i++) c[HT_JC_FRAME + i] = r[12 + i];
-	}
+	ht_model *m = *out = new ht_model();
+	const ht_model_rec &rec = m->rec;
+	if (!ht_model_read(path, hand_tweaks ? HT_BUILD_HAND_TWEAKS : 0, m->rec, m->err)) return HT_ERR_IO;
+	// this view needs the bodies whole (hull triangles included) and the joint table; the physics constants, collision lists and unibody proxy it can do without
+	if (rec.lacks("nb") || rec.lacks("nj") || rec.lacks("body_f")) { m->err = "model entries missing"; return HT_ERR_IO; }
+	for (const std::string &n : rec.missing) if (n[0] == 'b' && n[1] >= '0' && n[1] <= '9') { m->err = "model body arrays missing"; return HT_ERR_IO; }
+	if (rec.nj > 0 && (rec.lacks("joint_i") || rec.lacks("joint_f"))) { m->err = "model joint arrays missing"; return HT_ERR_IO; }
 	return HT_OK;
 }
 // the limits of the joint coordinates c = (s.x, s.y, t.z) (ConstrainAngularRangeW physics.h:351-393), as a context computes them at model load
 extern "C" int ht_model_joint_limits(const ht_model *m, float *lo, float *hi, int *swapped)
 {
-	if (!m || m->jointc.size() != (size_t)m->nj * HT_JC) return HT_ERR_ARG;
-	std::vector<float> jl((size_t)m->nj * HT_JL, 0.0f);
-	ht_joint_limits(m->jointc.data(), m->nj, jl.data());
-	ht_joint_limits_public(jl.data(), m->nj, lo, hi, swapped);
+	if (!m || m->rec.jointc.size() != (size_t)m->rec.nj * HT_JC) return HT_ERR_ARG;
+	std::vector<float> jl((size_t)m->rec.nj * HT_JL, 0.0f);
+	ht_joint_limits(m->rec.jointc.data(), m->rec.nj, jl.data());
+	ht_joint_limits_public(jl.data(), m->rec.nj, lo, hi, swapped);
 	return HT_OK;
 }
 extern "C" int ht_model_close(ht_model *m) { if (!m) return HT_ERR_ARG; delete m; return HT_OK; }
 extern "C" const char *ht_model_error(const ht_model *m) { return m ? m->err.c_str() : "null model"; }
-extern "C" int ht_model_counts(const ht_model *m, int *nb, int *nj) { if (!m) return HT_ERR_ARG; if (nb) *nb = m->nb; if (nj) *nj = m->nj; return HT_OK; }
+extern "C" int ht_model_counts(const ht_model *m, int *nb, int *nj) { if (!m) return HT_ERR_ARG; if (nb) *nb = m->rec.nb; if (nj) *nj = m->rec.nj; return HT_OK; }
 extern "C" int ht_model_body(const ht_model *m, int body, int *nverts, int *ntris, int *nplanes, float *com3, float *rest_pose7)
 {
-	if (!m || body < 0 || body >= m->nb) return HT_ERR_ARG;
-	if (nverts) *nverts = (int)m->verts[body].size() / 3;
-	if (ntris) *ntris = (int)m->tris[body].size() / 3;
-	if (nplanes) *nplanes = (int)m->planes[body].size() / 4;
-	if (com3) memcpy(com3, &m->com[3 * body], 3 * sizeof(float));
-	if (rest_pose7) memcpy(rest_pose7, &m->rest[7 * body], 7 * sizeof(float));
+	if (!m || !m->has(body)) return HT_ERR_ARG;
+	const ht_model_rec &r = m->rec;
+	if (nverts) *nverts = r.vert_off[body + 1] - r.vert_off[body];
+	if (ntris) *ntris = r.tri_off[body + 1] - r.tri_off[body];
+	if (nplanes) *nplanes = r.plane_off[body + 1] - r.plane_off[body];
+	if (com3) memcpy(com3, m->com(body), 3 * sizeof(float));
+	if (rest_pose7)      // position_start, orientation_start
+	{
+		memcpy(rest_pose7, &r.bodyc[(size_t)body * HT_BC + HT_BC_POS0], 3 * sizeof(float));
+		memcpy(rest_pose7 + 3, &r.bodyc[(size_t)body * HT_BC + HT_BC_Q0], 4 * sizeof(float));
+	}
 	return HT_OK;
 }
 extern "C" int ht_model_body_mesh(const ht_model *m, int body, float *verts, int *tris)
 {
-	if (!m || body < 0 || body >= m->nb) return HT_ERR_ARG;
-	if (verts) memcpy(verts, m->verts[body].data(), m->verts[body].size() * sizeof(float));
-	if (tris) memcpy(tris, m->tris[body].data(), m->tris[body].size() * sizeof(int));
+	if (!m || !m->has(body)) return HT_ERR_ARG;
+	const ht_model_rec &r = m->rec;
+	if (verts) memcpy(verts, r.verts.data() + (size_t)3 * r.vert_off[body], (size_t)3 * (r.vert_off[body + 1] - r.vert_off[body]) * sizeof(float));
+	if (tris) memcpy(tris, r.tris.data() + (size_t)3 * r.tri_off[body], (size_t)3 * (r.tri_off[body + 1] - r.tri_off[body]) * sizeof(int));
 	return HT_OK;
 }
 // the subdivision surface of a body (PhysModel::sdmeshes, physmodel.h:258: MeshFlatShadeTex of the twice-subdivided control cage): *nverts corner positions, three per
 // triangle in order, in the bone's rig frame -- drawn at Pose{PositionUser, orientation} (physmodel.h:297-298).  verts may be NULL to ask for the count.
 extern "C" int ht_model_body_sdmesh(const ht_model *m, int body, int *nverts, float *verts)
 {
-	if (!m || body < 0 || body >= m->nb) return HT_ERR_ARG;
-	if (nverts) *nverts = (int)m->sdverts[body].size() / 3;
-	if (verts) memcpy(verts, m->sdverts[body].data(), m->sdverts[body].size() * sizeof(float));
+	if (!m || !m->has(body)) return HT_ERR_ARG;
+	const int t0 = m->rec.mesh_off[body], nt = m->rec.mesh_off[body + 1] - t0;
+	if (nverts) *nverts = 3 * nt;
+	if (verts) memcpy(verts, m->rec.corners.data() + (size_t)9 * t0, (size_t)9 * nt * sizeof(float));
 	return HT_OK;
 }
 // PhysModel::HitCheck(v0, v1): the segment is clipped against the hull of every body in turn, each body starting from the impact the previous
@@ -114,14 +171,14 @@ extern "C" int ht_model_hitcheck(const ht_model *m, const float *poses, const fl
 	const v3 v0w = V3(v0_[0], v0_[1], v0_[2]);
 	v3 impact = V3(v1_[0], v1_[1], v1_[2]), normal = V3(0, 0, 0);
 	int who = -1;
-	for (int b = 0; b < m->nb; b++)
+	for (int b = 0; b < m->bodies(); b++)
 	{
 		const float *p = poses + 7 * b;
 		const xf pose = XF(V3(p[0], p[1], p[2]), V4(p[3], p[4], p[5], p[6])), inv = inverse(pose);
 		v3 a = apply(inv, v0w), c = apply(inv, impact), n = V3(0, 0, 0);
 		bool hit = true;
-		const std::vector<float> &pl = m->planes[b];
-		for (size_t k = 0; k + 3 < pl.size(); k += 4)      // ConvexHitCheck geometric.h:275-297
+		const float *pl = m->rec.planes.data();
+		for (size_t k = (size_t)4 * m->rec.plane_off[b]; k < (size_t)4 * m->rec.plane_off[b + 1]; k += 4)      // ConvexHitCheck geometric.h:275-297
 		{
 			const v4 plane = V4(pl[k], pl[k + 1], pl[k + 2], pl[k + 3]);
 			const float d0 = dot_plane(plane, a), d1 = dot_plane(plane, c);
@@ -138,21 +195,14 @@ extern "C" int ht_model_hitcheck(const ht_model *m, const float *poses, const fl
 	return HT_OK;
 }
 
-// PhysModel::scale (physmodel.h:196-219,304-319) for what this view holds: hull vertices and plane offsets, the subdivision meshes and the centres of mass times s,
-// the operations ht_scale applies to a context's model, so a scaled host model and a scaled context stay bit-equal.  The mesh planes are made again from the scaled corners.
+// PhysModel::scale (physmodel.h:196-219,304-319): ht_model_rec_scale, the statement ht_scale applies to a context's record, so a scaled host model and a scaled
+// context are bit-equal.
 static void model_mirror_arrays(ht_model *m);
 extern "C" int ht_model_scale(ht_model *m, float s)
 {
 	if (!m || !(s > 0.0f)) return HT_ERR_ARG;
 	if (m->mirrored) { model_mirror_arrays(m); const int r = ht_model_scale(m, s); model_mirror_arrays(m); return r; }      // PolyPlane's sums depend on the corner order: scaled as the right hand, so that scale and mirror commute to the bit
-	for (int b = 0; b < m->nb; b++)
-	{
-		for (auto &v : m->verts[b]) v *= s;
-		for (size_t k = 3; k < m->planes[b].size(); k += 4) m->planes[b][k] *= s;
-		for (auto &v : m->sdverts[b]) v *= s;
-		ht_mesh_rows(m->sdverts[b].data(), m->sdverts[b].size() / 9, m->sdrows[b].data());
-	}
-	for (auto &v : m->com) v *= s;
+	ht_model_rec_scale(m->rec, s);
 	return HT_OK;
 }
 
@@ -163,31 +213,31 @@ extern "C" int ht_model_scale(ht_model *m, float s)
 static inline void flip_sign(float &v) { unsigned u; memcpy(&u, &v, 4); u ^= 0x80000000u; memcpy(&v, &u, 4); }
 static void model_mirror_arrays(ht_model *m)
 {
-	for (int b = 0; b < m->nb; b++)
+	ht_model_rec &R = m->rec;
+	for (size_t k = 0; k < R.verts.size(); k += 3) flip_sign(R.verts[k]);
+	for (size_t k = 0; k < R.planes.size(); k += 4) flip_sign(R.planes[k]);
+	for (size_t k = 0; k + 2 < R.tris.size(); k += 3) std::swap(R.tris[k + 1], R.tris[k + 2]);
+	for (size_t t = 0; t < R.corners.size() / 9; t++)
 	{
-		for (size_t k = 0; k < m->verts[b].size(); k += 3) flip_sign(m->verts[b][k]);
-		for (size_t k = 0; k < m->planes[b].size(); k += 4) flip_sign(m->planes[b][k]);
-		for (size_t k = 0; k + 2 < m->tris[b].size(); k += 3) std::swap(m->tris[b][k + 1], m->tris[b][k + 2]);
-		std::vector<float> &sv = m->sdverts[b], &sr = m->sdrows[b];
-		for (size_t t = 0; t < sv.size() / 9; t++)
-		{
-			float *c = &sv[9 * t], *r = &sr[16 * t];
-			for (int i = 0; i < 3; i++) { std::swap(c[3 + i], c[6 + i]); std::swap(r[4 + i], r[8 + i]); }
-			for (int i = 0; i < 3; i++) { flip_sign(c[3 * i]); flip_sign(r[4 * i]); }
-			flip_sign(r[12]);
-		}
-		flip_sign(m->com[3 * b]);
-		float *p = &m->rest[7 * b];
-		flip_sign(p[0]); flip_sign(p[4]); flip_sign(p[5]);
+		float *c = &R.corners[9 * t], *r = &R.rows[16 * t];
+		for (int i = 0; i < 3; i++) { std::swap(c[3 + i], c[6 + i]); std::swap(r[4 + i], r[8 + i]); }
+		for (int i = 0; i < 3; i++) { flip_sign(c[3 * i]); flip_sign(r[4 * i]); }
+		flip_sign(r[12]);
+	}
+	for (size_t b = 0; b < R.bodyc.size() / HT_BC; b++)
+	{
+		float *c = &R.bodyc[b * HT_BC];
+		flip_sign(c[HT_BC_COM]); flip_sign(c[HT_BC_POS0]); flip_sign(c[HT_BC_Q0 + 1]); flip_sign(c[HT_BC_Q0 + 2]);
 	}
 	m->mirrored = !m->mirrored;
 }
 // the stored planes of a body: its hull's [nplanes][4] and the PolyPlane [t][4] of every triangle of its subdivision mesh (what the two ray casts read); either may be null
 extern "C" int ht_model_body_planes(const ht_model *m, int body, float *hull_planes, float *mesh_planes)
 {
-	if (!m || body < 0 || body >= m->nb) return HT_ERR_ARG;
-	if (hull_planes) memcpy(hull_planes, m->planes[body].data(), m->planes[body].size() * sizeof(float));
-	if (mesh_planes) for (size_t t = 0; t < m->sdrows[body].size() / 16; t++) memcpy(mesh_planes + 4 * t, &m->sdrows[body][16 * t + 12], 4 * sizeof(float));
+	if (!m || !m->has(body)) return HT_ERR_ARG;
+	const ht_model_rec &r = m->rec;
+	if (hull_planes) memcpy(hull_planes, r.planes.data() + (size_t)4 * r.plane_off[body], (size_t)4 * (r.plane_off[body + 1] - r.plane_off[body]) * sizeof(float));
+	if (mesh_planes) for (int t = r.mesh_off[body]; t < r.mesh_off[body + 1]; t++) memcpy(mesh_planes + 4 * (t - r.mesh_off[body]), &r.rows[(size_t)16 * t + 12], 4 * sizeof(float));
 	return HT_OK;
 }
 extern "C" int ht_model_mirror(ht_model *m)
@@ -206,16 +256,15 @@ static mesh_hit mesh_hitcheck(const ht_model *m, const float *poses, v3 v0, v3 v
 {
 	mesh_hit h; h.body = -1; h.tri = -1; h.impact = v1; h.normal = V3(0, 0, 0);
 	float best = INFINITY;
-	for (int b = 0; b < m->nb; b++)
+	for (int b = 0; b < m->bodies(); b++)
 	{
-		const float *p = poses + 7 * b;
+		const float *p = poses + 7 * b, *com = m->com(b);
 		const v4 q = V4(p[3], p[4], p[5], p[6]);
-		const xf U = XF(V3(p[0], p[1], p[2]) - qrot(q, V3(m->com[3 * b], m->com[3 * b + 1], m->com[3 * b + 2])), q), inv = inverse(U);
+		const xf U = XF(V3(p[0], p[1], p[2]) - qrot(q, V3(com[0], com[1], com[2])), q), inv = inverse(U);
 		const v3 a = apply(inv, v0), c = apply(inv, v1);
-		const std::vector<float> &R = m->sdrows[b];
-		for (size_t k = 0; 16 * k < R.size(); k++)
+		for (size_t k = 0; k < (size_t)(m->rec.mesh_off[b + 1] - m->rec.mesh_off[b]); k++)      // k: the triangle within the body
 		{
-			const float *r = &R[16 * k];
+			const float *r = &m->rec.rows[16 * (m->rec.mesh_off[b] + k)];
 			const v4 P = V4(r[12], r[13], r[14], r[15]);
 			const float d0 = dot_plane(P, a), d1 = dot_plane(P, c);
 			if (!(d0 > 0 && d1 < 0)) continue;
@@ -266,15 +315,14 @@ extern "C" int ht_model_raster_mesh(const ht_model *m, const float *poses, const
 	if (!m || !poses || !cam12 || !depth || w < 1 || h < 1 || w > 4096 || h > 4096 || !(far > 0.0f) || !(pixel_offset >= 0.0f && pixel_offset <= 1.0f)) return HT_ERR_ARG;
 	const float fx = cam12[0], fy = cam12[1], px = cam12[2], py = cam12[3], ds = cam12[4];
 	std::vector<int> best((size_t)w * h, 65536), who((size_t)w * h, -1);
-	for (int b = 0; b < m->nb; b++)
+	for (int b = 0; b < m->bodies(); b++)
 	{
-		const float *p = poses + 7 * b;
+		const float *p = poses + 7 * b, *com = m->com(b);
 		const m3 R = qmat(V4(p[3], p[4], p[5], p[6]));
-		const v3 up = V3(p[0], p[1], p[2]) - mul(R, V3(m->com[3 * b], m->com[3 * b + 1], m->com[3 * b + 2]));
-		const std::vector<float> &C = m->sdverts[b];
-		for (size_t k = 0; 9 * k < C.size(); k++)
+		const v3 up = V3(p[0], p[1], p[2]) - mul(R, V3(com[0], com[1], com[2]));
+		for (int k = m->rec.mesh_off[b]; k < m->rec.mesh_off[b + 1]; k++)
 		{
-			const float *c = &C[9 * k];
+			const float *c = &m->rec.corners[(size_t)9 * k];
 			rz_tri T;
 			if (!rz_setup(R, up, V3(c[0], c[1], c[2]), V3(c[3], c[4], c[5]), V3(c[6], c[7], c[8]), fx, fy, px, py, pixel_offset, T)) continue;
 			int x0, x1, y0, y1;

@@ -142,7 +142,7 @@ static int rz_check_args(ht_ctx *ctx, const void *poses, const void *cams, const
 {
 	{ const int r = rc_check_args(ctx, "ht_raster_mesh_depth", poses, cams, depth, w, h, far, B, off >= 0.0f && off <= 1.0f); if (r) return r; }
 	if (!ctx->d_mesh) { ctx->err = "the model file holds no subdivision meshes (bake it again)"; return HT_ERR_STATE; }
-	if (ctx->mesh_off[ctx->model.nb] >= 65535) { ctx->err = "ht_raster_mesh_depth: the model has 65535 or more mesh triangles (the z-buffer keeps a 16-bit triangle index)"; return HT_ERR_STATE; }
+	if (ctx->rec.mesh_off[ctx->model.nb] >= 65535) { ctx->err = "ht_raster_mesh_depth: the model has 65535 or more mesh triangles (the z-buffer keeps a 16-bit triangle index)"; return HT_ERR_STATE; }
 	return HT_OK;
 }
 
@@ -154,9 +154,8 @@ extern "C" int ht_raster_mesh_depth_dev(ht_ctx *ctx, const float *d_poses, const
 	hipStream_t s = ht_user_stream(ctx, stream);
 	rz_model m;
 	memset(&m, 0, sizeof m);
-	m.rows = ctx->d_mesh; m.nb = ctx->model.nb; m.ntri = ctx->mesh_off[m.nb];
-	for (int b = 0; b <= m.nb; b++) m.tri_off[b] = ctx->mesh_off[b];
-	for (int b = 0; b < m.nb; b++) for (int i = 0; i < 3; i++) m.com[3 * b + i] = ctx->h_bodyc[(size_t)b * HT_BC + HT_BC_COM + i];
+	m.rows = ctx->d_mesh; m.nb = ctx->model.nb;
+	ht_mesh_args(ctx, m.com, m.tri_off); m.ntri = m.tri_off[m.nb];
 	const int rows = rz_band_rows(w, h), bands = (h + rows - 1) / rows;
 	const int per = INT_MAX / bands;      // frames per launch (grid size limit)
 	for (int f0 = 0; f0 < B; f0 += per)

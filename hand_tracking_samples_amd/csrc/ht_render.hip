@@ -121,16 +121,17 @@ __global__ __launch_bounds__(RC_THREADS) void k_render_depth(const rt_model M, c
 
 // Per-body radii of the context's current model (after ht_scale), from the hull planes themselves (the collision vertices are not the planes' polytope:
 // the planes may lie outside them): the farthest vertex of the polytope {x : dot_plane(p, x) <= 0 for every plane p} from the centre of mass, by
-// enumerating the feasible intersections of three planes in double, and the nearest plane.  Derived once per model state (about 50 ms for the hand).
+// enumerating the feasible intersections of three planes in double, and the nearest plane.  Derived once per model state (about 50 ms for the hand): again when
+// the record's generation has moved (ht_scale).
 static void rt_fill_model(ht_ctx *ctx, rt_model &m)
 {
 	memset(&m, 0, sizeof m);
 	m.planes = ctx->model.planes; m.nb = ctx->model.nb;
 	for (int b = 0; b <= m.nb; b++) m.plane_off[b] = ctx->model.plane_off[b];
-	const std::vector<float4> &P = ctx->h_planes;
-	const bool same = ctx->render_planes.size() == P.size() && ctx->render_radii.size() == 2 * (size_t)m.nb && (P.empty() || !memcmp(ctx->render_planes.data(), P.data(), P.size() * sizeof(float4)));
-	if (!same)
+	if (ctx->render_radii.size() != 2 * (size_t)m.nb || ctx->render_gen != ctx->rec.gen)
 	{
+		std::vector<float4> P(ctx->rec.planes.size() / 4);      // the record's planes, for the time of the derivation
+		if (!P.empty()) memcpy(P.data(), ctx->rec.planes.data(), P.size() * sizeof(float4));
 		ctx->render_radii.assign(2 * (size_t)m.nb, 0.0f);
 		for (int b = 0; b < m.nb; b++)
 		{
@@ -165,7 +166,7 @@ static void rt_fill_model(ht_ctx *ctx, rt_model &m)
 			ctx->render_radii[2 * b] = ok ? (float)(r * (1.0 + 1e-4) + 1e-6) : INFINITY;
 			ctx->render_radii[2 * b + 1] = ok ? (float)(hmin * (1.0 - 1e-6)) : -1.0f;
 		}
-		ctx->render_planes = P;
+		ctx->render_gen = ctx->rec.gen;
 	}
 	for (int b = 0; b < m.nb; b++) { m.rad[b] = ctx->render_radii[2 * b]; m.hin[b] = ctx->render_radii[2 * b + 1]; }
 }

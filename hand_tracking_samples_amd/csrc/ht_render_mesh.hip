@@ -162,26 +162,24 @@ __global__ __launch_bounds__(RC_THREADS) void k_render_mesh(const rm_model M, co
 // rows and radii of the context's current meshes (after ht_scale): called by the model loader and by ht_scale, which have waited for the renders in flight
 int ht_mesh_upload(ht_ctx *ctx)
 {
-	const int nb = ctx->model.nb;
-	const size_t nt = ctx->h_mesh_corners.size() / 9;
+	const ht_model_rec &rec = ctx->rec;
+	const int nb = ctx->model.nb; const size_t nt = rec.corners.size() / 9;
 	ctx->mesh_rad.assign((size_t)nb, 0.0f);
 	if (!nt) return HT_OK;
-	std::vector<float> rows(nt * 16);
-	ht_mesh_rows(ctx->h_mesh_corners.data(), nt, rows.data());
 	for (int b = 0; b < nb; b++)
 	{
-		const float *com = &ctx->h_bodyc[(size_t)b * HT_BC + HT_BC_COM];
+		const float *com = &rec.bodyc[(size_t)b * HT_BC + HT_BC_COM];
 		double r2 = 0.0;
-		for (int k = ctx->mesh_off[b]; k < ctx->mesh_off[b + 1]; k++) for (int i = 0; i < 3; i++)
+		for (int k = rec.mesh_off[b]; k < rec.mesh_off[b + 1]; k++) for (int i = 0; i < 3; i++)
 		{
-			const float *p = &ctx->h_mesh_corners[(size_t)9 * k + 3 * i];
+			const float *p = &rec.corners[(size_t)9 * k + 3 * i];
 			const double dx = (double)p[0] - com[0], dy = (double)p[1] - com[1], dz = (double)p[2] - com[2];
 			r2 = fmax(r2, dx * dx + dy * dy + dz * dz);
 		}
 		ctx->mesh_rad[b] = (float)(sqrt(r2) * (1.0 + 1e-6) + 1e-7);
 	}
 	if (!ctx->d_mesh) { const int r = dev_alloc(ctx, &ctx->d_mesh, nt * 4); if (r) return r; }
-	HIPCHK(ctx, hipMemcpy(ctx->d_mesh, rows.data(), rows.size() * sizeof(float), hipMemcpyHostToDevice));
+	HIPCHK(ctx, hipMemcpy(ctx->d_mesh, rec.rows.data(), rec.rows.size() * sizeof(float), hipMemcpyHostToDevice));
 	return HT_OK;
 }
 
@@ -201,8 +199,8 @@ extern "C" int ht_render_mesh_depth_dev(ht_ctx *ctx, const float *d_poses, const
 	rm_model m;
 	memset(&m, 0, sizeof m);
 	m.rows = ctx->d_mesh; m.nb = ctx->model.nb;
-	for (int b = 0; b <= m.nb; b++) m.tri_off[b] = ctx->mesh_off[b];
-	for (int b = 0; b < m.nb; b++) { m.rad[b] = ctx->mesh_rad[b]; for (int i = 0; i < 3; i++) m.com[3 * b + i] = ctx->h_bodyc[(size_t)b * HT_BC + HT_BC_COM + i]; }
+	ht_mesh_args(ctx, m.com, m.tri_off);
+	for (int b = 0; b < m.nb; b++) m.rad[b] = ctx->mesh_rad[b];
 	rc_launch_frames(w, h, B, [&](int blocks, int f0, int groups) { hipLaunchKernelGGL(k_render_mesh, dim3(blocks), dim3(RC_THREADS), 0, s, m, d_poses, d_cams, w, h, far, pixel_offset, f0, groups, d_depth, d_body); });
 	HIPCHK(ctx, hipGetLastError());
 	return HT_OK;

@@ -400,7 +400,7 @@ int ht_model_hitcheck(const ht_model *m, const float *poses, const float *v0, co
  *                    definition ht_render_mesh_depth equals bit for bit.  pixel_offset in [0, 1]: 0 is FakeDepth's convention, 0.5 where OpenGL samples.
  *                    body (optional) [h][w], -1 = background.  cam12: focal, principal point and depth_scale are used.
  * ht_model_scale     replaces  PhysModel::scale (physmodel.h:304-319) for this view's geometry (hull vertices, plane offsets, sdmeshes, centres of mass),
- *                    with ht_scale's operations: a host model and a context scaled alike render the same bits. */
+ *                    by the function ht_scale applies to a context's model: a host model and a context scaled alike render the same bits. */
 int ht_model_hitcheck_mesh(const ht_model *m, const float *poses, const float *v0, const float *v1, float *impact3, float *normal3, int *body, int *tri);
 int ht_model_render_mesh(const ht_model *m, const float *poses, const float *cam12, int w, int h, float far, float pixel_offset, uint16_t *depth, int8_t *body);
 int ht_model_scale(ht_model *m, float s);
