@@ -310,11 +310,10 @@ extern "C" int ht_model_render_mesh(const ht_model *m, const float *poses, const
 // The forward z-buffer rasteriser of the same meshes (the definition is in include/ht_mi355x.h and, per triangle and pixel, in ht_raster.hpp):
 // a plain loop over bodies, triangles and the pixels of each triangle's own rectangle.  The smallest count wins a pixel, the first in (body, triangle) order on equal
 // counts.  This is the definition ht_raster_mesh_depth is held to.
-extern "C" int ht_model_raster_mesh(const ht_model *m, const float *poses, const float *cam12, int w, int h, float far, float pixel_offset, uint16_t *depth, int8_t *body)
+// one hand's layer: best [h][w] the winning counts (65536: not covered), who [h][w] the winning bodies (-1), through the principal point (px, py)
+static void raster_layer(const ht_model *m, const float *poses, float fx, float fy, float px, float py, float ds, int w, int h, float far, float pixel_offset, std::vector<int> &best, std::vector<int> &who)
 {
-	if (!m || !poses || !cam12 || !depth || w < 1 || h < 1 || w > 4096 || h > 4096 || !(far > 0.0f) || !(pixel_offset >= 0.0f && pixel_offset <= 1.0f)) return HT_ERR_ARG;
-	const float fx = cam12[0], fy = cam12[1], px = cam12[2], py = cam12[3], ds = cam12[4];
-	std::vector<int> best((size_t)w * h, 65536), who((size_t)w * h, -1);
+	best.assign((size_t)w * h, 65536); who.assign((size_t)w * h, -1);
 	for (int b = 0; b < m->bodies(); b++)
 	{
 		const float *p = poses + 7 * b, *com = m->com(b);
@@ -337,11 +336,68 @@ extern "C" int ht_model_raster_mesh(const ht_model *m, const float *poses, const
 			}
 		}
 	}
+}
+static bool raster_args_ok(const void *m, const void *poses, const void *cam12, const void *depth, int w, int h, float far, float pixel_offset)
+{
+	return m && poses && cam12 && depth && w >= 1 && h >= 1 && w <= 4096 && h <= 4096 && far > 0.0f && pixel_offset >= 0.0f && pixel_offset <= 1.0f;
+}
+extern "C" int ht_model_raster_mesh(const ht_model *m, const float *poses, const float *cam12, int w, int h, float far, float pixel_offset, uint16_t *depth, int8_t *body)
+{
+	if (!raster_args_ok(m, poses, cam12, depth, w, h, far, pixel_offset)) return HT_ERR_ARG;
+	const float ds = cam12[4];
+	std::vector<int> best, who;
+	raster_layer(m, poses, cam12[0], cam12[1], cam12[2], cam12[3], ds, w, h, far, pixel_offset, best, who);
 	const unsigned short bg = (unsigned short)(far / ds);
 	for (size_t o = 0; o < best.size(); o++)
 	{
 		depth[o] = who[o] >= 0 ? (unsigned short)best[o] : bg;
 		if (body) body[o] = (int8_t)who[o];
+	}
+	return HT_OK;
+}
+
+// A scene of H hands in one z-buffer (the definition is in include/ht_mi355x.h): the layer of every instance that is present, a left one from its
+// mirrored pose through the mirrored principal point and read at the flipped column (ht_raster.hpp), then the smallest count per pixel, the lowest instance on equal
+// counts, over the background frame.  This is the definition ht_raster_scene_depth is held to.
+extern "C" int ht_model_raster_scene(const ht_model *m, const float *poses, const uint8_t *hands, int H, const float *cam12, int w, int h, float far, float pixel_offset,
+                                     const uint16_t *bg, uint16_t *depth, int8_t *hand, int8_t *body, int32_t *visible)
+{
+	if (!raster_args_ok(m, poses, cam12, depth, w, h, far, pixel_offset) || H < 1 || H > HT_SCENE_MAX_HANDS) return HT_ERR_ARG;
+	const int nb = m->bodies();
+	if (!rz_scene_fits(H, m->rec.mesh_off[nb])) { const_cast<ht_model *>(m)->err = "ht_model_raster_scene: instances times mesh triangles exceed 65535"; return HT_ERR_STATE; }
+	const size_t npx = (size_t)w * h, db = npx * sizeof(uint16_t);
+	// bg == depth exactly composes in place (a pixel is read, then written); any other overlap of an output with a buffer of the call is refused
+	const struct { const void *p; size_t n; } buf[7] = { { depth, db }, { hand, npx }, { body, npx }, { visible, (size_t)H * sizeof(int32_t) }, { bg == depth ? nullptr : bg, db },
+	                                                     { poses, (size_t)H * nb * 7 * sizeof(float) }, { cam12, 12 * sizeof(float) } };
+	for (int i = 0; i < 4; i++) for (int j = i + 1; j < 7; j++)
+		if (buf[i].p && buf[j].p && (uintptr_t)buf[i].p < (uintptr_t)buf[j].p + buf[j].n && (uintptr_t)buf[j].p < (uintptr_t)buf[i].p + buf[i].n) return HT_ERR_ARG;
+	const float fx = cam12[0], fy = cam12[1], px = cam12[2], py = cam12[3], ds = cam12[4];
+	std::vector<int> cnt(npx, 65536), inst(npx, -1), bod(npx, -1), best, who;
+	std::vector<float> mp((size_t)nb * 7);
+	for (int i = 0; i < H; i++)
+	{
+		const unsigned char flag = hands ? hands[i] : 0;
+		if (rz_scene_absent(flag)) continue;
+		const bool left = rz_scene_left(flag);
+		const float *p = poses + (size_t)i * nb * 7;
+		if (left) { for (int b = 0; b < nb; b++) rz_mirror_pose(p + 7 * b, &mp[(size_t)7 * b]); p = mp.data(); }
+		raster_layer(m, p, fx, fy, left ? rz_mirror_px(px, w, pixel_offset) : px, py, ds, w, h, far, pixel_offset, best, who);
+		for (int y = 0; y < h; y++) for (int x = 0; x < w; x++)
+		{
+			const size_t o = (size_t)y * w + x, l = (size_t)y * w + rz_scene_column(x, w, left);      // the layer is read at the flipped column
+			if (who[l] >= 0 && best[l] < cnt[o]) { cnt[o] = best[l]; inst[o] = i; bod[o] = who[l]; }
+		}
+	}
+	const unsigned short none = (unsigned short)(far / ds);
+	if (visible) for (int i = 0; i < H; i++) visible[i] = 0;
+	for (size_t o = 0; o < npx; o++)
+	{
+		const unsigned short bgv = bg ? bg[o] : none;
+		const bool on = inst[o] >= 0 && rz_scene_wins(cnt[o], bg != nullptr, bgv);
+		depth[o] = on ? (unsigned short)cnt[o] : bgv;
+		if (hand) hand[o] = (int8_t)(on ? inst[o] : -1);
+		if (body) body[o] = (int8_t)(on ? bod[o] : -1);
+		if (on && visible) visible[inst[o]]++;
 	}
 	return HT_OK;
 }

@@ -1,6 +1,7 @@
 // ht_raster.hpp -- the mesh rasteriser's definition, one triangle and one pixel at a time (include/ht_mi355x.h: ht_model_raster_mesh).  The host's plain loop
 // (ht_model_host.hip) and the kernel (ht_raster_mesh.hip) both call these, so each evaluates the same float expressions in the same order and the same exact
-// integers; tests/mesh_raster_ref.py restates them in numpy.
+// integers; tests/mesh_raster_ref.py restates them in numpy.  The scene call (ht_model_raster_scene, ht_raster_scene.hip) adds the pieces at the end: a left
+// instance's pose, principal point and column, the limits and the composite rule (tests/scene_raster_ref.py).
 //
 // Screen coordinates are snapped to 1/256 pixel: |sx|, |sy| < 2^20 gives |X|, |Y| < 2^28, every difference below fits 32 bits and every product 64.
 #pragma once
@@ -65,3 +66,21 @@ HT_HD int rz_count(const rz_tri &T, float rx, float ry, float far, float ds)
 	if (!rz_finite(c) || !(z >= HT_RASTER_NEAR && z < far) || !(c >= 0.0f && c < 65536.0f)) return -1;
 	return (int)(unsigned short)c;
 }
+
+// ---- scenes of several hands (ht_model_raster_scene) ----
+HT_HD bool rz_scene_absent(unsigned char flag) { return flag == HT_SCENE_ABSENT; }
+HT_HD bool rz_scene_left(unsigned char flag) { return flag != 0 && flag != HT_SCENE_ABSENT; }
+// H instances of a model with T mesh triangles: the winner's index i * T + triangle must stay below 65535 (0xffff is "nothing yet" beside the count 0xffff)
+HT_HD bool rz_scene_fits(int H, int T) { return H >= 1 && H <= HT_SCENE_MAX_HANDS && T >= 0 && (long long)H * T <= 65535; }
+// a left instance's pose as the definition takes it: the sign bits of px, qy, qz flipped (ht_mirror_poses); negation is the sign bit's flip, for -0 and NaN too
+HT_HD void rz_mirror_pose(const float *p, float *o) { o[0] = -p[0]; o[1] = p[1]; o[2] = p[2]; o[3] = p[3]; o[4] = -p[4]; o[5] = -p[5]; o[6] = p[6]; }
+// its principal point: pixel x samples x + off and its mirror pixel w-1-x samples w-1-x + off, so cx' = (w-1) + 2 off - cx; at off 0 the bits of ht_mirror_cams
+HT_HD float rz_mirror_px(float cx, int w, float off)
+{
+	const float m = (float)(w - 1) - cx;
+	return off == 0.0f ? m : m + (off + off);
+}
+// column x of an instance's layer is this column of the scene
+HT_HD int rz_scene_column(int x, int w, bool left) { return left ? w - 1 - x : x; }
+// the composite: is the winner's count written over the background count bgv?  (has_bg false: no background frame was given)
+HT_HD bool rz_scene_wins(int count, bool has_bg, unsigned short bgv) { return !has_bg || bgv == 0 || count <= (int)bgv; }

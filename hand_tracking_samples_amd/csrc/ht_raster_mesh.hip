@@ -10,35 +10,7 @@
 //              its pixel rectangle clipped to the band; a small rectangle is walked by the lane alone, a large one (RZ_BIG pixels or more: a hand close
 //              to the camera) by the whole wave, one column per lane
 //   write-out  the band is contiguous in the frame: four pixels per thread as one 8-byte depth store and one 4-byte body store, where the alignment allows
-#include <string.h>
-#include "ht_render_common.hpp"
-#include "ht_raster.hpp"
-
-#define RZ_THREADS 256
-#define RZ_PIX 19200            // pixels of a band's z-buffer: 76800 bytes of LDS, two blocks per CU (320 x 60, 640 x 30, 4096 x 4)
-#define RZ_BIG 64               // rectangles of this many pixels or more are walked by the wave
-#define RZ_NONE 0xffffffffu
-
-struct rz_model
-{
-	const float4 *rows;         // [t][4]: p0 p1 p2 plane (the plane is not read here)
-	int nb, ntri;
-	int tri_off[HT_MAXNB + 1];
-	float com[HT_MAXNB * 3];
-};
-
-__host__ __device__ __forceinline__ int rz_band_rows(int w, int h)      // rows per band: as few bands as fit RZ_PIX, of equal height
-{
-	const int most = RZ_PIX / w, bands = (h + most - 1) / most;
-	return (h + bands - 1) / bands;
-}
-
-__device__ __forceinline__ int rz_body_of(const rz_model &M, int k)
-{
-	int b = 0;
-	for (int i = 1; i < M.nb; i++) b += k >= M.tri_off[i] ? 1 : 0;
-	return b;
-}
+#include "ht_raster_band.hpp"
 
 // pixel (x, y) of the band (row y0 first) against triangle `key16`
 __device__ __forceinline__ void rz_pixel(unsigned *zb, const rz_tri &T, int x, int y, int y0, int w, float fx, float fy, float px, float py, float off, float F, float ds, unsigned key16)
@@ -152,10 +124,7 @@ extern "C" int ht_raster_mesh_depth_dev(ht_ctx *ctx, const float *d_poses, const
 	{ const int r = rz_check_args(ctx, d_poses, d_cams, d_depth, w, h, far, pixel_offset, B); if (r) return r; }
 	if (B == 0) return HT_OK;
 	hipStream_t s = ht_user_stream(ctx, stream);
-	rz_model m;
-	memset(&m, 0, sizeof m);
-	m.rows = ctx->d_mesh; m.nb = ctx->model.nb;
-	ht_mesh_args(ctx, m.com, m.tri_off); m.ntri = m.tri_off[m.nb];
+	const rz_model m = rz_model_of(ctx);
 	const int rows = rz_band_rows(w, h), bands = (h + rows - 1) / rows;
 	const int per = INT_MAX / bands;      // frames per launch (grid size limit)
 	for (int f0 = 0; f0 < B; f0 += per)

@@ -19,6 +19,7 @@ LABELS_SIDE128 = 2            # HT_LABELS_SIDE128
 SENSOR_IVY, SENSOR_DS4 = 0, 1 # HT_SENSOR_IVY, HT_SENSOR_DS4
 JOINTS_COM_POSES = 1          # HT_JOINTS_COM_POSES
 SAMPLE_ENHANCED = 2           # HT_SAMPLE_ENHANCED
+SCENE_RIGHT, SCENE_LEFT, SCENE_ABSENT, SCENE_MAX_HANDS = 0, 1, 255, 4      # HT_SCENE_RIGHT, any value but 0 and 255, HT_SCENE_ABSENT, HT_SCENE_MAX_HANDS
 SPLIT_RIGHT_IS_LOW_X, SPLIT_MIRROR_LEFT = 1, 2      # HT_SPLIT_RIGHT_IS_LOW_X, HT_SPLIT_MIRROR_LEFT
 SPLIT_MODEL_ALWAYS, SPLIT_MODEL_MERGED, SPLIT_USER_POSES = 0, 1, 4      # HT_SPLIT_MODEL_ALWAYS, HT_SPLIT_MODEL_MERGED, HT_SPLIT_USER_POSES
 KP_COM_POSES = 1              # HT_KP_COM_POSES
@@ -39,6 +40,7 @@ SYMBOLS = (
     "ht_cnn_opt_reset_sized", "ht_cnn_opt_state_get_sized", "ht_cnn_opt_state_set_sized", "ht_cnn_opt_last_sized", "ht_cnn_train_opt_sized_dev",
     "ht_model_open", "ht_model_close", "ht_model_error", "ht_model_counts", "ht_model_body", "ht_model_body_mesh", "ht_model_body_sdmesh", "ht_model_hitcheck", "ht_model_hitcheck_mesh", "ht_model_render_mesh", "ht_model_scale", "ht_render_mesh_depth", "ht_render_mesh_depth_dev",
     "ht_model_raster_mesh", "ht_raster_mesh_depth", "ht_raster_mesh_depth_dev",
+    "ht_model_raster_scene", "ht_raster_scene_depth", "ht_raster_scene_depth_dev",
     "ht_tracker_reset", "ht_get_state", "ht_set_state", "ht_get_tracker_flags", "ht_set_tracker_flags", "ht_update_sync", "ht_update_dev", "ht_update_frames_sync", "ht_update_frames_dev", "ht_update_direct_sync", "ht_update_direct_dev", "ht_update_cnn_model_sync", "ht_get_cnn_results", "ht_get_cnn_layers", "ht_get_cnn_layers_sized", "ht_frames_overflow", "ht_reserve_points", "ht_point_capacity", "ht_capacity_events", "ht_segment_vr", "ht_segment_vr_dev", "ht_segment_vr_supported", "ht_segment_vr_sized", "ht_segment_vr_sized_dev", "ht_update_frames_sized_sync", "ht_update_frames_sized_dev", "ht_render_depth", "ht_render_depth_dev", "ht_slowfit", "ht_set_points", "ht_fit_rows", "ht_physics_update",
     "ht_stage_prepare", "ht_stage_decode", "ht_stage_fit_error", "ht_stage_cloud_rows", "ht_stage_contacts", "ht_stage_fit", "ht_debug_contact_plan",
     "ht_stage_multistep", "ht_stage_multistep_range", "ht_stage_scratch_unibody", "ht_stage_chamber", "ht_profile_enable", "ht_profile_read", "ht_debug_solve_stats", "ht_debug_contact_stats", "ht_debug_solver_build", "ht_debug_reset_flags", "ht_debug_reset_organisation", "ht_update_passes_sync", "ht_job_start", "ht_job_poll", "ht_job_wait", "ht_job_collect", "ht_debug_contact_kernel", "ht_debug_contact_order", "ht_debug_rank_desc", "ht_contact_capacity", "ht_debug_solve_tables", "ht_debug_solve_tables_header", "ht_debug_train_buffers",
@@ -239,6 +241,10 @@ def load(build_if_missing=True):
     L.ht_raster_mesh_depth.argtypes = L.ht_render_mesh_depth.argtypes
     L.ht_raster_mesh_depth_dev.argtypes = L.ht_render_mesh_depth_dev.argtypes
     L.ht_model_raster_mesh.argtypes = L.ht_model_render_mesh.argtypes
+    i8p, i32p_ = C.POINTER(C.c_int8), C.POINTER(C.c_int32)
+    L.ht_model_raster_scene.argtypes = [vp, fp, C.POINTER(C.c_uint8), C.c_int, fp, C.c_int, C.c_int, C.c_float, C.c_float, u16p, u16p, i8p, i8p, i32p_]
+    L.ht_raster_scene_depth.argtypes = [vp, fp, C.POINTER(C.c_uint8), C.c_int, fp, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int, u16p, u16p, i8p, i8p, i32p_]
+    L.ht_raster_scene_depth_dev.argtypes = [vp, vp, vp, C.c_int, vp, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int, vp, vp, vp, vp, vp, vp]
     L.ht_model_scale.argtypes = [vp, C.c_float]
     L.ht_profile_read.argtypes = [vp, C.c_int, C.c_int, C.c_char_p, C.c_int, fp, ip, ip]
     L.ht_debug_solve_stats.argtypes = [vp, C.c_int, fp, C.c_int]
@@ -917,6 +923,32 @@ class Context:
         """ht_raster_mesh_depth_dev: device pointers, asynchronous on `stream`."""
         self._chk(self.L.ht_raster_mesh_depth_dev(self.h, d_poses, d_cams, int(w), int(h), float(far), float(pixel_offset), int(B), d_depth, d_body, stream))
 
+    def raster_scene_depth(self, poses, cams, w, h, hands=None, far=4.0, pixel_offset=0.0, bg=None, want_hand=True, want_body=True, want_visible=True, in_place=False):
+        """Scenes of H hands a frame, each right or left, in one z-buffer pass (ht_raster_scene_depth), bit-identical to HostModel.raster_scene: poses [B,H,nb,7],
+        cameras [B,12], hands u8[B,H] (SCENE_RIGHT, SCENE_ABSENT, anything else left; None: all right), bg u16[B,h,w] or None -> a dict of depth u16[B,h,w] and, as asked
+        for, hand int8[B,h,w], body int8[B,h,w], visible int32[B,H].  in_place: bg itself is the depth buffer (bg == depth) and is returned composed."""
+        poses = _c(poses, np.float32); B, H = poses.shape[0], poses.shape[1]
+        poses = poses.reshape(B, H, self.nb, POSE); cams = _c(cams, np.float32).reshape(B, CAM)
+        hands = None if hands is None else _c(hands, np.uint8).reshape(B, H)
+        bg = None if bg is None else _c(bg, np.uint16).reshape(B, int(h), int(w))
+        depth = bg if (in_place and bg is not None) else np.empty((B, int(h), int(w)), np.uint16)
+        hand = np.empty((B, int(h), int(w)), np.int8) if want_hand else None
+        body = np.empty((B, int(h), int(w)), np.int8) if want_body else None
+        visible = np.empty((B, H), np.int32) if want_visible else None
+        u16p, i8p = C.POINTER(C.c_uint16), C.POINTER(C.c_int8)
+        self._chk(self.L.ht_raster_scene_depth(self.h, _f(poses), hands.ctypes.data_as(C.POINTER(C.c_uint8)) if hands is not None else None, H, _f(cams), int(w), int(h), float(far), float(pixel_offset), B,
+                                               bg.ctypes.data_as(u16p) if bg is not None else None, depth.ctypes.data_as(u16p), hand.ctypes.data_as(i8p) if want_hand else None,
+                                               body.ctypes.data_as(i8p) if want_body else None, _i(visible) if want_visible else None))
+        out = dict(depth=depth)
+        if want_hand: out["hand"] = hand
+        if want_body: out["body"] = body
+        if want_visible: out["visible"] = visible
+        return out
+
+    def raster_scene_depth_dev(self, d_poses, d_hands, H, d_cams, w, h, far, pixel_offset, B, d_bg, d_depth, d_hand=None, d_body=None, d_visible=None, stream=None):
+        """ht_raster_scene_depth_dev: device pointers (d_hands, d_bg and the label outputs may be None), asynchronous on `stream`; d_bg == d_depth composes in place."""
+        self._chk(self.L.ht_raster_scene_depth_dev(self.h, d_poses, d_hands, int(H), d_cams, int(w), int(h), float(far), float(pixel_offset), int(B), d_bg, d_depth, d_hand, d_body, d_visible, stream))
+
     # -- joint coordinates (ht_mi355x.h "joint coordinates"): c = (s.x, s.y, t.z) per joint; com_poses: centre-of-mass poses instead of user poses
     def joint_coords(self, poses, com_poses=False, want_gaps=False):
         """poses [B,nb,7] -> coords [B,nj,3] (and the joints' anchor gaps [B,nj] with want_gaps)."""
@@ -1531,6 +1563,21 @@ class HostModel:
         if self.L.ht_model_raster_mesh(self.m, _f(poses), _f(cam), int(w), int(h), float(far), float(pixel_offset), depth.ctypes.data_as(C.POINTER(C.c_uint16)), body.ctypes.data_as(C.POINTER(C.c_int8))):
             raise HTError("ht_model_raster_mesh: bad argument")
         return depth, body
+
+    def raster_scene(self, poses, cam, w, h, hands=None, far=4.0, pixel_offset=0.0, bg=None, in_place=False):
+        """one frame of the scene's definition (ht_model_raster_scene): poses [H,nb,7], hands u8[H] or None, bg u16[h,w] or None ->
+        (depth u16[h,w], hand int8[h,w], body int8[h,w], visible int32[H]).  in_place: bg itself is composed and returned as depth."""
+        poses = _c(poses, np.float32); H = poses.shape[0]; cam = _c(cam, np.float32)
+        hands = None if hands is None else _c(hands, np.uint8).reshape(H)
+        bg = None if bg is None else _c(bg, np.uint16).reshape(int(h), int(w))
+        depth = bg if (in_place and bg is not None) else np.empty((int(h), int(w)), np.uint16)
+        hand = np.empty((int(h), int(w)), np.int8); body = np.empty((int(h), int(w)), np.int8); visible = np.empty(H, np.int32)
+        u16p, i8p = C.POINTER(C.c_uint16), C.POINTER(C.c_int8)
+        r = self.L.ht_model_raster_scene(self.m, _f(poses), hands.ctypes.data_as(C.POINTER(C.c_uint8)) if hands is not None else None, H, _f(cam), int(w), int(h), float(far), float(pixel_offset),
+                                         bg.ctypes.data_as(u16p) if bg is not None else None, depth.ctypes.data_as(u16p), hand.ctypes.data_as(i8p), body.ctypes.data_as(i8p), _i(visible))
+        if r:
+            raise HTError("ht_model_raster_scene: status %d" % r)
+        return depth, hand, body, visible
 
 
 Model = HostModel      # the name the C ABI uses (ht_model): Model.mirror() is ht_model_mirror

@@ -687,6 +687,30 @@ struct HandTracker                                                              
 	}
 	Image<unsigned short> render_mesh_raster(const std::vector<Pose> &poses, const DCamera &cam, float far = 4.0f, float pixel_offset = 0.0f) const
 	{ return render_mesh_raster(std::vector<std::vector<Pose>>{ poses }, cam, far, pixel_offset)[0]; }
+	// Addition, not a reference name: one frame of up to HT_SCENE_MAX_HANDS hands, each right or left, in one z-buffer pass over an optional background frame
+	// (ht_raster_scene_depth).  hands: (centre-of-mass poses, left?) per instance, a left hand's poses as the camera sees them (what GetPose returns with left_hand
+	// set).  background: an image of cam's dimensions, or one without a raster for none.  hand and body are -1 where no hand is written.
+	struct Scene { Image<unsigned short> depth; std::vector<signed char> hand, body; std::vector<int> visible; };
+	Scene render_scene(const std::vector<std::pair<std::vector<Pose>, bool>> &hands, const DCamera &cam, float far = 4.0f, float pixel_offset = 0.0f,
+	                   const Image<unsigned short> &background = Image<unsigned short>()) const
+	{
+		const int H = (int)hands.size(), w = cam.dim().x, h = cam.dim().y;
+		const size_t n = (size_t)w * h;
+		if (!background.raster.empty() && background.raster.size() != n) throw std::runtime_error("render_scene: the background does not match the camera's dimensions");
+		std::vector<float> p7; p7.reserve((size_t)H * nb_ * HT_POSE);
+		std::vector<uint8_t> flags;
+		for (auto &hd : hands)
+		{
+			if ((int)hd.first.size() != nb_) throw std::runtime_error("render_scene: one pose per body");
+			const std::vector<float> f = flat(hd.first); p7.insert(p7.end(), f.begin(), f.end());
+			flags.push_back(hd.second ? 1 : HT_SCENE_RIGHT);
+		}
+		float c[HT_CAM]; cam12(cam, c);
+		Scene s; s.depth = Image<unsigned short>(cam); s.hand.resize(n); s.body.resize(n); s.visible.assign((size_t)(H > 0 ? H : 0), 0);
+		check(ctx_, ht_raster_scene_depth(ctx_, p7.data(), flags.data(), H, c, w, h, far, pixel_offset, 1, background.raster.empty() ? nullptr : background.raster.data(), s.depth.raster.data(),
+		                                  (int8_t *)s.hand.data(), (int8_t *)s.body.data(), (int32_t *)s.visible.data()));
+		return s;
+	}
 	// Additions, not reference names (ht_mi355x.h "tracking accuracy").  keypoints: where the hand of the latest update is in `image` -- the points of a built-in table in
 	// the poses' frame, in pixels of image.cam, and their visibility against the frame (0 visible, 1 occluded, 2 nothing there, 3 outside the image, 4 behind the camera;
 	// the tolerances in metres).  What the reference's overlay computes per point (handtrack.h:632-634).  With left_hand set the points are the left hand's.

@@ -422,6 +422,28 @@ int ht_model_scale(ht_model *m, float s);
  *                    in double, on the same pixels: counts differ by at most 1 where both pick the same triangle (DESIGN section 35 has the measured shares). */
 #define HT_RASTER_NEAR 0.01f   /* metres */
 int ht_model_raster_mesh(const ht_model *m, const float *poses, const float *cam12, int w, int h, float far, float pixel_offset, uint16_t *depth, int8_t *body);
+/* Scenes of several hands, each right or left, in one z-buffer over an optional background frame (an addition).
+ * ht_model_raster_scene   one w x h frame of H instances.  poses [H][nb][7]: centre-of-mass poses as ht_model_raster_mesh takes them; a left instance's are the left
+ *                    hand's as this camera sees it (what ht_mirror_poses makes of canonical ones).  hands [H] (uint8): HT_SCENE_RIGHT, HT_SCENE_ABSENT (the instance is
+ *                    skipped), any other value left ("nonzero = left", as everywhere); NULL: all right.  cam12, far, pixel_offset as ht_model_raster_mesh.
+ *                      layer     of a right instance i: ht_model_raster_mesh's frame of poses[i] through cam12, word for word.  Of a left one: the same definition applied
+ *                                to mirror(poses[i]) (the sign bits of px, qy, qz flipped) with the principal point cx' = ((float)(w-1) - cx) + (pixel_offset +
+ *                                pixel_offset), the second addition skipped when pixel_offset == 0 (cx' then has ht_mirror_cams' bits); the layer is read at column
+ *                                w-1-x.  Pixel x samples x + o and its mirror pixel w-1-x samples w-1-x + o, hence w-1 + 2o - cx: the layer equals the frame of the
+ *                                x-negated meshes (ht_model_mirror) through cam12, which the plain ht_mirror_cams camera misses by one pixel at o = 0.5
+ *                      winner    among the instances whose layer covers the pixel (body != -1): the smallest count, the lowest instance index on equal counts; within an
+ *                                instance the (body, triangle) order of ht_model_raster_mesh
+ *                      bg        [h][w] (optional): the winner is written iff bg == 0 or count <= bg, otherwise depth = bg and hand = body = -1; no covering instance:
+ *                                depth = bg, zeros included.  Without bg: (uint16)(far / depth_scale), as ht_model_raster_mesh.  bg == depth exactly composes in place
+ *                      outputs   depth [h][w]; optional: hand [h][w] the winner's instance index, body [h][w] its body (both -1 where no hand is written), visible [H] the
+ *                                number of pixels each instance is written on
+ *                    H in [1, HT_SCENE_MAX_HANDS] (HT_ERR_ARG); H times the model's mesh triangles <= 65535 (HT_ERR_STATE; the stock hands have 6016 and 8896); buffers
+ *                    that overlap, other than bg == depth, are HT_ERR_ARG; the other arguments as ht_model_raster_mesh. */
+#define HT_SCENE_RIGHT 0
+#define HT_SCENE_ABSENT 255
+#define HT_SCENE_MAX_HANDS 4
+int ht_model_raster_scene(const ht_model *m, const float *poses, const uint8_t *hands, int H, const float *cam12, int w, int h, float far, float pixel_offset,
+                          const uint16_t *bg, uint16_t *depth, int8_t *hand, int8_t *body, int32_t *visible);
 
 /* ---- segmentation: the step before the tracker for full-size frames --------------------------------------------------
  * ht_segment_vr       replaces  Image<unsigned short> HandSegmentVR(const Image<unsigned short> &depth, int entry_options = 0xF,
@@ -477,6 +499,18 @@ int ht_render_mesh_depth_dev(ht_ctx *ctx, const float *d_poses, const float *d_c
  * ht_raster_mesh_depth_dev the same on device buffers, asynchronous on `stream`. */
 int ht_raster_mesh_depth(ht_ctx *ctx, const float *poses, const float *cams, int w, int h, float far, float pixel_offset, int B, uint16_t *depth, int8_t *body);
 int ht_raster_mesh_depth_dev(ht_ctx *ctx, const float *d_poses, const float *d_cams, int w, int h, float far, float pixel_offset, int B, uint16_t *d_depth, int8_t *d_body, void *stream);
+/* ht_raster_scene_depth    ht_model_raster_scene (above, where the definition is) for B frames, bit-identical to it on every output, with the context's model as
+ *                     ht_create built it and ht_scale left it: poses [B][H][nb][7], hands [B][H] (optional), cams [B][12], bg [B][h][w] (optional) -> depth [B][h][w] and,
+ *                     each optional, hand [B][h][w], body [B][h][w], visible [B][H].  One z-buffer pass: every band of a frame is cleared and written once, whatever H.
+ *                     Argument rules and return codes are ht_raster_mesh_depth's; in addition H outside [1, HT_SCENE_MAX_HANDS] is HT_ERR_ARG, H times the model's mesh
+ *                     triangles above 65535 HT_ERR_STATE, and any overlap among the buffers HT_ERR_ARG, except bg == depth exactly (in-place composition: each pixel is
+ *                     read and then written by one thread).  B is not bounded by max_batch; B = 0 does nothing.  Deterministic: atomic minima of (count, instance,
+ *                     triangle), integer atomic adds for visible.
+ * ht_raster_scene_depth_dev the same on device buffers (hands included), asynchronous on `stream`; it zeroes visible on the stream before the kernel adds to it. */
+int ht_raster_scene_depth(ht_ctx *ctx, const float *poses, const uint8_t *hands, int H, const float *cams, int w, int h, float far, float pixel_offset, int B, const uint16_t *bg,
+                          uint16_t *depth, int8_t *hand, int8_t *body, int32_t *visible);
+int ht_raster_scene_depth_dev(ht_ctx *ctx, const float *d_poses, const uint8_t *d_hands, int H, const float *d_cams, int w, int h, float far, float pixel_offset, int B, const uint16_t *d_bg,
+                              uint16_t *d_depth, int8_t *d_hand, int8_t *d_body, int32_t *d_visible, void *stream);
 
 /* ---- joint coordinates (an addition: the reference decomposes every joint on every solver pass and never hands the result out) ----
  * Joint j of the model (parent body rbi0 at orientation q0, child rbi1 at q1, jointframe F, anchors p0 / p1) has the coordinates c = (s.x, s.y, t.z) of

@@ -4,6 +4,7 @@ render -> ht_update_frames_dev at 1024 frames with a new batch of poses every st
     python tools/bench_render.py [--steps 20] [--warmup 3] [--out profiles/r07_render.json] [--quick]
     python tools/bench_render.py --mesh      the mesh ray cast beside the hulls (profiles/r08_render_mesh.json)
     python tools/bench_render.py --raster    the mesh rasteriser beside the ray cast, the hulls and the tracking step (profiles/r26_raster_mesh.json)
+    python tools/bench_render.py --scene     the scene call beside its composition from tested calls, the two-hand update and the one-hand rasteriser (profiles/r27_raster_scene.json)
 
 Hands: the bench recording's ground truths (bench_data/frames1024.npz, 17 bones) and the 26-bone start poses of bench_data/frames5_256.npz, seen
 through the application's 320x240 camera (focal 305) or a 128x128 one (focal 163).  Empty frames: the same hands moved 10 m behind the camera."""
@@ -165,6 +166,105 @@ def main_raster(a):
         json.dump(res, f, indent=1)
         f.write("\n")
 
+def main_scene(a):
+    """--scene: ht_raster_scene_depth_dev on scenes of one right and one left hand beside the same frames composed on the device from two ht_raster_mesh_depth_dev, the three
+    mirror calls and a torch.minimum, on one stream; beside ht_update_two_hands_dev on the same scenes; and with one right hand beside ht_raster_mesh_depth_dev.  Resident
+    batches, device events, every shape warmed, five series of each leg taken in turn within one run: the median and the spread (largest minus smallest) are reported."""
+    dev = torch.device("cuda:0")
+    torch.cuda.set_device(dev)
+    s = torch.cuda.Stream(device=dev)
+    z = np.load(os.path.join(ROOT, "bench_data", "frames1024.npz"))
+    gt = z["gtpose"].astype(np.float32)
+    res = {"device": torch.cuda.get_device_name(dev), "steps": a.steps, "warmup": a.warmup, "series": 5, "scenes": [], "usage": {}}
+    for k, v in hb.resource_usage().items():
+        if "raster" in k:
+            res["usage"][k] = {x: v.get(x) for x in ("VGPRs", "SGPRs", "AGPRs", "ScratchSize", "LDS Size", "Occupancy")}
+
+    def series(legs):
+        """{name: (median, spread)} of five series, the legs in turn"""
+        t = {n: [] for n in legs}
+        for _ in range(5):
+            for n, (fn, steps) in legs.items():
+                t[n].append(time_it(fn, s, steps, 1))
+        return {n: (float(np.median(v)), float(max(v) - min(v))) for n, v in t.items()}
+
+    ctx = native.Context(M17, 1024)
+    try:
+        ctx.load_weights(W.make_cnnb()); ctx.set_params(microforce=3.0, mainthreadpasses=3); ctx.reserve_points(320 * 240 // 4)
+        for w, h, B in (((320, 240, 512),) if a.quick else ((320, 240, 512), (320, 240, 1024), (640, 480, 512))):
+            right = gt[np.arange(B) % len(gt)].copy(); right[:, :, 0] += 0.06
+            left = gt[(np.arange(B) + 300) % len(gt)].copy(); left[:, :, 0] *= -1; left[:, :, 4:6] *= -1; left[:, :, 0] -= 0.06      # the mirror image of another hand, on the other side
+            poses = np.stack([right, left], 1)
+            tp = torch.from_numpy(poses).to(dev); tr = torch.from_numpy(right).to(dev); tl = torch.from_numpy(left).to(dev); tc = torch.from_numpy(cam_of(w, h, B)).to(dev)
+            th = torch.from_numpy(np.tile(np.array([0, 1], np.uint8), (B, 1))).to(dev)
+            td = torch.empty((B, h, w), dtype=torch.int16, device=dev); tha = torch.empty((B, h, w), dtype=torch.int8, device=dev); tb = torch.empty_like(tha); tv = torch.empty((B, 2), dtype=torch.int32, device=dev)
+            ta, tm, tf, tout = (torch.empty_like(td) for _ in range(4)); tcan = torch.empty_like(tl); tmc = torch.empty_like(tc)
+
+            def scene():
+                ctx.raster_scene_depth_dev(tp.data_ptr(), th.data_ptr(), 2, tc.data_ptr(), w, h, 4.0, 0.0, B, None, td.data_ptr(), tha.data_ptr(), tb.data_ptr(), tv.data_ptr(), s.cuda_stream)
+
+            def scene_depth_only():
+                ctx.raster_scene_depth_dev(tp.data_ptr(), th.data_ptr(), 2, tc.data_ptr(), w, h, 4.0, 0.0, B, None, td.data_ptr(), None, None, None, s.cuda_stream)
+
+            def composed():
+                ctx.raster_mesh_depth_dev(tr.data_ptr(), tc.data_ptr(), w, h, 4.0, 0.0, B, ta.data_ptr(), None, s.cuda_stream)
+                ctx.mirror_poses_dev(tl.data_ptr(), 17, B, None, tcan.data_ptr(), s.cuda_stream)
+                ctx.mirror_cams_dev(tc.data_ptr(), w, B, None, tmc.data_ptr(), s.cuda_stream)
+                ctx.raster_mesh_depth_dev(tcan.data_ptr(), tmc.data_ptr(), w, h, 4.0, 0.0, B, tm.data_ptr(), None, s.cuda_stream)
+                ctx.mirror_frames_dev(tm.data_ptr(), w, h, B, None, tf.data_ptr(), s.cuda_stream)
+                with torch.cuda.stream(s):
+                    torch.minimum(ta, tf, out=tout)      # counts stay below 32768 here, so the signed minimum is the unsigned one
+
+            def one_scene():
+                ctx.raster_scene_depth_dev(tr.data_ptr(), None, 1, tc.data_ptr(), w, h, 4.0, 0.0, B, None, td.data_ptr(), None, None, None, s.cuda_stream)
+
+            def one_mesh():
+                ctx.raster_mesh_depth_dev(tr.data_ptr(), tc.data_ptr(), w, h, 4.0, 0.0, B, ta.data_ptr(), None, s.cuda_stream)
+
+            s.wait_stream(torch.cuda.current_stream(dev))
+            for fn in (scene, scene_depth_only, composed, one_scene, one_mesh):
+                for _ in range(a.warmup):
+                    fn()
+            s.synchronize()
+            scene(); composed(); s.synchronize()
+            same = bool(torch.equal(td, tout))
+            t = series({"scene": (scene, a.steps), "composed": (composed, a.steps), "scene_depth_only": (scene_depth_only, a.steps)})
+            row = {"w": w, "h": h, "B": B, "hands": "one right, one left", "scene_equals_composition": same, "hand_pixel_fraction": round(float((tha[:64] >= 0).float().mean()), 4)}
+            for n, (med, spread) in t.items():
+                row[n + "_ms"] = round(med, 4); row[n + "_spread_ms"] = round(spread, 4)
+            row["scene_minus_composed_ms"] = round(t["scene"][0] - t["composed"][0], 4)
+            row["bar_not_slower_by_more_than_ms"] = round(2 * t["composed"][1], 4)
+            row["bar_met"] = bool(t["scene"][0] - t["composed"][0] <= 2 * t["composed"][1])
+            t1 = series({"one_scene": (one_scene, a.steps), "one_mesh": (one_mesh, a.steps)})
+            row["one_right_hand_scene_ms"] = round(t1["one_scene"][0], 4); row["one_right_hand_scene_spread_ms"] = round(t1["one_scene"][1], 4)
+            row["raster_mesh_ms"] = round(t1["one_mesh"][0], 4); row["raster_mesh_spread_ms"] = round(t1["one_mesh"][1], 4)
+            row["one_hand_scene_over_raster_mesh"] = round(t1["one_scene"][0] / t1["one_mesh"][0], 4)
+            if (w, h, B) == (320, 240, 512):      # the step these frames feed: the two-hand update of the same scenes, in the same run
+                seeds = poses.reshape(2 * B, 17, 7).copy(); odd = np.arange(2 * B) % 2 == 1
+                seeds[odd, :, 0] *= -1; seeds[odd, :, 4:6] *= -1      # a left slot is seeded with the canonical pose
+                ctx.tracker_reset(seeds)
+                out = torch.empty((2 * B, 17, 7), dtype=torch.float32, device=dev); info = torch.empty((B, 2, 8), dtype=torch.int32, device=dev)
+                scene(); s.synchronize()
+
+                def update():
+                    ctx.update_two_hands_dev(64, td.data_ptr(), tc.data_ptr(), w, h, 0.17, 0, 650, 65535, 50, 3999, 0, None, B, out.data_ptr(), info.data_ptr(), s.cuda_stream)
+                update(); s.synchronize()
+                tu = series({"update": (update, max(3, a.steps // 4)), "scene": (scene, a.steps)})
+                row["update_two_hands_dev_ms"] = round(tu["update"][0], 3); row["update_two_hands_dev_spread_ms"] = round(tu["update"][1], 3)
+                row["both_hands_found_share"] = round(float((info[:, :, 0] > 0).float().mean()), 4)
+                row["scene_over_update"] = round(tu["scene"][0] / tu["update"][0], 4); row["bar_scene_over_update"] = 0.25
+            print(json.dumps(row), flush=True)
+            res["scenes"].append(row)
+            del tp, tr, tl, tc, th, td, tha, tb, tv, ta, tm, tf, tout, tcan, tmc
+    finally:
+        ctx.close()
+    res["k_raster_mesh"] = "its instructions are the parent's (only the headers its definitions sit in were rearranged), so no parent comparison was run"
+    out_path = a.out if a.out != DEFAULT_OUT else os.path.join(ROOT, "profiles", "r27_raster_scene.json")
+    os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
+    with open(out_path, "w") as f:
+        json.dump(res, f, indent=1)
+        f.write("\n")
+
 
 DEFAULT_OUT = os.path.join(ROOT, "profiles", "r07_render.json")
 
@@ -173,6 +273,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--mesh", action="store_true", help="measure ht_render_mesh_depth_dev (the subdivision surface) beside the hull renderer and the tracking step")
     ap.add_argument("--raster", action="store_true", help="measure ht_raster_mesh_depth_dev (the z-buffer rasteriser) beside the mesh ray cast, the hull renderer and the tracking step")
+    ap.add_argument("--scene", action="store_true", help="measure ht_raster_scene_depth_dev (several hands in one z-buffer pass) beside its composition from single-hand calls and the two-hand update")
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--out", default=DEFAULT_OUT)
@@ -183,6 +284,8 @@ def main():
         return main_mesh(a)
     if a.raster:
         return main_raster(a)
+    if a.scene:
+        return main_scene(a)
     dev = torch.device("cuda:0")
     torch.cuda.set_device(dev)
     s = torch.cuda.Stream(device=dev)

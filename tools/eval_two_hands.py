@@ -4,7 +4,10 @@
 The scenes are section 27's (two hands of tests/golden/poses1024.htfx, one mirrored), hull frames at 320x240; the lateral offset goes from 0.09 m down to --closest
 (default 0.04 m) and back in 5 mm steps, the poses otherwise unchanged, so the truth of every frame is known.  Per mode and frame: presence of both hands, the share
 of foreground cells whose label differs from the composition's ground truth (which solo frame supplied the cell's depth), and the mean and worst HT_KP_SKELETON error
-per hand against the truth (ht_keypoint_errors).  No figure is promised: the table is the result.  Writes profiles/r24_two_hands_accuracy.json (or --out)."""
+per hand against the truth (ht_keypoint_errors).  No figure is promised: the table is the result.  Writes profiles/r24_two_hands_accuracy.json (or --out).
+
+With --scene-render the scenes are drawn by ht_raster_scene_depth instead: both hands of a frame in one z-buffer pass on the subdivision surface the application draws
+(DESIGN section 36), and the ground truth of a cell is the call's own hand label at the cell's nearest pixel.  Writes profiles/r27_two_hands_scene_accuracy.json (or --out)."""
 import argparse
 import json
 import os
@@ -28,8 +31,11 @@ MODES = {"Blobs": None, "ModelWhenMerged": R.MERGED, "ModelAlways": R.ALWAYS}
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--closest", type=float, default=0.04, help="the smallest lateral offset of the sequence, metres")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r24_two_hands_accuracy.json"))
+    ap.add_argument("--scene-render", action="store_true", help="draw the scenes with ht_raster_scene_depth on the mesh surface (the default stays the composed hull frames)")
+    ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    if a.out is None:
+        a.out = os.path.join(ROOT, "profiles", "r27_two_hands_scene_accuracy.json" if a.scene_render else "r24_two_hands_accuracy.json")
     steps = int(round((S.SCENE_SHIFT - a.closest) / 0.005))
     shifts = [S.SCENE_SHIFT - 0.005 * i for i in range(steps + 1)]
     shifts = shifts + shifts[-2::-1]
@@ -37,12 +43,20 @@ def main():
     odd = (np.arange(n) % 2).astype(np.uint8)
     cams = np.repeat(S.SCENE_CAM[None], B, axis=0)
     c = native.Context(os.path.join(ROOT, "tests", "golden", "model_hand17.htfx"), n)
-    res = {"scenes": list(S.SCENES), "frame": "%dx%d hull frames" % (W_, H_), "lateral_offsets_m": [round(x, 3) for x in shifts], "modes": {}}
+    res = {"scenes": list(S.SCENES), "frame": ("%dx%d mesh frames of ht_raster_scene_depth" if a.scene_render else "%dx%d hull frames") % (W_, H_), "lateral_offsets_m": [round(x, 3) for x in shifts], "modes": {}}
     try:
         c.load_weights(W.make_cnnb()); c.set_params(microforce=3.0, mainthreadpasses=3)
         seq = []
         for shift in shifts:
             poses = np.stack([R.scene_poses_at(k, shift) for k in S.SCENES])
+            if a.scene_render:      # one call: the frame and, per pixel, which hand it shows
+                sc = c.raster_scene_depth(poses, cams, W_, H_, hands=np.tile(np.array([native.SCENE_RIGHT, native.SCENE_LEFT], np.uint8), (B, 1)), far=4.0, pixel_offset=0.0, want_body=False, want_visible=False)
+                truth = []
+                for b in range(B):
+                    Q, xs, ys = R.first_min(sc["depth"][b])
+                    truth.append(np.where(Q >= S.SCENE_HI, R.NONE, sc["hand"][b][ys, xs].astype(np.int64)).astype(np.uint16))
+                seq.append(dict(poses=poses, frames=sc["depth"], truth=np.stack(truth), kp=c.keypoints(poses.reshape(n, c.nb, 7), table=native.KP_SKELETON, com_poses=True, hands=odd)["xyz"]))
+                continue
             right = c.render_depth(poses[:, 0], cams, W_, H_, far=4.0).reshape(B, H_, W_)
             left = c.render_depth(mirror_ref.poses(poses[:, 1]), mirror_ref.cams(cams, W_), W_, H_, far=4.0).reshape(B, H_, W_)[:, :, ::-1]
             truth = np.stack([R.compose(right[b], left[b])[1] for b in range(B)])
