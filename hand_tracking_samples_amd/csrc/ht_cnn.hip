@@ -4,10 +4,12 @@
 // (include/handtrack.h:108-118), preceded by the depth normalisation of handtrack.h:700 and the point-cloud
 // extraction of misc_image.h:409-417 / physmodel.h:58-64 (both read the same depth tile, so one kernel does both).
 //
-//   k_prepare   u16 depth tile -> fp32 CNN input + order-preserving compacted point cloud  (HBM-bound, 8 KB in / 16 KB out per frame)
+//   k_prepare   u16 depth tile -> fp32 CNN input + order-preserving compacted point cloud  (HBM-bound, 8 KB in / 16 KB out per frame); k_prepare_frame (the cloud of a
+//               full-size frame) and k_cnn_input (the input alone) share its pieces: depth_metres, cnn_input_value, depth_in_range, deproject_point, block_prefix256
 //   k_conv1     5x5x1->16 valid conv + 4x4 max-pool + tanh as an implicit GEMM on v_mfma_f32_16x16x4_f32 (one pooling window = one 16-row tile), input rows staged in LDS
 //   k_conv2     4x4x16->64 valid conv as an implicit GEMM on v_mfma_f32_16x16x4_f32, + 2x2 max-pool + tanh
 //   k_conv12    both of them in one launch for the 64x64 net (the first layer's pooled array in LDS is the second layer's input image)
+//               -- the layers' stages are functions that the three kernels call: conv1_fragments, conv1_windows, conv2_fragments, conv2_tiles
 //   k_fc        [B,K]x[K,N]+bias (+tanh) on v_mfma_f32_32x32x2_f32, 128x64 block tile on 8 waves, double-buffered LDS, register prefetch
 //   k_fc144_pk  the last layer on a 64x144 tile (v_mfma_f32_16x16x4_f32), tiles by LDS-DMA, both operands in the instruction's order (128-bit fragment reads)
 //   k_softmax_decode   chunked softmax (cnn.h:497-511) fused with the heat-map decode (handtrack.h:218-241)
@@ -18,6 +20,26 @@
 #include "ht_device.hpp"
 
 // ------------------------------------------------------------------------------------------------- k_prepare
+// What k_prepare, k_prepare_frame and k_cnn_input make of a depth word, each stated once
+__device__ __forceinline__ float depth_metres(unsigned px, float dscale) { return (float)(int)px * dscale; }
+__device__ __forceinline__ float cnn_input_value(float d, float drangey) { return clamp_std(1.0f - (d - 0.1f) / (drangey - 0.1f), 0.0f, 1.0f); }      // handtrack.h:700
+__device__ __forceinline__ bool depth_in_range(float d, float drangey) { return d >= 0.1f && d < drangey; }                                          // FallsWithinRange misc_image.h:24
+__device__ __forceinline__ float4 deproject_point(float x, float y, float d, float fx, float fy, float cx, float cy) { return make_float4(((x - cx) / fx) * d, ((y - cy) / fy) * d, 1.0f * d, 0.0f); }      // deprojectz misc_image.h:48
+// exclusive prefix of cnt over the block's 256 threads (every thread calls it): the thread's base; total: the block's sum
+__device__ __forceinline__ int block_prefix256(int cnt, int lane, int wave, int &total)
+{
+	int incl = cnt;
+#pragma unroll
+	for (int o = 1; o < 64; o <<= 1) { int v = __shfl_up(incl, o); if (lane >= o) incl += v; }
+	__shared__ int wsum[4];
+	if (lane == 63) wsum[wave] = incl;
+	__syncthreads();
+	int base = incl - cnt;
+	for (int i = 0; i < wave; i++) base += wsum[i];
+	total = wsum[0] + wsum[1] + wsum[2] + wsum[3];
+	return base;
+}
+
 // one block per frame; thread t owns pixels [16t, 16t+16) so that a block-wide prefix sum keeps the row-major order
 __global__ __launch_bounds__(256) void k_prepare(const uint16_t *__restrict__ depth, const float *__restrict__ cams, float drangey, int fraction,
                                                   float *__restrict__ cnn_in, float4 *__restrict__ pts, int *__restrict__ npts, int cap, ht_prepare_extra x)
@@ -45,9 +67,9 @@ __global__ __launch_bounds__(256) void k_prepare(const uint16_t *__restrict__ de
 	for (int i = 0; i < 16; i++)
 	{
 		unsigned px = (w[i >> 1] >> ((i & 1) * 16)) & 0xffffu;
-		d[i] = (float)(int)px * dscale;
-		cin[i] = clamp_std(1.0f - (d[i] - 0.1f) / (drangey - 0.1f), 0.0f, 1.0f);     // handtrack.h:700
-		bool in = d[i] >= 0.1f && d[i] < drangey;                                     // FallsWithinRange misc_image.h:24
+		d[i] = depth_metres(px, dscale);
+		cin[i] = cnn_input_value(d[i], drangey);
+		bool in = depth_in_range(d[i], drangey);
 		mask |= in ? (1u << i) : 0u;
 		cnt += in;
 	}
@@ -57,15 +79,8 @@ __global__ __launch_bounds__(256) void k_prepare(const uint16_t *__restrict__ de
 #pragma unroll
 		for (int i = 0; i < 4; i++) dst[i] = make_float4(cin[4 * i], cin[4 * i + 1], cin[4 * i + 2], cin[4 * i + 3]);
 	}
-	// exclusive prefix of cnt over the 256 threads
-	int incl = cnt;
-#pragma unroll
-	for (int o = 1; o < 64; o <<= 1) { int v = __shfl_up(incl, o); if (lane >= o) incl += v; }
-	__shared__ int wsum[4];
-	if (lane == 63) wsum[wave] = incl;
-	__syncthreads();
-	int base = incl - cnt;
-	for (int i = 0; i < wave; i++) base += wsum[i];
+	int total;
+	const int base = block_prefix256(cnt, lane, wave, total);
 	if (pts)
 	{
 		int rank = base;
@@ -76,14 +91,13 @@ __global__ __launch_bounds__(256) void k_prepare(const uint16_t *__restrict__ de
 			{
 				int p = 16 * t + i;
 				float x = (float)(p & 63), y = (float)(p >> 6);
-				pts[(size_t)b * cap + rank / fraction] = make_float4(((x - cx) / fx) * d[i], ((y - cy) / fy) * d[i], 1.0f * d[i], 0.0f);   // deprojectz misc_image.h:48
+				pts[(size_t)b * cap + rank / fraction] = deproject_point(x, y, d[i], fx, fy, cx, cy);
 			}
 			rank++;
 		}
 	}
 	if (npts && t == 255)
 	{
-		int total = base + cnt;
 		int n = (total + fraction - 1) / fraction;
 		npts[b] = n < cap ? n : cap;
 	}
@@ -102,29 +116,23 @@ __global__ __launch_bounds__(256) void k_prepare_frame(const uint16_t *__restric
 	const int npx = w * h, chunk = (npx + 255) / 256, p0 = min(npx, t * chunk), p1 = min(npx, p0 + chunk);
 	const uint16_t *src = depth + (size_t)b * npx;
 	int cnt = 0;
-	for (int p = p0; p < p1; p++) { const float d = (float)(int)src[p] * dscale; cnt += (d >= 0.1f && d < drangey) ? 1 : 0; }
-	int incl = cnt;
-#pragma unroll
-	for (int o = 1; o < 64; o <<= 1) { int v = __shfl_up(incl, o); if (lane >= o) incl += v; }
-	__shared__ int wsum[4];
-	if (lane == 63) wsum[wave] = incl;
-	__syncthreads();
-	int rank = incl - cnt;
-	for (int i = 0; i < wave; i++) rank += wsum[i];
+	for (int p = p0; p < p1; p++) cnt += depth_in_range(depth_metres(src[p], dscale), drangey) ? 1 : 0;
+	int total;
+	int rank = block_prefix256(cnt, lane, wave, total);
 	for (int p = p0; p < p1; p++)
 	{
-		const float d = (float)(int)src[p] * dscale;
-		if (!(d >= 0.1f && d < drangey)) continue;
+		const float d = depth_metres(src[p], dscale);
+		if (!depth_in_range(d, drangey)) continue;
 		if (rank % fraction == 0 && rank / fraction < cap)
 		{
 			const float x = (float)(p % w), y = (float)(p / w);
-			pts[(size_t)b * cap + rank / fraction] = make_float4(((x - cx) / fx) * d, ((y - cy) / fy) * d, 1.0f * d, 0.0f);      // deprojectz misc_image.h:48
+			pts[(size_t)b * cap + rank / fraction] = deproject_point(x, y, d, fx, fy, cx, cy);
 		}
 		rank++;
 	}
 	if (t == 255)
 	{
-		const int n = (rank + fraction - 1) / fraction;
+		const int n = (total + fraction - 1) / fraction;
 		npts[b] = n < cap ? n : cap;
 		if (n > cap && overflow) atomicAdd(overflow, 1);
 	}
@@ -143,8 +151,7 @@ __global__ __launch_bounds__(256) void k_cnn_input(const uint16_t *__restrict__ 
 #pragma unroll
 	for (int k = 0; k < 8; k++)
 	{
-		const float d = (float)(int)((w[k >> 1] >> ((k & 1) * 16)) & 0xffffu) * dscale;
-		c[k] = clamp_std(1.0f - (d - 0.1f) / (drangey - 0.1f), 0.0f, 1.0f);
+		c[k] = cnn_input_value(depth_metres((w[k >> 1] >> ((k & 1) * 16)) & 0xffffu, dscale), drangey);
 	}
 	float4 *dst = reinterpret_cast<float4 *>(cnn_in + (size_t)b * npx + i);
 	dst[0] = make_float4(c[0], c[1], c[2], c[3]); dst[1] = make_float4(c[4], c[5], c[6], c[7]);
@@ -188,22 +195,12 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 // is four register maxima and two cross-lane steps, and tanh (an exponential in double) is applied once per pooled value by all threads at the end.
 // 64x64 input: IW = 64, PW = 15, PR = 15 (one block per frame; bands of 8, 5 or 3 pooled rows, which would stagger the blocks' phases, were measured: no change).  128x128 input (BASELINE configs[4]): IW = 128, PW = 31, PR = 8 -> 4 bands of
 // 36 rows (19 KB) instead of one 64 KB tile, so several blocks stay resident per CU.
-template <int IW, int PW, int PR>
-__global__ __launch_bounds__(256) void k_conv1(const float *__restrict__ cnn_in, const float *__restrict__ W1, const float *__restrict__ B1, float *__restrict__ act1)
+// The stages below are stated once: k_conv1<> and k_conv12 call the same two functions.
+// A lane's operands for a padded row stride IWP: B = weight of (tap k, channel n), A = pixel (py, px) of the window shifted by tap k; k = 4 * step + (lane >> 4)
+template <int IWP>
+__device__ __forceinline__ void conv1_fragments(const float *__restrict__ W1, const float *__restrict__ B1, int lane, float (&wreg)[7], int (&aoff)[7], float &bias)
 {
-	constexpr int TR = 4 * PR + 4, IWP = IW + 4;         // input rows a band touches, padded row stride
-	static_assert(TR <= IW && (IW % 4) == 0, "band does not fit the image");
-	__shared__ __attribute__((aligned(16))) float tile[TR * IWP];
-	__shared__ float pooled[16 * PR * PW];
-	const int b = blockIdx.x, band = blockIdx.y, t = threadIdx.x, lane = t & 63, wave = t >> 6;
-	const int row0 = 4 * PR * band;
-	const int nrows = min(TR, IW - row0);
-	const int prows = min(PR, PW - PR * band);           // pooled rows this band really has
-	const float4 *src = reinterpret_cast<const float4 *>(cnn_in + (size_t)b * IW * IW + (size_t)row0 * IW);
-	for (int i = t; i < nrows * IW / 4; i += 256) { const int r = i / (IW / 4), c4 = i % (IW / 4); *reinterpret_cast<float4 *>(tile + r * IWP + 4 * c4) = src[i]; }
-	// this lane's operands: B = weight of (tap k, channel n), A = pixel (py, px) of the window shifted by tap k; k = 4 * step + (lane >> 4)
 	const int n = lane & 15, g = lane >> 4, px = lane & 3, py = (lane >> 2) & 3;
-	float wreg[7]; int aoff[7];
 #pragma unroll
 	for (int s = 0; s < 7; s++)
 	{
@@ -211,14 +208,19 @@ __global__ __launch_bounds__(256) void k_conv1(const float *__restrict__ cnn_in,
 		wreg[s] = k < 25 ? W1[n * 25 + k] : 0.0f;        // W index = kx + 5*(ky + 5*(ic + 1*oc)), cnn.h:45-47,227
 		aoff[s] = (py + kk / 5) * IWP + px + kk % 5;
 	}
-	const float bias = B1[n];
-	__syncthreads();
-	// The window loop is bound by the SIMD's one vector issue port, not by the matrix pipe: 7 MFMAs hold the port for 56 of their 224 clocks, and everything else a window
-	// issues has to fit the rest beside three other waves' windows.  So the wave's index is read into a scalar register -- the window's coordinates and its tile address
-	// are then scalar arithmetic -- and a maximum is one v_max_f32 (a compare and a select cost three issue slots with their wait state).
+	bias = B1[n];
+}
+
+// The window loop: wave `wave` takes windows wave, wave + 4, ... of the nwin = (pooled rows) x PW windows of `tile`; lanes 0-15 store a window's maximum (before tanh) at
+// pdst[ty * PW + tx], pdst being the lane's channel.
+// The loop is bound by the SIMD's one vector issue port, not by the matrix pipe: 7 MFMAs hold the port for 56 of their 224 clocks, and everything else a window
+// issues has to fit the rest beside three other waves' windows.  So the wave's index is read into a scalar register -- the window's coordinates and its tile address
+// are then scalar arithmetic -- and a maximum is one v_max_f32 (a compare and a select cost three issue slots with their wait state).
+template <int IWP, int PW>
+__device__ __forceinline__ void conv1_windows(const float *tile, float *pdst, int nwin, int wave, int lane, const float (&wreg)[7], const int (&aoff)[7], float bias)
+{
 	const int swave = __builtin_amdgcn_readfirstlane(wave);
-	float *const pdst = pooled + n * PR * PW;
-	for (int w = swave; w < prows * PW; w += 4)
+	for (int w = swave; w < nwin; w += 4)
 	{
 		const int ty = w / PW, tx = w % PW;
 		const float *base = tile + 4 * ty * IWP + 4 * tx;
@@ -232,6 +234,25 @@ __global__ __launch_bounds__(256) void k_conv1(const float *__restrict__ cnn_in,
 		{ const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(m), __float_as_uint(m), false, false); m = max_pool(__uint_as_float(r[0]), __uint_as_float(r[1])); }
 		if (lane < 16) pdst[ty * PW + tx] = m;
 	}
+}
+
+template <int IW, int PW, int PR>
+__global__ __launch_bounds__(256) void k_conv1(const float *__restrict__ cnn_in, const float *__restrict__ W1, const float *__restrict__ B1, float *__restrict__ act1)
+{
+	constexpr int TR = 4 * PR + 4, IWP = IW + 4;         // input rows a band touches, padded row stride
+	static_assert(TR <= IW && (IW % 4) == 0, "band does not fit the image");
+	__shared__ __attribute__((aligned(16))) float tile[TR * IWP];
+	__shared__ float pooled[16 * PR * PW];
+	const int b = blockIdx.x, band = blockIdx.y, t = threadIdx.x, lane = t & 63, wave = t >> 6;
+	const int row0 = 4 * PR * band;
+	const int nrows = min(TR, IW - row0);
+	const int prows = min(PR, PW - PR * band);           // pooled rows this band really has
+	const float4 *src = reinterpret_cast<const float4 *>(cnn_in + (size_t)b * IW * IW + (size_t)row0 * IW);
+	for (int i = t; i < nrows * IW / 4; i += 256) { const int r = i / (IW / 4), c4 = i % (IW / 4); *reinterpret_cast<float4 *>(tile + r * IWP + 4 * c4) = src[i]; }
+	float wreg[7], bias; int aoff[7];
+	conv1_fragments<IWP>(W1, B1, lane, wreg, aoff, bias);
+	__syncthreads();
+	conv1_windows<IWP, PW>(tile, pooled + (lane & 15) * PR * PW, prows * PW, wave, lane, wreg, aoff, bias);
 	__syncthreads();
 	for (int i = t; i < 16 * prows * PW; i += 256)
 	{
@@ -250,27 +271,23 @@ __global__ __launch_bounds__(256) void k_conv1(const float *__restrict__ cnn_in,
 // a window's four pre-pool values into the four accumulator registers of one lane, the max-pool (cnn.h:141-148) is three register maxima, and every lane ends a tile with
 // one finished output -- tanh and the store follow at once.  (Rows in image order needed 37 KB of LDS for the pre-pool values of a 64x64-net frame, a second pass and a
 // barrier; with 51 KB per block a CU held three of the four blocks it gets at 1024 frames and ran the fourth alone: 56 us, now 14 KB per block and one round.)
-template <int IWD, int OW, int BAND>
-__global__ __launch_bounds__(256) void k_conv2(const float *__restrict__ act1, const float *__restrict__ W2p, const float *__restrict__ B2, float *__restrict__ act2)
+// The stages below are stated once: k_conv2<> and k_conv12 call the same two functions.
+// A lane's 64 weight fragments for output channel n: k-step ks holds k = 4 * ks + (lane >> 4), i.e. tap p = ks >> 2 and ic = 4 * (ks & 3) + (lane >> 4)
+__device__ __forceinline__ void conv2_fragments(const float *__restrict__ W2p, int n, int lane, float (&breg)[64])
 {
-	constexpr int IR = BAND + 3, PO = OW / 2, CH = IR * IWD, NW = (BAND / 2) * PO, MT = NW / 4;      // NW: pooling windows of the band
-	static_assert(NW % 4 == 0 && BAND % 2 == 0 && OW % 2 == 0 && OW % BAND == 0, "band must hold whole MFMA tiles of whole pooling windows");
-	__shared__ __attribute__((aligned(16))) float in[16 * CH];
-	const int b = blockIdx.x, band = blockIdx.y, t = threadIdx.x, lane = t & 63, wave = t >> 6;
-	const int oy0 = band * BAND;
-	// the band's input rows in the order the matrix instruction reads them: [position][ic & 3][ic >> 2] -- a lane takes ic = 4 * j + (lane >> 4) for the four k-steps j of a
-	// tap, so its four values are one 128-bit read (16 reads per tile, where [ic][position] took 64 values in 32 double reads)
-	for (int i = t; i < 16 * CH; i += 256) { const int ic = i / CH, r = i % CH; in[(r * 4 + (ic & 3)) * 4 + (ic >> 2)] = act1[(size_t)b * (16 * IWD * IWD) + ic * (IWD * IWD) + oy0 * IWD + r]; }
-	const int n = 16 * wave + (lane & 15);
-	float breg[64];
 #pragma unroll
 	for (int ks = 0; ks < 64; ks++) breg[ks] = W2p[(4 * ks + (lane >> 4)) * 64 + n];
-	const float bias = B2[n];
-	__syncthreads();
-	// per lane k decomposition is fixed per k-step: k = 4*ks + (lane>>4): tap p = k>>4 = ks>>2, ic = 4*(ks&3) + (lane>>4)
+}
+
+// The tile loop: MT tiles of four pooling windows each over the staged input `in` (rows of IWD positions, in [position][ic & 3][ic >> 2] order -- a lane takes
+// ic = 4 * j + (lane >> 4) for the four k-steps j of a tap, so its four values are one 128-bit read: 16 reads per tile, where [ic][position] took 64 values in 32 double
+// reads); window wo (pooled row wo / PO, column wo % PO) of the lane's channel goes to dst[wo], pooled and through tanh.
+template <int IWD, int PO, int MT>
+__device__ __forceinline__ void conv2_tiles(const float *in, const float (&breg)[64], float bias, float *dst, int lane)
+{
 	const int icl = lane >> 4;
 	const int arow = lane & 15, awin = arow >> 2, ady = (arow >> 1) & 1, adx = arow & 1;      // A operand: this lane supplies pixel (ady, adx) of window awin of the tile
-	float *const dst = act2 + (size_t)b * (64 * PO * PO) + n * (PO * PO) + (oy0 / 2) * PO;       // index = x + PO*y + PO*PO*c, the layout LFull consumes
+#pragma unroll      // stated: inside a function the compiler no longer unrolls the tiles on its own, and the loop is written for straight-line code
 	for (int mt = 0; mt < MT; mt++)
 	{
 		const int win = 4 * mt + awin, wy = win / PO, wx = win % PO;
@@ -292,17 +309,35 @@ __global__ __launch_bounds__(256) void k_conv2(const float *__restrict__ act1, c
 	}
 }
 
+template <int IWD, int OW, int BAND>
+__global__ __launch_bounds__(256) void k_conv2(const float *__restrict__ act1, const float *__restrict__ W2p, const float *__restrict__ B2, float *__restrict__ act2)
+{
+	constexpr int IR = BAND + 3, PO = OW / 2, CH = IR * IWD, NW = (BAND / 2) * PO, MT = NW / 4;      // NW: pooling windows of the band
+	static_assert(NW % 4 == 0 && BAND % 2 == 0 && OW % 2 == 0 && OW % BAND == 0, "band must hold whole MFMA tiles of whole pooling windows");
+	__shared__ __attribute__((aligned(16))) float in[16 * CH];
+	const int b = blockIdx.x, band = blockIdx.y, t = threadIdx.x, lane = t & 63, wave = t >> 6;
+	const int oy0 = band * BAND;
+	// the band's input rows in the order conv2_tiles reads them
+	for (int i = t; i < 16 * CH; i += 256) { const int ic = i / CH, r = i % CH; in[(r * 4 + (ic & 3)) * 4 + (ic >> 2)] = act1[(size_t)b * (16 * IWD * IWD) + ic * (IWD * IWD) + oy0 * IWD + r]; }
+	const int n = 16 * wave + (lane & 15);
+	float breg[64];
+	conv2_fragments(W2p, n, lane, breg);
+	const float bias = B2[n];
+	__syncthreads();
+	conv2_tiles<IWD, PO, MT>(in, breg, bias, act2 + (size_t)b * (64 * PO * PO) + n * (PO * PO) + (oy0 / 2) * PO, lane);      // index = x + PO*y + PO*PO*c, the layout LFull consumes
+}
+
 // ------------------------------------------------------------------------------------------------- k_conv12
 // Both convolution layers of the 64x64 net in one launch, a block per frame: k_conv1's window loop leaves the 16 x 15 x 15 pooled values in LDS, tanh is applied in place --
 // which makes that array exactly the input image k_conv2 stages ([ic][15 x 15]) -- and k_conv2's tiles follow.  Saved against the two launches: conv2's load phase, 14.7 MB
 // written and read back, a launch boundary with every block of the chip in step, and -- what the phases of a single launch cannot hide from each other (section 15) -- the 64 KB
 // of conv2 weights every block loads into registers, which are asked for HERE before the first layer's window loop and arrive under it.  act1 is still written (the layer
-// getter reads it), nobody waits for it.  Same arithmetic in the same order as the two kernels (the 128x128 net keeps them: its bands do not line up).
+// getter reads it), nobody waits for it.  The arithmetic is the two kernels': the same functions (the 128x128 net keeps the two kernels: its bands do not line up).
 __global__ __launch_bounds__(256, 4) void k_conv12(const float *__restrict__ cnn_in, const float *__restrict__ W1, const float *__restrict__ B1, const float *__restrict__ W2p, const float *__restrict__ B2,
                                                 float *__restrict__ act1, float *__restrict__ act2)
 {
 	constexpr int IW = 64, PW = 15, PR = 15, TR = 4 * PR + 4, IWP = IW + 4;
-	constexpr int IWD = 15, OW = 12, PO = 6, CH = IWD * IWD, MT = 9;
+	constexpr int IWD = 15, PO = 6, CH = IWD * IWD, MT = 9;
 	__shared__ __attribute__((aligned(16))) float tile[TR * IWP];
 	__shared__ float pooled[16 * CH];      // layer 1's pooled values, then (tanh applied) layer 2's input [ic][15 x 15]
 	const int b = blockIdx.x, t = threadIdx.x, lane = t & 63, wave = t >> 6;
@@ -311,71 +346,25 @@ __global__ __launch_bounds__(256, 4) void k_conv12(const float *__restrict__ cnn
 	// layer 2's weight fragments, on their way while layer 1 runs
 	const int n2 = 16 * wave + (lane & 15);
 	float breg[64];
-#pragma unroll
-	for (int ks = 0; ks < 64; ks++) breg[ks] = W2p[(4 * ks + (lane >> 4)) * 64 + n2];
+	conv2_fragments(W2p, n2, lane, breg);
 	const float bias2 = B2[n2];
-	// ---- layer 1 (k_conv1)
+	// ---- layer 1 (k_conv1<64, 15, 15>'s stages)
+	float wreg[7], bias; int aoff[7];
+	conv1_fragments<IWP>(W1, B1, lane, wreg, aoff, bias);
+	__syncthreads();
+	conv1_windows<IWP, PW>(tile, pooled + (lane & 15) * CH, PR * PW, wave, lane, wreg, aoff, bias);
+	__syncthreads();
+	// tanh after pooling (monotone), into the dead input tile in the order conv2_tiles reads it
+	for (int i = t; i < 16 * CH; i += 256)
 	{
-		const int n = lane & 15, g = lane >> 4, px = lane & 3, py = (lane >> 2) & 3;
-		float wreg[7]; int aoff[7];
-#pragma unroll
-		for (int s = 0; s < 7; s++)
-		{
-			const int k = 4 * s + g, kk = k < 25 ? k : 24;
-			wreg[s] = k < 25 ? W1[n * 25 + k] : 0.0f;
-			aoff[s] = (py + kk / 5) * IWP + px + kk % 5;
-		}
-		const float bias = B1[n];
-		__syncthreads();
-		const int swave = __builtin_amdgcn_readfirstlane(wave);
-		float *const pdst = pooled + n * CH;
-		for (int w = swave; w < PR * PW; w += 4)
-		{
-			const int ty = w / PW, tx = w % PW;
-			const float *base = tile + 4 * ty * IWP + 4 * tx;
-			f32x4 acc = { bias, bias, bias, bias };
-#pragma unroll
-			for (int s = 0; s < 7; s++) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(base[aoff[s]], wreg[s], acc, 0, 0, 0);
-			float m = max_pool4(acc[0], acc[1], acc[2], acc[3]);
-			{ const auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(m), __float_as_uint(m), false, false); m = max_pool(__uint_as_float(r[0]), __uint_as_float(r[1])); }
-			{ const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(m), __float_as_uint(m), false, false); m = max_pool(__uint_as_float(r[0]), __uint_as_float(r[1])); }
-			if (lane < 16) pdst[ty * PW + tx] = m;
-		}
-		__syncthreads();
-		// tanh after pooling (monotone), into the dead input tile in the order layer 2 reads it: [position][ic & 3][ic >> 2] -- a lane of the matrix instruction takes
-		// ic = 4 * j + (lane >> 4) for the four k-steps j of a tap, so its four values are one 128-bit read (16 reads per tile instead of 64 values in 32 double reads)
-		for (int i = t; i < 16 * CH; i += 256)
-		{
-			const float v = tanh_ref(pooled[i]);
-			const int ic = i / CH, pos = i % CH;
-			tile[(pos * 4 + (ic & 3)) * 4 + (ic >> 2)] = v;
-			act1[(size_t)b * (16 * CH) + i] = v;
-		}
-		__syncthreads();
+		const float v = tanh_ref(pooled[i]);
+		const int ic = i / CH, pos = i % CH;
+		tile[(pos * 4 + (ic & 3)) * 4 + (ic >> 2)] = v;
+		act1[(size_t)b * (16 * CH) + i] = v;
 	}
-	// ---- layer 2 (k_conv2<15, 12, 12>), its input from `tile`
-	{
-		const int icl = lane >> 4;
-		const int arow = lane & 15, awin = arow >> 2, ady = (arow >> 1) & 1, adx = arow & 1;
-		float *const dst = act2 + (size_t)b * (64 * PO * PO) + n2 * (PO * PO);
-		for (int mt = 0; mt < MT; mt++)
-		{
-			const int win = 4 * mt + awin, wy = win / PO, wx = win % PO;
-			f32x4 acc = { bias2, bias2, bias2, bias2 };
-			const float *base = tile + (((2 * wy + ady) * IWD + 2 * wx + adx) * 4 + icl) * 4;
-#pragma unroll
-			for (int p = 0; p < 16; p++)      // tap p = (ky, kx); k = 16 * p + 4 * j + icl, ascending as in k_conv2
-			{
-				const float4 a = *reinterpret_cast<const float4 *>(base + ((p >> 2) * IWD + (p & 3)) * 16);
-				acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.x, breg[4 * p + 0], acc, 0, 0, 0);
-				acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.y, breg[4 * p + 1], acc, 0, 0, 0);
-				acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.z, breg[4 * p + 2], acc, 0, 0, 0);
-				acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.w, breg[4 * p + 3], acc, 0, 0, 0);
-			}
-			const float mm = max_pool4(acc[0], acc[1], acc[2], acc[3]);
-			dst[4 * mt + icl] = tanh_ref(mm);
-		}
-	}
+	__syncthreads();
+	// ---- layer 2 (k_conv2<15, 12, 12>'s stages), its input from `tile`
+	conv2_tiles<IWD, PO, MT>(tile, breg, bias2, act2 + (size_t)b * (64 * PO * PO) + n2 * (PO * PO), lane);
 }
 
 // ------------------------------------------------------------------------------------------------- k_fc

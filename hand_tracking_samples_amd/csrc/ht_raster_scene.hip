@@ -3,7 +3,8 @@
 // functions, the per-triangle ones and the scene's (mirrored pose and principal point, column flip, limits, composite rule), so every output is bit-identical to the
 // host's (tests/test_gpu_raster_scene.py).  DESIGN section 36.
 //
-// Mapping: k_raster_mesh's (ht_raster_mesh.hip), one block of four waves per (frame, band of rows), the band's z-buffer in LDS.  What differs:
+// Mapping: k_raster_mesh's (ht_raster_mesh.hip), one block of four waves per (frame, band of rows), the band's z-buffer in LDS; the table entry, the pass over the
+// triangles (rz_triangles) and the packers are the same functions of ht_raster_band.hpp, called here once per present instance.  What differs:
 //   key        count << 16 | (instance * T + triangle), T the model's mesh triangles: the smallest key is the definition's winner (smallest count, then the lowest
 //              instance, then the first in (body, triangle) order) whatever the order of arrival; instances * T <= 65535 keeps 0xffffffff for "nothing yet"
 //   instances  walked one after another with ONE pose table in LDS, rebuilt behind a barrier (four tables would cost the second block per CU).  The flag of an
@@ -12,14 +13,6 @@
 //   write-out  four pixels per thread: the background read with the width the depth is written with, by the thread that writes the pixel (bg == depth composes in
 //              place); hand and body decoded from the index; visible counted in registers, reduced over the wave, one integer atomic add per wave and instance
 #include "ht_raster_band.hpp"
-
-// pixel (x, y) of an instance's layer against triangle `key16`, written at column `rz_scene_column` of the band (row y0 first)
-__device__ __forceinline__ void rs_pixel(unsigned *zb, const rz_tri &T, int x, int y, int y0, int w, bool left, float fx, float fy, float px, float py, float off, float F, float ds, unsigned key16)
-{
-	if (!rz_inside(T, x, y)) return;
-	const int n = rz_count(T, rz_ray(x, off, px, fx), rz_ray(y, off, py, fy), F, ds);
-	if (n >= 0) atomicMin(&zb[(y - y0) * w + rz_scene_column(x, w, left)], ((unsigned)n << 16) | key16);
-}
 
 __global__ __launch_bounds__(RZ_THREADS) void k_raster_scene(const rz_model M, const float *__restrict__ poses, const unsigned char *__restrict__ hands, const float *__restrict__ cams, int H, int w, int h,
                                                              float F, float off, int f0, int bands, int rows, const uint16_t *bg, uint16_t *depth, int8_t *hand, int8_t *body, int *visible)
@@ -46,50 +39,10 @@ __global__ __launch_bounds__(RZ_THREADS) void k_raster_scene(const rz_model M, c
 			const float *g = poses + (((size_t)frame * H + inst) * nb + t) * HT_POSE;
 			float p[HT_POSE] = { g[0], g[1], g[2], g[3], g[4], g[5], g[6] };
 			if (left) { float m[HT_POSE]; rz_mirror_pose(p, m); for (int k = 0; k < HT_POSE; k++) p[k] = m[k]; }
-			const m3 R = qmat(V4(p[3], p[4], p[5], p[6]));
-			const v3 up = V3(p[0], p[1], p[2]) - mul(R, V3(M.com[3 * t], M.com[3 * t + 1], M.com[3 * t + 2]));
-			float *e = tab + t * 12;
-			e[0] = R.x.x; e[1] = R.x.y; e[2] = R.x.z; e[3] = R.y.x; e[4] = R.y.y; e[5] = R.y.z; e[6] = R.z.x; e[7] = R.z.y; e[8] = R.z.z; e[9] = up.x; e[10] = up.y; e[11] = up.z;
+			rz_table_put(tab + t * 12, p, M.com + 3 * t);
 		}
 		__syncthreads();      // the table stands (and, the first time, the z-buffer is cleared)
-		const unsigned key0 = (unsigned)(inst * NT);
-		for (int base = 0; base < NT; base += RZ_THREADS)      // uniform over the block: the wave's ballots and shuffles below see every lane
-		{
-			const int k = base + t;
-			rz_tri T = {};
-			int x0 = 0, x1 = -1, ya = 0, yb = -1;
-			bool live = k < NT;
-			if (live)
-			{
-				const float *e = tab + rz_body_of(M, k) * 12;
-				m3 R; R.x = V3(e[0], e[1], e[2]); R.y = V3(e[3], e[4], e[5]); R.z = V3(e[6], e[7], e[8]);
-				const float4 *row = M.rows + 4 * (size_t)k;
-				const float4 q0 = row[0], q1 = row[1], q2 = row[2];
-				live = rz_setup(R, V3(e[9], e[10], e[11]), V3(q0.x, q0.y, q0.z), V3(q1.x, q1.y, q1.z), V3(q2.x, q2.y, q2.z), fx, fy, px, py, off, T);
-				if (live)
-				{
-					rz_rect(T, x0, x1, ya, yb);      // in the layer's columns; the band's rows are the layer's rows
-					x0 = max(x0, 0); x1 = min(x1, w - 1); ya = max(ya, y0); yb = min(yb, y1);
-					live = x0 <= x1 && ya <= yb;
-				}
-			}
-			const bool big = live && (x1 - x0 + 1) * (yb - ya + 1) >= RZ_BIG;      // at most 4096 * 4096: fits
-			if (live && !big)
-				for (int y = ya; y <= yb; y++) for (int x = x0; x <= x1; x++) rs_pixel(zb, T, x, y, y0, w, left, fx, fy, px, py, off, F, ds, key0 + (unsigned)k);
-			unsigned long long bm = __ballot(big);
-			while (bm)
-			{
-				const int j = __ffsll((long long)bm) - 1;
-				bm &= bm - 1ull;
-				rz_tri S;
-				S.X[0] = __shfl(T.X[0], j); S.X[1] = __shfl(T.X[1], j); S.X[2] = __shfl(T.X[2], j);
-				S.Y[0] = __shfl(T.Y[0], j); S.Y[1] = __shfl(T.Y[1], j); S.Y[2] = __shfl(T.Y[2], j);
-				S.N.x = __shfl(T.N.x, j); S.N.y = __shfl(T.N.y, j); S.N.z = __shfl(T.N.z, j); S.k = __shfl(T.k, j);
-				const int sx0 = __shfl(x0, j), sx1 = __shfl(x1, j), sya = __shfl(ya, j), syb = __shfl(yb, j);
-				const unsigned key16 = key0 + (unsigned)(k - lane + j);
-				for (int y = sya; y <= syb; y++) for (int x = sx0 + lane; x <= sx1; x += 64) rs_pixel(zb, S, x, y, y0, w, left, fx, fy, px, py, off, F, ds, key16);
-			}
-		}
+		rz_triangles(zb, M, tab, t, y0, y1, w, left, fx, fy, px, py, off, F, ds, (unsigned)(inst * NT));
 	}
 	__syncthreads();
 	// write-out: the band's pixels are [o0, o0 + npx) of the batch, in groups of four aligned in the batch
@@ -136,9 +89,9 @@ __global__ __launch_bounds__(RZ_THREADS) void k_raster_scene(const rz_model M, c
 		}
 		if (whole)
 		{
-			*(uint2 *)(depth + 4 * g) = make_uint2((unsigned)d[0] | ((unsigned)d[1] << 16), (unsigned)d[2] | ((unsigned)d[3] << 16));
-			if (hand) *(unsigned *)(hand + 4 * g) = (unsigned)(hi[0] & 0xff) | ((unsigned)(hi[1] & 0xff) << 8) | ((unsigned)(hi[2] & 0xff) << 16) | ((unsigned)(hi[3] & 0xff) << 24);
-			if (body) *(unsigned *)(body + 4 * g) = (unsigned)(who[0] & 0xff) | ((unsigned)(who[1] & 0xff) << 8) | ((unsigned)(who[2] & 0xff) << 16) | ((unsigned)(who[3] & 0xff) << 24);
+			*(uint2 *)(depth + 4 * g) = rz_pack_u16(d);
+			if (hand) *(unsigned *)(hand + 4 * g) = rz_pack_i8(hi);
+			if (body) *(unsigned *)(body + 4 * g) = rz_pack_i8(who);
 		}
 		else
 		{

@@ -51,6 +51,24 @@ def test_closest_feature_and_cnn_kernels(usage):
             assert usage[k]["ScratchSize"] == 0, k
 
 
+def test_raster_kernels(usage):
+    """k_raster_mesh and k_raster_scene: no private segment, no spill of either kind (a scalar spill was why wider stores were taken out), and the band's z-buffer with
+    the pose table twice in a CU's 160 KB: two blocks per CU (DESIGN.md sections 35 and 36)."""
+    for name in ("k_raster_mesh", "k_raster_scene"):
+        k = _one(usage, name)
+        assert k["ScratchSize"] == 0 and k["SGPRs Spill"] == 0 and k["VGPRs Spill"] == 0, name
+        assert 2 * k["LDS Size"] <= 160 * 1024, name
+
+
+def test_conv_kernels_keep_four_blocks(usage):
+    """k_conv12 is built for four blocks of four waves per CU (__launch_bounds__(256, 4)): 128 registers a lane with the accumulator file, and every k_conv2, whose tile
+    loop it shares, stays within the same."""
+    hits = [k for k in usage if "k_conv12" in k or "k_conv2I" in k]
+    assert len(hits) == 3, hits      # k_conv12, k_conv2<15,12,12>, k_conv2<31,28,4>
+    for k in hits:
+        assert usage[k]["VGPRs"] + usage[k]["AGPRs"] <= 128, k
+
+
 def test_cooperative_contact_kernel(usage):
     """k_contacts_coop (two waves per SIMD: 256 registers a wave): everything in registers, no private segment.  Until round 6 a run's two simplices kept p = a - b beside a
     and b (24 registers), and the kernel spilled 32 registers to 76 bytes of scratch per lane."""
