@@ -243,10 +243,14 @@ __device__ __forceinline__ void closest_chunk(const ht_model_dev &M, const float
 #define CR_THREADS 256
 // One frame's rows by one block (or by `ny` blocks that share its passes: block `by` takes every ny-th).  tab / L / wq / wI: the block's LDS (wq, wI only in
 // record mode); the planes go to s_planes.  k_cloud_rows below and the full-reset kernel (k_reset) both run this.
+// VIEWS (k_view_rows, the fused cloud of several views, ht_views.hip): a point's ray starts at the origin its .w names in the frame's table view_origins
+// [2 HT_VIEWS_MAX][3], in the `want` test and as ConvexHitCheck's segment start alike; the source rides in the top three bits of the point's hit-list entry.  Compiled
+// out of the other launches, whose instructions are what they were.
+template <bool VIEWS = false>
 __device__ __forceinline__ void cloud_rows_frame(const ht_model_dev &M, const float *__restrict__ state, const float4 *__restrict__ pts, const float *__restrict__ cams, int stride,
                                                  int use_cam_origin, int mode, float microforce, float weak_force, float cf_max_point, float cf_max_sum, float unibody_force,
                                                  float *__restrict__ rows, int *__restrict__ nrows, const cloud_records &rec, int dbg, int b, int n, int by, int ny,
-                                                 float *tab, closest_lds &L, float (*wq)[4], float (*wI)[10])
+                                                 float *tab, closest_lds &L, float (*wq)[4], float (*wI)[10], const float *__restrict__ view_origins = nullptr)
 {
 	const int t = threadIdx.x;
 	const int nsub = (n + stride - 1) / stride;
@@ -264,7 +268,7 @@ __device__ __forceinline__ void cloud_rows_frame(const ht_model_dev &M, const fl
 	stage_planes(M, t, CR_THREADS);
 	__syncthreads();
 	const float *cam = cams + (size_t)b * HT_CAM;
-	const v3 origin = use_cam_origin ? V3(cam[5], cam[6], cam[7]) : V3(0, 0, 0);
+	v3 origin = !VIEWS && use_cam_origin ? V3(cam[5], cam[6], cam[7]) : V3(0, 0, 0);      // VIEWS: point by point, below (cams is not read)
 	int npmax = 0;
 	for (int bb = 0; bb < M.nb; bb++) npmax = max(npmax, M.plane_off[bb + 1] - M.plane_off[bb]);
 	for (int base = by * CH; base < nsub; base += ny * CH)
@@ -273,6 +277,8 @@ __device__ __forceinline__ void cloud_rows_frame(const ht_model_dev &M, const fl
 		const bool exists = i < nsub, active = t < CH && exists;
 		const float4 pv = exists ? pts[(size_t)b * M.pts_cap + i * stride] : make_float4(0, 0, 0, 0);
 		const v3 v = V3(pv.x, pv.y, pv.z);
+		int src = 0;
+		if constexpr (VIEWS) { src = min(max((int)pv.w, 0), 2 * HT_VIEWS_MAX - 1); origin = load3(view_origins + 3 * src); }
 		int rb; v4 p; float dmin;
 		closest_chunk<CR_THREADS>(M, tab, L, active, exists, v, npmax, rb, p, dmin);
 		if (rb < 0) rb = 0;
@@ -291,7 +297,7 @@ __device__ __forceinline__ void cloud_rows_frame(const ht_model_dev &M, const fl
 		bool hit = false; v3 impact = V3(0, 0, 0);
 		if (nwant > 0)
 		{
-			if (want) L.pair[((t >> 6) ? nw0 : 0) + __popcll(wm & ((1ull << (t & 63)) - 1ull))] = (unsigned short)(t | (rb << 8));
+			if (want) L.pair[((t >> 6) ? nw0 : 0) + __popcll(wm & ((1ull << (t & 63)) - 1ull))] = (unsigned short)(t | (rb << 8) | (VIEWS ? src << 13 : 0));
 			__syncthreads();
 			const int g = t & 15;
 			auto row_min = [](int x) -> int {
@@ -309,10 +315,10 @@ __device__ __forceinline__ void cloud_rows_frame(const ht_model_dev &M, const fl
 				const int q = q0 + (t >> 4);
 				const bool on = q < nwant;
 				const unsigned e = on ? L.pair[q] : 0;
-				const int pt = e & 255, body = e >> 8;
+				const int pt = e & 255, body = VIEWS ? (e >> 8) & 31 : e >> 8;
 				const float *tr = tab + body * BT;
 				const float4 pw = L.v[pt];
-				v3 v0 = tab_to_local(tr, origin), v1 = tab_to_local(tr, V3(pw.x, pw.y, pw.z));
+				v3 v0 = tab_to_local(tr, VIEWS ? load3(view_origins + 3 * (e >> 13)) : origin), v1 = tab_to_local(tr, V3(pw.x, pw.y, pw.z));
 				const float4 *pl = s_planes + tab_plane0(tr);
 				const int np = on ? tab_nplanes(tr) : 0;
 				int k0 = 0; bool done = !on, ok = true;
@@ -406,6 +412,23 @@ __global__ __launch_bounds__(CR_THREADS) void k_cloud_rows(ht_model_dev M, const
 	if ((int)blockIdx.y * CH >= nsub && blockIdx.y > 0) return;      // ny blocks share a frame's passes (a row only depends on its own point)
 	if (t == 0 && blockIdx.y == 0) nrows[b] = nsub;
 	cloud_rows_frame(M, state, pts, cams, stride, use_cam_origin, mode, microforce, weak_force, cf_max_point, cf_max_sum, unibody_force, rows, nrows, rec, dbg, b, n, blockIdx.y, ny, tab, L, wq, wI);
+}
+
+// The fused cloud of several views (ht_views.hip): every point of the frame, each from its own ray origin (origins [B][2 HT_VIEWS_MAX][3]); no plane-row role, no frame
+// order, no mask.  The per-frame code is the one above in its VIEWS mode.
+__global__ __launch_bounds__(CR_THREADS) void k_view_rows(ht_model_dev M, const float *__restrict__ state, const float4 *__restrict__ pts, const int *__restrict__ npts,
+                                                                 const float *__restrict__ origins, int mode, float microforce, float weak_force, float cf_max_point, float cf_max_sum, float unibody_force,
+                                                                 float *__restrict__ rows, int *__restrict__ nrows, cloud_records rec, int dbg)
+{
+	__shared__ float tab[HT_MAXNB * BT];
+	__shared__ closest_lds L;
+	__shared__ float wq[HT_MAXNB][4], wI[HT_MAXNB][10];
+	const int b = blockIdx.x, t = threadIdx.x, ny = gridDim.y;
+	const int n = npts[b];
+	if ((int)blockIdx.y * CH >= n && blockIdx.y > 0) return;
+	if (t == 0 && blockIdx.y == 0) nrows[b] = n;
+	cloud_rows_frame<true>(M, state, pts, nullptr, 1, 0, mode, microforce, weak_force, cf_max_point, cf_max_sum, unibody_force, rows, nrows, rec, dbg, b, n, blockIdx.y, ny, tab, L, wq, wI,
+	                       origins + (size_t)b * 2 * HT_VIEWS_MAX * 3);
 }
 
 // ------------------------------------------------------------------------------------------------- k_reset
@@ -957,6 +980,15 @@ void ht_launch_cloud_rows(const ht_model_dev &M, const float *state, const float
 	// `planes`: the frames' boundary-plane rows (k_chamber's) by one more block per frame, behind the cloud-row blocks in dispatch order
 	hipLaunchKernelGGL(k_cloud_rows, dim3(B, split + (planes ? 1 : 0)), dim3(CR_THREADS), ((size_t)M.plane_off[M.nb] + 16) * sizeof(float4), s, M, state, pts, npts, cams, active_flag, take.stride, take.cam_origin, take.mode,
 	                   lim.microforce, lim.weak_force, lim.cf_max_point, lim.cf_max_sum, lim.unibody_force, rows, nrows, rec ? *rec : none, planes ? *planes : no_planes, ht_tuning_flags());
+}
+void ht_launch_cloud_rows_views(const ht_model_dev &M, const float *state, const float4 *pts, const int *npts, const float *origins, const cloud_limits &lim, float *rows, int *nrows, int B, hipStream_t s,
+                                const cloud_records *rec)
+{
+	const cloud_records none = { nullptr, 0, nullptr, 0.0f };
+	const int pts_max = M.pts_bound > 0 ? M.pts_bound : M.pts_cap, passes = (pts_max + CH - 1) / CH;
+	const int split = B <= 2048 && passes >= 2 ? 2 : 1;      // ht_launch_cloud_rows' rule
+	hipLaunchKernelGGL(k_view_rows, dim3(B, split), dim3(CR_THREADS), ((size_t)M.plane_off[M.nb] + 16) * sizeof(float4), s, M, state, pts, npts, origins, (int)CLOUD_FIT,
+	                   lim.microforce, lim.weak_force, lim.cf_max_point, lim.cf_max_sum, lim.unibody_force, rows, nrows, rec ? *rec : none, ht_tuning_flags());
 }
 // the full-reset branch for the frames list[0 .. *nlist) (all B frames with list == nullptr); many_frames: the caller expects more of them than the device has CUs
 // (the two-blocks-per-CU build)

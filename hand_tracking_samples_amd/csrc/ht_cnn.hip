@@ -20,25 +20,8 @@
 #include "ht_device.hpp"
 
 // ------------------------------------------------------------------------------------------------- k_prepare
-// What k_prepare, k_prepare_frame and k_cnn_input make of a depth word, each stated once
-__device__ __forceinline__ float depth_metres(unsigned px, float dscale) { return (float)(int)px * dscale; }
-__device__ __forceinline__ float cnn_input_value(float d, float drangey) { return clamp_std(1.0f - (d - 0.1f) / (drangey - 0.1f), 0.0f, 1.0f); }      // handtrack.h:700
-__device__ __forceinline__ bool depth_in_range(float d, float drangey) { return d >= 0.1f && d < drangey; }                                          // FallsWithinRange misc_image.h:24
-__device__ __forceinline__ float4 deproject_point(float x, float y, float d, float fx, float fy, float cx, float cy) { return make_float4(((x - cx) / fx) * d, ((y - cy) / fy) * d, 1.0f * d, 0.0f); }      // deprojectz misc_image.h:48
-// exclusive prefix of cnt over the block's 256 threads (every thread calls it): the thread's base; total: the block's sum
-__device__ __forceinline__ int block_prefix256(int cnt, int lane, int wave, int &total)
-{
-	int incl = cnt;
-#pragma unroll
-	for (int o = 1; o < 64; o <<= 1) { int v = __shfl_up(incl, o); if (lane >= o) incl += v; }
-	__shared__ int wsum[4];
-	if (lane == 63) wsum[wave] = incl;
-	__syncthreads();
-	int base = incl - cnt;
-	for (int i = 0; i < wave; i++) base += wsum[i];
-	total = wsum[0] + wsum[1] + wsum[2] + wsum[3];
-	return base;
-}
+// What k_prepare, k_prepare_frame and k_cnn_input make of a depth word is stated once, in ht_prepare.hpp (k_fuse_views, ht_views.hip, takes the same pieces)
+#include "ht_prepare.hpp"
 
 // one block per frame; thread t owns pixels [16t, 16t+16) so that a block-wide prefix sum keeps the row-major order
 __global__ __launch_bounds__(256) void k_prepare(const uint16_t *__restrict__ depth, const float *__restrict__ cams, float drangey, int fraction,

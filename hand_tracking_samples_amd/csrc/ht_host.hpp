@@ -126,6 +126,11 @@ struct ht_ctx
 	// [B][nb][7] and rendered frames [B][h][w], grown to the largest call with one synchronising re-allocation before anything is enqueued (quality_reserve)
 	float kp_feature8[24] = { 0, 0, 0, -0.03f, 0, -0.03f, 0.03f, 0, -0.03f, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0 };
 	float *d_quality_poses = nullptr; size_t quality_poses_cap = 0; uint16_t *d_quality_frames = nullptr; size_t quality_frames_cap = 0;
+	// several views (ht_views.hip): the ray origins of the slots' fused clouds [B][2 HT_VIEWS_MAX][3] (k_fuse_views writes them, k_view_rows reads the one a point's
+	// .w names), the per-source counts of a call whose caller wants none [B][2 HT_VIEWS_MAX] with the count of cut slots behind them (allocated on first use), the slots
+	// [0, views_B) the latest ht_fuse_views filled, and ht_update_views_*'s contiguous copy of view 0's frames and cameras (dev_grow)
+	float *d_view_origins = nullptr; int *d_view_src = nullptr; int views_B = 0;
+	uint16_t *d_view0 = nullptr; size_t view0_cap = 0; float *d_view0_cams = nullptr;
 };
 
 // The net of a side x side input; any other side is refused here, and only here
@@ -218,6 +223,15 @@ bool ql_any_overlap(const ql_buf *in, int nin, const ql_buf *out, int nout);
 // PhysModel::FitPointCloud step on model `which` of slots [0,B) with the linear rows and counts that d_user_lin / d_user_n hold, enqueued on s and not waited for
 int ht_user_rows_reserve(ht_ctx *ctx, int lin_cap, int ang_cap);
 void ht_fit_rows_enqueue(ht_ctx *ctx, int which, int B, float microforce, int ang_bound, int zero_momenta, hipStream_t s);
+// Several views (ht_views.hip; the fit's launch sequence is ht_solver_api.hip's).  ht_fuse_views_reserve: every refusal of ht_fuse_views_dev and whatever grows, before
+// anything runs; ht_fuse_views_enqueue: the launch alone, on s.  ht_views_planes_ok: the mirror planes a host form refuses.  ht_fit_views_enqueue: `passes` times
+// ht_fit_rows_enqueue's sequence with the cloud rows of the fused points from their own ray origins and no caller rows, the momenta kept; the last solve writes the user
+// poses to d_poses (may be null)
+int ht_fuse_views_reserve(ht_ctx *ctx, const char *fn, const void *depth, const void *cams, int w, int h, int V, int B, const ht_views *o);
+int ht_fuse_views_enqueue(ht_ctx *ctx, const uint16_t *d_depth, const float *d_cams, const float *d_planes, int w, int h, int V, int B, const ht_views *o, int *d_npoints, int *d_per_source,
+                          float *d_origins, int *d_cut, hipStream_t s);
+int ht_views_planes_ok(ht_ctx *ctx, const char *fn, const float *planes, size_t n);
+int ht_fit_views_enqueue(ht_ctx *ctx, int which, int B, int passes, float *d_poses, hipStream_t s);
 
 struct ht_prof_scope
 {

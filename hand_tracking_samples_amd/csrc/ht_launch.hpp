@@ -70,6 +70,10 @@ static inline cloud_limits ht_cloud_limits(const ht_params &par, int mode, float
 }
 void ht_launch_cloud_rows(const ht_model_dev &M, const float *state, const float4 *pts, const int *npts, const float *cams, const int *active_flag, const cloud_take &take, const cloud_limits &lim,
                           float *rows, int *nrows, int B, hipStream_t s, const cloud_records *rec = nullptr, const plane_rows *planes = nullptr);
+// The same rows for a fused cloud of several views (ht_views.hip): every point, CLOUD_FIT's limits, and each point's ray from the origin its .w names in the frame's
+// table origins [B][2 HT_VIEWS_MAX][3] (k_view_rows: the compile-time mode of the same per-frame code; no plane rows, they assume one viewpoint)
+void ht_launch_cloud_rows_views(const ht_model_dev &M, const float *state, const float4 *pts, const int *npts, const float *origins, const cloud_limits &lim, float *rows, int *nrows, int B, hipStream_t s,
+                                const cloud_records *rec = nullptr);
 // What follows a FitError in HandTracker::update and needs nothing but that frame's error rides on the kernel's last thread instead of a launch of its own:
 // mode 1 = the full-reset decision (handtrack.h:706: flags[b] = angles_only || error > threshold), mode 2 = the accept step (handtrack.h:713-731).
 struct ht_fit_after

@@ -827,6 +827,80 @@ extern "C" int ht_update_frames_sized_sync(ht_ctx *ctx, int side, const uint16_t
 	update_req q = { "ht_update_frames_sized", FRAMES_SIZED, side, w, h, segment_scale, UPD_FULL, B, depth, cams, poses_out }; q.cnn = cnn_out;
 	return update_host(ctx, q);
 }
+// ---- several views (ht_views.hip): ht_update_frames_sized_* on view 0, the existing request unchanged, then the fused cloud of all views and `passes`
+// fits of the handmodel against it; the last of them writes the poses the caller gets.  The net, the segmentation, FitError and MultiStepSim see view 0 only.
+struct views_req { const float *planes; int V; const ht_views *opt; int passes; };
+// everything the call can be refused for or has to grow, before anything runs: the view-0 request, the fused cloud, the fit, the contiguous copy of view 0
+static int update_views_prepare(ht_ctx *ctx, update_req &q, const views_req &v, bool dev)
+{
+	{ const int r = update_check(ctx, q, dev); if (r) return r; }
+	{ const int r = ht_fuse_views_reserve(ctx, "ht_update_views", q.depth, q.cams, q.w, q.h, v.V, q.B, v.opt); if (r) return r; }
+	if (v.passes < 1 || v.passes > 64) { ctx->err = "ht_update_views: passes between 1 and 64"; return HT_ERR_ARG; }
+	REFUSE_EXACT_SOLVER(ctx);
+	if (v.V > 1)
+	{
+		const size_t px = (size_t)q.w * q.h;
+		if (px > ctx->view0_cap) HIPCHK(ctx, ht_sync_all(ctx));
+		int r;
+		if ((r = dev_grow(ctx, &ctx->d_view0, &ctx->view0_cap, px, (size_t)ctx->B)) || (!ctx->d_view0_cams && (r = dev_alloc(ctx, &ctx->d_view0_cams, (size_t)ctx->B * HT_CAM)))) return r;
+	}
+	return HT_OK;
+}
+// q: the request on device pointers, depth [B][V][h][w] and cams [B][V][12]
+static int update_views_enqueue(ht_ctx *ctx, const update_req &q, const views_req &v, hipStream_t s)
+{
+	update_req q0 = q;
+	const size_t px = (size_t)q.w * q.h;
+	if (v.V > 1)      // view 0 of every slot, contiguous, as the update takes its frames
+	{
+		HIPCHK(ctx, hipMemcpy2DAsync(ctx->d_view0, px * sizeof(uint16_t), q.depth, v.V * px * sizeof(uint16_t), px * sizeof(uint16_t), q.B, hipMemcpyDeviceToDevice, s));
+		HIPCHK(ctx, hipMemcpy2DAsync(ctx->d_view0_cams, HT_CAM * sizeof(float), q.cams, (size_t)v.V * HT_CAM * sizeof(float), HT_CAM * sizeof(float), q.B, hipMemcpyDeviceToDevice, s));
+		q0.depth = ctx->d_view0; q0.cams = ctx->d_view0_cams;
+	}
+	int r;
+	if ((r = update_enqueue(ctx, q0, s))) return r;
+	if ((r = ht_fuse_views_enqueue(ctx, q.depth, q.cams, v.planes, q.w, q.h, v.V, q.B, v.opt, nullptr, nullptr, nullptr, nullptr, s))) return r;
+	return ht_fit_views_enqueue(ctx, 0, q.B, v.passes, q.poses, s);
+}
+extern "C" int ht_update_views_dev(ht_ctx *ctx, int side, const uint16_t *d_depth, const float *d_cams, const float *d_planes, int w, int h, int V, float segment_scale, const float *d_start_poses, int B,
+                                   const ht_views *o, int passes, float *d_poses_out, void *stream)
+{
+	update_req q = { "ht_update_views", FRAMES_SIZED, side, w, h, segment_scale, UPD_FULL, B, d_depth, d_cams, d_poses_out }; q.start = d_start_poses;
+	const views_req v = { d_planes, V, o, passes };
+	CHECK_READY(ctx);
+	{ const int r = update_views_prepare(ctx, q, v, true); if (r) return r; }
+	return update_dev_end(ctx, update_views_enqueue(ctx, q, v, ht_user_stream(ctx, stream)));
+}
+extern "C" int ht_update_views_sync(ht_ctx *ctx, int side, const uint16_t *depth, const float *cams, const float *planes, int w, int h, int V, float segment_scale, int B, const ht_views *o, int passes,
+                                    float *poses_out, float *cnn_out)
+{
+	update_req q = { "ht_update_views", FRAMES_SIZED, side, w, h, segment_scale, UPD_FULL, B, depth, cams, poses_out };
+	const views_req v = { planes, V, o, passes };
+	CHECK_READY(ctx);
+	{ const int r = update_views_prepare(ctx, q, v, false); if (r) return r; }
+	const size_t n = (size_t)B, nv = n * V;
+	for (size_t b = 0; b < n; b++)      // the reference's PointCloud is camera-local (handtrack.h:703): view 0 is the tracking space
+	{
+		const float *c = cams + b * V * HT_CAM;
+		if (!(c[5] == 0.0f && c[6] == 0.0f && c[7] == 0.0f && c[8] == 0.0f && c[9] == 0.0f && c[10] == 0.0f && c[11] == 1.0f)) { ctx->err = "ht_update_views: view 0's camera pose must be identity (the other views are posed in its space)"; return HT_ERR_ARG; }
+	}
+	{ const int r = ht_views_planes_ok(ctx, "ht_update_views", planes, nv); if (r) return r; }
+	ht_seg seg[4] = { { (void *)depth, nv * w * h * sizeof(uint16_t), false }, { (void *)cams, nv * HT_CAM * sizeof(float), false }, { (void *)planes, nv * 4 * sizeof(float), false },
+	                  { poses_out, n * ctx->model.nb * HT_POSE * sizeof(float), true } };
+	const int r = ht_staged_call(ctx, seg, 4, [&](hipStream_t s)
+	                             {
+		                             update_req d = q; d.depth = (const uint16_t *)seg[0].dev; d.cams = (const float *)seg[1].dev; d.poses = (float *)seg[3].dev;
+		                             const views_req dv = { (const float *)seg[2].dev, V, o, passes };
+		                             return update_views_enqueue(ctx, d, dv, s);
+	                             });
+	if (r) return r;
+	HIPCHK(ctx, hipGetLastError());
+	if (cnn_out) HIPCHK(ctx, hipMemcpy(cnn_out, ctx->d_cnn_out, n * HT_CNN_OUT * sizeof(float), hipMemcpyDeviceToHost));
+	int over = 0;
+	if (q.fs.kind == FRAME_SEGMENTED) HIPCHK(ctx, hipMemcpy(&over, ctx->d_overflow, sizeof(int), hipMemcpyDeviceToHost));
+	if (over) { ctx->err = "ht_update_views: " + std::to_string(over) + " frame(s) have more in-range points than the context's point capacity holds; their result is not the reference's"; return HT_ERR_ARG; }
+	return HT_OK;
+}
 extern "C" int ht_update_direct_dev(ht_ctx *ctx, const uint16_t *d_depth, const float *d_cams, int side, const float *d_start_poses, int B, float *d_poses_out, void *stream)
 {
 	update_req q = { "ht_update_direct", FRAMES_DIRECT, side, side, side, 0.0f, UPD_FULL, B, d_depth, d_cams, d_poses_out }; q.start = d_start_poses;
@@ -1340,6 +1414,27 @@ void ht_fit_rows_enqueue(ht_ctx *ctx, int which, int B, float microforce, int an
 	a.cloud_body = ctx->d_rowbody; a.n_cloud = ctx->d_nrows;
 	a.zero_momenta = zero_momenta;
 	enqueue_caller_rows(ctx, a, ang_bound, B, s);
+}
+// ht_fit_views (ht_views.hip): `passes` times the sequence above on the slots' fused cloud, with the cloud-row launch that takes every point's ray from its own origin
+// and without caller rows or boundary planes; the momenta are kept from pass to pass as in update()'s main passes, and the last solve writes the user poses (d_poses may
+// be null).  All on s, nothing copied or waited for between the passes
+int ht_fit_views_enqueue(ht_ctx *ctx, int which, int B, int passes, float *d_poses, hipStream_t s)
+{
+	const bool coll = ctx->phys.use_collision != 0;
+	const cloud_records cr = cloud_rec(ctx);
+	for (int pass = 0; pass < passes; pass++)
+	{
+		ht_launch_cloud_rows_views(ctx->model, ctx->d_state[which], ctx->d_pts, ctx->d_npts, ctx->d_view_origins, ht_cloud_limits(ctx->par, CLOUD_FIT), ctx->d_rows, ctx->d_nrows, B, s, &cr);
+		if (coll) launch_contacts(ctx, which, nullptr, B, s);
+		solve_args a = solve_head(ctx, which, coll);
+		a.cloud_body = ctx->d_rowbody; a.n_cloud = ctx->d_nrows;
+		a.force_build = ctx->solver_build;
+		if (d_poses && pass + 1 == passes) { a.out_poses = d_poses; a.out_npts = ctx->d_npts; a.out_initializing = ctx->d_initializing; a.out_min_point_num = 0; }      // (no point count is below 0: the tracker's flags are not touched)
+		ctx->model.pts_bound = 0;
+		ht_launch_solve(ctx->model, ctx->phys, a, B, s);
+	}
+	HIPCHK(ctx, hipGetLastError());
+	return HT_OK;
 }
 // void PhysModel::FitPointCloud(const std::vector<float3> &points, std::vector<LimitLinear> linears, std::vector<LimitAngular> angulars, float microforce)
 // on model `which` of slots [0,B): the caller's linear rows, then CloudConstraints(points) with the +-microforce limits (x physics_weak_force on

@@ -25,6 +25,7 @@ SPLIT_MODEL_ALWAYS, SPLIT_MODEL_MERGED, SPLIT_USER_POSES = 0, 1, 4      # HT_SPL
 KP_COM_POSES = 1              # HT_KP_COM_POSES
 KP_FEATURE8, KP_SKELETON, KP_CALLER, KP_MAX, KP_MAX_THR = 0, 1, 2, 64, 32      # HT_KP_FEATURE8, HT_KP_SKELETON, HT_KP_CALLER, HT_KP_MAX, HT_KP_MAX_THR
 KPFIT_KEEP_MOMENTA = 1        # HT_KPFIT_KEEP_MOMENTA
+VIEWS_MAX = 4                 # HT_VIEWS_MAX
 CNN128_IN, CNNB128_COUNT = 16384, 30429920
 # ht_debug_train_buffers: (name, floats, shape) of the segments of act and err, in order (None: padding)
 TRAIN_ACT = (("a1", 57600, (16, 60, 60)), ("a3", 3600, (16, 15, 15)), ("a5", 9216, (64, 12, 12)), ("a6", 2304, (2304,)), ("a8", 2048, (2048,)))
@@ -54,6 +55,7 @@ SYMBOLS = (
     "ht_keypoint_table", "ht_keypoints", "ht_keypoints_dev", "ht_keypoint_errors", "ht_keypoint_errors_dev", "ht_depth_compare", "ht_depth_compare_dev",
     "ht_pose_depth_residual", "ht_pose_depth_residual_dev", "ht_pose_mesh_residual", "ht_pose_mesh_residual_dev",
     "ht_kpfit_default", "ht_fit_keypoints", "ht_fit_keypoints_dev",
+    "ht_views_default", "ht_fuse_views", "ht_fuse_views_dev", "ht_stage_view_rows", "ht_fit_views", "ht_fit_views_dev", "ht_update_views_sync", "ht_update_views_dev", "ht_debug_prepare_frames_dev", "ht_debug_fit_rows_pass_dev",
     "ht_comm_available", "ht_comm_unique_id", "ht_comm_init", "ht_comm_info", "ht_gather_poses_dev", "ht_gather_wait", "ht_gather_wait_host", "ht_comm_destroy",
 )
 
@@ -114,6 +116,11 @@ class Opt(C.Structure):
 class KpFit(C.Structure):
     """ht_kpfit: the options of ht_fit_keypoints (kpfit_default() fills in slowfit's figures)"""
     _fields_ = [("steps", C.c_int), ("max_force", C.c_float), ("ray_radius", C.c_float), ("ray_force", C.c_float), ("flags", C.c_int)]
+
+
+class Views(C.Structure):
+    """ht_views: the options of ht_fuse_views (Context.views_default() fills in the tracker's figures)"""
+    _fields_ = [("range_lo", C.c_float), ("range_hi", C.c_float), ("fraction", C.c_int), ("mirror_eps", C.c_float)]
 
 
 class HTError(RuntimeError):
@@ -303,6 +310,17 @@ def load(build_if_missing=True):
     L.ht_kpfit_default.argtypes = [C.POINTER(KpFit)]
     L.ht_fit_keypoints.argtypes = [vp, ci, ci, ci, ci, ip, fp, ip, ip, fp, fp, fp, fp, C.POINTER(KpFit), fp, fp]
     L.ht_fit_keypoints_dev.argtypes = [vp, ci, ci, ci, ci, ip, fp, ip, ip, vp, vp, vp, vp, C.POINTER(KpFit), vp, vp, vp]
+    vwp = C.POINTER(Views)
+    L.ht_views_default.argtypes = [vp, vwp]
+    L.ht_fuse_views.argtypes = [vp, u16p, fp, fp, ci, ci, ci, ci, vwp, fp, ci, ip, ip, fp, ip]
+    L.ht_fuse_views_dev.argtypes = [vp, vp, vp, vp, ci, ci, ci, ci, vwp, vp, vp, vp, vp, vp]
+    L.ht_stage_view_rows.argtypes = [vp, ci, ci, fp, ci, ip]
+    L.ht_fit_views.argtypes = [vp, ci, ci, ci, fp]
+    L.ht_fit_views_dev.argtypes = [vp, ci, ci, ci, vp, vp]
+    L.ht_update_views_sync.argtypes = [vp, ci, u16p, fp, fp, ci, ci, ci, cf, ci, vwp, ci, fp, fp]
+    L.ht_update_views_dev.argtypes = [vp, ci, vp, vp, vp, ci, ci, ci, cf, vp, ci, vwp, ci, vp, vp]
+    L.ht_debug_prepare_frames_dev.argtypes = [vp, vp, vp, ci, ci, ci, vp]
+    L.ht_debug_fit_rows_pass_dev.argtypes = [vp, ci, ci, vp]
     L.ht_keypoint_errors.argtypes = [vp, fp, fp, ci, ci, fp, ci, fp, fp, dp, i64p, i64p]
     L.ht_keypoint_errors_dev.argtypes = [vp, vp, vp, ci, ci, fp, ci, vp, vp, vp, vp, vp, vp]
     L.ht_depth_compare.argtypes = [vp, u16p, u16p, ci, ci, ci, ci, ci, ci, i64p]
@@ -1068,6 +1086,72 @@ class Context:
         kind = None if kind is None else _c(kind, np.int32).reshape(-1)
         self._chk(self.L.ht_fit_keypoints_dev(self.h, int(which_model), int(B), which, K, tp[0], tp[1], tp[2], None if kind is None else _i(kind), d_xyz, d_pix, d_weights, d_cams,
                                               None if options is None else C.byref(options), d_poses, d_resid, stream))
+
+    # -- several views (ht_mi355x.h "several views"): one hand from V <= VIEWS_MAX depth cameras and their mirrors
+    def views_default(self, **kw):
+        """ht_views_default (range {0.1, drangey}, fraction = subsample_fraction, mirror_eps 0.02), then the fields given"""
+        o = Views()
+        self._chk(self.L.ht_views_default(self.h, C.byref(o)))
+        for k, v in kw.items():
+            if k not in dict(Views._fields_):
+                raise TypeError("ht_views has no field %r" % k)
+            setattr(o, k, v)
+        return o
+
+    @staticmethod
+    def _views_io(depth, cams, planes):
+        depth = _c(depth, np.uint16)
+        B, V, h, w = depth.shape
+        cams = _c(cams, np.float32).reshape(B, V, CAM)
+        planes = None if planes is None else _c(planes, np.float32).reshape(B, V, 4)
+        return depth, cams, planes, B, V, h, w
+
+    def fuse_views(self, depth, cams, planes=None, options=None, cap=None):
+        """depth u16[B,V,h,w], cams f32[B,V,12] posed in one tracking space, planes f32[B,V,4] or None -> dict(points f32[B,cap,4] (x y z source; cap None: the most the
+        views can carry), npoints i32[B], per_source i32[B,2V], origins f32[B,2V,3], cut).  The cloud stays in slots [0,B) for fit_views / stage_view_rows."""
+        depth, cams, planes, B, V, h, w = self._views_io(depth, cams, planes)
+        if cap is None:
+            fr = (options.fraction if options is not None else self.views_default().fraction) or 1
+            cap = max(V * ((w * h + fr - 1) // max(fr, 1)), 1)
+        out = dict(points=np.zeros((B, cap, 4), np.float32), npoints=np.zeros(B, np.int32), per_source=np.zeros((B, 2 * V), np.int32), origins=np.zeros((B, 2 * V, 3), np.float32))
+        cut = C.c_int(0)
+        self._chk(self.L.ht_fuse_views(self.h, depth.ctypes.data_as(C.POINTER(C.c_uint16)), _f(cams), None if planes is None else _f(planes), w, h, V, B, None if options is None else C.byref(options),
+                                       _f(out["points"]), int(cap), _i(out["npoints"]), _i(out["per_source"]), _f(out["origins"]), C.byref(cut)))
+        out["cut"] = cut.value
+        return out
+
+    def fuse_views_dev(self, d_depth, d_cams, w, h, V, B, d_planes=None, options=None, d_npoints=None, d_per_source=None, d_origins=None, d_cut=None, stream=None):
+        """ht_fuse_views_dev: device pointers, only enqueued on `stream`; the cloud is left in slots [0,B)."""
+        self._chk(self.L.ht_fuse_views_dev(self.h, d_depth, d_cams, d_planes, int(w), int(h), int(V), int(B), None if options is None else C.byref(options), d_npoints, d_per_source, d_origins, d_cut, stream))
+
+    def stage_view_rows(self, which, B, cap=None):
+        """The cloud rows of the fused points of slots [0,B), each from its own ray origin -> (rows f32[B,cap,16], nrows i32[B]); cap None: the context's point capacity."""
+        if cap is None:
+            cap = self.point_capacity()
+        rows = np.zeros((B, cap, ROW), np.float32); n = np.zeros(B, np.int32)
+        self._chk(self.L.ht_stage_view_rows(self.h, int(which), int(B), _f(rows), int(cap), _i(n)))
+        return rows, n
+
+    def fit_views(self, which, B, passes=1, want_poses=True):
+        """`passes` fits of model `which` of slots [0,B) against the fused cloud -> the user poses f32[B,nb,7] (or None)."""
+        poses = np.empty((B, self.nb, POSE), np.float32) if want_poses else None
+        self._chk(self.L.ht_fit_views(self.h, int(which), int(B), int(passes), None if poses is None else _f(poses)))
+        return poses
+
+    def fit_views_dev(self, which, B, passes=1, d_poses=None, stream=None):
+        self._chk(self.L.ht_fit_views_dev(self.h, int(which), int(B), int(passes), d_poses, stream))
+
+    def update_views_sync(self, depth, cams, planes=None, side=64, segment_scale=0.17, options=None, passes=3, want_cnn=False):
+        """ht_update_frames_sized_sync on view 0, then the fused cloud of all views and `passes` fits: depth u16[B,V,h,w], cams f32[B,V,12] (view 0's pose identity)."""
+        depth, cams, planes, B, V, h, w = self._views_io(depth, cams, planes)
+        poses = np.empty((B, self.nb, POSE), np.float32); cnn = np.empty((B, CNN_OUT), np.float32) if want_cnn else None
+        self._chk(self.L.ht_update_views_sync(self.h, int(side), depth.ctypes.data_as(C.POINTER(C.c_uint16)), _f(cams), None if planes is None else _f(planes), w, h, V, float(segment_scale), B,
+                                              None if options is None else C.byref(options), int(passes), _f(poses), None if cnn is None else _f(cnn)))
+        return (poses, cnn) if want_cnn else poses
+
+    def update_views_dev(self, side, d_depth, d_cams, w, h, V, segment_scale, d_start, B, d_poses_out, d_planes=None, options=None, passes=3, stream=None):
+        self._chk(self.L.ht_update_views_dev(self.h, int(side), d_depth, d_cams, d_planes, int(w), int(h), int(V), float(segment_scale), d_start, int(B), None if options is None else C.byref(options),
+                                             int(passes), d_poses_out, stream))
 
     def keypoint_errors(self, a, b, thr=()):
         """a, b f32[B,K,3] -> dict(dist f32[B,K], frame f32[B,2] (mean, max), sum_kp f64[K], hits_kp i64[T], hits_frame i64[T], and from them mean_kp f64[K],

@@ -774,6 +774,44 @@ struct HandTracker                                                              
 		r.before.assign(resid.begin(), resid.begin() + K); r.after.assign(resid.begin() + K, resid.begin() + 2 * K);
 		return r;
 	}
+	// Additions, not reference names (ht_mi355x.h "several views").  The reference keeps the pieces -- PlaneSplit, Mirror, MirrorPlaneSplit "to get some view of the back of
+	// an object" (misc_image.h:401-485), a mirror plane in every data set header (dataset.h:24,45) -- and tracks from one camera.  views: up to HT_VIEWS_MAX frames of one
+	// size whose cameras' poses are expressed in one tracking space; mirrors: a plane per view in that view's camera space, empty or (0,0,0,FLT_MAX) for none.
+	// FuseViews: the views' clouds as one, every point with the ray source that saw it (2 v: view v directly, 2 v + 1: through its mirror) and the sources' origins; the
+	// cloud stays on the device for the fit.  update_views: update() on views[0] (whose camera pose must be identity: the reference's PointCloud is camera-local,
+	// handtrack.h:703), then `passes` fits of handmodel against the fused cloud, each point's ray from its own source's origin (CloudConstraint, physmodel.h:164-174).
+	// Right hands only: mirror the inputs first.
+	struct ViewOptions : ht_views { explicit ViewOptions(const HandTracker &t) { ht_views_default(t.ctx_, this); } };      // range {0.1, drangey}, fraction = subsample_fraction, mirror_eps 0.02
+	struct FusedCloud { std::vector<float3> points; std::vector<int> source, per_source; std::vector<float3> origins; bool cut; };
+	FusedCloud FuseViews(const std::vector<Image<unsigned short>> &views, const std::vector<float4> &mirrors = std::vector<float4>(), const ht_views *options = nullptr)
+	{
+		push_params();
+		view_arrays a = pack_views(views, mirrors);
+		const ViewOptions dflt(*this);
+		const ht_views &o = options ? *options : dflt;
+		const int cap = a.V * ((a.w * a.h + (o.fraction > 0 ? o.fraction : 1) - 1) / (o.fraction > 0 ? o.fraction : 1));
+		std::vector<float> pts((size_t)(cap > 0 ? cap : 1) * 4), org((size_t)a.V * 6);
+		int n = 0, cut = 0;
+		FusedCloud f; f.per_source.assign((size_t)2 * a.V, 0);
+		check(ctx_, ht_fuse_views(ctx_, a.depth.data(), a.cams.data(), a.planes.empty() ? nullptr : a.planes.data(), a.w, a.h, a.V, 1, &o, pts.data(), cap > 0 ? cap : 1, &n, f.per_source.data(), org.data(), &cut));
+		for (int i = 0; i < n; i++) { f.points.push_back({ pts[4 * (size_t)i], pts[4 * (size_t)i + 1], pts[4 * (size_t)i + 2] }); f.source.push_back((int)pts[4 * (size_t)i + 3]); }
+		for (int s = 0; s < 2 * a.V; s++) f.origins.push_back({ org[3 * (size_t)s], org[3 * (size_t)s + 1], org[3 * (size_t)s + 2] });
+		f.cut = cut != 0;
+		return f;
+	}
+	std::vector<Pose> update_views(const std::vector<Image<unsigned short>> &views, const std::vector<float4> &mirrors = std::vector<float4>(), int passes = 3, const ht_views *options = nullptr)
+	{
+		if (left_hand) throw std::runtime_error("update_views: right hands only: mirror the frames, cameras and planes first");
+		push_params();
+		view_arrays a = pack_views(views, mirrors);
+		std::vector<float> out((size_t)nb_ * HT_POSE);
+		check(ctx_, ht_update_views_sync(ctx_, 64, a.depth.data(), a.cams.data(), a.planes.empty() ? nullptr : a.planes.data(), a.w, a.h, a.V, segment_scale, 1, options, passes, out.data(), cnn_output.data()));
+		const bool full = a.w != 64 || a.h != 64;
+		fill_visualisation(full ? segment(views[0], 0xF, { 0.1f, drangey }, segment_scale) : views[0]);      // what the net saw: view 0's segment
+		std::vector<Pose> pose(nb_);
+		for (int b = 0; b < nb_; b++) { const float *p = &out[(size_t)b * HT_POSE]; pose[b].position = { p[0], p[1], p[2] }; pose[b].orientation = { p[3], p[4], p[5], p[6] }; }
+		return pose;
+	}
 	// Addition, not a reference name: GatherHandExpectedCNN (handtrack.h:160-173) for a batch of pose sets on this tracker's device, frame b seen by the
 	// heat-map camera hcams[b] (as the single-frame form takes it); segment_frame: train-cnn's compress first (train-cnn.cpp:31-50: the poses in the
 	// camera's frame, the camera at the identity).  The same ExpectedCNN sets as the single-frame form, bit for bit (ht_expected_cnn_batch).
@@ -809,6 +847,25 @@ private:
 		return left_hand ? mirrored(pose) : pose;
 	}
 	// (addition) the frame and its camera under the mirror, by the host mirror calls (ht_mirror_frames, ht_mirror_cams)
+	// the arrays the several-views calls take for one slot: frames [V][h][w], cameras [V][12], planes [V][4] (empty: none)
+	struct view_arrays { int V, w, h; std::vector<unsigned short> depth; std::vector<float> cams, planes; };
+	static view_arrays pack_views(const std::vector<Image<unsigned short>> &views, const std::vector<float4> &mirrors)
+	{
+		view_arrays a;
+		a.V = (int)views.size();
+		if (a.V < 1 || a.V > HT_VIEWS_MAX) throw std::runtime_error("HandTracker: between 1 and HT_VIEWS_MAX views");
+		if (!mirrors.empty() && (int)mirrors.size() != a.V) throw std::runtime_error("HandTracker: one mirror plane per view, or none");
+		a.w = views[0].dim().x; a.h = views[0].dim().y;
+		a.cams.resize((size_t)a.V * HT_CAM);
+		for (int v = 0; v < a.V; v++)
+		{
+			if (views[v].dim().x != a.w || views[v].dim().y != a.h || views[v].raster.size() != (size_t)a.w * a.h) throw std::runtime_error("HandTracker: the views of a call have one size");
+			a.depth.insert(a.depth.end(), views[v].raster.begin(), views[v].raster.end());
+			cam12(views[v].cam, &a.cams[(size_t)v * HT_CAM]);
+		}
+		for (const float4 &m : mirrors) { a.planes.push_back(m.x); a.planes.push_back(m.y); a.planes.push_back(m.z); a.planes.push_back(m.w); }
+		return a;
+	}
 	static void cam12(const DCamera &c, float *cam)
 	{
 		const float v[HT_CAM] = { c.focal().x, c.focal().y, c.principal().x, c.principal().y, c.depth_scale, c.pose.position.x, c.pose.position.y, c.pose.position.z,

@@ -872,6 +872,64 @@ int ht_kpfit_default(ht_kpfit *o);
 int ht_fit_keypoints(ht_ctx *ctx, int which_model, int B, int which, int K, const int *bones, const float *offsets, const int *rel, const int *kind, const float *xyz, const float *pix, const float *weights, const float *cams, const ht_kpfit *o, float *poses, float *resid);
 int ht_fit_keypoints_dev(ht_ctx *ctx, int which_model, int B, int which, int K, const int *bones, const float *offsets, const int *rel, const int *kind, const float *d_xyz, const float *d_pix, const float *d_weights, const float *d_cams, const ht_kpfit *o, float *d_poses, float *d_resid, void *stream);
 
+/* ---- several views (an addition: the reference keeps the pieces -- ImageClip, PlaneSplit, Mirror, MirrorPlaneSplit "to get some view of the back of an object",
+ * misc_image.h:401-485, and a mirror plane in every data set header, dataset.h:24,45 -- and tracks from one camera) ----------------------------------------------
+ * One hand seen by V <= HT_VIEWS_MAX depth cameras at once, and by their mirror images where a view holds a mirror.  Per slot: frames depth [B][V][h][w] (one w x h for
+ * all views of a call), cameras cams [B][V][12] in the usual layout with their poses in ONE tracking space, and optionally mirror planes planes [B][V][4], each in its
+ * view's camera space; NULL, or a plane (0,0,0,FLT_MAX) as dataset.h:45 defaults it, means none.
+ * ht_fuse_views       the views' clouds as one, fp32, one IEEE operation after another (no contraction):
+ *                       1. the views in order, each view's pixels in raster order;
+ *                       2. d = pixel * depth_scale, in range iff d >= range_lo && d < range_hi (FallsWithinRange, misc_image.h:24);
+ *                       3. p = deprojectz(x, y, d) = (((x - cx) / fx) * d, ((y - cy) / fy) * d, d) (misc_image.h:48);
+ *                       4. with a mirror plane, pd = dot(float4(p, 1), plane) (PlaneSplit, misc_image.h:462-473): pd <= -mirror_eps, the point is virtual,
+ *                          p += n * (pd * -2) (Mirror, :474-479), source 2v + 1; pd > mirror_eps, direct, source 2v; otherwise (coplanar) the pixel is dropped.
+ *                          Without a plane every in-range pixel is direct;
+ *                       5. the kept pixels of a view are ranked in raster order, rank r is emitted iff r % fraction == 0 (takesubsample, physmodel.h:58-64);
+ *                       6. an emitted point goes to tracking space by its view's pose, pos + qrot(q, p); a pose that is exactly identity is not applied at all;
+ *                       7. the fused cloud is view-major and keeps the order within a view; direct and mirrored points interleave as they come.
+ *                     The cloud is left where a fit pass reads the slot's prepared points (as ht_stage_prepare or an update leaves theirs), x y z and the source index
+ *                     as a float beside them (the .w the other producers write as 0).  Outputs of the host form, all optional: points [B][cap][4], cut at cap (the
+ *                     point capacity grows to min(cap, V * ceil(w h / fraction)), HT_ERR_ARG if that exceeds HT_POINTS_LIMIT); npoints [B]; per_source [B][2V], the
+ *                     points kept of every source; origins [B][2V][3]: the view's camera position for a direct source, pos + qrot(q, n * (plane.w * -2)) for a
+ *                     mirrored one (the camera's image in the mirror; the camera position again where the view has no plane); *cut, the slots whose cloud was cut.
+ * ht_fuse_views_dev   device arrays, enqueued on `stream`.  Grows the point capacity to V * ceil(w h / fraction) before its launch (one synchronising re-allocation,
+ *                     as ht_reserve_points) and refuses a call that could exceed HT_POINTS_LIMIT, so no cloud is cut.  d_npoints, d_per_source, d_origins, d_cut optional.
+ *                     It cannot read the planes: a view whose plane is neither "none" nor finite with a normal other than zero emits nothing.
+ * ht_views_default    range {0.1, drangey} (handtrack.h:703), fraction = subsample_fraction, mirror_eps 0.02 (PlaneSplit's default).  NULL options mean these.
+ * ht_stage_view_rows  CloudConstraints (physmodel.h:164-181) of model `which` for every fused point with FitPointCloud's force limits (:347), each point's ray from ITS
+ *                     source's origin: CloudConstraint decides "the point lies behind the body" by dot(v - origin, n) > 0 and casts ConvexHitCheck from that origin
+ *                     (:170-171), so a point seen from behind and judged from another camera's origin takes the wrong branch.  rows [B][cap][16] in
+ *                     ht_stage_cloud_rows' layout, nrows [B].  Host buffers, synchronous.
+ * ht_fit_views        `passes` (1..64) times PhysModel::FitPointCloud's sequence on model `which` of slots [0,B) against the fused cloud: the joint ranges brought up to
+ *                     date (HandModelEnhancements), those rows, contacts if physics_use_collision, the solve.  No boundary planes (they assume one viewpoint); the
+ *                     momenta are kept from pass to pass as in update()'s main passes (handtrack.h:769-780); the last solve writes the user poses [B][nb][7]
+ *                     (optional).  The tracker's flags are not touched.  _dev: everything on `stream`, no copy or wait between the passes.  HT_ERR_STATE unless
+ *                     the latest ht_fuse_views of the context covered slots [0,B); points another call leaves there afterwards read as source 0.
+ * ht_update_views_*   ht_update_frames_sized_* on view 0, byte for byte the existing call, then ht_fuse_views of all views and ht_fit_views(0, B, passes), whose poses
+ *                     the caller gets.  The net, the segmentation, FitError and MultiStepSim see view 0 only.  View 0's camera pose must be identity (the reference's
+ *                     PointCloud is camera-local, handtrack.h:703): HT_ERR_ARG in the host form; the device form cannot read the cameras.
+ * Refused before anything grows or runs, the context left usable (HT_ERR_ARG / HT_ERR_STATE): V outside [1, HT_VIEWS_MAX]; a bad range (0 <= range_lo < range_hi),
+ * fraction (>= 1) or mirror_eps (>= 0); in the host forms a plane with a non-finite or zero normal that is not the "none" plane, and an output that overlaps an input
+ * or another output; B outside [1, max_batch]; a context without a hand model; for the fits the exact-order solver build.  Slots >= B and the other model are not
+ * touched.  There is no left-hand form: mirror the inputs with ht_mirror_* and the poses back.  Views of different sizes, the voxel subsample and a net evaluation on
+ * views other than view 0 are not served. */
+#define HT_VIEWS_MAX 4
+typedef struct { float range_lo, range_hi; int fraction; float mirror_eps; } ht_views;
+int ht_views_default(ht_ctx *ctx, ht_views *o);
+int ht_fuse_views(ht_ctx *ctx, const uint16_t *depth, const float *cams, const float *planes, int w, int h, int V, int B, const ht_views *o, float *points, int cap, int *npoints, int *per_source, float *origins, int *cut);
+int ht_fuse_views_dev(ht_ctx *ctx, const uint16_t *d_depth, const float *d_cams, const float *d_planes, int w, int h, int V, int B, const ht_views *o, int *d_npoints, int *d_per_source, float *d_origins, int *d_cut, void *stream);
+int ht_stage_view_rows(ht_ctx *ctx, int which, int B, float *rows, int cap, int *nrows);
+int ht_fit_views(ht_ctx *ctx, int which, int B, int passes, float *poses);
+int ht_fit_views_dev(ht_ctx *ctx, int which, int B, int passes, float *d_poses, void *stream);
+int ht_update_views_sync(ht_ctx *ctx, int side, const uint16_t *depth, const float *cams, const float *planes, int w, int h, int V, float segment_scale, int B, const ht_views *o, int passes, float *poses_out, float *cnn_out);
+int ht_update_views_dev(ht_ctx *ctx, int side, const uint16_t *d_depth, const float *d_cams, const float *d_planes, int w, int h, int V, float segment_scale, const float *d_start_poses, int B, const ht_views *o, int passes, float *d_poses_out, void *stream);
+/* Timing only (tools/bench_views.py): the yardsticks the calls above are measured beside, on device buffers, enqueued on `stream` and not waited for.
+ * ht_debug_prepare_frames_dev   k_prepare_frame alone on B frames [B][h][w] with the tracker's range and fraction, into the slots' prepared points (what an update's input
+ *                               stage launches for full-size frames; takesubsample(PointCloud(..)), handtrack.h:703,751).
+ * ht_debug_fit_rows_pass_dev    one pass of ht_fit_rows' launch sequence on model `which` against the slots' prepared points, without caller rows, the momenta kept. */
+int ht_debug_prepare_frames_dev(ht_ctx *ctx, const uint16_t *d_depth, const float *d_cams, int w, int h, int B, void *stream);
+int ht_debug_fit_rows_pass_dev(ht_ctx *ctx, int which, int B, void *stream);
+
 /* ---- annotation fit loop ---------------------------------------------------------------------------------------------
  * ht_slowfit          replaces  void HandTracker::slowfit(const std::vector<float3> &points, int hold, const std::vector<Pose> &refpose,
  *                     int steps_ = 6, RigidBody *selectrb = NULL, const float3 &spoint, const float3 &rbpoint, const std::vector<float4> &crays)
