@@ -170,7 +170,7 @@ __device__ __forceinline__ void closest_chunk(const ht_model_dev &M, const float
 			const unsigned long long live = __ballot(on);
 			// this lane's faces g, g + 4, ...: the first is taken as it is (std::max_element starts from it), the others replace it when strictly larger; four are
 			// read ahead of their use.  When every pair of the wave sits on a body with the model's largest face count (one count for all bodies of the hand) the
-			// faces up to the last round need no range test; a face index past a body's last reads the next body's planes or the slack behind the copy.
+			// faces up to the last round need no range test; a face index past a body's last reads the next body's planes or the slack behind the copy (ht_plane_slack, ht_device.hpp).
 			// The dot product ((x vx + y vy) + z vz) + w with the x and y products as ONE packed multiply on the (even-aligned) first two registers of the plane
 			// read -- left to itself the compiler packs y with z and copies both into an aligned pair first, two moves per face.  The face index is counted in
 			// its wave-uniform part u (a scalar register; this lane's face is g + u), so that taking a face is a select on a scalar, not an add per face.
@@ -461,7 +461,7 @@ template <bool EXACT> __device__ __forceinline__ void reset_frame(const ht_model
 	const float *cam = cams + (size_t)b * HT_CAM;
 	// the dynamic LDS, phase by phase
 	float4 *const wp = s_planes;                                                                        // PoseFromScratch: 256 weighted points
-	closest_lds &L = *reinterpret_cast<closest_lds *>(s_planes + ((M.plane_off[nb] + 16 + 3) & ~3));      // cloud rows: planes, closest-feature scratch, body table
+	closest_lds &L = *reinterpret_cast<closest_lds *>(s_planes + ((M.plane_off[nb] + ht_plane_slack(M) + 3) & ~3));      // cloud rows: planes, closest-feature scratch, body table
 	float *const tab = reinterpret_cast<float *>(reinterpret_cast<char *>(&L) + ((sizeof(closest_lds) + 15) & ~15));
 	float *const urow = reinterpret_cast<float *>(s_planes);                                            // single-body solve: records, impulse sums, chain
 	float *const usum = urow + (UB_LDS_ROWS + QUAD_CHAIN_SLACK) * CREC;
@@ -978,7 +978,7 @@ void ht_launch_cloud_rows(const ht_model_dev &M, const float *state, const float
 	if (split > passes) split = passes;
 	if (split < 1) split = 1;
 	// `planes`: the frames' boundary-plane rows (k_chamber's) by one more block per frame, behind the cloud-row blocks in dispatch order
-	hipLaunchKernelGGL(k_cloud_rows, dim3(B, split + (planes ? 1 : 0)), dim3(CR_THREADS), ((size_t)M.plane_off[M.nb] + 16) * sizeof(float4), s, M, state, pts, npts, cams, active_flag, take.stride, take.cam_origin, take.mode,
+	hipLaunchKernelGGL(k_cloud_rows, dim3(B, split + (planes ? 1 : 0)), dim3(CR_THREADS), ((size_t)M.plane_off[M.nb] + ht_plane_slack(M)) * sizeof(float4), s, M, state, pts, npts, cams, active_flag, take.stride, take.cam_origin, take.mode,
 	                   lim.microforce, lim.weak_force, lim.cf_max_point, lim.cf_max_sum, lim.unibody_force, rows, nrows, rec ? *rec : none, planes ? *planes : no_planes, ht_tuning_flags());
 }
 void ht_launch_cloud_rows_views(const ht_model_dev &M, const float *state, const float4 *pts, const int *npts, const float *origins, const cloud_limits &lim, float *rows, int *nrows, int B, hipStream_t s,
@@ -987,7 +987,7 @@ void ht_launch_cloud_rows_views(const ht_model_dev &M, const float *state, const
 	const cloud_records none = { nullptr, 0, nullptr, 0.0f };
 	const int pts_max = M.pts_bound > 0 ? M.pts_bound : M.pts_cap, passes = (pts_max + CH - 1) / CH;
 	const int split = B <= 2048 && passes >= 2 ? 2 : 1;      // ht_launch_cloud_rows' rule
-	hipLaunchKernelGGL(k_view_rows, dim3(B, split), dim3(CR_THREADS), ((size_t)M.plane_off[M.nb] + 16) * sizeof(float4), s, M, state, pts, npts, origins, (int)CLOUD_FIT,
+	hipLaunchKernelGGL(k_view_rows, dim3(B, split), dim3(CR_THREADS), ((size_t)M.plane_off[M.nb] + ht_plane_slack(M)) * sizeof(float4), s, M, state, pts, npts, origins, (int)CLOUD_FIT,
 	                   lim.microforce, lim.weak_force, lim.cf_max_point, lim.cf_max_sum, lim.unibody_force, rows, nrows, rec ? *rec : none, ht_tuning_flags());
 }
 // the full-reset branch for the frames list[0 .. *nlist) (all B frames with list == nullptr); many_frames: the caller expects more of them than the device has CUs
@@ -995,7 +995,7 @@ void ht_launch_cloud_rows_views(const ht_model_dev &M, const float *state, const
 void ht_launch_reset(const ht_model_dev &M, const ht_physics_dev &ph, float *state, const float4 *pts, const int *npts, const float *analysis, const float *cams, const int *list, const int *nlist,
                      int n_unibody, const ht_params &par, float *rows, int *nrows, float *scratch, int scratch_stride, int batch, int B, hipStream_t s, bool many_frames, int n_cu, bool exact)
 {
-	const size_t cloud = (((size_t)M.plane_off[M.nb] + 16 + 3) & ~(size_t)3) * sizeof(float4) + ((sizeof(closest_lds) + 15) & ~(size_t)15) + HT_MAXNB * BT * sizeof(float);
+	const size_t cloud = (((size_t)M.plane_off[M.nb] + ht_plane_slack(M) + 3) & ~(size_t)3) * sizeof(float4) + ((sizeof(closest_lds) + 15) & ~(size_t)15) + HT_MAXNB * BT * sizeof(float);
 	const size_t solve = (size_t)(UB_LDS_ROWS + QUAD_CHAIN_SLACK) * (CREC * sizeof(float) + sizeof(float) + sizeof(unsigned short));
 	const size_t dyn = cloud > solve ? cloud : solve;
 	static ht_lds_limit limit; limit.raise(dyn, k_reset<1>, k_reset<2>, k_reset<2, true>);
@@ -1017,7 +1017,7 @@ void ht_launch_fit_error(const ht_model_dev &M, const float *state, const float4
 #ifdef HT_TUNING
 	{ static int done = 0; if (!done) { const int f = ht_tuning_flags(); (void)hipMemcpyToSymbol(HIP_SYMBOL(ht_fit_error_dbg), &f, sizeof(int)); done = 1; } }
 #endif
-	hipLaunchKernelGGL(k_fit_error, dim3(B), dim3(256), ((size_t)M.plane_off[M.nb] + 16) * sizeof(float4), s, M, state, pts, npts, depth, cams, w, h, scale, err, after ? *after : none);
+	hipLaunchKernelGGL(k_fit_error, dim3(B), dim3(256), ((size_t)M.plane_off[M.nb] + ht_plane_slack(M)) * sizeof(float4), s, M, state, pts, npts, depth, cams, w, h, scale, err, after ? *after : none);
 }
 void ht_launch_chamber(const ht_model_dev &M, const float *state, const float *planes, const int *planes_on, float maxforce, float *rows, int *nch, int B, hipStream_t s)
 {

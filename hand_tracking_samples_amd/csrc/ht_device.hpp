@@ -151,6 +151,16 @@ struct ht_model_dev
 	// UnibodyFit's cube proxy (handtrack.h:454-455)
 	float ub_massinv, ub_dampleft; float ub_com[3]; float ub_tinv[9];
 };
+// float4s kept free behind the LDS copy of the face planes (csrc/ht_cloud.hip: stage_planes).  closest_chunk's face scan reads four faces ahead without a range test
+// and discards what lies past a body's last face: up to face npmax + 11 of ANY body, npmax the model's largest face count.  Behind every body but the last that is
+// the next bodies' planes; behind the last it is this slack, which has to reach npmax - (faces of the last body) + 12.  16 where all bodies have one count (the hand).
+__host__ __device__ inline int ht_plane_slack(const ht_model_dev &M)
+{
+	int npmax = 0;
+	for (int b = 0; b < M.nb; b++) { const int np = M.plane_off[b + 1] - M.plane_off[b]; npmax = np > npmax ? np : npmax; }
+	const int need = M.nb > 0 ? npmax - (M.plane_off[M.nb] - M.plane_off[M.nb - 1]) + 12 : 0;
+	return need > 16 ? need : 16;
+}
 
 struct ht_physics_dev      // physics.h:34-47 after handtrack.h:837-838
 {
