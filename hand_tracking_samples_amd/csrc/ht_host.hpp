@@ -131,6 +131,9 @@ struct ht_ctx
 	// [0, views_B) the latest ht_fuse_views filled, and ht_update_views_*'s contiguous copy of view 0's frames and cameras (dev_grow)
 	float *d_view_origins = nullptr; int *d_view_src = nullptr; int views_B = 0;
 	uint16_t *d_view0 = nullptr; size_t view0_cap = 0; float *d_view0_cams = nullptr;
+	// a view's extrinsics (ht_calib.hip): the view's clouds in camera space [calib_B][calib_stride] with their counts [calib_B], the slots' 29 sums
+	// [calib_B][CA_PART] and the transforms [calib_B][8], both float64; all four follow the largest call (calib_reserve: one synchronising re-allocation)
+	float4 *d_calib_pts = nullptr; int *d_calib_n = nullptr; double *d_calib_part = nullptr, *d_calib_T = nullptr; size_t calib_B = 0, calib_stride = 0;
 };
 
 // The net of a side x side input; any other side is refused here, and only here

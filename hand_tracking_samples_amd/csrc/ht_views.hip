@@ -23,10 +23,7 @@
 #include "ht_host.hpp"
 #include "ht_prepare.hpp"
 
-#define FV_THREADS 256
-struct fv_opts { float lo, hi, eps; int fraction; };
-// a view: its intrinsics, its pose in tracking space (posed: not exactly identity), its mirror plane (mirror: it has one; bad: a plane that is neither "none" nor usable)
-struct fv_view { float fx, fy, cx, cy, dscale; v3 pos; v4 q; v4 plane; bool posed, mirror, bad; };
+struct fv_opts { float lo, hi, eps; int fraction; };      // (fv_view, fv_side, fv_emit: ht_prepare.hpp, shared with k_calib_cloud)
 __device__ __forceinline__ fv_view fv_load(const float *__restrict__ cam, const float *__restrict__ plane)
 {
 	fv_view c;
@@ -38,15 +35,6 @@ __device__ __forceinline__ fv_view fv_load(const float *__restrict__ cam, const 
 	c.bad = !none && (!(isfinite(c.plane.x) && isfinite(c.plane.y) && isfinite(c.plane.z) && isfinite(c.plane.w)) || is_zero(xyz(c.plane)));
 	c.mirror = !none && !c.bad;
 	return c;
-}
-// fv_side: what becomes of in-range pixel i with depth d: 0 dropped (coplanar), 1 direct, 2 mirrored; p: the point in the view's camera space, pd: its plane distance.
-// MIRROR is the view's, so a view without a plane pays for none
-template <bool MIRROR> __device__ __forceinline__ int fv_side(const fv_view &c, float eps, int i, int w, float d, float4 &p, float &pd)
-{
-	p = deproject_point((float)(i % w), (float)(i / w), d, c.fx, c.fy, c.cx, c.cy);
-	if (!MIRROR) return 1;
-	pd = dot_plane(c.plane, V3(p.x, p.y, p.z));                    // dot(float4(p, 1), plane), PlaneSplit misc_image.h:468
-	return pd <= -eps ? 2 : pd > eps ? 1 : 0;                      // under (virtual) | over (direct) | coplanar
 }
 // this thread's share of the pixels a view keeps, lanes on neighbouring pixels (the order does not matter to a count).  lo > hi: no pixel is in range (a bad plane)
 template <bool MIRROR> __device__ __forceinline__ int fv_count(const fv_view &c, const uint16_t *__restrict__ src, int npx, int w, float lo, float hi, float eps)
@@ -60,48 +48,6 @@ template <bool MIRROR> __device__ __forceinline__ int fv_count(const fv_view &c,
 		else if (depth_in_range(d, lo, hi)) cnt += fv_side<true>(c, eps, i, w, d, p, pd) != 0 ? 1 : 0;
 	}
 	return cnt;
-}
-// The block's own view, one walk: tile by tile the kept pixels are ranked (the tiles before + the block's prefix + the thread's own) and every fraction-th goes to
-// out[base + rank / fraction] while that is below cap.  Returns the view's kept pixels; nd / nm: the direct and mirrored points this thread wrote
-#define FV_PER 4
-template <bool MIRROR> __device__ __forceinline__ int fv_emit(const fv_view &c, const uint16_t *__restrict__ src, int npx, int w, float lo, float hi, float eps, int fraction, int base, int cap, int v,
-                                                               float4 *__restrict__ out, int &nd, int &nm)
-{
-	const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-	int before = 0;
-	for (int tile = 0; tile < npx; tile += FV_THREADS * FV_PER)
-	{
-		const int i0 = tile + FV_PER * t;
-		float d[FV_PER], pd[FV_PER]; float4 p[FV_PER]; int k[FV_PER];
-		int cnt = 0;
-#pragma unroll
-		for (int j = 0; j < FV_PER; j++)
-		{
-			k[j] = 0; pd[j] = 0.0f;
-			d[j] = i0 + j < npx ? depth_metres(src[i0 + j], c.dscale) : -1.0f;      // (no range holds a negative depth: range_lo >= 0)
-			if (depth_in_range(d[j], lo, hi)) k[j] = fv_side<MIRROR>(c, eps, i0 + j, w, d[j], p[j], pd[j]);
-			cnt += k[j] != 0 ? 1 : 0;
-		}
-		int total;
-		int rank = before + block_prefix256(cnt, lane, wave, total);
-#pragma unroll
-		for (int j = 0; j < FV_PER; j++) if (k[j])
-		{
-			const int idx = base + rank / fraction;
-			if (rank % fraction == 0 && idx < cap)
-			{
-				v3 q = V3(p[j].x, p[j].y, p[j].z);
-				if (k[j] == 2) q = q + xyz(c.plane) * (pd[j] * -2.0f);      // Mirror misc_image.h:477
-				if (c.posed) q = c.pos + qrot(c.q, q);
-				out[idx] = make_float4(q.x, q.y, q.z, (float)(2 * v + (k[j] - 1)));
-				nd += k[j] == 1 ? 1 : 0; nm += k[j] == 2 ? 1 : 0;
-			}
-			rank++;
-		}
-		before += total;
-		__syncthreads();      // the prefix's wave sums are free for the next tile
-	}
-	return before;
 }
 // the source origins of a view in tracking space: the camera's position, and its image in the mirror (the camera-space origin mirrored: n * (plane.w * -2), Mirror
 // misc_image.h:477 on (0,0,0)); a view without a plane has the camera's position in both places

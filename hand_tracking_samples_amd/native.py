@@ -56,6 +56,7 @@ SYMBOLS = (
     "ht_pose_depth_residual", "ht_pose_depth_residual_dev", "ht_pose_mesh_residual", "ht_pose_mesh_residual_dev",
     "ht_kpfit_default", "ht_fit_keypoints", "ht_fit_keypoints_dev",
     "ht_views_default", "ht_fuse_views", "ht_fuse_views_dev", "ht_stage_view_rows", "ht_fit_views", "ht_fit_views_dev", "ht_update_views_sync", "ht_update_views_dev", "ht_debug_prepare_frames_dev", "ht_debug_fit_rows_pass_dev",
+    "ht_calib_default", "ht_calibrate_view", "ht_calibrate_view_dev",
     "ht_comm_available", "ht_comm_unique_id", "ht_comm_init", "ht_comm_info", "ht_gather_poses_dev", "ht_gather_wait", "ht_gather_wait_host", "ht_comm_destroy",
 )
 
@@ -121,6 +122,16 @@ class KpFit(C.Structure):
 class Views(C.Structure):
     """ht_views: the options of ht_fuse_views (Context.views_default() fills in the tracker's figures)"""
     _fields_ = [("range_lo", C.c_float), ("range_hi", C.c_float), ("fraction", C.c_int), ("mirror_eps", C.c_float)]
+
+
+class Calib(C.Structure):
+    """ht_calib: the options of ht_calibrate_view (Context.calib_default() fills in the documented defaults)"""
+    _fields_ = [("range_lo", C.c_float), ("range_hi", C.c_float), ("fraction", C.c_int), ("mode", C.c_int), ("iterations", C.c_int), ("max_dist", C.c_float), ("damping", C.c_float),
+                ("min_points", C.c_int), ("centre", C.c_float * 3)]
+
+
+CALIB_RIG, CALIB_PER_SLOT, CALIB_STATS = 0, 1, 27
+CALIB_FEW_INLIERS, CALIB_BAD_PIVOT = 1, 2
 
 
 class HTError(RuntimeError):
@@ -320,6 +331,10 @@ def load(build_if_missing=True):
     L.ht_update_views_sync.argtypes = [vp, ci, u16p, fp, fp, ci, ci, ci, cf, ci, vwp, ci, fp, fp]
     L.ht_update_views_dev.argtypes = [vp, ci, vp, vp, vp, ci, ci, ci, cf, vp, ci, vwp, ci, vp, vp]
     L.ht_debug_prepare_frames_dev.argtypes = [vp, vp, vp, ci, ci, ci, vp]
+    cbp = C.POINTER(Calib)
+    L.ht_calib_default.argtypes = [vp, cbp]
+    L.ht_calibrate_view.argtypes = [vp, ci, fp, u16p, fp, ci, ci, ci, cbp, fp, dp]
+    L.ht_calibrate_view_dev.argtypes = [vp, ci, vp, vp, vp, ci, ci, ci, cbp, vp, vp, vp]
     L.ht_debug_fit_rows_pass_dev.argtypes = [vp, ci, ci, vp]
     L.ht_keypoint_errors.argtypes = [vp, fp, fp, ci, ci, fp, ci, fp, fp, dp, i64p, i64p]
     L.ht_keypoint_errors_dev.argtypes = [vp, vp, vp, ci, ci, fp, ci, vp, vp, vp, vp, vp, vp]
@@ -1152,6 +1167,34 @@ class Context:
     def update_views_dev(self, side, d_depth, d_cams, w, h, V, segment_scale, d_start, B, d_poses_out, d_planes=None, options=None, passes=3, stream=None):
         self._chk(self.L.ht_update_views_dev(self.h, int(side), d_depth, d_cams, d_planes, int(w), int(h), int(V), float(segment_scale), d_start, int(B), None if options is None else C.byref(options),
                                              int(passes), d_poses_out, stream))
+
+    # -- a view's extrinsics from the tracked hand (ht_mi355x.h "a view's extrinsics")
+    def calib_default(self, **kw):
+        """ht_calib_default (range {0.1, drangey}, fraction = subsample_fraction, RIG, 10 iterations, max_dist 0.03, damping 1e-3, min_points 12, centre 0), then the fields given"""
+        o = Calib()
+        self._chk(self.L.ht_calib_default(self.h, C.byref(o)))
+        for k, v in kw.items():
+            if k not in dict(Calib._fields_):
+                raise TypeError("ht_calib has no field %r" % k)
+            setattr(o, k, tuple(float(x) for x in v) if k == "centre" else v)
+        return o
+
+    def calibrate_view(self, depth, cams, poses=None, which=0, options=None):
+        """depth u16[B,h,w] and cams f32[B,12] of ONE view (its guess in cams[:,5:12]), poses f32[B,nb,7] centre-of-mass poses in tracking space or None for the state of
+        model `which` of slots [0,B) -> (T f32[N,7] mapping the view's camera space to tracking space, stats f64[iterations + 1,N,27]); N = 1 (RIG) or B (PER_SLOT)."""
+        depth = _c(depth, np.uint16); B, h, w = depth.shape
+        cams = _c(cams, np.float32).reshape(B, CAM)
+        poses = None if poses is None else _c(poses, np.float32).reshape(B, self.nb, POSE)
+        o = options if options is not None else self.calib_default()
+        N = B if o.mode == CALIB_PER_SLOT else 1
+        T = np.zeros((N, 7), np.float32); stats = np.zeros((max(o.iterations, 0) + 1, N, CALIB_STATS), np.float64)
+        self._chk(self.L.ht_calibrate_view(self.h, int(which), None if poses is None else _f(poses), depth.ctypes.data_as(C.POINTER(C.c_uint16)), _f(cams), w, h, B, C.byref(o), _f(T),
+                                           stats.ctypes.data_as(C.POINTER(C.c_double))))
+        return T, stats
+
+    def calibrate_view_dev(self, d_depth, d_cams, w, h, B, d_T_out, d_stats, d_poses=None, which=0, options=None, stream=None):
+        """ht_calibrate_view_dev: device pointers, only enqueued on `stream`."""
+        self._chk(self.L.ht_calibrate_view_dev(self.h, int(which), d_poses, d_depth, d_cams, int(w), int(h), int(B), None if options is None else C.byref(options), d_T_out, d_stats, stream))
 
     def keypoint_errors(self, a, b, thr=()):
         """a, b f32[B,K,3] -> dict(dist f32[B,K], frame f32[B,2] (mean, max), sum_kp f64[K], hits_kp i64[T], hits_frame i64[T], and from them mean_kp f64[K],

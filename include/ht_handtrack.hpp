@@ -812,6 +812,42 @@ struct HandTracker                                                              
 		for (int b = 0; b < nb_; b++) { const float *p = &out[(size_t)b * HT_POSE]; pose[b].position = { p[0], p[1], p[2] }; pose[b].orientation = { p[3], p[4], p[5], p[6] }; }
 		return pose;
 	}
+	// Addition, not a reference name (ht_mi355x.h "a view's extrinsics"; the reference never calibrates anything).  CalibrateView: where another depth camera stands, from
+	// the tracked hand alone.  frames: that camera's frames, one per tracked frame (one size; their cameras' intrinsics are read, their poses are not); poses: per frame the
+	// tracked model's centre-of-mass poses in tracking space (handmodel.GetPose() after the update of that frame); guess: the camera's pose as far as it is known.
+	// T maps the camera's space to tracking space (a point p of the view lies at T.position + qrot(T.orientation, p)): write it into that view's DCamera::pose for
+	// update_views.  One T for the batch (HT_CALIB_RIG); the batch is not bounded by the tracker's one slot, as SplitHandsByModel's is not.  stats: the
+	// (iterations + 1) records of HT_CALIB_STATS doubles the C call documents; degenerate: some record carries a flag (too few inliers, a pivot that is not positive).
+	struct CalibOptions : ht_calib { explicit CalibOptions(const HandTracker &t) { ht_calib_default(t.ctx_, this); } };
+	struct ViewCalibration { Pose T; std::vector<double> stats; bool degenerate; };
+	ViewCalibration CalibrateView(const std::vector<Image<unsigned short>> &frames, const std::vector<std::vector<Pose>> &poses, const Pose &guess, const ht_calib *options = nullptr)
+	{
+		const int B = (int)frames.size();
+		if (B < 1 || poses.size() != frames.size()) throw std::runtime_error("CalibrateView: one set of poses per frame, at least one frame");
+		const CalibOptions dflt(*this);
+		ht_calib o = options ? *options : dflt;
+		if (o.mode != HT_CALIB_RIG) throw std::runtime_error("CalibrateView: one transform for the batch (HT_CALIB_RIG); the per-slot mode is the C call's");
+		const int w = frames[0].dim().x, h = frames[0].dim().y;
+		std::vector<unsigned short> depth; std::vector<float> cams((size_t)B * HT_CAM), p7;
+		for (int b = 0; b < B; b++)
+		{
+			if (frames[b].dim().x != w || frames[b].dim().y != h || frames[b].raster.size() != (size_t)w * h) throw std::runtime_error("CalibrateView: the frames of a call have one size");
+			if ((int)poses[b].size() != nb_) throw std::runtime_error("CalibrateView: one pose per body of the tracker's model for every frame");
+			depth.insert(depth.end(), frames[b].raster.begin(), frames[b].raster.end());
+			DCamera c = frames[b].cam; c.pose = guess;
+			cam12(c, &cams[(size_t)b * HT_CAM]);
+			const std::vector<float> f = flat(poses[b]);
+			p7.insert(p7.end(), f.begin(), f.end());
+		}
+		ViewCalibration r;
+		r.stats.assign((size_t)(o.iterations > 0 ? o.iterations + 1 : 1) * HT_CALIB_STATS, 0.0);
+		float T[7];
+		check(ctx_, ht_calibrate_view(ctx_, 0, p7.data(), depth.data(), cams.data(), w, h, B, &o, T, r.stats.data()));
+		r.T.position = { T[0], T[1], T[2] }; r.T.orientation = { T[3], T[4], T[5], T[6] };
+		r.degenerate = false;
+		for (size_t i = 5; i < r.stats.size(); i += HT_CALIB_STATS) r.degenerate = r.degenerate || r.stats[i] != 0.0;
+		return r;
+	}
 	// Addition, not a reference name: GatherHandExpectedCNN (handtrack.h:160-173) for a batch of pose sets on this tracker's device, frame b seen by the
 	// heat-map camera hcams[b] (as the single-frame form takes it); segment_frame: train-cnn's compress first (train-cnn.cpp:31-50: the poses in the
 	// camera's frame, the camera at the identity).  The same ExpectedCNN sets as the single-frame form, bit for bit (ht_expected_cnn_batch).

@@ -930,6 +930,58 @@ int ht_update_views_dev(ht_ctx *ctx, int side, const uint16_t *d_depth, const fl
 int ht_debug_prepare_frames_dev(ht_ctx *ctx, const uint16_t *d_depth, const float *d_cams, int w, int h, int B, void *stream);
 int ht_debug_fit_rows_pass_dev(ht_ctx *ctx, int which, int B, void *stream);
 
+/* ---- a view's extrinsics from the tracked hand (an addition: the reference never calibrates anything, it has no rig) -----------------------------
+ * "Several views" above needs every camera posed in one tracking space.  While view 0 tracks the hand, the tracked model is a known 3-D object in that space and another
+ * view's depth pixels lie on its surface: ht_calibrate_view registers that view's cloud rigidly against the tracked models of a batch of frames, a Gauss-Newton loop
+ * around the tracker's own closest() (physmodel.h:137-162).  depth [B][h][w] and cams [B][12] are the view's frames and cameras, one a slot.
+ *   cloud      per slot, the view's pixels in raster order: d = pixel * depth_scale, kept iff d >= range_lo && d < range_hi (FallsWithinRange, misc_image.h:24),
+ *              p = deprojectz(x, y, d) (misc_image.h:48), every fraction-th kept pixel emitted (takesubsample, physmodel.h:58-64): exactly ht_fuse_views' cloud for
+ *              V = 1, an identity pose and no plane.  The points stay in the camera's space in a buffer of the context's own, grown to ceil(w h / fraction) points a
+ *              slot by one synchronising re-allocation as ht_reserve_points grows its arrays (more than HT_POINTS_LIMIT: HT_ERR_ARG, raise the fraction).  The slots'
+ *              prepared points, both models' states and the tracker's flags are not touched.  Mirror planes are not accepted.
+ *   model      poses == NULL: the state of model `which` (0 handmodel, 1 othermodel) of slots [0,B), B <= max_batch.  Otherwise poses [B][nb][7], centre-of-mass poses
+ *              in tracking space as ht_split_hands_model takes them; no slot is read and B is bounded by 65535 only.  The same poses give the same bits either way.
+ *   transform  T = (pos, q) maps camera space to tracking space as the fused cloud does: x = pos + qrot(q, p).  The guess is the pose in cams[b][5:12].
+ *              HT_CALIB_RIG: one T for the batch (the rig is fixed and the hand moves), N = 1, the guess is slot 0's.  HT_CALIB_PER_SLOT: one T a slot, N = B.
+ *              T is carried in float64.  Per point x is formed in fp32 from T rounded to fp32 (quaternion not renormalised), so closest() sees what a fused cloud holds.
+ *   per point  fp32, one IEEE operation after another in ht_fuse_views' forms (dot = ((ax bx + ay by) + az bz) [+ w], qrot over qmat's columns):
+ *              plane = closest(bodies of slot b, x), bit for bit the reference's (strict "<", the first minimum in body order, both walks);
+ *              r = dot(plane, (x, 1)); n = plane.xyz; J = [n, cross(x - c, n)] about the caller's centre c = o.centre; w = |r| <= max_dist ? 1 : 0.
+ *   sums       29 float64 values S: k = 0..20 the upper triangle of J J^T row by row ((0,0), (0,1), .. (0,5), (1,1), ..), 21..26 J r, 27 the truncated cost
+ *              (r r < m ? r r : m with m = (double)max_dist * (double)max_dist), 28 the inlier count.  Every product is of the two fp32 terms widened to float64;
+ *              the first 27 take w ? term : 0.0, the cost takes every point.
+ *   order      part of the definition.  Thread t of 256 adds its points t, t + 256, .. in cloud order onto +0.0.  A wave's 64 threads are reduced by the butterfly
+ *              v[l] += v[l ^ 32], then ^ 16, 8, 4, 2, 1 (five levels of pairwise adds; every lane holds the same bits); the four waves as (w0 + w1) + (w2 + w3).
+ *              In RIG mode the slots' sums are added in slot order onto slot 0's.  No floating-point atomics, nothing depends on arrival.
+ *   step       float64, + - * / and sqrt only, no contraction.  A is S's symmetric matrix with A_ii *= 1 + (double)damping, g = S[21..26].  Cholesky A = L L^T column by
+ *              column: s = A_jj - L_j0 L_j0 - .. (k ascending); the pivot s must be > 0; L_jj = sqrt(s); L_ij = (A_ij - L_i0 L_j0 - ..) / L_jj.  Forward
+ *              y_i = (-g_i - L_i0 y_0 - ..) / L_ii, back d_i = (y_i - L_{i+1,i} d_{i+1} - .. - L_{5,i} d_5) / L_ii (k ascending).  dt = d[0..2], dw = d[3..5].
+ *              dq = (dw / 2, 1) / sqrt(((x x + y y) + z z) + 1), q <- qmul(dq, q) / its length, pos <- (c + qrot(dq, pos - c)) + dt, qmul and qrot in the forms above.
+ *   degenerate fewer than min_points inliers (flag bit 0), a pivot that is not > 0 or a step that is not finite (bit 1): the step is zero, T keeps its bits.
+ *              A NaN never comes out of finite inputs.
+ *   iterations every one of o.iterations (0..64) is the same pair of launches on the caller's stream, one more evaluates the final state.  iterations = 0 evaluates
+ *              the guess and returns its cost: the way to score any T.
+ *   T_out      fp32 [N][7], T rounded.  stats float64 [iterations + 1][N][HT_CALIB_STATS]: row i describes the state before step i, row `iterations` the final state
+ *              (no step: |dt| = |dw| = 0, flag bit 0 only).  A record: inliers, points, truncated cost, |dt|, |dw|, flag, then the 21 entries of the undamped A in
+ *              S's order -- a flat hand shows as a sliding direction in A.
+ * ht_calib_default    range {0.1, drangey}, fraction = subsample_fraction, HT_CALIB_RIG, 10 iterations, max_dist 0.03 m, damping 1e-3, min_points 12, centre (0,0,0).
+ *                     NULL options mean these.
+ * ht_calibrate_view   host arrays, synchronous.  ht_calibrate_view_dev: device arrays (d_stats and d_T_out 4-byte aligned), everything enqueued on `stream`, no host
+ *                     wait inside but the re-allocation above.
+ * Refused before anything grows or runs, the context left usable (HT_ERR_ARG / HT_ERR_STATE): frames or cameras missing, w or h outside [1, 4096]; T_out or stats NULL;
+ * which not 0 or 1; B < 1 or beyond the bound above; a bad range (0 <= range_lo < range_hi, finite), fraction (>= 1), mode, iterations (0..64), max_dist (> 0, finite),
+ * damping (>= 0, finite), min_points (>= 0) or centre (finite); a context without a hand model.  Out of scope: estimating a mirror plane, intrinsics, time offsets
+ * between cameras, several views in one call (call once a view), the overlapped arrangement, and feeding T back into ht_update_views_* (the caller writes it into cams). */
+#define HT_CALIB_RIG 0
+#define HT_CALIB_PER_SLOT 1
+#define HT_CALIB_STATS 27
+#define HT_CALIB_FEW_INLIERS 1
+#define HT_CALIB_BAD_PIVOT 2
+typedef struct { float range_lo, range_hi; int fraction, mode, iterations; float max_dist, damping; int min_points; float centre[3]; } ht_calib;
+int ht_calib_default(ht_ctx *ctx, ht_calib *o);
+int ht_calibrate_view(ht_ctx *ctx, int which, const float *poses, const uint16_t *depth, const float *cams, int w, int h, int B, const ht_calib *o, float *T_out, double *stats);
+int ht_calibrate_view_dev(ht_ctx *ctx, int which, const float *d_poses, const uint16_t *d_depth, const float *d_cams, int w, int h, int B, const ht_calib *o, float *d_T_out, double *d_stats, void *stream);
+
 /* ---- annotation fit loop ---------------------------------------------------------------------------------------------
  * ht_slowfit          replaces  void HandTracker::slowfit(const std::vector<float3> &points, int hold, const std::vector<Pose> &refpose,
  *                     int steps_ = 6, RigidBody *selectrb = NULL, const float3 &spoint, const float3 &rbpoint, const std::vector<float4> &crays)
