@@ -128,6 +128,7 @@ def lib():
         L.ho_epa_peak_tris.argtypes = []; L.ho_epa_peak_tris.restype = C.c_int
         L.ho_body_ptr.argtypes = [C.c_void_p, C.c_int]; L.ho_body_ptr.restype = C.c_void_p
         L.ho_scale.argtypes = [C.c_void_p, C.c_float]
+        L.ho_physics_update.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.c_void_p, C.POINTER(Linear), C.c_int, C.c_int, C.POINTER(Angular), C.c_int]; L.ho_physics_update.restype = None
         L.ho_cnn_train.argtypes = [fp, fp, fp, C.c_float]; L.ho_cnn_train.restype = C.c_float
         L.ho_cnn_train_layers.argtypes = [fp, fp, fp, C.c_float, C.POINTER(fp), C.POINTER(fp)]; L.ho_cnn_train_layers.restype = C.c_float
         L.ho_expected_cnn.argtypes = [fp, C.POINTER(Camera), fp, fp]
