@@ -15,61 +15,10 @@
 // (w0 + w1) + (w2 + w3).  Partials go out per slot.  k_calib_solve: one block of 64 lanes a transform; a lane a sum adds the slots' partials in slot order (RIG) or
 // takes its slot's, lane 0 runs the 6 x 6 Cholesky step unrolled in registers and commits T, the lanes write the record.  Every loop is bounded by a count known when
 // it is entered; no lane waits for another but at the block's barriers; no floating-point atomic anywhere.
-#include <limits.h>
-#include <string.h>
-#include <math.h>
-#include "ht_host.hpp"
-#include "ht_prepare.hpp"
+#include "ht_calib_common.hpp"
 
-#define CA_THREADS 256
-#define CA_BT 32       // floats per body-table entry, k_split_model's layout: pos 0..2 | radius 3 | rinner 4 | invp 5..7 | RI columns 8..16 | RF columns 17..25 | first face, faces (as integers) 26, 27
 #define CA_NSUM 29     // 21 of J J^T's upper triangle, 6 of J r, the truncated cost, the inliers
 #define CA_PART 32     // doubles a slot's partial takes: the sums, then the slot's point count
-#define CA_MAX_ITER 64
-#define CA_MAX_B 65535
-
-extern __shared__ __attribute__((aligned(16))) float4 ca_planes[];      // all face planes of the model
-
-// closest(rigidbodies, v), physmodel.h:137-162, for one point by one lane against the bodies of `tab`: the plane it returns (sm_closest of ht_split_model.hip keeps the
-// distance alone).  dmin is dot(pmin, (v, 1)) throughout, as the reference re-evaluates it
-__device__ __forceinline__ v4 ca_closest(const float *tab, int nb, v3 v)
-{
-	v4 pmin = V4(0, 0, 0, FLT_MAX);
-	float dmin = dot_plane(pmin, v);
-	for (int b = 0; b < nb; b++)      // :141-150
-	{
-		const float *t = tab + b * CA_BT;
-		const v3 pos = V3(t[0], t[1], t[2]);
-		const v3 n = safenormalize(v - pos);
-		const v4 p = V4(n, -dot(pos, n) - t[4]);
-		const float d = dot_plane(p, v);
-		if (d < dmin) { dmin = d; pmin = p; }
-	}
-	for (int b = 0; b < nb; b++)      // :151-160
-	{
-		const float *t = tab + b * CA_BT;
-		const v3 pos = V3(t[0], t[1], t[2]);
-		if (length(v - pos) - t[3] > dmin) continue;
-		const v3 X = V3(t[8], t[9], t[10]), Y = V3(t[11], t[12], t[13]), Z = V3(t[14], t[15], t[16]);
-		const v3 vl = V3(t[5], t[6], t[7]) + ((X * v.x + Y * v.y) + Z * v.z);      // pose.inverse() * v
-		const float4 *pl = ca_planes + __float_as_int(t[26]);
-		const int np = __float_as_int(t[27]);
-		float4 f = pl[0];      // mostabove :127-131: std::max_element keeps the first maximum
-		float best = dot_plane(V4(f.x, f.y, f.z, f.w), vl);
-		for (int i = 1; i < np; i++)
-		{
-			const float4 g = pl[i];
-			const float d = dot_plane(V4(g.x, g.y, g.z, g.w), vl);
-			if (best < d) { best = d; f = g; }
-		}
-		const v3 FX = V3(t[17], t[18], t[19]), FY = V3(t[20], t[21], t[22]), FZ = V3(t[23], t[24], t[25]);
-		const v3 n = (FX * f.x + FY * f.y) + FZ * f.z;      // Pose::TransformPlane, geometric.h:124
-		const v4 p = V4(n, f.w - dot(pos, n));
-		const float d = dot_plane(p, v);
-		if (d < dmin) { dmin = d; pmin = p; }
-	}
-	return pmin;
-}
 
 // depth [B][h][w], cams [B][12] -> pts [B][stride] in camera space, npts [B]; T [N][8]: the guess widened (N = B per slot, else slot 0's alone).  stride holds every
 // point a frame can give, so nothing is cut
@@ -94,27 +43,9 @@ __global__ __launch_bounds__(CA_THREADS) void k_calib_accum(const ht_model_dev M
 {
 	__shared__ __align__(16) float tab[HT_MAXNB * CA_BT];
 	__shared__ double red[CA_THREADS / 64][CA_NSUM];
-	const int t = threadIdx.x, lane = t & 63, wave = t >> 6, b = blockIdx.x;
+	const int t = threadIdx.x, b = blockIdx.x;
 	const int nb = M.nb;
-	{
-		const int np = M.plane_off[nb];
-		for (int i = t; i < np; i += CA_THREADS) ca_planes[i] = M.planes[i];
-	}
-	if (t < nb)
-	{
-		const float *p = poses + ((size_t)b * (unsigned)nb + (unsigned)t) * (unsigned)pose_stride;
-		const v3 pos = V3(p[0], p[1], p[2]);
-		const v4 q = V4(p[3], p[4], p[5], p[6]);
-		const float *bc = M.bodyc + t * HT_BC;
-		const xf pi = inverse(XF(pos, q));
-		const m3 ri = qmat(pi.q), rf = qmat(q);
-		float *e = &tab[t * CA_BT];
-		e[0] = pos.x; e[1] = pos.y; e[2] = pos.z; e[3] = bc[HT_BC_RADIUS]; e[4] = bc[HT_BC_RINNER];
-		e[5] = pi.p.x; e[6] = pi.p.y; e[7] = pi.p.z;
-		e[8] = ri.x.x; e[9] = ri.x.y; e[10] = ri.x.z; e[11] = ri.y.x; e[12] = ri.y.y; e[13] = ri.y.z; e[14] = ri.z.x; e[15] = ri.z.y; e[16] = ri.z.z;
-		e[17] = rf.x.x; e[18] = rf.x.y; e[19] = rf.x.z; e[20] = rf.y.x; e[21] = rf.y.y; e[22] = rf.y.z; e[23] = rf.z.x; e[24] = rf.z.y; e[25] = rf.z.z;
-		e[26] = __int_as_float(M.plane_off[t]); e[27] = __int_as_float(M.plane_off[t + 1] - M.plane_off[t]);
-	}
+	ca_stage(M, poses, pose_stride, b, tab);
 	const double *Tb = T + (size_t)(per_slot ? b : 0) * 8;
 	const v3 tp = V3((float)Tb[0], (float)Tb[1], (float)Tb[2]);
 	const v4 tq = V4((float)Tb[3], (float)Tb[4], (float)Tb[5], (float)Tb[6]);
@@ -146,25 +77,10 @@ __global__ __launch_bounds__(CA_THREADS) void k_calib_accum(const ht_model_dev M
 		acc[27] += r2 < md2 ? r2 : md2;
 		acc[28] += in ? 1.0 : 0.0;
 	}
-	// the wave: a fixed butterfly through registers; the waves: 4 x 29 doubles of LDS
-#pragma unroll
-	for (int k = 0; k < CA_NSUM; k++)
-	{
-		double v = acc[k];
-#pragma unroll
-		for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
-		if (lane == 0) red[wave][k] = v;
-	}
-	__syncthreads();
-	if (t < CA_NSUM) part[(size_t)b * CA_PART + t] = (red[0][t] + red[1][t]) + (red[2][t] + red[3][t]);
-	else if (t == CA_NSUM) part[(size_t)b * CA_PART + CA_NSUM] = (double)n;
+	ca_reduce<CA_NSUM>(acc, red, part + (size_t)b * CA_PART, n);
 }
 
 struct ca_step { double damping, min_points, cx, cy, cz; };
-// a float64 as two words: the caller's stats are 4-byte aligned and no more
-__device__ __forceinline__ void ca_store(unsigned *at, double v) { at[0] = (unsigned)__double2loint(v); at[1] = (unsigned)__double2hiint(v); }
-__device__ __forceinline__ bool ca_finite(double v) { return fabs(v) <= DBL_MAX; }      // false for NaN too
-
 // part [B][CA_PART] -> T [N][8] stepped (unless last), T_out [N][7], row [N][HT_CALIB_STATS] as words.  Block = transform
 __global__ __launch_bounds__(64) void k_calib_solve(const double *__restrict__ part, int B, int per_slot, const ca_step o, int last, double *__restrict__ T, float *__restrict__ T_out, unsigned *__restrict__ row)
 {
@@ -185,7 +101,7 @@ __global__ __launch_bounds__(64) void k_calib_solve(const double *__restrict__ p
 	int flag = S[28] < o.min_points ? HT_CALIB_FEW_INLIERS : 0;
 	if (!last && !flag)
 	{
-		double L[6][6], y[6], d[6];
+		double L[6][6], g[6], d[6], n[7];
 		{
 			int k = 0;
 #pragma unroll
@@ -195,61 +111,16 @@ __global__ __launch_bounds__(64) void k_calib_solve(const double *__restrict__ p
 		}
 		const double scale = 1.0 + o.damping;
 #pragma unroll
-		for (int i = 0; i < 6; i++) L[i][i] = L[i][i] * scale;
-		bool ok = true;
-#pragma unroll
-		for (int j = 0; j < 6; j++)
-		{
-			double v = L[j][j];
-#pragma unroll
-			for (int k = 0; k < j; k++) v -= L[j][k] * L[j][k];
-			if (!(v > 0.0)) { ok = false; v = 1.0; }
-			const double pj = sqrt(v);
-			L[j][j] = pj;
-#pragma unroll
-			for (int i = j + 1; i < 6; i++)
-			{
-				double u = L[i][j];
-#pragma unroll
-				for (int k = 0; k < j; k++) u -= L[i][k] * L[j][k];
-				L[i][j] = u / pj;
-			}
-		}
-#pragma unroll
-		for (int i = 0; i < 6; i++)
-		{
-			double v = -S[21 + i];
-#pragma unroll
-			for (int k = 0; k < i; k++) v -= L[i][k] * y[k];
-			y[i] = v / L[i][i];
-		}
-#pragma unroll
-		for (int i = 5; i >= 0; i--)
-		{
-			double v = y[i];
-#pragma unroll
-			for (int k = i + 1; k < 6; k++) v -= L[k][i] * d[k];
-			d[i] = v / L[i][i];
-		}
-		// the candidate
-		const double hx = d[3] * 0.5, hy = d[4] * 0.5, hz = d[5] * 0.5;
-		const double hl = sqrt(((hx * hx + hy * hy) + hz * hz) + 1.0);
-		const double ax = hx / hl, ay = hy / hl, az = hz / hl, aw = 1.0 / hl;      // dq
-		const double bx = Ts[3], by = Ts[4], bz = Ts[5], bw = Ts[6];
-		double qx = ax * bw + aw * bx + ay * bz - az * by, qy = ay * bw + aw * by + az * bx - ax * bz, qz = az * bw + aw * bz + ax * by - ay * bx, qw = aw * bw - ax * bx - ay * by - az * bz;
-		const double ql = sqrt(((qx * qx + qy * qy) + qz * qz) + qw * qw);
-		qx = qx / ql; qy = qy / ql; qz = qz / ql; qw = qw / ql;
-		const double px = Ts[0] - o.cx, py = Ts[1] - o.cy, pz = Ts[2] - o.cz;
-		const double Xx = aw * aw + ax * ax - ay * ay - az * az, Xy = (ax * ay + az * aw) * 2.0, Xz = (az * ax - ay * aw) * 2.0;
-		const double Yx = (ax * ay - az * aw) * 2.0, Yy = aw * aw - ax * ax + ay * ay - az * az, Yz = (ay * az + ax * aw) * 2.0;
-		const double Zx = (az * ax + ay * aw) * 2.0, Zy = (ay * az - ax * aw) * 2.0, Zz = aw * aw - ax * ax - ay * ay + az * az;
-		const double nx = (o.cx + ((Xx * px + Yx * py) + Zx * pz)) + d[0], ny = (o.cy + ((Xy * px + Yy * py) + Zy * pz)) + d[1], nz = (o.cz + ((Xz * px + Yz * py) + Zz * pz)) + d[2];
-		ok = ok && ca_finite(nx) && ca_finite(ny) && ca_finite(nz) && ca_finite(qx) && ca_finite(qy) && ca_finite(qz) && ca_finite(qw);
+		for (int i = 0; i < 6; i++) { L[i][i] = L[i][i] * scale; g[i] = -S[21 + i]; }
+		bool ok = ca_cholesky<6>(L);
+		ca_substitute<6>(L, g, d);
+		ok = ca_candidate(Ts, d, o.cx, o.cy, o.cz, n) && ok;
 #pragma unroll
 		for (int i = 0; i < 6; i++) ok = ok && ca_finite(d[i]);
 		if (ok)
 		{
-			Ts[0] = nx; Ts[1] = ny; Ts[2] = nz; Ts[3] = qx; Ts[4] = qy; Ts[5] = qz; Ts[6] = qw;
+#pragma unroll
+			for (int i = 0; i < 7; i++) Ts[i] = n[i];
 			ndt = sqrt((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]); ndw = sqrt((d[3] * d[3] + d[4] * d[4]) + d[5] * d[5]);
 		}
 		else flag |= HT_CALIB_BAD_PIVOT;
@@ -269,7 +140,6 @@ extern "C" int ht_calib_default(ht_ctx *ctx, ht_calib *o)
 	o->centre[0] = o->centre[1] = o->centre[2] = 0.0f;
 	return HT_OK;
 }
-struct ca_call { ht_calib o; int bound, N; };      // bound: the most points a slot's cloud can have; N: transforms
 // every refusal that needs no device, before anything grows or runs (a context that never came up answers them too)
 int ht_calib_check(ht_ctx *ctx, const char *fn, int which, const void *poses, const void *depth, const void *cams, int w, int h, int B, const ht_calib *opt, const void *T_out, const void *stats, ca_call &c)
 {
@@ -295,12 +165,12 @@ int ht_calib_check(ht_ctx *ctx, const char *fn, int which, const void *poses, co
 }
 static const size_t CA_LDS_FIXED = sizeof(float) * HT_MAXNB * CA_BT + sizeof(double) * (CA_THREADS / 64) * CA_NSUM + 64;
 // what needs the device but launches nothing: the context's state, the kernel's LDS, and the buffers grown to this call (one synchronising re-allocation, as
-// ht_reserve_points: nothing of the context's can still be reading the outgrown ones)
-static int calib_reserve(ht_ctx *ctx, const char *fn, const ca_call &c, int B)
+// ht_reserve_points: nothing of the context's can still be reading the outgrown ones).  lds_fixed: the static LDS of the caller's accumulate kernel
+int ht_calib_reserve(ht_ctx *ctx, const char *fn, const ca_call &c, int B, size_t lds_fixed)
 {
 	if (!ctx->ready) { ctx->err = "context not initialised (ht_create failed)"; return HT_ERR_STATE; }
 	if (ctx->cnn_only) { ctx->err = std::string(fn) + ": this context was created without a hand model (CNN only)"; return HT_ERR_STATE; }
-	if ((size_t)ctx->model.plane_off[ctx->model.nb] * sizeof(float4) + CA_LDS_FIXED > 80 * 1024) { ctx->err = std::string(fn) + ": the model's face planes do not fit the kernel's LDS"; return HT_ERR_STATE; }
+	if ((size_t)ctx->model.plane_off[ctx->model.nb] * sizeof(float4) + lds_fixed > 80 * 1024) { ctx->err = std::string(fn) + ": the model's face planes do not fit the kernel's LDS"; return HT_ERR_STATE; }
 	const size_t stride = ((size_t)c.bound + 63) & ~(size_t)63;
 	if ((size_t)B <= ctx->calib_B && stride <= ctx->calib_stride) return HT_OK;
 	ht_device_guard dev_guard_(ctx->device);
@@ -314,6 +184,12 @@ static int calib_reserve(ht_ctx *ctx, const char *fn, const ca_call &c, int B)
 	ctx->d_calib_pts = pts; ctx->d_calib_n = n; ctx->d_calib_part = part; ctx->d_calib_T = T; ctx->calib_B = nB; ctx->calib_stride = ns;
 	return HT_OK;
 }
+void ht_calib_cloud(ht_ctx *ctx, const ca_call &c, const uint16_t *d_depth, const float *d_cams, int w, int h, int B, int per_slot, hipStream_t s)
+{
+	ht_prof_scope ps(ctx, "k_calib_cloud", s);
+	hipLaunchKernelGGL(k_calib_cloud, dim3((unsigned)B), dim3(FV_THREADS), 0, s, d_depth, d_cams, w, h, c.o.range_lo, c.o.range_hi, c.o.fraction, per_slot, ctx->d_calib_pts, (int)ctx->calib_stride, ctx->d_calib_n,
+	                   ctx->d_calib_T);
+}
 // the launches, on s alone: the cloud, then iterations + 1 times the pair (accumulate, solve); the last pair evaluates the final state and steps nothing
 static int calib_enqueue(ht_ctx *ctx, const ca_call &c, int which, const float *d_poses, const uint16_t *d_depth, const float *d_cams, int w, int h, int B, float *d_T_out, double *d_stats, hipStream_t s)
 {
@@ -321,10 +197,7 @@ static int calib_enqueue(ht_ctx *ctx, const ca_call &c, int which, const float *
 	const int per_slot = o.mode == HT_CALIB_PER_SLOT ? 1 : 0, stride = (int)ctx->calib_stride;
 	const float *poses = d_poses ? d_poses : ctx->d_state[which];
 	const int pose_stride = d_poses ? HT_POSE : HT_STATE_STRIDE;
-	{
-		ht_prof_scope ps(ctx, "k_calib_cloud", s);
-		hipLaunchKernelGGL(k_calib_cloud, dim3((unsigned)B), dim3(FV_THREADS), 0, s, d_depth, d_cams, w, h, o.range_lo, o.range_hi, o.fraction, per_slot, ctx->d_calib_pts, stride, ctx->d_calib_n, ctx->d_calib_T);
-	}
+	ht_calib_cloud(ctx, c, d_depth, d_cams, w, h, B, per_slot, s);
 	const size_t dyn = (size_t)ctx->model.plane_off[ctx->model.nb] * sizeof(float4);
 	static ht_lds_limit limit; limit.raise(dyn, k_calib_accum);
 	const ca_step st = { (double)o.damping, (double)o.min_points, (double)o.centre[0], (double)o.centre[1], (double)o.centre[2] };
@@ -348,7 +221,7 @@ extern "C" int ht_calibrate_view_dev(ht_ctx *ctx, int which, const float *d_pose
 	ca_call c;
 	{ const int r = ht_calib_check(ctx, "ht_calibrate_view_dev", which, d_poses, d_depth, d_cams, w, h, B, o, d_T_out, d_stats, c); if (r) return r; }
 	if (((uintptr_t)d_T_out | (uintptr_t)d_stats) & 3) { ctx->err = "ht_calibrate_view_dev: d_T_out and d_stats must be 4-byte aligned"; return HT_ERR_ARG; }
-	{ const int r = calib_reserve(ctx, "ht_calibrate_view_dev", c, B); if (r) return r; }
+	{ const int r = ht_calib_reserve(ctx, "ht_calibrate_view_dev", c, B, CA_LDS_FIXED); if (r) return r; }
 	ht_device_guard dev_guard_(ctx->device);
 	return calib_enqueue(ctx, c, which, d_poses, d_depth, d_cams, w, h, B, d_T_out, d_stats, ht_user_stream(ctx, stream));
 }
@@ -373,7 +246,7 @@ extern "C" int ht_calibrate_view(ht_ctx *ctx, int which, const float *poses, con
 		const ql_buf in[3] = { { seg[0].host, seg[0].bytes }, { seg[1].host, seg[1].bytes }, { seg[2].host, seg[2].bytes } }, out[2] = { { seg[3].host, seg[3].bytes }, { seg[4].host, seg[4].bytes } };
 		if (ql_any_overlap(in, 3, out, 2)) { ctx->err = "ht_calibrate_view: an output overlaps an input or the other output"; return HT_ERR_ARG; }
 	}
-	{ const int r = calib_reserve(ctx, "ht_calibrate_view", c, B); if (r) return r; }
+	{ const int r = ht_calib_reserve(ctx, "ht_calibrate_view", c, B, CA_LDS_FIXED); if (r) return r; }
 	ht_device_guard dev_guard_(ctx->device);
 	return ht_staged_call(ctx, seg, n, [&](hipStream_t s)
 	                      { return calib_enqueue(ctx, c, which, (const float *)seg[0].dev, (const uint16_t *)seg[1].dev, (const float *)seg[2].dev, w, h, B, (float *)seg[3].dev, (double *)seg[4].dev, s); });

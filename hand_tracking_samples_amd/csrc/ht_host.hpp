@@ -134,6 +134,9 @@ struct ht_ctx
 	// a view's extrinsics (ht_calib.hip): the view's clouds in camera space [calib_B][calib_stride] with their counts [calib_B], the slots' 29 sums
 	// [calib_B][CA_PART] and the transforms [calib_B][8], both float64; all four follow the largest call (calib_reserve: one synchronising re-allocation)
 	float4 *d_calib_pts = nullptr; int *d_calib_n = nullptr; double *d_calib_part = nullptr, *d_calib_T = nullptr; size_t calib_B = 0, calib_stride = 0;
+	// the hand's size (ht_size.hip) takes the cloud, its counts and the transforms above, and keeps the slots' 37 sums with the solve's per-slot pieces [size_B][SZ_PART]
+	// and the scales [size_B], both float64 (size_reserve, the same growth)
+	double *d_size_part = nullptr, *d_size_s = nullptr; size_t size_B = 0;
 };
 
 // The net of a side x side input; any other side is refused here, and only here

@@ -57,6 +57,7 @@ SYMBOLS = (
     "ht_kpfit_default", "ht_fit_keypoints", "ht_fit_keypoints_dev",
     "ht_views_default", "ht_fuse_views", "ht_fuse_views_dev", "ht_stage_view_rows", "ht_fit_views", "ht_fit_views_dev", "ht_update_views_sync", "ht_update_views_dev", "ht_debug_prepare_frames_dev", "ht_debug_fit_rows_pass_dev",
     "ht_calib_default", "ht_calibrate_view", "ht_calibrate_view_dev",
+    "ht_size_default", "ht_estimate_scale", "ht_estimate_scale_dev",
     "ht_comm_available", "ht_comm_unique_id", "ht_comm_init", "ht_comm_info", "ht_gather_poses_dev", "ht_gather_wait", "ht_gather_wait_host", "ht_comm_destroy",
 )
 
@@ -132,6 +133,21 @@ class Calib(C.Structure):
 
 CALIB_RIG, CALIB_PER_SLOT, CALIB_STATS = 0, 1, 27
 CALIB_FEW_INLIERS, CALIB_BAD_PIVOT = 1, 2
+
+
+class Size(C.Structure):
+    """ht_size: the options of ht_estimate_scale (Context.size_default() fills in the documented defaults)"""
+    _fields_ = [("range_lo", C.c_float), ("range_hi", C.c_float), ("fraction", C.c_int), ("mode", C.c_int), ("free_pose", C.c_int), ("iterations", C.c_int), ("max_dist", C.c_float),
+                ("damping", C.c_float), ("min_points", C.c_int), ("scale0", C.c_float), ("scale_lo", C.c_float), ("scale_hi", C.c_float)]
+
+
+SIZE_SHARED, SIZE_PER_SLOT, SIZE_STATS, SIZE_SLOT_STATS = 0, 1, 6, 3
+SIZE_FEW_INLIERS, SIZE_BAD_PIVOT, SIZE_CLAMPED = 1, 2, 4
+
+
+def size_row(N, B):
+    """HT_SIZE_ROW: the float64 values of one row of ht_estimate_scale's stats"""
+    return N * SIZE_STATS + B * SIZE_SLOT_STATS
 
 
 class HTError(RuntimeError):
@@ -335,6 +351,10 @@ def load(build_if_missing=True):
     L.ht_calib_default.argtypes = [vp, cbp]
     L.ht_calibrate_view.argtypes = [vp, ci, fp, u16p, fp, ci, ci, ci, cbp, fp, dp]
     L.ht_calibrate_view_dev.argtypes = [vp, ci, vp, vp, vp, ci, ci, ci, cbp, vp, vp, vp]
+    szp = C.POINTER(Size)
+    L.ht_size_default.argtypes = [vp, szp]
+    L.ht_estimate_scale.argtypes = [vp, ci, fp, u16p, fp, ci, ci, ci, szp, fp, fp, dp]
+    L.ht_estimate_scale_dev.argtypes = [vp, ci, vp, vp, vp, ci, ci, ci, szp, vp, vp, vp, vp]
     L.ht_debug_fit_rows_pass_dev.argtypes = [vp, ci, ci, vp]
     L.ht_keypoint_errors.argtypes = [vp, fp, fp, ci, ci, fp, ci, fp, fp, dp, i64p, i64p]
     L.ht_keypoint_errors_dev.argtypes = [vp, vp, vp, ci, ci, fp, ci, vp, vp, vp, vp, vp, vp]
@@ -1195,6 +1215,34 @@ class Context:
     def calibrate_view_dev(self, d_depth, d_cams, w, h, B, d_T_out, d_stats, d_poses=None, which=0, options=None, stream=None):
         """ht_calibrate_view_dev: device pointers, only enqueued on `stream`."""
         self._chk(self.L.ht_calibrate_view_dev(self.h, int(which), d_poses, d_depth, d_cams, int(w), int(h), int(B), None if options is None else C.byref(options), d_T_out, d_stats, stream))
+
+    # -- the hand's size from tracked frames (ht_mi355x.h "the hand's size")
+    def size_default(self, **kw):
+        """ht_size_default (ht_calib_default's range, fraction, max_dist, damping and min_points; SHARED, free_pose 1, 10 iterations, scale0 1 in [0.5, 2]), then the fields given"""
+        o = Size()
+        self._chk(self.L.ht_size_default(self.h, C.byref(o)))
+        for k, v in kw.items():
+            if k not in dict(Size._fields_):
+                raise TypeError("ht_size has no field %r" % k)
+            setattr(o, k, v)
+        return o
+
+    def estimate_scale(self, depth, cams, poses=None, which=0, options=None):
+        """depth u16[B,h,w] and cams f32[B,12] of ONE view, poses f32[B,nb,7] centre-of-mass poses in tracking space or None for the state of model `which` of slots [0,B)
+        -> (scale f32[N], T f32[B,7], stats f64[iterations + 1, size_row(N, B)]); N = 1 (SHARED) or B (PER_SLOT).  Applying the scale is ht_scale's."""
+        depth = _c(depth, np.uint16); B, h, w = depth.shape
+        cams = _c(cams, np.float32).reshape(B, CAM)
+        poses = None if poses is None else _c(poses, np.float32).reshape(B, self.nb, POSE)
+        o = options if options is not None else self.size_default()
+        N = B if o.mode == SIZE_PER_SLOT else 1
+        scale = np.zeros(N, np.float32); T = np.zeros((B, 7), np.float32); stats = np.zeros((max(o.iterations, 0) + 1, size_row(N, B)), np.float64)
+        self._chk(self.L.ht_estimate_scale(self.h, int(which), None if poses is None else _f(poses), depth.ctypes.data_as(C.POINTER(C.c_uint16)), _f(cams), w, h, B, C.byref(o), _f(scale), _f(T),
+                                           stats.ctypes.data_as(C.POINTER(C.c_double))))
+        return scale, T, stats
+
+    def estimate_scale_dev(self, d_depth, d_cams, w, h, B, d_scale_out, d_T_out, d_stats, d_poses=None, which=0, options=None, stream=None):
+        """ht_estimate_scale_dev: device pointers, only enqueued on `stream`."""
+        self._chk(self.L.ht_estimate_scale_dev(self.h, int(which), d_poses, d_depth, d_cams, int(w), int(h), int(B), None if options is None else C.byref(options), d_scale_out, d_T_out, d_stats, stream))
 
     def keypoint_errors(self, a, b, thr=()):
         """a, b f32[B,K,3] -> dict(dist f32[B,K], frame f32[B,2] (mean, max), sum_kp f64[K], hits_kp i64[T], hits_frame i64[T], and from them mean_kp f64[K],

@@ -848,6 +848,43 @@ struct HandTracker                                                              
 		for (size_t i = 5; i < r.stats.size(); i += HT_CALIB_STATS) r.degenerate = r.degenerate || r.stats[i] != 0.0;
 		return r;
 	}
+	// Addition, not a reference name (ht_mi355x.h "the hand's size"; the reference's applications ask the user: "hand size %f cm (use +/- to scale)").  EstimateHandSize:
+	// the factor by which this tracker's model should grow to explain the frames of one view.  frames: one per tracked frame (one size; each frame's DCamera is read whole,
+	// its pose places the view in tracking space); poses: per frame the tracked model's centre-of-mass poses (handmodel.GetPose() after the update of that frame).  One
+	// scale for the batch (HT_SIZE_SHARED); the batch is not bounded by the tracker's one slot.  scale is relative to the model as it is now: apply it with scale(r.scale).
+	// T: per frame the view's pose after the rigid shifts free_pose allows (the cameras' own when free_pose is 0); stats: the (iterations + 1) rows of
+	// HT_SIZE_ROW(1, frames) doubles the C call documents; degenerate: the scale's record of some row carries a flag (no usable frame, no positive pivot, a clamped step).
+	struct SizeOptions : ht_size { explicit SizeOptions(const HandTracker &t) { ht_size_default(t.ctx_, this); } };
+	struct HandSize { float scale; std::vector<Pose> T; std::vector<double> stats; bool degenerate; };
+	HandSize EstimateHandSize(const std::vector<Image<unsigned short>> &frames, const std::vector<std::vector<Pose>> &poses, const ht_size *options = nullptr)
+	{
+		const int B = (int)frames.size();
+		if (B < 1 || poses.size() != frames.size()) throw std::runtime_error("EstimateHandSize: one set of poses per frame, at least one frame");
+		const SizeOptions dflt(*this);
+		ht_size o = options ? *options : dflt;
+		if (o.mode != HT_SIZE_SHARED) throw std::runtime_error("EstimateHandSize: one scale for the batch (HT_SIZE_SHARED); the per-slot mode is the C call's");
+		const int w = frames[0].dim().x, h = frames[0].dim().y;
+		std::vector<unsigned short> depth; std::vector<float> cams((size_t)B * HT_CAM), p7;
+		for (int b = 0; b < B; b++)
+		{
+			if (frames[b].dim().x != w || frames[b].dim().y != h || frames[b].raster.size() != (size_t)w * h) throw std::runtime_error("EstimateHandSize: the frames of a call have one size");
+			if ((int)poses[b].size() != nb_) throw std::runtime_error("EstimateHandSize: one pose per body of the tracker's model for every frame");
+			depth.insert(depth.end(), frames[b].raster.begin(), frames[b].raster.end());
+			cam12(frames[b].cam, &cams[(size_t)b * HT_CAM]);
+			const std::vector<float> f = flat(poses[b]);
+			p7.insert(p7.end(), f.begin(), f.end());
+		}
+		HandSize r;
+		const size_t row = (size_t)HT_SIZE_ROW(1, B);
+		r.stats.assign((size_t)(o.iterations > 0 ? o.iterations + 1 : 1) * row, 0.0);
+		std::vector<float> T((size_t)B * 7);
+		check(ctx_, ht_estimate_scale(ctx_, 0, p7.data(), depth.data(), cams.data(), w, h, B, &o, &r.scale, T.data(), r.stats.data()));
+		r.T.resize(B);
+		for (int b = 0; b < B; b++) { const float *t = &T[(size_t)b * 7]; r.T[b].position = { t[0], t[1], t[2] }; r.T[b].orientation = { t[3], t[4], t[5], t[6] }; }
+		r.degenerate = false;
+		for (size_t i = 5; i < r.stats.size(); i += row) r.degenerate = r.degenerate || r.stats[i] != 0.0;
+		return r;
+	}
 	// Addition, not a reference name: GatherHandExpectedCNN (handtrack.h:160-173) for a batch of pose sets on this tracker's device, frame b seen by the
 	// heat-map camera hcams[b] (as the single-frame form takes it); segment_frame: train-cnn's compress first (train-cnn.cpp:31-50: the poses in the
 	// camera's frame, the camera at the identity).  The same ExpectedCNN sets as the single-frame form, bit for bit (ht_expected_cnn_batch).

@@ -982,6 +982,71 @@ int ht_calib_default(ht_ctx *ctx, ht_calib *o);
 int ht_calibrate_view(ht_ctx *ctx, int which, const float *poses, const uint16_t *depth, const float *cams, int w, int h, int B, const ht_calib *o, float *T_out, double *stats);
 int ht_calibrate_view_dev(ht_ctx *ctx, int which, const float *d_poses, const uint16_t *d_depth, const float *d_cams, int w, int h, int B, const ht_calib *o, float *d_T_out, double *d_stats, void *stream);
 
+/* ---- the hand's size from tracked frames (an addition: every live application of the reference asks the user for it, "hand size %f cm (use +/- to scale)",
+ * openvr-demo.cpp:109, realtime-annotator.cpp:238) ---------------------------------------------------------------------------------------------------
+ * The tracker fits a model of one fixed size; ht_scale applies a size and nothing found it.  PhysModel::scale(s) (physmodel.h:196-219, :304-319) is a uniform
+ * similarity about body 0's position w, so a depth point y lies at distance s * dist(w + (y - w) / s) from the hand scaled by s, dist being the unscaled model's
+ * closest(): size is a seventh degree of freedom beside "a view's extrinsics"' six, evaluated against the model the context holds, and ht_estimate_scale is that
+ * section's Gauss-Newton loop with it.  depth [B][h][w] and cams [B][12] are ONE view's frames and cameras, one a slot; cloud, model (poses or the state of model
+ * `which`) and their bounds are ht_calibrate_view's, the cloud in the same buffer of the context's.  The result is the scale at which the model best explains the frames;
+ * applying it stays the caller's ht_scale(ctx, s).
+ *   transform  every slot has its own T_b = (pos, q), carried in float64, starting at the camera's pose cams[b][5:12]; y = pos + qrot(q, p) from T_b rounded to fp32.
+ *   scale      s is carried in float64 and starts at (double)o.scale0.  HT_SIZE_SHARED: one s for the batch (one user, many frames), N = 1.  HT_SIZE_PER_SLOT: one s a
+ *              slot, N = B.
+ *   per point  fp32, one IEEE operation after another in the forms of "a view's extrinsics" (dot = (ax bx + ay by) + az bz [+ w]; vector by scalar per component):
+ *              w = body 0's position in slot b's poses; e = y - w; u = w + e * (float)(1.0 / s) (the division in float64, then rounded);
+ *              plane = closest(bodies of slot b, u), bit for bit the reference's; r0 = dot(plane, (u, 1)); n = plane.xyz; r = (float)s * r0;
+ *              J = [n, cross(e, n), r - dot(n, e)] -- the last entry is dr for a relative step dsigma = ds / s; in = |r| <= max_dist.
+ *   sums       37 float64 values a slot: k = 0..27 the upper triangle of J J^T row by row ((0,0), (0,1), .. (0,6), (1,1), ..), 28..34 J r, 35 the truncated cost
+ *              (r r < m ? r r : m with m = (double)max_dist * (double)max_dist, every point), 36 the inlier count; every product of the two fp32 terms widened, the
+ *              first 35 take in ? term : 0.0.  Order: "a view's extrinsics"' (thread t of 256 its points t, t + 256, .. onto +0.0; the wave's xor butterfly 32, 16,
+ *              .. 1; the four waves as (w0 + w1) + (w2 + w3)).  Below A is the slot's symmetric 7 x 7, A6 its leading 6 x 6, c = A[0..5][6], a = A[6][6],
+ *              g = S[28..33], h = S[34].  No floating-point atomics, nothing depends on arrival.
+ *   usable     a slot with fewer than min_points inliers (slot flag HT_SIZE_FEW_INLIERS) or whose pivot below is not > 0 (HT_SIZE_BAD_PIVOT) contributes nothing and
+ *              its T keeps its bits.
+ *   step       float64, + - * / and sqrt only, no contraction; D = 1 + (double)damping; Cholesky, forward and back substitution and the update of a transform are
+ *              those of "a view's extrinsics" (L L^T x = rhs: y_i = (rhs_i - L_i0 y_0 - ..) / L_ii, x_i = (y_i - L_{i+1,i} x_{i+1} - ..) / L_ii).
+ *              free_pose = 0 (the poses are trusted; T never moves; a slot's pivot is a):  PER_SLOT dsigma = -h / (a D);  SHARED  S = sum a_b, H = sum h_b over the
+ *              usable slots in slot order onto +0.0, dsigma = -H / (S D).
+ *              free_pose = 1 (every slot may also shift rigidly about its wrist, which absorbs the pose bias a wrongly sized model leaves):
+ *                PER_SLOT  Cholesky of A with A_ii *= D (all seven), d = the solution for rhs -[g, h], dsigma = d[6], the slot's step d[0..5].
+ *                SHARED    the bordered system by its Schur complement: every usable slot factors A6 with A6_ii *= D, solves A6 z = c and A6 v = g;
+ *                          S = sum (a - c.z), H = sum (h - c.v) over the usable slots in slot order onto +0.0 (x.y = ((((x0 y0 + x1 y1) + x2 y2) + x3 y3) + x4 y4)
+ *                          + x5 y5; a slot whose two terms are not finite is not usable); dsigma = -H / (S D); the slot's step d_i = -(v_i + z_i dsigma).
+ *              Every moved T_b takes (dt, dw) = d by the update of "a view's extrinsics" about c = (double)w_b; a candidate that is not finite leaves T_b's bits and
+ *              sets the slot's BAD_PIVOT (PER_SLOT: and the scale stays too).  In every form s <- s + s * dsigma.
+ *   degenerate no usable slot (scale flag HT_SIZE_FEW_INLIERS when every slot has too few inliers, else HT_SIZE_BAD_PIVOT), S not > 0 or dsigma or the new s not
+ *              finite (HT_SIZE_BAD_PIVOT): s and every T of that scale keep
+ *              their bits.  A new s below (double)scale_lo or above (double)scale_hi becomes that bound (HT_SIZE_CLAMPED; the transforms still take their steps).
+ *              A NaN never comes out of finite inputs.
+ *   iterations every one of o.iterations (0..64) is one accumulate and one solve launch on the caller's stream, one more pair evaluates the final state.
+ *              iterations = 0 scores scale0 at the cameras' poses.
+ *   outputs    scale_out fp32 [N], s rounded.  T_out fp32 [B][7], T_b rounded: the cameras' poses when free_pose = 0.  stats float64
+ *              [iterations + 1][HT_SIZE_ROW(N, B)]: row i describes the state before step i, row `iterations` the final state (no step, flags FEW_INLIERS only).  A row:
+ *              N scale records of HT_SIZE_STATS (inliers, points, truncated cost -- sums over the scale's slots in slot order --, |dsigma| taken (0: none), the s the
+ *              row was evaluated at, flag), then B slot records of HT_SIZE_SLOT_STATS (inliers, truncated cost, flag).
+ * ht_size_default     range, fraction, max_dist, damping and min_points are ht_calib_default's; HT_SIZE_SHARED, free_pose 1, 10 iterations, scale0 1, scale_lo 0.5,
+ *                     scale_hi 2.  NULL options mean these.
+ * ht_estimate_scale   host arrays, synchronous.  ht_estimate_scale_dev: device arrays (d_scale_out, d_T_out and d_stats 4-byte aligned), everything enqueued on
+ *                     `stream`, no host wait inside but the buffers' re-allocation.  The slots' prepared points, both models' states, the tracker's flags and the model
+ *                     are not touched.
+ * Refused before anything grows or runs, the context left usable (HT_ERR_ARG / HT_ERR_STATE): everything ht_calibrate_view refuses (scale_out NULL as T_out); a mode
+ * or free_pose outside its values; scale0, scale_lo or scale_hi not finite or not 0 < scale_lo <= scale0 <= scale_hi.  Out of scope: left hands (mirror the frames
+ * first), mirror planes, several views in one call, per-finger or per-bone proportions (one number scales the whole hand), and applying the result. */
+#define HT_SIZE_SHARED 0
+#define HT_SIZE_PER_SLOT 1
+#define HT_SIZE_STATS 6
+#define HT_SIZE_SLOT_STATS 3
+#define HT_SIZE_ROW(N, B) ((N) * HT_SIZE_STATS + (B) * HT_SIZE_SLOT_STATS)
+#define HT_SIZE_FEW_INLIERS 1
+#define HT_SIZE_BAD_PIVOT 2
+#define HT_SIZE_CLAMPED 4
+typedef struct { float range_lo, range_hi; int fraction, mode, free_pose, iterations; float max_dist, damping; int min_points; float scale0, scale_lo, scale_hi; } ht_size;
+int ht_size_default(ht_ctx *ctx, ht_size *o);
+int ht_estimate_scale(ht_ctx *ctx, int which, const float *poses, const uint16_t *depth, const float *cams, int w, int h, int B, const ht_size *o, float *scale_out, float *T_out, double *stats);
+int ht_estimate_scale_dev(ht_ctx *ctx, int which, const float *d_poses, const uint16_t *d_depth, const float *d_cams, int w, int h, int B, const ht_size *o, float *d_scale_out, float *d_T_out, double *d_stats,
+                          void *stream);
+
 /* ---- annotation fit loop ---------------------------------------------------------------------------------------------
  * ht_slowfit          replaces  void HandTracker::slowfit(const std::vector<float3> &points, int hold, const std::vector<Pose> &refpose,
  *                     int steps_ = 6, RigidBody *selectrb = NULL, const float3 &spoint, const float3 &rbpoint, const std::vector<float4> &crays)
