@@ -153,9 +153,9 @@ extern "C" int ht_create(const char *model_path, int max_batch, int device, ht_c
 	HIPCHK(ctx, hipGetDeviceProperties(&prop, device));
 	if (!strstr(prop.gcnArchName, "gfx950")) { ctx->err = std::string("device is ") + prop.gcnArchName + ", kernels are built for gfx950 only"; return HT_ERR_HIP; }
 	HIPCHK(ctx, hipStreamCreate(&ctx->stream));
-	for (int i = 0; i < 2; i++) { HIPCHK(ctx, hipStreamCreateWithFlags(&ctx->side[i], hipStreamNonBlocking)); HIPCHK(ctx, hipEventCreateWithFlags(&ctx->ev_join[i], hipEventDisableTiming)); }
-	HIPCHK(ctx, hipEventCreateWithFlags(&ctx->ev_fork, hipEventDisableTiming));
-	HIPCHK(ctx, hipEventCreateWithFlags(&ctx->ev_lap, hipEventDisableTiming));
+	for (int i = 0; i < 2; i++) { HIPCHK(ctx, hipStreamCreateWithFlags(&ctx->side[i], hipStreamNonBlocking)); HIPCHK(ctx, ht_edge_event(ctx, &ctx->ev_join[i])); }
+	HIPCHK(ctx, ht_edge_event(ctx, &ctx->ev_fork));
+	HIPCHK(ctx, ht_edge_event(ctx, &ctx->ev_lap));
 	// model_path == NULL: a context that only evaluates / trains the CNN (what a stand-alone CNN object of the reference is, cnn.h:100-605)
 	int r = model_path ? load_model(ctx, model_path) : HT_OK;
 	if (r) return r;

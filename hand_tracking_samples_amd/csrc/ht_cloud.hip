@@ -964,7 +964,7 @@ void ht_launch_chamber_planes(const ht_model_dev &M, const float4 *pts, const in
 // `rec`: instead of the 16-float rows, write each row's solver record into the frames' scratch slots and the rows' bodies into rec->body (k_solve then only
 // lists them per body); null: the reference-layout rows (stage calls, UnibodyFit)
 void ht_launch_cloud_rows(const ht_model_dev &M, const float *state, const float4 *pts, const int *npts, const float *cams, const int *active_flag, const cloud_take &take, const cloud_limits &lim,
-                          float *rows, int *nrows, int B, hipStream_t s, const cloud_records *rec, const plane_rows *planes)
+                          float *rows, int *nrows, int B, hipStream_t s, const cloud_records *rec, const plane_rows *planes, hipEvent_t done)
 {
 	const cloud_records none = { nullptr, 0, nullptr, 0.0f };
 	const plane_rows no_planes = { nullptr, nullptr, 0.0f, nullptr, nullptr };
@@ -978,8 +978,13 @@ void ht_launch_cloud_rows(const ht_model_dev &M, const float *state, const float
 	if (split > passes) split = passes;
 	if (split < 1) split = 1;
 	// `planes`: the frames' boundary-plane rows (k_chamber's) by one more block per frame, behind the cloud-row blocks in dispatch order
-	hipLaunchKernelGGL(k_cloud_rows, dim3(B, split + (planes ? 1 : 0)), dim3(CR_THREADS), ((size_t)M.plane_off[M.nb] + ht_plane_slack(M)) * sizeof(float4), s, M, state, pts, npts, cams, active_flag, take.stride, take.cam_origin, take.mode,
-	                   lim.microforce, lim.weak_force, lim.cf_max_point, lim.cf_max_sum, lim.unibody_force, rows, nrows, rec ? *rec : none, planes ? *planes : no_planes, ht_tuning_flags());
+	const dim3 grid(B, split + (planes ? 1 : 0)); const size_t lds = ((size_t)M.plane_off[M.nb] + ht_plane_slack(M)) * sizeof(float4);
+	if (done)      // the launch completes the caller's event itself (ht_launch.hpp)
+		hipExtLaunchKernelGGL(k_cloud_rows, grid, dim3(CR_THREADS), lds, s, nullptr, done, 0, M, state, pts, npts, cams, active_flag, take.stride, take.cam_origin, take.mode,
+		                      lim.microforce, lim.weak_force, lim.cf_max_point, lim.cf_max_sum, lim.unibody_force, rows, nrows, rec ? *rec : none, planes ? *planes : no_planes, ht_tuning_flags());
+	else
+		hipLaunchKernelGGL(k_cloud_rows, grid, dim3(CR_THREADS), lds, s, M, state, pts, npts, cams, active_flag, take.stride, take.cam_origin, take.mode,
+		                   lim.microforce, lim.weak_force, lim.cf_max_point, lim.cf_max_sum, lim.unibody_force, rows, nrows, rec ? *rec : none, planes ? *planes : no_planes, ht_tuning_flags());
 }
 void ht_launch_cloud_rows_views(const ht_model_dev &M, const float *state, const float4 *pts, const int *npts, const float *origins, const cloud_limits &lim, float *rows, int *nrows, int B, hipStream_t s,
                                 const cloud_records *rec)

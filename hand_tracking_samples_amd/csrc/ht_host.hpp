@@ -49,6 +49,11 @@ struct ht_ctx
 	hipStream_t side[2] = { nullptr, nullptr };     // independent kernels of one fit step (cloud rows, contacts, chamber) run side by side
 	hipEvent_t ev_fork = nullptr, ev_join[2] = { nullptr, nullptr }, ev_lap = nullptr;
 	unsigned side_open = 0;                         // bit i: side stream i was forked off an update's stream and has not come back to it yet
+	// The edges between an update's streams (ht_edge_event, ht_solver_api.hip: fork / join1).  edge_mode: ht_debug_stream_edges, 0 = the product's events and launch forms,
+	// 1 = the edges as they were up to round 29 (tests only).  edges_on_launch: this update's solves and cloud-row launches may carry the next edge's event as their own
+	// completion event (never while the caller's stream is being captured).  fork_carried: the stream whose last launch, a solve, completes ev_fork -- the fork that follows
+	// on that stream records nothing; join_carried, bit i: side stream i's last launch, the cloud rows, completes ev_join[i] -- the join that follows records nothing.
+	int edge_mode = 0; bool edges_on_launch = false; hipStream_t fork_carried = nullptr; unsigned join_carried = 0;
 	hipEvent_t ev_job = nullptr, ev_seed = nullptr; bool job_pending = false; void *h_job_in = nullptr; size_t h_job_cap = 0;      // ht_job_start: the CNN job of the overlapped update() in flight on this context, its pinned input staging
 	ht_params par;
 	ht_physics_dev phys;
@@ -257,6 +262,14 @@ static inline void ht_mesh_args(const ht_ctx *ctx, float *com, int *tri_off)
 	for (int b = 0; b <= ctx->model.nb; b++) tri_off[b] = ctx->rec.mesh_off[b];
 	for (int b = 0; b < ctx->model.nb; b++) for (int i = 0; i < 3; i++) com[3 * b + i] = ctx->rec.bodyc[(size_t)b * HT_BC + HT_BC_COM + i];
 }
+// The one creator of the events that order an update's own streams (ev_fork, ev_join[], ev_lap) and the job's seed copy against the caller's stream (ev_seed).  Every
+// consumer of these events is a kernel or a copy of THIS device behind a hipStreamWaitEvent, and a kernel's end already releases its writes at device scope, so the events go
+// without the system-scope fence of an ordinary record (hipEventDisableSystemFence): tools/exp_stream_edges.hip measured a fork / join pair at 10.0 -> 7.9 us with the join
+// hidden and 24.5 -> 20.4 us with the join exposed, every read on the other stream correct across the XCDs (profiles/r30_stream_edges.md; hipEventReleaseToDevice
+// measured the same as no flag).  Not for an event the host queries or waits for (ev_job) and not for the events that order an update against RCCL, whose peers are other
+// devices (ht_comm.hip): those keep the ordinary fence.  ht_debug_stream_edges(ctx, 1) makes the events as they were up to round 29.
+#define HT_EDGE_EVENT_FLAGS (hipEventDisableTiming | hipEventDisableSystemFence)
+static inline hipError_t ht_edge_event(const ht_ctx *ctx, hipEvent_t *ev) { return hipEventCreateWithFlags(ev, ctx->edge_mode == 1 ? (unsigned)hipEventDisableTiming : (unsigned)HT_EDGE_EVENT_FLAGS); }
 int ht_alloc_solve_tables(ht_ctx *ctx);      // d_tables and nothing else, once (d_chplanes / d_chon come with ht_alloc_buffers): from ht_debug_solve_tables(ctx, 1 or 2), and from ht_alloc_buffers under HT_TABLES in a tuning build
 int ht_reserve_points_locked(ht_ctx *ctx, int points);      // grows the per-point arrays (ht_api.hip); waits for the context's streams
 // *_dev entry points: a NULL stream means the context's own stream (never the legacy default stream); the choice is remembered so that the

@@ -1,6 +1,7 @@
 // ht_launch.hpp -- host-callable launchers of the solver-side kernels (product code).
 #pragma once
 #include "ht_device.hpp"
+#include <hip/hip_ext.h>      // hipExtLaunchKernelGGL: a launch that completes an event of the caller's (ht_launch_solve, ht_launch_cloud_rows)
 
 struct solve_args
 {
@@ -68,8 +69,10 @@ static inline cloud_limits ht_cloud_limits(const ht_params &par, int mode, float
 	const bool sf = mode == CLOUD_SLOWFIT;
 	return cloud_limits{ par.microforce, sf ? sf_ratio : par.physics_weak_force, sf ? sf_wrist : par.cloudforce_max_point, par.cloudforce_max_sum, par.unibody_force };
 }
+// `done` (here and on ht_launch_solve): an event the launch itself completes when its kernel has ended (the stopEvent of hipExtLaunchKernelGGL), instead of a
+// hipEventRecord behind it: the same kernel with the same arguments, one marker less in the stream (ht_solver_api.hip: fork1 / join1)
 void ht_launch_cloud_rows(const ht_model_dev &M, const float *state, const float4 *pts, const int *npts, const float *cams, const int *active_flag, const cloud_take &take, const cloud_limits &lim,
-                          float *rows, int *nrows, int B, hipStream_t s, const cloud_records *rec = nullptr, const plane_rows *planes = nullptr);
+                          float *rows, int *nrows, int B, hipStream_t s, const cloud_records *rec = nullptr, const plane_rows *planes = nullptr, hipEvent_t done = nullptr);
 // The same rows for a fused cloud of several views (ht_views.hip): every point, CLOUD_FIT's limits, and each point's ray from the origin its .w names in the frame's
 // table origins [B][2 HT_VIEWS_MAX][3] (k_view_rows: the compile-time mode of the same per-frame code; no plane rows, they assume one viewpoint)
 void ht_launch_cloud_rows_views(const ht_model_dev &M, const float *state, const float4 *pts, const int *npts, const float *origins, const cloud_limits &lim, float *rows, int *nrows, int B, hipStream_t s,
@@ -98,7 +101,7 @@ void ht_launch_order_by_points(const int *npts, int *order, int B, hipStream_t s
 void ht_launch_rank_desc(const int *work, int *order, int B, int stride, unsigned slots, int nslots, hipStream_t s);      // order[slot][.] = the frames of every segment (ht_rank.hpp: HT_RANK_SEG) by work[slot][.], largest first
 void ht_launch_contact_order(const int *work, int *order, int B, int nfr, int stride, unsigned slots, int nslots, int epb, hipStream_t s);
 size_t ht_contacts_workspace_bytes(int B);
-void ht_launch_solve(const ht_model_dev &M, const ht_physics_dev &ph, const solve_args &a, int B, hipStream_t s);
+void ht_launch_solve(const ht_model_dev &M, const ht_physics_dev &ph, const solve_args &a, int B, hipStream_t s, hipEvent_t done = nullptr);
 void ht_launch_set_pose(float *state, const float *src, int nb, int n, int mode, hipStream_t s);
 void ht_launch_get_state(const float *state, float *dst, int nb, int n, hipStream_t s);
 void ht_launch_clear_flags(float *prev_err, int *initializing, int n, hipStream_t s);

@@ -1558,7 +1558,10 @@ void ht_launch_rank_desc(const int *work, int *order, int B, int stride, unsigne
 static_assert(sizeof(lds_t<66, 1024, 126, 1024, 2, SOLVE_ONLY_NCG>) <= 40960, "the build for 1024 frames must fit four times into a CU's LDS");
 static_assert(sizeof(lds_t<34, 584, 84, 0>) <= 20480, "the small build must leave room for eight frames per CU (160 KB of LDS)");
 static_assert(HT_SCRATCH_TAIL * HT_CREC >= MAXG_CAP * LGRP + (MAXA_CAP_OF(4) + 4) * AROW + HT_CREC, "the tail of a frame's scratch slot must hold its linear groups, its angular records and the tuning record");
-void ht_launch_solve(const ht_model_dev &M, const ht_physics_dev &ph, const solve_args &a, int B, hipStream_t s)
+// one launch of a build of k_solve; with `done`, through the launch form that completes that event at the kernel's end (ht_launch.hpp)
+#define SOLVE_LAUNCH(...) do { if (done) hipExtLaunchKernelGGL((k_solve<__VA_ARGS__>), dim3(B), dim3(64), 0, s, nullptr, done, 0, M, ph, a); \
+                               else hipLaunchKernelGGL((k_solve<__VA_ARGS__>), dim3(B), dim3(64), 0, s, M, ph, a); } while (0)
+void ht_launch_solve(const ht_model_dev &M, const ht_physics_dev &ph, const solve_args &a, int B, hipStream_t s, hipEvent_t done)
 {
 	// the build by what the host knows of the launch: the model's joints and the most points a frame of this call can carry.  A frame that exceeds
 	// the chosen build's arrays (contacts, points: device-side data) keeps the array in question in HBM (top of the file); nothing is relaunched.
@@ -1567,15 +1570,16 @@ void ht_launch_solve(const ht_model_dev &M, const ht_physics_dev &ph, const solv
 	// Up to four frames per CU (1024 on the 256 CUs) a launch gains nothing from the small build's footprint, so the build that keeps 49 contacts and
 	// 126 angular rows in LDS runs.  Not when other kernels share the GPU with this launch (the reset path): they need LDS on every CU too.
 	int build = a.force_build;
-	if (build == 7) { solve_args b = a; b.force_build = 0; b.two_body_levels = 1; ht_launch_solve(M, ph, b, B, s); return; }      // tests only: the two-body rows by the level schedule for every frame
+	if (build == 7) { solve_args b = a; b.force_build = 0; b.two_body_levels = 1; ht_launch_solve(M, ph, b, B, s, done); return; }      // tests only: the two-body rows by the level schedule for every frame
 	if (!build) build = tile ? (B <= 1024 && !a.shared_gpu ? 2 : 1) : 3;
 	// the angular rows a frame of this launch can have at most (13 CNN-driven + 6 per joint + what the caller states on top: slowfit's relative rows, caller-built rows):
 	// beyond the 126 of the ordinary builds the build with four row slots per lane runs (252)
 	if (build >= 1 && build <= 3 && 13 + 6 * M.nj + a.ang_extra_bound > MAXA_CAP_OF(2)) build = 6;
-	if (build == 2) hipLaunchKernelGGL((k_solve<66, 1024, 126, 1024, false, 2, SOLVE_ONLY_NCG>), dim3(B), dim3(64), 0, s, M, ph, a);
-	else if (build == 1) hipLaunchKernelGGL((k_solve<34, 584, 84, 0>), dim3(B), dim3(64), 0, s, M, ph, a);
-	else if (build == 3) hipLaunchKernelGGL((k_solve<71, 1520, 126, 1520>), dim3(B), dim3(64), 0, s, M, ph, a);
-	else if (build == 5) hipLaunchKernelGGL((k_solve<71, 1520, 126, 1520, true, 4>), dim3(B), dim3(64), 0, s, M, ph, a);      // tests only: the reference's own sweeps (ht_debug_exact_solver)
-	else if (build == 6) hipLaunchKernelGGL((k_solve<71, 1520, 126, 1520, false, 4>), dim3(B), dim3(64), 0, s, M, ph, a);     // models / calls with up to 252 angular rows (records beyond 126 in HBM)
-	else hipLaunchKernelGGL((k_solve<2, 64, 4, 0>), dim3(B), dim3(64), 0, s, M, ph, a);      // tests only: nothing fits, every frame keeps its groups, sums and angular records in HBM
+	if (build == 2) SOLVE_LAUNCH(66, 1024, 126, 1024, false, 2, SOLVE_ONLY_NCG);
+	else if (build == 1) SOLVE_LAUNCH(34, 584, 84, 0);
+	else if (build == 3) SOLVE_LAUNCH(71, 1520, 126, 1520);
+	else if (build == 5) SOLVE_LAUNCH(71, 1520, 126, 1520, true, 4);      // tests only: the reference's own sweeps (ht_debug_exact_solver)
+	else if (build == 6) SOLVE_LAUNCH(71, 1520, 126, 1520, false, 4);     // models / calls with up to 252 angular rows (records beyond 126 in HBM)
+	else SOLVE_LAUNCH(2, 64, 4, 0);      // tests only: nothing fits, every frame keeps its groups, sums and angular records in HBM
 }
+#undef SOLVE_LAUNCH

@@ -50,7 +50,7 @@ static int pass_slot(int pass) { return pass >= 0 && pass < 8 ? 8 + pass : -1; }
 // that started last (results do not depend on the order): the cloud-row and FitError kernels by the frames' point counts (update_inputs), the solves by what every frame took
 // in the same launch of the previous update (solve_hist: k_solve notes it, update_orders ranks it beside the net).
 static bool several_rounds(const ht_ctx *ctx, int B) { return B > ctx->n_cu * 8; }
-struct solve_opts { const int *active = nullptr; int hist_slot = -1; bool tables = false, shared_gpu = false; float *poses_out = nullptr; const int *out_npts = nullptr; };      // active: only the frames whose flag is set; tables: solve_prep has made them for exactly this solve; poses_out: the solve also writes the user poses
+struct solve_opts { const int *active = nullptr; int hist_slot = -1; bool tables = false, shared_gpu = false; float *poses_out = nullptr; const int *out_npts = nullptr; bool fork_next = false; };      // active: only the frames whose flag is set; tables: solve_prep has made them for exactly this solve; poses_out: the solve also writes the user poses; fork_next: the stream's next operation is a fork (fork / fork1), so the launch may carry its event (forks_from)
 // Tuning builds: a launch that takes a launch table while the tables are still being made on side stream 0 must be on that stream (update_resets)
 static void table_read_on(const ht_ctx *ctx, hipStream_t s)
 {
@@ -58,6 +58,31 @@ static void table_read_on(const ht_ctx *ctx, hipStream_t s)
 	if (ctx->tables_out && s != ctx->side[0]) { fprintf(stderr, "a launch table read on a stream that has not joined side stream 0\n"); abort(); }
 #endif
 }
+// The edges between an update's streams.  The row-producing kernels of one fit step only read the pose, so they run side by side with the contacts on a side stream and the
+// solve waits for them (each is latency-bound on its slowest frame and leaves most of the chip idle).  An edge is an event of the context (ht_host.hpp: ht_edge_event --
+// no system-scope fence: the consumer of every edge below is a kernel of this device) that the other stream waits for.  Who completes the event:
+//   a hipEventRecord behind the producer                                       fork + join of a 100 us step: 7.9 us over the ideal, 20.4 us when the solve waits for the join
+//   the producer's own launch (hipExtLaunchKernelGGL's stopEvent: `done`)      6.5 / 17.7 us: no marker between the solve and the contacts that follow it
+// (tools/exp_stream_edges.hip, profiles/r30_stream_edges.md; with the events of rounds 1 to 29 a pair cost 10.0 / 24.5 us).  The launch form is taken where a solve is
+// followed by the next step's fork (forks_from) and where the cloud rows are the last launch of their side stream before the join (joins_from), in updates that are not being
+// captured into a HIP graph (run_update_: a stopEvent is not known to become a graph dependency) and not under ht_debug_stream_edges(ctx, 1).  The first fork of a loop,
+// the forks and joins of the update's head and ev_lap follow other kernels and stay records.
+// (side_open keeps track of the side streams that are out: an update ends by bringing back whichever still is, join_open)
+#ifndef HT_EDGE_ON_LAUNCH
+#define HT_EDGE_ON_LAUNCH 1
+#endif
+static hipEvent_t forks_from(ht_ctx *ctx, hipStream_t s) { if (!ctx->edges_on_launch) return nullptr; ctx->fork_carried = s; return ctx->ev_fork; }      // for the launch after which stream s forks next: the event it completes
+static hipEvent_t joins_from(ht_ctx *ctx, int i) { if (!ctx->edges_on_launch) return nullptr; ctx->join_carried |= 1u << i; return ctx->ev_join[i]; }      // for the last launch of side stream i before its join
+static void fork_event(ht_ctx *ctx, hipStream_t s) { if (ctx->fork_carried != s) (void)hipEventRecord(ctx->ev_fork, s); ctx->fork_carried = nullptr; }
+static void fork(ht_ctx *ctx, hipStream_t s) { fork_event(ctx, s); for (int i = 0; i < 2; i++) (void)hipStreamWaitEvent(ctx->side[i], ctx->ev_fork, 0); ctx->side_open |= 3u; }
+static void fork1(ht_ctx *ctx, hipStream_t s, int i) { fork_event(ctx, s); (void)hipStreamWaitEvent(ctx->side[i], ctx->ev_fork, 0); ctx->side_open |= 1u << i; }
+static void join1(ht_ctx *ctx, hipStream_t s, int i)
+{
+	if (!((ctx->join_carried >> i) & 1u)) (void)hipEventRecord(ctx->ev_join[i], ctx->side[i]);
+	(void)hipStreamWaitEvent(s, ctx->ev_join[i], 0); ctx->join_carried &= ~(1u << i); ctx->side_open &= ~(1u << i); if (i == 0) ctx->tables_out = false;
+}
+static void join(ht_ctx *ctx, hipStream_t s, int n) { for (int i = 0; i < n; i++) join1(ctx, s, i); }
+static void join_open(ht_ctx *ctx, hipStream_t s) { for (int i = 0; i < 2; i++) if ((ctx->side_open >> i) & 1u) join1(ctx, s, i); }
 static void solve_step(ht_ctx *ctx, int which, const step_mix &m, int B, hipStream_t s, const solve_opts &o)
 {
 	solve_args a = solve_head(ctx, which, ctx->phys.use_collision != 0);
@@ -71,7 +96,7 @@ static void solve_step(ht_ctx *ctx, int which, const step_mix &m, int B, hipStre
 	// (a solve on some of the frames -- o.active -- keeps no cost history and takes no order table: update_resets relies on it, as on launch_contacts' rule for the reset frames)
 	if (!o.active && !exact_solver(ctx) && several_rounds(ctx, B)) { const ht_history::rows h = ctx->solve_hist.take(o.hist_slot, B); a.cost_out = h.work; a.frame_order = h.order; }
 	if (a.frame_order) table_read_on(ctx, s);
-	ht_launch_solve(ctx->model, ctx->phys, a, B, s);
+	ht_launch_solve(ctx->model, ctx->phys, a, B, s, o.fork_next ? forks_from(ctx, s) : nullptr);
 }
 // Round 6: the tables of a solve (ht_solve_shared.hpp) are made by k_solve_prep on whichever stream runs the solve's row producers, behind the cloud rows (it lists them per
 // body) and beside the contact kernel; the solve_step that follows is told to start from them.  Off for the exact-order builds (their sweeps take the rows as the reference
@@ -97,8 +122,6 @@ static void solve_prep(ht_ctx *ctx, int which, const step_mix &m, bool pose_only
 	a.tables = ctx->d_tables; a.dbg = ht_tuning_flags(); a.parts = pose_only ? 1 : 3;
 	ht_launch_solve_prep(ctx->model, ctx->phys, a, B, s);
 }
-// Fork/join helpers: the row-producing kernels of one fit step only read the pose, so they run side by side on two extra streams
-// and the solve waits for all of them (each of them is latency-bound on its slowest frame and leaves most of the chip idle).
 // Tuning builds, HT_MARKS=1: events at named points of an update on whichever stream, printed (ms since the first) after the update -- the concurrent streams as
 // they really ran (a kernel trace serialises them).
 #ifdef HT_TUNING
@@ -141,13 +164,6 @@ static void update_orders(ht_ctx *ctx, int B, hipStream_t t)
 	c.begin(B, plan.nfr > 1 && ht_contacts_coop(ctx->model, B, ctx->contact_kernel, false), [&](unsigned slots) { ht_launch_contact_order(c.work, c.order, B, plan.nfr, c.stride, slots, HT_CONTACT_SLOTS, epb, t); });
 	v.begin(B, several_rounds(ctx, B), [&](unsigned slots) { ht_launch_rank_desc(v.work, v.order, B, v.stride, slots, HT_CONTACT_SLOTS, t); });
 }
-// (side_open keeps track of the side streams that are out: an update ends by bringing back whichever still is, join_open)
-static void fork(ht_ctx *ctx, hipStream_t s) { (void)hipEventRecord(ctx->ev_fork, s); for (int i = 0; i < 2; i++) (void)hipStreamWaitEvent(ctx->side[i], ctx->ev_fork, 0); ctx->side_open |= 3u; }
-static void fork1(ht_ctx *ctx, hipStream_t s, int i) { (void)hipEventRecord(ctx->ev_fork, s); (void)hipStreamWaitEvent(ctx->side[i], ctx->ev_fork, 0); ctx->side_open |= 1u << i; }
-static void join1(ht_ctx *ctx, hipStream_t s, int i) { (void)hipEventRecord(ctx->ev_join[i], ctx->side[i]); (void)hipStreamWaitEvent(s, ctx->ev_join[i], 0); ctx->side_open &= ~(1u << i); if (i == 0) ctx->tables_out = false; }
-static void join(ht_ctx *ctx, hipStream_t s, int n) { for (int i = 0; i < n; i++) join1(ctx, s, i); }
-static void join_open(ht_ctx *ctx, hipStream_t s) { for (int i = 0; i < 2; i++) if ((ctx->side_open >> i) & 1u) join1(ctx, s, i); }
-
 // Which steps of MultiStepSim to run, where and how much of each: multistep(ctx, B, steps_on(stream).steps(0, 1).frames(ctx->d_flags).in_order().rows_only()).
 // Unless told otherwise: every step of every frame, whole, bracketed for the profile, the cloud rows of a step on side stream 0 beside its contacts.
 struct steps_on
@@ -163,7 +179,22 @@ struct steps_on
 	steps_on &shares_gpu() { shared_gpu = true; return *this; }                         // other kernels run beside the solves (solve_args::shared_gpu)
 	steps_on &rows_only() { solve = false; return *this; }                              // only what precedes the solve (cloud rows, contacts)
 	steps_on &solve_only() { rows = false; return *this; }
+	bool fork_follows = false;
+	steps_on &then_forks(bool yes = true) { fork_follows = yes; return *this; }         // the stream's next operation behind the last of these steps is a fork: its solve may carry the event (forks_from)
 };
+// What step st of MultiStepSim under `o` puts beside its contact kernel: the step's cloud rows, and (round 6) the solve's tables behind them -- a step without cloud rows
+// forks for the tables alone.  The answer is whether the step forks at all
+struct step_sides { bool par, pose_only, tables; };
+static step_sides sides_of_step(ht_ctx *ctx, const steps_on &o, int st)
+{
+	const bool coll = ctx->phys.use_collision != 0, whole = o.rows && o.solve;
+	static const bool no_side = ht_tuning_env("HT_NO_SIDE");      // timing experiments (-DHT_TUNING builds only)
+	step_sides r;
+	r.pose_only = solve_tables_mode(ctx) == 2 && o.side >= 0 && coll && !ctx->profile_phases && !no_side && whole && !o.active;      // the pose-only tables: on the OTHER side stream, beside the cloud rows
+	r.tables = solve_tables_on(ctx) || r.pose_only;
+	r.par = o.side >= 0 && (mix_of_step(ctx->par, st).cloud || r.tables) && coll && !ctx->profile_phases && !no_side;
+	return r;
+}
 // HandTracker::MultiStepSim on othermodel (handtrack.h:642-690)
 static void multistep(ht_ctx *ctx, int B, const steps_on &o)
 {
@@ -172,17 +203,14 @@ static void multistep(ht_ctx *ctx, int B, const steps_on &o)
 	for (int st = o.from; st < p.steps && st < o.to; st++)
 	{
 		const step_mix m = mix_of_step(p, st); const bool coll = ctx->phys.use_collision != 0;
-		static const bool no_side = ht_tuning_env("HT_NO_SIDE");      // timing experiments (-DHT_TUNING builds only)
-		const bool pose_only = solve_tables_mode(ctx) == 2 && o.side >= 0 && coll && !ctx->profile_phases && !no_side && whole && !active;      // the pose-only tables: on the OTHER side stream, beside the cloud rows
-		const bool tables = solve_tables_on(ctx) || pose_only;
-		// beside the contact kernel: the step's cloud rows, and (round 6) the solve's tables behind them -- a step without cloud rows forks for the tables alone
-		const bool par = o.side >= 0 && (m.cloud || tables) && coll && !ctx->profile_phases && !no_side;
+		const step_sides sd = sides_of_step(ctx, o, st); const bool pose_only = sd.pose_only, tables = sd.tables, par = sd.par;
 		if (o.rows)
 		{
 			hipStream_t rows_stream = par ? ctx->side[o.side] : s;
 			if (par && pose_only) fork(ctx, s); else if (par) fork1(ctx, s, o.side);
 			const cloud_records cr = cloud_rec(ctx);
-			if (m.cloud) { ht_prof_scope ps(ctx, o.prof ? "cloud_rows" : nullptr, s, true); ht_launch_cloud_rows(ctx->model, ctx->d_state[1], ctx->d_pts, ctx->d_npts, ctx->d_cams, active, step_take, ht_cloud_limits(p, CLOUD_MULTISTEP), ctx->d_rows, ctx->d_nrows, B, rows_stream, rec_or_rows(ctx, &cr)); }
+			const bool rows_last = par && !tables;      // the cloud rows are the side stream's last launch before the join: the launch carries the join's event
+			if (m.cloud) { ht_prof_scope ps(ctx, o.prof ? "cloud_rows" : nullptr, s, true); ht_launch_cloud_rows(ctx->model, ctx->d_state[1], ctx->d_pts, ctx->d_npts, ctx->d_cams, active, step_take, ht_cloud_limits(p, CLOUD_MULTISTEP), ctx->d_rows, ctx->d_nrows, B, rows_stream, rec_or_rows(ctx, &cr), nullptr, rows_last ? joins_from(ctx, o.side) : nullptr); }
 			if (pose_only) solve_prep(ctx, 1, m, true, active, B, ctx->side[1 - o.side]);
 			else if (tables) { ht_prof_scope ps(ctx, o.prof ? "solve_prep" : nullptr, s, true); solve_prep(ctx, 1, m, false, active, B, rows_stream); }
 			if (coll) { ht_prof_scope ps(ctx, o.prof ? "contacts" : nullptr, s, true); launch_contacts(ctx, 1, active, B, s, false, step_slot(st)); }
@@ -192,13 +220,15 @@ static void multistep(ht_ctx *ctx, int B, const steps_on &o)
 		if (!o.solve) continue;
 		ht_prof_scope ps(ctx, o.prof ? "solve" : nullptr, s);
 		solve_opts so; so.active = active; so.hist_slot = step_slot(st); so.tables = tables; so.shared_gpu = o.shared_gpu;
+		const bool more = st + 1 < p.steps && st + 1 < o.to;      // behind this solve: the next step's fork, or what the caller says follows the last step
+		so.fork_next = more ? o.rows && sides_of_step(ctx, o, st + 1).par : o.fork_follows;
 		solve_step(ctx, 1, m, B, s, so);
 	}
 }
 // one main-thread pass of HandTracker::update (handtrack.h:769-780).  Its row producers run beside the contact kernel on ONE side stream: a cross-stream edge costs about
 // 10 us and the solve waited for the later of two joins; inside an update the boundary planes' rows are extra blocks of the cloud-row launch (k_cloud_rows: plane_rows), which
 // fill that launch's tail instead of competing with it for the CUs the contact kernel frees.
-static void main_pass(ht_ctx *ctx, int B, hipStream_t s, float *poses_out = nullptr, int pass = -1)      // poses_out: the update's last pass also writes the user poses
+static void main_pass(ht_ctx *ctx, int B, hipStream_t s, float *poses_out = nullptr, int pass = -1, bool pass_follows = false)      // poses_out: the update's last pass also writes the user poses; pass_follows: the stream's next operation is another pass of the same update
 {
 	const ht_params &p = ctx->par;
 	const float4 *pts = p.subsample_voxel ? ctx->d_ptsv : ctx->d_pts;      // handtrack.h:751: the main-thread cloud
@@ -218,7 +248,8 @@ static void main_pass(ht_ctx *ctx, int B, hipStream_t s, float *poses_out = null
 	if (!tables && !fused) { ht_prof_scope ps(ctx, "chamber", s, true); ht_launch_chamber(ctx->model, ctx->d_state[0], ctx->d_chplanes, ctx->d_chon, 10.0f, ctx->d_chamber, ctx->d_nchamber, B, chamber_stream); }
 	const cloud_records cr = cloud_rec(ctx);
 	const plane_rows pr = { ctx->d_chplanes, ctx->d_chon, 10.0f, ctx->d_chamber, ctx->d_nchamber };
-	{ ht_prof_scope ps(ctx, "cloud_rows", s, true); ht_launch_cloud_rows(ctx->model, ctx->d_state[0], pts, npts, ctx->d_cams, nullptr, fit_take(CLOUD_FIT), ht_cloud_limits(p, CLOUD_FIT), ctx->d_rows, ctx->d_nrows, B, rows_stream, rec_or_rows(ctx, &cr), fused ? &pr : nullptr); }
+	{ ht_prof_scope ps(ctx, "cloud_rows", s, true); ht_launch_cloud_rows(ctx->model, ctx->d_state[0], pts, npts, ctx->d_cams, nullptr, fit_take(CLOUD_FIT), ht_cloud_limits(p, CLOUD_FIT), ctx->d_rows, ctx->d_nrows, B, rows_stream, rec_or_rows(ctx, &cr), fused ? &pr : nullptr,
+	                                                                         par && !tables && !pose_only ? joins_from(ctx, 0) : nullptr); }      // side stream 0's last launch before the join carries the join's event
 	if (tables) { ht_prof_scope ps(ctx, "solve_prep", s, true); solve_prep(ctx, 0, m, false, nullptr, B, rows_stream); }
 	if (coll) { ht_prof_scope ps(ctx, "contacts", s, true); launch_contacts(ctx, 0, nullptr, B, s, par, pass_slot(pass)); }
 	mark("  pass: contacts done", s);
@@ -230,11 +261,15 @@ static void main_pass(ht_ctx *ctx, int B, hipStream_t s, float *poses_out = null
 	mark("  pass: rows joined", s);
 	ht_prof_scope ps(ctx, "solve", s);
 	solve_opts so; so.hist_slot = pass_slot(pass); so.tables = tables || pose_only; so.poses_out = poses_out; so.out_npts = npts;
+	so.fork_next = pass_follows && par && ctx->planes_valid;      // the next pass starts with its fork (its planes are the update's: no launch ahead of the fork)
 	solve_step(ctx, 0, m, B, s, so);
 }
 // Behind the join of the side stream, so nothing of the step waits for it: the running counts of reset frames go to the host (ht_host.hpp: d_nreset).  The
 // update's stream picks the copy up again at its very end (reset_tail_join: long finished by then) -- every stream of an update has to come back to the
-// caller's, or the update could not be captured into a HIP graph.
+// caller's, or the update could not be captured into a HIP graph.  The consumer of that last join is whatever the caller enqueues next; the host reads h_nreset without ever
+// waiting, and what makes the two words visible to it is the copy itself (a copy engine or a blit kernel with its own system-scope release), not the event behind it.
+// The same holds for a pose output in pinned host memory (zero copy): the update's last solve writes it on the caller's stream, and the caller's own event or
+// synchronisation, which the library does not make, releases it to the host.
 static void reset_tail(ht_ctx *ctx) { (void)hipMemcpyAsync(const_cast<unsigned *>(ctx->h_nreset), ctx->d_nreset, 2 * sizeof(unsigned), hipMemcpyDeviceToHost, ctx->side[0]); ctx->tail_pending = true; }
 static void reset_tail_join(ht_ctx *ctx, hipStream_t s) { if (ctx->tail_pending) { join(ctx, s, 1); ctx->tail_pending = false; } }
 static void reset_path(ht_ctx *ctx, bool listed, int n_unibody, int B, hipStream_t s, hipStream_t prof_stream, bool many_frames = false)      // listed: the frames of d_flist; otherwise all
@@ -397,13 +432,14 @@ static void resets_lap(ht_ctx *ctx, int B, hipStream_t s)      // p.steps >= 2
 	reset_path(ctx, true, ctx->par.steps_unibody, B, s, s, ctx->many_reset); mark("reset kernel done", s);
 	multistep(ctx, B, steps_on(u).steps(0, 1).frames(batch_frames).in_order().unprofiled().shares_gpu()); mark("batch step 0 done", u);
 	multistep(ctx, B, steps_on(s).steps(0, 1).frames(reset_frames).in_order().rows_only()); mark("reset frames contacts done", s);
-	(void)hipEventRecord(ctx->ev_lap, s); (void)hipStreamWaitEvent(u, ctx->ev_lap, 0);
+	(void)hipEventRecord(ctx->ev_lap, s); (void)hipStreamWaitEvent(u, ctx->ev_lap, 0);      // (consumer: the batch's step-1 kernels on the side stream; a record, it follows a contact launch)
 	multistep(ctx, B, steps_on(s).steps(0, 1).frames(reset_frames).in_order().solve_only()); mark("reset frames step 0 done", s);
 	multistep(ctx, B, steps_on(u).steps(1, 2).frames(batch_frames).in_order().unprofiled().rows_only()); mark("batch step 1 rows done", u);      // in order on the side stream: there is time (0.76 against 0.82 ms), and a fork out of a forked stream does not survive a HIP graph capture
 	multistep(ctx, B, steps_on(s).steps(1, 2).frames(reset_frames).rows_beside(1).rows_only()); mark("reset frames step 1 rows done", s);      // the reset frames' rows for step 1, beside the batch's
 	join(ctx, s, 1); mark("side branch back", s); reset_tail(ctx);      // the batch's steps so far, and ahead of them the tables and the planes of the update's head
-	multistep(ctx, B, steps_on(s).steps(1, 2).all_frames().solve_only()); mark("step 1 done", s);
-	multistep(ctx, B, steps_on(s).steps(2).all_frames().rows_beside(0)); mark("MultiStepSim done", s);
+	const steps_on rest = steps_on(s).steps(2).all_frames().rows_beside(0);
+	multistep(ctx, B, steps_on(s).steps(1, 2).all_frames().solve_only().then_forks(ctx->par.steps > 2 && sides_of_step(ctx, rest, 2).par)); mark("step 1 done", s);
+	multistep(ctx, B, rest); mark("MultiStepSim done", s);
 }
 // The overlapped update behind the net: the side branch comes back, then the reset frames and MultiStepSim in one of the organisations above
 static void update_resets(ht_ctx *ctx, const update_call &u)
@@ -442,7 +478,7 @@ static void update_passes(ht_ctx *ctx, const update_call &u)      // the main-th
 {
 	const ht_params &p = ctx->par;
 	const int passes = p.angles_only ? 0 : p.mainthreadpasses;
-	for (int i = 0; i < passes; i++) { main_pass(ctx, u.B, u.s, i + 1 == passes ? u.d_poses_out : nullptr, i); mark("pass done", u.s); }
+	for (int i = 0; i < passes; i++) { main_pass(ctx, u.B, u.s, i + 1 == passes ? u.d_poses_out : nullptr, i, i + 1 < passes); mark("pass done", u.s); }
 	if (passes < 1) ht_launch_output(ctx->model, ctx->d_state[0], p.subsample_voxel ? ctx->d_nptsv : ctx->d_npts, ctx->d_initializing, p.min_point_num, u.d_poses_out, u.B, u.s);
 }
 static int run_update_(ht_ctx *ctx, update_call &u)
@@ -450,6 +486,13 @@ static int run_update_(ht_ctx *ctx, update_call &u)
 	const ht_params &p = ctx->par; hipStream_t s = u.s;
 	u.net = ht_net_of(ctx, u.fs.side);      // (resolve_frames has checked the side)
 	if (u.mode != UPD_PASSES && !u.net->have) { ctx->err = u.net->missing; return HT_ERR_STATE; }      // (no net in the caller's part of the overlapped update)
+	{      // the launches of this update may carry its edges' events unless the caller is capturing its stream: every edge of a captured update is a record and a wait.
+		// Nor under the profile (ht_profile_enable): its timing events bracket the very solves that would carry a fork, and a launch with a completion event between two
+		// timing records costs more than the record it saves (bench.py --full, 1024 frames: 4.53 against 4.41 ms per step with a record per edge; the parent 4.46)
+		hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+		const bool capturing = hipStreamIsCapturing(s, &cap) != hipSuccess || cap != hipStreamCaptureStatusNone;
+		ctx->edges_on_launch = HT_EDGE_ON_LAUNCH && ctx->edge_mode == 0 && !capturing && !ctx->profile; ctx->fork_carried = nullptr; ctx->join_carried = 0;
+	}
 	{ const int r = update_inputs(ctx, u); if (r) return r; }
 	if (u.mode == UPD_PASSES) { update_planes(ctx, u, s); update_passes(ctx, u); return HT_OK; }
 	static const bool no_overlap = ht_tuning_env("HT_NO_OVERLAP");      // timing experiments (-DHT_TUNING builds only)
@@ -479,6 +522,7 @@ static int run_update(ht_ctx *ctx, const uint16_t *d_depth, const float *d_cams,
 	const int r = run_update_(ctx, u);
 	ctx->model.frame_order = nullptr; ctx->model.pts_bound = 0;      // the per-call hints of update_inputs (launch order of the block-per-frame kernels, largest cloud) belong to the update that set them
 	ctx->planes_valid = false;                                       // and so do the boundary planes of its cloud
+	ctx->edges_on_launch = false; ctx->fork_carried = nullptr; ctx->join_carried = 0;      // and the launch form of its edges (a fit step outside an update records its events)
 	return r;
 }
 static int update_dev_end(ht_ctx *ctx, int r) { if (r) return r; HIPCHK(ctx, hipGetLastError()); return HT_OK; }      // what a *_dev update ends with: nothing is waited for, a launch that failed is reported
@@ -994,7 +1038,7 @@ extern "C" int ht_job_start(ht_ctx *job, ht_ctx *main, const uint16_t *depth, co
 	hipStream_t s = job->stream;
 	const int nb = job->model.nb;
 	const size_t npx = (size_t)w * h, in_bytes = (size_t)B * npx * sizeof(uint16_t), cam_bytes = (size_t)B * HT_CAM * sizeof(float);
-	if (!job->ev_job) HIPCHK(job, hipEventCreateWithFlags(&job->ev_job, hipEventDisableTiming));
+	if (!job->ev_job) HIPCHK(job, hipEventCreateWithFlags(&job->ev_job, hipEventDisableTiming));      // (the host queries and waits for this one: the ordinary fence, not ht_edge_event)
 	if (job->h_job_cap < in_bytes + cam_bytes) { if (job->h_job_in) (void)hipHostFree(job->h_job_in); job->h_job_in = nullptr; HIPCHK(job, hipHostMalloc(&job->h_job_in, in_bytes + cam_bytes, hipHostMallocDefault)); job->h_job_cap = in_bytes + cam_bytes; }
 	HIPCHK(job, hipStreamSynchronize(main->stream));      // the caller's context is between two of its (synchronous) calls: its handmodel is final
 	memcpy(job->h_job_in, depth, in_bytes); memcpy((char *)job->h_job_in + in_bytes, cams, cam_bytes);      // the caller's image need not outlive this call (the reference moves it into the task)
@@ -1007,7 +1051,7 @@ extern "C" int ht_job_start(ht_ctx *job, ht_ctx *main, const uint16_t *depth, co
 	HIPCHK(job, hipMemcpyAsync(job->d_initializing, main->d_initializing, (size_t)B * sizeof(int), hipMemcpyDeviceToDevice, s));
 	// othermodel's seed is taken BEFORE the caller goes on (the reference copies synchronously in front of std::async, :757): the caller's stream waits for these copies, so its
 	// next passes cannot overwrite handmodel under them
-	if (!job->ev_seed) HIPCHK(job, hipEventCreateWithFlags(&job->ev_seed, hipEventDisableTiming));
+	if (!job->ev_seed) HIPCHK(job, ht_edge_event(job, &job->ev_seed));      // (consumer: the kernels of the caller's next passes on main's stream, same device)
 	HIPCHK(job, hipEventRecord(job->ev_seed, s));
 	HIPCHK(job, hipStreamWaitEvent(main->stream, job->ev_seed, 0));
 	int r = run_update(job, d_in, d_cin, nullptr, B, job->d_poses_out, nullptr, s, fs, UPD_CNN_MODEL);
@@ -1196,6 +1240,21 @@ extern "C" int ht_debug_solver_build(ht_ctx *ctx, int which)
 		if ((r = dev_alloc(ctx, &ctx->d_exact_ang, (size_t)ctx->B * 256 * 8)) || (r = dev_alloc(ctx, &ctx->d_exact_lin, (size_t)ctx->B * HT_EX_LIN * HT_ROW))) return r;
 	}
 	ctx->solver_build = which;
+	return HT_OK;
+}
+// Tests only: how the edges between an update's streams are made.  0 = the product's choice (ht_host.hpp: ht_edge_event; fork / join1 above); 1 = as up to round 29: events
+// with hipEventDisableTiming alone, every edge a hipEventRecord and a hipStreamWaitEvent.  Waits for the context's work and makes its events anew, so that a test can run
+// both paths in one process; the results must be the same bits (tests/test_gpu_stream_edges.py).
+extern "C" int ht_debug_stream_edges(ht_ctx *ctx, int mode)
+{
+	if (!ctx || mode < 0 || mode > 1) return HT_ERR_ARG;
+	ht_device_guard dev_guard_(ctx->device);
+	HIPCHK(ctx, ht_sync_all(ctx));
+	for (int i = 0; i < 2; i++) HIPCHK(ctx, hipStreamSynchronize(ctx->side[i]));
+	ctx->edge_mode = mode;
+	hipEvent_t *ev[] = { &ctx->ev_fork, &ctx->ev_join[0], &ctx->ev_join[1], &ctx->ev_lap };
+	for (hipEvent_t *e : ev) { if (*e) (void)hipEventDestroy(*e); *e = nullptr; HIPCHK(ctx, ht_edge_event(ctx, e)); }
+	if (ctx->ev_seed && !ctx->job_pending) { (void)hipEventDestroy(ctx->ev_seed); ctx->ev_seed = nullptr; }      // made again by the next ht_job_start
 	return HT_OK;
 }
 // Tests only: which organisation the latest update launched the full-reset branch in (0 = few frames: one k_reset block per CU, a contact block per reset frame;

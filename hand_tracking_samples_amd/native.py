@@ -44,7 +44,7 @@ SYMBOLS = (
     "ht_model_raster_scene", "ht_raster_scene_depth", "ht_raster_scene_depth_dev",
     "ht_tracker_reset", "ht_get_state", "ht_set_state", "ht_get_tracker_flags", "ht_set_tracker_flags", "ht_update_sync", "ht_update_dev", "ht_update_frames_sync", "ht_update_frames_dev", "ht_update_direct_sync", "ht_update_direct_dev", "ht_update_cnn_model_sync", "ht_get_cnn_results", "ht_get_cnn_layers", "ht_get_cnn_layers_sized", "ht_frames_overflow", "ht_reserve_points", "ht_point_capacity", "ht_capacity_events", "ht_segment_vr", "ht_segment_vr_dev", "ht_segment_vr_supported", "ht_segment_vr_sized", "ht_segment_vr_sized_dev", "ht_update_frames_sized_sync", "ht_update_frames_sized_dev", "ht_render_depth", "ht_render_depth_dev", "ht_slowfit", "ht_set_points", "ht_fit_rows", "ht_physics_update",
     "ht_stage_prepare", "ht_stage_decode", "ht_stage_fit_error", "ht_stage_cloud_rows", "ht_stage_contacts", "ht_stage_fit", "ht_debug_contact_plan",
-    "ht_stage_multistep", "ht_stage_multistep_range", "ht_stage_scratch_unibody", "ht_stage_chamber", "ht_profile_enable", "ht_profile_read", "ht_debug_solve_stats", "ht_debug_contact_stats", "ht_debug_solver_build", "ht_debug_reset_flags", "ht_debug_reset_organisation", "ht_update_passes_sync", "ht_job_start", "ht_job_poll", "ht_job_wait", "ht_job_collect", "ht_debug_contact_kernel", "ht_debug_contact_order", "ht_debug_rank_desc", "ht_contact_capacity", "ht_debug_solve_tables", "ht_debug_solve_tables_header", "ht_debug_train_buffers",
+    "ht_stage_multistep", "ht_stage_multistep_range", "ht_stage_scratch_unibody", "ht_stage_chamber", "ht_profile_enable", "ht_profile_read", "ht_debug_solve_stats", "ht_debug_contact_stats", "ht_debug_solver_build", "ht_debug_reset_flags", "ht_debug_reset_organisation", "ht_update_passes_sync", "ht_job_start", "ht_job_poll", "ht_job_wait", "ht_job_collect", "ht_debug_contact_kernel", "ht_debug_stream_edges", "ht_debug_contact_order", "ht_debug_rank_desc", "ht_contact_capacity", "ht_debug_solve_tables", "ht_debug_solve_tables_header", "ht_debug_train_buffers",
     "ht_sensor_out_dims", "ht_sensor_filter", "ht_sensor_filter_dev", "ht_sensor_background", "ht_sensor_background_dev",
     "ht_sensor_noise_default", "ht_sensor_simulate", "ht_sensor_simulate_dev",
     "ht_model_joint_limits", "ht_joint_coords", "ht_joint_coords_dev", "ht_joint_pose", "ht_joint_pose_dev", "ht_sample_poses", "ht_sample_poses_dev",
@@ -286,6 +286,7 @@ def load(build_if_missing=True):
     L.ht_debug_reset_organisation.argtypes = [vp, ip]
     L.ht_debug_reset_flags.argtypes = [vp, ip, C.c_int]
     L.ht_debug_contact_kernel.argtypes = [vp, C.c_int]
+    L.ht_debug_stream_edges.argtypes = [vp, C.c_int]
     L.ht_debug_contact_plan.argtypes = [vp, C.c_int, ip, ip]
     L.ht_debug_contact_order.argtypes = [vp, ip, C.c_int, C.c_int, C.c_int, ip]
     L.ht_debug_rank_desc.argtypes = [vp, ip, C.c_int, ip]
@@ -871,6 +872,11 @@ class Context:
     def debug_contact_kernel(self, which):
         """Test aid: pin the contact kernel's organisation (0 auto, 1 cooperative, 2 lane-per-pair).  Same contacts either way."""
         self._chk(self.L.ht_debug_contact_kernel(self.h, int(which)))
+
+    def debug_stream_edges(self, mode):
+        """Test aid: how the edges between an update's streams are made (0 the product's choice, 1 a record and a wait per edge on the events of round 29 and before).
+        Waits for the context's work.  Same results either way."""
+        self._chk(self.L.ht_debug_stream_edges(self.h, int(mode)))
 
     def debug_contact_plan(self, B):
         """Test aid: (frames per block of the cooperative kernel, waves per frame of the lane-per-pair kernel) of a contact launch on B frames under the current pin; the

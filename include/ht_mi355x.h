@@ -1151,6 +1151,9 @@ int ht_debug_reset_organisation(ht_ctx *ctx, int *many);
 /* Test aid: pins the organisation of the contact kernel (0 = chosen per launch: the cooperative kernel whenever the model fits its LDS; 1 cooperative,
  * 2 one lane group per body pair).  Same contacts in the same order either way. */
 int ht_debug_contact_kernel(ht_ctx *ctx, int which);
+/* Test aid: how the edges between an update's streams are made (0 = the product's events and launch forms; 1 = a record and a wait per edge on events with
+ * hipEventDisableTiming alone, as up to round 29).  Waits for the context's work.  Same results either way, bit for bit. */
+int ht_debug_stream_edges(ht_ctx *ctx, int mode);
 /* Test aid: the kernel a contact launch on B frames takes under that pin: *coop_frames = frames per block of the cooperative kernel (0: the lane-group kernel runs, also
  * under pin 1 when a frame of the model does not fit the cooperative kernel's LDS), *lane_waves = waves per frame of the lane-group kernel (0: the cooperative kernel
  * runs; 2 for models of more than 200 body pairs). */
