@@ -1207,6 +1207,29 @@ extern "C" int ht_stage_multistep_range(ht_ctx *ctx, const float *analysis, int 
 	return stage_on_analysis(ctx, range_ok ? analysis : nullptr, B, [&](hipStream_t s) { multistep(ctx, B, steps_on(s).steps(from_step, to_step).all_frames()); });
 }
 extern "C" int ht_stage_scratch_unibody(ht_ctx *ctx, const float *analysis, int B, int n_unibody) { return stage_on_analysis(ctx, analysis, B, [&](hipStream_t s) { reset_path(ctx, false, n_unibody, B, s, s); }); }
+// Tests only: the same for the frames list[0 .. nlist) alone, through the flagged-frame list as an update launches it (many_frames 0: k_reset<1>, one block per CU;
+// 1: k_reset<2>) -- the listed launch without a whole update around it.  The other frames keep their state and their row counts.  Refused before anything is
+// uploaded: a null pointer, nlist outside [0, B], an index outside [0, B), an index given twice.  Leaves the list empty, as an update's head does.
+extern "C" int ht_stage_scratch_unibody_listed(ht_ctx *ctx, const float *analysis, int B, int n_unibody, const int *list, int nlist, int many_frames)
+{
+	CHECK_READY(ctx); CHECK_MODEL(ctx); CHECK_BATCH(ctx, B);
+	if (!analysis || !list || nlist < 0 || nlist > B) return HT_ERR_ARG;
+	std::vector<char> seen((size_t)B, 0);
+	for (int i = 0; i < nlist; i++)
+	{
+		if (list[i] < 0 || list[i] >= B || seen[list[i]]) return HT_ERR_ARG;
+		seen[list[i]] = 1;
+	}
+	const int organisation = ctx->last_reset_many;      // what the latest update chose stays on record (ht_debug_reset_organisation)
+	const int r = stage_on_analysis(ctx, analysis, B, [&](hipStream_t s) {
+		if (nlist > 0) (void)hipMemcpyAsync(ctx->d_flist, list, (size_t)nlist * sizeof(int), hipMemcpyHostToDevice, s);
+		(void)hipMemcpyAsync(ctx->d_nflist, &nlist, sizeof(int), hipMemcpyHostToDevice, s);
+		reset_path(ctx, true, n_unibody, B, s, s, many_frames != 0);
+		(void)hipMemsetAsync(ctx->d_nflist, 0, sizeof(int), s);
+	});
+	ctx->last_reset_many = organisation;
+	return r;
+}
 
 // Timing experiments only (HT_DEBUG_SKIP & 2048): per-frame k_solve statistics accumulated in the last scratch record of each frame:
 // launches, cycles in chains / two-body linear / angular, cycles in all sweeps, steps (linear, angular), longest chain, row counts.
@@ -1272,6 +1295,15 @@ extern "C" int ht_debug_reset_flags(ht_ctx *ctx, int *flags, int n)
 	ht_device_guard dev_guard_(ctx->device);
 	HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
 	HIPCHK(ctx, hipMemcpy(flags, ctx->d_flags, (size_t)n * sizeof(int), hipMemcpyDeviceToHost));
+	return HT_OK;
+}
+// Tests only: the cloud-row counts of slots [0, B) as the latest launch that wrote them left them (the cloud-row kernels, k_reset)
+extern "C" int ht_debug_row_counts(ht_ctx *ctx, int B, int *nrows)
+{
+	CHECK_READY(ctx); CHECK_BATCH(ctx, B);
+	if (!nrows) return HT_ERR_ARG;
+	HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+	HIPCHK(ctx, hipMemcpy(nrows, ctx->d_nrows, (size_t)B * sizeof(int), hipMemcpyDeviceToHost));
 	return HT_OK;
 }
 // Tests only: pins the organisation of the contact kernel (0 = the launcher's choice; 1 cooperative, 2 lane-per-pair).  Same arithmetic, same contacts in the same order.

@@ -44,7 +44,7 @@ SYMBOLS = (
     "ht_model_raster_scene", "ht_raster_scene_depth", "ht_raster_scene_depth_dev",
     "ht_tracker_reset", "ht_get_state", "ht_set_state", "ht_get_tracker_flags", "ht_set_tracker_flags", "ht_update_sync", "ht_update_dev", "ht_update_frames_sync", "ht_update_frames_dev", "ht_update_direct_sync", "ht_update_direct_dev", "ht_update_cnn_model_sync", "ht_get_cnn_results", "ht_get_cnn_layers", "ht_get_cnn_layers_sized", "ht_frames_overflow", "ht_reserve_points", "ht_point_capacity", "ht_capacity_events", "ht_segment_vr", "ht_segment_vr_dev", "ht_segment_vr_supported", "ht_segment_vr_sized", "ht_segment_vr_sized_dev", "ht_update_frames_sized_sync", "ht_update_frames_sized_dev", "ht_render_depth", "ht_render_depth_dev", "ht_slowfit", "ht_set_points", "ht_fit_rows", "ht_physics_update",
     "ht_stage_prepare", "ht_stage_decode", "ht_stage_fit_error", "ht_stage_cloud_rows", "ht_stage_contacts", "ht_stage_fit", "ht_debug_contact_plan",
-    "ht_stage_multistep", "ht_stage_multistep_range", "ht_stage_scratch_unibody", "ht_stage_chamber", "ht_profile_enable", "ht_profile_read", "ht_debug_solve_stats", "ht_debug_contact_stats", "ht_debug_solver_build", "ht_debug_reset_flags", "ht_debug_reset_organisation", "ht_update_passes_sync", "ht_job_start", "ht_job_poll", "ht_job_wait", "ht_job_collect", "ht_debug_contact_kernel", "ht_debug_stream_edges", "ht_debug_contact_order", "ht_debug_rank_desc", "ht_contact_capacity", "ht_debug_solve_tables", "ht_debug_solve_tables_header", "ht_debug_train_buffers",
+    "ht_stage_multistep", "ht_stage_multistep_range", "ht_stage_scratch_unibody", "ht_stage_scratch_unibody_listed", "ht_debug_row_counts", "ht_stage_chamber", "ht_profile_enable", "ht_profile_read", "ht_debug_solve_stats", "ht_debug_contact_stats", "ht_debug_solver_build", "ht_debug_reset_flags", "ht_debug_reset_organisation", "ht_update_passes_sync", "ht_job_start", "ht_job_poll", "ht_job_wait", "ht_job_collect", "ht_debug_contact_kernel", "ht_debug_stream_edges", "ht_debug_contact_order", "ht_debug_rank_desc", "ht_contact_capacity", "ht_debug_solve_tables", "ht_debug_solve_tables_header", "ht_debug_train_buffers",
     "ht_sensor_out_dims", "ht_sensor_filter", "ht_sensor_filter_dev", "ht_sensor_background", "ht_sensor_background_dev",
     "ht_sensor_noise_default", "ht_sensor_simulate", "ht_sensor_simulate_dev",
     "ht_model_joint_limits", "ht_joint_coords", "ht_joint_coords_dev", "ht_joint_pose", "ht_joint_pose_dev", "ht_sample_poses", "ht_sample_poses_dev",
@@ -214,6 +214,8 @@ def load(build_if_missing=True):
     L.ht_stage_multistep.argtypes = [vp, fp, C.c_int]
     L.ht_stage_multistep_range.argtypes = [vp, fp, C.c_int, C.c_int, C.c_int]
     L.ht_stage_scratch_unibody.argtypes = [vp, fp, C.c_int, C.c_int]
+    L.ht_debug_row_counts.argtypes = [vp, C.c_int, C.POINTER(C.c_int)]
+    L.ht_stage_scratch_unibody_listed.argtypes = [vp, fp, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int, C.c_int]
     L.ht_profile_enable.argtypes = [vp, C.c_int]
     L.ht_scale.argtypes = [vp, C.c_float]
     L.ht_cnn_train.argtypes = [vp, fp, fp, C.c_int, C.c_float, fp]
@@ -812,6 +814,19 @@ class Context:
     def stage_scratch_unibody(self, analysis, B, n_unibody):
         analysis = _c(analysis, np.float32).reshape(B, ANALYSIS)
         self._chk(self.L.ht_stage_scratch_unibody(self.h, _f(analysis), B, n_unibody))
+
+    def row_counts(self, B):
+        """Test aid: the cloud-row counts of slots [0, B) as the latest launch that wrote them left them."""
+        n = np.empty(B, np.int32)
+        self._chk(self.L.ht_debug_row_counts(self.h, B, _i(n)))
+        return n
+
+    def stage_scratch_unibody_listed(self, analysis, B, n_unibody, frames, many_frames=False, nlist=None):
+        """Test aid: the same for the listed frames alone, through the flagged-frame list (many_frames False: the few-frames build of k_reset).  nlist: the length handed
+        to the library where it is not len(frames)."""
+        analysis = _c(analysis, np.float32).reshape(B, ANALYSIS)
+        frames = _c(frames, np.int32).reshape(-1)
+        self._chk(self.L.ht_stage_scratch_unibody_listed(self.h, _f(analysis), B, n_unibody, _i(frames), len(frames) if nlist is None else int(nlist), int(bool(many_frames))))
 
     # -- profiling
     def profile_enable(self, level=1):

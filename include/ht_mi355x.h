@@ -1148,6 +1148,11 @@ int ht_debug_reset_flags(ht_ctx *ctx, int *flags, int n);      /* test aid: flag
  * (physics.h:251-265, 289-307) in the reference's row order, no fused multiply-adds (update entry points only; tests/test_gpu_exact_solver.py).
  * ht_debug_reset_organisation: how the latest update launched the full-reset branch (0 few frames, 1 many frames, -1 none yet). */
 int ht_debug_reset_organisation(ht_ctx *ctx, int *many);
+/* Test aid: ht_stage_scratch_unibody for the frames list[0 .. nlist) alone, launched through the flagged-frame list as an update launches its full-reset branch
+ * (many_frames 0: one block per CU, the few-frames build; 1: two blocks per CU).  The frames not listed keep their state and their row counts.  HT_ERR_ARG, with nothing
+ * uploaded, for a null pointer, nlist outside [0, B], an index outside [0, B) or an index listed twice. */
+int ht_debug_row_counts(ht_ctx *ctx, int B, int *nrows);      /* test aid: the cloud-row counts of slots [0, B) as the latest launch that wrote them left them */
+int ht_stage_scratch_unibody_listed(ht_ctx *ctx, const float *analysis, int B, int n_unibody, const int *list, int nlist, int many_frames);
 /* Test aid: pins the organisation of the contact kernel (0 = chosen per launch: the cooperative kernel whenever the model fits its LDS; 1 cooperative,
  * 2 one lane group per body pair).  Same contacts in the same order either way. */
 int ht_debug_contact_kernel(ht_ctx *ctx, int which);

@@ -618,7 +618,7 @@ void ho_pose_from_scratch(ho_tracker *t, ho_model *m, const f3 *pts, int n, cons
 	fix_positions(m);
 }
 /* UnibodyFit handtrack.h:451-470 */
-void ho_unibody_fit(ho_tracker *t, ho_model *m, const f3 *pts, int n, f3 camera_position)
+static void unibody_fit(ho_tracker *t, ho_model *m, const f3 *pts, int n, f3 camera_position, float *proxy13)
 {
 	ho_linear *lin = malloc(sizeof(ho_linear) * MAXLIN);
 	int nl = cloud_constraints(m, pts, n, 4, camera_position, lin);
@@ -637,11 +637,20 @@ void ho_unibody_fit(ho_tracker *t, ho_model *m, const f3 *pts, int n, f3 camera_
 	ho_sanity_check(m);
 	ho_body *UB[1] = { &ub };
 	ho_physics_update(t, UB, 1, NULL, lin, nl, MAXLIN, NULL, 0);
+	if (proxy13)
+	{
+		const float s[13] = { ub.position.x, ub.position.y, ub.position.z, ub.orientation.x, ub.orientation.y, ub.orientation.z, ub.orientation.w,
+		                      ub.linmom.x, ub.linmom.y, ub.linmom.z, ub.angmom.x, ub.angmom.y, ub.angmom.z };
+		memcpy(proxy13, s, sizeof s);
+	}
 	pose_t dp = pose_mul(POSE(ub.position, ub.orientation), pose_inverse(POSE(m->bodies[1].position, m->bodies[1].orientation)));
 	for (int b = 0; b < m->nb; b++) { pose_t np = pose_mul(dp, POSE(m->bodies[b].position, m->bodies[b].orientation)); m->bodies[b].position = np.position; m->bodies[b].orientation = np.orientation; }
 	ho_sanity_check(m);
 	free(lin);
 }
+void ho_unibody_fit(ho_tracker *t, ho_model *m, const f3 *pts, int n, f3 camera_position) { unibody_fit(t, m, pts, n, camera_position, NULL); }
+/* tests: the same, and the proxy body as PhysicsUpdate left it (position, orientation, momenta: the momenta are where the post sweeps show, UnibodyFit drops them) */
+void ho_unibody_fit_proxy(ho_tracker *t, ho_model *m, const f3 *pts, int n, f3 camera_position, float *proxy13) { unibody_fit(t, m, pts, n, camera_position, proxy13); }
 
 /* ------------------------------------------------------------------------------------------------ tracker */
 /* update_cnn_model(_threadsafe) handtrack.h:693-741 for a 64x64 tile (HandSegmentVR is the identity, :283-284) */

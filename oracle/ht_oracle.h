@@ -132,6 +132,7 @@ void ho_fit_pointcloud(ho_tracker *t, ho_model *m, const f3 *pts, int n, const h
 void ho_multistep(ho_tracker *t, ho_model *m, const ho_analysis *an, const f3 *vpts, int n, pose_t camera_pose);
 void ho_pose_from_scratch(ho_tracker *t, ho_model *m, const f3 *pts, int n, const ho_analysis *an, pose_t camera_pose);
 void ho_unibody_fit(ho_tracker *t, ho_model *m, const f3 *pts, int n, f3 camera_position);
+void ho_unibody_fit_proxy(ho_tracker *t, ho_model *m, const f3 *pts, int n, f3 camera_position, float *proxy13);   /* tests: and the proxy body after its PhysicsUpdate [13] */
 
 /* GJK (gjk.h) on two posed bodies of a model */
 typedef struct ho_gjk_contact { f3 normal, p0w, p1w, impact; float separation, dist; int type; } ho_gjk_contact;

@@ -117,6 +117,7 @@ def lib():
         L.ho_multistep.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(Analysis), C.POINTER(F3), C.c_int, Pose]
         L.ho_pose_from_scratch.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(F3), C.c_int, C.POINTER(Analysis), Pose]
         L.ho_unibody_fit.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(F3), C.c_int, F3]
+        L.ho_unibody_fit_proxy.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(F3), C.c_int, F3, fp]
         L.ho_update_cnn_model.argtypes = [C.c_void_p, C.POINTER(C.c_uint16), C.POINTER(Camera), fp]; L.ho_update_cnn_model.restype = C.c_int
         L.ho_update.argtypes = [C.c_void_p, C.POINTER(C.c_uint16), C.POINTER(Camera), fp]
         L.ho_camera_from12.argtypes = [fp, C.c_int, C.c_int, C.POINTER(Camera)]

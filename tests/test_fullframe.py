@@ -145,7 +145,9 @@ def test_gpu_config5_full_size_properties(weights):
 def test_gpu_full_reset_on_clouds_over_the_default_capacity(weights):
     """The full-reset path (PoseFromScratch + three UnibodyFit solves, handtrack.h:705-712) on the close-hand frames: 7723 / 10628 points give
     1931 / 2657 single-body rows per UnibodyFit solve, more than the proxy body's LDS records hold (896), so k_reset streams them from HBM.
-    full_reset_on_error = 0 sends every frame down that path; the expected result is the pinned oracle's on the same setting."""
+    full_reset_on_error = 0 sends every frame down that path; the expected result is the pinned oracle's on the same setting.
+    Of k_reset's three solve organisations this reaches the last alone (rows from HBM, beyond 896), through the listed launch of an update with few reset frames
+    (k_reset<1>); the other two, the seams and the listed launch on its own are held by tests/test_gpu_reset_fuzz.py."""
     from hand_tracking_samples_amd import native
     G, (_, model, nb) = GOLD["qvga_close"], CASES["qvga_close"]
     nf = len(G["rows"])
@@ -183,7 +185,9 @@ def test_gpu_full_reset_on_clouds_over_the_default_capacity(weights):
 @pytest.mark.gpu
 def test_gpu_reset_stages_bit_exact_over_the_default_capacity(weights):
     """k_reset (PoseFromScratch, UnibodyFit) on a 10628-point cloud (2657 rows per UnibodyFit solve: the proxy body's records stream from HBM instead of LDS),
-    stage by stage against the oracle on the same inputs: same analysis, same points, same start pose."""
+    stage by stage against the oracle on the same inputs: same analysis, same points, same start pose.  One frame, one organisation of the solve (rows from HBM, beyond
+    896 rows), the unlisted launch (k_reset<2>), a cloud beyond the default capacity -- the one size tests/test_gpu_reset_fuzz.py, which covers the three organisations
+    and their seams at the default capacity, leaves to this test."""
     from hand_tracking_samples_amd import native
     G, (_, model, nb) = GOLD["qvga_close"], CASES["qvga_close"]
     w, h = (int(x) for x in G["dims"])

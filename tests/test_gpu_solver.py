@@ -187,6 +187,9 @@ def test_multistep(ctx, golden, steps):
 
 
 def test_reset_path(ctx, golden):
+    """PoseFromScratch and 0 to 3 rounds of UnibodyFit on the first three golden tiles: 1685, 944 and 1368 points, so 422, 236 and 342 rows per single-body solve -- all
+    three on k_reset's sixteen-rows-at-a-time organisation (up to 448 rows), none on a multiple of sixteen, through the unlisted launch (k_reset<2>).  The row-by-row
+    organisations (449 to 896 rows from LDS, more from HBM), the seams between the three and the listed launch are held by tests/test_gpu_reset_fuzz.py."""
     depth, cams, start = _inputs(golden)
     an = _analysis(golden)
     for k in range(4):
